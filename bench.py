@@ -15,15 +15,20 @@ ceil(16384 / N) queries (strong scaling, the way BASELINE configs 4 and 5 are wr
 rank a full 16384-query batch of its own instead.
 
     python bench.py [--gpus N --steps K --warmup W] [--config cfg5|cfg3|cfg4|cfg2] [--scaling strong|weak]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Beside the contract's keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K pipelined steps and reports them (`value`,
+`ms_per_step`).  `--dump-outputs DIR` then writes the last timed step's results as DIR/<name>.npy (see dump_outputs).
+Everything else is measured and checked only with `--full`, where the line also carries
   roofline       the scoring kernel alone, descriptors resident: algorithmic bytes per launch / HIP-event duration vs 8 TB/s
   kernel_only    the device-only rate of the same batch (what round 1 reported as `value`)
   hbm_resident   (N = 1) the same query law over a 20 x 1M-doc index — 1.1 GB of postings, beyond the 256 MiB Infinity
                  Cache — with its own roofline numbers
   cpu_baseline   (N = 1) the REAL reference engine on one host core of this box (+ cpu_baselines: the as-shipped
                  no-flag build, and the oracle port on all cores as the generous upper bound)
+  in_place, impact_stream, pruned   (N = 1) the same batch with sharing off / over the impact streams / with block-max pruning
+and every leg's results are compared with an unpipelined run of the same batch.
 """
 import argparse
 import json
@@ -39,6 +44,7 @@ PKG = os.path.join(ROOT, "nextsearch-api_amd")
 sys.path.insert(0, PKG)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is what streaming kernels reach
+RAMP_S = 0.5            # seconds of untimed launches that bring the device clocks up before the first timed step
 
 WORKLOAD_TEXT = {
     "cfg5": "BASELINE config 5 query law: 1-8 terms (1+Poisson(2)), 30% hot ranks [1,32] / 70% log-uniform tail, OR, k=10",
@@ -75,7 +81,15 @@ def parse_args():
     ap.add_argument("--hbm-queries", type=int, default=2048)
     ap.add_argument("--hbm-only", action="store_true", help="profiling runs: ONLY the hbm_resident leg (prints its object as the JSON line)")
     ap.add_argument("--kernel-only", action="store_true", help="profiling runs: only the kernel leg (descriptors resident), no pipelined loop, no extra legs")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel leg (roofline, kernel_only), the extra legs, the CPU baselines and the result checks; "
+                         "a plain run times the pipelined steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's results to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_info():
@@ -103,6 +117,33 @@ def lib_info():
         except OSError:
             out[name] = None
     return out
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs stays below 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, hits, nhits, found):
+    """Writes what a caller of the timed path receives for one batch (hits [Q, K], nhits [Q], found [Q]) as
+    out_dir/<name>.npy: hits_score in float32 (the fp32 scores as returned), hits_seg, hits_doc, nhits and found in float64
+    (exact).  Hit slots past nhits[q] hold no result and are written as 0.  A batch beyond DUMP_LIMIT_BYTES is written as
+    a fixed, seeded sample of its rows, in row order; rows.npy then names them."""
+    import numpy as np
+
+    Q, K = hits.shape
+    valid = np.arange(K)[None, :] < nhits.astype(np.int64)[:, None]
+    arrays = {"hits_score": np.where(valid, hits["score"], np.float32(0)).astype(np.float32),
+              "hits_seg": np.where(valid, hits["seg"], 0).astype(np.float64),
+              "hits_doc": np.where(valid, hits["doc"], 0).astype(np.float64),
+              "nhits": nhits.astype(np.float64),
+              "found": found.astype(np.float64)}
+    row_bytes = K * (4 + 8 + 8) + 8 + 8
+    if Q * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(Q, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baselines(index_dir, queries, k, budget_s):
@@ -270,29 +311,39 @@ def main():
     assert usable.all()
 
     # ---- kernel leg: descriptors resident in HBM, the scoring launch alone under HIP events (the roofline's numbers) ----
+    # (a plain run only warms the device up on it)
+    kernel_leg = args.full or args.kernel_only
     kb = nsbind.prepare_raw(eng.ctx, qd, refs, K, flags)
-    # the first launches after an idle period run ~10 % slow while the device clocks ramp (profiles/r01/final_cfg5_kernel_trace_head.csv)
-    for _ in range(6):
-        kb.run(timed=False)
-    kb.sync()
-    for _ in range(args.warmup):
-        kb.run(timed=False)
-    kb.sync()
+    # the first launches after an idle period run ~10 % slow while the device clocks ramp (profiles/r01/final_cfg5_kernel_trace_head.csv):
+    # batch 0 runs untimed for RAMP_S before anything is timed
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        kb.run(timed=True)
-    kb.sync()   # also reads the HIP events recorded on the stream
-    kernel_elapsed = time.perf_counter() - t0
+    while True:
+        for _ in range(6):
+            kb.run(timed=False)
+        kb.sync()
+        if time.perf_counter() - t0 >= RAMP_S:
+            break
+    kernel_elapsed = None
+    if kernel_leg:
+        for _ in range(args.warmup):
+            kb.run(timed=False)
+        kb.sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            kb.run(timed=True)
+        kb.sync()   # also reads the HIP events recorded on the stream
+        kernel_elapsed = time.perf_counter() - t0
     kinfo = kb.info()
-    k_hits, k_nhits, k_found = kb.fetch()
-    assert (k_nhits == np.minimum(k_found, K)).all(), "result sanity check failed"
+    if kernel_leg:
+        k_hits, k_nhits, k_found = outputs = kb.fetch()
+        assert (k_nhits == np.minimum(k_found, K)).all(), "result sanity check failed"
     kb.close()
     score_ms = kinfo.sum_score_kernel_ms / max(kinfo.timed_runs, 1)
     total_ms = kinfo.sum_total_ms / max(kinfo.timed_runs, 1)
     shared = bool(kinfo.flags & nsbind.NS_INFO_SHARED)
     # the same batch with sharing off (every posting scored in place, once per query that names it): reported next to the roofline
     in_place_leg = None
-    if shared and not args.kernel_only:
+    if shared and args.full and not args.kernel_only:
         eng.share_scores(0)
         pb = nsbind.prepare_raw(eng.ctx, qd, refs, K, flags)
         for _ in range(max(args.warmup, 2)):
@@ -316,8 +367,8 @@ def main():
     # ---- value leg: K pipelined steps at the C-ABI boundary ----
     # A serving loop sees a different batch every step: the steps rotate over ROT distinct batches of the same query law and
     # size (batch 0 = the kernel leg's; batch i = seed + 104729 i), so the device never sees the same launch twice in a row
-    # (other items, other launch order, other L2 / Infinity-Cache footprint).  Every batch's expected answer is computed once,
-    # untimed, one batch at a time; the timed region's last step is compared with its batch's.
+    # (other items, other launch order, other L2 / Infinity-Cache footprint).  With --full every batch's expected answer is
+    # computed once, untimed, one batch at a time; the timed region's last step is compared with its batch's.
     ROT = 4
     elapsed = None
     if not args.kernel_only:
@@ -328,17 +379,21 @@ def main():
             rot_queries = None
             rot_local = [queries] + [gen(Q, seed + 7919 * rank + 104729 * i) for i in range(1, ROT)]
         rot = []          # per batch: (qd, refs) of THIS rank's shard
-        rot_expect = []   # per batch: (hits, nhits, found) of this rank's shard, from an unpipelined run
+        rot_expect = []   # per batch (--full): (hits, nhits, found) of this rank's shard, from an unpipelined run
         for i, qs_ in enumerate(rot_local):
             if i == 0:
-                rot.append((qd, refs)); rot_expect.append((k_hits, k_nhits, k_found))
+                rot.append((qd, refs))
+                if args.full:
+                    rot_expect.append((k_hits, k_nhits, k_found))
                 continue
             qd_i, refs_i, us_i = eng.build_refs(qs_)
             assert us_i.all() and len(qd_i) == Qr
-            rb = nsbind.prepare_raw(eng.ctx, qd_i, refs_i, K, flags)
-            rb.run(timed=False); rb.sync()
-            rot.append((qd_i, refs_i)); rot_expect.append(rb.fetch())
-            rb.close()
+            rot.append((qd_i, refs_i))
+            if args.full:
+                rb = nsbind.prepare_raw(eng.ctx, qd_i, refs_i, K, flags)
+                rb.run(timed=False); rb.sync()
+                rot_expect.append(rb.fetch())
+                rb.close()
         L.ns_ctx_set_overlap(eng.ctx, 0 if args.no_overlap else 1)
         depth = max(1, args.depth)
         if dist is None:
@@ -356,10 +411,12 @@ def main():
             last = run_steps(args.steps)
             torch.cuda.synchronize()
             elapsed = time.perf_counter() - t0
-            # the timed region's results are real: the last step's host buffers equal what its batch gives one batch at a time
-            e_hits, e_nhits, e_found = rot_expect[(args.steps - 1) % ROT]
-            assert last[0].tobytes() == e_hits.tobytes() and last[1].tobytes() == e_nhits.tobytes() and last[2].tobytes() == e_found.tobytes(), \
-                "pipelined results differ from the unpipelined run of the same batch"
+            outputs = last[:3]
+            if args.full:
+                # the timed region's results are real: the last step's host buffers equal what its batch gives one batch at a time
+                e_hits, e_nhits, e_found = rot_expect[(args.steps - 1) % ROT]
+                assert last[0].tobytes() == e_hits.tobytes() and last[1].tobytes() == e_nhits.tobytes() and last[2].tobytes() == e_found.tobytes(), \
+                    "pipelined results differ from the unpipelined run of the same batch"
         else:
             # every rank: prepare(own shard) -> kernels into ITS packed block -> ONE all-gather of the blocks; up to `depth`
             # steps in flight (the host only waits for the step that left the pipeline)
@@ -408,18 +465,23 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-            # The gathered block of the LAST timed step, checked on every rank: this rank's own rows — hits, nhits, found — equal
-            # what its shard of that batch gives one batch at a time; and under strong scaling (every rank knows the whole
-            # global batch) ALL ranks' rows equal this rank's own unsharded answer to the global batch, computed here once.
-            gh, gn, gf = shard.packed_views(gathered[(args.steps - 1) % depth], per, K, n_gpus)
+            # The gathered block of the LAST timed step: all ranks' rows, what the step hands its caller.  With --full it is
+            # checked on every rank: this rank's own rows — hits, nhits, found — equal what its shard of that batch gives one
+            # batch at a time; and under strong scaling (every rank knows the whole global batch) ALL ranks' rows equal this
+            # rank's own unsharded answer to the global batch, computed here once.
+            if args.full or (rank == 0 and args.dump_outputs):
+                gh, gn, gf = shard.packed_views(gathered[(args.steps - 1) % depth], per, K, n_gpus)
+                g_hits = gh.cpu().numpy().view(nsbind.HIT_DTYPE).reshape(n_gpus, per, K)
+                g_nhits = gn.cpu().numpy().astype(np.uint32)
+                g_found = gf.cpu().numpy().astype(np.uint64)
+                rows = [shard.shard_bounds(Q, r, n_gpus) if strong else (0, per) for r in range(n_gpus)]   # padding rows dropped
+                outputs = tuple(np.concatenate([g[r, :b_ - a] for r, (a, b_) in enumerate(rows)]) for g in (g_hits, g_nhits, g_found))
             li = (args.steps - 1) % ROT
-            e_hits, e_nhits, e_found = rot_expect[li]
-            g_hits = gh.cpu().numpy().view(nsbind.HIT_DTYPE).reshape(n_gpus, per, K)
-            g_nhits = gn.cpu().numpy().astype(np.uint32)
-            g_found = gf.cpu().numpy().astype(np.uint64)
-            assert g_hits[rank, :Qr].tobytes() == e_hits.tobytes() and np.array_equal(g_nhits[rank, :Qr], e_nhits) and np.array_equal(g_found[rank, :Qr], e_found), \
-                "gathered results (own rows) differ from the unpipelined run of the same batch"
-            if strong:
+            if args.full:
+                e_hits, e_nhits, e_found = rot_expect[li]
+                assert g_hits[rank, :Qr].tobytes() == e_hits.tobytes() and np.array_equal(g_nhits[rank, :Qr], e_nhits) and np.array_equal(g_found[rank, :Qr], e_found), \
+                    "gathered results (own rows) differ from the unpipelined run of the same batch"
+            if args.full and strong:
                 gq, grefs, gus = eng.build_refs(rot_queries[li])
                 assert gus.all()
                 gb = nsbind.prepare_raw(eng.ctx, gq, grefs, K, flags)
@@ -432,9 +494,9 @@ def main():
                         and np.array_equal(g_found[r, :b_ - a], w_found[a:b_]), f"gathered rows of rank {r} differ from the unsharded answer"
         L.ns_ctx_set_overlap(eng.ctx, 0)
 
-    # ---- extra legs (N = 1 only; reported next to the headline, never as `value`) ----
+    # ---- extra legs (--full, N = 1 only; reported next to the headline, never as `value`) ----
     impact_leg = None
-    if n_gpus == 1 and args.variant == 0 and not args.no_impact_leg and not args.kernel_only:
+    if n_gpus == 1 and args.full and args.variant == 0 and not args.no_impact_leg and not args.kernel_only:
         t0 = time.perf_counter()
         eng.build_impacts()
         build_s = time.perf_counter() - t0
@@ -465,7 +527,7 @@ def main():
     # "algorithmic bytes" are bytes actually scanned.
     pruned_leg = None
     st_queries = [q for q in queries if len(q.split()) == 1]   # (the workloads' words are all index terms: one word = one scored term)
-    if n_gpus == 1 and args.variant == 0 and not args.no_impact_leg and not args.kernel_only and flags == 0 and st_queries:
+    if n_gpus == 1 and args.full and args.variant == 0 and not args.no_impact_leg and not args.kernel_only and flags == 0 and st_queries:
         t0 = time.perf_counter()
         eng.build_blockmax()
         build_s = time.perf_counter() - t0
@@ -525,7 +587,7 @@ def main():
             traffic_db = {}
 
     hbm_leg = None
-    if n_gpus == 1 and args.config == "cfg5" and not args.no_hbm_leg and not args.kernel_only:
+    if n_gpus == 1 and args.full and args.config == "cfg5" and not args.no_hbm_leg and not args.kernel_only:
         hbm_leg = run_hbm_leg(args, nsbind, np, gen, seed, docs, K, flags, local_rank, traffic_db)
 
     if rank == 0:
@@ -565,7 +627,9 @@ def main():
                                 f"in front of the scoring kernel and inside the timed region ({kinfo.postings / max(kinfo.shared_postings, 1):.0f} uses per distinct posting); nothing is kept between steps")
                                if shared else "in place: every posting scored once per query that names its list",
             },
-            "roofline": {
+        }
+        if kernel_leg:
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_share_scores + k_uscore" if (args.variant == 0 and shared) else "k_uscore" if args.variant == 0 else "k_dscore" if args.variant in (12, 13, 14, 15, 16, 17) else "k_tscore" if args.variant in (18, 19, 20) else "k_score",
                 "achieved": achieved,
@@ -582,13 +646,12 @@ def main():
                 "all_kernels_ms": total_ms,
                 "measured": "HIP events on the ctx stream around every scoring launch of the kernel leg (descriptors resident, one batch at a time)"
                             + ("; the span holds BOTH kernels of a step: k_share_scores (the batch's distinct lists scored once) and k_uscore" if shared else ""),
-            },
-            "kernel_only": {"value": Qr * n_gpus * args.steps / kernel_elapsed, "unit": "queries/s", "ms_per_step": kernel_elapsed / args.steps * 1e3,
-                            "what": "device-only: the prepared batch re-run with descriptors resident in HBM (round 1's `value`)"},
-            "host": host_info(),
-            "library": lib_info(),
-        }
-        if n_gpus == 1 and args.cpu_seconds > 0 and flags == 0 and not args.kernel_only:
+            }
+            line["kernel_only"] = {"value": Qr * n_gpus * args.steps / kernel_elapsed, "unit": "queries/s", "ms_per_step": kernel_elapsed / args.steps * 1e3,
+                                   "what": "device-only: the prepared batch re-run with descriptors resident in HBM (round 1's `value`)"}
+        line["host"] = host_info()
+        line["library"] = lib_info()
+        if n_gpus == 1 and args.full and args.cpu_seconds > 0 and flags == 0 and not args.kernel_only:
             cb, allcb = cpu_baselines(index_dir, queries, K, args.cpu_seconds)
             if cb is not None:
                 line["cpu_baseline"] = cb
@@ -601,6 +664,8 @@ def main():
             line["impact_stream"] = impact_leg
         if pruned_leg is not None:
             line["pruned"] = pruned_leg
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *outputs)
         print(json.dumps(line), flush=True)
 
     eng.close()

@@ -22,7 +22,7 @@ if [[ $PART == *A* ]]; then
   timeout -k 10 900 python3 -m pytest $R/tests -m gpu -x -q -p no:cacheprovider > $O/tests.txt 2>&1 || { tail -20 $O/tests.txt; exit 1; }
   tail -2 $O/tests.txt
   for c in cfg5 cfg2 cfg3 cfg4; do
-    timeout -k 10 400 python3 $R/bench.py --config $c 2>$O/bench_$c.err | tail -1 > $O/bench_$c.json || exit 1
+    timeout -k 10 400 python3 $R/bench.py --full --config $c 2>$O/bench_$c.err | tail -1 > $O/bench_$c.json || exit 1
   done
   prof stats --kernel-trace --stats --output-format csv -d $O/stats/raw -- $B || exit 1
   cp $(find $O/stats/raw -name "*kernel_stats.csv" | head -1) $O/stats/cfg5_kernel_stats.csv
@@ -93,7 +93,7 @@ open('/tmp/cfg3.txt','w').write('\n'.join(workloads.cfg3_queries())+'\n')"
   prof sem_stats --kernel-trace --stats --output-format csv -d $O/sem_stats/raw -- python3 $R/tools/sem_bench.py || exit 1
   cp $(find $O/sem_stats/raw -name "*kernel_stats.csv" | head -1) $O/sem_kernel_stats.csv; rm -rf $O/sem_stats
   for sc in strong weak; do
-    timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 $R/bench.py --gpus 2 --backend gloo --scaling $sc --steps 10 --warmup 2 2> $O/n2_$sc.err | tail -1 > $O/n2_$sc.json || exit 1
+    timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 $R/bench.py --full --gpus 2 --backend gloo --scaling $sc --steps 10 --warmup 2 2> $O/n2_$sc.err | tail -1 > $O/n2_$sc.json || exit 1
   done
   echo "part B collected"
 fi

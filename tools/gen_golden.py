@@ -129,7 +129,7 @@ def make_meta_fixture(outdir):
 def make_invert_fixture(outdir):
     """Index inversion: a small forward.bin / terms.bin pair (committed as base64: a fixture is
     inputs + expected outputs) and the sha256 of every file the REAL `lexicon` tool (oracle/_ref/lexicon)
-    writes for it."""
+    writes for it; under `larger`, the same for a larger input that forward_gen regenerates from its seed."""
     import base64
     import hashlib
     import shutil
@@ -145,15 +145,23 @@ def make_invert_fixture(outdir):
         seg = os.path.join(tmp, "seg")
         pairs = forward_gen.write_inputs(seg, 400, 900, 18, 20261)
         inputs = {f: base64.b64encode(open(os.path.join(seg, f), "rb").read()).decode() for f in ("terms.bin", "forward.bin")}
-        subprocess.run([tool, seg], check=True, stderr=subprocess.DEVNULL)
-        outs = {}
-        for f in invert_oracle.output_files():
-            b = open(os.path.join(seg, f), "rb").read()
-            outs[f] = {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()}
+        big = os.path.join(tmp, "big")
+        big_pairs = forward_gen.write_inputs(big, 20_000, 70_000, 45, 99)
+
+        def tool_outputs(d):
+            subprocess.run([tool, d], check=True, stderr=subprocess.DEVNULL)
+            outs = {}
+            for f in invert_oracle.output_files():
+                b = open(os.path.join(d, f), "rb").read()
+                outs[f] = {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()}
+            return outs
+
         with open(os.path.join(outdir, "invert1.json"), "w") as fh:
             json.dump({"what": "oracle/_ref/lexicon (the reference's src/lexicon.cpp, built as it lies) on the inputs below",
                        "generator": "forward_gen.write_inputs(seg, 400, 900, 18, 20261)", "pairs": pairs,
-                       "inputs_base64": inputs, "outputs": outs}, fh, indent=0)
+                       "inputs_base64": inputs, "outputs": tool_outputs(seg),
+                       "larger": {"generator": "forward_gen.write_inputs(seg, 20000, 70000, 45, 99)", "pairs": big_pairs,
+                                  "outputs": tool_outputs(big)}}, fh, indent=0)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

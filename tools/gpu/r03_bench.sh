@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 timeout -k 10 1000 python3 -m pytest $R/tests -m gpu -x -q -p no:cacheprovider --durations=5 > $O/tests.txt 2>&1 || { tail -40 $O/tests.txt; exit 1; }
 tail -4 $O/tests.txt
 cd $R
-timeout -k 10 600 python3 bench.py 2>$O/bench.err | tail -1 > $O/bench.json || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json || { tail -20 $O/bench.err; exit 1; }
 python3 - <<PY
 import json
 d = json.load(open("$O/bench.json"))

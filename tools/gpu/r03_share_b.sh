@@ -13,7 +13,7 @@ for rep in 1 2; do
 done
 cat $O/big.txt
 for m in 1 0; do
-  timeout -k 10 600 python3 bench.py --share $m --no-hbm-leg --cpu-seconds 0 > $O/bench_share$m.json 2> $O/bench_share$m.err || { tail -5 $O/bench_share$m.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --share $m --no-hbm-leg --cpu-seconds 0 > $O/bench_share$m.json 2> $O/bench_share$m.err || { tail -5 $O/bench_share$m.err; exit 1; }
 done
 python3 - <<PY
 import json

@@ -7,7 +7,7 @@ cd $R
 timeout -k 10 300 python3 tools/dbg/prepare_time.py 16384,4096,2048 > $O/prepare.txt 2>&1 || { tail $O/prepare.txt; exit 1; }
 cat $O/prepare.txt
 for m in 1 0 1 0; do
-  timeout -k 10 600 python3 bench.py --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   python3 -c "
 import json
 d = json.load(open('$O/bench.json'))

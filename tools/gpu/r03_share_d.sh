@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 for rep in 1 2 3; do
 for m in 1 0; do
-  timeout -k 10 600 python3 bench.py --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 --steps ${STEPS:-20} > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 --steps ${STEPS:-20} > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   python3 -c "
 import json
 d = json.load(open('$O/bench.json'))

@@ -6,7 +6,7 @@ O=$R/gpurun_out/${1:-r03_share_f}
 mkdir -p $O
 cd $R
 one() {
-  timeout -k 10 600 python3 bench.py --no-hbm-leg --no-impact-leg --cpu-seconds 0 "$@" > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --no-hbm-leg --no-impact-leg --cpu-seconds 0 "$@" > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   python3 -c "
 import json,sys
 d = json.load(open('$O/bench.json'))

@@ -6,7 +6,7 @@ O=$R/gpurun_out/${1:-r03_share_trace}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for m in 1 0; do
-  timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/raw$m -- python3 $R/bench.py --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 --steps 12 --warmup 3 > $O/bench$m.json 2> $O/bench$m.err || { tail -5 $O/bench$m.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/raw$m -- python3 $R/bench.py --full --share $m --no-hbm-leg --no-impact-leg --cpu-seconds 0 --steps 12 --warmup 3 > $O/bench$m.json 2> $O/bench$m.err || { tail -5 $O/bench$m.err; exit 1; }
   cp $(find $O/raw$m -name "*kernel_trace.csv" | head -1) $O/trace$m.csv; rm -rf $O/raw$m
   python3 - <<PY
 import csv
