@@ -265,6 +265,25 @@ int ns_sem_topk(ns_ctx* ctx, ns_sem* sem, const float* qvecs, uint32_t n_q, uint
                 const uint32_t* ban_off, const uint32_t* ban_rows, uint32_t* rows_out, float* sims_out,
                 uint32_t* counts_out, float* device_ms_out);
 
+/* Autocomplete (the reference's AutocompleteIndex, src/api_autocomplete.cpp, behind Engine::suggest): a dictionary of
+ * n_terms terms SORTED BY THEIR BYTES (memcmp order; equal terms may repeat), term i = pool[offsets[i] .. offsets[i + 1]),
+ * with a u32 score each.  ns_ac_upload copies it to the device and builds the range top-10 tree there; it fails with
+ * NS_E_INVAL for unsorted terms, offsets[0] != 0, decreasing offsets, or a pool of 4 GiB or more (offsets[n_terms]).
+ * n_terms == 0 is a valid, empty table.
+ * ns_ac_suggest: for each of n_q prefixes (host: prefix q = prefix_bytes[prefix_offsets[q] .. prefix_offsets[q + 1]))
+ * the L (1..10) best terms that start with it, best first — score descending, then term ascending (== index ascending) —
+ * as dictionary indices in idx_out[q * L + r] (host, n_q x L; ~0u past the end) and their number in count_out[q].  The
+ * prefix is compared as raw bytes (the caller normalises it); an empty prefix matches every term.  Synchronous; staged
+ * through the ctx's pinned buffers.  device_ms_out (may be NULL): the kernel's time.
+ * Lifetime: a table belongs to its ctx, like a segment.  Release it with ns_ac_release(ctx, table) before the ctx; a
+ * ctx destroyed first frees the tables it still holds, after which their handles are dangling and must not be passed
+ * to any call. */
+typedef struct ns_ac ns_ac;
+int ns_ac_upload(ns_ctx* ctx, const uint8_t* pool, const uint64_t* offsets, const uint32_t* scores, uint32_t n_terms, ns_ac** out);
+int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes, const uint32_t* prefix_offsets, uint32_t n_q, uint32_t L,
+                  uint32_t* idx_out, uint32_t* count_out, float* device_ms_out);
+int ns_ac_release(ns_ctx* ctx, ns_ac* ac);
+
 /* Segment-sharded multi-GPU (the alternative to query sharding for an index that outgrows one
  * GPU's HBM): rank r holds a subset of the segments and scores ALL queries over it; the fixed-size per-rank rows
  * are all-gathered rank-major (hits [n_ranks][n_queries][k], nhits and found [n_ranks][n_queries]) and joined here

@@ -136,6 +136,27 @@ int nsh_engine_search_batch(nsh_engine* e, const char* const* queries, uint32_t 
 int nsh_engine_prepare(nsh_engine* e, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
                        ns_batch** out);
 
+/* Autocomplete: Engine::suggest(input, limit) (include/api_engine.hpp:67, src/api_engine.cpp:164-187).  The input is
+ * input_len raw bytes (NUL and other control bytes included); *json_out receives {"limit", "query", "suggestions"} in
+ * dump(2) layout (free with nsh_free).  -1 without a device context (there is no CPU path) or on failure. */
+int nsh_engine_suggest_json(nsh_engine* e, const char* input, uint64_t input_len, int limit, char** json_out);
+/* A batch of suggest requests: input q = bytes[offsets[q] .. offsets[q + 1]) (offsets: n_inputs + 1 entries).  With
+ * L = clamp(limit, 1, 10): term_idx[q * L + r] = row of the suggest table (nsh_engine_suggest_table) of suggestion r,
+ * best first, ~0u past count[q]; suggestion r = input[0 .. base_len[q]) + that row's term.  device_ms (may be NULL):
+ * kernel time summed over the batch's device calls. */
+int nsh_engine_suggest_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_inputs, int limit,
+                             uint32_t* term_idx, uint32_t* count, uint32_t* base_len, float* device_ms);
+/* The sorted suggest table the last reload built (valid until close/reload): term i = pool[offsets[i] .. offsets[i + 1]),
+ * scores[i] = its df summed over the segments.  build_ms: the table's host build time in that reload; upload_ms: its
+ * upload and device tree build (0 on a host-only engine, which has the table too).  Any output may be NULL. */
+int nsh_engine_suggest_table(nsh_engine* e, const char** pool, const uint64_t** offsets, const uint32_t** scores,
+                             uint64_t* n_terms, double* build_ms, double* upload_ms);
+/* The request split alone (src/api_autocomplete.cpp:176-187): *base_len = bytes of the input before its last alnum run;
+ * the run lower-cased (the prefix) is written to prefix (up to cap bytes, not NUL-terminated); returns its length. */
+uint64_t nsh_suggest_split(const char* input, uint64_t input_len, uint64_t* base_len, char* prefix, uint64_t cap);
+/* The limit clamp of Engine::suggest (src/api_engine.cpp:171): 1..10. */
+int nsh_suggest_clamp_limit(int limit);
+
 #ifdef __cplusplus
 }
 #endif

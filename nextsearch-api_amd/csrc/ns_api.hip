@@ -29,6 +29,7 @@
 #include "ns_tile_kernel.hip"
 #include "ns_invert.hip"
 #include "ns_sem.hip"
+#include "ns_suggest.hip"
 
 using namespace ns;
 
@@ -194,9 +195,11 @@ struct ns_ctx {
     uint32_t key_pct[4] = {100, 100, 100, 100};   // launch-order key of general / thin / tile / merge items in per cent (NS_KEY_PCT=g,t,d,m: sweeps)
     uint32_t tile_dens64 = 16;   // doc-tile class from this many postings per 64 docs (0.25 per doc); NS_TILE_DENS64 overrides (sweeps)
     bool order_coarse_forced = false;   // NS_ORDER_COARSE given: no automatic choice
+    std::vector<ns_ac*> acs;   // autocomplete tables (ns_ac_upload): owned by the ctx, freed by ns_ac_release or ns_ctx_destroy
 };
 
 static thread_local std::string g_create_err;
+static void ac_free_fwd(ns_ac* ac);
 static void seg_free_device_fwd(ns_seg* s);
 static void seg_free_staging_fwd(ns_seg* s);
 
@@ -345,6 +348,7 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
         seg_free_device_fwd(s);
         delete s;
     }
+    for (ns_ac* ac : ctx->acs) ac_free_fwd(ac);   // tables still held: their handles die with the ctx
     for (auto& blk : ctx->pool) (void)hipFree(blk.p);
     if (ctx->h_up) (void)hipHostFree(ctx->h_up);
     if (ctx->h_down) (void)hipHostFree(ctx->h_down);
@@ -2551,6 +2555,199 @@ extern "C" int ns_sem_topk(ns_ctx* ctx, ns_sem* sem, const float* qvecs, uint32_
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_sem_topk: %s", hipGetErrorString(e));
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Autocomplete (csrc/ns_suggest.hip): the sorted dictionary, its range top-10 tree, and the batched prefix top-L.
+struct ns_ac {
+    ns_ctx* ctx = nullptr;
+    uint32_t n = 0;
+    AcLevels lv{};
+    uint8_t* d_pool = nullptr;     // term bytes back to back
+    uint32_t* d_offs = nullptr;    // n + 1
+    uint64_t* d_heads = nullptr;   // first 8 bytes of each term, big-endian, zero-padded
+    uint64_t* d_keys = nullptr;    // (~score << 32) | index: the scores live here
+    uint64_t* d_tree = nullptr;    // levels back to back, kAcTop keys per node
+};
+
+static void ac_free(ns_ac* ac) {
+    if (!ac) return;
+    (void)hipFree(ac->d_pool);
+    (void)hipFree(ac->d_offs);
+    (void)hipFree(ac->d_heads);
+    (void)hipFree(ac->d_keys);
+    (void)hipFree(ac->d_tree);
+    delete ac;
+}
+static void ac_free_fwd(ns_ac* ac) { ac_free(ac); }
+
+extern "C" int ns_ac_upload(ns_ctx* ctx, const uint8_t* pool, const uint64_t* offsets, const uint32_t* scores, uint32_t n_terms, ns_ac** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_upload: ctx is NULL");
+    if (!out) return fail(ctx, NS_E_INVAL, "ns_ac_upload: out is NULL");
+    *out = nullptr;
+    if (n_terms && (!offsets || !scores)) return fail(ctx, NS_E_INVAL, "ns_ac_upload: null argument");
+    if (n_terms == ~0u) return fail(ctx, NS_E_INVAL, "ns_ac_upload: %u terms (the index ~0 is reserved)", n_terms);
+    const uint64_t pool_bytes = n_terms ? offsets[n_terms] : 0;
+    if (n_terms && offsets[0] != 0) return fail(ctx, NS_E_INVAL, "ns_ac_upload: offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
+    if (pool_bytes >= (1ull << 32)) return fail(ctx, NS_E_INVAL, "ns_ac_upload: a pool of %llu bytes (>= 4 GiB)", (unsigned long long)pool_bytes);
+    if (pool_bytes && !pool) return fail(ctx, NS_E_INVAL, "ns_ac_upload: pool is NULL");
+    for (uint32_t i = 0; i < n_terms; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(ctx, NS_E_INVAL, "ns_ac_upload: offsets decrease at term %u", i);
+        if (i == 0) continue;
+        const uint64_t la = offsets[i] - offsets[i - 1], lb = offsets[i + 1] - offsets[i];
+        const int c = std::memcmp(pool + offsets[i - 1], pool + offsets[i], (size_t)std::min(la, lb));
+        if (c > 0 || (c == 0 && la > lb)) return fail(ctx, NS_E_INVAL, "ns_ac_upload: terms %u and %u are not in byte order", i - 1, i);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ns_ac* ac = new ns_ac();
+    ac->ctx = ctx;
+    ac->n = n_terms;
+    if (n_terms == 0) {   // an empty table answers every prefix with nothing, on the host
+        ctx->acs.push_back(ac);
+        *out = ac;
+        return NS_OK;
+    }
+    std::vector<uint32_t> offs32(n_terms + 1);
+    std::vector<uint64_t> heads(n_terms), keys(n_terms);
+    for (uint32_t i = 0; i <= n_terms; i++) offs32[i] = (uint32_t)offsets[i];
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        uint64_t h = 0;
+        for (uint64_t j = 0; j < len && j < 8; j++) h |= (uint64_t)pool[offsets[i] + j] << (56 - 8 * j);
+        heads[i] = h;
+        keys[i] = ((uint64_t)(~scores[i]) << 32) | i;
+    }
+    uint32_t nodes = (n_terms + kAcFan - 1) / kAcFan;
+    uint64_t tree_keys = 0;
+    for (;;) {
+        ac->lv.off[ac->lv.n_levels] = tree_keys;
+        ac->lv.nodes[ac->lv.n_levels] = nodes;
+        tree_keys += (uint64_t)nodes * kAcTop;
+        ac->lv.n_levels++;
+        if (nodes <= (uint32_t)kAcFan) break;
+        nodes = (nodes + kAcFan - 1) / kAcFan;
+    }
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    chk(hipMalloc((void**)&ac->d_pool, std::max<uint64_t>(pool_bytes, 1)));
+    chk(hipMalloc((void**)&ac->d_offs, (size_t)(n_terms + 1) * 4));
+    chk(hipMalloc((void**)&ac->d_heads, (size_t)n_terms * 8));
+    chk(hipMalloc((void**)&ac->d_keys, (size_t)n_terms * 8));
+    chk(hipMalloc((void**)&ac->d_tree, (size_t)tree_keys * 8));
+    if (e == hipSuccess) {
+        if (pool_bytes) chk(hipMemcpyAsync(ac->d_pool, pool, pool_bytes, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(ac->d_offs, offs32.data(), offs32.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(ac->d_heads, heads.data(), heads.size() * 8, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(ac->d_keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, st));
+    }
+    for (uint32_t j = 0; j < ac->lv.n_levels && e == hipSuccess; j++) {
+        const uint64_t* src = j == 0 ? ac->d_keys : ac->d_tree + ac->lv.off[j - 1];
+        const uint32_t n_src = j == 0 ? n_terms : ac->lv.nodes[j - 1];
+        hipLaunchKernelGGL(k_ac_build, dim3((ac->lv.nodes[j] + 3) / 4), dim3(256), 0, st, src, n_src, j == 0 ? 1u : (uint32_t)kAcTop,
+                           j == 0 ? 1u : (uint32_t)kAcTop, ac->d_tree + ac->lv.off[j], ac->lv.nodes[j]);
+        chk(hipGetLastError());
+    }
+    chk(hipStreamSynchronize(st));   // the host arrays above are pageable and die here
+    if (e != hipSuccess) {
+        ac_free(ac);
+        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_upload: %s", hipGetErrorString(e));
+    }
+    ctx->acs.push_back(ac);
+    *out = ac;
+    return NS_OK;
+}
+
+extern "C" int ns_ac_release(ns_ctx* ctx, ns_ac* ac) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_release: ctx is NULL");
+    auto it = std::find(ctx->acs.begin(), ctx->acs.end(), ac);
+    if (!ac || it == ctx->acs.end()) return fail(ctx, NS_E_INVAL, "ns_ac_release: table does not belong to this ctx");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->acs.erase(it);
+    ac_free(ac);
+    return NS_OK;
+}
+
+extern "C" int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes, const uint32_t* prefix_offsets, uint32_t n_q, uint32_t L,
+                             uint32_t* idx_out, uint32_t* count_out, float* device_ms_out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_suggest: ctx is NULL");
+    if (!ac || std::find(ctx->acs.begin(), ctx->acs.end(), ac) == ctx->acs.end())
+        return fail(ctx, NS_E_INVAL, "ns_ac_suggest: table does not belong to this ctx");
+    if (L < 1 || L > (uint32_t)kAcTop) return fail(ctx, NS_E_INVAL, "ns_ac_suggest: L=%u outside [1,%d]", L, kAcTop);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (!n_q) return NS_OK;
+    if (!prefix_offsets || !idx_out || !count_out) return fail(ctx, NS_E_INVAL, "ns_ac_suggest: null argument");
+    for (uint32_t q = 0; q < n_q; q++)
+        if (prefix_offsets[q + 1] < prefix_offsets[q]) return fail(ctx, NS_E_INVAL, "ns_ac_suggest: prefix offsets decrease at %u", q);
+    const uint32_t b0 = prefix_offsets[0], n_bytes = prefix_offsets[n_q] - b0;
+    if (n_bytes && !prefix_bytes) return fail(ctx, NS_E_INVAL, "ns_ac_suggest: prefix_bytes is NULL");
+    if (ac->n == 0) {   // nothing starts with anything
+        std::fill(idx_out, idx_out + (size_t)n_q * L, ~0u);
+        std::fill(count_out, count_out + n_q, 0u);
+        return NS_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // device block: [offsets (n_q + 1) | prefix bytes | idx n_q x L | counts n_q]; the first two go up in one copy through the
+    // ctx's pinned upload buffer, the last two come down in one copy through its pinned result buffer
+    const size_t o_bytes = ((size_t)(n_q + 1) * 4 + 7) & ~(size_t)7;
+    const size_t up = o_bytes + n_bytes;
+    const size_t o_idx = (up + 255) & ~(size_t)255;
+    const size_t down = (size_t)n_q * L * 4 + (size_t)n_q * 4;
+    const size_t block_bytes = o_idx + down;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (ctx->up_busy) {   // a batch's upload may still be reading the staging buffer
+        chk(hipEventSynchronize(ctx->up_done));
+        ctx->up_busy = false;
+    }
+    if (e == hipSuccess && up <= kStageMaxBytes && ctx->h_up_cap < up) {
+        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
+        ctx->h_up = nullptr; ctx->h_up_cap = 0;
+        const size_t cap = std::max<size_t>(up + up / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
+        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
+    }
+    const bool down_pinned = !ctx->down_owner && down <= kStageMaxBytes;
+    if (e == hipSuccess && down_pinned && ctx->h_down_cap < down) {
+        if (ctx->h_down) (void)hipHostFree(ctx->h_down);
+        ctx->h_down = nullptr; ctx->h_down_cap = 0;
+        const size_t cap = std::max<size_t>(down + down / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_down, cap, hipHostMallocDefault) == hipSuccess) ctx->h_down_cap = cap;
+        else { ctx->h_down = nullptr; (void)hipGetLastError(); }
+    }
+    std::vector<char> up_own, down_own;
+    char* hu = (ctx->h_up_cap >= up) ? (char*)ctx->h_up : (up_own.resize(up), up_own.data());
+    char* hd = (down_pinned && ctx->h_down_cap >= down) ? (char*)ctx->h_down : (down_own.resize(down), down_own.data());
+    for (uint32_t q = 0; q <= n_q; q++) ((uint32_t*)hu)[q] = prefix_offsets[q] - b0;
+    if (n_bytes) std::memcpy(hu + o_bytes, prefix_bytes + b0, n_bytes);
+    char* blk = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (e == hipSuccess) chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    if (e == hipSuccess && device_ms_out) { chk(hipEventCreate(&ev0)); chk(hipEventCreate(&ev1)); }
+    if (e == hipSuccess) {
+        chk(hipMemcpyAsync(blk, hu, up, hipMemcpyHostToDevice, st));
+        if (ev0) chk(hipEventRecord(ev0, st));
+        hipLaunchKernelGGL(k_ac_suggest, dim3((n_q + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_tree, ac->lv,
+                           ac->n, (const uint8_t*)(blk + o_bytes), (const uint32_t*)blk, n_q, L, (uint32_t*)(blk + o_idx),
+                           (uint32_t*)(blk + o_idx + (size_t)n_q * L * 4));
+        chk(hipGetLastError());
+        if (ev1) chk(hipEventRecord(ev1, st));
+        chk(hipMemcpyAsync(hd, blk + o_idx, down, hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));
+    }
+    if (e == hipSuccess) {
+        std::memcpy(idx_out, hd, (size_t)n_q * L * 4);
+        std::memcpy(count_out, hd + (size_t)n_q * L * 4, (size_t)n_q * 4);
+        float ms = 0.0f;
+        if (ev0 && ev1 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_suggest: %s", hipGetErrorString(e));
     return NS_OK;
 }
 

@@ -1,6 +1,7 @@
 #include "engine.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -39,6 +40,8 @@ void Engine::release_device_segments() {
     dev_segs_.clear();
     if (ctx_ && sem.dev) ns_sem_release(ctx_, sem.dev);
     sem.dev = nullptr;
+    if (ctx_ && ac_) ns_ac_release(ctx_, ac_);
+    ac_ = nullptr;
 }
 
 // One segment's postings to the device without a host copy: every inverted file is mapped, appended from the mapping
@@ -135,7 +138,16 @@ bool Engine::reload() {
         }
     }
 
+    // autocomplete's table (src/api_engine.cpp:91-107), sorted on the engine's host threads
+    nsx::SuggestTable fresh_table;
+    const auto t_build = std::chrono::steady_clock::now();
+    if (!pool_) pool_.reset(new ForkJoin(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u)));
+    fresh_table.build(loaded, pool_.get());
+    const double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+    double upload_ms = 0.0;
+
     ns_ctx* fresh_ctx = nullptr;
+    ns_ac* fresh_ac = nullptr;
     std::vector<ns_seg*> fresh_segs;
     std::vector<Replica> fresh_replicas;
     if (device_ >= 0) {
@@ -145,6 +157,13 @@ bool Engine::reload() {
         fresh_segs.assign(loaded.size(), nullptr);
         bool ok = true;
         for (size_t i = 0; i < loaded.size() && ok; i++) ok = upload_segment(fresh_ctx, (uint32_t)i, loaded[i], &fresh_segs[i], err_);
+        if (ok) {   // autocomplete on the primary context only
+            const auto t_up = std::chrono::steady_clock::now();
+            rc = ns_ac_upload(fresh_ctx, (const uint8_t*)fresh_table.pool.data(), fresh_table.off.data(), fresh_table.score.data(),
+                              (uint32_t)fresh_table.size(), &fresh_ac);
+            if (rc != NS_OK) { err_ = std::string("ns_ac_upload: ") + ns_last_error(fresh_ctx); ok = false; }
+            upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up).count();
+        }
         if (ok && fresh_sem.enabled) {
             rc = ns_sem_upload(fresh_ctx, fresh_sem.vecs.data(), (uint32_t)fresh_sem.terms.size(), (uint32_t)fresh_sem.dim, &fresh_sem.dev);
             if (rc != NS_OK) { err_ = std::string("ns_sem_upload: ") + ns_last_error(fresh_ctx); ok = false; }
@@ -169,6 +188,7 @@ bool Engine::reload() {
     release_device_segments();
     if (ctx_) ns_ctx_destroy(ctx_);
     ctx_ = fresh_ctx;
+    ac_ = fresh_ac;
     dev_segs_ = std::move(fresh_segs);
     if (device_ >= 0) {
         for (auto& r : replicas_) if (r.ctx) ns_ctx_destroy(r.ctx);
@@ -178,6 +198,9 @@ bool Engine::reload() {
     segments = std::move(loaded);
     meta = std::move(fresh_meta);
     sem = std::move(fresh_sem);
+    suggest_table = std::move(fresh_table);
+    suggest_build_ms = build_ms;
+    suggest_upload_ms = upload_ms;
     dict.build(segments, [](uint32_t N, uint32_t df) { return bm25_idf(N, df); });
     cache_.clear();
     lru_.clear();
@@ -751,6 +774,157 @@ std::string Engine::search(const std::string& query, int k) {
     std::string body;
     if (!search_text(query, k, body)) {
         // the reference lets exceptions reach the HTTP layer's 500 handler (src/api_server.cpp:76-84)
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- autocomplete (include/api_engine.hpp:67, src/api_engine.cpp:164-187) --------------------------------------------
+// One sub-batch's host side: the inputs' split (base / prefix) and the prefixes that can match something, packed for
+// ns_ac_suggest.  An input whose prefix is empty or longer than every term, or a table without terms, has no suggestion
+// (api_autocomplete.cpp:190-194) and never reaches the device.
+namespace {
+struct SuggestPrep {
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> offs;
+    std::vector<uint32_t> rows;          // input (relative to the sub-batch) of each prefix sent
+    std::vector<uint32_t> at, len;       // per input: the prefix run's position in the input; len 0 = not sent
+    std::vector<uint32_t> idx, cnt;      // the device's answers per prefix sent
+};
+}  // namespace
+
+static void suggest_prepare(const Engine::QueryView* in, size_t q0, size_t q1, size_t max_len, uint32_t* base_len, SuggestPrep& sp,
+                            ForkJoin* fj) {
+    const size_t Q = q1 - q0;
+    sp.at.assign(Q, 0);
+    sp.len.assign(Q, 0);
+    // pass 1 (parallel): the split; the prefix is the last alnum run, lower-cased, so its length is the run's length
+    auto split = [&](size_t a, size_t b) {
+        for (size_t q = a; q < b; q++) {
+            size_t start = 0, end = 0;
+            nsx::suggest_last_run(in[q0 + q].p, in[q0 + q].n, start, end);
+            base_len[q0 + q] = (uint32_t)start;
+            sp.at[q] = (uint32_t)start;
+            sp.len[q] = (end > start && end - start <= max_len) ? (uint32_t)(end - start) : 0u;
+        }
+    };
+    const unsigned nt = fj ? std::min<unsigned>(fj->width(), (unsigned)std::max<size_t>(1, Q / 2048)) : 1u;
+    if (nt <= 1) split(0, Q);
+    else fj->run(nt, [&](unsigned i) { split(Q * i / nt, Q * (i + 1) / nt); });
+    sp.rows.clear();
+    sp.offs.assign(1, 0);
+    uint32_t total = 0;
+    for (size_t q = 0; q < Q; q++) {
+        if (!sp.len[q]) continue;
+        sp.rows.push_back((uint32_t)q);
+        total += sp.len[q];
+        sp.offs.push_back(total);
+    }
+    sp.bytes.resize(total);
+    // pass 2 (parallel): the lower-cased prefix bytes
+    const size_t R = sp.rows.size();
+    auto fill = [&](size_t a, size_t b) {
+        for (size_t r = a; r < b; r++) {
+            const uint32_t q = sp.rows[r];
+            const unsigned char* s = (const unsigned char*)in[q0 + q].p + sp.at[q];
+            uint8_t* d = sp.bytes.data() + sp.offs[r];
+            for (uint32_t j = 0; j < sp.len[q]; j++) d[j] = (s[j] >= 'A' && s[j] <= 'Z') ? (uint8_t)(s[j] - 'A' + 'a') : s[j];
+        }
+    };
+    const unsigned nf = fj ? std::min<unsigned>(fj->width(), (unsigned)std::max<size_t>(1, R / 2048)) : 1u;
+    if (nf <= 1) fill(0, R);
+    else fj->run(nf, [&](unsigned i) { fill(R * i / nf, R * (i + 1) / nf); });
+}
+
+bool Engine::suggest_batch(const QueryView* inputs, size_t Q, int limit, uint32_t* term_idx, uint32_t* count, uint32_t* base_len,
+                           float* device_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_ || !ac_) { err_ = "no device context: this engine has no CPU autocomplete path"; return false; }
+    if (Q && (!inputs || !term_idx || !count || !base_len)) { err_ = "suggest_batch: null argument"; return false; }
+    const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
+    if (Q == 0) return true;
+    if (Q >= 4096 && (!pool_ || pool_->width() < 2)) pool_.reset(new ForkJoin(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u)));
+    ForkJoin* fj = Q >= 4096 ? pool_.get() : nullptr;
+    const size_t kSub = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSub ? (Q + kSub - 1) / kSub : 1;
+    const size_t max_len = suggest_table.size() ? suggest_table.max_len : 0;
+    SuggestPrep sp[2];
+    float dev_ms = 0.0f;
+    // the device's part of sub-batch i: ns_ac_suggest on the prefixes sent, answers scattered to the caller's rows
+    auto device = [&](size_t i, SuggestPrep& p, std::string& err) -> bool {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        for (size_t q = a; q < b; q++) count[q] = 0;
+        std::fill(term_idx + a * L, term_idx + b * L, ~0u);
+        const uint32_t R = (uint32_t)p.rows.size();
+        if (!R) return true;
+        p.idx.resize((size_t)R * L);
+        p.cnt.resize(R);
+        float ms = 0.0f;
+        const int rc = ns_ac_suggest(ctx_, ac_, p.bytes.data(), p.offs.data(), R, L, p.idx.data(), p.cnt.data(), device_ms ? &ms : nullptr);
+        if (rc != NS_OK) { err = std::string("ns_ac_suggest: ") + ns_last_error(ctx_); return false; }
+        dev_ms += ms;
+        for (uint32_t r = 0; r < R; r++) {
+            const size_t q = a + p.rows[r];
+            count[q] = p.cnt[r];
+            std::memcpy(term_idx + q * L, p.idx.data() + (size_t)r * L, (size_t)L * 4);
+        }
+        return true;
+    };
+    suggest_prepare(inputs, 0, Q * 1 / n_sub, max_len, base_len, sp[0], fj);
+    bool ok = true;
+    for (size_t i = 0; i < n_sub && ok; i++) {
+        SuggestPrep& cur = sp[i & 1];
+        if (i + 1 < n_sub) {   // prepare(i + 1) on the host threads while the device answers sub-batch i
+            std::string err;
+            bool dok = true;
+            std::thread dev([&]() { dok = device(i, cur, err); });
+            suggest_prepare(inputs, Q * (i + 1) / n_sub, Q * (i + 2) / n_sub, max_len, base_len, sp[(i + 1) & 1], fj);
+            dev.join();
+            if (!dok) { err_ = err; ok = false; }
+        } else if (!device(i, cur, err_)) {
+            ok = false;
+        }
+    }
+    if (device_ms) *device_ms = dev_ms;
+    return ok;
+}
+
+bool Engine::suggest_text(const std::string& input, int limit, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
+    const QueryView v{input.data(), input.size()};
+    uint32_t idx[nsx::kSuggestMaxLimit], cnt = 0, base_len = 0;
+    if (!suggest_batch(&v, 1, limit, idx, &cnt, &base_len)) { body = err_; return false; }
+    // out["query"], out["limit"], out["suggestions"] (src/api_engine.cpp:174-177), printed by dump(2): keys sorted
+    body.clear();
+    body += "{\n  \"limit\": " + std::to_string(L) + ",\n  \"query\": ";
+    json_escape(body, input);
+    body += ",\n  \"suggestions\": ";
+    if (cnt == 0) {
+        body += "[]";
+    } else {
+        body += "[\n";
+        std::string s;
+        for (uint32_t r = 0; r < cnt; r++) {
+            s.assign(input, 0, base_len);
+            s.append(suggest_table.term(idx[r]), suggest_table.term_len(idx[r]));
+            body += "    ";
+            json_escape(body, s);
+            body += r + 1 < cnt ? ",\n" : "\n";
+        }
+        body += "  ]";
+    }
+    body += "\n}";
+    return true;
+}
+
+std::string Engine::suggest(const std::string& input, int limit) {
+    std::string body;
+    if (!suggest_text(input, limit, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

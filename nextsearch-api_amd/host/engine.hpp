@@ -11,7 +11,10 @@
 //   posting traversal, BM25 term scores, accumulation, top-k, found   src/api_engine.cpp:441-504
 //
 //   result decoration from metadata.csv (title, url, publish_time, author): src/api_engine.cpp:516-531
-// Out of scope here: the three LRU caches, semantic expansion, autocomplete.  There is no CPU scoring path: without a device search*() fails.
+// Autocomplete (include/api_engine.hpp:67, src/api_engine.cpp:91-107,:164-187): suggest() / suggest_batch() answer from
+// a sorted table built at reload() (suggest.hpp) and uploaded to the primary device (csrc/ns_suggest.hip).
+// Out of scope here: the AI overview and AI summary caches.  There is no CPU scoring or autocomplete
+// path: without a device search*() and suggest*() fail.
 #pragma once
 
 #include <cstdint>
@@ -26,6 +29,7 @@
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
+#include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
 
@@ -59,6 +63,11 @@ public:
     // term -> per-segment {byte_off, count, idf}, built at reload() next to the lexicons (term_dict.hpp):
     // the one probe per query term that replaces the reference's per-(term, segment) seg.lex.find + bm25_idf (:454-461)
     nsx::TermDict dict;
+    // autocomplete's sorted (term, score) table (suggest.hpp), rebuilt by every reload(); its device copy lives on the
+    // primary context.  suggest_build_ms: the table's host build (sums, normalising, sort); suggest_upload_ms: its upload
+    // and the device tree build (ns_ac_upload), both of the last reload().
+    nsx::SuggestTable suggest_table;
+    double suggest_build_ms = 0.0, suggest_upload_ms = 0.0;
 
     // device < 0: host-only (index + query preparation; every search call fails loudly)
     explicit Engine(int device = 0);
@@ -132,6 +141,18 @@ public:
     // Staged form used by bench.py: descriptors resident on the device, caller drives ns_batch_*.
     bool prepare(const std::vector<std::string>& queries, int k, uint32_t flags, ns_batch** out);
 
+    // Engine::suggest (include/api_engine.hpp:67, src/api_engine.cpp:164-187): JSON text {"limit", "query",
+    // "suggestions"} in dump(2) layout.  Without a device context it returns {"error": ...} (suggest_text: the failure
+    // visible to the caller, body = the message).
+    std::string suggest(const std::string& input, int limit);
+    bool suggest_text(const std::string& input, int limit, std::string& body);
+    // A batch of suggest requests with flat, caller-owned outputs: for input q, L = clamp(limit, 1, 10) entries
+    // term_idx[q * L + r] (rows of suggest_table, best first, ~0u past count[q]) and base_len[q]: suggestion r is
+    // input[0, base_len[q]) + suggest_table term term_idx[q * L + r].  A large batch is cut into sub-batches whose host
+    // preparation overlaps the device's work on the previous one.  device_ms (may be null): summed kernel time.
+    bool suggest_batch(const QueryView* inputs, size_t Q, int limit, uint32_t* term_idx, uint32_t* count, uint32_t* base_len,
+                       float* device_ms = nullptr);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -172,6 +193,7 @@ private:
     mutable bool refs_failed_ = false;   // build_refs could not run the device part of the expansion (err_ says why)
     int device_;
     ns_ctx* ctx_ = nullptr;
+    ns_ac* ac_ = nullptr;    // suggest_table on ctx_ (ns_ac_upload)
     std::vector<ns_seg*> dev_segs_;
     // further devices holding a replica of the index (multi-device engine): context + segments each
     struct Replica { int device = 0; ns_ctx* ctx = nullptr; std::vector<ns_seg*> segs; };

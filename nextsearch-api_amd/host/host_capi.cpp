@@ -391,3 +391,54 @@ extern "C" int nsh_engine_prepare(nsh_engine* e, const char* const* queries, uin
     return 0;
 } NSH_CATCH(e, "nsh_engine_prepare", -1)
 }
+
+// ---- autocomplete ----------------------------------------------------------------------------
+extern "C" int nsh_engine_suggest_json(nsh_engine* e, const char* input, uint64_t input_len, int limit, char** json_out) { try {
+    if (!e || !json_out || (input_len && !input)) return -1;
+    std::string s;
+    const bool ok = e->eng.suggest_text(std::string(input ? input : "", (size_t)input_len), limit, s);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); *json_out = nullptr; return -1; }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_suggest_json", -1)
+}
+
+extern "C" int nsh_engine_suggest_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_inputs, int limit,
+                                        uint32_t* term_idx, uint32_t* count, uint32_t* base_len, float* device_ms) { try {
+    if (!e || (n_inputs && (!offsets || !term_idx || !count || !base_len))) return -1;
+    std::vector<nextsearch::Engine::QueryView> views(n_inputs);
+    for (uint32_t q = 0; q < n_inputs; q++) {
+        if (offsets[q + 1] < offsets[q] || (offsets[q + 1] > offsets[q] && !bytes)) { nsh_set_err(e, "nsh_engine_suggest_batch: bad offsets"); return -1; }
+        views[q] = {bytes ? bytes + offsets[q] : "", (size_t)(offsets[q + 1] - offsets[q])};
+    }
+    if (!e->eng.suggest_batch(views.data(), n_inputs, limit, term_idx, count, base_len, device_ms)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_suggest_batch", -1)
+}
+
+extern "C" int nsh_engine_suggest_table(nsh_engine* e, const char** pool, const uint64_t** offsets, const uint32_t** scores,
+                                        uint64_t* n_terms, double* build_ms, double* upload_ms) { try {
+    if (!e) return -1;
+    const auto& t = e->eng.suggest_table;
+    if (pool) *pool = t.pool.data();
+    if (offsets) *offsets = t.off.data();
+    if (scores) *scores = t.score.data();
+    if (n_terms) *n_terms = t.size();
+    if (build_ms) *build_ms = e->eng.suggest_build_ms;
+    if (upload_ms) *upload_ms = e->eng.suggest_upload_ms;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_suggest_table", -1)
+}
+
+extern "C" uint64_t nsh_suggest_split(const char* input, uint64_t input_len, uint64_t* base_len, char* prefix, uint64_t cap) {
+    size_t b = 0;
+    std::string p;
+    nsx::split_suggest_input(input ? input : "", input ? (size_t)input_len : 0, b, p);
+    if (base_len) *base_len = b;
+    if (prefix && cap) std::memcpy(prefix, p.data(), std::min<size_t>(p.size(), (size_t)cap));
+    return p.size();
+}
+
+extern "C" int nsh_suggest_clamp_limit(int limit) { return nsx::clamp_suggest_limit(limit); }

@@ -61,6 +61,7 @@ HIP_SYMBOLS = [
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
     "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores",
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
+    "ns_ac_upload", "ns_ac_suggest", "ns_ac_release",
 ]
 HOST_SYMBOLS = [
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -70,6 +71,7 @@ HOST_SYMBOLS = [
     "nsh_engine_search_batch", "nsh_engine_prepare", "nsh_engine_doc_metadata", "nsh_engine_hits_to_json", "nsh_engine_search_batch_json",
     "nsh_engine_build_impacts", "nsh_engine_use_impacts", "nsh_engine_build_packed", "nsh_engine_use_packed", "nsh_engine_build_blockmax", "nsh_engine_use_pruning", "nsh_engine_use_merge", "nsh_engine_share_scores", "nsh_engine_use_skips", "nsh_invert_segment", "nsh_invert_error",
     "nsh_engine_semantic_info", "nsh_engine_expand", "nsh_engine_semantic_row", "nsh_engine_set_cache", "nsh_engine_cache_size",
+    "nsh_engine_suggest_json", "nsh_engine_suggest_batch", "nsh_engine_suggest_table", "nsh_suggest_split", "nsh_suggest_clamp_limit",
 ]
 
 _hip = None
@@ -88,6 +90,9 @@ def hip_lib():
         L.ns_ctx_destroy.argtypes = [vp]
         L.ns_ctx_destroy.restype = None
         L.ns_ctx_set_stream.argtypes = [vp, vp]
+        L.ns_ac_upload.argtypes = [vp, vp, vp, vp, u32, C.POINTER(vp)]
+        L.ns_ac_suggest.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, C.POINTER(C.c_float)]
+        L.ns_ac_release.argtypes = [vp, vp]
         L.ns_last_error.argtypes = [vp]
         L.ns_last_error.restype = C.c_char_p
         L.ns_device_name.argtypes = [vp]
@@ -203,6 +208,14 @@ def host_lib():
         L.nsh_engine_use_merge.restype = None
         L.nsh_engine_share_scores.argtypes = [vp, i32]
         L.nsh_engine_share_scores.restype = None
+        L.nsh_engine_suggest_json.argtypes = [vp, C.c_char_p, u64, i32, C.POINTER(vp)]
+        L.nsh_engine_suggest_batch.argtypes = [vp, C.c_char_p, vp, u32, i32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_suggest_table.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double)]
+        L.nsh_suggest_split.argtypes = [C.c_char_p, u64, C.POINTER(u64), C.c_char_p, u64]
+        L.nsh_suggest_split.restype = u64
+        L.nsh_suggest_clamp_limit.argtypes = [i32]
+        L.nsh_suggest_clamp_limit.restype = i32
         _host = L
     return _host
 
@@ -446,6 +459,60 @@ class Engine:
         _LIVE_BATCHES.setdefault(_ctx_key(self.ctx), weakref.WeakSet()).add(bt)
         return bt
 
+    def suggest_json(self, user_input, limit):
+        """Engine::suggest(input, limit).dump(2) as bytes (the input: str or raw bytes)."""
+        b = _as_bytes(user_input)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_suggest_json(self.h, b, len(b), int(limit), C.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"suggest failed: {self.error()}")
+        s = C.string_at(out)
+        self._L.nsh_free(out)
+        return s
+
+    def suggest_batch_raw(self, inputs, limit, flat=None):
+        """-> (term_idx uint32 [Q, L], count uint32 [Q], base_len uint32 [Q], kernel ms); flat: flat_inputs(inputs), when
+        the caller flattens the batch once for many calls"""
+        data, offs = flat if flat is not None else _flat_bytes(inputs)
+        Q, L = len(inputs), clamp_suggest_limit(limit)
+        idx = np.empty((Q, L), dtype=np.uint32)
+        cnt = np.empty(Q, dtype=np.uint32)
+        base = np.empty(Q, dtype=np.uint32)
+        ms = C.c_float(0.0)
+        rc = self._L.nsh_engine_suggest_batch(self.h, data, offs.ctypes.data, Q, int(limit), idx.ctypes.data, cnt.ctypes.data,
+                                              base.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"suggest_batch failed: {self.error()}")
+        return idx, cnt, base, ms.value
+
+    def suggest_table(self):
+        """-> (terms: list of bytes, scores: uint32 array, build ms) of the sorted table the last reload built"""
+        pool, offs, sc, n, ms = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_double()
+        if self._L.nsh_engine_suggest_table(self.h, C.byref(pool), C.byref(offs), C.byref(sc), C.byref(n), C.byref(ms), None) != 0:
+            raise RuntimeError(f"suggest_table failed: {self.error()}")
+        n = n.value
+        o = np.ctypeslib.as_array(C.cast(offs, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        raw = C.string_at(pool, int(o[n])) if n else b""
+        scores = np.ctypeslib.as_array(C.cast(sc, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        return [raw[int(o[i]):int(o[i + 1])] for i in range(n)], scores, ms.value
+
+    def suggest_build_times(self):
+        """-> (host build ms, upload + device tree build ms) of the suggest table in the last reload"""
+        b, u = C.c_double(), C.c_double()
+        if self._L.nsh_engine_suggest_table(self.h, None, None, None, None, C.byref(b), C.byref(u)) != 0:
+            raise RuntimeError(f"suggest_table failed: {self.error()}")
+        return b.value, u.value
+
+    def suggest_batch(self, inputs, limit, table=None):
+        """-> one list of suggestions (bytes) per input; `table` = suggest_table()[0] (fetched when omitted)"""
+        terms = table if table is not None else self.suggest_table()[0]
+        idx, cnt, base, _ = self.suggest_batch_raw(inputs, limit)
+        out = []
+        for q, s in enumerate(inputs):
+            b = _as_bytes(s)[:int(base[q])]
+            out.append([b + terms[int(i)] for i in idx[q, :int(cnt[q])]])
+        return out
+
     def set_cache(self, on):
         self._L.nsh_engine_set_cache(self.h, 1 if on else 0)
 
@@ -582,6 +649,69 @@ def pipelined_search(ctx, batches, k, flags=NS_FLAG_OR, out=None, timed=False, d
             yield collect(*flight.popleft())
     while flight:
         yield collect(*flight.popleft())
+
+
+def clamp_suggest_limit(limit):
+    return max(1, min(int(limit), 10))
+
+
+def suggest_split(user_input):
+    """-> (base bytes, prefix bytes): the host library's split of a suggest request"""
+    b = _as_bytes(user_input)
+    base = C.c_uint64(0)
+    buf = C.create_string_buffer(len(b) + 1)
+    n = host_lib().nsh_suggest_split(b, len(b), C.byref(base), buf, len(b) + 1)
+    return b[:base.value], buf.raw[:n]
+
+
+def _as_bytes(s):
+    return s.encode("utf-8") if isinstance(s, str) else bytes(s)
+
+
+def _flat_bytes(items):
+    """(concatenated bytes, uint64 offsets[n + 1]) of a list of str / bytes"""
+    bs = [_as_bytes(x) for x in items]
+    offs = np.zeros(len(bs) + 1, dtype=np.uint64)
+    if bs:
+        offs[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    return b"".join(bs), offs
+
+
+def flat_inputs(items):
+    """(bytes, uint64 offsets) of a batch of suggest inputs, for Engine.suggest_batch_raw(..., flat=)"""
+    return _flat_bytes(items)
+
+
+class AcTable:
+    """Raw ns_ac_* on a ctx: a sorted dictionary (list of bytes, byte order) with u32 scores.  close() before the ctx."""
+
+    def __init__(self, ctx, terms, scores):
+        self.ctx = ctx
+        pool, offs = _flat_bytes(terms)
+        sc = np.ascontiguousarray(scores, dtype=np.uint32)
+        h = C.c_void_p()
+        self.rc = hip_lib().ns_ac_upload(ctx, pool if pool else None, offs.ctypes.data, sc.ctypes.data if len(sc) else None,
+                                         len(terms), C.byref(h))
+        self.h = h if self.rc == NS_OK else None
+
+    def suggest(self, prefixes, L):
+        """-> (idx uint32 [n_q, L], count uint32 [n_q], kernel ms); raises on failure"""
+        data, offs = _flat_bytes(prefixes)
+        offs32 = offs.astype(np.uint32)
+        n_q = len(prefixes)
+        idx = np.empty((n_q, max(int(L), 1)), dtype=np.uint32)
+        cnt = np.empty(n_q, dtype=np.uint32)
+        ms = C.c_float(0.0)
+        rc = hip_lib().ns_ac_suggest(self.ctx, self.h, data if data else None, offs32.ctypes.data, n_q, int(L), idx.ctypes.data,
+                                     cnt.ctypes.data, C.byref(ms))
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_ac_suggest rc={rc}: {hip_lib().ns_last_error(self.ctx).decode()}")
+        return idx, cnt, ms.value
+
+    def close(self):
+        if self.h:
+            hip_lib().ns_ac_release(self.ctx, self.h)
+            self.h = None
 
 
 def search_batch_raw(ctx, qd, refs, k, flags=NS_FLAG_OR):
