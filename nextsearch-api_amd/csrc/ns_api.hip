@@ -9,18 +9,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <numeric>
 #include <string>
-#include <thread>
-#include <map>
 #include <vector>
 
 #include "../../include/nextsearch_hip.h"
 #include "ns_internal.h"
-#include "ns_forkjoin.hpp"
+#include "ns_plan.hpp"
 #include "ns_kernels.hip"
 #include "ns_wave_kernel.hip"
 #include "ns_driver_kernel.hip"
@@ -35,9 +29,6 @@ using namespace ns;
 
 static_assert(sizeof(ns_hit) == sizeof(Hit), "ns_hit layout");
 
-
-struct ns_prep;
-static void prep_free(ns_prep* p);
 
 // ------------------------------------------------------------------------------------------------
 struct ns_seg {
@@ -65,69 +56,19 @@ struct ns_seg {
     uint16_t* d_nidx = nullptr;
     float* d_ntab = nullptr;
     uint32_t n_norms = 0;
-    // Optional impact stream (ns_segment_build_impacts): {docId, term score bits} per posting of the registered lists,
-    // index-aligned with d_postings.  `imp_tab`: open-addressed (first posting index -> count, idf bits) of those lists.
+    // Optional impact stream (ns_segment_build_impacts): {docId, term score bits} per posting of the registered lists
+    // (lists.imp), index-aligned with d_postings.
     uint2* d_impacts = nullptr;
-    struct ImpList { uint32_t first = 0xFFFFFFFFu, count = 0, idf_bits = 0; };
-    std::vector<ImpList> imp_tab;   // size is a power of two (or 0)
-    size_t imp_lists = 0;
-    // Optional skip tables (ns_segment_build_skips; DevSeg::skips): `skip_tab` maps a list's first posting index to its count and
-    // to the index of its first table entry; every table has skip_entries() entries.
+    // Optional skip tables (ns_segment_build_skips; DevSeg::skips): every registered list (lists.skip) has skip_entries() entries.
     uint32_t* d_skips = nullptr;
     std::vector<uint32_t*> skip_retired;    // outgrown blocks: batches prepared before the growth still point into them
     uint64_t skip_cap = 0, skip_used = 0;   // entries allocated / in use
-    struct SkipList { uint32_t first = 0xFFFFFFFFu, count = 0, entry = 0; };
-    std::vector<SkipList> skip_tab;   // open-addressed, size a power of two (or 0)
-    size_t skip_lists = 0;
     uint32_t skip_entries() const { return (n_docs + kSkipDocs - 1) / kSkipDocs + 2; }
-    // 1 + index of the first table entry of the list [first, first + count), or 0
-    uint32_t skip_of(uint32_t first, uint32_t count) const {
-        if (skip_tab.empty()) return 0;
-        const size_t mask = skip_tab.size() - 1;
-        for (size_t h = ((size_t)first * 0x9E3779B1u) & mask;; h = (h + 1) & mask) {
-            const SkipList& e = skip_tab[h];
-            if (e.first == first) return e.count == count ? e.entry + 1u : 0u;
-            if (e.first == 0xFFFFFFFFu) return 0;
-        }
-    }
-    // Optional block maxima (ns_segment_build_blockmax; DevSeg::blockmax): per registered list ceil(count / 256) fp32 values.
+    // Optional block maxima (ns_segment_build_blockmax; DevSeg::blockmax): per registered list (lists.bmx) ceil(count / 256) fp32 values.
     float* d_blockmax = nullptr;
     std::vector<float*> bmx_retired;         // outgrown blocks: batches prepared before the growth still point into them
     uint64_t bmx_cap = 0, bmx_used = 0;      // entries allocated / in use
-    struct BmxList { uint32_t first = 0xFFFFFFFFu, count = 0, idf_bits = 0, entry = 0; };
-    std::vector<BmxList> bmx_tab;            // open-addressed, size a power of two (or 0)
-    // 1 + index of the first block maximum of the list [first, first + count) built with this idf, or 0
-    uint32_t bmx_of(uint32_t first, uint32_t count, uint32_t idf_bits) const {
-        if (bmx_tab.empty()) return 0;
-        const size_t mask = bmx_tab.size() - 1;
-        for (size_t h = ((size_t)first * 0x9E3779B1u) & mask;; h = (h + 1) & mask) {
-            const BmxList& e = bmx_tab[h];
-            if (e.first == first) return (e.count == count && e.idf_bits == idf_bits) ? e.entry + 1u : 0u;
-            if (e.first == 0xFFFFFFFFu) return 0;
-        }
-    }
-    // Shared term scores (ns_ctx_share_scores): every list a sharing batch ever built into d_impacts, first -> count.  Lists
-    // that overlap another one are refused (two builders would write the same postings with different values).
-    std::map<uint32_t, uint32_t> share_lists;
-    bool share_admit(uint32_t first, uint32_t count) {
-        auto it = share_lists.lower_bound(first);
-        if (it != share_lists.end() && (it->first == first ? it->second != count : (uint64_t)first + count > it->first)) return false;
-        if (it != share_lists.begin() && (it == share_lists.end() || it->first != first)) {
-            auto pv = std::prev(it);
-            if ((uint64_t)pv->first + pv->second > first) return false;
-        }
-        share_lists.emplace(first, count);
-        return true;
-    }
-    bool imp_has(uint32_t first, uint32_t count, uint32_t idf_bits) const {
-        if (imp_tab.empty()) return false;
-        const size_t mask = imp_tab.size() - 1;
-        for (size_t h = ((size_t)first * 0x9E3779B1u) & mask;; h = (h + 1) & mask) {
-            const ImpList& e = imp_tab[h];
-            if (e.first == first) return e.count == count && e.idf_bits == idf_bits;
-            if (e.first == 0xFFFFFFFFu) return false;
-        }
-    }
+    SegLists lists;   // the host side of the three above and of the shared term scores (ns_plan.hpp)
 };
 
 struct ns_ctx {
@@ -148,12 +89,8 @@ struct ns_ctx {
     bool overlap = false, flip = false;
     std::string err;
     std::string devname;
-    int n_cus = 0;
     std::vector<ns_seg*> segs;   // indexed by seg_id
     std::vector<ns_seg*> pending_uploads;   // begun (ns_segment_upload_begin), not yet ended or released: freed with the ctx
-    uint32_t variant = 0;
-    uint32_t min_items = 0;
-    uint32_t split_postings = 0;
     // Pinned staging: a batch's descriptor arrays go up in ONE copy and its three result arrays come down in
     // ONE copy (a lone query is otherwise dominated by ten small pageable copies and the syncs they imply).
     void* h_up = nullptr;
@@ -168,33 +105,9 @@ struct ns_ctx {
     // pinned result buffers for batches in flight (NS_RUN_FETCH): one per batch between its run and its fetch
     struct DownSlot { void* p = nullptr; size_t cap = 0; bool busy = false; };
     std::vector<DownSlot> down_slots;
-    // Shared term scores (ns_ctx_share_scores): 0 off; 1 a batch whose term refs name each distinct list often enough computes
-    // every list's BM25 term scores ONCE (k_share_scores, in front of the scoring kernel, on every run) and scores from
-    // {docId, score}; 2 every batch that can (tests).  The registry maps (segment, first posting) to the list's count and idf and
-    // to the last batch that listed it; `live_shared` counts the sharing batches alive: an idf may only change while it is 0.
-    int share_mode = 1;
-    uint32_t share_ratio = 48;           // share when postings >= share_ratio x distinct postings (below ~50 uses per posting the extra kernel costs what it saves) ...
-    uint64_t share_min_postings = 4u << 20;   // ... and the batch scans at least this many postings
-    struct ShareEnt { uint64_t key = ~0ull; uint32_t count = 0, idf_bits = 0, epoch = 0; bool bad = false; };
-    std::vector<ShareEnt> share_tab;     // open-addressed, size a power of two (or 0)
-    size_t share_n = 0;
-    uint32_t share_epoch = 0;
-    uint32_t live_shared = 0;
-    bool use_impacts = true;   // batches take the impact stream when every list they touch has one (ns_ctx_use_impacts)
-    int use_packed = 1;        // 0 off; 1, 2: batches read the packed stream when every segment they touch has one (ns_ctx_use_packed)
-    bool use_skips = true;     // doc-tile groups walk the skip grid when their lists have skip tables (ns_ctx_use_skips)
-    bool use_merge = true;     // general-class groups of exactly two term refs take the two-list merge body (ns_ctx_use_merge)
-    uint32_t merge_ratio = 8;  // ... when the longer list is at most this many times the shorter (NS_MERGE_RATIO: sweeps)
-    bool use_pruning = false;  // single-term groups whose list has block maxima skip the blocks that cannot enter the top-K (ns_ctx_use_pruning)
-    ns_prep* prep = nullptr;   // ns_batch_prepare's host threads and per-thread scratch, kept from batch to batch
-    unsigned prep_threads = 0; // 0 = automatic (up to 8); 1 = prepare on the calling thread only (ns_ctx_set_host_threads)
-    // Launch order inside coarse run-time classes (see "XCD dealing" in ns_batch_prepare): 1 = on.  The environment variables
-    // NS_ORDER_MODE (0 = off) / NS_ORDER_COARSE (log2 of the fine buckets per class) override it for experiments; read at
-    // ns_ctx_create.
-    int order_mode = 1, order_coarse = 3;
-    uint32_t key_pct[4] = {100, 100, 100, 100};   // launch-order key of general / thin / tile / merge items in per cent (NS_KEY_PCT=g,t,d,m: sweeps)
-    uint32_t tile_dens64 = 16;   // doc-tile class from this many postings per 64 docs (0.25 per doc); NS_TILE_DENS64 overrides (sweeps)
-    bool order_coarse_forced = false;   // NS_ORDER_COARSE given: no automatic choice
+    PlanSettings cfg;      // what ns_batch_prepare's planner reads: ns_set_tuning, ns_ctx_use_*, ns_ctx_share_scores, the sweep knobs
+    ShareRegistry share;   // every list a sharing batch built (ns_ctx_share_scores) and the sharing batches alive
+    BatchPlan plan;        // ns_batch_prepare's host threads and per-thread scratch, kept from batch to batch
     std::vector<ns_ac*> acs;   // autocomplete tables (ns_ac_upload): owned by the ctx, freed by ns_ac_release or ns_ctx_destroy
 };
 
@@ -204,12 +117,10 @@ static void seg_free_device_fwd(ns_seg* s);
 static void seg_free_staging_fwd(ns_seg* s);
 
 static int fail(ns_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof(buf), fmt, ap);
+    (ctx ? ctx->err : g_create_err) = vformat(fmt, ap);
     va_end(ap);
-    if (ctx) ctx->err = buf; else g_create_err = buf;
     return code;
 }
 
@@ -219,40 +130,6 @@ static int fail(ns_ctx* ctx, int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                                     \
             return fail((ctx), NS_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-// Kernel variants (DESIGN.md "kernel variants").
-//   wave variants: hb = table entries per wave (k_dscore) or docs per tile (k_tscore)
-//   workgroup variants (k_score, the >64-terms fallback and the round-1 baseline): threads per
-//   workgroup, slots per thread, postings per thread per round; tile_docs = nt * spt.
-struct VariantDesc { uint32_t hb; uint32_t nt, spt, u; uint32_t d; };
-static const VariantDesc kVariants[] = {
-    {512, 512, 12, 4, 0},       // 0: default = AUTO: k_uscore, per (query, segment) group the driver-stream body (64 or 192 foreign postings per super-batch) or 1024-doc tiles, by its mix of lists
-    {0, 1024, 12, 4, 0},        // 1: workgroup kernel, 12288-doc tiles
-    {0, 512, 12, 4, 0},         // 2: workgroup kernel,  6144-doc tiles
-    {0, 256, 16, 4, 0},         // 3: workgroup kernel,  4096-doc tiles
-    {0, 512, 16, 8, 0},         // 4: workgroup kernel,  8192-doc tiles
-    {0, 0, 0, 0, 0},            // 5..11: retired in round 2 (the wave-private batch kernel k_wscore); ns_set_tuning rejects them
-    {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0},
-    {512, 512, 12, 4, 0},       // 12: driver-stream kernel (k_dscore), 512 slots, 128 foreign postings per super-batch   [d == 0 marks k_dscore]
-    {256, 512, 12, 4, 0},       // 13: k_dscore  256 slots /  64 foreign
-    {1024, 512, 12, 4, 0},      // 14: k_dscore 1024 slots / 256 foreign
-    {512, 512, 12, 4, 0},       // 15: k_dscore  512 slots /  64 foreign
-    {512, 512, 12, 4, 0},       // 16: k_dscore  512 slots / 256 foreign
-    {1024, 512, 12, 4, 0},      // 17: k_dscore 1024 slots / 128 foreign
-    {512, 512, 12, 4, 1},       // 18: doc-tile kernel k_tscore for every group, 512-doc tiles   [d == 1 marks k_tscore]
-    {1024, 512, 12, 4, 1},      // 19: k_tscore, 1024-doc tiles
-    {2048, 512, 12, 4, 1},      // 20: k_tscore, 2048-doc tiles
-};
-static constexpr uint32_t kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-static constexpr uint32_t kWaveMaxTerms = 64;
-static constexpr uint32_t kDefaultSplitPostings = 32768;   // forced variants: postings per work item
-// auto mode: work units per item (one unit = one streamed driver posting).  Every item pays for its own
-// top-K warm-up and its K-row partial result, so large K wants fewer, longer items (sweeps: profiles/r01).
-static constexpr uint32_t kSplitWorkSmallK = 98304, kSplitWorkLargeK = 131072;
-static constexpr uint64_t kWorkForeign = 8, kWorkTile = 2, kWorkMerge = 4;   // merge: fitted on two-list laws (profiles/r03): 1.0 ps per unit, like the general class
-static constexpr uint32_t kSkipMinCount = 64;   // shorter lists are never looked up in the skip registry (ns_segment_build_skips)
-// per-item, per-term constants of the launch-order key (fitted to per-item timestamps, tools/dbg/item_times.py)
-static constexpr uint64_t kItemTermGeneral = 4000, kItemTermThin = 3000, kItemTermTile = 8000;   // general re-fitted in round 2 (10000 -> 4000: ab16)
 
 template <int HK, int FB>
 static void launch_dscore(bool and_mode, uint32_t n_items, hipStream_t st, const DevWItem* items, const DevTerm* terms,
@@ -302,7 +179,7 @@ extern "C" int ns_ctx_create(int device, ns_ctx** out) {
     ns_ctx* ctx = new ns_ctx();
     ctx->device = device;
     ctx->devname = std::string(prop.gcnArchName) + " " + prop.name;
-    ctx->n_cus = prop.multiProcessorCount;
+    ctx->cfg.n_cus = prop.multiProcessorCount;
     e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         int rc = fail(nullptr, NS_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
@@ -310,18 +187,18 @@ extern "C" int ns_ctx_create(int device, ns_ctx** out) {
         return rc;
     }
     ctx->stream = ctx->own_stream;
-    if (const char* om = std::getenv("NS_ORDER_MODE")) ctx->order_mode = std::atoi(om);
+    if (const char* om = std::getenv("NS_ORDER_MODE")) ctx->cfg.order_mode = std::atoi(om);
     if (const char* kp = std::getenv("NS_KEY_PCT")) {
         unsigned a = 100, b = 100, c = 100, d = 100;
-        if (std::sscanf(kp, "%u,%u,%u,%u", &a, &b, &c, &d) >= 1) { ctx->key_pct[0] = a; ctx->key_pct[1] = b; ctx->key_pct[2] = c; ctx->key_pct[3] = d; }
+        if (std::sscanf(kp, "%u,%u,%u,%u", &a, &b, &c, &d) >= 1) { ctx->cfg.key_pct[0] = a; ctx->cfg.key_pct[1] = b; ctx->cfg.key_pct[2] = c; ctx->cfg.key_pct[3] = d; }
     }
-    if (const char* td = std::getenv("NS_TILE_DENS64")) ctx->tile_dens64 = (uint32_t)std::max(1, std::atoi(td));
-    if (const char* um = std::getenv("NS_MERGE")) ctx->use_merge = std::atoi(um) != 0;
-    if (const char* mr = std::getenv("NS_MERGE_RATIO")) ctx->merge_ratio = (uint32_t)std::max(1, std::atoi(mr));
-    if (const char* sm = std::getenv("NS_SHARE")) ctx->share_mode = std::max(0, std::min(2, std::atoi(sm)));
-    if (const char* sr = std::getenv("NS_SHARE_RATIO")) ctx->share_ratio = (uint32_t)std::max(1, std::atoi(sr));
-    if (const char* sp = std::getenv("NS_SHARE_MIN")) ctx->share_min_postings = (uint64_t)std::max(0ll, std::atoll(sp));
-    if (const char* oc = std::getenv("NS_ORDER_COARSE")) { ctx->order_coarse = std::max(0, std::min(11, std::atoi(oc))); ctx->order_coarse_forced = true; }
+    if (const char* td = std::getenv("NS_TILE_DENS64")) ctx->cfg.tile_dens64 = (uint32_t)std::max(1, std::atoi(td));
+    if (const char* um = std::getenv("NS_MERGE")) ctx->cfg.use_merge = std::atoi(um) != 0;
+    if (const char* mr = std::getenv("NS_MERGE_RATIO")) ctx->cfg.merge_ratio = (uint32_t)std::max(1, std::atoi(mr));
+    if (const char* sm = std::getenv("NS_SHARE")) ctx->cfg.share_mode = std::max(0, std::min(2, std::atoi(sm)));
+    if (const char* sr = std::getenv("NS_SHARE_RATIO")) ctx->cfg.share_ratio = (uint32_t)std::max(1, std::atoi(sr));
+    if (const char* sp = std::getenv("NS_SHARE_MIN")) ctx->cfg.share_min_postings = (uint64_t)std::max(0ll, std::atoll(sp));
+    if (const char* oc = std::getenv("NS_ORDER_COARSE")) { ctx->cfg.order_coarse = std::max(0, std::min(11, std::atoi(oc))); ctx->cfg.order_coarse_forced = true; }
     if (hipStreamCreateWithFlags(&ctx->alt_stream, hipStreamNonBlocking) != hipSuccess) { ctx->alt_stream = nullptr; (void)hipGetLastError(); }
     {
         int lo_pri = 0, hi_pri = 0;
@@ -357,7 +234,6 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->alt_stream) (void)hipStreamDestroy(ctx->alt_stream);
     if (ctx->pull_stream) (void)hipStreamDestroy(ctx->pull_stream);
-    prep_free(ctx->prep);
     delete ctx;
 }
 
@@ -379,9 +255,9 @@ extern "C" int ns_set_tuning(ns_ctx* ctx, uint32_t variant, uint32_t min_items, 
     // parity tests and for sweeps: `make -C nextsearch-api_amd variants` builds libnextsearch_hip_variants.so with them.
     if (variant != 0) return fail(ctx, NS_E_INVAL, "kernel variant %u exists only in the variants build (make -C nextsearch-api_amd variants)", variant);
 #endif
-    ctx->variant = variant;
-    ctx->min_items = min_items;
-    ctx->split_postings = split_postings;
+    ctx->cfg.variant = variant;
+    ctx->cfg.min_items = min_items;
+    ctx->cfg.split_postings = split_postings;
     return NS_OK;
 }
 
@@ -419,8 +295,8 @@ static void seg_free_device(ns_seg* s) {
     (void)hipFree(s->d_blockmax);
     for (float* p : s->bmx_retired) (void)hipFree(p);
     s->bmx_retired.clear();
-    s->d_blockmax = nullptr; s->bmx_cap = s->bmx_used = 0; s->bmx_tab.clear();
-    s->d_skips = nullptr; s->skip_cap = s->skip_used = 0; s->skip_tab.clear(); s->skip_lists = 0;
+    s->d_blockmax = nullptr; s->bmx_cap = s->bmx_used = 0; s->lists.bmx.clear();
+    s->d_skips = nullptr; s->skip_cap = s->skip_used = 0; s->lists.skip.clear();
     s->d_postings = nullptr; s->d_norm = nullptr; s->d_pnorm = nullptr; s->d_impacts = nullptr; s->d_packed = nullptr;
     s->d_pk_hdr = nullptr; s->d_pk_scores = nullptr; s->d_nidx = nullptr; s->d_ntab = nullptr;
 }
@@ -599,19 +475,7 @@ extern "C" int ns_segment_release(ns_ctx* ctx, ns_seg* seg) {
     seg_free_device(seg);
     // the shared-score registry forgets the segment's lists: a later segment under the same id starts with an empty interval map
     // and must see every one of its lists as new (that is when overlaps are checked)
-    if (!seg->pending && ctx->share_n) {
-        std::vector<ns_ctx::ShareEnt> kept(ctx->share_tab.size());
-        const size_t m = kept.size() - 1;
-        size_t n = 0;
-        for (const auto& en : ctx->share_tab)
-            if (en.key != ~0ull && (uint32_t)(en.key >> 32) != seg->id) {
-                size_t h = (size_t)((en.key * 0x9E3779B97F4A7C15ull) >> 20) & m;
-                while (kept[h].key != ~0ull) h = (h + 1) & m;
-                kept[h] = en; n++;
-            }
-        ctx->share_tab.swap(kept);
-        ctx->share_n = n;
-    }
+    if (!seg->pending) ctx->share.tab.erase_if([&](uint64_t key, const ShareRegistry::Ent&) { return (uint32_t)(key >> 32) == seg->id; });
     if (!seg->pending) ctx->segs[seg->id] = nullptr;
     else ctx->pending_uploads.erase(std::remove(ctx->pending_uploads.begin(), ctx->pending_uploads.end(), seg), ctx->pending_uploads.end());
     delete seg;
@@ -658,23 +522,29 @@ __global__ void __launch_bounds__(256) k_build_impacts(const uint2* __restrict__
     }
 }
 
+// the lists [byte_off / 8, + count) given to a ns_segment_build_* call: byte offsets a multiple of 8, lists inside the segment
+static int check_lists(ns_ctx* ctx, const ns_seg* seg, const uint64_t* byte_off, const uint32_t* counts, uint32_t n_lists) {
+    for (uint32_t i = 0; i < n_lists; i++) {
+        if (byte_off[i] % 8 != 0) return fail(ctx, NS_E_INVAL, "list %u: byte offset %llu is not a multiple of 8", i, (unsigned long long)byte_off[i]);
+        if (byte_off[i] / 8 + counts[i] > seg->n_postings) return fail(ctx, NS_E_INVAL, "list %u runs past the segment's postings", i);
+    }
+    return NS_OK;
+}
+
 extern "C" int ns_segment_build_impacts(ns_ctx* ctx, ns_seg* seg, const uint64_t* byte_off, const uint32_t* counts,
                                         const float* idfs, uint32_t n_lists) {
     if (!ctx || !seg) return fail(ctx, NS_E_INVAL, "ns_segment_build_impacts: null argument");
     if (seg->id >= ctx->segs.size() || ctx->segs[seg->id] != seg) return fail(ctx, NS_E_INVAL, "segment does not belong to this ctx");
     if (n_lists && (!byte_off || !counts || !idfs)) return fail(ctx, NS_E_INVAL, "null list arrays");
     if (!n_lists || !seg->n_postings) return NS_OK;
-    if (ctx->live_shared) return fail(ctx, NS_E_STATE, "ns_segment_build_impacts: %u batch(es) that compute shared term scores into the same buffer are alive; destroy them first", ctx->live_shared);
+    if (ctx->share.live) return fail(ctx, NS_E_STATE, "ns_segment_build_impacts: %u batch(es) that compute shared term scores into the same buffer are alive; destroy them first", ctx->share.live);
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_lists(ctx, seg, byte_off, counts, n_lists)) return rc;
     struct L { uint32_t first, count; float idf; };
     std::vector<L> lists;
     lists.reserve(n_lists);
-    for (uint32_t i = 0; i < n_lists; i++) {
-        if (byte_off[i] % 8 != 0) return fail(ctx, NS_E_INVAL, "list %u: byte offset %llu is not a multiple of 8", i, (unsigned long long)byte_off[i]);
-        const uint64_t first = byte_off[i] / 8;
-        if (first + counts[i] > seg->n_postings) return fail(ctx, NS_E_INVAL, "list %u runs past the segment's postings", i);
-        if (counts[i]) lists.push_back({(uint32_t)first, counts[i], idfs[i]});
-    }
+    for (uint32_t i = 0; i < n_lists; i++)
+        if (counts[i]) lists.push_back({(uint32_t)(byte_off[i] / 8), counts[i], idfs[i]});
     std::sort(lists.begin(), lists.end(), [](const L& a, const L& b) { return a.first < b.first; });
     for (size_t i = 1; i < lists.size(); i++)
         if (lists[i - 1].first + (uint64_t)lists[i - 1].count > lists[i].first) return fail(ctx, NS_E_INVAL, "lists overlap at posting %u", lists[i].first);
@@ -704,22 +574,10 @@ extern "C" int ns_segment_build_impacts(ns_ctx* ctx, ns_seg* seg, const uint64_t
     (void)hipFree(d_tmp);
     if (e == hipSuccess) e = seg_fill_pk_scores(ctx, seg);
     if (e != hipSuccess) return fail(ctx, NS_E_HIP, "ns_segment_build_impacts: %s", hipGetErrorString(e));
-    // registry: old entries + new ones (a list given again replaces its entry)
-    std::vector<ns_seg::ImpList> all;
-    for (const auto& t : seg->imp_tab) if (t.first != 0xFFFFFFFFu) all.push_back(t);
-    for (const auto& l : lists) { ns_seg::ImpList t; t.first = l.first; t.count = l.count; std::memcpy(&t.idf_bits, &l.idf, 4); all.push_back(t); }
-    size_t cap = 16;
-    while (cap < all.size() * 2) cap <<= 1;
-    std::vector<ns_seg::ImpList> tab(cap);
-    size_t distinct = 0;
-    for (const auto& t : all) {
-        for (size_t h = ((size_t)t.first * 0x9E3779B1u) & (cap - 1);; h = (h + 1) & (cap - 1)) {
-            if (tab[h].first == 0xFFFFFFFFu) { tab[h] = t; distinct++; break; }
-            if (tab[h].first == t.first) { tab[h] = t; break; }
-        }
+    for (const auto& l : lists) {   // a list given again replaces its entry
+        uint32_t ib; std::memcpy(&ib, &l.idf, 4);
+        seg->lists.imp.put(l.first, {l.count, ib});
     }
-    seg->imp_tab.swap(tab);
-    seg->imp_lists = distinct;
     return NS_OK;
 }
 
@@ -773,31 +631,8 @@ __global__ void __launch_bounds__(256) k_share_scores(const DevShare* __restrict
 extern "C" int ns_ctx_share_scores(ns_ctx* ctx, int mode) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_share_scores: ctx is NULL");
     if (mode < 0 || mode > 2) return fail(ctx, NS_E_INVAL, "ns_ctx_share_scores: mode %d outside [0, 2]", mode);
-    ctx->share_mode = mode;
+    ctx->cfg.share_mode = mode;
     return NS_OK;
-}
-
-// the registry entry of list (seg, first): found or made (the table doubles at half load; entries are never removed)
-static ns_ctx::ShareEnt& share_entry(ns_ctx* ctx, uint32_t seg, uint32_t first, bool& fresh) {
-    if (ctx->share_tab.empty() || ctx->share_n * 2 >= ctx->share_tab.size()) {
-        std::vector<ns_ctx::ShareEnt> bigger(std::max<size_t>(1024, ctx->share_tab.size() * 2));
-        const size_t m = bigger.size() - 1;
-        for (const auto& e : ctx->share_tab)
-            if (e.key != ~0ull) {
-                size_t h = (size_t)((e.key * 0x9E3779B97F4A7C15ull) >> 20) & m;
-                while (bigger[h].key != ~0ull) h = (h + 1) & m;
-                bigger[h] = e;
-            }
-        ctx->share_tab.swap(bigger);
-    }
-    const uint64_t key = ((uint64_t)seg << 32) | first;
-    const size_t m = ctx->share_tab.size() - 1;
-    size_t h = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 20) & m;
-    for (;; h = (h + 1) & m) {
-        ns_ctx::ShareEnt& e = ctx->share_tab[h];
-        if (e.key == key) { fresh = false; return e; }
-        if (e.key == ~0ull) { e.key = key; ctx->share_n++; fresh = true; return e; }
-    }
 }
 
 extern "C" int ns_segment_build_packed(ns_ctx* ctx, ns_seg* seg) {
@@ -880,15 +715,12 @@ extern "C" int ns_segment_build_skips(ns_ctx* ctx, ns_seg* seg, const uint64_t* 
     if (n_lists && (!byte_off || !counts)) return fail(ctx, NS_E_INVAL, "null list arrays");
     if (!n_lists || !seg->n_postings || !seg->n_docs) return NS_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_lists(ctx, seg, byte_off, counts, n_lists)) return rc;
     struct L { uint32_t first, count; };
     std::vector<L> lists;
     lists.reserve(n_lists);
-    for (uint32_t i = 0; i < n_lists; i++) {
-        if (byte_off[i] % 8 != 0) return fail(ctx, NS_E_INVAL, "list %u: byte offset %llu is not a multiple of 8", i, (unsigned long long)byte_off[i]);
-        const uint64_t first = byte_off[i] / 8;
-        if (first + counts[i] > seg->n_postings) return fail(ctx, NS_E_INVAL, "list %u runs past the segment's postings", i);
-        if (counts[i] && !seg->skip_of((uint32_t)first, counts[i])) lists.push_back({(uint32_t)first, counts[i]});
-    }
+    for (uint32_t i = 0; i < n_lists; i++)
+        if (counts[i] && !seg->lists.skip_of((uint32_t)(byte_off[i] / 8), counts[i])) lists.push_back({(uint32_t)(byte_off[i] / 8), counts[i]});
     std::sort(lists.begin(), lists.end(), [](const L& a, const L& b) { return a.first < b.first || (a.first == b.first && a.count < b.count); });
     lists.erase(std::unique(lists.begin(), lists.end(), [](const L& a, const L& b) { return a.first == b.first; }), lists.end());
     if (lists.empty()) return NS_OK;
@@ -931,23 +763,10 @@ extern "C" int ns_segment_build_skips(ns_ctx* ctx, ns_seg* seg, const uint64_t* 
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_tmp);
     if (e != hipSuccess) return fail(ctx, NS_E_HIP, "ns_segment_build_skips: %s", hipGetErrorString(e));
-    // registry
-    std::vector<ns_seg::SkipList> all;
-    for (const auto& t : seg->skip_tab) if (t.first != 0xFFFFFFFFu) all.push_back(t);
-    for (size_t i = 0; i < n; i++) {
-        if (bad[i]) continue;   // not ascending: no table
-        ns_seg::SkipList t; t.first = lists[i].first; t.count = lists[i].count; t.entry = (uint32_t)(seg->skip_used + i * per_list);
-        all.push_back(t);
-    }
+    // registry (a list that is not ascending gets no table; a list registered already, under another count, keeps its entry)
+    for (size_t i = 0; i < n; i++)
+        if (!bad[i] && !seg->lists.skip.find(lists[i].first)) seg->lists.skip.put(lists[i].first, {lists[i].count, (uint32_t)(seg->skip_used + i * per_list)});
     seg->skip_used = need;
-    size_t cap = 16;
-    while (cap < all.size() * 2) cap <<= 1;
-    std::vector<ns_seg::SkipList> tab(cap);
-    for (const auto& t : all)
-        for (size_t hh = ((size_t)t.first * 0x9E3779B1u) & (cap - 1);; hh = (hh + 1) & (cap - 1))
-            if (tab[hh].first == 0xFFFFFFFFu) { tab[hh] = t; break; }
-    seg->skip_tab.swap(tab);
-    seg->skip_lists = all.size();
     return NS_OK;
 }
 
@@ -960,15 +779,13 @@ extern "C" int ns_segment_build_blockmax(ns_ctx* ctx, ns_seg* seg, const uint64_
     if (n_lists && (!byte_off || !counts || !idfs)) return fail(ctx, NS_E_INVAL, "null list arrays");
     if (!n_lists || !seg->n_postings) return NS_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_lists(ctx, seg, byte_off, counts, n_lists)) return rc;
     struct L { uint32_t first, count; float idf; uint32_t entry; };
     std::vector<L> lists;
     lists.reserve(n_lists);
     for (uint32_t i = 0; i < n_lists; i++) {
-        if (byte_off[i] % 8 != 0) return fail(ctx, NS_E_INVAL, "list %u: byte offset %llu is not a multiple of 8", i, (unsigned long long)byte_off[i]);
-        const uint64_t first = byte_off[i] / 8;
-        if (first + counts[i] > seg->n_postings) return fail(ctx, NS_E_INVAL, "list %u runs past the segment's postings", i);
         uint32_t ib; std::memcpy(&ib, &idfs[i], 4);
-        if (counts[i] && !seg->bmx_of((uint32_t)first, counts[i], ib)) lists.push_back({(uint32_t)first, counts[i], idfs[i], 0u});
+        if (counts[i] && !seg->lists.bmx_of((uint32_t)(byte_off[i] / 8), counts[i], ib)) lists.push_back({(uint32_t)(byte_off[i] / 8), counts[i], idfs[i], 0u});
     }
     std::sort(lists.begin(), lists.end(), [](const L& a, const L& b) { return a.first < b.first; });
     lists.erase(std::unique(lists.begin(), lists.end(), [](const L& a, const L& b) { return a.first == b.first; }), lists.end());
@@ -1019,42 +836,35 @@ extern "C" int ns_segment_build_blockmax(ns_ctx* ctx, ns_seg* seg, const uint64_
     (void)hipFree(d_tmp);
     if (e != hipSuccess) return fail(ctx, NS_E_HIP, "ns_segment_build_blockmax: %s", hipGetErrorString(e));
     seg->bmx_used = need;
-    std::vector<ns_seg::BmxList> all;
-    for (const auto& t : seg->bmx_tab) if (t.first != 0xFFFFFFFFu) all.push_back(t);
-    for (const auto& l : lists) { ns_seg::BmxList t; t.first = l.first; t.count = l.count; std::memcpy(&t.idf_bits, &l.idf, 4); t.entry = l.entry; all.push_back(t); }
-    size_t cap = 16;
-    while (cap < all.size() * 2) cap <<= 1;
-    std::vector<ns_seg::BmxList> tab(cap);
-    for (const auto& t : all)
-        for (size_t hh = ((size_t)t.first * 0x9E3779B1u) & (cap - 1);; hh = (hh + 1) & (cap - 1)) {
-            if (tab[hh].first == 0xFFFFFFFFu || tab[hh].first == t.first) { tab[hh] = t; break; }   // a list given again: the later table wins
-        }
-    seg->bmx_tab.swap(tab);
+    for (const auto& l : lists) {   // a list given again: the later table wins
+        uint32_t ib; std::memcpy(&ib, &l.idf, 4);
+        seg->lists.bmx.put(l.first, {l.count, ib, l.entry});
+    }
     return NS_OK;
 }
 
 extern "C" int ns_ctx_use_merge(ns_ctx* ctx, int on) {
     if (!ctx) return NS_E_INVAL;
-    ctx->use_merge = on != 0;
+    ctx->cfg.use_merge = on != 0;
     return NS_OK;
 }
 
 extern "C" int ns_ctx_use_pruning(ns_ctx* ctx, int on) {
     if (!ctx) return NS_E_INVAL;
-    ctx->use_pruning = on != 0;
+    ctx->cfg.use_pruning = on != 0;
     return NS_OK;
 }
 
 extern "C" int ns_ctx_use_skips(ns_ctx* ctx, int on) {
     if (!ctx) return NS_E_INVAL;
-    ctx->use_skips = on != 0;
+    ctx->cfg.use_skips = on != 0;
     return NS_OK;
 }
 
 extern "C" int ns_ctx_use_packed(ns_ctx* ctx, int on) {
     if (!ctx) return NS_E_INVAL;
     if (on < 0 || on > 2) return fail(ctx, NS_E_INVAL, "ns_ctx_use_packed: mode %d (0, 1 or 2)", on);
-    ctx->use_packed = on;
+    ctx->cfg.use_packed = on;
     return NS_OK;
 }
 
@@ -1068,13 +878,13 @@ extern "C" int ns_ctx_set_overlap(ns_ctx* ctx, int on) {
 extern "C" int ns_ctx_set_host_threads(ns_ctx* ctx, uint32_t n) {
     if (!ctx) return NS_E_INVAL;
     if (n > 64) return fail(ctx, NS_E_INVAL, "ns_ctx_set_host_threads: %u threads (at most 64)", n);
-    ctx->prep_threads = n;
+    ctx->cfg.prep_threads = n;
     return NS_OK;
 }
 
 extern "C" int ns_ctx_use_impacts(ns_ctx* ctx, int on) {
     if (!ctx) return NS_E_INVAL;
-    ctx->use_impacts = on != 0;
+    ctx->cfg.use_impacts = on != 0;
     return NS_OK;
 }
 
@@ -1191,7 +1001,7 @@ extern "C" void ns_batch_destroy(ns_batch* b) {
     else (void)hipStreamSynchronize(b->st);
     if (b->ctx->down_owner == b) b->ctx->down_owner = nullptr;
     if (b->down_slot >= 0) b->ctx->down_slots[(size_t)b->down_slot].busy = false;
-    if (b->shared && b->ctx->live_shared) b->ctx->live_shared--;
+    if (b->shared && b->ctx->share.live) b->ctx->share.live--;
     for (auto& blk : b->blocks) pool_free(b->ctx, blk.first, blk.second);
     for (auto& e : b->ev_pool) if (e) (void)hipEventDestroy(e);
     if (b->done) (void)hipEventDestroy(b->done);
@@ -1203,85 +1013,7 @@ static hipError_t batch_alloc(ns_batch* b, void** dptr, size_t n) {
     if (e == hipSuccess) b->blocks.push_back({*dptr, n});
     return e;
 }
-// ---- host side of a batch: term refs -> (query, segment) groups -> work items, on several host threads ----------
-// A batch is prepared in three fork-join phases over contiguous slices of the queries (the reference's requests are
-// independent, src/api_engine.cpp:369): A regroup + classify, B cut into work items, C write the descriptors into the
-// pinned staging buffer in launch order.  Between the phases only prefix sums over the slices run serially.  Every
-// result (descriptor bytes, launch order) is independent of the number of threads.
-namespace {
-
-struct HostGroup { DevGroup g; uint32_t query; uint64_t cost; uint64_t cmax; uint64_t work; bool wave; uint8_t cls; bool fast_div; bool signed_in; bool grid; bool merge2; };
-
-constexpr uint32_t kOrderBuckets = 2048;   // launch-order key: 6 bits of exponent x 5 bits of mantissa of the estimated run time
-inline uint32_t order_bucket(uint64_t c) {  // descending: bucket 0 holds the longest items
-    if (c < 32) return kOrderBuckets - 1 - (uint32_t)c;
-    const int b = 63 - __builtin_clzll(c);
-    const uint32_t key = (uint32_t)b * 32u + (uint32_t)((c >> (b - 5)) & 31u);
-    return kOrderBuckets - 1 - std::min(key, kOrderBuckets - 1);
-}
-
-struct PrepSlice {
-    uint32_t q0 = 0, q1 = 0;
-    std::vector<DevTerm> dterms;
-    std::vector<HostGroup> groups;
-    std::vector<uint32_t> qgroup_begin;   // q1 - q0 + 1 entries, local group indices
-    std::vector<uint32_t> seg_ids;
-    uint64_t bounds_total = 0, postings_total = 0, total_work = 0;
-    bool all_imp = true, all_pk = true, any_pruned = false;
-    int err_code = NS_OK;
-    uint32_t err_query = 0xFFFFFFFFu;
-    std::string err_msg;
-    // phase B
-    std::vector<DevWItem> witems;
-    std::vector<uint16_t> wbucket;        // launch-order bucket of each wave item; bit 15: > 16 terms (the "wide" instantiation)
-    std::vector<uint32_t> wshare;         // locality key of the item: segment (6 bits) | doc range on the 4096-grid (12) | hash of its largest list (14) -> XCD dealing
-    std::vector<DevItem> items;
-    std::vector<uint64_t> item_cost;
-    std::vector<DevGroup> bgroups;
-    uint32_t n_rows = 0;
-    bool direct = true;
-    std::vector<uint32_t> hist;           // [2][kOrderBuckets]: narrow, wide
-    // offsets handed down by the serial steps
-    uint32_t term_off = 0, row_off = 0, item_off = 0, bgroup_off = 0;
-    uint64_t bounds_off = 0;
-    std::vector<uint32_t> start;          // [2][kOrderBuckets]: this slice's first position in each bucket of the sorted item array
-    void reset(uint32_t a, uint32_t b) {
-        q0 = a; q1 = b;
-        dterms.clear(); groups.clear(); qgroup_begin.clear(); seg_ids.clear();
-        bounds_total = postings_total = total_work = 0; all_imp = true; all_pk = true; any_pruned = false;
-        err_code = NS_OK; err_query = 0xFFFFFFFFu; err_msg.clear();
-        witems.clear(); wbucket.clear(); wshare.clear(); items.clear(); item_cost.clear(); bgroups.clear();
-        n_rows = 0; direct = true;
-        hist.assign(2 * kOrderBuckets, 0u);
-        start.assign(2 * kOrderBuckets, 0u);
-        term_off = row_off = item_off = bgroup_off = 0; bounds_off = 0;
-    }
-    void fail_at(uint32_t q, int code, const char* fmt, ...) {
-        if (err_code != NS_OK) return;   // the first failing query of the slice is reported
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        std::vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        err_code = code; err_query = q; err_msg = buf;
-    }
-};
-
-}  // namespace
-
-struct ns_prep {
-    std::vector<PrepSlice> slices;
-    std::vector<DevShare> share_build;    // shared term scores: the distinct lists the batch builds, in build order
-    std::vector<uint32_t> share_at;       // per launch position: the item's locality key (XCD dealing)
-    std::vector<uint32_t> bucket_pos;     // launch position at which each fine bucket of the narrow half starts (+ the end)
-    std::vector<std::vector<DevWItem>> deal_tmp;   // per host thread
-    std::vector<std::vector<uint64_t>> deal_key, deal_alt;
-    std::vector<std::vector<uint32_t>> deal_bins;
-    ForkJoin* pool = nullptr;
-    ~ns_prep() { delete pool; }
-};
-static void prep_free(ns_prep* p) { delete p; }
-
+// ---- a batch: planned on the host (ns_plan.hpp), then one device block, the descriptor image staged and uploaded --------
 extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const ns_term_ref* terms, uint32_t n_queries,
                                 uint32_t k, uint32_t flags, ns_batch** out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_batch_prepare: ctx is NULL");
@@ -1292,12 +1024,10 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
     if (flags & ~NS_FLAG_AND) return fail(ctx, NS_E_INVAL, "unknown flags 0x%x", flags);
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-    const VariantDesc vd = kVariants[ctx->variant];
+    // the segments as the planner sees them, and the per-batch segment table (n_tiles depends on the workgroup-kernel variant)
+    const VariantDesc vd = kVariants[ctx->cfg.variant];
     const uint32_t tile_docs = vd.nt * vd.spt;
-    const bool wave_path = vd.hb != 0;
-    const bool auto_mode = ctx->variant == 0;
-
-    // per-batch segment table (n_tiles depends on the workgroup-kernel variant)
+    std::vector<SegView> views(ctx->segs.size());
     std::vector<DevSeg> segs(ctx->segs.size());
     for (size_t i = 0; i < ctx->segs.size(); i++) {
         DevSeg d{};
@@ -1315,405 +1045,31 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
             d.n_postings = s->n_postings;
             d.n_docs = s->n_docs;
             d.n_tiles = (s->n_docs + tile_docs - 1) / tile_docs;
+            views[i] = SegView{s->n_docs, d.n_tiles, s->n_postings, s->norm_safe, s->d_packed != nullptr, &s->lists};
         }
         segs[i] = d;
     }
 
-    // ---- slices: one per host thread for large batches (below ~1500 queries per thread the hand-over costs more than it saves) ----
-    if (!ctx->prep) ctx->prep = new ns_prep();
-    ns_prep& P = *ctx->prep;
-    unsigned width = 1;
-    if (n_queries >= 3000 && ctx->prep_threads != 1) {
-        unsigned want = ctx->prep_threads ? ctx->prep_threads : std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 8u);
-        // one thread per ~1500 queries or ~6000 term refs, whichever asks for more (a query over 8 segments carries 8x the refs)
-        uint64_t n_refs = 0;
-        for (uint32_t q = 0; q < n_queries; q++) n_refs += queries[q].term_count;
-        width = std::max(1u, std::min<unsigned>(want, std::max<unsigned>(n_queries / 1500, (unsigned)std::min<uint64_t>(n_refs / 6000, 64))));
-    }
-    if (width > 1 && (!P.pool || P.pool->width() < width)) { delete P.pool; P.pool = new ForkJoin(width); }
-    if (P.slices.size() < width) P.slices.resize(width);
-    for (unsigned s = 0; s < width; s++) P.slices[s].reset((uint32_t)((uint64_t)n_queries * s / width), (uint32_t)((uint64_t)n_queries * (s + 1) / width));
-    auto fork = [&](const std::function<void(unsigned)>& fn) {
-        if (width == 1) fn(0); else P.pool->run(width, fn);
-    };
-    const bool want_imp = ctx->use_impacts && auto_mode;
-
-    // ---- phase A: regroup term refs by (query, segment), keeping query-term order inside each group; classify ----
-    fork([&](unsigned si) {
-        PrepSlice& S = P.slices[si];
-        S.all_imp = want_imp;   // stays true while every list met so far has an impact stream built with this idf
-        S.qgroup_begin.reserve(S.q1 - S.q0 + 1);
-        for (uint32_t q = S.q0; q < S.q1; q++) {
-            S.qgroup_begin.push_back((uint32_t)S.groups.size());
-            const ns_query_desc qd = queries[q];
-            if (qd.term_count && !terms) { S.fail_at(q, NS_E_INVAL, "terms is NULL"); break; }
-            S.seg_ids.clear();
-            bool bad = false;
-            for (uint32_t i = 0; i < qd.term_count && !bad; i++) {
-                const ns_term_ref& r = terms[qd.term_begin + i];
-                if (r.seg_id >= ctx->segs.size() || !ctx->segs[r.seg_id]) { S.fail_at(q, NS_E_INVAL, "query %u term %u: unknown segment %u", q, i, r.seg_id); bad = true; break; }
-                const ns_seg* s = ctx->segs[r.seg_id];
-                if (r.byte_off % 8 != 0) { S.fail_at(q, NS_E_INVAL, "query %u term %u: byte_off %llu not a multiple of 8", q, i, (unsigned long long)r.byte_off); bad = true; break; }
-                if (r.byte_off / 8 + r.count > s->n_postings) { S.fail_at(q, NS_E_INVAL, "query %u term %u: list [%llu,+%u) outside segment %u (%llu postings)", q, i, (unsigned long long)(r.byte_off / 8), r.count, r.seg_id, (unsigned long long)s->n_postings); bad = true; break; }
-                if (std::find(S.seg_ids.begin(), S.seg_ids.end(), r.seg_id) == S.seg_ids.end()) S.seg_ids.push_back(r.seg_id);
-            }
-            if (bad) break;
-            std::sort(S.seg_ids.begin(), S.seg_ids.end());   // segments in manifest (id) order, api_engine.cpp:441
-            for (uint32_t sid : S.seg_ids) {
-                HostGroup hg{};
-                hg.fast_div = ctx->segs[sid]->norm_safe;
-                if (!ctx->segs[sid]->d_packed) S.all_pk = false;
-                hg.g.term_begin = (uint32_t)S.dterms.size();   // local to the slice until phase B
-                hg.g.seg = sid;
-                hg.query = q;
-                for (uint32_t i = 0; i < qd.term_count; i++) {
-                    const ns_term_ref& r = terms[qd.term_begin + i];
-                    if (r.seg_id != sid) continue;
-                    DevTerm t{};
-                    t.list_off = r.byte_off / 8;
-                    t.count = r.count;
-                    t.idf = r.idf;
-                    t.weight = r.qweight;
-                    t.seg = sid;
-                    S.dterms.push_back(t);
-                    hg.cost += r.count;
-                    hg.cmax = std::max<uint64_t>(hg.cmax, r.count);
-                    if (S.all_imp) {
-                        uint32_t ib; std::memcpy(&ib, &r.idf, 4);
-                        S.all_imp = ctx->segs[sid]->imp_has((uint32_t)(r.byte_off / 8), r.count, ib);
-                    }
-                    // 2^-30 <= idf <= 2^30 (and finite): see ns_div_short
-                    if (!(r.idf >= 9.313225746154785e-10f && r.idf <= 1073741824.0f)) hg.fast_div = false;
-                    if (std::signbit(r.idf) || std::signbit(r.qweight)) hg.signed_in = true;   // a contribution may be -0.0f (see dscore_body)
-                }
-                hg.g.term_count = (uint32_t)S.dterms.size() - hg.g.term_begin;
-                if ((flags & NS_FLAG_AND) && hg.g.term_count > 255) { S.fail_at(q, NS_E_INVAL, "AND mode supports at most 255 term refs per (query, segment)"); bad = true; break; }
-                hg.wave = wave_path && hg.g.term_count <= kWaveMaxTerms;
-                // class of the group (auto mode only): which scoring body suits its mix of lists (sweeps on
-                // MI355X, profiles/r01): 1 = one list dominates (the others hold <= 1/32 of its postings): driver
-                // stream with the 64-posting foreign budget; 2 = dense (>= 0.25 postings per doc over >= 2
-                // lists): doc tiles; 0 = driver stream with the 192-posting budget.
-                {
-                    const uint64_t rest = hg.cost - hg.cmax;
-                    const uint32_t nd = std::max<uint32_t>(segs[sid].n_docs, 1);
-                    if (rest * 32 <= hg.cmax) hg.cls = 1;
-                    else if (hg.g.term_count >= 2 && hg.cost * 64 >= (uint64_t)nd * ctx->tile_dens64) hg.cls = 2;
-                    else hg.cls = 0;
-                    // work estimate in units of one streamed driver posting (measured, profiles/r01): a foreign
-                    // posting (claim, accumulate, read back) costs ~8x, a doc-tile posting ~2x
-                    hg.work = !auto_mode ? hg.cost : (hg.cls == 2 ? hg.cost * kWorkTile : hg.cmax + rest * kWorkForeign);
-                    // two lists, general class: the merge body (no table): both lists cost about alike per posting
-                    // (two COMPARABLE lists: when one is more than 8x the other, a window of the short one per round of the long
-                    // one is mostly padding and the table path is as good: r8 + r300, 37 : 1, measured 3 % slower with the merge)
-                    hg.merge2 = auto_mode && ctx->use_merge && hg.cls == 0 && hg.g.term_count == 2 && rest * ctx->merge_ratio >= hg.cmax;
-                    if (hg.merge2) hg.work = hg.cmax + rest * kWorkMerge;
-                }
-                if (!hg.wave) {
-                    hg.g.bounds_off = S.bounds_total;   // local; the slice's base is added in phase B
-                    S.bounds_total += (uint64_t)(segs[sid].n_tiles + 1) * hg.g.term_count;
-                }
-                S.postings_total += hg.cost;
-                S.total_work += hg.work;
-                S.groups.push_back(hg);
-            }
-            if (bad) break;
-        }
-        S.qgroup_begin.resize(S.q1 - S.q0 + 1, (uint32_t)S.groups.size());
-    });
-    {
-        const PrepSlice* first = nullptr;
-        for (unsigned s = 0; s < width; s++)
-            if (P.slices[s].err_code != NS_OK && (!first || P.slices[s].err_query < first->err_query)) first = &P.slices[s];
-        if (first) return fail(ctx, first->err_code, "%s", first->err_msg.c_str());
-    }
-    uint64_t bounds_total = 0, postings_total = 0, total_work = 0;
-    uint32_t n_dterms = 0, G = 0;
-    bool all_imp = want_imp, all_pk = ctx->use_packed != 0 && auto_mode;
-    for (unsigned s = 0; s < width; s++) {
-        PrepSlice& S = P.slices[s];
-        S.term_off = n_dterms; S.bounds_off = bounds_total;
-        n_dterms += (uint32_t)S.dterms.size(); G += (uint32_t)S.groups.size();
-        bounds_total += S.bounds_total; postings_total += S.postings_total; total_work += S.total_work;
-        all_imp = all_imp && S.all_imp;
-        all_pk = all_pk && S.all_pk;
-    }
-    if (bounds_total >= (1ull << 32)) return fail(ctx, NS_E_INVAL, "batch too large: %llu boundary entries; split the batch", (unsigned long long)bounds_total);
-
-    // ---- shared term scores (ns_ctx_share_scores; k_share_scores): the batch's distinct lists, each listed once, in the
-    // order the term refs name them.  A list is refused — and the batch then scores every posting in place, as it
-    // always did — when it overlaps another list ever shared in its segment (two builders, one posting), when the segment
-    // carries an optional impact stream that does not hold exactly this list with this idf (the stream is not the batch's
-    // to overwrite), or when its idf differs from the one a LIVE sharing batch built it with (that batch may run again).
-    std::vector<DevShare>& share_build = P.share_build;
-    share_build.clear();
-    uint64_t share_postings = 0;
-    bool shared = false;
-    if (!all_imp && want_imp && ctx->share_mode != 0 && !all_pk && postings_total > 0 &&
-        (ctx->share_mode == 2 || postings_total >= ctx->share_min_postings)) {
-        shared = true;
-        if (++ctx->share_epoch == 0) {   // the batch counter wrapped: no entry may look like this batch's
-            for (auto& en : ctx->share_tab) en.epoch = 0;
-            ctx->share_epoch = 1;
-        }
-        const uint32_t epoch = ctx->share_epoch;
-        for (unsigned sl = 0; sl < width && shared; sl++) {
-            const std::vector<DevTerm>& dts = P.slices[sl].dterms;
-            for (size_t ti = 0; ti < dts.size(); ti++) {
-                // the registry is a few MB and every probe of it a cache miss: the probe of the term 8 ahead is requested now
-                if (ti + 8 < dts.size() && !ctx->share_tab.empty()) {
-                    const uint64_t k8 = ((uint64_t)dts[ti + 8].seg << 32) | (uint32_t)dts[ti + 8].list_off;
-                    __builtin_prefetch(&ctx->share_tab[(size_t)((k8 * 0x9E3779B97F4A7C15ull) >> 20) & (ctx->share_tab.size() - 1)]);
-                }
-                const DevTerm& t = dts[ti];
-                if (!t.count) continue;
-                ns_seg* sg = ctx->segs[t.seg];
-                uint32_t ib; std::memcpy(&ib, &t.idf, 4);
-                const uint32_t first = (uint32_t)t.list_off;
-                if (sg->imp_lists) {
-                    if (sg->imp_has(first, t.count, ib)) continue;   // the optional stream holds this list already
-                    shared = false; break;
-                }
-                bool fresh = false;
-                ns_ctx::ShareEnt& en = share_entry(ctx, t.seg, first, fresh);
-                if (fresh) { en.count = t.count; en.idf_bits = ib; en.epoch = 0; en.bad = !sg->share_admit(first, t.count); }
-                if (en.bad || en.count != t.count) { shared = false; break; }
-                if (en.idf_bits != ib) {
-                    if (ctx->live_shared || en.epoch == epoch) { shared = false; break; }
-                    en.idf_bits = ib;
-                }
-                if (en.epoch != epoch) {
-                    en.epoch = epoch;
-                    if (share_postings + t.count >= (1ull << 32)) { shared = false; break; }
-                    share_build.push_back(DevShare{first, t.count, t.idf, t.seg, (uint32_t)share_postings});
-                    share_postings += t.count;
-                    // (a batch that cannot reach the ratio gives up here: the frequent lists come early, and with them the verdict)
-                    if (ctx->share_mode == 1 && share_postings * ctx->share_ratio > postings_total) { shared = false; break; }
-                }
+    BatchPlan& P = ctx->plan;
+    int rc = P.group(ctx->cfg, views, ctx->share, queries, terms, n_queries, k, flags);
+    if (rc != NS_OK) return fail(ctx, rc, "%s", P.err.c_str());
+    for (size_t i = 0; P.shared && i < P.share_build.size(); i++) {   // the score buffers of the segments the batch builds into
+        ns_seg* sg = ctx->segs[P.share_build[i].seg];
+        if (!sg->d_impacts) {
+            const size_t nb = (size_t)(sg->n_postings + kPadPostings) * 8;
+            hipError_t ea = hipMalloc((void**)&sg->d_impacts, nb);
+            if (ea == hipSuccess) ea = hipMemsetAsync(sg->d_impacts, 0xFF, nb, ctx->stream);   // docId ~0: never taken
+            if (ea == hipSuccess) ea = hipStreamSynchronize(ctx->stream);
+            if (ea != hipSuccess) {   // no room for the scores: the batch scores in place
+                if (sg->d_impacts) (void)hipFree(sg->d_impacts);
+                sg->d_impacts = nullptr; (void)hipGetLastError();
+                P.shared = false;
             }
         }
-        if (shared && ctx->share_mode == 1 && postings_total < (uint64_t)ctx->share_ratio * share_postings) shared = false;
-        for (size_t i = 0; shared && i < share_build.size(); i++) {   // the score buffers of the segments the batch builds into
-            ns_seg* sg = ctx->segs[share_build[i].seg];
-            if (!sg->d_impacts) {
-                const size_t nb = (size_t)(sg->n_postings + kPadPostings) * 8;
-                hipError_t ea = hipMalloc((void**)&sg->d_impacts, nb);
-                if (ea == hipSuccess) ea = hipMemsetAsync(sg->d_impacts, 0xFF, nb, ctx->stream);   // docId ~0: never taken
-                if (ea == hipSuccess) ea = hipStreamSynchronize(ctx->stream);
-                if (ea != hipSuccess) {   // no room for the scores: the batch scores in place
-                    if (sg->d_impacts) (void)hipFree(sg->d_impacts);
-                    sg->d_impacts = nullptr; (void)hipGetLastError();
-                    shared = false;
-                }
-            }
-            if (shared) segs[share_build[i].seg].impacts = sg->d_impacts;
-        }
-        if (shared) all_imp = true;
-        else { share_build.clear(); share_postings = 0; }
+        if (P.shared) segs[P.share_build[i].seg].impacts = sg->d_impacts;
     }
-
-    // ---- work items.  A group is split into doc ranges (a) so that no single worker carries more
-    // than ~split_postings units of estimated work (the longest item bounds the batch's tail; launch
-    // order is longest-estimated-work first), and (b) so that a small batch still fills the chip.  Partial rows of one query are contiguous; k_merge joins them.
-    const uint32_t min_items = ctx->min_items ? ctx->min_items : (uint32_t)std::max(ctx->n_cus, 1) * 24u;
-    int small_mode = 0;   // thin / tile items: 0 = double share, 1 = plain share, 2 = half share (see below)
-    uint64_t split_postings = ctx->split_postings ? ctx->split_postings
-                              : (!auto_mode ? kDefaultSplitPostings : (k <= 32 ? kSplitWorkSmallK : kSplitWorkLargeK));
-    bool fine_cut = false;   // the batch is cut finer than the default share: it does not fill the chip for long
-    if (!ctx->split_postings && auto_mode) {
-        // a small batch: cut finer so that the chip still sees ~100 items per CU (an item of the default size
-        // runs 0.3-1.3 ms: with fewer items than wave slots that would be the whole batch's time), but not
-        // below ~16 K units, where an item's fixed cost takes over
-        const uint64_t fine = total_work / ((uint64_t)std::max(ctx->n_cus, 1) * 96u);
-        fine_cut = fine < split_postings;
-        split_postings = std::min<uint64_t>(split_postings, std::max<uint64_t>(fine, 16384));
-        // A batch that leaves wave slots idle is bound by its LONGEST item, and a streaming item is a chain of dependent
-        // round trips (one 256-posting round in flight per wave).  When the double share of a thin or tile item would
-        // exceed what a wave slot gets on average, those items lose it; when even a plain share does, they are halved
-        // (profiles/r02/small_batch_split_modes.txt: 256 / 512 / 1024 queries of the cfg5 law run 36 / 27 / 14 % faster;
-        // batches that fill the chip — all thin groups of cfg5 alone, 4096 single-term queries — are left as they were).
-        const uint64_t per_slot = total_work / ((uint64_t)std::max(ctx->n_cus, 1) * 24u);
-        small_mode = per_slot >= 2 * split_postings ? 0 : (per_slot >= split_postings ? 1 : 2);
-    }
-    uint32_t chunks_per_group = 1;
-    if (G > 0 && G < min_items) chunks_per_group = std::min<uint32_t>((min_items + G - 1) / G, 1024u);   // one query alone: 1024 ranges are plenty
-    std::vector<DevQuery> dq(n_queries);
-
-    // ---- phase B: cut the groups into work items (rows numbered inside the slice) ----
-    fork([&](unsigned si) {
-        PrepSlice& S = P.slices[si];
-        for (uint32_t q = S.q0; q < S.q1; q++) {
-            dq[q].part_begin = S.n_rows;
-            for (uint32_t gi = S.qgroup_begin[q - S.q0]; gi < S.qgroup_begin[q - S.q0 + 1]; gi++) {
-                HostGroup& hg = S.groups[gi];
-                hg.g.term_begin += S.term_off;          // global from here on
-                const DevSeg& sg = segs[hg.g.seg];
-                if (sg.n_docs == 0) continue;   // empty segment: nothing to score
-                if (hg.wave) {
-                    // thin and tile groups run at a steady rate per posting: fewer, longer items (less per-item set-up,
-                    // same balance); groups with dense foreign lists vary more per posting and stay finer
-                    uint64_t sp_ = (auto_mode && hg.cls != 0) ? split_postings * 2 : split_postings;
-                    if (auto_mode && hg.cls != 0 && small_mode) sp_ = small_mode == 2 ? split_postings / 2 : split_postings;
-                    const uint64_t want = std::max<uint64_t>((hg.work + sp_ - 1) / sp_, chunks_per_group);
-                    uint32_t ns = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(want, 1), std::min<uint32_t>(sg.n_docs, 4096));
-                    // The number of ranges is a POWER OF TWO (the nearest in ratio; the next one up for a small batch): range boundaries then come from one
-                    // nested grid, so the items of different queries cover IDENTICAL doc ranges of the lists they share, and
-                    // items of one range — equal size, adjacent in the launch order — read the same bytes at about the same
-                    // time: L2 / Infinity-Cache hits instead of misses (same number of items on average; cfg3 -5 %, cfg5's
-                    // tile groups -7 %, a 2048-query batch -4 %; profiles/r02/ab/ab14_range_grid.txt).
-                    if (auto_mode && ns > 1) {
-                        uint32_t p2 = 1;
-                        while (p2 < ns) p2 <<= 1;
-                        if (!small_mode && (uint64_t)ns * ns * 2 < (uint64_t)p2 * p2) p2 >>= 1;   // a batch that leaves wave slots idle never gets fewer items
-                        // K > 32: a group that is cut at all is cut into at least 8 ranges (cfg3 -7 %, at K = 64 -7 %, another seed
-                        // -7 %; 16 is too many; at K <= 32 the same rule costs 2 %: ab14 / ab19)
-                        if (k > 32 && p2 < 8) p2 = 8;
-                        ns = std::min<uint32_t>(p2, std::min<uint32_t>(sg.n_docs, 4096));
-                    }
-                    // Skip tables (ns_segment_build_skips): a doc-tile group walks the grid of its lists' tables; a group of the
-                    // driver-stream bodies that is cut into ranges takes the ranges' ends of its frequent lists from their
-                    // tables instead of searching for them (the searches of a hot list are a dozen dependent loads: 4-20 % of
-                    // an item's time, most in small batches).  Either way the ranges start and end on the grid.
-                    if (auto_mode && ctx->use_skips && (hg.cls == 2 || ns > 1) && !ctx->segs[hg.g.seg]->skip_tab.empty()) {
-                        const ns_seg* sg_ = ctx->segs[hg.g.seg];
-                        DevTerm* dt = S.dterms.data() + (hg.g.term_begin - S.term_off);
-                        for (uint32_t ti = 0; ti < hg.g.term_count; ti++) {
-                            if (dt[ti].count < kSkipMinCount) continue;
-                            dt[ti].skip = sg_->skip_of((uint32_t)dt[ti].list_off, dt[ti].count);
-                            if (dt[ti].skip) hg.grid = true;
-                        }
-                    }
-                    // Block-max pruning (ns_ctx_use_pruning): a group of ONE list whose block maxima were built with this idf, scored
-                    // with a positive weight — the fp32 product w * s is then monotone in s and never a negative zero
-                    bool pruned = false;
-                    if (auto_mode && ctx->use_pruning && hg.g.term_count == 1 && !ctx->segs[hg.g.seg]->bmx_tab.empty()) {
-                        DevTerm* dt = S.dterms.data() + (hg.g.term_begin - S.term_off);
-                        uint32_t ib; std::memcpy(&ib, &dt[0].idf, 4);
-                        if (dt[0].idf > 0.0f && std::isfinite(dt[0].idf) && dt[0].weight > 0.0f && std::isfinite(dt[0].weight)) {
-                            dt[0].bmx = ctx->segs[hg.g.seg]->bmx_of((uint32_t)dt[0].list_off, dt[0].count, ib);
-                            pruned = dt[0].bmx != 0;
-                        }
-                        if (pruned) S.any_pruned = true;
-                    }
-                    // launch-order key = estimated run time of the ITEM: its share of the group's work plus what
-                    // every item pays per term regardless of size (window planning, range searches, table set-up)
-                    const uint64_t per_term = hg.cls == 2 ? kItemTermTile : (hg.cls == 1 ? kItemTermThin : kItemTermGeneral);
-                    uint64_t key = hg.work / ns + 1 + (auto_mode ? per_term * hg.g.term_count : 0);
-                    // In a batch cut finer than the default share the streaming items (thin, tile) are chains of round trips that
-                    // a less loaded chip does not shorten, while the issue-bound general items do run faster: those start
-                    // later (2048 queries of the cfg5 law -11 %, 4096 -5 %, 512 -4 %; ab16_order_key_small_batches.txt).
-                    if (fine_cut && hg.cls == 0) key = key * 5 / 8;
-                    // K > 32: the streaming items pay more per posting than the work units (fitted at K = 10) say — fewer waves
-                    // per CU, larger candidate buffers — so the general items start later there too (cfg3 -2.6 %, at K = 64 -2.3 %)
-                    else if (auto_mode && k > 32 && hg.cls == 0) key = key * 3 / 4;
-                    if (auto_mode) key = key * ctx->key_pct[hg.merge2 ? 3 : hg.cls] / 100;   // sweeps (NS_KEY_PCT); 100 each by default
-                    const bool wide = auto_mode && hg.g.term_count > 16;
-                    const uint32_t bucket = order_bucket(key);
-                    // what the group's items read most of: its largest list (the driver of a driver-stream item)
-                    uint64_t big_off = 0;
-                    {
-                        const DevTerm* dt = S.dterms.data() + (hg.g.term_begin - S.term_off);
-                        uint32_t cm = 0;
-                        for (uint32_t ti = 0; ti < hg.g.term_count; ti++)
-                            if (dt[ti].count >= cm) { cm = dt[ti].count; big_off = dt[ti].list_off; }
-                    }
-                    for (uint32_t i = 0; i < ns; i++) {
-                        DevWItem it{};
-                        it.query = q;
-                        it.seg = hg.g.seg;
-                        it.term_begin = hg.g.term_begin;
-                        it.term_count = hg.g.term_count;
-                        it.doc_lo = (uint32_t)((uint64_t)sg.n_docs * i / ns);
-                        it.doc_hi = (uint32_t)((uint64_t)sg.n_docs * (i + 1) / ns);
-                        if (hg.grid) {   // ranges of a skip-grid group start and end on the grid
-                            it.doc_lo -= it.doc_lo % kSkipDocs;
-                            if (i + 1 < ns) it.doc_hi -= it.doc_hi % kSkipDocs;
-                        }
-                        if (it.doc_hi <= it.doc_lo) continue;
-                        it.out_slot = S.n_rows++;
-                        it.whole = (ns == 1 ? 1u : 0u) | (hg.fast_div ? 8u : 0u) | (hg.signed_in ? 16u : 0u) | (hg.grid ? (hg.cls == 2 ? 32u : 64u) : 0u);
-                        // auto mode: very dense groups take the doc-tile body (bit 1), groups with thin non-driver lists the small foreign budget (bit 2)
-                        if (auto_mode) it.whole |= (hg.cls == 2 ? 2u : 0u) | (hg.cls == 1 ? 4u : 0u) | (pruned ? 128u : 0u) | (hg.merge2 && hg.wave ? 256u : 0u);
-                        S.witems.push_back(it);
-                        S.wbucket.push_back((uint16_t)(bucket | (wide ? 0x8000u : 0u)));
-                        {
-                            uint64_t h = big_off * 0x9E3779B97F4A7C15ull;
-                            h ^= h >> 29;
-                            const uint32_t r12 = (uint32_t)(((uint64_t)it.doc_lo << 12) / std::max<uint32_t>(sg.n_docs, 1u)) & 4095u;
-                            S.wshare.push_back(((it.seg & 63u) << 26) | (r12 << 14) | (uint32_t)((h >> 40) & 0x3FFFu));
-                        }
-                        S.hist[(wide ? kOrderBuckets : 0) + bucket]++;
-                    }
-                } else {
-                    DevGroup g = hg.g;
-                    g.bounds_off += S.bounds_off;
-                    S.bgroups.push_back(g);
-                    const uint32_t nt = sg.n_tiles;
-                    const uint32_t chunks = std::min(chunks_per_group, nt);
-                    const uint32_t per = (nt + chunks - 1) / chunks;
-                    for (uint32_t tb = 0; tb < nt; tb += per) {
-                        DevItem it{};
-                        it.bounds_off = g.bounds_off;
-                        it.query = q;
-                        it.seg = g.seg;
-                        it.term_begin = g.term_begin;
-                        it.term_count = g.term_count;
-                        it.tile_begin = tb;
-                        it.tile_end = std::min(nt, tb + per);
-                        it.out_slot = S.n_rows++;
-                        S.item_cost.push_back(hg.cost * (it.tile_end - it.tile_begin) / nt + 1);
-                        S.items.push_back(it);
-                    }
-                }
-            }
-            dq[q].part_count = S.n_rows - dq[q].part_begin;
-            if (dq[q].part_count != 1) S.direct = false;
-        }
-    });
-    uint32_t n_rows = 0, n_witems = 0, n_items = 0, n_bgroups = 0;
-    bool direct = n_queries > 0;
-    for (unsigned s = 0; s < width; s++) {
-        PrepSlice& S = P.slices[s];
-        S.row_off = n_rows; S.item_off = n_items; S.bgroup_off = n_bgroups;
-        n_rows += S.n_rows; n_witems += (uint32_t)S.witems.size(); n_items += (uint32_t)S.items.size(); n_bgroups += (uint32_t)S.bgroups.size();
-        direct = direct && S.direct;
-    }
-    // launch order of the wave items: narrow (<= 16 terms) before wide, longest estimated run time first, ties in query order
-    uint32_t n_class[3] = {0, 0, 0};
-    {
-        uint32_t pos = 0;
-        P.bucket_pos.assign(kOrderBuckets + 1, 0u);
-        for (uint32_t half = 0; half < 2; half++) {
-            for (uint32_t bkt = 0; bkt < kOrderBuckets; bkt++) {
-                if (half == 0) P.bucket_pos[bkt] = pos;
-                for (unsigned s = 0; s < width; s++) {
-                    P.slices[s].start[half * kOrderBuckets + bkt] = pos;
-                    pos += P.slices[s].hist[half * kOrderBuckets + bkt];
-                }
-            }
-            if (half == 0) { n_class[0] = pos; P.bucket_pos[kOrderBuckets] = pos; }
-        }
-        n_class[1] = pos - n_class[0];
-        // every wave item has exactly one launch position (the kernels trust the item array: an item lost or doubled here
-        // would be a wild descriptor on the device)
-        if (pos != n_witems) return fail(ctx, NS_E_STATE, "internal: launch order holds %u of %u work items", pos, n_witems);
-        if (!auto_mode) { n_class[0] = n_class[1] = 0; }
-    }
-    // the workgroup-kernel items (fallback path: few): longest first, serially
-    std::vector<DevItem> sorted_items;
-    if (n_items) {
-        struct Cost { uint64_t c; uint32_t slice, idx; };
-        std::vector<Cost> ic;
-        ic.reserve(n_items);
-        for (unsigned s = 0; s < width; s++)
-            for (uint32_t i = 0; i < P.slices[s].items.size(); i++) ic.push_back({P.slices[s].item_cost[i], s, i});
-        std::stable_sort(ic.begin(), ic.end(), [](const Cost& a, const Cost& b) { return a.c > b.c; });
-        sorted_items.resize(n_items);
-        for (uint32_t i = 0; i < n_items; i++) {
-            DevItem it = P.slices[ic[i].slice].items[ic[i].idx];
-            it.out_slot = direct ? it.query : it.out_slot + P.slices[ic[i].slice].row_off;
-            sorted_items[i] = it;
-        }
-    }
+    rc = P.cut();
+    if (rc != NS_OK) return fail(ctx, rc, "%s", P.err.c_str());
 
     ns_batch* b = new ns_batch();
     b->ctx = ctx;
@@ -1723,48 +1079,35 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
         if (ctx->flip) b->st = ctx->alt_stream;
     }
     b->Q = n_queries; b->K = k; b->flags = flags;
-    b->variant = ctx->variant; b->tile_docs = tile_docs; b->hb = vd.hb;
-    b->n_items = n_items; b->n_witems = n_witems;
-    b->n_bgroups = n_bgroups; b->n_terms = n_dterms;
-    for (int c = 0; c < 3; c++) b->n_class[c] = n_class[c];
-    b->n_parts = direct ? 0 : n_rows;
-    b->postings = postings_total;
-    b->direct = direct;
-    b->imp = all_imp && postings_total > 0;
-    if (shared) {
+    b->variant = ctx->cfg.variant; b->tile_docs = tile_docs; b->hb = vd.hb;
+    b->n_items = P.n_items; b->n_witems = P.n_witems;
+    b->n_bgroups = P.n_bgroups; b->n_terms = P.n_dterms;
+    for (int c = 0; c < 3; c++) b->n_class[c] = P.n_class[c];
+    b->n_parts = P.direct ? 0 : P.n_rows;
+    b->postings = P.postings_total;
+    b->direct = P.direct;
+    b->imp = P.all_imp && P.postings_total > 0;
+    if (P.shared) {
         b->shared = true;
-        b->n_share = (uint32_t)share_build.size();
-        b->share_postings = share_postings;
-        ctx->live_shared++;
+        b->n_share = (uint32_t)P.share_build.size();
+        b->share_postings = P.share_postings;
+        ctx->share.live++;
     }
-    b->pk = (all_pk && postings_total > 0) ? ctx->use_packed : 0;
-    for (unsigned s2 = 0; s2 < width; s2++) b->pruned = b->pruned || P.slices[s2].any_pruned;
-
-    // queries cut into many partial rows: joined by k_merge_wide, one workgroup each
-    std::vector<uint32_t> wide_q;
-    if (!direct)
-        for (uint32_t q = 0; q < n_queries; q++)
-            if (merge_is_wide(dq[q].part_count, k)) wide_q.push_back(q);
-    b->n_wide_q = (uint32_t)wide_q.size();
+    b->pk = (P.all_pk && P.postings_total > 0) ? ctx->cfg.use_packed : 0;
+    b->pruned = P.pruned;
+    b->n_wide_q = (uint32_t)P.wide_q.size();
 
     // One device block per batch: [descriptors, uploaded in one copy][scratch][hits | nhits | found, fetched in one copy]
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
+    const BatchPlan::Layout& L = P.layout;   // the descriptor image ...
+    const size_t up_bytes = L.bytes;
+    size_t off = up_bytes;                   // ... and behind it
+    auto place = [&](size_t bytes) { return place_at(off, bytes); };
     const size_t Qn = std::max<uint32_t>(n_queries, 1), Pn = std::max<uint32_t>(b->n_parts, 1);
-    const size_t o_items = place((size_t)n_items * sizeof(DevItem));
-    const size_t o_witems = place((size_t)n_witems * sizeof(DevWItem));
-    const size_t o_terms = place((size_t)n_dterms * sizeof(DevTerm));
-    const size_t o_groups = place((size_t)n_bgroups * sizeof(DevGroup));
-    const size_t o_queries = place(dq.size() * sizeof(dq[0]));
-    const size_t o_segs = place(segs.size() * sizeof(segs[0]));
-    const size_t o_wideq = place(wide_q.size() * 4);
-    const size_t o_share = place(shared ? (share_build.size() + 1) * sizeof(DevShare) : 0);
-    const size_t up_bytes = off;
-    const size_t o_bounds = place(bounds_total * 4);
+    const size_t o_bounds = place(P.bounds_total * 4);
     size_t o_phits = 0, o_pnhits = 0, o_pfound = 0, o_heads = 0;
-    if (!direct) {
+    if (!P.direct) {
         o_phits = place(Pn * k * sizeof(Hit));
         o_pnhits = place(Pn * 4);
         o_pfound = place(Pn * 8);
@@ -1776,16 +1119,16 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
     char* base = nullptr;
     chk(batch_alloc(b, (void**)&base, off));
     if (e == hipSuccess) {
-        b->d_items = (decltype(b->d_items))(base + o_items);
-        b->d_witems = (decltype(b->d_witems))(base + o_witems);
-        b->d_terms = (decltype(b->d_terms))(base + o_terms);
-        b->d_groups = (decltype(b->d_groups))(base + o_groups);
-        b->d_queries = (decltype(b->d_queries))(base + o_queries);
-        b->d_segs = (decltype(b->d_segs))(base + o_segs);
-        b->d_wide_q = (uint32_t*)(base + o_wideq);
-        b->d_share = (DevShare*)(base + o_share);
+        b->d_items = (decltype(b->d_items))(base + L.items);
+        b->d_witems = (decltype(b->d_witems))(base + L.witems);
+        b->d_terms = (decltype(b->d_terms))(base + L.terms);
+        b->d_groups = (decltype(b->d_groups))(base + L.groups);
+        b->d_queries = (decltype(b->d_queries))(base + L.queries);
+        b->d_segs = (decltype(b->d_segs))(base + L.segs);
+        b->d_wide_q = (uint32_t*)(base + L.wideq);
+        b->d_share = (DevShare*)(base + L.share);
         b->d_bounds = (uint32_t*)(base + o_bounds);
-        if (!direct) {
+        if (!P.direct) {
             b->d_part_hits = (Hit*)(base + o_phits);
             b->d_part_nhits = (uint32_t*)(base + o_pnhits);
             b->d_part_found = (uint64_t*)(base + o_pfound);
@@ -1825,103 +1168,14 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
     }
     if (e == hipSuccess && !ctx->up_done) chk(hipEventCreateWithFlags(&ctx->up_done, hipEventDisableTiming));
     if (e == hipSuccess) {
-        // ---- phase C: the descriptors go straight into the pinned staging buffer (or, for a batch too large for it, into
-        // a host vector that is copied array by array), wave items at their place in the launch order ----
+        // ---- the descriptors go straight into the pinned staging buffer (or, for a batch too large for it, into a host
+        // vector that is copied array by array) ----
         const bool staged = ctx->h_up_cap >= up_bytes && ctx->up_done;
         std::vector<char> unstaged;
         if (!staged) unstaged.resize(up_bytes);
         char* hb = staged ? (char*)ctx->h_up : unstaged.data();
-        // The dealing costs host time (a sort per class: +0.2 ms for cfg5's 16384 queries on 8 prepare threads).  A batch small
-        // enough to be prepared by fewer than 4 threads over a cache-resident index gains ~1 % of kernel time from it and would
-        // pay 0.3 ms of single-threaded sorting per 2048 queries — more than the batch's kernel — so it keeps the plain order
-        // (2048-query batches pipelined: 0.71 ms per batch with the dealing, 0.44 without; profiles/r03/final_e2e_*.txt).
-        uint64_t resident_bytes = 0;
-        for (const ns_seg* sg_ : ctx->segs) if (sg_) resident_bytes += sg_->n_postings * 12ull;
-        const bool deal = ctx->order_mode >= 1 && auto_mode && n_class[0] >= 64 && (width >= 4 || resident_bytes > (256ull << 20) || ctx->order_mode >= 2);
-        if (deal && P.share_at.size() < n_witems) P.share_at.resize(n_witems);
-        fork([&](unsigned si) {
-            PrepSlice& S = P.slices[si];
-            DevWItem* wdst = (DevWItem*)(hb + o_witems);
-            for (size_t i = 0; i < S.witems.size(); i++) {
-                DevWItem it = S.witems[i];
-                it.out_slot = direct ? it.query : it.out_slot + S.row_off;
-                const uint32_t bk = S.wbucket[i];
-                const uint32_t at = S.start[((bk & 0x8000u) ? kOrderBuckets : 0) + (bk & 0x7FFFu)]++;
-                wdst[at] = it;
-                if (deal) P.share_at[at] = S.wshare[i];
-            }
-            if (!S.dterms.empty()) std::memcpy(hb + o_terms + (size_t)S.term_off * sizeof(DevTerm), S.dterms.data(), S.dterms.size() * sizeof(DevTerm));
-            if (!S.bgroups.empty()) std::memcpy(hb + o_groups + (size_t)S.bgroup_off * sizeof(DevGroup), S.bgroups.data(), S.bgroups.size() * sizeof(DevGroup));
-            for (uint32_t q = S.q0; q < S.q1; q++) dq[q].part_begin += S.row_off;
-            if (S.q1 > S.q0) std::memcpy(hb + o_queries + (size_t)S.q0 * sizeof(DevQuery), dq.data() + S.q0, (size_t)(S.q1 - S.q0) * sizeof(DevQuery));
-        });
-        // ---- XCD dealing.  The launch order is longest-estimated-run-time first (2048 fine buckets).  Inside a coarse class of
-        // 8 fine buckets (run times within ~19 % of each other) the order is free, and it is used for locality: workgroup i
-        // runs on XCD i % 8, each XCD has its own 4 MB L2, and items that read the same bytes — same segment, same doc range
-        // of the grid, same largest list: the shards of a hot list that dozens of queries of a batch share — should meet
-        // in ONE L2 at about the same time, so that one of them pulls a line from HBM and the others hit it.  The items of a
-        // class are sorted by their locality key (segment, then doc range, then a hash of the largest list), the sorted
-        // sequence is cut into eight equal parts, and XCD x — the launch positions p with p % 8 == x — takes part x in
-        // order: one L2 per part of the doc space, neighbours in time share lists.
-        // Measured (profiles/r03): 20 x 1M-doc index, L2-miss traffic of the cfg5 launch 44.2 -> 31 GB, 7.05 -> 6.70 ms; the
-        // 1M-doc index 2.61 -> 2.56 ms.  (A key quantised to eighths of the doc space lost 3 % there: the exact range matters.)
-        // The classes are spread over the prepare threads; a class of n items costs one sort of n 64-bit words.
-        if (deal) {
-            DevWItem* wd = (DevWItem*)(hb + o_witems);
-            // classes of 8 fine buckets while the index fits the 256 MiB Infinity Cache (an L2 miss is cheap there and the
-            // longest-first order matters more), of 16 when it does not (20 x 1M docs: L2-miss traffic 31.6 -> 28.6 GB at
-            // the same launch time; the 1M-doc index loses 3 % with 32, profiles/r03)
-            const uint32_t shift = ctx->order_coarse_forced ? (uint32_t)ctx->order_coarse : (resident_bytes > (256ull << 20) ? 4u : 3u);
-            const uint32_t n_cls = kOrderBuckets >> shift;
-            if (P.deal_tmp.size() < width) { P.deal_tmp.resize(width); P.deal_key.resize(width); P.deal_alt.resize(width); P.deal_bins.resize(width); }
-            fork([&](unsigned si) {
-                std::vector<DevWItem>& tmp = P.deal_tmp[si];
-                std::vector<uint64_t>& ord = P.deal_key[si];   // (key << 32 | index in the class): sorted = stable by key
-                for (uint32_t c = si; c < n_cls; c += width) {
-                    const uint32_t p0 = P.bucket_pos[c << shift], p1 = P.bucket_pos[(c + 1) << shift];
-                    const uint32_t n = p1 - p0;
-                    if (n < 16) continue;
-                    ord.resize(n);
-                    for (uint32_t i = 0; i < n; i++) ord[i] = ((uint64_t)P.share_at[p0 + i] << 32) | i;
-                    if (n <= 4096) {
-                        std::sort(ord.begin(), ord.end());
-                    } else {
-                        // a large class (all thin items of a batch have about the same run time: 17 000 items in one class of
-                        // cfg5) would keep ONE prepare thread in a comparison sort for ~1 ms: two stable counting passes over
-                        // the key's halves instead (the index in the low word is ascending already)
-                        std::vector<uint64_t>& alt = P.deal_alt[si];
-                        std::vector<uint32_t>& bins = P.deal_bins[si];
-                        alt.resize(n);
-                        bins.resize(65537);
-                        for (int pass = 0; pass < 2; pass++) {
-                            const int sh = 32 + 16 * pass;
-                            std::fill(bins.begin(), bins.end(), 0u);
-                            const uint64_t* src = pass ? alt.data() : ord.data();
-                            uint64_t* dst = pass ? ord.data() : alt.data();
-                            for (uint32_t i = 0; i < n; i++) bins[((src[i] >> sh) & 0xFFFFu) + 1u]++;
-                            for (uint32_t b2 = 0; b2 < 65536; b2++) bins[b2 + 1] += bins[b2];
-                            for (uint32_t i = 0; i < n; i++) dst[bins[(src[i] >> sh) & 0xFFFFu]++] = src[i];
-                        }
-                    }
-                    tmp.assign(wd + p0, wd + p1);
-                    uint32_t cur[8], end[8];
-                    for (uint32_t x = 0; x < 8; x++) { cur[x] = (uint32_t)((uint64_t)n * x / 8); end[x] = (uint32_t)((uint64_t)n * (x + 1) / 8); }
-                    for (uint32_t p = 0; p < n; p++) {
-                        uint32_t x = (p0 + p) & 7u;
-                        for (uint32_t tr = 0; tr < 8 && cur[x] >= end[x]; tr++) x = (x + 1) & 7u;   // a part one item short of its slots
-                        wd[p0 + p] = tmp[(uint32_t)ord[cur[x]++]];
-                    }
-                }
-            });
-        }
-        if (n_items) std::memcpy(hb + o_items, sorted_items.data(), (size_t)n_items * sizeof(DevItem));
-        if (!segs.empty()) std::memcpy(hb + o_segs, segs.data(), segs.size() * sizeof(segs[0]));
-        if (!wide_q.empty()) std::memcpy(hb + o_wideq, wide_q.data(), wide_q.size() * 4);
-        if (shared) {
-            std::memcpy(hb + o_share, share_build.data(), share_build.size() * sizeof(DevShare));
-            const DevShare sentinel{0u, 0u, 0.0f, 0u, (uint32_t)share_postings};
-            std::memcpy(hb + o_share + share_build.size() * sizeof(DevShare), &sentinel, sizeof(DevShare));
-        }
+        P.write(hb);
+        if (!segs.empty()) std::memcpy(hb + L.segs, segs.data(), segs.size() * sizeof(segs[0]));
         if (staged) {
             // a small upload is pulled by a kernel (the pinned buffer is device-addressable): a DMA-engine copy
             // followed by a kernel costs ~11 us of cross-engine hand-over, more than the copy itself
@@ -1952,7 +1206,7 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
         }
     }
     if (e != hipSuccess) {
-        int rc = fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_batch_prepare: %s", hipGetErrorString(e));
+        rc = fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_batch_prepare: %s", hipGetErrorString(e));
         ns_batch_destroy(b);
         return rc;
     }

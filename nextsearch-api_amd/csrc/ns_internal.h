@@ -128,6 +128,8 @@ struct DevQuery {
     uint32_t part_begin;   // first partial-result row of this query
     uint32_t part_count;   // number of partial rows (work items); 0 => no scored terms
 };
+// a query cut into this many partial rows is joined by k_merge_wide (one workgroup) instead of k_merge (ns_kernels.hip)
+constexpr bool merge_is_wide(uint32_t part_count, uint32_t K) { return part_count > 64 && part_count >= K; }
 
 struct Hit {   // == ns_hit
     float    score;

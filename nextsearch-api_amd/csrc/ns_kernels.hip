@@ -410,8 +410,6 @@ __global__ void __launch_bounds__(NT) k_score(const DevItem* __restrict__ items,
 // score >= theta, where theta is (a lower bound of) the K-th largest row HEAD: two 11-bit histogram
 // passes over the heads find it, the prefixes are gathered into LDS, sorted once, and the first K
 // leave.  Cost is independent of K and linear in rows / 256.
-__host__ __device__ inline bool merge_is_wide(uint32_t part_count, uint32_t K) { return part_count > 64 && part_count >= K; }
-
 constexpr int kMergeStage = 2048;   // entries k_merge stages in LDS per query
 __device__ __forceinline__ uint32_t merge_wave_max(uint32_t v) {   // DPP reduction (row_shr / row_bcast forms), wave-uniform result
     v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));
