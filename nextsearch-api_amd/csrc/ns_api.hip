@@ -131,6 +131,27 @@ static int fail(ns_ctx* ctx, int code, const char* fmt, ...) {
             return fail((ctx), NS_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// k_uscore, the unified scoring kernel, over n_items work items of one class (one wave each)
+template <int CB, int TMAX, bool IMP, int PK>
+static void launch_uscore(bool and_mode, uint32_t n_items, hipStream_t st, const DevWItem* items, const DevTerm* terms,
+                          const DevSeg* segs, Hit* hits, uint32_t* nhits, uint64_t* found, uint32_t K) {
+    dim3 grid((n_items + kUscoreWavesPerBlock - 1) / kUscoreWavesPerBlock), block(64 * kUscoreWavesPerBlock);
+    if (and_mode)
+        hipLaunchKernelGGL((k_uscore<512, 192, true, CB, TMAX, IMP, PK>), grid, block, 0, st, items, n_items, terms, segs, hits, nhits, found, K);
+    else
+        hipLaunchKernelGGL((k_uscore<512, 192, false, CB, TMAX, IMP, PK>), grid, block, 0, st, items, n_items, terms, segs, hits, nhits, found, K);
+}
+// ... in the instantiation for the streams the batch reads: term scores precomputed (imp) and / or packed blocks (pk)
+template <int CB, int TMAX>
+static void launch_uscore(bool and_mode, bool imp, int pk, uint32_t n_items, hipStream_t st, const DevWItem* items,
+                          const DevTerm* terms, const DevSeg* segs, Hit* hits, uint32_t* nhits, uint64_t* found, uint32_t K) {
+    if (imp && pk) launch_uscore<CB, TMAX, true, 1>(and_mode, n_items, st, items, terms, segs, hits, nhits, found, K);   // scores come with the block: no norms at all
+    else if (imp) launch_uscore<CB, TMAX, true, 0>(and_mode, n_items, st, items, terms, segs, hits, nhits, found, K);
+    else if (pk == 2) launch_uscore<CB, TMAX, false, 2>(and_mode, n_items, st, items, terms, segs, hits, nhits, found, K);
+    else if (pk == 1) launch_uscore<CB, TMAX, false, 1>(and_mode, n_items, st, items, terms, segs, hits, nhits, found, K);
+    else launch_uscore<CB, TMAX, false, 0>(and_mode, n_items, st, items, terms, segs, hits, nhits, found, K);
+}
+
 template <int HK, int FB>
 static void launch_dscore(bool and_mode, uint32_t n_items, hipStream_t st, const DevWItem* items, const DevTerm* terms,
                           const DevSeg* segs, Hit* hits, uint32_t* nhits, uint64_t* found, uint32_t K) {
@@ -1260,35 +1281,18 @@ extern "C" int ns_batch_run(ns_batch* b, int run_flags) {
     uint64_t* sf = b->direct ? b->o_found : b->d_part_found;
     if (b->n_witems && b->variant == 0) {
         // auto mode: ONE launch; each wave picks the body that suits its item (DevWItem::whole bit 1)
-        dim3 grid((b->n_witems + 3) / 4), block(64 * kUscoreWavesPerBlock);
         // K <= 64: a 128-entry candidate buffer is enough (K + 64 appended per step at most) and its
         // smaller LDS footprint admits more workgroups per CU.  Groups of <= 16 terms (all but exotic
         // queries) run in the instantiation with 16-entry term tables; the rest in the 64-entry one.
-#define NS_U2(CBV, TM, N, PTR, IMPV, PKV)                                                                         \
-        {                                                                                                          \
-            dim3 g_(((N) + kUscoreWavesPerBlock - 1) / kUscoreWavesPerBlock);                                     \
-            if (and_mode) hipLaunchKernelGGL((k_uscore<512, 192, true, CBV, TM, IMPV, PKV>), g_, block, 0, st, (PTR), (N), b->d_terms, b->d_segs, sh, sn, sf, b->K); \
-            else hipLaunchKernelGGL((k_uscore<512, 192, false, CBV, TM, IMPV, PKV>), g_, block, 0, st, (PTR), (N), b->d_terms, b->d_segs, sh, sn, sf, b->K);         \
-        }
-#define NS_U(CBV, TM, N, PTR)                                                                                      \
-        {                                                                                                          \
-            if (b->imp && b->pk) NS_U2(CBV, TM, N, PTR, true, 1)          /* scores come with the block: no norms at all */ \
-            else if (b->imp) NS_U2(CBV, TM, N, PTR, true, 0)                                                       \
-            else if (b->pk == 2) NS_U2(CBV, TM, N, PTR, false, 2)                                                  \
-            else if (b->pk == 1) NS_U2(CBV, TM, N, PTR, false, 1)                                                  \
-            else NS_U2(CBV, TM, N, PTR, false, 0)                                                                  \
-        }
         const uint32_t n_narrow = b->n_class[0], n_wide = b->n_witems - b->n_class[0];
-        (void)grid;
+        const DevWItem* wide = b->d_witems + n_narrow;
         if (b->K <= 32) {   // the buffer is shrunk to K when it holds more than CB - 64 entries: CB = 128 needs K well below 64
-            if (n_narrow) NS_U(128, 16, n_narrow, b->d_witems);
-            if (n_wide) NS_U(128, 64, n_wide, b->d_witems + n_narrow);
+            if (n_narrow) launch_uscore<128, 16>(and_mode, b->imp, b->pk, n_narrow, st, b->d_witems, b->d_terms, b->d_segs, sh, sn, sf, b->K);
+            if (n_wide) launch_uscore<128, 64>(and_mode, b->imp, b->pk, n_wide, st, wide, b->d_terms, b->d_segs, sh, sn, sf, b->K);
         } else {
-            if (n_narrow) NS_U(256, 16, n_narrow, b->d_witems);
-            if (n_wide) NS_U(256, 64, n_wide, b->d_witems + n_narrow);
+            if (n_narrow) launch_uscore<256, 16>(and_mode, b->imp, b->pk, n_narrow, st, b->d_witems, b->d_terms, b->d_segs, sh, sn, sf, b->K);
+            if (n_wide) launch_uscore<256, 64>(and_mode, b->imp, b->pk, n_wide, st, wide, b->d_terms, b->d_segs, sh, sn, sf, b->K);
         }
-#undef NS_U
-#undef NS_U2
     }
 #ifdef NS_VARIANTS
     else if (b->n_witems) {

@@ -171,21 +171,9 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         base = (uint32_t)tm.list_off;
         idf_bits = __float_as_uint(tm.idf);
         wq_bits = __float_as_uint(tm.weight);
-        end = tm.count;
-        if (!(it.whole & 1u)) {
-            if ((it.whole & 64u) && tm.skip != 0u) {
-                // the range's ends come from the list's skip table (the host put doc_lo, and doc_hi unless it is n_docs, on the grid)
-                const gp_u32 sk = (gp_u32)seg.skips + (tm.skip - 1u);
-                cur = sk[it.doc_lo / kSkipDocs] - base;
-                end = sk[(it.doc_hi + (kSkipDocs - 1u)) / kSkipDocs] - base;
-            } else {
-                const uint2* lst = seg.postings + tm.list_off;
-                list_range(lst, tm.count, it.doc_lo, it.doc_hi, seg.n_docs, cur, end);
-            }
-            if (end < cur) end = cur;
-        }
-        cur += base;   // absolute posting indices from here on
-        end += base;
+        const uint2 r = item_list_range(it, seg, tm);
+        cur = r.x + base;   // absolute posting indices from here on
+        end = r.y + base;
         tab[lane] = make_uint4(idf_bits, wq_bits, 0u, 0u);   // .z/.w: this super-batch's window, written below
     }
     // ---- the driver: the term with the most postings in this item's range (fixed for the item) ----
@@ -219,50 +207,8 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
 #endif
     uint32_t lo = it.doc_lo;
     const uint32_t last_doc = it.doc_hi - 1;   // host guarantees doc_hi > doc_lo and doc_hi <= n_docs
-    float theta = -__builtin_inff();
-    uint32_t ncand = 0;
-    uint32_t nsorted = 0;   // leading candidates already in descending order (left by the last shrink)
+    WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one super-batch
     uint32_t found_s = 0;      // `found`, wave-uniform: private driver postings and owners of table entries, counted by ballots
-    bool ge_mode = false;   // a shrink happened inside the current super-batch: ties with theta may still win on docId
-
-    // offer (score, doc) of the lanes where `cond` holds to the candidate buffer
-#define NS_OFFER(cond, scorev, docv)                                                               \
-    {                                                                                              \
-        bool qf_ = (cond) && ((scorev) > theta);                                                   \
-        if (ge_mode) qf_ = (cond) && ((scorev) >= theta);   /* rare: after a shrink inside this super-batch */ \
-        unsigned long long mask_ = wballot(qf_);                                                   \
-        if (mask_ != 0ull) {                                                                       \
-            uint32_t n_ = (uint32_t)__popcll(mask_);                                               \
-            if (ncand + n_ > (uint32_t)CB) {                                                       \
-                ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);                                  \
-                ge_mode = true;                                                                    \
-                qf_ = (cond) && ((scorev) >= theta);                                               \
-                mask_ = wballot(qf_);                                                              \
-                n_ = (uint32_t)__popcll(mask_);                                                    \
-            }                                                                                      \
-            if (qf_) cand[ncand + lanes_below(mask_)] = make_key((scorev), (docv));                \
-            ncand += n_;                                                                           \
-        }                                                                                          \
-    }
-
-    // the same with the condition given as a lane mask in SGPRs
-#define NS_OFFER_M(condm, scorev, docv)                                                            \
-    {                                                                                              \
-        uint64_t mask_ = wballot((scorev) > theta);                                                \
-        if (ge_mode) mask_ = wballot((scorev) >= theta);   /* rare: only after a shrink inside this super-batch */ \
-        mask_ &= (condm);                                                                          \
-        if (mask_ != 0ull) {                                                                       \
-            uint32_t n_ = (uint32_t)__popcll(mask_);                                               \
-            if (ncand + n_ > (uint32_t)CB) {                                                       \
-                ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);                                  \
-                ge_mode = true;                                                                    \
-                mask_ = (condm) & wballot((scorev) >= theta);                                      \
-                n_ = (uint32_t)__popcll(mask_);                                                    \
-            }                                                                                      \
-            if (__builtin_amdgcn_inverse_ballot_w64(mask_)) cand[ncand + lanes_below(mask_)] = make_key((scorev), (docv)); \
-            ncand += n_;                                                                           \
-        }                                                                                          \
-    }
 
     // Foreign windows: sizes proportional to what is left of each foreign list (all windows span about
     // the same doc range), at most FB postings in total; one docId probe per window (its last posting).
@@ -284,7 +230,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
     NS_PLAN_FOREIGN();
     wave_sync();
     for (;;) {
-        ge_mode = false;
+        top.begin_step();
         NS_CNT(1, 1);
         // ================= 1. foreign windows of this super-batch (planned one super-batch ahead) ==========
         const uint32_t w = w_n;
@@ -720,7 +666,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                 found_s += cnt - r_hits;   // every taken posting that did not join a table entry is a doc of its own
 #pragma unroll
                 for (int j = 0; j < DE; j++) {
-                    NS_OFFER_M(dokm[j], dx[j], ps[j].x);
+                    top.offer_mask_stream(dokm[j], dx[j], ps[j].x);
                 }
             }
             NS_CNT(9, cnt);                     // driver postings consumed
@@ -753,11 +699,11 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                     if (AND) mcnt[j * 64 + lane] = 0;
                 }
                 found_s += (uint32_t)__popcll(wballot(scored[j]));
-                NS_OFFER(scored[j], fin[j], fdoc[j]);
+                top.offer(scored[j], fin[j], fdoc[j]);
             }
             wave_sync();
         }
-        if (ncand > (uint32_t)(CB - 64)) ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);   // keep room for one more step of offers
+        top.keep_room();
 
         if (hi >= last_doc) break;
         if (Rf == 0 && d_cur >= d_end) break;
@@ -765,8 +711,6 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         lo = hi + 1;
     }
 #undef NS_FOREIGN_RMW
-#undef NS_OFFER
-#undef NS_OFFER_M
 #undef NS_PLAN_FOREIGN
 #undef NS_TAG
 #undef NS_IDENT
@@ -775,29 +719,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
 #ifdef NS_COUNT
     const unsigned long long cyc_t1_ = __builtin_readcyclecounter();
 #endif
-    // ---- this item's top-K ----
-    wave_sync();
-    ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-    const uint32_t n = min(ncand, K);
-    Hit* oh = out_hits + (uint64_t)it.out_slot * K;
-    for (uint32_t i = lane; i < K; i += 64) {
-        Hit h;
-        if (i < n) {
-            const uint64_t key = cand[i];
-            h.score = unorder_bits((uint32_t)(key >> 32));
-            h.seg = it.seg;
-            h.doc = 0xFFFFFFFFu - (uint32_t)key;
-        } else {
-            h.score = -__builtin_inff();
-            h.seg = 0xFFFFFFFFu;
-            h.doc = 0xFFFFFFFFu;
-        }
-        oh[i] = h;
-    }
-    if (lane == 63) {
-        out_nhits[it.out_slot] = n;
-        out_found[it.out_slot] = (uint64_t)found_s;
-    }
+    top.write_out(it.seg, it.out_slot, found_s, out_hits, out_nhits, out_found);
 #ifdef NS_COUNT
     cnt_[17] = __builtin_readcyclecounter() - cyc_t0_;
     cnt_[18] = __builtin_readcyclecounter() - cyc_t1_;

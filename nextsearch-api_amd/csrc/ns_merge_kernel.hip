@@ -46,19 +46,9 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
         const uint32_t base = (uint32_t)tm.list_off;
         idf_bits = __float_as_uint(tm.idf);
         wq_bits = __float_as_uint(tm.weight);
-        end = tm.count;
-        if (!(it.whole & 1u)) {
-            if ((it.whole & 64u) && tm.skip != 0u) {
-                const gp_u32 sk = (gp_u32)seg.skips + (tm.skip - 1u);
-                cur = sk[it.doc_lo / kSkipDocs] - base;
-                end = sk[(it.doc_hi + (kSkipDocs - 1u)) / kSkipDocs] - base;
-            } else {
-                list_range(seg.postings + tm.list_off, tm.count, it.doc_lo, it.doc_hi, seg.n_docs, cur, end);
-            }
-            if (end < cur) end = cur;
-        }
-        cur += base;
-        end += base;
+        const uint2 r = item_list_range(it, seg, tm);
+        cur = r.x + base;
+        end = r.y + base;
     }
     // A = the list with more postings in the range (ties: the first term); its index decides the accumulation order
     const uint32_t rem0 = rdlane(end, 0) - rdlane(cur, 0), rem1 = rdlane(end, 1) - rdlane(cur, 1);
@@ -70,32 +60,14 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
     const bool a_first = ai < bi;   // A precedes B in query-term order
 
     const uint32_t last_doc = it.doc_hi - 1;
-    float theta = -__builtin_inff();
-    uint32_t ncand = 0, nsorted = 0, found_s = 0;
-    bool ge_mode = false;
-
-#define NS_MOFFER(condm, scorev, docv)                                                             \
-    {                                                                                              \
-        uint64_t mask_ = ge_mode ? wballot((scorev) >= theta) : wballot((scorev) > theta);         \
-        mask_ &= (condm);                                                                          \
-        if (mask_ != 0ull) {                                                                       \
-            uint32_t n_ = (uint32_t)__popcll(mask_);                                               \
-            if (ncand + n_ > (uint32_t)CB) {                                                       \
-                ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);                  \
-                ge_mode = true;   /* ties with theta may still win on docId inside this step */    \
-                mask_ = (condm) & wballot((scorev) >= theta);                                      \
-                n_ = (uint32_t)__popcll(mask_);                                                    \
-            }                                                                                      \
-            if (__builtin_amdgcn_inverse_ballot_w64(mask_)) cand[ncand + lanes_below(mask_)] = make_key((scorev), (docv)); \
-            ncand += n_;                                                                           \
-        }                                                                                          \
-    }
+    WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one merge step
+    uint32_t found_s = 0;
 
     wave_sync();
     for (;;) {
         const uint32_t a_rem = a_end - a_cur, b_rem = b_end - b_cur;
         if (a_rem == 0u && b_rem == 0u) break;
-        ge_mode = false;
+        top.begin_step();
         const uint32_t na = min(a_rem, (uint32_t)(DE * 64));
         // B's window: what B is expected to hold under one round of A (the lists thin out alike), a quarter more, whole chunks
         uint32_t nb;
@@ -239,7 +211,7 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
                 uint64_t priv = ta[j];
                 if (n_match != 0u) priv &= ~wballot(l_docs[j * 64 + lane] == kMark);   // scored by B's lane
                 const float s = 0.0f + xa[j];   // the reference's accumulators start at +0.0f (:480)
-                NS_MOFFER(priv, s, pa[j].x);
+                top.offer_mask(priv, s, pa[j].x);
             }
         } else {
             found_s += n_match;   // conjunctive extension: both term refs hit the doc
@@ -252,38 +224,15 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
             const float x1 = both ? (a_first ? xam[j] : xb[j]) : xb[j];
             float s = 0.0f + x1;
             if (both) s = s + (a_first ? xb[j] : xam[j]);
-            NS_MOFFER(who, s, pb[j].x);
+            top.offer_mask(who, s, pb[j].x);
         }
         wave_sync();   // the next step rewrites the LDS arrays
         a_cur += cnt_a;
         b_cur += cnt_b;
-        if (ncand > (uint32_t)(CB - 64)) ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
+        top.keep_room();
     }
-#undef NS_MOFFER
 
-    // ---- this item's top-K ----
-    wave_sync();
-    ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-    const uint32_t n = min(ncand, K);
-    Hit* oh = out_hits + (uint64_t)it.out_slot * K;
-    for (uint32_t i = lane; i < K; i += 64) {
-        Hit h;
-        if (i < n) {
-            const uint64_t key = cand[i];
-            h.score = unorder_bits((uint32_t)(key >> 32));
-            h.seg = it.seg;
-            h.doc = 0xFFFFFFFFu - (uint32_t)key;
-        } else {
-            h.score = -__builtin_inff();
-            h.seg = 0xFFFFFFFFu;
-            h.doc = 0xFFFFFFFFu;
-        }
-        oh[i] = h;
-    }
-    if (lane == 63) {
-        out_nhits[it.out_slot] = n;
-        out_found[it.out_slot] = (uint64_t)found_s;
-    }
+    top.write_out(it.seg, it.out_slot, found_s, out_hits, out_nhits, out_found);
 }
 
 }  // namespace ns

@@ -70,17 +70,9 @@ __device__ __forceinline__ void pscore_body(const DevWItem& it, const DevTerm* _
         idf_bits = __float_as_uint(tm.idf);
         wq_bits = __float_as_uint(tm.weight);
         bmx0 = tm.bmx - 1u;
-        end = tm.count;
-        if (!(it.whole & 1u)) {
-            if ((it.whole & 64u) && tm.skip != 0u) {
-                const gp_u32 sk = (gp_u32)seg.skips + (tm.skip - 1u);
-                cur = sk[it.doc_lo / kSkipDocs] - base;
-                end = sk[(it.doc_hi + (kSkipDocs - 1u)) / kSkipDocs] - base;
-            } else {
-                list_range(seg.postings + tm.list_off, tm.count, it.doc_lo, it.doc_hi, seg.n_docs, cur, end);
-            }
-            if (end < cur) end = cur;
-        }
+        const uint2 r = item_list_range(it, seg, tm);
+        cur = r.x;
+        end = r.y;
     }
     const uint32_t l_base = rdlane(base, 0);
     const uint32_t r_cur = rdlane(cur, 0), r_end = rdlane(end, 0);   // list-relative posting range of this item
@@ -88,8 +80,9 @@ __device__ __forceinline__ void pscore_body(const DevWItem& it, const DevTerm* _
     const float d_wq = __uint_as_float(rdlane(wq_bits, 0));
     const gp_f32 bmx = (gp_f32)seg.blockmax + rdlane(bmx0, 0);
 
-    float theta = -__builtin_inff();
-    uint32_t ncand = 0, nsorted = 0;
+    // docIds ascend from block to block and inside a block: whoever is in the buffer has a smaller docId than the posting
+    // offered now, so a tie with theta loses — `>` is exact (no `>=` mode in this body)
+    WaveTopK<CB, true> top(cand, K, lane);
     uint32_t n_read = 0;   // blocks actually read (diagnostic builds)
     (void)n_read;
     wave_sync();
@@ -100,11 +93,11 @@ __device__ __forceinline__ void pscore_body(const DevWItem& it, const DevTerm* _
             const uint32_t myb = bb + (uint32_t)lane;
             float bound = -__builtin_inff();
             if (myb <= blk_last) bound = d_wq * bmx[myb];   // the score the block's best posting has: the fp32 product is monotone for w > 0
-            uint64_t live = wballot(bound > theta);
+            uint64_t live = wballot(bound > top.theta);
             while (live != 0ull) {
                 const uint32_t l = (uint32_t)__builtin_ctzll(live);
                 live &= live - 1ull;
-                if (!(__uint_as_float(rdlane(__float_as_uint(bound), l)) > theta)) continue;   // theta has risen since the ballot
+                if (!(__uint_as_float(rdlane(__float_as_uint(bound), l)) > top.theta)) continue;   // theta has risen since the ballot
                 const uint32_t b = bb + l;
                 const uint32_t p0 = max(r_cur, b * kBmxBlock), p1 = min(r_end, (b + 1u) * kBmxBlock);
                 const uint32_t n = p1 - p0;   // 1 .. 256
@@ -134,48 +127,16 @@ __device__ __forceinline__ void pscore_body(const DevWItem& it, const DevTerm* _
                     const uint32_t left = (n > (uint32_t)(j * 64)) ? (n - (uint32_t)(j * 64)) : 0u;   // scalar
                     if (left == 0u) continue;
                     const uint64_t nmask = (left >= 64u) ? ~0ull : ((1ull << left) - 1ull);
-                    // docIds ascend from block to block and inside a block: whoever is in the buffer has a smaller docId than
-                    // the posting offered now, so a tie with theta loses — `>` is exact (no `>=` mode in this body)
-                    uint64_t m = wballot(dx[j] > theta) & nmask;
-                    if (m == 0ull) continue;
-                    uint32_t c = (uint32_t)__popcll(m);
-                    if (ncand + c > (uint32_t)CB) {
-                        ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-                        m = wballot(dx[j] > theta) & nmask;
-                        c = (uint32_t)__popcll(m);
-                    }
-                    if (__builtin_amdgcn_inverse_ballot_w64(m)) cand[ncand + lanes_below(m)] = make_key(dx[j], ps[j].x);
-                    ncand += c;
+                    top.offer_mask(nmask, dx[j], ps[j].x);
                 }
                 // theta is what prunes: raise it as soon as the buffer holds K candidates that the last shrink has not seen
-                if (ncand >= K && ncand - nsorted >= max(16u, K >> 2)) ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
+                if (top.ncand >= K && top.ncand - top.nsorted >= max(16u, K >> 2)) top.shrink();
             }
         }
     }
 
-    // ---- this item's top-K ----
-    wave_sync();
-    ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-    const uint32_t n = min(ncand, K);
-    Hit* oh = out_hits + (uint64_t)it.out_slot * K;
-    for (uint32_t i = lane; i < K; i += 64) {
-        Hit h;
-        if (i < n) {
-            const uint64_t key = cand[i];
-            h.score = unorder_bits((uint32_t)(key >> 32));
-            h.seg = it.seg;
-            h.doc = 0xFFFFFFFFu - (uint32_t)key;
-        } else {
-            h.score = -__builtin_inff();
-            h.seg = 0xFFFFFFFFu;
-            h.doc = 0xFFFFFFFFu;
-        }
-        oh[i] = h;
-    }
-    if (lane == 63) {
-        out_nhits[it.out_slot] = n;
-        out_found[it.out_slot] = (uint64_t)(r_end - r_cur);   // one list: every posting of the range is a doc of its own (:495)
-    }
+    top.write_out(it.seg, it.out_slot, r_end - r_cur,   // found: one list, every posting of the range is a doc of its own (:495)
+                  out_hits, out_nhits, out_found);
 }
 
 }  // namespace ns

@@ -95,9 +95,7 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
     const uint64_t gridm = grid ? wballot(on_grid) : 0ull;
 
     const uint32_t last_doc = it.doc_hi - 1;   // host guarantees doc_hi > doc_lo and doc_hi <= n_docs
-    float theta = -__builtin_inff();
-    uint32_t ncand = 0;
-    uint32_t nsorted = 0;   // leading candidates already in descending order (left by the last shrink)
+    WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one tile
     uint32_t found_s = 0;   // wave-uniform count (popcounts of ballots)
 #ifdef NS_COUNT
     unsigned long long tc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -313,7 +311,7 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
         }
 
         // ---- read the tile back: candidates, reset (and, for the conjunctive extension, found) ----
-        bool ge_mode = false;   // after a shrink INSIDE this tile, ties with theta may still win on docId
+        top.begin_step();
 #ifdef NS_COUNT
         const unsigned long long trb0_ = __builtin_readcyclecounter();
 #endif
@@ -329,7 +327,7 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
             // one max + one compare per four slots decides whether anything here can be offered.
             if (!AND) {
                 const float mx = __builtin_fmaxf(__builtin_fmaxf(vv[0], vv[1]), __builtin_fmaxf(vv[2], vv[3]));
-                if ((ge_mode ? wballot(mx >= theta) : wballot(mx > theta)) == 0ull) continue;
+                if ((top.ge_mode ? wballot(mx >= top.theta) : wballot(mx > top.theta)) == 0ull) continue;
             }
             uint64_t scm[4];
             uint64_t anyq = 0ull;
@@ -340,30 +338,16 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
                     scm[c] &= wballot(((cw >> (8 * c)) & 0xFFu) == T);   // conjunctive extension
                     found_s += (uint32_t)__popcll(scm[c]);
                 }
-                anyq |= scm[c] & wballot(vv[c] > theta);
+                anyq |= scm[c] & wballot(vv[c] > top.theta);
             }
             if (anyq != 0ull) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    uint64_t mask = scm[c] & (ge_mode ? wballot(vv[c] >= theta) : wballot(vv[c] > theta));
-                    if (mask != 0ull) {
-                        uint32_t n = (uint32_t)__popcll(mask);
-                        if (ncand + n > (uint32_t)CB) {
-                            ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-                            ge_mode = true;
-                            mask = scm[c] & wballot(vv[c] >= theta);
-                            n = (uint32_t)__popcll(mask);
-                        }
-                        if (__builtin_amdgcn_inverse_ballot_w64(mask))
-                            cand[ncand + lanes_below(mask)] = make_key(vv[c], tile_lo + (uint32_t)((g * 64 + lane) * 4 + c));
-                        ncand += n;
-                    }
-                }
+                for (int c = 0; c < 4; c++) top.offer_mask(scm[c], vv[c], tile_lo + (uint32_t)((g * 64 + lane) * 4 + c));
             }
         }
         }
         wave_sync();
-        if (ncand > (uint32_t)(CB - 64)) ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);   // keep room for one more step of offers
+        top.keep_room();
 #ifdef NS_COUNT
         NS_TCNT(10, __builtin_readcyclecounter() - trb0_);
 #endif
@@ -372,29 +356,7 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
 #undef NS_ROUND_SIZE
 #undef NS_TILE_HEADER
 
-    // ---- this item's top-K ----
-    wave_sync();
-    ncand = wave_shrink_cb<CB>(cand, ncand, nsorted, theta, K, lane);
-    const uint32_t n = min(ncand, K);
-    Hit* oh = out_hits + (uint64_t)it.out_slot * K;
-    for (uint32_t i = lane; i < K; i += 64) {
-        Hit h;
-        if (i < n) {
-            const uint64_t key = cand[i];
-            h.score = unorder_bits((uint32_t)(key >> 32));
-            h.seg = it.seg;
-            h.doc = 0xFFFFFFFFu - (uint32_t)key;
-        } else {
-            h.score = -__builtin_inff();
-            h.seg = 0xFFFFFFFFu;
-            h.doc = 0xFFFFFFFFu;
-        }
-        oh[i] = h;
-    }
-    if (lane == 63) {
-        out_nhits[it.out_slot] = n;
-        out_found[it.out_slot] = (uint64_t)found_s;
-    }
+    top.write_out(it.seg, it.out_slot, found_s, out_hits, out_nhits, out_found);
 #ifdef NS_COUNT
     NS_TCNT(6, T);
     NS_TCNT(7, __builtin_readcyclecounter() - tc_t0_);

@@ -1,6 +1,7 @@
-// Wave-level primitives shared by the scoring bodies (ns_driver_kernel.hip, ns_tile_kernel.hip): LDS ordering
-// fence, DPP reductions and scans, ballot helpers, the wave bitonic sort / merge of the candidate buffer, the exact
-// short form of the BM25 division, list range searches, address-space-qualified pointer types, and k_pnorm.
+// Wave-level primitives shared by the scoring bodies (ns_driver_kernel.hip, ns_tile_kernel.hip, ns_merge_kernel.hip,
+// ns_prune_kernel.hip): LDS ordering fence, DPP reductions and scans, ballot helpers, the register sort of the candidate
+// buffer and the wave's running top-K built on it (WaveTopK), the exact short form of the BM25 division, list range
+// searches, address-space-qualified pointer types, and k_pnorm.
 // (The wave-private batch kernel k_wscore that used to live here — round 1's second design — was retired in
 // round 2: the driver-stream and doc-tile bodies superseded it.)
 #pragma once
@@ -19,111 +20,17 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = min(v, (uint32_t)__shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// in-LDS bitonic sort (descending) of a[0..P), P a power of two, by ONE wave
-__device__ __forceinline__ void wave_bitonic(uint64_t* a, uint32_t P, int lane, bool ascending) {
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t q = lane; q < (P >> 1); q += 64) {
-                uint32_t i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-                uint32_t p = i | j;
-                uint64_t x = a[i], y = a[p];
-                bool desc = ((i & k) == 0) != ascending;
-                if (desc ? (x < y) : (x > y)) { a[i] = y; a[p] = x; }
-            }
-            wave_sync();
-        }
-    }
-}
-__device__ __forceinline__ void wave_bitonic_desc(uint64_t* a, uint32_t P, int lane) { wave_bitonic(a, P, lane, false); }
-// a[0..P) is bitonic (here: a descending run followed by an ascending one): the last log2(P) stages of
-// the sorting network leave it sorted descending
-__device__ __forceinline__ void wave_bitonic_merge_desc(uint64_t* a, uint32_t P, int lane) {
-    for (uint32_t j = P >> 1; j > 0; j >>= 1) {
-        for (uint32_t q = lane; q < (P >> 1); q += 64) {
-            uint32_t i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-            uint32_t p = i | j;
-            uint64_t x = a[i], y = a[p];
-            if (x < y) { a[i] = y; a[p] = x; }
-        }
-        wave_sync();
-    }
-}
-
-// Sort the wave's candidates, keep the best min(n, K), raise theta to the K-th best.
-// Returns (theta bits << 32) | new n  (by value: a reference would push theta to scratch).
-__device__ __noinline__ uint64_t wave_shrink_packed(uint64_t* cand, uint32_t n, uint32_t theta_bits, uint32_t K, int lane) {
-    uint32_t P = 2;
-    while (P < n) P <<= 1;
-    for (uint32_t i = n + lane; i < P; i += 64) cand[i] = 0;   // padding sorts last
-    wave_sync();
-    wave_bitonic_desc(cand, P, lane);
-    if (n >= K) {
-        theta_bits = __float_as_uint(unorder_bits((uint32_t)(cand[K - 1] >> 32)));   // same address in all lanes: broadcast
-        n = K;
-    }
-    return ((uint64_t)theta_bits << 32) | n;
-}
-// The same for the 256-entry buffer (K > 32), where the buffer is shrunk every ~90 new candidates.
-// `sorted`: the first `sorted` entries are already in descending order (what the previous shrink
-// left; new candidates are appended behind them).  With 129..256 entries of which at most 128 are new,
-// only the new ones are sorted (128-entry network, ascending) and merged with the old run (8 stages
-// over 256): 44 compare-exchange steps per lane instead of 72.
-__device__ __noinline__ uint64_t wave_shrink_merge_packed(uint64_t* cand, uint32_t n, uint32_t sorted, uint32_t theta_bits, uint32_t K, int lane) {
-    if (sorted > 0 && sorted <= 128u && n > 128u && n - sorted <= 128u) {
-        const uint32_t nn = n - sorted;
-        uint64_t v0 = 0, v1 = 0;   // 0 = padding: sorts last descending, first ascending
-        if ((uint32_t)lane < nn) v0 = cand[sorted + lane];
-        if ((uint32_t)(64 + lane) < nn) v1 = cand[sorted + 64 + lane];
-        wave_sync();
-        for (uint32_t i = sorted + lane; i < 128u; i += 64) cand[i] = 0;
-        cand[128 + lane] = v0;
-        cand[192 + lane] = v1;
-        wave_sync();
-        wave_bitonic(cand + 128, 128, lane, true);
-        wave_bitonic_merge_desc(cand, 256, lane);
-    } else {
-        uint32_t P = 2;
-        while (P < n) P <<= 1;
-        for (uint32_t i = n + lane; i < P; i += 64) cand[i] = 0;   // padding sorts last
-        wave_sync();
-        wave_bitonic_desc(cand, P, lane);
-    }
-    if (n >= K) {
-        theta_bits = __float_as_uint(unorder_bits((uint32_t)(cand[K - 1] >> 32)));
-        n = K;
-    }
-    return ((uint64_t)theta_bits << 32) | n;
-}
-__device__ __forceinline__ uint32_t wave_shrink(uint64_t* cand, uint32_t n, float& theta, uint32_t K, int lane) {
-    uint64_t r = wave_shrink_packed(cand, n, __float_as_uint(theta), K, lane);
-    // wave-uniform by construction; telling the compiler keeps theta, the candidate count and every
-    // decision that depends on them in SGPRs (scalar branches instead of exec-masked vector code)
-    theta = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(r >> 32)));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r);
-}
-// CB-aware form used by the scoring bodies: the merge variant (and its `sorted` bookkeeping) exists only in
-// the 256-entry instantiations; `sorted` is updated to the new count (a shrink leaves a descending run)
 // ---- the candidate buffer sorted in REGISTERS ----
-// The in-LDS network above pays an LDS round trip per stage (72 stages over 256 entries: the shrink of a K = 100 batch
-// took a third of its doc-tile items' time).  Here lane l holds entries l*R .. l*R + R - 1 (R = CB / 64): the stages with
+// Round 1's in-LDS bitonic network paid an LDS round trip per stage (72 stages over 256 entries: the shrink of a K = 100
+// batch took a third of its doc-tile items' time).  Here lane l holds entries l*R .. l*R + R - 1 (R = CB / 64): the stages with
 // a partner distance below R are compare-exchanges between registers of one lane, the others exchange with lane l ^ m
 // (quad DPP for m = 1, 2; the LDS crossbar without touching memory — ds_swizzle / ds_bpermute — for m = 4 .. 32).
-// Keys are unique except for the zero padding, so every correct network yields the same order as the one above.
+// Keys are unique except for the zero padding, so every correct sorting network yields the same order.
 template <int M>
 __device__ __forceinline__ uint32_t lane_xor_u32(uint32_t v, int lane) {
     if constexpr (M == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);        // quad_perm [1,0,3,2]
@@ -183,6 +90,8 @@ __device__ __forceinline__ void wave_sort_desc_regs(uint64_t* cand, uint32_t n, 
     for (int r = 0; r < R; r++) cand[lane * R + r] = k[r];
     wave_sync();
 }
+// Sort the wave's candidates, keep the best min(n, K), raise theta to the K-th best.
+// Returns (theta bits << 32) | new n  (by value: a reference would push theta to scratch).
 template <int CB>
 __device__ __noinline__ uint64_t wave_shrink_regs_packed(uint64_t* cand, uint32_t n, uint32_t theta_bits, uint32_t K, int lane) {
     wave_sync();
@@ -194,19 +103,132 @@ __device__ __noinline__ uint64_t wave_shrink_regs_packed(uint64_t* cand, uint32_
     return ((uint64_t)theta_bits << 32) | n;
 }
 
-template <int CB>
-__device__ __forceinline__ uint32_t wave_shrink_cb(uint64_t* cand, uint32_t n, uint32_t& sorted, float& theta, uint32_t K, int lane) {
-    static_assert(CB == 128 || CB == 256, "candidate buffer of 128 or 256 entries");
-    const uint64_t r = wave_shrink_regs_packed<CB>(cand, n, __float_as_uint(theta), K, lane);
-    // wave-uniform by construction; telling the compiler keeps theta, the candidate count and every
-    // decision that depends on them in SGPRs (scalar branches instead of exec-masked vector code)
-    theta = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(r >> 32)));
-    sorted = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r);
-    return sorted;
-}
-
 // ballot straight from the compare (HIP's __ballot goes through an int and costs two extra vector instructions)
 __device__ __forceinline__ uint64_t wballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
+// ---- the wave's running top-K, kept the same way by every scoring body ----
+// A buffer of CB LDS entries (make_key: higher score first, then smaller docId; CB a power of two >= K + 64) takes the
+// candidates above theta, the K-th best score as of the last shrink.  A shrink sorts the buffer, keeps its best K and
+// raises theta; it runs when an offer would overflow the buffer, and between steps when fewer than 64 entries are free.
+// The tie rule decides whether results come out in the canonical order (score desc, seg asc, doc asc): a body offers the
+// docs of each step (super-batch, tile, merge step) above the docs of every earlier step, so a score equal to theta loses
+// on docId and `>` is exact — until a shrink INSIDE the step leaves docs of the same step in the buffer: then ties may
+// still win on docId, and offers take `>=` (ge_mode) until the step ends.  STRICT: the body offers its docs in ascending
+// order throughout (pscore_body), so `>` stays exact after any shrink.
+// All members inline into the body; theta and the counts are wave-uniform and stay in SGPRs.
+template <int CB, bool STRICT = false>
+struct WaveTopK {
+    static_assert(CB == 128 || CB == 256, "candidate buffer of 128 or 256 entries");
+    uint64_t* const cand;
+    const uint32_t K;
+    const int lane;
+    float theta = -__builtin_inff();
+    uint32_t ncand = 0;
+    uint32_t nsorted = 0;    // leading candidates already in descending order (left by the last shrink)
+    bool ge_mode = false;    // a shrink happened inside the current step
+
+    __device__ __forceinline__ WaveTopK(uint64_t* c, uint32_t k, int l) : cand(c), K(k), lane(l) {}
+
+    __device__ __forceinline__ void begin_step() { ge_mode = false; }
+
+    __device__ __forceinline__ void shrink() {
+        // lane & 63 == lane: the range [0, 64) stays visible to the compiler at this out-of-line call (a field loses it, and
+        // wave_shrink_regs_packed then compiles to other code)
+        const uint64_t r = wave_shrink_regs_packed<CB>(cand, ncand, __float_as_uint(theta), K, lane & 63);
+        // wave-uniform by construction; telling the compiler keeps theta, the candidate count and every
+        // decision that depends on them in SGPRs (scalar branches instead of exec-masked vector code)
+        theta = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(r >> 32)));
+        nsorted = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r);
+        ncand = nsorted;
+    }
+
+    // keep room for one more step of offers
+    __device__ __forceinline__ void keep_room() {
+        if (ncand > (uint32_t)(CB - 64)) shrink();
+    }
+
+    // offer (score, doc) of the lanes where `cond` holds
+    __device__ __forceinline__ void offer(bool cond, float score, uint32_t doc) {
+        bool q = cond && (score > theta);
+        if (!STRICT && ge_mode) q = cond && (score >= theta);   // rare: after a shrink inside this step
+        uint64_t mask = wballot(q);
+        if (mask != 0ull) {
+            uint32_t n = (uint32_t)__popcll(mask);
+            if (ncand + n > (uint32_t)CB) {
+                shrink();
+                if (!STRICT) ge_mode = true;
+                q = cond && (STRICT ? score > theta : score >= theta);
+                mask = wballot(q);
+                n = (uint32_t)__popcll(mask);
+            }
+            if (q) cand[ncand + lanes_below(mask)] = make_key(score, doc);
+            ncand += n;
+        }
+    }
+
+    // the same with the condition given as a lane mask in SGPRs
+    __device__ __forceinline__ void offer_mask(uint64_t condm, float score, uint32_t doc) {
+        uint64_t mask = (!STRICT && ge_mode) ? wballot(score >= theta) : wballot(score > theta);
+        mask &= condm;
+        if (mask != 0ull) {
+            uint32_t n = (uint32_t)__popcll(mask);
+            if (ncand + n > (uint32_t)CB) {
+                shrink();
+                if (!STRICT) ge_mode = true;
+                mask = condm & wballot(STRICT ? score > theta : score >= theta);
+                n = (uint32_t)__popcll(mask);
+            }
+            if (__builtin_amdgcn_inverse_ballot_w64(mask)) cand[ncand + lanes_below(mask)] = make_key(score, doc);
+            ncand += n;
+        }
+    }
+
+    // the same in the driver stream's spelling (the `>` ballot first, replaced by the `>=` one in ge_mode): in dscore_body
+    // offer_mask's select of the two ballots compiles to ~40 more instructions
+    __device__ __forceinline__ void offer_mask_stream(uint64_t condm, float score, uint32_t doc) {
+        uint64_t mask = wballot(score > theta);
+        if (!STRICT && ge_mode) mask = wballot(score >= theta);   // rare: only after a shrink inside this step
+        mask &= condm;
+        if (mask != 0ull) {
+            uint32_t n = (uint32_t)__popcll(mask);
+            if (ncand + n > (uint32_t)CB) {
+                shrink();
+                if (!STRICT) ge_mode = true;
+                mask = condm & wballot(STRICT ? score > theta : score >= theta);
+                n = (uint32_t)__popcll(mask);
+            }
+            if (__builtin_amdgcn_inverse_ballot_w64(mask)) cand[ncand + lanes_below(mask)] = make_key(score, doc);
+            ncand += n;
+        }
+    }
+
+    // the item's top-K: K rows of its output slot (-inf / ~0 past the hits), the hit count and `found`
+    __device__ __forceinline__ void write_out(uint32_t seg, uint32_t out_slot, uint32_t found, Hit* out_hits,
+                                              uint32_t* out_nhits, uint64_t* out_found) {
+        wave_sync();
+        shrink();
+        const uint32_t n = min(ncand, K);
+        Hit* oh = out_hits + (uint64_t)out_slot * K;
+        for (uint32_t i = lane; i < K; i += 64) {
+            Hit h;
+            if (i < n) {
+                const uint64_t key = cand[i];
+                h.score = unorder_bits((uint32_t)(key >> 32));
+                h.seg = seg;
+                h.doc = 0xFFFFFFFFu - (uint32_t)key;
+            } else {
+                h.score = -__builtin_inff();
+                h.seg = 0xFFFFFFFFu;
+                h.doc = 0xFFFFFFFFu;
+            }
+            oh[i] = h;
+        }
+        if (lane == 63) {
+            out_nhits[out_slot] = n;
+            out_found[out_slot] = (uint64_t)found;
+        }
+    }
+};
 
 // a / b, correctly rounded.  `fast`: the caller guarantees a is +0 or in [2^-32, 2^64] and b in [2^-20, 2^34]
 // (checked on the host per item: idf in [2^-30, 2^30], norms in [2^-20, 2^30]); there v_div_scale_f32 scales
@@ -337,6 +359,23 @@ typedef unsigned int nat_u2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(1))) nat_u2* gp_u2;
 typedef const __attribute__((address_space(1))) float* gp_f32;
 typedef const __attribute__((address_space(1))) uint32_t* gp_u32;
+
+// list-relative posting range [x, y) of term `tm` inside item `it`'s doc range: the whole list (DevWItem::whole bit 0), the
+// ends from the list's skip table (bit 6: the host put doc_lo, and doc_hi unless it is n_docs, on the grid), or list_range
+__device__ __forceinline__ uint2 item_list_range(const DevWItem& it, const DevSeg& seg, const DevTerm& tm) {
+    uint32_t cur = 0, end = tm.count;
+    if (!(it.whole & 1u)) {
+        if ((it.whole & 64u) && tm.skip != 0u) {
+            const gp_u32 sk = (gp_u32)seg.skips + (tm.skip - 1u);
+            cur = sk[it.doc_lo / kSkipDocs] - (uint32_t)tm.list_off;
+            end = sk[(it.doc_hi + (kSkipDocs - 1u)) / kSkipDocs] - (uint32_t)tm.list_off;
+        } else {
+            list_range(seg.postings + tm.list_off, tm.count, it.doc_lo, it.doc_hi, seg.n_docs, cur, end);
+        }
+        if (end < cur) end = cur;
+    }
+    return make_uint2(cur, end);
+}
 
 // per-posting norm, built once at upload: pnorm[i] = norm[postings[i].docId]
 __global__ void k_pnorm(const uint2* __restrict__ postings, const float* __restrict__ norm, float* __restrict__ pnorm,
