@@ -317,6 +317,58 @@ int ns_segment_upload_inverted(ns_ctx* ctx, ns_seg* seg, const uint32_t* doc_ter
                                uint64_t n_pairs, uint32_t n_terms, uint32_t* df_out, void* postings_out,
                                uint64_t* kept_out, float* device_ms_out);
 
+/* Indexing (csrc/ns_ingest.hip): document texts -> forward index, the step in front of ns_invert_forward.
+ * Replaces tokenize + the per-document tf map + the term dictionary of the reference's `forwardindex` tool
+ * (include/textutil.hpp:13-37, src/ForwardIndex.cpp:139-179; the same loop in src/AddDocument.cpp:80-130 and
+ * src/api_add_document.cpp:252-421).
+ *   text, text_bytes   the texts of all documents back to back; any byte may occur, NUL included
+ *   offsets[n_docs+1]  document d = text[offsets[d] .. offsets[d + 1]); offsets[0] == 0, non-decreasing,
+ *                      offsets[n_docs] <= text_bytes (bytes past it are ignored)
+ * Semantics (byte for byte the reference's): a token is a maximal run of [0-9A-Za-z] bytes inside one document,
+ * lower-cased; every other byte and every document boundary separates; tokens shorter than 2 bytes and the 24 stop
+ * words are dropped (:146-147); doc_len = kept tokens of the document, tf = occurrences of a term in it (:148-149); a
+ * document with doc_len == 0 is dropped and the later ones move up (:152-155).  No cap on a token's length.
+ * TERM IDS: the reference numbers terms in std::unordered_map iteration order (:159-173), an accident nothing downstream
+ * reads.  Here term id = rank of the term's first kept occurrence in the input (document order, then byte position):
+ * deterministic and independent of GPU scheduling.  Two different byte strings never share an id (the hash only routes;
+ * the bytes are compared).
+ * Limits: offsets[n_docs] < 4 GiB - 64 KiB (positions are 32 bits wide); n_docs < 2^32 - 1.  Beyond: NS_E_INVAL (NS_E_ARG).
+ * n_docs == 0, or no surviving document, is NS_OK with an empty result (kept_docs == 0).
+ * The result stays on the device behind the handle until ns_forward_destroy; sizes come from ns_forward_get_info. */
+#define NS_E_ARG NS_E_INVAL
+typedef struct ns_forward ns_forward;
+typedef struct ns_forward_info {
+    uint32_t struct_size;   /* IN: sizeof(ns_forward_info) as the caller was compiled; no more than that many bytes are written */
+    uint32_t kept_docs;     /* documents with doc_len > 0 */
+    uint32_t n_terms;
+    uint32_t n_docs;        /* documents handed in */
+    uint64_t n_pairs;       /* (termId, tf) pairs of all kept documents */
+    uint64_t term_bytes;    /* bytes of all terms back to back */
+    uint64_t n_tokens;      /* tokens before the length and stop-word rules */
+    uint64_t kept_tokens;   /* sum of doc_len */
+    uint64_t device_bytes;  /* device memory the build used at its peak (scratch + result) */
+    float    device_ms;     /* HIP events around the device part (upload excluded) */
+    uint32_t pad;
+} ns_forward_info;
+int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_bytes, const uint64_t* offsets, uint32_t n_docs,
+                     ns_forward** out);
+/* NS_E_INVAL for a NULL argument or struct_size < 4. */
+int ns_forward_get_info(const ns_forward* fwd, ns_forward_info* info);
+/* Copies the result to host memory; every pointer may be NULL (that array is skipped); may be called any number of times.
+ *   kept_docs_out[kept_docs]   input index of each surviving document, ascending (docId j = kept_docs_out[j])
+ *   doc_len_out[kept_docs]     (src/ForwardIndex.cpp:149), counts_out[kept_docs]: pairs of the document (forward.bin's cnt, :218)
+ *   pairs_out[2 * n_pairs]     u32 {termId, tf}, documents back to back, termId ascending inside a document (:176, :219-222):
+ *                              with counts_out exactly ns_invert_forward's `pairs` and `doc_term_counts`
+ *   term_bytes_out[term_bytes], term_offsets_out[n_terms + 1]   term t = bytes [term_offsets_out[t], term_offsets_out[t + 1]) (terms.bin, :225-230)
+ * NS_E_STATE if the handle's ctx has been destroyed (the result went with it). */
+int ns_forward_fetch(ns_forward* fwd, uint32_t* kept_docs_out, uint32_t* doc_len_out, uint32_t* counts_out,
+                     uint32_t* pairs_out, uint8_t* term_bytes_out, uint64_t* term_offsets_out);
+/* Lifetime: the ctx keeps a list of its live handles.  ns_ctx_destroy frees their device memory and orphans them; an
+ * orphaned handle still answers ns_forward_get_info, fails ns_forward_fetch with NS_E_STATE and is freed by
+ * ns_forward_destroy without touching the ctx.  Errors of these three calls are read with ns_last_error(NULL) when the
+ * handle has no ctx any more. */
+void ns_forward_destroy(ns_forward* fwd);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -136,6 +136,32 @@ int nsh_engine_search_batch(nsh_engine* e, const char* const* queries, uint32_t 
 int nsh_engine_prepare(nsh_engine* e, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
                        ns_batch** out);
 
+/* Indexing (host/forward_index.hpp; the reference's `forwardindex` tool from the text handed to tokenize onwards,
+ * src/ForwardIndex.cpp:139-230): n_docs documents of four fields each — cord_uid, title, json_relpath, text, in this
+ * order — as raw bytes with explicit lengths: field f of document d = bytes[field_offsets[4 d + f] .. field_offsets[4 d + f + 1])
+ * (4 * n_docs + 1 offsets).  Tokenising, tf counting and the term dictionary run on the device (ns_forward_build). */
+typedef struct nsh_index_stats {
+    uint32_t struct_size;   /* IN: sizeof(nsh_index_stats) as the caller was compiled; no more than that is written */
+    uint32_t n_docs_in, n_docs, n_terms;
+    uint64_t text_bytes, tokens, kept_tokens, pairs, device_bytes;
+    float    avgdl, device_ms;
+    double   call_s, total_s;
+} nsh_index_stats;
+/* Writes docs.bin, stats.bin, forward.bin, terms.bin into seg_dir (created) on a context of its own on `device`.
+ * -1 on failure, also when no document survives the length and stop-word rules (nothing is written then);
+ * nsh_index_error() says why.  stats may be NULL. */
+int nsh_index_documents(const char* seg_dir, int device, const char* bytes, const uint64_t* field_offsets, uint32_t n_docs,
+                        nsh_index_stats* stats);
+const char* nsh_index_error(void);
+/* An engine on index_dir WITHOUT the initial reload (nsh_engine_open fails on a directory that holds no segment yet):
+ * what nsh_engine_add_documents needs on a fresh index directory.  Searches fail until a reload succeeded. */
+int nsh_engine_open_noload(const char* index_dir, int device, nsh_engine** out);
+/* Engine::add_documents: the batch becomes the next free segments/seg_%06u (forward index and inversion on the device),
+ * manifest.bin gains its name (src/AddDocument.cpp:20-60,:160-170) and the engine reloads.  -1 on failure: the manifest
+ * keeps its bytes, the new segment directory is gone, nsh_engine_error() says why. */
+int nsh_engine_add_documents(nsh_engine* e, const char* bytes, const uint64_t* field_offsets, uint32_t n_docs,
+                             nsh_index_stats* stats);
+
 /* Autocomplete: Engine::suggest(input, limit) (include/api_engine.hpp:67, src/api_engine.cpp:164-187).  The input is
  * input_len raw bytes (NUL and other control bytes included); *json_out receives {"limit", "query", "suggestions"} in
  * dump(2) layout (free with nsh_free).  -1 without a device context (there is no CPU path) or on failure. */

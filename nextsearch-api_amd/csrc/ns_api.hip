@@ -22,6 +22,7 @@
 #include "ns_merge_kernel.hip"
 #include "ns_tile_kernel.hip"
 #include "ns_invert.hip"
+#include "ns_ingest.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 
@@ -109,10 +110,12 @@ struct ns_ctx {
     ShareRegistry share;   // every list a sharing batch built (ns_ctx_share_scores) and the sharing batches alive
     BatchPlan plan;        // ns_batch_prepare's host threads and per-thread scratch, kept from batch to batch
     std::vector<ns_ac*> acs;   // autocomplete tables (ns_ac_upload): owned by the ctx, freed by ns_ac_release or ns_ctx_destroy
+    std::vector<ns_forward*> fwds;   // live forward-index handles (ns_forward_build): orphaned, not freed, by ns_ctx_destroy
 };
 
 static thread_local std::string g_create_err;
 static void ac_free_fwd(ns_ac* ac);
+static void forward_orphan_fwd(ns_forward* f);
 static void seg_free_device_fwd(ns_seg* s);
 static void seg_free_staging_fwd(ns_seg* s);
 
@@ -247,6 +250,7 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
         delete s;
     }
     for (ns_ac* ac : ctx->acs) ac_free_fwd(ac);   // tables still held: their handles die with the ctx
+    for (ns_forward* f : ctx->fwds) forward_orphan_fwd(f);   // their device memory goes; the handles stay valid for ns_forward_destroy
     for (auto& blk : ctx->pool) (void)hipFree(blk.p);
     if (ctx->h_up) (void)hipHostFree(ctx->h_up);
     if (ctx->h_down) (void)hipHostFree(ctx->h_down);
@@ -1679,6 +1683,297 @@ extern "C" int ns_segment_upload_inverted(ns_ctx* ctx, ns_seg* seg, const uint32
     if (seg->filled != 0) return fail(ctx, NS_E_STATE, "ns_segment_upload_inverted: the segment already received %llu payload bytes", (unsigned long long)seg->filled);
     if (seg->n_postings != n_pairs) return fail(ctx, NS_E_INVAL, "ns_segment_upload_inverted: %llu pairs, but ns_segment_upload_begin announced %llu postings", (unsigned long long)n_pairs, (unsigned long long)seg->n_postings);
     return invert_run(ctx, doc_term_counts, seg->n_docs, pairs, n_pairs, n_terms, df_out, postings_out, kept_out, device_ms_out, seg);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Indexing: document texts -> forward index (csrc/ns_ingest.hip)
+struct ns_forward {
+    ns_ctx* ctx = nullptr;          // nullptr: orphaned by ns_ctx_destroy (the device arrays below are gone)
+    ns_forward_info info{};
+    uint32_t* d_map = nullptr;      // kept_docs
+    uint32_t* d_len = nullptr;      // kept_docs
+    uint32_t* d_cnt = nullptr;      // kept_docs
+    uint2* d_pairs = nullptr;       // n_pairs {termId, tf}
+    uint8_t* d_terms = nullptr;     // term_bytes
+    uint32_t* d_toff = nullptr;     // n_terms + 1
+};
+
+static void forward_free_device(ns_forward* f) {
+    (void)hipFree(f->d_map); (void)hipFree(f->d_len); (void)hipFree(f->d_cnt);
+    (void)hipFree(f->d_pairs); (void)hipFree(f->d_terms); (void)hipFree(f->d_toff);
+    f->d_map = f->d_len = f->d_cnt = f->d_toff = nullptr; f->d_pairs = nullptr; f->d_terms = nullptr;
+}
+static void forward_orphan_fwd(ns_forward* f) { forward_free_device(f); f->ctx = nullptr; }
+
+// exclusive scan of a[0 .. m) in place; the sum of all goes to *d_total (device, may be NULL); d_sums: ceil(m / 1024) words
+static void ig_scan(hipStream_t st, uint32_t* d_a, uint32_t m, uint32_t* d_sums, uint32_t* d_total) {
+    const uint32_t blocks = (m + 1023) / 1024;
+    hipLaunchKernelGGL(k_iv_scan_sums, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
+    hipLaunchKernelGGL(k_iv_scan_top, dim3(1), dim3(1024), 0, st, d_sums, blocks, d_total);
+    hipLaunchKernelGGL(k_iv_scan_apply, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
+}
+
+// stable LSD radix sort of n (key, value) items by the keys below key_range, with ns_invert.hip's passes; the input is
+// buffer *cur, the result buffer *cur afterwards.  d_hist: 2048 * ceil(n / kIvTile) words
+static void ig_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_keys[2], uint2* d_vals[2], int* cur, uint32_t* d_hist, uint32_t* d_sums) {
+    const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
+    int bits = 1;
+    while (bits < 32 && key_range > 1 && ((key_range - 1) >> bits) != 0) bits++;
+    const int passes = std::max(1, (bits + 10) / 11);
+    uint32_t shift = 0;
+    int left = bits;
+    for (int p = 0; p < passes; p++) {
+        const int share = (left + (passes - p) - 1) / (passes - p);
+        const int pb = std::min(11, std::max(8, share));
+        left = std::max(0, left - pb);
+        const int nxt = *cur ^ 1;
+        const uint32_t m = ((uint32_t)1 << pb) * n_tiles;
+#define NS_IG_HIST(B) hipLaunchKernelGGL((k_iv_hist_w<B>), dim3(n_tiles), dim3(256), 0, st, d_keys[*cur], (const uint2*)nullptr, n, (const uint32_t*)nullptr, key_range, shift, d_hist, n_tiles)
+#define NS_IG_PASS(B) hipLaunchKernelGGL((k_iv_pass<B, false, false>), dim3(n_tiles), dim3(256), 0, st, (const uint2*)nullptr, (const uint64_t*)nullptr, (const uint2*)nullptr, key_range, d_keys[*cur], d_vals[*cur], d_keys[nxt], d_vals[nxt], n, (const uint32_t*)nullptr, shift, d_hist, n_tiles)
+        switch (pb) { case 8: NS_IG_HIST(8); break; case 9: NS_IG_HIST(9); break; case 10: NS_IG_HIST(10); break; default: NS_IG_HIST(11); break; }
+        ig_scan(st, d_hist, m, d_sums, nullptr);
+        switch (pb) { case 8: NS_IG_PASS(8); break; case 9: NS_IG_PASS(9); break; case 10: NS_IG_PASS(10); break; default: NS_IG_PASS(11); break; }
+#undef NS_IG_HIST
+#undef NS_IG_PASS
+        shift += (uint32_t)pb;
+        *cur = nxt;
+    }
+}
+
+extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_bytes, const uint64_t* offsets, uint32_t n_docs, ns_forward** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_forward_build: ctx is NULL");
+    if (!out) return fail(ctx, NS_E_INVAL, "ns_forward_build: out is NULL");
+    *out = nullptr;
+    if (n_docs == 0xFFFFFFFFu) return fail(ctx, NS_E_INVAL, "ns_forward_build: n_docs too large");
+    if (n_docs && !offsets) return fail(ctx, NS_E_INVAL, "ns_forward_build: offsets is NULL");
+    if (n_docs && offsets[0] != 0) return fail(ctx, NS_E_INVAL, "ns_forward_build: offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
+    for (uint32_t d = 0; d < n_docs; d++)
+        if (offsets[d + 1] < offsets[d]) return fail(ctx, NS_E_INVAL, "ns_forward_build: offsets decrease at document %u", d);
+    const uint64_t n64 = n_docs ? offsets[n_docs] : 0;
+    if (n64 > text_bytes) return fail(ctx, NS_E_INVAL, "ns_forward_build: offsets[n_docs] = %llu lies past the %llu bytes of text", (unsigned long long)n64, (unsigned long long)text_bytes);
+    if (n64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "ns_forward_build: %llu bytes of text; this build addresses text with 32 bits (below 4 GiB - 64 KiB per call: split the batch)", (unsigned long long)n64);
+    if (n64 && !text) return fail(ctx, NS_E_INVAL, "ns_forward_build: text is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ns_forward* f = new ns_forward();
+    f->ctx = ctx;
+    f->info.struct_size = (uint32_t)sizeof(ns_forward_info);
+    f->info.n_docs = n_docs;
+    auto publish = [&]() { ctx->fwds.push_back(f); *out = f; return NS_OK; };
+    if (n64 == 0) return publish();   // no text: no token, no document survives
+    const uint32_t n = (uint32_t)n64;
+    hipStream_t st = ctx->stream;
+    uint64_t hash_mask = ~0ull;
+#ifdef NS_VARIANTS
+    // test knob (variants build only): narrow the hash so that every probe collides and the byte comparison decides
+    if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) hash_mask = (1ull << b) - 1ull; }
+#endif
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    char *blkA = nullptr, *blkB = nullptr, *blkC = nullptr;
+    size_t bytesA = 0, bytesB = 0, bytesC = 0, off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    enum { C_TOK = 0, C_TOKE = 1, C_KEPT = 2, C_LONG = 3, C_KD = 4, C_TERMS = 5, C_TBYTES = 6, C_PAIRS = 7 };
+    auto read_counts = [&]() {
+        chk(hipGetLastError());
+        if (e == hipSuccess) chk(hipMemcpyAsync(h_cnt, blkA, sizeof(h_cnt), hipMemcpyDeviceToHost, st));   // the counters open block A
+        if (e == hipSuccess) chk(hipStreamSynchronize(st));
+    };
+    const uint32_t nd1 = n_docs + 1, n_tiles = (n + kIgTile - 1) / kIgTile;
+    const uint32_t g_docs = (n_docs + 255) / 256;
+    std::vector<uint32_t> offs32(nd1);
+    for (uint32_t d = 0; d <= n_docs; d++) offs32[d] = (uint32_t)offsets[d];
+
+    // ---- block A: what the text and the documents size ----
+    off = 0;
+    const size_t o_cnt = place(sizeof(h_cnt)), o_text = place((size_t)n + 16), o_bits = place(((size_t)(n >> 5) + 2) * 4), o_offs = place((size_t)nd1 * 4);
+    const size_t o_ts = place((size_t)n_tiles * 4), o_te = place((size_t)n_tiles * 4), o_sumsA = place(((size_t)std::max(n_tiles, n_docs) / 1024 + 2) * 4);
+    const size_t o_long = place(((size_t)n / kIgLong + 1) * 4);
+    const size_t o_df = place((size_t)n_docs * 4), o_dl = place((size_t)n_docs * 4), o_pf = place((size_t)n_docs * 4), o_pl = place((size_t)n_docs * 4), o_dx = place((size_t)n_docs * 4);
+    bytesA = off;
+    chk(pool_alloc(ctx, (void**)&blkA, bytesA));
+    chk(hipEventCreate(&ev0));
+    chk(hipEventCreate(&ev1));
+    uint32_t n_tok = 0, n_kept = 0;
+    if (e == hipSuccess) {
+        uint32_t* d_cntv = (uint32_t*)(blkA + o_cnt);
+        uint8_t* d_text = (uint8_t*)(blkA + o_text);
+        uint32_t *d_bits = (uint32_t*)(blkA + o_bits), *d_offs = (uint32_t*)(blkA + o_offs), *d_ts = (uint32_t*)(blkA + o_ts), *d_te = (uint32_t*)(blkA + o_te);
+        uint32_t *d_sumsA = (uint32_t*)(blkA + o_sumsA), *d_long = (uint32_t*)(blkA + o_long);
+        uint32_t *d_dfirst = (uint32_t*)(blkA + o_df), *d_dlast = (uint32_t*)(blkA + o_dl), *d_pfirst = (uint32_t*)(blkA + o_pf), *d_plast = (uint32_t*)(blkA + o_pl), *d_didx = (uint32_t*)(blkA + o_dx);
+        chk(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_offs, offs32.data(), (size_t)nd1 * 4, hipMemcpyHostToDevice, st));
+        chk(hipEventRecord(ev0, st));
+        chk(hipMemsetAsync(d_cntv, 0, sizeof(h_cnt), st));
+        chk(hipMemsetAsync(d_bits, 0, ((size_t)(n >> 5) + 2) * 4, st));
+        chk(hipMemsetAsync(d_dfirst, 0xFF, (size_t)n_docs * 4, st));
+        chk(hipMemsetAsync(d_pfirst, 0xFF, (size_t)n_docs * 4, st));
+        hipLaunchKernelGGL(k_ig_docmark, dim3(g_docs), dim3(256), 0, st, d_offs, n_docs, n, d_bits);
+        hipLaunchKernelGGL((k_ig_text<false>), dim3(n_tiles), dim3(256), 0, st, d_text, n, d_bits, d_ts, d_te, (uint32_t*)nullptr, (uint32_t*)nullptr);
+        ig_scan(st, d_ts, n_tiles, d_sumsA, d_cntv + C_TOK);
+        ig_scan(st, d_te, n_tiles, d_sumsA, d_cntv + C_TOKE);
+        read_counts();
+        n_tok = h_cnt[C_TOK];
+        if (e == hipSuccess && h_cnt[C_TOKE] != n_tok) { e = hipErrorUnknown; }   // every token has one start and one end
+        f->info.n_tokens = n_tok;
+
+        // ---- block B: what the tokens size ----
+        uint32_t *d_tstart = nullptr, *d_tend = nullptr, *d_kidx = nullptr, *d_sums = nullptr;
+        if (e == hipSuccess && n_tok) {
+            off = 0;
+            const size_t o_a = place((size_t)n_tok * 4), o_b = place((size_t)n_tok * 4), o_c = place((size_t)n_tok * 4);
+            const size_t scan_max = std::max<size_t>((size_t)n_tok + 1, (size_t)2048 * ((n_tok + kIvTile - 1) / kIvTile));
+            const size_t o_s = place((scan_max / 1024 + 2) * 4);
+            bytesB = off;
+            chk(pool_alloc(ctx, (void**)&blkB, bytesB));
+            if (e == hipSuccess) {
+                d_tstart = (uint32_t*)(blkB + o_a); d_tend = (uint32_t*)(blkB + o_b); d_kidx = (uint32_t*)(blkB + o_c); d_sums = (uint32_t*)(blkB + o_s);
+                hipLaunchKernelGGL((k_ig_text<true>), dim3(n_tiles), dim3(256), 0, st, d_text, n, d_bits, d_ts, d_te, d_tstart, d_tend);
+                hipLaunchKernelGGL(k_ig_keep, dim3((n_tok + 255) / 256), dim3(256), 0, st, d_text, d_tstart, d_tend, n_tok, d_kidx);
+                ig_scan(st, d_kidx, n_tok, d_sums, d_cntv + C_KEPT);
+                read_counts();
+                n_kept = h_cnt[C_KEPT];
+                f->info.kept_tokens = n_kept;
+            }
+        }
+        // ---- block C: what the kept tokens size ----
+        if (e == hipSuccess && n_kept) {
+            const uint32_t K = n_kept, gK = (K + 255) / 256, kt = (K + kIvTile - 1) / kIvTile;
+            uint64_t cap = 1024;
+            while (cap < 2ull * K) cap <<= 1;                      // K <= n / 2 < 2^31: cap <= 2^32, its mask fits 32 bits
+            off = 0;
+            const size_t o_ks = place((size_t)K * 4), o_kl = place((size_t)K * 4), o_kd = place((size_t)K * 4), o_kh = place((size_t)K * 8);
+            const size_t o_sl = place((size_t)K * 4), o_kr = place((size_t)K * 4), o_fi = place((size_t)K * 4), o_tsrc = place((size_t)K * 4);
+            const size_t o_tab = place((size_t)cap * 4), o_k0 = place((size_t)K * 4), o_k1 = place((size_t)K * 4), o_v0 = place((size_t)K * 8), o_v1 = place((size_t)K * 8);
+            const size_t o_hist = place((size_t)2048 * kt * 4);
+            bytesC = off;
+            chk(pool_alloc(ctx, (void**)&blkC, bytesC));
+            if (e == hipSuccess) {
+                uint32_t *d_kstart = (uint32_t*)(blkC + o_ks), *d_klen = (uint32_t*)(blkC + o_kl), *d_kdoc = (uint32_t*)(blkC + o_kd);
+                uint64_t* d_khash = (uint64_t*)(blkC + o_kh);
+                uint32_t *d_kslot = (uint32_t*)(blkC + o_sl), *d_krep = (uint32_t*)(blkC + o_kr), *d_fid = (uint32_t*)(blkC + o_fi), *d_tsrc = (uint32_t*)(blkC + o_tsrc);
+                uint32_t* d_table = (uint32_t*)(blkC + o_tab);
+                uint32_t* d_keys[2] = {(uint32_t*)(blkC + o_k0), (uint32_t*)(blkC + o_k1)};
+                uint2* d_vals[2] = {(uint2*)(blkC + o_v0), (uint2*)(blkC + o_v1)};
+                uint32_t* d_hist = (uint32_t*)(blkC + o_hist);
+                chk(hipMemsetAsync(d_table, 0xFF, (size_t)cap * 4, st));
+                hipLaunchKernelGGL(k_ig_kept, dim3((n_tok + 255) / 256), dim3(256), 0, st, d_text, d_tstart, d_tend, n_tok, d_kidx, d_cntv + C_KEPT, d_offs, n_docs,
+                                   hash_mask, d_kstart, d_klen, d_kdoc, d_khash, d_long, d_cntv + C_LONG);
+                hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
+                // doc_len: the kept tokens are in document order, a document's tokens are one run of kdoc
+                hipLaunchKernelGGL(k_iv_runs, dim3((K + 1023) / 1024), dim3(256), 0, st, d_kdoc, K, n_docs, d_dfirst, d_dlast, (const uint32_t*)nullptr);
+                hipLaunchKernelGGL(k_ig_docflag, dim3(g_docs), dim3(256), 0, st, d_dfirst, n_docs, d_didx);
+                ig_scan(st, d_didx, n_docs, d_sumsA, d_cntv + C_KD);
+                hipLaunchKernelGGL(k_ig_insert, dim3(gK), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, K, d_table, (uint32_t)(cap - 1), d_kslot);
+                hipLaunchKernelGGL(k_ig_first, dim3(gK), dim3(256), 0, st, d_table, d_kslot, K, d_krep, d_fid);
+                ig_scan(st, d_fid, K, d_sums, d_cntv + C_TERMS);
+                read_counts();
+                const uint32_t n_terms = h_cnt[C_TERMS], n_kd = h_cnt[C_KD];
+                f->info.n_terms = n_terms; f->info.kept_docs = n_kd;
+                if (e == hipSuccess) {
+                    chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+                    chk(hipMalloc((void**)&f->d_map, (size_t)n_kd * 4));
+                    chk(hipMalloc((void**)&f->d_len, (size_t)n_kd * 4));
+                    chk(hipMalloc((void**)&f->d_cnt, (size_t)n_kd * 4));
+                }
+                int cur = 0;
+                if (e == hipSuccess) {
+                    chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
+                    hipLaunchKernelGGL(k_ig_termid, dim3(gK), dim3(256), 0, st, d_krep, d_fid, d_kdoc, d_kstart, d_klen, K, d_keys[0], d_vals[0], f->d_toff, d_tsrc);
+                    ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
+                    ig_sort(st, K, n_terms, d_keys, d_vals, &cur, d_hist, d_sums);
+                    hipLaunchKernelGGL(k_ig_runflag, dim3(gK), dim3(256), 0, st, d_vals[cur], K, d_kslot);
+                    ig_scan(st, d_kslot, K, d_sums, d_cntv + C_PAIRS);
+                    read_counts();
+                }
+                const uint32_t n_pairs = h_cnt[C_PAIRS], tbytes = h_cnt[C_TBYTES];
+                f->info.n_pairs = n_pairs; f->info.term_bytes = tbytes;
+                if (e == hipSuccess) {
+                    chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
+                    chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
+                }
+                if (e == hipSuccess) {
+                    hipLaunchKernelGGL(k_ig_term_bytes, dim3((n_terms + 3) / 4), dim3(256), 0, st, d_text, d_tsrc, f->d_toff, n_terms, f->d_terms);
+                    // the runs, (term, doc)-ordered: keys = doc, values = {term, tf}, into the buffer the first sort left free
+                    const int in = cur ^ 1;
+                    uint32_t *d_rterm = d_krep, *d_rpos = d_kstart;   // (dead since k_ig_termid)
+                    hipLaunchKernelGGL(k_ig_runemit, dim3(gK), dim3(256), 0, st, d_vals[cur], K, d_kslot, d_keys[in], d_rterm, d_rpos);
+                    hipLaunchKernelGGL(k_ig_tf, dim3((n_pairs + 255) / 256), dim3(256), 0, st, d_rterm, d_rpos, n_pairs, K, d_vals[in]);
+                    cur = in;
+                    ig_sort(st, n_pairs, n_docs, d_keys, d_vals, &cur, d_hist, d_sums);
+                    hipLaunchKernelGGL(k_iv_runs, dim3((n_pairs + 1023) / 1024), dim3(256), 0, st, d_keys[cur], n_pairs, n_docs, d_pfirst, d_plast, (const uint32_t*)nullptr);
+                    hipLaunchKernelGGL(k_ig_docemit, dim3(g_docs), dim3(256), 0, st, d_dfirst, d_dlast, d_pfirst, d_plast, d_didx, n_docs, f->d_map, f->d_len, f->d_cnt);
+                    chk(hipMemcpyAsync(f->d_pairs, d_vals[cur], (size_t)n_pairs * 8, hipMemcpyDeviceToDevice, st));
+                    chk(hipGetLastError());
+                }
+            }
+        }
+        if (e == hipSuccess) chk(hipEventRecord(ev1, st));
+        if (e == hipSuccess) chk(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) f->info.device_ms = ms;
+    }
+    (void)hipStreamSynchronize(st);   // nothing in flight uses the blocks any more
+    if (blkC) pool_free(ctx, blkC, bytesC);
+    if (blkB) pool_free(ctx, blkB, bytesB);
+    if (blkA) pool_free(ctx, blkA, bytesA);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    f->info.device_bytes = (uint64_t)bytesA + bytesB + bytesC + ((uint64_t)f->info.n_terms + 1) * 4 + (uint64_t)f->info.kept_docs * 12 + f->info.n_pairs * 8 + f->info.term_bytes;
+    if (e != hipSuccess) {
+        forward_free_device(f);
+        delete f;
+        (void)hipGetLastError();
+        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_forward_build: %s", e == hipErrorUnknown ? "token starts and ends disagree (internal error)" : hipGetErrorString(e));
+    }
+    return publish();
+}
+
+extern "C" int ns_forward_get_info(const ns_forward* fwd, ns_forward_info* info) {
+    ns_ctx* ctx = fwd ? fwd->ctx : nullptr;
+    if (!fwd || !info) return fail(ctx, NS_E_INVAL, "ns_forward_get_info: null argument");
+    if (info->struct_size < 4) return fail(ctx, NS_E_INVAL, "ns_forward_get_info: struct_size = %u (the caller sets it to sizeof(ns_forward_info))", info->struct_size);
+    const uint32_t sz = std::min<uint32_t>(info->struct_size, (uint32_t)sizeof(ns_forward_info));
+    ns_forward_info tmp = fwd->info;
+    tmp.struct_size = sz;
+    std::memcpy(info, &tmp, sz);
+    return NS_OK;
+}
+
+extern "C" int ns_forward_fetch(ns_forward* fwd, uint32_t* kept_docs_out, uint32_t* doc_len_out, uint32_t* counts_out,
+                                uint32_t* pairs_out, uint8_t* term_bytes_out, uint64_t* term_offsets_out) {
+    if (!fwd) return fail(nullptr, NS_E_INVAL, "ns_forward_fetch: handle is NULL");
+    ns_ctx* ctx = fwd->ctx;
+    if (!ctx) return fail(nullptr, NS_E_STATE, "ns_forward_fetch: the handle's ctx has been destroyed");
+    const ns_forward_info& in = fwd->info;
+    if (in.kept_docs == 0) {   // empty result: nothing on the device
+        if (term_offsets_out) term_offsets_out[0] = 0;
+        return NS_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (kept_docs_out) HIPCHK(ctx, hipMemcpy(kept_docs_out, fwd->d_map, (size_t)in.kept_docs * 4, hipMemcpyDeviceToHost));
+    if (doc_len_out) HIPCHK(ctx, hipMemcpy(doc_len_out, fwd->d_len, (size_t)in.kept_docs * 4, hipMemcpyDeviceToHost));
+    if (counts_out) HIPCHK(ctx, hipMemcpy(counts_out, fwd->d_cnt, (size_t)in.kept_docs * 4, hipMemcpyDeviceToHost));
+    if (pairs_out && in.n_pairs) HIPCHK(ctx, hipMemcpy(pairs_out, fwd->d_pairs, (size_t)in.n_pairs * 8, hipMemcpyDeviceToHost));
+    if (term_bytes_out && in.term_bytes) HIPCHK(ctx, hipMemcpy(term_bytes_out, fwd->d_terms, (size_t)in.term_bytes, hipMemcpyDeviceToHost));
+    if (term_offsets_out) {
+        std::vector<uint32_t> t32((size_t)in.n_terms + 1);
+        HIPCHK(ctx, hipMemcpy(t32.data(), fwd->d_toff, t32.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < t32.size(); i++) term_offsets_out[i] = t32[i];
+    }
+    return NS_OK;
+}
+
+extern "C" void ns_forward_destroy(ns_forward* fwd) {
+    if (!fwd) return;
+    if (ns_ctx* ctx = fwd->ctx) {
+        (void)hipSetDevice(ctx->device);
+        auto it = std::find(ctx->fwds.begin(), ctx->fwds.end(), fwd);
+        if (it != ctx->fwds.end()) ctx->fwds.erase(it);
+        forward_free_device(fwd);
+    }
+    delete fwd;
 }
 
 // ------------------------------------------------------------------------------------------------

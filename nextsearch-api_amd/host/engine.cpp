@@ -1,4 +1,5 @@
 #include "engine.hpp"
+#include "invert.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -223,6 +224,54 @@ bool Engine::reload() {
         }
     }
     return true;
+}
+
+bool Engine::add_documents(const std::vector<nsx::DocInput>& docs, nsx::IndexStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (device_ < 0) { err_ = "add_documents: host-only engine (indexing runs on the device; there is no CPU path)"; return false; }
+    // an engine that has not loaded anything yet has no context: a context of its own for the two device steps
+    ns_ctx* ctx = ctx_;
+    ns_ctx* own = nullptr;
+    if (!ctx) {
+        if (ns_ctx_create(device_, &own) != NS_OK) { err_ = std::string("ns_ctx_create: ") + ns_last_error(nullptr); return false; }
+        ctx = own;
+    }
+    const nsx::fs::path manifest = index_dir / "manifest.bin", segroot = index_dir / "segments";
+    std::error_code ec;
+    std::vector<std::string> segs = nsx::load_manifest(manifest);                  // src/AddDocument.cpp:54
+    uint32_t id = (uint32_t)segs.size();
+    while (nsx::fs::exists(segroot / nsx::seg_name(id), ec) || std::find(segs.begin(), segs.end(), nsx::seg_name(id)) != segs.end()) id++;
+    const std::string name = nsx::seg_name(id);
+    const nsx::fs::path segdir = segroot / name;
+    nsx::IndexStats st;
+    bool ok = nsx::index_documents(ctx, docs, segdir, st, err_);                    // (creates segdir only when a document survives)
+    if (ok) {
+        nsx::InvertStats ist;
+        ok = nsx::invert_segment(ctx, segdir, ist, err_);
+    }
+    if (own) ns_ctx_destroy(own);
+    if (stats) *stats = st;
+    bool had_manifest = false;
+    std::vector<uint8_t> old_manifest;
+    if (ok) {
+        nsx::FileBytes fb;
+        had_manifest = nsx::fs::exists(manifest, ec) && fb.load(manifest);
+        if (had_manifest) old_manifest = fb.bytes();
+        try {
+            segs.push_back(name);
+            nsx::save_manifest(manifest, segs);                                     // src/AddDocument.cpp:168-169
+        } catch (const std::exception& ex) { err_ = ex.what(); ok = false; }
+        if (ok && !reload()) ok = false;                                            // (err_ is reload's)
+        if (!ok) {   // the manifest as it was
+            const std::string keep = err_;
+            if (had_manifest) { try { nsx::FileOut out(manifest); out.raw(old_manifest.data(), old_manifest.size()); } catch (...) {} }
+            else nsx::fs::remove(manifest, ec);
+            err_ = keep;
+        }
+    }
+    if (!ok) nsx::fs::remove_all(segdir, ec);
+    return ok;
 }
 
 const std::vector<uint8_t>* Engine::raw_postings(uint32_t seg) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/nextsearch_hip.h"
+#include "forward_index.hpp"
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
@@ -91,6 +92,14 @@ public:
     Engine& operator=(const Engine&) = delete;
 
     bool reload();                                              // include/api_engine.hpp:65
+    // What the reference's `adddocument` tool (src/AddDocument.cpp:20-60,:160-170) and its disabled /api/add_document
+    // (src/api_add_document.cpp:252-421) do, for a batch: the documents become ONE new segment, the next free seg_%06u
+    // under <index>/segments — forward index on the device (forward_index.hpp), inverted on the device (invert.hpp) —
+    // which is appended to manifest.bin (a missing manifest is an empty list, src/AddDocument.cpp:23), then reload().
+    // Works on a fresh index directory and on an engine whose reload() has not succeeded yet.  On any failure the
+    // manifest keeps its bytes and the new segment directory is removed; if no document has a token left after the
+    // length and stop-word rules that is a failure and nothing is written.  stats (may be null): the indexing step's.
+    bool add_documents(const std::vector<nsx::DocInput>& docs, nsx::IndexStats* stats = nullptr);
     // Optional: per-posting term scores for every list of every lexicon, built on the device
     // (ns_segment_build_impacts); searches then read {docId, score} instead of {docId, tf} + norm.  Same results.
     bool build_impacts();

@@ -2,9 +2,11 @@
 // No C++ exception crosses the boundary: every entry runs inside try/catch (std::filesystem errors, bad_alloc on a
 // corrupt count, ...) and reports failure through its return value and nsh_engine_error().
 #include "invert.hpp"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -310,6 +312,64 @@ extern "C" int nsh_invert_segment(const char* seg_dir, int device, uint64_t* pai
     if (total_s) *total_s = st.total_s;
     return ok ? 0 : -1;
 } NSH_CATCH(nullptr, "nsh_invert_segment", -1)
+}
+
+// Indexing: documents as four length-delimited fields each (include/nextsearch_host.h)
+static std::vector<nsx::DocInput> to_docs(const char* bytes, const uint64_t* fo, uint32_t n_docs) {
+    std::vector<nsx::DocInput> docs(n_docs);
+    for (uint32_t d = 0; d < n_docs; d++) {
+        const uint64_t* o = fo + 4 * (size_t)d;
+        std::string* f[4] = {&docs[d].cord_uid, &docs[d].title, &docs[d].json_relpath, &docs[d].text};
+        for (int k = 0; k < 4; k++) {
+            if (o[k + 1] < o[k]) throw std::runtime_error("field offsets decrease at document " + std::to_string(d));
+            f[k]->assign(bytes + o[k], (size_t)(o[k + 1] - o[k]));
+        }
+    }
+    return docs;
+}
+static void put_stats(nsh_index_stats* out, const nsx::IndexStats& st) {
+    if (!out || out->struct_size < 4) return;
+    nsh_index_stats t{};
+    t.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(t));
+    t.n_docs_in = st.n_docs_in; t.n_docs = st.n_docs; t.n_terms = st.n_terms;
+    t.text_bytes = st.text_bytes; t.tokens = st.tokens; t.kept_tokens = st.kept_tokens; t.pairs = st.pairs; t.device_bytes = st.device_bytes;
+    t.avgdl = st.avgdl; t.device_ms = st.device_ms; t.call_s = st.call_s; t.total_s = st.total_s;
+    std::memcpy(out, &t, t.struct_size);
+}
+static thread_local std::string g_index_err;
+extern "C" const char* nsh_index_error(void) { return g_index_err.c_str(); }
+extern "C" int nsh_index_documents(const char* seg_dir, int device, const char* bytes, const uint64_t* field_offsets, uint32_t n_docs,
+                                   nsh_index_stats* stats) { try {
+    if (!seg_dir || (n_docs && (!field_offsets || !bytes))) { g_index_err = "nsh_index_documents: null argument"; return -1; }
+    const std::vector<nsx::DocInput> docs = to_docs(bytes, field_offsets, n_docs);
+    ns_ctx* ctx = nullptr;
+    if (ns_ctx_create(device, &ctx) != NS_OK) { g_index_err = std::string("ns_ctx_create: ") + ns_last_error(nullptr); return -1; }
+    nsx::IndexStats st;
+    const bool ok = nsx::index_documents(ctx, docs, seg_dir, st, g_index_err);
+    ns_ctx_destroy(ctx);
+    put_stats(stats, st);
+    return ok ? 0 : -1;
+} catch (const std::exception& ex) { g_index_err = std::string("nsh_index_documents: ") + ex.what(); return -1; }
+  catch (...) { g_index_err = "nsh_index_documents: unknown exception"; return -1; }
+}
+extern "C" int nsh_engine_open_noload(const char* index_dir, int device, nsh_engine** out) { try {
+    if (!out) return -1;
+    nsh_engine* e = new nsh_engine(device);
+    e->eng.index_dir = index_dir ? index_dir : "";
+    *out = e;
+    return 0;
+} NSH_CATCH(nullptr, "nsh_engine_open_noload", -1)
+}
+extern "C" int nsh_engine_add_documents(nsh_engine* e, const char* bytes, const uint64_t* field_offsets, uint32_t n_docs,
+                                        nsh_index_stats* stats) { try {
+    if (!e) return -1;
+    if (n_docs && (!field_offsets || !bytes)) { nsh_set_err(e, "nsh_engine_add_documents: null argument"); return -1; }
+    nsx::IndexStats st;
+    const bool ok = e->eng.add_documents(to_docs(bytes, field_offsets, n_docs), &st);
+    put_stats(stats, st);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_add_documents", -1)
 }
 
 // Semantic expansion (src/api_engine.cpp:409-417): rows/dim of the loaded embedding table (0/0: none), and the

@@ -1,6 +1,10 @@
 // ns_tool — small CLI over the host facade.
 //   ns_tool gen-index <index_dir> <n_segments> <docs_per_segment> [vocab=65536] [seed=1337] [--legacy]
 //   ns_tool search <index_dir> <k> <query text ...>        (needs an MI355X; prints the /api/search JSON body)
+//   ns_tool index <segment_dir> <documents_file> [device=0]  (needs an MI355X)
+//        documents_file: u32 n, then n x {string cord_uid, string title, string json_relpath, string text} with
+//        string = u32 length + bytes (include/indexio.hpp:18-29).  Runs the reference's two offline steps on the device:
+//        `forwardindex` from the extracted text onwards (forward_index.hpp) and `lexicon` (invert.hpp).  One JSON line.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -16,6 +20,7 @@
 
 #include "engine.hpp"
 #include "gen_index.hpp"
+#include "invert.hpp"
 
 int main(int argc, char** argv) {
     if (argc >= 5 && std::strcmp(argv[1], "gen-index") == 0) {
@@ -42,6 +47,27 @@ int main(int argc, char** argv) {
         std::string q;
         for (int i = 4; i < argc; i++) { if (i > 4) q.push_back(' '); q += argv[i]; }
         std::printf("%s\n", eng.search(q, k).c_str());
+        return 0;
+    }
+    if (argc >= 4 && std::strcmp(argv[1], "index") == 0) {
+        nsx::FileBytes in;
+        if (!in.load(argv[3])) { std::fprintf(stderr, "cannot read %s\n", argv[3]); return 1; }
+        const uint32_t n = in.u32();
+        if ((uint64_t)n * 16 > in.size()) { std::fprintf(stderr, "%s: document count %u does not fit the file\n", argv[3], n); return 1; }
+        std::vector<nsx::DocInput> docs(n);
+        for (auto& d : docs) { d.cord_uid = in.str(); d.title = in.str(); d.json_relpath = in.str(); d.text = in.str(); }
+        ns_ctx* ctx = nullptr;
+        if (ns_ctx_create(argc > 4 ? std::atoi(argv[4]) : 0, &ctx) != NS_OK) { std::fprintf(stderr, "ns_ctx_create: %s\n", ns_last_error(nullptr)); return 1; }
+        nsx::IndexStats st;
+        nsx::InvertStats ist;
+        std::string err;
+        const bool ok = nsx::index_documents(ctx, docs, argv[2], st, err) && nsx::invert_segment(ctx, argv[2], ist, err);
+        ns_ctx_destroy(ctx);
+        if (!ok) { std::fprintf(stderr, "index failed: %s\n", err.c_str()); return 1; }
+        std::printf("{\"docs_in\": %u, \"docs\": %u, \"terms\": %u, \"text_bytes\": %llu, \"tokens\": %llu, \"kept_tokens\": %llu, \"pairs\": %llu, "
+                    "\"forward_device_ms\": %.3f, \"forward_total_s\": %.4f, \"invert_device_ms\": %.3f, \"invert_total_s\": %.4f}\n",
+                    st.n_docs_in, st.n_docs, st.n_terms, (unsigned long long)st.text_bytes, (unsigned long long)st.tokens,
+                    (unsigned long long)st.kept_tokens, (unsigned long long)st.pairs, st.device_ms, st.total_s, ist.device_ms, ist.total_s);
         return 0;
     }
     if (argc >= 5 && std::strcmp(argv[1], "facade-bench") == 0) {
@@ -97,6 +123,6 @@ int main(int argc, char** argv) {
                     Q, K, refs.size(), reload_ms, p, p > 0 ? Q / (p * 1e-3) : 0.0, f, f > 0 ? Q / (f * 1e-3) : 0.0, reps, (unsigned long long)check);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n", argv[0], argv[0]);
+    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n", argv[0], argv[0], argv[0]);
     return 2;
 }

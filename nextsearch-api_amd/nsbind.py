@@ -62,6 +62,7 @@ HIP_SYMBOLS = [
     "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores",
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release",
+    "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
 ]
 HOST_SYMBOLS = [
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -72,7 +73,23 @@ HOST_SYMBOLS = [
     "nsh_engine_build_impacts", "nsh_engine_use_impacts", "nsh_engine_build_packed", "nsh_engine_use_packed", "nsh_engine_build_blockmax", "nsh_engine_use_pruning", "nsh_engine_use_merge", "nsh_engine_share_scores", "nsh_engine_use_skips", "nsh_invert_segment", "nsh_invert_error",
     "nsh_engine_semantic_info", "nsh_engine_expand", "nsh_engine_semantic_row", "nsh_engine_set_cache", "nsh_engine_cache_size",
     "nsh_engine_suggest_json", "nsh_engine_suggest_batch", "nsh_engine_suggest_table", "nsh_suggest_split", "nsh_suggest_clamp_limit",
+    "nsh_index_documents", "nsh_index_error", "nsh_engine_open_noload", "nsh_engine_add_documents",
 ]
+
+class NsForwardInfo(C.Structure):   # include/nextsearch_hip.h ns_forward_info
+    _fields_ = [("struct_size", C.c_uint32), ("kept_docs", C.c_uint32), ("n_terms", C.c_uint32), ("n_docs", C.c_uint32),
+                ("n_pairs", C.c_uint64), ("term_bytes", C.c_uint64), ("n_tokens", C.c_uint64), ("kept_tokens", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("device_ms", C.c_float), ("pad", C.c_uint32)]
+
+
+class NshIndexStats(C.Structure):   # include/nextsearch_host.h nsh_index_stats
+    _fields_ = [("struct_size", C.c_uint32), ("n_docs_in", C.c_uint32), ("n_docs", C.c_uint32), ("n_terms", C.c_uint32),
+                ("text_bytes", C.c_uint64), ("tokens", C.c_uint64), ("kept_tokens", C.c_uint64), ("pairs", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("avgdl", C.c_float), ("device_ms", C.c_float), ("call_s", C.c_double), ("total_s", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
 
 _hip = None
 _host = None
@@ -133,6 +150,11 @@ def hip_lib():
         L.ns_batch_destroy.argtypes = [vp]
         L.ns_batch_destroy.restype = None
         L.ns_set_tuning.argtypes = [vp, u32, u32, u32]
+        L.ns_forward_build.argtypes = [vp, vp, u64, vp, u32, C.POINTER(vp)]
+        L.ns_forward_get_info.argtypes = [vp, C.POINTER(NsForwardInfo)]
+        L.ns_forward_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.ns_forward_destroy.argtypes = [vp]
+        L.ns_forward_destroy.restype = None
         _hip = L
     return _hip
 
@@ -186,6 +208,10 @@ def host_lib():
         L.nsh_engine_search_batch_json.argtypes = [vp, C.POINTER(C.c_char_p), u32, i32, C.POINTER(vp), vp]
         L.nsh_invert_segment.argtypes = [C.c_char_p, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.nsh_invert_error.restype = C.c_char_p
+        L.nsh_index_documents.argtypes = [C.c_char_p, i32, vp, vp, u32, C.POINTER(NshIndexStats)]
+        L.nsh_index_error.restype = C.c_char_p
+        L.nsh_engine_open_noload.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_add_documents.argtypes = [vp, vp, vp, u32, C.POINTER(NshIndexStats)]
         L.nsh_engine_set_cache.argtypes = [vp, i32]
         L.nsh_engine_set_cache.restype = None
         L.nsh_engine_cache_size.argtypes = [vp]
@@ -317,6 +343,31 @@ class Engine:
             self.h = None
             raise RuntimeError(f"Engine.reload failed: {msg}")
         self.device = device
+
+    @classmethod
+    def create(cls, index_dir, device=0):
+        """An engine on a directory that may hold no segment yet (no initial reload): for add_documents on a fresh index."""
+        self = cls.__new__(cls)
+        self._L = host_lib()
+        h = C.c_void_p()
+        if self._L.nsh_engine_open_noload(str(index_dir).encode(), device, C.byref(h)) != 0:
+            raise RuntimeError("nsh_engine_open_noload failed")
+        self.h = h
+        self.device = device
+        return self
+
+    def add_documents(self, docs):
+        """Engine::add_documents: docs = iterable of (cord_uid, title, json_relpath, text) or dicts with those keys (str or
+        bytes); they become the next free segment, which is served after the call.  Returns the indexing stats."""
+        blob, offs = pack_documents(docs)
+        st = NshIndexStats(struct_size=C.sizeof(NshIndexStats))
+        old_ctx = self.ctx
+        rc = self._L.nsh_engine_add_documents(self.h, blob, offs.ctypes.data, (len(offs) - 1) // 4, C.byref(st))
+        if _ctx_key(self.ctx) != _ctx_key(old_ctx):
+            _LIVE_BATCHES.pop(_ctx_key(old_ctx), None)
+        if rc != 0:
+            raise RuntimeError(f"Engine.add_documents failed: {self.error()}")
+        return st.as_dict()
 
     def close(self):
         if self.h:
@@ -596,6 +647,64 @@ def invert_segment(seg_dir, device=0):
 
 def u64_():
     return C.c_uint64()
+
+
+DOC_FIELDS = ("cord_uid", "title", "json_relpath", "text")
+
+
+def pack_documents(docs):
+    """-> (bytes, u64 offsets[4 n + 1]): the four fields of every document back to back (include/nextsearch_host.h)"""
+    parts, offs, at = [], [0], 0
+    for d in docs:
+        fields = [d[k] for k in DOC_FIELDS] if isinstance(d, dict) else list(d)
+        assert len(fields) == 4
+        for f in fields:
+            b = f.encode("utf-8") if isinstance(f, str) else bytes(f)
+            parts.append(b)
+            at += len(b)
+            offs.append(at)
+    return b"".join(parts), np.asarray(offs, dtype=np.uint64)
+
+
+def index_documents(seg_dir, docs, device=0):
+    """The reference's `forwardindex` step from the extracted text onwards, on the device: writes docs.bin, stats.bin,
+    forward.bin, terms.bin into seg_dir; returns a stats dict.  Raises when no document survives (nothing written)."""
+    blob, offs = pack_documents(docs)
+    st = NshIndexStats(struct_size=C.sizeof(NshIndexStats))
+    rc = host_lib().nsh_index_documents(str(seg_dir).encode(), device, blob, offs.ctypes.data, (len(offs) - 1) // 4, C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"index_documents failed: {host_lib().nsh_index_error().decode()}")
+    return st.as_dict()
+
+
+def forward_build(ctx, texts):
+    """Raw ns_forward_build + fetch: texts = list of bytes -> dict(kept_docs, doc_len, counts, pairs[n, 2], terms[list of bytes], info)"""
+    L = hip_lib()
+    blob = b"".join(texts)
+    offs = np.zeros(len(texts) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+    h = C.c_void_p()
+    rc = L.ns_forward_build(ctx, blob, len(blob), offs.ctypes.data, len(texts), C.byref(h))
+    if rc != NS_OK:
+        raise RuntimeError(f"ns_forward_build: {rc}: {L.ns_last_error(ctx).decode()}")
+    try:
+        info = NsForwardInfo(struct_size=C.sizeof(NsForwardInfo))
+        assert L.ns_forward_get_info(h, C.byref(info)) == NS_OK
+        kept = np.zeros(info.kept_docs, dtype=np.uint32)
+        dl = np.zeros(info.kept_docs, dtype=np.uint32)
+        cnt = np.zeros(info.kept_docs, dtype=np.uint32)
+        pairs = np.zeros((info.n_pairs, 2), dtype=np.uint32)
+        tb = np.zeros(max(1, info.term_bytes), dtype=np.uint8)
+        to = np.zeros(info.n_terms + 1, dtype=np.uint64)
+        rc = L.ns_forward_fetch(h, kept.ctypes.data, dl.ctypes.data, cnt.ctypes.data, pairs.ctypes.data, tb.ctypes.data, to.ctypes.data)
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_forward_fetch: {rc}: {L.ns_last_error(ctx).decode()}")
+        raw = tb.tobytes()
+        terms = [raw[int(to[i]):int(to[i + 1])] for i in range(info.n_terms)]
+        return {"kept_docs": kept, "doc_len": dl, "counts": cnt, "pairs": pairs, "terms": terms,
+                "info": {k: getattr(info, k) for k, _ in info._fields_}}
+    finally:
+        L.ns_forward_destroy(h)
 
 
 # Batches alive per device context (keyed by the ctx pointer): a batch must be destroyed BEFORE its ctx (it returns its

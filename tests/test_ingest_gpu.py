@@ -1,0 +1,289 @@
+"""Indexing on the device (csrc/ns_ingest.hip behind ns_forward_build, nsx::index_documents, Engine::add_documents) against
+the Python restatement (tests/ingest_ref.py), file for file, and end to end against the REAL reference's recorded answers
+(tests/golden/ingest/ingest1.json).  Everything here is integers and bytes: every comparison is exact."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":   # the child process of test_order_independence_with_the_hash_narrowed
+    sys.path.insert(0, os.path.join(ROOT, "nextsearch-api_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import ingest_ref  # noqa: E402
+import nsbind  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ingest", "ingest1.json")
+VARIANTS_LIB = os.path.join(ROOT, "nextsearch-api_amd", "libnextsearch_hip_variants.so")
+NS_E_INVAL, NS_E_STATE = -1, -5
+
+SEPS = [b" ", b" ", b" ", b" ", b", ", b". ", b"-", b"\n", b"\t", b" (", b") ", b"\x00", b"\xc3\xa9", b"\xff\xfe", b"/", b"  "]
+
+
+def make_vocab(rng, n):
+    letters = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz0123456789", dtype=np.uint8)
+    stop = sorted(ingest_ref.STOP_WORDS)
+    out = []
+    for i in range(n):
+        if i % 5 == 1 and i // 5 < len(stop):
+            out.append(stop[i // 5])                                   # stop words sit among the most frequent ranks
+        elif i % 17 == 3:
+            out.append(bytes(rng.choice(letters, 1)))                  # one-byte tokens
+        else:
+            out.append(bytes(rng.choice(letters, int(rng.integers(2, 13)))) + (b"%d" % i if i % 3 == 0 else b""))
+    return out
+
+
+def gen_corpus(seed, n_docs, words_per_doc, vocab=5000, long_tokens=(70001,), many=0):
+    """A seeded corpus: Zipf vocabulary with case, punctuation, NUL and bytes >= 0x80 as separators, empty documents,
+    documents of dropped tokens only, documents that end inside a token followed by one that starts with alnum bytes,
+    and tokens longer than 70 000 bytes (twice each, in different letter case, plus a neighbour differing in its last byte)."""
+    rng = np.random.default_rng(seed)
+    words = make_vocab(rng, vocab)
+    variants = [[w, w.upper(), w.capitalize()] for w in words]
+    docs = []
+    for d in range(n_docs):
+        r = d % 97
+        if r == 13:
+            docs.append(b"")
+            continue
+        if r == 29:
+            docs.append(b"The of AND a b c ;;")
+            continue
+        n = max(1, int(rng.integers(words_per_doc // 2, words_per_doc * 3 // 2 + 1)))
+        ranks = np.minimum(rng.zipf(1.25, n) - 1, vocab - 1)
+        case = rng.integers(0, 12, n)
+        seps = rng.integers(0, len(SEPS), n)
+        parts = []
+        for k in range(n):
+            parts.append(variants[ranks[k]][case[k] if case[k] < 3 else 0])
+            parts.append(SEPS[seps[k]])
+        if r in (41, 42):
+            parts.pop()                                                # ends inside a token; the next document starts with one
+        docs.append(b"".join(parts))
+    letters = np.frombuffer(b"abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789", dtype=np.uint8)
+    for i, ln in enumerate(long_tokens):
+        big = bytes(rng.choice(letters, ln))
+        at = (i * 7 + 3) % max(1, n_docs)
+        docs[at] = docs[at] + b" " + big + b" mid " + big.swapcase() + b"." + big[:-1] + (b"0" if big[-1:] != b"0" else b"1")
+    if many:
+        docs[n_docs // 2] = docs[n_docs // 2] + b" " + b"Quokka,quokka " * (many // 2)
+    return docs
+
+
+def as_docs(texts):
+    return [(b"uid%07d" % i, b"Title %d" % i, b"document_parses/pdf_json/%07d.json" % i, t) for i, t in enumerate(texts)]
+
+
+def assert_device_equals_restatement(tmp_path, docs, name, min_tokens=0):
+    seg = str(tmp_path / name)
+    st = nsbind.index_documents(seg, docs)
+    fwd = ingest_ref.build([ingest_ref.doc_text(d) for d in docs])
+    want = ingest_ref.file_bytes(docs, fwd)
+    for fn in ingest_ref.FILES:
+        got = open(os.path.join(seg, fn), "rb").read()
+        assert len(got) == len(want[fn]) and got == want[fn], (name, fn)
+    assert st["n_docs"] == len(fwd["kept_docs"]) and st["n_terms"] == len(fwd["terms"]) and st["pairs"] == len(fwd["pairs"])
+    assert st["kept_tokens"] == int(fwd["doc_len"].sum()) and st["tokens"] >= max(min_tokens, st["kept_tokens"])
+    print(f"{name}: {st}")
+    return st, fwd
+
+
+def load_fixture():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def test_fixture_corpus_four_files_equal_the_restatement(tmp_path):
+    g = load_fixture()
+    assert_device_equals_restatement(tmp_path, g["documents"], "fixture")
+
+
+@pytest.mark.parametrize("n_docs,words,long_tokens,min_tokens", [(1, 40, (70001,), 20), (1000, 120, (70001, 90000), 100_000),
+                                                                 (12000, 365, (70001, 70002, 131072), 4_000_000)])
+def test_generated_corpora_equal_the_restatement(tmp_path, n_docs, words, long_tokens, min_tokens):
+    texts = gen_corpus(1000 + n_docs, n_docs, words, long_tokens=long_tokens)
+    st, fwd = assert_device_equals_restatement(tmp_path, as_docs(texts), f"gen{n_docs}", min_tokens)
+    assert max(len(t) for t in fwd["terms"]) > 70000
+    if n_docs > 1:
+        assert st["n_docs"] < n_docs                                   # empty documents and documents of dropped tokens only
+
+
+def test_one_document_with_1e5_occurrences_of_one_term(tmp_path):
+    texts = gen_corpus(5, 50, 60, long_tokens=(), many=100_000)
+    st, fwd = assert_device_equals_restatement(tmp_path, as_docs(texts), "many")
+    tid = fwd["terms"].index(b"quokka")
+    assert (fwd["pairs"][fwd["pairs"][:, 0] == tid][:, 1] == 100_000).all()
+
+
+@pytest.mark.parametrize("texts", [[b" .,;\x00\xff\n"], [b"", b"  ", b"--"], [b"the of", b"a b c", b"", b"AND The"], []])
+def test_no_surviving_document_is_an_error_and_nothing_is_written(tmp_path, texts):
+    seg = str(tmp_path / "seg")
+    with pytest.raises(RuntimeError, match="no document"):
+        nsbind.index_documents(seg, as_docs(texts))
+    assert not os.path.exists(seg)
+
+
+def _child(out_dir):
+    assert "variants" in os.path.basename(nsbind.HIP_LIB_PATH)
+    texts = gen_corpus(2001, 1000, 120, long_tokens=(70001, 90000))
+    nsbind.index_documents(out_dir, as_docs(texts))
+
+
+def test_order_independence_with_the_hash_narrowed(tmp_path):
+    """The variants build narrows the hash to 3 bits (NS_INGEST_HASH_BITS; the product library ignores the knob): every
+    probe collides, the table is filled in another order, and only the byte comparison tells terms apart.  Same files."""
+    assert os.path.exists(VARIANTS_LIB), "libnextsearch_hip_variants.so is missing: make -C nextsearch-api_amd variants"
+    texts = gen_corpus(2001, 1000, 120, long_tokens=(70001, 90000))
+    a, b = str(tmp_path / "product"), str(tmp_path / "narrow")
+    os.environ["NS_INGEST_HASH_BITS"] = "3"                            # ignored by the product library
+    try:
+        nsbind.index_documents(a, as_docs(texts))
+    finally:
+        del os.environ["NS_INGEST_HASH_BITS"]
+    env = dict(os.environ, NS_HIP_LIB=VARIANTS_LIB, NS_INGEST_HASH_BITS="3")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), b], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    for fn in ingest_ref.FILES:
+        assert open(os.path.join(a, fn), "rb").read() == open(os.path.join(b, fn), "rb").read(), fn
+    want = ingest_ref.file_bytes(as_docs(texts), ingest_ref.build(texts))
+    for fn in ingest_ref.FILES:
+        assert open(os.path.join(a, fn), "rb").read() == want[fn], fn
+
+
+def _answers(eng, queries, k):
+    hits, nhits, found, usable = eng.search_batch(queries, k, 0)
+    out = []
+    for q in range(len(queries)):
+        n = int(nhits[q])
+        out.append({"found": int(found[q]) if usable[q] else -1,
+                    "hits": [[int(h["seg"]), int(h["doc"]), int(np.asarray(h["score"]).view(np.uint32))] for h in hits[q, :n]]})
+    return out
+
+
+def test_add_documents_end_to_end_equals_the_reference_answers(tmp_path):
+    g = load_fixture()
+    index = str(tmp_path / "index")
+    os.makedirs(index)
+    eng = nsbind.Engine.create(index, 0)
+    try:
+        st = eng.add_documents(g["documents"])
+        assert st["n_docs"] == len(g["forward"]) and eng.num_segments == 1
+        assert os.path.isdir(os.path.join(index, "segments", "seg_000000"))
+        queries = [q["query"] for q in g["queries"]]
+        got = _answers(eng, queries, g["k"])
+        for q, a in zip(g["queries"], got):
+            assert a["found"] == q["found"] and a["hits"] == q["hits"], q["query"]      # docIds, ranks, found, fp32 score bits
+
+        # a second batch becomes seg_000001; both segments answer; autocomplete sees the new terms
+        manifest = os.path.join(index, "manifest.bin")
+        eng.add_documents([("n0", "new 0", "p0", "Quokka zebrafish covid"), ("n1", "new 1", "p1", "the of"), ("n2", "new 2", "p2", "quokka QUOKKA habitat")])
+        assert eng.num_segments == 2 and os.path.isdir(os.path.join(index, "segments", "seg_000001"))
+        both = _answers(eng, ["quokka", "covid"], 100)
+        assert both[0]["found"] == 2 and [h[:2] for h in both[0]["hits"]] == [[1, 1], [1, 0]]   # equal lengths: tf 2 first
+        ref_covid = next(q for q in g["queries"] if q["query"] == "covid")
+        assert both[1]["found"] == ref_covid["found"] + 1 and any(h[0] == 1 for h in both[1]["hits"])
+        assert b"quokka" in eng.suggest_json("quok", 5)
+
+        # a call that fails leaves the manifest as it is and no directory behind
+        before = open(manifest, "rb").read()
+        with pytest.raises(RuntimeError, match="no document"):
+            eng.add_documents([("x", "t", "p", "the of and"), ("y", "t", "p", "")])
+        assert open(manifest, "rb").read() == before
+        assert sorted(os.listdir(os.path.join(index, "segments"))) == ["seg_000000", "seg_000001"]
+        assert eng.num_segments == 2 and _answers(eng, ["quokka"], 10)[0]["found"] == 2
+    finally:
+        eng.close()
+
+
+def test_a_failing_first_call_on_a_fresh_directory_writes_nothing(tmp_path):
+    index = str(tmp_path / "index")
+    os.makedirs(index)
+    eng = nsbind.Engine.create(index, 0)
+    try:
+        with pytest.raises(RuntimeError, match="no document"):
+            eng.add_documents([("x", "t", "p", "of the a")])
+        assert os.listdir(index) == []
+    finally:
+        eng.close()
+
+
+def test_raw_c_abi_codes_and_handle_lifetime():
+    L = nsbind.hip_lib()
+    ctx = C.c_void_p()
+    assert L.ns_ctx_create(0, C.byref(ctx)) == 0
+    text = b"Alpha beta alpha. The gamma"
+    h = C.c_void_p()
+
+    def build(offsets, n_docs, nbytes=len(text)):
+        offs = np.asarray(offsets, dtype=np.uint64)
+        return L.ns_forward_build(ctx, text, nbytes, offs.ctypes.data, n_docs, C.byref(h))
+
+    assert build([0, 17, 5], 2) == NS_E_INVAL and b"decrease" in L.ns_last_error(ctx) and not h.value
+    assert build([0, 17, len(text) + 1], 2) == NS_E_INVAL and b"past" in L.ns_last_error(ctx) and not h.value
+    assert build([3, 17, len(text)], 2) == NS_E_INVAL
+    assert L.ns_forward_build(ctx, text, len(text), None, 2, C.byref(h)) == NS_E_INVAL
+    assert L.ns_forward_build(ctx, text, len(text), None, 0, None) == NS_E_INVAL
+    # n_docs == 0: an empty result
+    assert L.ns_forward_build(ctx, text, len(text), None, 0, C.byref(h)) == 0 and h.value
+    info = nsbind.NsForwardInfo(struct_size=C.sizeof(nsbind.NsForwardInfo))
+    assert L.ns_forward_get_info(h, C.byref(info)) == 0 and info.kept_docs == 0 and info.n_terms == 0 and info.n_pairs == 0
+    assert L.ns_forward_fetch(h, None, None, None, None, None, None) == 0
+    L.ns_forward_destroy(h)
+    # struct_size is honoured: a caller compiled against a shorter struct gets no byte past it
+    assert build([0, 17, len(text)], 2) == 0
+    short = nsbind.NsForwardInfo(struct_size=12)
+    short.n_docs = 0xABCDEF
+    assert L.ns_forward_get_info(h, C.byref(short)) == 0 and short.kept_docs == 2 and short.n_terms == 3 and short.n_docs == 0xABCDEF
+    bad = nsbind.NsForwardInfo(struct_size=0)
+    assert L.ns_forward_get_info(h, C.byref(bad)) == NS_E_INVAL and L.ns_forward_get_info(h, None) == NS_E_INVAL
+    # fetched twice, destroyed once
+    rows = []
+    for _ in range(2):
+        kept, dl, cnt = (np.zeros(2, dtype=np.uint32) for _ in range(3))
+        pairs = np.zeros((3, 2), dtype=np.uint32)
+        tb, to = np.zeros(14, dtype=np.uint8), np.zeros(4, dtype=np.uint64)
+        assert L.ns_forward_fetch(h, kept.ctypes.data, dl.ctypes.data, cnt.ctypes.data, pairs.ctypes.data, tb.ctypes.data, to.ctypes.data) == 0
+        rows.append((kept.tolist(), dl.tolist(), cnt.tolist(), pairs.tolist(), tb.tobytes(), to.tolist()))
+    assert rows[0] == rows[1] == ([0, 1], [3, 1], [2, 1], [[0, 2], [1, 1], [2, 1]], b"alphabetagamma", [0, 5, 9, 14])
+    L.ns_forward_destroy(h)
+    # a handle that outlives its ctx: orphaned, not dangling
+    assert build([0, 17, len(text)], 2) == 0
+    L.ns_ctx_destroy(ctx)
+    assert L.ns_forward_get_info(h, C.byref(info)) == 0 and info.kept_docs == 2
+    assert L.ns_forward_fetch(h, None, None, None, None, None, None) == NS_E_STATE
+    L.ns_forward_destroy(h)
+
+
+def test_forward_build_feeds_invert_forward_directly():
+    """counts and pairs are exactly the arrays ns_invert_forward takes"""
+    L = nsbind.hip_lib()
+    ctx = C.c_void_p()
+    assert L.ns_ctx_create(0, C.byref(ctx)) == 0
+    try:
+        texts = gen_corpus(77, 300, 80, long_tokens=())
+        got = nsbind.forward_build(ctx, texts)
+        want = ingest_ref.build(texts)
+        for k in ("kept_docs", "doc_len", "counts", "pairs"):
+            assert np.array_equal(got[k], want[k]), k
+        assert got["terms"] == want["terms"]
+        n_terms, n_pairs = len(got["terms"]), len(got["pairs"])
+        df = np.zeros(n_terms, dtype=np.uint32)
+        post = np.zeros((n_pairs, 2), dtype=np.uint32)
+        kept = C.c_uint64()
+        pairs = np.ascontiguousarray(got["pairs"])
+        assert L.ns_invert_forward(ctx, got["counts"].ctypes.data, len(got["counts"]), pairs.ctypes.data, n_pairs, n_terms, df.ctypes.data,
+                                   post.ctypes.data, C.byref(kept), None) == 0
+        assert kept.value == n_pairs and np.array_equal(df, np.bincount(pairs[:, 0], minlength=n_terms))
+    finally:
+        L.ns_ctx_destroy(ctx)
+
+
+if __name__ == "__main__":
+    _child(sys.argv[1])
