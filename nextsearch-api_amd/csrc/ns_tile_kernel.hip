@@ -28,6 +28,77 @@ namespace ns {
 __device__ unsigned long long g_ns_tcnt[12];   // diagnostic build: event counts of the doc-tile body (tools/dbg/count_run.py)
 #endif
 
+// The PARTIAL round of a term on the skip grid: the 1..255 postings that the term's full rounds leave in the tile, as
+// C = 1..4 chunks of 64.  The wave knows them as two scalars before any load, so the round is straight-line code: exactly
+// C chunk loads, chunks 0 .. C-2 with every lane live, chunk C-1 under ONE scalar lane mask `lastm` (all ones when that
+// chunk is full), which enters the `found` popcount and guards the LDS write.  The LDS read stays unconditional (the slot
+// index is masked into the tile; what a lane past the end reads is dropped).  Same arithmetic on the same slots as the
+// general round of tscore_body.  Returns the number of slots touched for the first time (OR mode).  tscore_body uses
+// C = 1..3 and runs four chunks as two rounds of two (the four-chunk form costs k_uscore a wave per SIMD).
+template <int TD, bool AND, bool IMP, int C>
+__device__ __forceinline__ uint32_t tile_round_exact(const gp_u2 sp, const gp_f32 np, const uint64_t lastm,
+                                                     const float idf, const float wq, const bool fast_div, const uint32_t tile_lo,
+                                                     float* vals, uint8_t* mcnt, const int lane) {
+    nat_u2 ps[C];
+    float nr[C], x[C], old[C];
+    uint32_t slot[C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        ps[j] = sp[j * 64 + lane];
+        if (!IMP) nr[j] = np[j * 64 + lane];
+    }
+    // src/api_engine.cpp:477-480, operation for operation; by pairs of chunks like the full round (the compiler packs the
+    // two BM25 evaluations into v_pk_* instructions), then the odd chunk
+#pragma unroll
+    for (int j0 = 0; j0 < C; j0 += 2) {
+        const int nj = C - j0 >= 2 ? 2 : 1;
+        if (IMP) {
+#pragma unroll
+            for (int jj = 0; jj < nj; jj++) x[j0 + jj] = __uint_as_float(ps[j0 + jj].y);
+        } else if (nj == 2) {
+            float num_[2], den_[2], q_[2];
+#pragma unroll
+            for (int jj = 0; jj < 2; jj++) {
+                const float tf = (float)ps[j0 + jj].y;
+                den_[jj] = tf + nr[j0 + jj];
+                num_[jj] = idf * (tf * (1.2f + 1.0f));
+            }
+            ns_div_n<2>(q_, num_, den_, fast_div);
+            x[j0] = q_[0];
+            x[j0 + 1] = q_[1];
+        } else {
+            float num_[1], den_[1], q_[1];
+            const float tf = (float)ps[j0].y;
+            den_[0] = tf + nr[j0];
+            num_[0] = idf * (tf * (1.2f + 1.0f));
+            ns_div_n<1>(q_, num_, den_, fast_div);
+            x[j0] = q_[0];
+        }
+#pragma unroll
+        for (int jj = 0; jj < nj; jj++) {
+            slot[j0 + jj] = (ps[j0 + jj].x - tile_lo) & (uint32_t)(TD - 1);
+            old[j0 + jj] = vals[slot[j0 + jj]];
+        }
+    }
+    uint32_t fresh_n = 0;
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        const bool fresh_ = __float_as_uint(old[j]) == kTileEmptyBits;
+        if (!AND) fresh_n += (uint32_t)__popcll(j == C - 1 ? (wballot(fresh_) & lastm) : wballot(fresh_));
+        old[j] = fresh_ ? 0.0f : old[j];
+    }
+#pragma unroll
+    for (int j = 0; j < C - 1; j++) {
+        vals[slot[j]] = old[j] + wq * x[j];
+        if (AND) mcnt[slot[j]] = (uint8_t)(mcnt[slot[j]] + 1);
+    }
+    if (__builtin_amdgcn_inverse_ballot_w64(lastm)) {
+        vals[slot[C - 1]] = old[C - 1] + wq * x[C - 1];
+        if (AND) mcnt[slot[C - 1]] = (uint8_t)(mcnt[slot[C - 1]] + 1);
+    }
+    return fresh_n;
+}
+
 template <int TD, bool AND, int CB = 256, bool IMP = false>
 __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* __restrict__ terms, const DevSeg* __restrict__ segs,
                                             float* vals, uint8_t* mcnt, uint64_t* cand,
@@ -93,6 +164,8 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
         }
     }
     const uint64_t gridm = grid ? wballot(on_grid) : 0ull;
+    // every term of the item is on the grid (wave-uniform, once per item): the round-size estimate (`frac`) is dead
+    const bool all_grid = gridm != 0ull && gridm == (~0ull >> ((64u - T) & 63u));
 
     const uint32_t last_doc = it.doc_hi - 1;   // host guarantees doc_hi > doc_lo and doc_hi <= n_docs
     WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one tile
@@ -137,8 +210,11 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
         done = lo > last_doc;                                                                      \
         if (!done) {                                                                               \
             hi = (last_doc - lo >= (uint32_t)TD) ? (lo + (uint32_t)(TD - 1)) : last_doc;           \
-            frac = (float)(hi - lo + 1u) * __builtin_amdgcn_rcpf((float)(last_doc - lo + 1u));     \
-            act = wballot(nd <= hi) | (wballot(end > cur) & gridm);                                \
+            if (all_grid) act = wballot(end > cur);   /* no cursor term: nothing sizes a round */  \
+            else {                                                                                 \
+                frac = (float)(hi - lo + 1u) * __builtin_amdgcn_rcpf((float)(last_doc - lo + 1u)); \
+                act = wballot(nd <= hi) | (wballot(end > cur) & gridm);                            \
+            }                                                                                      \
         }                                                                                          \
     } else {                                                                                       \
         const uint32_t mind_ = wave_min_dpp(nd);                                                   \
@@ -163,19 +239,21 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
             act &= act - 1ull;
             uint32_t s_cur = rdlane(cur, t);
             const uint32_t s_end = rdlane(end, t);
-            const float idf = __uint_as_float(rdlane(idf_bits, t));
+            const float idf = IMP ? 0.0f : __uint_as_float(rdlane(idf_bits, t));   // IMP: the scores are in the stream
             const float wq = __uint_as_float(rdlane(wq_bits, t));
-            const bool exact = ((gridm >> t) & 1ull) != 0ull;   // [s_cur, s_end) are the term's postings of this tile, all of them
-            uint32_t want = exact ? (uint32_t)(E * 64) : 16u + (uint32_t)((float)(s_end - s_cur) * frac * 1.125f);
-            uint32_t s_nd = 0xFFFFFFFFu;
-            for (;;) {
-                const uint32_t remd = s_end - s_cur;
-                if (remd == 0) break;
-                if (exact && remd >= (uint32_t)(E * 64)) {
+            if (((gridm >> t) & 1ull) != 0ull) {
+                // ---- a term on the skip grid: [s_cur, s_end) are its postings of this tile, all of them.  Nothing to
+                //      estimate, nothing to compare with tile_hi, no count to take, no next docId to find, and no cursor to
+                //      write back (the tile header re-derives cur / end from the table): full rounds of 256, then at most
+                //      ONE partial round, dispatched once on its chunk count to straight-line code (tile_round_exact).
+                //      An earlier attempt (profiles/r02/ab) ran ALL rounds of such a term as four-chunk straight-line code
+                //      and parked the lanes past the end on dummy slots: fewer instructions, but slower on mixed batches.
+                //      This one loads only the chunks that hold postings and masks the one ragged chunk; it parks nothing
+                //      (profiles/tile_exact). ----
+                uint32_t remd = s_end - s_cur;
+                for (; remd >= (uint32_t)(E * 64); remd -= (uint32_t)(E * 64)) {
                     // A FULL round on the skip grid: 256 postings that are all in this tile.  No lane masks, no exec
                     // games, no per-chunk branches: the arithmetic of the general round below with every lane live.
-                    // (Measured next to it: ALL rounds of such a term as straight-line code, lanes past the segment's end
-                    // parked on dummy slots — fewer instructions, but slower on mixed batches; profiles/r02/ab.)
 #ifdef NS_COUNT
                     const unsigned long long tr0_ = __builtin_readcyclecounter();
 #endif
@@ -222,14 +300,43 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     NS_TCNT(11, __builtin_readcyclecounter() - tr0_);
 #endif
-                    continue;
                 }
+                if (remd != 0u) {
+                    const uint32_t c_ = (remd + 63u) >> 6;
+                    const uint32_t left_ = remd - ((c_ - 1u) << 6);   // 1..64 postings in the last chunk
+                    const uint64_t lastm = ~0ull >> (64u - left_);
+                    const gp_u2 sp_ = stream + s_cur;
+                    const gp_f32 np_ = pnorm + s_cur;
+                    NS_TCNT(3, 1); NS_TCNT(4, c_); NS_TCNT(5, remd);
+                    uint32_t fr_;
+                    switch (c_) {
+                    case 1: fr_ = tile_round_exact<TD, AND, IMP, 1>(sp_, np_, lastm, idf, wq, fast_div, tile_lo, vals, mcnt, lane); break;
+                    case 2: fr_ = tile_round_exact<TD, AND, IMP, 2>(sp_, np_, lastm, idf, wq, fast_div, tile_lo, vals, mcnt, lane); break;
+                    case 3: fr_ = tile_round_exact<TD, AND, IMP, 3>(sp_, np_, lastm, idf, wq, fast_div, tile_lo, vals, mcnt, lane); break;
+                    default:   // four chunks as two rounds of two (docIds of one term are distinct: no fence between them): the four-chunk
+                               // form costs the kernel a register more than 72, i.e. a wave per SIMD
+                        fr_ = tile_round_exact<TD, AND, IMP, 2>(sp_, np_, ~0ull, idf, wq, fast_div, tile_lo, vals, mcnt, lane);
+                        fr_ += tile_round_exact<TD, AND, IMP, 2>(sp_ + 128, np_ + 128, lastm, idf, wq, fast_div, tile_lo, vals, mcnt, lane);
+                        break;
+                    }
+                    found_s += fr_;
+                }
+                wave_sync();   // the next term's read-add-writes follow this term's
+                continue;
+            }
+            // ---- a cursor term (a list without a skip table, or an item off the grid): rounds sized by estimate, the
+            //      tile's end found by comparing docIds ----
+            uint32_t want = 16u + (uint32_t)((float)(s_end - s_cur) * frac * 1.125f);
+            uint32_t s_nd = 0xFFFFFFFFu;
+            for (;;) {
+                const uint32_t remd = s_end - s_cur;
+                if (remd == 0) break;
                 const uint32_t n = NS_ROUND_SIZE(remd, want);
                 NS_ISSUE(ps, nr, s_cur, n);
                 NS_TCNT(3, 1);                       // rounds
                 NS_TCNT(4, (n + 63) / 64);           // chunks loaded
                 const bool expect_more = want > n;
-                if (!exact) want = expect_more ? (want - n) : 64u;   // exact: every round is as large as what is left allows
+                want = expect_more ? (want - n) : 64u;
                 uint32_t cnt = 0;
                 uint64_t takem[E];
                 float x[E];
@@ -246,7 +353,7 @@ __device__ __forceinline__ void tscore_body(const DevWItem& it, const DevTerm* _
                         const int j = (J0) + jj;                                                   \
                         const uint32_t left = (n > (uint32_t)(j * 64)) ? (n - (uint32_t)(j * 64)) : 0u;   /* scalar */ \
                         const uint64_t nmask = (left >= 64u) ? ~0ull : ((1ull << left) - 1ull);    \
-                        takem[j] = exact ? nmask : (wballot(ps[j].x <= tile_hi) & nmask);          \
+                        takem[j] = wballot(ps[j].x <= tile_hi) & nmask;                            \
                         cnt += (uint32_t)__popcll(takem[j]);                                       \
                         const float tf = (float)ps[j].y;                                           \
                         den_[jj] = tf + nr[j];                                                     \
