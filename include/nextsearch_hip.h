@@ -369,6 +369,37 @@ int ns_forward_fetch(ns_forward* fwd, uint32_t* kept_docs_out, uint32_t* doc_len
  * handle has no ctx any more. */
 void ns_forward_destroy(ns_forward* fwd);
 
+/* Compaction (csrc/ns_compact.hip): the forward indexes of several segments -> the forward index of ONE
+ * segment.  A source is what a segment's docs.bin / forward.bin / terms.bin hold, in host memory: */
+typedef struct ns_forward_src {
+    uint32_t n_docs;  const uint32_t* doc_len;  const uint32_t* counts;   /* [n_docs]: kept tokens, pairs of each document */
+    uint64_t n_pairs; const uint32_t* pairs;                              /* u32 {termId, tf} x n_pairs, file order */
+    uint32_t n_terms; const uint8_t* term_bytes; const uint64_t* term_offsets;   /* [n_terms + 1]: term t = term_bytes[term_offsets[t] .. term_offsets[t + 1]) */
+} ns_forward_src;
+/* The result is an ordinary ns_forward handle: ns_forward_get_info, ns_forward_fetch, ns_forward_destroy and the lifetime
+ * rules above apply; kept_docs_out is the identity, n_docs == kept_docs, n_tokens == kept_tokens == the sum of doc_len.
+ *   DOCUMENTS  the sources' documents back to back in source order; docId = position.
+ *   TERM IDS   walk the sources' term lists in source order, each in its own id order: a byte string gets the next free id
+ *              the first time it is seen.  For sources numbered by ns_forward_build's rule this IS "rank of the first kept
+ *              occurrence in the concatenated input": merging the segments of batches D1 .. Dn gives the arrays that one
+ *              ns_forward_build of D1 + .. + Dn gives.  For sources numbered otherwise (the reference's unordered_map
+ *              order) it is still deterministic and independent of GPU scheduling.
+ *   PAIRS      termId replaced through that map, then ascending termId inside each document (src/ForwardIndex.cpp:176).
+ * Refused with NS_E_INVAL and a message that names the source, nothing left allocated: a termId >= the source's n_terms;
+ * the same byte string twice in ONE source's term list (two pairs of a document could collide); counts that do not sum to
+ * n_pairs; term offsets that decrease; totals beyond the widths the kernels use — term bytes of all sources below
+ * 4 GiB - 64 KiB, pairs below 2^32 - 4096, documents below 2^32 - 1, source terms below 2^31; the totals are checked from
+ * the counts and offsets before a byte of payload is read.  n_src == 0, or no document at all: NS_OK, empty result. */
+int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t n_src, ns_forward** out);
+/* ns_invert_forward over a handle's pairs and counts where they are, on the device: nothing is uploaded.  df_out[n_terms],
+ * postings_out (capacity n_pairs * 8 bytes), kept_out and device_ms_out as there.  NS_E_STATE on an orphaned handle. */
+int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postings_out, uint64_t* kept_out, float* device_ms_out);
+/* ns_forward_merge sorts the pairs of a document where they lie: up to 64 pairs in one wave's registers, up to
+ * ns_compact_doc_cut() pairs in LDS by one workgroup; longer documents go through the global radix sort.  on == 0 sends
+ * every document through the radix sort (the A/B baseline; same bytes).  Default: on. */
+uint32_t ns_compact_doc_cut(void);
+int ns_ctx_use_docsort(ns_ctx* ctx, int on);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

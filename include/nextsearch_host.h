@@ -162,6 +162,30 @@ int nsh_engine_open_noload(const char* index_dir, int device, nsh_engine** out);
 int nsh_engine_add_documents(nsh_engine* e, const char* bytes, const uint64_t* field_offsets, uint32_t n_docs,
                              nsh_index_stats* stats);
 
+/* Compaction (host/compact.hpp): several segments become one.  The sources' docs.bin, stats.bin,
+ * forward.bin and terms.bin are read and cross-checked on the host; the term lists are merged, the pairs remapped and
+ * re-sorted (ns_forward_merge) and inverted (ns_forward_invert) on the device; the result is a complete segment: the four
+ * forward files, barrels.bin and the 64 + 64 barrel files.  For sources whose term ids follow ns_forward_build's rule it is
+ * byte for byte the segment ONE nsh_index_documents + nsh_invert_segment over all their documents writes. */
+typedef struct nsh_compact_stats {
+    uint32_t struct_size;   /* IN: sizeof(nsh_compact_stats) as the caller was compiled; no more than that is written */
+    uint32_t sources, n_docs, n_terms;
+    uint64_t terms_in, pairs, device_bytes;
+    float    merge_ms, invert_ms;   /* HIP events around the device parts */
+    double   call_s, total_s;
+} nsh_compact_stats;
+/* Merges the segment directories source_dirs[0 .. n_sources) into out_dir (created) on a context of its own on `device`.
+ * The sources are read and checked before the device is touched.  -1 on failure: nothing is written,
+ * nsh_compact_error() says why and names the file or the source.  stats may be NULL. */
+int nsh_merge_segments(const char* const* source_dirs, uint32_t n_sources, const char* out_dir, int device, nsh_compact_stats* stats);
+const char* nsh_compact_error(void);
+/* Engine::compact: the segments at manifest positions [first, first + count) (clamped to the manifest) become the next
+ * free segments/seg_%06u, whose name takes the range's place in manifest.bin; the engine reloads; with remove_sources the
+ * source directories are removed afterwards.  Fewer than two segments in the range: 0, nothing touched.  -1 on failure
+ * (also on a host-only engine): the manifest keeps its bytes, the new directory is gone, no source is touched, the engine
+ * answers as before, nsh_engine_error() says why.  0 with a non-empty nsh_engine_error(): a source could not be removed. */
+int nsh_engine_compact(nsh_engine* e, uint64_t first, uint64_t count, int remove_sources, nsh_compact_stats* stats);
+
 /* Autocomplete: Engine::suggest(input, limit) (include/api_engine.hpp:67, src/api_engine.cpp:164-187).  The input is
  * input_len raw bytes (NUL and other control bytes included); *json_out receives {"limit", "query", "suggestions"} in
  * dump(2) layout (free with nsh_free).  -1 without a device context (there is no CPU path) or on failure. */

@@ -23,6 +23,7 @@
 #include "ns_tile_kernel.hip"
 #include "ns_invert.hip"
 #include "ns_ingest.hip"
+#include "ns_compact.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 
@@ -110,7 +111,8 @@ struct ns_ctx {
     ShareRegistry share;   // every list a sharing batch built (ns_ctx_share_scores) and the sharing batches alive
     BatchPlan plan;        // ns_batch_prepare's host threads and per-thread scratch, kept from batch to batch
     std::vector<ns_ac*> acs;   // autocomplete tables (ns_ac_upload): owned by the ctx, freed by ns_ac_release or ns_ctx_destroy
-    std::vector<ns_forward*> fwds;   // live forward-index handles (ns_forward_build): orphaned, not freed, by ns_ctx_destroy
+    std::vector<ns_forward*> fwds;   // live forward-index handles (ns_forward_build, ns_forward_merge): orphaned, not freed, by ns_ctx_destroy
+    bool cp_inplace = true;          // ns_forward_merge sorts documents up to kCpDocCut pairs where they lie (ns_ctx_use_docsort)
 };
 
 static thread_local std::string g_create_err;
@@ -1513,11 +1515,12 @@ extern "C" int ns_search_batch(ns_ctx* ctx, const ns_query_desc* queries, const 
 // f3: forward.bin -> inverted lists (csrc/ns_invert.hip)
 // `adopt` != nullptr: the inverted lists also become the posting stream of that segment (an upload in progress whose announced
 // payload is n_pairs postings) by a device-to-device copy; postings_out may then be NULL.
+// `dev_pairs` != nullptr: the pairs are on the device already (ns_forward_invert); `pairs` is not read and nothing is uploaded for them.
 static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_docs, const uint32_t* pairs,
                       uint64_t n_pairs, uint32_t n_terms, uint32_t* df_out, void* postings_out, uint64_t* kept_out,
-                      float* device_ms_out, ns_seg* adopt) {
+                      float* device_ms_out, ns_seg* adopt, const uint2* dev_pairs = nullptr) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_invert_forward: ctx is NULL");
-    if ((n_docs && !doc_term_counts) || (n_pairs && !pairs) || (n_terms && !df_out) || !kept_out) return fail(ctx, NS_E_INVAL, "ns_invert_forward: null argument");
+    if ((n_docs && !doc_term_counts) || (n_pairs && !pairs && !dev_pairs) || (n_terms && !df_out) || !kept_out) return fail(ctx, NS_E_INVAL, "ns_invert_forward: null argument");
     if (n_pairs >= (1ull << 32) - kIvTile) return fail(ctx, NS_E_INVAL, "ns_invert_forward: %llu pairs; this build indexes pairs with 32 bits (split the segment)", (unsigned long long)n_pairs);
     if (n_terms == 0xFFFFFFFFu) return fail(ctx, NS_E_INVAL, "ns_invert_forward: n_terms too large");
     *kept_out = 0;
@@ -1575,14 +1578,14 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
     size_t off = 0;
     auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
     const size_t nt1 = (size_t)std::max<uint32_t>(n_terms, 1);
-    const size_t o_pairs = place((size_t)n * 8), o_v0 = place((size_t)n * 8), o_v1 = place(passes > 1 ? (size_t)n * 8 : 1);
+    const size_t o_pairs = place(dev_pairs ? 1 : (size_t)n * 8), o_v0 = place((size_t)n * 8), o_v1 = place(passes > 1 ? (size_t)n * 8 : 1);
     const size_t o_k0 = place((size_t)n * 4), o_k1 = place(passes > 1 ? (size_t)n * 4 : 1);
     const size_t o_df = place(nt1 * 4), o_first = place(nt1 * 4), o_hist = place(m_max * 4), o_sums = place((size_t)scan_blocks_max * 4), o_kept = place(4), o_prefix = place(prefix.size() * 8), o_tdocs = place((size_t)n_tiles * 8);
     const size_t block_bytes = off;
     char* blk = nullptr;
     chk(pool_alloc(ctx, (void**)&blk, block_bytes));
     if (e == hipSuccess) {
-        d_pairs = (uint2*)(blk + o_pairs); d_vals[0] = (uint2*)(blk + o_v0); d_vals[1] = (uint2*)(blk + o_v1);
+        d_pairs = dev_pairs ? const_cast<uint2*>(dev_pairs) : (uint2*)(blk + o_pairs); d_vals[0] = (uint2*)(blk + o_v0); d_vals[1] = (uint2*)(blk + o_v1);
         d_keys[0] = (uint32_t*)(blk + o_k0); d_keys[1] = (uint32_t*)(blk + o_k1);
         d_df = (uint32_t*)(blk + o_df); d_first = (uint32_t*)(blk + o_first); d_hist = (uint32_t*)(blk + o_hist); d_sums = (uint32_t*)(blk + o_sums);
         d_kept = (uint32_t*)(blk + o_kept);
@@ -1593,7 +1596,7 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
     chk(hipEventCreate(&ev1));
     uint2* d_final = nullptr;
     if (e == hipSuccess) {
-        chk(hipMemcpyAsync(d_pairs, pairs, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        if (!dev_pairs) chk(hipMemcpyAsync(d_pairs, pairs, (size_t)n * 8, hipMemcpyHostToDevice, st));
         chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 8, hipMemcpyHostToDevice, st));
         chk(hipMemcpyAsync(d_tile_docs, tile_docs.data(), tile_docs.size() * 4, hipMemcpyHostToDevice, st));
         chk(hipMemsetAsync(d_df, 0, nt1 * 4, st));
@@ -1974,6 +1977,260 @@ extern "C" void ns_forward_destroy(ns_forward* fwd) {
         forward_free_device(fwd);
     }
     delete fwd;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Compaction: the forward indexes of several segments -> one (csrc/ns_compact.hip)
+extern "C" uint32_t ns_compact_doc_cut(void) { return kCpDocCut; }
+
+extern "C" int ns_ctx_use_docsort(ns_ctx* ctx, int on) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_use_docsort: ctx is NULL");
+    ctx->cp_inplace = on != 0;
+    return NS_OK;
+}
+
+extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t n_src, ns_forward** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_forward_merge: ctx is NULL");
+    if (!out) return fail(ctx, NS_E_INVAL, "ns_forward_merge: out is NULL");
+    *out = nullptr;
+    if (n_src && !src) return fail(ctx, NS_E_INVAL, "ns_forward_merge: src is NULL");
+    // ---- the totals, from the counts alone ----
+    uint64_t docs64 = 0, pairs64 = 0, terms64 = 0;
+    for (uint32_t s = 0; s < n_src; s++) {
+        docs64 += src[s].n_docs; terms64 += src[s].n_terms;
+        if (src[s].n_pairs >= (1ull << 32) || (pairs64 += src[s].n_pairs) >= (1ull << 32) - kIvTile)
+            return fail(ctx, NS_E_INVAL, "ns_forward_merge: more than %llu pairs up to source %u; this build indexes pairs with 32 bits (compact fewer segments)", (unsigned long long)((1ull << 32) - kIvTile - 1), s);
+    }
+    if (docs64 >= 0xFFFFFFFFull) return fail(ctx, NS_E_INVAL, "ns_forward_merge: %llu documents; docIds are 32 bits wide (below 2^32 - 1: compact fewer segments)", (unsigned long long)docs64);
+    if (terms64 >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "ns_forward_merge: %llu source terms; the dictionary holds fewer than 2^31 (compact fewer segments)", (unsigned long long)terms64);
+    uint64_t bytes64 = 0;
+    for (uint32_t s = 0; s < n_src; s++) {
+        const ns_forward_src& S = src[s];
+        if ((S.n_docs && (!S.doc_len || !S.counts)) || (S.n_pairs && !S.pairs) || (S.n_terms && !S.term_offsets)) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: null array", s);
+        if (S.n_terms) {
+            if (S.term_offsets[S.n_terms] < S.term_offsets[0]) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term offsets decrease", s);
+            bytes64 += S.term_offsets[S.n_terms] - S.term_offsets[0];
+            if (bytes64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "ns_forward_merge: more than 4 GiB - 64 KiB of term bytes up to source %u; this build addresses them with 32 bits (compact fewer segments)", s);
+        }
+    }
+    const uint32_t n_docs = (uint32_t)docs64, n_pairs = (uint32_t)pairs64, T = (uint32_t)terms64, n = (uint32_t)bytes64;
+    std::vector<uint32_t> term_base((size_t)n_src + 1, 0), pair_base((size_t)n_src + 1, 0), kstart(T), klen(T), prefix((size_t)n_docs + 1, 0);
+    uint64_t total_len = 0;
+    {
+        uint32_t d = 0, k = 0, at = 0;
+        for (uint32_t s = 0; s < n_src; s++) {
+            const ns_forward_src& S = src[s];
+            uint64_t sum = 0;
+            for (uint32_t j = 0; j < S.n_docs; j++, d++) { sum += S.counts[j]; total_len += S.doc_len[j]; prefix[d + 1] = (uint32_t)(pair_base[s] + sum); if (sum > S.n_pairs) break; }
+            if (sum != S.n_pairs) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: the per-document counts do not sum to n_pairs = %llu", s, (unsigned long long)S.n_pairs);
+            for (uint32_t t = 0; t < S.n_terms; t++, k++) {
+                if (S.term_offsets[t + 1] < S.term_offsets[t]) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term offsets decrease at term %u", s, t);
+                kstart[k] = at + (uint32_t)(S.term_offsets[t] - S.term_offsets[0]);
+                klen[k] = (uint32_t)(S.term_offsets[t + 1] - S.term_offsets[t]);
+            }
+            if (S.n_terms && S.term_offsets[S.n_terms] != S.term_offsets[0] && !S.term_bytes) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term_bytes is NULL", s);
+            if (S.n_terms) at += (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]);
+            term_base[s + 1] = term_base[s] + S.n_terms;
+            pair_base[s + 1] = pair_base[s] + (uint32_t)S.n_pairs;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ns_forward* f = new ns_forward();
+    f->ctx = ctx;
+    f->info.struct_size = (uint32_t)sizeof(ns_forward_info);
+    auto publish = [&]() { ctx->fwds.push_back(f); *out = f; return NS_OK; };
+    if (n_docs == 0) return publish();   // no document: an empty result, whatever the term lists hold
+    f->info.n_docs = f->info.kept_docs = n_docs;
+    f->info.n_tokens = f->info.kept_tokens = total_len;
+    f->info.n_pairs = n_pairs;
+    hipStream_t st = ctx->stream;
+    uint64_t hash_mask = ~0ull;
+#ifdef NS_VARIANTS
+    if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) hash_mask = (1ull << b) - 1ull; }
+#endif
+    // the documents by size class: sorted by a wave, by a workgroup in LDS, or by the global radix sort (a document of one
+    // pair is in order as it is)
+    std::vector<uint32_t> l_wave, l_lds, l_big, big_prefix(1, 0);
+    for (uint32_t d = 0; d < n_docs; d++) {
+        const uint32_t c = prefix[d + 1] - prefix[d];
+        if (c < 2) continue;
+        if (ctx->cp_inplace && c <= kCpWaveMax) l_wave.push_back(d);
+        else if (ctx->cp_inplace && c <= kCpDocCut) l_lds.push_back(d);
+        else { l_big.push_back(d); big_prefix.push_back(big_prefix.back() + c); }
+    }
+    const uint32_t n_wave = (uint32_t)l_wave.size(), n_lds = (uint32_t)l_lds.size(), n_bigdocs = (uint32_t)l_big.size(), n_big = big_prefix.back();
+    std::vector<uint32_t> lists;
+    lists.reserve((size_t)n_wave + n_lds + 2 * (size_t)n_bigdocs + 1);
+    lists.insert(lists.end(), l_wave.begin(), l_wave.end());
+    lists.insert(lists.end(), l_lds.begin(), l_lds.end());
+    lists.insert(lists.end(), l_big.begin(), l_big.end());
+    lists.insert(lists.end(), big_prefix.begin(), big_prefix.end());
+
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    char *blkA = nullptr, *blkB = nullptr;
+    size_t bytesA = 0, bytesB = 0, off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    enum { C_TERMS = 0, C_TBYTES = 1, C_LONG = 2, C_DUP = 4, C_BAD = 5 };   // C_DUP / C_BAD: the smallest refused source, ~0 for none
+    uint64_t cap = 1024;
+    while (cap < 2ull * T) cap <<= 1;                                  // T < 2^31: cap <= 2^32, its mask fits 32 bits
+    const uint32_t big_tiles = (n_big + kIvTile - 1) / kIvTile;
+    const size_t scan_max = std::max<size_t>({(size_t)T + 1, (size_t)2048 * big_tiles, (size_t)1});
+
+    // ---- block A: the dictionary stage, sized by the source terms; the per-source bases, the document prefix, the lists ----
+    const size_t T1 = std::max<uint32_t>(T, 1);
+    const size_t o_cnt = place(sizeof(h_cnt)), o_text = place((size_t)n + 16), o_ks = place(T1 * 4), o_kl = place(T1 * 4), o_src = place(T1 * 4), o_kh = place(T1 * 8);
+    const size_t o_sl = place(T1 * 4), o_kr = place(T1 * 4), o_fi = place(T1 * 4), o_tsrc = place(T1 * 4), o_map = place(T1 * 4), o_vals = place(T1 * 8);
+    const size_t o_tab = place((size_t)cap * 4), o_dtab = place((size_t)cap * 8), o_long = place(((size_t)n / kIgLong + 1) * 4), o_sums = place((scan_max / 1024 + 2) * 4);
+    const size_t o_tb = place(term_base.size() * 4), o_pb = place(pair_base.size() * 4), o_prefix = place(prefix.size() * 4), o_lists = place(lists.size() * 4);
+    bytesA = off;
+    chk(pool_alloc(ctx, (void**)&blkA, bytesA));
+    chk(hipEventCreate(&ev0));
+    chk(hipEventCreate(&ev1));
+    chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
+    chk(hipMalloc((void**)&f->d_map, (size_t)n_docs * 4));
+    chk(hipMalloc((void**)&f->d_len, (size_t)n_docs * 4));
+    chk(hipMalloc((void**)&f->d_cnt, (size_t)n_docs * 4));
+    uint32_t n_terms = 0, tbytes = 0;
+    int refused_src = -1;
+    const char* refused_why = "";
+    if (e == hipSuccess) {
+        uint32_t* d_cntv = (uint32_t*)(blkA + o_cnt);
+        uint8_t* d_text = (uint8_t*)(blkA + o_text);
+        uint32_t *d_kstart = (uint32_t*)(blkA + o_ks), *d_klen = (uint32_t*)(blkA + o_kl), *d_ksrc = (uint32_t*)(blkA + o_src);
+        uint64_t* d_khash = (uint64_t*)(blkA + o_kh);
+        uint32_t *d_kslot = (uint32_t*)(blkA + o_sl), *d_krep = (uint32_t*)(blkA + o_kr), *d_fid = (uint32_t*)(blkA + o_fi), *d_tsrc = (uint32_t*)(blkA + o_tsrc);
+        uint32_t* d_newid = (uint32_t*)(blkA + o_map);
+        uint2* d_tvals = (uint2*)(blkA + o_vals);                      // k_ig_termid's {source, new id} per source term: written, not read
+        uint32_t* d_table = (uint32_t*)(blkA + o_tab);
+        unsigned long long* d_dtab = (unsigned long long*)(blkA + o_dtab);
+        uint32_t *d_long = (uint32_t*)(blkA + o_long), *d_sums = (uint32_t*)(blkA + o_sums);
+        uint32_t *d_tb = (uint32_t*)(blkA + o_tb), *d_pb = (uint32_t*)(blkA + o_pb), *d_prefix = (uint32_t*)(blkA + o_prefix), *d_lists = (uint32_t*)(blkA + o_lists);
+        const uint32_t *d_lwave = d_lists, *d_llds = d_lists + n_wave, *d_lbig = d_lists + n_wave + n_lds, *d_bigpre = d_lists + n_wave + n_lds + n_bigdocs;
+        // uploads: term bytes, pairs, counts and doc_len source by source; the host-made arrays
+        {
+            uint32_t at = 0, d = 0;
+            for (uint32_t s = 0; s < n_src; s++) {
+                const ns_forward_src& S = src[s];
+                const uint32_t nb = S.n_terms ? (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]) : 0u;
+                if (nb) chk(hipMemcpyAsync(d_text + at, S.term_bytes + S.term_offsets[0], nb, hipMemcpyHostToDevice, st));
+                if (S.n_pairs) chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                if (S.n_docs) {
+                    chk(hipMemcpyAsync(f->d_len + d, S.doc_len, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
+                    chk(hipMemcpyAsync(f->d_cnt + d, S.counts, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
+                }
+                at += nb; d += S.n_docs;
+            }
+        }
+        std::vector<uint32_t> iota(n_docs);
+        for (uint32_t d = 0; d < n_docs; d++) iota[d] = d;
+        chk(hipMemcpyAsync(f->d_map, iota.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+        if (T) {
+            chk(hipMemcpyAsync(d_kstart, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(d_klen, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+        }
+        chk(hipMemcpyAsync(d_tb, term_base.data(), term_base.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_pb, pair_base.data(), pair_base.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipEventRecord(ev0, st));
+        h_cnt[C_DUP] = h_cnt[C_BAD] = 0xFFFFFFFFu;
+        chk(hipMemcpyAsync(d_cntv, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
+        auto read_counts = [&]() {
+            chk(hipGetLastError());
+            if (e == hipSuccess) chk(hipMemcpyAsync(h_cnt, d_cntv, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+            if (e == hipSuccess) chk(hipStreamSynchronize(st));
+        };
+        const uint32_t gT = (T + 255) / 256;
+        if (e == hipSuccess && T) {
+            chk(hipMemsetAsync(d_table, 0xFF, (size_t)cap * 4, st));
+            chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)cap * 8, st));
+            hipLaunchKernelGGL(k_cp_hash, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, T, d_tb, n_src, hash_mask, d_ksrc, d_khash, d_long, d_cntv + C_LONG);
+            hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
+            hipLaunchKernelGGL(k_ig_insert, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, T, d_table, (uint32_t)(cap - 1), d_kslot);
+            hipLaunchKernelGGL(k_ig_first, dim3(gT), dim3(256), 0, st, d_table, d_kslot, T, d_krep, d_fid);
+            ig_scan(st, d_fid, T, d_sums, d_cntv + C_TERMS);
+            read_counts();
+            n_terms = h_cnt[C_TERMS];
+        }
+        f->info.n_terms = n_terms;
+        if (e == hipSuccess) chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+        if (e == hipSuccess) {
+            chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
+            if (T) {
+                hipLaunchKernelGGL(k_ig_termid, dim3(gT), dim3(256), 0, st, d_krep, d_fid, d_ksrc, d_kstart, d_klen, T, d_newid, d_tvals, f->d_toff, d_tsrc);
+                ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
+                hipLaunchKernelGGL(k_cp_dup, dim3(gT), dim3(256), 0, st, d_newid, d_ksrc, T, d_dtab, (uint32_t)(cap - 1), d_cntv + C_DUP);
+            }
+            if (n_pairs) hipLaunchKernelGGL(k_cp_remap, dim3((n_pairs + 255) / 256), dim3(256), 0, st, f->d_pairs, n_pairs, d_pb, d_tb, n_src, d_newid, d_cntv + C_BAD);
+            read_counts();
+            tbytes = h_cnt[C_TBYTES];
+            f->info.term_bytes = tbytes;
+            if (e == hipSuccess && h_cnt[C_DUP] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_DUP]; refused_why = "one byte string occurs twice in its term list"; }
+            else if (e == hipSuccess && h_cnt[C_BAD] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_BAD]; refused_why = "a pair's termId is not below the source's n_terms"; }
+        }
+        if (e == hipSuccess && refused_src < 0) chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
+        if (e == hipSuccess && refused_src < 0) {
+            if (n_terms) hipLaunchKernelGGL(k_ig_term_bytes, dim3((n_terms + 3) / 4), dim3(256), 0, st, d_text, d_tsrc, f->d_toff, n_terms, f->d_terms);
+            // ---- the order inside each document ----
+            if (n_wave) hipLaunchKernelGGL(k_cp_docsort_wave, dim3((n_wave + 3) / 4), dim3(256), 0, st, f->d_pairs, d_prefix, d_lwave, n_wave);
+            if (n_lds) hipLaunchKernelGGL(k_cp_docsort_lds, dim3(n_lds), dim3(256), 0, st, f->d_pairs, d_prefix, d_llds);
+            if (n_big) {
+                off = 0;
+                const size_t o_k0 = place((size_t)n_big * 4), o_k1 = place((size_t)n_big * 4), o_v0 = place((size_t)n_big * 8), o_v1 = place((size_t)n_big * 8);
+                const size_t o_hist = place((size_t)2048 * big_tiles * 4);
+                bytesB = off;
+                chk(pool_alloc(ctx, (void**)&blkB, bytesB));
+                if (e == hipSuccess) {
+                    uint32_t* d_keys[2] = {(uint32_t*)(blkB + o_k0), (uint32_t*)(blkB + o_k1)};
+                    uint2* d_vals[2] = {(uint2*)(blkB + o_v0), (uint2*)(blkB + o_v1)};
+                    uint32_t* d_hist = (uint32_t*)(blkB + o_hist);
+                    const uint32_t gB = (n_big + 255) / 256;
+                    int cur = 0;
+                    hipLaunchKernelGGL(k_cp_big_gather, dim3(gB), dim3(256), 0, st, f->d_pairs, d_prefix, d_lbig, d_bigpre, n_bigdocs, n_big, d_keys[0], d_vals[0]);
+                    ig_sort(st, n_big, n_terms, d_keys, d_vals, &cur, d_hist, d_sums);
+                    hipLaunchKernelGGL(k_cp_big_rekey, dim3(gB), dim3(256), 0, st, d_keys[cur], d_vals[cur], n_big, d_keys[cur ^ 1], d_vals[cur ^ 1]);
+                    cur ^= 1;
+                    ig_sort(st, n_big, n_bigdocs, d_keys, d_vals, &cur, d_hist, d_sums);
+                    hipLaunchKernelGGL(k_cp_big_scatter, dim3(gB), dim3(256), 0, st, d_keys[cur], d_vals[cur], n_big, d_prefix, d_lbig, d_bigpre, f->d_pairs);
+                }
+            }
+            chk(hipGetLastError());
+        }
+        if (e == hipSuccess) chk(hipEventRecord(ev1, st));
+        if (e == hipSuccess) chk(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) f->info.device_ms = ms;
+    }
+    (void)hipStreamSynchronize(st);   // nothing in flight uses the blocks any more
+    if (blkB) pool_free(ctx, blkB, bytesB);
+    if (blkA) pool_free(ctx, blkA, bytesA);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    f->info.device_bytes = (uint64_t)bytesA + bytesB + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
+    if (e != hipSuccess || refused_src >= 0) {
+        forward_free_device(f);
+        delete f;
+        (void)hipGetLastError();
+        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %d: %s", refused_src, refused_why);
+        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_forward_merge: %s", hipGetErrorString(e));
+    }
+    return publish();
+}
+
+extern "C" int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postings_out, uint64_t* kept_out, float* device_ms_out) {
+    if (!fwd) return fail(nullptr, NS_E_INVAL, "ns_forward_invert: handle is NULL");
+    ns_ctx* ctx = fwd->ctx;
+    if (!ctx) return fail(nullptr, NS_E_STATE, "ns_forward_invert: the handle's ctx has been destroyed");
+    const ns_forward_info& in = fwd->info;
+    if (!kept_out || (in.n_terms && !df_out) || (in.n_pairs && !postings_out)) return fail(ctx, NS_E_INVAL, "ns_forward_invert: null argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> counts(in.kept_docs);                       // the host keeps the prefix sums (the tiles' first and last documents)
+    if (in.kept_docs) HIPCHK(ctx, hipMemcpy(counts.data(), fwd->d_cnt, (size_t)in.kept_docs * 4, hipMemcpyDeviceToHost));
+    return invert_run(ctx, counts.data(), in.kept_docs, nullptr, in.n_pairs, in.n_terms, df_out, postings_out, kept_out, device_ms_out, nullptr,
+                      in.n_pairs ? fwd->d_pairs : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

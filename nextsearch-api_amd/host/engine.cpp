@@ -274,6 +274,69 @@ bool Engine::add_documents(const std::vector<nsx::DocInput>& docs, nsx::IndexSta
     return ok;
 }
 
+bool Engine::compact(size_t first, size_t count, bool remove_sources, nsx::CompactStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (stats) *stats = nsx::CompactStats{};
+    if (device_ < 0) { err_ = "compact: host-only engine (compaction runs on the device; there is no CPU path)"; return false; }
+    const nsx::fs::path manifest = index_dir / "manifest.bin", segroot = index_dir / "segments";
+    std::error_code ec;
+    std::vector<std::string> segs = nsx::load_manifest(manifest);
+    first = std::min(first, segs.size());
+    count = std::min(count, segs.size() - first);
+    if (count < 2) return true;                                                     // nothing to merge
+    std::vector<nsx::fs::path> sources;
+    for (size_t i = first; i < first + count; i++) sources.push_back(segroot / segs[i]);
+    std::vector<nsx::SourceSegment> loaded;
+    if (!nsx::load_sources(sources, loaded, err_)) { err_ = "compact: " + err_; return false; }
+    ns_ctx* ctx = ctx_;
+    ns_ctx* own = nullptr;
+    if (!ctx) {
+        if (ns_ctx_create(device_, &own) != NS_OK) { err_ = std::string("ns_ctx_create: ") + ns_last_error(nullptr); return false; }
+        ctx = own;
+    }
+    uint32_t id = (uint32_t)segs.size();                                            // the next free name, as add_documents finds it
+    while (nsx::fs::exists(segroot / nsx::seg_name(id), ec) || std::find(segs.begin(), segs.end(), nsx::seg_name(id)) != segs.end()) id++;
+    const std::string name = nsx::seg_name(id);
+    const nsx::fs::path segdir = segroot / name;
+    nsx::CompactStats st;
+    const auto t0 = std::chrono::steady_clock::now();
+    bool ok = nsx::merge_loaded(ctx, loaded, segdir, st, err_);
+    if (!ok) err_ = "compact: " + err_;
+    loaded.clear();
+    if (own) ns_ctx_destroy(own);
+    std::vector<std::string> fresh(segs.begin(), segs.begin() + first);
+    fresh.push_back(name);
+    fresh.insert(fresh.end(), segs.begin() + first + count, segs.end());
+    if (ok) {
+        nsx::FileBytes fb;
+        const bool had_manifest = nsx::fs::exists(manifest, ec) && fb.load(manifest);
+        const std::vector<uint8_t> old_manifest = had_manifest ? fb.bytes() : std::vector<uint8_t>();
+        try {
+            nsx::save_manifest(manifest, fresh);
+        } catch (const std::exception& ex) { err_ = ex.what(); ok = false; }
+        if (ok && !reload()) ok = false;                                            // (err_ is reload's)
+        if (!ok) {   // the manifest as it was
+            const std::string keep = err_;
+            if (had_manifest) { try { nsx::FileOut out(manifest); out.raw(old_manifest.data(), old_manifest.size()); } catch (...) {} }
+            else nsx::fs::remove(manifest, ec);
+            err_ = keep;
+        }
+    }
+    if (!ok) { nsx::fs::remove_all(segdir, ec); return false; }
+    if (remove_sources) {
+        for (size_t i = first; i < first + count; i++) {
+            if (std::find(fresh.begin(), fresh.end(), segs[i]) != fresh.end()) continue;   // still named by the manifest
+            std::error_code rec;
+            nsx::fs::remove_all(segroot / segs[i], rec);
+            if (rec) err_ += (err_.empty() ? "compact: could not remove " : "; ") + (segroot / segs[i]).string() + ": " + rec.message();
+        }
+    }
+    st.total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = st;
+    return true;
+}
+
 const std::vector<uint8_t>* Engine::raw_postings(uint32_t seg) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (seg >= segments.size()) return nullptr;

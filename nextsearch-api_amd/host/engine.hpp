@@ -27,6 +27,7 @@
 
 #include "../../include/nextsearch_hip.h"
 #include "forward_index.hpp"
+#include "compact.hpp"
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
@@ -100,6 +101,13 @@ public:
     // manifest keeps its bytes and the new segment directory is removed; if no document has a token left after the
     // length and stop-word rules that is a failure and nothing is written.  stats (may be null): the indexing step's.
     bool add_documents(const std::vector<nsx::DocInput>& docs, nsx::IndexStats* stats = nullptr);
+    // Compaction (host/compact.hpp): the segments at manifest positions [first, first + count) (clamped)
+    // become ONE new segment, the next free seg_%06u, which takes the range's place in the manifest; the engine reloads.
+    // Fewer than two segments in the range: success, nothing touched.  All or nothing like add_documents: on any failure the
+    // manifest keeps its bytes, the new directory is removed, no source is touched and the engine keeps answering from the
+    // index it had.  The source directories are removed only after the reload succeeded and only with remove_sources; a
+    // failure to remove one is reported in last_error() while the call returns true.  Needs a device (device < 0: fails).
+    bool compact(size_t first = 0, size_t count = SIZE_MAX, bool remove_sources = true, nsx::CompactStats* stats = nullptr);
     // Optional: per-posting term scores for every list of every lexicon, built on the device
     // (ns_segment_build_impacts); searches then read {docId, score} instead of {docId, tf} + norm.  Same results.
     bool build_impacts();

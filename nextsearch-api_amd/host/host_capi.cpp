@@ -3,6 +3,7 @@
 // corrupt count, ...) and reports failure through its return value and nsh_engine_error().
 #include "invert.hpp"
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -370,6 +371,49 @@ extern "C" int nsh_engine_add_documents(nsh_engine* e, const char* bytes, const 
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
     return 0;
 } NSH_CATCH(e, "nsh_engine_add_documents", -1)
+}
+
+// Compaction (host/compact.hpp)
+static void put_cstats(nsh_compact_stats* out, const nsx::CompactStats& st) {
+    if (!out || out->struct_size < 4) return;
+    nsh_compact_stats t{};
+    t.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(t));
+    t.sources = st.sources; t.n_docs = st.n_docs; t.n_terms = st.n_terms;
+    t.terms_in = st.terms_in; t.pairs = st.pairs; t.device_bytes = st.device_bytes;
+    t.merge_ms = st.merge_ms; t.invert_ms = st.invert_ms; t.call_s = st.call_s; t.total_s = st.total_s;
+    std::memcpy(out, &t, t.struct_size);
+}
+static thread_local std::string g_compact_err;
+extern "C" const char* nsh_compact_error(void) { return g_compact_err.c_str(); }
+extern "C" int nsh_merge_segments(const char* const* source_dirs, uint32_t n_sources, const char* out_dir, int device, nsh_compact_stats* stats) { try {
+    if (!out_dir || (n_sources && !source_dirs)) { g_compact_err = "nsh_merge_segments: null argument"; return -1; }
+    std::vector<nsx::fs::path> dirs;
+    for (uint32_t i = 0; i < n_sources; i++) {
+        if (!source_dirs[i]) { g_compact_err = "nsh_merge_segments: null argument"; return -1; }
+        dirs.emplace_back(source_dirs[i]);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<nsx::SourceSegment> loaded;
+    if (!nsx::load_sources(dirs, loaded, g_compact_err)) return -1;            // before the device is touched
+    ns_ctx* ctx = nullptr;
+    if (ns_ctx_create(device, &ctx) != NS_OK) { g_compact_err = std::string("ns_ctx_create: ") + ns_last_error(nullptr); return -1; }
+    nsx::CompactStats st;
+    const bool ok = nsx::merge_loaded(ctx, loaded, out_dir, st, g_compact_err);
+    ns_ctx_destroy(ctx);
+    st.total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    put_cstats(stats, st);
+    return ok ? 0 : -1;
+} catch (const std::exception& ex) { g_compact_err = std::string("nsh_merge_segments: ") + ex.what(); return -1; }
+  catch (...) { g_compact_err = "nsh_merge_segments: unknown exception"; return -1; }
+}
+extern "C" int nsh_engine_compact(nsh_engine* e, uint64_t first, uint64_t count, int remove_sources, nsh_compact_stats* stats) { try {
+    if (!e) return -1;
+    nsx::CompactStats st;
+    const bool ok = e->eng.compact((size_t)first, (size_t)count, remove_sources != 0, &st);
+    put_cstats(stats, st);
+    nsh_set_err(e, e->eng.last_error());                                       // (success: empty, or the sources that could not be removed)
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_compact", -1)
 }
 
 // Semantic expansion (src/api_engine.cpp:409-417): rows/dim of the loaded embedding table (0/0: none), and the

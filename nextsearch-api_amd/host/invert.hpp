@@ -21,6 +21,37 @@ struct InvertStats {
     double total_s = 0.0;         // files in -> files out
 };
 
+// barrels.bin and the 64 lexicon_bNNN.bin / inverted_bNNN.bin files (src/lexicon.cpp:84-146) from the inversion's output:
+// df per termId, the posting lists in termId order back to back; term_at(t) = the bytes of term t.  Throws on a file error.
+template <class TermAt>
+inline void write_barrels(const fs::path& seg, uint32_t tcount, const std::vector<uint32_t>& df, const std::vector<uint8_t>& postings, TermAt term_at) {
+    // 64 of them, ceil(tcount / 64) consecutive termIds each
+    const uint32_t barrel_count = 64;
+    uint32_t tpb = (tcount + barrel_count - 1) / barrel_count;
+    if (tpb == 0) tpb = 1;
+    { FileOut m(seg / "barrels.bin"); m.u32(barrel_count); m.u32(tpb); }
+    uint64_t src = 0;   // byte position in `postings` (lists are in termId order == barrel order)
+    uint32_t tid = 0;
+    for (uint32_t b = 0; b < barrel_count; b++) {
+        FileOut inv(inv_barrel_path(seg, b)), lex(lex_barrel_path(seg, b));
+        lex.u32(0);
+        uint32_t in_barrel = 0;
+        uint64_t off = 0;
+        const uint64_t first = src;
+        // barrel_for_term: tid / tpb, the last barrel takes the rest (include/barrels.hpp:43-48)
+        for (; tid < tcount && (b + 1 == barrel_count || tid / tpb == b); tid++) {
+            const uint32_t n = df[tid];
+            if (!n) continue;                                    // :108
+            in_barrel++;
+            lex.str(term_at(tid)); lex.u32(tid); lex.u32(n); lex.u64(off); lex.u32(n);   // :117-121
+            off += (uint64_t)n * 8;
+            src += (uint64_t)n * 8;
+        }
+        inv.raw(postings.data() + first, (size_t)(src - first));
+        lex.patch_u32_at0(in_barrel);                              // :133-146
+    }
+}
+
 inline bool invert_segment(ns_ctx* ctx, const fs::path& seg, InvertStats& st, std::string& err) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
@@ -57,32 +88,8 @@ inline bool invert_segment(ns_ctx* ctx, const fs::path& seg, InvertStats& st, st
     st.call_s = std::chrono::duration<double>(clk::now() - t1).count();
     if (rc != NS_OK) { err = std::string("ns_invert_forward: ") + ns_last_error(ctx); return false; }
 
-    // barrels (:84-146): 64 of them, ceil(tcount / 64) consecutive termIds each
-    const uint32_t barrel_count = 64;
-    uint32_t tpb = (tcount + barrel_count - 1) / barrel_count;
-    if (tpb == 0) tpb = 1;
     try {
-        { FileOut m(seg / "barrels.bin"); m.u32(barrel_count); m.u32(tpb); }
-        uint64_t src = 0;   // byte position in `postings` (lists are in termId order == barrel order)
-        uint32_t tid = 0;
-        for (uint32_t b = 0; b < barrel_count; b++) {
-            FileOut inv(inv_barrel_path(seg, b)), lex(lex_barrel_path(seg, b));
-            lex.u32(0);
-            uint32_t in_barrel = 0;
-            uint64_t off = 0;
-            const uint64_t first = src;
-            // barrel_for_term: tid / tpb, the last barrel takes the rest (include/barrels.hpp:43-48)
-            for (; tid < tcount && (b + 1 == barrel_count || tid / tpb == b); tid++) {
-                const uint32_t n = df[tid];
-                if (!n) continue;                                    // :108
-                in_barrel++;
-                lex.str(terms[tid]); lex.u32(tid); lex.u32(n); lex.u64(off); lex.u32(n);   // :117-121
-                off += (uint64_t)n * 8;
-                src += (uint64_t)n * 8;
-            }
-            inv.raw(postings.data() + first, (size_t)(src - first));
-            lex.patch_u32_at0(in_barrel);                              // :133-146
-        }
+        write_barrels(seg, tcount, df, postings, [&](uint32_t t) -> const std::string& { return terms[t]; });
     } catch (const std::exception& ex) { err = ex.what(); return false; }
     st.total_s = std::chrono::duration<double>(clk::now() - t0).count();
     return true;

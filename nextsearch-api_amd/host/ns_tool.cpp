@@ -5,6 +5,8 @@
 //        documents_file: u32 n, then n x {string cord_uid, string title, string json_relpath, string text} with
 //        string = u32 length + bytes (include/indexio.hpp:18-29).  Runs the reference's two offline steps on the device:
 //        `forwardindex` from the extracted text onwards (forward_index.hpp) and `lexicon` (invert.hpp).  One JSON line.
+//   ns_tool compact <index_dir> [first count]             (needs an MI355X)
+//        Engine::compact: the manifest's segments [first, first + count) (default: all) become one (compact.hpp).  One JSON line.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -47,6 +49,19 @@ int main(int argc, char** argv) {
         std::string q;
         for (int i = 4; i < argc; i++) { if (i > 4) q.push_back(' '); q += argv[i]; }
         std::printf("%s\n", eng.search(q, k).c_str());
+        return 0;
+    }
+    if (argc >= 3 && std::strcmp(argv[1], "compact") == 0) {
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        const size_t first = argc > 3 ? (size_t)std::strtoull(argv[3], nullptr, 10) : 0;
+        const size_t count = argc > 4 ? (size_t)std::strtoull(argv[4], nullptr, 10) : SIZE_MAX;
+        nsx::CompactStats st;
+        if (!eng.compact(first, count, true, &st)) { std::fprintf(stderr, "compact failed: %s\n", eng.last_error().c_str()); return 1; }
+        if (!eng.last_error().empty()) std::fprintf(stderr, "%s\n", eng.last_error().c_str());
+        std::printf("{\"sources\": %u, \"docs\": %u, \"terms_in\": %llu, \"terms\": %u, \"pairs\": %llu, \"merge_ms\": %.3f, \"invert_ms\": %.3f, \"call_s\": %.4f, \"total_s\": %.4f, \"segments\": %zu}\n",
+                    st.sources, st.n_docs, (unsigned long long)st.terms_in, st.n_terms, (unsigned long long)st.pairs, st.merge_ms, st.invert_ms, st.call_s, st.total_s, eng.segments.size());
         return 0;
     }
     if (argc >= 4 && std::strcmp(argv[1], "index") == 0) {

@@ -63,6 +63,7 @@ HIP_SYMBOLS = [
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
+    "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort",
 ]
 HOST_SYMBOLS = [
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -74,6 +75,7 @@ HOST_SYMBOLS = [
     "nsh_engine_semantic_info", "nsh_engine_expand", "nsh_engine_semantic_row", "nsh_engine_set_cache", "nsh_engine_cache_size",
     "nsh_engine_suggest_json", "nsh_engine_suggest_batch", "nsh_engine_suggest_table", "nsh_suggest_split", "nsh_suggest_clamp_limit",
     "nsh_index_documents", "nsh_index_error", "nsh_engine_open_noload", "nsh_engine_add_documents",
+    "nsh_merge_segments", "nsh_compact_error", "nsh_engine_compact",
 ]
 
 class NsForwardInfo(C.Structure):   # include/nextsearch_hip.h ns_forward_info
@@ -86,6 +88,20 @@ class NshIndexStats(C.Structure):   # include/nextsearch_host.h nsh_index_stats
     _fields_ = [("struct_size", C.c_uint32), ("n_docs_in", C.c_uint32), ("n_docs", C.c_uint32), ("n_terms", C.c_uint32),
                 ("text_bytes", C.c_uint64), ("tokens", C.c_uint64), ("kept_tokens", C.c_uint64), ("pairs", C.c_uint64),
                 ("device_bytes", C.c_uint64), ("avgdl", C.c_float), ("device_ms", C.c_float), ("call_s", C.c_double), ("total_s", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class NsForwardSrc(C.Structure):   # include/nextsearch_hip.h ns_forward_src
+    _fields_ = [("n_docs", C.c_uint32), ("doc_len", C.c_void_p), ("counts", C.c_void_p), ("n_pairs", C.c_uint64), ("pairs", C.c_void_p),
+                ("n_terms", C.c_uint32), ("term_bytes", C.c_void_p), ("term_offsets", C.c_void_p)]
+
+
+class NshCompactStats(C.Structure):   # include/nextsearch_host.h nsh_compact_stats
+    _fields_ = [("struct_size", C.c_uint32), ("sources", C.c_uint32), ("n_docs", C.c_uint32), ("n_terms", C.c_uint32),
+                ("terms_in", C.c_uint64), ("pairs", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("merge_ms", C.c_float), ("invert_ms", C.c_float), ("call_s", C.c_double), ("total_s", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
@@ -155,6 +171,11 @@ def hip_lib():
         L.ns_forward_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.ns_forward_destroy.argtypes = [vp]
         L.ns_forward_destroy.restype = None
+        L.ns_forward_merge.argtypes = [vp, vp, u32, C.POINTER(vp)]
+        L.ns_forward_invert.argtypes = [vp, vp, vp, C.POINTER(u64), vp]
+        L.ns_compact_doc_cut.argtypes = []
+        L.ns_compact_doc_cut.restype = u32
+        L.ns_ctx_use_docsort.argtypes = [vp, i32]
         _hip = L
     return _hip
 
@@ -212,6 +233,9 @@ def host_lib():
         L.nsh_index_error.restype = C.c_char_p
         L.nsh_engine_open_noload.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_add_documents.argtypes = [vp, vp, vp, u32, C.POINTER(NshIndexStats)]
+        L.nsh_merge_segments.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, i32, C.POINTER(NshCompactStats)]
+        L.nsh_compact_error.restype = C.c_char_p
+        L.nsh_engine_compact.argtypes = [vp, u64, u64, i32, C.POINTER(NshCompactStats)]
         L.nsh_engine_set_cache.argtypes = [vp, i32]
         L.nsh_engine_set_cache.restype = None
         L.nsh_engine_cache_size.argtypes = [vp]
@@ -367,6 +391,19 @@ class Engine:
             _LIVE_BATCHES.pop(_ctx_key(old_ctx), None)
         if rc != 0:
             raise RuntimeError(f"Engine.add_documents failed: {self.error()}")
+        return st.as_dict()
+
+    def compact(self, first=0, count=None, remove_sources=True):
+        """Engine::compact: the segments at manifest positions [first, first + count) (count None: to the end) become one
+        new segment in the range's place, served after the call.  Returns the stats; self.error() afterwards names a
+        source directory that could not be removed."""
+        st = NshCompactStats(struct_size=C.sizeof(NshCompactStats))
+        old_ctx = self.ctx
+        rc = self._L.nsh_engine_compact(self.h, int(first), 0xFFFFFFFFFFFFFFFF if count is None else int(count), 1 if remove_sources else 0, C.byref(st))
+        if _ctx_key(self.ctx) != _ctx_key(old_ctx):
+            _LIVE_BATCHES.pop(_ctx_key(old_ctx), None)
+        if rc != 0:
+            raise RuntimeError(f"Engine.compact failed: {self.error()}")
         return st.as_dict()
 
     def close(self):
@@ -675,6 +712,73 @@ def index_documents(seg_dir, docs, device=0):
     if rc != 0:
         raise RuntimeError(f"index_documents failed: {host_lib().nsh_index_error().decode()}")
     return st.as_dict()
+
+
+def merge_segments(sources, out_dir, device=0):
+    """nsx::merge_segments on a context of its own: the segment directories `sources` -> one complete segment in out_dir."""
+    arr = (C.c_char_p * len(sources))(*[str(p).encode() for p in sources])
+    st = NshCompactStats(struct_size=C.sizeof(NshCompactStats))
+    rc = host_lib().nsh_merge_segments(arr, len(sources), str(out_dir).encode(), device, C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"merge_segments failed: {host_lib().nsh_compact_error().decode()}")
+    return st.as_dict()
+
+
+def _fetch_forward(L, ctx, h):
+    info = NsForwardInfo(struct_size=C.sizeof(NsForwardInfo))
+    assert L.ns_forward_get_info(h, C.byref(info)) == NS_OK
+    kept = np.zeros(info.kept_docs, dtype=np.uint32)
+    dl = np.zeros(info.kept_docs, dtype=np.uint32)
+    cnt = np.zeros(info.kept_docs, dtype=np.uint32)
+    pairs = np.zeros((info.n_pairs, 2), dtype=np.uint32)
+    tb = np.zeros(max(1, info.term_bytes), dtype=np.uint8)
+    to = np.zeros(info.n_terms + 1, dtype=np.uint64)
+    rc = L.ns_forward_fetch(h, kept.ctypes.data, dl.ctypes.data, cnt.ctypes.data, pairs.ctypes.data, tb.ctypes.data, to.ctypes.data)
+    if rc != NS_OK:
+        raise RuntimeError(f"ns_forward_fetch: {rc}: {L.ns_last_error(ctx).decode()}")
+    raw = tb.tobytes()
+    terms = [raw[int(to[i]):int(to[i + 1])] for i in range(info.n_terms)]
+    return {"kept_docs": kept, "doc_len": dl, "counts": cnt, "pairs": pairs, "terms": terms,
+            "info": {k: getattr(info, k) for k, _ in info._fields_}}
+
+
+def forward_sources(parts):
+    """parts: dicts in forward_build's form (doc_len, counts, pairs[n, 2], terms) -> (NsForwardSrc array, keep-alive list)"""
+    arr = (NsForwardSrc * max(1, len(parts)))()
+    keep = []
+    for i, p in enumerate(parts):
+        dl = np.ascontiguousarray(p["doc_len"], dtype=np.uint32)
+        cnt = np.ascontiguousarray(p["counts"], dtype=np.uint32)
+        pairs = np.ascontiguousarray(p["pairs"], dtype=np.uint32).reshape(-1, 2)
+        tb, to = _flat_bytes(p["terms"])
+        tbytes = np.frombuffer(tb + b"\0", dtype=np.uint8)
+        keep.append((dl, cnt, pairs, tbytes, to))
+        arr[i] = NsForwardSrc(len(dl), dl.ctypes.data, cnt.ctypes.data, len(pairs), pairs.ctypes.data, len(p["terms"]), tbytes.ctypes.data, to.ctypes.data)
+    return arr, keep
+
+
+def forward_merge(ctx, parts, invert=False):
+    """Raw ns_forward_merge + fetch (+ ns_forward_invert: adds df, postings[kept, 2], invert_ms) over parts in
+    forward_build's form; raises RuntimeError with the library's message when the merge is refused."""
+    L = hip_lib()
+    arr, keep = forward_sources(parts)
+    h = C.c_void_p()
+    rc = L.ns_forward_merge(ctx, arr, len(parts), C.byref(h))
+    if rc != NS_OK:
+        raise RuntimeError(f"ns_forward_merge: {rc}: {L.ns_last_error(ctx).decode()}")
+    try:
+        out = _fetch_forward(L, ctx, h)
+        if invert:
+            df = np.zeros(out["info"]["n_terms"], dtype=np.uint32)
+            post = np.zeros((out["info"]["n_pairs"], 2), dtype=np.uint32)
+            kept, ms = C.c_uint64(), C.c_float()
+            rc = L.ns_forward_invert(h, df.ctypes.data, post.ctypes.data, C.byref(kept), C.byref(ms))
+            if rc != NS_OK:
+                raise RuntimeError(f"ns_forward_invert: {rc}: {L.ns_last_error(ctx).decode()}")
+            out.update(df=df, postings=post[:kept.value], invert_ms=ms.value)
+        return out
+    finally:
+        L.ns_forward_destroy(h)
 
 
 def forward_build(ctx, texts):
