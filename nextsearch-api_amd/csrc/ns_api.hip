@@ -2562,9 +2562,9 @@ extern "C" int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes
 }
 
 #ifdef NS_COUNT
-// Diagnostic build only: the driver-stream body's event counters (ns_driver_kernel.hip), optionally reset.
+// Counting build only: the driver-stream body's event counters (ns_driver_kernel.hip; 32 values), optionally reset.
 extern "C" int ns_debug_counters(unsigned long long* out, int reset) {
-    unsigned long long h[20];
+    unsigned long long h[ns::kNsCnt];
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_cnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
@@ -2577,6 +2577,24 @@ extern "C" int ns_debug_tile_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_tcnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_tcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the merge body's counters (ns_merge_kernel.hip): 16 values
+extern "C" int ns_debug_merge_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsMcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_mcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_mcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the candidate buffer's shrinks over all wave bodies (ns_wave_kernel.hip WaveTopK): 4 values
+extern "C" int ns_debug_topk_counters(unsigned long long* out, int reset) {
+    unsigned long long h[4];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_kcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_kcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 #endif

@@ -31,8 +31,14 @@ namespace ns {
 
 #ifdef NS_COUNT
 // Diagnostic build only (make -C nextsearch-api_amd count): event counts of the driver-stream body, summed over all
-// items of all launches since the last reset; read through ns_debug_counters (tools/dbg/count_run.py).
-__device__ unsigned long long g_ns_cnt[20];
+// items of all launches since the last reset; read through ns_debug_counters (tests/test_body_shapes_gpu.py asserts which
+// of the body's rare paths its inputs reached; tools/dbg/count_run.py prints them).  0 .. 18: see count_run.py; the table's
+// rare paths: 20 pass-A lanes whose bucket is full (pos >= 4), 21 pass-A chunks that start in the bucket the previous chunk
+// ended in (carry), 22 claim-loop lanes that move to the next bucket, 23 ... of which wrap to bucket 0, 24 claim-loop lanes
+// that found their doc's owner in the table, 25 super-batches without a primary term (largest window < 8), 26 super-batches
+// that find a posting's term by binary search (T > 8), 27 super-batches whose span was clamped.
+constexpr int kNsCnt = 32;
+__device__ unsigned long long g_ns_cnt[kNsCnt];
 #define NS_CNT(i, v) cnt_[(i)] += (unsigned long long)(v)
 #else
 #define NS_CNT(i, v)
@@ -200,7 +206,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
     if ((uint32_t)lane == dl) { cur = end; }   // the driver is streamed through d_cur, not through its lane
 
 #ifdef NS_COUNT
-    unsigned long long cnt_[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt_[kNsCnt] = {};
     cnt_[16] = __builtin_readcyclecounter() - cyc_t0_; cnt_[17] = 0;
     NS_CNT(0, 1);
     NS_CNT(10, T);
@@ -242,6 +248,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         const uint32_t span_hi = (last_doc - lo > MAXSPAN) ? (lo + MAXSPAN) : last_doc;
         const bool span_clamped = hi > span_hi && span_hi != last_doc;
         hi = min(hi, span_hi);
+        NS_CNT(27, span_clamped ? 1 : 0);
         // the bucket function of this super-batch (see NS_BUCKET): bm = floor(NB * 2^16 / (hi - lo + 1)), exact
         uint32_t bm;
         {
@@ -265,6 +272,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
             if ((uint32_t)lane < T) reinterpret_cast<uint2*>(tab + lane)[1] = make_uint2(cur - (incl - w), cur);
             if (T > 8 && (uint32_t)lane < T) aux[lane] = incl;
             wave_sync();
+            NS_CNT(26, T > 8 ? 1 : 0);
             if (T <= 8) {
                 for (uint32_t t = 0; t + 1 < T; t++) {
                     const uint32_t sp = rdlane(incl, t);
@@ -382,6 +390,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
             {
                 const uint32_t wmax = wave_max_dpp(w);
                 if (wmax >= 8u) pterm = (uint32_t)__builtin_ctzll(wballot(w == wmax));
+                NS_CNT(25, wmax < 8u ? 1 : 0);
             }
             if (pterm != 0xFFFFFFFFu) {
                 uint32_t carry_b = 0xFFFFFFFFu, carry_n = 0u;   // the bucket the term's previous chunk ended in, and its fill
@@ -392,6 +401,9 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                     const uint64_t pm = wballot(isp);
                     if ((uint32_t)(j * 64) < total && pm != 0ull && sorted_ok) {   // uniform
                         const uint32_t bkt = NS_BUCKET(fdoc[j]);
+#ifdef NS_COUNT
+                        const uint32_t carry_b_in_ = carry_b;   // the bucket the previous chunk ended in, before this chunk replaces it
+#endif
                         const uint32_t bprev = (uint32_t)__builtin_amdgcn_ds_bpermute((lane - 1) << 2, (int)bkt);
                         const bool prevp = __builtin_amdgcn_inverse_ballot_w64(pm << 1);
                         // sorted docIds give non-decreasing buckets; a list that is not sorted keeps to the claim loop
@@ -416,6 +428,8 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                             carry_b = rdlane(bkt, last);
                             carry_n = rdlane(pos, last) + 1u;
                             NS_CNT(15, (uint32_t)__popcll(wballot(isp && pos < 4u)));   // entries placed without a claim
+                            NS_CNT(20, (uint32_t)__popcll(wballot(isp && pos >= 4u)));
+                            NS_CNT(21, (wballot(isp && bkt == carry_b_in_ && (uint32_t)lane == hl) != 0ull) ? 1 : 0);
                         }
                     }
                 }
@@ -441,6 +455,9 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                     if (wballot(pending) == 0ull) break;
                     NS_CNT(6, 1);               // claim iterations
                     if (wballot(scan) != 0ull) {
+#ifdef NS_COUNT
+                        bool owner_found_ = false;
+#endif
                         if (scan) {
                             const uint4 q = ent4[b];
                             // entry ^ mine is below 256 exactly for the entry of the same docId (at most one), and then it is
@@ -448,8 +465,12 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                             const uint32_t tmin = min(min(q.x ^ mine, q.y ^ mine), min(q.z ^ mine, q.w ^ mine));
                             pos = (q.x >> 31) + (q.y >> 31) + (q.z >> 31) + (q.w >> 31);   // entries fill a bucket in order
                             if (tmin < 256u) { own = tmin ^ me; pending = false; }
+#ifdef NS_COUNT
+                            owner_found_ = tmin < 256u;
+#endif
                             scan = false;
                         }
+                        NS_CNT(24, (uint32_t)__popcll(wballot(owner_found_)));
                     }
                     // Every lane that stores into a bucket in this step saw the same fill level, so they all
                     // target the same position and exactly one entry lands: the losers' next free position
@@ -465,6 +486,8 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
                         b = (b + 1) & (uint32_t)(NB - 1);   // full bucket without a match
                         scan = true;
                     }
+                    NS_CNT(22, (uint32_t)__popcll(wballot(pending && scan)));
+                    NS_CNT(23, (uint32_t)__popcll(wballot(pending && scan && b == 0u)));
                     wave_sync();
                 }
                 if (todo) {
@@ -724,7 +747,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
     cnt_[17] = __builtin_readcyclecounter() - cyc_t0_;
     cnt_[18] = __builtin_readcyclecounter() - cyc_t1_;
     if (lane == 0)
-        for (int i = 0; i < 20; i++) if (cnt_[i]) atomicAdd(&g_ns_cnt[i], cnt_[i]);
+        for (int i = 0; i < kNsCnt; i++) if (cnt_[i]) atomicAdd(&g_ns_cnt[i], cnt_[i]);
 #endif
 }
 

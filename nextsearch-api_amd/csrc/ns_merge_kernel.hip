@@ -24,6 +24,18 @@
 
 namespace ns {
 
+#ifdef NS_COUNT
+// Counting build only: event counts of the merge body, summed over all items since the last reset; read through
+// ns_debug_merge_counters.  0 items, 1 steps, steps whose hi is 2 A's last loaded docId / 3 the last docId of B's window /
+// 4 the end of the doc range (a tie of 2 and 3 counts in both), 5 steps with a_rem == 0, 6 steps with b_rem == 0,
+// 7 .. 10 B windows of 1 .. 4 chunks, 11 docs found in both lists.
+constexpr int kNsMcnt = 16;
+__device__ unsigned long long g_ns_mcnt[kNsMcnt];
+#define NS_MCNT(i, v) mc_[(i)] += (unsigned long long)(v)
+#else
+#define NS_MCNT(i, v)
+#endif
+
 // IMP: both lists have their term scores in the segment's score stream ({docId, score bits}, index-aligned with the postings:
 // the optional impact stream, or the batch's shared term scores): no tf, no norm, no division here (see dscore_body).
 template <bool AND, int CB, bool IMP = false>
@@ -62,12 +74,19 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
     const uint32_t last_doc = it.doc_hi - 1;
     WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one merge step
     uint32_t found_s = 0;
+#ifdef NS_COUNT
+    unsigned long long mc_[kNsMcnt] = {};
+    NS_MCNT(0, 1);
+#endif
 
     wave_sync();
     for (;;) {
         const uint32_t a_rem = a_end - a_cur, b_rem = b_end - b_cur;
         if (a_rem == 0u && b_rem == 0u) break;
         top.begin_step();
+        NS_MCNT(1, 1);
+        NS_MCNT(5, a_rem == 0u ? 1 : 0);
+        NS_MCNT(6, b_rem == 0u ? 1 : 0);
         const uint32_t na = min(a_rem, (uint32_t)(DE * 64));
         // B's window: what B is expected to hold under one round of A (the lists thin out alike), a quarter more, whole chunks
         uint32_t nb;
@@ -77,6 +96,7 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
             nb = min(b_rem, min((uint32_t)(BE * 64), (w + 63u) & ~63u));
             nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
         }
+        NS_MCNT(6 + (nb + 63u) / 64u, nb > 0u ? 1 : 0);   // 7 .. 10: the window's chunks
         // ---- loads: scalar base + fixed lane offset (the buffers are padded past the last list) ----
         nat_u2 pa[DE], pb[BE];
         float na_[DE], nb_[BE];
@@ -100,6 +120,10 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
         }
         // ---- hi: every posting <= hi of both lists is loaded ----
         uint32_t hi = last_doc;
+#ifdef NS_COUNT
+        uint32_t lasta_ = kNone, lastb_ = kNone;   // the bounds the two loads set (kNone: the list ends inside its load)
+        if (a_rem > na) lasta_ = rdlane(pa[DE - 1].x, 63);
+#endif
         if (a_rem > na) {   // A goes on beyond this round: its last loaded docId bounds the step (na == 256 here)
             hi = min(hi, rdlane(pa[DE - 1].x, 63));
         }
@@ -110,7 +134,13 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
             for (int j = 0; j < BE; j++)
                 if ((lp >> 6) == (uint32_t)j) lastb = rdlane(pb[j].x, lp & 63u);   // uniform select
             hi = min(hi, lastb);
+#ifdef NS_COUNT
+            lastb_ = lastb;
+#endif
         }
+        NS_MCNT(2, hi == lasta_ ? 1 : 0);
+        NS_MCNT(3, hi == lastb_ ? 1 : 0);
+        NS_MCNT(4, (hi != lasta_ && hi != lastb_) ? 1 : 0);
         // ---- who is taken (lanes inside the load with docId <= hi) ----
         uint64_t ta[DE], tb[BE];
         uint32_t cnt_a = 0, cnt_b = 0;
@@ -187,6 +217,7 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
             mb[j] = wballot(l_docs[p] == pb[j].x) & tb[j];
             n_match += (uint32_t)__popcll(mb[j]);
         }
+        NS_MCNT(11, n_match);
         // matched B lanes take A's score and mark A's slot (all searches are done: the marks cannot disturb them)
         float xam[BE];
 #pragma unroll
@@ -233,6 +264,10 @@ __device__ __forceinline__ void mscore_body(const DevWItem& it, const DevTerm* _
     }
 
     top.write_out(it.seg, it.out_slot, found_s, out_hits, out_nhits, out_found);
+#ifdef NS_COUNT
+    if (lane == 0)
+        for (int i = 0; i < kNsMcnt; i++) if (mc_[i]) atomicAdd(&g_ns_mcnt[i], mc_[i]);
+#endif
 }
 
 }  // namespace ns

@@ -106,6 +106,12 @@ __device__ __noinline__ uint64_t wave_shrink_regs_packed(uint64_t* cand, uint32_
 // ballot straight from the compare (HIP's __ballot goes through an int and costs two extra vector instructions)
 __device__ __forceinline__ uint64_t wballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
+#ifdef NS_COUNT
+// Counting build only: shrinks of the candidate buffer over all bodies since the last reset (ns_debug_topk_counters):
+// 0 between steps (keep_room), 1 INSIDE a step (an offer that would overflow the buffer), 2 the final one of write_out.
+__device__ unsigned long long g_ns_kcnt[4];
+#endif
+
 // ---- the wave's running top-K, kept the same way by every scoring body ----
 // A buffer of CB LDS entries (make_key: higher score first, then smaller docId; CB a power of two >= K + 64) takes the
 // candidates above theta, the K-th best score as of the last shrink.  A shrink sorts the buffer, keeps its best K and
@@ -126,6 +132,12 @@ struct WaveTopK {
     uint32_t ncand = 0;
     uint32_t nsorted = 0;    // leading candidates already in descending order (left by the last shrink)
     bool ge_mode = false;    // a shrink happened inside the current step
+#ifdef NS_COUNT
+    uint32_t n_shrink_[3] = {0, 0, 0};
+#define NS_KCNT(i) n_shrink_[(i)]++
+#else
+#define NS_KCNT(i)
+#endif
 
     __device__ __forceinline__ WaveTopK(uint64_t* c, uint32_t k, int l) : cand(c), K(k), lane(l) {}
 
@@ -144,7 +156,7 @@ struct WaveTopK {
 
     // keep room for one more step of offers
     __device__ __forceinline__ void keep_room() {
-        if (ncand > (uint32_t)(CB - 64)) shrink();
+        if (ncand > (uint32_t)(CB - 64)) { shrink(); NS_KCNT(0); }
     }
 
     // offer (score, doc) of the lanes where `cond` holds
@@ -156,6 +168,7 @@ struct WaveTopK {
             uint32_t n = (uint32_t)__popcll(mask);
             if (ncand + n > (uint32_t)CB) {
                 shrink();
+                NS_KCNT(1);
                 if (!STRICT) ge_mode = true;
                 q = cond && (STRICT ? score > theta : score >= theta);
                 mask = wballot(q);
@@ -174,6 +187,7 @@ struct WaveTopK {
             uint32_t n = (uint32_t)__popcll(mask);
             if (ncand + n > (uint32_t)CB) {
                 shrink();
+                NS_KCNT(1);
                 if (!STRICT) ge_mode = true;
                 mask = condm & wballot(STRICT ? score > theta : score >= theta);
                 n = (uint32_t)__popcll(mask);
@@ -193,6 +207,7 @@ struct WaveTopK {
             uint32_t n = (uint32_t)__popcll(mask);
             if (ncand + n > (uint32_t)CB) {
                 shrink();
+                NS_KCNT(1);
                 if (!STRICT) ge_mode = true;
                 mask = condm & wballot(STRICT ? score > theta : score >= theta);
                 n = (uint32_t)__popcll(mask);
@@ -207,6 +222,11 @@ struct WaveTopK {
                                               uint32_t* out_nhits, uint64_t* out_found) {
         wave_sync();
         shrink();
+        NS_KCNT(2);
+#ifdef NS_COUNT
+        if (lane == 0)
+            for (int i = 0; i < 3; i++) if (n_shrink_[i]) atomicAdd(&g_ns_kcnt[i], (unsigned long long)n_shrink_[i]);
+#endif
         const uint32_t n = min(ncand, K);
         Hit* oh = out_hits + (uint64_t)out_slot * K;
         for (uint32_t i = lane; i < K; i += 64) {

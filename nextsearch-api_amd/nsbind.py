@@ -176,8 +176,29 @@ def hip_lib():
         L.ns_compact_doc_cut.argtypes = []
         L.ns_compact_doc_cut.restype = u32
         L.ns_ctx_use_docsort.argtypes = [vp, i32]
+        for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [C.POINTER(u64), i32]
         _hip = L
     return _hip
+
+
+# counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
+DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4}
+
+
+def debug_counters(reset=False):
+    """{getter: [values]} of every event counter the loaded HIP library exports ({} for the product library); `reset`
+    zeroes them after the read."""
+    L = hip_lib()
+    out = {}
+    for name, n in DEBUG_COUNTERS.items():
+        if hasattr(L, name):
+            buf = (C.c_uint64 * n)()
+            if getattr(L, name)(buf, int(bool(reset))) != 0:
+                raise RuntimeError(name + " failed")
+            out[name] = [int(v) for v in buf]
+    return out
 
 
 def host_lib():

@@ -13,6 +13,7 @@ from conftest import GOLDEN_NAMES, VARIANTS_BUILD, VARIANTS_LIB, need_variants
 import nsbind
 import orc
 import workloads
+from rawseg import _np_bm25
 
 pytestmark = pytest.mark.gpu
 
@@ -904,22 +905,6 @@ def test_idf_outside_short_division_range_scales_exactly(engines):
             n = int(n0[q])
             np.testing.assert_array_equal(h0[q, :n]["doc"], h1[q, :n]["doc"])
             np.testing.assert_array_equal((h0[q, :n]["score"] * np.float32(scale)).view(np.uint32), h1[q, :n]["score"].view(np.uint32))
-
-
-def _np_bm25(seg_lists, refs_idx, idfs, weights, doc_len, avgdl):
-    """fp32 restatement of src/api_engine.cpp:477-480 in numpy (every operation rounds to fp32)."""
-    f = np.float32
-    acc = {}
-    for li, idf, w in zip(refs_idx, idfs, weights):
-        docs, tfs = seg_lists[li]
-        dl = doc_len[docs].astype(np.float32)
-        norm = f(1.2) * ((f(1.0) - f(0.75)) + f(0.75) * (dl / f(avgdl)))
-        tf = tfs.astype(np.float32)
-        s = (f(idf) * (tf * (f(1.2) + f(1.0)))) / (tf + norm)
-        x = f(w) * s
-        for d, v in zip(docs.tolist(), x.tolist()):
-            acc[d] = f(acc.get(d, f(0.0)) + f(v))
-    return acc
 
 
 def test_sparse_lists_over_20m_docs_span_clamp():
