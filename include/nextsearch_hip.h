@@ -400,6 +400,28 @@ int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postings_out, uin
 uint32_t ns_compact_doc_cut(void);
 int ns_ctx_use_docsort(ns_ctx* ctx, int on);
 
+/* Deleting documents (csrc/ns_delete.hip): ns_forward_merge over FILTERED sources.  keep[s] is a bitmap
+ * over source s's documents: document d stays iff bit (d & 31) of word (d >> 5) is set; (n_docs + 31) / 32 words are read
+ * and the bits at and past n_docs in the last word are ignored.  keep == NULL or keep[s] == NULL: the source passes
+ * through unchanged; with every entry NULL the call IS ns_forward_merge, byte for byte and launch for launch.
+ * DEFINITION  the result is what ns_forward_merge returns over the filtered sources, and the refusals are the ones it makes
+ * over them.  A source with a bitmap is filtered like this: it loses its dropped documents and their pairs; it loses every
+ * term that no surviving pair names; the surviving terms keep their relative id order (new id = number of surviving terms
+ * with a smaller old id); the surviving pairs are renumbered through that map.  The merge's own rules stay: sources in
+ * order, a byte string gets the next free id the first time the walk meets it.  It follows that
+ *   - the pairs of dropped documents are not read: an out-of-range termId inside a dropped document is not reported (one
+ *     in a surviving pair is, with the smallest such source named, as ns_forward_merge does);
+ *   - "the same byte string twice in one source" is refused among the SURVIVING terms only;
+ *   - a source whose documents are all dropped contributes nothing, neither documents nor terms;
+ *   - when nothing survives anywhere the call returns NS_OK with an empty handle (kept_docs == 0);
+ *   - the result is an ordinary ns_forward handle: ns_forward_get_info, ns_forward_fetch, ns_forward_invert,
+ *     ns_forward_destroy and the lifetime rules apply unchanged; n_docs == kept_docs == the surviving documents, docId =
+ *     position among them;
+ *   - the limits and the message style are ns_forward_merge's (messages start with "ns_forward_merge_keep:").  The limits
+ *     and the structural checks (counts that sum to n_pairs, term offsets that do not decrease) are applied to the sources
+ *     as handed in, before the filter: the counts of dropped documents are needed to find the surviving pairs. */
+int ns_forward_merge_keep(ns_ctx* ctx, const ns_forward_src* src, const uint32_t* const* keep, uint32_t n_src, ns_forward** out);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -186,6 +186,33 @@ const char* nsh_compact_error(void);
  * answers as before, nsh_engine_error() says why.  0 with a non-empty nsh_engine_error(): a source could not be removed. */
 int nsh_engine_compact(nsh_engine* e, uint64_t first, uint64_t count, int remove_sources, nsh_compact_stats* stats);
 
+/* Deleting documents (host/purge.hpp).  A uid list travels as uid i = bytes[offsets[i] .. offsets[i + 1])
+ * (offsets: n_uids + 1 entries). */
+typedef struct nsh_delete_stats {
+    uint32_t struct_size;   /* IN: sizeof(nsh_delete_stats) as the caller was compiled; no more than that is written */
+    uint32_t segments_rewritten, segments_dropped, docs_deleted, uids_not_found, terms_dropped;
+    uint64_t pairs_in, pairs_out, device_bytes;   /* pairs of the rewritten segments before / after */
+    float    merge_ms, invert_ms;                 /* HIP events around the device parts, summed over the rewritten segments */
+    double   call_s, total_s;
+} nsh_delete_stats;
+/* Engine::find_documents: every (manifest position, docId) whose docs.bin uid is listed, ascending, as u32 pairs into
+ * seg_doc_out (capacity pairs; may be NULL).  Returns the number of matches (which may exceed capacity: call again), -1
+ * on failure.  Host only: works on a host-only engine. */
+int64_t nsh_engine_find_documents(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_uids,
+                                  uint32_t* seg_doc_out, uint64_t capacity);
+/* Engine::delete_documents: every document that carries a listed uid goes, in every segment.  Each affected segment is
+ * rewritten on the device into the next free segments/seg_%06u, which takes its place in manifest.bin; a segment with no
+ * survivor leaves the manifest; untouched segments are not rewritten; the engine reloads; the old directories are removed
+ * afterwards.  Uids that match nothing are counted in stats->uids_not_found; nothing matching at all: 0, nothing touched.
+ * Surviving documents of a rewritten segment get new docIds (their positions): the uid is the stable handle.
+ * -1 on failure (also on a host-only engine, and when every document of the index would go): the manifest keeps its bytes,
+ * the new directories are gone, the engine answers as before, nsh_engine_error() says why.  0 with a non-empty
+ * nsh_engine_error(): an old directory could not be removed. */
+int nsh_engine_delete_documents(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_uids, nsh_delete_stats* stats);
+/* Engine::delete_by_id: the same for n_pairs u32 pairs (manifest position, docId).  A pair out of range: -1, nothing
+ * touched; a pair listed twice counts once. */
+int nsh_engine_delete_by_id(nsh_engine* e, const uint32_t* seg_doc, uint64_t n_pairs, nsh_delete_stats* stats);
+
 /* Autocomplete: Engine::suggest(input, limit) (include/api_engine.hpp:67, src/api_engine.cpp:164-187).  The input is
  * input_len raw bytes (NUL and other control bytes included); *json_out receives {"limit", "query", "suggestions"} in
  * dump(2) layout (free with nsh_free).  -1 without a device context (there is no CPU path) or on failure. */

@@ -24,6 +24,7 @@
 #include "ns_invert.hip"
 #include "ns_ingest.hip"
 #include "ns_compact.hip"
+#include "ns_delete.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 
@@ -1989,50 +1990,80 @@ extern "C" int ns_ctx_use_docsort(ns_ctx* ctx, int on) {
     return NS_OK;
 }
 
-extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t n_src, ns_forward** out) {
-    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_forward_merge: ctx is NULL");
-    if (!out) return fail(ctx, NS_E_INVAL, "ns_forward_merge: out is NULL");
+// The body of ns_forward_merge and ns_forward_merge_keep (fn: the entry point's name for the messages).  keep == NULL, or
+// every keep[s] NULL: the plain merge, launch for launch what it always was.  Otherwise the filter stages of
+// csrc/ns_delete.hip run first and hand the dictionary, remap and docsort stages their input in device memory.
+static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* src, const uint32_t* const* keep, uint32_t n_src, ns_forward** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
     *out = nullptr;
-    if (n_src && !src) return fail(ctx, NS_E_INVAL, "ns_forward_merge: src is NULL");
+    if (n_src && !src) return fail(ctx, NS_E_INVAL, "%s: src is NULL", fn);
     // ---- the totals, from the counts alone ----
     uint64_t docs64 = 0, pairs64 = 0, terms64 = 0;
     for (uint32_t s = 0; s < n_src; s++) {
         docs64 += src[s].n_docs; terms64 += src[s].n_terms;
         if (src[s].n_pairs >= (1ull << 32) || (pairs64 += src[s].n_pairs) >= (1ull << 32) - kIvTile)
-            return fail(ctx, NS_E_INVAL, "ns_forward_merge: more than %llu pairs up to source %u; this build indexes pairs with 32 bits (compact fewer segments)", (unsigned long long)((1ull << 32) - kIvTile - 1), s);
+            return fail(ctx, NS_E_INVAL, "%s: more than %llu pairs up to source %u; this build indexes pairs with 32 bits (compact fewer segments)", fn, (unsigned long long)((1ull << 32) - kIvTile - 1), s);
     }
-    if (docs64 >= 0xFFFFFFFFull) return fail(ctx, NS_E_INVAL, "ns_forward_merge: %llu documents; docIds are 32 bits wide (below 2^32 - 1: compact fewer segments)", (unsigned long long)docs64);
-    if (terms64 >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "ns_forward_merge: %llu source terms; the dictionary holds fewer than 2^31 (compact fewer segments)", (unsigned long long)terms64);
+    if (docs64 >= 0xFFFFFFFFull) return fail(ctx, NS_E_INVAL, "%s: %llu documents; docIds are 32 bits wide (below 2^32 - 1: compact fewer segments)", fn, (unsigned long long)docs64);
+    if (terms64 >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu source terms; the dictionary holds fewer than 2^31 (compact fewer segments)", fn, (unsigned long long)terms64);
     uint64_t bytes64 = 0;
     for (uint32_t s = 0; s < n_src; s++) {
         const ns_forward_src& S = src[s];
-        if ((S.n_docs && (!S.doc_len || !S.counts)) || (S.n_pairs && !S.pairs) || (S.n_terms && !S.term_offsets)) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: null array", s);
+        if ((S.n_docs && (!S.doc_len || !S.counts)) || (S.n_pairs && !S.pairs) || (S.n_terms && !S.term_offsets)) return fail(ctx, NS_E_INVAL, "%s: source %u: null array", fn, s);
         if (S.n_terms) {
-            if (S.term_offsets[S.n_terms] < S.term_offsets[0]) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term offsets decrease", s);
+            if (S.term_offsets[S.n_terms] < S.term_offsets[0]) return fail(ctx, NS_E_INVAL, "%s: source %u: term offsets decrease", fn, s);
             bytes64 += S.term_offsets[S.n_terms] - S.term_offsets[0];
-            if (bytes64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "ns_forward_merge: more than 4 GiB - 64 KiB of term bytes up to source %u; this build addresses them with 32 bits (compact fewer segments)", s);
+            if (bytes64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "%s: more than 4 GiB - 64 KiB of term bytes up to source %u; this build addresses them with 32 bits (compact fewer segments)", fn, s);
         }
     }
-    const uint32_t n_docs = (uint32_t)docs64, n_pairs = (uint32_t)pairs64, T = (uint32_t)terms64, n = (uint32_t)bytes64;
+    bool filtered = false;                                             // some source has a bitmap: the stages of ns_delete.hip run
+    for (uint32_t s = 0; keep && s < n_src; s++) filtered = filtered || keep[s] != nullptr;
+    const uint32_t raw_pairs = (uint32_t)pairs64, T = (uint32_t)terms64, n = (uint32_t)bytes64;
+    uint32_t n_docs = (uint32_t)docs64, n_pairs = raw_pairs;           // filtered: the survivors', set below
     std::vector<uint32_t> term_base((size_t)n_src + 1, 0), pair_base((size_t)n_src + 1, 0), kstart(T), klen(T), prefix((size_t)n_docs + 1, 0);
+    // filtered only: where a source's pairs lie in the upload, per surviving document its first pair there, its doc_len and
+    // count, and per source term 1 where the source has no bitmap (its terms all stay)
+    std::vector<uint32_t> raw_base, srcpos, kept_len, kept_cnt, live0;
+    if (filtered) { raw_base.assign((size_t)n_src + 1, 0); srcpos.reserve(n_docs); kept_len.reserve(n_docs); kept_cnt.reserve(n_docs); live0.assign((size_t)T + 1, 0); }
     uint64_t total_len = 0;
     {
         uint32_t d = 0, k = 0, at = 0;
         for (uint32_t s = 0; s < n_src; s++) {
             const ns_forward_src& S = src[s];
             uint64_t sum = 0;
-            for (uint32_t j = 0; j < S.n_docs; j++, d++) { sum += S.counts[j]; total_len += S.doc_len[j]; prefix[d + 1] = (uint32_t)(pair_base[s] + sum); if (sum > S.n_pairs) break; }
-            if (sum != S.n_pairs) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: the per-document counts do not sum to n_pairs = %llu", s, (unsigned long long)S.n_pairs);
+            if (!filtered) {
+                for (uint32_t j = 0; j < S.n_docs; j++, d++) { sum += S.counts[j]; total_len += S.doc_len[j]; prefix[d + 1] = (uint32_t)(pair_base[s] + sum); if (sum > S.n_pairs) break; }
+                pair_base[s + 1] = pair_base[s] + (uint32_t)S.n_pairs;
+            } else {
+                const uint32_t* bits = keep[s];
+                uint64_t stay = 0;                                     // pairs of the source's surviving documents so far
+                for (uint32_t j = 0; j < S.n_docs; j++) {
+                    const uint32_t c = S.counts[j];
+                    if (!bits || ((bits[j >> 5] >> (j & 31u)) & 1u)) {
+                        srcpos.push_back(raw_base[s] + (uint32_t)sum); kept_len.push_back(S.doc_len[j]); kept_cnt.push_back(c);
+                        total_len += S.doc_len[j];
+                        stay += c;
+                        prefix[++d] = (uint32_t)(pair_base[s] + stay);
+                    }
+                    sum += c;
+                    if (sum > S.n_pairs) break;
+                }
+                raw_base[s + 1] = raw_base[s] + (uint32_t)S.n_pairs;
+                pair_base[s + 1] = pair_base[s] + (uint32_t)stay;
+                if (!bits) std::fill(live0.begin() + term_base[s], live0.begin() + term_base[s] + S.n_terms, 1u);
+            }
+            if (sum != S.n_pairs) return fail(ctx, NS_E_INVAL, "%s: source %u: the per-document counts do not sum to n_pairs = %llu", fn, s, (unsigned long long)S.n_pairs);
             for (uint32_t t = 0; t < S.n_terms; t++, k++) {
-                if (S.term_offsets[t + 1] < S.term_offsets[t]) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term offsets decrease at term %u", s, t);
+                if (S.term_offsets[t + 1] < S.term_offsets[t]) return fail(ctx, NS_E_INVAL, "%s: source %u: term offsets decrease at term %u", fn, s, t);
                 kstart[k] = at + (uint32_t)(S.term_offsets[t] - S.term_offsets[0]);
                 klen[k] = (uint32_t)(S.term_offsets[t + 1] - S.term_offsets[t]);
             }
-            if (S.n_terms && S.term_offsets[S.n_terms] != S.term_offsets[0] && !S.term_bytes) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %u: term_bytes is NULL", s);
+            if (S.n_terms && S.term_offsets[S.n_terms] != S.term_offsets[0] && !S.term_bytes) return fail(ctx, NS_E_INVAL, "%s: source %u: term_bytes is NULL", fn, s);
             if (S.n_terms) at += (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]);
             term_base[s + 1] = term_base[s] + S.n_terms;
-            pair_base[s + 1] = pair_base[s] + (uint32_t)S.n_pairs;
         }
+        if (filtered) { n_docs = d; n_pairs = pair_base[n_src]; prefix.resize((size_t)n_docs + 1); }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ns_forward* f = new ns_forward();
@@ -2068,12 +2099,12 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
 
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    char *blkA = nullptr, *blkB = nullptr;
-    size_t bytesA = 0, bytesB = 0, off = 0;
+    char *blkA = nullptr, *blkB = nullptr, *blkF = nullptr;
+    size_t bytesA = 0, bytesB = 0, bytesF = 0, off = 0;
     auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    enum { C_TERMS = 0, C_TBYTES = 1, C_LONG = 2, C_DUP = 4, C_BAD = 5 };   // C_DUP / C_BAD: the smallest refused source, ~0 for none
+    enum { C_TERMS = 0, C_TBYTES = 1, C_LONG = 2, C_LIVE = 3, C_DUP = 4, C_BAD = 5 };   // C_DUP / C_BAD: the smallest refused source, ~0 for none; C_LIVE: the terms that stay (filtered)
     uint64_t cap = 1024;
     while (cap < 2ull * T) cap <<= 1;                                  // T < 2^31: cap <= 2^32, its mask fits 32 bits
     const uint32_t big_tiles = (n_big + kIvTile - 1) / kIvTile;
@@ -2087,6 +2118,15 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
     const size_t o_tb = place(term_base.size() * 4), o_pb = place(pair_base.size() * 4), o_prefix = place(prefix.size() * 4), o_lists = place(lists.size() * 4);
     bytesA = off;
     chk(pool_alloc(ctx, (void**)&blkA, bytesA));
+    // ---- block F (filtered only): the pairs as uploaded, the live flags and their scan, the source terms' (start, length),
+    // the surviving terms' per-source base, the (source, old id) -> new id map, the surviving documents' places in the upload ----
+    off = 0;
+    const size_t o_raw = place((size_t)raw_pairs * 8), o_live = place(((size_t)T + 1) * 4), o_rank = place(((size_t)T + 1) * 4), o_ks0 = place(T1 * 4), o_kl0 = place(T1 * 4);
+    const size_t o_tbl = place(term_base.size() * 4), o_omap = place(T1 * 4), o_spos = place((size_t)n_docs * 4);
+    if (filtered) {
+        bytesF = off;
+        chk(pool_alloc(ctx, (void**)&blkF, bytesF));
+    }
     chk(hipEventCreate(&ev0));
     chk(hipEventCreate(&ev1));
     chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
@@ -2108,6 +2148,10 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
         unsigned long long* d_dtab = (unsigned long long*)(blkA + o_dtab);
         uint32_t *d_long = (uint32_t*)(blkA + o_long), *d_sums = (uint32_t*)(blkA + o_sums);
         uint32_t *d_tb = (uint32_t*)(blkA + o_tb), *d_pb = (uint32_t*)(blkA + o_pb), *d_prefix = (uint32_t*)(blkA + o_prefix), *d_lists = (uint32_t*)(blkA + o_lists);
+        uint2* d_raw = filtered ? (uint2*)(blkF + o_raw) : nullptr;
+        uint32_t *d_live = filtered ? (uint32_t*)(blkF + o_live) : nullptr, *d_rank = filtered ? (uint32_t*)(blkF + o_rank) : nullptr;
+        uint32_t *d_ks0 = filtered ? (uint32_t*)(blkF + o_ks0) : d_kstart, *d_kl0 = filtered ? (uint32_t*)(blkF + o_kl0) : d_klen;   // where the host's (start, length) go
+        uint32_t *d_tbl = filtered ? (uint32_t*)(blkF + o_tbl) : d_tb, *d_omap = filtered ? (uint32_t*)(blkF + o_omap) : d_newid, *d_spos = filtered ? (uint32_t*)(blkF + o_spos) : nullptr;
         const uint32_t *d_lwave = d_lists, *d_llds = d_lists + n_wave, *d_lbig = d_lists + n_wave + n_lds, *d_bigpre = d_lists + n_wave + n_lds + n_bigdocs;
         // uploads: term bytes, pairs, counts and doc_len source by source; the host-made arrays
         {
@@ -2116,8 +2160,10 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
                 const ns_forward_src& S = src[s];
                 const uint32_t nb = S.n_terms ? (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]) : 0u;
                 if (nb) chk(hipMemcpyAsync(d_text + at, S.term_bytes + S.term_offsets[0], nb, hipMemcpyHostToDevice, st));
-                if (S.n_pairs) chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
-                if (S.n_docs) {
+                if (filtered) {   // (a source without a surviving pair is not uploaded: nothing reads it)
+                    if (pair_base[s + 1] != pair_base[s]) chk(hipMemcpyAsync(d_raw + raw_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                } else if (S.n_pairs) chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                if (S.n_docs && !filtered) {
                     chk(hipMemcpyAsync(f->d_len + d, S.doc_len, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
                     chk(hipMemcpyAsync(f->d_cnt + d, S.counts, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
                 }
@@ -2128,8 +2174,14 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
         for (uint32_t d = 0; d < n_docs; d++) iota[d] = d;
         chk(hipMemcpyAsync(f->d_map, iota.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
         if (T) {
-            chk(hipMemcpyAsync(d_kstart, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(d_klen, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(d_ks0, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(d_kl0, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+        }
+        if (filtered) {
+            chk(hipMemcpyAsync(f->d_len, kept_len.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(f->d_cnt, kept_cnt.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(d_spos, srcpos.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(d_live, live0.data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice, st));
         }
         chk(hipMemcpyAsync(d_tb, term_base.data(), term_base.size() * 4, hipMemcpyHostToDevice, st));
         chk(hipMemcpyAsync(d_pb, pair_base.data(), pair_base.size() * 4, hipMemcpyHostToDevice, st));
@@ -2143,15 +2195,36 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
             if (e == hipSuccess) chk(hipMemcpyAsync(h_cnt, d_cntv, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
             if (e == hipSuccess) chk(hipStreamSynchronize(st));
         };
-        const uint32_t gT = (T + 255) / 256;
-        if (e == hipSuccess && T) {
-            chk(hipMemsetAsync(d_table, 0xFF, (size_t)cap * 4, st));
-            chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)cap * 8, st));
-            hipLaunchKernelGGL(k_cp_hash, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, T, d_tb, n_src, hash_mask, d_ksrc, d_khash, d_long, d_cntv + C_LONG);
+        // ---- the filter (csrc/ns_delete.hip): afterwards Td "tokens" in d_kstart / d_klen with their bases in d_tbl, the
+        // surviving pairs in f->d_pairs under the sources' OLD term ids ----
+        uint32_t Td = T;                                               // the dictionary stage's tokens: the source terms that stay
+        if (e == hipSuccess && filtered) {
+            if (n_pairs) {
+                const uint32_t gK = (n_pairs + kCpKeepTile - 1) / kCpKeepTile;
+#ifdef NS_VARIANTS
+                // test and A/B knob (variants build only): every pair searches the whole document prefix; same bytes
+                if (std::getenv("NS_KEEP_FULL_SEARCH")) hipLaunchKernelGGL((k_cp_keep_gather<false>), dim3(gK), dim3(256), 0, st, d_raw, d_prefix, d_spos, n_docs, n_pairs, d_pb, d_tb, n_src, f->d_pairs, d_live);
+                else
+#endif
+                hipLaunchKernelGGL((k_cp_keep_gather<true>), dim3(gK), dim3(256), 0, st, d_raw, d_prefix, d_spos, n_docs, n_pairs, d_pb, d_tb, n_src, f->d_pairs, d_live);
+            }
+            chk(hipMemcpyAsync(d_rank, d_live, ((size_t)T + 1) * 4, hipMemcpyDeviceToDevice, st));
+            ig_scan(st, d_rank, T + 1, d_sums, d_cntv + C_LIVE);       // (entry T is 0: the total is rank[T] as well)
+            hipLaunchKernelGGL(k_cp_keep_terms, dim3((std::max(T, n_src + 1) + 255) / 256), dim3(256), 0, st, d_live, d_rank, T, d_ks0, d_kl0, d_tb, n_src, d_kstart, d_klen, d_tbl);
+            read_counts();
+            Td = h_cnt[C_LIVE];
+        }
+        uint64_t capd = 1024;                                          // == cap unless terms were dropped
+        while (capd < 2ull * Td) capd <<= 1;
+        const uint32_t gT = (Td + 255) / 256;
+        if (e == hipSuccess && Td) {
+            chk(hipMemsetAsync(d_table, 0xFF, (size_t)capd * 4, st));
+            chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)capd * 8, st));
+            hipLaunchKernelGGL(k_cp_hash, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, Td, d_tbl, n_src, hash_mask, d_ksrc, d_khash, d_long, d_cntv + C_LONG);
             hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
-            hipLaunchKernelGGL(k_ig_insert, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, T, d_table, (uint32_t)(cap - 1), d_kslot);
-            hipLaunchKernelGGL(k_ig_first, dim3(gT), dim3(256), 0, st, d_table, d_kslot, T, d_krep, d_fid);
-            ig_scan(st, d_fid, T, d_sums, d_cntv + C_TERMS);
+            hipLaunchKernelGGL(k_ig_insert, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, Td, d_table, (uint32_t)(capd - 1), d_kslot);
+            hipLaunchKernelGGL(k_ig_first, dim3(gT), dim3(256), 0, st, d_table, d_kslot, Td, d_krep, d_fid);
+            ig_scan(st, d_fid, Td, d_sums, d_cntv + C_TERMS);
             read_counts();
             n_terms = h_cnt[C_TERMS];
         }
@@ -2159,12 +2232,14 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
         if (e == hipSuccess) chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
         if (e == hipSuccess) {
             chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
-            if (T) {
-                hipLaunchKernelGGL(k_ig_termid, dim3(gT), dim3(256), 0, st, d_krep, d_fid, d_ksrc, d_kstart, d_klen, T, d_newid, d_tvals, f->d_toff, d_tsrc);
+            if (Td) {
+                hipLaunchKernelGGL(k_ig_termid, dim3(gT), dim3(256), 0, st, d_krep, d_fid, d_ksrc, d_kstart, d_klen, Td, d_newid, d_tvals, f->d_toff, d_tsrc);
                 ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
-                hipLaunchKernelGGL(k_cp_dup, dim3(gT), dim3(256), 0, st, d_newid, d_ksrc, T, d_dtab, (uint32_t)(cap - 1), d_cntv + C_DUP);
+                hipLaunchKernelGGL(k_cp_dup, dim3(gT), dim3(256), 0, st, d_newid, d_ksrc, Td, d_dtab, (uint32_t)(capd - 1), d_cntv + C_DUP);
             }
-            if (n_pairs) hipLaunchKernelGGL(k_cp_remap, dim3((n_pairs + 255) / 256), dim3(256), 0, st, f->d_pairs, n_pairs, d_pb, d_tb, n_src, d_newid, d_cntv + C_BAD);
+            // d_omap: the map over the sources' own term ids (filtered: through the ranks; otherwise d_newid itself)
+            if (filtered && T) hipLaunchKernelGGL(k_cp_keep_map, dim3((T + 255) / 256), dim3(256), 0, st, d_live, d_rank, T, d_newid, d_omap);
+            if (n_pairs) hipLaunchKernelGGL(k_cp_remap, dim3((n_pairs + 255) / 256), dim3(256), 0, st, f->d_pairs, n_pairs, d_pb, d_tb, n_src, d_omap, d_cntv + C_BAD);
             read_counts();
             tbytes = h_cnt[C_TBYTES];
             f->info.term_bytes = tbytes;
@@ -2206,18 +2281,29 @@ extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t
     }
     (void)hipStreamSynchronize(st);   // nothing in flight uses the blocks any more
     if (blkB) pool_free(ctx, blkB, bytesB);
+    if (blkF) pool_free(ctx, blkF, bytesF);
     if (blkA) pool_free(ctx, blkA, bytesA);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
-    f->info.device_bytes = (uint64_t)bytesA + bytesB + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
+    f->info.device_bytes = (uint64_t)bytesA + bytesB + bytesF + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
     if (e != hipSuccess || refused_src >= 0) {
         forward_free_device(f);
         delete f;
         (void)hipGetLastError();
-        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "ns_forward_merge: source %d: %s", refused_src, refused_why);
-        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_forward_merge: %s", hipGetErrorString(e));
+        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "%s: source %d: %s", fn, refused_src, refused_why);
+        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
     return publish();
+}
+
+extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t n_src, ns_forward** out) {
+    return forward_merge_run(ctx, "ns_forward_merge", src, nullptr, n_src, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Deleting documents: the merge over filtered sources (csrc/ns_delete.hip)
+extern "C" int ns_forward_merge_keep(ns_ctx* ctx, const ns_forward_src* src, const uint32_t* const* keep, uint32_t n_src, ns_forward** out) {
+    return forward_merge_run(ctx, "ns_forward_merge_keep", src, keep, n_src, out);
 }
 
 extern "C" int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postings_out, uint64_t* kept_out, float* device_ms_out) {

@@ -115,6 +115,80 @@ inline bool load_sources(const std::vector<fs::path>& dirs, std::vector<SourceSe
     return true;
 }
 
+// What ns_forward_merge / ns_forward_merge_keep left on the device, on the host: the forward arrays and the inverted lists
+struct MergedSegment {
+    ns_forward_info info{};
+    std::vector<uint32_t> doc_len, counts, pairs, df;
+    std::vector<uint8_t> tbytes, postings;
+    std::vector<uint64_t> toff;
+};
+
+// fetch + ns_forward_invert; fwd is destroyed in every case.  false + err (the C-ABI's message) on failure
+inline bool fetch_merged(ns_ctx* ctx, ns_forward* fwd, MergedSegment& m, float& invert_ms, std::string& err) {
+    const ns_forward_info& info = m.info;
+    m.doc_len.resize(info.kept_docs); m.counts.resize(info.kept_docs); m.pairs.resize((size_t)info.n_pairs * 2); m.df.resize(info.n_terms);
+    m.tbytes.resize((size_t)info.term_bytes); m.postings.resize((size_t)info.n_pairs * 8);
+    m.toff.resize((size_t)info.n_terms + 1);
+    uint64_t kept = 0;
+    int rc = ns_forward_fetch(fwd, nullptr, m.doc_len.data(), m.counts.data(), m.pairs.data(), m.tbytes.data(), m.toff.data());
+    if (rc == NS_OK) rc = ns_forward_invert(fwd, m.df.data(), m.postings.data(), &kept, &invert_ms);
+    if (rc != NS_OK) err = ns_last_error(ctx);
+    ns_forward_destroy(fwd);
+    return rc == NS_OK;
+}
+
+// The complete segment out_seg from m: docs.bin = the count + the raw records in `records` back to back, stats.bin,
+// forward.bin, terms.bin, barrels.bin and the barrel files.  A directory this call created is removed again when a file
+// cannot be written.
+inline bool write_merged(const fs::path& out_seg, const MergedSegment& m, const std::vector<std::pair<const uint8_t*, size_t>>& records, std::string& err) {
+    const ns_forward_info& info = m.info;
+    uint64_t total_len = 0;
+    for (uint32_t v : m.doc_len) total_len += v;
+    const float avgdl = (float)total_len / (float)info.kept_docs;       // src/ForwardIndex.cpp:186
+    std::error_code ec;
+    const bool existed = fs::exists(out_seg, ec);
+    try {
+        fs::create_directories(out_seg, ec);
+        {
+            FileOut out(out_seg / "docs.bin");
+            out.u32(info.kept_docs);
+            for (const auto& r : records) out.raw(r.first, r.second);
+        }
+        { FileOut out(out_seg / "stats.bin"); out.u32(info.kept_docs); out.f32(avgdl); }
+        {
+            FileOut out(out_seg / "forward.bin");
+            out.u32(info.kept_docs);
+            size_t at = 0;
+            for (uint32_t j = 0; j < info.kept_docs; j++) {
+                out.u32(m.counts[j]);
+                out.raw(m.pairs.data() + at, (size_t)m.counts[j] * 8);
+                at += (size_t)m.counts[j] * 2;
+            }
+        }
+        {
+            FileOut out(out_seg / "terms.bin");
+            out.u32(info.n_terms);
+            for (uint32_t t = 0; t < info.n_terms; t++) {
+                out.u32((uint32_t)(m.toff[t + 1] - m.toff[t]));
+                out.raw(m.tbytes.data() + m.toff[t], (size_t)(m.toff[t + 1] - m.toff[t]));
+            }
+        }
+        write_barrels(out_seg, info.n_terms, m.df, m.postings,
+                      [&](uint32_t t) { return std::string((const char*)m.tbytes.data() + m.toff[t], (size_t)(m.toff[t + 1] - m.toff[t])); });
+    } catch (const std::exception& ex) {
+        err = ex.what();
+        if (!existed) fs::remove_all(out_seg, ec);
+        return false;
+    }
+    return true;
+}
+
+inline void fill_forward_src(const SourceSegment& s, ns_forward_src& out) {
+    out.n_docs = (uint32_t)s.doc_len.size(); out.doc_len = s.doc_len.data(); out.counts = s.counts.data();
+    out.n_pairs = s.pairs.size() / 2; out.pairs = s.pairs.data();
+    out.n_terms = (uint32_t)(s.term_offsets.size() - 1); out.term_bytes = s.term_bytes.data(); out.term_offsets = s.term_offsets.data();
+}
+
 // The loaded sources -> out_seg.  Nothing is written before the device work has succeeded; a directory this call created
 // is removed again when a file cannot be written.
 inline bool merge_loaded(ns_ctx* ctx, const std::vector<SourceSegment>& sources, const fs::path& out_seg, CompactStats& st, std::string& err) {
@@ -123,10 +197,7 @@ inline bool merge_loaded(ns_ctx* ctx, const std::vector<SourceSegment>& sources,
     if (!ctx) { err = "merge_segments: no device context (compaction runs on the device; there is no CPU path)"; return false; }
     std::vector<ns_forward_src> src(sources.size());
     for (size_t i = 0; i < sources.size(); i++) {
-        const SourceSegment& s = sources[i];
-        src[i].n_docs = (uint32_t)s.doc_len.size(); src[i].doc_len = s.doc_len.data(); src[i].counts = s.counts.data();
-        src[i].n_pairs = s.pairs.size() / 2; src[i].pairs = s.pairs.data();
-        src[i].n_terms = (uint32_t)(s.term_offsets.size() - 1); src[i].term_bytes = s.term_bytes.data(); src[i].term_offsets = s.term_offsets.data();
+        fill_forward_src(sources[i], src[i]);
         st.terms_in += src[i].n_terms;
     }
     st.sources = (uint32_t)sources.size();
@@ -142,59 +213,17 @@ inline bool merge_loaded(ns_ctx* ctx, const std::vector<SourceSegment>& sources,
     ns_forward* fwd = nullptr;
     int rc = ns_forward_merge(ctx, src.data(), (uint32_t)src.size(), &fwd);
     if (rc != NS_OK) { err = name_source(ns_last_error(ctx)); return false; }
-    ns_forward_info info{};
-    info.struct_size = (uint32_t)sizeof(info);
-    (void)ns_forward_get_info(fwd, &info);
+    MergedSegment m;
+    m.info.struct_size = (uint32_t)sizeof(m.info);
+    (void)ns_forward_get_info(fwd, &m.info);
+    const ns_forward_info& info = m.info;
     st.n_docs = info.kept_docs; st.n_terms = info.n_terms; st.pairs = info.n_pairs; st.merge_ms = info.device_ms; st.device_bytes = info.device_bytes;
     if (info.kept_docs == 0) { ns_forward_destroy(fwd); err = "merge_segments: the sources hold no document"; return false; }
-    std::vector<uint32_t> doc_len(info.kept_docs), counts(info.kept_docs), pairs((size_t)info.n_pairs * 2), df(info.n_terms);
-    std::vector<uint8_t> tbytes((size_t)info.term_bytes), postings((size_t)info.n_pairs * 8);
-    std::vector<uint64_t> toff((size_t)info.n_terms + 1);
-    uint64_t kept = 0;
-    rc = ns_forward_fetch(fwd, nullptr, doc_len.data(), counts.data(), pairs.data(), tbytes.data(), toff.data());
-    if (rc == NS_OK) rc = ns_forward_invert(fwd, df.data(), postings.data(), &kept, &st.invert_ms);
-    if (rc != NS_OK) err = ns_last_error(ctx);
-    ns_forward_destroy(fwd);
-    if (rc != NS_OK) return false;
+    if (!fetch_merged(ctx, fwd, m, st.invert_ms, err)) return false;
     st.call_s = std::chrono::duration<double>(clk::now() - t0).count();
-    uint64_t total_len = 0;
-    for (uint32_t v : doc_len) total_len += v;
-    const float avgdl = (float)total_len / (float)info.kept_docs;       // src/ForwardIndex.cpp:186
-    std::error_code ec;
-    const bool existed = fs::exists(out_seg, ec);
-    try {
-        fs::create_directories(out_seg, ec);
-        {
-            FileOut out(out_seg / "docs.bin");
-            out.u32(info.kept_docs);
-            for (const SourceSegment& s : sources) out.raw(s.doc_records.data(), s.doc_records.size());
-        }
-        { FileOut out(out_seg / "stats.bin"); out.u32(info.kept_docs); out.f32(avgdl); }
-        {
-            FileOut out(out_seg / "forward.bin");
-            out.u32(info.kept_docs);
-            size_t at = 0;
-            for (uint32_t j = 0; j < info.kept_docs; j++) {
-                out.u32(counts[j]);
-                out.raw(pairs.data() + at, (size_t)counts[j] * 8);
-                at += (size_t)counts[j] * 2;
-            }
-        }
-        {
-            FileOut out(out_seg / "terms.bin");
-            out.u32(info.n_terms);
-            for (uint32_t t = 0; t < info.n_terms; t++) {
-                out.u32((uint32_t)(toff[t + 1] - toff[t]));
-                out.raw(tbytes.data() + toff[t], (size_t)(toff[t + 1] - toff[t]));
-            }
-        }
-        write_barrels(out_seg, info.n_terms, df, postings,
-                      [&](uint32_t t) { return std::string((const char*)tbytes.data() + toff[t], (size_t)(toff[t + 1] - toff[t])); });
-    } catch (const std::exception& ex) {
-        err = ex.what();
-        if (!existed) fs::remove_all(out_seg, ec);
-        return false;
-    }
+    std::vector<std::pair<const uint8_t*, size_t>> records;
+    for (const SourceSegment& s : sources) records.emplace_back(s.doc_records.data(), s.doc_records.size());
+    if (!write_merged(out_seg, m, records, err)) return false;
     st.total_s = std::chrono::duration<double>(clk::now() - t0).count();
     return true;
 }

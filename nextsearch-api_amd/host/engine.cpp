@@ -337,6 +337,118 @@ bool Engine::compact(size_t first, size_t count, bool remove_sources, nsx::Compa
     return true;
 }
 
+bool Engine::find_documents(const std::vector<std::string>& uids, std::vector<std::pair<uint32_t, uint32_t>>& out) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    out.clear();
+    const std::unordered_set<std::string> wanted(uids.begin(), uids.end());
+    if (wanted.empty()) return true;
+    for (size_t i = 0; i < segments.size(); i++)
+        for (size_t d = 0; d < segments[i].cord_uid.size(); d++)
+            if (wanted.count(segments[i].cord_uid[d])) out.emplace_back((uint32_t)i, (uint32_t)d);
+    return true;
+}
+
+bool Engine::delete_documents(const std::vector<std::string>& uids, nsx::DeleteStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (stats) *stats = nsx::DeleteStats{};
+    if (device_ < 0) { err_ = "delete_documents: host-only engine (deleting runs on the device; there is no CPU path)"; return false; }
+    std::vector<std::pair<uint32_t, uint32_t>> hits;
+    find_documents(uids, hits);
+    std::unordered_set<std::string> missing(uids.begin(), uids.end());
+    for (const auto& h : hits) missing.erase(segments[h.first].cord_uid[h.second]);
+    nsx::DeleteStats st;
+    const bool ok = delete_by_id(hits, &st);
+    st.uids_not_found = (uint32_t)missing.size();
+    if (stats) *stats = st;
+    return ok;
+}
+
+bool Engine::delete_by_id(const std::vector<std::pair<uint32_t, uint32_t>>& seg_doc, nsx::DeleteStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    const auto t0 = std::chrono::steady_clock::now();
+    err_.clear();
+    if (stats) *stats = nsx::DeleteStats{};
+    if (device_ < 0) { err_ = "delete_documents: host-only engine (deleting runs on the device; there is no CPU path)"; return false; }
+    // ---- which documents stay, per touched segment (one bit per document; nothing is touched before this is complete) ----
+    std::vector<std::vector<uint32_t>> keep(segments.size());
+    std::vector<uint32_t> gone(segments.size(), 0);
+    nsx::DeleteStats st;
+    for (const auto& sd : seg_doc) {
+        if (sd.first >= segments.size() || sd.second >= segments[sd.first].cord_uid.size()) {
+            err_ = "delete_documents: (segment " + std::to_string(sd.first) + ", document " + std::to_string(sd.second) + ") is not in the index";
+            return false;
+        }
+        std::vector<uint32_t>& bits = keep[sd.first];
+        if (bits.empty()) bits.assign((segments[sd.first].cord_uid.size() + 31) / 32, 0xFFFFFFFFu);
+        uint32_t& w = bits[sd.second >> 5];
+        const uint32_t b = 1u << (sd.second & 31u);
+        if (w & b) { w &= ~b; gone[sd.first]++; st.docs_deleted++; }
+    }
+    if (st.docs_deleted == 0) return true;                                          // nothing matches: nothing touched
+    uint64_t left = 0;
+    for (size_t i = 0; i < segments.size(); i++) left += segments[i].cord_uid.size() - gone[i];
+    if (left == 0) { err_ = "delete_documents: the call would delete every document of the index (an index without a segment cannot be loaded)"; return false; }
+    const nsx::fs::path manifest = index_dir / "manifest.bin", segroot = index_dir / "segments";
+    std::error_code ec;
+    std::vector<std::string> segs = nsx::load_manifest(manifest);
+    if (segs.empty()) segs = seg_names;                                             // (an index without a manifest: the sorted scan reload() made)
+    if (segs != seg_names) { err_ = "delete_documents: manifest.bin names other segments than the engine serves (reload first)"; return false; }
+    ns_ctx* ctx = ctx_;
+    ns_ctx* own = nullptr;
+    if (!ctx) {
+        if (ns_ctx_create(device_, &own) != NS_OK) { err_ = std::string("ns_ctx_create: ") + ns_last_error(nullptr); return false; }
+        ctx = own;
+    }
+    // ---- every affected segment with a survivor, rewritten on its own into the next free name ----
+    std::vector<std::string> fresh, made, old;
+    bool ok = true;
+    uint32_t id = (uint32_t)segs.size();
+    for (size_t i = 0; i < segs.size() && ok; i++) {
+        if (!gone[i]) { fresh.push_back(segs[i]); continue; }
+        old.push_back(segs[i]);
+        if (gone[i] == segments[i].cord_uid.size()) { st.segments_dropped++; continue; }
+        nsx::SourceSegment src;
+        ok = nsx::load_source(segroot / segs[i], src, err_);
+        if (ok && src.doc_len.size() != segments[i].cord_uid.size()) { err_ = (segroot / segs[i]).string() + ": its document count differs from the loaded segment's"; ok = false; }
+        if (!ok) break;
+        while (nsx::fs::exists(segroot / nsx::seg_name(id), ec) || std::find(segs.begin(), segs.end(), nsx::seg_name(id)) != segs.end()) id++;
+        const std::string name = nsx::seg_name(id++);
+        made.push_back(name);                                                       // (removed again below if anything fails)
+        ok = nsx::rewrite_loaded(ctx, src, keep[i], segroot / name, st, err_);
+        if (ok) { fresh.push_back(name); st.segments_rewritten++; }
+    }
+    if (own) ns_ctx_destroy(own);
+    if (!ok) err_ = "delete_documents: " + err_;
+    if (ok) {
+        nsx::FileBytes fb;
+        const bool had_manifest = nsx::fs::exists(manifest, ec) && fb.load(manifest);
+        const std::vector<uint8_t> old_manifest = had_manifest ? fb.bytes() : std::vector<uint8_t>();
+        try {
+            nsx::save_manifest(manifest, fresh);
+        } catch (const std::exception& ex) { err_ = ex.what(); ok = false; }
+        if (ok && !reload()) ok = false;                                            // (err_ is reload's)
+        if (!ok) {   // the manifest as it was
+            const std::string why = err_;
+            if (had_manifest) { try { nsx::FileOut out(manifest); out.raw(old_manifest.data(), old_manifest.size()); } catch (...) {} }
+            else nsx::fs::remove(manifest, ec);
+            err_ = why;
+        }
+    }
+    if (!ok) {
+        for (const std::string& name : made) nsx::fs::remove_all(segroot / name, ec);
+        return false;
+    }
+    for (const std::string& name : old) {
+        std::error_code rec;
+        nsx::fs::remove_all(segroot / name, rec);
+        if (rec) err_ += (err_.empty() ? "delete_documents: could not remove " : "; ") + (segroot / name).string() + ": " + rec.message();
+    }
+    st.total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = st;
+    return true;
+}
+
 const std::vector<uint8_t>* Engine::raw_postings(uint32_t seg) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (seg >= segments.size()) return nullptr;

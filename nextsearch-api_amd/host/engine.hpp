@@ -28,6 +28,7 @@
 #include "../../include/nextsearch_hip.h"
 #include "forward_index.hpp"
 #include "compact.hpp"
+#include "purge.hpp"
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
@@ -108,6 +109,30 @@ public:
     // index it had.  The source directories are removed only after the reload succeeded and only with remove_sources; a
     // failure to remove one is reported in last_error() while the call returns true.  Needs a device (device < 0: fails).
     bool compact(size_t first = 0, size_t count = SIZE_MAX, bool remove_sources = true, nsx::CompactStats* stats = nullptr);
+    // Deleting (host/purge.hpp).  find_documents: every (manifest position, docId) of the index this engine
+    // serves whose docs.bin uid equals one of uids, ascending; host only (it reads what reload() loaded from docs.bin),
+    // so it works on a host-only engine too.  Always true; uids that match nothing simply add no pair.
+    bool find_documents(const std::vector<std::string>& uids, std::vector<std::pair<uint32_t, uint32_t>>& out);
+    // delete_documents: every document that carries a listed uid is deleted, in every segment; duplicates of a uid in the
+    // index all go.  A listed uid that matches nothing is counted in uids_not_found (once, however often it is listed) and
+    // is not an error; if nothing matches, the call succeeds and nothing is touched.
+    // delete_by_id: the same for (manifest position, docId) pairs.  A pair out of range is refused and nothing is touched;
+    // a pair listed twice counts once.
+    // Each affected segment is rewritten on its own into the next free seg_%06u — one ns_forward_merge_keep over the one
+    // source and one ns_forward_invert; docs.bin = the surviving records copied raw, stats.bin's avgdl as compaction
+    // computes it, the files written by compaction's writer — and the new segment takes the old one's place in the
+    // manifest.  Untouched segments are neither read nor rewritten.  A segment with no survivor is dropped from the manifest
+    // and the later positions move up.  THE SURVIVORS OF A REWRITTEN SEGMENT GET NEW docIds, their positions among the
+    // survivors: the uid is the stable handle of a document, a (position, docId) pair is good until the next delete or
+    // compaction.  Term ids are renumbered too; no search result depends on them.
+    // All or nothing like compact: the manifest is written once, after every new segment is complete, then reload() runs
+    // (which rebuilds autocomplete's table and empties the search cache); on any failure the manifest keeps its bytes, every
+    // new directory is removed and the engine keeps answering from the index it had.  The old directories are removed only
+    // after the reload succeeded; a failure to remove one is reported in last_error() while the call returns true.
+    // A call that would delete every document of the index fails and touches nothing (an index without a segment cannot be
+    // loaded).  Needs a device (device < 0: fails, and says so).  stats may be null.
+    bool delete_documents(const std::vector<std::string>& uids, nsx::DeleteStats* stats = nullptr);
+    bool delete_by_id(const std::vector<std::pair<uint32_t, uint32_t>>& seg_doc, nsx::DeleteStats* stats = nullptr);
     // Optional: per-posting term scores for every list of every lexicon, built on the device
     // (ns_segment_build_impacts); searches then read {docId, score} instead of {docId, tf} + norm.  Same results.
     bool build_impacts();

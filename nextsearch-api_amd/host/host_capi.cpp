@@ -416,6 +416,55 @@ extern "C" int nsh_engine_compact(nsh_engine* e, uint64_t first, uint64_t count,
 } NSH_CATCH(e, "nsh_engine_compact", -1)
 }
 
+// Deleting (host/purge.hpp)
+static void put_dstats(nsh_delete_stats* out, const nsx::DeleteStats& st) {
+    if (!out || out->struct_size < 4) return;
+    nsh_delete_stats t{};
+    t.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(t));
+    t.segments_rewritten = st.segments_rewritten; t.segments_dropped = st.segments_dropped; t.docs_deleted = st.docs_deleted;
+    t.uids_not_found = st.uids_not_found; t.terms_dropped = st.terms_dropped;
+    t.pairs_in = st.pairs_in; t.pairs_out = st.pairs_out; t.device_bytes = st.device_bytes;
+    t.merge_ms = st.merge_ms; t.invert_ms = st.invert_ms; t.call_s = st.call_s; t.total_s = st.total_s;
+    std::memcpy(out, &t, t.struct_size);
+}
+static std::vector<std::string> to_uids(const char* bytes, const uint64_t* offsets, uint32_t n) {
+    std::vector<std::string> out(n);
+    for (uint32_t i = 0; i < n; i++) out[i].assign(bytes + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return out;
+}
+extern "C" int64_t nsh_engine_find_documents(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_uids,
+                                             uint32_t* seg_doc_out, uint64_t capacity) { try {
+    if (!e) return -1;
+    if (n_uids && (!bytes || !offsets)) { nsh_set_err(e, "nsh_engine_find_documents: null argument"); return -1; }
+    std::vector<std::pair<uint32_t, uint32_t>> hits;
+    e->eng.find_documents(to_uids(bytes, offsets, n_uids), hits);
+    for (size_t i = 0; seg_doc_out && i < hits.size() && i < capacity; i++) { seg_doc_out[2 * i] = hits[i].first; seg_doc_out[2 * i + 1] = hits[i].second; }
+    return (int64_t)hits.size();
+} NSH_CATCH(e, "nsh_engine_find_documents", -1)
+}
+extern "C" int nsh_engine_delete_documents(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_uids, nsh_delete_stats* stats) { try {
+    if (!e) return -1;
+    if (n_uids && (!bytes || !offsets)) { nsh_set_err(e, "nsh_engine_delete_documents: null argument"); return -1; }
+    nsx::DeleteStats st;
+    const bool ok = e->eng.delete_documents(to_uids(bytes, offsets, n_uids), &st);
+    put_dstats(stats, st);
+    nsh_set_err(e, e->eng.last_error());                                       // (success: empty, or the directories that could not be removed)
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_delete_documents", -1)
+}
+extern "C" int nsh_engine_delete_by_id(nsh_engine* e, const uint32_t* seg_doc, uint64_t n_pairs, nsh_delete_stats* stats) { try {
+    if (!e) return -1;
+    if (n_pairs && !seg_doc) { nsh_set_err(e, "nsh_engine_delete_by_id: null argument"); return -1; }
+    std::vector<std::pair<uint32_t, uint32_t>> ids((size_t)n_pairs);
+    for (size_t i = 0; i < ids.size(); i++) ids[i] = {seg_doc[2 * i], seg_doc[2 * i + 1]};
+    nsx::DeleteStats st;
+    const bool ok = e->eng.delete_by_id(ids, &st);
+    put_dstats(stats, st);
+    nsh_set_err(e, e->eng.last_error());
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_delete_by_id", -1)
+}
+
 // Semantic expansion (src/api_engine.cpp:409-417): rows/dim of the loaded embedding table (0/0: none), and the
 // weighted terms a query is scored with, one "term<TAB>fp32 weight bits in hex" line each, in scoring order.
 extern "C" int nsh_engine_semantic_info(nsh_engine* e, uint32_t* rows, uint32_t* dim) { try {

@@ -7,6 +7,9 @@
 //        `forwardindex` from the extracted text onwards (forward_index.hpp) and `lexicon` (invert.hpp).  One JSON line.
 //   ns_tool compact <index_dir> [first count]             (needs an MI355X)
 //        Engine::compact: the manifest's segments [first, first + count) (default: all) become one (compact.hpp).  One JSON line.
+//   ns_tool delete <index_dir> <uid>...                   (needs an MI355X)
+//        Engine::delete_documents: every document that carries one of the uids goes; the segments that lose documents are
+//        rewritten on the device (purge.hpp).  One JSON line.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -62,6 +65,19 @@ int main(int argc, char** argv) {
         if (!eng.last_error().empty()) std::fprintf(stderr, "%s\n", eng.last_error().c_str());
         std::printf("{\"sources\": %u, \"docs\": %u, \"terms_in\": %llu, \"terms\": %u, \"pairs\": %llu, \"merge_ms\": %.3f, \"invert_ms\": %.3f, \"call_s\": %.4f, \"total_s\": %.4f, \"segments\": %zu}\n",
                     st.sources, st.n_docs, (unsigned long long)st.terms_in, st.n_terms, (unsigned long long)st.pairs, st.merge_ms, st.invert_ms, st.call_s, st.total_s, eng.segments.size());
+        return 0;
+    }
+    if (argc >= 4 && std::strcmp(argv[1], "delete") == 0) {
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        std::vector<std::string> uids(argv + 3, argv + argc);
+        nsx::DeleteStats st;
+        if (!eng.delete_documents(uids, &st)) { std::fprintf(stderr, "delete failed: %s\n", eng.last_error().c_str()); return 1; }
+        if (!eng.last_error().empty()) std::fprintf(stderr, "%s\n", eng.last_error().c_str());
+        std::printf("{\"docs_deleted\": %u, \"uids_not_found\": %u, \"segments_rewritten\": %u, \"segments_dropped\": %u, \"terms_dropped\": %u, \"pairs_in\": %llu, \"pairs_out\": %llu, \"merge_ms\": %.3f, \"invert_ms\": %.3f, \"call_s\": %.4f, \"total_s\": %.4f, \"segments\": %zu}\n",
+                    st.docs_deleted, st.uids_not_found, st.segments_rewritten, st.segments_dropped, st.terms_dropped, (unsigned long long)st.pairs_in, (unsigned long long)st.pairs_out,
+                    st.merge_ms, st.invert_ms, st.call_s, st.total_s, eng.segments.size());
         return 0;
     }
     if (argc >= 4 && std::strcmp(argv[1], "index") == 0) {
@@ -138,6 +154,6 @@ int main(int argc, char** argv) {
                     Q, K, refs.size(), reload_ms, p, p > 0 ? Q / (p * 1e-3) : 0.0, f, f > 0 ? Q / (f * 1e-3) : 0.0, reps, (unsigned long long)check);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n", argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
 }

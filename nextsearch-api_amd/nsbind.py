@@ -64,6 +64,7 @@ HIP_SYMBOLS = [
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
     "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort",
+    "ns_forward_merge_keep",
 ]
 HOST_SYMBOLS = [
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -76,6 +77,7 @@ HOST_SYMBOLS = [
     "nsh_engine_suggest_json", "nsh_engine_suggest_batch", "nsh_engine_suggest_table", "nsh_suggest_split", "nsh_suggest_clamp_limit",
     "nsh_index_documents", "nsh_index_error", "nsh_engine_open_noload", "nsh_engine_add_documents",
     "nsh_merge_segments", "nsh_compact_error", "nsh_engine_compact",
+    "nsh_engine_find_documents", "nsh_engine_delete_documents", "nsh_engine_delete_by_id",
 ]
 
 class NsForwardInfo(C.Structure):   # include/nextsearch_hip.h ns_forward_info
@@ -101,6 +103,16 @@ class NsForwardSrc(C.Structure):   # include/nextsearch_hip.h ns_forward_src
 class NshCompactStats(C.Structure):   # include/nextsearch_host.h nsh_compact_stats
     _fields_ = [("struct_size", C.c_uint32), ("sources", C.c_uint32), ("n_docs", C.c_uint32), ("n_terms", C.c_uint32),
                 ("terms_in", C.c_uint64), ("pairs", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("merge_ms", C.c_float), ("invert_ms", C.c_float), ("call_s", C.c_double), ("total_s", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class NshDeleteStats(C.Structure):   # include/nextsearch_host.h nsh_delete_stats
+    _fields_ = [("struct_size", C.c_uint32), ("segments_rewritten", C.c_uint32), ("segments_dropped", C.c_uint32), ("docs_deleted", C.c_uint32),
+                ("uids_not_found", C.c_uint32), ("terms_dropped", C.c_uint32),
+                ("pairs_in", C.c_uint64), ("pairs_out", C.c_uint64), ("device_bytes", C.c_uint64),
                 ("merge_ms", C.c_float), ("invert_ms", C.c_float), ("call_s", C.c_double), ("total_s", C.c_double)]
 
     def as_dict(self):
@@ -176,6 +188,7 @@ def hip_lib():
         L.ns_compact_doc_cut.argtypes = []
         L.ns_compact_doc_cut.restype = u32
         L.ns_ctx_use_docsort.argtypes = [vp, i32]
+        L.ns_forward_merge_keep.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -257,6 +270,10 @@ def host_lib():
         L.nsh_merge_segments.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, i32, C.POINTER(NshCompactStats)]
         L.nsh_compact_error.restype = C.c_char_p
         L.nsh_engine_compact.argtypes = [vp, u64, u64, i32, C.POINTER(NshCompactStats)]
+        L.nsh_engine_find_documents.argtypes = [vp, C.c_char_p, vp, u32, vp, u64]
+        L.nsh_engine_find_documents.restype = C.c_int64
+        L.nsh_engine_delete_documents.argtypes = [vp, C.c_char_p, vp, u32, C.POINTER(NshDeleteStats)]
+        L.nsh_engine_delete_by_id.argtypes = [vp, vp, u64, C.POINTER(NshDeleteStats)]
         L.nsh_engine_set_cache.argtypes = [vp, i32]
         L.nsh_engine_set_cache.restype = None
         L.nsh_engine_cache_size.argtypes = [vp]
@@ -426,6 +443,45 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"Engine.compact failed: {self.error()}")
         return st.as_dict()
+
+    def find_documents(self, uids):
+        """Engine::find_documents: [(manifest position, docId)] of every document whose uid is listed, ascending; host only."""
+        blob, offs = _flat_bytes(uids)
+        cap = 64
+        while True:   # one call fills the array and returns the number of matches; more matches than capacity: again, that large
+            out = np.zeros((cap, 2), dtype=np.uint32)
+            n = self._L.nsh_engine_find_documents(self.h, blob, offs.ctypes.data, len(offs) - 1, out.ctypes.data, cap)
+            if n < 0:
+                raise RuntimeError(f"Engine.find_documents failed: {self.error()}")
+            if n <= cap:
+                return [(int(s), int(d)) for s, d in out[:n]]
+            cap = int(n)
+
+    def _deleted(self, rc, st, old_ctx, what):
+        if _ctx_key(self.ctx) != _ctx_key(old_ctx):
+            _LIVE_BATCHES.pop(_ctx_key(old_ctx), None)
+        if rc != 0:
+            raise RuntimeError(f"Engine.{what} failed: {self.error()}")
+        return st.as_dict()
+
+    def delete_documents(self, uids):
+        """Engine::delete_documents: every document that carries a listed uid goes, in every segment; each affected segment
+        is rewritten on the device and takes its old place in the manifest, the engine reloads.  The survivors of a
+        rewritten segment get new docIds: the uid is the stable handle.  Returns the stats (uids_not_found among them);
+        self.error() afterwards names an old directory that could not be removed."""
+        blob, offs = _flat_bytes(uids)
+        st = NshDeleteStats(struct_size=C.sizeof(NshDeleteStats))
+        old_ctx = self.ctx
+        rc = self._L.nsh_engine_delete_documents(self.h, blob, offs.ctypes.data, len(offs) - 1, C.byref(st))
+        return self._deleted(rc, st, old_ctx, "delete_documents")
+
+    def delete_by_id(self, seg_doc):
+        """Engine::delete_by_id: the same for (manifest position, docId) pairs; a pair out of range is refused."""
+        ids = np.ascontiguousarray(np.asarray(list(seg_doc), dtype=np.uint32).reshape(-1, 2))
+        st = NshDeleteStats(struct_size=C.sizeof(NshDeleteStats))
+        old_ctx = self.ctx
+        rc = self._L.nsh_engine_delete_by_id(self.h, ids.ctypes.data, len(ids), C.byref(st))
+        return self._deleted(rc, st, old_ctx, "delete_by_id")
 
     def close(self):
         if self.h:
@@ -778,6 +834,39 @@ def forward_sources(parts):
     return arr, keep
 
 
+def keep_bitmaps(keeps):
+    """keeps: per part None, a boolean array over its documents or a ready uint32 bitmap (handed over as it is) -> (array of
+    pointers for ns_forward_merge_keep, keep-alive list); bit d & 31 of word d >> 5 is document d"""
+    arr = (C.c_void_p * max(1, len(keeps)))()
+    alive = []
+    for i, k in enumerate(keeps):
+        if k is None:
+            continue
+        k = np.asarray(k)
+        if k.dtype == np.uint32:
+            words = np.ascontiguousarray(k)
+        else:
+            packed = np.packbits(k.astype(bool), bitorder="little")
+            words = np.zeros((len(k) + 31) // 32 + 1, dtype=np.uint32)
+            words.view(np.uint8)[:len(packed)] = packed
+        alive.append(words)
+        arr[i] = words.ctypes.data
+    return arr, alive
+
+
+def forward_merge_keep(ctx, parts, keeps, invert=False):
+    """Raw ns_forward_merge_keep + fetch (+ ns_forward_invert) like forward_merge; keeps as keep_bitmaps takes them (None:
+    the part passes through); keeps None: the NULL bitmap list."""
+    L = hip_lib()
+    arr, alive = forward_sources(parts)
+    bits, alive2 = keep_bitmaps(keeps) if keeps is not None else (None, [])
+    h = C.c_void_p()
+    rc = L.ns_forward_merge_keep(ctx, arr, bits, len(parts), C.byref(h))
+    if rc != NS_OK:
+        raise RuntimeError(f"ns_forward_merge_keep: {rc}: {L.ns_last_error(ctx).decode()}")
+    return _fetched(L, ctx, h, invert)
+
+
 def forward_merge(ctx, parts, invert=False):
     """Raw ns_forward_merge + fetch (+ ns_forward_invert: adds df, postings[kept, 2], invert_ms) over parts in
     forward_build's form; raises RuntimeError with the library's message when the merge is refused."""
@@ -787,6 +876,10 @@ def forward_merge(ctx, parts, invert=False):
     rc = L.ns_forward_merge(ctx, arr, len(parts), C.byref(h))
     if rc != NS_OK:
         raise RuntimeError(f"ns_forward_merge: {rc}: {L.ns_last_error(ctx).decode()}")
+    return _fetched(L, ctx, h, invert)
+
+
+def _fetched(L, ctx, h, invert):
     try:
         out = _fetch_forward(L, ctx, h)
         if invert:
