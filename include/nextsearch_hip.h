@@ -284,6 +284,30 @@ int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes, const uin
                   uint32_t* idx_out, uint32_t* count_out, float* device_ms_out);
 int ns_ac_release(ns_ctx* ctx, ns_ac* ac);
 
+/* Spelling correction over the same table (csrc/ns_fuzzy.hip): for each query term the L best CANDIDATES
+ * within a bounded edit distance.
+ *   candidates  the table's entries whose score is not 0 and whose bytes differ from their predecessor's (of a run of equal
+ *               strings only the first)
+ *   distance    optimal string alignment over bytes (Levenshtein + transposition of two adjacent bytes, no substring
+ *               edited twice: d("ab","ba") = 1, d("ca","abc") = 3), at most max_edits[q] (0, 1 or 2; more: NS_E_INVAL)
+ *   prefix      with p = min(prefix_len, length of the query term) a candidate shares its first p bytes with the term
+ *   order       distance ascending, then score descending, then index ascending: a strict total order, so two calls return
+ *               equal bytes
+ * ns_ac_build_fuzzy builds the side structures once per table (the candidates ordered by length with a byte-set
+ * signature each: 12 B per candidate); it is idempotent, fails with NS_E_INVAL for a table of 2^30 terms or more, and
+ * leaves ns_ac_suggest's answers as they were.  *device_ms_out (may be NULL): the kernels' time, 0 when already built.
+ * ns_ac_fuzzy: term q = term_bytes[term_offsets[q] .. term_offsets[q + 1]) (host, raw bytes: the caller normalises).  L is
+ * clamped to 1..10 and the rows have the clamped width: idx_out[q * L + r] = table index of the r-th answer (~0u past
+ * count_out[q]), dist_out[q * L + r] = its distance (0xff past the end).  An empty term or one longer than
+ * NS_FUZZY_MAX_LEN bytes gets count 0 and is not sent to the device.  Synchronous; staged through the ctx's pinned
+ * buffers.  NS_E_STATE before ns_ac_build_fuzzy.  ns_ac_release frees the side structures with the table. */
+#define NS_FUZZY_MAX_LEN   64u
+#define NS_FUZZY_MAX_EDITS 2u
+int ns_ac_build_fuzzy(ns_ctx* ctx, ns_ac* ac, float* device_ms_out);
+int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets, uint32_t n_q,
+                const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                uint32_t* count_out, float* device_ms_out);
+
 /* Segment-sharded multi-GPU (the alternative to query sharding for an index that outgrows one
  * GPU's HBM): rank r holds a subset of the segments and scores ALL queries over it; the fixed-size per-rank rows
  * are all-gathered rank-major (hits [n_ranks][n_queries][k], nhits and found [n_ranks][n_queries]) and joined here

@@ -234,6 +234,26 @@ uint64_t nsh_suggest_split(const char* input, uint64_t input_len, uint64_t* base
 /* The limit clamp of Engine::suggest (src/api_engine.cpp:171): 1..10. */
 int nsh_suggest_clamp_limit(int limit);
 
+/* Spelling correction ("did you mean") over the suggest table, on the primary device.  The first call after
+ * a reload builds the corrector's side structures (nsh_engine_correct_build_ms: that build's time, 0 before it).
+ * nsh_engine_correct_batch: term q = bytes[offsets[q] .. offsets[q + 1]), normalised like the table's terms (ASCII alnum
+ * bytes, lower-cased).  With L = clamp(limit, 1, 10): term_idx[q * L + r] = suggest-table row of the r-th best candidate
+ * (~0u past count[q]), dist[q * L + r] = its distance (0xff past the end).  Candidates: rows with a score above 0, of equal
+ * strings the first; distance: optimal string alignment over bytes, at most max_edits (0..2, or -1 = auto:
+ * nsh_correct_auto_edits of the normalised length); with p = min(prefix_len, length) a candidate shares the term's first p
+ * bytes; order: distance, score descending, row ascending.  A term that normalises to nothing or to more than 64 bytes
+ * gets count 0.  -1 without a device context, for max_edits above 2, or on failure. */
+int nsh_engine_correct_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_terms, int limit,
+                             int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist, uint32_t* count, float* device_ms);
+/* Engine::did_you_mean(query, limit): *json_out receives {"changed", "corrected", "query", "terms"} in dump(2) layout
+ * (free with nsh_free).  "terms" lists the query's alnum runs without stop words and one-byte tokens: "known" = the term
+ * dictionary holds it (no suggestions), else its best L with auto edits and no prefix; "corrected" = the query with each
+ * unknown token that has a suggestion replaced by the best one, every other byte kept. */
+int nsh_engine_did_you_mean_json(nsh_engine* e, const char* query, uint64_t query_len, int limit, char** json_out);
+/* The auto rule: under 3 bytes 0 edits, 3..5 one, above 5 two. */
+int nsh_correct_auto_edits(uint64_t normalized_len);
+double nsh_engine_correct_build_ms(nsh_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

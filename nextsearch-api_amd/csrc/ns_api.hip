@@ -27,6 +27,7 @@
 #include "ns_delete.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
+#include "ns_fuzzy.hip"
 
 using namespace ns;
 
@@ -2465,6 +2466,13 @@ struct ns_ac {
     uint64_t* d_heads = nullptr;   // first 8 bytes of each term, big-endian, zero-padded
     uint64_t* d_keys = nullptr;    // (~score << 32) | index: the scores live here
     uint64_t* d_tree = nullptr;    // levels back to back, kAcTop keys per node
+    // the spelling corrector's side structures (ns_ac_build_fuzzy, csrc/ns_fuzzy.hip); absent until asked for
+    bool fz_built = false;
+    uint32_t fz_cands = 0;                       // candidates = slots of the permutation
+    uint32_t* d_fz_perm = nullptr;               // candidates ordered by (length, index)
+    uint64_t* d_fz_sig = nullptr;                // their signatures, in the same order
+    uint32_t* d_fz_len_start = nullptr;          // kFzBuckets + 1: first slot of each length
+    uint32_t fz_len_start[kFzBuckets + 1] = {};  // the same on the host: sizes a query's slices
 };
 
 static void ac_free(ns_ac* ac) {
@@ -2474,6 +2482,9 @@ static void ac_free(ns_ac* ac) {
     (void)hipFree(ac->d_heads);
     (void)hipFree(ac->d_keys);
     (void)hipFree(ac->d_tree);
+    (void)hipFree(ac->d_fz_perm);
+    (void)hipFree(ac->d_fz_sig);
+    (void)hipFree(ac->d_fz_len_start);
     delete ac;
 }
 static void ac_free_fwd(ns_ac* ac) { ac_free(ac); }
@@ -2644,6 +2655,233 @@ extern "C" int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_suggest: %s", hipGetErrorString(e));
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Spelling correction (csrc/ns_fuzzy.hip): the side structures of a table, and the batched bounded-distance top-L.
+extern "C" int ns_ac_build_fuzzy(ns_ctx* ctx, ns_ac* ac, float* device_ms_out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_build_fuzzy: ctx is NULL");
+    if (!ac || std::find(ctx->acs.begin(), ctx->acs.end(), ac) == ctx->acs.end())
+        return fail(ctx, NS_E_INVAL, "ns_ac_build_fuzzy: table does not belong to this ctx");
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (ac->fz_built) return NS_OK;
+    if (ac->n >= (1u << kFzIdxBits)) return fail(ctx, NS_E_INVAL, "ns_ac_build_fuzzy: %u terms (the ranking key holds 30 index bits)", ac->n);
+    if (ac->n == 0) { ac->fz_built = true; return NS_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t n = ac->n, n_blocks = (n + kFzChunk - 1) / kFzChunk;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    uint32_t* d_hist = nullptr;
+    uint32_t *d_perm = nullptr, *d_len_start = nullptr;
+    uint64_t* d_sig = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint32_t len_start[kFzBuckets + 1] = {};
+    chk(hipMalloc((void**)&d_hist, (size_t)kFzBuckets * n_blocks * 4));
+    chk(hipMalloc((void**)&d_len_start, sizeof(len_start)));
+    if (e == hipSuccess && device_ms_out) { chk(hipEventCreate(&ev0)); chk(hipEventCreate(&ev1)); }
+    if (e == hipSuccess) {
+        if (ev0) chk(hipEventRecord(ev0, st));
+        hipLaunchKernelGGL(k_fz_build_count, dim3(n_blocks), dim3(64), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, n, d_hist, n_blocks);
+        chk(hipGetLastError());
+        hipLaunchKernelGGL(k_fz_build_scan, dim3(1), dim3(128), 0, st, d_hist, n_blocks, d_len_start);
+        chk(hipGetLastError());
+        chk(hipMemcpyAsync(len_start, d_len_start, sizeof(len_start), hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));   // the number of candidates sizes the permutation
+    }
+    const uint32_t cands = len_start[kFzBuckets];
+    if (e == hipSuccess && cands > n) e = hipErrorUnknown;
+    if (e == hipSuccess) {
+        chk(hipMalloc((void**)&d_perm, std::max<size_t>((size_t)cands * 4, 4)));
+        chk(hipMalloc((void**)&d_sig, std::max<size_t>((size_t)cands * 8, 8)));
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_fz_build_scatter, dim3(n_blocks), dim3(64), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, n, d_hist, n_blocks,
+                           d_len_start, d_perm, d_sig);
+        chk(hipGetLastError());
+        if (ev1) chk(hipEventRecord(ev1, st));
+        chk(hipStreamSynchronize(st));
+    }
+    if (e == hipSuccess) {
+        float ms = 0.0f;
+        if (ev0 && ev1 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+    }
+    (void)hipFree(d_hist);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) {
+        (void)hipFree(d_perm);
+        (void)hipFree(d_sig);
+        (void)hipFree(d_len_start);
+        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_build_fuzzy: %s", hipGetErrorString(e));
+    }
+    ac->d_fz_perm = d_perm;
+    ac->d_fz_sig = d_sig;
+    ac->d_fz_len_start = d_len_start;
+    std::memcpy(ac->fz_len_start, len_start, sizeof(len_start));
+    ac->fz_cands = cands;
+    ac->fz_built = true;
+    return NS_OK;
+}
+
+// Measurement knobs of ns_ac_fuzzy (tools/correct_bench.py's A/B; process-wide, never set by the product):
+//   NS_FUZZY_NO_SIG=1    the signature filter passes everything
+static bool fz_env_flag(const char* name) {
+    const char* v = std::getenv(name);
+    return v && v[0] == '1';
+}
+
+extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets, uint32_t n_q,
+                           const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                           uint32_t* count_out, float* device_ms_out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_fuzzy: ctx is NULL");
+    if (!ac || std::find(ctx->acs.begin(), ctx->acs.end(), ac) == ctx->acs.end())
+        return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: table does not belong to this ctx");
+    if (!ac->fz_built) return fail(ctx, NS_E_STATE, "ns_ac_fuzzy: ns_ac_build_fuzzy has not been called on this table");
+    L = std::max(1u, std::min(L, (uint32_t)kAcTop));
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (!n_q) return NS_OK;
+    if (!term_offsets || !max_edits || !idx_out || !dist_out || !count_out) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: null argument");
+    for (uint32_t q = 0; q < n_q; q++) {
+        if (term_offsets[q + 1] < term_offsets[q]) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: term offsets decrease at %u", q);
+        if (max_edits[q] > kFzMaxEdits) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: max_edits[%u] = %u above %d", q, max_edits[q], kFzMaxEdits);
+    }
+    if (term_offsets[n_q] != term_offsets[0] && !term_bytes) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: term_bytes is NULL");
+    std::fill(idx_out, idx_out + (size_t)n_q * L, ~0u);
+    std::fill(dist_out, dist_out + (size_t)n_q * L, (uint8_t)0xff);
+    std::fill(count_out, count_out + n_q, 0u);
+    // the terms that can match something: 1..64 bytes, and some candidate inside the length window
+    std::vector<uint32_t> rows, window;
+    size_t n_bytes = 0;
+    for (uint32_t q = 0; q < n_q && ac->fz_cands; q++) {
+        const uint32_t len = term_offsets[q + 1] - term_offsets[q], e = max_edits[q];
+        if (len == 0 || len > (uint32_t)kFzMaxLen) continue;
+        const uint32_t w = ac->fz_len_start[len + e + 1] - ac->fz_len_start[len > e ? len - e : 0];
+        if (!w) continue;
+        rows.push_back(q);
+        window.push_back(w);
+        n_bytes += len;
+    }
+    const uint32_t R = (uint32_t)rows.size();
+    if (!R) return NS_OK;
+    // slice size: 1024 candidates per workgroup, doubled while the launch would exceed 65536 workgroups
+    uint32_t slice = 1024;
+    uint64_t n_slices = 0;
+    for (;; slice *= 2) {
+        n_slices = 0;
+        for (uint32_t w : window) n_slices += (w + slice - 1) / slice;
+        if (n_slices <= 65536 || slice >= (1u << 30)) break;
+    }
+    if (n_slices >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: %llu slices in one call", (unsigned long long)n_slices);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // device block: [term offsets (R + 1) | slice bases (R + 1) | signatures R | edits R | term bytes] go up in one copy through
+    // the ctx's pinned upload buffer; [plans | slice lists] stay on the device; [idx R x L | counts R | dist R x L] come
+    // down in one copy through its pinned result buffer
+    auto al8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    const size_t o_base = al8((size_t)(R + 1) * 4), o_sig = o_base + al8((size_t)(R + 1) * 4), o_ed = o_sig + (size_t)R * 8;
+    const size_t o_bytes = o_ed + al8(R);
+    const size_t up = o_bytes + n_bytes;
+    const size_t o_plan = (up + 255) & ~(size_t)255;
+    const size_t o_part = o_plan + (((size_t)R * sizeof(FzPlan) + 255) & ~(size_t)255);
+    const size_t o_idx = o_part + (size_t)n_slices * kAcTop * 8;
+    const size_t down = (size_t)R * L * 4 + (size_t)R * 4 + (size_t)R * L;
+    const size_t block_bytes = o_idx + down;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (ctx->up_busy) {   // a batch's upload may still be reading the staging buffer
+        chk(hipEventSynchronize(ctx->up_done));
+        ctx->up_busy = false;
+    }
+    if (e == hipSuccess && up <= kStageMaxBytes && ctx->h_up_cap < up) {
+        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
+        ctx->h_up = nullptr; ctx->h_up_cap = 0;
+        const size_t cap = std::max<size_t>(up + up / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
+        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
+    }
+    const bool down_pinned = !ctx->down_owner && down <= kStageMaxBytes;
+    if (e == hipSuccess && down_pinned && ctx->h_down_cap < down) {
+        if (ctx->h_down) (void)hipHostFree(ctx->h_down);
+        ctx->h_down = nullptr; ctx->h_down_cap = 0;
+        const size_t cap = std::max<size_t>(down + down / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_down, cap, hipHostMallocDefault) == hipSuccess) ctx->h_down_cap = cap;
+        else { ctx->h_down = nullptr; (void)hipGetLastError(); }
+    }
+    std::vector<char> up_own, down_own;
+    char* hu = (ctx->h_up_cap >= up) ? (char*)ctx->h_up : (up_own.resize(up), up_own.data());
+    char* hd = (down_pinned && ctx->h_down_cap >= down) ? (char*)ctx->h_down : (down_own.resize(down), down_own.data());
+    {
+        uint32_t* h_offs = (uint32_t*)hu;
+        uint32_t* h_base = (uint32_t*)(hu + o_base);
+        uint64_t* h_sig = (uint64_t*)(hu + o_sig);
+        uint8_t* h_ed = (uint8_t*)(hu + o_ed);
+        uint8_t* h_bytes = (uint8_t*)(hu + o_bytes);
+        uint32_t at = 0, sl = 0;
+        for (uint32_t r = 0; r < R; r++) {
+            const uint32_t q = rows[r], len = term_offsets[q + 1] - term_offsets[q];
+            const uint8_t* t = term_bytes + term_offsets[q];
+            h_offs[r] = at;
+            h_base[r] = sl;
+            h_ed[r] = max_edits[q];
+            uint64_t sig = 0;
+            for (uint32_t j = 0; j < len; j++) {
+                const uint8_t c = t[j];
+                h_bytes[at + j] = c;
+                sig |= (c >= '0' && c <= '9') ? 1ull << (c - '0') : (c >= 'a' && c <= 'z') ? 1ull << (10 + c - 'a') : 1ull << 36;
+            }
+            h_sig[r] = sig;
+            at += len;
+            sl += (window[r] + slice - 1) / slice;
+        }
+        h_offs[R] = at;
+        h_base[R] = sl;
+    }
+    char* blk = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (e == hipSuccess) chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    if (e == hipSuccess && device_ms_out) { chk(hipEventCreate(&ev0)); chk(hipEventCreate(&ev1)); }
+    if (e == hipSuccess) {
+        const uint32_t use_sig = fz_env_flag("NS_FUZZY_NO_SIG") ? 0u : 1u;
+        const uint32_t* d_offs = (const uint32_t*)blk;
+        const uint32_t* d_base = (const uint32_t*)(blk + o_base);
+        const uint8_t* d_ed = (const uint8_t*)(blk + o_ed);
+        uint32_t* d_idx = (uint32_t*)(blk + o_idx);
+        uint32_t* d_cnt = d_idx + (size_t)R * L;
+        uint8_t* d_dist = (uint8_t*)(d_cnt + R);
+        chk(hipMemcpyAsync(blk, hu, up, hipMemcpyHostToDevice, st));
+        if (ev0) chk(hipEventRecord(ev0, st));
+        hipLaunchKernelGGL(k_fz_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
+                           ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FzPlan*)(blk + o_plan));
+        chk(hipGetLastError());
+        hipLaunchKernelGGL(k_fz_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
+                           ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
+                           (const FzPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
+        chk(hipGetLastError());
+        hipLaunchKernelGGL(k_fz_select, dim3((R + 3) / 4), dim3(256), 0, st, (const uint64_t*)(blk + o_part), d_base, R, L, d_idx, d_dist, d_cnt);
+        chk(hipGetLastError());
+        if (ev1) chk(hipEventRecord(ev1, st));
+        chk(hipMemcpyAsync(hd, blk + o_idx, down, hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));
+    }
+    if (e == hipSuccess) {
+        const uint32_t* h_idx = (const uint32_t*)hd;
+        const uint32_t* h_cnt = h_idx + (size_t)R * L;
+        const uint8_t* h_dist = (const uint8_t*)(h_cnt + R);
+        for (uint32_t r = 0; r < R; r++) {
+            const size_t q = rows[r];
+            count_out[q] = h_cnt[r];
+            std::memcpy(idx_out + q * L, h_idx + (size_t)r * L, (size_t)L * 4);
+            std::memcpy(dist_out + q * L, h_dist + (size_t)r * L, L);
+        }
+        float ms = 0.0f;
+        if (ev0 && ev1 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_fuzzy: %s", hipGetErrorString(e));
     return NS_OK;
 }
 

@@ -121,6 +121,36 @@ __device__ __forceinline__ uint32_t ac_search(uint32_t a, uint32_t b, int thr, u
     return a;
 }
 
+// [lo, hi): the index range of the terms that start with p (one wave; every lane gets both ends).  One search for both
+// ends while their ranges coincide, then one each.  Shared by k_ac_suggest and the spelling corrector's k_fz_plan.
+__device__ __forceinline__ void ac_prefix_range(uint32_t n, uint32_t lane, const uint64_t* __restrict__ heads,
+                                                const uint32_t* __restrict__ offs, const uint8_t* __restrict__ pool,
+                                                const uint8_t* __restrict__ p, uint32_t plen, uint64_t ph, uint64_t mask,
+                                                uint32_t& lo, uint32_t& hi) {
+    uint32_t a = 0, b = n;
+    bool split = false;
+    uint32_t alo = 0, blo = 0, ahi = 0, bhi = 0;
+    while (b > a) {
+        const uint32_t s = (b - a + 63) / 64;
+        const uint64_t piv = (uint64_t)a + (uint64_t)(lane + 1) * s - 1;
+        const int c = piv < b ? ac_cmp((uint32_t)piv, heads, offs, pool, p, plen, ph, mask) : 1;
+        const uint32_t mlo = ac_first_false_count(c >= 0), mhi = ac_first_false_count(c > 0);
+        if (mlo != mhi) {
+            alo = a; blo = b; ac_narrow(alo, blo, s, mlo);
+            ahi = a; bhi = b; ac_narrow(ahi, bhi, s, mhi);
+            split = true;
+            break;
+        }
+        ac_narrow(a, b, s, mlo);
+    }
+    if (split) {
+        lo = ac_search(alo, blo, 0, lane, heads, offs, pool, p, plen, ph, mask);
+        hi = ac_search(ahi, bhi, 1, lane, heads, offs, pool, p, plen, ph, mask);
+    } else {
+        lo = hi = a;
+    }
+}
+
 // The lists [x, y) of one level (level < 0: raw terms, one key each; else nodes, L keys each) offered in chunks of 63.
 __device__ __forceinline__ void ac_offer(const uint64_t* __restrict__ base, uint32_t stride, uint32_t len, uint32_t x, uint32_t y,
                                          uint32_t lane, uint32_t L, uint64_t (&best)[kAcTop], uint64_t& worst) {
@@ -157,32 +187,8 @@ __global__ void __launch_bounds__(256) k_ac_suggest(const uint64_t* __restrict__
     for (uint32_t j = 0; j < hlen; j++) ph |= (uint64_t)p[j] << (56 - 8 * j);
     const uint64_t mask = hlen ? ~0ull << (64 - 8 * hlen) : 0ull;
 
-    // [lo, hi): one search for both ends while their ranges coincide, then one each
     uint32_t lo = 0, hi = 0;
-    {
-        uint32_t a = 0, b = n;
-        bool split = false;
-        uint32_t alo = 0, blo = 0, ahi = 0, bhi = 0;
-        while (b > a) {
-            const uint32_t s = (b - a + 63) / 64;
-            const uint64_t piv = (uint64_t)a + (uint64_t)(lane + 1) * s - 1;
-            const int c = piv < b ? ac_cmp((uint32_t)piv, heads, offs, pool, p, plen, ph, mask) : 1;
-            const uint32_t mlo = ac_first_false_count(c >= 0), mhi = ac_first_false_count(c > 0);
-            if (mlo != mhi) {
-                alo = a; blo = b; ac_narrow(alo, blo, s, mlo);
-                ahi = a; bhi = b; ac_narrow(ahi, bhi, s, mhi);
-                split = true;
-                break;
-            }
-            ac_narrow(a, b, s, mlo);
-        }
-        if (split) {
-            lo = ac_search(alo, blo, 0, lane, heads, offs, pool, p, plen, ph, mask);
-            hi = ac_search(ahi, bhi, 1, lane, heads, offs, pool, p, plen, ph, mask);
-        } else {
-            lo = hi = a;
-        }
-    }
+    ac_prefix_range(n, lane, heads, offs, pool, p, plen, ph, mask, lo, hi);
 
     uint64_t best[kAcTop], worst = kAcEmpty;
 #pragma unroll

@@ -43,6 +43,7 @@ void Engine::release_device_segments() {
     sem.dev = nullptr;
     if (ctx_ && ac_) ns_ac_release(ctx_, ac_);
     ac_ = nullptr;
+    ac_fuzzy_ = false;
 }
 
 // One segment's postings to the device without a host copy: every inverted file is mapped, appended from the mapping
@@ -202,6 +203,7 @@ bool Engine::reload() {
     suggest_table = std::move(fresh_table);
     suggest_build_ms = build_ms;
     suggest_upload_ms = upload_ms;
+    correct_build_ms = 0.0;
     dict.build(segments, [](uint32_t N, uint32_t df) { return bm25_idf(N, df); });
     cache_.clear();
     lru_.clear();
@@ -1149,6 +1151,190 @@ bool Engine::suggest_text(const std::string& input, int limit, std::string& body
 std::string Engine::suggest(const std::string& input, int limit) {
     std::string body;
     if (!suggest_text(input, limit, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- spelling correction (correct.hpp, csrc/ns_fuzzy.hip) --------------------------------------------------------------
+bool Engine::ensure_fuzzy() {
+    if (ac_fuzzy_) return true;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (ns_ac_build_fuzzy(ctx_, ac_, nullptr) != NS_OK) { err_ = std::string("ns_ac_build_fuzzy: ") + ns_last_error(ctx_); return false; }
+    correct_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ac_fuzzy_ = true;
+    return true;
+}
+
+namespace {
+struct CorrectPrep {
+    std::vector<uint8_t> bytes, edits;
+    std::vector<uint32_t> offs;
+    std::vector<uint32_t> rows;          // term (relative to the sub-batch) of each term sent
+    std::vector<uint32_t> idx, cnt;      // the device's answers per term sent
+    std::vector<uint8_t> dist;
+};
+}  // namespace
+
+// One sub-batch's host side: the terms normalised; those of 1..kFuzzyMaxLen bytes packed for ns_ac_fuzzy.
+static void correct_prepare(const Engine::QueryView* in, size_t q0, size_t q1, int max_edits, CorrectPrep& cp, ForkJoin* fj) {
+    const size_t Q = q1 - q0;
+    std::vector<std::string> norm(Q);
+    auto run = [&](size_t a, size_t b) {
+        for (size_t q = a; q < b; q++) nsx::normalize_token(in[q0 + q].p, in[q0 + q].n, norm[q]);
+    };
+    const unsigned nt = fj ? std::min<unsigned>(fj->width(), (unsigned)std::max<size_t>(1, Q / 2048)) : 1u;
+    if (nt <= 1) run(0, Q);
+    else fj->run(nt, [&](unsigned i) { run(Q * i / nt, Q * (i + 1) / nt); });
+    cp.rows.clear();
+    cp.bytes.clear();
+    cp.edits.clear();
+    cp.offs.assign(1, 0);
+    for (size_t q = 0; q < Q; q++) {
+        const std::string& t = norm[q];
+        if (t.empty() || t.size() > nsx::kFuzzyMaxLen) continue;
+        cp.rows.push_back((uint32_t)q);
+        cp.bytes.insert(cp.bytes.end(), t.begin(), t.end());
+        cp.offs.push_back((uint32_t)cp.bytes.size());
+        cp.edits.push_back((uint8_t)(max_edits < 0 ? nsx::correct_auto_edits(t.size()) : max_edits));
+    }
+}
+
+bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
+                           uint32_t* count, float* device_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_ || !ac_) { err_ = "no device context: this engine has no CPU spelling correction path"; return false; }
+    if (Q && (!terms || !term_idx || !dist || !count)) { err_ = "correct_batch: null argument"; return false; }
+    if (max_edits > nsx::kFuzzyMaxEdits) { err_ = "correct_batch: max_edits " + std::to_string(max_edits) + " above " + std::to_string(nsx::kFuzzyMaxEdits); return false; }
+    const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
+    const uint32_t plen = prefix_len > 0 ? (uint32_t)prefix_len : 0u;
+    if (Q == 0) return true;
+    if (!ensure_fuzzy()) return false;
+    if (Q >= 4096 && (!pool_ || pool_->width() < 2)) pool_.reset(new ForkJoin(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u)));
+    ForkJoin* fj = Q >= 4096 ? pool_.get() : nullptr;
+    const size_t kSub = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSub ? (Q + kSub - 1) / kSub : 1;
+    CorrectPrep cp[2];
+    float dev_ms = 0.0f;
+    // the device's part of sub-batch i: ns_ac_fuzzy on the terms sent, answers scattered to the caller's rows
+    auto device = [&](size_t i, CorrectPrep& p, std::string& err) -> bool {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        for (size_t q = a; q < b; q++) count[q] = 0;
+        std::fill(term_idx + a * L, term_idx + b * L, ~0u);
+        std::fill(dist + a * L, dist + b * L, (uint8_t)0xff);
+        const uint32_t R = (uint32_t)p.rows.size();
+        if (!R) return true;
+        p.idx.resize((size_t)R * L);
+        p.dist.resize((size_t)R * L);
+        p.cnt.resize(R);
+        float ms = 0.0f;
+        const int rc = ns_ac_fuzzy(ctx_, ac_, p.bytes.data(), p.offs.data(), R, p.edits.data(), plen, L, p.idx.data(), p.dist.data(), p.cnt.data(),
+                                   device_ms ? &ms : nullptr);
+        if (rc != NS_OK) { err = std::string("ns_ac_fuzzy: ") + ns_last_error(ctx_); return false; }
+        dev_ms += ms;
+        for (uint32_t r = 0; r < R; r++) {
+            const size_t q = a + p.rows[r];
+            count[q] = p.cnt[r];
+            std::memcpy(term_idx + q * L, p.idx.data() + (size_t)r * L, (size_t)L * 4);
+            std::memcpy(dist + q * L, p.dist.data() + (size_t)r * L, L);
+        }
+        return true;
+    };
+    correct_prepare(terms, 0, Q * 1 / n_sub, max_edits, cp[0], fj);
+    bool ok = true;
+    for (size_t i = 0; i < n_sub && ok; i++) {
+        CorrectPrep& cur = cp[i & 1];
+        if (i + 1 < n_sub) {   // prepare(i + 1) on the host threads while the device answers sub-batch i
+            std::string err;
+            bool dok = true;
+            std::thread dev([&]() { dok = device(i, cur, err); });
+            correct_prepare(terms, Q * (i + 1) / n_sub, Q * (i + 2) / n_sub, max_edits, cp[(i + 1) & 1], fj);
+            dev.join();
+            if (!dok) { err_ = err; ok = false; }
+        } else if (!device(i, cur, err_)) {
+            ok = false;
+        }
+    }
+    if (device_ms) *device_ms = dev_ms;
+    return ok;
+}
+
+bool Engine::did_you_mean_text(const std::string& query, int limit, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_ || !ac_) { err_ = "no device context: this engine has no CPU spelling correction path"; body = err_; return false; }
+    const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
+    // the tokens search would score (src/api_engine.cpp:391-397), with their place in the query
+    std::vector<nsx::QueryToken> toks;
+    for (auto& t : nsx::correct_tokens(query))
+        if (t.text.size() >= 2 && !is_stopword(t.text)) toks.push_back(std::move(t));
+    std::vector<char> known(toks.size(), 0);
+    std::vector<QueryView> ask;
+    std::vector<size_t> ask_tok;
+    for (size_t i = 0; i < toks.size(); i++) {
+        known[i] = dict.find(toks[i].text.data(), toks[i].text.size()) >= 0;
+        if (!known[i]) { ask.push_back(QueryView{toks[i].text.data(), toks[i].text.size()}); ask_tok.push_back(i); }
+    }
+    std::vector<uint32_t> idx(ask.size() * L), cnt(ask.size());
+    std::vector<uint8_t> dist(ask.size() * L);
+    if (!ask.empty() && !correct_batch(ask.data(), ask.size(), limit, -1, 0, idx.data(), dist.data(), cnt.data())) { body = err_; return false; }
+    std::vector<size_t> row(toks.size(), SIZE_MAX);
+    for (size_t a = 0; a < ask.size(); a++) row[ask_tok[a]] = a;
+    // "corrected": every unknown token with a suggestion replaced by its best one, every other byte kept
+    std::string corrected;
+    bool changed = false;
+    size_t at = 0;
+    for (size_t i = 0; i < toks.size(); i++) {
+        if (row[i] == SIZE_MAX || cnt[row[i]] == 0) continue;
+        const uint32_t best = idx[row[i] * L];
+        corrected.append(query, at, toks[i].at - at);
+        corrected.append(suggest_table.term(best), suggest_table.term_len(best));
+        at = toks[i].at + toks[i].len;
+        changed = true;
+    }
+    corrected.append(query, at, std::string::npos);
+    body.clear();
+    body += std::string("{\n  \"changed\": ") + (changed ? "true" : "false") + ",\n  \"corrected\": ";
+    json_escape(body, corrected);
+    body += ",\n  \"query\": ";
+    json_escape(body, query);
+    body += ",\n  \"terms\": ";
+    if (toks.empty()) {
+        body += "[]";
+    } else {
+        body += "[\n";
+        for (size_t i = 0; i < toks.size(); i++) {
+            body += std::string("    {\n      \"known\": ") + (known[i] ? "true" : "false") + ",\n      \"suggestions\": ";
+            const uint32_t n = row[i] == SIZE_MAX ? 0u : cnt[row[i]];
+            if (n == 0) {
+                body += "[]";
+            } else {
+                body += "[\n";
+                for (uint32_t r = 0; r < n; r++) {
+                    const uint32_t t = idx[row[i] * L + r];
+                    body += "        {\n          \"distance\": " + std::to_string((unsigned)dist[row[i] * L + r]) + ",\n          \"score\": " +
+                            std::to_string(suggest_table.score[t]) + ",\n          \"term\": ";
+                    json_escape(body, std::string(suggest_table.term(t), suggest_table.term_len(t)));
+                    body += r + 1 < n ? "\n        },\n" : "\n        }\n";
+                }
+                body += "      ]";
+            }
+            body += ",\n      \"token\": ";
+            json_escape(body, toks[i].text);
+            body += i + 1 < toks.size() ? "\n    },\n" : "\n    }\n";
+        }
+        body += "  ]";
+    }
+    body += "\n}";
+    return true;
+}
+
+std::string Engine::did_you_mean(const std::string& query, int limit) {
+    std::string body;
+    if (!did_you_mean_text(query, limit, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

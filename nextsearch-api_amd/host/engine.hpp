@@ -32,6 +32,7 @@
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
+#include "correct.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -71,6 +72,9 @@ public:
     // and the device tree build (ns_ac_upload), both of the last reload().
     nsx::SuggestTable suggest_table;
     double suggest_build_ms = 0.0, suggest_upload_ms = 0.0;
+    // the spelling corrector's side structures on that device copy (ns_ac_build_fuzzy): built by the first correct_batch /
+    // did_you_mean after a reload(), never by reload() itself; the time of that build (0 until it happened)
+    double correct_build_ms = 0.0;
 
     // device < 0: host-only (index + query preparation; every search call fails loudly)
     explicit Engine(int device = 0);
@@ -195,6 +199,21 @@ public:
     bool suggest_batch(const QueryView* inputs, size_t Q, int limit, uint32_t* term_idx, uint32_t* count, uint32_t* base_len,
                        float* device_ms = nullptr);
 
+    // Spelling correction (correct.hpp, csrc/ns_fuzzy.hip).  For term q (normalised like the table's terms)
+    // the L = clamp(limit, 1, 10) best candidates of suggest_table within max_edits (0..2; -1 = auto by normalised
+    // length: < 3 bytes 0, 3..5 one, above two) that share the term's first min(prefix_len, length) bytes: rows
+    // term_idx[q * L + r] (best first, ~0u past count[q]) with their distances dist[q * L + r] (0xff past the end).
+    // Ranked by (distance, score desc, index asc).  Large batches are cut and pipelined like suggest_batch's.
+    bool correct_batch(const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
+                       uint32_t* count, float* device_ms = nullptr);
+    // "Did you mean": JSON text {"changed", "corrected", "query", "terms": [{"known", "suggestions": [{"distance",
+    // "score", "term"}], "token"}]} in dump(2) layout.  Tokens are the query's alnum runs without stop words and
+    // one-byte tokens; a token the term dictionary holds is known and keeps its place; an unknown one gets its best L
+    // (auto edits, no prefix) and, in "corrected", is replaced by the best of them.  Without a device context:
+    // {"error": ...} (did_you_mean_text: false, body = the message).
+    std::string did_you_mean(const std::string& query, int limit);
+    bool did_you_mean_text(const std::string& query, int limit, std::string& body);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -236,6 +255,8 @@ private:
     int device_;
     ns_ctx* ctx_ = nullptr;
     ns_ac* ac_ = nullptr;    // suggest_table on ctx_ (ns_ac_upload)
+    bool ac_fuzzy_ = false;  // ns_ac_build_fuzzy has run on ac_
+    bool ensure_fuzzy();
     std::vector<ns_seg*> dev_segs_;
     // further devices holding a replica of the index (multi-device engine): context + segments each
     struct Replica { int device = 0; ns_ctx* ctx = nullptr; std::vector<ns_seg*> segs; };

@@ -585,6 +585,39 @@ extern "C" int nsh_engine_suggest_table(nsh_engine* e, const char** pool, const 
 } NSH_CATCH(e, "nsh_engine_suggest_table", -1)
 }
 
+extern "C" int nsh_engine_correct_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_terms, int limit,
+                                        int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist, uint32_t* count,
+                                        float* device_ms) { try {
+    if (!e || (n_terms && (!offsets || !term_idx || !dist || !count))) return -1;
+    std::vector<nextsearch::Engine::QueryView> views(n_terms);
+    for (uint32_t q = 0; q < n_terms; q++) {
+        if (offsets[q + 1] < offsets[q] || (offsets[q + 1] > offsets[q] && !bytes)) { nsh_set_err(e, "nsh_engine_correct_batch: bad offsets"); return -1; }
+        views[q] = {bytes ? bytes + offsets[q] : "", (size_t)(offsets[q + 1] - offsets[q])};
+    }
+    if (!e->eng.correct_batch(views.data(), n_terms, limit, max_edits, prefix_len, term_idx, dist, count, device_ms)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_correct_batch", -1)
+}
+
+extern "C" int nsh_engine_did_you_mean_json(nsh_engine* e, const char* query, uint64_t query_len, int limit, char** json_out) { try {
+    if (!e || !json_out || (query_len && !query)) return -1;
+    std::string s;
+    const bool ok = e->eng.did_you_mean_text(std::string(query ? query : "", (size_t)query_len), limit, s);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); *json_out = nullptr; return -1; }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_did_you_mean_json", -1)
+}
+
+extern "C" int nsh_correct_auto_edits(uint64_t normalized_len) { return nsx::correct_auto_edits((size_t)normalized_len); }
+
+extern "C" double nsh_engine_correct_build_ms(nsh_engine* e) { return e ? e->eng.correct_build_ms : 0.0; }
+
 extern "C" uint64_t nsh_suggest_split(const char* input, uint64_t input_len, uint64_t* base_len, char* prefix, uint64_t cap) {
     size_t b = 0;
     std::string p;
