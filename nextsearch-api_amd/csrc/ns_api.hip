@@ -2921,4 +2921,13 @@ extern "C" int ns_debug_topk_counters(unsigned long long* out, int reset) {
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_kcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
+// the row join's paths and tie rounds (ns_kernels.hip k_merge, k_merge_wide, k_merge_ranks): 16 values
+extern "C" int ns_debug_join_counters(unsigned long long* out, int reset) {
+    unsigned long long h[16];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_jcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_jcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
 #endif

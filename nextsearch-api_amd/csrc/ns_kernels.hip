@@ -411,6 +411,11 @@ __global__ void __launch_bounds__(NT) k_score(const DevItem* __restrict__ items,
 // passes over the heads find it, the prefixes are gathered into LDS, sorted once, and the first K
 // leave.  Cost is independent of K and linear in rows / 256.
 constexpr int kMergeStage = 2048;   // entries k_merge stages in LDS per query
+#ifdef NS_COUNT
+// counting build: which join path a query took and how often its tie rules decided (ns_debug_join_counters; the
+// indices are named in tests/join_shapes.py JOIN_EVENTS).  One add per query by one lane; 8, 9, 12 count rounds, 10 rows.
+__device__ unsigned long long g_ns_jcnt[16];
+#endif
 __device__ __forceinline__ uint32_t merge_wave_max(uint32_t v) {   // DPP reduction (row_shr / row_bcast forms), wave-uniform result
     v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));
     v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));
@@ -428,6 +433,9 @@ __device__ __forceinline__ void merge_rows_wave(uint32_t q, uint32_t pb, uint32_
     for (uint32_t i = lane; i < pc; i += 64) heads[pb + i] = 0;
     Hit* oh = out_hits + (uint64_t)q * K;
     uint32_t produced = 0;
+#ifdef NS_COUNT
+    unsigned long long tie_rounds_ = 0;
+#endif
     for (; produced < K; produced++) {
         // each lane proposes the best head among its rows
         uint32_t best_s = 0;                 // order_bits(score); 0 == nothing
@@ -452,6 +460,9 @@ __device__ __forceinline__ void merge_rows_wave(uint32_t q, uint32_t pb, uint32_
         for (int d = 32; d > 0; d >>= 1) ms = max(ms, (uint32_t)__shfl_xor(ms, d, 64));
         unsigned long long anyb = __ballot(has);
         if (anyb == 0ull) break;
+#ifdef NS_COUNT
+        if (__popcll(__ballot(has && ws == ms)) > 1) tie_rounds_++;
+#endif
         uint64_t cid = (has && ws == ms) ? best_id : ~0ull;
         uint64_t mid = cid;
 #pragma unroll
@@ -480,6 +491,9 @@ __device__ __forceinline__ void merge_rows_wave(uint32_t q, uint32_t pb, uint32_
     if (lane == 0) {
         out_nhits[q] = produced;
         out_found[q] = found;
+#ifdef NS_COUNT
+        if (tie_rounds_) atomicAdd(&g_ns_jcnt[9], tie_rounds_);
+#endif
     }
 }
 
@@ -546,6 +560,10 @@ __global__ void __launch_bounds__(256) k_merge(const DevQuery* __restrict__ quer
         if (lane == 0) {
             out_nhits[q] = produced;
             out_found[q] = found;
+#ifdef NS_COUNT
+            atomicAdd(&g_ns_jcnt[0], 1ull);
+            if (pc == 0) atomicAdd(&g_ns_jcnt[13], 1ull);
+#endif
         }
         return;
     }
@@ -569,9 +587,15 @@ __global__ void __launch_bounds__(256) k_merge(const DevQuery* __restrict__ quer
         uint32_t h = 0;
         uint32_t cur = ((uint32_t)lane < pc) ? sc[(uint32_t)lane * K] : 0u;   // 0 == nothing (left)
         uint32_t produced = 0;
+#ifdef NS_COUNT
+        unsigned long long tie_rounds_ = 0;
+#endif
         for (; produced < K; produced++) {
             const uint32_t ms = merge_wave_max(cur);
             if (ms == 0u) break;
+#ifdef NS_COUNT
+            if (__popcll(__builtin_amdgcn_ballot_w64(cur == ms)) > 1) tie_rounds_++;
+#endif
             const uint32_t w = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(cur == ms));
             if ((uint32_t)lane == w) {
                 win[produced] = (uint16_t)((w << 7) | h);
@@ -598,9 +622,16 @@ __global__ void __launch_bounds__(256) k_merge(const DevQuery* __restrict__ quer
         if (lane == 0) {
             out_nhits[q] = produced;
             out_found[q] = found;
+#ifdef NS_COUNT
+            atomicAdd(&g_ns_jcnt[1], 1ull);
+            if (tie_rounds_) atomicAdd(&g_ns_jcnt[8], tie_rounds_);
+#endif
         }
         return;
     }
+#ifdef NS_COUNT
+    if (lane == 0) atomicAdd(&g_ns_jcnt[2], 1ull);
+#endif
     merge_rows_wave(q, pb, pc, part_hits, part_nhits, out_hits, out_nhits, out_found, found, K, heads, lane);
 }
 
@@ -625,6 +656,9 @@ __global__ void __launch_bounds__(256) k_merge_ranks(const Hit* __restrict__ hit
     const Hit* my = hits + row * K;
     uint32_t h = 0, produced = 0;
     Hit* oh = out_hits + (size_t)q * K;
+#ifdef NS_COUNT
+    unsigned long long tie_rounds_ = 0;
+#endif
     for (; produced < K; produced++) {
         uint32_t s = 0;
         uint64_t id = ~0ull;
@@ -638,6 +672,9 @@ __global__ void __launch_bounds__(256) k_merge_ranks(const Hit* __restrict__ hit
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) ms = max(ms, (uint32_t)__shfl_xor(ms, d, 64));
         if (__ballot(h < n) == 0ull) break;
+#ifdef NS_COUNT
+        if (__popcll(__ballot(h < n && s == ms)) > 1) tie_rounds_++;
+#endif
         uint64_t mid = (h < n && s == ms) ? id : ~0ull;
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
@@ -663,6 +700,10 @@ __global__ void __launch_bounds__(256) k_merge_ranks(const Hit* __restrict__ hit
     if (lane == 0) {
         out_nhits[q] = produced;
         out_found[q] = f;
+#ifdef NS_COUNT
+        atomicAdd(&g_ns_jcnt[11], 1ull);
+        if (tie_rounds_) atomicAdd(&g_ns_jcnt[12], tie_rounds_);
+#endif
     }
 }
 
@@ -776,6 +817,14 @@ __global__ void __launch_bounds__(256) k_merge_wide(const DevQuery* __restrict__
     for (uint32_t i = tid + R * 256; i < pc; i += 256) gather_row(i);
     __syncthreads();
     const uint32_t C = s_ncand;
+#ifdef NS_COUNT
+    if (tid == 0) {
+        atomicAdd(&g_ns_jcnt[3], 1ull);
+        atomicAdd(&g_ns_jcnt[b1 == 0xFFFFFFFFu ? 4 : 5], 1ull);
+        if (C > kMergeCap) atomicAdd(&g_ns_jcnt[6], 1ull);
+        if (pc > 256 * R) atomicAdd(&g_ns_jcnt[7], 1ull);
+    }
+#endif
     if (C > kMergeCap) {   // uniform: one wave redoes the query the slow way
         if (tid < 64) merge_rows_wave(q, pb, pc, part_hits, part_nhits, out_hits, out_nhits, out_found, found, K, heads, (int)tid);
         return;
@@ -798,6 +847,13 @@ __global__ void __launch_bounds__(256) k_merge_wide(const DevQuery* __restrict__
             __syncthreads();
         }
     const uint32_t produced = C < K ? C : K;
+#ifdef NS_COUNT
+    if (tid == 0 && C > K) {   // sorted: the candidates that tie with the K-th best follow it
+        unsigned long long ties = 0;
+        for (uint32_t i = K; i < C && s_cs[i] == s_cs[K - 1]; i++) ties++;
+        if (ties) atomicAdd(&g_ns_jcnt[10], ties);
+    }
+#endif
     Hit* oh = out_hits + (uint64_t)q * K;
     for (uint32_t i = tid; i < K; i += 256) {
         Hit h;

@@ -200,7 +200,8 @@ def hip_lib():
 
 
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
-DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4}
+DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
+                  "ns_debug_join_counters": 16}
 
 
 def debug_counters(reset=False):

@@ -7,6 +7,8 @@ process that loaded the counting build (NS_HIP_LIB=libnextsearch_hip_count.so):
 
 There every family resets the event counters, runs, is checked against the restatement as well, and must have reached the
 events it names; the generator-based inputs (the mid1 golden queries, the reduced cfg5 workload) run once for comparison.
+The join families of tests/join_shapes.py and one synthetic rank-row case run there too (tests/join_run.py reach()): the
+report's "join" key holds their counters and the per-path query counts their declarations predict.
 OUT.json receives every counter of every input."""
 import json
 import os
@@ -21,6 +23,7 @@ for p in (os.path.join(ROOT, "nextsearch-api_amd"), HERE):
 
 import nsbind  # noqa: E402
 import body_shapes  # noqa: E402
+import join_run  # noqa: E402
 from rawseg import RawSegment, check_results, descriptors, reference  # noqa: E402
 
 AND = nsbind.NS_FLAG_AND
@@ -146,6 +149,11 @@ def main(out_path):
             c = nsbind.debug_counters(reset=True)
             report["generator"][label] = {"events": _named(c), "raw": c}
             print(label, "done", flush=True)
+    t1 = time.time()
+    report["join"] = join_run.reach()
+    report["join"]["seconds"] = round(time.time() - t1, 1)
+    for name, missed in report["join"].pop("missed").items():
+        report["missed"]["join " + name] = missed
     report["seconds"] = round(time.time() - t0, 1)
     with open(out_path, "w") as f:
         json.dump(report, f, indent=1, sort_keys=True)

@@ -137,3 +137,97 @@ def check_results(ref, hits, nhits, found, k, and_mode=False, label=""):
         assert got_docs == [d for d, _ in keyed], what + ("docs", got_docs[:8], [d for d, _ in keyed[:8]])
         want_bits = np.array([v for _, v in keyed], dtype=np.float32).view(np.uint32)
         np.testing.assert_array_equal(hits[qi, :n]["score"].view(np.uint32), want_bits, err_msg=str(what))
+
+
+# ---- several segments in one ctx (tests/join_shapes.py): a term ref names (segment, list) -------------------------------
+PAD_SCORE_BITS, PAD_ID = 0xFF800000, 0xFFFFFFFF   # the tail of a result row past nhits: -inf, seg = doc = 0xFFFFFFFF
+
+
+def descriptors_multi(queries, seg_lists, seg_offs, idfs, weights):
+    """queries (lists of (segment, list number)) -> (QDESC array, TERM array); idfs / weights: [segment][list]"""
+    qd = np.zeros(len(queries), dtype=nsbind.QDESC_DTYPE)
+    refs = []
+    for qi, q in enumerate(queries):
+        qd[qi] = (len(refs), len(q))
+        for s, li in q:
+            refs.append((s, len(seg_lists[s][li][0]), int(seg_offs[s][li]), idfs[s][li], weights[s][li]))
+    refs = np.array(refs, dtype=nsbind.TERM_DTYPE) if refs else np.zeros(0, dtype=nsbind.TERM_DTYPE)
+    return qd, refs
+
+
+class RawSegments:
+    """One ctx with several uploaded segments, ids 0 .. n-1 in the order given; `segments` holds (n_docs, doc_len, lists) per
+    segment.  release() frees everything (use try / finally)."""
+
+    def __init__(self, segments, device=0):
+        self.L = nsbind.hip_lib()
+        self.ctx = C.c_void_p()
+        assert self.L.ns_ctx_create(device, C.byref(self.ctx)) == 0
+        self.segs, self.doc_len, self.avgdl, self.lists, self.offs, self._keep = [], [], [], [], [], []
+        for sid, (n_docs, doc_len, lists) in enumerate(segments):
+            dl = np.ascontiguousarray(doc_len, dtype=np.uint32)
+            assert len(dl) == int(n_docs)
+            flat, offs = payload_of(lists)
+            h = C.c_void_p()
+            rc = self.L.ns_segment_upload(self.ctx, sid, int(n_docs), C.c_float(avgdl_of(dl)), dl.ctypes.data, flat.ctypes.data, flat.nbytes, C.byref(h))
+            if rc != 0:
+                msg = self.L.ns_last_error(self.ctx)
+                self.release()
+                raise AssertionError(msg)
+            self.segs.append(h)
+            self.doc_len.append(dl)
+            self.avgdl.append(avgdl_of(dl))
+            self.lists.append(lists)
+            self.offs.append(offs)
+            self._keep.append(flat)
+
+    def err(self):
+        return self.L.ns_last_error(self.ctx)
+
+    run = RawSegment.run
+
+    def release(self):
+        if self.ctx:
+            nsbind.close_batches_of(self.ctx)
+            for h in self.segs:
+                self.L.ns_segment_release(self.ctx, h)
+            self.L.ns_ctx_destroy(self.ctx)
+            self.ctx = None
+
+
+def reference_multi(segments, queries, idfs, weights):
+    """per query: the restatement's (score, seg, doc) triples in the join's canonical order (score desc, seg asc, doc asc), of
+    every doc some term ref touches (OR) and of the docs that hold EVERY term ref the query names in their segment (AND);
+    `reference()` per segment, joined"""
+    out = []
+    for q in queries:
+        both = ([], [])
+        for s in sorted({s for s, _ in q}):
+            n_docs, doc_len, lists = segments[s]
+            dl = np.ascontiguousarray(doc_len, dtype=np.uint32)
+            (keyed, anded), = reference(lists, [[li for ss, li in q if ss == s]], idfs[s], weights[s], dl, avgdl_of(dl))
+            both[0].extend((v, s, d) for d, v in keyed)
+            both[1].extend((v, s, d) for d, v in anded)
+        out.append(tuple(sorted(x, key=lambda t: (-float(t[0]), t[1], t[2])) for x in both))
+    return out
+
+
+def check_results_multi(ref, hits, nhits, found, k, and_mode=False, label=""):
+    """`found`, `nhits`, segs and docs in the canonical order, score BITS and the padding of the row's tail, for every query,
+    against `reference_multi(...)`"""
+    for qi, both in enumerate(ref):
+        keyed = both[1] if and_mode else both[0]
+        what = (label, "AND" if and_mode else "OR", "k", k, "query", qi)
+        assert int(found[qi]) == len(keyed), what + ("found", int(found[qi]), len(keyed))
+        keyed = keyed[:k]
+        n = int(nhits[qi])
+        assert n == len(keyed), what + ("nhits", n, len(keyed))
+        got = [(int(s), int(d)) for s, d in zip(hits[qi, :n]["seg"], hits[qi, :n]["doc"])]
+        want = [(s, d) for _, s, d in keyed]
+        if got != want:
+            at = next(i for i in range(n) if got[i] != want[i])
+            raise AssertionError(what + ("(seg, doc) differ first at rank", at, "got", got[at:at + 4], "want", want[at:at + 4]))
+        want_bits = np.array([v for v, _, _ in keyed], dtype=np.float32).view(np.uint32)
+        np.testing.assert_array_equal(hits[qi, :n]["score"].view(np.uint32), want_bits, err_msg=str(what))
+        tail = hits[qi, n:k]
+        assert np.all(tail["score"].view(np.uint32) == PAD_SCORE_BITS) and np.all(tail["seg"] == PAD_ID) and np.all(tail["doc"] == PAD_ID), what + ("padding",)

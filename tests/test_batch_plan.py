@@ -117,6 +117,10 @@ def check_exactly_once(p, segs, n_queries):
         order = np.argsort(slots, kind="stable")
         assert np.array_equal(qs[order], np.repeat(np.arange(n_queries), q["part_count"]))   # rows of a query: contiguous ...
         assert np.array_equal(q["part_begin"], np.concatenate([[0], np.cumsum(q["part_count"])[:-1]]))   # ... at part_begin
+        # ... and ascending strictly in (segment, doc range): k_merge's staged rounds break ties by the lowest row
+        key = np.concatenate([p.witems["seg"].astype(np.int64) << 32 | p.witems["doc_lo"], p.items["seg"].astype(np.int64) << 32 | p.items["tile_begin"]])[order]
+        same_q = qs[order][1:] == qs[order][:-1]
+        assert np.all(key[1:][same_q] > key[:-1][same_q])
     # the wave items of one (query, segment) group tile [0, n_docs) without overlap
     w = p.witems
     o = np.lexsort((w["doc_lo"], w["seg"], w["query"]))

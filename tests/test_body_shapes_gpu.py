@@ -11,14 +11,16 @@ import pytest
 
 import body_reach
 import body_shapes
+import join_run
+import join_shapes
 from conftest import PKG
 
 pytestmark = pytest.mark.gpu
 
 COUNT_LIB = os.path.join(PKG, "libnextsearch_hip_count.so")
-# The child's timeout.  The child took 2.2 s on an MI355X (profiles/body_shapes/README.md; 1.8 s of it inside main()); five
-# times that is 11 s, plus 19 s for what does not scale with the work: starting the interpreter, loading the library and
-# the first use of a device that other processes share.
+# The child's timeout.  The child took 2.2 s on an MI355X before the join families ran in it too (1.8 s of it inside main();
+# profiles/body_shapes/README.md holds both times); five times that is 11 s, plus 19 s for what does not scale with the
+# work: starting the interpreter, loading the library and the first use of a device that other processes share.
 REACH_TIMEOUT_S = 30
 
 
@@ -35,7 +37,10 @@ def test_directed_families_reach_their_paths_in_the_counting_build(tmp_path):
     restatement again and asserts that every event a family names was counted: pos >= 4 lanes and next-bucket moves for the
     full-bucket families, wrap moves for the wrap families, chunks that continue a bucket for the carry family, every hi
     source, both exhausted-list step kinds and B windows of 1 and 4 chunks for the merge families, shrinks inside a step
-    for the flood."""
+    for the flood.  The same child runs the join families of tests/join_shapes.py and one synthetic rank-row case: every
+    join counter a family names is above zero, and the number of queries counted on each of the four join paths EQUALS what
+    the family declares (which tests/test_join_shapes_cpu.py pins to the planner): a query that silently took another path
+    changes a count."""
     if "count" in os.path.basename(os.environ.get("NS_HIP_LIB", "")):
         pytest.skip("this IS a counting-build process")
     assert os.path.exists(COUNT_LIB), "libnextsearch_hip_count.so is missing: make -C nextsearch-api_amd all"
@@ -51,6 +56,16 @@ def test_directed_families_reach_their_paths_in_the_counting_build(tmp_path):
     for name, fn in body_shapes.FAMILIES.items():
         for e in fn.events:
             assert rep["directed"][name]["events"][e] > 0, (name, e)
+    join = rep["join"]
+    assert set(join["families"]) == set(join_shapes.FAMILIES)
+    for name, fn in join_shapes.FAMILIES.items():
+        got, fam = join["families"][name], fn()
+        for e in fam.events:
+            assert got["events"][e] > 0, (name, e)
+        assert [got["events"][p] for p in join_shapes.PATHS] == join_run.predicted_path_counts(name, got["batches_at_k"]), name
+        assert sorted(set(got["batches_at_k"])) == sorted(fam.ks)
+    assert {e for fn in join_shapes.FAMILIES.values() for e in fn().events} | {"rank_join", "rank_join_tie_rounds"} == set(join_shapes.JOIN_EVENTS)
+    assert join["rank_join"]["events"]["rank_join"] == join_shapes.RANK_QUERIES and join["rank_join"]["events"]["rank_join_tie_rounds"] > 0
     keep = os.environ.get("NS_REACH_JSON")   # a recorded run for profiles/body_shapes/
     if keep:
         with open(keep, "w") as f:

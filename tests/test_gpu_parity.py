@@ -962,11 +962,14 @@ def test_lone_query_wide_merge_ties_and_thresholds():
     """A lone query is cut into thousands of doc ranges and joined by k_merge_wide (threshold from the
     row heads, one sort).  Three shapes through the raw C-ABI against the numpy restatement: every
     score equal (mass ties: more candidates than the LDS buffer holds -> tournament fall-back), two
-    score levels (ties AT the threshold), and distinct scores."""
+    score levels (ties AT the threshold), and distinct scores.  The segment is the smallest that is still cut into enough rows
+    for k_merge_wide at every K here (join_shapes.LONE_WIDE_N; tests/test_join_shapes_cpu.py checks that with the planner);
+    mass ties past the LDS buffer, thousands of rows and the threshold's edges are the business of tests/join_shapes.py."""
+    import join_shapes
     L = nsbind.hip_lib()
     ctx = C.c_void_p()
     assert L.ns_ctx_create(0, C.byref(ctx)) == 0
-    N = 600_000
+    N = join_shapes.LONE_WIDE_N
     rng = np.random.default_rng(3)
     docs = np.arange(0, N, 2, dtype=np.uint32)
     shapes = {

@@ -1,7 +1,8 @@
 """Segment-sharded multi-GPU path (SURVEY 8(e) alternative; nextsearch-api_amd/shard.py): every rank scores all
 queries over ITS segments, one all-gather of the per-rank rows, one join.
   * CPU, world_size 2 on gloo: sub-index manifests, the exchange layout and the join's semantics, with the
-    oracle standing in for each rank's scoring and a numpy join as the checker (there is no CPU join in the product);
+    oracle standing in for each rank's scoring and the numpy join of tests/join_ref.py as the checker (there is no CPU
+    join in the product);
   * GPU, one process: the ranks' engines run one after the other on the same device, their rows are stacked
     rank-major as the all-gather would deliver them, and ns_merge_rank_rows must reproduce the unsharded
     engine's results bit for bit."""
@@ -29,22 +30,6 @@ def _rows_to_tensors(res, K):
     return torch.from_numpy(t), torch.from_numpy(nhits.astype(np.int32)), torch.from_numpy(found.astype(np.int64))
 
 
-def _np_join(g_hits, g_nhits, g_found, seg_map, K):
-    """Checker: the global heap over the ranks' rows — score desc, GLOBAL seg asc, doc asc."""
-    W, Q = g_nhits.shape
-    out = []
-    for q in range(Q):
-        cand = []
-        for r in range(W):
-            for i in range(int(g_nhits[r, q])):
-                bits, seg, doc = (int(x) & 0xFFFFFFFF for x in g_hits[r, q, i])
-                score = np.array([bits], dtype=np.uint32).view(np.float32)[0]
-                cand.append((-float(score), int(seg_map[r, seg]), doc, bits))
-        cand.sort()
-        out.append(([(c[3], c[1], c[2]) for c in cand[:K]], int(g_found[:, q].sum())))
-    return out
-
-
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -58,6 +43,7 @@ def _worker(rank, world, port, index_dir, shard_root, queries, K, ret):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import orc
     import shard
+    from join_ref import np_join
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -73,7 +59,7 @@ def _worker(rank, world, port, index_dir, shard_root, queries, K, ret):
         ora.close()
         g_hits, g_nhits, g_found = shard.exchange_rank_rows(*local)
         assert g_hits.shape == (world, len(queries), K, 3)
-        joined = _np_join(g_hits.numpy(), g_nhits.numpy(), g_found.numpy(), seg_map.numpy(), K)
+        joined = np_join(g_hits.numpy(), g_nhits.numpy(), g_found.numpy(), seg_map.numpy(), K)
         full = orc.Oracle(index_dir)
         fh, fn, ff, fu = full.search_batch(queries, K)
         full.close()
