@@ -4,7 +4,8 @@
 // The term with the most postings in the range is the item's DRIVER; all other terms are FOREIGN.
 // The wave advances in super-batches [lo, hi]:
 //   1. plan windows over the FOREIGN terms only (<= FB postings in total, proportional to what is
-//      left of each list), probe each window's last docId: hi = min of those (or the end of the range)
+//      left of each list plus a few postings of slack), probe each window's last docId: hi = min of those (or the
+//      end of the range)
 //   2. load the foreign postings (flat, coalesced), BM25 term scores, claim an entry per distinct docId
 //      in a BUCKETED table (NB buckets of 4 entries = one ds_read_b128; bucket = low docId bits; entry =
 //      (docId - lo) << 8 | index of the posting that owns the doc's accumulator; no LDS atomics: store /
@@ -218,15 +219,17 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
 
     // Foreign windows: sizes proportional to what is left of each foreign list (all windows span about
     // the same doc range), at most FB postings in total; one docId probe per window (its last posting).
-    // Planned right after the cursors move, so the probes fly while the driver streams.
+    // Planned right after the cursors move, so the probes fly while the driver streams.  Every window carries WSLACK
+    // postings of slack beyond its share (ns_internal.h foreign_slack / foreign_window: the rule and its two fall-backs).
+    constexpr uint32_t WSLACK = (FB == 64) ? kWinSlackThin : kWinSlackGen;
     uint32_t w_n = 0, e_n = 0xFFFFFFFFu;
 #define NS_PLAN_FOREIGN()                                                                          \
     {                                                                                              \
         const uint32_t rem_ = end - cur;   /* 0 for the driver's lane and lanes >= T */            \
         const uint32_t nact_ = (uint32_t)__popcll(wballot(rem_ > 0));                             \
-        const float scale_ = (float)(FB - (int)nact_) * __builtin_amdgcn_rcpf((float)max(Rf, 1u)); \
-        uint32_t w_ = 1u + (uint32_t)((float)rem_ * scale_);                                       \
-        w_ = (w_ < rem_) ? w_ : rem_;                                                              \
+        const uint32_t c_ = foreign_slack(WSLACK, (uint32_t)FB, nact_, Rf);   /* scalar */         \
+        const float scale_ = foreign_scale(c_, (uint32_t)FB, nact_, __builtin_amdgcn_rcpf((float)max(Rf, 1u))); \
+        const uint32_t w_ = foreign_window(rem_, c_, scale_);                                      \
         const bool probe_ = w_ < rem_;                                                             \
         const uint32_t pi_ = probe_ ? (cur + w_ - 1u) : 0u;                                        \
         const nat_u2 pv_ = postings[pi_];   /* unconditional load of a valid index: no branch */   \

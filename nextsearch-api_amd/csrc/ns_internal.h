@@ -131,6 +131,47 @@ struct DevQuery {
 // a query cut into this many partial rows is joined by k_merge_wide (one workgroup) instead of k_merge (ns_kernels.hip)
 constexpr bool merge_is_wide(uint32_t part_count, uint32_t K) { return part_count > 64 && part_count >= K; }
 
+// ---- foreign windows of the driver-stream body (ns_driver_kernel.hip NS_PLAN_FOREIGN; tests/window_harness.cpp compiles
+// the same lines on the host) ----
+// A super-batch loads at most FB foreign postings.  A list with `rem` postings left gets a window of
+//     w = min(rem, c + floor(rem * (FB - c * nact) / Rf))        nact lists with postings left, Rf postings left in all,
+// i.e. a share of the budget proportional to what is left of it plus c postings of SLACK: the super-batch ends at the
+// smallest last docId of the windows, and a tail list that expects m postings in the span has its (m + 1)-th before the
+// span's end about a third of the time (m = 2: P(Gamma(3) < 2) = 0.32) — without slack one such list cuts the super-batch
+// short and the primary list's loaded postings are scored again by the next one.  The windows sum to at most
+// c * nact + (FB - c * nact) = FB, whatever c.  kWinSlack*: c per class (FB == 64: thin groups, else the general class);
+// -D overrides them for a sweep.  c == 1 is the rule before slack existed.  Swept over 1, 2, 3, 4, 6 per class on an MI355X
+// (profiles/window_slack): general 3 (its cfg5 groups -6.4 %, 4 and 6 the same within the spread, 2: -5.0 %); thin stays 1
+// (no c moved the thin groups or cfg5 beyond the spread of the runs without slack).
+#ifndef NS_WIN_SLACK_THIN
+#define NS_WIN_SLACK_THIN 1
+#endif
+#ifndef NS_WIN_SLACK_GEN
+#define NS_WIN_SLACK_GEN 3
+#endif
+static constexpr uint32_t kWinSlackThin = NS_WIN_SLACK_THIN, kWinSlackGen = NS_WIN_SLACK_GEN;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define NS_HD __host__ __device__
+#else
+#define NS_HD
+#endif
+// The slack in effect for one plan (uniform over the lists).  c falls back to 1
+//   (a) when everything left fits the budget (Rf + nact <= FB): every window is then the whole rest of its list, and
+//   (b) when the slack would take more than half the budget (FB - c * nact < FB / 2): groups of many foreign terms.
+NS_HD inline uint32_t foreign_slack(uint32_t c, uint32_t FB, uint32_t nact, uint32_t Rf) {
+    if (Rf <= FB - nact) return 1u;                  // nact <= 63 < FB
+    if (2u * c * nact > FB) return 1u;
+    return c;
+}
+// proportional share per posting left: (FB - c * nact) / Rf with the caller's reciprocal (the device: v_rcp_f32, 1 ulp)
+NS_HD inline float foreign_scale(uint32_t c_eff, uint32_t FB, uint32_t nact, float rcp_Rf) {
+    return (float)((int)FB - (int)(c_eff * nact)) * rcp_Rf;
+}
+NS_HD inline uint32_t foreign_window(uint32_t rem, uint32_t c_eff, float scale) {
+    const uint32_t w = c_eff + (uint32_t)((float)rem * scale);
+    return (w < rem) ? w : rem;
+}
+
 struct Hit {   // == ns_hit
     float    score;
     uint32_t seg;
