@@ -308,6 +308,25 @@ int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_
                 const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
                 uint32_t* count_out, float* device_ms_out);
 
+/* Typo-tolerant completion over the same table and side structures (csrc/ns_fuzzy.hip): for each prefix that is
+ * still being typed the L best candidates that some prefix of which is within a bounded edit distance of it.
+ *   distance    the PREFIX distance pd(q, c) = min over 0 <= j <= |c| of osa(q, c[0, j)), osa = ns_ac_fuzzy's optimal string
+ *               alignment: pd("cornoa", "coronavirus") = 1, pd("ca", "abc") = 1, pd("abcd", "ab") = 2, pd("abcde", "cdxxx") = 3;
+ *               at most max_edits[q] (0, 1 or 2; more: NS_E_INVAL)
+ *   candidates  ns_ac_fuzzy's (score not 0; of a run of equal strings only the first), of ANY length from
+ *               |q| - max_edits[q] upwards: terms longer than 66 bytes are found as well
+ *   prefix      with p = min(prefix_len, |q|) a candidate shares its first p bytes with q exactly; the distance is still taken
+ *               over the whole strings
+ *   order       distance ascending, then score descending, then index ascending (strict and total: two calls return equal
+ *               bytes)
+ * With max_edits 0 the answer is the candidates that start with q, best score first; a query of at most max_edits bytes matches
+ * every candidate (all of it can be deleted) and gets the table's best L by score.  Arguments, clamping of L, row layout
+ * (~0u / 0xff tails), the limits on a query's length (0 or more than NS_FUZZY_MAX_LEN bytes: count 0, never sent), staging and
+ * refusals are ns_ac_fuzzy's; NS_E_STATE before ns_ac_build_fuzzy.  ns_ac_suggest's and ns_ac_fuzzy's answers stay as they are. */
+int ns_ac_fuzzy_prefix(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes, const uint32_t* prefix_offsets, uint32_t n_q,
+                       const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                       uint32_t* count_out, float* device_ms_out);
+
 /* Segment-sharded multi-GPU (the alternative to query sharding for an index that outgrows one
  * GPU's HBM): rank r holds a subset of the segments and scores ALL queries over it; the fixed-size per-rank rows
  * are all-gathered rank-major (hits [n_ranks][n_queries][k], nhits and found [n_ranks][n_queries]) and joined here

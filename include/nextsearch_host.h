@@ -254,6 +254,21 @@ int nsh_engine_did_you_mean_json(nsh_engine* e, const char* query, uint64_t quer
 int nsh_correct_auto_edits(uint64_t normalized_len);
 double nsh_engine_correct_build_ms(nsh_engine* e);
 
+/* Typo-tolerant completion over the suggest table, on the primary device: suggest for a prefix that is still
+ * being typed and already has a typo in it.  Shares the corrector's side structures (built by the first call after a reload).
+ * nsh_engine_complete_batch: input q = bytes[offsets[q] .. offsets[q + 1]) is split like a suggest request: its last alnum
+ * run, lower-cased, is the prefix and base_len[q] counts the bytes before it.  Rows as nsh_engine_correct_batch's, for the
+ * candidates SOME PREFIX OF WHICH is within max_edits (0..2, or -1 = auto: nsh_correct_auto_edits of the prefix length) of the
+ * prefix, of any length, that share its first min(prefix_len, length) bytes exactly; order: distance, score descending, row
+ * ascending; completion r of input q = input[0, base_len[q]) + term term_idx[q * L + r].  A prefix of 0 or more than 64
+ * bytes gets count 0.  -1 without a device context, for max_edits above 2, or on failure. */
+int nsh_engine_complete_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_inputs, int limit,
+                              int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist, uint32_t* count,
+                              uint32_t* base_len, float* device_ms);
+/* Engine::complete(input, limit): *json_out receives {"limit", "query", "suggestions": [{"distance", "score", "suggestion",
+ * "term"}]} in dump(2) layout (free with nsh_free): auto edits, prefix_len 1; suggestion = base + term. */
+int nsh_engine_complete_json(nsh_engine* e, const char* input, uint64_t input_len, int limit, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

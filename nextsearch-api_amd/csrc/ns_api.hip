@@ -2473,6 +2473,9 @@ struct ns_ac {
     uint64_t* d_fz_sig = nullptr;                // their signatures, in the same order
     uint32_t* d_fz_len_start = nullptr;          // kFzBuckets + 1: first slot of each length
     uint32_t fz_len_start[kFzBuckets + 1] = {};  // the same on the host: sizes a query's slices
+    // completion with a fixed prefix (ns_ac_fuzzy_prefix, prefix_len >= 1): candidates per first byte, counted by the first such call
+    bool fp_first_built = false;
+    uint32_t fp_first[256] = {};
 };
 
 static void ac_free(ns_ac* ac) {
@@ -2725,39 +2728,62 @@ extern "C" int ns_ac_build_fuzzy(ns_ctx* ctx, ns_ac* ac, float* device_ms_out) {
     return NS_OK;
 }
 
-// Measurement knobs of ns_ac_fuzzy (tools/correct_bench.py's A/B; process-wide, never set by the product):
+// Measurement knobs of ns_ac_fuzzy and ns_ac_fuzzy_prefix (the A/B of tools/correct_bench.py and tools/complete_bench.py; process-wide,
+// never set by the product):
 //   NS_FUZZY_NO_SIG=1    the signature filter passes everything
 static bool fz_env_flag(const char* name) {
     const char* v = std::getenv(name);
     return v && v[0] == '1';
 }
 
-extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets, uint32_t n_q,
-                           const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
-                           uint32_t* count_out, float* device_ms_out) {
-    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ac_fuzzy: ctx is NULL");
+// ns_ac_fuzzy (fn = its name, complete = false) and ns_ac_fuzzy_prefix (complete = true): the same arguments, refusals, staging
+// and three launches.  They differ in a query's length window (n - e .. n + e, or n - e and everything longer), in the plan
+// (FzPlan / FpPlan) and in the plan and scan kernels.
+static int ac_fuzzy_call(const char* fn, bool complete, ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets,
+                         uint32_t n_q, const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                         uint32_t* count_out, float* device_ms_out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (!ac || std::find(ctx->acs.begin(), ctx->acs.end(), ac) == ctx->acs.end())
-        return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: table does not belong to this ctx");
-    if (!ac->fz_built) return fail(ctx, NS_E_STATE, "ns_ac_fuzzy: ns_ac_build_fuzzy has not been called on this table");
+        return fail(ctx, NS_E_INVAL, "%s: table does not belong to this ctx", fn);
+    if (!ac->fz_built) return fail(ctx, NS_E_STATE, "%s: ns_ac_build_fuzzy has not been called on this table", fn);
     L = std::max(1u, std::min(L, (uint32_t)kAcTop));
     if (device_ms_out) *device_ms_out = 0.0f;
     if (!n_q) return NS_OK;
-    if (!term_offsets || !max_edits || !idx_out || !dist_out || !count_out) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: null argument");
+    if (!term_offsets || !max_edits || !idx_out || !dist_out || !count_out) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     for (uint32_t q = 0; q < n_q; q++) {
-        if (term_offsets[q + 1] < term_offsets[q]) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: term offsets decrease at %u", q);
-        if (max_edits[q] > kFzMaxEdits) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: max_edits[%u] = %u above %d", q, max_edits[q], kFzMaxEdits);
+        if (term_offsets[q + 1] < term_offsets[q]) return fail(ctx, NS_E_INVAL, "%s: term offsets decrease at %u", fn, q);
+        if (max_edits[q] > kFzMaxEdits) return fail(ctx, NS_E_INVAL, "%s: max_edits[%u] = %u above %d", fn, q, max_edits[q], kFzMaxEdits);
     }
-    if (term_offsets[n_q] != term_offsets[0] && !term_bytes) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: term_bytes is NULL");
+    if (term_offsets[n_q] != term_offsets[0] && !term_bytes) return fail(ctx, NS_E_INVAL, "%s: term_bytes is NULL", fn);
     std::fill(idx_out, idx_out + (size_t)n_q * L, ~0u);
     std::fill(dist_out, dist_out + (size_t)n_q * L, (uint8_t)0xff);
     std::fill(count_out, count_out + n_q, 0u);
-    // the terms that can match something: 1..64 bytes, and some candidate inside the length window
+    const bool by_first = complete && prefix_len >= 1;
+    if (by_first && ac->fz_cands && !ac->fp_first_built) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        uint32_t* d_hist = nullptr;
+        HIPCHK(ctx, hipMalloc((void**)&d_hist, sizeof(ac->fp_first)));
+        hipError_t e = hipMemsetAsync(d_hist, 0, sizeof(ac->fp_first), ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_fp_first_bytes, dim3(std::min(1024u, (ac->fz_cands + 4095) / 4096)), dim3(256), 0, ctx->stream, ac->d_heads,
+                               ac->d_fz_perm, ac->fz_cands, d_hist);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(ac->fp_first, d_hist, sizeof(ac->fp_first), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_hist);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        ac->fp_first_built = true;
+    }
+    // the terms that can match something: 1..64 bytes, and some candidate inside the length window (completion with a fixed
+    // prefix: and some candidate that starts with the term's first byte; the smaller of the two counts bounds its candidates)
     std::vector<uint32_t> rows, window;
     size_t n_bytes = 0;
     for (uint32_t q = 0; q < n_q && ac->fz_cands; q++) {
         const uint32_t len = term_offsets[q + 1] - term_offsets[q], e = max_edits[q];
         if (len == 0 || len > (uint32_t)kFzMaxLen) continue;
-        const uint32_t w = ac->fz_len_start[len + e + 1] - ac->fz_len_start[len > e ? len - e : 0];
+        uint32_t w = ac->fz_len_start[complete ? (uint32_t)kFzBuckets : len + e + 1] - ac->fz_len_start[len > e ? len - e : 0];
+        if (by_first) w = std::min(w, ac->fp_first[term_bytes[term_offsets[q]]]);
         if (!w) continue;
         rows.push_back(q);
         window.push_back(w);
@@ -2765,7 +2791,8 @@ extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, co
     }
     const uint32_t R = (uint32_t)rows.size();
     if (!R) return NS_OK;
-    // slice size: 1024 candidates per workgroup, doubled while the launch would exceed 65536 workgroups
+    // slice size: 1024 candidates per workgroup, doubled while the launch would exceed 65536 workgroups (a query's slices
+    // are sized from an upper bound of its candidates; the ones that the prefix range leaves empty return at once)
     uint32_t slice = 1024;
     uint64_t n_slices = 0;
     for (;; slice *= 2) {
@@ -2773,7 +2800,7 @@ extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, co
         for (uint32_t w : window) n_slices += (w + slice - 1) / slice;
         if (n_slices <= 65536 || slice >= (1u << 30)) break;
     }
-    if (n_slices >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "ns_ac_fuzzy: %llu slices in one call", (unsigned long long)n_slices);
+    if (n_slices >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu slices in one call", fn, (unsigned long long)n_slices);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // device block: [term offsets (R + 1) | slice bases (R + 1) | signatures R | edits R | term bytes] go up in one copy through
@@ -2784,7 +2811,7 @@ extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, co
     const size_t o_bytes = o_ed + al8(R);
     const size_t up = o_bytes + n_bytes;
     const size_t o_plan = (up + 255) & ~(size_t)255;
-    const size_t o_part = o_plan + (((size_t)R * sizeof(FzPlan) + 255) & ~(size_t)255);
+    const size_t o_part = o_plan + (((size_t)R * (complete ? sizeof(FpPlan) : sizeof(FzPlan)) + 255) & ~(size_t)255);
     const size_t o_idx = o_part + (size_t)n_slices * kAcTop * 8;
     const size_t down = (size_t)R * L * 4 + (size_t)R * 4 + (size_t)R * L;
     const size_t block_bytes = o_idx + down;
@@ -2852,13 +2879,23 @@ extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, co
         uint8_t* d_dist = (uint8_t*)(d_cnt + R);
         chk(hipMemcpyAsync(blk, hu, up, hipMemcpyHostToDevice, st));
         if (ev0) chk(hipEventRecord(ev0, st));
-        hipLaunchKernelGGL(k_fz_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
-                           ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FzPlan*)(blk + o_plan));
-        chk(hipGetLastError());
-        hipLaunchKernelGGL(k_fz_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
-                           ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
-                           (const FzPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
-        chk(hipGetLastError());
+        if (complete) {
+            hipLaunchKernelGGL(k_fp_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
+                               ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FpPlan*)(blk + o_plan));
+            chk(hipGetLastError());
+            hipLaunchKernelGGL(k_fp_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
+                               ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
+                               (const FpPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
+            chk(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_fz_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
+                               ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FzPlan*)(blk + o_plan));
+            chk(hipGetLastError());
+            hipLaunchKernelGGL(k_fz_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
+                               ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
+                               (const FzPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
+            chk(hipGetLastError());
+        }
         hipLaunchKernelGGL(k_fz_select, dim3((R + 3) / 4), dim3(256), 0, st, (const uint64_t*)(blk + o_part), d_base, R, L, d_idx, d_dist, d_cnt);
         chk(hipGetLastError());
         if (ev1) chk(hipEventRecord(ev1, st));
@@ -2881,8 +2918,23 @@ extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, co
     if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_fuzzy: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     return NS_OK;
+}
+
+extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets, uint32_t n_q,
+                           const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                           uint32_t* count_out, float* device_ms_out) {
+    return ac_fuzzy_call("ns_ac_fuzzy", false, ctx, ac, term_bytes, term_offsets, n_q, max_edits, prefix_len, L, idx_out, dist_out, count_out,
+                         device_ms_out);
+}
+
+// Typo-tolerant completion: the best L candidates whose PREFIX distance to the query is within max_edits.
+extern "C" int ns_ac_fuzzy_prefix(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes, const uint32_t* prefix_offsets, uint32_t n_q,
+                                  const uint8_t* max_edits, uint32_t prefix_len, uint32_t L, uint32_t* idx_out, uint8_t* dist_out,
+                                  uint32_t* count_out, float* device_ms_out) {
+    return ac_fuzzy_call("ns_ac_fuzzy_prefix", true, ctx, ac, prefix_bytes, prefix_offsets, n_q, max_edits, prefix_len, L, idx_out, dist_out,
+                         count_out, device_ms_out);
 }
 
 #ifdef NS_COUNT

@@ -20,6 +20,12 @@
 // the candidates' lengths; band (2e + 1 cells), three rows and the sliding window of candidate bytes are registers with
 // compile-time indices (templated on e).  Survivors better than the wave's current L-th key are appended to a per-wave
 // LDS buffer that is reduced to its best L when it fills.  k_fz_select merges a query's slices.
+//
+// Typo-tolerant completion (k_fp_plan, k_fp_scan) is a second scan over the same structures with another
+// end condition: the distance is the PREFIX distance pd(q, c) = min over j of osa(q, c[0, j)), so a candidate may be any
+// length from n - e upwards (the bucket of terms past 66 bytes included: signature 0, length from the offsets), the plan
+// has one piece per length bucket (FpPlan) and the signature test is one-sided (a byte class of the query that the
+// candidate lacks costs an edit of its own).  DP rows, queue, keep buffer, merges and k_fz_select are the ones above.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -28,7 +34,7 @@ namespace ns {
 
 constexpr int kFzMaxLen = 64;                  // NS_FUZZY_MAX_LEN: longer query terms never reach the device
 constexpr int kFzMaxEdits = 2;
-constexpr int kFzBuckets = kFzMaxLen + kFzMaxEdits + 2;   // lengths 0..66 and one bucket for everything longer (never scanned)
+constexpr int kFzBuckets = kFzMaxLen + kFzMaxEdits + 2;   // lengths 0..66 and one bucket for everything longer (k_fp_scan only)
 constexpr uint32_t kFzChunk = 4096;            // entries per wave of the build kernels
 constexpr uint64_t kFzSigBits = (1ull << 37) - 1;
 constexpr uint32_t kFzIdxBits = 30;
@@ -40,6 +46,16 @@ struct FzPlan {            // one query's pieces of the permutation, one per len
     uint32_t start[5];
     uint32_t cum[5];       // inclusive running counts; cum[4] = the query's candidates
     uint32_t pad[2];
+};
+
+struct FpPlan {            // completion: one piece per length bucket (a bucket below n - e is empty)
+    uint32_t start[kFzBuckets];
+    uint32_t cum[kFzBuckets];   // inclusive running counts; cum[kFzBuckets - 1] = the query's candidates
+};
+
+struct FpPieces {          // a query's FpPlan, copied to LDS by the scanning workgroup
+    const uint32_t* start;
+    const uint32_t* cum;
 };
 
 __device__ __forceinline__ uint64_t fz_sig_bit(uint32_t c) {
@@ -206,7 +222,10 @@ __device__ __forceinline__ uint32_t fz_load4(const uint8_t* __restrict__ pool, u
 // Banded optimal string alignment of the query qs[0, n) (LDS, uniform) against one candidate per lane: first 8 bytes in
 // `head` (big-endian), the rest at pool[o + 8, o + m).  Row i covers the cells j = i - E .. i + E; returns D[n][m], or a
 // value above E once no cell of two consecutive rows is within E for any lane of the wave.
-template <int E>
+// kPrefix: returns min over j of D[n][j] instead, over the band's columns j = n - E + t that lie in [0, m].  A cell only
+// depends on cells of smaller or equal j, so the cells with j <= m are exact whatever follows the term in the pool; the
+// cells with j > m were computed from those bytes and are masked here, where they would be read.
+template <int E, bool kPrefix = false>
 __device__ __forceinline__ uint32_t fz_osa(const uint8_t* qs, uint32_t n, uint64_t head, uint32_t o, uint32_t m,
                                            const uint8_t* __restrict__ pool) {
     constexpr int B = 2 * E + 1;
@@ -257,9 +276,15 @@ __device__ __forceinline__ uint32_t fz_osa(const uint8_t* qs, uint32_t n, uint64
         if (!__builtin_amdgcn_ballot_w64(min(before, now) <= (uint32_t)E)) { done = i == n; break; }
     }
     uint32_t d = kInf;
-    const int dd = (int)m - (int)n + E;
+    if constexpr (kPrefix) {
+        const int last = (int)min(m, n + (uint32_t)E) - (int)n + E;   // the band cell of column min(m, n + E); >= 0 as m >= n - E
 #pragma unroll
-    for (int t = 0; t < B; t++) d = dd == t ? p1[t] : d;
+        for (int t = 0; t < B; t++) d = t <= last ? min(d, p1[t]) : d;   // a cell of column j < 0 holds kInf
+    } else {
+        const int dd = (int)m - (int)n + E;
+#pragma unroll
+        for (int t = 0; t < B; t++) d = dd == t ? p1[t] : d;
+    }
     return done ? d : kInf;
 }
 
@@ -288,7 +313,8 @@ __device__ __forceinline__ uint64_t fz_reduce(uint64_t* keep, uint32_t& cnt, uin
 }
 
 // The DP on one wave of queued candidates (slot < 0: idle lane), survivors appended to the wave's keep buffer.
-template <int E>
+// kPrefix: the prefix distance; a slot with signature 0 (the bucket past 66 bytes) has its length in the offsets.
+template <int E, bool kPrefix = false>
 __device__ __forceinline__ void fz_verify(int64_t slot, const uint8_t* qs, uint32_t n, const uint32_t* __restrict__ perm,
                                           const uint64_t* __restrict__ psig, const uint64_t* __restrict__ heads,
                                           const uint32_t* __restrict__ offs, const uint8_t* __restrict__ pool,
@@ -297,9 +323,10 @@ __device__ __forceinline__ void fz_verify(int64_t slot, const uint8_t* qs, uint3
     uint64_t key = kAcEmpty;
     if (slot >= 0) {
         const uint32_t idx = perm[slot];
-        const uint32_t m = (uint32_t)(psig[slot] >> 40) & 0xffu;
+        uint32_t m = (uint32_t)(psig[slot] >> 40) & 0xffu;
+        if constexpr (kPrefix) m = psig[slot] ? m : offs[idx + 1] - offs[idx];
         const uint32_t o = m > 8 ? offs[idx] : 0u;
-        const uint32_t d = fz_osa<E>(qs, n, heads[idx], o, m, pool);
+        const uint32_t d = fz_osa<E, kPrefix>(qs, n, heads[idx], o, m, pool);
         if (d <= (uint32_t)E) key = ((uint64_t)d << 62) | ((keys[idx] >> 32) << kFzIdxBits) | idx;
     }
     const bool take = key < worst;   // kAcEmpty is never below worst
@@ -312,8 +339,20 @@ __device__ __forceinline__ void fz_verify(int64_t slot, const uint8_t* qs, uint3
     cnt += add;
 }
 
-template <int E>
-__device__ __forceinline__ void fz_scan_body(const FzPlan& pl, uint64_t p0, uint64_t p1, uint64_t qsig, const uint8_t* qs, uint32_t n,
+// x -> the slot of position x of a query's candidates: the piece with cum[t - 1] <= x < cum[t] (x below the last cum)
+__device__ __forceinline__ uint32_t fp_slot(const FpPieces& pl, uint32_t x) {
+    uint32_t a = 0, b = (uint32_t)kFzBuckets - 1;   // the first t with x < cum[t]
+    while (a < b) {
+        const uint32_t t = (a + b) / 2;
+        if (x < pl.cum[t]) b = t; else a = t + 1;
+    }
+    return pl.start[a] + (x - (a ? pl.cum[a - 1] : 0u));
+}
+
+// Positions [p0, p1) of a query's candidates, dealt to the workgroup's four waves 64 at a time.  kPrefix (Plan =
+// FpPieces): completion's pieces, signature test and distance.
+template <int E, bool kPrefix = false, class Plan>
+__device__ __forceinline__ void fz_scan_body(const Plan& pl, uint64_t p0, uint64_t p1, uint64_t qsig, const uint8_t* qs, uint32_t n,
                                              const uint32_t* __restrict__ perm, const uint64_t* __restrict__ psig,
                                              const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs,
                                              const uint8_t* __restrict__ pool, const uint64_t* __restrict__ keys, uint32_t* queue,
@@ -327,10 +366,16 @@ __device__ __forceinline__ void fz_scan_body(const FzPlan& pl, uint64_t p0, uint
         if (p < p1) {
             const uint32_t x = (uint32_t)p;
             // the piece that holds position x of the query's candidates
-            slot = pl.start[0] + x;
+            if constexpr (kPrefix) {
+                slot = fp_slot(pl, x);
+                const uint64_t cs = psig[slot];   // 0: the bucket past 66 bytes, which has no byte set
+                pass = !use_sig || cs == 0 || __builtin_popcountll(qsig & ~cs & kFzSigBits) <= E;
+            } else {
+                slot = pl.start[0] + x;
 #pragma unroll
-            for (int t = 1; t < 2 * E + 1; t++) slot = x >= pl.cum[t - 1] ? pl.start[t] + (x - pl.cum[t - 1]) : slot;
-            pass = !use_sig || __builtin_popcountll((psig[slot] ^ qsig) & kFzSigBits) <= 2 * E;
+                for (int t = 1; t < 2 * E + 1; t++) slot = x >= pl.cum[t - 1] ? pl.start[t] + (x - pl.cum[t - 1]) : slot;
+                pass = !use_sig || __builtin_popcountll((psig[slot] ^ qsig) & kFzSigBits) <= 2 * E;
+            }
         }
         const uint64_t bal = __builtin_amdgcn_ballot_w64(pass);
         if (pass) queue[queued + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = slot;
@@ -340,13 +385,37 @@ __device__ __forceinline__ void fz_scan_body(const FzPlan& pl, uint64_t p0, uint
             queued -= 64;
             const uint32_t s = queue[queued + lane];
             __builtin_amdgcn_wave_barrier();
-            fz_verify<E>((int64_t)s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
+            fz_verify<E, kPrefix>((int64_t)s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
         }
     }
     if (queued) {
         const int64_t s = lane < queued ? (int64_t)queue[lane] : -1;
         __builtin_amdgcn_wave_barrier();
-        fz_verify<E>(s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
+        fz_verify<E, kPrefix>(s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
+    }
+}
+
+// The end of a slice: each wave's keep buffer reduced to its best L, the four lists merged by wave 0 into part[b * kAcTop ..].
+// k_fp_scan's; k_fz_scan keeps the same lines in its own body (calling this from there reorders a few of its scalar
+// instructions, and that kernel stays the code object it was).
+__device__ __forceinline__ void fz_finish_slice(uint64_t (*keep_all)[kFzKeep], uint64_t* keep, uint32_t& cnt, uint32_t wave, uint32_t lane,
+                                                uint32_t L, uint32_t b, uint64_t* __restrict__ part) {
+    fz_reduce(keep, cnt, lane, L);   // keep[0, L): the wave's best
+    __syncthreads();
+    if (wave == 0) {                 // the four waves' lists, one per lane
+        uint64_t k[kAcTop];
+#pragma unroll
+        for (int i = 0; i < kAcTop; i++) k[i] = (lane < 4 && (uint32_t)i < L) ? keep_all[lane][i] : kAcEmpty;
+        uint64_t best[kAcTop], w2 = kAcEmpty;
+#pragma unroll
+        for (int i = 0; i < kAcTop; i++) best[i] = kAcEmpty;
+        ac_merge(k, L, best, w2);
+        if (lane < (uint32_t)kAcTop) {
+            uint64_t v = best[0];
+#pragma unroll
+            for (int i = 1; i < kAcTop; i++) v = lane == (uint32_t)i ? best[i] : v;
+            part[(uint64_t)b * kAcTop + lane] = v;
+        }
     }
 }
 
@@ -404,6 +473,115 @@ k_fz_scan(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs,
             part[(uint64_t)b * kAcTop + lane] = v;
         }
     }
+}
+
+// Completion's plan.  One wave per query: the fixed prefix's index range [lo, hi), then for every length bucket from
+// n - e upwards (the one past 66 bytes included) the slots of that bucket whose index lies in it.  Lane l has the buckets
+// 2l and 2l + 1.
+__global__ void __launch_bounds__(256) k_fp_plan(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs,
+                                                 const uint8_t* __restrict__ pool, uint32_t n, const uint32_t* __restrict__ perm,
+                                                 const uint32_t* __restrict__ len_start, const uint8_t* __restrict__ qbytes,
+                                                 const uint32_t* __restrict__ qoffs, const uint8_t* __restrict__ qedits, uint32_t n_q,
+                                                 uint32_t prefix_len, FpPlan* __restrict__ plans) {
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (q >= n_q) return;   // wave-uniform
+    const uint8_t* p = qbytes + qoffs[q];
+    const uint32_t qlen = qoffs[q + 1] - qoffs[q];
+    const uint32_t e = qedits[q];
+    const uint32_t plen = prefix_len < qlen ? prefix_len : qlen;
+    uint32_t lo = 0, hi = n;
+    if (plen) {
+        const uint32_t hlen = plen < 8 ? plen : 8;
+        uint64_t ph = 0;
+        for (uint32_t j = 0; j < hlen; j++) ph |= (uint64_t)p[j] << (56 - 8 * j);
+        ac_prefix_range(n, lane, heads, offs, pool, p, plen, ph, ~0ull << (64 - 8 * hlen), lo, hi);
+    }
+    const uint32_t first = qlen > e ? qlen - e : 0u;   // the shortest candidate
+    uint32_t start[2] = {0, 0}, count[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint32_t bk = 2 * lane + h;
+        if (bk < (uint32_t)kFzBuckets && bk >= first) {
+            const uint32_t a = len_start[bk], b = len_start[bk + 1];
+            uint32_t x = a, y = b;             // first slot with perm >= lo
+            while (x < y) { const uint32_t m = x + (y - x) / 2; if (perm[m] < lo) x = m + 1; else y = m; }
+            start[h] = x;
+            y = b;                             // first slot with perm >= hi
+            while (x < y) { const uint32_t m = x + (y - x) / 2; if (perm[m] < hi) x = m + 1; else y = m; }
+            count[h] = x - start[h];
+        }
+    }
+    uint32_t cum = count[0] + count[1];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)cum, d, 64);
+        if (lane >= (uint32_t)d) cum += o;
+    }
+    if (2 * lane + 1 < (uint32_t)kFzBuckets) {   // kFzBuckets is even
+        plans[q].start[2 * lane] = start[0];
+        plans[q].start[2 * lane + 1] = start[1];
+        plans[q].cum[2 * lane] = cum - count[1];
+        plans[q].cum[2 * lane + 1] = cum;
+    }
+}
+
+// hist[b] += the candidates whose first byte is b (a candidate of 0 bytes counts under 0); hist has 256 zeroed entries.  Once per
+// table: with a fixed prefix the host sizes a query's slices from min(length window, candidates that start with its first byte).
+__global__ void __launch_bounds__(256) k_fp_first_bytes(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ perm, uint32_t cands,
+                                                        uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cands; s += (uint64_t)gridDim.x * 256)
+        atomicAdd(&h[(uint32_t)(heads[perm[s]] >> 56)], 1u);
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// Completion's scan: k_fz_scan with the plan of k_fp_plan in LDS.  How a query's slices were sized (slice_base) decides
+// nothing but the work's cut: a slice past the query's candidates returns at once.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4)))
+k_fp_scan(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs, const uint8_t* __restrict__ pool,
+          const uint64_t* __restrict__ keys, const uint32_t* __restrict__ perm, const uint64_t* __restrict__ psig,
+          const uint8_t* __restrict__ qbytes, const uint32_t* __restrict__ qoffs, const uint8_t* __restrict__ qedits,
+          const uint64_t* __restrict__ qsigs, const uint32_t* __restrict__ slice_base, uint32_t n_q, uint32_t slice,
+          const FpPlan* __restrict__ plans, uint32_t L, uint32_t use_sig, uint64_t* __restrict__ part) {
+    __shared__ uint8_t qs[kFzMaxLen];
+    __shared__ uint32_t pstart[kFzBuckets], pcum[kFzBuckets];
+    __shared__ uint32_t queue_all[4][kFzQueue];
+    __shared__ uint64_t keep_all[4][kFzKeep];
+    const uint32_t b = blockIdx.x;
+    uint32_t q = 0, hi = n_q;   // the last q with slice_base[q] <= b
+    while (hi - q > 1) {
+        const uint32_t m = q + (hi - q) / 2;
+        if (slice_base[m] <= b) q = m; else hi = m;
+    }
+    const uint32_t total = plans[q].cum[kFzBuckets - 1];
+    const uint64_t p0 = (uint64_t)(b - slice_base[q]) * slice;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (p0 >= total) {   // uniform: nothing of the query falls into this slice
+        if (threadIdx.x < (uint32_t)kAcTop) part[(uint64_t)b * kAcTop + threadIdx.x] = kAcEmpty;
+        return;
+    }
+    const uint64_t p1 = p0 + slice < total ? p0 + slice : (uint64_t)total;
+    const uint32_t qo = qoffs[q], n = qoffs[q + 1] - qo, e = qedits[q];
+    if (threadIdx.x < n) qs[threadIdx.x] = qbytes[qo + threadIdx.x];
+    if (threadIdx.x < (uint32_t)kFzBuckets) {
+        pstart[threadIdx.x] = plans[q].start[threadIdx.x];
+        pcum[threadIdx.x] = plans[q].cum[threadIdx.x];
+    }
+    __syncthreads();
+    const FpPieces pl{pstart, pcum};
+    const uint64_t qsig = qsigs[q];
+    uint32_t cnt = 0;
+    uint64_t worst = kAcEmpty;
+    uint32_t* queue = queue_all[wave];
+    uint64_t* keep = keep_all[wave];
+    if (e == 0) fz_scan_body<0, true>(pl, p0, p1, qsig, qs, n, perm, psig, heads, offs, pool, keys, queue, keep, cnt, worst, wave, lane, L, use_sig != 0);
+    else if (e == 1) fz_scan_body<1, true>(pl, p0, p1, qsig, qs, n, perm, psig, heads, offs, pool, keys, queue, keep, cnt, worst, wave, lane, L, use_sig != 0);
+    else fz_scan_body<2, true>(pl, p0, p1, qsig, qs, n, perm, psig, heads, offs, pool, keys, queue, keep, cnt, worst, wave, lane, L, use_sig != 0);
+    fz_finish_slice(keep_all, keep, cnt, wave, lane, L, b, part);
 }
 
 // One wave per query: the best L over its slices' lists.

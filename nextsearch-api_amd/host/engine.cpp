@@ -1179,12 +1179,18 @@ struct CorrectPrep {
 };
 }  // namespace
 
-// One sub-batch's host side: the terms normalised; those of 1..kFuzzyMaxLen bytes packed for ns_ac_fuzzy.
-static void correct_prepare(const Engine::QueryView* in, size_t q0, size_t q1, int max_edits, CorrectPrep& cp, ForkJoin* fj) {
+// One sub-batch's host side: the terms normalised; those of 1..kFuzzyMaxLen bytes packed for ns_ac_fuzzy.  base_len (completion):
+// an input is a suggest request, split like suggest_batch's; its prefix is the term and base_len[q] the bytes before it.
+static void correct_prepare(const Engine::QueryView* in, size_t q0, size_t q1, int max_edits, uint32_t* base_len, CorrectPrep& cp, ForkJoin* fj) {
     const size_t Q = q1 - q0;
     std::vector<std::string> norm(Q);
     auto run = [&](size_t a, size_t b) {
-        for (size_t q = a; q < b; q++) nsx::normalize_token(in[q0 + q].p, in[q0 + q].n, norm[q]);
+        for (size_t q = a; q < b; q++) {
+            if (!base_len) { nsx::normalize_token(in[q0 + q].p, in[q0 + q].n, norm[q]); continue; }
+            size_t base = 0;
+            nsx::split_suggest_input(in[q0 + q].p, in[q0 + q].n, base, norm[q]);
+            base_len[q0 + q] = (uint32_t)base;
+        }
     };
     const unsigned nt = fj ? std::min<unsigned>(fj->width(), (unsigned)std::max<size_t>(1, Q / 2048)) : 1u;
     if (nt <= 1) run(0, Q);
@@ -1205,11 +1211,26 @@ static void correct_prepare(const Engine::QueryView* in, size_t q0, size_t q1, i
 
 bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
                            uint32_t* count, float* device_ms) {
+    return fuzzy_batch("correct_batch", terms, Q, limit, max_edits, prefix_len, term_idx, dist, count, nullptr, device_ms);
+}
+
+bool Engine::complete_batch(const QueryView* inputs, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
+                            uint32_t* count, uint32_t* base_len, float* device_ms) {
+    if (Q && !base_len) { std::lock_guard<std::recursive_mutex> lock(mtx_); err_ = "complete_batch: null argument"; return false; }
+    return fuzzy_batch("complete_batch", inputs, Q, limit, max_edits, prefix_len, term_idx, dist, count, base_len, device_ms);
+}
+
+// correct_batch (base_len null: ns_ac_fuzzy on the normalised terms) and complete_batch (ns_ac_fuzzy_prefix on the inputs' prefixes).
+bool Engine::fuzzy_batch(const char* fn, const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx,
+                         uint8_t* dist, uint32_t* count, uint32_t* base_len, float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
-    if (!ctx_ || !ac_) { err_ = "no device context: this engine has no CPU spelling correction path"; return false; }
-    if (Q && (!terms || !term_idx || !dist || !count)) { err_ = "correct_batch: null argument"; return false; }
-    if (max_edits > nsx::kFuzzyMaxEdits) { err_ = "correct_batch: max_edits " + std::to_string(max_edits) + " above " + std::to_string(nsx::kFuzzyMaxEdits); return false; }
+    if (!ctx_ || !ac_) {
+        err_ = base_len ? "no device context: this engine has no CPU completion path" : "no device context: this engine has no CPU spelling correction path";
+        return false;
+    }
+    if (Q && (!terms || !term_idx || !dist || !count)) { err_ = std::string(fn) + ": null argument"; return false; }
+    if (max_edits > nsx::kFuzzyMaxEdits) { err_ = std::string(fn) + ": max_edits " + std::to_string(max_edits) + " above " + std::to_string(nsx::kFuzzyMaxEdits); return false; }
     const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
     const uint32_t plen = prefix_len > 0 ? (uint32_t)prefix_len : 0u;
     if (Q == 0) return true;
@@ -1220,7 +1241,8 @@ bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_
     const size_t n_sub = Q >= 2 * kSub ? (Q + kSub - 1) / kSub : 1;
     CorrectPrep cp[2];
     float dev_ms = 0.0f;
-    // the device's part of sub-batch i: ns_ac_fuzzy on the terms sent, answers scattered to the caller's rows
+    // the device's part of sub-batch i: ns_ac_fuzzy / ns_ac_fuzzy_prefix on the terms sent, answers scattered to the caller's rows
+    const char* call = base_len ? "ns_ac_fuzzy_prefix: " : "ns_ac_fuzzy: ";
     auto device = [&](size_t i, CorrectPrep& p, std::string& err) -> bool {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
         for (size_t q = a; q < b; q++) count[q] = 0;
@@ -1232,9 +1254,9 @@ bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_
         p.dist.resize((size_t)R * L);
         p.cnt.resize(R);
         float ms = 0.0f;
-        const int rc = ns_ac_fuzzy(ctx_, ac_, p.bytes.data(), p.offs.data(), R, p.edits.data(), plen, L, p.idx.data(), p.dist.data(), p.cnt.data(),
-                                   device_ms ? &ms : nullptr);
-        if (rc != NS_OK) { err = std::string("ns_ac_fuzzy: ") + ns_last_error(ctx_); return false; }
+        const int rc = (base_len ? ns_ac_fuzzy_prefix : ns_ac_fuzzy)(ctx_, ac_, p.bytes.data(), p.offs.data(), R, p.edits.data(), plen, L, p.idx.data(),
+                                                                    p.dist.data(), p.cnt.data(), device_ms ? &ms : nullptr);
+        if (rc != NS_OK) { err = std::string(call) + ns_last_error(ctx_); return false; }
         dev_ms += ms;
         for (uint32_t r = 0; r < R; r++) {
             const size_t q = a + p.rows[r];
@@ -1244,7 +1266,7 @@ bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_
         }
         return true;
     };
-    correct_prepare(terms, 0, Q * 1 / n_sub, max_edits, cp[0], fj);
+    correct_prepare(terms, 0, Q * 1 / n_sub, max_edits, base_len, cp[0], fj);
     bool ok = true;
     for (size_t i = 0; i < n_sub && ok; i++) {
         CorrectPrep& cur = cp[i & 1];
@@ -1252,7 +1274,7 @@ bool Engine::correct_batch(const QueryView* terms, size_t Q, int limit, int max_
             std::string err;
             bool dok = true;
             std::thread dev([&]() { dok = device(i, cur, err); });
-            correct_prepare(terms, Q * (i + 1) / n_sub, Q * (i + 2) / n_sub, max_edits, cp[(i + 1) & 1], fj);
+            correct_prepare(terms, Q * (i + 1) / n_sub, Q * (i + 2) / n_sub, max_edits, base_len, cp[(i + 1) & 1], fj);
             dev.join();
             if (!dok) { err_ = err; ok = false; }
         } else if (!device(i, cur, err_)) {
@@ -1335,6 +1357,52 @@ bool Engine::did_you_mean_text(const std::string& query, int limit, std::string&
 std::string Engine::did_you_mean(const std::string& query, int limit) {
     std::string body;
     if (!did_you_mean_text(query, limit, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- typo-tolerant completion ----------------------------------------------------------------------------
+bool Engine::complete_text(const std::string& input, int limit, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    const uint32_t L = (uint32_t)nsx::clamp_suggest_limit(limit);
+    const QueryView v{input.data(), input.size()};
+    uint32_t idx[nsx::kSuggestMaxLimit], cnt = 0, base_len = 0;
+    uint8_t dist[nsx::kSuggestMaxLimit];
+    // auto edits; the first typed byte is trusted: one request scans the terms that start with it, not the table
+    if (!complete_batch(&v, 1, limit, -1, 1, idx, dist, &cnt, &base_len)) { body = err_; return false; }
+    body.clear();
+    body += "{\n  \"limit\": " + std::to_string(L) + ",\n  \"query\": ";
+    json_escape(body, input);
+    body += ",\n  \"suggestions\": ";
+    if (cnt == 0) {
+        body += "[]";
+    } else {
+        body += "[\n";
+        std::string s;
+        for (uint32_t r = 0; r < cnt; r++) {
+            const std::string term(suggest_table.term(idx[r]), suggest_table.term_len(idx[r]));
+            s.assign(input, 0, base_len);
+            s += term;
+            body += "    {\n      \"distance\": " + std::to_string((unsigned)dist[r]) + ",\n      \"score\": " + std::to_string(suggest_table.score[idx[r]]) +
+                    ",\n      \"suggestion\": ";
+            json_escape(body, s);
+            body += ",\n      \"term\": ";
+            json_escape(body, term);
+            body += r + 1 < cnt ? "\n    },\n" : "\n    }\n";
+        }
+        body += "  ]";
+    }
+    body += "\n}";
+    return true;
+}
+
+std::string Engine::complete(const std::string& input, int limit) {
+    std::string body;
+    if (!complete_text(input, limit, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

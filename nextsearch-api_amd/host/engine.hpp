@@ -214,6 +214,19 @@ public:
     std::string did_you_mean(const std::string& query, int limit);
     bool did_you_mean_text(const std::string& query, int limit, std::string& body);
 
+    // Typo-tolerant completion (csrc/ns_fuzzy.hip k_fp_*): suggest for a prefix that is still being typed and
+    // already has a typo in it.  An input is split like suggest_batch's (last alnum run, normalised = the prefix; the bytes
+    // before it = the base, base_len[q]); the answer is the L = clamp(limit, 1, 10) best candidates of suggest_table some
+    // prefix of which is within max_edits (0..2; -1 = auto by the normalised prefix length, as correct_batch) of the
+    // prefix, and which share its first min(prefix_len, length) bytes exactly.  Rows and ranking as correct_batch's.
+    bool complete_batch(const QueryView* inputs, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
+                        uint32_t* count, uint32_t* base_len, float* device_ms = nullptr);
+    // JSON text {"limit", "query", "suggestions": [{"distance", "score", "suggestion", "term"}]} in dump(2) layout;
+    // suggestion = base + term.  Auto edits, prefix_len 1 (the first typed byte is trusted).  Without a device context:
+    // {"error": ...} (complete_text: false, body = the message).  suggest() itself is unchanged.
+    std::string complete(const std::string& input, int limit);
+    bool complete_text(const std::string& input, int limit, std::string& body);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -257,6 +270,8 @@ private:
     ns_ac* ac_ = nullptr;    // suggest_table on ctx_ (ns_ac_upload)
     bool ac_fuzzy_ = false;  // ns_ac_build_fuzzy has run on ac_
     bool ensure_fuzzy();
+    bool fuzzy_batch(const char* fn, const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
+                     uint32_t* count, uint32_t* base_len, float* device_ms);
     std::vector<ns_seg*> dev_segs_;
     // further devices holding a replica of the index (multi-device engine): context + segments each
     struct Replica { int device = 0; ns_ctx* ctx = nullptr; std::vector<ns_seg*> segs; };

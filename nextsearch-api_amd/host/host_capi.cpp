@@ -614,6 +614,35 @@ extern "C" int nsh_engine_did_you_mean_json(nsh_engine* e, const char* query, ui
 } NSH_CATCH(e, "nsh_engine_did_you_mean_json", -1)
 }
 
+extern "C" int nsh_engine_complete_batch(nsh_engine* e, const char* bytes, const uint64_t* offsets, uint32_t n_inputs, int limit,
+                                         int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist, uint32_t* count,
+                                         uint32_t* base_len, float* device_ms) { try {
+    if (!e || (n_inputs && (!offsets || !term_idx || !dist || !count || !base_len))) return -1;
+    std::vector<nextsearch::Engine::QueryView> views(n_inputs);
+    for (uint32_t q = 0; q < n_inputs; q++) {
+        if (offsets[q + 1] < offsets[q] || (offsets[q + 1] > offsets[q] && !bytes)) { nsh_set_err(e, "nsh_engine_complete_batch: bad offsets"); return -1; }
+        views[q] = {bytes ? bytes + offsets[q] : "", (size_t)(offsets[q + 1] - offsets[q])};
+    }
+    if (!e->eng.complete_batch(views.data(), n_inputs, limit, max_edits, prefix_len, term_idx, dist, count, base_len, device_ms)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_complete_batch", -1)
+}
+
+extern "C" int nsh_engine_complete_json(nsh_engine* e, const char* input, uint64_t input_len, int limit, char** json_out) { try {
+    if (!e || !json_out || (input_len && !input)) return -1;
+    std::string s;
+    const bool ok = e->eng.complete_text(std::string(input ? input : "", (size_t)input_len), limit, s);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); *json_out = nullptr; return -1; }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_complete_json", -1)
+}
+
 extern "C" int nsh_correct_auto_edits(uint64_t normalized_len) { return nsx::correct_auto_edits((size_t)normalized_len); }
 
 extern "C" double nsh_engine_correct_build_ms(nsh_engine* e) { return e ? e->eng.correct_build_ms : 0.0; }

@@ -63,6 +63,15 @@ int main(int argc, char** argv) {
         std::printf("%s\n", body.c_str());
         return 0;
     }
+    if (argc >= 4 && std::strcmp(argv[1], "complete") == 0) {
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        std::string body;
+        if (!eng.complete_text(argv[3], argc > 4 ? std::atoi(argv[4]) : 5, body)) { std::fprintf(stderr, "complete failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
     if (argc >= 3 && std::strcmp(argv[1], "compact") == 0) {
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
@@ -163,6 +172,6 @@ int main(int argc, char** argv) {
                     Q, K, refs.size(), reload_ms, p, p > 0 ? Q / (p * 1e-3) : 0.0, f, f > 0 ? Q / (f * 1e-3) : 0.0, reps, (unsigned long long)check);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n       %s complete <index_dir> <input> [limit]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
 }

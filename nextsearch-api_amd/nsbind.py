@@ -61,7 +61,7 @@ HIP_SYMBOLS = [
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
     "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores",
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
-    "ns_ac_upload", "ns_ac_suggest", "ns_ac_release", "ns_ac_build_fuzzy", "ns_ac_fuzzy",
+    "ns_ac_upload", "ns_ac_suggest", "ns_ac_release", "ns_ac_build_fuzzy", "ns_ac_fuzzy", "ns_ac_fuzzy_prefix",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
     "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort",
     "ns_forward_merge_keep",
@@ -76,6 +76,7 @@ HOST_SYMBOLS = [
     "nsh_engine_semantic_info", "nsh_engine_expand", "nsh_engine_semantic_row", "nsh_engine_set_cache", "nsh_engine_cache_size",
     "nsh_engine_suggest_json", "nsh_engine_suggest_batch", "nsh_engine_suggest_table", "nsh_suggest_split", "nsh_suggest_clamp_limit",
     "nsh_engine_correct_batch", "nsh_engine_did_you_mean_json", "nsh_correct_auto_edits", "nsh_engine_correct_build_ms",
+    "nsh_engine_complete_batch", "nsh_engine_complete_json",
     "nsh_index_documents", "nsh_index_error", "nsh_engine_open_noload", "nsh_engine_add_documents",
     "nsh_merge_segments", "nsh_compact_error", "nsh_engine_compact",
     "nsh_engine_find_documents", "nsh_engine_delete_documents", "nsh_engine_delete_by_id",
@@ -141,6 +142,7 @@ def hip_lib():
         L.ns_ac_release.argtypes = [vp, vp]
         L.ns_ac_build_fuzzy.argtypes = [vp, vp, C.POINTER(C.c_float)]
         L.ns_ac_fuzzy.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_ac_fuzzy_prefix.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_last_error.argtypes = [vp]
         L.ns_last_error.restype = C.c_char_p
         L.ns_device_name.argtypes = [vp]
@@ -314,6 +316,8 @@ def host_lib():
         L.nsh_correct_auto_edits.restype = i32
         L.nsh_engine_correct_build_ms.argtypes = [vp]
         L.nsh_engine_correct_build_ms.restype = C.c_double
+        L.nsh_engine_complete_batch.argtypes = [vp, C.c_char_p, vp, u32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_complete_json.argtypes = [vp, C.c_char_p, u64, i32, C.POINTER(vp)]
         _host = L
     return _host
 
@@ -720,6 +724,43 @@ class Engine:
         self._L.nsh_free(out)
         return s
 
+    def complete_batch_raw(self, inputs, limit, max_edits=-1, prefix_len=1, flat=None):
+        """Engine::complete_batch -> (term_idx uint32 [Q, L], dist uint8 [Q, L], count uint32 [Q], base_len uint32 [Q], kernel ms);
+        max_edits -1 = auto; flat: flat_inputs(inputs)"""
+        data, offs = flat if flat is not None else _flat_bytes(inputs)
+        Q, L = len(inputs), clamp_suggest_limit(limit)
+        idx = np.empty((Q, L), dtype=np.uint32)
+        dist = np.empty((Q, L), dtype=np.uint8)
+        cnt = np.empty(Q, dtype=np.uint32)
+        base = np.empty(Q, dtype=np.uint32)
+        ms = C.c_float(0.0)
+        rc = self._L.nsh_engine_complete_batch(self.h, data, offs.ctypes.data, Q, int(limit), int(max_edits), int(prefix_len),
+                                               idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data, base.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"complete_batch failed: {self.error()}")
+        return idx, dist, cnt, base, ms.value
+
+    def complete_batch(self, inputs, limit, max_edits=-1, prefix_len=1, table=None):
+        """-> one list of (completion bytes, distance) per input, best first; `table` = suggest_table()[0]"""
+        words = table if table is not None else self.suggest_table()[0]
+        idx, dist, cnt, base, _ = self.complete_batch_raw(inputs, limit, max_edits, prefix_len)
+        out = []
+        for q, s in enumerate(inputs):
+            b = _as_bytes(s)[:int(base[q])]
+            out.append([(b + words[int(idx[q, r])], int(dist[q, r])) for r in range(int(cnt[q]))])
+        return out
+
+    def complete_json(self, user_input, limit=5):
+        """Engine::complete(input, limit) as bytes (the input: str or raw bytes)."""
+        b = _as_bytes(user_input)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_complete_json(self.h, b, len(b), int(limit), C.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"complete failed: {self.error()}")
+        s = C.string_at(out)
+        self._L.nsh_free(out)
+        return s
+
     def correct_build_ms(self):
         """time of the corrector's lazy build since the last reload (0.0: not built yet)"""
         return self._L.nsh_engine_correct_build_ms(self.h)
@@ -1102,6 +1143,23 @@ class AcTable:
                                    idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data, C.byref(ms))
         if rc != NS_OK:
             raise RuntimeError(f"ns_ac_fuzzy rc={rc}: {hip_lib().ns_last_error(self.ctx).decode()}")
+        return idx, dist, cnt, ms.value
+
+    def fuzzy_prefix(self, prefixes, max_edits, prefix_len, L):
+        """ns_ac_fuzzy_prefix -> (idx uint32 [n_q, clamp(L)], dist uint8 [n_q, clamp(L)], count uint32 [n_q], kernel ms); max_edits:
+        one int or one per prefix; raises on failure (the rc in the message)"""
+        data, offs = _flat_bytes(prefixes)
+        offs32 = offs.astype(np.uint32)
+        n_q, W = len(prefixes), clamp_suggest_limit(L)
+        ed = np.ascontiguousarray(np.broadcast_to(np.asarray(max_edits, dtype=np.uint8), (n_q,)))
+        idx = np.empty((n_q, W), dtype=np.uint32)
+        dist = np.empty((n_q, W), dtype=np.uint8)
+        cnt = np.empty(n_q, dtype=np.uint32)
+        ms = C.c_float(0.0)
+        rc = hip_lib().ns_ac_fuzzy_prefix(self.ctx, self.h, data if data else None, offs32.ctypes.data, n_q, ed.ctypes.data, int(prefix_len),
+                                          int(L), idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data, C.byref(ms))
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_ac_fuzzy_prefix rc={rc}: {hip_lib().ns_last_error(self.ctx).decode()}")
         return idx, dist, cnt, ms.value
 
     def close(self):
