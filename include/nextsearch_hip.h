@@ -465,6 +465,34 @@ int ns_ctx_use_docsort(ns_ctx* ctx, int on);
  *     as handed in, before the filter: the counts of dropped documents are needed to find the surviving pairs. */
 int ns_forward_merge_keep(ns_ctx* ctx, const ns_forward_src* src, const uint32_t* const* keep, uint32_t n_src, ns_forward** out);
 
+/* "More like this" (csrc/ns_similar.hip): for a batch of documents of ONE segment the most telling terms
+ * of each, picked from the document's forward pairs — the step in front of a weighted OR search over those terms.
+ * ns_docterms_upload makes a device copy of the segment: the pairs, a document offset array built from src->counts, and
+ * df[n_terms] / idf[n_terms] by term id (the caller computes idf on the host: bm25_idf(N, df) with glibc logf, the value
+ * search uses; no logf runs on the device).  src->doc_len, term_bytes and term_offsets are not read.  Structural checks
+ * and limits are ns_forward_merge's (counts that sum to n_pairs; pairs below 2^32 - 4096, documents below 2^32 - 1, terms
+ * below 2^31); a termId >= n_terms is found by a kernel at upload time and refused with NS_E_INVAL, so that selection never
+ * indexes df / idf out of range.  An empty source (no document, or documents without pairs) is valid.
+ * RULE (host/similar.hpp is the authority): a pair (t, tf) qualifies when tf >= max(min_tf, 1), min_df <= df[t] <= max_df,
+ * df[t] >= 1 and 0 < idf[t] < inf.  Its weight is w = (float)tf * idf[t], one fp32 multiply.  The selection is the first
+ * T = clamp(max_terms, 1, 32) qualifying pairs by (bit pattern of w descending, termId ascending).
+ * ns_docterms_select: host arrays in and out; row i answers doc_ids[i] (the same document may be listed any number of
+ * times): term_out[i * T + r], w_out[i * T + r] for r < count_out[i], ~0u and 0.0f past the count.  A doc id >= n_docs
+ * returns NS_E_INVAL before anything is launched; n == 0 returns NS_OK.  Synchronous.  device_ms_out (may be NULL): the
+ * kernels' time.
+ * Lifetime: as ns_forward handles — the ctx keeps a list of its live handles, ns_ctx_destroy frees their device memory and
+ * orphans them; an orphaned handle fails ns_docterms_select with NS_E_STATE (message: ns_last_error(NULL)) and is freed by
+ * ns_docterms_destroy without touching the ctx. */
+typedef struct ns_docterms ns_docterms;
+int ns_docterms_upload(ns_ctx* ctx, const ns_forward_src* src, const uint32_t* df, const float* idf, ns_docterms** out);
+int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint32_t n, uint32_t max_terms, uint32_t min_tf, uint32_t min_df,
+                       uint32_t max_df, uint32_t* term_out /* n * T */, float* w_out /* n * T */, uint32_t* count_out /* n */,
+                       float* device_ms_out);
+void ns_docterms_destroy(ns_docterms* h);
+/* Documents of at most this many pairs are streamed by one wave, longer ones by a workgroup (the tests' size classes; a
+ * document of at most 64 pairs is one chunk of the wave's stream). */
+uint32_t ns_docterms_doc_cut(void);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -269,6 +269,42 @@ int nsh_engine_complete_batch(nsh_engine* e, const char* bytes, const uint64_t* 
  * "term"}]} in dump(2) layout (free with nsh_free): auto edits, prefix_len 1; suggestion = base + term. */
 int nsh_engine_complete_json(nsh_engine* e, const char* input, uint64_t input_len, int limit, char** json_out);
 
+/* "More like this" (host/similar.hpp is the rule, csrc/ns_similar.hip runs it on the device).
+ * nsh_similar_select_host: the selection rule on one host thread, over the arrays ns_docterms_upload / ns_docterms_select
+ * take: counts[n_docs] and pairs (u32 {termId, tf} x n_pairs) of a segment's forward index, df[n_terms] / idf[n_terms] by
+ * term id, doc_ids[n]; term_out / w_out n x T with T = nsh_similar_clamp_terms(max_terms), count_out[n]; rows padded
+ * with ~0u / 0.0f.  -1 for counts that do not sum to n_pairs, a doc id >= n_docs or a termId >= n_terms. */
+int nsh_similar_select_host(const uint32_t* counts, uint32_t n_docs, const uint32_t* pairs, uint64_t n_pairs, const uint32_t* df,
+                            const float* idf, uint32_t n_terms, const uint32_t* doc_ids, uint32_t n, uint32_t max_terms,
+                            uint32_t min_tf, uint32_t min_df, uint32_t max_df, uint32_t* term_out, float* w_out, uint32_t* count_out);
+uint32_t nsh_similar_clamp_terms(uint32_t max_terms);   /* 1..32 */
+int nsh_similar_clamp_k(int k);                          /* 1..99: the search behind it runs with k + 1 */
+/* the query weight of a selected term: 1.0f, or with boost w / w_first (one fp32 division) */
+float nsh_similar_qweight(float w, float w_first, int boost);
+/* The defaults of Engine::more_like_this (any output may be NULL). */
+void nsh_similar_defaults(uint32_t* max_terms, uint32_t* min_tf, uint32_t* min_df, uint32_t* max_df, int* boost);
+/* df / idf by term id of segment seg (manifest position), as similar_batch uploads them: the segment's own lexicon entry of
+ * terms.bin[t], idf = bm25_idf(N, df); a term without an entry has df 0 and idf 0.  Returns the segment's number of terms
+ * and fills up to cap entries of each array (either may be NULL); -1 when the segment has no forward.bin / terms.bin (the
+ * message names it).  Host only. */
+int64_t nsh_engine_similar_term_stats(nsh_engine* e, uint32_t seg, uint32_t* df_out, float* idf_out, uint64_t cap);
+/* Engine::similar_batch: source q = (manifest position, docId) = (seg_doc[2q], seg_doc[2q + 1]).  With K = nsh_similar_clamp_k(k):
+ * hits n x K (unused tail entries {-inf, ~0, ~0}), nhits[n], found[n], usable[n] (0: nothing selected).  Optional (each may be
+ * NULL): term_count[n] and term_w[n x T] (the selected terms' weights w = tf * idf, 0.0f past the count) and, malloc'ed
+ * (nsh_free), *term_bytes_out / *term_offsets_out: the selected terms of all sources back to back, source-major in selection
+ * order, term j = bytes[offsets[j] .. offsets[j + 1]), sum(term_count) + 1 offsets.  -1 for a pair out of range (nothing runs),
+ * a segment without forward files, no device, or on failure. */
+int nsh_engine_similar_batch(nsh_engine* e, const uint32_t* seg_doc, uint64_t n, int k, uint32_t max_terms, uint32_t min_tf,
+                             uint32_t min_df, uint32_t max_df, int boost, ns_hit* hits, uint32_t* nhits, uint64_t* found,
+                             uint8_t* usable, uint32_t* term_count, float* term_w, char** term_bytes_out, uint64_t** term_offsets_out);
+/* Engine::more_like_this(uid, k): *json_out receives {"found", "k", "query_terms": [{"term", "weight"}], "results", "segments",
+ * "source": {"cord_uid", "docId", "segment"}} in dump(2) layout (free with nsh_free); default options; the first document that
+ * carries the uid is the source.  -1 for an unknown uid and on failure (nsh_engine_error has the message). */
+int nsh_engine_more_like_this_json(nsh_engine* e, const char* uid, uint64_t uid_len, int k, char** json_out);
+/* Frees the device copies similar_batch built (reload does too); the count of segments that have one right now. */
+void nsh_engine_release_similar(nsh_engine* e);
+uint64_t nsh_engine_similar_segments_on_device(nsh_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

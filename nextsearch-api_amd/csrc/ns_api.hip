@@ -25,6 +25,7 @@
 #include "ns_ingest.hip"
 #include "ns_compact.hip"
 #include "ns_delete.hip"
+#include "ns_similar.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
@@ -115,11 +116,13 @@ struct ns_ctx {
     std::vector<ns_ac*> acs;   // autocomplete tables (ns_ac_upload): owned by the ctx, freed by ns_ac_release or ns_ctx_destroy
     std::vector<ns_forward*> fwds;   // live forward-index handles (ns_forward_build, ns_forward_merge): orphaned, not freed, by ns_ctx_destroy
     bool cp_inplace = true;          // ns_forward_merge sorts documents up to kCpDocCut pairs where they lie (ns_ctx_use_docsort)
+    std::vector<ns_docterms*> dts;   // live ns_docterms handles (ns_docterms_upload): orphaned, not freed, by ns_ctx_destroy
 };
 
 static thread_local std::string g_create_err;
 static void ac_free_fwd(ns_ac* ac);
 static void forward_orphan_fwd(ns_forward* f);
+static void docterms_orphan_fwd(ns_docterms* h);
 static void seg_free_device_fwd(ns_seg* s);
 static void seg_free_staging_fwd(ns_seg* s);
 
@@ -255,6 +258,7 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
     }
     for (ns_ac* ac : ctx->acs) ac_free_fwd(ac);   // tables still held: their handles die with the ctx
     for (ns_forward* f : ctx->fwds) forward_orphan_fwd(f);   // their device memory goes; the handles stay valid for ns_forward_destroy
+    for (ns_docterms* h : ctx->dts) docterms_orphan_fwd(h);  // the same for ns_docterms handles
     for (auto& blk : ctx->pool) (void)hipFree(blk.p);
     if (ctx->h_up) (void)hipHostFree(ctx->h_up);
     if (ctx->h_down) (void)hipHostFree(ctx->h_down);
@@ -2318,6 +2322,155 @@ extern "C" int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postin
     if (in.kept_docs) HIPCHK(ctx, hipMemcpy(counts.data(), fwd->d_cnt, (size_t)in.kept_docs * 4, hipMemcpyDeviceToHost));
     return invert_run(ctx, counts.data(), in.kept_docs, nullptr, in.n_pairs, in.n_terms, df_out, postings_out, kept_out, device_ms_out, nullptr,
                       in.n_pairs ? fwd->d_pairs : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// "More like this": the most telling terms of a batch of documents (csrc/ns_similar.hip)
+struct ns_docterms {
+    ns_ctx* ctx = nullptr;          // nullptr: orphaned by ns_ctx_destroy (the device arrays below are gone)
+    uint32_t n_docs = 0, n_terms = 0, n_pairs = 0;
+    std::vector<uint32_t> doc_off;  // n_docs + 1: the host keeps the offsets too (the size class of a listed document)
+    uint2* d_pairs = nullptr;       // n_pairs {termId, tf}
+    uint32_t* d_off = nullptr;      // n_docs + 1
+    uint32_t* d_df = nullptr;       // n_terms
+    float* d_idf = nullptr;         // n_terms
+};
+
+static void docterms_free_device(ns_docterms* h) {
+    (void)hipFree(h->d_pairs); (void)hipFree(h->d_off); (void)hipFree(h->d_df); (void)hipFree(h->d_idf);
+    h->d_pairs = nullptr; h->d_off = h->d_df = nullptr; h->d_idf = nullptr;
+}
+static void docterms_orphan_fwd(ns_docterms* h) { docterms_free_device(h); h->ctx = nullptr; }
+
+extern "C" uint32_t ns_docterms_doc_cut(void) { return kMlDocCut; }
+
+extern "C" int ns_docterms_upload(ns_ctx* ctx, const ns_forward_src* src, const uint32_t* df, const float* idf, ns_docterms** out) {
+    const char* fn = "ns_docterms_upload";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (!src) return fail(ctx, NS_E_INVAL, "%s: src is NULL", fn);
+    const ns_forward_src& S = *src;
+    // the structural checks and limits of ns_forward_merge (the term bytes are not needed here)
+    if (S.n_pairs >= (1ull << 32) - kIvTile) return fail(ctx, NS_E_INVAL, "%s: more than %llu pairs; this build indexes pairs with 32 bits", fn, (unsigned long long)((1ull << 32) - kIvTile - 1));
+    if (S.n_docs == 0xFFFFFFFFu) return fail(ctx, NS_E_INVAL, "%s: %u documents; docIds are 32 bits wide (below 2^32 - 1)", fn, S.n_docs);
+    if (S.n_terms >= (1u << 31)) return fail(ctx, NS_E_INVAL, "%s: %u terms; the dictionary holds fewer than 2^31", fn, S.n_terms);
+    if ((S.n_docs && !S.counts) || (S.n_pairs && !S.pairs) || (S.n_terms && (!df || !idf))) return fail(ctx, NS_E_INVAL, "%s: null array", fn);
+    ns_docterms* h = new ns_docterms();
+    h->doc_off.assign((size_t)S.n_docs + 1, 0u);
+    uint64_t sum = 0;
+    for (uint32_t j = 0; j < S.n_docs; j++) {
+        sum += S.counts[j];
+        if (sum > S.n_pairs) break;
+        h->doc_off[j + 1] = (uint32_t)sum;
+    }
+    if (sum != S.n_pairs) { delete h; return fail(ctx, NS_E_INVAL, "%s: the per-document counts do not sum to n_pairs = %llu", fn, (unsigned long long)S.n_pairs); }
+    h->n_docs = S.n_docs; h->n_terms = S.n_terms; h->n_pairs = (uint32_t)S.n_pairs;
+    hipError_t e = hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    uint32_t* d_bad = nullptr;
+    uint32_t bad = 0;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (e == hipSuccess) chk(hipMalloc((void**)&h->d_off, h->doc_off.size() * 4));
+    if (h->n_pairs) chk(hipMalloc((void**)&h->d_pairs, (size_t)h->n_pairs * 8));
+    if (h->n_terms) { chk(hipMalloc((void**)&h->d_df, (size_t)h->n_terms * 4)); chk(hipMalloc((void**)&h->d_idf, (size_t)h->n_terms * 4)); }
+    chk(hipMalloc((void**)&d_bad, 4));
+    if (e == hipSuccess) {
+        chk(hipMemcpyAsync(h->d_off, h->doc_off.data(), h->doc_off.size() * 4, hipMemcpyHostToDevice, st));
+        if (h->n_pairs) chk(hipMemcpyAsync(h->d_pairs, S.pairs, (size_t)h->n_pairs * 8, hipMemcpyHostToDevice, st));
+        if (h->n_terms) {
+            chk(hipMemcpyAsync(h->d_df, df, (size_t)h->n_terms * 4, hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(h->d_idf, idf, (size_t)h->n_terms * 4, hipMemcpyHostToDevice, st));
+        }
+        chk(hipMemsetAsync(d_bad, 0, 4, st));
+        if (e == hipSuccess && h->n_pairs) {
+            hipLaunchKernelGGL(k_ml_check, dim3((h->n_pairs + 255) / 256), dim3(256), 0, st, h->d_pairs, h->n_pairs, h->n_terms, d_bad);
+            chk(hipGetLastError());
+        }
+        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (e == hipSuccess || d_bad) { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host arrays are the caller's: nothing may still read them)
+    (void)hipFree(d_bad);
+    if (e != hipSuccess || bad) {
+        docterms_free_device(h);
+        delete h;
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return fail(ctx, NS_E_INVAL, "%s: a pair names a termId >= n_terms = %u", fn, S.n_terms);
+    }
+    h->ctx = ctx;
+    ctx->dts.push_back(h);
+    *out = h;
+    return NS_OK;
+}
+
+extern "C" void ns_docterms_destroy(ns_docterms* h) {
+    if (!h) return;
+    if (ns_ctx* ctx = h->ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        auto it = std::find(ctx->dts.begin(), ctx->dts.end(), h);
+        if (it != ctx->dts.end()) ctx->dts.erase(it);
+        docterms_free_device(h);
+    }
+    delete h;
+}
+
+extern "C" int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint32_t n, uint32_t max_terms, uint32_t min_tf, uint32_t min_df,
+                                  uint32_t max_df, uint32_t* term_out, float* w_out, uint32_t* count_out, float* device_ms_out) {
+    const char* fn = "ns_docterms_select";
+    if (!h) return fail(nullptr, NS_E_INVAL, "%s: handle is NULL", fn);
+    ns_ctx* ctx = h->ctx;
+    if (!ctx) return fail(nullptr, NS_E_STATE, "%s: the handle's ctx has been destroyed", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n == 0) return NS_OK;
+    if (!doc_ids || !term_out || !w_out || !count_out) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    const uint32_t T = std::max(1u, std::min(max_terms, kMlMaxTerms));
+    const MlRule rule{std::max(1u, min_tf), min_df, max_df};
+    // the rows by size class; nothing is launched before every doc id has been checked
+    std::vector<uint32_t> lists(n);
+    uint32_t n_wave = 0, n_block = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t d = doc_ids[i];
+        if (d >= h->n_docs) return fail(ctx, NS_E_INVAL, "%s: doc_ids[%u] = %u, the handle holds %u documents", fn, i, d, h->n_docs);
+        if (h->doc_off[d + 1] - h->doc_off[d] <= kMlDocCut) lists[n_wave++] = i; else lists[n - 1 - n_block++] = i;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
+    const size_t o_ids = place((size_t)n * 4), o_list = place((size_t)n * 4), o_term = place((size_t)n * T * 4), o_w = place((size_t)n * T * 4), o_cnt = place((size_t)n * 4);
+    const size_t block_bytes = off;
+    char* blk = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    chk(hipEventCreate(&ev0));
+    chk(hipEventCreate(&ev1));
+    if (e == hipSuccess) {
+        uint32_t* d_ids = (uint32_t*)(blk + o_ids); uint32_t* d_list = (uint32_t*)(blk + o_list);
+        uint32_t* d_term = (uint32_t*)(blk + o_term); uint32_t* d_w = (uint32_t*)(blk + o_w); uint32_t* d_cnt = (uint32_t*)(blk + o_cnt);
+        chk(hipMemcpyAsync(d_ids, doc_ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_list, lists.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        chk(hipEventRecord(ev0, st));
+        if (e == hipSuccess && n_wave)
+            hipLaunchKernelGGL(k_ml_wave, dim3((n_wave + 3) / 4), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, d_ids, d_list, n_wave, rule, T, d_term, d_w, d_cnt);
+        if (e == hipSuccess && n_block)
+            hipLaunchKernelGGL(k_ml_block, dim3(n_block), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, d_ids, d_list + (n - n_block), rule, T, d_term, d_w, d_cnt);
+        chk(hipGetLastError());
+        chk(hipEventRecord(ev1, st));
+        chk(hipMemcpyAsync(term_out, d_term, (size_t)n * T * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(w_out, d_w, (size_t)n * T * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(count_out, d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        if (e == hipSuccess && device_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return NS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -34,7 +34,21 @@ Engine::~Engine() {
     for (auto& r : replicas_) if (r.ctx) ns_ctx_destroy(r.ctx);   // frees the segments it holds
 }
 
+void Engine::release_similar() {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    for (SimilarSeg& s : similar_) if (s.dev) ns_docterms_destroy(s.dev);
+    similar_.clear();
+}
+
+size_t Engine::similar_segments_on_device() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const SimilarSeg& s : similar_) n += s.dev != nullptr;
+    return n;
+}
+
 void Engine::release_device_segments() {
+    release_similar();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
             if (s) ns_segment_release(ctx_, s);
@@ -900,21 +914,14 @@ std::string Engine::to_json(const SearchResult& r) const {
     return to_json_impl(r);
 }
 
-// no lock: search_batch_json runs it on several threads while the calling thread holds the engine lock
-std::string Engine::to_json_impl(const SearchResult& r) const {
-    std::string o;
-    o += "{\n";
-    if (r.has_found) o += "  \"found\": " + std::to_string(r.found) + ",\n";
-    o += "  \"k\": " + std::to_string(r.k) + ",\n";
-    o += "  \"query\": ";
-    json_escape(o, r.query);
-    o += ",\n";
-    if (r.hits.empty()) {
+// the "results" member of a search body (and of more_like_this's): src/api_engine.cpp:505-536
+void Engine::append_results_json(std::string& o, const std::vector<SearchHit>& hits) const {
+    if (hits.empty()) {
         o += "  \"results\": [],\n";
     } else {
         o += "  \"results\": [\n";
-        for (size_t i = 0; i < r.hits.size(); i++) {
-            const SearchHit& h = r.hits[i];
+        for (size_t i = 0; i < hits.size(); i++) {
+            const SearchHit& h = hits[i];
             o += "    {\n";
             // result decoration (src/api_engine.cpp:516-531): only non-empty fields; keys in nlohmann's (alphabetical) order
             const nsx::MetaFields* md = meta.get(h.seg, h.doc);
@@ -933,10 +940,22 @@ std::string Engine::to_json_impl(const SearchResult& r) const {
             if (md && !md->title.empty()) { o += ",\n      \"title\": "; json_escape(o, md->title); }
             if (md && !md->url.empty()) { o += ",\n      \"url\": "; json_escape(o, md->url); }
             o += "\n";
-            o += (i + 1 < r.hits.size()) ? "    },\n" : "    }\n";
+            o += (i + 1 < hits.size()) ? "    },\n" : "    }\n";
         }
         o += "  ],\n";
     }
+}
+
+// no lock: search_batch_json runs it on several threads while the calling thread holds the engine lock
+std::string Engine::to_json_impl(const SearchResult& r) const {
+    std::string o;
+    o += "{\n";
+    if (r.has_found) o += "  \"found\": " + std::to_string(r.found) + ",\n";
+    o += "  \"k\": " + std::to_string(r.k) + ",\n";
+    o += "  \"query\": ";
+    json_escape(o, r.query);
+    o += ",\n";
+    append_results_json(o, r.hits);
     o += "  \"segments\": " + std::to_string(r.segments) + "\n";
     o += "}";
     return o;
@@ -1403,6 +1422,260 @@ bool Engine::complete_text(const std::string& input, int limit, std::string& bod
 std::string Engine::complete(const std::string& input, int limit) {
     std::string body;
     if (!complete_text(input, limit, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- more like this -----------------------------------------------------------------------------------------
+bool Engine::similar_term_stats(uint32_t seg, std::vector<uint32_t>& df, std::vector<float>& idf) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (seg >= segments.size()) { err_ = "similar_term_stats: segment " + std::to_string(seg) + " is not in the index"; return false; }
+    nsx::SourceSegment src;
+    std::string why;
+    if (!nsx::load_source(segments[seg].dir, src, why)) { err_ = "similar_term_stats: segment " + seg_names[seg] + " carries no forward index: " + why; return false; }
+    nsx::similar_term_stats(segments[seg], src, [](uint32_t N, uint32_t d) { return bm25_idf(N, d); }, df, idf);
+    return true;
+}
+
+// The host side (forward.bin, terms.bin, df / idf by term id) first, so that a segment without forward files is named
+// whether or not there is a device; then the upload to the primary context.
+bool Engine::ensure_similar(uint32_t seg) {
+    if (similar_.size() != segments.size()) similar_.resize(segments.size());
+    SimilarSeg& ss = similar_[seg];
+    if (ss.dev) return true;
+    nsx::SourceSegment src;
+    std::string why;
+    if (!nsx::load_source(segments[seg].dir, src, why)) {
+        err_ = "similar_batch: segment " + seg_names[seg] + " carries no forward index (legacy and generated segments have none): " + why;
+        return false;
+    }
+    if (!ctx_) { err_ = "similar_batch: no device context (the term selection and the scoring run on the device; there is no CPU path)"; return false; }
+    std::vector<uint32_t> df;
+    std::vector<float> idf;
+    nsx::similar_term_stats(segments[seg], src, [](uint32_t N, uint32_t d) { return bm25_idf(N, d); }, df, idf);
+    ns_forward_src fs;
+    nsx::fill_forward_src(src, fs);
+    const int rc = ns_docterms_upload(ctx_, &fs, df.data(), idf.data(), &ss.dev);
+    if (rc != NS_OK) { ss.dev = nullptr; err_ = "similar_batch: segment " + seg_names[seg] + ": " + ns_last_error(ctx_); return false; }
+    ss.term_bytes = std::move(src.term_bytes);
+    ss.term_offsets = std::move(src.term_offsets);
+    return true;
+}
+
+bool Engine::similar_batch(const std::pair<uint32_t, uint32_t>* seg_doc, size_t Q, int k, const nsx::SimilarOptions& opt, ns_hit* hits,
+                           uint32_t* nhits, uint64_t* found, uint8_t* usable, std::vector<nsx::WeightedTerms>* terms_out) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (terms_out) terms_out->clear();
+    if (Q && (!seg_doc || !hits || !nhits || !found || !usable)) { err_ = "similar_batch: null argument"; return false; }
+    if (Q >= 0xFFFFFFFFull) { err_ = "similar_batch: too many sources"; return false; }
+    const uint32_t K = (uint32_t)std::max(1, std::min(k, 99)), K1 = K + 1;   // the search runs with K + 1 <= NS_MAX_K
+    for (size_t q = 0; q < Q; q++)
+        if (seg_doc[q].first >= segments.size() || seg_doc[q].second >= segments[seg_doc[q].first].cord_uid.size()) {
+            err_ = "similar_batch: (segment " + std::to_string(seg_doc[q].first) + ", document " + std::to_string(seg_doc[q].second) + ") is not in the index";
+            return false;
+        }
+    if (Q == 0) {
+        if (!ctx_) { err_ = "similar_batch: no device context (the term selection and the scoring run on the device; there is no CPU path)"; return false; }
+        return true;
+    }
+    // ---- selection: one ns_docterms_select per segment named ----
+    const uint32_t T = nsx::similar_clamp_terms(opt.max_terms);
+    std::vector<std::vector<uint32_t>> rows_of(segments.size());
+    for (size_t q = 0; q < Q; q++) rows_of[seg_doc[q].first].push_back((uint32_t)q);
+    for (uint32_t s = 0; s < segments.size(); s++)
+        if (!rows_of[s].empty() && !ensure_similar(s)) return false;
+    std::vector<uint32_t> sel_term(Q * (size_t)T), sel_cnt(Q);
+    std::vector<float> sel_w(Q * (size_t)T);
+    {
+        std::vector<uint32_t> ids, t_, c_;
+        std::vector<float> w_;
+        for (uint32_t s = 0; s < segments.size(); s++) {
+            const std::vector<uint32_t>& rows = rows_of[s];
+            if (rows.empty()) continue;
+            ids.resize(rows.size()); t_.resize(rows.size() * (size_t)T); w_.resize(rows.size() * (size_t)T); c_.resize(rows.size());
+            for (size_t i = 0; i < rows.size(); i++) ids[i] = seg_doc[rows[i]].second;
+            const int rc = ns_docterms_select(similar_[s].dev, ids.data(), (uint32_t)ids.size(), opt.max_terms, opt.min_tf, opt.min_df, opt.max_df,
+                                              t_.data(), w_.data(), c_.data(), nullptr);
+            if (rc != NS_OK) { err_ = "ns_docterms_select (segment " + seg_names[s] + "): " + ns_last_error(ctx_); return false; }
+            for (size_t i = 0; i < rows.size(); i++) {
+                std::memcpy(&sel_term[rows[i] * (size_t)T], &t_[i * (size_t)T], (size_t)T * 4);
+                std::memcpy(&sel_w[rows[i] * (size_t)T], &w_[i * (size_t)T], (size_t)T * 4);
+                sel_cnt[rows[i]] = c_[i];
+            }
+        }
+    }
+    if (terms_out) terms_out->assign(Q, {});
+    // ---- term refs of sources [a, b): ids -> bytes (terms.bin) -> one dictionary probe -> every segment, selection order ----
+    const uint32_t S = (uint32_t)segments.size();
+    // sources [a, b) into refs (appended); qd[q - q_base].term_begin counts from refs' start
+    auto build_slice = [&](size_t a, size_t b, size_t q_base, ns_query_desc* qd, std::vector<ns_term_ref>& refs, std::vector<uint32_t>& gids) {
+        float qw[nsx::kSimilarMaxTerms];
+        for (size_t q = a; q < b; q++) {
+            const SimilarSeg& ss = similar_[seg_doc[q].first];
+            const uint32_t* tid = &sel_term[q * (size_t)T];
+            const float* w = &sel_w[q * (size_t)T];
+            const uint32_t n = sel_cnt[q];
+            ns_query_desc& d = qd[q - q_base];
+            d.term_begin = (uint32_t)refs.size();
+            usable[q] = n != 0 ? 1 : 0;
+            gids.clear();
+            uint32_t n_q = 0;
+            for (uint32_t r = 0; r < n; r++) {
+                const char* tp = (const char*)ss.term_bytes.data() + ss.term_offsets[tid[r]];
+                const size_t tn = (size_t)(ss.term_offsets[tid[r] + 1] - ss.term_offsets[tid[r]]);
+                if (terms_out) (*terms_out)[q].emplace_back(std::string(tp, tn), w[r]);
+                const int64_t g = dict.find(tp, tn);
+                if (g < 0) continue;
+                gids.push_back((uint32_t)g);
+                qw[n_q++] = nsx::similar_qweight(w[r], w[0], opt.boost);
+            }
+            for (uint32_t sid = 0; sid < S; sid++)
+                for (uint32_t i = 0; i < n_q; i++) {
+                    const nsx::TermSeg& e = dict.row(gids[i])[sid];
+                    if (e.byte_off == nsx::kAbsent) continue;
+                    refs.push_back(ns_term_ref{sid, e.count, e.byte_off, e.idf, qw[i]});
+                }
+            d.term_count = (uint32_t)refs.size() - d.term_begin;
+        }
+    };
+    // ... on the engine's host threads, as build_refs_parallel cuts a text batch (the dictionary is read-only; every source
+    // writes its own usable / terms_out entry), the slices' refs concatenated in source order
+    auto build = [&](size_t a, size_t b, std::vector<ns_query_desc>& qd, std::vector<ns_term_ref>& refs) {
+        const size_t n = b - a;
+        qd.assign(n, ns_query_desc{0, 0});
+        refs.clear();
+        const unsigned nt = prep_width(n);
+        if (scratch_.size() < std::max(1u, nt)) scratch_.resize(std::max(1u, nt));
+        if (nt <= 1) { build_slice(a, b, a, qd.data(), refs, scratch_[0].gids); return; }
+        if (!pool_ || pool_->width() < nt) pool_.reset(new ForkJoin(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u)));
+        pool_->run(nt, [&](unsigned i) {
+            PrepScratch& sc = scratch_[i];
+            sc.refs.clear();
+            const size_t lo = a + n * i / nt, hi = a + n * (i + 1) / nt;
+            build_slice(lo, hi, a, qd.data(), sc.refs, sc.gids);
+        });
+        size_t total = 0;
+        std::vector<size_t> base(nt);
+        for (unsigned i = 0; i < nt; i++) { base[i] = total; total += scratch_[i].refs.size(); }
+        refs.resize(total);
+        pool_->run(nt, [&](unsigned i) {
+            for (size_t q = n * i / nt; q < n * (i + 1) / nt; q++) qd[q].term_begin += (uint32_t)base[i];
+            if (!scratch_[i].refs.empty()) std::memcpy(refs.data() + base[i], scratch_[i].refs.data(), scratch_[i].refs.size() * sizeof(ns_term_ref));
+        });
+    };
+    // ---- the existing batch path with K + 1, sub-batches pipelined as run_range does ----
+    std::vector<ns_hit> h1(Q * (size_t)K1);
+    std::vector<uint32_t> n1(Q);
+    std::vector<uint64_t> f1(Q);
+    {
+        const size_t kSubBatch = sub_batch_size();
+        const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+        const bool piped = n_sub > 1;
+        if (piped) (void)ns_ctx_set_overlap(ctx_, 1);
+        struct InFlight { ns_batch* b = nullptr; size_t q0 = 0; };
+        InFlight prev;
+        bool ok = true;
+        auto retire = [&](InFlight& f) {
+            if (!f.b) return;
+            if (ok) {
+                const int rc = ns_batch_fetch(f.b, h1.data() + f.q0 * (size_t)K1, n1.data() + f.q0, f1.data() + f.q0);
+                if (rc != NS_OK) { err_ = std::string("ns_batch_fetch: ") + ns_last_error(ctx_); ok = false; }
+            }
+            ns_batch_destroy(f.b);
+            f.b = nullptr;
+        };
+        std::vector<ns_query_desc> qd;
+        std::vector<ns_term_ref> refs;
+        for (size_t i = 0; i < n_sub && ok; i++) {
+            const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+            build(a, b, qd, refs);
+            InFlight cur;
+            cur.q0 = a;
+            int rc = ns_batch_prepare(ctx_, qd.data(), refs.data(), (uint32_t)(b - a), K1, NS_FLAG_OR, &cur.b);
+            if (rc == NS_OK) rc = ns_batch_run(cur.b, NS_RUN_FETCH);
+            if (rc != NS_OK) {
+                err_ = std::string("ns_batch_prepare/run: ") + ns_last_error(ctx_);
+                ok = false;
+                if (cur.b) ns_batch_destroy(cur.b);
+                break;
+            }
+            retire(prev);
+            prev = cur;
+        }
+        retire(prev);
+        if (piped) (void)ns_ctx_set_overlap(ctx_, 0);
+        if (!ok) return false;
+    }
+    // ---- the source leaves its own row ----
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    for (size_t q = 0; q < Q; q++) {
+        ns_hit* out = hits + q * (size_t)K;
+        uint32_t n = 0;
+        if (usable[q]) {
+            const ns_hit* in = h1.data() + q * (size_t)K1;
+            for (uint32_t i = 0; i < n1[q] && n < K; i++) {
+                if (in[i].seg_id == seg_doc[q].first && in[i].doc_id == seg_doc[q].second) continue;
+                out[n++] = in[i];                                       // source absent from the K + 1: the last one is dropped
+            }
+        }
+        nhits[q] = n;
+        found[q] = usable[q] && f1[q] ? f1[q] - 1 : 0;
+        for (uint32_t i = n; i < K; i++) out[i] = pad;
+    }
+    return true;
+}
+
+bool Engine::more_like_this_text(const std::string& uid, int k, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    const uint32_t K = (uint32_t)std::max(1, std::min(k, 99));
+    std::vector<std::pair<uint32_t, uint32_t>> where;
+    find_documents({uid}, where);
+    if (where.empty()) { err_ = "more_like_this: no document with cord_uid \"" + uid + "\" in the index"; body = err_; return false; }
+    const std::pair<uint32_t, uint32_t> src = where[0];                // the first match is the source
+    std::vector<ns_hit> hits(K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    std::vector<nsx::WeightedTerms> terms;
+    if (!similar_batch(&src, 1, k, nsx::SimilarOptions{}, hits.data(), &nh, &fd, &us, &terms)) { body = err_; return false; }
+    std::vector<SearchHit> sh;
+    for (uint32_t i = 0; i < nh; i++) sh.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    std::string& o = body;
+    o.clear();
+    o += "{\n";
+    if (us) o += "  \"found\": " + std::to_string(fd) + ",\n";
+    o += "  \"k\": " + std::to_string(K) + ",\n";
+    if (terms[0].empty()) {
+        o += "  \"query_terms\": [],\n";
+    } else {
+        o += "  \"query_terms\": [\n";
+        for (size_t i = 0; i < terms[0].size(); i++) {
+            o += "    {\n      \"term\": ";
+            json_escape(o, terms[0][i].first);
+            o += ",\n      \"weight\": ";
+            json_number_from_float(o, terms[0][i].second);
+            o += i + 1 < terms[0].size() ? "\n    },\n" : "\n    }\n";
+        }
+        o += "  ],\n";
+    }
+    append_results_json(o, sh);
+    o += "  \"segments\": " + std::to_string(segments.size()) + ",\n";
+    o += "  \"source\": {\n    \"cord_uid\": ";
+    json_escape(o, uid);
+    o += ",\n    \"docId\": " + std::to_string(src.second) + ",\n    \"segment\": ";
+    json_escape(o, seg_names[src.first]);
+    o += "\n  }\n}";
+    return true;
+}
+
+std::string Engine::more_like_this(const std::string& uid, int k) {
+    std::string body;
+    if (!more_like_this_text(uid, k, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

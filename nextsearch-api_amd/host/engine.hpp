@@ -32,6 +32,7 @@
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
+#include "similar.hpp"
 #include "correct.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
@@ -227,6 +228,30 @@ public:
     std::string complete(const std::string& input, int limit);
     bool complete_text(const std::string& input, int limit, std::string& body);
 
+    // "More like this" (host/similar.hpp, csrc/ns_similar.hip).  Source q is the document seg_doc[q] =
+    // (manifest position, docId), as delete_by_id names documents; a pair out of range is refused and nothing runs.  Its
+    // most telling terms are selected on the device from its forward pairs (ns_docterms_select; the segment's OWN df / idf),
+    // turned into byte strings through the segment's terms.bin and scored over EVERY segment as one weighted OR query, in
+    // selection order (the fp32 accumulation order), qweight 1.0f or, with opt.boost, w / w_first.  The search runs with
+    // K + 1, K = clamp(k, 1, 99); the source's own hit is removed if it is among the K + 1, otherwise the last hit is dropped.
+    // hits Q x K (unused tail entries {-inf, ~0, ~0}), nhits[Q], found[Q] = the search's found - 1 (the source always matches
+    // its own terms), usable[Q] (0 = nothing selected: no hits, no found).  terms_out (may be null): per source the selected
+    // (term, w) in selection order, w = (float)tf * idf.  No semantic expansion, no search cache.  The device copy of a
+    // segment's forward index is built by the first call that names the segment (never by reload()) on the primary context,
+    // and freed by reload(), release_similar() and the destructor.  A segment without forward.bin / terms.bin (legacy
+    // segments, gen_index output) fails the call with a message that names it; so does an engine without a device.
+    bool similar_batch(const std::pair<uint32_t, uint32_t>* seg_doc, size_t Q, int k, const nsx::SimilarOptions& opt, ns_hit* hits,
+                       uint32_t* nhits, uint64_t* found, uint8_t* usable, std::vector<nsx::WeightedTerms>* terms_out = nullptr);
+    // JSON text {"found", "k", "query_terms": [{"term", "weight"}], "results": [search's entries], "segments", "source":
+    // {"cord_uid", "docId", "segment"}} in dump(2) layout, default options.  The uid is resolved with find_documents; the
+    // first match is the source.  An unknown uid, or any failure: {"error": ...} (more_like_this_text: false, body = the message).
+    std::string more_like_this(const std::string& uid, int k);
+    bool more_like_this_text(const std::string& uid, int k, std::string& body);
+    void release_similar();
+    size_t similar_segments_on_device() const;   // segments whose forward index has a device copy right now
+    // df / idf by term id of segment seg as similar_batch uploads them (host only: works without a device)
+    bool similar_term_stats(uint32_t seg, std::vector<uint32_t>& df, std::vector<float>& idf);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -272,6 +297,11 @@ private:
     bool ensure_fuzzy();
     bool fuzzy_batch(const char* fn, const QueryView* terms, size_t Q, int limit, int max_edits, int prefix_len, uint32_t* term_idx, uint8_t* dist,
                      uint32_t* count, uint32_t* base_len, float* device_ms);
+    // more-like-this: per segment the device copy of its forward index and, on the host, the term bytes of terms.bin
+    struct SimilarSeg { ns_docterms* dev = nullptr; std::vector<uint8_t> term_bytes; std::vector<uint64_t> term_offsets; };
+    std::vector<SimilarSeg> similar_;
+    bool ensure_similar(uint32_t seg);
+    void append_results_json(std::string& o, const std::vector<SearchHit>& hits) const;
     std::vector<ns_seg*> dev_segs_;
     // further devices holding a replica of the index (multi-device engine): context + segments each
     struct Replica { int device = 0; ns_ctx* ctx = nullptr; std::vector<ns_seg*> segs; };

@@ -657,3 +657,92 @@ extern "C" uint64_t nsh_suggest_split(const char* input, uint64_t input_len, uin
 }
 
 extern "C" int nsh_suggest_clamp_limit(int limit) { return nsx::clamp_suggest_limit(limit); }
+
+// ---- more like this ----
+extern "C" int nsh_similar_select_host(const uint32_t* counts, uint32_t n_docs, const uint32_t* pairs, uint64_t n_pairs, const uint32_t* df,
+                                       const float* idf, uint32_t n_terms, const uint32_t* doc_ids, uint32_t n, uint32_t max_terms,
+                                       uint32_t min_tf, uint32_t min_df, uint32_t max_df, uint32_t* term_out, float* w_out, uint32_t* count_out) { try {
+    if ((n_docs && !counts) || (n_pairs && !pairs) || (n_terms && (!df || !idf)) || (n && (!doc_ids || !term_out || !w_out || !count_out))) return -1;
+    std::vector<uint64_t> off((size_t)n_docs + 1, 0);
+    for (uint32_t d = 0; d < n_docs; d++) off[d + 1] = off[d] + counts[d];
+    if (off[n_docs] != n_pairs) return -1;
+    return nsx::similar_select_host(off.data(), n_docs, pairs, df, idf, n_terms, doc_ids, n, max_terms, min_tf, min_df, max_df, term_out, w_out, count_out) ? 0 : -1;
+} catch (...) { return -1; }
+}
+extern "C" uint32_t nsh_similar_clamp_terms(uint32_t max_terms) { return nsx::similar_clamp_terms(max_terms); }
+extern "C" int nsh_similar_clamp_k(int k) { return std::max(1, std::min(k, 99)); }
+extern "C" float nsh_similar_qweight(float w, float w_first, int boost) { return nsx::similar_qweight(w, w_first, boost != 0); }
+extern "C" void nsh_similar_defaults(uint32_t* max_terms, uint32_t* min_tf, uint32_t* min_df, uint32_t* max_df, int* boost) {
+    const nsx::SimilarOptions o;
+    if (max_terms) *max_terms = o.max_terms;
+    if (min_tf) *min_tf = o.min_tf;
+    if (min_df) *min_df = o.min_df;
+    if (max_df) *max_df = o.max_df;
+    if (boost) *boost = o.boost ? 1 : 0;
+}
+
+extern "C" int64_t nsh_engine_similar_term_stats(nsh_engine* e, uint32_t seg, uint32_t* df_out, float* idf_out, uint64_t cap) { try {
+    if (!e) return -1;
+    std::vector<uint32_t> df;
+    std::vector<float> idf;
+    if (!e->eng.similar_term_stats(seg, df, idf)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    const size_t m = (size_t)std::min<uint64_t>(cap, df.size());
+    if (df_out && m) std::memcpy(df_out, df.data(), m * 4);
+    if (idf_out && m) std::memcpy(idf_out, idf.data(), m * 4);
+    return (int64_t)df.size();
+} NSH_CATCH(e, "nsh_engine_similar_term_stats", -1)
+}
+
+extern "C" int nsh_engine_similar_batch(nsh_engine* e, const uint32_t* seg_doc, uint64_t n, int k, uint32_t max_terms, uint32_t min_tf,
+                                        uint32_t min_df, uint32_t max_df, int boost, ns_hit* hits, uint32_t* nhits, uint64_t* found,
+                                        uint8_t* usable, uint32_t* term_count, float* term_w, char** term_bytes_out, uint64_t** term_offsets_out) { try {
+    if (!e) return -1;
+    if (term_bytes_out) *term_bytes_out = nullptr;
+    if (term_offsets_out) *term_offsets_out = nullptr;
+    if (n && (!seg_doc || !hits || !nhits || !found || !usable)) { nsh_set_err(e, "nsh_engine_similar_batch: null argument"); return -1; }
+    std::vector<std::pair<uint32_t, uint32_t>> ids((size_t)n);
+    for (size_t i = 0; i < ids.size(); i++) ids[i] = {seg_doc[2 * i], seg_doc[2 * i + 1]};
+    nsx::SimilarOptions opt;
+    opt.max_terms = max_terms; opt.min_tf = min_tf; opt.min_df = min_df; opt.max_df = max_df; opt.boost = boost != 0;
+    const bool want_terms = term_count || term_w || term_bytes_out || term_offsets_out;
+    std::vector<nsx::WeightedTerms> terms;
+    if (!e->eng.similar_batch(ids.data(), ids.size(), k, opt, hits, nhits, found, usable, want_terms ? &terms : nullptr)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    if (!want_terms) return 0;
+    const uint32_t T = nsx::similar_clamp_terms(max_terms);
+    size_t total = 0, bytes = 0;
+    for (size_t q = 0; q < terms.size(); q++) {
+        if (term_count) term_count[q] = (uint32_t)terms[q].size();
+        for (uint32_t r = 0; r < T && term_w; r++) term_w[q * (size_t)T + r] = r < terms[q].size() ? terms[q][r].second : 0.0f;
+        total += terms[q].size();
+        for (const auto& t : terms[q]) bytes += t.first.size();
+    }
+    if (term_bytes_out && term_offsets_out) {
+        char* tb = (char*)std::malloc(bytes + 1);
+        uint64_t* to = (uint64_t*)std::malloc((total + 1) * sizeof(uint64_t));
+        if (!tb || !to) { std::free(tb); std::free(to); nsh_set_err(e, "nsh_engine_similar_batch: out of memory"); return -1; }
+        size_t j = 0, at = 0;
+        for (const auto& row : terms)
+            for (const auto& t : row) { to[j++] = at; std::memcpy(tb + at, t.first.data(), t.first.size()); at += t.first.size(); }
+        to[j] = at;
+        tb[at] = 0;
+        *term_bytes_out = tb;
+        *term_offsets_out = to;
+    }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_similar_batch", -1)
+}
+
+extern "C" int nsh_engine_more_like_this_json(nsh_engine* e, const char* uid, uint64_t uid_len, int k, char** json_out) { try {
+    if (!e || !json_out || (uid_len && !uid)) return -1;
+    std::string s;
+    const bool ok = e->eng.more_like_this_text(std::string(uid ? uid : "", (size_t)uid_len), k, s);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); *json_out = nullptr; return -1; }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_more_like_this_json", -1)
+}
+
+extern "C" void nsh_engine_release_similar(nsh_engine* e) { try { if (e) e->eng.release_similar(); } NSH_CATCH_VOID(e, "nsh_engine_release_similar") }
+extern "C" uint64_t nsh_engine_similar_segments_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.similar_segments_on_device() : 0; }

@@ -10,6 +10,8 @@
 //   ns_tool delete <index_dir> <uid>...                   (needs an MI355X)
 //        Engine::delete_documents: every document that carries one of the uids goes; the segments that lose documents are
 //        rewritten on the device (purge.hpp).  One JSON line.
+//   ns_tool similar <index_dir> <uid> [k=10]               (needs an MI355X)
+//        Engine::more_like_this: the documents most like the one that carries the uid (similar.hpp); prints the JSON body.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -69,6 +71,15 @@ int main(int argc, char** argv) {
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
         std::string body;
         if (!eng.complete_text(argv[3], argc > 4 ? std::atoi(argv[4]) : 5, body)) { std::fprintf(stderr, "complete failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 4 && std::strcmp(argv[1], "similar") == 0) {
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        std::string body;
+        if (!eng.more_like_this_text(argv[3], argc > 4 ? std::atoi(argv[4]) : 10, body)) { std::fprintf(stderr, "similar failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
@@ -172,6 +183,6 @@ int main(int argc, char** argv) {
                     Q, K, refs.size(), reload_ms, p, p > 0 ? Q / (p * 1e-3) : 0.0, f, f > 0 ? Q / (f * 1e-3) : 0.0, reps, (unsigned long long)check);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n       %s complete <index_dir> <input> [limit]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n       %s complete <index_dir> <input> [limit]\n       %s similar <index_dir> <uid> [k]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
 }

@@ -65,6 +65,7 @@ HIP_SYMBOLS = [
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
     "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort",
     "ns_forward_merge_keep",
+    "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
 HOST_SYMBOLS = [
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -80,6 +81,9 @@ HOST_SYMBOLS = [
     "nsh_index_documents", "nsh_index_error", "nsh_engine_open_noload", "nsh_engine_add_documents",
     "nsh_merge_segments", "nsh_compact_error", "nsh_engine_compact",
     "nsh_engine_find_documents", "nsh_engine_delete_documents", "nsh_engine_delete_by_id",
+    "nsh_similar_select_host", "nsh_similar_clamp_terms", "nsh_similar_clamp_k", "nsh_similar_qweight", "nsh_similar_defaults",
+    "nsh_engine_similar_term_stats", "nsh_engine_similar_batch", "nsh_engine_more_like_this_json", "nsh_engine_release_similar",
+    "nsh_engine_similar_segments_on_device",
 ]
 
 class NsForwardInfo(C.Structure):   # include/nextsearch_hip.h ns_forward_info
@@ -194,6 +198,12 @@ def hip_lib():
         L.ns_compact_doc_cut.restype = u32
         L.ns_ctx_use_docsort.argtypes = [vp, i32]
         L.ns_forward_merge_keep.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
+        L.ns_docterms_upload.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
+        L.ns_docterms_select.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_docterms_destroy.argtypes = [vp]
+        L.ns_docterms_destroy.restype = None
+        L.ns_docterms_doc_cut.argtypes = []
+        L.ns_docterms_doc_cut.restype = u32
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -318,6 +328,23 @@ def host_lib():
         L.nsh_engine_correct_build_ms.restype = C.c_double
         L.nsh_engine_complete_batch.argtypes = [vp, C.c_char_p, vp, u32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.nsh_engine_complete_json.argtypes = [vp, C.c_char_p, u64, i32, C.POINTER(vp)]
+        L.nsh_similar_select_host.argtypes = [vp, u32, vp, u64, vp, vp, u32, vp, u32, u32, u32, u32, u32, vp, vp, vp]
+        L.nsh_similar_clamp_terms.argtypes = [u32]
+        L.nsh_similar_clamp_terms.restype = u32
+        L.nsh_similar_clamp_k.argtypes = [i32]
+        L.nsh_similar_clamp_k.restype = i32
+        L.nsh_similar_qweight.argtypes = [C.c_float, C.c_float, i32]
+        L.nsh_similar_qweight.restype = C.c_float
+        L.nsh_similar_defaults.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]
+        L.nsh_similar_defaults.restype = None
+        L.nsh_engine_similar_term_stats.argtypes = [vp, u32, vp, vp, u64]
+        L.nsh_engine_similar_term_stats.restype = C.c_int64
+        L.nsh_engine_similar_batch.argtypes = [vp, vp, u64, i32, u32, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+        L.nsh_engine_more_like_this_json.argtypes = [vp, C.c_char_p, u64, i32, C.POINTER(vp)]
+        L.nsh_engine_release_similar.argtypes = [vp]
+        L.nsh_engine_release_similar.restype = None
+        L.nsh_engine_similar_segments_on_device.argtypes = [vp]
+        L.nsh_engine_similar_segments_on_device.restype = u64
         _host = L
     return _host
 
@@ -761,6 +788,62 @@ class Engine:
         self._L.nsh_free(out)
         return s
 
+    def similar_term_stats(self, seg):
+        """(df u32[n_terms], idf f32[n_terms]) by term id of segment seg, as similar_batch uploads them; host only."""
+        n = self._L.nsh_engine_similar_term_stats(self.h, seg, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"similar_term_stats failed: {self.error()}")
+        df, idf = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float32)
+        if self._L.nsh_engine_similar_term_stats(self.h, seg, df.ctypes.data, idf.ctypes.data, n) != n:
+            raise RuntimeError(f"similar_term_stats failed: {self.error()}")
+        return df, idf
+
+    def similar_batch(self, seg_doc, k, max_terms=None, min_tf=None, min_df=None, max_df=None, boost=False, terms=False):
+        """Engine::similar_batch over (manifest position, docId) pairs; options None: the defaults.  Returns (hits[Q, K], nhits,
+        found, usable) and, with terms, a fifth item: per source [(term bytes, w)] in selection order."""
+        d = similar_defaults()
+        opt = [d[n] if v is None else int(v) for n, v in (("max_terms", max_terms), ("min_tf", min_tf), ("min_df", min_df), ("max_df", max_df))]
+        ids = np.ascontiguousarray(np.asarray(list(seg_doc), dtype=np.uint32).reshape(-1, 2))
+        Q, K, T = len(ids), similar_clamp_k(k), similar_clamp_terms(opt[0])
+        hits = np.empty((Q, K), dtype=HIT_DTYPE)
+        nhits, found, usable = np.zeros(Q, dtype=np.uint32), np.zeros(Q, dtype=np.uint64), np.zeros(Q, dtype=np.uint8)
+        cnt, w = np.zeros(Q, dtype=np.uint32), np.zeros((Q, T), dtype=np.float32)
+        tb, to = C.c_void_p(), C.c_void_p()
+        rc = self._L.nsh_engine_similar_batch(self.h, ids.ctypes.data, Q, int(k), *opt, 1 if boost else 0, hits.ctypes.data, nhits.ctypes.data,
+                                              found.ctypes.data, usable.ctypes.data, cnt.ctypes.data if terms else None, w.ctypes.data if terms else None,
+                                              C.byref(tb) if terms else None, C.byref(to) if terms else None)
+        if rc != 0:
+            raise RuntimeError(f"similar_batch failed: {self.error()}")
+        if not terms:
+            return hits, nhits, found, usable
+        total = int(cnt.sum())
+        offs = np.ctypeslib.as_array(C.cast(to, C.POINTER(C.c_uint64)), shape=(total + 1,)).copy()
+        raw = C.string_at(tb, int(offs[total]))
+        self._L.nsh_free(tb)
+        self._L.nsh_free(to)
+        out, j = [], 0
+        for q in range(Q):
+            out.append([(raw[int(offs[j + r]):int(offs[j + r + 1])], w[q, r]) for r in range(int(cnt[q]))])
+            j += int(cnt[q])
+        return hits, nhits, found, usable, out
+
+    def more_like_this_json(self, uid, k=10):
+        """Engine::more_like_this(uid, k) as bytes (the uid: str or raw bytes)."""
+        b = _as_bytes(uid)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_more_like_this_json(self.h, b, len(b), int(k), C.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"more_like_this failed: {self.error()}")
+        s = C.string_at(out)
+        self._L.nsh_free(out)
+        return s
+
+    def release_similar(self):
+        self._L.nsh_engine_release_similar(self.h)
+
+    def similar_segments_on_device(self):
+        return int(self._L.nsh_engine_similar_segments_on_device(self.h))
+
     def correct_build_ms(self):
         """time of the corrector's lazy build since the last reload (0.0: not built yet)"""
         return self._L.nsh_engine_correct_build_ms(self.h)
@@ -952,6 +1035,92 @@ def forward_merge_keep(ctx, parts, keeps, invert=False):
     if rc != NS_OK:
         raise RuntimeError(f"ns_forward_merge_keep: {rc}: {L.ns_last_error(ctx).decode()}")
     return _fetched(L, ctx, h, invert)
+
+
+def similar_defaults():
+    """Engine::more_like_this's options: {max_terms, min_tf, min_df, max_df, boost}"""
+    v = [C.c_uint32() for _ in range(4)]
+    b = C.c_int32()
+    host_lib().nsh_similar_defaults(*[C.byref(x) for x in v], C.byref(b))
+    return {"max_terms": v[0].value, "min_tf": v[1].value, "min_df": v[2].value, "max_df": v[3].value, "boost": bool(b.value)}
+
+
+def similar_clamp_terms(max_terms):
+    return int(host_lib().nsh_similar_clamp_terms(int(max_terms) & 0xFFFFFFFF))
+
+
+def similar_clamp_k(k):
+    return int(host_lib().nsh_similar_clamp_k(int(k)))
+
+
+def _select_arrays(part, df, idf):
+    cnt = np.ascontiguousarray(part["counts"], dtype=np.uint32)
+    pairs = np.ascontiguousarray(part["pairs"], dtype=np.uint32).reshape(-1, 2)
+    return cnt, pairs, np.ascontiguousarray(df, dtype=np.uint32), np.ascontiguousarray(idf, dtype=np.float32)
+
+
+def similar_select_host(part, df, idf, doc_ids, max_terms=25, min_tf=1, min_df=1, max_df=0xFFFFFFFF):
+    """nsh_similar_select_host (the rule on one host thread) over a part in forward_build's form (counts, pairs[n, 2]) and
+    df / idf by term id -> (term u32[n, T], w f32[n, T], count u32[n]); ValueError when the input is refused"""
+    cnt, pairs, df, idf = _select_arrays(part, df, idf)
+    ids = np.ascontiguousarray(doc_ids, dtype=np.uint32)
+    T = similar_clamp_terms(max_terms)
+    term, w, count = np.zeros((len(ids), T), dtype=np.uint32), np.zeros((len(ids), T), dtype=np.float32), np.zeros(len(ids), dtype=np.uint32)
+    rc = host_lib().nsh_similar_select_host(cnt.ctypes.data, len(cnt), pairs.ctypes.data, len(pairs), df.ctypes.data, idf.ctypes.data, len(df),
+                                            ids.ctypes.data, len(ids), max_terms, min_tf, min_df, max_df, term.ctypes.data, w.ctypes.data, count.ctypes.data)
+    if rc != 0:
+        raise ValueError("nsh_similar_select_host refused its input")
+    return term, w, count
+
+
+class DocTerms:
+    """Raw ns_docterms_upload / ns_docterms_select over a part in forward_build's form (counts, pairs[n, 2]; doc_len and terms are
+    not needed) and df / idf by term id; n_pairs / n_terms override what is announced (refusal tests).  Raises RuntimeError
+    with .args = (message, code) when the library refuses."""
+
+    def __init__(self, ctx, part, df, idf, n_pairs=None, n_terms=None):
+        self._L, self.ctx = hip_lib(), ctx
+        cnt, pairs, df, idf = _select_arrays(part, df, idf)
+        src = NsForwardSrc(len(cnt), None, cnt.ctypes.data, len(pairs) if n_pairs is None else n_pairs, pairs.ctypes.data,
+                           len(df) if n_terms is None else n_terms, None, None)
+        self.h = C.c_void_p()
+        rc = self._L.ns_docterms_upload(ctx, C.byref(src), df.ctypes.data, idf.ctypes.data, C.byref(self.h))
+        if rc != NS_OK:
+            self.h = None
+            raise RuntimeError(f"ns_docterms_upload: {rc}: {self._L.ns_last_error(ctx).decode()}", rc)
+
+    def select(self, doc_ids, max_terms=25, min_tf=1, min_df=1, max_df=0xFFFFFFFF, garbage=True):
+        """-> (term u32[n, T], w f32[n, T], count u32[n], device_ms); the outputs start as garbage so that the padding is the call's"""
+        ids = np.ascontiguousarray(doc_ids, dtype=np.uint32)
+        T = similar_clamp_terms(max_terms)
+        fill = 0x5A if garbage else 0
+        term, count = np.full((len(ids), T), fill * 0x01010101, dtype=np.uint32), np.full(len(ids), fill * 0x01010101, dtype=np.uint32)
+        w = np.full((len(ids), T), fill * 0x01010101, dtype=np.uint32).view(np.float32)
+        ms = C.c_float()
+        rc = self._L.ns_docterms_select(self.h, ids.ctypes.data, len(ids), max_terms, min_tf, min_df, max_df, term.ctypes.data, w.ctypes.data,
+                                        count.ctypes.data, C.byref(ms))
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_docterms_select: {rc}: {self._L.ns_last_error(self.ctx if rc != -5 else None).decode()}", rc)
+        return term, w, count, ms.value
+
+    def close(self):
+        if self.h:
+            self._L.ns_docterms_destroy(self.h)
+            self.h = None
+
+
+def docterms_upload(ctx, part, df, idf):
+    """Raw ns_docterms_upload -> DocTerms (close() it before its ctx, or after: an orphaned handle frees itself)"""
+    return DocTerms(ctx, part, df, idf)
+
+
+def docterms_select(ctx, part, df, idf, doc_ids, max_terms=25, min_tf=1, min_df=1, max_df=0xFFFFFFFF):
+    """Raw ns_docterms_upload + ns_docterms_select + ns_docterms_destroy like forward_merge_keep: -> (term, w, count, device_ms)"""
+    dt = DocTerms(ctx, part, df, idf)
+    try:
+        return dt.select(doc_ids, max_terms, min_tf, min_df, max_df)
+    finally:
+        dt.close()
 
 
 def forward_merge(ctx, parts, invert=False):
