@@ -174,6 +174,21 @@ int ns_ctx_use_impacts(ns_ctx* ctx, int on);
  * is not docId-ascending keeps no table (its groups take the cursor path); lists given again are left as they are.
  * Meant for the frequent lists of a segment (the facade registers lists of >= n_docs / 512 postings at reload). */
 int ns_segment_build_skips(ns_ctx* ctx, ns_seg* seg, const uint64_t* byte_off, const uint32_t* counts, uint32_t n_lists);
+/* A filtered copy of a segment (csrc/ns_filter.hip).  keep_bits (host, ceil(n_docs / 32) words): bit d % 32 of
+ * word d / 32 says whether document d of `src` is kept; bits past n_docs are ignored.  The postings of kept documents, in
+ * stream order, become the payload of a NEW segment published under new_seg_id: same n_docs, avgdl and norms as the source,
+ * padded like an uploaded one, without packed / impact streams, skip tables or block maxima (ns_segment_build_skips works on
+ * it as on any segment), and without any pointer into `src`: the two are released in either order with ns_segment_release.
+ * A posting whose docId is >= n_docs is dropped.  The lists [byte_off[i] / 8, + counts[i]) of the source (as in ns_term_ref;
+ * they may overlap, leave gaps and come in any order) are answered with their place in the copy: new_byte_off_out[i],
+ * new_counts_out[i]; compaction keeps the order, so a docId-ascending list stays one.  A list with no kept posting has
+ * count 0.  postings_out (host, may be NULL; capacity: the source's payload bytes): the filtered payload, for tests and
+ * tools; the postings do not visit the host otherwise.  kept_postings_out, device_ms_out (may be NULL): postings kept; time
+ * of the four passes.  Synchronous.  NS_E_INVAL: a null argument, new_seg_id in use or >= 2^20, a source that is not a
+ * published segment of this ctx (an upload that has not ended included), a list outside the source's payload. */
+int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint32_t* keep_bits, const uint64_t* byte_off,
+                      const uint32_t* counts, uint32_t n_lists, uint64_t* new_byte_off_out, uint32_t* new_counts_out,
+                      void* postings_out, uint64_t* kept_postings_out, float* device_ms_out, ns_seg** out);
 /* on = 0: batches prepared from now on ignore skip tables (default: on = 1). */
 int ns_ctx_use_skips(ns_ctx* ctx, int on);
 /* Block-max scores with `found`-exact pruning.  The reference reads every posting of every scored list

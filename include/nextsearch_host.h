@@ -305,6 +305,39 @@ int nsh_engine_more_like_this_json(nsh_engine* e, const char* uid, uint64_t uid_
 void nsh_engine_release_similar(nsh_engine* e);
 uint64_t nsh_engine_similar_segments_on_device(nsh_engine* e);
 
+/* ---- filtered search (host/filter.hpp) ----
+ * nsh_date_key: "YYYY", "YYYY-MM" (01..12) or "YYYY-MM-DD" (01..31), blanks stripped -> Y * 10000 + M * 100 + D with the
+ * missing parts 0; anything else 0 = undated.
+ * A date filter keeps the documents with date_from <= key <= date_to; a missing part of date_to counts as 99, an empty or NULL
+ * bound is open, undated documents (no metadata row included) are kept only with keep_undated; a bound that is neither empty
+ * nor a date fails the call.  With date_from = "2020-03" a document dated just "2020" is NOT kept. */
+uint32_t nsh_date_key(const char* s, uint64_t len);
+/* Engine::filter_bits (host only): words_out (capacity cap words, may be NULL) receives the segments' keep-bitmaps back to
+ * back in manifest order, ceil(N / 32) words each, unused bits 0.  Returns the number of words in all, or -1. */
+int64_t nsh_engine_filter_bits(nsh_engine* e, const char* date_from, const char* date_to, int keep_undated, uint32_t* words_out, uint64_t cap);
+/* Engine::open_filter: filtered copies of the segments' posting streams on the primary device (ns_segment_filter).  At most 8
+ * filters are open; all or nothing.  stats_u64 (6 values, may be NULL): documents kept / total, postings kept / total,
+ * segments that got a device copy, bytes of HBM; stats_ms (2, may be NULL): the device passes, the whole call.  The handle is
+ * good until nsh_engine_close_filter or the next reload (add_documents, compact and delete reload).  -1 without a device. */
+int nsh_engine_open_filter(nsh_engine* e, const char* date_from, const char* date_to, int keep_undated, uint32_t* handle_out,
+                           uint64_t* stats_u64, double* stats_ms);
+/* The same for a caller's bitmaps (laid out as nsh_engine_filter_bits writes them; n_words must match exactly). */
+int nsh_engine_open_filter_bits(nsh_engine* e, const uint32_t* words, uint64_t n_words, uint32_t* handle_out, uint64_t* stats_u64,
+                                double* stats_ms);
+/* -1 for a stale handle (the message says so). */
+int nsh_engine_close_filter(nsh_engine* e, uint32_t handle);
+uint32_t nsh_engine_open_filters(nsh_engine* e);
+/* nsh_engine_search_batch under an open filter: the unfiltered ranking restricted to kept documents (same score bits), found =
+ * kept documents that match, hits in manifest positions.  A query with base terms stays usable with found = 0 when nothing
+ * kept matches.  NS_FLAG_AND: a document must hold every term the unfiltered query has in its segment. */
+int nsh_engine_search_filtered_batch(nsh_engine* e, uint32_t handle, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
+                                     ns_hit* hits, uint32_t* nhits, uint64_t* found, uint8_t* has_found);
+/* Engine::search_filtered: *json_out (free with nsh_free) = search's body plus "filter": {"date_from", "date_to", "documents",
+ * "keep_undated"}; the last 4 distinct filters stay open (they count towards the 8).  On failure -1 and *json_out =
+ * {"error": ...}. */
+int nsh_engine_search_filtered_json(nsh_engine* e, const char* query, int k, const char* date_from, const char* date_to, int keep_undated,
+                                    char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 #include "ns_ingest.hip"
 #include "ns_compact.hip"
 #include "ns_delete.hip"
+#include "ns_filter.hip"
 #include "ns_similar.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
@@ -1747,6 +1748,119 @@ static void ig_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_
         shift += (uint32_t)pb;
         *cur = nxt;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Filtered copy of a segment (csrc/ns_filter.hip)
+extern "C" int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint32_t* keep_bits, const uint64_t* byte_off,
+                                 const uint32_t* counts, uint32_t n_lists, uint64_t* new_byte_off_out, uint32_t* new_counts_out,
+                                 void* postings_out, uint64_t* kept_postings_out, float* device_ms_out, ns_seg** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_segment_filter: ctx is NULL");
+    if (!out) return fail(ctx, NS_E_INVAL, "ns_segment_filter: out is NULL");
+    *out = nullptr;
+    if (!src) return fail(ctx, NS_E_INVAL, "ns_segment_filter: src is NULL");
+    if (src->ctx != ctx) return fail(ctx, NS_E_INVAL, "ns_segment_filter: the source does not belong to this ctx");
+    if (src->pending) return fail(ctx, NS_E_INVAL, "ns_segment_filter: the source's upload has not ended");
+    if (src->id >= ctx->segs.size() || ctx->segs[src->id] != src) return fail(ctx, NS_E_INVAL, "ns_segment_filter: the source does not belong to this ctx");
+    if (src->n_docs && !keep_bits) return fail(ctx, NS_E_INVAL, "ns_segment_filter: keep_bits is NULL");
+    if (n_lists && (!byte_off || !counts || !new_byte_off_out || !new_counts_out)) return fail(ctx, NS_E_INVAL, "ns_segment_filter: null list arrays");
+    if (new_seg_id >= (1u << 20)) return fail(ctx, NS_E_INVAL, "seg_id %u too large", new_seg_id);
+    if (new_seg_id < ctx->segs.size() && ctx->segs[new_seg_id]) return fail(ctx, NS_E_INVAL, "segment %u already uploaded", new_seg_id);
+    for (const ns_seg* p : ctx->pending_uploads)
+        if (p->id == new_seg_id) return fail(ctx, NS_E_INVAL, "segment %u is being uploaded", new_seg_id);
+    if (src->n_postings >= (1ull << 32) - 2 * kFlChunk) return fail(ctx, NS_E_INVAL, "ns_segment_filter: the source has too many postings");
+    if (int rc = check_lists(ctx, src, byte_off, counts, n_lists)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    const uint32_t n = (uint32_t)src->n_postings, n_docs = src->n_docs;
+    const uint32_t n_chunks = (n + kFlChunk - 1) / kFlChunk, m = n_chunks + 1;
+    const uint32_t n_words = (n_docs + 31) / 32;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_bits = nullptr, *d_base = nullptr, *d_sums = nullptr, *d_total = nullptr, *d_starts = nullptr, *d_counts = nullptr, *d_ncnt = nullptr;
+    uint64_t *d_mask = nullptr, *d_noff = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ns_seg* s = new ns_seg();
+    s->ctx = ctx;
+    s->id = new_seg_id;
+    s->n_docs = n_docs;
+    s->avgdl = src->avgdl;
+    s->norm_safe = src->norm_safe;
+    auto cleanup = [&]() {
+        (void)hipFree(d_bits); (void)hipFree(d_base); (void)hipFree(d_sums); (void)hipFree(d_total); (void)hipFree(d_starts);
+        (void)hipFree(d_counts); (void)hipFree(d_ncnt); (void)hipFree(d_mask); (void)hipFree(d_noff);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    };
+    auto bail = [&](int code, const char* what, hipError_t e) {
+        (void)hipStreamSynchronize(st);
+        cleanup();
+        seg_free_device(s);
+        delete s;
+        return fail(ctx, code, "ns_segment_filter: %s: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_bits, (size_t)std::max<uint32_t>(n_words, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, (size_t)m * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_base, (size_t)m * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, (size_t)((m + 1023) / 1024) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_total, 4);
+    if (e == hipSuccess && n_lists) {
+        e = hipMalloc((void**)&d_starts, (size_t)n_lists * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&d_counts, (size_t)n_lists * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&d_ncnt, (size_t)n_lists * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&d_noff, (size_t)n_lists * 8);
+    }
+    if (e != hipSuccess) return bail(NS_E_NOMEM, "allocation", e);
+    std::vector<uint32_t> starts(n_lists);
+    for (uint32_t i = 0; i < n_lists; i++) starts[i] = (uint32_t)(byte_off[i] / 8);
+    if (n_words) e = hipMemcpyAsync(d_bits, keep_bits, (size_t)n_words * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(d_starts, starts.data(), (size_t)n_lists * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(d_counts, counts, (size_t)n_lists * 4, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return bail(NS_E_HIP, "upload", e);
+
+    // mark + scan, then the one number the host needs before it can size the copy
+    const uint32_t grid = std::min<uint32_t>((m + 3) / 4, 1u << 16);
+    (void)hipEventRecord(ev[0], st);
+    hipLaunchKernelGGL(k_fl_mark, dim3(grid), dim3(256), 0, st, src->d_postings, n, d_bits, n_docs, d_mask, d_base);
+    ig_scan(st, d_base, m, d_sums, d_total);
+    (void)hipEventRecord(ev[1], st);
+    uint32_t kept = 0;
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&kept, d_total, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return bail(NS_E_HIP, "mark", e);
+    if (kept > n) return bail(NS_E_HIP, "mark", hipErrorUnknown);
+
+    s->n_postings = kept;
+    if ((e = hipMalloc((void**)&s->d_postings, ((size_t)kept + kPadPostings) * 8)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc postings", e);
+    if ((e = hipMalloc((void**)&s->d_pnorm, ((size_t)kept + kPadPostings) * 4)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc per-posting norms", e);
+    if ((e = hipMalloc((void**)&s->d_norm, (size_t)std::max<uint32_t>(n_docs, 1) * 4)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc norm", e);
+    e = hipMemsetAsync(s->d_postings + kept, 0xFF, kPadPostings * 8, st);   // docId ~0: never taken
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_pnorm + kept, 0, kPadPostings * 4, st);
+    if (e == hipSuccess && n_docs) e = hipMemcpyAsync(s->d_norm, src->d_norm, (size_t)n_docs * 4, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return bail(NS_E_HIP, "copy", e);
+    (void)hipEventRecord(ev[2], st);
+    if (n_chunks) hipLaunchKernelGGL(k_fl_scatter, dim3(std::min<uint32_t>((n_chunks + 3) / 4, 1u << 16)), dim3(256), 0, st, src->d_postings, src->d_pnorm, n, d_mask, d_base, s->d_postings, s->d_pnorm);
+    if (n_lists) hipLaunchKernelGGL(k_fl_lists, dim3((n_lists + 255) / 256), dim3(256), 0, st, d_starts, d_counts, n_lists, d_mask, d_base, d_noff, d_ncnt);
+    (void)hipEventRecord(ev[3], st);
+    e = hipGetLastError();
+    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(new_byte_off_out, d_noff, (size_t)n_lists * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(new_counts_out, d_ncnt, (size_t)n_lists * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && postings_out && kept) e = hipMemcpyAsync(postings_out, s->d_postings, (size_t)kept * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return bail(NS_E_HIP, "scatter", e);
+    if (device_ms_out) {
+        float a = 0.0f, b = 0.0f;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&b, ev[2], ev[3]);
+        *device_ms_out = a + b;
+    }
+    if (kept_postings_out) *kept_postings_out = kept;
+    cleanup();
+    if (ctx->segs.size() <= new_seg_id) ctx->segs.resize(new_seg_id + 1, nullptr);
+    ctx->segs[new_seg_id] = s;
+    *out = s;
+    return NS_OK;
 }
 
 extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_bytes, const uint64_t* offsets, uint32_t n_docs, ns_forward** out) {

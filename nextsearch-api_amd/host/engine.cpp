@@ -49,6 +49,7 @@ size_t Engine::similar_segments_on_device() const {
 
 void Engine::release_device_segments() {
     release_similar();
+    close_all_filters();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
             if (s) ns_segment_release(ctx_, s);
@@ -588,7 +589,8 @@ void Engine::use_impacts(bool on) {
 // qd[q].term_begin is relative to it.  Terms are probed in the dictionary, once per term for all segments.
 void Engine::build_refs_range(const std::vector<std::string>& queries, size_t q0, size_t q1, std::vector<ns_query_desc>& qd,
                               std::vector<ns_term_ref>& refs, std::vector<uint8_t>& usable,
-                              const std::vector<nsx::WeightedTerms>* expanded) const {
+                              const std::vector<nsx::WeightedTerms>* expanded, const nsx::RowSource& rs, bool and_mode) const {
+    const uint32_t S = (uint32_t)segments.size();
     std::vector<int64_t> gid;
     for (size_t q = q0; q < q1; q++) {
         nsx::WeightedTerms own;
@@ -601,12 +603,19 @@ void Engine::build_refs_range(const std::vector<std::string>& queries, size_t q0
         gid.clear();
         for (const auto& tw : terms) gid.push_back(dict.find(tw.first.data(), tw.first.size()));
         for (uint32_t sid = 0; sid < segments.size(); sid++) {
+            if (rs.rows && and_mode) {   // a list of the group lost all its postings: no kept document of the segment matches
+                bool dead = false;
+                for (size_t ti = 0; ti < terms.size() && !dead; ti++)
+                    dead = gid[ti] >= 0 && dict.row((uint32_t)gid[ti])[sid].byte_off != nsx::kAbsent &&
+                           rs.rows[(size_t)gid[ti] * S + sid].byte_off == nsx::kAbsent;
+                if (dead) continue;
+            }
             for (size_t ti = 0; ti < terms.size(); ti++) {
                 if (gid[ti] < 0) continue;                    // :455
-                const nsx::TermSeg& e = dict.row((uint32_t)gid[ti])[sid];
+                const nsx::TermSeg& e = rs.rows ? rs.rows[(size_t)gid[ti] * S + sid] : dict.row((uint32_t)gid[ti])[sid];
                 if (e.byte_off == nsx::kAbsent) continue;     // :455 / :458
                 ns_term_ref r;
-                r.seg_id = sid;
+                r.seg_id = rs.id_base + sid;
                 r.count = e.count;
                 r.byte_off = e.byte_off;
                 r.idf = e.idf;
@@ -621,7 +630,8 @@ void Engine::build_refs_range(const std::vector<std::string>& queries, size_t q0
 // The same for plain base terms (weight 1.0f, src/api_engine.cpp:419-421) straight from the query bytes: no std::string
 // per token, one dictionary probe per term, the per-segment numbers read from the term's row.
 void Engine::build_refs_views(const QueryView* queries, size_t q0, size_t q1, ns_query_desc* qd, std::vector<ns_term_ref>& refs,
-                              uint8_t* usable, std::vector<char>& scratch, std::vector<uint32_t>& gids) const {
+                              uint8_t* usable, std::vector<char>& scratch, std::vector<uint32_t>& gids, const nsx::RowSource& rs,
+                              bool and_mode) const {
     const uint32_t S = (uint32_t)segments.size();
     for (size_t q = q0; q < q1; q++) {
         ns_query_desc& d = qd[q - q0];
@@ -637,10 +647,16 @@ void Engine::build_refs_views(const QueryView* queries, size_t q0, size_t q1, ns
         usable[q - q0] = (n_terms != 0 && S != 0) ? 1 : 0;   // src/api_engine.cpp:407: no base terms (or no segments) -> early return
         if (!usable[q - q0]) continue;
         for (uint32_t sid = 0; sid < S; sid++) {
+            if (rs.rows && and_mode) {   // a list of the group lost all its postings: no kept document of the segment matches
+                bool dead = false;
+                for (const uint32_t g : gids)
+                    if (dict.row(g)[sid].byte_off != nsx::kAbsent && rs.rows[(size_t)g * S + sid].byte_off == nsx::kAbsent) { dead = true; break; }
+                if (dead) continue;
+            }
             for (const uint32_t g : gids) {
-                const nsx::TermSeg& e = dict.row(g)[sid];
+                const nsx::TermSeg& e = rs.rows ? rs.rows[(size_t)g * S + sid] : dict.row(g)[sid];
                 if (e.byte_off == nsx::kAbsent) continue;
-                refs.push_back(ns_term_ref{sid, e.count, e.byte_off, e.idf, 1.0f});
+                refs.push_back(ns_term_ref{rs.id_base + sid, e.count, e.byte_off, e.idf, 1.0f});
             }
         }
         d.term_count = (uint32_t)refs.size() - d.term_begin;
@@ -655,14 +671,14 @@ unsigned Engine::prep_width(size_t Q) const {
 // queries [q0, q1) on the engine's host threads (contiguous slices; the dictionary is read-only), the slices' term refs
 // concatenated in query order.  qd / usable are indexed from q0.
 void Engine::build_refs_parallel(const QueryView* queries, size_t q0, size_t q1, std::vector<ns_query_desc>& qd,
-                                 std::vector<ns_term_ref>& refs, uint8_t* usable) const {
+                                 std::vector<ns_term_ref>& refs, uint8_t* usable, const nsx::RowSource& rs, bool and_mode) const {
     const size_t Q = q1 - q0;
     qd.resize(Q);
     refs.clear();
     const unsigned nt = prep_width(Q);
     if (scratch_.size() < nt) scratch_.resize(nt);
     if (nt <= 1) {
-        build_refs_views(queries, q0, q1, qd.data(), refs, usable, scratch_[0].text, scratch_[0].gids);
+        build_refs_views(queries, q0, q1, qd.data(), refs, usable, scratch_[0].text, scratch_[0].gids, rs, and_mode);
         return;
     }
     if (!pool_ || pool_->width() < nt) pool_.reset(new ForkJoin(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u)));
@@ -670,7 +686,7 @@ void Engine::build_refs_parallel(const QueryView* queries, size_t q0, size_t q1,
         PrepScratch& sc = scratch_[i];
         sc.refs.clear();
         const size_t a = q0 + Q * i / nt, b = q0 + Q * (i + 1) / nt;
-        build_refs_views(queries, a, b, qd.data() + (a - q0), sc.refs, usable + (a - q0), sc.text, sc.gids);
+        build_refs_views(queries, a, b, qd.data() + (a - q0), sc.refs, usable + (a - q0), sc.text, sc.gids, rs, and_mode);
     });
     size_t total = 0;
     std::vector<size_t> base(nt);
@@ -756,14 +772,15 @@ static size_t sub_batch_size() {   // NS_SUBBATCH overrides it (experiments)
 // on the device || results(i - 1) on their way back.  pooled_prep: query preparation on the engine's host threads (the one
 // range of a single-device engine); otherwise on the calling thread (a multi-device engine runs one such call per device).
 bool Engine::run_range(ns_ctx* ctx, const QueryView* queries, size_t q0, size_t q1, int K, uint32_t flags, ns_hit* hits, uint32_t* nhits,
-                       uint64_t* found, uint8_t* usable, bool pooled_prep, std::string& err) {
+                       uint64_t* found, uint8_t* usable, bool pooled_prep, std::string& err, const nsx::RowSource& rs) {
     const size_t Q = q1 - q0;
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
     if (Q == 0) return true;
     const size_t kSubBatch = sub_batch_size();
     const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
     const bool piped = n_sub > 1;
     if (piped) (void)ns_ctx_set_overlap(ctx, 1);
-    struct InFlight { ns_batch* b = nullptr; size_t q0 = 0; };
+    struct InFlight { ns_batch* b = nullptr; size_t q0 = 0, q1 = 0; };
     InFlight prev;
     bool ok = true;
     auto retire = [&](InFlight& f) {
@@ -771,6 +788,9 @@ bool Engine::run_range(ns_ctx* ctx, const QueryView* queries, size_t q0, size_t 
         if (ok) {
             const int rc = ns_batch_fetch(f.b, hits + f.q0 * (size_t)K, nhits + f.q0, found + f.q0);
             if (rc != NS_OK) { err = std::string("ns_batch_fetch: ") + ns_last_error(ctx); ok = false; }
+            if (ok && rs.rows)   // a filter's device ids back to manifest positions
+                for (size_t q = f.q0; q < f.q1; q++)
+                    for (uint32_t i = 0; i < nhits[q]; i++) hits[q * (size_t)K + i].seg_id -= rs.id_base;
         }
         ns_batch_destroy(f.b);
         f.b = nullptr;
@@ -782,14 +802,15 @@ bool Engine::run_range(ns_ctx* ctx, const QueryView* queries, size_t q0, size_t 
     std::vector<ns_term_ref>& refs = pooled_prep ? flat_refs_ : own_refs;
     for (size_t i = 0; i < n_sub && ok; i++) {
         const size_t a = q0 + Q * i / n_sub, b = q0 + Q * (i + 1) / n_sub;
-        if (pooled_prep) build_refs_parallel(queries, a, b, qd, refs, usable + a);
+        if (pooled_prep) build_refs_parallel(queries, a, b, qd, refs, usable + a, rs, and_mode);
         else {
             qd.resize(b - a);
             refs.clear();
-            build_refs_views(queries, a, b, qd.data(), refs, usable + a, own_sc.text, own_sc.gids);
+            build_refs_views(queries, a, b, qd.data(), refs, usable + a, own_sc.text, own_sc.gids, rs, and_mode);
         }
         InFlight cur;
         cur.q0 = a;
+        cur.q1 = b;
         int rc = ns_batch_prepare(ctx, qd.data(), refs.data(), (uint32_t)(b - a), (uint32_t)K, flags, &cur.b);
         if (rc == NS_OK) rc = ns_batch_run(cur.b, NS_RUN_FETCH);
         if (rc != NS_OK) {
@@ -1676,6 +1697,241 @@ bool Engine::more_like_this_text(const std::string& uid, int k, std::string& bod
 std::string Engine::more_like_this(const std::string& uid, int k) {
     std::string body;
     if (!more_like_this_text(uid, k, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- filtered search (host/filter.hpp, csrc/ns_filter.hip) ------------------------------------------------
+bool Engine::filter_bits(const nsx::DocFilter& f, std::vector<std::vector<uint32_t>>& bits) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    bits.clear();
+    nsx::DateRange r;
+    if (!nsx::parse_filter(f, r, err_)) return false;
+    bits.resize(segments.size());
+    for (uint32_t s = 0; s < segments.size(); s++) {
+        const uint32_t N = segments[s].N;
+        bits[s].assign(((size_t)N + 31) / 32, 0u);
+        for (uint32_t d = 0; d < N; d++) {
+            const nsx::MetaFields* md = meta.get(s, d);   // nullptr: no metadata row = undated
+            if (r.keeps(md ? nsx::date_key(md->publish_time) : 0u)) bits[s][d >> 5] |= 1u << (d & 31u);
+        }
+    }
+    return true;
+}
+
+Engine::OpenFilter* Engine::filter_of(uint32_t handle) {
+    OpenFilter& f = filters_[handle % kMaxFilters];
+    return (f.open && f.handle == handle) ? &f : nullptr;
+}
+
+void Engine::close_filter_slot(OpenFilter& f) {
+    if (ctx_)
+        for (ns_seg* s : f.segs)
+            if (s) (void)ns_segment_release(ctx_, s);
+    f = OpenFilter{};
+}
+
+void Engine::close_all_filters() {
+    for (OpenFilter& f : filters_) if (f.open) close_filter_slot(f);
+    filter_lru_.clear();
+}
+
+size_t Engine::open_filters() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const OpenFilter& f : filters_) n += f.open;
+    return n;
+}
+
+bool Engine::close_filter(uint32_t handle) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    OpenFilter* f = filter_of(handle);
+    if (!f) { err_ = "close_filter: handle " + std::to_string(handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    close_filter_slot(*f);
+    filter_lru_.remove_if([&](const FilterLruEnt& e) { return e.handle == handle; });
+    return true;
+}
+
+bool Engine::open_filter(const nsx::DocFilter& f, uint32_t& handle, nsx::FilterStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { err_ = "open_filter: no device context: a filter is built on the device, there is no CPU path"; return false; }
+    std::vector<std::vector<uint32_t>> bits;
+    if (!filter_bits(f, bits)) return false;
+    return open_filter(bits, handle, stats);
+}
+
+bool Engine::open_filter(const std::vector<std::vector<uint32_t>>& bits, uint32_t& handle, nsx::FilterStats* stats) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ctx_) { err_ = "open_filter: no device context: a filter is built on the device, there is no CPU path"; return false; }
+    const uint32_t S = (uint32_t)segments.size();
+    if (bits.size() != S) { err_ = "open_filter: " + std::to_string(bits.size()) + " bitmaps for " + std::to_string(S) + " segments"; return false; }
+    for (uint32_t s = 0; s < S; s++)
+        if (bits[s].size() != ((size_t)segments[s].N + 31) / 32) {
+            err_ = "open_filter: the bitmap of segment " + std::to_string(s) + " has " + std::to_string(bits[s].size()) + " words, its " +
+                   std::to_string(segments[s].N) + " documents need " + std::to_string(((size_t)segments[s].N + 31) / 32);
+            return false;
+        }
+    size_t slot = kMaxFilters;
+    for (size_t i = 0; i < kMaxFilters; i++) if (!filters_[i].open) { slot = i; break; }
+    if (slot == kMaxFilters) { err_ = "open_filter: " + std::to_string(kMaxFilters) + " filters are open already; close one first"; return false; }
+    if (((uint64_t)slot + 2) * S > (1u << 20)) { err_ = "open_filter: the filter's device segment ids would reach 2^20"; return false; }
+    const uint32_t id_base = (uint32_t)(slot + 1) * S;
+
+    OpenFilter fl;
+    fl.segs.assign(S, nullptr);
+    const size_t T = dict.n_terms();
+    fl.rows.assign(T * (size_t)S, nsx::TermSeg{nsx::kAbsent, 0u, 0.0f});
+    nsx::FilterStats fs;
+    std::vector<uint64_t> off, noff;
+    std::vector<uint32_t> cnt, ncnt, gid;
+    auto undo = [&]() { for (ns_seg* s : fl.segs) if (s) (void)ns_segment_release(ctx_, s); };
+    for (uint32_t sid = 0; sid < S; sid++) {
+        const nsx::SegmentData& sd = segments[sid];
+        fs.docs_total += sd.N;
+        fs.postings_total += sd.postings_bytes / 8;
+        uint64_t kept_docs = 0;
+        for (uint32_t w = 0; w < bits[sid].size(); w++) {
+            uint32_t v = bits[sid][w];
+            if (w + 1 == bits[sid].size() && (sd.N & 31u)) v &= (1u << (sd.N & 31u)) - 1u;   // bits past N do not count
+            kept_docs += (uint64_t)__builtin_popcount(v);
+        }
+        fs.docs_kept += kept_docs;
+        if (!kept_docs || !dev_segs_[sid]) continue;
+        // every list of the dictionary that lies inside the payload (a damaged record stays absent under the filter)
+        off.clear(); cnt.clear(); gid.clear();
+        for (size_t g = 0; g < T; g++) {
+            const nsx::TermSeg& e = dict.row((uint32_t)g)[sid];
+            if (e.byte_off == nsx::kAbsent || e.byte_off % 8 != 0 || e.byte_off / 8 + e.count > sd.postings_bytes / 8) continue;
+            off.push_back(e.byte_off); cnt.push_back(e.count); gid.push_back((uint32_t)g);
+        }
+        noff.resize(off.size()); ncnt.resize(off.size());
+        uint64_t kept = 0;
+        float ms = 0.0f;
+        int rc = ns_segment_filter(ctx_, dev_segs_[sid], id_base + sid, bits[sid].data(), off.data(), cnt.data(), (uint32_t)off.size(),
+                                   noff.data(), ncnt.data(), nullptr, &kept, &ms, &fl.segs[sid]);
+        if (rc != NS_OK) { err_ = std::string("ns_segment_filter: ") + ns_last_error(ctx_); undo(); return false; }
+        fs.device_ms += ms;
+        if (!kept) {   // no surviving posting: no copy, no refs
+            (void)ns_segment_release(ctx_, fl.segs[sid]);
+            fl.segs[sid] = nullptr;
+            continue;
+        }
+        fs.postings_kept += kept;
+        fs.segments_on_device++;
+        fs.hbm_bytes += (kept + 256) * 12 + (uint64_t)std::max<uint32_t>(sd.N, 1) * 4;
+        const uint32_t min_count = std::max<uint32_t>(64u, sd.N / 512u);   // reload()'s rule for skip tables
+        std::vector<uint64_t> soff;
+        std::vector<uint32_t> scnt;
+        for (size_t i = 0; i < off.size(); i++) {
+            if (!ncnt[i]) continue;
+            fl.rows[(size_t)gid[i] * S + sid] = nsx::TermSeg{noff[i], ncnt[i], dict.row(gid[i])[sid].idf};
+            if (ncnt[i] >= min_count) { soff.push_back(noff[i]); scnt.push_back(ncnt[i]); }
+        }
+        if (!soff.empty()) (void)ns_segment_build_skips(ctx_, fl.segs[sid], soff.data(), scnt.data(), (uint32_t)soff.size());
+    }
+    fl.open = true;
+    fl.docs_kept = fs.docs_kept;
+    filter_gen_++;
+    fl.handle = (uint32_t)(filter_gen_ * kMaxFilters + slot);
+    handle = fl.handle;
+    filters_[slot] = std::move(fl);
+    fs.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = fs;
+    return true;
+}
+
+bool Engine::search_filtered_batch_flat(uint32_t handle, const QueryView* queries, size_t Q, int k, uint32_t flags, ns_hit* hits,
+                                        uint32_t* nhits, uint64_t* found, uint8_t* usable) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { err_ = "no device context: this engine has no CPU scoring path"; return false; }
+    OpenFilter* f = filter_of(handle);
+    if (!f) { err_ = "search_filtered: handle " + std::to_string(handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = "search_filtered_batch_flat: null argument"; return false; }
+    const int K = std::max(1, std::min(k, 100));
+    if (Q == 0) return true;
+    nsx::RowSource rs;
+    rs.rows = f->rows.data();
+    rs.id_base = (uint32_t)(handle % kMaxFilters + 1) * (uint32_t)segments.size();
+    static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+    if (!rs.rows) rs.rows = &no_rows;   // an index without terms: never read, but "filtered" all the same
+    if (sem.enabled) {   // the expansion of search_batch_flat, then the expanded terms over the filter's rows
+        std::vector<std::string> qs(Q);
+        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
+        std::vector<nsx::WeightedTerms> expanded;
+        if (!expand_queries(qs, expanded)) return false;
+        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
+        std::vector<ns_term_ref> refs;
+        std::vector<uint8_t> us(Q, 0);
+        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, (flags & NS_FLAG_AND) != 0);
+        std::memcpy(usable, us.data(), Q);
+        const int rc = ns_search_batch(ctx_, qd.data(), refs.data(), (uint32_t)Q, (uint32_t)K, hits, nhits, found, flags);
+        if (rc != NS_OK) { err_ = std::string("ns_search_batch: ") + ns_last_error(ctx_); return false; }
+        for (size_t q = 0; q < Q; q++)
+            for (uint32_t i = 0; i < nhits[q]; i++) hits[q * (size_t)K + i].seg_id -= rs.id_base;
+        return true;
+    }
+    return run_range(ctx_, queries, 0, Q, K, flags, hits, nhits, found, usable, /*pooled_prep*/ true, err_, rs);
+}
+
+bool Engine::search_filtered_text(const std::string& query, int k, const nsx::DocFilter& f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_filtered: no device context: this engine has no CPU scoring path"; return false; }
+    nsx::DateRange r;
+    if (!nsx::parse_filter(f, r, err_)) { body = err_; return false; }
+    const std::string key = r.cache_key();
+    OpenFilter* of = nullptr;
+    for (auto it = filter_lru_.begin(); it != filter_lru_.end(); ++it)
+        if (it->key == key) {
+            of = filter_of(it->handle);
+            if (of) filter_lru_.splice(filter_lru_.begin(), filter_lru_, it);
+            else filter_lru_.erase(it);   // closed behind the cache's back
+            break;
+        }
+    if (!of) {
+        while (filter_lru_.size() >= kFilterLru) {   // the least recently used goes
+            if (OpenFilter* old = filter_of(filter_lru_.back().handle)) close_filter_slot(*old);
+            filter_lru_.pop_back();
+        }
+        nsx::DocFilter norm{r.from_text, r.to_text, r.keep_undated};
+        uint32_t h = 0;
+        if (!open_filter(norm, h, nullptr)) { body = err_; return false; }
+        filter_lru_.push_front(FilterLruEnt{key, h});
+        of = filter_of(h);
+    }
+    const int K = std::max(1, std::min(k, 100));
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits((size_t)K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!search_filtered_batch_flat(of->handle, &qv, 1, K, NS_FLAG_OR, hits.data(), &nh, &fd, &us)) { body = err_; return false; }
+    SearchResult res;
+    res.query = query;
+    res.k = K;
+    res.segments = (int)segments.size();
+    res.has_found = us != 0;
+    res.found = fd;
+    if (res.has_found)
+        for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    // search's body with the "filter" member in front ("filter" < "found" < "k": nlohmann keeps keys sorted)
+    std::string o = "{\n  \"filter\": {\n    \"date_from\": ";
+    json_escape(o, r.from_text);
+    o += ",\n    \"date_to\": ";
+    json_escape(o, r.to_text);
+    o += ",\n    \"documents\": " + std::to_string(of->docs_kept);
+    o += std::string(",\n    \"keep_undated\": ") + (r.keep_undated ? "true" : "false") + "\n  },\n";
+    body = o + to_json_impl(res).substr(2);
+    return true;
+}
+
+std::string Engine::search_filtered(const std::string& query, int k, const nsx::DocFilter& f) {
+    std::string body;
+    if (!search_filtered_text(query, k, f, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

@@ -34,6 +34,7 @@
 #include "semantic.hpp"
 #include "similar.hpp"
 #include "correct.hpp"
+#include "filter.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -180,7 +181,8 @@ public:
     // `expanded`: the queries' weighted terms from semantic expansion (nullptr: base terms, weight 1.0)
     void build_refs_range(const std::vector<std::string>& queries, size_t q0, size_t q1, std::vector<ns_query_desc>& qd,
                           std::vector<ns_term_ref>& refs, std::vector<uint8_t>& usable,
-                          const std::vector<nsx::WeightedTerms>* expanded = nullptr) const;
+                          const std::vector<nsx::WeightedTerms>* expanded = nullptr, const nsx::RowSource& rs = nsx::RowSource{},
+                          bool and_mode = false) const;
     // The weighted query terms a search scores (base terms, or their semantic expansion when embeddings are loaded)
     bool expand_queries(const std::vector<std::string>& queries, std::vector<nsx::WeightedTerms>& out) const;
     void build_refs(const std::vector<std::string>& queries, std::vector<ns_query_desc>& qd,
@@ -252,6 +254,33 @@ public:
     // df / idf by term id of segment seg as similar_batch uploads them (host only: works without a device)
     bool similar_term_stats(uint32_t seg, std::vector<uint32_t>& df, std::vector<float>& idf);
 
+    // Filtered search (host/filter.hpp, csrc/ns_filter.hip).  A filter is one keep-bitmap per segment, in
+    // manifest order, ceil(N / 32) words each.  filter_bits: the bitmaps of a date filter from metadata.csv's publish_time
+    // (host only: works on a host-only engine); false for a malformed bound.  The unused bits of a last word are 0.
+    bool filter_bits(const nsx::DocFilter& f, std::vector<std::vector<uint32_t>>& bits);
+    // open_filter: per segment with a kept document ONE ns_segment_filter over every list of the dictionary, on the primary
+    // context; the copies get the device ids (slot + 1) * S + position (S = segments of the index), so the order inside a
+    // filter is manifest order.  A segment without a kept document or without a surviving posting gets no copy.  Lists of
+    // reload()'s size get skip tables.  At most kMaxFilters are open; all or nothing.  The handle is good until
+    // close_filter, the next reload() (add_documents, compact and delete_* reload) or the destructor.
+    static constexpr size_t kMaxFilters = 8;
+    static constexpr size_t kFilterLru = 4;     // search_filtered's own filters, which count towards kMaxFilters
+    bool open_filter(const std::vector<std::vector<uint32_t>>& bits, uint32_t& handle, nsx::FilterStats* stats = nullptr);
+    bool open_filter(const nsx::DocFilter& f, uint32_t& handle, nsx::FilterStats* stats = nullptr);
+    bool close_filter(uint32_t handle);
+    size_t open_filters() const;
+    // search_batch_flat under a filter: the same query preparation, sub-batch pipeline and outputs, with the filter's rows.
+    // Hits are the unfiltered ranking restricted to kept documents (score bits included), found counts kept documents only,
+    // hits carry manifest positions.  Under NS_FLAG_AND a (query, segment) group one of whose lists lost all its postings
+    // emits no refs.  A multi-device engine scores filtered batches on devices[0].  The search cache is not used.
+    bool search_filtered_batch_flat(uint32_t handle, const QueryView* queries, size_t Q, int k, uint32_t flags, ns_hit* hits,
+                                    uint32_t* nhits, uint64_t* found, uint8_t* usable);
+    // JSON text: search's body plus "filter": {"date_from", "date_to", "documents", "keep_undated"} (the bounds without
+    // their blanks; documents = how many are kept), dump(2) layout.  The last kFilterLru distinct filters stay open.
+    // Any failure: {"error": ...} (search_filtered_text: false, body = the message).
+    std::string search_filtered(const std::string& query, int k, const nsx::DocFilter& f);
+    bool search_filtered_text(const std::string& query, int k, const nsx::DocFilter& f, std::string& body);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -278,8 +307,10 @@ private:
     bool cache_on_ = true;
     // query preparation of queries [q0, q1) through the term dictionary: refs appended to `refs`, qd[q - q0] filled with
     // term_begin relative to `refs`' start, usable[q - q0] set
+    // rs: the rows the refs come from (the dictionary's own, or an open filter's); and_mode matters under a filter only
     void build_refs_views(const QueryView* queries, size_t q0, size_t q1, ns_query_desc* qd, std::vector<ns_term_ref>& refs,
-                          uint8_t* usable, std::vector<char>& scratch, std::vector<uint32_t>& gids) const;
+                          uint8_t* usable, std::vector<char>& scratch, std::vector<uint32_t>& gids, const nsx::RowSource& rs = nsx::RowSource{},
+                          bool and_mode = false) const;
     // host threads of query preparation (kept from batch to batch) and their scratch
     struct PrepScratch { std::vector<ns_term_ref> refs; std::vector<char> text; std::vector<uint32_t> gids; };
     mutable std::unique_ptr<ForkJoin> pool_;
@@ -288,7 +319,8 @@ private:
     std::vector<ns_term_ref> flat_refs_;
     unsigned prep_width(size_t Q) const;
     void build_refs_parallel(const QueryView* queries, size_t q0, size_t q1, std::vector<ns_query_desc>& qd,
-                             std::vector<ns_term_ref>& refs, uint8_t* usable) const;
+                             std::vector<ns_term_ref>& refs, uint8_t* usable, const nsx::RowSource& rs = nsx::RowSource{},
+                             bool and_mode = false) const;
     mutable bool refs_failed_ = false;   // build_refs could not run the device part of the expansion (err_ says why)
     int device_;
     ns_ctx* ctx_ = nullptr;
@@ -308,7 +340,22 @@ private:
     std::vector<Replica> replicas_;
     // one contiguous range of a batch on one context: sub-batches pipelined (prepare(i+1) || kernels(i) || results(i-1))
     bool run_range(ns_ctx* ctx, const QueryView* queries, size_t q0, size_t q1, int K, uint32_t flags, ns_hit* hits, uint32_t* nhits,
-                   uint64_t* found, uint8_t* usable, bool pooled_prep, std::string& err);
+                   uint64_t* found, uint8_t* usable, bool pooled_prep, std::string& err, const nsx::RowSource& rs = nsx::RowSource{});
+    // open filters: the device copies per manifest position (nullptr: none) and the rows parallel to dict's
+    struct OpenFilter {
+        bool open = false;
+        uint32_t handle = 0;
+        std::vector<ns_seg*> segs;
+        std::vector<nsx::TermSeg> rows;
+        uint64_t docs_kept = 0;
+    };
+    OpenFilter filters_[kMaxFilters];
+    uint32_t filter_gen_ = 0;
+    OpenFilter* filter_of(uint32_t handle);
+    void close_filter_slot(OpenFilter& f);
+    void close_all_filters();
+    struct FilterLruEnt { std::string key; uint32_t handle; };
+    std::list<FilterLruEnt> filter_lru_;   // most recently used at the front
     mutable std::string err_;
 };
 

@@ -15,6 +15,7 @@
 #include "engine.hpp"
 #include "gen_index.hpp"
 #include "textutil.hpp"
+#include "json_writer.hpp"
 
 struct nsh_engine {
     nextsearch::Engine eng;
@@ -746,3 +747,125 @@ extern "C" int nsh_engine_more_like_this_json(nsh_engine* e, const char* uid, ui
 
 extern "C" void nsh_engine_release_similar(nsh_engine* e) { try { if (e) e->eng.release_similar(); } NSH_CATCH_VOID(e, "nsh_engine_release_similar") }
 extern "C" uint64_t nsh_engine_similar_segments_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.similar_segments_on_device() : 0; }
+
+// ---- filtered search (host/filter.hpp) ----
+extern "C" uint32_t nsh_date_key(const char* s, uint64_t len) { return nsx::date_key(std::string_view(s ? s : "", s ? (size_t)len : 0)); }
+
+static nsx::DocFilter nsh_doc_filter(const char* from, const char* to, int keep_undated) {
+    nsx::DocFilter f;
+    f.date_from = from ? from : "";
+    f.date_to = to ? to : "";
+    f.keep_undated = keep_undated != 0;
+    return f;
+}
+static void nsh_filter_stats_out(const nsx::FilterStats& st, uint64_t* stats_u64, double* stats_ms) {
+    if (stats_u64) {
+        stats_u64[0] = st.docs_kept; stats_u64[1] = st.docs_total; stats_u64[2] = st.postings_kept; stats_u64[3] = st.postings_total;
+        stats_u64[4] = st.segments_on_device; stats_u64[5] = st.hbm_bytes;
+    }
+    if (stats_ms) { stats_ms[0] = st.device_ms; stats_ms[1] = st.total_ms; }
+}
+
+// words_out (capacity cap words, may be NULL): the segments' bitmaps back to back, ceil(N / 32) words each.  Returns the
+// number of words in all, or -1 (a malformed bound).
+extern "C" int64_t nsh_engine_filter_bits(nsh_engine* e, const char* date_from, const char* date_to, int keep_undated, uint32_t* words_out,
+                                          uint64_t cap) { try {
+    if (!e) return -1;
+    std::vector<std::vector<uint32_t>> bits;
+    if (!e->eng.filter_bits(nsh_doc_filter(date_from, date_to, keep_undated), bits)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    uint64_t at = 0;
+    for (const auto& b : bits) {
+        for (size_t i = 0; i < b.size(); i++)
+            if (words_out && at + i < cap) words_out[at + i] = b[i];
+        at += b.size();
+    }
+    return (int64_t)at;
+} NSH_CATCH(e, "nsh_engine_filter_bits", -1)
+}
+
+// stats_u64 (6, may be NULL): documents kept / total, postings kept / total, segments with a device copy, bytes of HBM;
+// stats_ms (2, may be NULL): device passes, whole call
+extern "C" int nsh_engine_open_filter(nsh_engine* e, const char* date_from, const char* date_to, int keep_undated, uint32_t* handle_out,
+                                      uint64_t* stats_u64, double* stats_ms) { try {
+    if (!e || !handle_out) return -1;
+    nsx::FilterStats st;
+    if (!e->eng.open_filter(nsh_doc_filter(date_from, date_to, keep_undated), *handle_out, &st)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    nsh_filter_stats_out(st, stats_u64, stats_ms);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_open_filter", -1)
+}
+
+// words: the segments' bitmaps back to back (n_words in all; the engine checks them against its segments)
+extern "C" int nsh_engine_open_filter_bits(nsh_engine* e, const uint32_t* words, uint64_t n_words, uint32_t* handle_out, uint64_t* stats_u64,
+                                           double* stats_ms) { try {
+    if (!e || !handle_out || (n_words && !words)) return -1;
+    // whole bitmaps as far as the words reach; words left over become one more: the engine refuses either with a message
+    std::vector<std::vector<uint32_t>> bits;
+    uint64_t at = 0;
+    for (size_t s = 0; s < e->eng.segments.size(); s++) {
+        const uint64_t w = ((uint64_t)e->eng.segments[s].N + 31) / 32;
+        if (at + w > n_words) break;
+        bits.emplace_back(words + at, words + at + w);
+        at += w;
+    }
+    if (bits.size() == e->eng.segments.size() && at != n_words) bits.emplace_back(words + at, words + n_words);
+    nsx::FilterStats st;
+    if (!e->eng.open_filter(bits, *handle_out, &st)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    nsh_filter_stats_out(st, stats_u64, stats_ms);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_open_filter_bits", -1)
+}
+
+extern "C" int nsh_engine_close_filter(nsh_engine* e, uint32_t handle) { try {
+    if (!e) return -1;
+    if (!e->eng.close_filter(handle)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_close_filter", -1)
+}
+extern "C" uint32_t nsh_engine_open_filters(nsh_engine* e) { try { return e ? (uint32_t)e->eng.open_filters() : 0; } NSH_CATCH(e, "nsh_engine_open_filters", 0)
+}
+
+// nsh_engine_search_batch under an open filter: the same arrays, hits in manifest positions
+extern "C" int nsh_engine_search_filtered_batch(nsh_engine* e, uint32_t handle, const char* const* queries, uint32_t n_queries, int k,
+                                                uint32_t flags, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint8_t* has_found) { try {
+    if (!e) return -1;
+    const uint32_t K = (uint32_t)std::max(1, std::min(k, 100));
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<ns_hit> h_;
+    std::vector<uint32_t> n_;
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!hits) { h_.resize((size_t)n_queries * K); hits = h_.data(); }
+    if (!nhits) { n_.resize(n_queries); nhits = n_.data(); }
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    if (!e->eng.search_filtered_batch_flat(handle, views.data(), n_queries, k, flags, hits, nhits, found, has_found)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    for (uint32_t q = 0; q < n_queries; q++) {
+        if (has_found[q]) continue;
+        nhits[q] = 0; found[q] = 0;
+        for (uint32_t i = 0; i < K; i++) hits[(size_t)q * K + i] = ns_hit{-__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    }
+    return 0;
+} NSH_CATCH(e, "nsh_engine_search_filtered_batch", -1)
+}
+
+// Engine::search_filtered: *json_out (free with nsh_free) is the body, or {"error": ...} with -1 returned
+extern "C" int nsh_engine_search_filtered_json(nsh_engine* e, const char* query, int k, const char* date_from, const char* date_to,
+                                               int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const bool ok = e->eng.search_filtered_text(query ? query : "", k, nsh_doc_filter(date_from, date_to, keep_undated), s);
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_filtered_json", -1)
+}

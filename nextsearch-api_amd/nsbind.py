@@ -56,6 +56,7 @@ assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 
 # every symbol include/nextsearch_hip.h declares
 HIP_SYMBOLS = [
+    "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
@@ -68,6 +69,8 @@ HIP_SYMBOLS = [
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
 HOST_SYMBOLS = [
+    "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
+    "nsh_engine_search_filtered_batch", "nsh_engine_search_filtered_json",
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
     "nsh_engine_num_segments", "nsh_engine_segment_name", "nsh_engine_segment_info",
     "nsh_engine_segment_doc_len", "nsh_engine_segment_postings", "nsh_engine_lookup", "nsh_bm25_idf",
@@ -160,6 +163,7 @@ def hip_lib():
         L.ns_ctx_use_impacts.argtypes = [vp, i32]
         L.ns_segment_build_skips.argtypes = [vp, vp, vp, vp, u32]
         L.ns_ctx_use_skips.argtypes = [vp, i32]
+        L.ns_segment_filter.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, C.POINTER(u64), C.POINTER(C.c_float), C.POINTER(vp)]
         L.ns_ctx_set_host_threads.argtypes = [vp, u32]
         L.ns_ctx_set_overlap.argtypes = [vp, i32]
         L.ns_segment_build_packed.argtypes = [vp, vp]
@@ -345,6 +349,17 @@ def host_lib():
         L.nsh_engine_release_similar.restype = None
         L.nsh_engine_similar_segments_on_device.argtypes = [vp]
         L.nsh_engine_similar_segments_on_device.restype = u64
+        L.nsh_date_key.argtypes = [C.c_char_p, u64]
+        L.nsh_date_key.restype = u32
+        L.nsh_engine_filter_bits.argtypes = [vp, C.c_char_p, C.c_char_p, i32, vp, u64]
+        L.nsh_engine_filter_bits.restype = C.c_int64
+        L.nsh_engine_open_filter.argtypes = [vp, C.c_char_p, C.c_char_p, i32, C.POINTER(u32), vp, vp]
+        L.nsh_engine_open_filter_bits.argtypes = [vp, vp, u64, C.POINTER(u32), vp, vp]
+        L.nsh_engine_close_filter.argtypes = [vp, u32]
+        L.nsh_engine_open_filters.argtypes = [vp]
+        L.nsh_engine_open_filters.restype = u32
+        L.nsh_engine_search_filtered_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp]
+        L.nsh_engine_search_filtered_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         _host = L
     return _host
 
@@ -654,6 +669,73 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"search_batch failed: {self.error()}")
         return hits, nhits, found, has_found
+
+    # ---- filtered search ----
+    def _bitmap_words(self):
+        return [(self.segment_info(s)["n_docs"] + 31) // 32 for s in range(self.num_segments)]
+
+    def filter_bits(self, date_from="", date_to="", keep_undated=False):
+        """Engine::filter_bits: one uint32 keep-bitmap per segment (manifest order) for a date filter; host only."""
+        words = self._bitmap_words()
+        flat = np.zeros(max(sum(words), 1), dtype=np.uint32)
+        n = self._L.nsh_engine_filter_bits(self.h, _as_bytes(date_from), _as_bytes(date_to), int(bool(keep_undated)), flat.ctypes.data, len(flat))
+        if n < 0:
+            raise RuntimeError(f"filter_bits failed: {self.error()}")
+        assert n == sum(words)
+        cuts = np.cumsum([0] + words)
+        return [flat[cuts[i]:cuts[i + 1]].copy() for i in range(len(words))]
+
+    @staticmethod
+    def _filter_stats(u, ms):
+        return {"docs_kept": int(u[0]), "docs_total": int(u[1]), "postings_kept": int(u[2]), "postings_total": int(u[3]),
+                "segments_on_device": int(u[4]), "hbm_bytes": int(u[5]), "device_ms": float(ms[0]), "total_ms": float(ms[1])}
+
+    def open_filter(self, date_from="", date_to="", keep_undated=False, bits=None, stats=False):
+        """Engine::open_filter for a date filter, or (bits: one uint32 array per segment) for a caller's bitmaps.  Returns the
+        handle, with stats=True (handle, stats)."""
+        h = C.c_uint32()
+        u, ms = np.zeros(6, dtype=np.uint64), np.zeros(2, dtype=np.float64)
+        if bits is not None:
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.uint32).ravel() for b in bits]) if len(bits) else np.zeros(0, np.uint32))
+            rc = self._L.nsh_engine_open_filter_bits(self.h, flat.ctypes.data if len(flat) else None, len(flat), C.byref(h), u.ctypes.data, ms.ctypes.data)
+        else:
+            rc = self._L.nsh_engine_open_filter(self.h, _as_bytes(date_from), _as_bytes(date_to), int(bool(keep_undated)), C.byref(h),
+                                                u.ctypes.data, ms.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"open_filter failed: {self.error()}")
+        return (h.value, self._filter_stats(u, ms)) if stats else h.value
+
+    def close_filter(self, handle):
+        if self._L.nsh_engine_close_filter(self.h, int(handle)) != 0:
+            raise RuntimeError(f"close_filter failed: {self.error()}")
+
+    def open_filters(self):
+        return int(self._L.nsh_engine_open_filters(self.h))
+
+    def search_filtered_batch(self, handle, queries, k, flags=NS_FLAG_OR):
+        """search_batch under an open filter: (hits, nhits, found, has_found), hits in manifest positions."""
+        Q, K = len(queries), clamp_k(k)
+        hits = np.empty((Q, K), dtype=HIT_DTYPE)
+        nhits = np.zeros(Q, dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        rc = self._L.nsh_engine_search_filtered_batch(self.h, int(handle), _cstr_array(queries), Q, k, flags, hits.ctypes.data,
+                                                      nhits.ctypes.data, found.ctypes.data, has_found.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"search_filtered_batch failed: {self.error()}")
+        return hits, nhits, found, has_found
+
+    def search_filtered_json(self, query, k, date_from="", date_to="", keep_undated=False, check=True):
+        """Engine::search_filtered: the JSON text; a failure raises (check=False: returns the {"error": ...} body)."""
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_filtered_json(self.h, _as_bytes(query), k, _as_bytes(date_from), _as_bytes(date_to),
+                                                     int(bool(keep_undated)), C.byref(out))
+        s = C.string_at(out).decode() if out else ""
+        if out:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_filtered failed: {self.error()}")
+        return s
 
     def prepare(self, queries, k, flags=NS_FLAG_OR):
         b = C.c_void_p()
@@ -1335,6 +1417,32 @@ class AcTable:
         if self.h:
             hip_lib().ns_ac_release(self.ctx, self.h)
             self.h = None
+
+
+def date_key(text):
+    """nsx::date_key: YYYY, YYYY-MM or YYYY-MM-DD -> Y * 10000 + M * 100 + D (missing parts 0); anything else 0."""
+    b = _as_bytes(text)
+    return int(host_lib().nsh_date_key(b, len(b)))
+
+
+def segment_filter(ctx, src, new_seg_id, keep_bits, byte_off, counts, payload_cap=None):
+    """ns_segment_filter (raw): the filtered copy of segment handle `src` under id new_seg_id.  payload_cap: the source's
+    number of postings when the filtered payload is wanted back (None: it stays on the device).  Returns (handle, new byte
+    offsets, new counts, kept postings, device ms, filtered payload as (kept, 2) uint32 or None)."""
+    L = hip_lib()
+    bits = np.ascontiguousarray(keep_bits, dtype=np.uint32)
+    off = np.ascontiguousarray(byte_off, dtype=np.uint64)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    n = len(off)
+    noff, ncnt = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+    payload = None if payload_cap is None else np.zeros((max(int(payload_cap), 1), 2), dtype=np.uint32)
+    kept, ms, h = C.c_uint64(), C.c_float(), C.c_void_p()
+    rc = L.ns_segment_filter(ctx, src, int(new_seg_id), bits.ctypes.data if len(bits) else None, off.ctypes.data if n else None,
+                             cnt.ctypes.data if n else None, n, noff.ctypes.data if n else None, ncnt.ctypes.data if n else None,
+                             payload.ctypes.data if payload is not None else None, C.byref(kept), C.byref(ms), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"ns_segment_filter failed ({rc}): {L.ns_last_error(ctx).decode()}")
+    return h, noff[:n], ncnt[:n], int(kept.value), float(ms.value), (payload[: kept.value] if payload is not None else None)
 
 
 def search_batch_raw(ctx, qd, refs, k, flags=NS_FLAG_OR):
