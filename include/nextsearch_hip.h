@@ -508,6 +508,33 @@ void ns_docterms_destroy(ns_docterms* h);
  * document of at most 64 pairs is one chunk of the wave's stream). */
 uint32_t ns_docterms_doc_cut(void);
 
+/* ---- facet counts (csrc/ns_facet.hip, csrc/ns_facet_plan.hpp) ------------------ */
+/* A per-document bucket table on the device, independent of any ns_seg: bucket_of_doc[n_docs], each < n_buckets,
+ * 1 <= n_buckets <= 1024.  A bucket id >= n_buckets is found by a kernel at upload and refused with NS_E_INVAL (as
+ * ns_docterms_upload does for termIds), nothing left allocated.  Release every table before ns_ctx_destroy. */
+typedef struct ns_facet ns_facet;
+int ns_facet_upload(ns_ctx* ctx, uint32_t n_docs, const uint16_t* bucket_of_doc, uint32_t n_buckets, ns_facet** out);
+int ns_facet_release(ns_ctx* ctx, ns_facet* table);
+/* counts_out[q * n_buckets + b] = the number of DISTINCT documents d, summed over the segments, with bucket_of_doc[d] == b,
+ * that query q matches.  NS_FLAG_OR: d is in at least one list that the query's refs name in d's segment.  NS_FLAG_AND: d is
+ * in every one of them (NS_FLAG_AND's rule for scoring: per segment, over the refs of that segment).  found_out[q] (may be
+ * NULL) = the sum over b.  queries / terms are what ns_batch_prepare takes; idf and qweight are ignored: no score is
+ * computed and no norm is read.  seg_ids[i] is the id the refs use for segs[i], whose documents tables[i] buckets, i < n_segs;
+ * a filtered copy (ns_segment_filter) is an ordinary segment here and takes its source's table.
+ * Lists must be docId-ascending (what the index writers produce and ns_segment_filter preserves); a posting whose docId is
+ * >= n_docs is not counted.  A ref listed twice in a query counts its documents once.  term_count == 0: a row of zeros.
+ * Any term_count works.  Synchronous; device_ms_out (may be NULL) = HIP-event time of the kernels.
+ * NS_E_INVAL, with a message and nothing launched: a null argument, a seg_id listed twice, a ref that names a seg_id not
+ * listed, a list outside its segment's payload, a table whose n_docs differs from its segment's, tables of different
+ * n_buckets, a segment or table of another ctx.  n_queries == 0 is NS_OK. */
+int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                   uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                   uint32_t* counts_out /* n_queries * n_buckets */, uint64_t* found_out /* n_queries */, float* device_ms_out);
+/* Documents per work item's tile: 131072 in the product library.  The variants and counting builds read the test knob
+ * NS_FACET_TILE_DOCS (a power of two, 32 .. 131072) from the environment at every call, so that tile edges can be hit with a
+ * few hundred documents; the product library ignores it. */
+uint32_t ns_facet_tile_docs(void);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -338,6 +338,43 @@ int nsh_engine_search_filtered_batch(nsh_engine* e, uint32_t handle, const char*
 int nsh_engine_search_filtered_json(nsh_engine* e, const char* query, int k, const char* date_from, const char* date_to, int keep_undated,
                                     char** json_out);
 
+/* ---- facet counts (host/facet.hpp) ----
+ * kind: 0 year, 1 month (metadata.csv's publish_time through nsh_date_key: key / 10000, key / 100), 2 custom.  Bucket 0 is
+ * "undated" with the label ""; the other buckets are the distinct values present in the index, ascending ("2020", "2020-03";
+ * under month a document dated only "2020" lands in a bucket labelled "2020" in front of 2020's months).  More than 1023
+ * distinct values fail the call.  The documents of year bucket "Y" are exactly what the date filter Y..Y keeps.
+ * custom: custom_buckets = the segments' bucket arrays back to back in manifest order (n_custom ids in all, one per document,
+ * each < n_custom_labels <= 1024); labels as given. */
+typedef struct nsh_facet_spec {
+    uint32_t kind;
+    uint32_t n_custom_labels;
+    const uint16_t* custom_buckets;
+    uint64_t n_custom;
+    const char* const* custom_labels;
+} nsh_facet_spec;
+/* Engine::facet_buckets (host only): buckets_out (capacity cap ids, may be NULL) receives the segments' tables back to back in
+ * manifest order; *n_buckets_out the number of buckets; *labels_out (free with nsh_free; may be NULL) the labels, each
+ * followed by a 0 byte, *labels_bytes_out bytes in all.  Returns the number of ids in all (= documents), or -1. */
+int64_t nsh_engine_facet_buckets(nsh_engine* e, const nsh_facet_spec* spec, uint16_t* buckets_out, uint64_t cap, uint32_t* n_buckets_out,
+                                 char** labels_out, uint64_t* labels_bytes_out);
+/* Engine::facet_batch_flat: counts_out[q * B + b] = the distinct documents of bucket b that query q matches (B as
+ * nsh_engine_facet_buckets reports it; counts_cap entries of capacity, fewer than n_queries * B fail the call), found[q] their
+ * sum = the found of nsh_engine_search_batch (nsh_engine_search_filtered_batch under filter_handle; 0 = no filter) for the
+ * same query and flags, has_found[q] as there.  The device copies of the tables are built by the first call that needs them.
+ * device_ms_out, count_ms_out (may be NULL): the kernels' HIP-event time and the wall time inside ns_facet_count, summed over
+ * the sub-batches.  -1 without a device, for a stale handle, or on failure. */
+int nsh_engine_facet_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                           uint32_t flags, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out,
+                           double* count_ms_out);
+/* Engine::search_faceted: *json_out (free with nsh_free) = search's body (search_filtered's with use_filter != 0) plus
+ * "facets": {"<year|month|custom>": [{"count", "value"}, ...]}, nonzero buckets only, in bucket order.  On failure -1 and
+ * *json_out = {"error": ...}. */
+int nsh_engine_search_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                   const char* date_to, int keep_undated, char** json_out);
+/* Frees the device copies of the bucket tables (reload does too); how many tables have one right now. */
+void nsh_engine_release_facets(nsh_engine* e);
+uint64_t nsh_engine_facet_tables_on_device(nsh_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

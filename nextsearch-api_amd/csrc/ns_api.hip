@@ -26,6 +26,7 @@
 #include "ns_compact.hip"
 #include "ns_delete.hip"
 #include "ns_filter.hip"
+#include "ns_facet.hip"
 #include "ns_similar.hip"
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
@@ -2588,6 +2589,151 @@ extern "C" int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint3
 }
 
 // ------------------------------------------------------------------------------------------------
+// Facet counts (csrc/ns_facet.hip, csrc/ns_facet_plan.hpp)
+struct ns_facet {
+    ns_ctx* ctx = nullptr;
+    uint32_t n_docs = 0, n_buckets = 0;
+    uint16_t* d_buckets = nullptr;
+};
+
+extern "C" uint32_t ns_facet_tile_docs(void) {
+#if defined(NS_VARIANTS) || defined(NS_COUNT)
+    // test knob (variants and counting builds only): small tiles, so that a few hundred documents span several
+    if (const char* t = std::getenv("NS_FACET_TILE_DOCS")) { const long v = std::atol(t); if (v > 0 && v <= (long)kFcTileDocs && fc_tile_ok((uint32_t)v)) return (uint32_t)v; }
+#endif
+    return kFcTileDocs;
+}
+
+extern "C" int ns_facet_upload(ns_ctx* ctx, uint32_t n_docs, const uint16_t* bucket_of_doc, uint32_t n_buckets, ns_facet** out) {
+    const char* fn = "ns_facet_upload";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (n_docs && !bucket_of_doc) return fail(ctx, NS_E_INVAL, "%s: bucket_of_doc is NULL", fn);
+    if (n_buckets < 1 || n_buckets > kFcMaxBuckets) return fail(ctx, NS_E_INVAL, "%s: n_buckets = %u outside [1, %u]", fn, n_buckets, kFcMaxBuckets);
+    ns_facet* t = new ns_facet();
+    t->ctx = ctx; t->n_docs = n_docs; t->n_buckets = n_buckets;
+    hipStream_t st = ctx->stream;
+    uint32_t* d_bad = nullptr;
+    uint32_t bad = 0;
+    hipError_t e = hipSetDevice(ctx->device);
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (e == hipSuccess) chk(hipMalloc((void**)&t->d_buckets, (size_t)std::max<uint32_t>(n_docs, 1) * 2));
+    chk(hipMalloc((void**)&d_bad, 4));
+    if (e == hipSuccess) {
+        if (n_docs) chk(hipMemcpyAsync(t->d_buckets, bucket_of_doc, (size_t)n_docs * 2, hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(d_bad, 0, 4, st));
+        if (e == hipSuccess && n_docs) {
+            hipLaunchKernelGGL(k_fc_check, dim3(std::min<uint32_t>((n_docs + 255) / 256, 1024u)), dim3(256), 0, st, t->d_buckets, n_docs, n_buckets, d_bad);
+            chk(hipGetLastError());
+        }
+        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    }
+    { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host array is the caller's: nothing may still read it)
+    (void)hipFree(d_bad);
+    if (e != hipSuccess || bad) {
+        (void)hipFree(t->d_buckets);
+        delete t;
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return fail(ctx, NS_E_INVAL, "%s: a document has a bucket id >= n_buckets = %u", fn, n_buckets);
+    }
+    *out = t;
+    return NS_OK;
+}
+
+extern "C" int ns_facet_release(ns_ctx* ctx, ns_facet* table) {
+    if (!ctx || !table || table->ctx != ctx) return fail(ctx, NS_E_INVAL, "ns_facet_release: table does not belong to this ctx");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(table->d_buckets);
+    delete table;
+    return NS_OK;
+}
+
+extern "C" int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                              uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                              uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+    const char* fn = "ns_facet_count";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
+    if (!queries || !counts_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed (the number of buckets comes from the tables)", fn);
+    if (!seg_ids || !segs || !tables) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    std::vector<FcSegView> views(n_segs);
+    std::vector<DevFcSeg> dsegs(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        const ns_facet* t = tables[i];
+        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or table %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: table %u does not belong to this ctx", fn, i);
+        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: table %u buckets %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+        if (t->n_buckets != tables[0]->n_buckets) return fail(ctx, NS_E_INVAL, "%s: table %u has %u buckets, table 0 has %u", fn, i, t->n_buckets, tables[0]->n_buckets);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, t->d_buckets, s->n_docs, 0u};
+    }
+    const uint32_t B = tables[0]->n_buckets;
+    std::vector<FcRef> refs;
+    std::vector<FcItem> items;
+    std::string why;
+    if (fc_plan(queries, n_queries, terms, n_terms, (flags & NS_FLAG_AND) != 0, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
+    const size_t n_counts = (size_t)n_queries * B;
+    if (!items.empty()) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        size_t off = 0;
+        const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(FcRef)),
+                     o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_counts = place_at(off, n_counts * 4);
+        const size_t block_bytes = off;
+        char* blk = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        hipError_t e = hipSuccess;
+        auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+        chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+        chk(hipEventCreate(&ev0));
+        chk(hipEventCreate(&ev1));
+        if (e == hipSuccess) {
+            chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(FcRef), hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
+            chk(hipEventRecord(ev0, st));
+            chk(hipMemsetAsync(blk + o_counts, 0, n_counts * 4, st));
+            if (e == hipSuccess) {
+                if (flags & NS_FLAG_AND)
+                    hipLaunchKernelGGL(k_fc_count<true>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const FcRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
+                else
+                    hipLaunchKernelGGL(k_fc_count<false>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const FcRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
+                chk(hipGetLastError());
+            }
+            chk(hipEventRecord(ev1, st));
+            chk(hipMemcpyAsync(counts_out, blk + o_counts, n_counts * 4, hipMemcpyDeviceToHost, st));
+            chk(hipStreamSynchronize(st));
+            float ms = 0.0f;
+            if (e == hipSuccess && device_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+        }
+        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    } else {
+        std::memset(counts_out, 0, n_counts * 4);
+    }
+    if (found_out)
+        for (uint32_t q = 0; q < n_queries; q++) {
+            uint64_t sum = 0;
+            for (uint32_t b = 0; b < B; b++) sum += counts_out[(size_t)q * B + b];
+            found_out[q] = sum;
+        }
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Segment-sharded multi-GPU: join the all-gathered per-rank rows (k_merge_ranks).  Device pointers; asynchronous on the ctx stream.
 extern "C" int ns_merge_rank_rows(ns_ctx* ctx, const void* d_hits, const void* d_nhits, const void* d_found, uint32_t n_ranks,
                                   uint32_t n_queries, uint32_t k, const uint32_t* d_seg_map, uint32_t seg_map_stride,
@@ -3247,6 +3393,15 @@ extern "C" int ns_debug_join_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_jcnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_jcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the facet kernel's paths (ns_facet.hip k_fc_count): 8 values
+extern "C" int ns_debug_facet_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsFcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_fcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_fcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 #endif

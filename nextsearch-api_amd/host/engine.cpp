@@ -49,6 +49,7 @@ size_t Engine::similar_segments_on_device() const {
 
 void Engine::release_device_segments() {
     release_similar();
+    release_facets();
     close_all_filters();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
@@ -1932,6 +1933,212 @@ bool Engine::search_filtered_text(const std::string& query, int k, const nsx::Do
 std::string Engine::search_filtered(const std::string& query, int k, const nsx::DocFilter& f) {
     std::string body;
     if (!search_filtered_text(query, k, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- facet counts (host/facet.hpp, csrc/ns_facet.hip) -------------------------------------------------------
+void Engine::release_facets() {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    for (FacetSet& fs : facets_) {
+        if (ctx_)
+            for (ns_facet* t : fs.dev)
+                if (t) (void)ns_facet_release(ctx_, t);
+        fs = FacetSet{};
+    }
+}
+
+size_t Engine::facet_tables_on_device() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const FacetSet& fs : facets_)
+        for (const ns_facet* t : fs.dev) n += t != nullptr;
+    return n;
+}
+
+bool Engine::facet_buckets(const nsx::FacetSpec& spec, std::vector<std::vector<uint16_t>>& tables, std::vector<std::string>& labels) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    tables.clear();
+    labels.clear();
+    const size_t S = segments.size();
+    if (spec.kind == nsx::FacetSpec::Custom) {
+        const size_t B = spec.custom_labels.size();
+        if (B < 1 || B > nsx::kMaxFacetBuckets) { err_ = "facet custom: " + std::to_string(B) + " labels; a facet has 1 to " + std::to_string(nsx::kMaxFacetBuckets) + " buckets"; return false; }
+        if (spec.custom_buckets.size() != S) { err_ = "facet custom: " + std::to_string(spec.custom_buckets.size()) + " bucket arrays for " + std::to_string(S) + " segments"; return false; }
+        for (size_t s = 0; s < S; s++) {
+            if (spec.custom_buckets[s].size() != segments[s].N) {
+                err_ = "facet custom: the bucket array of segment " + std::to_string(s) + " has " + std::to_string(spec.custom_buckets[s].size()) + " entries, the segment " + std::to_string(segments[s].N) + " documents";
+                return false;
+            }
+            for (const uint16_t b : spec.custom_buckets[s])
+                if (b >= B) { err_ = "facet custom: segment " + std::to_string(s) + " names bucket " + std::to_string(b) + " of " + std::to_string(B); return false; }
+        }
+        tables = spec.custom_buckets;
+        labels = spec.custom_labels;
+        return true;
+    }
+    if (spec.kind != nsx::FacetSpec::Year && spec.kind != nsx::FacetSpec::Month) { err_ = "facet: unknown kind"; return false; }
+    std::vector<std::vector<uint32_t>> keys(S);
+    for (uint32_t s = 0; s < S; s++) {
+        keys[s].resize(segments[s].N);
+        for (uint32_t d = 0; d < segments[s].N; d++) {
+            const nsx::MetaFields* md = meta.get(s, d);   // nullptr: no metadata row = undated
+            keys[s][d] = md ? nsx::date_key(md->publish_time) : 0u;
+        }
+    }
+    return nsx::facet_from_keys(spec.kind, keys, tables, labels, err_);
+}
+
+// the kind's tables on the host and, for every segment with a device copy, on the device
+bool Engine::ensure_facets(const nsx::FacetSpec& spec, FacetSet*& out) {
+    if ((unsigned)spec.kind > 2u) { err_ = "facet: unknown kind"; return false; }
+    FacetSet& fs = facets_[spec.kind];
+    if (fs.built && spec.kind == nsx::FacetSpec::Custom && (fs.tables != spec.custom_buckets || fs.labels != spec.custom_labels)) {
+        for (ns_facet* t : fs.dev) if (t) (void)ns_facet_release(ctx_, t);   // another custom facet takes the kind's place
+        fs = FacetSet{};
+    }
+    if (!fs.built) {
+        FacetSet fresh;
+        if (!facet_buckets(spec, fresh.tables, fresh.labels)) return false;
+        fresh.dev.assign(segments.size(), nullptr);
+        for (uint32_t s = 0; s < segments.size(); s++) {
+            if (!dev_segs_[s]) continue;
+            const int rc = ns_facet_upload(ctx_, segments[s].N, fresh.tables[s].data(), (uint32_t)fresh.labels.size(), &fresh.dev[s]);
+            if (rc != NS_OK) {
+                err_ = std::string("ns_facet_upload: ") + ns_last_error(ctx_);
+                for (ns_facet* t : fresh.dev) if (t) (void)ns_facet_release(ctx_, t);
+                return false;
+            }
+        }
+        fresh.built = true;
+        fs = std::move(fresh);
+    }
+    out = &fs;
+    return true;
+}
+
+bool Engine::facet_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, uint32_t flags,
+                              std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels,
+                              float* device_ms, double* count_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    counts.clear();
+    labels.clear();
+    if (device_ms) *device_ms = 0.0f;
+    if (count_ms) *count_ms = 0.0;
+    if (!ctx_) { err_ = "facet_batch_flat: no device context: facets are counted on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !found || !usable)) { err_ = "facet_batch_flat: null argument"; return false; }
+    OpenFilter* f = nullptr;
+    if (filter_handle) {
+        f = filter_of(filter_handle);
+        if (!f) { err_ = "facet_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    }
+    FacetSet* fs = nullptr;
+    if (!ensure_facets(spec, fs)) return false;
+    labels = fs->labels;
+    const size_t B = labels.size();
+    counts.assign(Q * B, 0u);
+    if (Q == 0) return true;
+    const uint32_t S = (uint32_t)segments.size();
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
+    nsx::RowSource rs;
+    if (f) {   // search_filtered_batch_flat's row source
+        rs.rows = f->rows.data();
+        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
+        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+        if (!rs.rows) rs.rows = &no_rows;
+    }
+    // the segments the refs can name: the index's own, or the filter's copies, each with its position's table
+    std::vector<uint32_t> ids;
+    std::vector<ns_seg*> segs;
+    std::vector<ns_facet*> tabs;
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
+        if (!h || !fs->dev[s]) continue;
+        ids.push_back(rs.id_base + s);
+        segs.push_back(h);
+        tabs.push_back(fs->dev[s]);
+    }
+    auto count_range = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
+        if (ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            return true;
+        }
+        float ms = 0.0f;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = ns_facet_count(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, flags, ids.data(), segs.data(), tabs.data(),
+                                      (uint32_t)ids.size(), counts.data() + a * B, found + a, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_facet_count: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        if (count_ms) *count_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    };
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
+        std::vector<std::string> qs(Q);
+        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
+        std::vector<nsx::WeightedTerms> expanded;
+        if (!expand_queries(qs, expanded)) return false;
+        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
+        std::vector<ns_term_ref> refs;
+        std::vector<uint8_t> us(Q, 0);
+        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
+        std::memcpy(usable, us.data(), Q);
+        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
+            if (!count_range(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
+        return true;
+    }
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
+        if (!count_range(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
+    }
+    return true;
+}
+
+bool Engine::search_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_faceted: no device context: this engine has no CPU scoring path"; return false; }
+    uint32_t handle = 0;
+    if (f) {   // search_filtered's body; its filter is then the most recently used of the cache
+        if (!search_filtered_text(query, k, *f, body)) return false;
+        handle = filter_lru_.front().handle;
+    } else {
+        SearchResult r;
+        if (!search_hits_locked(query, k, NS_FLAG_OR, r)) { body = err_; return false; }
+        body = to_json_impl(r);
+    }
+    const QueryView qv{query.data(), query.size()};
+    std::vector<uint32_t> counts;
+    std::vector<std::string> labels;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!facet_batch_flat(spec, handle, &qv, 1, NS_FLAG_OR, counts, &fd, &us, labels)) { body = err_; return false; }
+    // the "facets" member in front ("facets" < "filter" < "found" < "k": nlohmann keeps keys sorted)
+    std::string o = "{\n  \"facets\": {\n    ";
+    json_escape(o, nsx::facet_kind_name(spec.kind));
+    o += ": [";
+    bool first = true;
+    for (size_t b = 0; b < labels.size(); b++) {
+        if (!counts[b]) continue;
+        o += first ? "\n" : ",\n";
+        first = false;
+        o += "      {\n        \"count\": " + std::to_string(counts[b]) + ",\n        \"value\": ";
+        json_escape(o, labels[b]);
+        o += "\n      }";
+    }
+    o += first ? "]\n  },\n" : "\n    ]\n  },\n";
+    body = o + body.substr(2);
+    return true;
+}
+
+std::string Engine::search_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    if (!search_faceted_text(query, k, spec, f, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

@@ -35,6 +35,7 @@
 #include "similar.hpp"
 #include "correct.hpp"
 #include "filter.hpp"
+#include "facet.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -281,6 +282,30 @@ public:
     std::string search_filtered(const std::string& query, int k, const nsx::DocFilter& f);
     bool search_filtered_text(const std::string& query, int k, const nsx::DocFilter& f, std::string& body);
 
+    // Facet counts (host/facet.hpp, csrc/ns_facet.hip).  facet_buckets: the spec's bucket table per segment
+    // (manifest order, one uint16 per document) and the labels, bucket 0 = undated = ""; host only (works on a host-only
+    // engine).  false: more than 1023 distinct values, or a Custom spec that does not fit the index.
+    bool facet_buckets(const nsx::FacetSpec& spec, std::vector<std::vector<uint16_t>>& tables, std::vector<std::string>& labels);
+    // facet_batch_flat: counts (resized to Q x B, B = labels.size()) [q * B + b] = the distinct documents of bucket b that
+    // query q matches; found[q] = their sum.  The query preparation is search_batch_flat's (search_filtered_batch_flat's under
+    // a filter handle; 0 = no filter): build_refs_parallel, semantic expansion when embeddings are loaded, the filter's rows.
+    // So found[q] equals the search's found, query for query, and usable[q] its usable.  No score is computed.  Large
+    // batches are cut like run_range's sub-batches.  Runs on the primary context.  The device copies of the bucket tables
+    // are built by the first call that needs them (never by reload()), at most one per (kind, segment), serve the filtered
+    // copies under a filter unchanged, and are freed by reload(), release_facets() and the destructor.  device_ms / count_ms
+    // (may be null): the kernels' HIP-event time and the wall time inside ns_facet_count, summed over the sub-batches.
+    bool facet_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, uint32_t flags,
+                          std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels,
+                          float* device_ms = nullptr, double* count_ms = nullptr);
+    // JSON text: search's body (search_filtered's when a filter is given) plus "facets": {"<year|month|custom>": [{"count",
+    // "value"}, ...]}: the nonzero buckets in bucket order (values ascending, undated first with ""), dump(2) layout.  The
+    // counts are those of the query under the filter.  The search cache is not used.  Any failure: {"error": ...}
+    // (search_faceted_text: false, body = the message).
+    std::string search_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
+    void release_facets();
+    size_t facet_tables_on_device() const;   // bucket tables with a device copy right now
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -356,6 +381,15 @@ private:
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };
     std::list<FilterLruEnt> filter_lru_;   // most recently used at the front
+    // facets: per kind the host tables and labels and their device copies (nullptr: the segment has none)
+    struct FacetSet {
+        bool built = false;
+        std::vector<std::vector<uint16_t>> tables;
+        std::vector<std::string> labels;
+        std::vector<ns_facet*> dev;
+    };
+    FacetSet facets_[3];
+    bool ensure_facets(const nsx::FacetSpec& spec, FacetSet*& out);
     mutable std::string err_;
 };
 

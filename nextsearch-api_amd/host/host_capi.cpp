@@ -869,3 +869,109 @@ extern "C" int nsh_engine_search_filtered_json(nsh_engine* e, const char* query,
     return ok ? 0 : -1;
 } NSH_CATCH(e, "nsh_engine_search_filtered_json", -1)
 }
+
+// ---- facet counts (host/facet.hpp) ----
+// the C spec as the engine's; false (message in `why`): no spec, an unknown kind or a null array
+static bool nsh_facet_spec_of(nsh_engine* e, const nsh_facet_spec* in, nsx::FacetSpec& out, std::string& why) {
+    if (!in) { why = "facet: spec is NULL"; return false; }
+    if (in->kind > 2u) { why = "facet: unknown kind " + std::to_string(in->kind); return false; }
+    out.kind = (nsx::FacetSpec::Kind)in->kind;
+    if (out.kind != nsx::FacetSpec::Custom) return true;
+    if ((in->n_custom && !in->custom_buckets) || (in->n_custom_labels && !in->custom_labels)) { why = "facet custom: null array"; return false; }
+    // whole arrays as far as the ids reach; ids left over become one more: the engine refuses either with a message
+    uint64_t at = 0;
+    for (const auto& sd : e->eng.segments) {
+        if (at + sd.N > in->n_custom) break;
+        out.custom_buckets.emplace_back(in->custom_buckets + at, in->custom_buckets + at + sd.N);
+        at += sd.N;
+    }
+    if (out.custom_buckets.size() == e->eng.segments.size() && at != in->n_custom) out.custom_buckets.emplace_back(in->custom_buckets + at, in->custom_buckets + in->n_custom);
+    for (uint32_t i = 0; i < in->n_custom_labels; i++) out.custom_labels.emplace_back(in->custom_labels[i] ? in->custom_labels[i] : "");
+    return true;
+}
+
+extern "C" int64_t nsh_engine_facet_buckets(nsh_engine* e, const nsh_facet_spec* spec, uint16_t* buckets_out, uint64_t cap, uint32_t* n_buckets_out,
+                                            char** labels_out, uint64_t* labels_bytes_out) { try {
+    if (!e) return -1;
+    if (labels_out) *labels_out = nullptr;
+    nsx::FacetSpec sp;
+    std::string why;
+    if (!nsh_facet_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    std::vector<std::vector<uint16_t>> tables;
+    std::vector<std::string> labels;
+    if (!e->eng.facet_buckets(sp, tables, labels)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    uint64_t at = 0;
+    for (const auto& t : tables) {
+        for (size_t i = 0; i < t.size(); i++)
+            if (buckets_out && at + i < cap) buckets_out[at + i] = t[i];
+        at += t.size();
+    }
+    if (n_buckets_out) *n_buckets_out = (uint32_t)labels.size();
+    std::string flat;
+    for (const auto& l : labels) { flat += l; flat.push_back('\0'); }
+    if (labels_bytes_out) *labels_bytes_out = flat.size();
+    if (labels_out) {
+        *labels_out = (char*)std::malloc(flat.size() + 1);
+        if (!*labels_out) return -1;
+        std::memcpy(*labels_out, flat.data(), flat.size());
+        (*labels_out)[flat.size()] = '\0';
+    }
+    return (int64_t)at;
+} NSH_CATCH(e, "nsh_engine_facet_buckets", -1)
+}
+
+extern "C" int nsh_engine_facet_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                      uint32_t flags, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found,
+                                      float* device_ms_out, double* count_ms_out) { try {
+    if (!e) return -1;
+    nsx::FacetSpec sp;
+    std::string why;
+    if (!nsh_facet_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && !queries) { nsh_set_err(e, "nsh_engine_facet_batch: queries is NULL"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    std::vector<uint32_t> counts;
+    std::vector<std::string> labels;
+    if (!e->eng.facet_batch_flat(sp, filter_handle, views.data(), n_queries, flags, counts, found, has_found, labels, device_ms_out, count_ms_out)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    if (counts.size() > counts_cap || (!counts.empty() && !counts_out)) {
+        nsh_set_err(e, "nsh_engine_facet_batch: counts_out holds " + std::to_string(counts_cap) + " entries, " + std::to_string(n_queries) + " queries x " +
+                           std::to_string(labels.size()) + " buckets need " + std::to_string(counts.size()));
+        return -1;
+    }
+    if (!counts.empty()) std::memcpy(counts_out, counts.data(), counts.size() * 4);
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_facet_batch", -1)
+}
+
+extern "C" int nsh_engine_search_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                              const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::FacetSpec sp;
+    bool ok = nsh_facet_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_faceted_json", -1)
+}
+
+extern "C" void nsh_engine_release_facets(nsh_engine* e) { try { if (e) e->eng.release_facets(); } NSH_CATCH_VOID(e, "nsh_engine_release_facets") }
+extern "C" uint64_t nsh_engine_facet_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.facet_tables_on_device() : 0; }

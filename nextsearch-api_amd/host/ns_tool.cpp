@@ -15,6 +15,9 @@
 //   ns_tool search-filtered <index_dir> <from> <to> <k> <query text ...>   (needs an MI355X)
 //        Engine::search_filtered: the search restricted to the documents dated from..to (YYYY, YYYY-MM or YYYY-MM-DD; "" or
 //        "-" leaves a bound open); prints search's JSON body plus the "filter" member (filter.hpp).
+//   ns_tool search-faceted <index_dir> <year|month> <from> <to> <k> <query text ...>   (needs an MI355X)
+//        Engine::search_faceted: search's JSON body plus "facets": the matched documents per year (month) of publish_time
+//        (facet.hpp).  from / to as search-filtered's; "-" "-" searches the whole index, without a "filter" member.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -70,6 +73,25 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
         if (!eng.search_filtered_text(q, k, f, body)) { std::fprintf(stderr, "search-filtered failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 8 && std::strcmp(argv[1], "search-faceted") == 0) {
+        nsx::FacetSpec spec;
+        if (std::strcmp(argv[3], "year") == 0) spec.kind = nsx::FacetSpec::Year;
+        else if (std::strcmp(argv[3], "month") == 0) spec.kind = nsx::FacetSpec::Month;
+        else { std::fprintf(stderr, "search-faceted: the facet is year or month, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) f.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) f.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        std::string q, body;
+        for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_faceted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-faceted failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
@@ -200,6 +222,6 @@ int main(int argc, char** argv) {
                     Q, K, refs.size(), reload_ms, p, p > 0 ? Q / (p * 1e-3) : 0.0, f, f > 0 ? Q / (f * 1e-3) : 0.0, reps, (unsigned long long)check);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n       %s complete <index_dir> <input> [limit]\n       %s similar <index_dir> <uid> [k]\n       %s search-filtered <index_dir> <from> <to> <k> <query...>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, "usage: %s gen-index <dir> <n_segments> <docs_per_segment> [vocab] [seed] [--legacy]\n       %s search <dir> <k> <query...>\n       %s index <segment_dir> <documents_file> [device]\n       %s compact <index_dir> [first count]\n       %s delete <index_dir> <uid>...\n       %s correct <index_dir> <query> [limit]\n       %s complete <index_dir> <input> [limit]\n       %s similar <index_dir> <uid> [k]\n       %s search-filtered <index_dir> <from> <to> <k> <query...>\n       %s search-faceted <index_dir> <year|month> <from> <to> <k> <query...>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
 }

@@ -56,6 +56,7 @@ assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 
 # every symbol include/nextsearch_hip.h declares
 HIP_SYMBOLS = [
+    "ns_facet_upload", "ns_facet_release", "ns_facet_count", "ns_facet_tile_docs",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -69,6 +70,7 @@ HIP_SYMBOLS = [
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
 HOST_SYMBOLS = [
+    "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
     "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
     "nsh_engine_search_filtered_batch", "nsh_engine_search_filtered_json",
     "nsh_gen_index", "nsh_engine_open", "nsh_engine_open_multi", "nsh_engine_num_devices", "nsh_shard_bounds", "nsh_engine_close", "nsh_engine_reload", "nsh_engine_error", "nsh_engine_ctx",
@@ -127,6 +129,13 @@ class NshDeleteStats(C.Structure):   # include/nextsearch_host.h nsh_delete_stat
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
+
+class NshFacetSpec(C.Structure):   # include/nextsearch_host.h nsh_facet_spec
+    _fields_ = [("kind", C.c_uint32), ("n_custom_labels", C.c_uint32), ("custom_buckets", C.c_void_p), ("n_custom", C.c_uint64),
+                ("custom_labels", C.POINTER(C.c_char_p))]
+
+
+FACET_KINDS = {"year": 0, "month": 1, "custom": 2}
 
 _hip = None
 _host = None
@@ -208,6 +217,11 @@ def hip_lib():
         L.ns_docterms_destroy.restype = None
         L.ns_docterms_doc_cut.argtypes = []
         L.ns_docterms_doc_cut.restype = u32
+        L.ns_facet_upload.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
+        L.ns_facet_release.argtypes = [vp, vp]
+        L.ns_facet_count.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
+        L.ns_facet_tile_docs.argtypes = []
+        L.ns_facet_tile_docs.restype = u32
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -217,7 +231,7 @@ def hip_lib():
 
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
-                  "ns_debug_join_counters": 16}
+                  "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8}
 
 
 def debug_counters(reset=False):
@@ -360,6 +374,14 @@ def host_lib():
         L.nsh_engine_open_filters.restype = u32
         L.nsh_engine_search_filtered_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp]
         L.nsh_engine_search_filtered_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_facet_buckets.argtypes = [vp, C.POINTER(NshFacetSpec), vp, u64, C.POINTER(u32), C.POINTER(vp), C.POINTER(u64)]
+        L.nsh_engine_facet_buckets.restype = C.c_int64
+        L.nsh_engine_facet_batch.argtypes = [vp, C.POINTER(NshFacetSpec), u32, C.POINTER(C.c_char_p), u32, u32, vp, u64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+        L.nsh_engine_search_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_release_facets.argtypes = [vp]
+        L.nsh_engine_release_facets.restype = None
+        L.nsh_engine_facet_tables_on_device.argtypes = [vp]
+        L.nsh_engine_facet_tables_on_device.restype = u64
         _host = L
     return _host
 
@@ -736,6 +758,73 @@ class Engine:
         if rc != 0 and check:
             raise RuntimeError(f"search_filtered failed: {self.error()}")
         return s
+
+    # ---- facet counts ----
+    @staticmethod
+    def _facet_spec(kind, custom=None, labels=None):
+        """-> (NshFacetSpec, the objects it points into).  custom: one uint16 array per segment; labels: the custom labels."""
+        sp = NshFacetSpec()
+        sp.kind = FACET_KINDS[kind] if isinstance(kind, str) else int(kind)
+        keep = []
+        if custom is not None:
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.uint16).ravel() for t in custom]) if len(custom) else np.zeros(0, np.uint16))
+            arr = _cstr_array(list(labels or []))
+            sp.custom_buckets, sp.n_custom, sp.custom_labels, sp.n_custom_labels = flat.ctypes.data if len(flat) else None, len(flat), arr, len(arr)
+            keep = [flat, arr]
+        return sp, keep
+
+    def facet_buckets(self, kind="year", custom=None, labels=None):
+        """Engine::facet_buckets (host only): ([one uint16 bucket array per segment], [labels]); bucket 0 = undated = ''."""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        docs = [self.segment_info(s)["n_docs"] for s in range(self.num_segments)]
+        flat = np.zeros(max(sum(docs), 1), dtype=np.uint16)
+        nb, lab, nbytes = C.c_uint32(), C.c_void_p(), C.c_uint64()
+        n = self._L.nsh_engine_facet_buckets(self.h, C.byref(sp), flat.ctypes.data, len(flat), C.byref(nb), C.byref(lab), C.byref(nbytes))
+        if n < 0:
+            raise RuntimeError(f"facet_buckets failed: {self.error()}")
+        raw = C.string_at(lab, nbytes.value) if lab else b""
+        if lab:
+            self._L.nsh_free(lab)
+        names = [x.decode() for x in raw.split(b"\0")[:nb.value]]
+        assert n == sum(docs) and len(names) == nb.value
+        cuts = np.cumsum([0] + docs)
+        return [flat[cuts[i]:cuts[i + 1]].copy() for i in range(len(docs))], names
+
+    def facet_batch(self, queries, n_buckets, kind="year", flags=NS_FLAG_OR, handle=0, custom=None, labels=None, timing=False):
+        """Engine::facet_batch_flat: (counts Q x n_buckets, found, has_found); n_buckets = len(facet_buckets(...)[1]).
+        handle: an open filter's (0: none).  timing=True adds (the kernels' device ms, the wall ms inside ns_facet_count)."""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        Q = len(queries)
+        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        ms, wall = C.c_float(), C.c_double()
+        rc = self._L.nsh_engine_facet_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, flags, counts.ctypes.data, counts.size,
+                                            found.ctypes.data, has_found.ctypes.data, C.byref(ms), C.byref(wall))
+        if rc != 0:
+            raise RuntimeError(f"facet_batch failed: {self.error()}")
+        return (counts, found, has_found, float(ms.value), float(wall.value)) if timing else (counts, found, has_found)
+
+    def search_faceted_json(self, query, k, kind="year", date_filter=None, custom=None, labels=None, check=True):
+        """Engine::search_faceted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure raises
+        (check=False: returns the {"error": ...} body)."""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_faceted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
+                                                    int(bool(ku)), C.byref(out))
+        s = C.string_at(out).decode() if out else ""
+        if out:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_faceted failed: {self.error()}")
+        return s
+
+    def release_facets(self):
+        self._L.nsh_engine_release_facets(self.h)
+
+    def facet_tables_on_device(self):
+        return int(self._L.nsh_engine_facet_tables_on_device(self.h))
 
     def prepare(self, queries, k, flags=NS_FLAG_OR):
         b = C.c_void_p()
@@ -1443,6 +1532,37 @@ def segment_filter(ctx, src, new_seg_id, keep_bits, byte_off, counts, payload_ca
     if rc != 0:
         raise RuntimeError(f"ns_segment_filter failed ({rc}): {L.ns_last_error(ctx).decode()}")
     return h, noff[:n], ncnt[:n], int(kept.value), float(ms.value), (payload[: kept.value] if payload is not None else None)
+
+
+def facet_tile_docs():
+    """documents per tile of ns_facet_count's work items (the variants and counting builds read NS_FACET_TILE_DOCS)"""
+    return int(hip_lib().ns_facet_tile_docs())
+
+
+def facet_upload(ctx, buckets, n_buckets):
+    """ns_facet_upload (raw): (rc, handle); buckets: one uint16 id per document"""
+    b = np.ascontiguousarray(buckets, dtype=np.uint16)
+    h = C.c_void_p()
+    rc = hip_lib().ns_facet_upload(ctx, len(b), b.ctypes.data if len(b) else None, int(n_buckets), C.byref(h))
+    return rc, h
+
+
+def facet_release(ctx, table):
+    return hip_lib().ns_facet_release(ctx, table)
+
+
+def facet_count(ctx, qd, refs, flags, seg_ids, segs, tables, n_buckets):
+    """ns_facet_count (raw): (rc, counts Q x n_buckets, found, device ms); segs / tables: lists of handles"""
+    Q = len(qd)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    counts = np.full((max(Q, 1), int(n_buckets)), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_facet_count(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None, len(refs), int(flags),
+                                  ids.ctypes.data if len(ids) else None, sa, ta, len(ids), counts.ctypes.data, found.ctypes.data, C.byref(ms))
+    return rc, counts[:Q], found[:Q], float(ms.value)
 
 
 def search_batch_raw(ctx, qd, refs, k, flags=NS_FLAG_OR):
