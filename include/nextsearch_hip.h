@@ -535,6 +535,50 @@ int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries
  * few hundred documents; the product library ignores it. */
 uint32_t ns_facet_tile_docs(void);
 
+/* ---- search sorted by a per-document key (csrc/ns_sorted.hip, csrc/ns_sorted_plan.hpp) ---- */
+/* A per-document uint32 sort key on the device, independent of any ns_seg, like ns_facet: keys[n_docs].  Key 0 means "no key"
+ * (an undated article).  The value 0xFFFFFFFF is reserved: a kernel finds it at upload and the call refuses it with
+ * NS_E_INVAL, nothing left allocated.  Release every table before ns_ctx_destroy. */
+typedef struct ns_dockeys ns_dockeys;
+int ns_dockeys_upload(ns_ctx* ctx, uint32_t n_docs, const uint32_t* keys, ns_dockeys** out);
+int ns_dockeys_release(ns_ctx* ctx, ns_dockeys* table);
+/* direction of ns_search_sorted, or-ed into its flags next to NS_FLAG_OR / NS_FLAG_AND */
+#define NS_SORT_DESC    0u       /* larger key first ("newest first") */
+#define NS_SORT_ASC     0x1000u  /* smaller non-zero key first ("oldest first") */
+/* The first K = clamp(k, 1, NS_MAX_K) documents of each query's matched set in key order, with their BM25 scores.
+ *   MATCHED SET  exactly ns_facet_count's.  NS_FLAG_OR: per segment, a document in at least one list the query's refs name
+ *                there; NS_FLAG_AND: in every one of them.  Postings with docId >= n_docs are ignored; a list named twice
+ *                matches once; term_count == 0 gives nhits = 0, found = 0; any term_count works.  found_out[q] (may be NULL)
+ *                is the size of the set summed over the segments: ns_facet_count's found and the scoring path's.
+ *   ORDER        one total order, so the answer is unique: (rank key, position of the segment in the call's list ascending,
+ *                docId ascending).  NS_SORT_DESC: a larger key first; NS_SORT_ASC: a smaller non-zero key first.  KEY 0 IS
+ *                LAST IN BOTH DIRECTIONS.  (One transform gives both: t = key, or t = key ? ~key : 0 under NS_SORT_ASC, larger t
+ *                first; that is why 0xFFFFFFFF is reserved.)  The position in seg_ids orders, not the id's value.
+ *   HITS         hits_out[q * K + r] = {score, seg_ids[i] of the segment, docId}, keys_out[q * K + r] = the document's key as
+ *                uploaded.  nhits_out[q] = min(K, found); the tail past it is {-inf, 0xFFFFFFFF, 0xFFFFFFFF} with key 0.
+ *   SCORE        the BM25 score the scoring path gives that document for that query, bit for bit: the accumulator starts at
+ *                +0.0f; over the query's refs of the hit's segment IN QUERY ORDER, duplicates included, it adds
+ *                qweight * ((idf * (tf * 2.2f)) / (tf + norm[doc])), every operation rounded to fp32, with the segment's
+ *                per-document norm and the correctly rounded division.  A ref whose list does not hold the document adds
+ *                nothing.  NS_FLAG_AND scores over the same refs.
+ * seg_ids[i] is the id the refs use for segs[i], whose documents keys[i] keys, i < n_segs; a filtered copy (ns_segment_filter)
+ * is an ordinary segment here: it takes its source's key table and its own norms.  Lists must be docId-ascending; one that is
+ * not may lose hits but nothing is read or written out of bounds.  Synchronous; device_ms_out (may be NULL) = HIP-event time
+ * of the kernels.  A large batch is cut into sub-batches so that the candidate rows (work items x K x 8 B) never exceed
+ * 64 MiB of device memory.
+ * NS_E_INVAL, with a message and nothing launched: a null argument, no segment listed, a seg_id listed twice, a ref that names
+ * a seg_id not listed, a list outside its segment's payload, a key table whose n_docs differs from its segment's, a segment
+ * or table of another ctx, a flag bit other than NS_FLAG_AND and NS_SORT_ASC, a single query whose work items alone exceed
+ * the candidate buffer.  n_queries == 0 is NS_OK. */
+int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                     uint32_t k, uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
+                     ns_hit* hits_out /* Q x K */, uint32_t* keys_out /* Q x K */, uint32_t* nhits_out, uint64_t* found_out,
+                     float* device_ms_out);
+/* HIP-event time of k_sd_select, k_sd_join and k_sd_score, summed over the calling thread's ns_search_sorted calls (and their
+ * sub-batches) since the last reset: out3[0..2], milliseconds; reset != 0 zeroes the sums after the read.  For
+ * tools/sorted_bench.py. */
+int ns_sorted_kernel_ms(float* out3, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -375,6 +375,33 @@ int nsh_engine_search_faceted_json(nsh_engine* e, const char* query, int k, cons
 void nsh_engine_release_facets(nsh_engine* e);
 uint64_t nsh_engine_facet_tables_on_device(nsh_engine* e);
 
+/* ---- search sorted by date (host/sorted.hpp) ----
+ * A sort order is one uint32 key per document and a direction: kind 0 = date_key() of metadata.csv's publish_time (YYYYMMDD,
+ * missing parts 0, undated 0), kind 1 = the caller's keys (the segments' arrays back to back in manifest order; n_custom =
+ * their total).  Key 0 is last in both directions; 0xFFFFFFFF is reserved and refused. */
+typedef struct nsh_sort_spec {
+    uint32_t kind;         /* 0 date, 1 custom */
+    uint32_t ascending;    /* 0: newest (largest key) first; else oldest (smallest non-zero key) first */
+    const uint32_t* custom_keys;
+    uint64_t n_custom;
+} nsh_sort_spec;
+/* Engine::sort_keys (host only): keys_out (capacity cap keys, may be NULL) receives the segments' keys back to back in
+ * manifest order.  Returns their total number, or -1 (nsh_engine_error). */
+int64_t nsh_engine_sort_keys(nsh_engine* e, const nsh_sort_spec* spec, uint32_t* keys_out, uint64_t cap);
+/* Engine::search_sorted_batch_flat: per query the first K = clamp(k, 1, 100) matched documents in the order (key, manifest
+ * position ascending, docId ascending) with their BM25 scores; hits (n_queries x K nsh/ns_hit {score, segment position,
+ * docId}), keys_out (n_queries x K), nhits, found, has_found as nsh_engine_search_batch's (found 0 where has_found is 0).
+ * flags: NS_FLAG_OR or NS_FLAG_AND.  filter_handle: an open filter's, or 0.  device_ms_out (may be NULL): the kernels' time. */
+int nsh_engine_search_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                   int k, uint32_t flags, void* hits, uint32_t* keys_out, uint32_t* nhits, uint64_t* found, uint8_t* has_found,
+                                   float* device_ms_out);
+/* Engine::search_sorted: *json_out (free with nsh_free) = search's body (search_filtered's with use_filter != 0) with "results"
+ * in date order plus "sort": "newest" | "oldest" | "custom".  On failure -1 and {"error": ...}. */
+int nsh_engine_search_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                  const char* date_to, int keep_undated, char** json_out);
+void nsh_engine_release_sorted(nsh_engine* e);
+uint64_t nsh_engine_sort_tables_on_device(nsh_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

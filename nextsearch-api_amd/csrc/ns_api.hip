@@ -28,6 +28,7 @@
 #include "ns_filter.hip"
 #include "ns_facet.hip"
 #include "ns_similar.hip"
+#include "ns_sorted.hip"   // after ns_facet.hip (fc_cut, fc_mark, fc_lower_bound) and ns_similar.hip (ml_sort_up, ml_merge_down, ml_join)
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
@@ -2734,6 +2735,185 @@ extern "C" int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_
 }
 
 // ------------------------------------------------------------------------------------------------
+// Search sorted by a per-document key (csrc/ns_sorted.hip, csrc/ns_sorted_plan.hpp)
+struct ns_dockeys {
+    ns_ctx* ctx = nullptr;
+    uint32_t n_docs = 0;
+    uint32_t* d_keys = nullptr;
+};
+static thread_local float g_sd_ms[3] = {0.0f, 0.0f, 0.0f};   // k_sd_select, k_sd_join, k_sd_score: summed over the thread's ns_search_sorted calls (ns_sorted_kernel_ms)
+
+extern "C" int ns_dockeys_upload(ns_ctx* ctx, uint32_t n_docs, const uint32_t* keys, ns_dockeys** out) {
+    const char* fn = "ns_dockeys_upload";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (n_docs && !keys) return fail(ctx, NS_E_INVAL, "%s: keys is NULL", fn);
+    ns_dockeys* t = new ns_dockeys();
+    t->ctx = ctx; t->n_docs = n_docs;
+    hipStream_t st = ctx->stream;
+    uint32_t* d_bad = nullptr;
+    uint32_t bad = 0;
+    hipError_t e = hipSetDevice(ctx->device);
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (e == hipSuccess) chk(hipMalloc((void**)&t->d_keys, (size_t)std::max<uint32_t>(n_docs, 1) * 4));
+    chk(hipMalloc((void**)&d_bad, 4));
+    if (e == hipSuccess) {
+        if (n_docs) chk(hipMemcpyAsync(t->d_keys, keys, (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(d_bad, 0, 4, st));
+        if (e == hipSuccess && n_docs) {
+            hipLaunchKernelGGL(k_sd_check, dim3(std::min<uint32_t>((n_docs + 255) / 256, 1024u)), dim3(256), 0, st, t->d_keys, n_docs, d_bad);
+            chk(hipGetLastError());
+        }
+        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    }
+    { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host array is the caller's: nothing may still read it)
+    (void)hipFree(d_bad);
+    if (e != hipSuccess || bad) {
+        (void)hipFree(t->d_keys);
+        delete t;
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return fail(ctx, NS_E_INVAL, "%s: a document has the reserved key 0xFFFFFFFF", fn);
+    }
+    *out = t;
+    return NS_OK;
+}
+
+extern "C" int ns_dockeys_release(ns_ctx* ctx, ns_dockeys* table) {
+    if (!ctx || !table || table->ctx != ctx) return fail(ctx, NS_E_INVAL, "ns_dockeys_release: table does not belong to this ctx");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(table->d_keys);
+    delete table;
+    return NS_OK;
+}
+
+extern "C" int ns_sorted_kernel_ms(float* out3, int reset) {
+    if (!out3) return NS_E_INVAL;
+    for (int i = 0; i < 3; i++) out3[i] = g_sd_ms[i];
+    if (reset) g_sd_ms[0] = g_sd_ms[1] = g_sd_ms[2] = 0.0f;
+    return NS_OK;
+}
+
+extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                                uint32_t k, uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
+                                ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
+    const char* fn = "ns_search_sorted";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
+    if (!queries || !hits_out || !keys_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (flags & ~(NS_FLAG_AND | NS_SORT_ASC)) return fail(ctx, NS_E_INVAL, "%s: flags 0x%x: only NS_FLAG_AND and NS_SORT_ASC are known", fn, flags);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
+    if (!seg_ids || !segs || !keys) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
+    std::vector<FcSegView> views(n_segs);
+    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<DevSdSeg> sds(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        const ns_dockeys* t = keys[i];
+        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or key table %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: key table %u does not belong to this ctx", fn, i);
+        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: key table %u keys %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
+        sds[i] = DevSdSeg{t->d_keys, s->d_norm, seg_ids[i], 0u};
+    }
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
+    const uint32_t asc = (flags & NS_SORT_ASC) ? 1u : 0u;
+    std::vector<FcRef> refs;
+    std::vector<FcItem> items;
+    std::vector<uint32_t> q_off;
+    std::vector<SdBatch> cuts;
+    std::string why;
+    if (fc_plan(queries, n_queries, terms, n_terms, and_mode, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
+    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
+    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    uint64_t cand_rows = 0;
+    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
+    const size_t n_out = (size_t)n_queries * K;
+
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    size_t off = 0;
+    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(FcRef)),
+                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_sds = place_at(off, sds.size() * sizeof(DevSdSeg)),
+                 o_qoff = place_at(off, q_off.size() * 4), o_qd = place_at(off, (size_t)n_queries * sizeof(ns_query_desc)),
+                 o_terms = place_at(off, (size_t)n_terms * sizeof(ns_term_ref)), o_hits = place_at(off, n_out * sizeof(ns_hit)),
+                 o_keys = place_at(off, n_out * 4), o_pos = place_at(off, n_out * 4), o_nhits = place_at(off, (size_t)n_queries * 4),
+                 o_found = place_at(off, (size_t)n_queries * 8), o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
+    const size_t block_bytes = off;
+    char* blk = nullptr;
+    std::vector<hipEvent_t> evs(cuts.size() * 4, nullptr);
+    std::vector<uint64_t> found_tmp;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    for (auto& ev : evs) chk(hipEventCreate(&ev));
+    if (e == hipSuccess) {
+        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
+        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(FcRef), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_sds, sds.data(), sds.size() * sizeof(DevSdSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_qd, queries, (size_t)n_queries * sizeof(ns_query_desc), hipMemcpyHostToDevice, st));
+        if (n_terms) chk(hipMemcpyAsync(blk + o_terms, terms, (size_t)n_terms * sizeof(ns_term_ref), hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
+        const FcItem* d_items = (const FcItem*)(blk + o_items);
+        const DevFcSeg* d_segs = (const DevFcSeg*)(blk + o_segs);
+        const DevSdSeg* d_sds = (const DevSdSeg*)(blk + o_sds);
+        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
+        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
+            const SdBatch& b = cuts[c];
+            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
+            chk(hipEventRecord(evs[c * 4 + 0], st));
+            if (n_it) {
+                if (and_mode)
+                    hipLaunchKernelGGL(k_sd_select<true>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, (const FcRef*)(blk + o_refs), d_segs, d_sds, K, asc, d_cand, (unsigned long long*)(blk + o_found));
+                else
+                    hipLaunchKernelGGL(k_sd_select<false>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, (const FcRef*)(blk + o_refs), d_segs, d_sds, K, asc, d_cand, (unsigned long long*)(blk + o_found));
+                chk(hipGetLastError());
+            }
+            chk(hipEventRecord(evs[c * 4 + 1], st));
+            hipLaunchKernelGGL(k_sd_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_sds,
+                               (const uint64_t*)d_cand, K, asc, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_keys), (uint32_t*)(blk + o_pos), (uint32_t*)(blk + o_nhits));
+            chk(hipGetLastError());
+            chk(hipEventRecord(evs[c * 4 + 2], st));
+            const uint64_t n_waves = (uint64_t)n_q * K;
+            hipLaunchKernelGGL(k_sd_score, dim3((uint32_t)((n_waves + 3) / 4)), dim3(256), 0, st, (const ns_query_desc*)(blk + o_qd), (const ns_term_ref*)(blk + o_terms), b.q_begin, b.q_end,
+                               d_segs, d_sds, K, (const uint32_t*)(blk + o_pos), (const uint32_t*)(blk + o_nhits), (uint32_t*)(blk + o_hits));
+            chk(hipGetLastError());
+            chk(hipEventRecord(evs[c * 4 + 3], st));
+        }
+        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(keys_out, blk + o_keys, n_out * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
+        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));
+        if (e == hipSuccess) {
+            float sum = 0.0f;
+            for (size_t c = 0; c < cuts.size(); c++)
+                for (int j = 0; j < 3; j++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { g_sd_ms[j] += ms; sum += ms; }
+                }
+            if (device_ms_out) *device_ms_out = sum;
+        }
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Segment-sharded multi-GPU: join the all-gathered per-rank rows (k_merge_ranks).  Device pointers; asynchronous on the ctx stream.
 extern "C" int ns_merge_rank_rows(ns_ctx* ctx, const void* d_hits, const void* d_nhits, const void* d_found, uint32_t n_ranks,
                                   uint32_t n_queries, uint32_t k, const uint32_t* d_seg_map, uint32_t seg_map_stride,
@@ -3402,6 +3582,15 @@ extern "C" int ns_debug_facet_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_fcnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_fcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the sorted search's paths (ns_sorted.hip k_sd_select, k_sd_join, k_sd_score): 9 values
+extern "C" int ns_debug_sorted_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsScnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_scnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_scnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 #endif

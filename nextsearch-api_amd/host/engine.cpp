@@ -50,6 +50,7 @@ size_t Engine::similar_segments_on_device() const {
 void Engine::release_device_segments() {
     release_similar();
     release_facets();
+    release_sorted();
     close_all_filters();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
@@ -2139,6 +2140,208 @@ bool Engine::search_faceted_text(const std::string& query, int k, const nsx::Fac
 std::string Engine::search_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
     std::string body;
     if (!search_faceted_text(query, k, spec, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- search sorted by date (host/sorted.hpp, csrc/ns_sorted.hip) --------------------------------------------
+void Engine::release_sorted() {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    for (SortSet& ss : sorts_) {
+        if (ctx_)
+            for (ns_dockeys* t : ss.dev)
+                if (t) (void)ns_dockeys_release(ctx_, t);
+        ss = SortSet{};
+    }
+}
+
+size_t Engine::sort_tables_on_device() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const SortSet& ss : sorts_)
+        for (const ns_dockeys* t : ss.dev) n += t != nullptr;
+    return n;
+}
+
+bool Engine::sort_keys(const nsx::SortSpec& spec, std::vector<std::vector<uint32_t>>& keys) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    keys.clear();
+    const size_t S = segments.size();
+    if (spec.kind == nsx::SortSpec::Custom) {
+        if (spec.custom_keys.size() != S) { err_ = "sort custom: " + std::to_string(spec.custom_keys.size()) + " key arrays for " + std::to_string(S) + " segments"; return false; }
+        for (size_t s = 0; s < S; s++) {
+            if (spec.custom_keys[s].size() != segments[s].N) {
+                err_ = "sort custom: the key array of segment " + std::to_string(s) + " has " + std::to_string(spec.custom_keys[s].size()) + " entries, the segment " + std::to_string(segments[s].N) + " documents";
+                return false;
+            }
+            for (const uint32_t k : spec.custom_keys[s])
+                if (k == nsx::kSortReservedKey) { err_ = "sort custom: segment " + std::to_string(s) + " holds the reserved key 0xFFFFFFFF"; return false; }
+        }
+        keys = spec.custom_keys;
+        return true;
+    }
+    if (spec.kind != nsx::SortSpec::Date) { err_ = "sort: unknown kind"; return false; }
+    keys.resize(S);
+    for (uint32_t s = 0; s < S; s++) {
+        keys[s].resize(segments[s].N);
+        for (uint32_t d = 0; d < segments[s].N; d++) {
+            const nsx::MetaFields* md = meta.get(s, d);   // nullptr: no metadata row = undated
+            keys[s][d] = md ? nsx::date_key(md->publish_time) : 0u;
+        }
+    }
+    return true;
+}
+
+// the kind's keys on the host and, for every segment with a device copy, on the device
+bool Engine::ensure_sorted(const nsx::SortSpec& spec, SortSet*& out) {
+    if ((unsigned)spec.kind > 1u) { err_ = "sort: unknown kind"; return false; }
+    SortSet& ss = sorts_[spec.kind];
+    if (ss.built && spec.kind == nsx::SortSpec::Custom && ss.keys != spec.custom_keys) {
+        for (ns_dockeys* t : ss.dev) if (t) (void)ns_dockeys_release(ctx_, t);   // another custom order takes the kind's place
+        ss = SortSet{};
+    }
+    if (!ss.built) {
+        SortSet fresh;
+        if (!sort_keys(spec, fresh.keys)) return false;
+        fresh.dev.assign(segments.size(), nullptr);
+        for (uint32_t s = 0; s < segments.size(); s++) {
+            if (!dev_segs_[s]) continue;
+            const int rc = ns_dockeys_upload(ctx_, segments[s].N, fresh.keys[s].data(), &fresh.dev[s]);
+            if (rc != NS_OK) {
+                err_ = std::string("ns_dockeys_upload: ") + ns_last_error(ctx_);
+                for (ns_dockeys* t : fresh.dev) if (t) (void)ns_dockeys_release(ctx_, t);
+                return false;
+            }
+        }
+        fresh.built = true;
+        ss = std::move(fresh);
+    }
+    out = &ss;
+    return true;
+}
+
+bool Engine::search_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                                      ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint8_t* usable, float* device_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = "search_sorted_batch_flat: no device context: the sorted search runs on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = "search_sorted_batch_flat: null argument"; return false; }
+    if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = "search_sorted_batch_flat: flags are NS_FLAG_OR or NS_FLAG_AND; the direction is the spec's"; return false; }
+    OpenFilter* f = nullptr;
+    if (filter_handle) {
+        f = filter_of(filter_handle);
+        if (!f) { err_ = "search_sorted_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    }
+    SortSet* ss = nullptr;
+    if (!ensure_sorted(spec, ss)) return false;
+    if (Q == 0) return true;
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const uint32_t S = (uint32_t)segments.size();
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
+    const uint32_t call_flags = flags | (spec.ascending ? NS_SORT_ASC : NS_SORT_DESC);
+    nsx::RowSource rs;
+    if (f) {   // search_filtered_batch_flat's row source
+        rs.rows = f->rows.data();
+        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
+        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+        if (!rs.rows) rs.rows = &no_rows;
+    }
+    // the segments the refs can name, in manifest order: the index's own, or the filter's copies, each with its position's keys
+    std::vector<uint32_t> ids;
+    std::vector<ns_seg*> segs;
+    std::vector<ns_dockeys*> tabs;
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
+        if (!h || !ss->dev[s]) continue;
+        ids.push_back(rs.id_base + s);
+        segs.push_back(h);
+        tabs.push_back(ss->dev[s]);
+    }
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    auto run = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
+        if (ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            std::fill(nhits + a, nhits + b, 0u);
+            std::fill(hits + a * K, hits + b * K, pad);
+            std::fill(keys + a * K, keys + b * K, 0u);
+            return true;
+        }
+        float ms = 0.0f;
+        const int rc = ns_search_sorted(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, (uint32_t)K, call_flags, ids.data(), segs.data(), tabs.data(),
+                                        (uint32_t)ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_search_sorted: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        for (size_t q = a; q < b; q++)
+            for (uint32_t i = 0; i < nhits[q]; i++) hits[q * K + i].seg_id -= rs.id_base;   // manifest positions
+        return true;
+    };
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
+        std::vector<std::string> qs(Q);
+        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
+        std::vector<nsx::WeightedTerms> expanded;
+        if (!expand_queries(qs, expanded)) return false;
+        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
+        std::vector<ns_term_ref> refs;
+        std::vector<uint8_t> us(Q, 0);
+        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
+        std::memcpy(usable, us.data(), Q);
+        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
+            if (!run(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
+        return true;
+    }
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
+        if (!run(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
+    }
+    return true;
+}
+
+bool Engine::search_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_sorted: no device context: this engine has no CPU scoring path"; return false; }
+    uint32_t handle = 0;
+    if (f) {   // search_filtered's body; its filter is then the most recently used of the cache
+        if (!search_filtered_text(query, k, *f, body)) return false;
+        handle = filter_lru_.front().handle;
+    } else {
+        SearchResult r;
+        if (!search_hits_locked(query, k, NS_FLAG_OR, r)) { body = err_; return false; }
+        body = to_json_impl(r);
+    }
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits(K);
+    std::vector<uint32_t> keys(K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!search_sorted_batch_flat(spec, handle, &qv, 1, (int)K, NS_FLAG_OR, hits.data(), keys.data(), &nh, &fd, &us)) { body = err_; return false; }
+    std::vector<SearchHit> sorted;
+    if (us)
+        for (uint32_t i = 0; i < nh; i++) sorted.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    // the body's "results" member replaced ("query" is escaped: no line of it starts like a member), "sort" behind "segments"
+    const size_t a = body.find("\n  \"results\": "), b = body.rfind("\n  \"segments\": ");
+    if (a == std::string::npos || b == std::string::npos || b < a || body.size() < 2) { body = err_ = "search_sorted: the search body has no results member"; return false; }
+    std::string o = body.substr(0, a + 1);
+    append_results_json(o, sorted);
+    o += body.substr(b + 1, body.size() - (b + 1) - 2);   // "  \"segments\": N", without the closing "\n}"
+    o += ",\n  \"sort\": ";
+    json_escape(o, nsx::sort_name(spec));
+    o += "\n}";
+    body = std::move(o);
+    return true;
+}
+
+std::string Engine::search_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    if (!search_sorted_text(query, k, spec, f, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

@@ -36,6 +36,7 @@
 #include "correct.hpp"
 #include "filter.hpp"
 #include "facet.hpp"
+#include "sorted.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -306,6 +307,29 @@ public:
     void release_facets();
     size_t facet_tables_on_device() const;   // bucket tables with a device copy right now
 
+    // Search sorted by date (host/sorted.hpp, csrc/ns_sorted.hip).  sort_keys: the spec's key per document,
+    // per segment in manifest order: date_key() of publish_time (YYYYMMDD, missing parts 0, undated 0), or the caller's
+    // arrays; host only (works on a host-only engine).  false: a Custom spec that does not fit the index or holds the
+    // reserved value 0xFFFFFFFF.
+    bool sort_keys(const nsx::SortSpec& spec, std::vector<std::vector<uint32_t>>& keys);
+    // search_sorted_batch_flat: per query the first K = clamp(k, 1, 100) matched documents in the order (key, manifest
+    // position ascending, docId ascending) — newest first, or oldest first with spec.ascending; undated documents last in both
+    // directions — with the BM25 score the search gives them.  hits / keys: Q x K (pad: {-inf, ~0, ~0}, key 0), nhits[q] =
+    // min(K, found[q]).  flags: NS_FLAG_OR or NS_FLAG_AND.  The query preparation is facet_batch_flat's (the dictionary's
+    // rows, or an open filter's under a handle, 0 = none; semantic expansion when embeddings are loaded), so found and usable
+    // equal the search's, query for query; a query that is not usable has nhits = 0.  Hits carry manifest positions.  Runs on
+    // the primary context.  The device key tables are built by the first call that needs them (never by reload()), one per
+    // (kind, segment), serve the filtered copies unchanged, and are freed by reload(), release_sorted() and the destructor.
+    bool search_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                                  ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint8_t* usable, float* device_ms = nullptr);
+    // JSON text: search's body (search_filtered's when a filter is given) with "results" in date order, every entry decorated
+    // as search's are, plus "sort": "newest" | "oldest" | "custom"; dump(2) layout.  The search cache is not used.  Any
+    // failure: {"error": ...} (search_sorted_text: false, body = the message).
+    std::string search_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
+    void release_sorted();
+    size_t sort_tables_on_device() const;   // key tables with a device copy right now
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -390,6 +414,14 @@ private:
     };
     FacetSet facets_[3];
     bool ensure_facets(const nsx::FacetSpec& spec, FacetSet*& out);
+    // sort keys: per kind the host keys and their device copies (nullptr: the segment has none)
+    struct SortSet {
+        bool built = false;
+        std::vector<std::vector<uint32_t>> keys;
+        std::vector<ns_dockeys*> dev;
+    };
+    SortSet sorts_[2];
+    bool ensure_sorted(const nsx::SortSpec& spec, SortSet*& out);
     mutable std::string err_;
 };
 

@@ -975,3 +975,90 @@ extern "C" int nsh_engine_search_faceted_json(nsh_engine* e, const char* query, 
 
 extern "C" void nsh_engine_release_facets(nsh_engine* e) { try { if (e) e->eng.release_facets(); } NSH_CATCH_VOID(e, "nsh_engine_release_facets") }
 extern "C" uint64_t nsh_engine_facet_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.facet_tables_on_device() : 0; }
+
+// ---- search sorted by date (host/sorted.hpp) ----
+static bool nsh_sort_spec_of(nsh_engine* e, const nsh_sort_spec* in, nsx::SortSpec& out, std::string& why) {
+    if (!in) { why = "sort: spec is NULL"; return false; }
+    if (in->kind > 1u) { why = "sort: unknown kind " + std::to_string(in->kind); return false; }
+    out.kind = (nsx::SortSpec::Kind)in->kind;
+    out.ascending = in->ascending != 0;
+    if (out.kind != nsx::SortSpec::Custom) return true;
+    if (in->n_custom && !in->custom_keys) { why = "sort custom: null array"; return false; }
+    // whole arrays as far as the keys reach; keys left over become one more: the engine refuses either with a message
+    uint64_t at = 0;
+    for (const auto& sd : e->eng.segments) {
+        if (at + sd.N > in->n_custom) break;
+        out.custom_keys.emplace_back(in->custom_keys + at, in->custom_keys + at + sd.N);
+        at += sd.N;
+    }
+    if (out.custom_keys.size() == e->eng.segments.size() && at != in->n_custom) out.custom_keys.emplace_back(in->custom_keys + at, in->custom_keys + in->n_custom);
+    return true;
+}
+
+extern "C" int64_t nsh_engine_sort_keys(nsh_engine* e, const nsh_sort_spec* spec, uint32_t* keys_out, uint64_t cap) { try {
+    if (!e) return -1;
+    nsx::SortSpec sp;
+    std::string why;
+    if (!nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    std::vector<std::vector<uint32_t>> keys;
+    if (!e->eng.sort_keys(sp, keys)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    uint64_t at = 0;
+    for (const auto& t : keys) {
+        for (size_t i = 0; i < t.size(); i++)
+            if (keys_out && at + i < cap) keys_out[at + i] = t[i];
+        at += t.size();
+    }
+    return (int64_t)at;
+} NSH_CATCH(e, "nsh_engine_sort_keys", -1)
+}
+
+extern "C" int nsh_engine_search_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                              int k, uint32_t flags, void* hits, uint32_t* keys_out, uint32_t* nhits, uint64_t* found, uint8_t* has_found,
+                                              float* device_ms_out) { try {
+    if (!e) return -1;
+    nsx::SortSpec sp;
+    std::string why;
+    if (!nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !keys_out || !nhits)) { nsh_set_err(e, "nsh_engine_search_sorted_batch: null argument"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    if (!e->eng.search_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, (ns_hit*)hits, keys_out, nhits, found, has_found, device_ms_out)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_search_sorted_batch", -1)
+}
+
+extern "C" int nsh_engine_search_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                             const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::SortSpec sp;
+    bool ok = nsh_sort_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_sorted_json", -1)
+}
+
+extern "C" void nsh_engine_release_sorted(nsh_engine* e) { try { if (e) e->eng.release_sorted(); } NSH_CATCH_VOID(e, "nsh_engine_release_sorted") }
+extern "C" uint64_t nsh_engine_sort_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.sort_tables_on_device() : 0; }

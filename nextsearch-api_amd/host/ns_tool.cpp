@@ -18,6 +18,9 @@
 //   ns_tool search-faceted <index_dir> <year|month> <from> <to> <k> <query text ...>   (needs an MI355X)
 //        Engine::search_faceted: search's JSON body plus "facets": the matched documents per year (month) of publish_time
 //        (facet.hpp).  from / to as search-filtered's; "-" "-" searches the whole index, without a "filter" member.
+//   ns_tool search-sorted <index_dir> <newest|oldest> <from> <to> <k> <query text ...>   (needs an MI355X)
+//        Engine::search_sorted: search's JSON body with "results" in date order (publish_time; undated documents last in both
+//        directions) plus "sort" (sorted.hpp).  from / to as search-filtered's; "-" "-" searches the whole index.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -92,6 +95,25 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
         if (!eng.search_faceted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-faceted failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 8 && std::strcmp(argv[1], "search-sorted") == 0) {
+        nsx::SortSpec spec;
+        if (std::strcmp(argv[3], "newest") == 0) spec.ascending = false;
+        else if (std::strcmp(argv[3], "oldest") == 0) spec.ascending = true;
+        else { std::fprintf(stderr, "search-sorted: the order is newest or oldest, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) f.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) f.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        std::string q, body;
+        for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_sorted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-sorted failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

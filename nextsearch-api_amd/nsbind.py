@@ -19,6 +19,7 @@ HOST_LIB_PATH = os.path.join(HERE, "libnextsearch_host.so")
 NS_OK = 0
 NS_FLAG_OR = 0
 NS_FLAG_AND = 1
+NS_SORT_DESC, NS_SORT_ASC = 0, 0x1000   # ns_search_sorted
 NS_INFO_IMPACTS = 0x100
 NS_INFO_PACKED = 0x200
 NS_INFO_PRUNED = 0x400
@@ -57,6 +58,7 @@ assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 # every symbol include/nextsearch_hip.h declares
 HIP_SYMBOLS = [
     "ns_facet_upload", "ns_facet_release", "ns_facet_count", "ns_facet_tile_docs",
+    "ns_dockeys_upload", "ns_dockeys_release", "ns_search_sorted", "ns_sorted_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -70,6 +72,7 @@ HIP_SYMBOLS = [
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
 HOST_SYMBOLS = [
+    "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
     "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
     "nsh_engine_search_filtered_batch", "nsh_engine_search_filtered_json",
@@ -136,6 +139,13 @@ class NshFacetSpec(C.Structure):   # include/nextsearch_host.h nsh_facet_spec
 
 
 FACET_KINDS = {"year": 0, "month": 1, "custom": 2}
+
+
+class NshSortSpec(C.Structure):   # include/nextsearch_host.h nsh_sort_spec
+    _fields_ = [("kind", C.c_uint32), ("ascending", C.c_uint32), ("custom_keys", C.c_void_p), ("n_custom", C.c_uint64)]
+
+
+SORT_ORDERS = {"newest": (0, 0), "oldest": (0, 1)}   # name -> (kind, ascending); custom keys: kind 1
 
 _hip = None
 _host = None
@@ -222,6 +232,10 @@ def hip_lib():
         L.ns_facet_count.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
         L.ns_facet_tile_docs.argtypes = []
         L.ns_facet_tile_docs.restype = u32
+        L.ns_dockeys_upload.argtypes = [vp, u32, vp, C.POINTER(vp)]
+        L.ns_dockeys_release.argtypes = [vp, vp]
+        L.ns_search_sorted.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_sorted_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -231,7 +245,7 @@ def hip_lib():
 
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
-                  "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8}
+                  "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9}
 
 
 def debug_counters(reset=False):
@@ -382,6 +396,14 @@ def host_lib():
         L.nsh_engine_release_facets.restype = None
         L.nsh_engine_facet_tables_on_device.argtypes = [vp]
         L.nsh_engine_facet_tables_on_device.restype = u64
+        L.nsh_engine_sort_keys.argtypes = [vp, C.POINTER(NshSortSpec), vp, u64]
+        L.nsh_engine_sort_keys.restype = C.c_int64
+        L.nsh_engine_search_sorted_batch.argtypes = [vp, C.POINTER(NshSortSpec), u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_release_sorted.argtypes = [vp]
+        L.nsh_engine_release_sorted.restype = None
+        L.nsh_engine_sort_tables_on_device.argtypes = [vp]
+        L.nsh_engine_sort_tables_on_device.restype = u64
         _host = L
     return _host
 
@@ -825,6 +847,71 @@ class Engine:
 
     def facet_tables_on_device(self):
         return int(self._L.nsh_engine_facet_tables_on_device(self.h))
+
+    # ---- search sorted by date ----
+    @staticmethod
+    def _sort_spec(order, custom=None):
+        """order: "newest" | "oldest" (publish_time), or with custom (one uint32 key array per segment) "desc" | "asc" """
+        sp = NshSortSpec()
+        keep = None
+        if custom is not None:
+            sp.kind, sp.ascending = 1, int(order in ("asc", "oldest"))
+            keep = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32) for c in custom]) if len(custom) else np.zeros(0, np.uint32))
+            sp.custom_keys, sp.n_custom = (keep.ctypes.data if len(keep) else None), len(keep)
+        else:
+            sp.kind, sp.ascending = SORT_ORDERS[order]
+        return sp, keep
+
+    def sort_keys(self, order="newest", custom=None):
+        """Engine::sort_keys (host only): [one uint32 key array per segment]"""
+        sp, keep = self._sort_spec(order, custom)
+        sizes = [self.segment_info(s)["n_docs"] for s in range(self.num_segments)]
+        flat = np.zeros(max(sum(sizes), 1), dtype=np.uint32)
+        n = self._L.nsh_engine_sort_keys(self.h, C.byref(sp), flat.ctypes.data, len(flat))
+        if n < 0:
+            raise RuntimeError(f"sort_keys failed: {self.error()}")
+        out, at = [], 0
+        for m in sizes:
+            out.append(flat[at:at + m].copy())
+            at += m
+        return out
+
+    def search_sorted_batch(self, queries, k, order="newest", flags=NS_FLAG_OR, handle=0, custom=None, timing=False):
+        """Engine::search_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, has_found); handle: an open filter's (0:
+        none).  timing=True adds the kernels' device ms."""
+        sp, keep = self._sort_spec(order, custom)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k), int(flags), hits.ctypes.data,
+                                                    keys.ctypes.data, nhits.ctypes.data, found.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_sorted_batch failed: {self.error()}")
+        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_sorted_json(self, query, k, order="newest", date_filter=None, custom=None, check=True):
+        """Engine::search_sorted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure raises
+        (check=False: returns the {"error": ...} body)."""
+        sp, keep = self._sort_spec(order, custom)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_sorted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
+                                                   int(bool(ku)), C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_sorted failed: {self.error()}")
+        return body
+
+    def release_sorted(self):
+        self._L.nsh_engine_release_sorted(self.h)
+
+    def sort_tables_on_device(self):
+        return int(self._L.nsh_engine_sort_tables_on_device(self.h))
 
     def prepare(self, queries, k, flags=NS_FLAG_OR):
         b = C.c_void_p()
@@ -1563,6 +1650,43 @@ def facet_count(ctx, qd, refs, flags, seg_ids, segs, tables, n_buckets):
     rc = hip_lib().ns_facet_count(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None, len(refs), int(flags),
                                   ids.ctypes.data if len(ids) else None, sa, ta, len(ids), counts.ctypes.data, found.ctypes.data, C.byref(ms))
     return rc, counts[:Q], found[:Q], float(ms.value)
+
+
+def dockeys_upload(ctx, keys):
+    """ns_dockeys_upload (raw): (rc, handle); keys: one uint32 sort key per document, 0 = none, 0xFFFFFFFF refused"""
+    a = np.ascontiguousarray(keys, dtype=np.uint32)
+    h = C.c_void_p()
+    rc = hip_lib().ns_dockeys_upload(ctx, len(a), a.ctypes.data if len(a) else None, C.byref(h))
+    return rc, h
+
+
+def dockeys_release(ctx, table):
+    return hip_lib().ns_dockeys_release(ctx, table)
+
+
+def search_sorted_raw(ctx, qd, refs, k, flags, seg_ids, segs, tables):
+    """ns_search_sorted (raw): (rc, hits Q x K, keys Q x K, nhits, found, device ms); K = clamp(k, 1, 100); segs / tables:
+    lists of handles.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    keys = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_sorted(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None, len(refs), int(k), int(flags),
+                                    ids.ctypes.data if len(ids) else None, sa, ta, len(ids), hits.ctypes.data, keys.ctypes.data,
+                                    nhits.ctypes.data, found.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], keys[:Q], nhits[:Q], found[:Q], float(ms.value)
+
+
+def sorted_kernel_ms(reset=True):
+    """(k_sd_select, k_sd_join, k_sd_score) HIP-event ms summed over this thread's ns_search_sorted calls since the last reset"""
+    out = (C.c_float * 3)()
+    hip_lib().ns_sorted_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
 
 
 def search_batch_raw(ctx, qd, refs, k, flags=NS_FLAG_OR):
