@@ -579,6 +579,52 @@ int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queri
  * tools/sorted_bench.py. */
 int ns_sorted_kernel_ms(float* out3, int reset);
 
+/* ---- boolean queries ----------------------------------------------------------- */
+/* role of a term ref in ns_search_boolean: one byte per ref, parallel to the ref array */
+#define NS_ROLE_SHOULD 0u   /* optional: adds to the score; matches when the group has no MUST ref */
+#define NS_ROLE_MUST   1u   /* required */
+#define NS_ROLE_NOT    2u   /* excluded: never scored */
+/* The K = clamp(k, 1, NS_MAX_K) best documents of each query's matched set by BM25 score.  roles[r] is the role of terms[r]
+ * (roles == NULL: every ref is NS_ROLE_SHOULD, which is the NS_FLAG_OR search).
+ *   MATCHED SET  defined per (query, segment) group, over the refs the query has in that segment: M = its MUST refs, S = its
+ *                SHOULD refs with count > 0, X = its NOT refs with count > 0.  A MUST ref with count == 0 kills the group (no
+ *                document of that segment holds the term).  M not empty: the documents in every list of M and in no list of
+ *                X.  M empty, S not: the documents in at least one list of S and in no list of X.  Otherwise nothing: a group
+ *                of NOT refs alone matches nothing.  Postings with docId >= n_docs are ignored; a list named twice matches
+ *                once; term_count == 0 gives nhits = 0, found = 0; any term_count works.  found_out[q] (may be NULL) is the
+ *                size of the set summed over the segments.
+ *   SCORE        the scoring path's, bit for bit: the accumulator starts at +0.0f; over the group's refs whose role is not
+ *                NS_ROLE_NOT, IN QUERY ORDER, duplicates included, SHOULD refs next to MUST refs, it adds
+ *                qweight * ((idf * (tf * 2.2f)) / (tf + norm[doc])), every operation rounded to fp32, with the segment's
+ *                per-document norm and the correctly rounded division.  A ref whose list does not hold the document adds
+ *                nothing.
+ *   ORDER        the search's canonical one: score descending as floats compare, then position of the segment in the call's
+ *                list ascending (the position in seg_ids orders, not the id's value), then docId ascending.
+ *   HITS         hits_out[q * K + r] = {score, seg_ids[i] of the segment, docId}; nhits_out[q] = min(K, found); the tail past
+ *                it is {-inf, 0xFFFFFFFF, 0xFFFFFFFF}.
+ *   ODD NUMBERS  a MUST or SHOULD ref whose idf or qweight is NaN or infinite is REFUSED (ns_batch_prepare takes such refs and
+ *                leaves the order to the kernels; here the order is a promise).  Negative values and -0.0f are taken: the
+ *                accumulator starts at +0.0f and x + y is -0.0f only for x = y = -0.0f, so no score is a negative zero.  The
+ *                kernels order by the fp32 bits mapped monotonically (negative: ~bits, else bits | 0x80000000), which is the
+ *                order of the floats for every score that is not a NaN; a NaN that finite refs still produce (an overflow to
+ *                +inf and one to -inf in one sum, a norm of -tf) sorts by that map: above +inf with its sign bit clear,
+ *                below -inf with it set.
+ * seg_ids[i] is the id the refs use for segs[i], i < n_segs; a filtered copy (ns_segment_filter) is an ordinary segment here.
+ * Lists must be docId-ascending; one that is not may lose hits but nothing is read or written out of bounds.  Synchronous;
+ * device_ms_out (may be NULL) = HIP-event time of the kernels.  A large batch is cut into sub-batches so that the candidate
+ * rows (work items x K x 8 B) never exceed 64 MiB of device memory, as ns_search_sorted's.
+ * NS_E_INVAL, with a message, nothing launched and the output arrays untouched: a null argument, no segment listed, a seg_id
+ * listed twice, a ref that names a seg_id not listed, a list outside its segment's payload or at a byte offset that is not a
+ * multiple of 8, refs running past n_terms, a role above 2, a non-finite idf or qweight as above, a segment of another ctx,
+ * a single query whose work items alone exceed the candidate buffer.  n_queries == 0 is NS_OK. */
+int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                      const uint8_t* roles /* n_terms; NULL = all SHOULD */, uint32_t n_terms, uint32_t k, const uint32_t* seg_ids,
+                      ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out /* Q x K */, uint32_t* nhits_out,
+                      uint64_t* found_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+/* HIP-event time of k_bq_select and k_bq_join, summed over the calling thread's ns_search_boolean calls (and their sub-batches)
+ * since the last reset: out2[0..1], milliseconds; reset != 0 zeroes the sums after the read.  For tools/boolean_bench.py. */
+int ns_boolean_kernel_ms(float* out2, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

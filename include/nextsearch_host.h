@@ -402,6 +402,23 @@ int nsh_engine_search_sorted_json(nsh_engine* e, const char* query, int k, const
 void nsh_engine_release_sorted(nsh_engine* e);
 uint64_t nsh_engine_sort_tables_on_device(nsh_engine* e);
 
+/* ---- boolean queries (host/boolean.hpp) ----
+ * nsx::parse_boolean (host only, no engine): the query is split on whitespace; a piece that begins with '+' (MUST) or '-' (NOT)
+ * gives that role to every token the search's tokenizer takes from the rest of the piece, all other pieces are SHOULD; stop
+ * words and one-byte tokens are dropped, duplicates stay.  buf receives the terms joined by single spaces (NUL-terminated,
+ * truncated to cap), roles (capacity roles_cap, may be NULL) one NS_ROLE_* byte per term.  Returns the number of terms. */
+uint32_t nsh_parse_boolean(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t roles_cap);
+/* Engine::search_boolean_batch_flat: per query the K = clamp(k, 1, 100) best documents that hold every `+word`, no `-word` and,
+ * without a `+word`, at least one other word, in the search's order with the search's scores; hits (n_queries x K nsh/ns_hit
+ * {score, segment position, docId}), nhits, found, has_found as nsh_engine_search_batch's (found 0 where has_found is 0).
+ * filter_handle: an open filter's, or 0.  device_ms_out (may be NULL): the kernels' time. */
+int nsh_engine_search_boolean_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k, void* hits,
+                                    uint32_t* nhits, uint64_t* found, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_boolean: *json_out (free with nsh_free) = search's body (search_filtered's with use_filter != 0) over the
+ * boolean result plus "boolean": {"must", "must_not", "should"}.  On failure -1 and {"error": ...}. */
+int nsh_engine_search_boolean_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                   int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

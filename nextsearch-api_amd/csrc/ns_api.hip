@@ -29,6 +29,7 @@
 #include "ns_facet.hip"
 #include "ns_similar.hip"
 #include "ns_sorted.hip"   // after ns_facet.hip (fc_cut, fc_mark, fc_lower_bound) and ns_similar.hip (ml_sort_up, ml_merge_down, ml_join)
+#include "ns_boolean.hip"  // after ns_sorted.hip (SdSet, sd_insert) and ns_facet.hip (fc_cut, fc_mark)
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
@@ -2914,6 +2915,131 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
 }
 
 // ------------------------------------------------------------------------------------------------
+// Boolean queries (csrc/ns_boolean.hip, csrc/ns_boolean_plan.hpp)
+static thread_local float g_bq_ms[2] = {0.0f, 0.0f};   // k_bq_select, k_bq_join: summed over the thread's ns_search_boolean calls (ns_boolean_kernel_ms)
+
+// documents per window of k_bq_select: never more than the tile
+static uint32_t bq_win_docs(uint32_t tile_docs) {
+    uint32_t win = kBqWinDocs;
+#if defined(NS_VARIANTS) || defined(NS_COUNT)
+    // test knob (variants and counting builds only), next to NS_FACET_TILE_DOCS: small windows, so that a few hundred documents span several
+    if (const char* t = std::getenv("NS_BOOL_WIN_DOCS")) { const long v = std::atol(t); if (v > 0 && v <= (long)kBqMaxWinDocs && bq_win_ok((uint32_t)v)) win = (uint32_t)v; }
+#endif
+    return std::min(win, tile_docs);
+}
+
+extern "C" int ns_boolean_kernel_ms(float* out2, int reset) {
+    if (!out2) return NS_E_INVAL;
+    for (int i = 0; i < 2; i++) out2[i] = g_bq_ms[i];
+    if (reset) g_bq_ms[0] = g_bq_ms[1] = 0.0f;
+    return NS_OK;
+}
+
+extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                 uint32_t n_terms, uint32_t k, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                                 uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
+    const char* fn = "ns_search_boolean";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (n_queries == 0) { if (device_ms_out) *device_ms_out = 0.0f; return NS_OK; }
+    if (!queries || !hits_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
+    if (!seg_ids || !segs) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
+    std::vector<FcSegView> views(n_segs);
+    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<DevBqSeg> bqs(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        if (!s) return fail(ctx, NS_E_INVAL, "%s: segment %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
+        bqs[i] = DevBqSeg{s->d_norm, seg_ids[i], 0u};
+    }
+    std::vector<BqRef> refs;
+    std::vector<FcItem> items;
+    std::vector<uint32_t> q_off;
+    std::vector<SdBatch> cuts;
+    std::string why;
+    const uint32_t tile = ns_facet_tile_docs(), win = bq_win_docs(tile);
+    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, tile, refs, items, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
+    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
+    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (device_ms_out) *device_ms_out = 0.0f;
+    uint64_t cand_rows = 0;
+    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
+    const size_t n_out = (size_t)n_queries * K;
+    const size_t lds = bq_lds_bytes(win);
+
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    size_t off = 0;
+    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
+                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_bqs = place_at(off, bqs.size() * sizeof(DevBqSeg)),
+                 o_qoff = place_at(off, q_off.size() * 4), o_hits = place_at(off, n_out * sizeof(ns_hit)),
+                 o_nhits = place_at(off, (size_t)n_queries * 4), o_found = place_at(off, (size_t)n_queries * 8),
+                 o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
+    const size_t block_bytes = off;
+    char* blk = nullptr;
+    std::vector<hipEvent_t> evs(cuts.size() * 3, nullptr);
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+#if defined(NS_VARIANTS) || defined(NS_COUNT)
+    if (lds > (48u << 10)) chk(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bq_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+#endif
+    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    for (auto& ev : evs) chk(hipEventCreate(&ev));
+    if (e == hipSuccess) {
+        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
+        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_bqs, bqs.data(), bqs.size() * sizeof(DevBqSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
+        const FcItem* d_items = (const FcItem*)(blk + o_items);
+        const DevBqSeg* d_bqs = (const DevBqSeg*)(blk + o_bqs);
+        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
+        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
+            const SdBatch& b = cuts[c];
+            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
+            chk(hipEventRecord(evs[c * 3 + 0], st));
+            if (n_it) {
+                hipLaunchKernelGGL(k_bq_select, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
+                                   d_cand, (unsigned long long*)(blk + o_found));
+                chk(hipGetLastError());
+            }
+            chk(hipEventRecord(evs[c * 3 + 1], st));
+            hipLaunchKernelGGL(k_bq_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_bqs,
+                               (const uint64_t*)d_cand, K, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_nhits));
+            chk(hipGetLastError());
+            chk(hipEventRecord(evs[c * 3 + 2], st));
+        }
+        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
+        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
+        chk(hipStreamSynchronize(st));
+        if (e == hipSuccess) {
+            float sum = 0.0f;
+            for (size_t c = 0; c < cuts.size(); c++)
+                for (int j = 0; j < 2; j++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, evs[c * 3 + j], evs[c * 3 + j + 1]) == hipSuccess) { g_bq_ms[j] += ms; sum += ms; }
+                }
+            if (device_ms_out) *device_ms_out = sum;
+        }
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Segment-sharded multi-GPU: join the all-gathered per-rank rows (k_merge_ranks).  Device pointers; asynchronous on the ctx stream.
 extern "C" int ns_merge_rank_rows(ns_ctx* ctx, const void* d_hits, const void* d_nhits, const void* d_found, uint32_t n_ranks,
                                   uint32_t n_queries, uint32_t k, const uint32_t* d_seg_map, uint32_t seg_map_stride,
@@ -3591,6 +3717,15 @@ extern "C" int ns_debug_sorted_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_scnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_scnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the boolean search's paths (ns_boolean.hip k_bq_select, k_bq_join): 8 values
+extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsBcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 #endif

@@ -1,0 +1,273 @@
+// SPDX-License-Identifier: MIT
+// Boolean queries: every term ref has a role (SHOULD, MUST, NOT); per query the K best documents of the
+// matched set by BM25 score, in the search's canonical order (score descending, position of the segment in the call's list
+// ascending, docId ascending).  The work items are bq_plan's (ns_boolean_plan.hpp): one (query, segment) group over one
+// tile of the facet tile size; the sub-batches are ns_sorted_plan.hpp's.  The scoring launch (k_uscore) is not involved.
+//   k_bq_select   one workgroup of 256 threads per item.  The tile is walked in windows of `win` documents (kBqWinDocs in
+//                 the product); per window, in LDS: an fp32 accumulator per document, the matched bitmap, a scratch bitmap
+//                 and the excluded bitmap.
+//                   cut     every list to the window (fc_cut), once per pass that reads it
+//                   mark    MUST lists: the first marks the matched bitmap, every further one the scratch bitmap, which is
+//                           AND-ed in and cleared (as k_sd_select<true>); a MUST list without a posting in the window ends
+//                           the window.  No MUST ref: SHOULD lists mark the matched bitmap.  NOT lists mark the excluded
+//                           bitmap; matched &= ~excluded.  A window without a matched bit ends here (workgroup-uniform).
+//                   score   the MUST and SHOULD refs in query order, one at a time, a barrier in between: every posting of
+//                           the window whose document is matched does a plain LDS read-add-write
+//                               acc[doc] = acc[doc] + qweight * ((idf * (tf * 2.2f)) / (tf + norm[doc]))   each op rounds to fp32
+//                           docIds are unique within a list, so no two threads meet on a document; term by term is the
+//                           scoring path's fp32 order; a list named twice adds twice.
+//                   sweep   a wave takes 64 bitmap words at a time, one per lane; every lane pops its lowest set bit and offers
+//                               (ord(score) << 32) | ~(docId - doc_lo)        distinct per document of the tile, never 0
+//                           to the wave's kept set (§5q's SdSet / sd_insert), which lives across the windows of the item.
+//                 The four waves' sets meet in LDS, wave 0 joins them and writes the item's row of K candidates (0 = none).
+//                 The item's matched count goes into found[query] with one integer atomic.
+//   k_bq_join     one wave per query over the rows of its items (contiguous, in plan order: segment position, then tile):
+//                 k_sd_join's scheme, with the score taken back out of the key.  Writes the final row, nhits and the pad.
+// ord is the order-preserving map of fp32 bits: negative -> ~bits, else bits | 0x80000000.  The accumulator starts at +0.0f
+// and x + y is -0.0f only for x = y = -0.0f, so no score is a negative zero and ord orders as floats compare.
+// Every docId read from a list is tested against the window before it indexes LDS; a list that is not ascending may lose
+// hits but reads and writes nothing out of bounds.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "ns_boolean_plan.hpp"
+
+namespace ns {
+
+struct DevBqSeg {
+    const float* norm;   // per document (ns_seg::d_norm)
+    uint32_t seg_id;     // the id the refs use for this segment
+    uint32_t pad;
+};
+
+#ifdef NS_COUNT
+// Counting build only: events of the two kernels since the last reset (ns_debug_boolean_counters).  0 items, 1 windows,
+// 2 windows left early for an empty matched set, 3 MUST intersections (a further MUST list AND-ed in), 4 windows in which an
+// exclusion cleared a bit, 5 chunks skipped on the threshold ballot, 6 chunks that inserted, 7 rows joined.
+constexpr int kNsBcnt = 8;
+__device__ unsigned long long g_ns_bcnt[kNsBcnt];
+#define NS_BCNT(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_ns_bcnt[(i)], (unsigned long long)(v)); } while (0)
+#define NS_BCNT_WAVE(i, v) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&g_ns_bcnt[(i)], (unsigned long long)(v)); } while (0)
+#else
+#define NS_BCNT(i, v)
+#define NS_BCNT_WAVE(i, v)
+#endif
+
+__device__ __forceinline__ uint32_t bq_ord(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ uint32_t bq_unord(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
+
+// sd_insert, counting into this file's counters (the sorted search's stay its own)
+__device__ __forceinline__ void bq_insert(SdSet& s, uint64_t key, uint32_t K, uint32_t lane) {
+#ifdef NS_COUNT
+    const uint64_t thr = K <= 64u ? ml_shfl(s.hi, K - 1u) : ml_shfl(s.lo, K - 65u);
+    if (__ballot(key > thr) == 0ull) { NS_BCNT_WAVE(5, 1); return; }   // (wave-uniform; sd_insert would return here too)
+    NS_BCNT_WAVE(6, 1);
+    const uint64_t up = ml_sort_up(key, lane);
+    const uint64_t big = s.hi < up ? up : s.hi, small = s.hi < up ? s.hi : up;
+    s.hi = ml_merge_down(big, lane);
+    if (K > 64u) {
+        const uint64_t rest = ml_merge_down(small, lane);
+        s.lo = ml_join(s.lo, ml_shfl(rest, 63u - lane), lane);
+    }
+#else
+    sd_insert(s, key, K, lane);
+#endif
+}
+
+// Dynamic LDS, and no static LDS in front of it, so that the 8-byte rows stay aligned: 4 KiB row exchange, then win x 4 B
+// accumulators, then three bitmaps of win / 8 B, then the item's matched count.
+__host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (size_t)win * 4u + 3u * (size_t)(win / 8u) + 16u; }
+
+__global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
+                                                   const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
+                                                   uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    uint64_t (*s_rows)[128] = reinterpret_cast<uint64_t (*)[128]>(s_raw);
+    float* s_acc = reinterpret_cast<float*>(s_raw + 4096u);
+    uint32_t* s_bm = reinterpret_cast<uint32_t*>(s_raw + 4096u + (size_t)win * 4u);
+    uint32_t* s_tmp = s_bm + win / 32u;
+    uint32_t* s_ex = s_tmp + win / 32u;
+    uint32_t& s_cnt = s_ex[win / 32u];
+    const FcItem it = items[blockIdx.x];
+    const DevFcSeg sg = segs[it.seg];
+    const float* __restrict__ norm = bqs[it.seg].norm;
+    const BqRef* __restrict__ rf = refs + it.ref_begin;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, v = tid >> 6;
+    NS_BCNT(0, 1);
+    if (tid == 0) s_cnt = 0u;
+    uint32_t n_must = 0, n_not = 0;   // the same in every thread: they depend on the item alone
+    for (uint32_t r = 0; r < it.ref_count; r++) {
+        const uint32_t role = rf[r].role;
+        n_must += role == kBqMust;
+        n_not += role == kBqNot;
+    }
+    SdSet set{0ull, 0ull};
+    uint32_t cnt = 0;
+    const uint32_t tile_n = it.doc_hi - it.doc_lo;   // <= kFcTileDocs: the tile is the host's
+    for (uint32_t tile_rel = 0; tile_rel < tile_n; tile_rel += win) {   // (tile_rel + win <= 2^17 + 2^15: no wrap)
+        const uint32_t w_lo = it.doc_lo + tile_rel;
+        const uint32_t w_hi = tile_n - tile_rel > win ? w_lo + win : it.doc_hi;
+        const uint32_t n = w_hi - w_lo, n_words = (n + 31u) / 32u;      // n <= win
+        __syncthreads();   // the sweep of the window before is through
+        for (uint32_t i = tid; i < n; i += 256u) s_acc[i] = 0.0f;
+        for (uint32_t w = tid; w < n_words; w += 256u) {
+            s_bm[w] = 0u;
+            s_tmp[w] = 0u;
+            s_ex[w] = 0u;
+        }
+        __syncthreads();
+        NS_BCNT(1, 1);
+        bool alive = true;   // workgroup-uniform: the cuts depend on the item and the window alone
+        if (n_must) {
+            uint32_t seen = 0;
+            for (uint32_t r = 0; r < it.ref_count; r++) {
+                const BqRef b = rf[r];
+                if (b.role != kBqMust) continue;
+                uint64_t lo, hi;
+                fc_cut(sg, b.list, w_lo, w_hi, lane, lo, hi);
+                if (lo == hi) { alive = false; break; }
+                if (seen == 0u) {
+                    fc_mark(sg.postings, lo, hi, w_lo, w_hi, s_bm);
+                    __syncthreads();
+                } else {
+                    fc_mark(sg.postings, lo, hi, w_lo, w_hi, s_tmp);
+                    __syncthreads();
+                    for (uint32_t w = tid; w < n_words; w += 256u) {
+                        s_bm[w] &= s_tmp[w];
+                        s_tmp[w] = 0u;
+                    }
+                    __syncthreads();
+                    NS_BCNT(3, 1);
+                }
+                seen++;
+            }
+        } else {
+            for (uint32_t r = 0; r < it.ref_count; r++) {
+                const BqRef b = rf[r];
+                if (b.role != kBqShould) continue;
+                uint64_t lo, hi;
+                fc_cut(sg, b.list, w_lo, w_hi, lane, lo, hi);
+                fc_mark(sg.postings, lo, hi, w_lo, w_hi, s_bm);
+            }
+            __syncthreads();
+        }
+        if (alive && n_not) {
+            for (uint32_t r = 0; r < it.ref_count; r++) {
+                const BqRef b = rf[r];
+                if (b.role != kBqNot) continue;
+                uint64_t lo, hi;
+                fc_cut(sg, b.list, w_lo, w_hi, lane, lo, hi);
+                fc_mark(sg.postings, lo, hi, w_lo, w_hi, s_ex);
+            }
+            __syncthreads();
+            bool cleared = false;
+            for (uint32_t w = tid; w < n_words; w += 256u) {
+                const uint32_t m = s_bm[w], x = s_ex[w];
+                cleared = cleared || (m & x) != 0u;
+                s_bm[w] = m & ~x;
+            }
+#ifdef NS_COUNT
+            if (__syncthreads_or(cleared ? 1 : 0)) NS_BCNT(4, 1);
+#else
+            (void)cleared;
+#endif
+        }
+        int mine = 0;   // a thread tests the words it wrote last itself
+        if (alive)
+            for (uint32_t w = tid; w < n_words; w += 256u) mine |= s_bm[w] != 0u;
+        if (!__syncthreads_or(mine)) { NS_BCNT(2, 1); continue; }   // (workgroup-uniform)
+        for (uint32_t r = 0; r < it.ref_count; r++) {
+            const BqRef b = rf[r];
+            if (b.role == kBqNot) continue;
+            uint64_t lo, hi;
+            fc_cut(sg, b.list, w_lo, w_hi, lane, lo, hi);
+            for (uint64_t i = lo + tid; i < hi; i += 256u) {
+                const uint2 p = sg.postings[i];
+                if (p.x < w_lo || p.x >= w_hi) continue;
+                const uint32_t rel = p.x - w_lo;
+                if (!((s_bm[rel >> 5] >> (rel & 31u)) & 1u)) continue;
+                const float tf = (float)p.y;
+                const float s = (b.idf * (tf * (1.2f + 1.0f))) / (tf + norm[p.x]);   // p.x < w_hi <= n_docs
+                s_acc[rel] = s_acc[rel] + b.qweight * s;
+            }
+            __syncthreads();
+        }
+        for (uint32_t wb = v * 64u; wb < n_words; wb += 256u) {   // (wave-uniform)
+            const uint32_t w = wb + lane;
+            uint32_t bits = w < n_words ? s_bm[w] : 0u;
+            cnt += (uint32_t)__popc(bits);
+            while (__ballot(bits != 0u) != 0ull) {
+                uint64_t key = 0;
+                if (bits) {
+                    const uint32_t rel = w * 32u + (uint32_t)__builtin_ctz(bits);   // < n: only such bits are set
+                    bits &= bits - 1u;
+                    key = ((uint64_t)bq_ord(__float_as_uint(s_acc[rel])) << 32) | (uint32_t)~(tile_rel + rel);
+                }
+                bq_insert(set, key, K, lane);
+            }
+        }
+    }
+    __syncthreads();   // (s_cnt is zero; nobody reads the accumulators any more)
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    s_rows[v][lane] = set.hi;
+    s_rows[v][64u + lane] = set.lo;
+    __syncthreads();
+    if (v != 0u) return;
+    if (tid == 0 && s_cnt) atomicAdd(&found[it.query], (unsigned long long)s_cnt);
+#pragma unroll 1
+    for (uint32_t o = 1; o < 4u; o++) {
+        bq_insert(set, s_rows[o][lane], K, lane);
+        if (K > 64u) bq_insert(set, s_rows[o][64u + lane], K, lane);
+    }
+    uint64_t* __restrict__ row = cand + (size_t)blockIdx.x * K;
+    if (lane < K) row[lane] = set.hi;
+    if (64u + lane < K) row[64u + lane] = set.lo;
+}
+
+// items / q_off index the whole call's items; cand holds the rows of the items from item_begin on.
+__global__ void __launch_bounds__(256) k_bq_join(const FcItem* __restrict__ items, const uint32_t* __restrict__ q_off, uint32_t q_begin,
+                                                 uint32_t q_end, uint32_t item_begin, const DevBqSeg* __restrict__ bqs,
+                                                 const uint64_t* __restrict__ cand, uint32_t K, uint32_t* __restrict__ hits,
+                                                 uint32_t* __restrict__ nhits) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = q_begin + blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= q_end) return;                                            // (wave-uniform; no barrier in this kernel)
+    const uint32_t ib = q_off[q], ie = q_off[q + 1u];
+    SdSet set{0ull, 0ull};
+    for (uint32_t i = ib; i < ie; i++) {
+        const uint64_t* __restrict__ row = cand + (size_t)(i - item_begin) * K;
+        if (row[0] == 0ull) continue;                                  // an item that matched nothing (wave-uniform)
+        NS_BCNT_WAVE(7, 1);
+        const uint32_t base = (i - ib) * kSdRowSlots;
+#pragma unroll 1
+        for (uint32_t slot = lane; slot < kSdRowSlots && slot - lane < K; slot += 64u) {   // (wave-uniform: slot - lane is 0 or 64)
+            const uint64_t c = slot < K ? row[slot] : 0ull;
+            bq_insert(set, c ? ((c >> 32) << 32) | (uint32_t)~(base + slot) : 0ull, K, lane);
+        }
+    }
+    uint32_t n = 0;
+#pragma unroll 1
+    for (uint32_t r = lane; r - lane < K; r += 64u) {                  // (r - lane is 0 or 64; K <= 128)
+        const uint64_t jk = r < 64u ? set.hi : set.lo;
+        const bool have = r < K && jk != 0ull;
+        n += (uint32_t)__popcll(__ballot(have));
+        if (r >= K) continue;
+        const size_t at = (size_t)q * K + r;
+        if (have) {
+            const uint32_t low = ~(uint32_t)jk, rel = low / kSdRowSlots, slot = low % kSdRowSlots;
+            const FcItem it = items[ib + rel];
+            const uint64_t c = cand[(size_t)(ib + rel - item_begin) * K + slot];
+            hits[at * 3u + 0u] = bq_unord((uint32_t)(c >> 32));
+            hits[at * 3u + 1u] = bqs[it.seg].seg_id;
+            hits[at * 3u + 2u] = it.doc_lo + ~(uint32_t)c;
+        } else {
+            hits[at * 3u + 0u] = 0xFF800000u;                         // -inf
+            hits[at * 3u + 1u] = 0xFFFFFFFFu;
+            hits[at * 3u + 2u] = 0xFFFFFFFFu;
+        }
+    }
+    if (lane == 0) nhits[q] = n;
+}
+
+}  // namespace ns

@@ -1,0 +1,99 @@
+// Boolean queries: term refs with a role each -> (query, segment) groups -> work items of k_bq_select, one per
+// doc-range tile of the facet tile size.  Host code only, like ns_facet_plan.hpp: no HIP runtime call and no device
+// pointer; tests/boolean_plan_harness.cpp compiles it with g++ for the CPU suite.  fc_plan and ns_sorted_plan.hpp are
+// untouched: the items are FcItems, sd_query_items and sd_cut apply to them as they are.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "ns_sorted_plan.hpp"
+
+namespace ns {
+
+// role of a ref (NS_ROLE_SHOULD / NS_ROLE_MUST / NS_ROLE_NOT of nextsearch_hip.h)
+static constexpr uint32_t kBqShould = 0, kBqMust = 1, kBqNot = 2;
+// Documents per window of the product build: k_bq_select walks a tile in windows whose fp32 accumulators (4 B per
+// document) and three bitmaps live in LDS: 32 KiB + 3 KiB at 2^13.
+static constexpr uint32_t kBqWinDocs = 1u << 13;
+// The largest window a test build may ask for: 128 KiB + 12 KiB + the 4 KiB row exchange still fit the 160 KiB of a CU.
+static constexpr uint32_t kBqMaxWinDocs = 1u << 15;
+// a test window (variants and counting builds): a power of two, whole bitmap words
+inline bool bq_win_ok(uint32_t w) { return w >= 32 && w <= kBqMaxWinDocs && (w & (w - 1)) == 0; }
+
+// One posting list of a group, in the group's (= the query's) order.
+struct BqRef {
+    FcRef list;
+    uint32_t role;
+    float idf, qweight;   // unused under kBqNot
+    uint32_t pad;
+};
+
+// Checks the descriptors and cuts the items.  Per query the refs are grouped by segment (in the order of the call's segment
+// list, refs of a group in query order, each with its role; roles == nullptr: all SHOULD).  Per group: a MUST ref without
+// postings kills the group; SHOULD and NOT refs without postings are dropped; a group left without a MUST or SHOULD ref
+// matches nothing.  Every other group gets one item per tile of [0, n_docs), the last one shorter, query by query.  A ref
+// that scores (MUST, SHOULD) must have a finite idf and qweight.  Returns NS_OK, or NS_E_INVAL with `err` set and nothing
+// usable in the outputs.
+inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_ref* refs, const uint8_t* roles, uint32_t n_refs,
+                   const FcSegView* segs, uint32_t n_segs, uint32_t tile_docs, std::vector<BqRef>& out_refs,
+                   std::vector<FcItem>& out_items, std::string& err) {
+    out_refs.clear();
+    out_items.clear();
+    auto refuse = [&](const std::string& why) { out_refs.clear(); out_items.clear(); err = why; return NS_E_INVAL; };
+    if (!fc_tile_ok(tile_docs)) return refuse(fc_format("facet tile of %u documents: not a power of two in [32, %u]", tile_docs, kFcTileDocs));
+    std::vector<std::pair<uint32_t, uint32_t>> by_id(n_segs);   // (seg_id, position)
+    for (uint32_t i = 0; i < n_segs; i++) by_id[i] = {segs[i].seg_id, i};
+    std::sort(by_id.begin(), by_id.end());
+    for (uint32_t i = 1; i < n_segs; i++)
+        if (by_id[i].first == by_id[i - 1].first) return refuse(fc_format("seg_id %u is listed twice", by_id[i].first));
+    auto slot_of = [&](uint32_t id) -> int64_t {
+        auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(id, 0u));
+        return (it != by_id.end() && it->first == id) ? (int64_t)it->second : -1;
+    };
+    std::vector<std::pair<uint32_t, uint32_t>> order;   // (position of the segment, ref index) of one query
+    for (uint32_t q = 0; q < n_queries; q++) {
+        const uint64_t tb = qd[q].term_begin, tc = qd[q].term_count;
+        if (tb + tc > n_refs) return refuse(fc_format("query %u: refs [%llu, %llu) run past the %u given", q, (unsigned long long)tb, (unsigned long long)(tb + tc), n_refs));
+        order.clear();
+        for (uint64_t r = tb; r < tb + tc; r++) {
+            const ns_term_ref& t = refs[r];
+            const uint32_t role = roles ? roles[r] : kBqShould;
+            if (role > kBqNot) return refuse(fc_format("ref %llu: role %u is none of NS_ROLE_SHOULD, NS_ROLE_MUST, NS_ROLE_NOT", (unsigned long long)r, role));
+            const int64_t slot = slot_of(t.seg_id);
+            if (slot < 0) return refuse(fc_format("ref %llu names segment %u, which the call does not list", (unsigned long long)r, t.seg_id));
+            if (t.byte_off % 8 != 0) return refuse(fc_format("ref %llu: byte offset %llu is not a multiple of 8", (unsigned long long)r, (unsigned long long)t.byte_off));
+            if (t.byte_off / 8 + t.count > segs[slot].n_postings) return refuse(fc_format("ref %llu runs past the postings of segment %u", (unsigned long long)r, t.seg_id));
+            if (role != kBqNot && !(std::isfinite(t.idf) && std::isfinite(t.qweight))) return refuse(fc_format("ref %llu: idf or qweight is not finite", (unsigned long long)r));
+            order.push_back({(uint32_t)slot, (uint32_t)r});
+        }
+        std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (size_t i = 0; i < order.size();) {
+            size_t j = i;
+            while (j < order.size() && order[j].first == order[i].first) j++;
+            const FcSegView& sv = segs[order[i].first];
+            const uint32_t begin = (uint32_t)out_refs.size();
+            bool dead = false;
+            uint32_t positive = 0;
+            for (size_t k = i; k < j; k++) {
+                const ns_term_ref& t = refs[order[k].second];
+                const uint32_t role = roles ? roles[order[k].second] : kBqShould;
+                if (!t.count) { dead = dead || role == kBqMust; continue; }
+                const uint64_t first = t.byte_off / 8;
+                const uint32_t skip = (sv.skip_of && first < (1ull << 32)) ? sv.skip_of((uint32_t)first, t.count) : 0u;
+                out_refs.push_back(BqRef{FcRef{first, t.count, skip}, role, t.idf, t.qweight, 0u});
+                positive += role != kBqNot;
+            }
+            const uint32_t count = (uint32_t)out_refs.size() - begin;
+            if (dead || !positive || !sv.n_docs) out_refs.resize(begin);
+            else
+                for (uint64_t lo = 0; lo < sv.n_docs; lo += tile_docs)
+                    out_items.push_back(FcItem{q, order[i].first, begin, count, (uint32_t)lo, (uint32_t)std::min<uint64_t>(lo + tile_docs, sv.n_docs)});
+            i = j;
+        }
+    }
+    return NS_OK;
+}
+
+}  // namespace ns

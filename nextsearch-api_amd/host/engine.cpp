@@ -2350,4 +2350,149 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
     return body;
 }
 
+// ---- boolean queries (host/boolean.hpp, csrc/ns_boolean.hip) -------------------------------------------
+bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
+                                       uint64_t* found, uint8_t* usable, float* device_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = "search_boolean_batch_flat: no device context: boolean queries run on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = "search_boolean_batch_flat: null argument"; return false; }
+    OpenFilter* f = nullptr;
+    if (filter_handle) {
+        f = filter_of(filter_handle);
+        if (!f) { err_ = "search_boolean_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    }
+    if (Q == 0) return true;
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const uint32_t S = (uint32_t)segments.size();
+    nsx::RowSource rs;
+    if (f) {   // search_filtered_batch_flat's row source
+        rs.rows = f->rows.data();
+        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
+        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+        if (!rs.rows) rs.rows = &no_rows;
+    }
+    // the segments the refs can name, in manifest order: the index's own, or the filter's copies
+    std::vector<uint32_t> ids, listed;
+    std::vector<ns_seg*> segs;
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
+        if (!h) continue;
+        listed.push_back(s);
+        ids.push_back(rs.id_base + s);
+        segs.push_back(h);
+    }
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    std::vector<ns_query_desc> qd;
+    std::vector<ns_term_ref> refs;
+    std::vector<uint8_t> roles;
+    std::vector<char> scratch;
+    std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        qd.assign(b - a, ns_query_desc{0, 0});
+        refs.clear();
+        roles.clear();
+        for (size_t q = a; q < b; q++) {
+            terms.clear();
+            size_t positive = 0;
+            nsx::for_each_boolean_term(queries[q].p, queries[q].n, scratch, [&](const char* p, size_t n, uint8_t role) {
+                terms.emplace_back(dict.find(p, n), role);
+                positive += role != nsx::kRoleNot;
+            });
+            qd[q - a].term_begin = (uint32_t)refs.size();
+            usable[q] = (positive != 0 && S != 0) ? 1 : 0;
+            if (!usable[q]) continue;
+            for (const uint32_t sid : listed)
+                for (const auto& t : terms) {
+                    const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
+                    if (e && e->byte_off != nsx::kAbsent) {
+                        refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                        roles.push_back(t.second);
+                    } else if (t.second == nsx::kRoleMust) {   // the segment has no list of a required term: nothing of it matches
+                        refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});
+                        roles.push_back(t.second);
+                    }
+                }
+            qd[q - a].term_count = (uint32_t)refs.size() - qd[q - a].term_begin;
+        }
+        if (ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            std::fill(nhits + a, nhits + b, 0u);
+            std::fill(hits + a * K, hits + b * K, pad);
+            continue;
+        }
+        float ms = 0.0f;
+        const int rc = ns_search_boolean(ctx_, qd.data(), (uint32_t)(b - a), refs.data(), roles.data(), (uint32_t)refs.size(), (uint32_t)K, ids.data(), segs.data(),
+                                         (uint32_t)ids.size(), hits + a * K, nhits + a, found + a, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_search_boolean: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        for (size_t q = a; q < b; q++)
+            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= rs.id_base;   // manifest positions
+    }
+    return true;
+}
+
+bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_boolean: no device context: this engine has no CPU scoring path"; return false; }
+    const int K = std::max(1, std::min(k, 100));
+    uint32_t handle = 0;
+    std::string head = "{\n";
+    if (f) {   // search_filtered's filter (cached, most recently used in front) and its "filter" member
+        std::string ignored;
+        if (!search_filtered_text(std::string(), K, *f, ignored)) { body = err_; return false; }
+        handle = filter_lru_.front().handle;
+        const size_t at = ignored.find("\n  },\n");
+        if (ignored.compare(0, 14, "{\n  \"filter\": ") != 0 || at == std::string::npos) { body = err_ = "search_boolean: the filtered body has no filter member"; return false; }
+        head = ignored.substr(0, at + 6);
+    }
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits((size_t)K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us)) { body = err_; return false; }
+    SearchResult res;
+    res.query = query;
+    res.k = K;
+    res.segments = (int)segments.size();
+    res.has_found = us != 0;
+    res.found = fd;
+    if (res.has_found)
+        for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    // "boolean" < "filter" < "found": nlohmann keeps keys sorted, so the member sits in front
+    const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
+    std::string o = "{\n  \"boolean\": {\n";
+    static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
+    for (int m = 0; m < 3; m++) {
+        o += std::string("    \"") + kMembers[m].name + "\": [";
+        bool any = false;
+        for (const nsx::BoolTerm& t : terms)
+            if (t.role == kMembers[m].role) {
+                o += any ? ",\n      " : "\n      ";
+                json_escape(o, t.text);
+                any = true;
+            }
+        o += any ? "\n    ]" : "]";
+        o += m < 2 ? ",\n" : "\n";
+    }
+    o += "  },\n";
+    body = o + head.substr(2) + to_json_impl(res).substr(2);
+    return true;
+}
+
+std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    if (!search_boolean_text(query, k, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
 }  // namespace nextsearch

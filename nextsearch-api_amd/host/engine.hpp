@@ -37,6 +37,7 @@
 #include "filter.hpp"
 #include "facet.hpp"
 #include "sorted.hpp"
+#include "boolean.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -329,6 +330,23 @@ public:
     bool search_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
     void release_sorted();
     size_t sort_tables_on_device() const;   // key tables with a device copy right now
+
+    // Boolean queries (host/boolean.hpp, csrc/ns_boolean.hip): `+word` must be held, `-word` must not, every
+    // other word is optional and adds to the score (nsx::parse_boolean).  search_boolean_batch_flat: per query the K =
+    // clamp(k, 1, 100) best matched documents in the search's order with the search's score bits.  hits: Q x K (pad:
+    // {-inf, ~0, ~0}), nhits[q] = min(K, found[q]).  The query preparation goes through the term dictionary like the
+    // search's (the dictionary's rows, or an open filter's under a handle, 0 = none) with one difference: a MUST term gets a
+    // ref in EVERY segment on the device, with count == 0 where the segment (or the filter's copy) has no list of it or the
+    // dictionary does not hold the term at all, so that no document of that segment matches.  usable[q] == 0 (and nhits = 0,
+    // found = 0) when no MUST or SHOULD term is left or the index has no segment: exclusions alone select nothing.  No
+    // semantic expansion, no search cache.  Hits carry manifest positions.  Runs on the primary context.
+    bool search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
+                                   uint64_t* found, uint8_t* usable, float* device_ms = nullptr);
+    // JSON text: search's body (search_filtered's when a filter is given) over the boolean result, plus "boolean": {"must":
+    // [...], "must_not": [...], "should": [...]} (the parsed terms, in query order); dump(2) layout.  Any failure:
+    // {"error": ...} (search_boolean_text: false, body = the message).
+    std::string search_boolean(const std::string& query, int k, const nsx::DocFilter* f = nullptr);
+    bool search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
 
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;

@@ -1062,3 +1062,61 @@ extern "C" int nsh_engine_search_sorted_json(nsh_engine* e, const char* query, i
 
 extern "C" void nsh_engine_release_sorted(nsh_engine* e) { try { if (e) e->eng.release_sorted(); } NSH_CATCH_VOID(e, "nsh_engine_release_sorted") }
 extern "C" uint64_t nsh_engine_sort_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.sort_tables_on_device() : 0; }
+
+// ---- boolean queries (host/boolean.hpp) ----
+extern "C" uint32_t nsh_parse_boolean(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t roles_cap) { try {
+    const auto terms = nsx::parse_boolean(query ? query : "");
+    std::string joined;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (i) joined.push_back(' ');
+        joined += terms[i].text;
+        if (roles && i < roles_cap) roles[i] = terms[i].role;
+    }
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(joined.size(), cap - 1);
+        std::memcpy(buf, joined.data(), n);
+        buf[n] = 0;
+    }
+    return (uint32_t)terms.size();
+} NSH_CATCH(nullptr, "nsh_parse_boolean", 0)
+}
+
+extern "C" int nsh_engine_search_boolean_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k, void* hits,
+                                               uint32_t* nhits, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    if (!e) return -1;
+    if (n_queries && (!queries || !hits || !nhits)) { nsh_set_err(e, "nsh_engine_search_boolean_batch: null argument"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    if (!e->eng.search_boolean_batch_flat(filter_handle, views.data(), n_queries, k, (ns_hit*)hits, nhits, found, has_found, device_ms_out)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_search_boolean_batch", -1)
+}
+
+extern "C" int nsh_engine_search_boolean_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                              int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+    const bool ok = e->eng.search_boolean_text(query ? query : "", k, use_filter ? &f : nullptr, s);
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_boolean_json", -1)
+}

@@ -21,6 +21,9 @@
 //   ns_tool search-sorted <index_dir> <newest|oldest> <from> <to> <k> <query text ...>   (needs an MI355X)
 //        Engine::search_sorted: search's JSON body with "results" in date order (publish_time; undated documents last in both
 //        directions) plus "sort" (sorted.hpp).  from / to as search-filtered's; "-" "-" searches the whole index.
+//   ns_tool search-boolean <index_dir> <from> <to> <k> <query words ...>   (needs an MI355X)
+//        Engine::search_boolean: `+word` must be held, `-word` must not, other words are optional (boolean.hpp); search's JSON
+//        body plus "boolean".  from / to as search-filtered's; "-" "-" searches the whole index.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -114,6 +117,21 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
         if (!eng.search_sorted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-sorted failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 7 && std::strcmp(argv[1], "search-boolean") == 0) {
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[3], "-") != 0 || std::strcmp(argv[4], "-") != 0;
+        if (std::strcmp(argv[3], "-") != 0) f.date_from = argv[3];
+        if (std::strcmp(argv[4], "-") != 0) f.date_to = argv[4];
+        const int k = std::atoi(argv[5]);
+        std::string q, body;
+        for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_boolean_text(q, k, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

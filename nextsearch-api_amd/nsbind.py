@@ -20,6 +20,7 @@ NS_OK = 0
 NS_FLAG_OR = 0
 NS_FLAG_AND = 1
 NS_SORT_DESC, NS_SORT_ASC = 0, 0x1000   # ns_search_sorted
+NS_ROLE_SHOULD, NS_ROLE_MUST, NS_ROLE_NOT = 0, 1, 2   # ns_search_boolean
 NS_INFO_IMPACTS = 0x100
 NS_INFO_PACKED = 0x200
 NS_INFO_PRUNED = 0x400
@@ -59,6 +60,7 @@ assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 HIP_SYMBOLS = [
     "ns_facet_upload", "ns_facet_release", "ns_facet_count", "ns_facet_tile_docs",
     "ns_dockeys_upload", "ns_dockeys_release", "ns_search_sorted", "ns_sorted_kernel_ms",
+    "ns_search_boolean", "ns_boolean_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -72,6 +74,7 @@ HIP_SYMBOLS = [
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
 HOST_SYMBOLS = [
+    "nsh_parse_boolean", "nsh_engine_search_boolean_batch", "nsh_engine_search_boolean_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
     "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
@@ -236,6 +239,8 @@ def hip_lib():
         L.ns_dockeys_release.argtypes = [vp, vp]
         L.ns_search_sorted.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_sorted_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        L.ns_search_boolean.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_boolean_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -245,7 +250,8 @@ def hip_lib():
 
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
-                  "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9}
+                  "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
+                  "ns_debug_boolean_counters": 8}
 
 
 def debug_counters(reset=False):
@@ -404,6 +410,10 @@ def host_lib():
         L.nsh_engine_release_sorted.restype = None
         L.nsh_engine_sort_tables_on_device.argtypes = [vp]
         L.nsh_engine_sort_tables_on_device.restype = u64
+        L.nsh_parse_boolean.argtypes = [C.c_char_p, C.c_char_p, u32, vp, u32]
+        L.nsh_parse_boolean.restype = u32
+        L.nsh_engine_search_boolean_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_boolean_json.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         _host = L
     return _host
 
@@ -905,6 +915,34 @@ class Engine:
             self._L.nsh_free(out)
         if rc != 0 and check:
             raise RuntimeError(f"search_sorted failed: {self.error()}")
+        return body
+
+    def search_boolean_batch(self, queries, k, handle=0, timing=False):
+        """Engine::search_boolean_batch_flat: (hits Q x K, nhits, found, has_found); `+word` required, `-word` excluded, other
+        words optional.  handle: an open filter's (0: none).  timing=True adds the kernels' device ms."""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_boolean_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), hits.ctypes.data, nhits.ctypes.data,
+                                                     found.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_boolean_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_boolean_json(self, query, k, date_filter=None, check=True):
+        """Engine::search_boolean: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure raises
+        (check=False: returns the {"error": ...} body)."""
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_boolean_json(self.h, _as_bytes(query), k, int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
+                                                    int(bool(ku)), C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_boolean failed: {self.error()}")
         return body
 
     def release_sorted(self):
@@ -1686,6 +1724,41 @@ def sorted_kernel_ms(reset=True):
     """(k_sd_select, k_sd_join, k_sd_score) HIP-event ms summed over this thread's ns_search_sorted calls since the last reset"""
     out = (C.c_float * 3)()
     hip_lib().ns_sorted_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+def parse_boolean(text):
+    """nsx::parse_boolean (host only): [(term, role)] with role one of NS_ROLE_SHOULD / NS_ROLE_MUST / NS_ROLE_NOT"""
+    b = _as_bytes(text)
+    cap = len(b) + 2
+    buf, roles = C.create_string_buffer(cap), np.zeros(cap, dtype=np.uint8)
+    n = int(host_lib().nsh_parse_boolean(b, buf, cap, roles.ctypes.data, cap))
+    words = buf.value.decode().split(" ") if n else []
+    return [(w, int(r)) for w, r in zip(words, roles[:n])]
+
+
+def search_boolean_raw(ctx, qd, refs, roles, k, seg_ids, segs):
+    """ns_search_boolean (raw): (rc, hits Q x K, nhits, found, device ms); K = clamp(k, 1, 100); roles: one uint8 per ref, or
+    None (all SHOULD); segs: list of handles.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_boolean(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                     ro.ctypes.data if ro is not None and len(ro) else None, len(refs), int(k),
+                                     ids.ctypes.data if len(ids) else None, sa, len(ids), hits.ctypes.data, nhits.ctypes.data,
+                                     found.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], nhits[:Q], found[:Q], float(ms.value)
+
+
+def boolean_kernel_ms(reset=True):
+    """(k_bq_select, k_bq_join) HIP-event ms summed over this thread's ns_search_boolean calls since the last reset"""
+    out = (C.c_float * 2)()
+    hip_lib().ns_boolean_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
