@@ -227,6 +227,22 @@ int ns_ctx_use_merge(ns_ctx* ctx, int on);
  * ns_batch_info reports NS_INFO_SHARED, shared_lists and shared_postings; sum_score_kernel_ms covers both kernels. */
 int ns_ctx_share_scores(ns_ctx* ctx, int mode);
 
+/* Shared top rows.  A "thin" (query, segment) group is one hot list H plus tail lists that hold at most 1/32 of its postings.
+ * Every doc that no tail holds scores 0.0f + w * s_H(d), whichever query asks, so a sharing batch (ns_ctx_share_scores) ranks
+ * H ONCE per cell of its doc space (a power-of-two cut that leaves at most 64 Ki of H's postings per cell): the best 64
+ * postings of the cell, one row of a per-batch buffer (64 hits per row; allocated with the batch, nothing is kept between
+ * batches or runs).  The thin groups of the batch that name H with the same idf and weight are cut into exactly those cells
+ * and scored by a kernel of their own that does not stream H: the tails' docs look H up by docId through its skip table
+ * (ns_segment_build_skips), every other candidate comes from the row.  An item whose row cannot prove its top-K (more than
+ * 64 - K of the row's docs are docs of the tails, and the row does not hold the whole cell) is scored once more by the
+ * streaming body, inside the same launch.  Hits, order, nhits, found and score bits are identical either way.
+ * Eligible: OR mode, K <= 32, at most 16 term refs, no negative idf or weight, H has a skip table.  mode 1 (default): H gets
+ * rows when at least 4 eligible groups of the batch name it; mode 2: always (tests); mode 0: never. */
+int ns_ctx_share_rows(ns_ctx* ctx, int mode);
+/* out: producer items (rows) and consumer items of the batch as prepared, then, summed over the batch's runs so far (waits
+ * for them): consumer items that fell back to the streaming body, row entries that were docs of a tail. */
+int ns_batch_row_stats(ns_batch* b, uint32_t out[4]);
+
 /* ---- one-shot search (host buffers in, host buffers out) ------------------------------------ */
 /* hits_out: Q*K entries, query-major, best first: score desc, then seg_id asc, then doc_id asc
  * (the reference leaves ties unspecified: src/api_engine.cpp:485-492); unused tail entries are

@@ -21,6 +21,7 @@
 #include "ns_prune_kernel.hip"
 #include "ns_merge_kernel.hip"
 #include "ns_tile_kernel.hip"
+#include "ns_row_kernel.hip"   // after ns_tile_kernel.hip (kUscoreWavesPerBlock: the producers are items of k_uscore)
 #include "ns_invert.hip"
 #include "ns_ingest.hip"
 #include "ns_compact.hip"
@@ -96,6 +97,10 @@ struct ns_ctx {
     // runs NEXT TO batch i's scoring kernel instead of behind it on the batch's stream or in the shared DMA queue.
     hipStream_t pull_stream = nullptr;
     bool overlap = false, flip = false;
+    // shared top rows: the producers and consumers of a batch run here, next to its scoring launch (fork after k_share_scores,
+    // join in front of k_merge: two events of the batch); without it they run in front of and behind the scoring launch on
+    // the batch's stream
+    hipStream_t row_stream = nullptr;
     std::string err;
     std::string devname;
     std::vector<ns_seg*> segs;   // indexed by seg_id
@@ -233,6 +238,14 @@ extern "C" int ns_ctx_create(int device, ns_ctx** out) {
     if (const char* sm = std::getenv("NS_SHARE")) ctx->cfg.share_mode = std::max(0, std::min(2, std::atoi(sm)));
     if (const char* sr = std::getenv("NS_SHARE_RATIO")) ctx->cfg.share_ratio = (uint32_t)std::max(1, std::atoi(sr));
     if (const char* sp = std::getenv("NS_SHARE_MIN")) ctx->cfg.share_min_postings = (uint64_t)std::max(0ll, std::atoll(sp));
+    ctx->cfg.row_mode = 1;
+    if (const char* rm = std::getenv("NS_SHARE_ROWS")) ctx->cfg.row_mode = std::max(0, std::min(2, std::atoi(rm)));
+    if (const char* ru = std::getenv("NS_ROW_MIN_USERS")) ctx->cfg.row_min_users = (uint32_t)std::max(1, std::atoi(ru));
+    if (const char* rc = std::getenv("NS_ROW_CELL")) ctx->cfg.row_cell_postings = (uint32_t)std::max(1, std::atoi(rc));
+    {
+        const char* rf = std::getenv("NS_ROW_FORK");   // 0: the producers stay on the batch's stream (measurements)
+        if ((!rf || std::atoi(rf) != 0) && hipStreamCreateWithFlags(&ctx->row_stream, hipStreamNonBlocking) != hipSuccess) { ctx->row_stream = nullptr; (void)hipGetLastError(); }
+    }
     if (const char* oc = std::getenv("NS_ORDER_COARSE")) { ctx->cfg.order_coarse = std::max(0, std::min(11, std::atoi(oc))); ctx->cfg.order_coarse_forced = true; }
     if (hipStreamCreateWithFlags(&ctx->alt_stream, hipStreamNonBlocking) != hipSuccess) { ctx->alt_stream = nullptr; (void)hipGetLastError(); }
     {
@@ -250,6 +263,7 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->alt_stream) (void)hipStreamSynchronize(ctx->alt_stream);
     if (ctx->pull_stream) (void)hipStreamSynchronize(ctx->pull_stream);
+    if (ctx->row_stream) (void)hipStreamSynchronize(ctx->row_stream);
     for (ns_seg* s : ctx->segs) {
         if (!s) continue;
         seg_free_device_fwd(s);
@@ -271,6 +285,7 @@ extern "C" void ns_ctx_destroy(ns_ctx* ctx) {
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->alt_stream) (void)hipStreamDestroy(ctx->alt_stream);
     if (ctx->pull_stream) (void)hipStreamDestroy(ctx->pull_stream);
+    if (ctx->row_stream) (void)hipStreamDestroy(ctx->row_stream);
     delete ctx;
 }
 
@@ -672,6 +687,13 @@ extern "C" int ns_ctx_share_scores(ns_ctx* ctx, int mode) {
     return NS_OK;
 }
 
+extern "C" int ns_ctx_share_rows(ns_ctx* ctx, int mode) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_share_rows: ctx is NULL");
+    if (mode < 0 || mode > 2) return fail(ctx, NS_E_INVAL, "ns_ctx_share_rows: mode %d outside [0, 2]", mode);
+    ctx->cfg.row_mode = mode;
+    return NS_OK;
+}
+
 extern "C" int ns_segment_build_packed(ns_ctx* ctx, ns_seg* seg) {
     if (!ctx || !seg) return fail(ctx, NS_E_INVAL, "ns_segment_build_packed: null argument");
     if (seg->pending || seg->id >= ctx->segs.size() || ctx->segs[seg->id] != seg) return fail(ctx, NS_E_INVAL, "segment does not belong to this ctx");
@@ -944,6 +966,15 @@ struct ns_batch {
     uint32_t n_share = 0;          // distinct lists the batch builds
     uint64_t share_postings = 0;   // their postings
     DevShare* d_share = nullptr;   // n_share + 1 entries
+    // shared top rows (ns_ctx_share_rows): producer items (k_uscore with K' = kRowLen into the row buffer), consumer items (k_rscore)
+    uint32_t n_pitems = 0, n_ritems = 0;
+    DevWItem* d_pitems = nullptr;
+    DevRItem* d_ritems = nullptr;
+    Hit* d_row_hits = nullptr;         // kRowLen entries per producer item
+    uint32_t* d_row_nhits = nullptr;
+    uint64_t* d_row_found = nullptr;
+    uint32_t* d_row_stats = nullptr;   // over the batch's runs: fallbacks, row entries that hit the table
+    hipEvent_t row_fork = nullptr, row_join = nullptr;
     // device
     DevItem* d_items = nullptr;
     DevWItem* d_witems = nullptr;
@@ -1042,6 +1073,8 @@ extern "C" void ns_batch_destroy(ns_batch* b) {
     for (auto& blk : b->blocks) pool_free(b->ctx, blk.first, blk.second);
     for (auto& e : b->ev_pool) if (e) (void)hipEventDestroy(e);
     if (b->done) (void)hipEventDestroy(b->done);
+    if (b->row_fork) (void)hipEventDestroy(b->row_fork);
+    if (b->row_join) (void)hipEventDestroy(b->row_join);
     delete b;
 }
 
@@ -1133,6 +1166,7 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
     b->pk = (P.all_pk && P.postings_total > 0) ? ctx->cfg.use_packed : 0;
     b->pruned = P.pruned;
     b->n_wide_q = (uint32_t)P.wide_q.size();
+    b->n_pitems = P.n_pitems; b->n_ritems = P.n_ritems;
 
     // One device block per batch: [descriptors, uploaded in one copy][scratch][hits | nhits | found, fetched in one copy]
     hipError_t e = hipSuccess;
@@ -1150,6 +1184,12 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
         o_pfound = place(Pn * 8);
         o_heads = place(Pn * 4);
     }
+    size_t o_rhits = 0, o_rnhits = 0, o_rfound = 0;
+    if (b->n_pitems) {   // the row buffer: one row of kRowLen hits per producer item
+        o_rhits = place((size_t)b->n_pitems * kRowLen * sizeof(Hit));
+        o_rnhits = place((size_t)b->n_pitems * 4);
+        o_rfound = place((size_t)b->n_pitems * 8);
+    }
     const size_t o_hits = place(Qn * k * sizeof(Hit));
     const size_t o_nhits = place(Qn * 4);
     const size_t o_found = place(Qn * 8);
@@ -1165,6 +1205,14 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
         b->d_wide_q = (uint32_t*)(base + L.wideq);
         b->d_share = (DevShare*)(base + L.share);
         b->d_bounds = (uint32_t*)(base + o_bounds);
+        if (b->n_pitems) {
+            b->d_pitems = (DevWItem*)(base + L.pitems);
+            b->d_ritems = (DevRItem*)(base + L.ritems);
+            b->d_row_hits = (Hit*)(base + o_rhits);
+            b->d_row_nhits = (uint32_t*)(base + o_rnhits);
+            b->d_row_found = (uint64_t*)(base + o_rfound);
+            b->d_row_stats = (uint32_t*)(base + L.rstats);   // zero in the descriptor image
+        }
         if (!P.direct) {
             b->d_part_hits = (Hit*)(base + o_phits);
             b->d_part_nhits = (uint32_t*)(base + o_pnhits);
@@ -1295,6 +1343,29 @@ extern "C" int ns_batch_run(ns_batch* b, int run_flags) {
     Hit* sh = b->direct ? b->o_hits : b->d_part_hits;
     uint32_t* sn = b->direct ? b->o_nhits : b->d_part_nhits;
     uint64_t* sf = b->direct ? b->o_found : b->d_part_found;
+    // shared top rows, producers: the hot lists' cells as single-term items of the scoring kernel's own instantiation with
+    // K' = kRowLen (CB = 128 holds K' + 64), into the row buffer; next to the scoring launch when the ctx has the side stream
+    const bool rows = b->n_pitems && b->n_ritems && b->variant == 0;
+    bool row_forked = false;
+    if (rows) {
+        hipStream_t ps = st;
+        if (ctx->row_stream) {
+            if (!b->row_fork) HIPCHK(ctx, hipEventCreateWithFlags(&b->row_fork, hipEventDisableTiming));
+            if (!b->row_join) HIPCHK(ctx, hipEventCreateWithFlags(&b->row_join, hipEventDisableTiming));
+            HIPCHK(ctx, hipEventRecord(b->row_fork, st));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->row_stream, b->row_fork, 0));
+            ps = ctx->row_stream;
+            row_forked = true;
+        }
+        launch_uscore<128, 16>(false, true, 0, b->n_pitems, ps, b->d_pitems, b->d_terms, b->d_segs, b->d_row_hits, b->d_row_nhits, b->d_row_found, kRowLen);
+        // ... and the consumers right behind them: they wait for the producers alone (stream order), not for the scoring launch,
+        // whose wave slots they fill as it drains — launched after it they were a serial tail of 0.3 ms (profiles/row_share)
+        if (row_forked) {
+            hipLaunchKernelGGL((k_rscore<512, 128, 16>), dim3(b->n_ritems), dim3(64), 0, ps, b->d_ritems, b->n_ritems, b->d_terms, b->d_segs,
+                               b->d_row_hits, b->d_row_nhits, sh, sn, sf, b->K, b->d_row_stats);
+            HIPCHK(ctx, hipEventRecord(b->row_join, ps));
+        }
+    }
     if (b->n_witems && b->variant == 0) {
         // auto mode: ONE launch; each wave picks the body that suits its item (DevWItem::whole bit 1)
         // K <= 64: a 128-entry candidate buffer is enough (K + 64 appended per step at most) and its
@@ -1331,6 +1402,11 @@ extern "C" int ns_batch_run(ns_batch* b, int run_flags) {
 #undef NS_D
     }
 #endif
+    if (rows) {   // shared top rows: the side stream joins in front of the row join of the queries; without it the consumers run here
+        if (row_forked) HIPCHK(ctx, hipStreamWaitEvent(st, b->row_join, 0));
+        else hipLaunchKernelGGL((k_rscore<512, 128, 16>), dim3(b->n_ritems), dim3(64), 0, st, b->d_ritems, b->n_ritems, b->d_terms, b->d_segs,
+                                b->d_row_hits, b->d_row_nhits, sh, sn, sf, b->K, b->d_row_stats);
+    }
     if (b->n_items) {   // term groups of more than 64 terms (and, in the variants build, every group of variants 1-4): the workgroup-tile kernel
 #ifdef NS_VARIANTS
         const VariantDesc vd = kVariants[b->variant];
@@ -1493,7 +1569,7 @@ extern "C" int ns_batch_get_info(ns_batch* b, ns_batch_info* info) {
     info->postings = b->postings;
     info->algo_bytes = b->postings * 8;
     info->n_queries = b->Q;
-    info->n_items = b->n_items + b->n_witems;
+    info->n_items = b->n_items + b->n_witems + b->n_ritems + b->n_pitems;
     info->n_term_refs = b->n_terms;
     info->tile_docs = b->tile_docs;
     info->k = b->K;
@@ -1506,6 +1582,21 @@ extern "C" int ns_batch_get_info(ns_batch* b, ns_batch_info* info) {
     info->timed_runs = b->timed_runs;
     info->sum_score_kernel_ms = b->sum_score_ms;
     info->sum_total_ms = b->sum_total_ms;
+    return NS_OK;
+}
+
+// shared top rows of the batch: producer items, consumer items, and over its runs so far (waited for here) the consumer
+// items that fell back to the streaming body and the row entries that hit a table
+extern "C" int ns_batch_row_stats(ns_batch* b, uint32_t out[4]) {
+    if (!b || !out) return NS_E_INVAL;
+    ns_ctx* ctx = b->ctx;
+    const bool rows = b->n_pitems && b->n_ritems && b->variant == 0;
+    out[0] = rows ? b->n_pitems : 0u; out[1] = rows ? b->n_ritems : 0u; out[2] = 0u; out[3] = 0u;
+    if (rows && b->ran) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemcpyAsync(out + 2, b->d_row_stats, 8, hipMemcpyDeviceToHost, b->st));
+        HIPCHK(ctx, hipStreamSynchronize(b->st));
+    }
     return NS_OK;
 }
 

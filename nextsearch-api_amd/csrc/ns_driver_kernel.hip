@@ -37,7 +37,9 @@ namespace ns {
 // rare paths: 20 pass-A lanes whose bucket is full (pos >= 4), 21 pass-A chunks that start in the bucket the previous chunk
 // ended in (carry), 22 claim-loop lanes that move to the next bucket, 23 ... of which wrap to bucket 0, 24 claim-loop lanes
 // that found their doc's owner in the table, 25 super-batches without a primary term (largest window < 8), 26 super-batches
-// that find a posting's term by binary search (T > 8), 27 super-batches whose span was clamped.
+// that find a posting's term by binary search (T > 8), 27 super-batches whose span was clamped.  The row consumer (ROW):
+// 19 consumer items, 28 look-ups of an owner's doc in the hot list, 29 ... that found it, 30 row entries that probed the
+// table, 31 ... that hit it.
 constexpr int kNsCnt = 32;
 __device__ unsigned long long g_ns_cnt[kNsCnt];
 #define NS_CNT(i, v) cnt_[(i)] += (unsigned long long)(v)
@@ -119,11 +121,23 @@ __device__ __forceinline__ uint64_t lane_span(uint32_t lo, uint32_t hi) {
     return upto_hi & ~upto_lo;
 }
 
-template <int NB, int FB, bool AND, int CB = 256, bool IMP = false, int PK = 0>
-__device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* __restrict__ terms, const DevSeg* __restrict__ segs,
+// ROW (k_rscore, ns_row_kernel.hip; "shared top rows"): the driver — term `dterm` of the group, fixed by the host — is NOT
+// streamed.  Its best kRowLen postings over exactly this item's doc range lie in `hits` (a single-term item's result row
+// with K' = kRowLen, `nhits` entries), one per lane.  Section 3 is replaced: the owners of this super-batch's table entries
+// look their doc up in the driver's list (skip table + a lower bound of fixed length) and add its score at the driver's
+// place in the term order; the row entries of the super-batch's doc span probe the table as a driver chunk does: a miss is
+// a doc that no foreign list holds — its score is the row's, bit for bit — and is offered, a hit was scored through its
+// owner and is counted.  The item's result is proven when the row holds every posting of the range, or when at most
+// kRowLen - K of its entries hit the table (the K best docs outside the foreign lists are then among the rest); otherwise
+// the body returns false without writing and the caller runs the streaming body over the same item.
+struct RowArgs { const Hit* hits; uint32_t nhits; uint32_t dterm; uint32_t* stats; };
+
+template <int NB, int FB, bool AND, int CB = 256, bool IMP = false, int PK = 0, bool ROW = false>
+__device__ __forceinline__ bool dscore_body(const DevWItem& it, const DevTerm* __restrict__ terms, const DevSeg* __restrict__ segs,
                                             uint32_t* ent, float* vals, uint8_t* mcnt, uint64_t* cand, uint4* tab, uint32_t* aux,
                                             Hit* __restrict__ out_hits, uint32_t* __restrict__ out_nhits,
-                                            uint64_t* __restrict__ out_found, uint32_t K, const int lane) {
+                                            uint64_t* __restrict__ out_found, uint32_t K, const int lane, const RowArgs ra = RowArgs{}) {
+    static_assert(!ROW || (FB == 64 && !AND && IMP && PK == 0), "the row consumer is the thin OR body over shared term scores");
     // CB: candidate buffer entries, a power of two >= K + 64 (the launcher picks 128 for K <= 64: less LDS)
     constexpr int FE = FB / 64;            // foreign postings per lane per super-batch
     constexpr int DE = 4;                  // driver postings per lane per round
@@ -191,6 +205,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         dl = (uint32_t)__builtin_ctzll(wballot(remv == mx && (uint32_t)lane < T) | (1ull << 63));
         if (dl >= T) dl = 0;
     }
+    if constexpr (ROW) dl = ra.dterm;   // the hot list whose row this item reads, wherever most of this range's postings lie
     uint32_t d_cur = rdlane(cur, dl);
     const uint32_t d_end = rdlane(end, dl);
     const float d_idf = __uint_as_float(rdlane(idf_bits, dl));
@@ -216,6 +231,22 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
     const uint32_t last_doc = it.doc_hi - 1;   // host guarantees doc_hi > doc_lo and doc_hi <= n_docs
     WaveTopK<CB> top(cand, K, lane);   // a step of its tie rule is one super-batch
     uint32_t found_s = 0;      // `found`, wave-uniform: private driver postings and owners of table entries, counted by ballots
+    // ROW: lane l holds row entry l.  `found` = the driver's postings in the range + owners - owners that the driver holds too.
+    float r_sc = 0.0f;
+    uint32_t r_doc = 0xFFFFFFFFu, row_hits = 0;
+    uint64_t r_left = 0ull;    // row entries not yet offered or counted (docIds above every finished super-batch)
+    bool row_complete = false;
+    gp_u32 d_skips = nullptr;
+    if constexpr (ROW) {
+        const uint32_t nrow = min(ra.nhits, kRowLen);
+        const Hit rh = ra.hits[lane];
+        r_sc = rh.score; r_doc = rh.doc;
+        r_left = lane_span(0u, nrow);
+        found_s = d_end - d_cur;
+        row_complete = nrow == d_end - d_cur;
+        d_skips = (gp_u32)seg.skips + (terms[it.term_begin + dl].skip - 1u);
+        NS_CNT(19, 1);
+    }
 
     // Foreign windows: sizes proportional to what is left of each foreign list (all windows span about
     // the same doc range), at most FB postings in total; one docId probe per window (its last posting).
@@ -524,13 +555,95 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         }
         if (total > 0 && tb_min < dl) { NS_FOREIGN_RMW(tb_min, min(tb_max, dl - 1)); }
 
+        if constexpr (ROW) {
+            // ================= 3 (ROW). the owners look their doc up in the driver's list; the row entries of [lo, hi] =========
+            if (total > 0) {
+                static_assert(FE == 1, "one foreign posting per lane");
+                const bool own = fmine[0];
+                const uint32_t doc = own ? fdoc[0] : lo;          // every lane searches (a valid cell): no exec juggling
+                const uint32_t cell = doc / kSkipDocs;            // lo .. hi lie inside the item's range, which lies on the grid
+                uint32_t a = d_skips[cell];
+                uint32_t n = d_skips[cell + 1u] - a;   // the driver's postings in the doc's cell: at most kSkipDocs (a cell of ONE list)
+                // Lower bound by EIGHTS: a step probes the last posting of each of the first seven eighths of the bracket —
+                // seven independent loads, one round trip — and keeps the eighth the doc falls into: 1024 -> 128 -> 16 -> 2 -> 0
+                // postings in four steps (a halving search is eleven dependent round trips, and the look-up is most of a
+                // super-batch's latency here).  The bracket's right end is always the cell's end or a probed posting >= doc,
+                // so a posting that holds the doc has been probed when the bracket is empty: `hit` needs no further load.
+                bool hit = false;
+                uint32_t hbits = 0u;
+#pragma unroll
+                for (int step = 0; step < 4; step++) {
+                    const uint32_t s8 = (n + 7u) >> 3;   // postings per eighth (0 only when n == 0)
+                    nat_u2 pv[7];
+#pragma unroll
+                    for (int i = 0; i < 7; i++) {
+                        const uint32_t e = (uint32_t)(i + 1) * s8;            // the i-th eighth ends in front of posting e
+                        pv[i] = stream[a + ((e <= n && e != 0u) ? e - 1u : 0u)];   // (an eighth beyond the bracket: a valid address, dropped)
+                    }
+                    uint32_t c = 0u;
+#pragma unroll
+                    for (int i = 0; i < 7; i++) {
+                        const uint32_t e = (uint32_t)(i + 1) * s8;
+                        const bool valid = e <= n && e != 0u;
+                        c += (valid && pv[i].x < doc) ? 1u : 0u;              // sorted: a prefix of the probes
+                        if (valid && pv[i].x == doc) { hit = true; hbits = pv[i].y; }
+                    }
+                    const bool closed = c < 7u && (c + 1u) * s8 <= n;         // probe c exists and is >= doc: the bracket ends in front of it
+                    a += c * s8;
+                    n = (n == 0u) ? 0u : (closed ? s8 - 1u : n - c * s8);
+                }
+                hit = hit && own;
+                if (hit) vals[lane] = vals[lane] + d_wq * __uint_as_float(hbits);   // the owner's accumulator is its own slot
+                found_s -= (uint32_t)__popcll(wballot(hit));
+                NS_CNT(28, (uint32_t)__popcll(wballot(own)));
+                NS_CNT(29, (uint32_t)__popcll(wballot(hit)));
+                wave_sync();
+            }
+            const uint64_t inr = r_left & wballot(r_doc <= hi);
+            if (inr != 0ull) {
+                uint64_t offm = inr;
+                if (total > 0) {
+                    const uint32_t tag = NS_TAG(r_doc);
+                    const uint32_t hb = NS_BUCKET(r_doc);   // in range whatever the docId; only the entries of `inr` count
+                    uint32_t b = hb;
+                    uint4 q = ent4[b];
+                    const uint64_t cm = wballot((q.x >> 16) == tag) | wballot((q.y >> 16) == tag) |
+                                        wballot((q.z >> 16) == tag) | wballot((q.w >> 16) == tag);
+                    const uint64_t go = inr & (cm | wballot(q.w != EMPTY));
+                    NS_CNT(30, (uint32_t)__popcll(inr));
+                    if (go != 0ull) {
+                        const uint32_t ident = NS_IDENT(r_doc, hb);
+                        uint32_t m = 0;
+                        bool more = __builtin_amdgcn_inverse_ballot_w64(go);
+                        for (int round = 0; round < NB; round++) {   // a full bucket without a match: the next one, at most all of them
+                            if (wballot(more) == 0ull) break;
+                            if (more) {
+                                m = ((q.x ^ ident) < 256u) ? q.x : m;
+                                m = ((q.y ^ ident) < 256u) ? q.y : m;
+                                m = ((q.z ^ ident) < 256u) ? q.z : m;
+                                m = ((q.w ^ ident) < 256u) ? q.w : m;
+                                more = m == 0 && q.w != EMPTY;
+                                if (more) { b = (b + 1) & (uint32_t)(NB - 1); q = ent4[b]; }
+                            }
+                        }
+                        const uint64_t hitm = wballot(m != 0) & go;
+                        offm &= ~hitm;   // scored through the table's owner (whose look-up found this posting)
+                        row_hits += (uint32_t)__popcll(hitm);
+                        NS_CNT(31, (uint32_t)__popcll(hitm));
+                    }
+                }
+                top.offer_mask_stream(offm, r_sc, r_doc);
+                r_left &= ~inr;
+            }
+        }
+
         // ================= 3. stream the driver's postings with docId <= hi =================
         // Lane predicates of this section live in SGPR pairs (ballot masks combined with scalar logic);
         // the loads use a scalar base + a fixed lane offset (they may run up to 255 postings past the
         // end of the list: the device buffers are padded), so the only vector work per posting is the
         // docId compare, the BM25 term score and the bucket probe.
         bool driver_progress = false;
-        for (;;) {
+        if constexpr (!ROW) for (;;) {
             const uint32_t remd = d_end - d_cur;
             if (remd == 0) break;
             uint32_t n;
@@ -732,8 +845,10 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
         top.keep_room();
 
         if (hi >= last_doc) break;
-        if (Rf == 0 && d_cur >= d_end) break;
-        if (total == 0 && !driver_progress) break;   // only with corrupt lists: nothing can advance
+        if constexpr (!ROW) {   // (the row consumer goes on to last_doc: the rest of its row is offered on the way)
+            if (Rf == 0 && d_cur >= d_end) break;
+            if (total == 0 && !driver_progress) break;   // only with corrupt lists: nothing can advance
+        }
         lo = hi + 1;
     }
 #undef NS_FOREIGN_RMW
@@ -745,6 +860,16 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
 #ifdef NS_COUNT
     const unsigned long long cyc_t1_ = __builtin_readcyclecounter();
 #endif
+    if constexpr (ROW) {
+        if (lane == 0 && row_hits != 0u) atomicAdd(ra.stats + 1, row_hits);
+        if (!row_complete && row_hits > kRowLen - K) {   // not proven: nothing is written, the caller streams the item
+#ifdef NS_COUNT
+            if (lane == 0)
+                for (int i = 0; i < kNsCnt; i++) if (cnt_[i]) atomicAdd(&g_ns_cnt[i], cnt_[i]);
+#endif
+            return false;
+        }
+    }
     top.write_out(it.seg, it.out_slot, found_s, out_hits, out_nhits, out_found);
 #ifdef NS_COUNT
     cnt_[17] = __builtin_readcyclecounter() - cyc_t0_;
@@ -752,6 +877,7 @@ __device__ __forceinline__ void dscore_body(const DevWItem& it, const DevTerm* _
     if (lane == 0)
         for (int i = 0; i < kNsCnt; i++) if (cnt_[i]) atomicAdd(&g_ns_cnt[i], cnt_[i]);
 #endif
+    return true;
 }
 
 // HK = table entries per wave (4 per bucket)

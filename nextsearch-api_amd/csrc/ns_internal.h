@@ -115,6 +115,16 @@ struct DevWItem {
                            //        number of the list's postings in the doc range (one list: every posting is a doc of its own)
 };
 
+// Work item of k_rscore (ns_row_kernel.hip; "shared top rows"): a thin item whose hot list is not streamed.  `row` names the
+// row of the batch's row buffer that holds the best kRowLen postings of the hot list — term `dterm` of the group — over
+// exactly this item's doc range, written by the producer item of the same number earlier in the batch.
+struct DevRItem {
+    DevWItem it;
+    uint32_t row;
+    uint32_t dterm;
+};
+static constexpr uint32_t kRowLen = 64;   // entries per row: one per lane
+
 // Term group == the (query, segment) unit the boundary prepass works on.
 struct DevGroup {
     uint64_t bounds_off;

@@ -12,6 +12,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/nextsearch_hip.h"
@@ -53,6 +54,11 @@ static constexpr uint64_t kWorkForeign = 8, kWorkTile = 2, kWorkMerge = 4;   // 
 static constexpr uint32_t kSkipMinCount = 64;   // shorter lists are never looked up in the skip registry (ns_segment_build_skips)
 // per-item, per-term constants of the launch-order key (fitted to per-item timestamps, tools/dbg/item_times.py)
 static constexpr uint64_t kItemTermGeneral = 4000, kItemTermThin = 3000, kItemTermTile = 8000;   // general re-fitted in round 2 (10000 -> 4000: ab16)
+// Shared top rows (ns_ctx_share_rows; BatchPlan::cut "shared top rows"): a hot list gets rows when at least kRowMinUsers
+// thin groups of the batch name it with the same idf and weight; its doc space is cut into the smallest power-of-two
+// number of cells that leaves at most kRowCellPostings of its postings per cell on average.
+static constexpr uint32_t kRowMinUsers = 4, kRowCellPostings = 65536;
+static constexpr uint32_t kRowMaxTerms = 16;   // k_rscore has the 16-entry term tables only
 
 inline std::string vformat(const char* fmt, va_list ap) {
     char buf[512];
@@ -186,6 +192,12 @@ struct PlanSettings {
     bool order_coarse_forced = false;   // NS_ORDER_COARSE given: no automatic choice
     uint32_t key_pct[4] = {100, 100, 100, 100};   // launch-order key of general / thin / tile / merge items in per cent (NS_KEY_PCT=g,t,d,m: sweeps)
     uint32_t tile_dens64 = 16;   // doc-tile class from this many postings per 64 docs (0.25 per doc); NS_TILE_DENS64 overrides (sweeps)
+    // Shared top rows (ns_ctx_share_rows): 0 off; 1 thin groups whose hot list is named by at least row_min_users of them
+    // take the list's top row per cell instead of streaming it; 2 every thin group that can (tests).  A ctx starts with 1
+    // (ns_ctx_create; NS_SHARE_ROWS, NS_ROW_MIN_USERS and NS_ROW_CELL override the three for sweeps and tests).
+    int row_mode = 0;
+    uint32_t row_min_users = kRowMinUsers;
+    uint32_t row_cell_postings = kRowCellPostings;
 };
 
 // A batch's device block is laid out in 256-byte aligned arrays: the offset of the next one of `bytes` bytes
@@ -201,7 +213,23 @@ inline size_t place_at(size_t& off, size_t bytes) {
 // caller's buffer in launch order.  Between the phases only prefix sums over the slices run serially.  Every result
 // (descriptor bytes, launch order) is independent of the number of threads.
 
-struct HostGroup { DevGroup g; uint32_t query; uint64_t cost; uint64_t cmax; uint64_t work; bool wave; uint8_t cls; bool fast_div; bool signed_in; bool grid; bool merge2; };
+struct HostGroup { DevGroup g; uint32_t query; uint64_t cost; uint64_t cmax; uint64_t work; bool wave; uint8_t cls; bool fast_div; bool signed_in; bool grid; bool merge2;
+                   uint32_t rkey1; };   // shared top rows: 0, or 1 + the group's entry in BatchPlan::rkeys (its items are consumers)
+
+// Shared top rows: a hot list as its users score it — the list, its idf and its weight, bit for bit
+struct RowKey {
+    uint32_t seg, first, count, idf_bits, w_bits;
+    bool operator==(const RowKey& o) const { return seg == o.seg && first == o.first && count == o.count && idf_bits == o.idf_bits && w_bits == o.w_bits; }
+};
+struct RowKeyHash {
+    size_t operator()(const RowKey& k) const {
+        uint64_t h = ((uint64_t)k.seg << 32 | k.first) * 0x9E3779B97F4A7C15ull;
+        h ^= ((uint64_t)k.idf_bits << 32 | k.w_bits) * 0xC2B2AE3D27D4EB4Full;
+        return (size_t)(h ^ (h >> 29));
+    }
+};
+struct RowKeyEnt { RowKey key; uint32_t users, skip, cells, prod_begin, rank; bool on; };
+struct RowCand { uint32_t group, dterm, skip, key; };   // a thin group that could take rows: its hot term and that list's skip table
 
 constexpr uint32_t kOrderBuckets = 2048;   // launch-order key: 6 bits of exponent x 5 bits of mantissa of the estimated run time
 inline uint32_t order_bucket(uint64_t c) {  // descending: bucket 0 holds the longest items
@@ -217,6 +245,7 @@ struct PrepSlice {
     std::vector<HostGroup> groups;
     std::vector<uint32_t> qgroup_begin;   // q1 - q0 + 1 entries, local group indices
     std::vector<uint32_t> seg_ids;
+    std::vector<RowCand> rcand;           // shared top rows: the slice's candidate groups, in group order
     uint64_t bounds_total = 0, postings_total = 0, total_work = 0;
     bool all_imp = true, all_pk = true, any_pruned = false;
     int err_code = NS_OK;
@@ -226,25 +255,27 @@ struct PrepSlice {
     std::vector<DevWItem> witems;
     std::vector<uint16_t> wbucket;        // launch-order bucket of each wave item; bit 15: > 16 terms (the "wide" instantiation)
     std::vector<uint32_t> wshare;         // locality key of the item: segment (6 bits) | doc range on the 4096-grid (12) | hash of its largest list (14) -> XCD dealing
+    std::vector<DevRItem> ritems;         // shared top rows: consumer items (their own launch) ...
+    std::vector<uint16_t> rbucket;        // ... and their launch-order buckets
     std::vector<DevItem> items;
     std::vector<uint64_t> item_cost;
     std::vector<DevGroup> bgroups;
     uint32_t n_rows = 0;
     bool direct = true;
-    std::vector<uint32_t> hist;           // [2][kOrderBuckets]: narrow, wide
+    std::vector<uint32_t> hist;           // [3][kOrderBuckets]: narrow, wide, row consumers
     // offsets handed down by the serial steps
     uint32_t term_off = 0, row_off = 0, bgroup_off = 0;
     uint64_t bounds_off = 0;
-    std::vector<uint32_t> start;          // [2][kOrderBuckets]: this slice's first position in each bucket of the sorted item array
+    std::vector<uint32_t> start;          // [3][kOrderBuckets]: this slice's first position in each bucket of the sorted item array (row consumers: of theirs)
     void reset(uint32_t a, uint32_t b) {
         q0 = a; q1 = b;
-        dterms.clear(); groups.clear(); qgroup_begin.clear(); seg_ids.clear();
+        dterms.clear(); groups.clear(); qgroup_begin.clear(); seg_ids.clear(); rcand.clear();
         bounds_total = postings_total = total_work = 0; all_imp = true; all_pk = true; any_pruned = false;
         err_code = NS_OK; err_query = 0xFFFFFFFFu; err_msg.clear();
-        witems.clear(); wbucket.clear(); wshare.clear(); items.clear(); item_cost.clear(); bgroups.clear();
+        witems.clear(); wbucket.clear(); wshare.clear(); ritems.clear(); rbucket.clear(); items.clear(); item_cost.clear(); bgroups.clear();
         n_rows = 0; direct = true;
-        hist.assign(2 * kOrderBuckets, 0u);
-        start.assign(2 * kOrderBuckets, 0u);
+        hist.assign(3 * kOrderBuckets, 0u);
+        start.assign(3 * kOrderBuckets, 0u);
         term_off = row_off = bgroup_off = 0; bounds_off = 0;
     }
     void fail_at(uint32_t q, int code, const char* fmt, ...) {
@@ -274,7 +305,13 @@ struct BatchPlan {
     std::vector<DevShare> share_build;
     uint64_t share_postings = 0;
     std::vector<uint32_t> wide_q;       // queries cut into many partial rows: joined by k_merge_wide, one workgroup each
-    struct Layout { size_t items, witems, terms, groups, queries, segs, wideq, share, bytes; } layout{};
+    // shared top rows: consumer items (k_rscore), producer items (single-term items over the cells of the hot lists, one row
+    // of the row buffer each) and the producers' term entries, which follow the batch's own in the term array
+    uint32_t n_ritems = 0, n_pitems = 0, n_pterms = 0;
+    std::vector<RowKeyEnt> rkeys;
+    std::vector<DevWItem> pitems;
+    std::vector<DevTerm> pterms;
+    struct Layout { size_t items, witems, terms, groups, queries, segs, wideq, share, ritems, pitems, rstats, bytes; } layout{};
     bool deal = false;                  // write() deals the coarse classes over the XCDs ...
     uint32_t deal_shift = 0;            // ... classes of 2^deal_shift fine buckets
     std::vector<uint32_t> bucket_pos;   // launch position at which each fine bucket of the narrow half starts (+ the end)
@@ -285,7 +322,7 @@ struct BatchPlan {
     const ns_query_desc* queries = nullptr;
     const ns_term_ref* terms = nullptr;
     uint32_t n_queries = 0, k = 0, flags = 0;
-    bool auto_mode = false, want_imp = false;
+    bool auto_mode = false, want_imp = false, row_try = false;
     // ---- scratch ----
     unsigned width = 1;
     uint32_t G = 0;
@@ -329,6 +366,9 @@ struct BatchPlan {
         if (slices.size() < width) slices.resize(width);
         for (unsigned s = 0; s < width; s++) slices[s].reset((uint32_t)((uint64_t)n_queries * s / width), (uint32_t)((uint64_t)n_queries * (s + 1) / width));
         want_imp = C.use_impacts && auto_mode;
+        // shared top rows: worth looking for candidates only in a batch that may share its term scores, in OR mode, at K <= 32
+        // (the proof at the end of a consumer item needs kRowLen - K spare row entries)
+        row_try = want_imp && C.row_mode != 0 && C.share_mode != 0 && C.use_skips && !(flags & NS_FLAG_AND) && k <= 32;
 
         // ---- phase A: regroup term refs by (query, segment), keeping query-term order inside each group; classify ----
         fork([&](unsigned si) {
@@ -400,6 +440,15 @@ struct BatchPlan {
                         // one is mostly padding and the table path is as good: r8 + r300, 37 : 1, measured 3 % slower with the merge)
                         hg.merge2 = auto_mode && C.use_merge && hg.cls == 0 && hg.g.term_count == 2 && rest * C.merge_ratio >= hg.cmax;
                         if (hg.merge2) hg.work = hg.cmax + rest * kWorkMerge;
+                    }
+                    // shared top rows: a thin group whose hot list (its first largest one) has a skip table is a candidate
+                    if (row_try && hg.wave && hg.cls == 1 && !hg.signed_in && hg.g.term_count <= kRowMaxTerms && hg.cmax >= kSkipMinCount &&
+                        sv.n_docs > 0 && !sv.lists->skip.empty() && !(C.use_pruning && hg.g.term_count == 1)) {
+                        const DevTerm* dt = S.dterms.data() + hg.g.term_begin;
+                        uint32_t d = 0;
+                        while (dt[d].count != hg.cmax) d++;
+                        const uint32_t sk = sv.lists->skip_of((uint32_t)dt[d].list_off, dt[d].count);
+                        if (sk) S.rcand.push_back(RowCand{(uint32_t)S.groups.size(), d, sk, 0u});
                     }
                     if (!hg.wave) {
                         hg.g.bounds_off = S.bounds_total;   // local; the slice's base is added in phase B
@@ -485,6 +534,15 @@ struct BatchPlan {
         return NS_OK;
     }
 
+    // cell i of `cells` (a power of two, at most n_docs / kSkipDocs) of a segment's doc space: the nested grid of the range
+    // cut, on the skip grid
+    static void row_cell(uint32_t n_docs, uint32_t cells, uint32_t i, uint32_t& lo, uint32_t& hi) {
+        lo = (uint32_t)((uint64_t)n_docs * i / cells);
+        hi = (uint32_t)((uint64_t)n_docs * (i + 1) / cells);
+        lo -= lo % kSkipDocs;
+        if (i + 1 < cells) hi -= hi % kSkipDocs;
+    }
+
     int cut() {
         const PlanSettings& C = *cfg;
         const std::vector<SegView>& SV = *segs;
@@ -518,6 +576,58 @@ struct BatchPlan {
         if (G > 0 && G < min_items) chunks_per_group = std::min<uint32_t>((min_items + G - 1) / G, 1024u);   // one query alone: 1024 ranges are plenty
         dq.assign(n_queries, DevQuery{});
 
+        // ---- shared top rows (ns_ctx_share_rows; k_rscore, ns_row_kernel.hip).  A thin group is one hot list H plus tail lists.
+        // A doc that no tail holds scores 0.0f + w * s_H(d): what a single-term query on H gives it, bit for bit, whichever
+        // query asks.  So the batch ranks H once per cell of its doc space (a PRODUCER item: a plain single-term item with
+        // K' = kRowLen whose result row lies in the batch's row buffer), and the thin groups that name H with this idf and this
+        // weight are cut into exactly those cells; their items (CONSUMERS) leave the scoring launch for one of their own, in
+        // which H is looked up by docId for the tails' docs and otherwise taken from the row.  Serial: the users of a key are
+        // counted over the whole batch, keys are numbered in the order the queries name them.
+        rkeys.clear(); pitems.clear(); pterms.clear();
+        n_ritems = n_pitems = n_pterms = 0;
+        if (shared && row_try) {
+            std::unordered_map<RowKey, uint32_t, RowKeyHash> index;
+            for (unsigned s = 0; s < width; s++) {
+                PrepSlice& S = slices[s];
+                for (RowCand& c : S.rcand) {
+                    const DevTerm& t = S.dterms[S.groups[c.group].g.term_begin + c.dterm];
+                    RowKey key{t.seg, (uint32_t)t.list_off, t.count, 0u, 0u};
+                    std::memcpy(&key.idf_bits, &t.idf, 4); std::memcpy(&key.w_bits, &t.weight, 4);
+                    auto ins = index.emplace(key, (uint32_t)rkeys.size());
+                    if (ins.second) rkeys.push_back(RowKeyEnt{key, 0u, c.skip, 0u, 0u, 0u, false});
+                    c.key = ins.first->second;
+                    rkeys[c.key].users++;
+                }
+            }
+            for (RowKeyEnt& e : rkeys) {
+                if (C.row_mode != 2 && e.users < C.row_min_users) continue;
+                const SegView& sg = SV[e.key.seg];
+                // every cell holds at least one cell of the skip grid (the ranges start and end on it)
+                uint32_t cells = 1;
+                while ((uint64_t)cells * std::max<uint32_t>(C.row_cell_postings, 1u) < e.key.count && cells * 2 <= sg.n_docs / kSkipDocs && cells < 4096) cells <<= 1;
+                e.on = true; e.cells = cells; e.prod_begin = n_pitems; e.rank = n_pterms++;
+                DevTerm t{};
+                t.list_off = e.key.first; t.count = e.key.count; t.seg = e.key.seg; t.skip = e.skip;
+                std::memcpy(&t.idf, &e.key.idf_bits, 4); std::memcpy(&t.weight, &e.key.w_bits, 4);
+                pterms.push_back(t);
+                for (uint32_t i = 0; i < cells; i++) {
+                    DevWItem it{};
+                    it.seg = e.key.seg;
+                    it.term_begin = n_dterms + e.rank;
+                    it.term_count = 1;
+                    row_cell(sg.n_docs, cells, i, it.doc_lo, it.doc_hi);
+                    it.out_slot = n_pitems++;
+                    it.whole = (cells == 1 ? 1u : 0u) | 4u | 64u;   // thin body (no foreign list at all), range ends from the skip table
+                    pitems.push_back(it);
+                }
+            }
+            for (unsigned s = 0; s < width; s++) {
+                PrepSlice& S = slices[s];
+                for (const RowCand& c : S.rcand)
+                    if (rkeys[c.key].on) S.groups[c.group].rkey1 = c.key + 1u;
+            }
+        }
+
         // ---- phase B: cut the groups into work items (rows numbered inside the slice) ----
         fork([&](unsigned si) {
             PrepSlice& S = slices[si];
@@ -550,11 +660,14 @@ struct BatchPlan {
                             if (k > 32 && p2 < 8) p2 = 8;
                             ns = std::min<uint32_t>(p2, std::min<uint32_t>(sg.n_docs, 4096));
                         }
+                        // shared top rows: a consumer group is cut into exactly the cells of its hot list's rows
+                        const RowKeyEnt* rk = hg.rkey1 ? &rkeys[hg.rkey1 - 1u] : nullptr;
+                        if (rk) ns = rk->cells;
                         // Skip tables (ns_segment_build_skips): a doc-tile group walks the grid of its lists' tables; a group of the
                         // driver-stream bodies that is cut into ranges takes the ranges' ends of its frequent lists from their
                         // tables instead of searching for them (the searches of a hot list are a dozen dependent loads: 4-20 % of
                         // an item's time, most in small batches).  Either way the ranges start and end on the grid.
-                        if (auto_mode && C.use_skips && (hg.cls == 2 || ns > 1) && !sg.lists->skip.empty()) {
+                        if (auto_mode && C.use_skips && (hg.cls == 2 || ns > 1 || rk) && !sg.lists->skip.empty()) {
                             for (uint32_t ti = 0; ti < hg.g.term_count; ti++) {
                                 if (dt[ti].count < kSkipMinCount) continue;
                                 dt[ti].skip = sg.lists->skip_of((uint32_t)dt[ti].list_off, dt[ti].count);
@@ -584,6 +697,8 @@ struct BatchPlan {
                         // per CU, larger candidate buffers — so the general items start later there too (cfg3 -2.6 %, at K = 64 -2.3 %)
                         else if (auto_mode && k > 32 && hg.cls == 0) key = key * 3 / 4;
                         if (auto_mode) key = key * C.key_pct[hg.merge2 ? 3 : hg.cls] / 100;   // sweeps (NS_KEY_PCT); 100 each by default
+                        // a consumer pays for its foreign postings and per term; its hot list costs it a look-up per foreign doc
+                        if (rk) key = (hg.cost - hg.cmax) * kWorkForeign / ns + 1 + kItemTermThin * hg.g.term_count;
                         const bool wide = auto_mode && hg.g.term_count > 16;
                         const uint32_t bucket = order_bucket(key);
                         // what the group's items read most of: its largest list (the driver of a driver-stream item)
@@ -602,11 +717,20 @@ struct BatchPlan {
                                 it.doc_lo -= it.doc_lo % kSkipDocs;
                                 if (i + 1 < ns) it.doc_hi -= it.doc_hi % kSkipDocs;
                             }
+                            if (rk) row_cell(sg.n_docs, ns, i, it.doc_lo, it.doc_hi);   // (the same range; spelled by the rule the producers use)
                             if (it.doc_hi <= it.doc_lo) continue;
                             it.out_slot = S.n_rows++;
                             it.whole = (ns == 1 ? 1u : 0u) | (hg.fast_div ? 8u : 0u) | (hg.signed_in ? 16u : 0u) | (hg.grid ? (hg.cls == 2 ? 32u : 64u) : 0u);
                             // auto mode: very dense groups take the doc-tile body (bit 1), groups with thin non-driver lists the small foreign budget (bit 2)
                             if (auto_mode) it.whole |= (hg.cls == 2 ? 2u : 0u) | (hg.cls == 1 ? 4u : 0u) | (pruned_ ? 128u : 0u) | (hg.merge2 && hg.wave ? 256u : 0u);
+                            if (rk) {   // a consumer: k_rscore's, with the row of its cell and the place of the hot list in its term order
+                                uint32_t d = 0;
+                                while (dt[d].count != hg.cmax) d++;
+                                S.ritems.push_back(DevRItem{it, rk->prod_begin + i, d});
+                                S.rbucket.push_back((uint16_t)bucket);
+                                S.hist[2 * kOrderBuckets + bucket]++;
+                                continue;
+                            }
                             S.witems.push_back(it);
                             S.wbucket.push_back((uint16_t)(bucket | (wide ? 0x8000u : 0u)));
                             {
@@ -649,7 +773,7 @@ struct BatchPlan {
         for (unsigned s = 0; s < width; s++) {
             PrepSlice& S = slices[s];
             S.row_off = n_rows; S.bgroup_off = n_bgroups;
-            n_rows += S.n_rows; n_witems += (uint32_t)S.witems.size(); n_items += (uint32_t)S.items.size(); n_bgroups += (uint32_t)S.bgroups.size();
+            n_rows += S.n_rows; n_witems += (uint32_t)S.witems.size(); n_ritems += (uint32_t)S.ritems.size(); n_items += (uint32_t)S.items.size(); n_bgroups += (uint32_t)S.bgroups.size();
             direct = direct && S.direct;
             pruned = pruned || S.any_pruned;
         }
@@ -673,6 +797,14 @@ struct BatchPlan {
             // would be a wild descriptor on the device)
             if (pos != n_witems) return failed(NS_E_STATE, "internal: launch order holds %u of %u work items", pos, n_witems);
             if (!auto_mode) { n_class[0] = n_class[1] = 0; }
+            // the consumers of shared top rows: a launch of their own, longest estimated run time first, ties in query order
+            uint32_t rpos = 0;
+            for (uint32_t bkt = 0; bkt < kOrderBuckets; bkt++)
+                for (unsigned s = 0; s < width; s++) {
+                    slices[s].start[2 * kOrderBuckets + bkt] = rpos;
+                    rpos += slices[s].hist[2 * kOrderBuckets + bkt];
+                }
+            if (rpos != n_ritems) return failed(NS_E_STATE, "internal: launch order holds %u of %u row consumers", rpos, n_ritems);
         }
         // the workgroup-kernel items (fallback path: few): longest first, serially
         sorted_items.clear();
@@ -699,12 +831,15 @@ struct BatchPlan {
         size_t off = 0;
         layout.items = place_at(off, (size_t)n_items * sizeof(DevItem));
         layout.witems = place_at(off, (size_t)n_witems * sizeof(DevWItem));
-        layout.terms = place_at(off, (size_t)n_dterms * sizeof(DevTerm));
+        layout.terms = place_at(off, (size_t)(n_dterms + n_pterms) * sizeof(DevTerm));
         layout.groups = place_at(off, (size_t)n_bgroups * sizeof(DevGroup));
         layout.queries = place_at(off, dq.size() * sizeof(DevQuery));
         layout.segs = place_at(off, SV.size() * sizeof(DevSeg));
         layout.wideq = place_at(off, wide_q.size() * 4);
         layout.share = place_at(off, shared ? (share_build.size() + 1) * sizeof(DevShare) : 0);
+        layout.ritems = n_ritems ? place_at(off, (size_t)n_ritems * sizeof(DevRItem)) : off;   // (a batch without rows keeps its image byte for byte)
+        layout.pitems = n_pitems ? place_at(off, (size_t)n_pitems * sizeof(DevWItem)) : off;
+        layout.rstats = n_pitems ? place_at(off, 8) : off;   // k_rscore's two counters: zero in the image, so zeroed by the upload
         layout.bytes = off;
 
         // The dealing costs host time (a sort per class: +0.2 ms for cfg5's 16384 queries on 8 prepare threads).  A batch small
@@ -734,6 +869,12 @@ struct BatchPlan {
                 const uint32_t at = S.start[((bk & 0x8000u) ? kOrderBuckets : 0) + (bk & 0x7FFFu)]++;
                 wdst[at] = it;
                 if (deal) share_at[at] = S.wshare[i];
+            }
+            DevRItem* rdst = (DevRItem*)(hb + layout.ritems);
+            for (size_t i = 0; i < S.ritems.size(); i++) {
+                DevRItem ri = S.ritems[i];
+                ri.it.out_slot = direct ? ri.it.query : ri.it.out_slot + S.row_off;
+                rdst[S.start[2 * kOrderBuckets + S.rbucket[i]]++] = ri;
             }
             if (!S.dterms.empty()) std::memcpy(hb + layout.terms + (size_t)S.term_off * sizeof(DevTerm), S.dterms.data(), S.dterms.size() * sizeof(DevTerm));
             if (!S.bgroups.empty()) std::memcpy(hb + layout.groups + (size_t)S.bgroup_off * sizeof(DevGroup), S.bgroups.data(), S.bgroups.size() * sizeof(DevGroup));
@@ -795,6 +936,9 @@ struct BatchPlan {
                 }
             });
         }
+        if (n_pterms) std::memcpy(hb + layout.terms + (size_t)n_dterms * sizeof(DevTerm), pterms.data(), (size_t)n_pterms * sizeof(DevTerm));
+        if (n_pitems) std::memcpy(hb + layout.pitems, pitems.data(), (size_t)n_pitems * sizeof(DevWItem));
+        if (n_pitems) std::memset(hb + layout.rstats, 0, 8);
         if (n_items) std::memcpy(hb + layout.items, sorted_items.data(), (size_t)n_items * sizeof(DevItem));
         if (!wide_q.empty()) std::memcpy(hb + layout.wideq, wide_q.data(), wide_q.size() * 4);
         if (shared) {

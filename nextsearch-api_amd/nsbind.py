@@ -65,7 +65,7 @@ HIP_SYMBOLS = [
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
-    "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores",
+    "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores", "ns_ctx_share_rows", "ns_batch_row_stats",
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release", "ns_ac_build_fuzzy", "ns_ac_fuzzy", "ns_ac_fuzzy_prefix",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
@@ -194,6 +194,9 @@ def hip_lib():
         L.ns_ctx_use_pruning.argtypes = [vp, i32]
         L.ns_ctx_use_merge.argtypes = [vp, i32]
         L.ns_ctx_share_scores.argtypes = [vp, i32]
+        if hasattr(L, "ns_ctx_share_rows"):   # (an A/B run may load a library from before shared top rows: NS_HIP_LIB)
+            L.ns_ctx_share_rows.argtypes = [vp, i32]
+            L.ns_batch_row_stats.argtypes = [vp, vp]
         L.ns_sem_upload.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
         L.ns_sem_release.argtypes = [vp, vp]
         L.ns_sem_topk.argtypes = [vp, vp, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp]
@@ -485,6 +488,15 @@ class Batch:
         inf = NsBatchInfo()
         hip_lib().ns_batch_get_info(self.h, C.byref(inf))
         return inf
+
+    def row_stats(self):
+        """(producer items, consumer items, fallbacks, row-table hits) of the batch's shared top rows (ns_batch_row_stats);
+        the last two are sums over its runs so far, which this waits for."""
+        out = np.zeros(4, dtype=np.uint32)
+        rc = hip_lib().ns_batch_row_stats(self.h, out.ctypes.data)
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_batch_row_stats failed rc={rc}")
+        return tuple(int(x) for x in out)
 
     def close(self):
         if self.h:

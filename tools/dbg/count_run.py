@@ -19,7 +19,9 @@ names = ["items (driver-stream body)", "super-batches", "super-batches with fore
 # the table's rare paths (indices 20 .. 27 of ns_debug_counters), the merge body and the candidate buffer
 rare = {20: "pass-A lanes with a full bucket (pos >= 4)", 21: "pass-A chunks that continue the previous chunk's bucket (carry)",
         22: "claim-loop moves to the next bucket", 23: "... of which wrap to bucket 0", 24: "claim-loop lanes that found an owner",
-        25: "super-batches without a primary term (wmax < 8)", 26: "super-batches on the T > 8 branch", 27: "span clamps"}
+        25: "super-batches without a primary term (wmax < 8)", 26: "super-batches on the T > 8 branch", 27: "span clamps",
+        19: "row consumer items (k_rscore)", 28: "row consumer: look-ups of an owner's doc in the hot list", 29: "... that found it",
+        30: "row consumer: row entries that probed the table", 31: "... that hit it"}
 mnames = ["items (merge body)", "steps", "steps with hi from A's round", "steps with hi from B's window", "steps with hi = end of range",
           "steps with a_rem == 0", "steps with b_rem == 0", "B windows of 1 chunk", "B windows of 2 chunks", "B windows of 3 chunks",
           "B windows of 4 chunks", "docs in both lists"]
