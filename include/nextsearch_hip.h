@@ -221,7 +221,8 @@ int ns_ctx_use_merge(ns_ctx* ctx, int on);
  * batch to the next and nothing outlives the run: this is common-subexpression elimination inside one batch, with the
  * reference's operations in the reference's order, and hits, order, nhits, found and score bits are identical (tests run
  * both ways).  mode 1 (default): a batch shares when it scans >= 4 Mi postings and names each distinct posting >= 48 times on
- * average (measured break-even on MI355X: the extra kernel costs ~6 ps per distinct posting, sharing saves ~0.12 ps per use); mode 2: every batch that can (tests); mode 0: never.  A batch never shares when a list of it overlaps another
+ * average (measured break-even on MI355X: the extra kernel costs ~6 ps per distinct posting, sharing saves ~0.12 ps per use); mode 2: every batch that can (tests); mode 0: never.  A batch never shares when all its segments carry packed
+ * streams that it reads (ns_ctx_use_packed 1 or 2), when every list of it has a registered impact stream (it reads those), when a list of it overlaps another
  * list ever shared in the segment, when a segment of it carries an optional impact stream that lacks one of its lists, or
  * when a list's idf differs from the one a live sharing batch uses; it then scores every posting in place, as with mode 0.
  * ns_batch_info reports NS_INFO_SHARED, shared_lists and shared_postings; sum_score_kernel_ms covers both kernels. */
@@ -237,7 +238,11 @@ int ns_ctx_share_scores(ns_ctx* ctx, int mode);
  * 64 - K of the row's docs are docs of the tails, and the row does not hold the whole cell) is scored once more by the
  * streaming body, inside the same launch.  Hits, order, nhits, found and score bits are identical either way.
  * Eligible: OR mode, K <= 32, at most 16 term refs, no negative idf or weight, H has a skip table.  mode 1 (default): H gets
- * rows when at least 4 eligible groups of the batch name it; mode 2: always (tests); mode 0: never. */
+ * rows when at least 4 eligible groups of the batch name it; mode 2: always (tests); mode 0: never.
+ * Only a batch that shares its term scores takes rows: one that reads packed blocks (ns_ctx_use_packed) or registered impact
+ * streams (ns_segment_build_impacts, complete or not) does not share and takes none.  Under ns_ctx_use_pruning(1) a group of
+ * one list is no user of H and takes no row (where H has block maxima the block-max body scores it).  H with one idf under two weights is two
+ * keys, each with users and rows of its own; the same list offsets in two segments are two keys as well. */
 int ns_ctx_share_rows(ns_ctx* ctx, int mode);
 /* out: producer items (rows) and consumer items of the batch as prepared, then, summed over the batch's runs so far (waits
  * for them): consumer items that fell back to the streaming body, row entries that were docs of a tail. */

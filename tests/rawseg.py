@@ -11,17 +11,23 @@ import numpy as np
 import nsbind
 
 
+def np_contrib(docs, tfs, idf, w, doc_len, avgdl):
+    """one list's contributions  w * ((idf * (tf * 2.2f)) / (tf + norm))  per posting, every operation rounded to fp32"""
+    f = np.float32
+    dl = doc_len[docs].astype(np.float32)
+    norm = f(1.2) * ((f(1.0) - f(0.75)) + f(0.75) * (dl / f(avgdl)))
+    tf = tfs.astype(np.float32)
+    s = (f(idf) * (tf * (f(1.2) + f(1.0)))) / (tf + norm)
+    return f(w) * s
+
+
 def _np_bm25(seg_lists, refs_idx, idfs, weights, doc_len, avgdl):
     """fp32 restatement of src/api_engine.cpp:477-480 in numpy (every operation rounds to fp32)."""
     f = np.float32
     acc = {}
     for li, idf, w in zip(refs_idx, idfs, weights):
         docs, tfs = seg_lists[li]
-        dl = doc_len[docs].astype(np.float32)
-        norm = f(1.2) * ((f(1.0) - f(0.75)) + f(0.75) * (dl / f(avgdl)))
-        tf = tfs.astype(np.float32)
-        s = (f(idf) * (tf * (f(1.2) + f(1.0)))) / (tf + norm)
-        x = f(w) * s
+        x = np_contrib(docs, tfs, idf, w, doc_len, avgdl)
         for d, v in zip(docs.tolist(), x.tolist()):
             acc[d] = f(acc.get(d, f(0.0)) + f(v))
     return acc
@@ -80,11 +86,17 @@ class RawSegment:
         bo, cn = np.ascontiguousarray(self.offs[which]), np.ascontiguousarray(self.counts[which])
         assert self.L.ns_segment_build_skips(self.ctx, self.seg, bo.ctypes.data, cn.ctypes.data, len(which)) == 0, self.err()
 
-    def build_impacts(self, idfs):
-        which = np.flatnonzero(self.counts > 0)
+    def build_impacts(self, idfs, leave_out=()):
+        which = np.array([i for i in np.flatnonzero(self.counts > 0) if i not in leave_out], dtype=np.int64)
         bo, cn = np.ascontiguousarray(self.offs[which]), np.ascontiguousarray(self.counts[which])
         fi = np.array([idfs[i] for i in which], dtype=np.float32)
         assert self.L.ns_segment_build_impacts(self.ctx, self.seg, bo.ctypes.data, cn.ctypes.data, fi.ctypes.data, len(which)) == 0, self.err()
+
+    def build_blockmax(self, idfs, which):
+        which = np.asarray(which, dtype=np.int64)
+        bo, cn = np.ascontiguousarray(self.offs[which]), np.ascontiguousarray(self.counts[which])
+        fi = np.array([idfs[i] for i in which], dtype=np.float32)
+        assert self.L.ns_segment_build_blockmax(self.ctx, self.seg, bo.ctypes.data, cn.ctypes.data, fi.ctypes.data, len(which)) == 0, self.err()
 
     def build_packed(self):
         assert self.L.ns_segment_build_packed(self.ctx, self.seg) == 0, self.err()
@@ -185,6 +197,13 @@ class RawSegments:
         return self.L.ns_last_error(self.ctx)
 
     run = RawSegment.run
+
+    def build_skips(self, sid, min_count=64, leave_out=()):
+        """skip tables for segment sid's lists of at least min_count postings, except the list numbers in leave_out"""
+        counts = np.array([len(d) for d, _ in self.lists[sid]], dtype=np.uint32)
+        which = np.array([i for i in np.flatnonzero(counts >= min_count) if i not in leave_out], dtype=np.int64)
+        bo, cn = np.ascontiguousarray(self.offs[sid][which]), np.ascontiguousarray(counts[which])
+        assert self.L.ns_segment_build_skips(self.ctx, self.segs[sid], bo.ctypes.data, cn.ctypes.data, len(which)) == 0, self.err()
 
     def release(self):
         if self.ctx:
