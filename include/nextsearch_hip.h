@@ -646,6 +646,40 @@ int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_quer
  * since the last reset: out2[0..1], milliseconds; reset != 0 zeroes the sums after the read.  For tools/boolean_bench.py. */
 int ns_boolean_kernel_ms(float* out2, int reset);
 
+/* ---- pages past the first K (csrc/ns_after_plan.hpp, csrc/ns_after.hip) -------- */
+/* A cursor is a position in the total order of a ranked call, not an offset:
+ *   ns_search_boolean_after   (ord(score bits) descending, position of the segment in the call's list ascending, docId
+ *                             ascending); rank = the fp32 score bits, compared through the kernels' monotone map (negative:
+ *                             ~bits, else bits | 0x80000000), so -0.0f is legal, equals no score and sorts just below +0.0f,
+ *                             and NaN bits sort as ns_search_boolean says
+ *   ns_search_sorted_after    (t descending, position ascending, docId ascending), t = key, or key ? ~key : 0 under
+ *                             NS_SORT_ASC; rank = the key as uploaded, the direction is the call's flags
+ * seg_id is an id the call lists (its position orders), doc_id any value.  The cursor need not be a matched document, or a
+ * document at all.  set == 0: no cursor, the other fields are ignored. */
+typedef struct ns_cursor {
+    uint32_t rank, seg_id, doc_id, set;
+} ns_cursor;
+/* ns_search_boolean / ns_search_sorted with one cursor per query (after[n_queries]; NULL = none): the first K documents of the
+ * matched set that come STRICTLY AFTER the cursor, scores bit for bit those of the call without one.
+ *   found_out[q]  unchanged by a cursor: the size of the matched set.
+ *   rest_out[q]   (may be NULL) the number of matched documents strictly after the cursor; nhits_out[q] = min(K, rest); without
+ *                 a cursor rest = found.  found - rest is the offset of the page; rest > nhits means there is a next page.
+ * Handing the last hit of a page back as the cursor walks the matched set once: nothing repeats, nothing is skipped.  With
+ * after == NULL, or every cursor unset, the call is the one without cursors: the same kernels, the same outputs.
+ * NS_E_INVAL as the calls without cursors, and, with a message, nothing launched and the output arrays untouched: set > 1, a
+ * set cursor whose seg_id the call does not list, for ns_search_sorted_after a set cursor with rank 0xFFFFFFFF.
+ * ns_boolean_kernel_ms / ns_sorted_kernel_ms sum these calls' launches too. */
+int ns_search_boolean_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                            const uint8_t* roles /* n_terms; NULL = all SHOULD */, uint32_t n_terms, uint32_t k,
+                            const ns_cursor* after /* n_queries; NULL = none */, const uint32_t* seg_ids, ns_seg* const* segs,
+                            uint32_t n_segs, ns_hit* hits_out /* Q x K */, uint32_t* nhits_out, uint64_t* found_out /* may be NULL */,
+                            uint64_t* rest_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+int ns_search_sorted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                           uint32_t k, uint32_t flags, const ns_cursor* after /* n_queries; NULL = none */, const uint32_t* seg_ids,
+                           ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out /* Q x K */,
+                           uint32_t* keys_out /* Q x K */, uint32_t* nhits_out, uint64_t* found_out /* may be NULL */,
+                           uint64_t* rest_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -419,6 +419,40 @@ int nsh_engine_search_boolean_batch(nsh_engine* e, uint32_t filter_handle, const
 int nsh_engine_search_boolean_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
                                    int keep_undated, char** json_out);
 
+/* ---- pages past the first K (host/page.hpp) ----
+ * A cursor is a position (rank, manifest position of the segment, docId) in the total order of a ranked call: rank = the fp32
+ * score bits in score order (kind 's'), the sort key as uploaded in date order (kind 'd').  A call with a cursor answers with
+ * the first K matched documents strictly after it.  set == 0: no cursor.  A cursor is good until a reload changes the index. */
+typedef struct nsh_page_cursor {
+    uint32_t set, rank, seg, doc;
+} nsh_page_cursor;
+/* nsx::parse_cursor (host only, no engine): the text form is the kind letter, 8 lowercase hex digits of rank, '.', the position
+ * in decimal, '.', the docId in decimal, e.g. s41a3c28f.0.5121; the empty string is the unset cursor; anything else, or a
+ * cursor of another kind than `kind` ('s' or 'd'), fails with -1 and a message in err (NUL-terminated, truncated to err_cap). */
+int nsh_parse_cursor(const char* text, int kind, nsh_page_cursor* out, char* err, uint32_t err_cap);
+/* nsx::cursor_text: the text form into buf (NUL-terminated, truncated to cap); returns its length, 0 for an unset cursor. */
+uint32_t nsh_cursor_text(int kind, const nsh_page_cursor* c, char* buf, uint32_t cap);
+/* Engine::search_after_batch_flat / search_boolean_after_batch_flat / search_sorted_after_batch_flat: nsh_engine_search_batch
+ * (nsh_engine_search_filtered_batch under a handle), nsh_engine_search_boolean_batch and nsh_engine_search_sorted_batch with one
+ * cursor per query (after: n_queries, or NULL for none).  found is unchanged by a cursor; rest[q] (may be NULL) = the matched
+ * documents strictly after the cursor, nhits[q] = min(K, rest[q]); without a cursor rest = found.  A cursor whose position is
+ * outside the index, or of which the filter keeps nothing, is refused: -1 and nsh_engine_error. */
+int nsh_engine_search_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
+                                  const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found,
+                                  float* device_ms_out);
+int nsh_engine_search_boolean_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                          const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* has_found, float* device_ms_out);
+int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                         uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out,
+                                         uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_page: *json_out (free with nsh_free) = the mode's body (0 search OR, 1 search AND, 2 boolean, 3 sorted by spec;
+ * search_filtered's with use_filter != 0) over one page, plus "page": {"cursor", "next", "offset", "remaining"}; "next" is
+ * present only when documents remain.  cursor: "" or NULL for the first page, else a page's "next".  On failure -1 and
+ * {"error": ...}. */
+int nsh_engine_search_page_json(nsh_engine* e, const char* query, int k, const char* cursor, uint32_t mode, const nsh_sort_spec* spec, int use_filter,
+                                const char* date_from, const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2880,6 +2880,11 @@ extern "C" int ns_dockeys_release(ns_ctx* ctx, ns_dockeys* table) {
     return NS_OK;
 }
 
+static int sd_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                     uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys,
+                     uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
+                     float* device_ms_out);
+
 extern "C" int ns_sorted_kernel_ms(float* out3, int reset) {
     if (!out3) return NS_E_INVAL;
     for (int i = 0; i < 3; i++) out3[i] = g_sd_ms[i];
@@ -2887,10 +2892,57 @@ extern "C" int ns_sorted_kernel_ms(float* out3, int reset) {
     return NS_OK;
 }
 
+// Pages past the first K (csrc/ns_after_plan.hpp, csrc/ns_after.hip): the cursors of one call -> last[item].
+// rank_of maps a cursor's rank as the caller gives it to the rank the kernel's keys carry.  False, with `err` set, for a
+// cursor the call refuses.  any_set: at least one query has a cursor (otherwise `last` stays empty and the AFTER = false
+// kernels run).
+template <class RankOf>
+static bool after_plan(const ns_cursor* after, uint32_t n_queries, const std::vector<FcSegView>& views, const std::vector<FcItem>& items,
+                       RankOf rank_of, bool reserved_rank, std::vector<uint64_t>& last, bool& any_set, std::string& err) {
+    last.clear();
+    any_set = false;
+    if (!after) return true;
+    std::vector<uint32_t> pos_of(n_queries, 0u);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        const ns_cursor& c = after[q];
+        if (c.set > 1u) { err = fc_format("query %u: cursor with set = %u (0 or 1)", q, c.set); return false; }
+        if (!c.set) continue;
+        if (reserved_rank && c.rank == 0xFFFFFFFFu) { err = fc_format("query %u: cursor with the reserved key 0xFFFFFFFF", q); return false; }
+        uint32_t pos = 0;
+        while (pos < views.size() && views[pos].seg_id != c.seg_id) pos++;
+        if (pos == views.size()) { err = fc_format("query %u: cursor names segment %u, which the call does not list", q, c.seg_id); return false; }
+        pos_of[q] = pos;
+        any_set = true;
+    }
+    if (!any_set) return true;
+    last.resize(items.size());
+    for (size_t i = 0; i < items.size(); i++) {
+        const FcItem& it = items[i];
+        const ns_cursor& c = after[it.query];
+        last[i] = c.set ? after_last(rank_of(c.rank), pos_of[it.query], c.doc_id, it.seg, it.doc_lo, it.doc_hi) : kAfterAll;
+    }
+    return true;
+}
+
 extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
                                 uint32_t k, uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
                                 ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
-    const char* fn = "ns_search_sorted";
+    return sd_search(ctx, "ns_search_sorted", queries, n_queries, terms, n_terms, k, flags, nullptr, seg_ids, segs, keys, n_segs, hits_out, keys_out, nhits_out,
+                     found_out, nullptr, device_ms_out);
+}
+
+extern "C" int ns_search_sorted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                                      uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs,
+                                      ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out,
+                                      uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    return sd_search(ctx, "ns_search_sorted_after", queries, n_queries, terms, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out, keys_out,
+                     nhits_out, found_out, rest_out, device_ms_out);
+}
+
+static int sd_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
+                     uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys,
+                     uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
+                     float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
     if (n_queries == 0) return NS_OK;
@@ -2928,6 +2980,10 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
     if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
     if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
     if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
+    bool paged = false;
+    if (!after_plan(after, n_queries, views, items, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, last, paged, why))
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     uint64_t cand_rows = 0;
     for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
     const size_t n_out = (size_t)n_queries * K;
@@ -2935,6 +2991,7 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     size_t off = 0;
+    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
     const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(FcRef)),
                  o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_sds = place_at(off, sds.size() * sizeof(DevSdSeg)),
                  o_qoff = place_at(off, q_off.size() * 4), o_qd = place_at(off, (size_t)n_queries * sizeof(ns_query_desc)),
@@ -2958,6 +3015,10 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
         chk(hipMemcpyAsync(blk + o_qd, queries, (size_t)n_queries * sizeof(ns_query_desc), hipMemcpyHostToDevice, st));
         if (n_terms) chk(hipMemcpyAsync(blk + o_terms, terms, (size_t)n_terms * sizeof(ns_term_ref), hipMemcpyHostToDevice, st));
         chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
+        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
+        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
+        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
+        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
         const FcItem* d_items = (const FcItem*)(blk + o_items);
         const DevFcSeg* d_segs = (const DevFcSeg*)(blk + o_segs);
         const DevSdSeg* d_sds = (const DevSdSeg*)(blk + o_sds);
@@ -2967,10 +3028,16 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
             const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
             chk(hipEventRecord(evs[c * 4 + 0], st));
             if (n_it) {
-                if (and_mode)
-                    hipLaunchKernelGGL(k_sd_select<true>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, (const FcRef*)(blk + o_refs), d_segs, d_sds, K, asc, d_cand, (unsigned long long*)(blk + o_found));
+                const FcRef* d_refs = (const FcRef*)(blk + o_refs);
+                unsigned long long* d_found = (unsigned long long*)(blk + o_found);
+                if (paged && and_mode)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                    hipLaunchKernelGGL((k_sd_select<true, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
+                else if (paged)
+                    hipLaunchKernelGGL((k_sd_select<false, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
+                else if (and_mode)
+                    hipLaunchKernelGGL((k_sd_select<true, false>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
                 else
-                    hipLaunchKernelGGL(k_sd_select<false>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, (const FcRef*)(blk + o_refs), d_segs, d_sds, K, asc, d_cand, (unsigned long long*)(blk + o_found));
+                    hipLaunchKernelGGL((k_sd_select<false, false>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
                 chk(hipGetLastError());
             }
             chk(hipEventRecord(evs[c * 4 + 1], st));
@@ -2988,6 +3055,7 @@ extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint3
         chk(hipMemcpyAsync(keys_out, blk + o_keys, n_out * 4, hipMemcpyDeviceToHost, st));
         chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
         if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
+        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
         chk(hipStreamSynchronize(st));
         if (e == hipSuccess) {
             float sum = 0.0f;
@@ -3026,10 +3094,28 @@ extern "C" int ns_boolean_kernel_ms(float* out2, int reset) {
     return NS_OK;
 }
 
+static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                     uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
+
 extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                  uint32_t n_terms, uint32_t k, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                                  uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
-    const char* fn = "ns_search_boolean";
+    return bq_search(ctx, "ns_search_boolean", queries, n_queries, terms, roles, n_terms, k, nullptr, seg_ids, segs, n_segs, hits_out, nhits_out, found_out,
+                     nullptr, device_ms_out);
+}
+
+extern "C" int ns_search_boolean_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                       uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs,
+                                       uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
+                                       float* device_ms_out) {
+    return bq_search(ctx, "ns_search_boolean_after", queries, n_queries, terms, roles, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+                     found_out, rest_out, device_ms_out);
+}
+
+static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                     uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (n_queries == 0) { if (device_ms_out) *device_ms_out = 0.0f; return NS_OK; }
     if (!queries || !hits_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
@@ -3061,6 +3147,10 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
     if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
     if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
     if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
+    bool paged = false;
+    if (!after_plan(after, n_queries, views, items, [](uint32_t bits) { return after_ord(bits); }, false, last, paged, why))
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (device_ms_out) *device_ms_out = 0.0f;
     uint64_t cand_rows = 0;
     for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
@@ -3070,6 +3160,7 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     size_t off = 0;
+    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
     const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
                  o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_bqs = place_at(off, bqs.size() * sizeof(DevBqSeg)),
                  o_qoff = place_at(off, q_off.size() * 4), o_hits = place_at(off, n_out * sizeof(ns_hit)),
@@ -3081,7 +3172,9 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
 #if defined(NS_VARIANTS) || defined(NS_COUNT)
-    if (lds > (48u << 10)) chk(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bq_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > (48u << 10))
+        chk(hipFuncSetAttribute(paged ? reinterpret_cast<const void*>(k_bq_select<true>) : reinterpret_cast<const void*>(k_bq_select<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #endif
     chk(pool_alloc(ctx, (void**)&blk, block_bytes));
     for (auto& ev : evs) chk(hipEventCreate(&ev));
@@ -3092,6 +3185,10 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
         chk(hipMemcpyAsync(blk + o_bqs, bqs.data(), bqs.size() * sizeof(DevBqSeg), hipMemcpyHostToDevice, st));
         chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
         chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
+        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
+        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
+        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
+        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
         const FcItem* d_items = (const FcItem*)(blk + o_items);
         const DevBqSeg* d_bqs = (const DevBqSeg*)(blk + o_bqs);
         uint64_t* d_cand = (uint64_t*)(blk + o_cand);
@@ -3100,8 +3197,12 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
             const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
             chk(hipEventRecord(evs[c * 3 + 0], st));
             if (n_it) {
-                hipLaunchKernelGGL(k_bq_select, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
-                                   d_cand, (unsigned long long*)(blk + o_found));
+                if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                    hipLaunchKernelGGL(k_bq_select<true>, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
+                                       d_cand, (unsigned long long*)(blk + o_found), d_last + b.item_begin, d_rest);
+                else
+                    hipLaunchKernelGGL(k_bq_select<false>, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
+                                       d_cand, (unsigned long long*)(blk + o_found), (const uint64_t*)nullptr, (unsigned long long*)nullptr);
                 chk(hipGetLastError());
             }
             chk(hipEventRecord(evs[c * 3 + 1], st));
@@ -3113,6 +3214,7 @@ extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint
         chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
         chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
         if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
+        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
         chk(hipStreamSynchronize(st));
         if (e == hipSuccess) {
             float sum = 0.0f;
@@ -3808,6 +3910,15 @@ extern "C" int ns_debug_sorted_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_scnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_scnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the cursor bound in k_sd_select<., true> and k_bq_select<true> (ns_after.hip): 5 values
+extern "C" int ns_debug_after_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsAcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_acnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_acnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 // the boolean search's paths (ns_boolean.hip k_bq_select, k_bq_join): 8 values

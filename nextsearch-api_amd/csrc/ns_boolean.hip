@@ -79,9 +79,14 @@ __device__ __forceinline__ void bq_insert(SdSet& s, uint64_t key, uint32_t K, ui
 // accumulators, then three bitmaps of win / 8 B, then the item's matched count.
 __host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (size_t)win * 4u + 3u * (size_t)(win / 8u) + 16u; }
 
+// AFTER (§5s, ns_after.hip): last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
+// rest[query] through the word behind s_cnt.  With AFTER = false neither pointer is read and the code is what it was without
+// the parameter.
+template <bool AFTER>
 __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
-                                                   uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found) {
+                                                   uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
+                                                   const uint64_t* __restrict__ last_of, unsigned long long* __restrict__ rest) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     uint64_t (*s_rows)[128] = reinterpret_cast<uint64_t (*)[128]>(s_raw);
     float* s_acc = reinterpret_cast<float*>(s_raw + 4096u);
@@ -89,6 +94,7 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     uint32_t* s_tmp = s_bm + win / 32u;
     uint32_t* s_ex = s_tmp + win / 32u;
     uint32_t& s_cnt = s_ex[win / 32u];
+    uint32_t& s_rest = s_ex[win / 32u + 1u];   // (inside bq_lds_bytes' last 16 bytes)
     const FcItem it = items[blockIdx.x];
     const DevFcSeg sg = segs[it.seg];
     const float* __restrict__ norm = bqs[it.seg].norm;
@@ -96,6 +102,13 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     const uint32_t tid = threadIdx.x, lane = tid & 63u, v = tid >> 6;
     NS_BCNT(0, 1);
     if (tid == 0) s_cnt = 0u;
+    uint64_t last = kAfterAll;
+    uint32_t kept = 0;
+    if (AFTER) {
+        last = last_of[blockIdx.x];
+        if (tid == 0) s_rest = 0u;
+        af_count_item(last);
+    }
     uint32_t n_must = 0, n_not = 0;   // the same in every thread: they depend on the item alone
     for (uint32_t r = 0; r < it.ref_count; r++) {
         const uint32_t role = rf[r].role;
@@ -204,17 +217,20 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
                     bits &= bits - 1u;
                     key = ((uint64_t)bq_ord(__float_as_uint(s_acc[rel])) << 32) | (uint32_t)~(tile_rel + rel);
                 }
+                if (AFTER) key = af_clip(key, last, kept);
                 bq_insert(set, key, K, lane);
             }
         }
     }
     __syncthreads();   // (s_cnt is zero; nobody reads the accumulators any more)
     if (cnt) atomicAdd(&s_cnt, cnt);
+    if (AFTER && kept) atomicAdd(&s_rest, kept);
     s_rows[v][lane] = set.hi;
     s_rows[v][64u + lane] = set.lo;
     __syncthreads();
     if (v != 0u) return;
     if (tid == 0 && s_cnt) atomicAdd(&found[it.query], (unsigned long long)s_cnt);
+    if (AFTER && tid == 0 && s_rest) atomicAdd(&rest[it.query], (unsigned long long)s_rest);
 #pragma unroll 1
     for (uint32_t o = 1; o < 4u; o++) {
         bq_insert(set, s_rows[o][lane], K, lane);

@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "ns_sorted_plan.hpp"
+#include "ns_after.hip"
 
 namespace ns {
 
@@ -84,10 +85,14 @@ __device__ __forceinline__ void sd_insert(SdSet& s, uint64_t key, uint32_t K, ui
     }
 }
 
-template <bool AND>
+// AFTER (§5s, ns_after.hip): last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
+// rest[query].  Wave 0's own slot of s_rows is never read back, so under AFTER it is not written and its first word holds the
+// item's count instead.  With AFTER = false neither pointer is read and the code is what it was without the parameter.
+template <bool AND, bool AFTER>
 __global__ void __launch_bounds__(256) k_sd_select(const FcItem* __restrict__ items, const FcRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevSdSeg* __restrict__ sds, uint32_t K,
-                                                   uint32_t asc, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found) {
+                                                   uint32_t asc, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
+                                                   const uint64_t* __restrict__ last_of, unsigned long long* __restrict__ rest) {
     __shared__ uint32_t s_bm[kFcTileDocs / 32u];
     __shared__ uint32_t s_and[AND ? kFcTileDocs / 32u : 1u];
     __shared__ uint64_t s_rows[4][128];
@@ -99,6 +104,14 @@ __global__ void __launch_bounds__(256) k_sd_select(const FcItem* __restrict__ it
     const uint32_t n_words = (it.doc_hi - it.doc_lo + 31u) / 32u;   // <= kFcTileDocs / 32: the tile is the host's, at most the product's
     NS_SCNT(0, 1);
     if (tid == 0) s_cnt = 0u;
+    uint32_t* const s_rest = reinterpret_cast<uint32_t*>(&s_rows[0][0]);
+    uint64_t last = kAfterAll;
+    uint32_t kept = 0;
+    if (AFTER) {
+        last = last_of[blockIdx.x];
+        if (tid == 0) *s_rest = 0u;
+        af_count_item(last);
+    }
     SdSet set{0ull, 0ull};
     uint32_t cnt = 0;
     if (it.ref_count == 1u) {
@@ -112,6 +125,7 @@ __global__ void __launch_bounds__(256) k_sd_select(const FcItem* __restrict__ it
                 const uint32_t d = sg.postings[i].x;
                 if (d >= it.doc_lo && d < it.doc_hi) { cnt++; key = sd_key(keys[d], d - it.doc_lo, asc != 0u); }
             }
+            if (AFTER) key = af_clip(key, last, kept);
             sd_insert(set, key, K, lane);
         }
     } else {
@@ -156,17 +170,22 @@ __global__ void __launch_bounds__(256) k_sd_select(const FcItem* __restrict__ it
                         bits &= bits - 1u;
                         key = sd_key(keys[it.doc_lo + rel], rel, asc != 0u);
                     }
+                    if (AFTER) key = af_clip(key, last, kept);
                     sd_insert(set, key, K, lane);
                 }
             }
     }
     __syncthreads();   // (s_cnt is zero)
     if (cnt) atomicAdd(&s_cnt, cnt);
-    s_rows[v][lane] = set.hi;
-    s_rows[v][64u + lane] = set.lo;
+    if (AFTER && kept) atomicAdd(s_rest, kept);
+    if (!AFTER || v != 0u) {
+        s_rows[v][lane] = set.hi;
+        s_rows[v][64u + lane] = set.lo;
+    }
     __syncthreads();
     if (v != 0u) return;
     if (tid == 0 && s_cnt) atomicAdd(&found[it.query], (unsigned long long)s_cnt);
+    if (AFTER && tid == 0 && *s_rest) atomicAdd(&rest[it.query], (unsigned long long)*s_rest);
 #pragma unroll 1
     for (uint32_t o = 1; o < 4u; o++) {
         sd_insert(set, s_rows[o][lane], K, lane);

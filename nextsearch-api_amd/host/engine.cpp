@@ -2226,15 +2226,55 @@ bool Engine::ensure_sorted(const nsx::SortSpec& spec, SortSet*& out) {
 
 bool Engine::search_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
                                       ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint8_t* usable, float* device_ms) {
+    return sorted_batch_impl("search_sorted_batch_flat", spec, filter_handle, queries, Q, k, flags, nullptr, hits, keys, nhits, found, nullptr, usable, device_ms);
+}
+
+bool Engine::search_sorted_after_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                            uint8_t* usable, float* device_ms) {
+    return sorted_batch_impl("search_sorted_after_batch_flat", spec, filter_handle, queries, Q, k, flags, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+// Pages past the first K (host/page.hpp): the cursors of queries [a, b), which name manifest positions, as the
+// call's ns_cursors, which name the ids the refs use (under a filter: the filter copies').  listed[s]: position s is in the
+// call's segment list.
+bool Engine::translate_cursors(const char* fn, const nsx::PageCursor* after, size_t a, size_t b, uint32_t id_base, const std::vector<uint8_t>& listed,
+                               bool filtered, std::vector<ns_cursor>& out) {
+    out.clear();
+    if (!after) return true;
+    bool any = false;
+    for (size_t q = a; q < b; q++) any = any || after[q].set;
+    if (!any) return true;
+    out.assign(b - a, ns_cursor{0u, 0u, 0u, 0u});
+    for (size_t q = a; q < b; q++) {
+        const nsx::PageCursor& c = after[q];
+        if (!c.set) continue;
+        if (c.seg >= listed.size()) {
+            err_ = std::string(fn) + ": the cursor of query " + std::to_string(q) + " names position " + std::to_string(c.seg) + ", the index has " + std::to_string(listed.size()) + " segments";
+            return false;
+        }
+        if (!listed[c.seg]) {
+            err_ = std::string(fn) + ": the cursor of query " + std::to_string(q) + " names position " + std::to_string(c.seg) +
+                   (filtered ? ", of which the filter keeps nothing" : ", which has no copy on the device");
+            return false;
+        }
+        out[q - a] = ns_cursor{c.rank, id_base + c.seg, c.doc, 1u};
+    }
+    return true;
+}
+
+bool Engine::sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                               const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                               float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
-    if (!ctx_) { err_ = "search_sorted_batch_flat: no device context: the sorted search runs on the device, there is no CPU path"; return false; }
-    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = "search_sorted_batch_flat: null argument"; return false; }
-    if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = "search_sorted_batch_flat: flags are NS_FLAG_OR or NS_FLAG_AND; the direction is the spec's"; return false; }
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = std::string(fn) + ": flags are NS_FLAG_OR or NS_FLAG_AND; the direction is the spec's"; return false; }
     OpenFilter* f = nullptr;
     if (filter_handle) {
         f = filter_of(filter_handle);
-        if (!f) { err_ = "search_sorted_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
     }
     SortSet* ss = nullptr;
     if (!ensure_sorted(spec, ss)) return false;
@@ -2254,26 +2294,31 @@ bool Engine::search_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter
     std::vector<uint32_t> ids;
     std::vector<ns_seg*> segs;
     std::vector<ns_dockeys*> tabs;
+    std::vector<uint8_t> listed(S, 0);
     for (uint32_t s = 0; s < S; s++) {
         ns_seg* h = f ? f->segs[s] : dev_segs_[s];
         if (!h || !ss->dev[s]) continue;
+        listed[s] = 1;
         ids.push_back(rs.id_base + s);
         segs.push_back(h);
         tabs.push_back(ss->dev[s]);
     }
+    std::vector<ns_cursor> cur;
     const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
     auto run = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
+        if (!translate_cursors(fn, after, a, b, rs.id_base, listed, f != nullptr, cur)) return false;
         if (ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
+            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
             std::fill(nhits + a, nhits + b, 0u);
             std::fill(hits + a * K, hits + b * K, pad);
             std::fill(keys + a * K, keys + b * K, 0u);
             return true;
         }
         float ms = 0.0f;
-        const int rc = ns_search_sorted(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, (uint32_t)K, call_flags, ids.data(), segs.data(), tabs.data(),
-                                        (uint32_t)ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, &ms);
-        if (rc != NS_OK) { err_ = std::string("ns_search_sorted: ") + ns_last_error(ctx_); return false; }
+        const int rc = ns_search_sorted_after(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, (uint32_t)K, call_flags, cur.empty() ? nullptr : cur.data(), ids.data(),
+                                              segs.data(), tabs.data(), (uint32_t)ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string(after ? "ns_search_sorted_after: " : "ns_search_sorted: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t i = 0; i < nhits[q]; i++) hits[q * K + i].seg_id -= rs.id_base;   // manifest positions
@@ -2353,14 +2398,24 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
 // ---- boolean queries (host/boolean.hpp, csrc/ns_boolean.hip) -------------------------------------------
 bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
                                        uint64_t* found, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl("search_boolean_batch_flat", filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
+}
+
+bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                             uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl("search_boolean_after_batch_flat", filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
-    if (!ctx_) { err_ = "search_boolean_batch_flat: no device context: boolean queries run on the device, there is no CPU path"; return false; }
-    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = "search_boolean_batch_flat: null argument"; return false; }
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
     OpenFilter* f = nullptr;
     if (filter_handle) {
         f = filter_of(filter_handle);
-        if (!f) { err_ = "search_boolean_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
     }
     if (Q == 0) return true;
     const size_t K = (size_t)std::max(1, std::min(k, 100));
@@ -2375,9 +2430,12 @@ bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* 
     // the segments the refs can name, in manifest order: the index's own, or the filter's copies
     std::vector<uint32_t> ids, listed;
     std::vector<ns_seg*> segs;
+    std::vector<uint8_t> is_listed(S, 0);
+    std::vector<ns_cursor> cur;
     for (uint32_t s = 0; s < S; s++) {
         ns_seg* h = f ? f->segs[s] : dev_segs_[s];
         if (!h) continue;
+        is_listed[s] = 1;
         listed.push_back(s);
         ids.push_back(rs.id_base + s);
         segs.push_back(h);
@@ -2418,16 +2476,19 @@ bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* 
                 }
             qd[q - a].term_count = (uint32_t)refs.size() - qd[q - a].term_begin;
         }
+        if (!translate_cursors(fn, after, a, b, rs.id_base, is_listed, f != nullptr, cur)) return false;
         if (ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
+            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
             std::fill(nhits + a, nhits + b, 0u);
             std::fill(hits + a * K, hits + b * K, pad);
             continue;
         }
         float ms = 0.0f;
-        const int rc = ns_search_boolean(ctx_, qd.data(), (uint32_t)(b - a), refs.data(), roles.data(), (uint32_t)refs.size(), (uint32_t)K, ids.data(), segs.data(),
-                                         (uint32_t)ids.size(), hits + a * K, nhits + a, found + a, &ms);
-        if (rc != NS_OK) { err_ = std::string("ns_search_boolean: ") + ns_last_error(ctx_); return false; }
+        const int rc = ns_search_boolean_after(ctx_, qd.data(), (uint32_t)(b - a), refs.data(), roles.data(), (uint32_t)refs.size(), (uint32_t)K,
+                                               cur.empty() ? nullptr : cur.data(), ids.data(), segs.data(), (uint32_t)ids.size(), hits + a * K, nhits + a, found + a,
+                                               rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string(after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= rs.id_base;   // manifest positions
@@ -2487,6 +2548,198 @@ bool Engine::search_boolean_text(const std::string& query, int k, const nsx::Doc
 std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
     std::string body;
     if (!search_boolean_text(query, k, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- pages past the first K (host/page.hpp, csrc/ns_after_plan.hpp) -------------------------------------
+// The search's own query preparation, then ns_search_boolean_after: roles == NULL is the OR search bit for bit, every role
+// MUST the AND search, so page 1 is search_batch_flat's answer and page n continues it.
+bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags, const nsx::PageCursor* after,
+                                     ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    const char* fn = "search_after_batch_flat";
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: pages are cut on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = std::string(fn) + ": flags are NS_FLAG_OR or NS_FLAG_AND"; return false; }
+    OpenFilter* f = nullptr;
+    if (filter_handle) {
+        f = filter_of(filter_handle);
+        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    }
+    if (Q == 0) return true;
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const uint32_t S = (uint32_t)segments.size();
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
+    nsx::RowSource rs;
+    if (f) {   // search_filtered_batch_flat's row source
+        rs.rows = f->rows.data();
+        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
+        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+        if (!rs.rows) rs.rows = &no_rows;
+    }
+    std::vector<uint32_t> ids;
+    std::vector<ns_seg*> segs;
+    std::vector<uint8_t> listed(S, 0);
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
+        if (!h) continue;
+        listed[s] = 1;
+        ids.push_back(rs.id_base + s);
+        segs.push_back(h);
+    }
+    std::vector<ns_cursor> cur;
+    std::vector<uint8_t> roles;
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    auto run = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
+        if (!translate_cursors(fn, after, a, b, rs.id_base, listed, f != nullptr, cur)) return false;
+        if (ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
+            std::fill(nhits + a, nhits + b, 0u);
+            std::fill(hits + a * K, hits + b * K, pad);
+            return true;
+        }
+        if (and_mode) roles.assign(n_refs, nsx::kRoleMust);
+        float ms = 0.0f;
+        const int rc = ns_search_boolean_after(ctx_, qd, (uint32_t)(b - a), refs, and_mode ? roles.data() : nullptr, (uint32_t)n_refs, (uint32_t)K,
+                                               cur.empty() ? nullptr : cur.data(), ids.data(), segs.data(), (uint32_t)ids.size(), hits + a * K, nhits + a, found + a,
+                                               rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_search_boolean_after: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        for (size_t q = a; q < b; q++)
+            for (uint32_t i = 0; i < nhits[q]; i++) hits[q * K + i].seg_id -= rs.id_base;   // manifest positions
+        return true;
+    };
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
+        std::vector<std::string> qs(Q);
+        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
+        std::vector<nsx::WeightedTerms> expanded;
+        if (!expand_queries(qs, expanded)) return false;
+        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
+        std::vector<ns_term_ref> refs;
+        std::vector<uint8_t> us(Q, 0);
+        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
+        std::memcpy(usable, us.data(), Q);
+        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
+            if (!run(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
+        return true;
+    }
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
+        if (!run(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
+    }
+    return true;
+}
+
+bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::Sorted) { body = err_ = "search_page: unknown mode"; return false; }
+    const char kind = nsx::page_kind(spec.mode);
+    nsx::PageCursor cur;
+    if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
+    const int K = std::max(1, std::min(k, 100));
+    uint32_t handle = 0;
+    std::string head = "{\n";
+    if (spec.use_filter) {   // search_filtered's filter (cached, most recently used in front) and its "filter" member
+        std::string ignored;
+        if (!search_filtered_text(std::string(), K, spec.filter, ignored)) { body = err_; return false; }
+        handle = filter_lru_.front().handle;
+        const size_t at = ignored.find("\n  },\n");
+        if (ignored.compare(0, 14, "{\n  \"filter\": ") != 0 || at == std::string::npos) { body = err_ = "search_page: the filtered body has no filter member"; return false; }
+        head = ignored.substr(0, at + 6);
+    }
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits((size_t)K);
+    std::vector<uint32_t> keys((size_t)K, 0u);
+    uint32_t nh = 0;
+    uint64_t fd = 0, rs = 0;
+    uint8_t us = 0;
+    bool ok = false;
+    switch (spec.mode) {
+        case nsx::PageSpec::SearchOr:
+        case nsx::PageSpec::SearchAnd:
+            ok = search_after_batch_flat(handle, &qv, 1, K, spec.mode == nsx::PageSpec::SearchAnd ? NS_FLAG_AND : NS_FLAG_OR, &cur, hits.data(), &nh, &fd, &rs, &us);
+            break;
+        case nsx::PageSpec::Boolean:
+            ok = search_boolean_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
+            break;
+        case nsx::PageSpec::Sorted:
+            ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
+            break;
+    }
+    if (!ok) { body = err_; return false; }
+    SearchResult res;
+    res.query = query;
+    res.k = K;
+    res.segments = (int)segments.size();
+    res.has_found = us != 0;
+    res.found = fd;
+    if (!res.has_found) { nh = 0; rs = 0; fd = 0; }
+    for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    std::string o = "{\n";
+    if (spec.mode == nsx::PageSpec::Boolean) {   // search_boolean's "boolean" member
+        const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
+        o += "  \"boolean\": {\n";
+        static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
+        for (int m = 0; m < 3; m++) {
+            o += std::string("    \"") + kMembers[m].name + "\": [";
+            bool any = false;
+            for (const nsx::BoolTerm& t : terms)
+                if (t.role == kMembers[m].role) {
+                    o += any ? ",\n      " : "\n      ";
+                    json_escape(o, t.text);
+                    any = true;
+                }
+            o += any ? "\n    ]" : "]";
+            o += m < 2 ? ",\n" : "\n";
+        }
+        o += "  },\n";
+    }
+    o += head.substr(2);
+    std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
+    // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
+    const size_t at = rest_of.find("  \"query\": ");
+    if (at == std::string::npos || (at != 0 && rest_of[at - 1] != '\n')) { body = err_ = "search_page: the search body has no query member"; return false; }
+    std::string page = "  \"page\": {\n    \"cursor\": ";
+    json_escape(page, cursor_text);
+    if (rs > nh && nh > 0) {
+        nsx::PageCursor next;
+        next.set = true;
+        uint32_t score_bits = 0;
+        std::memcpy(&score_bits, &hits[nh - 1].score, 4);
+        next.rank = spec.mode == nsx::PageSpec::Sorted ? keys[nh - 1] : score_bits;
+        next.seg = hits[nh - 1].seg_id;
+        next.doc = hits[nh - 1].doc_id;
+        page += ",\n    \"next\": ";
+        json_escape(page, nsx::cursor_text(kind, next));
+    }
+    page += ",\n    \"offset\": " + std::to_string(fd - rs);
+    page += ",\n    \"remaining\": " + std::to_string(rs - nh) + "\n  },\n";
+    rest_of.insert(at, page);
+    o += rest_of;
+    if (spec.mode == nsx::PageSpec::Sorted) {   // search_sorted's "sort" member behind "segments"
+        o.resize(o.size() - 2);                 // the closing "\n}"
+        o += ",\n  \"sort\": ";
+        json_escape(o, nsx::sort_name(spec.sort));
+        o += "\n}";
+    }
+    body = std::move(o);
+    return true;
+}
+
+std::string Engine::search_page(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec) {
+    std::string body;
+    if (!search_page_text(query, k, cursor_text, spec, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";

@@ -38,6 +38,7 @@
 #include "facet.hpp"
 #include "sorted.hpp"
 #include "boolean.hpp"
+#include "page.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
 #include "../csrc/ns_forkjoin.hpp"
@@ -348,6 +349,30 @@ public:
     std::string search_boolean(const std::string& query, int k, const nsx::DocFilter* f = nullptr);
     bool search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
 
+    // Pages past the first K (host/page.hpp).  A cursor is a position (rank, manifest position, docId) in a call's
+    // total order; with one, a call answers with the first K matched documents STRICTLY AFTER it: found[q] stays the size of
+    // the matched set, rest[q] (may be nullptr) is the number of matched documents after the cursor, nhits[q] = min(K, rest[q]).
+    // after: one cursor per query, or nullptr (then, and with every cursor unset, the calls are their siblings without one).
+    // The engine translates the position to the call's segment id (the filter copy's under a filter handle); a position
+    // outside the index, or one the call lists no segment for, is refused with a message.  A cursor is good until a reload()
+    // changes the index.
+    // search_after_batch_flat is search_batch_flat's query preparation (search_filtered_batch_flat's under a handle) over the
+    // boolean kernels: page 1 equals search_batch_flat bit for bit, page n continues it.
+    bool search_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags, const nsx::PageCursor* after,
+                                 ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+    bool search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                         uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+    bool search_sorted_after_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                                        const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                        uint8_t* usable, float* device_ms = nullptr);
+    // JSON text: the mode's body (search's, search_filtered's with spec.use_filter, search_boolean's, search_sorted's) over one
+    // page, plus "page": {"cursor", "next", "offset", "remaining"}; "next" only when documents remain after this page; offset
+    // = found - rest, remaining = rest - nhits; dump(2) layout.  cursor_text: "" for the first page, else a page's "next"; its
+    // kind letter must fit the mode.  The search cache is not used.  Any failure: {"error": ...} (search_page_text: false,
+    // body = the message).
+    std::string search_page(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec);
+    bool search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body);
+
     std::string to_json(const SearchResult& r) const;
     std::string to_json_impl(const SearchResult& r) const;
     // A batch of searches straight to the /api/search JSON bodies (result assembly on several host threads).
@@ -419,6 +444,13 @@ private:
     OpenFilter filters_[kMaxFilters];
     uint32_t filter_gen_ = 0;
     OpenFilter* filter_of(uint32_t handle);
+    bool translate_cursors(const char* fn, const nsx::PageCursor* after, size_t a, size_t b, uint32_t id_base, const std::vector<uint8_t>& listed,
+                           bool filtered, std::vector<ns_cursor>& out);
+    bool sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                           const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                           float* device_ms);
+    bool boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };

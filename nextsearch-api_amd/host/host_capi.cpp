@@ -1120,3 +1120,125 @@ extern "C" int nsh_engine_search_boolean_json(nsh_engine* e, const char* query, 
     return ok ? 0 : -1;
 } NSH_CATCH(e, "nsh_engine_search_boolean_json", -1)
 }
+
+// ---- pages past the first K (host/page.hpp) ----
+extern "C" int nsh_parse_cursor(const char* text, int kind, nsh_page_cursor* out, char* err, uint32_t err_cap) { try {
+    if (err && err_cap) err[0] = 0;
+    if (!out) return -1;
+    nsx::PageCursor c;
+    std::string why;
+    const bool ok = nsx::parse_cursor(text ? text : "", (char)kind, c, why);
+    *out = nsh_page_cursor{c.set ? 1u : 0u, c.rank, c.seg, c.doc};
+    if (!ok && err && err_cap) {
+        const size_t n = std::min<size_t>(why.size(), err_cap - 1);
+        std::memcpy(err, why.data(), n);
+        err[n] = 0;
+    }
+    return ok ? 0 : -1;
+} NSH_CATCH(nullptr, "nsh_parse_cursor", -1)
+}
+
+extern "C" uint32_t nsh_cursor_text(int kind, const nsh_page_cursor* c, char* buf, uint32_t cap) { try {
+    if (buf && cap) buf[0] = 0;
+    if (!c) return 0;
+    nsx::PageCursor pc;
+    pc.set = c->set != 0; pc.rank = c->rank; pc.seg = c->seg; pc.doc = c->doc;
+    const std::string t = nsx::cursor_text((char)kind, pc);
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(t.size(), cap - 1);
+        std::memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return (uint32_t)t.size();
+} NSH_CATCH(nullptr, "nsh_cursor_text", 0)
+}
+
+static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<nsx::PageCursor>& out) {
+    out.clear();
+    if (!in) return;
+    out.resize(n);
+    for (uint32_t q = 0; q < n; q++) { out[q].set = in[q].set != 0; out[q].rank = in[q].rank; out[q].seg = in[q].seg; out[q].doc = in[q].doc; }
+}
+
+// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted
+static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                           uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                           uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
+    if (!e) return -1;
+    nsx::SortSpec sp;
+    std::string why;
+    if (mode == 3 && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !nhits || (mode == 3 && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<nsx::PageCursor> cur;
+    nsh_cursors_of(after, n_queries, cur);
+    const nsx::PageCursor* cp = after ? cur.data() : nullptr;
+    std::vector<uint64_t> f_, r_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!rest) { r_.resize(n_queries); rest = r_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    bool ok;
+    if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 2) ok = e->eng.search_boolean_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    else ok = e->eng.search_after_batch_flat(filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = rest[q] = 0;
+    return 0;
+}
+
+extern "C" int nsh_engine_search_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
+                                             const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found,
+                                             float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_after_batch", (flags & NS_FLAG_AND) ? 1 : 0, nullptr, filter_handle, queries, n_queries, k, flags, after, hits, nullptr,
+                           nhits, found, rest, has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_after_batch", -1)
+}
+
+extern "C" int nsh_engine_search_boolean_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                                     const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                                     uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_boolean_after_batch", 2, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_boolean_after_batch", -1)
+}
+
+extern "C" int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                                    uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out,
+                                                    uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_sorted_after_batch", 3, spec, filter_handle, queries, n_queries, k, flags, after, hits, keys_out, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_sorted_after_batch", -1)
+}
+
+extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int k, const char* cursor, uint32_t mode, const nsh_sort_spec* spec, int use_filter,
+                                           const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::PageSpec ps;
+    bool ok = mode <= 3u;
+    if (!ok) s = "search_page: unknown mode " + std::to_string(mode);
+    if (ok) {
+        ps.mode = (nsx::PageSpec::Mode)mode;
+        if (mode == 3u) ok = nsh_sort_spec_of(e, spec, ps.sort, s);
+    }
+    if (ok) {
+        ps.use_filter = use_filter != 0;
+        if (ps.use_filter) ps.filter = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_page_text(query ? query : "", k, cursor ? cursor : "", ps, s);
+    }
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_page_json", -1)
+}

@@ -24,6 +24,9 @@
 //   ns_tool search-boolean <index_dir> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean: `+word` must be held, `-word` must not, other words are optional (boolean.hpp); search's JSON
 //        body plus "boolean".  from / to as search-filtered's; "-" "-" searches the whole index.
+//   ns_tool page <index_dir> <or|and|boolean|newest|oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
+//        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
+//        "remaining"} (page.hpp).  cursor: "-" for the first page, else a page's "next".  from / to as search-filtered's.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
 //        times the C++ facade from INSIDE the process (no ctypes, no Python): query preparation alone (tokenise,
 //        dictionary probes, idf: src/api_engine.cpp:388-397,:454-461) and Engine::search_batch_flat, query TEXT in ->
@@ -132,6 +135,28 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
         if (!eng.search_boolean_text(q, k, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 9 && std::strcmp(argv[1], "page") == 0) {
+        nsx::PageSpec spec;
+        if (std::strcmp(argv[3], "or") == 0) spec.mode = nsx::PageSpec::SearchOr;
+        else if (std::strcmp(argv[3], "and") == 0) spec.mode = nsx::PageSpec::SearchAnd;
+        else if (std::strcmp(argv[3], "boolean") == 0) spec.mode = nsx::PageSpec::Boolean;
+        else if (std::strcmp(argv[3], "newest") == 0) { spec.mode = nsx::PageSpec::Sorted; spec.sort.ascending = false; }
+        else if (std::strcmp(argv[3], "oldest") == 0) { spec.mode = nsx::PageSpec::Sorted; spec.sort.ascending = true; }
+        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest or oldest, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        spec.use_filter = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) spec.filter.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) spec.filter.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        const std::string cursor = std::strcmp(argv[7], "-") != 0 ? argv[7] : "";
+        std::string q, body;
+        for (int i = 8; i < argc; i++) { if (i > 8) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_page_text(q, k, cursor, spec, body)) { std::fprintf(stderr, "page failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

@@ -55,12 +55,15 @@ QDESC_DTYPE = np.dtype([("term_begin", "<u4"), ("term_count", "<u4")])
 assert HIT_DTYPE.itemsize == C.sizeof(NsHit) == 12
 assert TERM_DTYPE.itemsize == C.sizeof(NsTermRef) == 24
 assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
+PAGE_CURSOR_DTYPE = np.dtype([("set", "<u4"), ("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4")])   # nsh_page_cursor: seg is a manifest position
+PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3}
+CURSOR_DTYPE = np.dtype([("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4"), ("set", "<u4")])   # ns_cursor
 
 # every symbol include/nextsearch_hip.h declares
 HIP_SYMBOLS = [
     "ns_facet_upload", "ns_facet_release", "ns_facet_count", "ns_facet_tile_docs",
     "ns_dockeys_upload", "ns_dockeys_release", "ns_search_sorted", "ns_sorted_kernel_ms",
-    "ns_search_boolean", "ns_boolean_kernel_ms",
+    "ns_search_boolean", "ns_boolean_kernel_ms", "ns_search_boolean_after", "ns_search_sorted_after",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -75,6 +78,8 @@ HIP_SYMBOLS = [
 ]
 HOST_SYMBOLS = [
     "nsh_parse_boolean", "nsh_engine_search_boolean_batch", "nsh_engine_search_boolean_json",
+    "nsh_parse_cursor", "nsh_cursor_text", "nsh_engine_search_after_batch", "nsh_engine_search_boolean_after_batch", "nsh_engine_search_sorted_after_batch",
+    "nsh_engine_search_page_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
     "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
@@ -244,6 +249,8 @@ def hip_lib():
         L.ns_sorted_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         L.ns_search_boolean.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_boolean_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        L.ns_search_boolean_after.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_search_sorted_after.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -254,7 +261,7 @@ def hip_lib():
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
-                  "ns_debug_boolean_counters": 8}
+                  "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5}
 
 
 def debug_counters(reset=False):
@@ -417,6 +424,14 @@ def host_lib():
         L.nsh_parse_boolean.restype = u32
         L.nsh_engine_search_boolean_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.nsh_engine_search_boolean_json.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_parse_cursor.argtypes = [C.c_char_p, i32, vp, C.c_char_p, u32]
+        L.nsh_cursor_text.argtypes = [i32, vp, C.c_char_p, u32]
+        L.nsh_cursor_text.restype = u32
+        L.nsh_engine_search_after_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_boolean_after_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_sorted_after_batch.argtypes = [vp, C.POINTER(NshSortSpec), u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp, vp, vp, vp,
+                                                           C.POINTER(C.c_float)]
+        L.nsh_engine_search_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, u32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         _host = L
     return _host
 
@@ -955,6 +970,70 @@ class Engine:
             self._L.nsh_free(out)
         if rc != 0 and check:
             raise RuntimeError(f"search_boolean failed: {self.error()}")
+        return body
+
+    # ---- pages past the first K ----
+    def search_after_batch(self, queries, k, after=None, flags=NS_FLAG_OR, handle=0, timing=False):
+        """Engine::search_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); after: None, or per query None |
+        (rank = score bits, manifest position, docId).  Without a cursor it is search_batch (search_filtered_batch under a
+        handle) bit for bit."""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), int(flags), cu.ctypes.data if cu is not None and Q else None,
+                                                   hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_boolean_after_batch(self, queries, k, after=None, handle=0, timing=False):
+        """Engine::search_boolean_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); after as search_after_batch's"""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_boolean_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
+                                                           hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_boolean_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_sorted_after_batch(self, queries, k, after=None, order="newest", flags=NS_FLAG_OR, handle=0, custom=None, timing=False):
+        """Engine::search_sorted_after_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); after: None, or per
+        query None | (rank = the sort key, manifest position, docId)"""
+        sp, keep = self._sort_spec(order, custom)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_sorted_after_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k), int(flags),
+                                                          cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data, nhits.ctypes.data,
+                                                          found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_sorted_after_batch failed: {self.error()}")
+        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_page_json(self, query, k, cursor="", mode="or", order="newest", date_filter=None, custom=None, check=True):
+        """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" (then order / custom as
+        search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
+        sp, keep = self._sort_spec(order, custom)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_page_json(self.h, _as_bytes(query), k, _as_bytes(cursor), PAGE_MODES[mode], C.byref(sp), int(date_filter is not None),
+                                                 _as_bytes(df), _as_bytes(dt), int(bool(ku)), C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_page failed: {self.error()}")
         return body
 
     def release_sorted(self):
@@ -1765,6 +1844,95 @@ def search_boolean_raw(ctx, qd, refs, roles, k, seg_ids, segs):
                                      ids.ctypes.data if len(ids) else None, sa, len(ids), hits.ctypes.data, nhits.ctypes.data,
                                      found.ctypes.data, C.byref(ms))
     return rc, hits[:Q], nhits[:Q], found[:Q], float(ms.value)
+
+
+def page_cursors(rows):
+    """[None | (rank, manifest position, doc)] per query -> an nsh_page_cursor array"""
+    a = np.zeros(max(len(rows), 1), dtype=PAGE_CURSOR_DTYPE)
+    for i, c in enumerate(rows):
+        if c is not None:
+            a[i] = (1, int(c[0]) & 0xFFFFFFFF, int(c[1]), int(c[2]))
+    return a
+
+
+def parse_cursor(text, kind="s"):
+    """nsx::parse_cursor (host only): None for the empty string, else (rank, manifest position, doc); ValueError with the
+    parser's message for anything else"""
+    c = np.zeros(1, dtype=PAGE_CURSOR_DTYPE)
+    err = C.create_string_buffer(256)
+    if host_lib().nsh_parse_cursor(_as_bytes(text), ord(kind), c.ctypes.data, err, 256) != 0:
+        raise ValueError(err.value.decode())
+    return (int(c[0]["rank"]), int(c[0]["seg"]), int(c[0]["doc"])) if c[0]["set"] else None
+
+
+def cursor_text(cursor, kind="s"):
+    """nsx::cursor_text (host only): None -> "", (rank, manifest position, doc) -> its text form"""
+    c = page_cursors([cursor])
+    buf = C.create_string_buffer(64)
+    host_lib().nsh_cursor_text(ord(kind), c.ctypes.data, buf, 64)
+    return buf.value.decode()
+
+
+def cursors(rows):
+    """[None | (rank, seg_id, doc)] per query -> an ns_cursor array"""
+    a = np.zeros(len(rows), dtype=CURSOR_DTYPE)
+    for i, c in enumerate(rows):
+        if c is not None:
+            a[i] = (int(c[0]) & 0xFFFFFFFF, int(c[1]), int(c[2]), 1)
+    return a
+
+
+def search_boolean_after_raw(ctx, qd, refs, roles, k, after, seg_ids, segs):
+    """ns_search_boolean_after (raw): (rc, hits Q x K, nhits, found, rest, device ms); after: None or a CURSOR_DTYPE array, one
+    per query; the rest as search_boolean_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_boolean_after(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                           ro.ctypes.data if ro is not None and len(ro) else None, len(refs), int(k),
+                                           cu.ctypes.data if cu is not None and len(cu) else None,
+                                           ids.ctypes.data if len(ids) else None, sa, len(ids), hits.ctypes.data, nhits.ctypes.data,
+                                           found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+def search_sorted_after_raw(ctx, qd, refs, k, flags, after, seg_ids, segs, tables):
+    """ns_search_sorted_after (raw): (rc, hits Q x K, keys Q x K, nhits, found, rest, device ms); after: None or a CURSOR_DTYPE
+    array (rank = the key as uploaded); the rest as search_sorted_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    keys = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_sorted_after(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None, len(refs), int(k), int(flags),
+                                          cu.ctypes.data if cu is not None and len(cu) else None,
+                                          ids.ctypes.data if len(ids) else None, sa, ta, len(ids), hits.ctypes.data, keys.ctypes.data,
+                                          nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+def after_counters(reset=True):
+    """ns_debug_after_counters of the counting build as {name: value}; None for a library without them"""
+    c = debug_counters(reset=reset).get("ns_debug_after_counters")
+    return None if c is None else dict(zip(AFTER_EVENTS, c))
+
+
+AFTER_EVENTS = ["bounded_items", "bound_in_tile", "bound_zero", "keys_dropped", "keys_passed"]
 
 
 def boolean_kernel_ms(reset=True):
