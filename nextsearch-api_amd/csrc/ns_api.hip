@@ -3930,4 +3930,13 @@ extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) {
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
+// the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values
+extern "C" int ns_debug_fuzzy_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsZcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_zcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_zcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
 #endif

@@ -42,6 +42,27 @@ constexpr uint32_t kFzIdxMask = (1u << kFzIdxBits) - 1;
 constexpr int kFzQueue = 128;                  // per wave: signature survivors waiting for the DP
 constexpr int kFzKeep = 128;                   // per wave: DP survivors waiting for a reduction
 
+#ifdef NS_COUNT
+// Counting build only: events of the fuzzy kernels since the last reset (ns_debug_fuzzy_counters; tests/fuzzy_shapes.py names
+// them).  0 candidates given to the signature test, 1 of those rejected, 2 DP calls on a full wave of the queue, 3 of those
+// that left entries waiting, 4 DP calls on the queue's remainder, 5 DP waves that left the row loop early, 6 DP rows in which
+// a lane was past the bound while another kept the wave going, 7 fz_load4 lanes that funnelled two dwords, 8 fz_load4 lanes
+// whose second dword holds no byte of the term, 9 DP lanes in which the transposition lowered a cell, 10 reductions of a full
+// keep buffer, 11 slices past a query's candidates, 12 queries with several slices, 13 DP lanes on the bucket past 66 bytes,
+// 14 entries dropped for score 0, 15 entries dropped as repeats (both in k_fz_build_count), 16 waves of k_fz_build_scatter
+// with more than one length round.
+constexpr int kNsZcnt = 17;
+__device__ unsigned long long g_ns_zcnt[kNsZcnt];
+// one atomic per wave, by its first active lane (the DP runs with the queue's idle lanes masked off)
+__device__ __forceinline__ void fz_count_wave(int i, unsigned long long v) {
+    const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+    if (v && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(act)) atomicAdd(&g_ns_zcnt[i], v);
+}
+__device__ __forceinline__ void fz_count_lanes(int i, bool on) {
+    fz_count_wave(i, (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(on)));
+}
+#endif
+
 struct FzPlan {            // one query's pieces of the permutation, one per length n - e + t
     uint32_t start[5];
     uint32_t cum[5];       // inclusive running counts; cum[4] = the query's candidates
@@ -72,12 +93,18 @@ __device__ __forceinline__ bool fz_classify(uint32_t i, const uint64_t* __restri
     const uint64_t h = heads[i];
     bucket = len < (uint32_t)kFzBuckets - 1 ? len : (uint32_t)kFzBuckets - 1;
     sig = 0;
+#ifdef NS_COUNT
+    if ((uint32_t)(keys[i] >> 32) == ~0u) sig = 1;        // the reason, for k_fz_build_count (a caller ignores sig of a non-candidate)
+#endif
     if ((uint32_t)(keys[i] >> 32) == ~0u) return false;   // ~score: score 0, no document carries the term
     if (i > 0) {                                           // equal to the predecessor: not the first of its run
         const uint32_t po = offs[i - 1];
         if (o - po == len && heads[i - 1] == h) {
             bool same = true;
             for (uint32_t j = 8; j < len && same; j++) same = pool[(uint64_t)po + j] == pool[(uint64_t)o + j];
+#ifdef NS_COUNT
+            if (same) sig = 2;
+#endif
             if (same) return false;
         }
     }
@@ -101,6 +128,10 @@ __global__ void __launch_bounds__(64) k_fz_build_count(const uint64_t* __restric
         uint32_t bucket = 0;
         uint64_t sig = 0;
         if (i < n && fz_classify((uint32_t)i, heads, offs, pool, keys, bucket, sig)) atomicAdd(&hist[bucket], 1u);
+#ifdef NS_COUNT
+        fz_count_lanes(14, sig == 1);   // (a candidate's signature carries its length from bit 40 up, or is 0)
+        fz_count_lanes(15, sig == 2);
+#endif
     }
     __syncthreads();
     for (uint32_t b = lane; b < (uint32_t)kFzBuckets; b += 64) ghist[(uint64_t)b * n_blocks + blockIdx.x] = hist[b];
@@ -146,6 +177,9 @@ __global__ void __launch_bounds__(64) k_fz_build_scatter(const uint64_t* __restr
         uint64_t sig = 0;
         const bool cand = i < n && fz_classify((uint32_t)i, heads, offs, pool, keys, bucket, sig);
         uint64_t todo = __builtin_amdgcn_ballot_w64(cand);
+#ifdef NS_COUNT
+        uint32_t zc_rounds = 0;
+#endif
         while (todo) {              // one round per distinct length among the wave's candidates
             const uint32_t lb = (uint32_t)__shfl((int)bucket, (int)__builtin_ctzll(todo), 64);
             const uint64_t same = __builtin_amdgcn_ballot_w64(cand && bucket == lb);
@@ -159,7 +193,13 @@ __global__ void __launch_bounds__(64) k_fz_build_scatter(const uint64_t* __restr
             if (lane == 0) next[lb] = at + (uint32_t)__builtin_popcountll(same);
             __builtin_amdgcn_wave_barrier();
             todo &= ~same;
+#ifdef NS_COUNT
+            zc_rounds++;
+#endif
         }
+#ifdef NS_COUNT
+        fz_count_wave(16, zc_rounds > 1 ? 1 : 0);
+#endif
     }
 }
 
@@ -215,6 +255,10 @@ __device__ __forceinline__ uint32_t fz_load4(const uint8_t* __restrict__ pool, u
     const uint32_t sh = (a & 3u) * 8;
     const uint32_t lo = w[0];
     if (sh == 0) return lo;
+#ifdef NS_COUNT
+    fz_count_lanes(7, (a & ~3u) + 4 < end);
+    fz_count_lanes(8, (a & ~3u) + 4 >= end);
+#endif
     const uint32_t hi = (a & ~3u) + 4 < end ? w[1] : 0u;
     return (lo >> sh) | (hi << (32 - sh));
 }
@@ -243,6 +287,9 @@ __device__ __forceinline__ uint32_t fz_osa(const uint8_t* qs, uint32_t n, uint64
     for (int k = 0; k < E; k++) w = (w >> 8) | (((head >> (56 - 8 * k)) & 0xffull) << (8 * (2 * E + 1)));
     uint32_t cw = 0, qp = 0;
     bool done = true;
+#ifdef NS_COUNT
+    bool zc_tr = false;
+#endif
     for (uint32_t i = 1; i <= n; i++) {
         const uint32_t k = i + E - 1;
         uint32_t b;
@@ -263,6 +310,9 @@ __device__ __forceinline__ uint32_t fz_osa(const uint8_t* qs, uint32_t n, uint64
             uint32_t v = p1[t] + (qc != c1 ? 1u : 0u);
             if (t + 1 < B) v = min(v, p1[t + 1] + 1);
             if (t >= 1) v = min(v, cur[t - 1] + 1);
+#ifdef NS_COUNT
+            zc_tr = zc_tr || (i >= 2 && j >= 2 && qc == c2 && qp == c1 && p2[t] + 1 < v);
+#endif
             if (i >= 2 && j >= 2 && qc == c2 && qp == c1) v = min(v, p2[t] + 1);
             if (j == 0) v = i;
             if (j < 0) v = kInf;
@@ -273,8 +323,15 @@ __device__ __forceinline__ uint32_t fz_osa(const uint8_t* qs, uint32_t n, uint64
 #pragma unroll
         for (int t = 0; t < B; t++) { p2[t] = p1[t]; p1[t] = cur[t]; }
         qp = qc;
+#ifdef NS_COUNT
+        if (__builtin_amdgcn_ballot_w64(min(before, now) <= (uint32_t)E)) fz_count_wave(6, __builtin_amdgcn_ballot_w64(min(before, now) > (uint32_t)E) ? 1 : 0);
+        else fz_count_wave(5, i < n ? 1 : 0);
+#endif
         if (!__builtin_amdgcn_ballot_w64(min(before, now) <= (uint32_t)E)) { done = i == n; break; }
     }
+#ifdef NS_COUNT
+    fz_count_lanes(9, zc_tr);
+#endif
     uint32_t d = kInf;
     if constexpr (kPrefix) {
         const int last = (int)min(m, n + (uint32_t)E) - (int)n + E;   // the band cell of column min(m, n + E); >= 0 as m >= n - E
@@ -325,6 +382,9 @@ __device__ __forceinline__ void fz_verify(int64_t slot, const uint8_t* qs, uint3
         const uint32_t idx = perm[slot];
         uint32_t m = (uint32_t)(psig[slot] >> 40) & 0xffu;
         if constexpr (kPrefix) m = psig[slot] ? m : offs[idx + 1] - offs[idx];
+#ifdef NS_COUNT
+        if constexpr (kPrefix) fz_count_lanes(13, psig[slot] == 0);
+#endif
         const uint32_t o = m > 8 ? offs[idx] : 0u;
         const uint32_t d = fz_osa<E, kPrefix>(qs, n, heads[idx], o, m, pool);
         if (d <= (uint32_t)E) key = ((uint64_t)d << 62) | ((keys[idx] >> 32) << kFzIdxBits) | idx;
@@ -333,6 +393,9 @@ __device__ __forceinline__ void fz_verify(int64_t slot, const uint8_t* qs, uint3
     const uint64_t bal = __builtin_amdgcn_ballot_w64(take);
     if (!bal) return;
     const uint32_t add = (uint32_t)__builtin_popcountll(bal);
+#ifdef NS_COUNT
+    fz_count_wave(10, cnt + add > (uint32_t)kFzKeep ? 1 : 0);
+#endif
     if (cnt + add > (uint32_t)kFzKeep) worst = fz_reduce(keep, cnt, lane, L);   // cnt = L <= 10 afterwards: 64 more fit
     if (take) keep[cnt + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = key;
     __builtin_amdgcn_wave_barrier();
@@ -377,18 +440,29 @@ __device__ __forceinline__ void fz_scan_body(const Plan& pl, uint64_t p0, uint64
                 pass = !use_sig || __builtin_popcountll((psig[slot] ^ qsig) & kFzSigBits) <= 2 * E;
             }
         }
+#ifdef NS_COUNT
+        fz_count_lanes(0, p < p1);
+        fz_count_lanes(1, p < p1 && !pass);
+#endif
         const uint64_t bal = __builtin_amdgcn_ballot_w64(pass);
         if (pass) queue[queued + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = slot;
         __builtin_amdgcn_wave_barrier();
         queued += (uint32_t)__builtin_popcountll(bal);
         if (queued >= 64) {   // a full wave of work for the DP, taken from the top
             queued -= 64;
+#ifdef NS_COUNT
+            fz_count_wave(2, 1);
+            fz_count_wave(3, queued ? 1 : 0);
+#endif
             const uint32_t s = queue[queued + lane];
             __builtin_amdgcn_wave_barrier();
             fz_verify<E, kPrefix>((int64_t)s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
         }
     }
     if (queued) {
+#ifdef NS_COUNT
+        fz_count_wave(4, 1);
+#endif
         const int64_t s = lane < queued ? (int64_t)queue[lane] : -1;
         __builtin_amdgcn_wave_barrier();
         fz_verify<E, kPrefix>(s, qs, n, perm, psig, heads, offs, pool, keys, keep, cnt, worst, lane, L);
@@ -441,6 +515,9 @@ k_fz_scan(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs,
     const uint64_t p0 = (uint64_t)(b - slice_base[q]) * slice;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (p0 >= pl.cum[4]) {   // uniform: nothing of the query falls into this slice
+#ifdef NS_COUNT
+        if (threadIdx.x == 0) atomicAdd(&g_ns_zcnt[11], 1ull);
+#endif
         if (threadIdx.x < (uint32_t)kAcTop) part[(uint64_t)b * kAcTop + threadIdx.x] = kAcEmpty;
         return;
     }
@@ -561,6 +638,9 @@ k_fp_scan(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ offs,
     const uint64_t p0 = (uint64_t)(b - slice_base[q]) * slice;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (p0 >= total) {   // uniform: nothing of the query falls into this slice
+#ifdef NS_COUNT
+        if (threadIdx.x == 0) atomicAdd(&g_ns_zcnt[11], 1ull);
+#endif
         if (threadIdx.x < (uint32_t)kAcTop) part[(uint64_t)b * kAcTop + threadIdx.x] = kAcEmpty;
         return;
     }
@@ -591,6 +671,9 @@ __global__ void __launch_bounds__(256) k_fz_select(const uint64_t* __restrict__ 
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (q >= n_q) return;   // wave-uniform
+#ifdef NS_COUNT
+    fz_count_wave(12, slice_base[q + 1] - slice_base[q] > 1 ? 1 : 0);
+#endif
     uint64_t best[kAcTop], worst = kAcEmpty;
 #pragma unroll
     for (int i = 0; i < kAcTop; i++) best[i] = kAcEmpty;

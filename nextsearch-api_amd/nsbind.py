@@ -261,7 +261,7 @@ def hip_lib():
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
-                  "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5}
+                  "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17}
 
 
 def debug_counters(reset=False):
@@ -276,6 +276,18 @@ def debug_counters(reset=False):
                 raise RuntimeError(name + " failed")
             out[name] = [int(v) for v in buf]
     return out
+
+
+def fuzzy_counters(reset=False):
+    """the 17 event counters of the corrector's and completion's kernels (csrc/ns_fuzzy.hip; tests/fuzzy_shapes.py names them), or
+    None when the loaded HIP library is not the counting build; `reset` zeroes them after the read."""
+    L = hip_lib()
+    if not hasattr(L, "ns_debug_fuzzy_counters"):
+        return None
+    buf = (C.c_uint64 * DEBUG_COUNTERS["ns_debug_fuzzy_counters"])()
+    if L.ns_debug_fuzzy_counters(buf, int(bool(reset))) != 0:
+        raise RuntimeError("ns_debug_fuzzy_counters failed")
+    return [int(v) for v in buf]
 
 
 def host_lib():
