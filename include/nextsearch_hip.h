@@ -680,6 +680,37 @@ int ns_search_sorted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n
                            uint32_t* keys_out /* Q x K */, uint32_t* nhits_out, uint64_t* found_out /* may be NULL */,
                            uint64_t* rest_out /* may be NULL */, float* device_ms_out /* may be NULL */);
 
+/* ---- facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip) - */
+/* ns_facet_count and ns_search_sorted(_after) over ns_search_boolean's MATCHED SET: roles[r] is the role of terms[r]
+ * (roles == NULL: every ref is NS_ROLE_SHOULD, and the answers are those of the calls under NS_FLAG_OR; every ref
+ * NS_ROLE_MUST gives those under NS_FLAG_AND).  Nothing else changes:
+ *   ns_facet_count_boolean    counts_out[q * n_buckets + b] = distinct matched documents of query q in bucket b, summed over
+ *                             the segments; found_out[q] (may be NULL) = the row sum = ns_search_boolean's found.
+ *   ns_search_sorted_boolean  the first K = clamp(k, 1, NS_MAX_K) documents of the matched set in ns_search_sorted's total order
+ *                             (rank key, position of the segment in the call's list, docId; key 0 last in both directions),
+ *                             STRICTLY AFTER the query's cursor where after[q].set == 1 (after == NULL: none), with
+ *                             ns_search_sorted_after's found / rest / nhits.  hits_out[..].score is ns_search_boolean's SCORE
+ *                             of that document, bit for bit: NOT refs add nothing.  flags: NS_SORT_ASC or 0.
+ * Synchronous; device_ms_out (may be NULL) = HIP-event time of the kernels.  NS_E_INVAL, with a message, nothing launched and
+ * the output arrays untouched: what ns_facet_count / ns_search_sorted_after refuse (a segment or table of another ctx, a cursor
+ * that names a segment the call does not list, a single query whose work items alone exceed the candidate buffer, ...), what
+ * ns_search_boolean refuses (a role above NS_ROLE_NOT, a ref past its segment's postings, a non-finite idf or qweight on a MUST
+ * or SHOULD ref, ...), and for ns_search_sorted_boolean a flag bit other than NS_SORT_ASC.  n_queries == 0 is NS_OK. */
+int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                           const uint8_t* roles /* n_terms; NULL = all SHOULD */, uint32_t n_terms, const uint32_t* seg_ids,
+                           ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs, uint32_t* counts_out /* Q x n_buckets */,
+                           uint64_t* found_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                             const uint8_t* roles /* n_terms; NULL = all SHOULD */, uint32_t n_terms, uint32_t k, uint32_t flags,
+                             const ns_cursor* after /* n_queries; NULL = none */, const uint32_t* seg_ids, ns_seg* const* segs,
+                             ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out /* Q x K */, uint32_t* keys_out /* Q x K */,
+                             uint32_t* nhits_out, uint64_t* found_out /* may be NULL */, uint64_t* rest_out /* may be NULL */,
+                             float* device_ms_out /* may be NULL */);
+/* HIP-event time of k_bs_count, k_bs_select, k_sd_join and k_bs_score, summed over the calling thread's two calls above (and
+ * their sub-batches) since the last reset: out4[0..3], milliseconds; reset != 0 zeroes the sums after the read.  For
+ * tools/boolean_sets_bench.py. */
+int ns_boolean_sets_kernel_ms(float* out4, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

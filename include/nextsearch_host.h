@@ -446,7 +446,26 @@ int nsh_engine_search_boolean_after_batch(nsh_engine* e, uint32_t filter_handle,
 int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                                          uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out,
                                          uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out);
-/* Engine::search_page: *json_out (free with nsh_free) = the mode's body (0 search OR, 1 search AND, 2 boolean, 3 sorted by spec;
+/* ---- facet counts and date order for boolean queries ----
+ * Engine::facet_boolean_batch_flat: nsh_engine_facet_batch over nsh_engine_search_boolean_batch's matched set (`+word`, `-word`);
+ * found and has_found equal nsh_engine_search_boolean_batch's.
+ * Engine::search_boolean_sorted_batch_flat: nsh_engine_search_sorted_after_batch over that set, hits with the boolean score bits;
+ * after: n_queries cursors of kind 'd', or NULL for page 1; rest may be NULL. */
+int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                   uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
+int nsh_engine_search_boolean_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                           uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                           uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_boolean_faceted / search_boolean_sorted: *json_out (free with nsh_free) = nsh_engine_search_boolean_json's body
+ * plus "facets" (as nsh_engine_search_faceted_json's), or with "results" in date order plus "sort" (as
+ * nsh_engine_search_sorted_json's).  On failure -1 and {"error": ...}. */
+int nsh_engine_search_boolean_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                           const char* date_to, int keep_undated, char** json_out);
+int nsh_engine_search_boolean_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                          const char* date_to, int keep_undated, char** json_out);
+
+/* Engine::search_page: *json_out (free with nsh_free) = the mode's body (0 search OR, 1 search AND, 2 boolean, 3 sorted by spec,
+ * 4 boolean sorted by spec: nsh_engine_search_boolean_sorted_json's body, cursors of kind 'd';
  * search_filtered's with use_filter != 0) over one page, plus "page": {"cursor", "next", "offset", "remaining"}; "next" is
  * present only when documents remain.  cursor: "" or NULL for the first page, else a page's "next".  On failure -1 and
  * {"error": ...}. */

@@ -31,6 +31,7 @@
 #include "ns_similar.hip"
 #include "ns_sorted.hip"   // after ns_facet.hip (fc_cut, fc_mark, fc_lower_bound) and ns_similar.hip (ml_sort_up, ml_merge_down, ml_join)
 #include "ns_boolean.hip"  // after ns_sorted.hip (SdSet, sd_insert) and ns_facet.hip (fc_cut, fc_mark)
+#include "ns_boolean_sets.hip"  // after ns_boolean.hip (BqRef), ns_sorted.hip (SdSet, sd_key, sd_insert, DevSdSeg, af_clip) and ns_facet.hip
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
@@ -3233,6 +3234,233 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip)
+static thread_local float g_bs_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // k_bs_count, k_bs_select, k_sd_join, k_bs_score: summed over the thread's calls (ns_boolean_sets_kernel_ms)
+
+extern "C" int ns_boolean_sets_kernel_ms(float* out4, int reset) {
+    if (!out4) return NS_E_INVAL;
+    for (int i = 0; i < 4; i++) out4[i] = g_bs_ms[i];
+    if (reset) g_bs_ms[0] = g_bs_ms[1] = g_bs_ms[2] = g_bs_ms[3] = 0.0f;
+    return NS_OK;
+}
+
+extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                      uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                                      uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+    const char* fn = "ns_facet_count_boolean";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
+    if (!queries || !counts_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed (the number of buckets comes from the tables)", fn);
+    if (!seg_ids || !segs || !tables) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    std::vector<FcSegView> views(n_segs);
+    std::vector<DevFcSeg> dsegs(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        const ns_facet* t = tables[i];
+        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or table %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: table %u does not belong to this ctx", fn, i);
+        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: table %u buckets %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+        if (t->n_buckets != tables[0]->n_buckets) return fail(ctx, NS_E_INVAL, "%s: table %u has %u buckets, table 0 has %u", fn, i, t->n_buckets, tables[0]->n_buckets);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, t->d_buckets, s->n_docs, 0u};
+    }
+    const uint32_t B = tables[0]->n_buckets;
+    std::vector<BqRef> refs;
+    std::vector<FcItem> items;
+    std::string why;
+    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
+    const size_t n_counts = (size_t)n_queries * B;
+    if (!items.empty()) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        size_t off = 0;
+        const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
+                     o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_counts = place_at(off, n_counts * 4);
+        const size_t block_bytes = off;
+        char* blk = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        hipError_t e = hipSuccess;
+        auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+        chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+        chk(hipEventCreate(&ev0));
+        chk(hipEventCreate(&ev1));
+        if (e == hipSuccess) {
+            chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
+            chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
+            chk(hipMemsetAsync(blk + o_counts, 0, n_counts * 4, st));
+            chk(hipEventRecord(ev0, st));
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_bs_count, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
+                chk(hipGetLastError());
+            }
+            chk(hipEventRecord(ev1, st));
+            chk(hipMemcpyAsync(counts_out, blk + o_counts, n_counts * 4, hipMemcpyDeviceToHost, st));
+            chk(hipStreamSynchronize(st));
+            float ms = 0.0f;
+            if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
+                g_bs_ms[0] += ms;
+                if (device_ms_out) *device_ms_out = ms;
+            }
+        }
+        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    } else {
+        std::memset(counts_out, 0, n_counts * 4);
+    }
+    if (found_out)
+        for (uint32_t q = 0; q < n_queries; q++) {
+            uint64_t sum = 0;
+            for (uint32_t b = 0; b < B; b++) sum += counts_out[(size_t)q * B + b];
+            found_out[q] = sum;
+        }
+    return NS_OK;
+}
+
+extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                        uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                                        ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
+                                        uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    const char* fn = "ns_search_sorted_boolean";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
+    if (!queries || !hits_out || !keys_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (flags & ~NS_SORT_ASC) return fail(ctx, NS_E_INVAL, "%s: flags 0x%x: only NS_SORT_ASC is known (the roles say what matches)", fn, flags);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
+    if (!seg_ids || !segs || !keys) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
+    std::vector<FcSegView> views(n_segs);
+    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<DevSdSeg> sds(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        const ns_dockeys* t = keys[i];
+        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or key table %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: key table %u does not belong to this ctx", fn, i);
+        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: key table %u keys %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
+        sds[i] = DevSdSeg{t->d_keys, s->d_norm, seg_ids[i], 0u};
+    }
+    const uint32_t asc = (flags & NS_SORT_ASC) ? 1u : 0u;
+    std::vector<BqRef> refs;
+    std::vector<FcItem> items;
+    std::vector<uint32_t> q_off;
+    std::vector<SdBatch> cuts;
+    std::string why;
+    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
+    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
+    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
+    bool paged = false;
+    if (!after_plan(after, n_queries, views, items, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, last, paged, why))
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    uint64_t cand_rows = 0;
+    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
+    const size_t n_out = (size_t)n_queries * K;
+    const size_t n_roles = roles ? (size_t)n_terms : 0;
+
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    size_t off = 0;
+    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
+    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
+                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_sds = place_at(off, sds.size() * sizeof(DevSdSeg)),
+                 o_qoff = place_at(off, q_off.size() * 4), o_qd = place_at(off, (size_t)n_queries * sizeof(ns_query_desc)),
+                 o_terms = place_at(off, (size_t)n_terms * sizeof(ns_term_ref)), o_roles = place_at(off, n_roles),
+                 o_hits = place_at(off, n_out * sizeof(ns_hit)), o_keys = place_at(off, n_out * 4), o_pos = place_at(off, n_out * 4),
+                 o_nhits = place_at(off, (size_t)n_queries * 4), o_found = place_at(off, (size_t)n_queries * 8),
+                 o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
+    const size_t block_bytes = off;
+    char* blk = nullptr;
+    std::vector<hipEvent_t> evs(cuts.size() * 4, nullptr);
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
+    for (auto& ev : evs) chk(hipEventCreate(&ev));
+    if (e == hipSuccess) {
+        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
+        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_sds, sds.data(), sds.size() * sizeof(DevSdSeg), hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(blk + o_qd, queries, (size_t)n_queries * sizeof(ns_query_desc), hipMemcpyHostToDevice, st));
+        if (n_terms) chk(hipMemcpyAsync(blk + o_terms, terms, (size_t)n_terms * sizeof(ns_term_ref), hipMemcpyHostToDevice, st));
+        if (n_roles) chk(hipMemcpyAsync(blk + o_roles, roles, n_roles, hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
+        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
+        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
+        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
+        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
+        const FcItem* d_items = (const FcItem*)(blk + o_items);
+        const BqRef* d_refs = (const BqRef*)(blk + o_refs);
+        const DevFcSeg* d_segs = (const DevFcSeg*)(blk + o_segs);
+        const DevSdSeg* d_sds = (const DevSdSeg*)(blk + o_sds);
+        const uint8_t* d_roles = n_roles ? (const uint8_t*)(blk + o_roles) : nullptr;
+        unsigned long long* d_found = (unsigned long long*)(blk + o_found);
+        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
+        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
+            const SdBatch& b = cuts[c];
+            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
+            chk(hipEventRecord(evs[c * 4 + 0], st));
+            if (n_it) {
+                if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                    hipLaunchKernelGGL(k_bs_select<true>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
+                else
+                    hipLaunchKernelGGL(k_bs_select<false>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
+                chk(hipGetLastError());
+            }
+            chk(hipEventRecord(evs[c * 4 + 1], st));
+            hipLaunchKernelGGL(k_sd_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_sds,
+                               (const uint64_t*)d_cand, K, asc, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_keys), (uint32_t*)(blk + o_pos), (uint32_t*)(blk + o_nhits));
+            chk(hipGetLastError());
+            chk(hipEventRecord(evs[c * 4 + 2], st));
+            const uint64_t n_waves = (uint64_t)n_q * K;
+            hipLaunchKernelGGL(k_bs_score, dim3((uint32_t)((n_waves + 3) / 4)), dim3(256), 0, st, (const ns_query_desc*)(blk + o_qd), (const ns_term_ref*)(blk + o_terms), d_roles,
+                               b.q_begin, b.q_end, d_segs, d_sds, K, (const uint32_t*)(blk + o_pos), (const uint32_t*)(blk + o_nhits), (uint32_t*)(blk + o_hits));
+            chk(hipGetLastError());
+            chk(hipEventRecord(evs[c * 4 + 3], st));
+        }
+        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(keys_out, blk + o_keys, n_out * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
+        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
+        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
+        chk(hipStreamSynchronize(st));
+        if (e == hipSuccess) {
+            float sum = 0.0f;
+            for (size_t c = 0; c < cuts.size(); c++)
+                for (int j = 0; j < 3; j++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { g_bs_ms[1 + j] += ms; sum += ms; }
+                }
+            if (device_ms_out) *device_ms_out = sum;
+        }
+    }
+    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
+    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Segment-sharded multi-GPU: join the all-gathered per-rank rows (k_merge_ranks).  Device pointers; asynchronous on the ctx stream.
 extern "C" int ns_merge_rank_rows(ns_ctx* ctx, const void* d_hits, const void* d_nhits, const void* d_found, uint32_t n_ranks,
                                   uint32_t n_queries, uint32_t k, const uint32_t* d_seg_map, uint32_t seg_map_stride,
@@ -3928,6 +4156,15 @@ extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bcnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values
+extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsBscnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bscnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bscnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values

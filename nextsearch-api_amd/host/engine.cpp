@@ -2101,6 +2101,24 @@ bool Engine::facet_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle
     return true;
 }
 
+// the "facets" member of search_faceted's body, with the comma and newline behind it
+static std::string facets_member(const nsx::FacetSpec& spec, const std::vector<std::string>& labels, const std::vector<uint32_t>& counts) {
+    std::string o = "  \"facets\": {\n    ";
+    json_escape(o, nsx::facet_kind_name(spec.kind));
+    o += ": [";
+    bool first = true;
+    for (size_t b = 0; b < labels.size(); b++) {
+        if (!counts[b]) continue;
+        o += first ? "\n" : ",\n";
+        first = false;
+        o += "      {\n        \"count\": " + std::to_string(counts[b]) + ",\n        \"value\": ";
+        json_escape(o, labels[b]);
+        o += "\n      }";
+    }
+    o += first ? "]\n  },\n" : "\n    ]\n  },\n";
+    return o;
+}
+
 bool Engine::search_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_faceted: no device context: this engine has no CPU scoring path"; return false; }
@@ -2120,20 +2138,7 @@ bool Engine::search_faceted_text(const std::string& query, int k, const nsx::Fac
     uint8_t us = 0;
     if (!facet_batch_flat(spec, handle, &qv, 1, NS_FLAG_OR, counts, &fd, &us, labels)) { body = err_; return false; }
     // the "facets" member in front ("facets" < "filter" < "found" < "k": nlohmann keeps keys sorted)
-    std::string o = "{\n  \"facets\": {\n    ";
-    json_escape(o, nsx::facet_kind_name(spec.kind));
-    o += ": [";
-    bool first = true;
-    for (size_t b = 0; b < labels.size(); b++) {
-        if (!counts[b]) continue;
-        o += first ? "\n" : ",\n";
-        first = false;
-        o += "      {\n        \"count\": " + std::to_string(counts[b]) + ",\n        \"value\": ";
-        json_escape(o, labels[b]);
-        o += "\n      }";
-    }
-    o += first ? "]\n  },\n" : "\n    ]\n  },\n";
-    body = o + body.substr(2);
+    body = "{\n" + facets_member(spec, labels, counts) + body.substr(2);
     return true;
 }
 
@@ -2406,78 +2411,83 @@ bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const Query
     return boolean_batch_impl("search_boolean_after_batch_flat", filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
 }
 
+// What search_boolean_batch_flat, facet_boolean_batch_flat and search_boolean_sorted_batch_flat share.  boolean_prepare: the
+// filter's row source under a handle and the segments the refs can name, in manifest order (the index's own, or the filter's
+// copies).  boolean_refs_range: descriptors, refs and roles of the queries [a, b) (qd indexed from a) and usable[a .. b).
+bool Engine::boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp) {
+    if (filter_handle) {
+        bp.f = filter_of(filter_handle);
+        if (!bp.f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    }
+    const uint32_t S = (uint32_t)segments.size();
+    if (bp.f) {   // search_filtered_batch_flat's row source
+        bp.rs.rows = bp.f->rows.data();
+        bp.rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
+        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+        if (!bp.rs.rows) bp.rs.rows = &no_rows;
+    }
+    bp.is_listed.assign(S, 0);
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = bp.f ? bp.f->segs[s] : dev_segs_[s];
+        if (!h) continue;
+        bp.is_listed[s] = 1;
+        bp.listed.push_back(s);
+        bp.ids.push_back(bp.rs.id_base + s);
+        bp.segs.push_back(h);
+    }
+    return true;
+}
+
+void Engine::boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
+    const uint32_t S = (uint32_t)segments.size();
+    const nsx::RowSource& rs = bp.rs;
+    bp.qd.assign(b - a, ns_query_desc{0, 0});
+    bp.refs.clear();
+    bp.roles.clear();
+    for (size_t q = a; q < b; q++) {
+        bp.terms.clear();
+        size_t positive = 0;
+        nsx::for_each_boolean_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role) {
+            bp.terms.emplace_back(dict.find(p, n), role);
+            positive += role != nsx::kRoleNot;
+        });
+        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
+        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
+        if (!usable[q]) continue;
+        for (const uint32_t sid : bp.listed)
+            for (const auto& t : bp.terms) {
+                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
+                if (e && e->byte_off != nsx::kAbsent) {
+                    bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                    bp.roles.push_back(t.second);
+                } else if (t.second == nsx::kRoleMust) {   // the segment has no list of a required term: nothing of it matches
+                    bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});
+                    bp.roles.push_back(t.second);
+                }
+            }
+        bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
+    }
+}
+
 bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                                 uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
-    OpenFilter* f = nullptr;
-    if (filter_handle) {
-        f = filter_of(filter_handle);
-        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
-    }
+    BooleanPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
     if (Q == 0) return true;
     const size_t K = (size_t)std::max(1, std::min(k, 100));
-    const uint32_t S = (uint32_t)segments.size();
-    nsx::RowSource rs;
-    if (f) {   // search_filtered_batch_flat's row source
-        rs.rows = f->rows.data();
-        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
-        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
-        if (!rs.rows) rs.rows = &no_rows;
-    }
-    // the segments the refs can name, in manifest order: the index's own, or the filter's copies
-    std::vector<uint32_t> ids, listed;
-    std::vector<ns_seg*> segs;
-    std::vector<uint8_t> is_listed(S, 0);
     std::vector<ns_cursor> cur;
-    for (uint32_t s = 0; s < S; s++) {
-        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
-        if (!h) continue;
-        is_listed[s] = 1;
-        listed.push_back(s);
-        ids.push_back(rs.id_base + s);
-        segs.push_back(h);
-    }
     const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
     const size_t kSubBatch = sub_batch_size();
     const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    std::vector<ns_query_desc> qd;
-    std::vector<ns_term_ref> refs;
-    std::vector<uint8_t> roles;
-    std::vector<char> scratch;
-    std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        qd.assign(b - a, ns_query_desc{0, 0});
-        refs.clear();
-        roles.clear();
-        for (size_t q = a; q < b; q++) {
-            terms.clear();
-            size_t positive = 0;
-            nsx::for_each_boolean_term(queries[q].p, queries[q].n, scratch, [&](const char* p, size_t n, uint8_t role) {
-                terms.emplace_back(dict.find(p, n), role);
-                positive += role != nsx::kRoleNot;
-            });
-            qd[q - a].term_begin = (uint32_t)refs.size();
-            usable[q] = (positive != 0 && S != 0) ? 1 : 0;
-            if (!usable[q]) continue;
-            for (const uint32_t sid : listed)
-                for (const auto& t : terms) {
-                    const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
-                    if (e && e->byte_off != nsx::kAbsent) {
-                        refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
-                        roles.push_back(t.second);
-                    } else if (t.second == nsx::kRoleMust) {   // the segment has no list of a required term: nothing of it matches
-                        refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});
-                        roles.push_back(t.second);
-                    }
-                }
-            qd[q - a].term_count = (uint32_t)refs.size() - qd[q - a].term_begin;
-        }
-        if (!translate_cursors(fn, after, a, b, rs.id_base, is_listed, f != nullptr, cur)) return false;
-        if (ids.empty()) {   // nothing on the device: no ref can exist
+        boolean_refs_range(queries, a, b, usable, bp);
+        if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
+        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
             if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
             std::fill(nhits + a, nhits + b, 0u);
@@ -2485,15 +2495,36 @@ bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const Qu
             continue;
         }
         float ms = 0.0f;
-        const int rc = ns_search_boolean_after(ctx_, qd.data(), (uint32_t)(b - a), refs.data(), roles.data(), (uint32_t)refs.size(), (uint32_t)K,
-                                               cur.empty() ? nullptr : cur.data(), ids.data(), segs.data(), (uint32_t)ids.size(), hits + a * K, nhits + a, found + a,
-                                               rest ? rest + a : nullptr, &ms);
+        const int rc = ns_search_boolean_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
+                                               cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * K, nhits + a,
+                                               found + a, rest ? rest + a : nullptr, &ms);
         if (rc != NS_OK) { err_ = std::string(after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
-            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= rs.id_base;   // manifest positions
+            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
     }
     return true;
+}
+
+// the "boolean" member of search_boolean's body (the parsed terms by role, in query order), with the comma and newline behind it
+static std::string boolean_member(const std::string& query) {
+    const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
+    std::string o = "  \"boolean\": {\n";
+    static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
+    for (int m = 0; m < 3; m++) {
+        o += std::string("    \"") + kMembers[m].name + "\": [";
+        bool any = false;
+        for (const nsx::BoolTerm& t : terms)
+            if (t.role == kMembers[m].role) {
+                o += any ? ",\n      " : "\n      ";
+                json_escape(o, t.text);
+                any = true;
+            }
+        o += any ? "\n    ]" : "]";
+        o += m < 2 ? ",\n" : "\n";
+    }
+    o += "  },\n";
+    return o;
 }
 
 bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
@@ -2525,29 +2556,171 @@ bool Engine::search_boolean_text(const std::string& query, int k, const nsx::Doc
     if (res.has_found)
         for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     // "boolean" < "filter" < "found": nlohmann keeps keys sorted, so the member sits in front
-    const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
-    std::string o = "{\n  \"boolean\": {\n";
-    static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
-    for (int m = 0; m < 3; m++) {
-        o += std::string("    \"") + kMembers[m].name + "\": [";
-        bool any = false;
-        for (const nsx::BoolTerm& t : terms)
-            if (t.role == kMembers[m].role) {
-                o += any ? ",\n      " : "\n      ";
-                json_escape(o, t.text);
-                any = true;
-            }
-        o += any ? "\n    ]" : "]";
-        o += m < 2 ? ",\n" : "\n";
-    }
-    o += "  },\n";
-    body = o + head.substr(2) + to_json_impl(res).substr(2);
+    body = "{\n" + boolean_member(query) + head.substr(2) + to_json_impl(res).substr(2);
     return true;
 }
 
 std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
     std::string body;
     if (!search_boolean_text(query, k, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+// ---- facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip) --------------------------
+bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                      uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    const char* fn = "facet_boolean_batch_flat";
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    counts.clear();
+    labels.clear();
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: facets are counted on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    BooleanPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    FacetSet* fs = nullptr;
+    if (!ensure_facets(spec, fs)) return false;
+    labels = fs->labels;
+    const size_t B = labels.size();
+    counts.assign(Q * B, 0u);
+    if (Q == 0) return true;
+    std::vector<ns_facet*> tabs;
+    for (const uint32_t s : bp.listed) {
+        if (!fs->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no bucket table on the device"; return false; }
+        tabs.push_back(fs->dev[s]);
+    }
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        boolean_refs_range(queries, a, b, usable, bp);
+        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            continue;
+        }
+        float ms = 0.0f;
+        const int rc = ns_facet_count_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), bp.ids.data(),
+                                              bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+    }
+    return true;
+}
+
+bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                              uint8_t* usable, float* device_ms) {
+    const char* fn = "search_boolean_sorted_batch_flat";
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    BooleanPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    SortSet* ss = nullptr;
+    if (!ensure_sorted(spec, ss)) return false;
+    if (Q == 0) return true;
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    std::vector<ns_dockeys*> tabs;
+    for (const uint32_t s : bp.listed) {
+        if (!ss->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no key table on the device"; return false; }
+        tabs.push_back(ss->dev[s]);
+    }
+    std::vector<ns_cursor> cur;
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    for (size_t i = 0; i < n_sub; i++) {
+        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
+        boolean_refs_range(queries, a, b, usable, bp);
+        if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
+        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
+            std::fill(found + a, found + b, (uint64_t)0);
+            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
+            std::fill(nhits + a, nhits + b, 0u);
+            std::fill(hits + a * K, hits + b * K, pad);
+            std::fill(keys + a * K, keys + b * K, 0u);
+            continue;
+        }
+        float ms = 0.0f;
+        const int rc = ns_search_sorted_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
+                                                spec.ascending ? NS_SORT_ASC : NS_SORT_DESC, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
+                                                tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string("ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        for (size_t q = a; q < b; q++)
+            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
+    }
+    return true;
+}
+
+bool Engine::search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_boolean_faceted: no device context: this engine has no CPU scoring path"; return false; }
+    if (!search_boolean_text(query, k, f, body)) return false;
+    const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
+    const QueryView qv{query.data(), query.size()};
+    std::vector<uint32_t> counts;
+    std::vector<std::string> labels;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels)) { body = err_; return false; }
+    // "boolean" < "facets" < "filter" < "found": the member goes behind the "boolean" member, which is the body's first and whose
+    // strings are escaped, so that its closing line is the first of that form
+    const size_t at = body.find("\n  },\n");
+    if (body.compare(0, 15, "{\n  \"boolean\": ") != 0 || at == std::string::npos) { body = err_ = "search_boolean_faceted: the boolean body has no boolean member"; return false; }
+    body.insert(at + 6, facets_member(spec, labels, counts));
+    return true;
+}
+
+std::string Engine::search_boolean_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    if (!search_boolean_faceted_text(query, k, spec, f, body)) {
+        std::string o = "{\n  \"error\": ";
+        json_escape(o, body);
+        o += "\n}";
+        return o;
+    }
+    return body;
+}
+
+bool Engine::search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_boolean_sorted: no device context: this engine has no CPU scoring path"; return false; }
+    if (!search_boolean_text(query, k, f, body)) return false;
+    const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits(K);
+    std::vector<uint32_t> keys(K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!search_boolean_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)) { body = err_; return false; }
+    std::vector<SearchHit> sorted;
+    if (us)
+        for (uint32_t i = 0; i < nh; i++) sorted.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    // the body's "results" member replaced ("query" is escaped: no line of it starts like a member), "sort" behind "segments"
+    const size_t a = body.find("\n  \"results\": "), b = body.rfind("\n  \"segments\": ");
+    if (a == std::string::npos || b == std::string::npos || b < a || body.size() < 2) { body = err_ = "search_boolean_sorted: the boolean body has no results member"; return false; }
+    std::string o = body.substr(0, a + 1);
+    append_results_json(o, sorted);
+    o += body.substr(b + 1, body.size() - (b + 1) - 2);   // "  \"segments\": N", without the closing "\n}"
+    o += ",\n  \"sort\": ";
+    json_escape(o, nsx::sort_name(spec));
+    o += "\n}";
+    body = std::move(o);
+    return true;
+}
+
+std::string Engine::search_boolean_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    if (!search_boolean_sorted_text(query, k, spec, f, body)) {
         std::string o = "{\n  \"error\": ";
         json_escape(o, body);
         o += "\n}";
@@ -2643,7 +2816,7 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
-    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::Sorted) { body = err_ = "search_page: unknown mode"; return false; }
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::BooleanSorted) { body = err_ = "search_page: unknown mode"; return false; }
     const char kind = nsx::page_kind(spec.mode);
     nsx::PageCursor cur;
     if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
@@ -2676,6 +2849,9 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
         case nsx::PageSpec::Sorted:
             ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
             break;
+        case nsx::PageSpec::BooleanSorted:
+            ok = search_boolean_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
+            break;
     }
     if (!ok) { body = err_; return false; }
     SearchResult res;
@@ -2687,24 +2863,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     if (!res.has_found) { nh = 0; rs = 0; fd = 0; }
     for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     std::string o = "{\n";
-    if (spec.mode == nsx::PageSpec::Boolean) {   // search_boolean's "boolean" member
-        const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
-        o += "  \"boolean\": {\n";
-        static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
-        for (int m = 0; m < 3; m++) {
-            o += std::string("    \"") + kMembers[m].name + "\": [";
-            bool any = false;
-            for (const nsx::BoolTerm& t : terms)
-                if (t.role == kMembers[m].role) {
-                    o += any ? ",\n      " : "\n      ";
-                    json_escape(o, t.text);
-                    any = true;
-                }
-            o += any ? "\n    ]" : "]";
-            o += m < 2 ? ",\n" : "\n";
-        }
-        o += "  },\n";
-    }
+    if (spec.mode == nsx::PageSpec::Boolean || spec.mode == nsx::PageSpec::BooleanSorted) o += boolean_member(query);   // search_boolean's "boolean" member
     o += head.substr(2);
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
@@ -2717,7 +2876,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
         next.set = true;
         uint32_t score_bits = 0;
         std::memcpy(&score_bits, &hits[nh - 1].score, 4);
-        next.rank = spec.mode == nsx::PageSpec::Sorted ? keys[nh - 1] : score_bits;
+        next.rank = kind == 'd' ? keys[nh - 1] : score_bits;
         next.seg = hits[nh - 1].seg_id;
         next.doc = hits[nh - 1].doc_id;
         page += ",\n    \"next\": ";
@@ -2727,7 +2886,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     page += ",\n    \"remaining\": " + std::to_string(rs - nh) + "\n  },\n";
     rest_of.insert(at, page);
     o += rest_of;
-    if (spec.mode == nsx::PageSpec::Sorted) {   // search_sorted's "sort" member behind "segments"
+    if (kind == 'd') {   // search_sorted's "sort" member behind "segments"
         o.resize(o.size() - 2);                 // the closing "\n}"
         o += ",\n  \"sort\": ";
         json_escape(o, nsx::sort_name(spec.sort));

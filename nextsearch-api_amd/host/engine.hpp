@@ -349,6 +349,27 @@ public:
     std::string search_boolean(const std::string& query, int k, const nsx::DocFilter* f = nullptr);
     bool search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
 
+    // Facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip): facet_batch_flat and
+    // search_sorted_after_batch_flat over search_boolean_batch_flat's matched set.  The query preparation is
+    // search_boolean_batch_flat's, so found and usable equal its, query for query.
+    // facet_boolean_batch_flat: counts (resized to Q x B, B = labels.size()) over ensure_facets' bucket tables.
+    // search_boolean_sorted_batch_flat: the first K = clamp(k, 1, 100) matched documents in the order of spec (ensure_sorted's
+    // key tables) strictly after each query's cursor (after == nullptr: page 1), with the boolean score bits; keys: Q x K;
+    // rest may be nullptr.  Hits carry manifest positions.  Both need a device, run on the primary context, and use neither
+    // semantic expansion nor the search cache.
+    bool facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                  uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms = nullptr);
+    bool search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                          const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* usable, float* device_ms = nullptr);
+    // JSON text: search_boolean's body plus "facets" (search_faceted's member), and search_boolean's body with "results" in date
+    // order plus "sort" (search_sorted's); dump(2) layout.  Any failure: {"error": ...} (the _text forms: false, body = the
+    // message).
+    std::string search_boolean_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
+    std::string search_boolean_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
+
     // Pages past the first K (host/page.hpp).  A cursor is a position (rank, manifest position, docId) in a call's
     // total order; with one, a call answers with the first K matched documents STRICTLY AFTER it: found[q] stays the size of
     // the matched set, rest[q] (may be nullptr) is the number of matched documents after the cursor, nhits[q] = min(K, rest[q]).
@@ -365,7 +386,8 @@ public:
     bool search_sorted_after_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
                                         const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                         uint8_t* usable, float* device_ms = nullptr);
-    // JSON text: the mode's body (search's, search_filtered's with spec.use_filter, search_boolean's, search_sorted's) over one
+    // JSON text: the mode's body (search's, search_filtered's with spec.use_filter, search_boolean's, search_sorted's,
+    // search_boolean_sorted's) over one
     // page, plus "page": {"cursor", "next", "offset", "remaining"}; "next" only when documents remain after this page; offset
     // = found - rest, remaining = rest - nhits; dump(2) layout.  cursor_text: "" for the first page, else a page's "next"; its
     // kind letter must fit the mode.  The search cache is not used.  Any failure: {"error": ...} (search_page_text: false,
@@ -451,6 +473,21 @@ private:
                            float* device_ms);
     bool boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                             uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
+    // what the three boolean paths share: filter row source, the call's segment list and the refs and roles of a query range
+    struct BooleanPrep {
+        OpenFilter* f = nullptr;
+        nsx::RowSource rs;
+        std::vector<uint32_t> ids, listed;      // the ids the refs use; the manifest positions behind them
+        std::vector<ns_seg*> segs;
+        std::vector<uint8_t> is_listed;         // per manifest position
+        std::vector<ns_query_desc> qd;
+        std::vector<ns_term_ref> refs;
+        std::vector<uint8_t> roles;
+        std::vector<char> scratch;
+        std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
+    };
+    bool boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp);
+    void boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };

@@ -1160,15 +1160,15 @@ static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<ns
     for (uint32_t q = 0; q < n; q++) { out[q].set = in[q].set != 0; out[q].rank = in[q].rank; out[q].seg = in[q].seg; out[q].doc = in[q].doc; }
 }
 
-// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted
+// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted
 static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                            uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                            uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::SortSpec sp;
     std::string why;
-    if (mode == 3 && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
-    if (n_queries && (!queries || !hits || !nhits || (mode == 3 && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
+    if (mode >= 3 && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !nhits || (mode >= 3 && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
     std::vector<nextsearch::Engine::QueryView> views(n_queries);
     for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
     std::vector<nsx::PageCursor> cur;
@@ -1180,7 +1180,8 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_so
     if (!rest) { r_.resize(n_queries); rest = r_.data(); }
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     bool ok;
-    if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    if (mode == 4) ok = e->eng.search_boolean_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 2) ok = e->eng.search_boolean_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     else ok = e->eng.search_after_batch_flat(filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
@@ -1213,17 +1214,102 @@ extern "C" int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sor
 } NSH_CATCH(e, "nsh_engine_search_sorted_after_batch", -1)
 }
 
+// ---- facet counts and date order for boolean queries ----
+extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                              uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    if (!e) return -1;
+    nsx::FacetSpec sp;
+    std::string why;
+    if (!nsh_facet_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && !queries) { nsh_set_err(e, "nsh_engine_facet_boolean_batch: queries is NULL"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    std::vector<uint32_t> counts;
+    std::vector<std::string> labels;
+    if (!e->eng.facet_boolean_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    if (counts.size() > counts_cap || (!counts.empty() && !counts_out)) {
+        nsh_set_err(e, "nsh_engine_facet_boolean_batch: counts_out holds " + std::to_string(counts_cap) + " entries, " + std::to_string(n_queries) + " queries x " +
+                           std::to_string(labels.size()) + " buckets need " + std::to_string(counts.size()));
+        return -1;
+    }
+    if (!counts.empty()) std::memcpy(counts_out, counts.data(), counts.size() * 4);
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_facet_boolean_batch", -1)
+}
+
+extern "C" int nsh_engine_search_boolean_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                                      uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                                      uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_boolean_sorted_batch", 4, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_boolean_sorted_batch", -1)
+}
+
+extern "C" int nsh_engine_search_boolean_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                                      const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::FacetSpec sp;
+    bool ok = nsh_facet_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_boolean_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_boolean_faceted_json", -1)
+}
+
+extern "C" int nsh_engine_search_boolean_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                                     const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::SortSpec sp;
+    bool ok = nsh_sort_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_boolean_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+} NSH_CATCH(e, "nsh_engine_search_boolean_sorted_json", -1)
+}
+
 extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int k, const char* cursor, uint32_t mode, const nsh_sort_spec* spec, int use_filter,
                                            const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
     if (!e || !json_out) return -1;
     *json_out = nullptr;
     std::string s;
     nsx::PageSpec ps;
-    bool ok = mode <= 3u;
+    bool ok = mode <= 4u;
     if (!ok) s = "search_page: unknown mode " + std::to_string(mode);
     if (ok) {
         ps.mode = (nsx::PageSpec::Mode)mode;
-        if (mode == 3u) ok = nsh_sort_spec_of(e, spec, ps.sort, s);
+        if (mode >= 3u) ok = nsh_sort_spec_of(e, spec, ps.sort, s);
     }
     if (ok) {
         ps.use_filter = use_filter != 0;

@@ -24,7 +24,11 @@
 //   ns_tool search-boolean <index_dir> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean: `+word` must be held, `-word` must not, other words are optional (boolean.hpp); search's JSON
 //        body plus "boolean".  from / to as search-filtered's; "-" "-" searches the whole index.
-//   ns_tool page <index_dir> <or|and|boolean|newest|oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
+//   ns_tool search-boolean-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>   (needs an MI355X)
+//        Engine::search_boolean_faceted: search-boolean's JSON body plus "facets", as search-faceted's.
+//   ns_tool search-boolean-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
+//        Engine::search_boolean_sorted: search-boolean's JSON body with "results" in date order plus "sort", as search-sorted's.
+//   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
 //        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
 //        "remaining"} (page.hpp).  cursor: "-" for the first page, else a page's "next".  from / to as search-filtered's.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
@@ -138,6 +142,44 @@ int main(int argc, char** argv) {
         std::printf("%s\n", body.c_str());
         return 0;
     }
+    if (argc >= 8 && std::strcmp(argv[1], "search-boolean-faceted") == 0) {
+        nsx::FacetSpec spec;
+        if (std::strcmp(argv[3], "year") == 0) spec.kind = nsx::FacetSpec::Year;
+        else if (std::strcmp(argv[3], "month") == 0) spec.kind = nsx::FacetSpec::Month;
+        else { std::fprintf(stderr, "search-boolean-faceted: the facet is year or month, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) f.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) f.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        std::string q, body;
+        for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean-faceted failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 8 && std::strcmp(argv[1], "search-boolean-sorted") == 0) {
+        nsx::SortSpec spec;
+        if (std::strcmp(argv[3], "newest") == 0) spec.ascending = false;
+        else if (std::strcmp(argv[3], "oldest") == 0) spec.ascending = true;
+        else { std::fprintf(stderr, "search-boolean-sorted: the order is newest or oldest, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) f.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) f.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        std::string q, body;
+        for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean-sorted failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
     if (argc >= 9 && std::strcmp(argv[1], "page") == 0) {
         nsx::PageSpec spec;
         if (std::strcmp(argv[3], "or") == 0) spec.mode = nsx::PageSpec::SearchOr;
@@ -145,7 +187,9 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[3], "boolean") == 0) spec.mode = nsx::PageSpec::Boolean;
         else if (std::strcmp(argv[3], "newest") == 0) { spec.mode = nsx::PageSpec::Sorted; spec.sort.ascending = false; }
         else if (std::strcmp(argv[3], "oldest") == 0) { spec.mode = nsx::PageSpec::Sorted; spec.sort.ascending = true; }
-        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest or oldest, not %s\n", argv[3]); return 2; }
+        else if (std::strcmp(argv[3], "boolean-newest") == 0) { spec.mode = nsx::PageSpec::BooleanSorted; spec.sort.ascending = false; }
+        else if (std::strcmp(argv[3], "boolean-oldest") == 0) { spec.mode = nsx::PageSpec::BooleanSorted; spec.sort.ascending = true; }
+        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest, oldest, boolean-newest or boolean-oldest, not %s\n", argv[3]); return 2; }
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }

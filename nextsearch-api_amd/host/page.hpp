@@ -28,13 +28,13 @@ struct PageCursor {
 
 // which call a page is a page of
 struct PageSpec {
-    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3 };
+    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4 };   // BooleanSorted: DESIGN.md §5t
     Mode mode = SearchOr;
-    SortSpec sort;                       // Sorted only
+    SortSpec sort;                       // Sorted and BooleanSorted only
     bool use_filter = false;
     DocFilter filter;
 };
-inline char page_kind(PageSpec::Mode m) { return m == PageSpec::Sorted ? 'd' : 's'; }
+inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted) ? 'd' : 's'; }
 
 inline std::string cursor_text(char kind, const PageCursor& c) {
     if (!c.set) return std::string();

@@ -56,7 +56,7 @@ assert HIT_DTYPE.itemsize == C.sizeof(NsHit) == 12
 assert TERM_DTYPE.itemsize == C.sizeof(NsTermRef) == 24
 assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 PAGE_CURSOR_DTYPE = np.dtype([("set", "<u4"), ("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4")])   # nsh_page_cursor: seg is a manifest position
-PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3}
+PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4}
 CURSOR_DTYPE = np.dtype([("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4"), ("set", "<u4")])   # ns_cursor
 
 # every symbol include/nextsearch_hip.h declares
@@ -64,6 +64,7 @@ HIP_SYMBOLS = [
     "ns_facet_upload", "ns_facet_release", "ns_facet_count", "ns_facet_tile_docs",
     "ns_dockeys_upload", "ns_dockeys_release", "ns_search_sorted", "ns_sorted_kernel_ms",
     "ns_search_boolean", "ns_boolean_kernel_ms", "ns_search_boolean_after", "ns_search_sorted_after",
+    "ns_facet_count_boolean", "ns_search_sorted_boolean", "ns_boolean_sets_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -80,6 +81,7 @@ HOST_SYMBOLS = [
     "nsh_parse_boolean", "nsh_engine_search_boolean_batch", "nsh_engine_search_boolean_json",
     "nsh_parse_cursor", "nsh_cursor_text", "nsh_engine_search_after_batch", "nsh_engine_search_boolean_after_batch", "nsh_engine_search_sorted_after_batch",
     "nsh_engine_search_page_json",
+    "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
     "nsh_date_key", "nsh_engine_filter_bits", "nsh_engine_open_filter", "nsh_engine_open_filter_bits", "nsh_engine_close_filter", "nsh_engine_open_filters",
@@ -251,6 +253,9 @@ def hip_lib():
         L.ns_boolean_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         L.ns_search_boolean_after.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_search_sorted_after.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_facet_count_boolean.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
+        L.ns_search_sorted_boolean.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_boolean_sets_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -261,7 +266,8 @@ def hip_lib():
 # counter getters of the counting build (libnextsearch_hip_count.so) -> number of values each returns
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
-                  "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17}
+                  "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
+                  "ns_debug_boolean_sets_counters": 12}
 
 
 def debug_counters(reset=False):
@@ -443,6 +449,10 @@ def host_lib():
         L.nsh_engine_search_boolean_after_batch.argtypes = [vp, u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.nsh_engine_search_sorted_after_batch.argtypes = [vp, C.POINTER(NshSortSpec), u32, C.POINTER(C.c_char_p), u32, i32, u32, vp, vp, vp, vp, vp, vp, vp,
                                                            C.POINTER(C.c_float)]
+        L.nsh_engine_facet_boolean_batch.argtypes = [vp, C.POINTER(NshFacetSpec), u32, C.POINTER(C.c_char_p), u32, vp, u64, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_boolean_sorted_batch.argtypes = [vp, C.POINTER(NshSortSpec), u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_engine_search_boolean_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_search_boolean_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, u32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         _host = L
     return _host
@@ -984,6 +994,71 @@ class Engine:
             raise RuntimeError(f"search_boolean failed: {self.error()}")
         return body
 
+    # ---- facet counts and date order for boolean queries ----
+    def facet_boolean_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
+        """Engine::facet_boolean_batch_flat: (counts Q x n_buckets, found, has_found) over search_boolean_batch's matched set;
+        n_buckets = len(facet_buckets(...)[1]); handle: an open filter's (0: none).  timing=True adds the kernel's device ms."""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        Q = len(queries)
+        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_facet_boolean_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
+                                                    found.ctypes.data, has_found.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"facet_boolean_batch failed: {self.error()}")
+        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+
+    def search_boolean_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
+        """Engine::search_boolean_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found) over
+        search_boolean_batch's matched set in date order; after: None, or per query None | (rank = the sort key, manifest
+        position, docId).  timing=True adds the kernels' device ms."""
+        sp, keep = self._sort_spec(order, custom)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_boolean_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
+                                                            cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
+                                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_boolean_sorted_batch failed: {self.error()}")
+        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_boolean_faceted_json(self, query, k, kind="year", date_filter=None, custom=None, labels=None, check=True):
+        """Engine::search_boolean_faceted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure
+        raises (check=False: returns the {"error": ...} body)."""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_boolean_faceted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df),
+                                                            _as_bytes(dt), int(bool(ku)), C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_boolean_faceted failed: {self.error()}")
+        return body
+
+    def search_boolean_sorted_json(self, query, k, order="newest", date_filter=None, custom=None, check=True):
+        """Engine::search_boolean_sorted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure
+        raises (check=False: returns the {"error": ...} body)."""
+        sp, keep = self._sort_spec(order, custom)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_search_boolean_sorted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df),
+                                                           _as_bytes(dt), int(bool(ku)), C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"search_boolean_sorted failed: {self.error()}")
+        return body
+
     # ---- pages past the first K (DESIGN.md §5s) ----
     def search_after_batch(self, queries, k, after=None, flags=NS_FLAG_OR, handle=0, timing=False):
         """Engine::search_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); after: None, or per query None |
@@ -1034,8 +1109,8 @@ class Engine:
         return out + (float(ms.value),) if timing else out
 
     def search_page_json(self, query, k, cursor="", mode="or", order="newest", date_filter=None, custom=None, check=True):
-        """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" (then order / custom as
-        search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
+        """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" | "boolean_sorted" (the last
+        two: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         out = C.c_void_p()
@@ -1951,6 +2026,56 @@ def boolean_kernel_ms(reset=True):
     """(k_bq_select, k_bq_join) HIP-event ms summed over this thread's ns_search_boolean calls since the last reset"""
     out = (C.c_float * 2)()
     hip_lib().ns_boolean_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+def facet_count_boolean(ctx, qd, refs, roles, seg_ids, segs, tables, n_buckets):
+    """ns_facet_count_boolean (raw): (rc, counts Q x n_buckets, found, device ms); roles: one uint8 per ref, or None (all
+    SHOULD); segs / tables: lists of handles.  The outputs are pre-filled with 0xAB bytes."""
+    Q = len(qd)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    counts = np.full((max(Q, 1), int(n_buckets)), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_facet_count_boolean(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                          ro.ctypes.data if ro is not None and len(ro) else None, len(refs),
+                                          ids.ctypes.data if len(ids) else None, sa, ta, len(ids), counts.ctypes.data, found.ctypes.data, C.byref(ms))
+    return rc, counts[:Q], found[:Q], float(ms.value)
+
+
+def search_sorted_boolean_raw(ctx, qd, refs, roles, k, flags, after, seg_ids, segs, tables):
+    """ns_search_sorted_boolean (raw): (rc, hits Q x K, keys Q x K, nhits, found, rest, device ms); roles: one uint8 per ref, or
+    None (all SHOULD); flags: NS_SORT_ASC or 0; after: None or a CURSOR_DTYPE array (rank = the key as uploaded); segs / tables:
+    lists of handles.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    keys = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_sorted_boolean(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                            ro.ctypes.data if ro is not None and len(ro) else None, len(refs), int(k), int(flags),
+                                            cu.ctypes.data if cu is not None and len(cu) else None,
+                                            ids.ctypes.data if len(ids) else None, sa, ta, len(ids), hits.ctypes.data, keys.ctypes.data,
+                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+def boolean_sets_kernel_ms(reset=True):
+    """(k_bs_count, k_bs_select, k_sd_join, k_bs_score) HIP-event ms summed over this thread's ns_facet_count_boolean and
+    ns_search_sorted_boolean calls since the last reset"""
+    out = (C.c_float * 4)()
+    hip_lib().ns_boolean_sets_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
