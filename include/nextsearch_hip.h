@@ -711,6 +711,46 @@ int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t
  * tools/boolean_sets_bench.py. */
 int ns_boolean_sets_kernel_ms(float* out4, int reset);
 
+/* ---- any-of groups in boolean queries ------------------------------------------ */
+/* One level of grouping, conjunctive normal form: a required clause may be a SET of terms, of which a document must hold at
+ * least one:  +(coronavirus covid sars) +(vaccine vaccination) -mouse safety.  Each call is its boolean sibling (ns_search_boolean_after,
+ * ns_facet_count_boolean, ns_search_sorted_boolean) with clauses[r] next to roles[r]: the clause of terms[r].
+ *   clauses[r]   is read for NS_ROLE_MUST refs only; the values on SHOULD and NOT refs are ignored.  Values need not be dense
+ *                or ordered.  Per (query, segment) group the MUST refs with equal value form one clause.
+ *   MATCHED SET  refs of a clause with count == 0 are dropped; a clause whose refs ALL have count == 0 kills the group (one-ref
+ *                clauses: "a MUST ref with count == 0 kills the group").  S and X as in ns_search_boolean.  At least one
+ *                clause: the documents that lie in at least one list of EVERY clause and in no list of X.  No clause, S not
+ *                empty: the documents in at least one list of S and in no list of X.  Otherwise nothing.  Postings with
+ *                docId >= n_docs are ignored; a list named twice in a clause matches once.
+ *   SCORE, ORDER, HITS, cursors, found, rest, ODD NUMBERS: exactly the sibling's.  The score runs over all MUST and SHOULD
+ *                refs in query order, duplicates included; a clause member that does not hold the document adds nothing.
+ *   clauses == NULL: the call IS its sibling (the same plan, the same kernels, the same bytes out).  Clause values that are all
+ *                distinct give the sibling's answers byte for byte, through the grouped kernels.  One clause holding every ref
+ *                gives the answers of roles == NULL.
+ * Refusals are the siblings'. */
+int ns_search_grouped_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                            const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the sibling */,
+                            uint32_t n_terms, uint32_t k, const ns_cursor* after /* n_queries; NULL = none (page 1) */,
+                            const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out /* Q x K */,
+                            uint32_t* nhits_out, uint64_t* found_out /* may be NULL */, uint64_t* rest_out /* may be NULL */,
+                            float* device_ms_out /* may be NULL */);
+int ns_facet_count_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                           const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the sibling */,
+                           uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                           uint32_t* counts_out /* Q x n_buckets */, uint64_t* found_out /* may be NULL */,
+                           float* device_ms_out /* may be NULL */);
+int ns_search_sorted_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                             const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the sibling */,
+                             uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after /* n_queries; NULL = none */,
+                             const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
+                             ns_hit* hits_out /* Q x K */, uint32_t* keys_out /* Q x K */, uint32_t* nhits_out,
+                             uint64_t* found_out /* may be NULL */, uint64_t* rest_out /* may be NULL */,
+                             float* device_ms_out /* may be NULL */);
+/* HIP-event time of the launches of the three calls above that were given clauses (with clauses == NULL the siblings' sums
+ * count them), summed over the calling thread's calls since the last reset: out6[0..5] = k_bq_select, k_bq_join, k_bs_count,
+ * k_bs_select, k_sd_join, k_bs_score, milliseconds; reset != 0 zeroes the sums after the read.  For tools/grouped_bench.py. */
+int ns_grouped_kernel_ms(float* out6, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

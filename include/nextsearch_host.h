@@ -472,6 +472,39 @@ int nsh_engine_search_boolean_sorted_json(nsh_engine* e, const char* query, int 
 int nsh_engine_search_page_json(nsh_engine* e, const char* query, int k, const char* cursor, uint32_t mode, const nsh_sort_spec* spec, int use_filter,
                                 const char* date_from, const char* date_to, int keep_undated, char** json_out);
 
+/* ---- any-of groups in boolean queries (host/grouped.hpp) ----
+ * nsx::parse_grouped: parse_boolean's dialect with one level of parentheses.  A piece that begins, after an optional '+' or '-',
+ * with '(' opens a group that runs to the first ')' (or to the end of the query); every token of its body gets the group's role,
+ * and the tokens of a MUST group share one clause id: `+(covid coronavirus sars) +vaccine -mouse`.  Every other MUST token is a
+ * clause of its own; a text without '(' parses as nsh_parse_boolean parses it.  The terms go to buf joined by single spaces
+ * (truncated to cap - 1 bytes), roles[i] and clauses[i] (i < terms_cap; clause ids count up from 0 in query order, 0 on SHOULD
+ * and NOT terms) next to them; returns the number of terms. */
+uint32_t nsh_parse_grouped(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t terms_cap);
+/* Engine::search_grouped_after_batch_flat, facet_grouped_batch_flat, search_grouped_sorted_batch_flat: the boolean batch calls
+ * (nsh_engine_search_boolean_after_batch, nsh_engine_facet_boolean_batch, nsh_engine_search_boolean_sorted_batch) over that
+ * dialect, parameter for parameter: a document must hold at least one term of every required group.  A term of a group that the
+ * index does not know is dropped; a group of only unknown terms matches nothing.  More than 65 535 required clauses in one query:
+ * -1 with a message. */
+int nsh_engine_search_grouped_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                          const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* has_found, float* device_ms_out);
+int nsh_engine_facet_grouped_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                   uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
+int nsh_engine_search_grouped_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                           uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                           uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_grouped, search_grouped_faceted, search_grouped_sorted: *json_out (free with nsh_free) = the body of
+ * nsh_engine_search_boolean_json / _faceted_json / _sorted_json over this dialect, with "grouped": {"must": [[...], ...], "must_not":
+ * [...], "should": [...]} in place of "boolean" (keys stay sorted): "must" lists the clauses, each the list of its terms.  On failure -1 and
+ * {"error": ...}.  nsh_engine_search_page_json pages them with mode 5 (grouped, cursors of kind 's') and mode 6 (grouped, sorted by
+ * spec, cursors of kind 'd'). */
+int nsh_engine_search_grouped_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                   int keep_undated, char** json_out);
+int nsh_engine_search_grouped_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                           const char* date_to, int keep_undated, char** json_out);
+int nsh_engine_search_grouped_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                          const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3096,13 +3096,13 @@ extern "C" int ns_boolean_kernel_ms(float* out2, int reset) {
 }
 
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
 
 extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                  uint32_t n_terms, uint32_t k, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                                  uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
-    return bq_search(ctx, "ns_search_boolean", queries, n_queries, terms, roles, n_terms, k, nullptr, seg_ids, segs, n_segs, hits_out, nhits_out, found_out,
+    return bq_search(ctx, "ns_search_boolean", queries, n_queries, terms, roles, nullptr, n_terms, k, nullptr, seg_ids, segs, n_segs, hits_out, nhits_out, found_out,
                      nullptr, device_ms_out);
 }
 
@@ -3110,12 +3110,31 @@ extern "C" int ns_search_boolean_after(ns_ctx* ctx, const ns_query_desc* queries
                                        uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs,
                                        uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
                                        float* device_ms_out) {
-    return bq_search(ctx, "ns_search_boolean_after", queries, n_queries, terms, roles, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+    return bq_search(ctx, "ns_search_boolean_after", queries, n_queries, terms, roles, nullptr, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+                     found_out, rest_out, device_ms_out);
+}
+
+// Grouped clauses: clauses == NULL is the sibling, plan and kernels; otherwise bq_plan_grouped and the GROUPED
+// instantiations of the same kernels.  The joins and the score lookup are the siblings'.
+static thread_local float g_gq_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // of the calls with clauses: k_bq_select, k_bq_join, k_bs_count, k_bs_select, k_sd_join, k_bs_score (ns_grouped_kernel_ms)
+
+extern "C" int ns_grouped_kernel_ms(float* out6, int reset) {
+    if (!out6) return NS_E_INVAL;
+    for (int i = 0; i < 6; i++) out6[i] = g_gq_ms[i];
+    if (reset) for (int i = 0; i < 6; i++) g_gq_ms[i] = 0.0f;
+    return NS_OK;
+}
+
+extern "C" int ns_search_grouped_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                       const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids,
+                                       ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out, uint64_t* found_out,
+                                       uint64_t* rest_out, float* device_ms_out) {
+    return bq_search(ctx, "ns_search_grouped_after", queries, n_queries, terms, roles, clauses, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
                      found_out, rest_out, device_ms_out);
 }
 
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (n_queries == 0) { if (device_ms_out) *device_ms_out = 0.0f; return NS_OK; }
@@ -3143,7 +3162,9 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     std::vector<SdBatch> cuts;
     std::string why;
     const uint32_t tile = ns_facet_tile_docs(), win = bq_win_docs(tile);
-    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, tile, refs, items, why) != NS_OK)
+    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    const bool grouped = clauses != nullptr;
+    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, tile, refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
     if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
@@ -3174,7 +3195,8 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
 #if defined(NS_VARIANTS) || defined(NS_COUNT)
     if (lds > (48u << 10))
-        chk(hipFuncSetAttribute(paged ? reinterpret_cast<const void*>(k_bq_select<true>) : reinterpret_cast<const void*>(k_bq_select<false>),
+        chk(hipFuncSetAttribute(grouped ? (paged ? reinterpret_cast<const void*>(k_bq_select<true, true>) : reinterpret_cast<const void*>(k_bq_select<false, true>))
+                                        : (paged ? reinterpret_cast<const void*>(k_bq_select<true>) : reinterpret_cast<const void*>(k_bq_select<false>)),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #endif
     chk(pool_alloc(ctx, (void**)&blk, block_bytes));
@@ -3198,7 +3220,13 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
             const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
             chk(hipEventRecord(evs[c * 3 + 0], st));
             if (n_it) {
-                if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                if (grouped && paged)
+                    hipLaunchKernelGGL((k_bq_select<true, true>), dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
+                                       d_cand, (unsigned long long*)(blk + o_found), d_last + b.item_begin, d_rest);
+                else if (grouped)
+                    hipLaunchKernelGGL((k_bq_select<false, true>), dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
+                                       d_cand, (unsigned long long*)(blk + o_found), (const uint64_t*)nullptr, (unsigned long long*)nullptr);
+                else if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
                     hipLaunchKernelGGL(k_bq_select<true>, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
                                        d_cand, (unsigned long long*)(blk + o_found), d_last + b.item_begin, d_rest);
                 else
@@ -3222,7 +3250,7 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
             for (size_t c = 0; c < cuts.size(); c++)
                 for (int j = 0; j < 2; j++) {
                     float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, evs[c * 3 + j], evs[c * 3 + j + 1]) == hipSuccess) { g_bq_ms[j] += ms; sum += ms; }
+                    if (hipEventElapsedTime(&ms, evs[c * 3 + j], evs[c * 3 + j + 1]) == hipSuccess) { (grouped ? g_gq_ms : g_bq_ms)[j] += ms; sum += ms; }
                 }
             if (device_ms_out) *device_ms_out = sum;
         }
@@ -3244,10 +3272,45 @@ extern "C" int ns_boolean_sets_kernel_ms(float* out4, int reset) {
     return NS_OK;
 }
 
+static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                    const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                    uint32_t* counts_out, uint64_t* found_out, float* device_ms_out);
+static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                     ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
+
 extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                       uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
                                       uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
-    const char* fn = "ns_facet_count_boolean";
+    return bs_facet(ctx, "ns_facet_count_boolean", queries, n_queries, terms, roles, nullptr, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
+}
+
+extern "C" int ns_facet_count_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                      const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables,
+                                      uint32_t n_segs, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+    return bs_facet(ctx, "ns_facet_count_grouped", queries, n_queries, terms, roles, clauses, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
+}
+
+extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                        uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                                        ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
+                                        uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    return bs_sorted(ctx, "ns_search_sorted_boolean", queries, n_queries, terms, roles, nullptr, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
+                     keys_out, nhits_out, found_out, rest_out, device_ms_out);
+}
+
+extern "C" int ns_search_sorted_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                        const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after,
+                                        const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out,
+                                        uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    return bs_sorted(ctx, "ns_search_sorted_grouped", queries, n_queries, terms, roles, clauses, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
+                     keys_out, nhits_out, found_out, rest_out, device_ms_out);
+}
+
+static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                    const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                    uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
     if (n_queries == 0) return NS_OK;
@@ -3274,7 +3337,9 @@ extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries,
     std::vector<BqRef> refs;
     std::vector<FcItem> items;
     std::string why;
-    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    const bool grouped = clauses != nullptr;
+    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
     const size_t n_counts = (size_t)n_queries * B;
@@ -3299,7 +3364,10 @@ extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries,
             chk(hipMemsetAsync(blk + o_counts, 0, n_counts * 4, st));
             chk(hipEventRecord(ev0, st));
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_bs_count, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
+                if (grouped)
+                    hipLaunchKernelGGL(k_bs_count<true>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
+                else
+                    hipLaunchKernelGGL(k_bs_count<false>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
                 chk(hipGetLastError());
             }
             chk(hipEventRecord(ev1, st));
@@ -3307,7 +3375,7 @@ extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries,
             chk(hipStreamSynchronize(st));
             float ms = 0.0f;
             if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
-                g_bs_ms[0] += ms;
+                (grouped ? g_gq_ms[2] : g_bs_ms[0]) += ms;
                 if (device_ms_out) *device_ms_out = ms;
             }
         }
@@ -3327,11 +3395,10 @@ extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries,
     return NS_OK;
 }
 
-extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                                        uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
-                                        ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
-                                        uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
-    const char* fn = "ns_search_sorted_boolean";
+static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                     ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
     if (n_queries == 0) return NS_OK;
@@ -3363,7 +3430,9 @@ extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* querie
     std::vector<uint32_t> q_off;
     std::vector<SdBatch> cuts;
     std::string why;
-    if (bq_plan(queries, n_queries, terms, roles, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    const bool grouped = clauses != nullptr;
+    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
     if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
@@ -3421,7 +3490,11 @@ extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* querie
             const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
             chk(hipEventRecord(evs[c * 4 + 0], st));
             if (n_it) {
-                if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                if (grouped && paged)
+                    hipLaunchKernelGGL((k_bs_select<true, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
+                else if (grouped)
+                    hipLaunchKernelGGL((k_bs_select<false, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
+                else if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
                     hipLaunchKernelGGL(k_bs_select<true>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
                 else
                     hipLaunchKernelGGL(k_bs_select<false>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
@@ -3449,7 +3522,7 @@ extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* querie
             for (size_t c = 0; c < cuts.size(); c++)
                 for (int j = 0; j < 3; j++) {
                     float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { g_bs_ms[1 + j] += ms; sum += ms; }
+                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { (grouped ? g_gq_ms + 3 : g_bs_ms + 1)[j] += ms; sum += ms; }
                 }
             if (device_ms_out) *device_ms_out = sum;
         }
@@ -4156,6 +4229,15 @@ extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bcnt), sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
     if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bcnt), h, sizeof(h)) != hipSuccess) return -1; }
+    return 0;
+}
+// the grouped required stage (ns_boolean.hip k_bq_select<., true>; ns_boolean_sets.hip bs_matched<true>): 11 values
+extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int reset) {
+    unsigned long long h[ns::kNsBgcnt];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bgcnt), sizeof(h)) != hipSuccess) return -1;
+    if (out) std::memcpy(out, h, sizeof(h));
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bgcnt), h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
 // facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values

@@ -11,6 +11,8 @@
 //                           AND-ed in and cleared (as k_sd_select<true>); a MUST list without a posting in the window ends
 //                           the window.  No MUST ref: SHOULD lists mark the matched bitmap.  NOT lists mark the excluded
 //                           bitmap; matched &= ~excluded.  A window without a matched bit ends here (workgroup-uniform).
+//                           GROUPED (§5u): a required clause is a SET of MUST lists; the lists of a clause are OR-ed into one
+//                           bitmap before the AND (see the template parameter below).
 //                   score   the MUST and SHOULD refs in query order, one at a time, a barrier in between: every posting of
 //                           the window whose document is matched does a plain LDS read-add-write
 //                               acc[doc] = acc[doc] + qweight * ((idf * (tf * 2.2f)) / (tf + norm[doc]))   each op rounds to fp32
@@ -49,9 +51,17 @@ constexpr int kNsBcnt = 8;
 __device__ unsigned long long g_ns_bcnt[kNsBcnt];
 #define NS_BCNT(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_ns_bcnt[(i)], (unsigned long long)(v)); } while (0)
 #define NS_BCNT_WAVE(i, v) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&g_ns_bcnt[(i)], (unsigned long long)(v)); } while (0)
+// Grouped clauses (§5u; ns_debug_boolean_groups_counters), the GROUPED instantiations only.  k_bq_select<., true>: 0 work items
+// (one per workgroup); then, counted per window, 1 clauses marked from two or more lists with a posting in the window, 2 clause
+// intersections, 3 windows ended by a clause without a posting, 4 clause members that missed a window their clause still hit.
+// The set kernels (ns_boolean_sets.hip): 5 work items; 6..9 as 1..4, counted per tile (= per item); 10 items on the single-list path.
+constexpr int kNsBgcnt = 11;
+__device__ unsigned long long g_ns_bgcnt[kNsBgcnt];
+#define NS_BGCNT(i, v) do { if (GROUPED && threadIdx.x == 0) atomicAdd(&g_ns_bgcnt[(i)], (unsigned long long)(v)); } while (0)
 #else
 #define NS_BCNT(i, v)
 #define NS_BCNT_WAVE(i, v)
+#define NS_BGCNT(i, v)
 #endif
 
 __device__ __forceinline__ uint32_t bq_ord(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
@@ -75,6 +85,73 @@ __device__ __forceinline__ void bq_insert(SdSet& s, uint64_t key, uint32_t K, ui
 #endif
 }
 
+// The grouped required stage (§5u) over the documents [doc_lo, doc_hi) (a window of k_bq_select, a tile of bs_matched), called by
+// all 256 threads in workgroup-uniform control flow.  For clause c = 0, 1, ... every list of the clause with a posting in the range
+// marks one bitmap (s_bm for c = 0, s_tmp after it) with fc_mark's atomic ORs, no barrier between the lists; then one barrier, and
+// for c > 0 the AND, the clearing of s_tmp and a second barrier.  False (in every thread) when a clause has no posting in the range:
+// nothing was marked for it, s_tmp is clear, and s_bm is not to be read.  A list that misses while another of its clause hits
+// does not end it.  The members of a clause need not be neighbours (the refs stay in query order, which is the score's):
+//   at most 64 refs   `mine` holds, per lane, the clause index of ref `lane` (bq_clause_of_lane: read ONCE per item), and a ballot
+//                     names the members of clause c; the loop then reads the refs it cuts and no other
+//   more than 64      the refs are scanned from the clause's first ref on; the numbering by first appearance puts the first ref
+//                     of clause c + 1 behind it
+// BASE: the first of the four counters (ns_debug_boolean_groups_counters) of the caller.
+constexpr uint32_t kBqNoClause = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t bq_clause_of_lane(const BqRef* __restrict__ rf, uint32_t ref_count, uint32_t lane) {
+    return (lane < ref_count && rf[lane].role == kBqMust) ? rf[lane].clause : kBqNoClause;
+}
+template <int BASE>
+__device__ __forceinline__ bool bq_mark_clauses(const DevFcSeg& sg, const BqRef* __restrict__ rf, uint32_t ref_count, uint32_t n_clauses,
+                                                uint32_t mine, uint32_t doc_lo, uint32_t doc_hi, uint32_t n_words, uint32_t* s_bm,
+                                                uint32_t* s_tmp) {
+    constexpr bool GROUPED = true;   // (NS_BGCNT counts in the grouped instantiations only)
+    (void)GROUPED;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t from = 0;
+    for (uint32_t c = 0; c < n_clauses; c++) {
+        uint32_t hit = 0, missed = 0;   // lists of the clause with / without a posting in the range
+        uint32_t* const bm = c == 0u ? s_bm : s_tmp;
+        if (ref_count <= 64u) {
+            unsigned long long members = __ballot(mine == c);   // (wave-uniform, and the same in all four waves)
+            while (members) {
+                const uint32_t r = (uint32_t)__builtin_ctzll(members);
+                members &= members - 1ull;
+                uint64_t lo, hi;
+                fc_cut(sg, rf[r].list, doc_lo, doc_hi, lane, lo, hi);
+                if (lo == hi) { missed++; continue; }
+                fc_mark(sg.postings, lo, hi, doc_lo, doc_hi, bm);
+                hit++;
+            }
+        } else {
+            uint32_t next = ref_count;
+            for (uint32_t r = from; r < ref_count; r++) {
+                const BqRef b = rf[r];
+                if (b.role != kBqMust) continue;
+                if (b.clause != c) { if (b.clause == c + 1u && next == ref_count) next = r; continue; }
+                uint64_t lo, hi;
+                fc_cut(sg, b.list, doc_lo, doc_hi, lane, lo, hi);
+                if (lo == hi) { missed++; continue; }
+                fc_mark(sg.postings, lo, hi, doc_lo, doc_hi, bm);
+                hit++;
+            }
+            from = next;
+        }
+        if (!hit) { NS_BGCNT(BASE + 2, 1); return false; }   // (workgroup-uniform: the cuts depend on the item and the range alone)
+        if (hit > 1u) NS_BGCNT(BASE, 1);
+        if (missed) NS_BGCNT(BASE + 3, missed);
+        __syncthreads();
+        if (c) {
+            for (uint32_t w = tid; w < n_words; w += 256u) {
+                s_bm[w] &= s_tmp[w];
+                s_tmp[w] = 0u;
+            }
+            __syncthreads();
+            NS_BGCNT(BASE + 1, 1);
+        }
+    }
+    return true;
+}
+
 // Dynamic LDS, and no static LDS in front of it, so that the 8-byte rows stay aligned: 4 KiB row exchange, then win x 4 B
 // accumulators, then three bitmaps of win / 8 B, then the item's matched count.
 __host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (size_t)win * 4u + 3u * (size_t)(win / 8u) + 16u; }
@@ -82,7 +159,10 @@ __host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (s
 // AFTER (§5s, ns_after.hip): last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
 // rest[query] through the word behind s_cnt.  With AFTER = false neither pointer is read and the code is what it was without
 // the parameter.
-template <bool AFTER>
+// GROUPED (§5u): the MUST refs carry a clause index (BqRef::clause, dense per group: bq_plan_grouped), and the required stage
+// of a window is bq_mark_clauses: a clause NONE of whose lists has a posting in the window ends the window.  With GROUPED = false
+// the code is what it was without the parameter.
+template <bool AFTER, bool GROUPED = false>
 __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
                                                    uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -110,11 +190,15 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
         af_count_item(last);
     }
     uint32_t n_must = 0, n_not = 0;   // the same in every thread: they depend on the item alone
+    uint32_t n_clauses = 0;           // GROUPED: 1 + the largest clause index of a MUST ref
     for (uint32_t r = 0; r < it.ref_count; r++) {
         const uint32_t role = rf[r].role;
         n_must += role == kBqMust;
         n_not += role == kBqNot;
+        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, rf[r].clause + 1u);
     }
+    const uint32_t my_clause = GROUPED ? bq_clause_of_lane(rf, it.ref_count, lane) : 0u;   // (once per item, not per window)
+    NS_BGCNT(0, 1);
     SdSet set{0ull, 0ull};
     uint32_t cnt = 0;
     const uint32_t tile_n = it.doc_hi - it.doc_lo;   // <= kFcTileDocs: the tile is the host's
@@ -132,7 +216,9 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
         __syncthreads();
         NS_BCNT(1, 1);
         bool alive = true;   // workgroup-uniform: the cuts depend on the item and the window alone
-        if (n_must) {
+        if (GROUPED && n_must) {
+            alive = bq_mark_clauses<1>(sg, rf, it.ref_count, n_clauses, my_clause, w_lo, w_hi, n_words, s_bm, s_tmp);
+        } else if (n_must) {
             uint32_t seen = 0;
             for (uint32_t r = 0; r < it.ref_count; r++) {
                 const BqRef b = rf[r];

@@ -2,6 +2,8 @@
 // doc-range tile of the facet tile size.  Host code only, like ns_facet_plan.hpp: no HIP runtime call and no device
 // pointer; tests/boolean_plan_harness.cpp compiles it with g++ for the CPU suite.  fc_plan and ns_sorted_plan.hpp are
 // untouched: the items are FcItems, sd_query_items and sd_cut apply to them as they are.
+// Any-of groups: bq_plan_grouped takes a clause value per ref next to its role; bq_plan is that call without
+// clause values (tests/grouped_plan_harness.cpp compiles both).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -27,7 +29,7 @@ struct BqRef {
     FcRef list;
     uint32_t role;
     float idf, qweight;   // unused under kBqNot
-    uint32_t pad;
+    uint32_t clause;      // bq_plan_grouped with clause values, MUST refs: the clause's dense index within the group; else 0
 };
 
 // Checks the descriptors and cuts the items.  Per query the refs are grouped by segment (in the order of the call's segment
@@ -36,9 +38,14 @@ struct BqRef {
 // matches nothing.  Every other group gets one item per tile of [0, n_docs), the last one shorter, query by query.  A ref
 // that scores (MUST, SHOULD) must have a finite idf and qweight.  Returns NS_OK, or NS_E_INVAL with `err` set and nothing
 // usable in the outputs.
-inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_ref* refs, const uint8_t* roles, uint32_t n_refs,
-                   const FcSegView* segs, uint32_t n_segs, uint32_t tile_docs, std::vector<BqRef>& out_refs,
-                   std::vector<FcItem>& out_items, std::string& err) {
+// Grouped: clauses[r] (parallel to refs; read under kBqMust only) names the clause of a MUST ref.  Per group
+// the MUST refs of equal value form one clause, of which a document must hold at least one list: its refs without postings
+// are dropped, and a clause ALL of whose refs are without postings kills the group.  BqRef::clause is the clause's dense
+// index within the group, numbered by first appearance among the refs that survive.  clauses == nullptr: every MUST ref is
+// a clause of its own, clause stays 0, and the output is bq_plan's byte for byte.
+inline int bq_plan_grouped(const ns_query_desc* qd, uint32_t n_queries, const ns_term_ref* refs, const uint8_t* roles, const uint16_t* clauses,
+                           uint32_t n_refs, const FcSegView* segs, uint32_t n_segs, uint32_t tile_docs, std::vector<BqRef>& out_refs,
+                           std::vector<FcItem>& out_items, std::string& err) {
     out_refs.clear();
     out_items.clear();
     auto refuse = [&](const std::string& why) { out_refs.clear(); out_items.clear(); err = why; return NS_E_INVAL; };
@@ -53,6 +60,8 @@ inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_re
         return (it != by_id.end() && it->first == id) ? (int64_t)it->second : -1;
     };
     std::vector<std::pair<uint32_t, uint32_t>> order;   // (position of the segment, ref index) of one query
+    std::vector<uint8_t> live(clauses ? 65536u : 0u, 0);   // per clause value: 1 = named by the group, 2 = a ref of it has postings
+    std::vector<uint32_t> dense(clauses ? 65536u : 0u, 0);  // per clause value that survives: its dense index
     for (uint32_t q = 0; q < n_queries; q++) {
         const uint64_t tb = qd[q].term_begin, tc = qd[q].term_count;
         if (tb + tc > n_refs) return refuse(fc_format("query %u: refs [%llu, %llu) run past the %u given", q, (unsigned long long)tb, (unsigned long long)(tb + tc), n_refs));
@@ -75,16 +84,34 @@ inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_re
             const FcSegView& sv = segs[order[i].first];
             const uint32_t begin = (uint32_t)out_refs.size();
             bool dead = false;
-            uint32_t positive = 0;
+            uint32_t positive = 0, n_clauses = 0;
+            if (clauses && roles) {
+                for (size_t k = i; k < j; k++)
+                    if (roles[order[k].second] == kBqMust) {
+                        uint8_t& l = live[clauses[order[k].second]];
+                        l = std::max<uint8_t>(l, refs[order[k].second].count ? 2 : 1);
+                    }
+                for (size_t k = i; k < j; k++)
+                    if (roles[order[k].second] == kBqMust) dead = dead || live[clauses[order[k].second]] == 1;
+            }
             for (size_t k = i; k < j; k++) {
                 const ns_term_ref& t = refs[order[k].second];
                 const uint32_t role = roles ? roles[order[k].second] : kBqShould;
-                if (!t.count) { dead = dead || role == kBqMust; continue; }
+                if (!t.count) { dead = dead || (role == kBqMust && !clauses); continue; }
                 const uint64_t first = t.byte_off / 8;
                 const uint32_t skip = (sv.skip_of && first < (1ull << 32)) ? sv.skip_of((uint32_t)first, t.count) : 0u;
-                out_refs.push_back(BqRef{FcRef{first, t.count, skip}, role, t.idf, t.qweight, 0u});
+                uint32_t clause = 0;
+                if (clauses && role == kBqMust) {
+                    const uint16_t c = clauses[order[k].second];
+                    if (live[c] == 2) { live[c] = 3; dense[c] = n_clauses++; }   // 3 = numbered
+                    clause = dense[c];
+                }
+                out_refs.push_back(BqRef{FcRef{first, t.count, skip}, role, t.idf, t.qweight, clause});
                 positive += role != kBqNot;
             }
+            if (clauses && roles)
+                for (size_t k = i; k < j; k++)
+                    if (roles[order[k].second] == kBqMust) live[clauses[order[k].second]] = 0;
             const uint32_t count = (uint32_t)out_refs.size() - begin;
             if (dead || !positive || !sv.n_docs) out_refs.resize(begin);
             else
@@ -94,6 +121,12 @@ inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_re
         }
     }
     return NS_OK;
+}
+
+inline int bq_plan(const ns_query_desc* qd, uint32_t n_queries, const ns_term_ref* refs, const uint8_t* roles, uint32_t n_refs,
+                   const FcSegView* segs, uint32_t n_segs, uint32_t tile_docs, std::vector<BqRef>& out_refs,
+                   std::vector<FcItem>& out_items, std::string& err) {
+    return bq_plan_grouped(qd, n_queries, refs, roles, nullptr, n_refs, segs, n_segs, tile_docs, out_refs, out_items, err);
 }
 
 }  // namespace ns

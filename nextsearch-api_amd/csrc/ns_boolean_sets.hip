@@ -15,6 +15,8 @@
 //                 af_clip; the four waves' sets meet in LDS, wave 0 joins them and writes the item's row of K candidates;
 //                 found / rest get one integer atomic each, as k_sd_select.
 //   k_bs_score    k_sd_score's lookup with a role per ref: NOT refs are skipped.
+// The GROUPED instantiations of k_bs_count and k_bs_select (§5u) differ in bs_matched's required stage alone; k_bs_score serves
+// them as it is: a clause member that does not hold the document adds nothing.
 // An item of ONE ref needs no bitmap (bq_plan emits it only when the ref is MUST or SHOULD): its in-tile postings are its
 // documents.  Every docId read from a list is tested against the tile before it indexes LDS, the bucket table or the key table.
 // Static LDS: 36 KiB per workgroup in both kernels (2 x 16 KiB bitmaps + 4 KiB histogram or row exchange).
@@ -62,6 +64,9 @@ __device__ __forceinline__ void bs_insert(SdSet& s, uint64_t key, uint32_t K, ui
 // The matched set of item `it` (ref_count >= 2) as bits of s_bm; s_tmp is the scratch bitmap.  Both hold at least
 // n_words = ceil((doc_hi - doc_lo) / 32) <= kFcTileDocs / 32 words.  Called by all 256 threads; ends behind a barrier.  False
 // (in every thread) when a MUST list has no posting in the tile: the item matches nothing and s_bm is not to be read.
+// GROUPED (§5u): the required stage is ns_boolean.hip's bq_mark_clauses over the tile, as k_bq_select<., true>'s is over a window;
+// false when a clause has no posting in the tile.  The scratch bitmap is clear when the NOT lists arrive, as before.
+template <bool GROUPED>
 __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg, const BqRef* __restrict__ rf, uint32_t n_words,
                                            uint32_t* s_bm, uint32_t* s_tmp) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -70,13 +75,18 @@ __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg,
         s_tmp[w] = 0u;
     }
     uint32_t n_must = 0, n_not = 0;   // the same in every thread: they depend on the item alone
+    uint32_t n_clauses = 0;           // GROUPED: 1 + the largest clause index of a MUST ref
     for (uint32_t r = 0; r < it.ref_count; r++) {
         const uint32_t role = rf[r].role;
         n_must += role == kBqMust;
         n_not += role == kBqNot;
+        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, rf[r].clause + 1u);
     }
+    const uint32_t my_clause = GROUPED ? bq_clause_of_lane(rf, it.ref_count, lane) : 0u;
     __syncthreads();
-    if (n_must) {
+    if (GROUPED && n_must) {
+        if (!bq_mark_clauses<6>(sg, rf, it.ref_count, n_clauses, my_clause, it.doc_lo, it.doc_hi, n_words, s_bm, s_tmp)) return false;
+    } else if (n_must) {
         uint32_t seen = 0;
         for (uint32_t r = 0; r < it.ref_count; r++) {
             const BqRef b = rf[r];
@@ -137,6 +147,7 @@ __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg,
     return true;
 }
 
+template <bool GROUPED = false>
 __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                   const DevFcSeg* __restrict__ segs, uint32_t n_buckets, uint32_t* __restrict__ counts) {
     __shared__ uint32_t s_hist[kFcMaxBuckets];
@@ -148,18 +159,20 @@ __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ ite
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t n_words = (it.doc_hi - it.doc_lo + 31u) / 32u;   // <= kFcTileDocs / 32: the tile is the host's, at most the product's
     NS_BSCNT(0, 1);
+    NS_BGCNT(5, 1);
     for (uint32_t b = tid; b < n_buckets; b += 256u) s_hist[b] = 0u;
     if (it.ref_count == 1u) {
         uint64_t lo, hi;
         fc_cut(sg, rf[0].list, it.doc_lo, it.doc_hi, lane, lo, hi);
         NS_BSCNT(1, 1);
+        NS_BGCNT(10, 1);
         __syncthreads();
         for (uint64_t i = lo + tid; i < hi; i += 256u) {
             const uint32_t d = sg.postings[i].x;
             if (d >= it.doc_lo && d < it.doc_hi) atomicAdd(&s_hist[sg.buckets[d]], 1u);
         }
     } else {
-        if (!bs_matched(it, sg, rf, n_words, s_bm, s_tmp)) return;   // (workgroup-uniform; the histogram is all zero)
+        if (!bs_matched<GROUPED>(it, sg, rf, n_words, s_bm, s_tmp)) return;   // (workgroup-uniform; the histogram is all zero)
         for (uint32_t w = tid; w < n_words; w += 256u) {
             uint32_t bits = s_bm[w];
             while (bits) {
@@ -185,7 +198,7 @@ __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ ite
 // AFTER as in k_sd_select: last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
 // rest[query].  Wave 0's own slot of s_rows is never read back, so under AFTER it is not written and its first word holds the
 // item's count instead.  With AFTER = false neither pointer is read.
-template <bool AFTER>
+template <bool AFTER, bool GROUPED = false>
 __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevSdSeg* __restrict__ sds, uint32_t K,
                                                    uint32_t asc, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -201,6 +214,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
     const uint32_t tid = threadIdx.x, lane = tid & 63u, v = tid >> 6;
     const uint32_t n_words = (it.doc_hi - it.doc_lo + 31u) / 32u;   // <= kFcTileDocs / 32: the tile is the host's, at most the product's
     NS_BSCNT(0, 1);
+    NS_BGCNT(5, 1);
     if (tid == 0) s_cnt = 0u;
     uint32_t* const s_rest = reinterpret_cast<uint32_t*>(&s_rows[0][0]);
     uint64_t last = kAfterAll;
@@ -216,6 +230,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
         uint64_t lo, hi;
         fc_cut(sg, rf[0].list, it.doc_lo, it.doc_hi, lane, lo, hi);
         NS_BSCNT(1, 1);
+        NS_BGCNT(10, 1);
         for (uint64_t base = lo + v * 64u; base < hi; base += 256u) {   // (wave-uniform)
             const uint64_t i = base + lane;
             uint64_t key = 0;
@@ -226,7 +241,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
             if (AFTER) key = af_clip(key, last, kept);
             bs_insert(set, key, K, lane);
         }
-    } else if (bs_matched(it, sg, rf, n_words, s_bm, s_tmp)) {          // (workgroup-uniform)
+    } else if (bs_matched<GROUPED>(it, sg, rf, n_words, s_bm, s_tmp)) { // (workgroup-uniform)
         for (uint32_t wb = v * 64u; wb < n_words; wb += 256u) {         // (wave-uniform)
             const uint32_t w = wb + lane;
             uint32_t bits = w < n_words ? s_bm[w] : 0u;

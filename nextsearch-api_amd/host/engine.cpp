@@ -2403,12 +2403,66 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
 // ---- boolean queries (host/boolean.hpp, csrc/ns_boolean.hip) -------------------------------------------
 bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
                                        uint64_t* found, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_batch_flat", filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
+    return boolean_batch_impl("search_boolean_batch_flat", false, filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
 }
 
 bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                                              uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_after_batch_flat", filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+    return boolean_batch_impl("search_boolean_after_batch_flat", false, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+// ---- any-of groups in boolean queries (host/grouped.hpp) -------------------------------------------------
+bool Engine::search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                             uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl("search_grouped_after_batch_flat", true, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                      uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    return boolean_facet_impl("facet_grouped_batch_flat", true, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::search_grouped_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                              uint8_t* usable, float* device_ms) {
+    return boolean_sorted_impl("search_grouped_sorted_batch_flat", true, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+// boolean_refs_range over parse_grouped's dialect, with the clause id of every ref next to its role; false, with a message, when
+// a query has more clauses than a clause value can name
+bool Engine::grouped_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
+    const uint32_t S = (uint32_t)segments.size();
+    const nsx::RowSource& rs = bp.rs;
+    bp.qd.assign(b - a, ns_query_desc{0, 0});
+    bp.refs.clear();
+    bp.roles.clear();
+    bp.clauses.clear();
+    for (size_t q = a; q < b; q++) {
+        bp.terms.clear();
+        bp.term_clauses.clear();
+        size_t positive = 0;
+        const uint32_t n_clauses = nsx::for_each_grouped_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause) {
+            bp.terms.emplace_back(dict.find(p, n), role);
+            bp.term_clauses.push_back(clause);
+            positive += role != nsx::kRoleNot;
+        });
+        if (n_clauses > 65535u) { err_ = std::string(fn) + ": query " + std::to_string(q) + " has " + std::to_string(n_clauses) + " required clauses (at most 65535)"; return false; }
+        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
+        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
+        if (!usable[q]) continue;
+        for (const uint32_t sid : bp.listed)
+            for (size_t i = 0; i < bp.terms.size(); i++) {
+                const auto& t = bp.terms[i];
+                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
+                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                else if (t.second == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
+                else continue;
+                bp.roles.push_back(t.second);
+                bp.clauses.push_back((uint16_t)bp.term_clauses[i]);
+            }
+        bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
+    }
+    return true;
 }
 
 // What search_boolean_batch_flat, facet_boolean_batch_flat and search_boolean_sorted_batch_flat share.  boolean_prepare: the
@@ -2469,8 +2523,8 @@ void Engine::boolean_refs_range(const QueryView* queries, size_t a, size_t b, ui
     }
 }
 
-bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
-                                uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+bool Engine::boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+                                ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
@@ -2485,7 +2539,8 @@ bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const Qu
     const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        boolean_refs_range(queries, a, b, usable, bp);
+        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
+        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
         if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
@@ -2495,10 +2550,13 @@ bool Engine::boolean_batch_impl(const char* fn, uint32_t filter_handle, const Qu
             continue;
         }
         float ms = 0.0f;
-        const int rc = ns_search_boolean_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
-                                               cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * K, nhits + a,
-                                               found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
+        const int rc = grouped ? ns_search_grouped_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+                                                         (uint32_t)bp.refs.size(), (uint32_t)K, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
+                                                         (uint32_t)bp.ids.size(), hits + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
+                               : ns_search_boolean_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
+                                                         cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * K, nhits + a,
+                                                         found + a, rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_search_grouped_after: " : after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
@@ -2527,9 +2585,69 @@ static std::string boolean_member(const std::string& query) {
     return o;
 }
 
+// the "grouped" member of search_grouped's body (§5u), which search_boolean's "boolean" member becomes: "must" is a list of clauses,
+// each the list of its terms, in query order; "must_not" and "should" as in boolean_member.  nlohmann keeps keys sorted, so the
+// member stands between "found" and "k" (grouped_insert), where "boolean" is the body's first.
+static std::string grouped_member(const std::string& query) {
+    const std::vector<nsx::GroupedTerm> terms = nsx::parse_grouped(query);
+    std::string o = "  \"grouped\": {\n    \"must\": [";
+    bool any_clause = false;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (terms[i].role != nsx::kRoleMust) continue;
+        bool first_of_clause = true;
+        for (size_t j = 0; j < i; j++) first_of_clause = first_of_clause && !(terms[j].role == nsx::kRoleMust && terms[j].clause == terms[i].clause);
+        if (!first_of_clause) continue;
+        o += any_clause ? ",\n      [" : "\n      [";
+        bool any = false;
+        for (size_t j = i; j < terms.size(); j++)
+            if (terms[j].role == nsx::kRoleMust && terms[j].clause == terms[i].clause) {
+                o += any ? ",\n        " : "\n        ";
+                json_escape(o, terms[j].text);
+                any = true;
+            }
+        o += "\n      ]";
+        any_clause = true;
+    }
+    o += any_clause ? "\n    ],\n" : "],\n";
+    static const struct { const char* name; uint8_t role; } kMembers[2] = {{"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
+    for (int m = 0; m < 2; m++) {
+        o += std::string("    \"") + kMembers[m].name + "\": [";
+        bool any = false;
+        for (const nsx::GroupedTerm& t : terms)
+            if (t.role == kMembers[m].role) {
+                o += any ? ",\n      " : "\n      ";
+                json_escape(o, t.text);
+                any = true;
+            }
+        o += any ? "\n    ]" : "]";
+        o += m < 1 ? ",\n" : "\n";
+    }
+    o += "  },\n";
+    return o;
+}
+
+// tail: to_json_impl's members from "found" (when usable) or "k" on; "found" is a number and "query" comes behind "k", so the first
+// line that starts like the "k" member is it
+static bool grouped_insert(std::string& tail, const std::string& query) {
+    size_t at = tail.compare(0, 7, "  \"k\": ") == 0 ? 0 : tail.find("\n  \"k\": ");
+    if (at == std::string::npos) return false;
+    if (at) at++;
+    tail.insert(at, grouped_member(query));
+    return true;
+}
+
 bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return boolean_text_impl("search_boolean", false, query, k, f, body);
+}
+
+bool Engine::search_grouped_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return boolean_text_impl("search_grouped", true, query, k, f, body);
+}
+
+// search_boolean's body, or (grouped) the same body over parse_grouped's dialect with "grouped" in place of "boolean"
+bool Engine::boolean_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
-    if (!ctx_) { body = err_ = "search_boolean: no device context: this engine has no CPU scoring path"; return false; }
+    if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
     const int K = std::max(1, std::min(k, 100));
     uint32_t handle = 0;
     std::string head = "{\n";
@@ -2538,7 +2656,7 @@ bool Engine::search_boolean_text(const std::string& query, int k, const nsx::Doc
         if (!search_filtered_text(std::string(), K, *f, ignored)) { body = err_; return false; }
         handle = filter_lru_.front().handle;
         const size_t at = ignored.find("\n  },\n");
-        if (ignored.compare(0, 14, "{\n  \"filter\": ") != 0 || at == std::string::npos) { body = err_ = "search_boolean: the filtered body has no filter member"; return false; }
+        if (ignored.compare(0, 14, "{\n  \"filter\": ") != 0 || at == std::string::npos) { body = err_ = std::string(name) + ": the filtered body has no filter member"; return false; }
         head = ignored.substr(0, at + 6);
     }
     const QueryView qv{query.data(), query.size()};
@@ -2546,7 +2664,8 @@ bool Engine::search_boolean_text(const std::string& query, int k, const nsx::Doc
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us)) { body = err_; return false; }
+    if (!(grouped ? search_grouped_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
+                  : search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us))) { body = err_; return false; }
     SearchResult res;
     res.query = query;
     res.k = K;
@@ -2556,8 +2675,41 @@ bool Engine::search_boolean_text(const std::string& query, int k, const nsx::Doc
     if (res.has_found)
         for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     // "boolean" < "filter" < "found": nlohmann keeps keys sorted, so the member sits in front
-    body = "{\n" + boolean_member(query) + head.substr(2) + to_json_impl(res).substr(2);
+    if (!grouped) { body = "{\n" + boolean_member(query) + head.substr(2) + to_json_impl(res).substr(2); return true; }
+    std::string tail = to_json_impl(res).substr(2);
+    if (!grouped_insert(tail, query)) { body = err_ = std::string(name) + ": the search body has no k member"; return false; }
+    body = head + tail;
     return true;
+}
+
+static std::string error_body(const std::string& why) {
+    std::string o = "{\n  \"error\": ";
+    json_escape(o, why);
+    o += "\n}";
+    return o;
+}
+
+std::string Engine::search_grouped(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    return search_grouped_text(query, k, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_grouped_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_grouped_faceted_text(query, k, spec, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_grouped_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_grouped_sorted_text(query, k, spec, f, body) ? body : error_body(body);
+}
+
+bool Engine::search_grouped_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_faceted_text_impl("search_grouped_faceted", true, query, k, spec, f, body);
+}
+
+bool Engine::search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_sorted_text_impl("search_grouped_sorted", true, query, k, spec, f, body);
 }
 
 std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
@@ -2574,7 +2726,11 @@ std::string Engine::search_boolean(const std::string& query, int k, const nsx::D
 // ---- facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip) --------------------------
 bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
                                       uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    const char* fn = "facet_boolean_batch_flat";
+    return boolean_facet_impl("facet_boolean_batch_flat", false, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                                std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     counts.clear();
     labels.clear();
@@ -2598,15 +2754,19 @@ bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filte
     const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        boolean_refs_range(queries, a, b, usable, bp);
+        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
+        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
             continue;
         }
         float ms = 0.0f;
-        const int rc = ns_facet_count_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), bp.ids.data(),
-                                              bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
-        if (rc != NS_OK) { err_ = std::string("ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
+        const int rc = grouped ? ns_facet_count_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+                                                        (uint32_t)bp.refs.size(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
+                                                        counts.data() + a * B, found + a, &ms)
+                               : ns_facet_count_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), bp.ids.data(),
+                                                        bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
+        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_facet_count_grouped: " : "ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
     }
     return true;
@@ -2615,7 +2775,12 @@ bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filte
 bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                                               const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                               uint8_t* usable, float* device_ms) {
-    const char* fn = "search_boolean_sorted_batch_flat";
+    return boolean_sorted_impl("search_boolean_sorted_batch_flat", false, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                 const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                                 float* device_ms) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
@@ -2637,7 +2802,8 @@ bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_
     const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        boolean_refs_range(queries, a, b, usable, bp);
+        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
+        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
         if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
@@ -2648,10 +2814,14 @@ bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_
             continue;
         }
         float ms = 0.0f;
-        const int rc = ns_search_sorted_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
-                                                spec.ascending ? NS_SORT_ASC : NS_SORT_DESC, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
-                                                tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string("ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
+        const int rc = grouped ? ns_search_sorted_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+                                                          (uint32_t)bp.refs.size(), (uint32_t)K, spec.ascending ? NS_SORT_ASC : NS_SORT_DESC,
+                                                          cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
+                                                          hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
+                               : ns_search_sorted_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
+                                                          spec.ascending ? NS_SORT_ASC : NS_SORT_DESC, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
+                                                          tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
+        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_search_sorted_grouped: " : "ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
@@ -2660,20 +2830,29 @@ bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_
 }
 
 bool Engine::search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_faceted_text_impl("search_boolean_faceted", false, query, k, spec, f, body);
+}
+
+bool Engine::boolean_faceted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
+                                       std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
-    if (!ctx_) { body = err_ = "search_boolean_faceted: no device context: this engine has no CPU scoring path"; return false; }
-    if (!search_boolean_text(query, k, f, body)) return false;
+    if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
+    if (!(grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const QueryView qv{query.data(), query.size()};
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels)) { body = err_; return false; }
+    if (!(grouped ? facet_grouped_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels))) { body = err_; return false; }
     // "boolean" < "facets" < "filter" < "found": the member goes behind the "boolean" member, which is the body's first and whose
     // strings are escaped, so that its closing line is the first of that form
     const size_t at = body.find("\n  },\n");
-    if (body.compare(0, 15, "{\n  \"boolean\": ") != 0 || at == std::string::npos) { body = err_ = "search_boolean_faceted: the boolean body has no boolean member"; return false; }
+    if (grouped) {   // "facets" < "filter" < "found" < "grouped": the member is the body's first
+        body.insert(2, facets_member(spec, labels, counts));
+        return true;
+    }
+    if (body.compare(0, 15, "{\n  \"boolean\": ") != 0 || at == std::string::npos) { body = err_ = std::string(name) + ": the boolean body has no boolean member"; return false; }
     body.insert(at + 6, facets_member(spec, labels, counts));
     return true;
 }
@@ -2690,9 +2869,14 @@ std::string Engine::search_boolean_faceted(const std::string& query, int k, cons
 }
 
 bool Engine::search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_sorted_text_impl("search_boolean_sorted", false, query, k, spec, f, body);
+}
+
+bool Engine::boolean_sorted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
+                                      std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
-    if (!ctx_) { body = err_ = "search_boolean_sorted: no device context: this engine has no CPU scoring path"; return false; }
-    if (!search_boolean_text(query, k, f, body)) return false;
+    if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
+    if (!(grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const size_t K = (size_t)std::max(1, std::min(k, 100));
     const QueryView qv{query.data(), query.size()};
@@ -2701,13 +2885,14 @@ bool Engine::search_boolean_sorted_text(const std::string& query, int k, const n
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!search_boolean_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)) { body = err_; return false; }
+    if (!(grouped ? search_grouped_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
+                  : search_boolean_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us))) { body = err_; return false; }
     std::vector<SearchHit> sorted;
     if (us)
         for (uint32_t i = 0; i < nh; i++) sorted.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     // the body's "results" member replaced ("query" is escaped: no line of it starts like a member), "sort" behind "segments"
     const size_t a = body.find("\n  \"results\": "), b = body.rfind("\n  \"segments\": ");
-    if (a == std::string::npos || b == std::string::npos || b < a || body.size() < 2) { body = err_ = "search_boolean_sorted: the boolean body has no results member"; return false; }
+    if (a == std::string::npos || b == std::string::npos || b < a || body.size() < 2) { body = err_ = std::string(name) + ": the boolean body has no results member"; return false; }
     std::string o = body.substr(0, a + 1);
     append_results_json(o, sorted);
     o += body.substr(b + 1, body.size() - (b + 1) - 2);   // "  \"segments\": N", without the closing "\n}"
@@ -2816,7 +3001,7 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
-    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::BooleanSorted) { body = err_ = "search_page: unknown mode"; return false; }
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::GroupedSorted) { body = err_ = "search_page: unknown mode"; return false; }
     const char kind = nsx::page_kind(spec.mode);
     nsx::PageCursor cur;
     if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
@@ -2852,6 +3037,12 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
         case nsx::PageSpec::BooleanSorted:
             ok = search_boolean_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
             break;
+        case nsx::PageSpec::Grouped:
+            ok = search_grouped_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
+            break;
+        case nsx::PageSpec::GroupedSorted:
+            ok = search_grouped_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
+            break;
     }
     if (!ok) { body = err_; return false; }
     SearchResult res;
@@ -2866,6 +3057,10 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     if (spec.mode == nsx::PageSpec::Boolean || spec.mode == nsx::PageSpec::BooleanSorted) o += boolean_member(query);   // search_boolean's "boolean" member
     o += head.substr(2);
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
+    if ((spec.mode == nsx::PageSpec::Grouped || spec.mode == nsx::PageSpec::GroupedSorted) && !grouped_insert(rest_of, query)) {   // search_grouped's "grouped" member
+        body = err_ = "search_page: the search body has no k member";
+        return false;
+    }
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
     const size_t at = rest_of.find("  \"query\": ");
     if (at == std::string::npos || (at != 0 && rest_of[at - 1] != '\n')) { body = err_ = "search_page: the search body has no query member"; return false; }

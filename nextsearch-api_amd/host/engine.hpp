@@ -38,6 +38,7 @@
 #include "facet.hpp"
 #include "sorted.hpp"
 #include "boolean.hpp"
+#include "grouped.hpp"
 #include "page.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
@@ -370,6 +371,30 @@ public:
     std::string search_boolean_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
     bool search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
 
+    // Any-of groups in boolean queries (host/grouped.hpp): the three boolean batch calls over nsx::parse_grouped's
+    // dialect, `+(covid coronavirus sars) +vaccine -mouse`.  Each has its sibling's parameters and its sibling's answers for a
+    // text without '('.  The query preparation is boolean_refs_range's with a clause id per MUST ref: every MUST token gets a
+    // ref in every listed segment, with count == 0 where the token is absent or unknown, so an unknown synonym is dropped and a
+    // clause of only unknown words kills the query.  A query with more than 65 535 clauses is refused with a message.
+    bool search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                         uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+    bool facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                  uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms = nullptr);
+    bool search_grouped_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                          const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* usable, float* device_ms = nullptr);
+
+    // JSON text: the boolean siblings' bodies (search_boolean, search_boolean_faceted, search_boolean_sorted) over this dialect,
+    // with "grouped": {"must": [[...], ...], "must_not": [...], "should": [...]} in place of "boolean" (in its sorted place, behind
+    // "found"): "must" lists the clauses, each the list of its terms.  search_page's modes Grouped and GroupedSorted page them with the cursor kinds of
+    // Boolean and BooleanSorted.  Any failure: {"error": ...} (the _text forms: false, body = the message).
+    std::string search_grouped(const std::string& query, int k, const nsx::DocFilter* f = nullptr);
+    bool search_grouped_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    std::string search_grouped_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_grouped_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
+    std::string search_grouped_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
+
     // Pages past the first K (host/page.hpp).  A cursor is a position (rank, manifest position, docId) in a call's
     // total order; with one, a call answers with the first K matched documents STRICTLY AFTER it: found[q] stays the size of
     // the matched set, rest[q] (may be nullptr) is the number of matched documents after the cursor, nhits[q] = min(K, rest[q]).
@@ -471,8 +496,13 @@ private:
     bool sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
                            float* device_ms);
-    bool boolean_batch_impl(const char* fn, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
-                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
+    bool boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+                            ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
+    bool boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                            std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms);
+    bool boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                             float* device_ms);
     // what the three boolean paths share: filter row source, the call's segment list and the refs and roles of a query range
     struct BooleanPrep {
         OpenFilter* f = nullptr;
@@ -483,11 +513,19 @@ private:
         std::vector<ns_query_desc> qd;
         std::vector<ns_term_ref> refs;
         std::vector<uint8_t> roles;
+        std::vector<uint16_t> clauses;                    // grouped_refs_range: parallel to refs
         std::vector<char> scratch;
         std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
+        std::vector<uint32_t> term_clauses;               // grouped_refs_range: parallel to terms
     };
     bool boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp);
     void boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
+    bool boolean_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    bool boolean_faceted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
+                                   std::string& body);
+    bool boolean_sorted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
+                                  std::string& body);
+    bool grouped_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };

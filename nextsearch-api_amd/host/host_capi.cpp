@@ -1160,15 +1160,16 @@ static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<ns
     for (uint32_t q = 0; q < n; q++) { out[q].set = in[q].set != 0; out[q].rank = in[q].rank; out[q].seg = in[q].seg; out[q].doc = in[q].doc; }
 }
 
-// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted
+// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted, 5 grouped, 6 grouped sorted
 static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                            uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                            uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::SortSpec sp;
     std::string why;
-    if (mode >= 3 && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
-    if (n_queries && (!queries || !hits || !nhits || (mode >= 3 && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
+    const bool dated = mode == 3 || mode == 4 || mode == 6;
+    if (dated && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !nhits || (dated && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
     std::vector<nextsearch::Engine::QueryView> views(n_queries);
     for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
     std::vector<nsx::PageCursor> cur;
@@ -1180,7 +1181,9 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_so
     if (!rest) { r_.resize(n_queries); rest = r_.data(); }
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     bool ok;
-    if (mode == 4) ok = e->eng.search_boolean_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    if (mode == 6) ok = e->eng.search_grouped_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 5) ok = e->eng.search_grouped_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 4) ok = e->eng.search_boolean_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 2) ok = e->eng.search_boolean_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     else ok = e->eng.search_after_batch_flat(filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
@@ -1215,13 +1218,118 @@ extern "C" int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sor
 }
 
 // ---- facet counts and date order for boolean queries ----
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, bool grouped, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+                             uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
+
 extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
                                               uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_facet_boolean(e, "nsh_engine_facet_boolean_batch", false, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_facet_boolean_batch", -1)
+}
+
+// ---- any-of groups in boolean queries (host/grouped.hpp) ----
+extern "C" uint32_t nsh_parse_grouped(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t terms_cap) { try {
+    const auto terms = nsx::parse_grouped(query ? query : "");
+    std::string joined;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (i) joined.push_back(' ');
+        joined += terms[i].text;
+        if (roles && i < terms_cap) roles[i] = terms[i].role;
+        if (clauses && i < terms_cap) clauses[i] = terms[i].clause;
+    }
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(joined.size(), cap - 1);
+        std::memcpy(buf, joined.data(), n);
+        buf[n] = 0;
+    }
+    return (uint32_t)terms.size();
+} NSH_CATCH(nullptr, "nsh_parse_grouped", 0)
+}
+
+extern "C" int nsh_engine_search_grouped_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                                     const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                                     uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_grouped_after_batch", 5, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_grouped_after_batch", -1)
+}
+
+extern "C" int nsh_engine_facet_grouped_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                              uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_facet_boolean(e, "nsh_engine_facet_grouped_batch", true, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_facet_grouped_batch", -1)
+}
+
+extern "C" int nsh_engine_search_grouped_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                                      uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                                      uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_grouped_sorted_batch", 6, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_grouped_sorted_batch", -1)
+}
+
+// a JSON body, or on failure the engine's message as {"error": ...}, as a malloc'ed string
+static int nsh_json_out(nsh_engine* e, bool ok, std::string& s, char** json_out) {
+    if (!ok) {
+        nsh_set_err(e, s);
+        std::string o = "{\n  \"error\": ";
+        nextsearch::json_escape(o, s);
+        s = o + "\n}";
+    }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return ok ? 0 : -1;
+}
+
+extern "C" int nsh_engine_search_grouped_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                              int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+    const bool ok = e->eng.search_grouped_text(query ? query : "", k, use_filter ? &f : nullptr, s);
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_grouped_json", -1)
+}
+
+extern "C" int nsh_engine_search_grouped_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                                      const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::FacetSpec sp;
+    bool ok = nsh_facet_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_grouped_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_grouped_faceted_json", -1)
+}
+
+extern "C" int nsh_engine_search_grouped_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                                     const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::SortSpec sp;
+    bool ok = nsh_sort_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_grouped_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_grouped_sorted_json", -1)
+}
+
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, bool grouped, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+                             uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::FacetSpec sp;
     std::string why;
     if (!nsh_facet_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
-    if (n_queries && !queries) { nsh_set_err(e, "nsh_engine_facet_boolean_batch: queries is NULL"); return -1; }
+    if (n_queries && !queries) { nsh_set_err(e, fn + ": queries is NULL"); return -1; }
     std::vector<nextsearch::Engine::QueryView> views(n_queries);
     for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
     std::vector<uint64_t> f_;
@@ -1230,9 +1338,11 @@ extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spe
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
-    if (!e->eng.facet_boolean_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    const bool ok = grouped ? e->eng.facet_grouped_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
+                            : e->eng.facet_boolean_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
     if (counts.size() > counts_cap || (!counts.empty() && !counts_out)) {
-        nsh_set_err(e, "nsh_engine_facet_boolean_batch: counts_out holds " + std::to_string(counts_cap) + " entries, " + std::to_string(n_queries) + " queries x " +
+        nsh_set_err(e, fn + ": counts_out holds " + std::to_string(counts_cap) + " entries, " + std::to_string(n_queries) + " queries x " +
                            std::to_string(labels.size()) + " buckets need " + std::to_string(counts.size()));
         return -1;
     }
@@ -1240,7 +1350,6 @@ extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spe
     for (uint32_t q = 0; q < n_queries; q++)
         if (!has_found[q]) found[q] = 0;
     return 0;
-} NSH_CATCH(e, "nsh_engine_facet_boolean_batch", -1)
 }
 
 extern "C" int nsh_engine_search_boolean_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
@@ -1305,11 +1414,11 @@ extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int
     *json_out = nullptr;
     std::string s;
     nsx::PageSpec ps;
-    bool ok = mode <= 4u;
+    bool ok = mode <= 6u;
     if (!ok) s = "search_page: unknown mode " + std::to_string(mode);
     if (ok) {
         ps.mode = (nsx::PageSpec::Mode)mode;
-        if (mode >= 3u) ok = nsh_sort_spec_of(e, spec, ps.sort, s);
+        if (nsx::page_kind(ps.mode) == 'd') ok = nsh_sort_spec_of(e, spec, ps.sort, s);
     }
     if (ok) {
         ps.use_filter = use_filter != 0;

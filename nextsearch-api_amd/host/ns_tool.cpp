@@ -27,6 +27,9 @@
 //   ns_tool search-boolean-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean_faceted: search-boolean's JSON body plus "facets", as search-faceted's.
 //   ns_tool search-boolean-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
+//   ns_tool search-grouped <index_dir> <from> <to> <k> <query words ...>                          (needs an MI355X; `+(a b) +c -d`)
+//   ns_tool search-grouped-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>     (needs an MI355X)
+//   ns_tool search-grouped-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean_sorted: search-boolean's JSON body with "results" in date order plus "sort", as search-sorted's.
 //   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
 //        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
@@ -127,7 +130,8 @@ int main(int argc, char** argv) {
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 7 && std::strcmp(argv[1], "search-boolean") == 0) {
+    if (argc >= 7 && (std::strcmp(argv[1], "search-boolean") == 0 || std::strcmp(argv[1], "search-grouped") == 0)) {
+        const bool grouped = argv[1][7] == 'g';
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
@@ -138,15 +142,16 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[5]);
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
-        if (!eng.search_boolean_text(q, k, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean failed: %s\n", body.c_str()); return 1; }
+        if (!(grouped ? eng.search_grouped_text(q, k, filtered ? &f : nullptr, body) : eng.search_boolean_text(q, k, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 8 && std::strcmp(argv[1], "search-boolean-faceted") == 0) {
+    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-faceted") == 0 || std::strcmp(argv[1], "search-grouped-faceted") == 0)) {
+        const bool grouped = argv[1][7] == 'g';
         nsx::FacetSpec spec;
         if (std::strcmp(argv[3], "year") == 0) spec.kind = nsx::FacetSpec::Year;
         else if (std::strcmp(argv[3], "month") == 0) spec.kind = nsx::FacetSpec::Month;
-        else { std::fprintf(stderr, "search-boolean-faceted: the facet is year or month, not %s\n", argv[3]); return 2; }
+        else { std::fprintf(stderr, "%s: the facet is year or month, not %s\n", argv[1], argv[3]); return 2; }
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
@@ -157,15 +162,16 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean-faceted failed: %s\n", body.c_str()); return 1; }
+        if (!(grouped ? eng.search_grouped_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 8 && std::strcmp(argv[1], "search-boolean-sorted") == 0) {
+    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-sorted") == 0 || std::strcmp(argv[1], "search-grouped-sorted") == 0)) {
+        const bool grouped = argv[1][7] == 'g';
         nsx::SortSpec spec;
         if (std::strcmp(argv[3], "newest") == 0) spec.ascending = false;
         else if (std::strcmp(argv[3], "oldest") == 0) spec.ascending = true;
-        else { std::fprintf(stderr, "search-boolean-sorted: the order is newest or oldest, not %s\n", argv[3]); return 2; }
+        else { std::fprintf(stderr, "%s: the order is newest or oldest, not %s\n", argv[1], argv[3]); return 2; }
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
@@ -176,7 +182,7 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boolean-sorted failed: %s\n", body.c_str()); return 1; }
+        if (!(grouped ? eng.search_grouped_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
@@ -189,7 +195,10 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[3], "oldest") == 0) { spec.mode = nsx::PageSpec::Sorted; spec.sort.ascending = true; }
         else if (std::strcmp(argv[3], "boolean-newest") == 0) { spec.mode = nsx::PageSpec::BooleanSorted; spec.sort.ascending = false; }
         else if (std::strcmp(argv[3], "boolean-oldest") == 0) { spec.mode = nsx::PageSpec::BooleanSorted; spec.sort.ascending = true; }
-        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest, oldest, boolean-newest or boolean-oldest, not %s\n", argv[3]); return 2; }
+        else if (std::strcmp(argv[3], "grouped") == 0) spec.mode = nsx::PageSpec::Grouped;
+        else if (std::strcmp(argv[3], "grouped-newest") == 0) { spec.mode = nsx::PageSpec::GroupedSorted; spec.sort.ascending = false; }
+        else if (std::strcmp(argv[3], "grouped-oldest") == 0) { spec.mode = nsx::PageSpec::GroupedSorted; spec.sort.ascending = true; }
+        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest, oldest, boolean-newest, boolean-oldest, grouped, grouped-newest or grouped-oldest, not %s\n", argv[3]); return 2; }
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }

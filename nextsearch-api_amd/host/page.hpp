@@ -28,13 +28,13 @@ struct PageCursor {
 
 // which call a page is a page of
 struct PageSpec {
-    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4 };   // BooleanSorted: DESIGN.md §5t
+    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u
     Mode mode = SearchOr;
-    SortSpec sort;                       // Sorted and BooleanSorted only
+    SortSpec sort;                       // Sorted, BooleanSorted and GroupedSorted only
     bool use_filter = false;
     DocFilter filter;
 };
-inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted) ? 'd' : 's'; }
+inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted || m == PageSpec::GroupedSorted) ? 'd' : 's'; }
 
 inline std::string cursor_text(char kind, const PageCursor& c) {
     if (!c.set) return std::string();

@@ -56,7 +56,7 @@ assert HIT_DTYPE.itemsize == C.sizeof(NsHit) == 12
 assert TERM_DTYPE.itemsize == C.sizeof(NsTermRef) == 24
 assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 PAGE_CURSOR_DTYPE = np.dtype([("set", "<u4"), ("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4")])   # nsh_page_cursor: seg is a manifest position
-PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4}
+PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4, "grouped": 5, "grouped_sorted": 6}
 CURSOR_DTYPE = np.dtype([("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4"), ("set", "<u4")])   # ns_cursor
 
 # every symbol include/nextsearch_hip.h declares
@@ -65,6 +65,7 @@ HIP_SYMBOLS = [
     "ns_dockeys_upload", "ns_dockeys_release", "ns_search_sorted", "ns_sorted_kernel_ms",
     "ns_search_boolean", "ns_boolean_kernel_ms", "ns_search_boolean_after", "ns_search_sorted_after",
     "ns_facet_count_boolean", "ns_search_sorted_boolean", "ns_boolean_sets_kernel_ms",
+    "ns_search_grouped_after", "ns_facet_count_grouped", "ns_search_sorted_grouped", "ns_grouped_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -81,6 +82,8 @@ HOST_SYMBOLS = [
     "nsh_parse_boolean", "nsh_engine_search_boolean_batch", "nsh_engine_search_boolean_json",
     "nsh_parse_cursor", "nsh_cursor_text", "nsh_engine_search_after_batch", "nsh_engine_search_boolean_after_batch", "nsh_engine_search_sorted_after_batch",
     "nsh_engine_search_page_json",
+    "nsh_parse_grouped", "nsh_engine_search_grouped_after_batch", "nsh_engine_facet_grouped_batch", "nsh_engine_search_grouped_sorted_batch",
+    "nsh_engine_search_grouped_json", "nsh_engine_search_grouped_faceted_json", "nsh_engine_search_grouped_sorted_json",
     "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
@@ -256,6 +259,10 @@ def hip_lib():
         L.ns_facet_count_boolean.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
         L.ns_search_sorted_boolean.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_boolean_sets_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        L.ns_search_grouped_after.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_facet_count_grouped.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
+        L.ns_search_sorted_grouped.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_grouped_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -267,7 +274,7 @@ def hip_lib():
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
                   "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
-                  "ns_debug_boolean_sets_counters": 12}
+                  "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11}
 
 
 def debug_counters(reset=False):
@@ -451,7 +458,15 @@ def host_lib():
                                                            C.POINTER(C.c_float)]
         L.nsh_engine_facet_boolean_batch.argtypes = [vp, C.POINTER(NshFacetSpec), u32, C.POINTER(C.c_char_p), u32, vp, u64, vp, vp, C.POINTER(C.c_float)]
         L.nsh_engine_search_boolean_sorted_batch.argtypes = [vp, C.POINTER(NshSortSpec), u32, C.POINTER(C.c_char_p), u32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.nsh_parse_grouped.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, u32]
+        L.nsh_parse_grouped.restype = u32
+        L.nsh_engine_search_grouped_after_batch.argtypes = L.nsh_engine_search_boolean_after_batch.argtypes
+        L.nsh_engine_facet_grouped_batch.argtypes = L.nsh_engine_facet_boolean_batch.argtypes
+        L.nsh_engine_search_grouped_sorted_batch.argtypes = L.nsh_engine_search_boolean_sorted_batch.argtypes
+        L.nsh_engine_search_grouped_json.argtypes = L.nsh_engine_search_boolean_json.argtypes
         L.nsh_engine_search_boolean_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_search_grouped_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_search_grouped_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_boolean_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, u32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         _host = L
@@ -1090,6 +1105,83 @@ class Engine:
         out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
         return out + (float(ms.value),) if timing else out
 
+    # ---- any-of groups in boolean queries: the boolean batch calls over `+(a b) +c -d` ----
+    def search_grouped_after_batch(self, queries, k, after=None, handle=0, timing=False):
+        """Engine::search_grouped_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_boolean_after_batch"""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_grouped_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
+                                                           hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_grouped_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def facet_grouped_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
+        """Engine::facet_grouped_batch_flat: (counts Q x n_buckets, found, has_found); as facet_boolean_batch"""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        Q = len(queries)
+        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_facet_grouped_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
+                                                    found.ctypes.data, has_found.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"facet_grouped_batch failed: {self.error()}")
+        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+
+    def search_grouped_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
+        """Engine::search_grouped_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); as
+        search_boolean_sorted_batch"""
+        sp, keep = self._sort_spec(order, custom)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_grouped_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
+                                                            cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
+                                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_grouped_sorted_batch failed: {self.error()}")
+        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def _json_call(self, name, fn, *args, check=True):
+        out = C.c_void_p()
+        rc = fn(self.h, *args, C.byref(out))
+        body = C.string_at(out).decode() if out.value else ""
+        if out.value:
+            self._L.nsh_free(out)
+        if rc != 0 and check:
+            raise RuntimeError(f"{name} failed: {self.error()}")
+        return body
+
+    def search_grouped_json(self, query, k, date_filter=None, check=True):
+        """Engine::search_grouped: the JSON text; as search_boolean_json"""
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_grouped", self._L.nsh_engine_search_grouped_json, _as_bytes(query), k, int(date_filter is not None), _as_bytes(df),
+                               _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_grouped_faceted_json(self, query, k, kind="year", date_filter=None, custom=None, labels=None, check=True):
+        """Engine::search_grouped_faceted: the JSON text; as search_boolean_faceted_json"""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_grouped_faceted", self._L.nsh_engine_search_grouped_faceted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_grouped_sorted_json(self, query, k, order="newest", date_filter=None, custom=None, check=True):
+        """Engine::search_grouped_sorted: the JSON text; as search_boolean_sorted_json"""
+        sp, keep = self._sort_spec(order, custom)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_grouped_sorted", self._L.nsh_engine_search_grouped_sorted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
     def search_sorted_after_batch(self, queries, k, after=None, order="newest", flags=NS_FLAG_OR, handle=0, custom=None, timing=False):
         """Engine::search_sorted_after_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); after: None, or per
         query None | (rank = the sort key, manifest position, docId)"""
@@ -1109,8 +1201,8 @@ class Engine:
         return out + (float(ms.value),) if timing else out
 
     def search_page_json(self, query, k, cursor="", mode="or", order="newest", date_filter=None, custom=None, check=True):
-        """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" | "boolean_sorted" (the last
-        two: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
+        """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" | "boolean_sorted" | "grouped" |
+        "grouped_sorted" (the sorted ones: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         out = C.c_void_p()
@@ -1915,6 +2007,17 @@ def parse_boolean(text):
     return [(w, int(r)) for w, r in zip(words, roles[:n])]
 
 
+def parse_grouped(text):
+    """nsx::parse_grouped (host only): [(term, role, clause)]; clause is the id of a MUST term's clause, 0 on SHOULD and NOT terms"""
+    b = _as_bytes(text)
+    cap = len(b) + 16
+    buf, roles, clauses = C.create_string_buffer(cap), np.zeros(cap, np.uint8), np.zeros(cap, np.uint32)
+    n = int(host_lib().nsh_parse_grouped(b, buf, cap, roles.ctypes.data, clauses.ctypes.data, cap))
+    words = buf.value.decode().split(" ") if n else []
+    assert len(words) == n, (words, n)
+    return [(w, int(r), int(c)) for w, r, c in zip(words, roles[:n], clauses[:n])]
+
+
 def search_boolean_raw(ctx, qd, refs, roles, k, seg_ids, segs):
     """ns_search_boolean (raw): (rc, hits Q x K, nhits, found, device ms); K = clamp(k, 1, 100); roles: one uint8 per ref, or
     None (all SHOULD); segs: list of handles.  The outputs are pre-filled with 0xAB bytes."""
@@ -2076,6 +2179,99 @@ def boolean_sets_kernel_ms(reset=True):
     ns_search_sorted_boolean calls since the last reset"""
     out = (C.c_float * 4)()
     hip_lib().ns_boolean_sets_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+# ---- any-of groups in boolean queries (DESIGN.md §5u): the boolean siblings with one uint16 clause value per ref ----
+def _clauses(clauses):
+    return None if clauses is None else np.ascontiguousarray(clauses, dtype=np.uint16)
+
+
+def search_grouped_after_raw(ctx, qd, refs, roles, clauses, k, after, seg_ids, segs):
+    """ns_search_grouped_after (raw): (rc, hits Q x K, nhits, found, rest, device ms); clauses: one uint16 per ref (read for MUST
+    refs), or None (the boolean sibling); the rest as search_boolean_after_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl = _clauses(clauses)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_grouped_after(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                           ro.ctypes.data if ro is not None and len(ro) else None,
+                                           cl.ctypes.data if cl is not None and len(cl) else None, len(refs), int(k),
+                                           cu.ctypes.data if cu is not None and len(cu) else None,
+                                           ids.ctypes.data if len(ids) else None, sa, len(ids), hits.ctypes.data, nhits.ctypes.data,
+                                           found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+def facet_count_grouped(ctx, qd, refs, roles, clauses, seg_ids, segs, tables, n_buckets):
+    """ns_facet_count_grouped (raw): (rc, counts Q x n_buckets, found, device ms); clauses as search_grouped_after_raw's, the rest
+    as facet_count_boolean.  The outputs are pre-filled with 0xAB bytes."""
+    Q = len(qd)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl = _clauses(clauses)
+    counts = np.full((max(Q, 1), int(n_buckets)), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_facet_count_grouped(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                          ro.ctypes.data if ro is not None and len(ro) else None,
+                                          cl.ctypes.data if cl is not None and len(cl) else None, len(refs),
+                                          ids.ctypes.data if len(ids) else None, sa, ta, len(ids), counts.ctypes.data, found.ctypes.data, C.byref(ms))
+    return rc, counts[:Q], found[:Q], float(ms.value)
+
+
+def search_sorted_grouped_raw(ctx, qd, refs, roles, clauses, k, flags, after, seg_ids, segs, tables):
+    """ns_search_sorted_grouped (raw): (rc, hits Q x K, keys Q x K, nhits, found, rest, device ms); clauses as
+    search_grouped_after_raw's, the rest as search_sorted_boolean_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl = _clauses(clauses)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    keys = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_sorted_grouped(ctx, qd.ctypes.data if Q else None, Q, refs.ctypes.data if len(refs) else None,
+                                            ro.ctypes.data if ro is not None and len(ro) else None,
+                                            cl.ctypes.data if cl is not None and len(cl) else None, len(refs), int(k), int(flags),
+                                            cu.ctypes.data if cu is not None and len(cu) else None,
+                                            ids.ctypes.data if len(ids) else None, sa, ta, len(ids), hits.ctypes.data, keys.ctypes.data,
+                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+GROUPED_EVENTS = ["search_items", "search_multi_list_clauses", "search_intersections", "search_windows_ended", "search_members_missed",
+                  "sets_items", "sets_multi_list_clauses", "sets_intersections", "sets_items_ended", "sets_members_missed",
+                  "sets_single_list_items"]
+
+
+def grouped_counters(reset=True):
+    """ns_debug_boolean_groups_counters of the counting build as {name: value}; None for a library without them"""
+    c = debug_counters(reset=reset).get("ns_debug_boolean_groups_counters")
+    return None if c is None else dict(zip(GROUPED_EVENTS, c))
+
+
+def grouped_kernel_ms(reset=True):
+    """(k_bq_select, k_bq_join, k_bs_count, k_bs_select, k_sd_join, k_bs_score) HIP-event ms summed over this thread's grouped
+    calls that were given clauses, since the last reset"""
+    out = (C.c_float * 6)()
+    hip_lib().ns_grouped_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
