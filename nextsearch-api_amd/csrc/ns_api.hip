@@ -35,6 +35,7 @@
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
+#include "ns_call_plan.hpp"   // host only: what a ranked call plans on top of ns_sorted_plan.hpp and ns_after_plan.hpp
 
 using namespace ns;
 
@@ -2683,6 +2684,288 @@ extern "C" int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint3
 }
 
 // ------------------------------------------------------------------------------------------------
+// The call scaffold of the facet, date-order and boolean entry points (the host-only part of a ranked call's
+// planning is csrc/ns_call_plan.hpp).  A call validates its own arguments, binds its segments (bind_segments), runs its
+// planner and hands the work items to run_count or run_ranked, which own the device block (CallBlock).
+
+// A per-document table checked by a kernel at upload (ns_facet_upload, ns_dockeys_upload): n_docs values go up to a fresh
+// allocation, launch_check(d_table, d_bad, grid, stream) starts the kernel that sets *d_bad for a value the call refuses.
+// On an error or a refused value nothing stays allocated and *d_out is NULL.
+template <class T, class Check>
+static hipError_t upload_checked(ns_ctx* ctx, const T* src, uint32_t n_docs, T** d_out, bool* refused, Check launch_check) {
+    hipStream_t st = ctx->stream;
+    uint32_t* d_bad = nullptr;
+    uint32_t bad = 0;
+    hipError_t e = hipSetDevice(ctx->device);
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (e == hipSuccess) chk(hipMalloc((void**)d_out, (size_t)std::max<uint32_t>(n_docs, 1) * sizeof(T)));
+    chk(hipMalloc((void**)&d_bad, 4));
+    if (e == hipSuccess) {
+        if (n_docs) chk(hipMemcpyAsync(*d_out, src, (size_t)n_docs * sizeof(T), hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(d_bad, 0, 4, st));
+        if (e == hipSuccess && n_docs) {
+            launch_check(*d_out, d_bad, dim3(std::min<uint32_t>((n_docs + 255) / 256, 1024u)), st);
+            chk(hipGetLastError());
+        }
+        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    }
+    { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host array is the caller's: nothing may still read it)
+    (void)hipFree(d_bad);
+    if (e != hipSuccess || bad) { (void)hipFree(*d_out); *d_out = nullptr; }
+    *refused = bad != 0;
+    return e;
+}
+
+// The listed segments of a call -> what its planner (views) and its kernels (dsegs) know of them.  `tables` is the call's
+// companion table per segment and `noun` its name in the messages; Table = void and both NULL for a call without one.
+// per_seg(i, s, t) is the caller's part: it checks the table (a code other than NS_OK, with the message set, ends the call)
+// and fills what the call adds per segment.
+template <class Table, class PerSeg>
+static int bind_segments(ns_ctx* ctx, const char* fn, const uint32_t* seg_ids, ns_seg* const* segs, Table* const* tables, const char* noun,
+                         uint32_t n_segs, std::vector<FcSegView>& views, std::vector<DevFcSeg>& dsegs, PerSeg per_seg) {
+    if (!seg_ids || !segs || (noun && !tables)) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
+    views.assign(n_segs, FcSegView());
+    dsegs.assign(n_segs, DevFcSeg());
+    for (uint32_t i = 0; i < n_segs; i++) {
+        ns_seg* s = segs[i];
+        const Table* t = tables ? tables[i] : nullptr;
+        if (noun && (!s || !t)) return fail(ctx, NS_E_INVAL, "%s: segment or %s %u is NULL", fn, noun, i);
+        if (!s) return fail(ctx, NS_E_INVAL, "%s: segment %u is NULL", fn, i);
+        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
+        views[i].seg_id = seg_ids[i];
+        views[i].n_docs = s->n_docs;
+        views[i].n_postings = s->n_postings;
+        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
+        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
+        const int rc = per_seg(i, s, t);
+        if (rc != NS_OK) return rc;
+    }
+    return NS_OK;
+}
+
+// Grouped clauses: clauses without roles name no MUST ref, so nothing reads them: the sibling's plan and
+// kernels, as for clauses == NULL.
+static const uint16_t* bq_live_clauses(const uint16_t* clauses, uint32_t n_terms, const uint8_t* roles) {
+    return (clauses && n_terms && !roles) ? nullptr : clauses;
+}
+
+// The device block of one call: regions laid out with place_at, one pooled allocation, the call's events and the first
+// HIP error.  reserve() everything, alloc(), then work on the stream only while ok(); finish() on every path after alloc().
+struct CallBlock {
+    ns_ctx* ctx;
+    hipStream_t st;
+    size_t bytes = 0;
+    char* blk = nullptr;
+    std::vector<hipEvent_t> evs;
+    hipError_t e = hipSuccess;
+
+    explicit CallBlock(ns_ctx* c) : ctx(c), st(c->stream) {}
+    void chk(hipError_t r) { if (e == hipSuccess) e = r; }
+    bool ok() const { return e == hipSuccess; }
+    size_t reserve(size_t n) { return place_at(bytes, n); }   // (a region of no bytes still takes a place)
+    void alloc(size_t n_events) {
+        chk(pool_alloc(ctx, (void**)&blk, bytes));
+        evs.assign(n_events, nullptr);
+        for (auto& ev : evs) chk(hipEventCreate(&ev));
+    }
+    template <class T> T* at(size_t off) const { return (T*)(blk + off); }
+    void upload(size_t off, const void* src, size_t n) { if (n) chk(hipMemcpyAsync(blk + off, src, n, hipMemcpyHostToDevice, st)); }
+    void zero(size_t off, size_t n) { chk(hipMemsetAsync(blk + off, 0, n, st)); }
+    void fetch(void* dst, size_t off, size_t n) { chk(hipMemcpyAsync(dst, blk + off, n, hipMemcpyDeviceToHost, st)); }
+    void record(size_t ev) { chk(hipEventRecord(evs[ev], st)); }
+    void launched() { chk(hipGetLastError()); }
+    void sync() { chk(hipStreamSynchronize(st)); }
+    // the block goes back to the pool only once nothing in flight uses it, whatever failed before
+    int finish(const char* fn) {
+        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, bytes); }
+        for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return NS_OK;
+    }
+};
+
+// The facet-count calls from their work items on: one kernel over the items adds to counts[q * B + b], found = the sum of a
+// query's buckets.  time_memset: whether the interval device_ms_out reports starts before the memset of the counts
+// (ns_facet_count) or after it (the boolean and grouped counts); ms_acc (may be NULL) also gets the interval.
+template <class Ref>
+static int run_count(ns_ctx* ctx, const char* fn, const std::vector<FcItem>& items, const std::vector<Ref>& refs, const std::vector<DevFcSeg>& dsegs,
+                     void (*kernel)(const FcItem*, const Ref*, const DevFcSeg*, uint32_t, uint32_t*), uint32_t n_queries, uint32_t B,
+                     bool time_memset, float* ms_acc, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+    std::string why;
+    if (!call_item_limit(items.size(), why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const size_t n_counts = (size_t)n_queries * B;
+    if (!items.empty()) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        CallBlock blk(ctx);
+        const size_t o_items = blk.reserve(items.size() * sizeof(FcItem)), o_refs = blk.reserve(refs.size() * sizeof(Ref)),
+                     o_segs = blk.reserve(dsegs.size() * sizeof(DevFcSeg)), o_counts = blk.reserve(n_counts * 4);
+        blk.alloc(2);
+        if (blk.ok()) {
+            blk.upload(o_items, items.data(), items.size() * sizeof(FcItem));
+            blk.upload(o_refs, refs.data(), refs.size() * sizeof(Ref));
+            blk.upload(o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg));
+            if (time_memset) blk.record(0);
+            blk.zero(o_counts, n_counts * 4);
+            if (!time_memset) blk.record(0);
+            if (blk.ok()) {
+                hipLaunchKernelGGL(kernel, dim3((uint32_t)items.size()), dim3(256), 0, blk.st, blk.at<const FcItem>(o_items), blk.at<const Ref>(o_refs),
+                                   blk.at<const DevFcSeg>(o_segs), B, blk.at<uint32_t>(o_counts));
+                blk.launched();
+            }
+            blk.record(1);
+            blk.fetch(counts_out, o_counts, n_counts * 4);
+            blk.sync();
+            float ms = 0.0f;
+            if (blk.ok() && hipEventElapsedTime(&ms, blk.evs[0], blk.evs[1]) == hipSuccess) {
+                if (ms_acc) *ms_acc += ms;
+                if (device_ms_out) *device_ms_out = ms;
+            }
+        }
+        const int rc = blk.finish(fn);
+        if (rc != NS_OK) return rc;
+    } else {
+        std::memset(counts_out, 0, n_counts * 4);
+    }
+    if (found_out)
+        for (uint32_t q = 0; q < n_queries; q++) {
+            uint64_t sum = 0;
+            for (uint32_t b = 0; b < B; b++) sum += counts_out[(size_t)q * B + b];
+            found_out[q] = sum;
+        }
+    return NS_OK;
+}
+
+// k_sd_select, k_bq_select and k_bs_select: (items, refs, segs, aux, K, asc or window, cand, found, last, rest)
+template <class Ref, class Aux>
+using SelectKernel = void (*)(const FcItem*, const Ref*, const DevFcSeg*, const Aux*, uint32_t, uint32_t, uint64_t*, unsigned long long*, const uint64_t*,
+                              unsigned long long*);
+
+// The regions of a ranked call's block as its kernels take them.
+template <class Ref, class Aux>
+struct RankedDev {
+    const FcItem* items;
+    const Ref* refs;
+    const DevFcSeg* segs;
+    const Aux* aux;               // DevSdSeg (date order) or DevBqSeg (ranked by score) per segment
+    const uint32_t* q_off;
+    const ns_query_desc* qd;      // qd, terms, roles, keys, pos: of the calls with a score stage only
+    const ns_term_ref* terms;
+    const uint8_t* roles;         // NULL: the call has none
+    uint32_t *hits, *keys, *pos, *nhits;
+    const uint64_t* cand;
+};
+
+// A ranked call from its plan on.  Per cut: the select kernel over the cut's items fills their candidate rows, join(dev, cut)
+// launches the kernel that joins them into the queries' rows, and score(dev, cut), in the calls ordered by date, the one
+// that looks the hits' scores up; `stages` = 2 or 3 says which, and ms_acc[stage] and device_ms_out get the kernels' times.
+template <class Ref, class Aux>
+struct RankedCall {
+    const std::vector<FcItem>& items;
+    const std::vector<Ref>& refs;
+    const std::vector<DevFcSeg>& dsegs;
+    const std::vector<Aux>& aux;
+    const RankedPlan& plan;
+    uint32_t n_queries;
+    // the select stage: the instantiation (the AFTER = false ones get NULL for last and rest), its scalar after K (asc, or
+    // the window) and its dynamic LDS
+    SelectKernel<Ref, Aux> select;
+    uint32_t select_arg;
+    size_t select_lds;
+    int stages;
+    float* ms_acc;
+    // what the score stage reads (stages == 3); roles_region: the block has a region for the roles, used or not
+    const ns_query_desc* queries;
+    const ns_term_ref* terms;
+    uint32_t n_terms;
+    const uint8_t* roles;
+    bool roles_region;
+    hipError_t before;            // the first error of what the caller did on the device before the block
+    ns_hit* hits_out;
+    uint32_t* keys_out;           // with stages == 3
+    uint32_t* nhits_out;
+    uint64_t *found_out, *rest_out;
+    float* device_ms_out;
+};
+
+template <class Ref, class Aux, class Join, class Score>
+static int run_ranked(ns_ctx* ctx, const char* fn, const RankedCall<Ref, Aux>& c, Join join, Score score) {
+    const RankedPlan& p = c.plan;
+    const bool scored = c.stages == 3;
+    const uint32_t K = p.K, n_queries = c.n_queries;
+    const size_t n_out = (size_t)n_queries * K, n_roles = c.roles ? (size_t)c.n_terms : 0;
+    const size_t per_cut = (size_t)c.stages + 1;
+    CallBlock blk(ctx);
+    blk.chk(c.before);
+    const size_t o_last = blk.reserve(p.last.size() * 8), o_rest = blk.reserve(p.paged ? (size_t)n_queries * 8 : 0);
+    const size_t o_items = blk.reserve(c.items.size() * sizeof(FcItem)), o_refs = blk.reserve(c.refs.size() * sizeof(Ref)),
+                 o_segs = blk.reserve(c.dsegs.size() * sizeof(DevFcSeg)), o_aux = blk.reserve(c.aux.size() * sizeof(Aux)),
+                 o_qoff = blk.reserve(p.q_off.size() * 4);
+    const size_t o_qd = scored ? blk.reserve((size_t)n_queries * sizeof(ns_query_desc)) : 0,
+                 o_terms = scored ? blk.reserve((size_t)c.n_terms * sizeof(ns_term_ref)) : 0, o_roles = c.roles_region ? blk.reserve(n_roles) : 0;
+    const size_t o_hits = blk.reserve(n_out * sizeof(ns_hit)), o_keys = scored ? blk.reserve(n_out * 4) : 0, o_pos = scored ? blk.reserve(n_out * 4) : 0,
+                 o_nhits = blk.reserve((size_t)n_queries * 4), o_found = blk.reserve((size_t)n_queries * 8),
+                 o_cand = blk.reserve((size_t)p.cand_rows * K * 8);   // <= kSdCandBytes
+    blk.alloc(p.cuts.size() * per_cut);
+    if (blk.ok()) {
+        blk.upload(o_items, c.items.data(), c.items.size() * sizeof(FcItem));
+        blk.upload(o_refs, c.refs.data(), c.refs.size() * sizeof(Ref));
+        blk.upload(o_segs, c.dsegs.data(), c.dsegs.size() * sizeof(DevFcSeg));
+        blk.upload(o_aux, c.aux.data(), c.aux.size() * sizeof(Aux));
+        blk.upload(o_qoff, p.q_off.data(), p.q_off.size() * 4);
+        if (scored) {
+            blk.upload(o_qd, c.queries, (size_t)n_queries * sizeof(ns_query_desc));
+            blk.upload(o_terms, c.terms, (size_t)c.n_terms * sizeof(ns_term_ref));
+            blk.upload(o_roles, c.roles, n_roles);
+        }
+        blk.zero(o_found, (size_t)n_queries * 8);
+        blk.upload(o_last, p.last.data(), p.last.size() * 8);
+        if (p.paged) blk.zero(o_rest, (size_t)n_queries * 8);
+        const uint64_t* d_last = blk.at<const uint64_t>(o_last);
+        uint64_t* d_cand = blk.at<uint64_t>(o_cand);
+        const RankedDev<Ref, Aux> dev{blk.at<const FcItem>(o_items), blk.at<const Ref>(o_refs), blk.at<const DevFcSeg>(o_segs), blk.at<const Aux>(o_aux),
+                                      blk.at<const uint32_t>(o_qoff), blk.at<const ns_query_desc>(o_qd), blk.at<const ns_term_ref>(o_terms),
+                                      n_roles ? blk.at<const uint8_t>(o_roles) : nullptr, blk.at<uint32_t>(o_hits), blk.at<uint32_t>(o_keys),
+                                      blk.at<uint32_t>(o_pos), blk.at<uint32_t>(o_nhits), d_cand};
+        for (size_t i = 0; i < p.cuts.size() && blk.ok(); i++) {
+            const SdBatch& b = p.cuts[i];
+            const uint32_t n_it = b.item_end - b.item_begin;
+            blk.record(i * per_cut + 0);
+            if (n_it) {   // last is indexed by the call's item number, as items: both start at the sub-batch's first
+                hipLaunchKernelGGL(c.select, dim3(n_it), dim3(256), c.select_lds, blk.st, dev.items + b.item_begin, dev.refs, dev.segs, dev.aux, K, c.select_arg,
+                                   d_cand, blk.at<unsigned long long>(o_found), p.paged ? d_last + b.item_begin : (const uint64_t*)nullptr,
+                                   p.paged ? blk.at<unsigned long long>(o_rest) : (unsigned long long*)nullptr);
+                blk.launched();
+            }
+            blk.record(i * per_cut + 1);
+            join(dev, b, blk.st);
+            blk.launched();
+            blk.record(i * per_cut + 2);
+            if (scored) {
+                score(dev, b, blk.st);
+                blk.launched();
+                blk.record(i * per_cut + 3);
+            }
+        }
+        blk.fetch(c.hits_out, o_hits, n_out * sizeof(ns_hit));
+        if (scored) blk.fetch(c.keys_out, o_keys, n_out * 4);
+        blk.fetch(c.nhits_out, o_nhits, (size_t)n_queries * 4);
+        if (c.found_out) blk.fetch(c.found_out, o_found, (size_t)n_queries * 8);
+        if (c.rest_out) blk.fetch(c.rest_out, p.paged ? o_rest : o_found, (size_t)n_queries * 8);   // no cursor: rest = found
+        blk.sync();
+        if (blk.ok()) {
+            float sum = 0.0f;
+            for (size_t i = 0; i < p.cuts.size(); i++)
+                for (int j = 0; j < c.stages; j++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, blk.evs[i * per_cut + j], blk.evs[i * per_cut + j + 1]) == hipSuccess) { c.ms_acc[j] += ms; sum += ms; }
+                }
+            if (c.device_ms_out) *c.device_ms_out = sum;
+        }
+    }
+    return blk.finish(fn);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Facet counts (csrc/ns_facet.hip, csrc/ns_facet_plan.hpp)
 struct ns_facet {
     ns_ctx* ctx = nullptr;
@@ -2707,26 +2990,11 @@ extern "C" int ns_facet_upload(ns_ctx* ctx, uint32_t n_docs, const uint16_t* buc
     if (n_buckets < 1 || n_buckets > kFcMaxBuckets) return fail(ctx, NS_E_INVAL, "%s: n_buckets = %u outside [1, %u]", fn, n_buckets, kFcMaxBuckets);
     ns_facet* t = new ns_facet();
     t->ctx = ctx; t->n_docs = n_docs; t->n_buckets = n_buckets;
-    hipStream_t st = ctx->stream;
-    uint32_t* d_bad = nullptr;
-    uint32_t bad = 0;
-    hipError_t e = hipSetDevice(ctx->device);
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    if (e == hipSuccess) chk(hipMalloc((void**)&t->d_buckets, (size_t)std::max<uint32_t>(n_docs, 1) * 2));
-    chk(hipMalloc((void**)&d_bad, 4));
-    if (e == hipSuccess) {
-        if (n_docs) chk(hipMemcpyAsync(t->d_buckets, bucket_of_doc, (size_t)n_docs * 2, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_bad, 0, 4, st));
-        if (e == hipSuccess && n_docs) {
-            hipLaunchKernelGGL(k_fc_check, dim3(std::min<uint32_t>((n_docs + 255) / 256, 1024u)), dim3(256), 0, st, t->d_buckets, n_docs, n_buckets, d_bad);
-            chk(hipGetLastError());
-        }
-        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-    }
-    { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host array is the caller's: nothing may still read it)
-    (void)hipFree(d_bad);
-    if (e != hipSuccess || bad) {
-        (void)hipFree(t->d_buckets);
+    bool refused = false;
+    const hipError_t e = upload_checked(ctx, bucket_of_doc, n_docs, &t->d_buckets, &refused, [&](const uint16_t* d_table, uint32_t* d_bad, dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(k_fc_check, grid, dim3(256), 0, st, d_table, n_docs, n_buckets, d_bad);
+    });
+    if (e != hipSuccess || refused) {
         delete t;
         if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
         return fail(ctx, NS_E_INVAL, "%s: a document has a bucket id >= n_buckets = %u", fn, n_buckets);
@@ -2744,6 +3012,16 @@ extern "C" int ns_facet_release(ns_ctx* ctx, ns_facet* table) {
     return NS_OK;
 }
 
+// The facet calls' part of bind_segments: the table buckets the segment's documents, as many buckets as table 0; the
+// kernels read it through the segment's DevFcSeg.
+static int fc_bind_table(ns_ctx* ctx, const char* fn, uint32_t i, const ns_seg* s, const ns_facet* t, const ns_facet* t0, DevFcSeg& dseg) {
+    if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: table %u does not belong to this ctx", fn, i);
+    if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: table %u buckets %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+    if (t->n_buckets != t0->n_buckets) return fail(ctx, NS_E_INVAL, "%s: table %u has %u buckets, table 0 has %u", fn, i, t->n_buckets, t0->n_buckets);
+    dseg.buckets = t->d_buckets;
+    return NS_OK;
+}
+
 extern "C" int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
                               uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
                               uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
@@ -2753,78 +3031,19 @@ extern "C" int ns_facet_count(ns_ctx* ctx, const ns_query_desc* queries, uint32_
     if (n_queries == 0) return NS_OK;
     if (!queries || !counts_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed (the number of buckets comes from the tables)", fn);
-    if (!seg_ids || !segs || !tables) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
-    std::vector<FcSegView> views(n_segs);
-    std::vector<DevFcSeg> dsegs(n_segs);
-    for (uint32_t i = 0; i < n_segs; i++) {
-        ns_seg* s = segs[i];
-        const ns_facet* t = tables[i];
-        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or table %u is NULL", fn, i);
-        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
-        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: table %u does not belong to this ctx", fn, i);
-        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: table %u buckets %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
-        if (t->n_buckets != tables[0]->n_buckets) return fail(ctx, NS_E_INVAL, "%s: table %u has %u buckets, table 0 has %u", fn, i, t->n_buckets, tables[0]->n_buckets);
-        views[i].seg_id = seg_ids[i];
-        views[i].n_docs = s->n_docs;
-        views[i].n_postings = s->n_postings;
-        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
-        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, t->d_buckets, s->n_docs, 0u};
-    }
-    const uint32_t B = tables[0]->n_buckets;
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
+    const int rc = bind_segments(ctx, fn, seg_ids, segs, tables, "table", n_segs, views, dsegs,
+                                 [&](uint32_t i, const ns_seg* s, const ns_facet* t) { return fc_bind_table(ctx, fn, i, s, t, tables[0], dsegs[i]); });
+    if (rc != NS_OK) return rc;
+    const bool and_mode = (flags & NS_FLAG_AND) != 0;
     std::vector<FcRef> refs;
     std::vector<FcItem> items;
     std::string why;
-    if (fc_plan(queries, n_queries, terms, n_terms, (flags & NS_FLAG_AND) != 0, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+    if (fc_plan(queries, n_queries, terms, n_terms, and_mode, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
-    const size_t n_counts = (size_t)n_queries * B;
-    if (!items.empty()) {
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        hipStream_t st = ctx->stream;
-        size_t off = 0;
-        const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(FcRef)),
-                     o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_counts = place_at(off, n_counts * 4);
-        const size_t block_bytes = off;
-        char* blk = nullptr;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        hipError_t e = hipSuccess;
-        auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-        chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-        chk(hipEventCreate(&ev0));
-        chk(hipEventCreate(&ev1));
-        if (e == hipSuccess) {
-            chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(FcRef), hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
-            chk(hipEventRecord(ev0, st));
-            chk(hipMemsetAsync(blk + o_counts, 0, n_counts * 4, st));
-            if (e == hipSuccess) {
-                if (flags & NS_FLAG_AND)
-                    hipLaunchKernelGGL(k_fc_count<true>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const FcRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
-                else
-                    hipLaunchKernelGGL(k_fc_count<false>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const FcRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
-                chk(hipGetLastError());
-            }
-            chk(hipEventRecord(ev1, st));
-            chk(hipMemcpyAsync(counts_out, blk + o_counts, n_counts * 4, hipMemcpyDeviceToHost, st));
-            chk(hipStreamSynchronize(st));
-            float ms = 0.0f;
-            if (e == hipSuccess && device_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
-        }
-        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    } else {
-        std::memset(counts_out, 0, n_counts * 4);
-    }
-    if (found_out)
-        for (uint32_t q = 0; q < n_queries; q++) {
-            uint64_t sum = 0;
-            for (uint32_t b = 0; b < B; b++) sum += counts_out[(size_t)q * B + b];
-            found_out[q] = sum;
-        }
-    return NS_OK;
+    return run_count(ctx, fn, items, refs, dsegs, and_mode ? k_fc_count<true> : k_fc_count<false>, n_queries, tables[0]->n_buckets, true, nullptr,
+                     counts_out, found_out, device_ms_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2844,26 +3063,11 @@ extern "C" int ns_dockeys_upload(ns_ctx* ctx, uint32_t n_docs, const uint32_t* k
     if (n_docs && !keys) return fail(ctx, NS_E_INVAL, "%s: keys is NULL", fn);
     ns_dockeys* t = new ns_dockeys();
     t->ctx = ctx; t->n_docs = n_docs;
-    hipStream_t st = ctx->stream;
-    uint32_t* d_bad = nullptr;
-    uint32_t bad = 0;
-    hipError_t e = hipSetDevice(ctx->device);
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    if (e == hipSuccess) chk(hipMalloc((void**)&t->d_keys, (size_t)std::max<uint32_t>(n_docs, 1) * 4));
-    chk(hipMalloc((void**)&d_bad, 4));
-    if (e == hipSuccess) {
-        if (n_docs) chk(hipMemcpyAsync(t->d_keys, keys, (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_bad, 0, 4, st));
-        if (e == hipSuccess && n_docs) {
-            hipLaunchKernelGGL(k_sd_check, dim3(std::min<uint32_t>((n_docs + 255) / 256, 1024u)), dim3(256), 0, st, t->d_keys, n_docs, d_bad);
-            chk(hipGetLastError());
-        }
-        chk(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-    }
-    { const hipError_t s2 = hipStreamSynchronize(st); chk(s2); }   // (the host array is the caller's: nothing may still read it)
-    (void)hipFree(d_bad);
-    if (e != hipSuccess || bad) {
-        (void)hipFree(t->d_keys);
+    bool refused = false;
+    const hipError_t e = upload_checked(ctx, keys, n_docs, &t->d_keys, &refused, [&](const uint32_t* d_table, uint32_t* d_bad, dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(k_sd_check, grid, dim3(256), 0, st, d_table, n_docs, d_bad);
+    });
+    if (e != hipSuccess || refused) {
         delete t;
         if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
         return fail(ctx, NS_E_INVAL, "%s: a document has the reserved key 0xFFFFFFFF", fn);
@@ -2893,38 +3097,7 @@ extern "C" int ns_sorted_kernel_ms(float* out3, int reset) {
     return NS_OK;
 }
 
-// Pages past the first K (csrc/ns_after_plan.hpp, csrc/ns_after.hip): the cursors of one call -> last[item].
-// rank_of maps a cursor's rank as the caller gives it to the rank the kernel's keys carry.  False, with `err` set, for a
-// cursor the call refuses.  any_set: at least one query has a cursor (otherwise `last` stays empty and the AFTER = false
-// kernels run).
-template <class RankOf>
-static bool after_plan(const ns_cursor* after, uint32_t n_queries, const std::vector<FcSegView>& views, const std::vector<FcItem>& items,
-                       RankOf rank_of, bool reserved_rank, std::vector<uint64_t>& last, bool& any_set, std::string& err) {
-    last.clear();
-    any_set = false;
-    if (!after) return true;
-    std::vector<uint32_t> pos_of(n_queries, 0u);
-    for (uint32_t q = 0; q < n_queries; q++) {
-        const ns_cursor& c = after[q];
-        if (c.set > 1u) { err = fc_format("query %u: cursor with set = %u (0 or 1)", q, c.set); return false; }
-        if (!c.set) continue;
-        if (reserved_rank && c.rank == 0xFFFFFFFFu) { err = fc_format("query %u: cursor with the reserved key 0xFFFFFFFF", q); return false; }
-        uint32_t pos = 0;
-        while (pos < views.size() && views[pos].seg_id != c.seg_id) pos++;
-        if (pos == views.size()) { err = fc_format("query %u: cursor names segment %u, which the call does not list", q, c.seg_id); return false; }
-        pos_of[q] = pos;
-        any_set = true;
-    }
-    if (!any_set) return true;
-    last.resize(items.size());
-    for (size_t i = 0; i < items.size(); i++) {
-        const FcItem& it = items[i];
-        const ns_cursor& c = after[it.query];
-        last[i] = c.set ? after_last(rank_of(c.rank), pos_of[it.query], c.doc_id, it.seg, it.doc_lo, it.doc_hi) : kAfterAll;
-    }
-    return true;
-}
-
+// (Pages past the first K, DESIGN.md §5s: ranked_call_plan of csrc/ns_call_plan.hpp turns the cursors of a call into last[item].)
 extern "C" int ns_search_sorted(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
                                 uint32_t k, uint32_t flags, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
                                 ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
@@ -2940,6 +3113,24 @@ extern "C" int ns_search_sorted_after(ns_ctx* ctx, const ns_query_desc* queries,
                      nhits_out, found_out, rest_out, device_ms_out);
 }
 
+// The date-ordered calls' part of bind_segments (ns_search_sorted*, ns_search_sorted_boolean, ns_search_sorted_grouped): the
+// table keys the segment's documents; the kernels read it, the norms and the segment's id through a DevSdSeg.
+static int sd_bind_table(ns_ctx* ctx, const char* fn, uint32_t i, const ns_seg* s, const ns_dockeys* t, uint32_t seg_id, DevSdSeg& sd) {
+    if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: key table %u does not belong to this ctx", fn, i);
+    if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: key table %u keys %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
+    sd = DevSdSeg{t->d_keys, s->d_norm, seg_id, 0u};
+    return NS_OK;
+}
+
+// the join stage of the date-ordered calls
+template <class Ref>
+static void sd_launch_join(const RankedDev<Ref, DevSdSeg>& d, const SdBatch& b, uint32_t K, uint32_t asc, hipStream_t st) {
+    hipLaunchKernelGGL(k_sd_join, dim3((b.q_end - b.q_begin + 3) / 4), dim3(256), 0, st, d.items, d.q_off, b.q_begin, b.q_end, b.item_begin, d.aux, d.cand, K, asc,
+                       d.hits, d.keys, d.pos, d.nhits);
+}
+// a score stage has one wave per hit of the cut's queries, four to a block
+static dim3 sd_score_grid(const SdBatch& b, uint32_t K) { return dim3((uint32_t)(((uint64_t)(b.q_end - b.q_begin) * K + 3) / 4)); }
+
 static int sd_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, uint32_t n_terms,
                      uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys,
                      uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
@@ -2950,128 +3141,37 @@ static int sd_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     if (!queries || !hits_out || !keys_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     if (flags & ~(NS_FLAG_AND | NS_SORT_ASC)) return fail(ctx, NS_E_INVAL, "%s: flags 0x%x: only NS_FLAG_AND and NS_SORT_ASC are known", fn, flags);
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
-    if (!seg_ids || !segs || !keys) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
-    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
-    std::vector<FcSegView> views(n_segs);
-    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
     std::vector<DevSdSeg> sds(n_segs);
-    for (uint32_t i = 0; i < n_segs; i++) {
-        ns_seg* s = segs[i];
-        const ns_dockeys* t = keys[i];
-        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or key table %u is NULL", fn, i);
-        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
-        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: key table %u does not belong to this ctx", fn, i);
-        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: key table %u keys %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
-        views[i].seg_id = seg_ids[i];
-        views[i].n_docs = s->n_docs;
-        views[i].n_postings = s->n_postings;
-        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
-        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
-        sds[i] = DevSdSeg{t->d_keys, s->d_norm, seg_ids[i], 0u};
-    }
+    const int rc = bind_segments(ctx, fn, seg_ids, segs, keys, "key table", n_segs, views, dsegs,
+                                 [&](uint32_t i, const ns_seg* s, const ns_dockeys* t) { return sd_bind_table(ctx, fn, i, s, t, seg_ids[i], sds[i]); });
+    if (rc != NS_OK) return rc;
     const bool and_mode = (flags & NS_FLAG_AND) != 0;
     const uint32_t asc = (flags & NS_SORT_ASC) ? 1u : 0u;
     std::vector<FcRef> refs;
     std::vector<FcItem> items;
-    std::vector<uint32_t> q_off;
-    std::vector<SdBatch> cuts;
+    RankedPlan plan;
     std::string why;
     if (fc_plan(queries, n_queries, terms, n_terms, and_mode, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
-    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
-    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
-    bool paged = false;
-    if (!after_plan(after, n_queries, views, items, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, last, paged, why))
+    if (!ranked_call_plan(items, n_queries, k, after, views, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    uint64_t cand_rows = 0;
-    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
-    const size_t n_out = (size_t)n_queries * K;
-
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    size_t off = 0;
-    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
-    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(FcRef)),
-                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_sds = place_at(off, sds.size() * sizeof(DevSdSeg)),
-                 o_qoff = place_at(off, q_off.size() * 4), o_qd = place_at(off, (size_t)n_queries * sizeof(ns_query_desc)),
-                 o_terms = place_at(off, (size_t)n_terms * sizeof(ns_term_ref)), o_hits = place_at(off, n_out * sizeof(ns_hit)),
-                 o_keys = place_at(off, n_out * 4), o_pos = place_at(off, n_out * 4), o_nhits = place_at(off, (size_t)n_queries * 4),
-                 o_found = place_at(off, (size_t)n_queries * 8), o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    std::vector<hipEvent_t> evs(cuts.size() * 4, nullptr);
-    std::vector<uint64_t> found_tmp;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    for (auto& ev : evs) chk(hipEventCreate(&ev));
-    if (e == hipSuccess) {
-        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
-        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(FcRef), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_sds, sds.data(), sds.size() * sizeof(DevSdSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_qd, queries, (size_t)n_queries * sizeof(ns_query_desc), hipMemcpyHostToDevice, st));
-        if (n_terms) chk(hipMemcpyAsync(blk + o_terms, terms, (size_t)n_terms * sizeof(ns_term_ref), hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
-        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
-        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
-        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
-        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
-        const FcItem* d_items = (const FcItem*)(blk + o_items);
-        const DevFcSeg* d_segs = (const DevFcSeg*)(blk + o_segs);
-        const DevSdSeg* d_sds = (const DevSdSeg*)(blk + o_sds);
-        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
-        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
-            const SdBatch& b = cuts[c];
-            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
-            chk(hipEventRecord(evs[c * 4 + 0], st));
-            if (n_it) {
-                const FcRef* d_refs = (const FcRef*)(blk + o_refs);
-                unsigned long long* d_found = (unsigned long long*)(blk + o_found);
-                if (paged && and_mode)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
-                    hipLaunchKernelGGL((k_sd_select<true, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
-                else if (paged)
-                    hipLaunchKernelGGL((k_sd_select<false, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
-                else if (and_mode)
-                    hipLaunchKernelGGL((k_sd_select<true, false>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                else
-                    hipLaunchKernelGGL((k_sd_select<false, false>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                chk(hipGetLastError());
-            }
-            chk(hipEventRecord(evs[c * 4 + 1], st));
-            hipLaunchKernelGGL(k_sd_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_sds,
-                               (const uint64_t*)d_cand, K, asc, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_keys), (uint32_t*)(blk + o_pos), (uint32_t*)(blk + o_nhits));
-            chk(hipGetLastError());
-            chk(hipEventRecord(evs[c * 4 + 2], st));
-            const uint64_t n_waves = (uint64_t)n_q * K;
-            hipLaunchKernelGGL(k_sd_score, dim3((uint32_t)((n_waves + 3) / 4)), dim3(256), 0, st, (const ns_query_desc*)(blk + o_qd), (const ns_term_ref*)(blk + o_terms), b.q_begin, b.q_end,
-                               d_segs, d_sds, K, (const uint32_t*)(blk + o_pos), (const uint32_t*)(blk + o_nhits), (uint32_t*)(blk + o_hits));
-            chk(hipGetLastError());
-            chk(hipEventRecord(evs[c * 4 + 3], st));
-        }
-        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(keys_out, blk + o_keys, n_out * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
-        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
-        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
-        chk(hipStreamSynchronize(st));
-        if (e == hipSuccess) {
-            float sum = 0.0f;
-            for (size_t c = 0; c < cuts.size(); c++)
-                for (int j = 0; j < 3; j++) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { g_sd_ms[j] += ms; sum += ms; }
-                }
-            if (device_ms_out) *device_ms_out = sum;
-        }
-    }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return NS_OK;
+    static const SelectKernel<FcRef, DevSdSeg> kSelect[2][2] = {{k_sd_select<false, false>, k_sd_select<false, true>},
+                                                                {k_sd_select<true, false>, k_sd_select<true, true>}};   // [and][paged]
+    const uint32_t K = plan.K;
+    RankedCall<FcRef, DevSdSeg> c{items, refs, dsegs, sds, plan, n_queries};
+    c.select = kSelect[and_mode][plan.paged];
+    c.select_arg = asc;
+    c.stages = 3;
+    c.ms_acc = g_sd_ms;
+    c.queries = queries; c.terms = terms; c.n_terms = n_terms;
+    c.hits_out = hits_out; c.keys_out = keys_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
+    return run_ranked(ctx, fn, c, [=](const RankedDev<FcRef, DevSdSeg>& d, const SdBatch& b, hipStream_t st) { sd_launch_join(d, b, K, asc, st); },
+                      [=](const RankedDev<FcRef, DevSdSeg>& d, const SdBatch& b, hipStream_t st) {
+                          hipLaunchKernelGGL(k_sd_score, sd_score_grid(b, K), dim3(256), 0, st, d.qd, d.terms, b.q_begin, b.q_end, d.segs, d.aux, K, d.pos, d.nhits, d.hits);
+                      });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3137,128 +3237,47 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
                      const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
-    if (n_queries == 0) { if (device_ms_out) *device_ms_out = 0.0f; return NS_OK; }
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
     if (!queries || !hits_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
-    if (!seg_ids || !segs) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
-    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
-    std::vector<FcSegView> views(n_segs);
-    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
     std::vector<DevBqSeg> bqs(n_segs);
-    for (uint32_t i = 0; i < n_segs; i++) {
-        ns_seg* s = segs[i];
-        if (!s) return fail(ctx, NS_E_INVAL, "%s: segment %u is NULL", fn, i);
-        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
-        views[i].seg_id = seg_ids[i];
-        views[i].n_docs = s->n_docs;
-        views[i].n_postings = s->n_postings;
-        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
-        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
+    const int rc = bind_segments<void>(ctx, fn, seg_ids, segs, nullptr, nullptr, n_segs, views, dsegs, [&](uint32_t i, const ns_seg* s, const void*) {
         bqs[i] = DevBqSeg{s->d_norm, seg_ids[i], 0u};
-    }
+        return (int)NS_OK;
+    });
+    if (rc != NS_OK) return rc;
     std::vector<BqRef> refs;
     std::vector<FcItem> items;
-    std::vector<uint32_t> q_off;
-    std::vector<SdBatch> cuts;
+    RankedPlan plan;
     std::string why;
     const uint32_t tile = ns_facet_tile_docs(), win = bq_win_docs(tile);
-    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    clauses = bq_live_clauses(clauses, n_terms, roles);
     const bool grouped = clauses != nullptr;
     if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, tile, refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
-    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
-    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
-    bool paged = false;
-    if (!after_plan(after, n_queries, views, items, [](uint32_t bits) { return after_ord(bits); }, false, last, paged, why))
+    if (!ranked_call_plan(items, n_queries, k, after, views, [](uint32_t bits) { return after_ord(bits); }, false, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (device_ms_out) *device_ms_out = 0.0f;
-    uint64_t cand_rows = 0;
-    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
-    const size_t n_out = (size_t)n_queries * K;
-    const size_t lds = bq_lds_bytes(win);
-
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    size_t off = 0;
-    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
-    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
-                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_bqs = place_at(off, bqs.size() * sizeof(DevBqSeg)),
-                 o_qoff = place_at(off, q_off.size() * 4), o_hits = place_at(off, n_out * sizeof(ns_hit)),
-                 o_nhits = place_at(off, (size_t)n_queries * 4), o_found = place_at(off, (size_t)n_queries * 8),
-                 o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    std::vector<hipEvent_t> evs(cuts.size() * 3, nullptr);
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    static const SelectKernel<BqRef, DevBqSeg> kSelect[2][2] = {{k_bq_select<false, false>, k_bq_select<true, false>},
+                                                                {k_bq_select<false, true>, k_bq_select<true, true>}};   // [grouped][paged]
+    const uint32_t K = plan.K;
+    RankedCall<BqRef, DevBqSeg> c{items, refs, dsegs, bqs, plan, n_queries};
+    c.select = kSelect[grouped][plan.paged];
+    c.select_arg = win;
+    c.select_lds = bq_lds_bytes(win);
 #if defined(NS_VARIANTS) || defined(NS_COUNT)
-    if (lds > (48u << 10))
-        chk(hipFuncSetAttribute(grouped ? (paged ? reinterpret_cast<const void*>(k_bq_select<true, true>) : reinterpret_cast<const void*>(k_bq_select<false, true>))
-                                        : (paged ? reinterpret_cast<const void*>(k_bq_select<true>) : reinterpret_cast<const void*>(k_bq_select<false>)),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (c.select_lds > (48u << 10))   // (the test windows only: the product's fits the default)
+        c.before = hipFuncSetAttribute(reinterpret_cast<const void*>(c.select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.select_lds);
 #endif
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    for (auto& ev : evs) chk(hipEventCreate(&ev));
-    if (e == hipSuccess) {
-        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
-        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_bqs, bqs.data(), bqs.size() * sizeof(DevBqSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
-        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
-        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
-        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
-        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
-        const FcItem* d_items = (const FcItem*)(blk + o_items);
-        const DevBqSeg* d_bqs = (const DevBqSeg*)(blk + o_bqs);
-        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
-        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
-            const SdBatch& b = cuts[c];
-            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
-            chk(hipEventRecord(evs[c * 3 + 0], st));
-            if (n_it) {
-                if (grouped && paged)
-                    hipLaunchKernelGGL((k_bq_select<true, true>), dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
-                                       d_cand, (unsigned long long*)(blk + o_found), d_last + b.item_begin, d_rest);
-                else if (grouped)
-                    hipLaunchKernelGGL((k_bq_select<false, true>), dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
-                                       d_cand, (unsigned long long*)(blk + o_found), (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                else if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
-                    hipLaunchKernelGGL(k_bq_select<true>, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
-                                       d_cand, (unsigned long long*)(blk + o_found), d_last + b.item_begin, d_rest);
-                else
-                    hipLaunchKernelGGL(k_bq_select<false>, dim3(n_it), dim3(256), lds, st, d_items + b.item_begin, (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), d_bqs, K, win,
-                                       d_cand, (unsigned long long*)(blk + o_found), (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                chk(hipGetLastError());
-            }
-            chk(hipEventRecord(evs[c * 3 + 1], st));
-            hipLaunchKernelGGL(k_bq_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_bqs,
-                               (const uint64_t*)d_cand, K, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_nhits));
-            chk(hipGetLastError());
-            chk(hipEventRecord(evs[c * 3 + 2], st));
-        }
-        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
-        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
-        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
-        chk(hipStreamSynchronize(st));
-        if (e == hipSuccess) {
-            float sum = 0.0f;
-            for (size_t c = 0; c < cuts.size(); c++)
-                for (int j = 0; j < 2; j++) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, evs[c * 3 + j], evs[c * 3 + j + 1]) == hipSuccess) { (grouped ? g_gq_ms : g_bq_ms)[j] += ms; sum += ms; }
-                }
-            if (device_ms_out) *device_ms_out = sum;
-        }
-    }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return NS_OK;
+    c.stages = 2;
+    c.ms_acc = grouped ? g_gq_ms : g_bq_ms;
+    c.hits_out = hits_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
+    return run_ranked(ctx, fn, c, [=](const RankedDev<BqRef, DevBqSeg>& d, const SdBatch& b, hipStream_t st) {
+        hipLaunchKernelGGL(k_bq_join, dim3((b.q_end - b.q_begin + 3) / 4), dim3(256), 0, st, d.items, d.q_off, b.q_begin, b.q_end, b.item_begin, d.aux, d.cand, K, d.hits, d.nhits);
+    }, [](const RankedDev<BqRef, DevBqSeg>&, const SdBatch&, hipStream_t) {});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3316,83 +3335,20 @@ static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, u
     if (n_queries == 0) return NS_OK;
     if (!queries || !counts_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed (the number of buckets comes from the tables)", fn);
-    if (!seg_ids || !segs || !tables) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
-    std::vector<FcSegView> views(n_segs);
-    std::vector<DevFcSeg> dsegs(n_segs);
-    for (uint32_t i = 0; i < n_segs; i++) {
-        ns_seg* s = segs[i];
-        const ns_facet* t = tables[i];
-        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or table %u is NULL", fn, i);
-        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
-        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: table %u does not belong to this ctx", fn, i);
-        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: table %u buckets %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
-        if (t->n_buckets != tables[0]->n_buckets) return fail(ctx, NS_E_INVAL, "%s: table %u has %u buckets, table 0 has %u", fn, i, t->n_buckets, tables[0]->n_buckets);
-        views[i].seg_id = seg_ids[i];
-        views[i].n_docs = s->n_docs;
-        views[i].n_postings = s->n_postings;
-        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
-        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, t->d_buckets, s->n_docs, 0u};
-    }
-    const uint32_t B = tables[0]->n_buckets;
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
+    const int rc = bind_segments(ctx, fn, seg_ids, segs, tables, "table", n_segs, views, dsegs,
+                                 [&](uint32_t i, const ns_seg* s, const ns_facet* t) { return fc_bind_table(ctx, fn, i, s, t, tables[0], dsegs[i]); });
+    if (rc != NS_OK) return rc;
     std::vector<BqRef> refs;
     std::vector<FcItem> items;
     std::string why;
-    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    clauses = bq_live_clauses(clauses, n_terms, roles);
     const bool grouped = clauses != nullptr;
     if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
-    const size_t n_counts = (size_t)n_queries * B;
-    if (!items.empty()) {
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        hipStream_t st = ctx->stream;
-        size_t off = 0;
-        const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
-                     o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_counts = place_at(off, n_counts * 4);
-        const size_t block_bytes = off;
-        char* blk = nullptr;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        hipError_t e = hipSuccess;
-        auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-        chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-        chk(hipEventCreate(&ev0));
-        chk(hipEventCreate(&ev1));
-        if (e == hipSuccess) {
-            chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
-            chk(hipMemsetAsync(blk + o_counts, 0, n_counts * 4, st));
-            chk(hipEventRecord(ev0, st));
-            if (e == hipSuccess) {
-                if (grouped)
-                    hipLaunchKernelGGL(k_bs_count<true>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
-                else
-                    hipLaunchKernelGGL(k_bs_count<false>, dim3((uint32_t)items.size()), dim3(256), 0, st, (const FcItem*)(blk + o_items), (const BqRef*)(blk + o_refs), (const DevFcSeg*)(blk + o_segs), B, (uint32_t*)(blk + o_counts));
-                chk(hipGetLastError());
-            }
-            chk(hipEventRecord(ev1, st));
-            chk(hipMemcpyAsync(counts_out, blk + o_counts, n_counts * 4, hipMemcpyDeviceToHost, st));
-            chk(hipStreamSynchronize(st));
-            float ms = 0.0f;
-            if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
-                (grouped ? g_gq_ms[2] : g_bs_ms[0]) += ms;
-                if (device_ms_out) *device_ms_out = ms;
-            }
-        }
-        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    } else {
-        std::memset(counts_out, 0, n_counts * 4);
-    }
-    if (found_out)
-        for (uint32_t q = 0; q < n_queries; q++) {
-            uint64_t sum = 0;
-            for (uint32_t b = 0; b < B; b++) sum += counts_out[(size_t)q * B + b];
-            found_out[q] = sum;
-        }
-    return NS_OK;
+    return run_count(ctx, fn, items, refs, dsegs, grouped ? k_bs_count<true> : k_bs_count<false>, n_queries, tables[0]->n_buckets, false,
+                     grouped ? &g_gq_ms[2] : &g_bs_ms[0], counts_out, found_out, device_ms_out);
 }
 
 static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
@@ -3405,132 +3361,38 @@ static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     if (!queries || !hits_out || !keys_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
     if (flags & ~NS_SORT_ASC) return fail(ctx, NS_E_INVAL, "%s: flags 0x%x: only NS_SORT_ASC is known (the roles say what matches)", fn, flags);
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
-    if (!seg_ids || !segs || !keys) return fail(ctx, NS_E_INVAL, "%s: null segment arrays", fn);
-    const uint32_t K = std::min<uint32_t>(std::max<uint32_t>(k, 1u), NS_MAX_K);
-    std::vector<FcSegView> views(n_segs);
-    std::vector<DevFcSeg> dsegs(n_segs);
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
     std::vector<DevSdSeg> sds(n_segs);
-    for (uint32_t i = 0; i < n_segs; i++) {
-        ns_seg* s = segs[i];
-        const ns_dockeys* t = keys[i];
-        if (!s || !t) return fail(ctx, NS_E_INVAL, "%s: segment or key table %u is NULL", fn, i);
-        if (s->ctx != ctx || s->pending || s->id >= ctx->segs.size() || ctx->segs[s->id] != s) return fail(ctx, NS_E_INVAL, "%s: segment %u is not a published segment of this ctx", fn, i);
-        if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: key table %u does not belong to this ctx", fn, i);
-        if (t->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: key table %u keys %u documents, its segment has %u", fn, i, t->n_docs, s->n_docs);
-        views[i].seg_id = seg_ids[i];
-        views[i].n_docs = s->n_docs;
-        views[i].n_postings = s->n_postings;
-        if (s->d_skips && !s->lists.skip.empty()) views[i].skip_of = [s](uint32_t first, uint32_t count) { return s->lists.skip_of(first, count); };
-        dsegs[i] = DevFcSeg{s->d_postings, s->d_skips, nullptr, s->n_docs, 0u};
-        sds[i] = DevSdSeg{t->d_keys, s->d_norm, seg_ids[i], 0u};
-    }
+    const int rc = bind_segments(ctx, fn, seg_ids, segs, keys, "key table", n_segs, views, dsegs,
+                                 [&](uint32_t i, const ns_seg* s, const ns_dockeys* t) { return sd_bind_table(ctx, fn, i, s, t, seg_ids[i], sds[i]); });
+    if (rc != NS_OK) return rc;
     const uint32_t asc = (flags & NS_SORT_ASC) ? 1u : 0u;
     std::vector<BqRef> refs;
     std::vector<FcItem> items;
-    std::vector<uint32_t> q_off;
-    std::vector<SdBatch> cuts;
+    RankedPlan plan;
     std::string why;
-    if (clauses && n_terms && !roles) clauses = nullptr;   // no MUST ref reads a clause: the sibling's plan and kernels
+    clauses = bq_live_clauses(clauses, n_terms, roles);
     const bool grouped = clauses != nullptr;
     if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    if (items.size() >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu work items; cut the batch", fn, (unsigned long long)items.size());
-    if (!sd_query_items(items, n_queries, q_off)) return fail(ctx, NS_E_INVAL, "%s: the work items are not grouped by query", fn);
-    if (sd_cut(q_off, n_queries, K, kSdCandBytes, cuts, why) != NS_OK) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    std::vector<uint64_t> last;   // per item of the call; empty: no query has a cursor
-    bool paged = false;
-    if (!after_plan(after, n_queries, views, items, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, last, paged, why))
+    if (!ranked_call_plan(items, n_queries, k, after, views, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
-    uint64_t cand_rows = 0;
-    for (const SdBatch& c : cuts) cand_rows = std::max<uint64_t>(cand_rows, c.item_end - c.item_begin);
-    const size_t n_out = (size_t)n_queries * K;
-    const size_t n_roles = roles ? (size_t)n_terms : 0;
-
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    size_t off = 0;
-    const size_t o_last = place_at(off, last.size() * 8), o_rest = place_at(off, paged ? (size_t)n_queries * 8 : 0);
-    const size_t o_items = place_at(off, items.size() * sizeof(FcItem)), o_refs = place_at(off, refs.size() * sizeof(BqRef)),
-                 o_segs = place_at(off, dsegs.size() * sizeof(DevFcSeg)), o_sds = place_at(off, sds.size() * sizeof(DevSdSeg)),
-                 o_qoff = place_at(off, q_off.size() * 4), o_qd = place_at(off, (size_t)n_queries * sizeof(ns_query_desc)),
-                 o_terms = place_at(off, (size_t)n_terms * sizeof(ns_term_ref)), o_roles = place_at(off, n_roles),
-                 o_hits = place_at(off, n_out * sizeof(ns_hit)), o_keys = place_at(off, n_out * 4), o_pos = place_at(off, n_out * 4),
-                 o_nhits = place_at(off, (size_t)n_queries * 4), o_found = place_at(off, (size_t)n_queries * 8),
-                 o_cand = place_at(off, (size_t)cand_rows * K * 8);   // <= kSdCandBytes
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    std::vector<hipEvent_t> evs(cuts.size() * 4, nullptr);
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    for (auto& ev : evs) chk(hipEventCreate(&ev));
-    if (e == hipSuccess) {
-        if (!items.empty()) chk(hipMemcpyAsync(blk + o_items, items.data(), items.size() * sizeof(FcItem), hipMemcpyHostToDevice, st));
-        if (!refs.empty()) chk(hipMemcpyAsync(blk + o_refs, refs.data(), refs.size() * sizeof(BqRef), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_sds, sds.data(), sds.size() * sizeof(DevSdSeg), hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(blk + o_qd, queries, (size_t)n_queries * sizeof(ns_query_desc), hipMemcpyHostToDevice, st));
-        if (n_terms) chk(hipMemcpyAsync(blk + o_terms, terms, (size_t)n_terms * sizeof(ns_term_ref), hipMemcpyHostToDevice, st));
-        if (n_roles) chk(hipMemcpyAsync(blk + o_roles, roles, n_roles, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(blk + o_found, 0, (size_t)n_queries * 8, st));
-        if (!last.empty()) chk(hipMemcpyAsync(blk + o_last, last.data(), last.size() * 8, hipMemcpyHostToDevice, st));
-        if (paged) chk(hipMemsetAsync(blk + o_rest, 0, (size_t)n_queries * 8, st));
-        const uint64_t* d_last = (const uint64_t*)(blk + o_last);
-        unsigned long long* d_rest = (unsigned long long*)(blk + o_rest);
-        const FcItem* d_items = (const FcItem*)(blk + o_items);
-        const BqRef* d_refs = (const BqRef*)(blk + o_refs);
-        const DevFcSeg* d_segs = (const DevFcSeg*)(blk + o_segs);
-        const DevSdSeg* d_sds = (const DevSdSeg*)(blk + o_sds);
-        const uint8_t* d_roles = n_roles ? (const uint8_t*)(blk + o_roles) : nullptr;
-        unsigned long long* d_found = (unsigned long long*)(blk + o_found);
-        uint64_t* d_cand = (uint64_t*)(blk + o_cand);
-        for (size_t c = 0; c < cuts.size() && e == hipSuccess; c++) {
-            const SdBatch& b = cuts[c];
-            const uint32_t n_it = b.item_end - b.item_begin, n_q = b.q_end - b.q_begin;
-            chk(hipEventRecord(evs[c * 4 + 0], st));
-            if (n_it) {
-                if (grouped && paged)
-                    hipLaunchKernelGGL((k_bs_select<true, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
-                else if (grouped)
-                    hipLaunchKernelGGL((k_bs_select<false, true>), dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                else if (paged)   // last is indexed by the call's item number, as items: both start at the sub-batch's first
-                    hipLaunchKernelGGL(k_bs_select<true>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, d_last + b.item_begin, d_rest);
-                else
-                    hipLaunchKernelGGL(k_bs_select<false>, dim3(n_it), dim3(256), 0, st, d_items + b.item_begin, d_refs, d_segs, d_sds, K, asc, d_cand, d_found, (const uint64_t*)nullptr, (unsigned long long*)nullptr);
-                chk(hipGetLastError());
-            }
-            chk(hipEventRecord(evs[c * 4 + 1], st));
-            hipLaunchKernelGGL(k_sd_join, dim3((n_q + 3) / 4), dim3(256), 0, st, d_items, (const uint32_t*)(blk + o_qoff), b.q_begin, b.q_end, b.item_begin, d_sds,
-                               (const uint64_t*)d_cand, K, asc, (uint32_t*)(blk + o_hits), (uint32_t*)(blk + o_keys), (uint32_t*)(blk + o_pos), (uint32_t*)(blk + o_nhits));
-            chk(hipGetLastError());
-            chk(hipEventRecord(evs[c * 4 + 2], st));
-            const uint64_t n_waves = (uint64_t)n_q * K;
-            hipLaunchKernelGGL(k_bs_score, dim3((uint32_t)((n_waves + 3) / 4)), dim3(256), 0, st, (const ns_query_desc*)(blk + o_qd), (const ns_term_ref*)(blk + o_terms), d_roles,
-                               b.q_begin, b.q_end, d_segs, d_sds, K, (const uint32_t*)(blk + o_pos), (const uint32_t*)(blk + o_nhits), (uint32_t*)(blk + o_hits));
-            chk(hipGetLastError());
-            chk(hipEventRecord(evs[c * 4 + 3], st));
-        }
-        chk(hipMemcpyAsync(hits_out, blk + o_hits, n_out * sizeof(ns_hit), hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(keys_out, blk + o_keys, n_out * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(nhits_out, blk + o_nhits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
-        if (found_out) chk(hipMemcpyAsync(found_out, blk + o_found, (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));
-        if (rest_out) chk(hipMemcpyAsync(rest_out, blk + (paged ? o_rest : o_found), (size_t)n_queries * 8, hipMemcpyDeviceToHost, st));   // no cursor: rest = found
-        chk(hipStreamSynchronize(st));
-        if (e == hipSuccess) {
-            float sum = 0.0f;
-            for (size_t c = 0; c < cuts.size(); c++)
-                for (int j = 0; j < 3; j++) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, evs[c * 4 + j], evs[c * 4 + j + 1]) == hipSuccess) { (grouped ? g_gq_ms + 3 : g_bs_ms + 1)[j] += ms; sum += ms; }
-                }
-            if (device_ms_out) *device_ms_out = sum;
-        }
-    }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return NS_OK;
+    static const SelectKernel<BqRef, DevSdSeg> kSelect[2][2] = {{k_bs_select<false, false>, k_bs_select<true, false>},
+                                                                {k_bs_select<false, true>, k_bs_select<true, true>}};   // [grouped][paged]
+    const uint32_t K = plan.K;
+    RankedCall<BqRef, DevSdSeg> c{items, refs, dsegs, sds, plan, n_queries};
+    c.select = kSelect[grouped][plan.paged];
+    c.select_arg = asc;
+    c.stages = 3;
+    c.ms_acc = grouped ? g_gq_ms + 3 : g_bs_ms + 1;
+    c.queries = queries; c.terms = terms; c.n_terms = n_terms; c.roles = roles; c.roles_region = true;
+    c.hits_out = hits_out; c.keys_out = keys_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
+    return run_ranked(ctx, fn, c, [=](const RankedDev<BqRef, DevSdSeg>& d, const SdBatch& b, hipStream_t st) { sd_launch_join(d, b, K, asc, st); },
+                      [=](const RankedDev<BqRef, DevSdSeg>& d, const SdBatch& b, hipStream_t st) {
+                          hipLaunchKernelGGL(k_bs_score, sd_score_grid(b, K), dim3(256), 0, st, d.qd, d.terms, d.roles, b.q_begin, b.q_end, d.segs, d.aux, K, d.pos, d.nhits, d.hits);
+                      });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4151,111 +4013,37 @@ extern "C" int ns_ac_fuzzy_prefix(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_
 }
 
 #ifdef NS_COUNT
-// Counting build only: the driver-stream body's event counters (ns_driver_kernel.hip; 32 values), optionally reset.
-extern "C" int ns_debug_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsCnt];
+// Counting build only: the N event counters of one device symbol, read after a device synchronize and optionally reset.
+template <size_t N, class Sym>
+static int debug_counters(const Sym& sym, unsigned long long* out, int reset) {
+    unsigned long long h[N];
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_cnt), sizeof(h)) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, sym, sizeof(h)) != hipSuccess) return -1;
     if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_cnt), h, sizeof(h)) != hipSuccess) return -1; }
+    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(sym, h, sizeof(h)) != hipSuccess) return -1; }
     return 0;
 }
-extern "C" int ns_debug_tile_counters(unsigned long long* out, int reset) {
-    unsigned long long h[12];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_tcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_tcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+// the driver-stream body's event counters (ns_driver_kernel.hip; 32 values)
+extern "C" int ns_debug_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsCnt>(HIP_SYMBOL(ns::g_ns_cnt), out, reset); }
+extern "C" int ns_debug_tile_counters(unsigned long long* out, int reset) { return debug_counters<12>(HIP_SYMBOL(ns::g_ns_tcnt), out, reset); }
 // the merge body's counters (ns_merge_kernel.hip): 16 values
-extern "C" int ns_debug_merge_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsMcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_mcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_mcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_merge_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsMcnt>(HIP_SYMBOL(ns::g_ns_mcnt), out, reset); }
 // the candidate buffer's shrinks over all wave bodies (ns_wave_kernel.hip WaveTopK): 4 values
-extern "C" int ns_debug_topk_counters(unsigned long long* out, int reset) {
-    unsigned long long h[4];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_kcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_kcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_topk_counters(unsigned long long* out, int reset) { return debug_counters<4>(HIP_SYMBOL(ns::g_ns_kcnt), out, reset); }
 // the row join's paths and tie rounds (ns_kernels.hip k_merge, k_merge_wide, k_merge_ranks): 16 values
-extern "C" int ns_debug_join_counters(unsigned long long* out, int reset) {
-    unsigned long long h[16];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_jcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_jcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_join_counters(unsigned long long* out, int reset) { return debug_counters<16>(HIP_SYMBOL(ns::g_ns_jcnt), out, reset); }
 // the facet kernel's paths (ns_facet.hip k_fc_count): 8 values
-extern "C" int ns_debug_facet_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsFcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_fcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_fcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_facet_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsFcnt>(HIP_SYMBOL(ns::g_ns_fcnt), out, reset); }
 // the sorted search's paths (ns_sorted.hip k_sd_select, k_sd_join, k_sd_score): 9 values
-extern "C" int ns_debug_sorted_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsScnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_scnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_scnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_sorted_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsScnt>(HIP_SYMBOL(ns::g_ns_scnt), out, reset); }
 // the cursor bound in k_sd_select<., true> and k_bq_select<true> (ns_after.hip): 5 values
-extern "C" int ns_debug_after_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsAcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_acnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_acnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_after_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsAcnt>(HIP_SYMBOL(ns::g_ns_acnt), out, reset); }
 // the boolean search's paths (ns_boolean.hip k_bq_select, k_bq_join): 8 values
-extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsBcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBcnt>(HIP_SYMBOL(ns::g_ns_bcnt), out, reset); }
 // the grouped required stage (ns_boolean.hip k_bq_select<., true>; ns_boolean_sets.hip bs_matched<true>): 11 values
-extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsBgcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bgcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bgcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBgcnt>(HIP_SYMBOL(ns::g_ns_bgcnt), out, reset); }
 // facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values
-extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsBscnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_bscnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_bscnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBscnt>(HIP_SYMBOL(ns::g_ns_bscnt), out, reset); }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values
-extern "C" int ns_debug_fuzzy_counters(unsigned long long* out, int reset) {
-    unsigned long long h[ns::kNsZcnt];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ns::g_ns_zcnt), sizeof(h)) != hipSuccess) return -1;
-    if (out) std::memcpy(out, h, sizeof(h));
-    if (reset) { std::memset(h, 0, sizeof(h)); if (hipMemcpyToSymbol(HIP_SYMBOL(ns::g_ns_zcnt), h, sizeof(h)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int ns_debug_fuzzy_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsZcnt>(HIP_SYMBOL(ns::g_ns_zcnt), out, reset); }
 #endif

@@ -554,6 +554,64 @@ def run_refusals():
         sets.release()
 
 
+def run_refused_between_two_runs():
+    """The five calls that share one call scaffold, each once; then calls that each of them refuses after it has
+    bound its segments (the planner's refusal for the counts, a cursor that names an unlisted segment for the ranked calls,
+    and an unknown flag for the dated ones); then the five again: every output byte is the first run's, and ns_last_error
+    names the refused call.  The refusals are host-side: nothing is launched, and the blocks of the first runs are in the pool."""
+    L = nsbind.hip_lib()
+    segments, queries, idfs, weights, order = mixed_inputs()
+    sets = Sets(boolean_shapes.Family(segments, queries, idfs, weights, seg_order=order), keys_for(segments, "pool5"))
+    fam = sets.fam
+    ctx, Q, B, K = fam.segs.ctx, len(fam.qd), 50, 10
+    tabs = [nsbind.facet_upload(ctx, t, B)[1] for t in [tables_for(segments, "modulo", B)[s] for s in order]]
+    try:
+        hs, ks = sets.handles, sets.key_handles()
+        alien = nsbind.cursors([(20200101, 7, 5)] * Q)                            # the call lists segments 2, 0, 1
+        past = fam.refs.copy()
+        past["byte_off"][0] = 8 * 10 ** 6
+        calls = {
+            "ns_facet_count": lambda refs=fam.refs: nsbind.facet_count(ctx, fam.qd, refs, 0, order, hs, tabs, B),
+            "ns_search_sorted_after": lambda after=None, flags=ASC: nsbind.search_sorted_after_raw(ctx, fam.qd, fam.refs, K, flags, after, order, hs, ks),
+            "ns_search_boolean_after": lambda after=None: nsbind.search_boolean_after_raw(ctx, fam.qd, fam.refs, fam.roles, K, after, order, hs),
+            "ns_facet_count_boolean": lambda refs=fam.refs: nsbind.facet_count_boolean(ctx, fam.qd, refs, fam.roles, order, hs, tabs, B),
+            "ns_search_sorted_boolean": lambda after=None, flags=ASC: nsbind.search_sorted_boolean_raw(ctx, fam.qd, fam.refs, fam.roles, K, flags, after, order, hs, ks),
+        }
+        unlisted = "query 0: cursor names segment 7, which the call does not list"
+        refusals = [("ns_facet_count", dict(refs=past), "runs past the postings"), ("ns_facet_count_boolean", dict(refs=past), "runs past the postings"),
+                    ("ns_search_sorted_after", dict(after=alien), unlisted), ("ns_search_boolean_after", dict(after=alien), unlisted),
+                    ("ns_search_sorted_boolean", dict(after=alien), unlisted),
+                    ("ns_search_sorted_after", dict(flags=0x2000), "flags 0x2000: only NS_FLAG_AND and NS_SORT_ASC are known"),
+                    ("ns_search_sorted_boolean", dict(flags=AND), "flags 0x1: only NS_SORT_ASC is known")]
+
+        def run_all():
+            out = {}
+            for name, call in calls.items():
+                res = call()
+                assert res[0] == 0, (name, L.ns_last_error(ctx).decode())
+                out[name] = [a.tobytes() for a in res[1:-1]]                      # every output array; the last member is the time
+                assert len(out[name]) >= 2 and all(out[name])
+            return out
+
+        first = run_all()
+        assert int(np.frombuffer(first["ns_facet_count"][1], dtype=np.uint64).sum()) > 0      # found: the runs are about something
+        for name, change, match in refusals:
+            res = calls[name](**change)
+            assert res[0] == NS_E_INVAL, (name, res[0])
+            msg = L.ns_last_error(ctx).decode()
+            assert msg.startswith(name + ": ") and match in msg, msg
+            # (the binding fills hits with 0xAB bytes and the integer arrays with the value 0xABABABAB)
+            assert all(np.all(a.view(np.uint8) == 0xAB if a.dtype.names else a == 0xABABABAB) for a in res[1:-1]), "a refused call writes nothing"
+        assert run_all() == first
+        for name, change, _ in refusals:                                           # and a refusal directly before its own call's rerun
+            assert calls[name](**change)[0] == NS_E_INVAL
+            assert [a.tobytes() for a in calls[name]()[1:-1]] == first[name], name
+    finally:
+        for h in tabs:
+            nsbind.facet_release(ctx, h)
+        sets.release()
+
+
 def run_one_query_past_the_candidate_buffer():
     """a single query whose work items x K x 8 B exceed the 64 MiB of candidate rows is refused; with one item fewer it runs.
     Only a small tile makes that many items affordable: a segment of (rows + 1) x tile documents and one list of three postings."""

@@ -113,6 +113,12 @@ def test_refusals():
     shapes.run_refusals()
 
 
+def test_a_refused_call_between_two_runs_changes_no_byte_of_the_second():
+    """ns_facet_count, ns_search_sorted_after, ns_search_boolean_after, ns_facet_count_boolean and ns_search_sorted_boolean share
+    one scaffold: after a call that one of them refuses, each answers as before, from the pooled block"""
+    shapes.run_refused_between_two_runs()
+
+
 # ---- 5: the engine ------------------------------------------------------------------------------------------------------
 served = bq.served                                   # the boolean engine tests' generated index: three segments, dated documents
 QUERIES = ["w001 w002", "+w001 +w002", "w001 w002 -w000", "+w001 w002 -w000", "+rarea w003 -rarec", "rareb -w001", "-w000", "+zzzzqq w001", ""]
