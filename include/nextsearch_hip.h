@@ -248,6 +248,23 @@ int ns_ctx_share_rows(ns_ctx* ctx, int mode);
  * for them): consumer items that fell back to the streaming body, row entries that were docs of a tail. */
 int ns_batch_row_stats(ns_batch* b, uint32_t out[4]);
 
+/* Class model: which scoring body a (query, segment) group takes.  The density rule sends a group of two or more lists with at
+ * least 0.25 postings per doc to the doc-tile body and every other group that no single list dominates to the driver-stream
+ * body (or, with two lists, the merge).  mode 1 (the default of a ctx): in a batch large enough to fill the chip, such a group
+ * also takes doc tiles when their modelled cost (per 1024-doc tile, per (list, tile) visit, per posting) undercuts the modelled
+ * cost of the body it would have, and tile groups are cut and ordered by that model.  mode 0: the density rule alone.  mode 2:
+ * the model in every batch, however small (tests, sweeps).  Results are byte-identical in every mode.  NS_CLASS_MODEL in the
+ * environment of ns_ctx_create overrides the default. */
+int ns_ctx_class_model(ns_ctx* ctx, int mode);
+/* out: groups of the batch as prepared that take the driver-stream or merge body, the thin driver-stream body (row consumers
+ * included) and the doc-tile body; then how many of the last the class model promoted. */
+int ns_batch_class_stats(ns_batch* b, uint32_t out[4]);
+/* Sweeps only (tools/class_fit.py): groups of three or more lists that the density rule leaves to the driver-stream body, whose
+ * share of postings outside the largest list lies in [share10 / 10, (share10 + 1) / 10) and whose postings per 64 docs lie in
+ * [dens64_lo, dens64_hi), take the doc-tile body (body 1) or keep the driver-stream body (body 2), whatever the mode and the
+ * size of the batch; body 0 ends the forcing. */
+int ns_ctx_class_force(ns_ctx* ctx, uint32_t body, uint32_t share10, uint32_t dens64_lo, uint32_t dens64_hi);
+
 /* ---- one-shot search (host buffers in, host buffers out) ------------------------------------ */
 /* hits_out: Q*K entries, query-major, best first: score desc, then seg_id asc, then doc_id asc
  * (the reference leaves ties unspecified: src/api_engine.cpp:485-492); unused tail entries are

@@ -248,6 +248,13 @@ extern "C" int ns_ctx_create(int device, ns_ctx** out) {
         const char* rf = std::getenv("NS_ROW_FORK");   // 0: the producers stay on the batch's stream (measurements)
         if ((!rf || std::atoi(rf) != 0) && hipStreamCreateWithFlags(&ctx->row_stream, hipStreamNonBlocking) != hipSuccess) { ctx->row_stream = nullptr; (void)hipGetLastError(); }
     }
+    ctx->cfg.class_model = 1;
+    if (const char* cm = std::getenv("NS_CLASS_MODEL")) ctx->cfg.class_model = std::max(0, std::min(2, std::atoi(cm)));
+    if (const char* mg = std::getenv("NS_CLASS_MARGIN")) ctx->cfg.class_margin_pct = (uint32_t)std::max(1, std::atoi(mg));
+    if (const char* tc = std::getenv("NS_TILE_COST")) {
+        unsigned a = kTileCostTile16, v = kTileCostVisit16, p = kTileCostPosting16;
+        if (std::sscanf(tc, "%u,%u,%u", &a, &v, &p) >= 1) { ctx->cfg.tile_cost16[0] = a; ctx->cfg.tile_cost16[1] = v; ctx->cfg.tile_cost16[2] = p; }
+    }
     if (const char* oc = std::getenv("NS_ORDER_COARSE")) { ctx->cfg.order_coarse = std::max(0, std::min(11, std::atoi(oc))); ctx->cfg.order_coarse_forced = true; }
     if (hipStreamCreateWithFlags(&ctx->alt_stream, hipStreamNonBlocking) != hipSuccess) { ctx->alt_stream = nullptr; (void)hipGetLastError(); }
     {
@@ -696,6 +703,21 @@ extern "C" int ns_ctx_share_rows(ns_ctx* ctx, int mode) {
     return NS_OK;
 }
 
+extern "C" int ns_ctx_class_model(ns_ctx* ctx, int mode) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_class_model: ctx is NULL");
+    if (mode < 0 || mode > 2) return fail(ctx, NS_E_INVAL, "ns_ctx_class_model: mode %d outside [0, 2]", mode);
+    ctx->cfg.class_model = mode;
+    return NS_OK;
+}
+
+// sweeps only (tools/class_fit.py): see PlanSettings::force_body
+extern "C" int ns_ctx_class_force(ns_ctx* ctx, uint32_t body, uint32_t share10, uint32_t dens64_lo, uint32_t dens64_hi) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_class_force: ctx is NULL");
+    if (body > 2 || share10 > 9 || dens64_lo > dens64_hi) return fail(ctx, NS_E_INVAL, "ns_ctx_class_force: body %u, share tenth %u, density [%u, %u)", body, share10, dens64_lo, dens64_hi);
+    ctx->cfg.force_body = body; ctx->cfg.force_share10 = share10; ctx->cfg.force_dens_lo = dens64_lo; ctx->cfg.force_dens_hi = dens64_hi;
+    return NS_OK;
+}
+
 extern "C" int ns_segment_build_packed(ns_ctx* ctx, ns_seg* seg) {
     if (!ctx || !seg) return fail(ctx, NS_E_INVAL, "ns_segment_build_packed: null argument");
     if (seg->pending || seg->id >= ctx->segs.size() || ctx->segs[seg->id] != seg) return fail(ctx, NS_E_INVAL, "segment does not belong to this ctx");
@@ -970,6 +992,7 @@ struct ns_batch {
     DevShare* d_share = nullptr;   // n_share + 1 entries
     // shared top rows (ns_ctx_share_rows): producer items (k_uscore with K' = kRowLen into the row buffer), consumer items (k_rscore)
     uint32_t n_pitems = 0, n_ritems = 0;
+    uint32_t class_stats[4] = {0, 0, 0, 0};   // ns_batch_class_stats
     DevWItem* d_pitems = nullptr;
     DevRItem* d_ritems = nullptr;
     Hit* d_row_hits = nullptr;         // kRowLen entries per producer item
@@ -1169,6 +1192,7 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
     b->pruned = P.pruned;
     b->n_wide_q = (uint32_t)P.wide_q.size();
     b->n_pitems = P.n_pitems; b->n_ritems = P.n_ritems;
+    std::memcpy(b->class_stats, P.class_stats, sizeof(b->class_stats));
 
     // One device block per batch: [descriptors, uploaded in one copy][scratch][hits | nhits | found, fetched in one copy]
     hipError_t e = hipSuccess;
@@ -1599,6 +1623,13 @@ extern "C" int ns_batch_row_stats(ns_batch* b, uint32_t out[4]) {
         HIPCHK(ctx, hipMemcpyAsync(out + 2, b->d_row_stats, 8, hipMemcpyDeviceToHost, b->st));
         HIPCHK(ctx, hipStreamSynchronize(b->st));
     }
+    return NS_OK;
+}
+
+// the batch's (query, segment) groups by scoring body after the class rule, and those the class model promoted
+extern "C" int ns_batch_class_stats(ns_batch* b, uint32_t out[4]) {
+    if (!b || !out) return NS_E_INVAL;
+    std::memcpy(out, b->class_stats, sizeof(b->class_stats));
     return NS_OK;
 }
 

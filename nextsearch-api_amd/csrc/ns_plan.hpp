@@ -51,6 +51,18 @@ static constexpr uint32_t kDefaultSplitPostings = 32768;   // forced variants: p
 // top-K warm-up and its K-row partial result, so large K wants fewer, longer items (sweeps: profiles/r01).
 static constexpr uint32_t kSplitWorkSmallK = 98304, kSplitWorkLargeK = 131072;
 static constexpr uint64_t kWorkForeign = 8, kWorkTile = 2, kWorkMerge = 4;   // merge: fitted on two-list laws (profiles/r03): 1.0 ps per unit, like the general class
+// Class model (ns_ctx_class_model; DESIGN.md §4 "Choosing the body by modelled cost"): what the doc-tile body costs a group, in
+// sixteenths of a work unit: 250 units per 1024-doc tile of the segment (header, top-K read-back, and the latency of a tile
+// in the item's chain), 40 per (term, tile) visit and 0.6 per posting.  The visits of a list of c postings over t tiles are
+// t * (1 - exp(-c / t)), from the table below (c / t in eighths, value in 1/256).  A class-0 group is promoted to doc tiles
+// when kClassMarginPct per cent of that cost is at most its general (or merge) cost: no margin, because the whole-batch A/B
+// that chose the constants (profiles/class_model/README.md) ran faster without one at every per-tile price tried.
+static constexpr uint32_t kTileCostTile16 = 4000, kTileCostVisit16 = 640, kTileCostPosting16 = 10;
+static constexpr uint32_t kClassMarginPct = 100;
+static constexpr uint16_t kTileOcc256[65] = {
+    0, 30, 57, 80, 101, 119, 135, 149, 162, 173, 183, 191, 199, 206, 212, 217, 221, 225, 229, 232, 235, 237, 240, 242, 243, 245,
+    246, 247, 248, 249, 250, 251, 251, 252, 252, 253, 253, 253, 254, 254, 254, 254, 255, 255, 255, 255, 255, 255, 255, 255,
+    256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256};
 static constexpr uint32_t kSkipMinCount = 64;   // shorter lists are never looked up in the skip registry (ns_segment_build_skips)
 // per-item, per-term constants of the launch-order key (fitted to per-item timestamps, tools/dbg/item_times.py)
 static constexpr uint64_t kItemTermGeneral = 4000, kItemTermThin = 3000, kItemTermTile = 8000;   // general re-fitted in round 2 (10000 -> 4000: ab16)
@@ -198,6 +210,17 @@ struct PlanSettings {
     int row_mode = 0;
     uint32_t row_min_users = kRowMinUsers;
     uint32_t row_cell_postings = kRowCellPostings;
+    // Class model (ns_ctx_class_model): 0 the density rule alone; 1 in a batch that fills the chip (no finer cut under the old
+    // classes) a class-0 group whose modelled doc-tile cost undercuts its general cost becomes a tile group, and every tile
+    // group is estimated by the model; 2 in every batch (tests, sweeps).  A ctx starts with 1 (ns_ctx_create; NS_CLASS_MODEL,
+    // NS_CLASS_MARGIN and NS_TILE_COST=tile,visit,posting override mode, margin and constants for sweeps).
+    int class_model = 0;
+    uint32_t class_margin_pct = kClassMarginPct;
+    uint32_t tile_cost16[3] = {kTileCostTile16, kTileCostVisit16, kTileCostPosting16};
+    // sweeps only (ns_ctx_class_force; tools/class_fit.py): class-0 groups of three or more terms whose foreign share
+    // rest / cost lies in tenth number force_share10 and whose postings per 64 docs lie in [force_dens_lo, force_dens_hi)
+    // take the doc-tile body (force_body 1) or keep the general one whatever the model says (2); 0 = no forcing
+    uint32_t force_body = 0, force_share10 = 0, force_dens_lo = 0, force_dens_hi = 0;
 };
 
 // A batch's device block is laid out in 256-byte aligned arrays: the offset of the next one of `bytes` bytes
@@ -207,6 +230,19 @@ inline size_t place_at(size_t& off, size_t bytes) {
     return o;
 }
 
+// The class model's doc-tile cost of a group in work units (integers only: the same on every host thread)
+inline uint64_t tile_model_cost(const uint32_t cost16[3], const DevTerm* dt, uint32_t n_terms, uint32_t n_docs) {
+    const uint64_t tiles = ((uint64_t)n_docs + kSkipDocs - 1) / kSkipDocs;
+    if (!tiles) return 0;
+    uint64_t occ = 0, postings = 0;   // occ: the sum over the lists of the share of the tiles they visit, in 1/256
+    for (uint32_t i = 0; i < n_terms; i++) {
+        occ += kTileOcc256[std::min<uint64_t>((uint64_t)dt[i].count * 8 / tiles, 64)];
+        postings += dt[i].count;
+    }
+    const uint64_t c16 = cost16[0] * tiles + cost16[1] * (tiles * occ / 256) + cost16[2] * postings;
+    return (c16 + 15) / 16;
+}
+
 // ---- the planner ---------------------------------------------------------------------------------------------------
 // A batch is planned in three fork-join phases over contiguous slices of the queries (the reference's requests are
 // independent, src/api_engine.cpp:369): A regroup + classify, B cut into work items, C write the descriptors into the
@@ -214,6 +250,7 @@ inline size_t place_at(size_t& off, size_t bytes) {
 // (descriptor bytes, launch order) is independent of the number of threads.
 
 struct HostGroup { DevGroup g; uint32_t query; uint64_t cost; uint64_t cmax; uint64_t work; bool wave; uint8_t cls; bool fast_div; bool signed_in; bool grid; bool merge2;
+                   bool promoted;     // class model: a class-0 group by the density rule that the model made a tile group
                    uint32_t rkey1; };   // shared top rows: 0, or 1 + the group's entry in BatchPlan::rkeys (its items are consumers)
 
 // Shared top rows: a hot list as its users score it — the list, its idf and its weight, bit for bit
@@ -299,6 +336,7 @@ struct BatchPlan {
     uint32_t n_class[3] = {0, 0, 0};    // auto mode: narrow wave items (<= 16 terms), then wide ones; contiguous in launch order
     uint64_t bounds_total = 0, postings_total = 0;
     bool direct = false;                // every query has exactly one work item: the scoring kernel writes final rows
+    uint32_t class_stats[4] = {0, 0, 0, 0};   // auto mode: groups of class 0 (general and merge), 1 (thin), 2 (tile) after the rule; groups the class model promoted
     bool all_imp = false, all_pk = false, pruned = false;
     // shared term scores: the distinct lists the batch builds, in build order, and their postings
     bool shared = false;
@@ -479,6 +517,44 @@ struct BatchPlan {
             all_imp = all_imp && S.all_imp;
             all_pk = all_pk && S.all_pk;
         }
+        // ---- class model (ns_ctx_class_model), between phases A and B as the row pass is: whether the batch fills the chip is
+        // known only now.  It does when cut() would not cut it finer than the default share under the classes of the density
+        // rule (cut()'s fine_cut, restated); a batch that leaves wave slots idle is bound by its longest chain, where the fitted
+        // costs do not hold.  Then every tile group is estimated by the model — the estimate cuts it into ranges and orders its
+        // items — and a class-0 group whose modelled tile cost undercuts its general or merge cost by the margin joins them.
+        if (auto_mode && (C.class_model != 0 || C.force_body != 0)) {
+            const uint64_t share0 = k <= 32 ? kSplitWorkSmallK : kSplitWorkLargeK;
+            const bool fills = !C.split_postings && total_work / ((uint64_t)std::max(C.n_cus, 1) * 96u) >= share0;
+            const bool model_on = C.class_model == 2 || (C.class_model == 1 && fills);
+            if (model_on || C.force_body != 0) {
+                fork([&](unsigned si) {
+                    PrepSlice& S = slices[si];
+                    for (HostGroup& hg : S.groups) {
+                        const uint32_t nd = SV[hg.g.seg].n_docs;
+                        if (!hg.wave || hg.g.term_count < 2 || hg.cls == 1 || nd == 0) continue;
+                        const uint64_t tc = tile_model_cost(C.tile_cost16, S.dterms.data() + hg.g.term_begin, hg.g.term_count, nd);
+                        const uint64_t old = hg.work;
+                        if (hg.cls == 2) {
+                            if (model_on) hg.work = tc;
+                        } else {
+                            bool promote = model_on && tc * C.class_margin_pct <= hg.work * 100;
+                            if (C.force_body != 0 && hg.g.term_count >= 3 && (hg.cost - hg.cmax) * 10 / hg.cost == C.force_share10) {
+                                const uint64_t d64 = hg.cost * 64 / nd;
+                                if (d64 >= C.force_dens_lo && d64 < C.force_dens_hi) promote = C.force_body == 1;
+                            }
+                            if (promote) { hg.cls = 2; hg.merge2 = false; hg.promoted = true; hg.work = tc; }
+                        }
+                        S.total_work += hg.work - old;   // (modulo 2^64: the sum stays exact)
+                    }
+                });
+                total_work = 0;
+                for (unsigned s = 0; s < width; s++) total_work += slices[s].total_work;
+            }
+        }
+        class_stats[0] = class_stats[1] = class_stats[2] = class_stats[3] = 0;
+        if (auto_mode)
+            for (unsigned s = 0; s < width; s++)
+                for (const HostGroup& hg : slices[s].groups) { class_stats[hg.cls]++; class_stats[3] += hg.promoted ? 1u : 0u; }
         if (bounds_total >= (1ull << 32)) return failed(NS_E_INVAL, "batch too large: %llu boundary entries; split the batch", (unsigned long long)bounds_total);
 
         // ---- shared term scores (ns_ctx_share_scores; k_share_scores): the batch's distinct lists, each listed once, in the

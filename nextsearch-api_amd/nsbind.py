@@ -71,6 +71,7 @@ HIP_SYMBOLS = [
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
     "ns_batch_destroy", "ns_set_tuning", "ns_segment_build_impacts", "ns_ctx_use_impacts", "ns_ctx_set_host_threads", "ns_ctx_set_overlap", "ns_segment_build_packed", "ns_ctx_use_packed", "ns_segment_build_skips", "ns_ctx_use_skips", "ns_segment_build_blockmax", "ns_ctx_use_pruning", "ns_ctx_use_merge", "ns_ctx_share_scores", "ns_ctx_share_rows", "ns_batch_row_stats",
+    "ns_ctx_class_model", "ns_batch_class_stats", "ns_ctx_class_force",
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release", "ns_ac_build_fuzzy", "ns_ac_fuzzy", "ns_ac_fuzzy_prefix",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
@@ -207,6 +208,10 @@ def hip_lib():
         if hasattr(L, "ns_ctx_share_rows"):   # (an A/B run may load a library from before shared top rows: NS_HIP_LIB)
             L.ns_ctx_share_rows.argtypes = [vp, i32]
             L.ns_batch_row_stats.argtypes = [vp, vp]
+        if hasattr(L, "ns_ctx_class_model"):   # (likewise: a library from before the class model)
+            L.ns_ctx_class_model.argtypes = [vp, i32]
+            L.ns_batch_class_stats.argtypes = [vp, vp]
+            L.ns_ctx_class_force.argtypes = [vp, u32, u32, u32, u32]
         L.ns_sem_upload.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
         L.ns_sem_release.argtypes = [vp, vp]
         L.ns_sem_topk.argtypes = [vp, vp, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp]
@@ -548,6 +553,14 @@ class Batch:
         rc = hip_lib().ns_batch_row_stats(self.h, out.ctypes.data)
         if rc != NS_OK:
             raise RuntimeError(f"ns_batch_row_stats failed rc={rc}")
+        return tuple(int(x) for x in out)
+
+    def class_stats(self):
+        """(general and merge, thin, tile, promoted) groups of the batch as prepared (ns_batch_class_stats)"""
+        out = np.zeros(4, dtype=np.uint32)
+        rc = hip_lib().ns_batch_class_stats(self.h, out.ctypes.data)
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_batch_class_stats failed rc={rc}")
         return tuple(int(x) for x in out)
 
     def close(self):
@@ -1479,6 +1492,16 @@ class Engine:
 
     def use_impacts(self, on):
         self._L.nsh_engine_use_impacts(self.h, 1 if on else 0)
+
+    def class_model(self, mode):
+        """0 the density rule alone, 1 (default) the cost model in batches that fill the chip, 2 in every batch (ns_ctx_class_model)"""
+        if hip_lib().ns_ctx_class_model(self.ctx, int(mode)) != NS_OK:
+            raise RuntimeError(hip_lib().ns_last_error(self.ctx).decode())
+
+    def class_force(self, body, share10=0, dens64_lo=0, dens64_hi=0):
+        """sweeps only: force the class-0 groups of one (foreign share, density) bin to one body (ns_ctx_class_force)"""
+        if hip_lib().ns_ctx_class_force(self.ctx, int(body), int(share10), int(dens64_lo), int(dens64_hi)) != NS_OK:
+            raise RuntimeError(hip_lib().ns_last_error(self.ctx).decode())
 
     def set_tuning(self, variant=0, min_items=0, split_postings=0):
         rc = hip_lib().ns_set_tuning(self.ctx, variant, min_items, split_postings)
