@@ -1080,6 +1080,96 @@ static void pool_free(ns_ctx* ctx, void* p, size_t n) {
     ctx->pool_bytes += n;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The scaffold of a pooled one-shot call.
+// The device blocks of one call: regions laid out with place_at, pooled allocations, the call's events and the first HIP
+// error.  reserve() everything, alloc(), then work on the stream only while ok(); finish() on every path after alloc().
+// A call that sizes a further block by what it read back from an earlier one goes on with open(), reserve() and alloc():
+// at(off), upload(), zero() and fetch() address the newest block, at(off, b) the one that alloc() numbered b.
+struct CallBlock {
+    struct Held { char* p; size_t n; };
+    ns_ctx* ctx;
+    hipStream_t st;
+    size_t bytes = 0;              // the layout cursor of the block being laid out
+    char* blk = nullptr;           // the newest block
+    std::vector<Held> held;        // every block the call holds, in order of allocation
+    std::vector<hipEvent_t> evs;   // none in a call that times nothing
+    hipError_t e = hipSuccess;
+
+    explicit CallBlock(ns_ctx* c) : ctx(c), st(c->stream) {}
+    void chk(hipError_t r) { if (e == hipSuccess) e = r; }
+    bool ok() const { return e == hipSuccess; }
+    size_t reserve(size_t n) { return place_at(bytes, n); }   // (a region of no bytes still takes a place)
+    void open() { bytes = 0; }
+    size_t alloc(size_t n_events) {
+        blk = nullptr;
+        const hipError_t r = pool_alloc(ctx, (void**)&blk, bytes);
+        chk(r);
+        if (r != hipSuccess) { blk = nullptr; return held.size(); }   // no block, no events: the call is not ok() from here on
+        held.push_back({blk, bytes});
+        for (size_t i = 0; i < n_events; i++) { hipEvent_t ev = nullptr; chk(hipEventCreate(&ev)); evs.push_back(ev); }
+        return held.size() - 1;   // the block's number for at(off, b)
+    }
+    template <class T> T* at(size_t off) const { return (T*)(blk + off); }
+    template <class T> T* at(size_t off, size_t b) const { return (T*)(held[b].p + off); }
+    size_t held_bytes() const { size_t n = 0; for (auto& h : held) n += h.n; return n; }
+    void upload(size_t off, const void* src, size_t n) { if (n) chk(hipMemcpyAsync(blk + off, src, n, hipMemcpyHostToDevice, st)); }
+    void zero(size_t off, size_t n) { chk(hipMemsetAsync(blk + off, 0, n, st)); }
+    void fetch(void* dst, size_t off, size_t n) { chk(hipMemcpyAsync(dst, blk + off, n, hipMemcpyDeviceToHost, st)); }
+    void record(size_t ev) { if (ev < evs.size()) chk(hipEventRecord(evs[ev], st)); }
+    void launched() { chk(hipGetLastError()); }
+    void sync() { chk(hipStreamSynchronize(st)); }
+    // the interval between two recorded events, once the call has synchronised without an error
+    bool elapsed_ms(size_t first, size_t second, float* ms) const {
+        return ok() && first < evs.size() && second < evs.size() && hipEventElapsedTime(ms, evs[first], evs[second]) == hipSuccess;
+    }
+    // the blocks go back to the pool, newest first, only once nothing in flight uses them, whatever failed before;
+    // `what` replaces the error's own text in the message
+    int finish(const char* fn, const char* what = nullptr) {
+        if (!held.empty()) (void)hipStreamSynchronize(st);
+        for (size_t b = held.size(); b-- > 0;) pool_free(ctx, held[b].p, held[b].n);
+        for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, what ? what : hipGetErrorString(e));
+        return NS_OK;
+    }
+};
+
+// Host memory for one call's upload image (`up` bytes) and, with down != 0, its result image: the ctx's pinned staging
+// buffers where they are free and hold the image (grown to n + n / 2, at least 64 KiB; nothing above kStageMaxBytes is
+// pinned, and h_down is a batch's while it has an owner), pageable memory of the call's own otherwise.
+struct Staged {
+    char *up = nullptr, *down = nullptr;
+    bool up_pinned = false;
+    std::vector<char> up_own, down_own;
+};
+static hipError_t stage_host(ns_ctx* ctx, size_t up, size_t down, Staged& s) {
+    if (ctx->up_busy) {   // a batch's upload may still be reading the staging buffer
+        const hipError_t e = hipEventSynchronize(ctx->up_done);
+        ctx->up_busy = false;
+        if (e != hipSuccess) return e;
+    }
+    if (up <= kStageMaxBytes && ctx->h_up_cap < up) {
+        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
+        ctx->h_up = nullptr; ctx->h_up_cap = 0;
+        const size_t cap = std::max<size_t>(up + up / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
+        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
+    }
+    s.up_pinned = ctx->h_up_cap >= up;
+    s.up = s.up_pinned ? (char*)ctx->h_up : (s.up_own.resize(up), s.up_own.data());
+    if (!down) return hipSuccess;
+    const bool down_free = !ctx->down_owner && down <= kStageMaxBytes;
+    if (down_free && ctx->h_down_cap < down) {
+        if (ctx->h_down) (void)hipHostFree(ctx->h_down);
+        ctx->h_down = nullptr; ctx->h_down_cap = 0;
+        const size_t cap = std::max<size_t>(down + down / 2, 1 << 16);
+        if (hipHostMalloc(&ctx->h_down, cap, hipHostMallocDefault) == hipSuccess) ctx->h_down_cap = cap;
+        else { ctx->h_down = nullptr; (void)hipGetLastError(); }
+    }
+    s.down = (down_free && ctx->h_down_cap >= down) ? (char*)ctx->h_down : (s.down_own.resize(down), s.down_own.data());
+    return hipSuccess;
+}
+
 __global__ void __launch_bounds__(256) k_pull(uint4* __restrict__ dst, const uint4* __restrict__ src, uint32_t n16) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n16) dst[i] = src[i];
@@ -1266,25 +1356,14 @@ extern "C" int ns_batch_prepare(ns_ctx* ctx, const ns_query_desc* queries, const
             }
         }
     }
-    if (e == hipSuccess && ctx->up_busy) {   // the previous batch's upload may still be reading the staging buffer
-        chk(hipEventSynchronize(ctx->up_done));
-        ctx->up_busy = false;
-    }
-    if (e == hipSuccess && up_bytes <= kStageMaxBytes && ctx->h_up_cap < up_bytes) {
-        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
-        ctx->h_up = nullptr; ctx->h_up_cap = 0;
-        const size_t cap = std::max<size_t>(up_bytes + up_bytes / 2, 1 << 16);
-        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
-        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
-    }
+    Staged stage;   // (the previous batch's upload may still be reading the staging buffer: stage_host waits for it)
+    if (e == hipSuccess) chk(stage_host(ctx, up_bytes, 0, stage));
     if (e == hipSuccess && !ctx->up_done) chk(hipEventCreateWithFlags(&ctx->up_done, hipEventDisableTiming));
     if (e == hipSuccess) {
         // ---- the descriptors go straight into the pinned staging buffer (or, for a batch too large for it, into a host
         // vector that is copied array by array) ----
-        const bool staged = ctx->h_up_cap >= up_bytes && ctx->up_done;
-        std::vector<char> unstaged;
-        if (!staged) unstaged.resize(up_bytes);
-        char* hb = staged ? (char*)ctx->h_up : unstaged.data();
+        const bool staged = stage.up_pinned;
+        char* hb = stage.up;
         P.write(hb);
         if (!segs.empty()) std::memcpy(hb + L.segs, segs.data(), segs.size() * sizeof(segs[0]));
         if (staged) {
@@ -1690,10 +1769,6 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
 
     // one block from the ctx pool for all scratch arrays (a build loop inverts segment after segment of similar size;
     // ten hipMalloc + hipFree per call cost more than the device work)
-    uint2 *d_pairs = nullptr, *d_vals[2] = {nullptr, nullptr};
-    uint32_t *d_keys[2] = {nullptr, nullptr}, *d_df = nullptr, *d_first = nullptr, *d_hist = nullptr, *d_sums = nullptr, *d_kept = nullptr;
-    uint64_t* d_prefix = nullptr;
-    uint2* d_tile_docs = nullptr;
     // the documents that hold each tile's first and last pair (the host has the prefix sums; the first pass marks the
     // documents that start in between): the last d with prefix[d] <= i
     std::vector<uint32_t> tile_docs((size_t)n_tiles * 2);
@@ -1706,36 +1781,27 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
             tile_docs[2 * (size_t)t + 1] = doc_of(i1);
         }
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
+    CallBlock blk(ctx);
     const size_t nt1 = (size_t)std::max<uint32_t>(n_terms, 1);
-    const size_t o_pairs = place(dev_pairs ? 1 : (size_t)n * 8), o_v0 = place((size_t)n * 8), o_v1 = place(passes > 1 ? (size_t)n * 8 : 1);
-    const size_t o_k0 = place((size_t)n * 4), o_k1 = place(passes > 1 ? (size_t)n * 4 : 1);
-    const size_t o_df = place(nt1 * 4), o_first = place(nt1 * 4), o_hist = place(m_max * 4), o_sums = place((size_t)scan_blocks_max * 4), o_kept = place(4), o_prefix = place(prefix.size() * 8), o_tdocs = place((size_t)n_tiles * 8);
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    if (e == hipSuccess) {
-        d_pairs = dev_pairs ? const_cast<uint2*>(dev_pairs) : (uint2*)(blk + o_pairs); d_vals[0] = (uint2*)(blk + o_v0); d_vals[1] = (uint2*)(blk + o_v1);
-        d_keys[0] = (uint32_t*)(blk + o_k0); d_keys[1] = (uint32_t*)(blk + o_k1);
-        d_df = (uint32_t*)(blk + o_df); d_first = (uint32_t*)(blk + o_first); d_hist = (uint32_t*)(blk + o_hist); d_sums = (uint32_t*)(blk + o_sums);
-        d_kept = (uint32_t*)(blk + o_kept);
-        d_prefix = (uint64_t*)(blk + o_prefix);
-        d_tile_docs = (uint2*)(blk + o_tdocs);
-    }
-    chk(hipEventCreate(&ev0));
-    chk(hipEventCreate(&ev1));
-    uint2* d_final = nullptr;
-    if (e == hipSuccess) {
-        if (!dev_pairs) chk(hipMemcpyAsync(d_pairs, pairs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 8, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_tile_docs, tile_docs.data(), tile_docs.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_df, 0, nt1 * 4, st));
-        chk(hipMemsetAsync(d_first, 0xFF, nt1 * 4, st));
-        chk(hipEventRecord(ev0, st));
+    const size_t o_pairs = blk.reserve(dev_pairs ? 1 : (size_t)n * 8), o_v0 = blk.reserve((size_t)n * 8), o_v1 = blk.reserve(passes > 1 ? (size_t)n * 8 : 1);
+    const size_t o_k0 = blk.reserve((size_t)n * 4), o_k1 = blk.reserve(passes > 1 ? (size_t)n * 4 : 1);
+    const size_t o_df = blk.reserve(nt1 * 4), o_first = blk.reserve(nt1 * 4), o_hist = blk.reserve(m_max * 4), o_sums = blk.reserve((size_t)scan_blocks_max * 4),
+                 o_kept = blk.reserve(4), o_prefix = blk.reserve(prefix.size() * 8), o_tdocs = blk.reserve((size_t)n_tiles * 8);
+    blk.alloc(2);
+    if (blk.ok()) {
+        uint2* d_pairs = dev_pairs ? const_cast<uint2*>(dev_pairs) : blk.at<uint2>(o_pairs);
+        uint2* d_vals[2] = {blk.at<uint2>(o_v0), blk.at<uint2>(o_v1)};
+        uint32_t* d_keys[2] = {blk.at<uint32_t>(o_k0), blk.at<uint32_t>(o_k1)};
+        uint32_t *d_df = blk.at<uint32_t>(o_df), *d_first = blk.at<uint32_t>(o_first), *d_hist = blk.at<uint32_t>(o_hist), *d_sums = blk.at<uint32_t>(o_sums),
+                 *d_kept = blk.at<uint32_t>(o_kept);
+        const uint64_t* d_prefix = blk.at<uint64_t>(o_prefix);
+        const uint2* d_tile_docs = blk.at<uint2>(o_tdocs);
+        if (!dev_pairs) blk.upload(o_pairs, pairs, (size_t)n * 8);
+        blk.upload(o_prefix, prefix.data(), prefix.size() * 8);
+        blk.upload(o_tdocs, tile_docs.data(), tile_docs.size() * 4);
+        blk.zero(o_df, nt1 * 4);
+        blk.chk(hipMemsetAsync(d_first, 0xFF, nt1 * 4, st));
+        blk.record(0);
         // pass p reads (p == 0: the pairs; else keys / vals buffer `cur`) and writes buffer `nxt`.  The number of items that
         // survive the first pass (the kept pairs) stays on the device: the first scan leaves it in d_kept, later kernels read it.
         int cur = -1;
@@ -1772,39 +1838,35 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
             shift += (uint32_t)pbits[p];
             cur = nxt;
         }
-        d_final = d_vals[cur];
+        const uint2* d_final = d_vals[cur];
         // df from the sorted keys: a run's first pair records where it starts, its last pair where it ends (d_df holds the ends)
         if (n_terms) hipLaunchKernelGGL(k_iv_runs, dim3((n + 1023) / 1024), dim3(256), 0, st, d_keys[cur], n, n_terms, d_first, d_df, d_kept);
-        chk(hipEventRecord(ev1, st));
-        chk(hipGetLastError());
+        blk.record(1);
+        blk.launched();
         std::vector<uint32_t> h_first(n_terms);
-        if (n_terms) chk(hipMemcpyAsync(df_out, d_df, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
-        if (n_terms) chk(hipMemcpyAsync(h_first.data(), d_first, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
-        chk(hipStreamSynchronize(st));
-        if (e == hipSuccess) {
+        if (n_terms) blk.fetch(df_out, o_df, (size_t)n_terms * 4);
+        if (n_terms) blk.fetch(h_first.data(), o_first, (size_t)n_terms * 4);
+        blk.sync();
+        if (blk.ok()) {
             uint64_t kept = 0;
             for (uint32_t t = 0; t < n_terms; t++) df_out[t] = (h_first[t] == 0xFFFFFFFFu) ? 0u : df_out[t] - h_first[t] + 1u;
             for (uint32_t t = 0; t < n_terms; t++) kept += df_out[t];
             *kept_out = kept;   // the dropped pairs left the sort in the first pass
-            if (kept && postings_out) chk(hipMemcpy(postings_out, d_final, (size_t)kept * 8, hipMemcpyDeviceToHost));
+            if (kept && postings_out) blk.chk(hipMemcpy(postings_out, d_final, (size_t)kept * 8, hipMemcpyDeviceToHost));
             if (adopt) {   // the lists stay on the device: they ARE the segment's posting stream
-                if (kept) chk(hipMemcpyAsync(adopt->d_postings, d_final, (size_t)kept * 8, hipMemcpyDeviceToDevice, st));
+                if (kept) blk.chk(hipMemcpyAsync(adopt->d_postings, d_final, (size_t)kept * 8, hipMemcpyDeviceToDevice, st));
                 if (kept != adopt->n_postings) {   // dropped pairs: the stream is shorter than announced; move the padding
-                    chk(hipMemsetAsync((char*)adopt->d_postings + kept * 8, 0xFF, kPadPostings * 8, st));
-                    chk(hipMemsetAsync((char*)adopt->d_pnorm + kept * 4, 0, kPadPostings * 4, st));
+                    blk.chk(hipMemsetAsync((char*)adopt->d_postings + kept * 8, 0xFF, kPadPostings * 8, st));
+                    blk.chk(hipMemsetAsync((char*)adopt->d_pnorm + kept * 4, 0, kPadPostings * 4, st));
                 }
-                chk(hipStreamSynchronize(st));
-                if (e == hipSuccess) { adopt->n_postings = kept; adopt->filled = kept * 8; }
+                blk.sync();
+                if (blk.ok()) { adopt->n_postings = kept; adopt->filled = kept * 8; }
             }
             float ms = 0.0f;
-            if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && device_ms_out) *device_ms_out = ms;
+            if (blk.elapsed_ms(0, 1, &ms) && device_ms_out) *device_ms_out = ms;
         }
     }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }   // nothing in flight uses the block any more
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_invert_forward: %s", hipGetErrorString(e));
-    return NS_OK;
+    return blk.finish("ns_invert_forward");
 }
 
 extern "C" int ns_invert_forward(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_docs, const uint32_t* pairs,
@@ -1990,6 +2052,14 @@ extern "C" int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, 
     return NS_OK;
 }
 
+// The eight counters of ns_forward_build and of the merge, once everything launched so far is done.  Both reserve them
+// first in their first block (o_cnt == 0 in block 0).
+static void read_counts(CallBlock& blk, uint32_t (&h_cnt)[8]) {
+    blk.launched();
+    if (blk.ok()) blk.chk(hipMemcpyAsync(h_cnt, blk.at<uint32_t>(0, 0), sizeof(h_cnt), hipMemcpyDeviceToHost, blk.st));
+    if (blk.ok()) blk.sync();
+}
+
 extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_bytes, const uint64_t* offsets, uint32_t n_docs, ns_forward** out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_forward_build: ctx is NULL");
     if (!out) return fail(ctx, NS_E_INVAL, "ns_forward_build: out is NULL");
@@ -2017,97 +2087,84 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
     // test knob (variants build only): narrow the hash so that every probe collides and the byte comparison decides
     if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) hash_mask = (1ull << b) - 1ull; }
 #endif
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    char *blkA = nullptr, *blkB = nullptr, *blkC = nullptr;
-    size_t bytesA = 0, bytesB = 0, bytesC = 0, off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    CallBlock blk(ctx);
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     enum { C_TOK = 0, C_TOKE = 1, C_KEPT = 2, C_LONG = 3, C_KD = 4, C_TERMS = 5, C_TBYTES = 6, C_PAIRS = 7 };
-    auto read_counts = [&]() {
-        chk(hipGetLastError());
-        if (e == hipSuccess) chk(hipMemcpyAsync(h_cnt, blkA, sizeof(h_cnt), hipMemcpyDeviceToHost, st));   // the counters open block A
-        if (e == hipSuccess) chk(hipStreamSynchronize(st));
-    };
     const uint32_t nd1 = n_docs + 1, n_tiles = (n + kIgTile - 1) / kIgTile;
     const uint32_t g_docs = (n_docs + 255) / 256;
     std::vector<uint32_t> offs32(nd1);
     for (uint32_t d = 0; d <= n_docs; d++) offs32[d] = (uint32_t)offsets[d];
 
     // ---- block A: what the text and the documents size ----
-    off = 0;
-    const size_t o_cnt = place(sizeof(h_cnt)), o_text = place((size_t)n + 16), o_bits = place(((size_t)(n >> 5) + 2) * 4), o_offs = place((size_t)nd1 * 4);
-    const size_t o_ts = place((size_t)n_tiles * 4), o_te = place((size_t)n_tiles * 4), o_sumsA = place(((size_t)std::max(n_tiles, n_docs) / 1024 + 2) * 4);
-    const size_t o_long = place(((size_t)n / kIgLong + 1) * 4);
-    const size_t o_df = place((size_t)n_docs * 4), o_dl = place((size_t)n_docs * 4), o_pf = place((size_t)n_docs * 4), o_pl = place((size_t)n_docs * 4), o_dx = place((size_t)n_docs * 4);
-    bytesA = off;
-    chk(pool_alloc(ctx, (void**)&blkA, bytesA));
-    chk(hipEventCreate(&ev0));
-    chk(hipEventCreate(&ev1));
+    const size_t o_cnt = blk.reserve(sizeof(h_cnt)), o_text = blk.reserve((size_t)n + 16), o_bits = blk.reserve(((size_t)(n >> 5) + 2) * 4), o_offs = blk.reserve((size_t)nd1 * 4);
+    const size_t o_ts = blk.reserve((size_t)n_tiles * 4), o_te = blk.reserve((size_t)n_tiles * 4), o_sumsA = blk.reserve(((size_t)std::max(n_tiles, n_docs) / 1024 + 2) * 4);
+    const size_t o_long = blk.reserve(((size_t)n / kIgLong + 1) * 4);
+    const size_t o_df = blk.reserve((size_t)n_docs * 4), o_dl = blk.reserve((size_t)n_docs * 4), o_pf = blk.reserve((size_t)n_docs * 4), o_pl = blk.reserve((size_t)n_docs * 4),
+                 o_dx = blk.reserve((size_t)n_docs * 4);
+    blk.alloc(2);
     uint32_t n_tok = 0, n_kept = 0;
-    if (e == hipSuccess) {
-        uint32_t* d_cntv = (uint32_t*)(blkA + o_cnt);
-        uint8_t* d_text = (uint8_t*)(blkA + o_text);
-        uint32_t *d_bits = (uint32_t*)(blkA + o_bits), *d_offs = (uint32_t*)(blkA + o_offs), *d_ts = (uint32_t*)(blkA + o_ts), *d_te = (uint32_t*)(blkA + o_te);
-        uint32_t *d_sumsA = (uint32_t*)(blkA + o_sumsA), *d_long = (uint32_t*)(blkA + o_long);
-        uint32_t *d_dfirst = (uint32_t*)(blkA + o_df), *d_dlast = (uint32_t*)(blkA + o_dl), *d_pfirst = (uint32_t*)(blkA + o_pf), *d_plast = (uint32_t*)(blkA + o_pl), *d_didx = (uint32_t*)(blkA + o_dx);
-        chk(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_offs, offs32.data(), (size_t)nd1 * 4, hipMemcpyHostToDevice, st));
-        chk(hipEventRecord(ev0, st));
-        chk(hipMemsetAsync(d_cntv, 0, sizeof(h_cnt), st));
-        chk(hipMemsetAsync(d_bits, 0, ((size_t)(n >> 5) + 2) * 4, st));
-        chk(hipMemsetAsync(d_dfirst, 0xFF, (size_t)n_docs * 4, st));
-        chk(hipMemsetAsync(d_pfirst, 0xFF, (size_t)n_docs * 4, st));
+    if (blk.ok()) {
+        uint32_t* d_cntv = blk.at<uint32_t>(o_cnt);
+        uint8_t* d_text = blk.at<uint8_t>(o_text);
+        uint32_t *d_bits = blk.at<uint32_t>(o_bits), *d_offs = blk.at<uint32_t>(o_offs), *d_ts = blk.at<uint32_t>(o_ts), *d_te = blk.at<uint32_t>(o_te);
+        uint32_t *d_sumsA = blk.at<uint32_t>(o_sumsA), *d_long = blk.at<uint32_t>(o_long);
+        uint32_t *d_dfirst = blk.at<uint32_t>(o_df), *d_dlast = blk.at<uint32_t>(o_dl), *d_pfirst = blk.at<uint32_t>(o_pf), *d_plast = blk.at<uint32_t>(o_pl),
+                 *d_didx = blk.at<uint32_t>(o_dx);
+        blk.upload(o_text, text, n);
+        blk.upload(o_offs, offs32.data(), (size_t)nd1 * 4);
+        blk.record(0);
+        blk.zero(o_cnt, sizeof(h_cnt));
+        blk.zero(o_bits, ((size_t)(n >> 5) + 2) * 4);
+        blk.chk(hipMemsetAsync(d_dfirst, 0xFF, (size_t)n_docs * 4, st));
+        blk.chk(hipMemsetAsync(d_pfirst, 0xFF, (size_t)n_docs * 4, st));
         hipLaunchKernelGGL(k_ig_docmark, dim3(g_docs), dim3(256), 0, st, d_offs, n_docs, n, d_bits);
         hipLaunchKernelGGL((k_ig_text<false>), dim3(n_tiles), dim3(256), 0, st, d_text, n, d_bits, d_ts, d_te, (uint32_t*)nullptr, (uint32_t*)nullptr);
         ig_scan(st, d_ts, n_tiles, d_sumsA, d_cntv + C_TOK);
         ig_scan(st, d_te, n_tiles, d_sumsA, d_cntv + C_TOKE);
-        read_counts();
+        read_counts(blk, h_cnt);
         n_tok = h_cnt[C_TOK];
-        if (e == hipSuccess && h_cnt[C_TOKE] != n_tok) { e = hipErrorUnknown; }   // every token has one start and one end
+        if (blk.ok() && h_cnt[C_TOKE] != n_tok) blk.chk(hipErrorUnknown);   // every token has one start and one end
         f->info.n_tokens = n_tok;
 
         // ---- block B: what the tokens size ----
         uint32_t *d_tstart = nullptr, *d_tend = nullptr, *d_kidx = nullptr, *d_sums = nullptr;
-        if (e == hipSuccess && n_tok) {
-            off = 0;
-            const size_t o_a = place((size_t)n_tok * 4), o_b = place((size_t)n_tok * 4), o_c = place((size_t)n_tok * 4);
+        if (blk.ok() && n_tok) {
+            blk.open();
+            const size_t o_a = blk.reserve((size_t)n_tok * 4), o_b = blk.reserve((size_t)n_tok * 4), o_c = blk.reserve((size_t)n_tok * 4);
             const size_t scan_max = std::max<size_t>((size_t)n_tok + 1, (size_t)2048 * ((n_tok + kIvTile - 1) / kIvTile));
-            const size_t o_s = place((scan_max / 1024 + 2) * 4);
-            bytesB = off;
-            chk(pool_alloc(ctx, (void**)&blkB, bytesB));
-            if (e == hipSuccess) {
-                d_tstart = (uint32_t*)(blkB + o_a); d_tend = (uint32_t*)(blkB + o_b); d_kidx = (uint32_t*)(blkB + o_c); d_sums = (uint32_t*)(blkB + o_s);
+            const size_t o_s = blk.reserve((scan_max / 1024 + 2) * 4);
+            blk.alloc(0);
+            if (blk.ok()) {
+                d_tstart = blk.at<uint32_t>(o_a); d_tend = blk.at<uint32_t>(o_b); d_kidx = blk.at<uint32_t>(o_c); d_sums = blk.at<uint32_t>(o_s);
                 hipLaunchKernelGGL((k_ig_text<true>), dim3(n_tiles), dim3(256), 0, st, d_text, n, d_bits, d_ts, d_te, d_tstart, d_tend);
                 hipLaunchKernelGGL(k_ig_keep, dim3((n_tok + 255) / 256), dim3(256), 0, st, d_text, d_tstart, d_tend, n_tok, d_kidx);
                 ig_scan(st, d_kidx, n_tok, d_sums, d_cntv + C_KEPT);
-                read_counts();
+                read_counts(blk, h_cnt);
                 n_kept = h_cnt[C_KEPT];
                 f->info.kept_tokens = n_kept;
             }
         }
         // ---- block C: what the kept tokens size ----
-        if (e == hipSuccess && n_kept) {
+        if (blk.ok() && n_kept) {
             const uint32_t K = n_kept, gK = (K + 255) / 256, kt = (K + kIvTile - 1) / kIvTile;
             uint64_t cap = 1024;
             while (cap < 2ull * K) cap <<= 1;                      // K <= n / 2 < 2^31: cap <= 2^32, its mask fits 32 bits
-            off = 0;
-            const size_t o_ks = place((size_t)K * 4), o_kl = place((size_t)K * 4), o_kd = place((size_t)K * 4), o_kh = place((size_t)K * 8);
-            const size_t o_sl = place((size_t)K * 4), o_kr = place((size_t)K * 4), o_fi = place((size_t)K * 4), o_tsrc = place((size_t)K * 4);
-            const size_t o_tab = place((size_t)cap * 4), o_k0 = place((size_t)K * 4), o_k1 = place((size_t)K * 4), o_v0 = place((size_t)K * 8), o_v1 = place((size_t)K * 8);
-            const size_t o_hist = place((size_t)2048 * kt * 4);
-            bytesC = off;
-            chk(pool_alloc(ctx, (void**)&blkC, bytesC));
-            if (e == hipSuccess) {
-                uint32_t *d_kstart = (uint32_t*)(blkC + o_ks), *d_klen = (uint32_t*)(blkC + o_kl), *d_kdoc = (uint32_t*)(blkC + o_kd);
-                uint64_t* d_khash = (uint64_t*)(blkC + o_kh);
-                uint32_t *d_kslot = (uint32_t*)(blkC + o_sl), *d_krep = (uint32_t*)(blkC + o_kr), *d_fid = (uint32_t*)(blkC + o_fi), *d_tsrc = (uint32_t*)(blkC + o_tsrc);
-                uint32_t* d_table = (uint32_t*)(blkC + o_tab);
-                uint32_t* d_keys[2] = {(uint32_t*)(blkC + o_k0), (uint32_t*)(blkC + o_k1)};
-                uint2* d_vals[2] = {(uint2*)(blkC + o_v0), (uint2*)(blkC + o_v1)};
-                uint32_t* d_hist = (uint32_t*)(blkC + o_hist);
-                chk(hipMemsetAsync(d_table, 0xFF, (size_t)cap * 4, st));
+            blk.open();
+            const size_t o_ks = blk.reserve((size_t)K * 4), o_kl = blk.reserve((size_t)K * 4), o_kd = blk.reserve((size_t)K * 4), o_kh = blk.reserve((size_t)K * 8);
+            const size_t o_sl = blk.reserve((size_t)K * 4), o_kr = blk.reserve((size_t)K * 4), o_fi = blk.reserve((size_t)K * 4), o_tsrc = blk.reserve((size_t)K * 4);
+            const size_t o_tab = blk.reserve((size_t)cap * 4), o_k0 = blk.reserve((size_t)K * 4), o_k1 = blk.reserve((size_t)K * 4), o_v0 = blk.reserve((size_t)K * 8),
+                         o_v1 = blk.reserve((size_t)K * 8);
+            const size_t o_hist = blk.reserve((size_t)2048 * kt * 4);
+            blk.alloc(0);
+            if (blk.ok()) {
+                uint32_t *d_kstart = blk.at<uint32_t>(o_ks), *d_klen = blk.at<uint32_t>(o_kl), *d_kdoc = blk.at<uint32_t>(o_kd);
+                uint64_t* d_khash = blk.at<uint64_t>(o_kh);
+                uint32_t *d_kslot = blk.at<uint32_t>(o_sl), *d_krep = blk.at<uint32_t>(o_kr), *d_fid = blk.at<uint32_t>(o_fi), *d_tsrc = blk.at<uint32_t>(o_tsrc);
+                uint32_t* d_table = blk.at<uint32_t>(o_tab);
+                uint32_t* d_keys[2] = {blk.at<uint32_t>(o_k0), blk.at<uint32_t>(o_k1)};
+                uint2* d_vals[2] = {blk.at<uint2>(o_v0), blk.at<uint2>(o_v1)};
+                uint32_t* d_hist = blk.at<uint32_t>(o_hist);
+                blk.chk(hipMemsetAsync(d_table, 0xFF, (size_t)cap * 4, st));
                 hipLaunchKernelGGL(k_ig_kept, dim3((n_tok + 255) / 256), dim3(256), 0, st, d_text, d_tstart, d_tend, n_tok, d_kidx, d_cntv + C_KEPT, d_offs, n_docs,
                                    hash_mask, d_kstart, d_klen, d_kdoc, d_khash, d_long, d_cntv + C_LONG);
                 hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
@@ -2118,32 +2175,32 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
                 hipLaunchKernelGGL(k_ig_insert, dim3(gK), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, K, d_table, (uint32_t)(cap - 1), d_kslot);
                 hipLaunchKernelGGL(k_ig_first, dim3(gK), dim3(256), 0, st, d_table, d_kslot, K, d_krep, d_fid);
                 ig_scan(st, d_fid, K, d_sums, d_cntv + C_TERMS);
-                read_counts();
+                read_counts(blk, h_cnt);
                 const uint32_t n_terms = h_cnt[C_TERMS], n_kd = h_cnt[C_KD];
                 f->info.n_terms = n_terms; f->info.kept_docs = n_kd;
-                if (e == hipSuccess) {
-                    chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
-                    chk(hipMalloc((void**)&f->d_map, (size_t)n_kd * 4));
-                    chk(hipMalloc((void**)&f->d_len, (size_t)n_kd * 4));
-                    chk(hipMalloc((void**)&f->d_cnt, (size_t)n_kd * 4));
+                if (blk.ok()) {
+                    blk.chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+                    blk.chk(hipMalloc((void**)&f->d_map, (size_t)n_kd * 4));
+                    blk.chk(hipMalloc((void**)&f->d_len, (size_t)n_kd * 4));
+                    blk.chk(hipMalloc((void**)&f->d_cnt, (size_t)n_kd * 4));
                 }
                 int cur = 0;
-                if (e == hipSuccess) {
-                    chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
+                if (blk.ok()) {
+                    blk.chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
                     hipLaunchKernelGGL(k_ig_termid, dim3(gK), dim3(256), 0, st, d_krep, d_fid, d_kdoc, d_kstart, d_klen, K, d_keys[0], d_vals[0], f->d_toff, d_tsrc);
                     ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
                     ig_sort(st, K, n_terms, d_keys, d_vals, &cur, d_hist, d_sums);
                     hipLaunchKernelGGL(k_ig_runflag, dim3(gK), dim3(256), 0, st, d_vals[cur], K, d_kslot);
                     ig_scan(st, d_kslot, K, d_sums, d_cntv + C_PAIRS);
-                    read_counts();
+                    read_counts(blk, h_cnt);
                 }
                 const uint32_t n_pairs = h_cnt[C_PAIRS], tbytes = h_cnt[C_TBYTES];
                 f->info.n_pairs = n_pairs; f->info.term_bytes = tbytes;
-                if (e == hipSuccess) {
-                    chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
-                    chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
+                if (blk.ok()) {
+                    blk.chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
+                    blk.chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
                 }
-                if (e == hipSuccess) {
+                if (blk.ok()) {
                     hipLaunchKernelGGL(k_ig_term_bytes, dim3((n_terms + 3) / 4), dim3(256), 0, st, d_text, d_tsrc, f->d_toff, n_terms, f->d_terms);
                     // the runs, (term, doc)-ordered: keys = doc, values = {term, tf}, into the buffer the first sort left free
                     const int in = cur ^ 1;
@@ -2154,28 +2211,23 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
                     ig_sort(st, n_pairs, n_docs, d_keys, d_vals, &cur, d_hist, d_sums);
                     hipLaunchKernelGGL(k_iv_runs, dim3((n_pairs + 1023) / 1024), dim3(256), 0, st, d_keys[cur], n_pairs, n_docs, d_pfirst, d_plast, (const uint32_t*)nullptr);
                     hipLaunchKernelGGL(k_ig_docemit, dim3(g_docs), dim3(256), 0, st, d_dfirst, d_dlast, d_pfirst, d_plast, d_didx, n_docs, f->d_map, f->d_len, f->d_cnt);
-                    chk(hipMemcpyAsync(f->d_pairs, d_vals[cur], (size_t)n_pairs * 8, hipMemcpyDeviceToDevice, st));
-                    chk(hipGetLastError());
+                    blk.chk(hipMemcpyAsync(f->d_pairs, d_vals[cur], (size_t)n_pairs * 8, hipMemcpyDeviceToDevice, st));
+                    blk.launched();
                 }
             }
         }
-        if (e == hipSuccess) chk(hipEventRecord(ev1, st));
-        if (e == hipSuccess) chk(hipStreamSynchronize(st));
+        if (blk.ok()) blk.record(1);
+        if (blk.ok()) blk.sync();
         float ms = 0.0f;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) f->info.device_ms = ms;
+        if (blk.elapsed_ms(0, 1, &ms)) f->info.device_ms = ms;
     }
-    (void)hipStreamSynchronize(st);   // nothing in flight uses the blocks any more
-    if (blkC) pool_free(ctx, blkC, bytesC);
-    if (blkB) pool_free(ctx, blkB, bytesB);
-    if (blkA) pool_free(ctx, blkA, bytesA);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    f->info.device_bytes = (uint64_t)bytesA + bytesB + bytesC + ((uint64_t)f->info.n_terms + 1) * 4 + (uint64_t)f->info.kept_docs * 12 + f->info.n_pairs * 8 + f->info.term_bytes;
-    if (e != hipSuccess) {
+    const int rc = blk.finish("ns_forward_build", blk.e == hipErrorUnknown ? "token starts and ends disagree (internal error)" : nullptr);
+    f->info.device_bytes = (uint64_t)blk.held_bytes() + ((uint64_t)f->info.n_terms + 1) * 4 + (uint64_t)f->info.kept_docs * 12 + f->info.n_pairs * 8 + f->info.term_bytes;
+    if (rc != NS_OK) {
         forward_free_device(f);
         delete f;
         (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_forward_build: %s", e == hipErrorUnknown ? "token starts and ends disagree (internal error)" : hipGetErrorString(e));
+        return rc;
     }
     return publish();
 }
@@ -2343,12 +2395,7 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
     lists.insert(lists.end(), l_big.begin(), l_big.end());
     lists.insert(lists.end(), big_prefix.begin(), big_prefix.end());
 
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    char *blkA = nullptr, *blkB = nullptr, *blkF = nullptr;
-    size_t bytesA = 0, bytesB = 0, bytesF = 0, off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    CallBlock blk(ctx);
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     enum { C_TERMS = 0, C_TBYTES = 1, C_LONG = 2, C_LIVE = 3, C_DUP = 4, C_BAD = 5 };   // C_DUP / C_BAD: the smallest refused source, ~0 for none; C_LIVE: the terms that stay (filtered)
     uint64_t cap = 1024;
@@ -2358,46 +2405,45 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
 
     // ---- block A: the dictionary stage, sized by the source terms; the per-source bases, the document prefix, the lists ----
     const size_t T1 = std::max<uint32_t>(T, 1);
-    const size_t o_cnt = place(sizeof(h_cnt)), o_text = place((size_t)n + 16), o_ks = place(T1 * 4), o_kl = place(T1 * 4), o_src = place(T1 * 4), o_kh = place(T1 * 8);
-    const size_t o_sl = place(T1 * 4), o_kr = place(T1 * 4), o_fi = place(T1 * 4), o_tsrc = place(T1 * 4), o_map = place(T1 * 4), o_vals = place(T1 * 8);
-    const size_t o_tab = place((size_t)cap * 4), o_dtab = place((size_t)cap * 8), o_long = place(((size_t)n / kIgLong + 1) * 4), o_sums = place((scan_max / 1024 + 2) * 4);
-    const size_t o_tb = place(term_base.size() * 4), o_pb = place(pair_base.size() * 4), o_prefix = place(prefix.size() * 4), o_lists = place(lists.size() * 4);
-    bytesA = off;
-    chk(pool_alloc(ctx, (void**)&blkA, bytesA));
+    const size_t o_cnt = blk.reserve(sizeof(h_cnt)), o_text = blk.reserve((size_t)n + 16), o_ks = blk.reserve(T1 * 4), o_kl = blk.reserve(T1 * 4), o_src = blk.reserve(T1 * 4),
+                 o_kh = blk.reserve(T1 * 8);
+    const size_t o_sl = blk.reserve(T1 * 4), o_kr = blk.reserve(T1 * 4), o_fi = blk.reserve(T1 * 4), o_tsrc = blk.reserve(T1 * 4), o_map = blk.reserve(T1 * 4),
+                 o_vals = blk.reserve(T1 * 8);
+    const size_t o_tab = blk.reserve((size_t)cap * 4), o_dtab = blk.reserve((size_t)cap * 8), o_long = blk.reserve(((size_t)n / kIgLong + 1) * 4),
+                 o_sums = blk.reserve((scan_max / 1024 + 2) * 4);
+    const size_t o_tb = blk.reserve(term_base.size() * 4), o_pb = blk.reserve(pair_base.size() * 4), o_prefix = blk.reserve(prefix.size() * 4),
+                 o_lists = blk.reserve(lists.size() * 4);
+    const size_t A = blk.alloc(2);
     // ---- block F (filtered only): the pairs as uploaded, the live flags and their scan, the source terms' (start, length),
     // the surviving terms' per-source base, the (source, old id) -> new id map, the surviving documents' places in the upload ----
-    off = 0;
-    const size_t o_raw = place((size_t)raw_pairs * 8), o_live = place(((size_t)T + 1) * 4), o_rank = place(((size_t)T + 1) * 4), o_ks0 = place(T1 * 4), o_kl0 = place(T1 * 4);
-    const size_t o_tbl = place(term_base.size() * 4), o_omap = place(T1 * 4), o_spos = place((size_t)n_docs * 4);
-    if (filtered) {
-        bytesF = off;
-        chk(pool_alloc(ctx, (void**)&blkF, bytesF));
-    }
-    chk(hipEventCreate(&ev0));
-    chk(hipEventCreate(&ev1));
-    chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
-    chk(hipMalloc((void**)&f->d_map, (size_t)n_docs * 4));
-    chk(hipMalloc((void**)&f->d_len, (size_t)n_docs * 4));
-    chk(hipMalloc((void**)&f->d_cnt, (size_t)n_docs * 4));
+    blk.open();
+    const size_t o_raw = blk.reserve((size_t)raw_pairs * 8), o_live = blk.reserve(((size_t)T + 1) * 4), o_rank = blk.reserve(((size_t)T + 1) * 4), o_ks0 = blk.reserve(T1 * 4),
+                 o_kl0 = blk.reserve(T1 * 4);
+    const size_t o_tbl = blk.reserve(term_base.size() * 4), o_omap = blk.reserve(T1 * 4), o_spos = blk.reserve((size_t)n_docs * 4);
+    const size_t F = filtered ? blk.alloc(0) : A;
+    blk.chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
+    blk.chk(hipMalloc((void**)&f->d_map, (size_t)n_docs * 4));
+    blk.chk(hipMalloc((void**)&f->d_len, (size_t)n_docs * 4));
+    blk.chk(hipMalloc((void**)&f->d_cnt, (size_t)n_docs * 4));
     uint32_t n_terms = 0, tbytes = 0;
     int refused_src = -1;
     const char* refused_why = "";
-    if (e == hipSuccess) {
-        uint32_t* d_cntv = (uint32_t*)(blkA + o_cnt);
-        uint8_t* d_text = (uint8_t*)(blkA + o_text);
-        uint32_t *d_kstart = (uint32_t*)(blkA + o_ks), *d_klen = (uint32_t*)(blkA + o_kl), *d_ksrc = (uint32_t*)(blkA + o_src);
-        uint64_t* d_khash = (uint64_t*)(blkA + o_kh);
-        uint32_t *d_kslot = (uint32_t*)(blkA + o_sl), *d_krep = (uint32_t*)(blkA + o_kr), *d_fid = (uint32_t*)(blkA + o_fi), *d_tsrc = (uint32_t*)(blkA + o_tsrc);
-        uint32_t* d_newid = (uint32_t*)(blkA + o_map);
-        uint2* d_tvals = (uint2*)(blkA + o_vals);                      // k_ig_termid's {source, new id} per source term: written, not read
-        uint32_t* d_table = (uint32_t*)(blkA + o_tab);
-        unsigned long long* d_dtab = (unsigned long long*)(blkA + o_dtab);
-        uint32_t *d_long = (uint32_t*)(blkA + o_long), *d_sums = (uint32_t*)(blkA + o_sums);
-        uint32_t *d_tb = (uint32_t*)(blkA + o_tb), *d_pb = (uint32_t*)(blkA + o_pb), *d_prefix = (uint32_t*)(blkA + o_prefix), *d_lists = (uint32_t*)(blkA + o_lists);
-        uint2* d_raw = filtered ? (uint2*)(blkF + o_raw) : nullptr;
-        uint32_t *d_live = filtered ? (uint32_t*)(blkF + o_live) : nullptr, *d_rank = filtered ? (uint32_t*)(blkF + o_rank) : nullptr;
-        uint32_t *d_ks0 = filtered ? (uint32_t*)(blkF + o_ks0) : d_kstart, *d_kl0 = filtered ? (uint32_t*)(blkF + o_kl0) : d_klen;   // where the host's (start, length) go
-        uint32_t *d_tbl = filtered ? (uint32_t*)(blkF + o_tbl) : d_tb, *d_omap = filtered ? (uint32_t*)(blkF + o_omap) : d_newid, *d_spos = filtered ? (uint32_t*)(blkF + o_spos) : nullptr;
+    if (blk.ok()) {
+        uint32_t* d_cntv = blk.at<uint32_t>(o_cnt, A);
+        uint8_t* d_text = blk.at<uint8_t>(o_text, A);
+        uint32_t *d_kstart = blk.at<uint32_t>(o_ks, A), *d_klen = blk.at<uint32_t>(o_kl, A), *d_ksrc = blk.at<uint32_t>(o_src, A);
+        uint64_t* d_khash = blk.at<uint64_t>(o_kh, A);
+        uint32_t *d_kslot = blk.at<uint32_t>(o_sl, A), *d_krep = blk.at<uint32_t>(o_kr, A), *d_fid = blk.at<uint32_t>(o_fi, A), *d_tsrc = blk.at<uint32_t>(o_tsrc, A);
+        uint32_t* d_newid = blk.at<uint32_t>(o_map, A);
+        uint2* d_tvals = blk.at<uint2>(o_vals, A);                     // k_ig_termid's {source, new id} per source term: written, not read
+        uint32_t* d_table = blk.at<uint32_t>(o_tab, A);
+        unsigned long long* d_dtab = blk.at<unsigned long long>(o_dtab, A);
+        uint32_t *d_long = blk.at<uint32_t>(o_long, A), *d_sums = blk.at<uint32_t>(o_sums, A);
+        uint32_t *d_tb = blk.at<uint32_t>(o_tb, A), *d_pb = blk.at<uint32_t>(o_pb, A), *d_prefix = blk.at<uint32_t>(o_prefix, A), *d_lists = blk.at<uint32_t>(o_lists, A);
+        uint2* d_raw = filtered ? blk.at<uint2>(o_raw, F) : nullptr;
+        uint32_t *d_live = filtered ? blk.at<uint32_t>(o_live, F) : nullptr, *d_rank = filtered ? blk.at<uint32_t>(o_rank, F) : nullptr;
+        uint32_t *d_ks0 = filtered ? blk.at<uint32_t>(o_ks0, F) : d_kstart, *d_kl0 = filtered ? blk.at<uint32_t>(o_kl0, F) : d_klen;   // where the host's (start, length) go
+        uint32_t *d_tbl = filtered ? blk.at<uint32_t>(o_tbl, F) : d_tb, *d_omap = filtered ? blk.at<uint32_t>(o_omap, F) : d_newid, *d_spos = filtered ? blk.at<uint32_t>(o_spos, F) : nullptr;
         const uint32_t *d_lwave = d_lists, *d_llds = d_lists + n_wave, *d_lbig = d_lists + n_wave + n_lds, *d_bigpre = d_lists + n_wave + n_lds + n_bigdocs;
         // uploads: term bytes, pairs, counts and doc_len source by source; the host-made arrays
         {
@@ -2405,46 +2451,41 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
             for (uint32_t s = 0; s < n_src; s++) {
                 const ns_forward_src& S = src[s];
                 const uint32_t nb = S.n_terms ? (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]) : 0u;
-                if (nb) chk(hipMemcpyAsync(d_text + at, S.term_bytes + S.term_offsets[0], nb, hipMemcpyHostToDevice, st));
+                if (nb) blk.chk(hipMemcpyAsync(d_text + at, S.term_bytes + S.term_offsets[0], nb, hipMemcpyHostToDevice, st));
                 if (filtered) {   // (a source without a surviving pair is not uploaded: nothing reads it)
-                    if (pair_base[s + 1] != pair_base[s]) chk(hipMemcpyAsync(d_raw + raw_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
-                } else if (S.n_pairs) chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                    if (pair_base[s + 1] != pair_base[s]) blk.chk(hipMemcpyAsync(d_raw + raw_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                } else if (S.n_pairs) blk.chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
                 if (S.n_docs && !filtered) {
-                    chk(hipMemcpyAsync(f->d_len + d, S.doc_len, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
-                    chk(hipMemcpyAsync(f->d_cnt + d, S.counts, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
+                    blk.chk(hipMemcpyAsync(f->d_len + d, S.doc_len, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
+                    blk.chk(hipMemcpyAsync(f->d_cnt + d, S.counts, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
                 }
                 at += nb; d += S.n_docs;
             }
         }
         std::vector<uint32_t> iota(n_docs);
         for (uint32_t d = 0; d < n_docs; d++) iota[d] = d;
-        chk(hipMemcpyAsync(f->d_map, iota.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(f->d_map, iota.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
         if (T) {
-            chk(hipMemcpyAsync(d_ks0, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(d_kl0, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_ks0, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_kl0, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
         }
         if (filtered) {
-            chk(hipMemcpyAsync(f->d_len, kept_len.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(f->d_cnt, kept_cnt.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(d_spos, srcpos.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            chk(hipMemcpyAsync(d_live, live0.data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(f->d_len, kept_len.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(f->d_cnt, kept_cnt.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_spos, srcpos.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_live, live0.data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice, st));
         }
-        chk(hipMemcpyAsync(d_tb, term_base.data(), term_base.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_pb, pair_base.data(), pair_base.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipEventRecord(ev0, st));
+        blk.chk(hipMemcpyAsync(d_tb, term_base.data(), term_base.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_pb, pair_base.data(), pair_base.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
+        blk.record(0);
         h_cnt[C_DUP] = h_cnt[C_BAD] = 0xFFFFFFFFu;
-        chk(hipMemcpyAsync(d_cntv, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
-        auto read_counts = [&]() {
-            chk(hipGetLastError());
-            if (e == hipSuccess) chk(hipMemcpyAsync(h_cnt, d_cntv, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-            if (e == hipSuccess) chk(hipStreamSynchronize(st));
-        };
+        blk.chk(hipMemcpyAsync(d_cntv, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
         // ---- the filter (csrc/ns_delete.hip): afterwards Td "tokens" in d_kstart / d_klen with their bases in d_tbl, the
         // surviving pairs in f->d_pairs under the sources' OLD term ids ----
         uint32_t Td = T;                                               // the dictionary stage's tokens: the source terms that stay
-        if (e == hipSuccess && filtered) {
+        if (blk.ok() && filtered) {
             if (n_pairs) {
                 const uint32_t gK = (n_pairs + kCpKeepTile - 1) / kCpKeepTile;
 #ifdef NS_VARIANTS
@@ -2454,30 +2495,30 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
 #endif
                 hipLaunchKernelGGL((k_cp_keep_gather<true>), dim3(gK), dim3(256), 0, st, d_raw, d_prefix, d_spos, n_docs, n_pairs, d_pb, d_tb, n_src, f->d_pairs, d_live);
             }
-            chk(hipMemcpyAsync(d_rank, d_live, ((size_t)T + 1) * 4, hipMemcpyDeviceToDevice, st));
+            blk.chk(hipMemcpyAsync(d_rank, d_live, ((size_t)T + 1) * 4, hipMemcpyDeviceToDevice, st));
             ig_scan(st, d_rank, T + 1, d_sums, d_cntv + C_LIVE);       // (entry T is 0: the total is rank[T] as well)
             hipLaunchKernelGGL(k_cp_keep_terms, dim3((std::max(T, n_src + 1) + 255) / 256), dim3(256), 0, st, d_live, d_rank, T, d_ks0, d_kl0, d_tb, n_src, d_kstart, d_klen, d_tbl);
-            read_counts();
+            read_counts(blk, h_cnt);
             Td = h_cnt[C_LIVE];
         }
         uint64_t capd = 1024;                                          // == cap unless terms were dropped
         while (capd < 2ull * Td) capd <<= 1;
         const uint32_t gT = (Td + 255) / 256;
-        if (e == hipSuccess && Td) {
-            chk(hipMemsetAsync(d_table, 0xFF, (size_t)capd * 4, st));
-            chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)capd * 8, st));
+        if (blk.ok() && Td) {
+            blk.chk(hipMemsetAsync(d_table, 0xFF, (size_t)capd * 4, st));
+            blk.chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)capd * 8, st));
             hipLaunchKernelGGL(k_cp_hash, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, Td, d_tbl, n_src, hash_mask, d_ksrc, d_khash, d_long, d_cntv + C_LONG);
             hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
             hipLaunchKernelGGL(k_ig_insert, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, Td, d_table, (uint32_t)(capd - 1), d_kslot);
             hipLaunchKernelGGL(k_ig_first, dim3(gT), dim3(256), 0, st, d_table, d_kslot, Td, d_krep, d_fid);
             ig_scan(st, d_fid, Td, d_sums, d_cntv + C_TERMS);
-            read_counts();
+            read_counts(blk, h_cnt);
             n_terms = h_cnt[C_TERMS];
         }
         f->info.n_terms = n_terms;
-        if (e == hipSuccess) chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
-        if (e == hipSuccess) {
-            chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
+        if (blk.ok()) blk.chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+        if (blk.ok()) {
+            blk.chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
             if (Td) {
                 hipLaunchKernelGGL(k_ig_termid, dim3(gT), dim3(256), 0, st, d_krep, d_fid, d_ksrc, d_kstart, d_klen, Td, d_newid, d_tvals, f->d_toff, d_tsrc);
                 ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
@@ -2486,28 +2527,28 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
             // d_omap: the map over the sources' own term ids (filtered: through the ranks; otherwise d_newid itself)
             if (filtered && T) hipLaunchKernelGGL(k_cp_keep_map, dim3((T + 255) / 256), dim3(256), 0, st, d_live, d_rank, T, d_newid, d_omap);
             if (n_pairs) hipLaunchKernelGGL(k_cp_remap, dim3((n_pairs + 255) / 256), dim3(256), 0, st, f->d_pairs, n_pairs, d_pb, d_tb, n_src, d_omap, d_cntv + C_BAD);
-            read_counts();
+            read_counts(blk, h_cnt);
             tbytes = h_cnt[C_TBYTES];
             f->info.term_bytes = tbytes;
-            if (e == hipSuccess && h_cnt[C_DUP] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_DUP]; refused_why = "one byte string occurs twice in its term list"; }
-            else if (e == hipSuccess && h_cnt[C_BAD] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_BAD]; refused_why = "a pair's termId is not below the source's n_terms"; }
+            if (blk.ok() && h_cnt[C_DUP] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_DUP]; refused_why = "one byte string occurs twice in its term list"; }
+            else if (blk.ok() && h_cnt[C_BAD] != 0xFFFFFFFFu) { refused_src = (int)h_cnt[C_BAD]; refused_why = "a pair's termId is not below the source's n_terms"; }
         }
-        if (e == hipSuccess && refused_src < 0) chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
-        if (e == hipSuccess && refused_src < 0) {
+        if (blk.ok() && refused_src < 0) blk.chk(hipMalloc((void**)&f->d_terms, std::max<size_t>(tbytes, 1)));
+        if (blk.ok() && refused_src < 0) {
             if (n_terms) hipLaunchKernelGGL(k_ig_term_bytes, dim3((n_terms + 3) / 4), dim3(256), 0, st, d_text, d_tsrc, f->d_toff, n_terms, f->d_terms);
             // ---- the order inside each document ----
             if (n_wave) hipLaunchKernelGGL(k_cp_docsort_wave, dim3((n_wave + 3) / 4), dim3(256), 0, st, f->d_pairs, d_prefix, d_lwave, n_wave);
             if (n_lds) hipLaunchKernelGGL(k_cp_docsort_lds, dim3(n_lds), dim3(256), 0, st, f->d_pairs, d_prefix, d_llds);
             if (n_big) {
-                off = 0;
-                const size_t o_k0 = place((size_t)n_big * 4), o_k1 = place((size_t)n_big * 4), o_v0 = place((size_t)n_big * 8), o_v1 = place((size_t)n_big * 8);
-                const size_t o_hist = place((size_t)2048 * big_tiles * 4);
-                bytesB = off;
-                chk(pool_alloc(ctx, (void**)&blkB, bytesB));
-                if (e == hipSuccess) {
-                    uint32_t* d_keys[2] = {(uint32_t*)(blkB + o_k0), (uint32_t*)(blkB + o_k1)};
-                    uint2* d_vals[2] = {(uint2*)(blkB + o_v0), (uint2*)(blkB + o_v1)};
-                    uint32_t* d_hist = (uint32_t*)(blkB + o_hist);
+                blk.open();
+                const size_t o_k0 = blk.reserve((size_t)n_big * 4), o_k1 = blk.reserve((size_t)n_big * 4), o_v0 = blk.reserve((size_t)n_big * 8),
+                             o_v1 = blk.reserve((size_t)n_big * 8);
+                const size_t o_hist = blk.reserve((size_t)2048 * big_tiles * 4);
+                blk.alloc(0);
+                if (blk.ok()) {
+                    uint32_t* d_keys[2] = {blk.at<uint32_t>(o_k0), blk.at<uint32_t>(o_k1)};
+                    uint2* d_vals[2] = {blk.at<uint2>(o_v0), blk.at<uint2>(o_v1)};
+                    uint32_t* d_hist = blk.at<uint32_t>(o_hist);
                     const uint32_t gB = (n_big + 255) / 256;
                     int cur = 0;
                     hipLaunchKernelGGL(k_cp_big_gather, dim3(gB), dim3(256), 0, st, f->d_pairs, d_prefix, d_lbig, d_bigpre, n_bigdocs, n_big, d_keys[0], d_vals[0]);
@@ -2518,26 +2559,21 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
                     hipLaunchKernelGGL(k_cp_big_scatter, dim3(gB), dim3(256), 0, st, d_keys[cur], d_vals[cur], n_big, d_prefix, d_lbig, d_bigpre, f->d_pairs);
                 }
             }
-            chk(hipGetLastError());
+            blk.launched();
         }
-        if (e == hipSuccess) chk(hipEventRecord(ev1, st));
-        if (e == hipSuccess) chk(hipStreamSynchronize(st));
+        if (blk.ok()) blk.record(1);
+        if (blk.ok()) blk.sync();
         float ms = 0.0f;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) f->info.device_ms = ms;
+        if (blk.elapsed_ms(0, 1, &ms)) f->info.device_ms = ms;
     }
-    (void)hipStreamSynchronize(st);   // nothing in flight uses the blocks any more
-    if (blkB) pool_free(ctx, blkB, bytesB);
-    if (blkF) pool_free(ctx, blkF, bytesF);
-    if (blkA) pool_free(ctx, blkA, bytesA);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    f->info.device_bytes = (uint64_t)bytesA + bytesB + bytesF + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
-    if (e != hipSuccess || refused_src >= 0) {
+    const int rc = blk.finish(fn);
+    f->info.device_bytes = (uint64_t)blk.held_bytes() + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
+    if (rc != NS_OK || refused_src >= 0) {
         forward_free_device(f);
         delete f;
         (void)hipGetLastError();
-        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "%s: source %d: %s", fn, refused_src, refused_why);
-        return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "%s: source %d: %s", fn, refused_src, refused_why);   // (the refusal is what the caller hears of)
+        return rc;
     }
     return publish();
 }
@@ -2677,47 +2713,37 @@ extern "C" int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint3
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
-    const size_t o_ids = place((size_t)n * 4), o_list = place((size_t)n * 4), o_term = place((size_t)n * T * 4), o_w = place((size_t)n * T * 4), o_cnt = place((size_t)n * 4);
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    chk(hipEventCreate(&ev0));
-    chk(hipEventCreate(&ev1));
-    if (e == hipSuccess) {
-        uint32_t* d_ids = (uint32_t*)(blk + o_ids); uint32_t* d_list = (uint32_t*)(blk + o_list);
-        uint32_t* d_term = (uint32_t*)(blk + o_term); uint32_t* d_w = (uint32_t*)(blk + o_w); uint32_t* d_cnt = (uint32_t*)(blk + o_cnt);
-        chk(hipMemcpyAsync(d_ids, doc_ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_list, lists.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        chk(hipEventRecord(ev0, st));
-        if (e == hipSuccess && n_wave)
+    CallBlock blk(ctx);
+    const size_t o_ids = blk.reserve((size_t)n * 4), o_list = blk.reserve((size_t)n * 4), o_term = blk.reserve((size_t)n * T * 4), o_w = blk.reserve((size_t)n * T * 4),
+                 o_cnt = blk.reserve((size_t)n * 4);
+    blk.alloc(2);
+    if (blk.ok()) {
+        const uint32_t *d_ids = blk.at<uint32_t>(o_ids), *d_list = blk.at<uint32_t>(o_list);
+        uint32_t *d_term = blk.at<uint32_t>(o_term), *d_w = blk.at<uint32_t>(o_w), *d_cnt = blk.at<uint32_t>(o_cnt);
+        blk.upload(o_ids, doc_ids, (size_t)n * 4);
+        blk.upload(o_list, lists.data(), (size_t)n * 4);
+        blk.record(0);
+        if (blk.ok() && n_wave)
             hipLaunchKernelGGL(k_ml_wave, dim3((n_wave + 3) / 4), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, d_ids, d_list, n_wave, rule, T, d_term, d_w, d_cnt);
-        if (e == hipSuccess && n_block)
+        if (blk.ok() && n_block)
             hipLaunchKernelGGL(k_ml_block, dim3(n_block), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, d_ids, d_list + (n - n_block), rule, T, d_term, d_w, d_cnt);
-        chk(hipGetLastError());
-        chk(hipEventRecord(ev1, st));
-        chk(hipMemcpyAsync(term_out, d_term, (size_t)n * T * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(w_out, d_w, (size_t)n * T * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(count_out, d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        chk(hipStreamSynchronize(st));
+        blk.launched();
+        blk.record(1);
+        blk.fetch(term_out, o_term, (size_t)n * T * 4);
+        blk.fetch(w_out, o_w, (size_t)n * T * 4);
+        blk.fetch(count_out, o_cnt, (size_t)n * 4);
+        blk.sync();
         float ms = 0.0f;
-        if (e == hipSuccess && device_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+        if (device_ms_out && blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
     }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return NS_OK;
+    return blk.finish(fn);
 }
 
 // ------------------------------------------------------------------------------------------------
-// The call scaffold of the facet, date-order and boolean entry points (the host-only part of a ranked call's
-// planning is csrc/ns_call_plan.hpp).  A call validates its own arguments, binds its segments (bind_segments), runs its
-// planner and hands the work items to run_count or run_ranked, which own the device block (CallBlock).
+// What the facet, date-order and boolean entry points share above CallBlock (the host-only part of a ranked
+// call's planning is csrc/ns_call_plan.hpp).  A call validates its own arguments, binds its segments (bind_segments), runs
+// its planner and hands the work items to run_count or run_ranked, which own the device block.  (CallBlock itself, behind
+// pool_free, also carries the indexing, merge, similar-terms, semantic and autocomplete calls.)
 
 // A per-document table checked by a kernel at upload (ns_facet_upload, ns_dockeys_upload): n_docs values go up to a fresh
 // allocation, launch_check(d_table, d_bad, grid, stream) starts the kernel that sets *d_bad for a value the call refuses.
@@ -2780,41 +2806,6 @@ static const uint16_t* bq_live_clauses(const uint16_t* clauses, uint32_t n_terms
     return (clauses && n_terms && !roles) ? nullptr : clauses;
 }
 
-// The device block of one call: regions laid out with place_at, one pooled allocation, the call's events and the first
-// HIP error.  reserve() everything, alloc(), then work on the stream only while ok(); finish() on every path after alloc().
-struct CallBlock {
-    ns_ctx* ctx;
-    hipStream_t st;
-    size_t bytes = 0;
-    char* blk = nullptr;
-    std::vector<hipEvent_t> evs;
-    hipError_t e = hipSuccess;
-
-    explicit CallBlock(ns_ctx* c) : ctx(c), st(c->stream) {}
-    void chk(hipError_t r) { if (e == hipSuccess) e = r; }
-    bool ok() const { return e == hipSuccess; }
-    size_t reserve(size_t n) { return place_at(bytes, n); }   // (a region of no bytes still takes a place)
-    void alloc(size_t n_events) {
-        chk(pool_alloc(ctx, (void**)&blk, bytes));
-        evs.assign(n_events, nullptr);
-        for (auto& ev : evs) chk(hipEventCreate(&ev));
-    }
-    template <class T> T* at(size_t off) const { return (T*)(blk + off); }
-    void upload(size_t off, const void* src, size_t n) { if (n) chk(hipMemcpyAsync(blk + off, src, n, hipMemcpyHostToDevice, st)); }
-    void zero(size_t off, size_t n) { chk(hipMemsetAsync(blk + off, 0, n, st)); }
-    void fetch(void* dst, size_t off, size_t n) { chk(hipMemcpyAsync(dst, blk + off, n, hipMemcpyDeviceToHost, st)); }
-    void record(size_t ev) { chk(hipEventRecord(evs[ev], st)); }
-    void launched() { chk(hipGetLastError()); }
-    void sync() { chk(hipStreamSynchronize(st)); }
-    // the block goes back to the pool only once nothing in flight uses it, whatever failed before
-    int finish(const char* fn) {
-        if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, bytes); }
-        for (auto& ev : evs) if (ev) (void)hipEventDestroy(ev);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-        return NS_OK;
-    }
-};
-
 // The facet-count calls from their work items on: one kernel over the items adds to counts[q * B + b], found = the sum of a
 // query's buckets.  time_memset: whether the interval device_ms_out reports starts before the memset of the counts
 // (ns_facet_count) or after it (the boolean and grouped counts); ms_acc (may be NULL) also gets the interval.
@@ -2847,7 +2838,7 @@ static int run_count(ns_ctx* ctx, const char* fn, const std::vector<FcItem>& ite
             blk.fetch(counts_out, o_counts, n_counts * 4);
             blk.sync();
             float ms = 0.0f;
-            if (blk.ok() && hipEventElapsedTime(&ms, blk.evs[0], blk.evs[1]) == hipSuccess) {
+            if (blk.elapsed_ms(0, 1, &ms)) {
                 if (ms_acc) *ms_acc += ms;
                 if (device_ms_out) *device_ms_out = ms;
             }
@@ -2988,7 +2979,7 @@ static int run_ranked(ns_ctx* ctx, const char* fn, const RankedCall<Ref, Aux>& c
             for (size_t i = 0; i < p.cuts.size(); i++)
                 for (int j = 0; j < c.stages; j++) {
                     float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, blk.evs[i * per_cut + j], blk.evs[i * per_cut + j + 1]) == hipSuccess) { c.ms_acc[j] += ms; sum += ms; }
+                    if (blk.elapsed_ms(i * per_cut + j, i * per_cut + j + 1, &ms)) { c.ms_acc[j] += ms; sum += ms; }
                 }
             if (c.device_ms_out) *c.device_ms_out = sum;
         }
@@ -3513,52 +3504,38 @@ extern "C" int ns_sem_topk(ns_ctx* ctx, ns_sem* sem, const float* qvecs, uint32_
     std::vector<float> qpad((size_t)n_groups * kSemB * dim, 0.0f);
     std::memcpy(qpad.data(), qvecs, (size_t)n_q * dim * 4);
 
-    float *d_q = nullptr, *d_osims = nullptr;
-    uint32_t *d_goff = nullptr, *d_grows = nullptr, *d_orows = nullptr, *d_ocnt = nullptr, *d_count = nullptr;
-    uint64_t* d_cand = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     const size_t n_pad = (size_t)n_groups * kSemB;
     // one block from the ctx pool for all scratch arrays (every search of a serving loop expands its query)
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
-    const size_t o_q = place(qpad.size() * 4), o_cand = place((size_t)kSemB * cap * 8), o_goff = place(goff.size() * 4), o_count = place((size_t)kSemB * 4),
-                 o_grows = place(grows.size() * 4), o_orows = place(n_pad * topk * 4), o_osims = place(n_pad * topk * 4), o_ocnt = place(n_pad * 4);
-    const size_t block_bytes = off;
-    char* blk = nullptr;
-    chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    if (e == hipSuccess) {
-        d_q = (float*)(blk + o_q); d_cand = (uint64_t*)(blk + o_cand); d_goff = (uint32_t*)(blk + o_goff); d_count = (uint32_t*)(blk + o_count);
-        d_grows = (uint32_t*)(blk + o_grows); d_orows = (uint32_t*)(blk + o_orows); d_osims = (float*)(blk + o_osims); d_ocnt = (uint32_t*)(blk + o_ocnt);
-    }
-    chk(hipEventCreate(&ev0));
-    chk(hipEventCreate(&ev1));
-    if (e == hipSuccess) {
-        chk(hipMemcpyAsync(d_q, qpad.data(), qpad.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_goff, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_grows, grows.data(), grows.size() * 4, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_count, 0, (size_t)kSemB * 4, st));   // k_sem_final_topk leaves it zero for the next group
-        chk(hipEventRecord(ev0, st));
+    CallBlock blk(ctx);
+    const size_t o_q = blk.reserve(qpad.size() * 4), o_cand = blk.reserve((size_t)kSemB * cap * 8), o_goff = blk.reserve(goff.size() * 4), o_count = blk.reserve((size_t)kSemB * 4),
+                 o_grows = blk.reserve(grows.size() * 4), o_orows = blk.reserve(n_pad * topk * 4), o_osims = blk.reserve(n_pad * topk * 4), o_ocnt = blk.reserve(n_pad * 4);
+    blk.alloc(2);
+    if (blk.ok()) {
+        const float* d_q = blk.at<float>(o_q);
+        float* d_osims = blk.at<float>(o_osims);
+        const uint32_t *d_goff = blk.at<uint32_t>(o_goff), *d_grows = blk.at<uint32_t>(o_grows);
+        uint32_t *d_orows = blk.at<uint32_t>(o_orows), *d_ocnt = blk.at<uint32_t>(o_ocnt), *d_count = blk.at<uint32_t>(o_count);
+        uint64_t* d_cand = blk.at<uint64_t>(o_cand);
+        blk.upload(o_q, qpad.data(), qpad.size() * 4);
+        blk.upload(o_goff, goff.data(), goff.size() * 4);
+        blk.upload(o_grows, grows.data(), grows.size() * 4);
+        blk.zero(o_count, (size_t)kSemB * 4);   // k_sem_final_topk leaves it zero for the next group
+        blk.record(0);
         for (uint32_t g = 0; g < n_groups; g++) {
             hipLaunchKernelGGL(k_sem_scan_topk, dim3((rows + 255) / 256), dim3(256), 0, st, sem->d_vt, rows, rp, dim, d_q + (size_t)g * kSemB * dim, min_sim,
                                d_goff + (size_t)g * (kSemB + 1), d_grows, topk, cap, d_cand, d_count);
             hipLaunchKernelGGL(k_sem_final_topk, dim3(kSemB), dim3(256), 0, st, d_cand, cap, d_count, topk, d_orows + (size_t)g * kSemB * topk, d_osims + (size_t)g * kSemB * topk, d_ocnt + (size_t)g * kSemB);
         }
-        chk(hipEventRecord(ev1, st));
-        chk(hipGetLastError());
-        chk(hipMemcpyAsync(rows_out, d_orows, (size_t)n_q * topk * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(sims_out, d_osims, (size_t)n_q * topk * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(counts_out, d_ocnt, (size_t)n_q * 4, hipMemcpyDeviceToHost, st));
-        chk(hipStreamSynchronize(st));
+        blk.record(1);
+        blk.launched();
+        blk.fetch(rows_out, o_orows, (size_t)n_q * topk * 4);
+        blk.fetch(sims_out, o_osims, (size_t)n_q * topk * 4);
+        blk.fetch(counts_out, o_ocnt, (size_t)n_q * 4);
+        blk.sync();
         float ms = 0.0f;
-        if (e == hipSuccess && device_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+        if (device_ms_out && blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
     }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_sem_topk: %s", hipGetErrorString(e));
-    return NS_OK;
+    return blk.finish("ns_sem_topk");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3712,59 +3689,32 @@ extern "C" int ns_ac_suggest(ns_ctx* ctx, ns_ac* ac, const uint8_t* prefix_bytes
     const size_t up = o_bytes + n_bytes;
     const size_t o_idx = (up + 255) & ~(size_t)255;
     const size_t down = (size_t)n_q * L * 4 + (size_t)n_q * 4;
-    const size_t block_bytes = o_idx + down;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    if (ctx->up_busy) {   // a batch's upload may still be reading the staging buffer
-        chk(hipEventSynchronize(ctx->up_done));
-        ctx->up_busy = false;
-    }
-    if (e == hipSuccess && up <= kStageMaxBytes && ctx->h_up_cap < up) {
-        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
-        ctx->h_up = nullptr; ctx->h_up_cap = 0;
-        const size_t cap = std::max<size_t>(up + up / 2, 1 << 16);
-        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
-        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
-    }
-    const bool down_pinned = !ctx->down_owner && down <= kStageMaxBytes;
-    if (e == hipSuccess && down_pinned && ctx->h_down_cap < down) {
-        if (ctx->h_down) (void)hipHostFree(ctx->h_down);
-        ctx->h_down = nullptr; ctx->h_down_cap = 0;
-        const size_t cap = std::max<size_t>(down + down / 2, 1 << 16);
-        if (hipHostMalloc(&ctx->h_down, cap, hipHostMallocDefault) == hipSuccess) ctx->h_down_cap = cap;
-        else { ctx->h_down = nullptr; (void)hipGetLastError(); }
-    }
-    std::vector<char> up_own, down_own;
-    char* hu = (ctx->h_up_cap >= up) ? (char*)ctx->h_up : (up_own.resize(up), up_own.data());
-    char* hd = (down_pinned && ctx->h_down_cap >= down) ? (char*)ctx->h_down : (down_own.resize(down), down_own.data());
-    for (uint32_t q = 0; q <= n_q; q++) ((uint32_t*)hu)[q] = prefix_offsets[q] - b0;
-    if (n_bytes) std::memcpy(hu + o_bytes, prefix_bytes + b0, n_bytes);
-    char* blk = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e == hipSuccess) chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    if (e == hipSuccess && device_ms_out) { chk(hipEventCreate(&ev0)); chk(hipEventCreate(&ev1)); }
-    if (e == hipSuccess) {
-        chk(hipMemcpyAsync(blk, hu, up, hipMemcpyHostToDevice, st));
-        if (ev0) chk(hipEventRecord(ev0, st));
+    CallBlock blk(ctx);
+    blk.reserve(o_idx + down);   // the image above is what the kernel indexes: one region
+    Staged h;
+    blk.chk(stage_host(ctx, up, down, h));
+    if (!blk.ok()) return blk.finish("ns_ac_suggest");
+    for (uint32_t q = 0; q <= n_q; q++) ((uint32_t*)h.up)[q] = prefix_offsets[q] - b0;
+    if (n_bytes) std::memcpy(h.up + o_bytes, prefix_bytes + b0, n_bytes);
+    blk.alloc(device_ms_out ? 2 : 0);
+    if (blk.ok()) {
+        blk.upload(0, h.up, up);
+        blk.record(0);
         hipLaunchKernelGGL(k_ac_suggest, dim3((n_q + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_tree, ac->lv,
-                           ac->n, (const uint8_t*)(blk + o_bytes), (const uint32_t*)blk, n_q, L, (uint32_t*)(blk + o_idx),
-                           (uint32_t*)(blk + o_idx + (size_t)n_q * L * 4));
-        chk(hipGetLastError());
-        if (ev1) chk(hipEventRecord(ev1, st));
-        chk(hipMemcpyAsync(hd, blk + o_idx, down, hipMemcpyDeviceToHost, st));
-        chk(hipStreamSynchronize(st));
+                           ac->n, blk.at<const uint8_t>(o_bytes), blk.at<const uint32_t>(0), n_q, L, blk.at<uint32_t>(o_idx),
+                           blk.at<uint32_t>(o_idx + (size_t)n_q * L * 4));
+        blk.launched();
+        blk.record(1);
+        blk.fetch(h.down, o_idx, down);
+        blk.sync();
     }
-    if (e == hipSuccess) {
-        std::memcpy(idx_out, hd, (size_t)n_q * L * 4);
-        std::memcpy(count_out, hd + (size_t)n_q * L * 4, (size_t)n_q * 4);
+    if (blk.ok()) {
+        std::memcpy(idx_out, h.down, (size_t)n_q * L * 4);
+        std::memcpy(count_out, h.down + (size_t)n_q * L * 4, (size_t)n_q * 4);
         float ms = 0.0f;
-        if (ev0 && ev1 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+        if (blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
     }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "ns_ac_suggest: %s", hipGetErrorString(e));
-    return NS_OK;
+    return blk.finish("ns_ac_suggest");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3840,6 +3790,48 @@ extern "C" int ns_ac_build_fuzzy(ns_ctx* ctx, ns_ac* ac, float* device_ms_out) {
 static bool fz_env_flag(const char* name) {
     const char* v = std::getenv(name);
     return v && v[0] == '1';
+}
+
+// The two host loops of ac_fuzzy_call over the rows of a call (a batch of 16384 queries walks some 10^5 query bytes here).
+// They are functions of their own, never inlined, so that the code the compiler makes for them does not change with the
+// function around them.
+// The staged upload image of the rows: per row its offset into the term bytes, its first slice, its edits, the signature
+// of its bytes ([0-9] -> bits 0..9, [a-z] -> bits 10..35, anything else bit 36), then the bytes; entry R closes both prefix sums.
+__attribute__((noinline)) static void fz_fill_image(const uint32_t* rows, const uint32_t* window, uint32_t R, uint32_t slice, const uint8_t* term_bytes,
+                                                    const uint32_t* term_offsets, const uint8_t* max_edits, uint32_t* h_offs, uint32_t* h_base,
+                                                    uint64_t* h_sig, uint8_t* h_ed, uint8_t* h_bytes) {
+    uint32_t at = 0, sl = 0;
+    for (uint32_t r = 0; r < R; r++) {
+        const uint32_t q = rows[r], len = term_offsets[q + 1] - term_offsets[q];
+        const uint8_t* t = term_bytes + term_offsets[q];
+        h_offs[r] = at;
+        h_base[r] = sl;
+        h_ed[r] = max_edits[q];
+        uint64_t sig = 0;
+        for (uint32_t j = 0; j < len; j++) {
+            const uint8_t c = t[j];
+            h_bytes[at + j] = c;
+            sig |= (c >= '0' && c <= '9') ? 1ull << (c - '0') : (c >= 'a' && c <= 'z') ? 1ull << (10 + c - 'a') : 1ull << 36;
+        }
+        h_sig[r] = sig;
+        at += len;
+        sl += (window[r] + slice - 1) / slice;
+    }
+    h_offs[R] = at;
+    h_base[R] = sl;
+}
+// The staged result image [idx R x L | counts R | dist R x L] -> the rows' queries in the caller's arrays.
+__attribute__((noinline)) static void fz_read_image(const uint32_t* rows, uint32_t R, uint32_t L, const char* h_down, uint32_t* idx_out, uint8_t* dist_out,
+                                                    uint32_t* count_out) {
+    const uint32_t* h_idx = (const uint32_t*)h_down;
+    const uint32_t* h_cnt = h_idx + (size_t)R * L;
+    const uint8_t* h_dist = (const uint8_t*)(h_cnt + R);
+    for (uint32_t r = 0; r < R; r++) {
+        const size_t q = rows[r];
+        count_out[q] = h_cnt[r];
+        std::memcpy(idx_out + q * L, h_idx + (size_t)r * L, (size_t)L * 4);
+        std::memcpy(dist_out + q * L, h_dist + (size_t)r * L, L);
+    }
 }
 
 // ns_ac_fuzzy (fn = its name, complete = false) and ns_ac_fuzzy_prefix (complete = true): the same arguments, refusals, staging
@@ -3920,112 +3912,52 @@ static int ac_fuzzy_call(const char* fn, bool complete, ns_ctx* ctx, ns_ac* ac, 
     const size_t o_part = o_plan + (((size_t)R * (complete ? sizeof(FpPlan) : sizeof(FzPlan)) + 255) & ~(size_t)255);
     const size_t o_idx = o_part + (size_t)n_slices * kAcTop * 8;
     const size_t down = (size_t)R * L * 4 + (size_t)R * 4 + (size_t)R * L;
-    const size_t block_bytes = o_idx + down;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    if (ctx->up_busy) {   // a batch's upload may still be reading the staging buffer
-        chk(hipEventSynchronize(ctx->up_done));
-        ctx->up_busy = false;
-    }
-    if (e == hipSuccess && up <= kStageMaxBytes && ctx->h_up_cap < up) {
-        if (ctx->h_up) (void)hipHostFree(ctx->h_up);
-        ctx->h_up = nullptr; ctx->h_up_cap = 0;
-        const size_t cap = std::max<size_t>(up + up / 2, 1 << 16);
-        if (hipHostMalloc(&ctx->h_up, cap, hipHostMallocDefault) == hipSuccess) ctx->h_up_cap = cap;
-        else { ctx->h_up = nullptr; (void)hipGetLastError(); }
-    }
-    const bool down_pinned = !ctx->down_owner && down <= kStageMaxBytes;
-    if (e == hipSuccess && down_pinned && ctx->h_down_cap < down) {
-        if (ctx->h_down) (void)hipHostFree(ctx->h_down);
-        ctx->h_down = nullptr; ctx->h_down_cap = 0;
-        const size_t cap = std::max<size_t>(down + down / 2, 1 << 16);
-        if (hipHostMalloc(&ctx->h_down, cap, hipHostMallocDefault) == hipSuccess) ctx->h_down_cap = cap;
-        else { ctx->h_down = nullptr; (void)hipGetLastError(); }
-    }
-    std::vector<char> up_own, down_own;
-    char* hu = (ctx->h_up_cap >= up) ? (char*)ctx->h_up : (up_own.resize(up), up_own.data());
-    char* hd = (down_pinned && ctx->h_down_cap >= down) ? (char*)ctx->h_down : (down_own.resize(down), down_own.data());
-    {
-        uint32_t* h_offs = (uint32_t*)hu;
-        uint32_t* h_base = (uint32_t*)(hu + o_base);
-        uint64_t* h_sig = (uint64_t*)(hu + o_sig);
-        uint8_t* h_ed = (uint8_t*)(hu + o_ed);
-        uint8_t* h_bytes = (uint8_t*)(hu + o_bytes);
-        uint32_t at = 0, sl = 0;
-        for (uint32_t r = 0; r < R; r++) {
-            const uint32_t q = rows[r], len = term_offsets[q + 1] - term_offsets[q];
-            const uint8_t* t = term_bytes + term_offsets[q];
-            h_offs[r] = at;
-            h_base[r] = sl;
-            h_ed[r] = max_edits[q];
-            uint64_t sig = 0;
-            for (uint32_t j = 0; j < len; j++) {
-                const uint8_t c = t[j];
-                h_bytes[at + j] = c;
-                sig |= (c >= '0' && c <= '9') ? 1ull << (c - '0') : (c >= 'a' && c <= 'z') ? 1ull << (10 + c - 'a') : 1ull << 36;
-            }
-            h_sig[r] = sig;
-            at += len;
-            sl += (window[r] + slice - 1) / slice;
-        }
-        h_offs[R] = at;
-        h_base[R] = sl;
-    }
-    char* blk = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e == hipSuccess) chk(pool_alloc(ctx, (void**)&blk, block_bytes));
-    if (e == hipSuccess && device_ms_out) { chk(hipEventCreate(&ev0)); chk(hipEventCreate(&ev1)); }
-    if (e == hipSuccess) {
+    CallBlock blk(ctx);
+    blk.reserve(o_idx + down);   // the image above is what the kernels index: one region
+    Staged h;
+    blk.chk(stage_host(ctx, up, down, h));
+    if (!blk.ok()) return blk.finish(fn);
+    fz_fill_image(rows.data(), window.data(), R, slice, term_bytes, term_offsets, max_edits, (uint32_t*)h.up, (uint32_t*)(h.up + o_base),
+                  (uint64_t*)(h.up + o_sig), (uint8_t*)(h.up + o_ed), (uint8_t*)(h.up + o_bytes));
+    blk.alloc(device_ms_out ? 2 : 0);
+    if (blk.ok()) {
         const uint32_t use_sig = fz_env_flag("NS_FUZZY_NO_SIG") ? 0u : 1u;
-        const uint32_t* d_offs = (const uint32_t*)blk;
-        const uint32_t* d_base = (const uint32_t*)(blk + o_base);
-        const uint8_t* d_ed = (const uint8_t*)(blk + o_ed);
-        uint32_t* d_idx = (uint32_t*)(blk + o_idx);
+        const uint32_t *d_offs = blk.at<const uint32_t>(0), *d_base = blk.at<const uint32_t>(o_base);
+        const uint8_t *d_ed = blk.at<const uint8_t>(o_ed), *d_bytes = blk.at<const uint8_t>(o_bytes);
+        const uint64_t* d_sig = blk.at<const uint64_t>(o_sig);
+        uint64_t* d_part = blk.at<uint64_t>(o_part);
+        uint32_t* d_idx = blk.at<uint32_t>(o_idx);
         uint32_t* d_cnt = d_idx + (size_t)R * L;
         uint8_t* d_dist = (uint8_t*)(d_cnt + R);
-        chk(hipMemcpyAsync(blk, hu, up, hipMemcpyHostToDevice, st));
-        if (ev0) chk(hipEventRecord(ev0, st));
+        blk.upload(0, h.up, up);
+        blk.record(0);
         if (complete) {
             hipLaunchKernelGGL(k_fp_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
-                               ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FpPlan*)(blk + o_plan));
-            chk(hipGetLastError());
+                               ac->d_fz_len_start, d_bytes, d_offs, d_ed, R, prefix_len, blk.at<FpPlan>(o_plan));
+            blk.launched();
             hipLaunchKernelGGL(k_fp_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
-                               ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
-                               (const FpPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
-            chk(hipGetLastError());
+                               ac->d_fz_sig, d_bytes, d_offs, d_ed, d_sig, d_base, R, slice, blk.at<const FpPlan>(o_plan), L, use_sig, d_part);
+            blk.launched();
         } else {
             hipLaunchKernelGGL(k_fz_plan, dim3((R + 3) / 4), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->n, ac->d_fz_perm,
-                               ac->d_fz_len_start, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, R, prefix_len, (FzPlan*)(blk + o_plan));
-            chk(hipGetLastError());
+                               ac->d_fz_len_start, d_bytes, d_offs, d_ed, R, prefix_len, blk.at<FzPlan>(o_plan));
+            blk.launched();
             hipLaunchKernelGGL(k_fz_scan, dim3((uint32_t)n_slices), dim3(256), 0, st, ac->d_heads, ac->d_offs, ac->d_pool, ac->d_keys, ac->d_fz_perm,
-                               ac->d_fz_sig, (const uint8_t*)(blk + o_bytes), d_offs, d_ed, (const uint64_t*)(blk + o_sig), d_base, R, slice,
-                               (const FzPlan*)(blk + o_plan), L, use_sig, (uint64_t*)(blk + o_part));
-            chk(hipGetLastError());
+                               ac->d_fz_sig, d_bytes, d_offs, d_ed, d_sig, d_base, R, slice, blk.at<const FzPlan>(o_plan), L, use_sig, d_part);
+            blk.launched();
         }
-        hipLaunchKernelGGL(k_fz_select, dim3((R + 3) / 4), dim3(256), 0, st, (const uint64_t*)(blk + o_part), d_base, R, L, d_idx, d_dist, d_cnt);
-        chk(hipGetLastError());
-        if (ev1) chk(hipEventRecord(ev1, st));
-        chk(hipMemcpyAsync(hd, blk + o_idx, down, hipMemcpyDeviceToHost, st));
-        chk(hipStreamSynchronize(st));
+        hipLaunchKernelGGL(k_fz_select, dim3((R + 3) / 4), dim3(256), 0, st, (const uint64_t*)d_part, d_base, R, L, d_idx, d_dist, d_cnt);
+        blk.launched();
+        blk.record(1);
+        blk.fetch(h.down, o_idx, down);
+        blk.sync();
     }
-    if (e == hipSuccess) {
-        const uint32_t* h_idx = (const uint32_t*)hd;
-        const uint32_t* h_cnt = h_idx + (size_t)R * L;
-        const uint8_t* h_dist = (const uint8_t*)(h_cnt + R);
-        for (uint32_t r = 0; r < R; r++) {
-            const size_t q = rows[r];
-            count_out[q] = h_cnt[r];
-            std::memcpy(idx_out + q * L, h_idx + (size_t)r * L, (size_t)L * 4);
-            std::memcpy(dist_out + q * L, h_dist + (size_t)r * L, L);
-        }
+    if (blk.ok()) {
+        fz_read_image(rows.data(), R, L, h.down, idx_out, dist_out, count_out);
         float ms = 0.0f;
-        if (ev0 && ev1 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms_out = ms;
+        if (blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
     }
-    if (blk) { (void)hipStreamSynchronize(st); pool_free(ctx, blk, block_bytes); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return NS_OK;
+    return blk.finish(fn);
 }
 
 extern "C" int ns_ac_fuzzy(ns_ctx* ctx, ns_ac* ac, const uint8_t* term_bytes, const uint32_t* term_offsets, uint32_t n_q,
