@@ -494,6 +494,13 @@ int ns_forward_invert(ns_forward* fwd, uint32_t* df_out, void* postings_out, uin
  * ns_compact_doc_cut() pairs in LDS by one workgroup; longer documents go through the global radix sort.  on == 0 sends
  * every document through the radix sort (the A/B baseline; same bytes).  Default: on. */
 uint32_t ns_compact_doc_cut(void);
+/* The radix sort under ns_invert_forward, ns_forward_build and ns_forward_merge (csrc/ns_invert.hip) sorts keys below
+ * key_range in 1 .. 3 passes of 8 .. 11 bits, a function of key_range alone (csrc/ns_radix_plan.hpp).  ns_radix_plan writes
+ * the digit of each pass, lowest first, to pbits_out (8 for the passes not used) and returns the number of passes;
+ * ns_radix_tile() is the number of items one workgroup of a pass sorts.  Both are for the tests, which build their shapes
+ * from them. */
+uint32_t ns_radix_plan(uint32_t key_range, uint32_t pbits_out[3]);
+uint32_t ns_radix_tile(void);
 int ns_ctx_use_docsort(ns_ctx* ctx, int on);
 
 /* Deleting documents (csrc/ns_delete.hip): ns_forward_merge over FILTERED sources.  keep[s] is a bitmap

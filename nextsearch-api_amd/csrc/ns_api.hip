@@ -36,6 +36,7 @@
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
 #include "ns_call_plan.hpp"   // host only: what a ranked call plans on top of ns_sorted_plan.hpp and ns_after_plan.hpp
+#include "ns_radix_plan.hpp"  // host only: the digits of the radix sort in ns_invert.hip
 
 using namespace ns;
 
@@ -1750,19 +1751,10 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
     const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
     // Digit plan, from n_terms alone (no device -> host sync decides it): the keys are the termIds below n_terms — a pair with
     // any other termId is dropped by the reference (src/lexicon.cpp:69-70) and leaves the sort in the first pass — so
-    // `bits` = the width of n_terms - 1, sorted in ceil(bits / 11) passes of 8 .. 11 bits, as even as possible.
-    int bits = 1;
-    while (bits < 32 && n_terms > 1 && ((n_terms - 1) >> bits) != 0) bits++;
-    const int passes = std::max(1, (bits + 10) / 11);
-    int pbits[3] = {8, 8, 8};
-    {
-        int left = bits;
-        for (int p = 0; p < passes; p++) {
-            const int share = (left + (passes - p) - 1) / (passes - p);
-            pbits[p] = std::min(11, std::max(8, share));
-            left = std::max(0, left - pbits[p]);
-        }
-    }
+    // the width of n_terms - 1 is sorted in ceil(bits / 11) passes of 8 .. 11 bits, as even as possible (ns_radix_plan.hpp).
+    const RadixPlan rp = radix_plan(n_terms);
+    const int passes = rp.passes;
+    const int* pbits = rp.pbits;
     size_t m_max = 0;
     for (int p = 0; p < passes; p++) m_max = std::max(m_max, ((size_t)1 << pbits[p]) * n_tiles);
     const uint32_t scan_blocks_max = (uint32_t)((m_max + 1023) / 1024);
@@ -1916,15 +1908,10 @@ static void ig_scan(hipStream_t st, uint32_t* d_a, uint32_t m, uint32_t* d_sums,
 // buffer *cur, the result buffer *cur afterwards.  d_hist: 2048 * ceil(n / kIvTile) words
 static void ig_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_keys[2], uint2* d_vals[2], int* cur, uint32_t* d_hist, uint32_t* d_sums) {
     const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
-    int bits = 1;
-    while (bits < 32 && key_range > 1 && ((key_range - 1) >> bits) != 0) bits++;
-    const int passes = std::max(1, (bits + 10) / 11);
+    const RadixPlan rp = radix_plan(key_range);
     uint32_t shift = 0;
-    int left = bits;
-    for (int p = 0; p < passes; p++) {
-        const int share = (left + (passes - p) - 1) / (passes - p);
-        const int pb = std::min(11, std::max(8, share));
-        left = std::max(0, left - pb);
+    for (int p = 0; p < rp.passes; p++) {
+        const int pb = rp.pbits[p];
         const int nxt = *cur ^ 1;
         const uint32_t m = ((uint32_t)1 << pb) * n_tiles;
 #define NS_IG_HIST(B) hipLaunchKernelGGL((k_iv_hist_w<B>), dim3(n_tiles), dim3(256), 0, st, d_keys[*cur], (const uint2*)nullptr, n, (const uint32_t*)nullptr, key_range, shift, d_hist, n_tiles)
@@ -2281,6 +2268,12 @@ extern "C" void ns_forward_destroy(ns_forward* fwd) {
 // ------------------------------------------------------------------------------------------------
 // Compaction: the forward indexes of several segments -> one (csrc/ns_compact.hip)
 extern "C" uint32_t ns_compact_doc_cut(void) { return kCpDocCut; }
+extern "C" uint32_t ns_radix_plan(uint32_t key_range, uint32_t pbits_out[3]) {
+    const RadixPlan rp = radix_plan(key_range);
+    for (int p = 0; pbits_out && p < 3; p++) pbits_out[p] = (uint32_t)rp.pbits[p];
+    return (uint32_t)rp.passes;
+}
+extern "C" uint32_t ns_radix_tile(void) { return (uint32_t)kIvTile; }
 
 extern "C" int ns_ctx_use_docsort(ns_ctx* ctx, int on) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_use_docsort: ctx is NULL");

@@ -75,7 +75,7 @@ HIP_SYMBOLS = [
     "ns_invert_forward", "ns_segment_upload_inverted", "ns_merge_rank_rows", "ns_sem_upload", "ns_sem_release", "ns_sem_topk",
     "ns_ac_upload", "ns_ac_suggest", "ns_ac_release", "ns_ac_build_fuzzy", "ns_ac_fuzzy", "ns_ac_fuzzy_prefix",
     "ns_forward_build", "ns_forward_get_info", "ns_forward_fetch", "ns_forward_destroy",
-    "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort",
+    "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort", "ns_radix_plan", "ns_radix_tile",
     "ns_forward_merge_keep",
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
 ]
@@ -241,6 +241,10 @@ def hip_lib():
         L.ns_compact_doc_cut.argtypes = []
         L.ns_compact_doc_cut.restype = u32
         L.ns_ctx_use_docsort.argtypes = [vp, i32]
+        L.ns_radix_plan.argtypes = [u32, vp]
+        L.ns_radix_plan.restype = u32
+        L.ns_radix_tile.argtypes = []
+        L.ns_radix_tile.restype = u32
         L.ns_forward_merge_keep.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
         L.ns_docterms_upload.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
         L.ns_docterms_select.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, C.POINTER(C.c_float)]
@@ -1742,12 +1746,18 @@ def _fetched(L, ctx, h, invert):
 
 def forward_build(ctx, texts):
     """Raw ns_forward_build + fetch: texts = list of bytes -> dict(kept_docs, doc_len, counts, pairs[n, 2], terms[list of bytes], info)"""
-    L = hip_lib()
     blob = b"".join(texts)
     offs = np.zeros(len(texts) + 1, dtype=np.uint64)
     offs[1:] = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+    return forward_build_raw(ctx, blob, offs)
+
+
+def forward_build_raw(ctx, blob, offs):
+    """forward_build on the call's own arguments: the concatenated text and the u64 offsets of its len(offs) - 1 documents"""
+    L = hip_lib()
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
     h = C.c_void_p()
-    rc = L.ns_forward_build(ctx, blob, len(blob), offs.ctypes.data, len(texts), C.byref(h))
+    rc = L.ns_forward_build(ctx, blob, len(blob), offs.ctypes.data, len(offs) - 1, C.byref(h))
     if rc != NS_OK:
         raise RuntimeError(f"ns_forward_build: {rc}: {L.ns_last_error(ctx).decode()}")
     try:

@@ -93,9 +93,9 @@ def test_device_inversion_equals_reference_golden(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_docs,n_terms,mean,seed", [(20_000, 70_000, 45, 99),      # 17-bit ids: three radix passes
+@pytest.mark.parametrize("n_docs,n_terms,mean,seed", [(20_000, 70_000, 45, 99),      # 17-bit ids: two passes, of 9 and 8 bits
                                                       (5_000, 200, 30, 3),           # one pass, long lists
-                                                      (50_000, 65_536, 60, 11),      # exactly 2^16 terms: the drop key needs a 17th bit
+                                                      (50_000, 65_536, 60, 11),      # exactly 2^16 terms: the widest ids of two 8-bit passes
                                                       (1, 10, 5, 5), (4097, 3, 2, 8)])
 def test_device_inversion_equals_oracle(tmp_path, n_docs, n_terms, mean, seed):
     a, b = str(tmp_path / "a"), str(tmp_path / "b")
