@@ -775,6 +775,43 @@ int ns_search_sorted_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t
  * k_bs_select, k_sd_join, k_bs_score, milliseconds; reset != 0 zeroes the sums after the read.  For tools/grouped_bench.py. */
 int ns_grouped_kernel_ms(float* out6, int reset);
 
+/* ---- at-least-m-of-n clauses in boolean queries -------------------------------- */
+/* "At least two of these four":  +(fever cough dyspnea fatigue)~2.  Each call is its grouped sibling with needs[r] behind
+ * clauses[r]: how many DISTINCT lists of the clause of terms[r] a document must lie in.
+ *   needs[r]     is read for NS_ROLE_MUST refs only.  0 reads as 1.  A value above 7 is refused.  The refs of one clause in one
+ *                (query, segment) group must carry the same need; needs with clauses == NULL are refused.
+ *   MATCHED SET  a clause with need m holds for a document that lies in at least m distinct lists of the clause.  Refs with
+ *                count == 0 are dropped.  A list named twice in a clause (the same byte_off and count) counts once.  A clause
+ *                with fewer than m distinct lists left kills the group (m = 1: the sibling's rule).  Everything else is the
+ *                sibling's: every clause must hold, no NOT list may, postings with docId >= n_docs are ignored.
+ *   SCORE, ORDER, HITS, cursors, found, rest, ODD NUMBERS: exactly the sibling's.
+ *   needs == NULL: the call IS its grouped sibling (the same plan, the same kernels, the same bytes out).  Needs that are all 1
+ *                give the sibling's answers byte for byte, through the quorum kernels.  A clause of n distinct lists with
+ *                postings and need n gives the answers of n one-term clauses.
+ * "At least m of the optional terms" is one required clause holding those terms: MUST and SHOULD refs score alike.
+ * Refusals are the siblings', and the three above. */
+int ns_search_quorum_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                           const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the boolean call */,
+                           const uint8_t* needs /* n_terms; NULL = the sibling */, uint32_t n_terms, uint32_t k,
+                           const ns_cursor* after /* n_queries; NULL = none (page 1) */, const uint32_t* seg_ids, ns_seg* const* segs,
+                           uint32_t n_segs, ns_hit* hits_out /* Q x K */, uint32_t* nhits_out, uint64_t* found_out /* may be NULL */,
+                           uint64_t* rest_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+int ns_facet_count_quorum(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                          const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the boolean call */,
+                          const uint8_t* needs /* n_terms; NULL = the sibling */, uint32_t n_terms, const uint32_t* seg_ids,
+                          ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs, uint32_t* counts_out /* Q x n_buckets */,
+                          uint64_t* found_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+int ns_search_sorted_quorum(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                            const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the boolean call */,
+                            const uint8_t* needs /* n_terms; NULL = the sibling */, uint32_t n_terms, uint32_t k, uint32_t flags,
+                            const ns_cursor* after /* n_queries; NULL = none */, const uint32_t* seg_ids, ns_seg* const* segs,
+                            ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out /* Q x K */, uint32_t* keys_out /* Q x K */,
+                            uint32_t* nhits_out, uint64_t* found_out /* may be NULL */, uint64_t* rest_out /* may be NULL */,
+                            float* device_ms_out /* may be NULL */);
+/* HIP-event time of the launches of the three calls above that were given needs (with needs == NULL the siblings' sums count
+ * them), summed over the calling thread's calls since the last reset: out6[0..5] as ns_grouped_kernel_ms. */
+int ns_quorum_kernel_ms(float* out6, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

@@ -505,6 +505,41 @@ int nsh_engine_search_grouped_faceted_json(nsh_engine* e, const char* query, int
 int nsh_engine_search_grouped_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                           const char* date_to, int keep_undated, char** json_out);
 
+/* ---- at-least-m-of-n clauses in boolean queries (host/quorum.hpp) ----
+ * nsx::parse_quorum: nsh_parse_grouped's dialect plus two forms.  A group's ')' directly followed by '~' and decimal digits sets
+ * the group's need m: `+(fever cough dyspnea fatigue)~2` is a required clause of which a document must hold at least two terms, and
+ * so is the bare `(...)~2`; on a `-( )` group the suffix is consumed and ignored.  A whole piece `~m` makes ALL optional terms of
+ * the query one required clause of need m (the last such piece wins, `~0` is none).  A text with neither form parses as
+ * nsh_parse_grouped parses it.  The terms go to buf joined by single spaces (truncated to cap - 1 bytes); roles[i], clauses[i],
+ * needs[i] (the need of a MUST term's clause, 0 on SHOULD and NOT terms) and promoted[i] (1: an optional term that `~m` made a
+ * member of the last clause) next to them (i < terms_cap; each may be NULL); *min_should_out (may be NULL) = the `~m` piece's m,
+ * 0 for none; returns the number of terms.  The parser is total; the engine refuses a need above 7. */
+uint32_t nsh_parse_quorum(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                          uint32_t terms_cap, uint32_t* min_should_out);
+/* Engine::search_quorum_after_batch_flat, facet_quorum_batch_flat, search_quorum_sorted_batch_flat: the grouped batch calls over
+ * that dialect, parameter for parameter, filters and cursors included.  A term of a clause that the index does not know is dropped
+ * and the need stays: a need above the known terms matches nothing.  A need above 7, or more than 65 535 required clauses in one
+ * query: -1 with a message. */
+int nsh_engine_search_quorum_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                         const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                         uint8_t* has_found, float* device_ms_out);
+int nsh_engine_facet_quorum_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                  uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
+int nsh_engine_search_quorum_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                          uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                          uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_quorum, search_quorum_faceted, search_quorum_sorted: *json_out (free with nsh_free) = the body of
+ * nsh_engine_search_grouped_json / _faceted_json / _sorted_json over this dialect, with "quorum": {"min_should": m, "must": [{"need":
+ * n, "terms": [...]}, ...], "must_not": [...], "should": [...]} in place of "grouped" (keys stay sorted: behind "query"); the terms a
+ * `~m` piece promoted are listed under "should".  On failure -1 and {"error": ...}.  nsh_engine_search_page_json pages them with
+ * mode 7 (quorum, cursors of kind 's') and mode 8 (quorum, sorted by spec, cursors of kind 'd'). */
+int nsh_engine_search_quorum_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                  int keep_undated, char** json_out);
+int nsh_engine_search_quorum_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                          const char* date_to, int keep_undated, char** json_out);
+int nsh_engine_search_quorum_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                         const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

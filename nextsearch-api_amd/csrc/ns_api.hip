@@ -2799,19 +2799,38 @@ static const uint16_t* bq_live_clauses(const uint16_t* clauses, uint32_t n_terms
     return (clauses && n_terms && !roles) ? nullptr : clauses;
 }
 
+// At-least-m-of-n clauses: needs belong to clauses; without live clauses nothing reads them.  False (with `why`):
+// needs were given without clauses.
+static bool bq_live_needs(const uint16_t* given_clauses, const uint16_t* live_clauses, const uint8_t*& needs, std::string& why) {
+    if (needs && !given_clauses) { why = "needs without clauses: a need belongs to a clause"; return false; }
+    if (!live_clauses) needs = nullptr;
+    return true;
+}
+
+// Counter planes of a quorum launch: what its largest need asks for.  Test builds may force three (NS_QUORUM_PLANES=3: the price of
+// the LDS alone, tools/quorum_bench.py).
+static uint32_t bq_launch_planes(uint32_t max_need) {
+    uint32_t planes = bq_need_planes(max_need);
+#if defined(NS_VARIANTS) || defined(NS_COUNT)
+    if (const char* t = std::getenv("NS_QUORUM_PLANES")) { if (planes && std::atol(t) == 3) planes = 3; }
+#endif
+    return planes;
+}
+
 // The facet-count calls from their work items on: one kernel over the items adds to counts[q * B + b], found = the sum of a
 // query's buckets.  time_memset: whether the interval device_ms_out reports starts before the memset of the counts
 // (ns_facet_count) or after it (the boolean and grouped counts); ms_acc (may be NULL) also gets the interval.
 template <class Ref>
 static int run_count(ns_ctx* ctx, const char* fn, const std::vector<FcItem>& items, const std::vector<Ref>& refs, const std::vector<DevFcSeg>& dsegs,
                      void (*kernel)(const FcItem*, const Ref*, const DevFcSeg*, uint32_t, uint32_t*), uint32_t n_queries, uint32_t B,
-                     bool time_memset, float* ms_acc, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+                     bool time_memset, float* ms_acc, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out, size_t lds = 0) {
     std::string why;
     if (!call_item_limit(items.size(), why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     const size_t n_counts = (size_t)n_queries * B;
     if (!items.empty()) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
         CallBlock blk(ctx);
+        if (lds) blk.chk(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (the quorum planes)
         const size_t o_items = blk.reserve(items.size() * sizeof(FcItem)), o_refs = blk.reserve(refs.size() * sizeof(Ref)),
                      o_segs = blk.reserve(dsegs.size() * sizeof(DevFcSeg)), o_counts = blk.reserve(n_counts * 4);
         blk.alloc(2);
@@ -2823,7 +2842,7 @@ static int run_count(ns_ctx* ctx, const char* fn, const std::vector<FcItem>& ite
             blk.zero(o_counts, n_counts * 4);
             if (!time_memset) blk.record(0);
             if (blk.ok()) {
-                hipLaunchKernelGGL(kernel, dim3((uint32_t)items.size()), dim3(256), 0, blk.st, blk.at<const FcItem>(o_items), blk.at<const Ref>(o_refs),
+                hipLaunchKernelGGL(kernel, dim3((uint32_t)items.size()), dim3(256), lds, blk.st, blk.at<const FcItem>(o_items), blk.at<const Ref>(o_refs),
                                    blk.at<const DevFcSeg>(o_segs), B, blk.at<uint32_t>(o_counts));
                 blk.launched();
             }
@@ -3211,13 +3230,13 @@ extern "C" int ns_boolean_kernel_ms(float* out2, int reset) {
 }
 
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
 
 extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                  uint32_t n_terms, uint32_t k, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                                  uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
-    return bq_search(ctx, "ns_search_boolean", queries, n_queries, terms, roles, nullptr, n_terms, k, nullptr, seg_ids, segs, n_segs, hits_out, nhits_out, found_out,
+    return bq_search(ctx, "ns_search_boolean", queries, n_queries, terms, roles, nullptr, nullptr, n_terms, k, nullptr, seg_ids, segs, n_segs, hits_out, nhits_out, found_out,
                      nullptr, device_ms_out);
 }
 
@@ -3225,7 +3244,7 @@ extern "C" int ns_search_boolean_after(ns_ctx* ctx, const ns_query_desc* queries
                                        uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs,
                                        uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
                                        float* device_ms_out) {
-    return bq_search(ctx, "ns_search_boolean_after", queries, n_queries, terms, roles, nullptr, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+    return bq_search(ctx, "ns_search_boolean_after", queries, n_queries, terms, roles, nullptr, nullptr, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
                      found_out, rest_out, device_ms_out);
 }
 
@@ -3244,12 +3263,31 @@ extern "C" int ns_search_grouped_after(ns_ctx* ctx, const ns_query_desc* queries
                                        const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids,
                                        ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out, uint64_t* found_out,
                                        uint64_t* rest_out, float* device_ms_out) {
-    return bq_search(ctx, "ns_search_grouped_after", queries, n_queries, terms, roles, clauses, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+    return bq_search(ctx, "ns_search_grouped_after", queries, n_queries, terms, roles, clauses, nullptr, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+                     found_out, rest_out, device_ms_out);
+}
+
+// At-least-m-of-n clauses: needs == NULL is the grouped sibling, plan and kernels; otherwise bq_plan_quorum and the
+// QUORUM instantiations of the same kernels, with counter planes in dynamic LDS when a need of the launch is above 1.
+static thread_local float g_qq_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // of the calls with needs: k_bq_select, k_bq_join, k_bs_count, k_bs_select, k_sd_join, k_bs_score (ns_quorum_kernel_ms)
+
+extern "C" int ns_quorum_kernel_ms(float* out6, int reset) {
+    if (!out6) return NS_E_INVAL;
+    for (int i = 0; i < 6; i++) out6[i] = g_qq_ms[i];
+    if (reset) for (int i = 0; i < 6; i++) g_qq_ms[i] = 0.0f;
+    return NS_OK;
+}
+
+extern "C" int ns_search_quorum_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                      const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after,
+                                      const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out, uint32_t* nhits_out,
+                                      uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    return bq_search(ctx, "ns_search_quorum_after", queries, n_queries, terms, roles, clauses, needs, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
                      found_out, rest_out, device_ms_out);
 }
 
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
+                     const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
@@ -3269,26 +3307,30 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     RankedPlan plan;
     std::string why;
     const uint32_t tile = ns_facet_tile_docs(), win = bq_win_docs(tile);
+    const uint16_t* const given = clauses;
     clauses = bq_live_clauses(clauses, n_terms, roles);
-    const bool grouped = clauses != nullptr;
-    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, tile, refs, items, why) != NS_OK)
+    if (!bq_live_needs(given, clauses, needs, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const bool grouped = clauses != nullptr, quorum = needs != nullptr;
+    uint32_t max_need = 0;
+    if (bq_plan_quorum(queries, n_queries, terms, roles, clauses, needs, n_terms, views.data(), n_segs, tile, refs, items, max_need, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (!ranked_call_plan(items, n_queries, k, after, views, [](uint32_t bits) { return after_ord(bits); }, false, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    static const SelectKernel<BqRef, DevBqSeg> kSelect[2][2] = {{k_bq_select<false, false>, k_bq_select<true, false>},
-                                                                {k_bq_select<false, true>, k_bq_select<true, true>}};   // [grouped][paged]
+    static const SelectKernel<BqRef, DevBqSeg> kSelect[3][2] = {{k_bq_select<false, false>, k_bq_select<true, false>},
+                                                                {k_bq_select<false, true>, k_bq_select<true, true>},
+                                                                {k_bq_select<false, true, true>, k_bq_select<true, true, true>}};   // [boolean, grouped, quorum][paged]
     const uint32_t K = plan.K;
     RankedCall<BqRef, DevBqSeg> c{items, refs, dsegs, bqs, plan, n_queries};
-    c.select = kSelect[grouped][plan.paged];
+    c.select = kSelect[quorum ? 2 : grouped][plan.paged];
     c.select_arg = win;
-    c.select_lds = bq_lds_bytes(win);
+    c.select_lds = quorum ? bq_quorum_lds_bytes(win, bq_launch_planes(max_need)) : bq_lds_bytes(win);   // (the product's: at most 42 KiB)
 #if defined(NS_VARIANTS) || defined(NS_COUNT)
     if (c.select_lds > (48u << 10))   // (the test windows only: the product's fits the default)
         c.before = hipFuncSetAttribute(reinterpret_cast<const void*>(c.select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.select_lds);
 #endif
     c.stages = 2;
-    c.ms_acc = grouped ? g_gq_ms : g_bq_ms;
+    c.ms_acc = quorum ? g_qq_ms : grouped ? g_gq_ms : g_bq_ms;
     c.hits_out = hits_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
     return run_ranked(ctx, fn, c, [=](const RankedDev<BqRef, DevBqSeg>& d, const SdBatch& b, hipStream_t st) {
         hipLaunchKernelGGL(k_bq_join, dim3((b.q_end - b.q_begin + 3) / 4), dim3(256), 0, st, d.items, d.q_off, b.q_begin, b.q_end, b.item_begin, d.aux, d.cand, K, d.hits, d.nhits);
@@ -3307,30 +3349,30 @@ extern "C" int ns_boolean_sets_kernel_ms(float* out4, int reset) {
 }
 
 static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                    const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                    const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
                     uint32_t* counts_out, uint64_t* found_out, float* device_ms_out);
 static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                     const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
                      ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
 
 extern "C" int ns_facet_count_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                       uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
                                       uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
-    return bs_facet(ctx, "ns_facet_count_boolean", queries, n_queries, terms, roles, nullptr, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
+    return bs_facet(ctx, "ns_facet_count_boolean", queries, n_queries, terms, roles, nullptr, nullptr, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
 }
 
 extern "C" int ns_facet_count_grouped(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                       const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables,
                                       uint32_t n_segs, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
-    return bs_facet(ctx, "ns_facet_count_grouped", queries, n_queries, terms, roles, clauses, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
+    return bs_facet(ctx, "ns_facet_count_grouped", queries, n_queries, terms, roles, clauses, nullptr, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
 }
 
 extern "C" int ns_search_sorted_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                         uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
                                         ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
                                         uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
-    return bs_sorted(ctx, "ns_search_sorted_boolean", queries, n_queries, terms, roles, nullptr, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
+    return bs_sorted(ctx, "ns_search_sorted_boolean", queries, n_queries, terms, roles, nullptr, nullptr, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
                      keys_out, nhits_out, found_out, rest_out, device_ms_out);
 }
 
@@ -3338,12 +3380,27 @@ extern "C" int ns_search_sorted_grouped(ns_ctx* ctx, const ns_query_desc* querie
                                         const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after,
                                         const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out,
                                         uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
-    return bs_sorted(ctx, "ns_search_sorted_grouped", queries, n_queries, terms, roles, clauses, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
+    return bs_sorted(ctx, "ns_search_sorted_grouped", queries, n_queries, terms, roles, clauses, nullptr, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
+                     keys_out, nhits_out, found_out, rest_out, device_ms_out);
+}
+
+extern "C" int ns_facet_count_quorum(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                     const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs,
+                                     ns_facet* const* tables, uint32_t n_segs, uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
+    return bs_facet(ctx, "ns_facet_count_quorum", queries, n_queries, terms, roles, clauses, needs, n_terms, seg_ids, segs, tables, n_segs, counts_out, found_out, device_ms_out);
+}
+
+extern "C" int ns_search_sorted_quorum(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                       const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, uint32_t flags,
+                                       const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs,
+                                       ns_hit* hits_out, uint32_t* keys_out, uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out,
+                                       float* device_ms_out) {
+    return bs_sorted(ctx, "ns_search_sorted_quorum", queries, n_queries, terms, roles, clauses, needs, n_terms, k, flags, after, seg_ids, segs, keys, n_segs, hits_out,
                      keys_out, nhits_out, found_out, rest_out, device_ms_out);
 }
 
 static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                    const uint16_t* clauses, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
+                    const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, const uint32_t* seg_ids, ns_seg* const* segs, ns_facet* const* tables, uint32_t n_segs,
                     uint32_t* counts_out, uint64_t* found_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
@@ -3358,16 +3415,22 @@ static int bs_facet(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, u
     std::vector<BqRef> refs;
     std::vector<FcItem> items;
     std::string why;
+    const uint16_t* const given = clauses;
     clauses = bq_live_clauses(clauses, n_terms, roles);
-    const bool grouped = clauses != nullptr;
-    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+    if (!bq_live_needs(given, clauses, needs, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const bool grouped = clauses != nullptr, quorum = needs != nullptr;
+    uint32_t max_need = 0;
+    if (bq_plan_quorum(queries, n_queries, terms, roles, clauses, needs, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, max_need, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (quorum)
+        return run_count(ctx, fn, items, refs, dsegs, k_bs_count<true, true>, n_queries, tables[0]->n_buckets, false, &g_qq_ms[2], counts_out, found_out,
+                         device_ms_out, (size_t)bq_launch_planes(max_need) * (kFcTileDocs / 8u));
     return run_count(ctx, fn, items, refs, dsegs, grouped ? k_bs_count<true> : k_bs_count<false>, n_queries, tables[0]->n_buckets, false,
                      grouped ? &g_gq_ms[2] : &g_bs_ms[0], counts_out, found_out, device_ms_out);
 }
 
 static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
-                     const uint16_t* clauses, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
+                     const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, uint32_t flags, const ns_cursor* after, const uint32_t* seg_ids,
                      ns_seg* const* segs, ns_dockeys* const* keys, uint32_t n_segs, ns_hit* hits_out, uint32_t* keys_out,
                      uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
@@ -3387,21 +3450,27 @@ static int bs_sorted(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     std::vector<FcItem> items;
     RankedPlan plan;
     std::string why;
+    const uint16_t* const given = clauses;
     clauses = bq_live_clauses(clauses, n_terms, roles);
-    const bool grouped = clauses != nullptr;
-    if (bq_plan_grouped(queries, n_queries, terms, roles, clauses, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, why) != NS_OK)
+    if (!bq_live_needs(given, clauses, needs, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const bool grouped = clauses != nullptr, quorum = needs != nullptr;
+    uint32_t max_need = 0;
+    if (bq_plan_quorum(queries, n_queries, terms, roles, clauses, needs, n_terms, views.data(), n_segs, ns_facet_tile_docs(), refs, items, max_need, why) != NS_OK)
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (!ranked_call_plan(items, n_queries, k, after, views, [asc](uint32_t key) { return after_sort_rank(key, asc != 0u); }, true, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    static const SelectKernel<BqRef, DevSdSeg> kSelect[2][2] = {{k_bs_select<false, false>, k_bs_select<true, false>},
-                                                                {k_bs_select<false, true>, k_bs_select<true, true>}};   // [grouped][paged]
+    static const SelectKernel<BqRef, DevSdSeg> kSelect[3][2] = {{k_bs_select<false, false>, k_bs_select<true, false>},
+                                                                {k_bs_select<false, true>, k_bs_select<true, true>},
+                                                                {k_bs_select<false, true, true>, k_bs_select<true, true, true>}};   // [boolean, grouped, quorum][paged]
     const uint32_t K = plan.K;
     RankedCall<BqRef, DevSdSeg> c{items, refs, dsegs, sds, plan, n_queries};
-    c.select = kSelect[grouped][plan.paged];
+    c.select = kSelect[quorum ? 2 : grouped][plan.paged];
     c.select_arg = asc;
+    if (quorum && (c.select_lds = (size_t)bq_launch_planes(max_need) * (kFcTileDocs / 8u)) != 0)   // (the quorum planes: past the default with the static 36 KiB)
+        c.before = hipFuncSetAttribute(reinterpret_cast<const void*>(c.select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.select_lds);
     c.stages = 3;
-    c.ms_acc = grouped ? g_gq_ms + 3 : g_bs_ms + 1;
+    c.ms_acc = quorum ? g_qq_ms + 3 : grouped ? g_gq_ms + 3 : g_bs_ms + 1;
     c.queries = queries; c.terms = terms; c.n_terms = n_terms; c.roles = roles; c.roles_region = true;
     c.hits_out = hits_out; c.keys_out = keys_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
     return run_ranked(ctx, fn, c, [=](const RankedDev<BqRef, DevSdSeg>& d, const SdBatch& b, hipStream_t st) { sd_launch_join(d, b, K, asc, st); },
@@ -3998,6 +4067,8 @@ extern "C" int ns_debug_after_counters(unsigned long long* out, int reset) { ret
 extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBcnt>(HIP_SYMBOL(ns::g_ns_bcnt), out, reset); }
 // the grouped required stage (ns_boolean.hip k_bq_select<., true>; ns_boolean_sets.hip bs_matched<true>): 11 values
 extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBgcnt>(HIP_SYMBOL(ns::g_ns_bgcnt), out, reset); }
+// the quorum required stage (ns_boolean.hip k_bq_select<., ., true>; ns_boolean_sets.hip bs_matched<., true>): 12 values
+extern "C" int ns_debug_boolean_quorum_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBqcnt>(HIP_SYMBOL(ns::g_ns_bqcnt), out, reset); }
 // facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values
 extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBscnt>(HIP_SYMBOL(ns::g_ns_bscnt), out, reset); }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values

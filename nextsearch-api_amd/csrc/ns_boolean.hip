@@ -58,10 +58,18 @@ __device__ unsigned long long g_ns_bcnt[kNsBcnt];
 constexpr int kNsBgcnt = 11;
 __device__ unsigned long long g_ns_bgcnt[kNsBgcnt];
 #define NS_BGCNT(i, v) do { if (GROUPED && threadIdx.x == 0) atomicAdd(&g_ns_bgcnt[(i)], (unsigned long long)(v)); } while (0)
+// At-least-m-of-n clauses (§5w; ns_debug_boolean_quorum_counters), the QUORUM instantiations only.  k_bq_select<., ., true>: 0 work
+// items; then, counted per window, 1 clauses counted (need > 1), 2 list additions into the planes, 3 additions that saturated a
+// bit, 4 windows ended because fewer lists of a clause hit than it needs, 5 non-counting duplicates skipped.  The set kernels
+// (ns_boolean_sets.hip): 6 work items; 7..11 as 1..5, counted per tile (= per item).
+constexpr int kNsBqcnt = 12;
+__device__ unsigned long long g_ns_bqcnt[kNsBqcnt];
+#define NS_BQCNT(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_ns_bqcnt[(i)], (unsigned long long)(v)); } while (0)
 #else
 #define NS_BCNT(i, v)
 #define NS_BCNT_WAVE(i, v)
 #define NS_BGCNT(i, v)
+#define NS_BQCNT(i, v)
 #endif
 
 __device__ __forceinline__ uint32_t bq_ord(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
@@ -152,9 +160,126 @@ __device__ __forceinline__ bool bq_mark_clauses(const DevFcSeg& sg, const BqRef*
     return true;
 }
 
+// The quorum required stage (§5w): bq_mark_clauses with a need per clause (bq_clause_need of the members' BqRef::clause, the same in
+// all of them: bq_plan_quorum), over the same range, with the same callers' contract: workgroup-uniform, false (in every thread)
+// when a clause cannot hold in the range, s_tmp clear on return either way.  `mine` holds the lane's whole clause word.
+//   need 1   bq_mark_clauses' path: the clause's lists mark its bitmap directly
+//   need m   every counting list with a posting in the range is marked into s_tmp with fc_mark; a barrier; a word-wise pass adds
+//            the scratch word into the p = bq_need_planes(m) bit-sliced counter planes (plane i holds bit i of every document's
+//            count) with a ripple-carry add that SATURATES: a carry out of the top plane sets all planes for those bits, so a count
+//            stays at 2^p - 1 >= m; the pass clears the scratch word; a second barrier.  After the last list a word-wise compare
+//            of the planes against m gives the clause's set, which becomes s_bm for c = 0 and is AND-ed into it afterwards.
+// A ref with kBqDupBit is skipped: an earlier ref of the clause named its list.  Fewer than m counting lists with a posting in the
+// range end it (m = 1: "no list hits").  The planes (s_pl: p arrays, `stride` words apart) are cleared before a clause counts into
+// them, so nothing is assumed about what an earlier clause, window or early exit left there; words past n_words are never touched.
+// BASE: the first of the five counters (ns_debug_boolean_quorum_counters) of the caller.
+template <int BASE>
+__device__ __forceinline__ bool bq_count_clauses(const DevFcSeg& sg, const BqRef* __restrict__ rf, uint32_t ref_count, uint32_t n_clauses,
+                                                 uint32_t mine, uint32_t doc_lo, uint32_t doc_hi, uint32_t n_words, uint32_t* s_bm,
+                                                 uint32_t* s_tmp, uint32_t* s_pl, uint32_t stride) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t from = 0;
+    for (uint32_t c = 0; c < n_clauses; c++) {
+        unsigned long long members = 0ull;   // at most 64 refs: the clause's refs (wave-uniform, and the same in all four waves)
+        uint32_t need = 1u;
+        if (ref_count <= 64u) {
+            members = __ballot(mine != kBqNoClause && bq_clause_index(mine) == c);
+            if (!members) return false;      // (never: the indices are dense)
+            need = bq_clause_need(rf[(uint32_t)__builtin_ctzll(members)].clause);
+        } else {
+            while (from < ref_count && !(rf[from].role == kBqMust && bq_clause_index(rf[from].clause) == c)) from++;
+            if (from == ref_count) return false;   // (never)
+            need = bq_clause_need(rf[from].clause);
+        }
+        const uint32_t planes = bq_need_planes(need);   // 0, 2 or 3 (workgroup-uniform, as `need`)
+        uint32_t* const bm = c == 0u ? s_bm : s_tmp;
+        uint32_t hit = 0, skipped = 0;
+        if (planes) {
+            for (uint32_t i = 0; i < planes; i++)
+                for (uint32_t w = tid; w < n_words; w += 256u) s_pl[i * stride + w] = 0u;
+            NS_BQCNT(BASE, 1);
+        }
+        // one list of the clause (workgroup-uniform)
+        auto take = [&](const BqRef& b) {
+            if (b.clause & kBqDupBit) { skipped++; return; }
+            uint64_t lo, hi;
+            fc_cut(sg, b.list, doc_lo, doc_hi, lane, lo, hi);
+            if (lo == hi) return;
+            hit++;
+            if (!planes) { fc_mark(sg.postings, lo, hi, doc_lo, doc_hi, bm); return; }
+            fc_mark(sg.postings, lo, hi, doc_lo, doc_hi, s_tmp);
+            __syncthreads();
+            bool full = false;
+            for (uint32_t w = tid; w < n_words; w += 256u) {
+                uint32_t carry = s_tmp[w];
+                if (!carry) continue;
+                s_tmp[w] = 0u;
+                for (uint32_t i = 0; i < planes; i++) {
+                    const uint32_t x = s_pl[i * stride + w];
+                    s_pl[i * stride + w] = x ^ carry;
+                    carry &= x;
+                }
+                if (carry) {   // these documents were at 2^p - 1: they stay there
+                    full = true;
+                    for (uint32_t i = 0; i < planes; i++) s_pl[i * stride + w] |= carry;
+                }
+            }
+#ifdef NS_COUNT
+            if (__syncthreads_or(full ? 1 : 0)) NS_BQCNT(BASE + 2, 1);
+            NS_BQCNT(BASE + 1, 1);
+#else
+            (void)full;
+            __syncthreads();
+#endif
+        };
+        if (ref_count <= 64u) {
+            while (members) {
+                const uint32_t r = (uint32_t)__builtin_ctzll(members);
+                members &= members - 1ull;
+                take(rf[r]);
+            }
+        } else {
+            uint32_t next = ref_count;
+            for (uint32_t r = from; r < ref_count; r++) {
+                const BqRef b = rf[r];
+                if (b.role != kBqMust) continue;
+                const uint32_t at = bq_clause_index(b.clause);
+                if (at != c) { if (at == c + 1u && next == ref_count) next = r; continue; }
+                take(b);
+            }
+            from = next;
+        }
+        if (skipped) NS_BQCNT(BASE + 4, skipped);
+        if (hit < need) { NS_BQCNT(BASE + 3, 1); return false; }   // (workgroup-uniform: the cuts depend on the item and the range alone)
+        if (planes) {
+            for (uint32_t w = tid; w < n_words; w += 256u) {
+                uint32_t ge = 0xFFFFFFFFu;   // count >= need, from the lowest bit up
+                for (uint32_t i = 0; i < planes; i++) {
+                    const uint32_t x = s_pl[i * stride + w];
+                    ge = ((need >> i) & 1u) ? (x & ge) : (x | ge);
+                }
+                s_bm[w] = c ? (s_bm[w] & ge) : ge;
+            }
+            __syncthreads();
+        } else {
+            __syncthreads();
+            if (c) {
+                for (uint32_t w = tid; w < n_words; w += 256u) {
+                    s_bm[w] &= s_tmp[w];
+                    s_tmp[w] = 0u;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    return true;
+}
+
 // Dynamic LDS, and no static LDS in front of it, so that the 8-byte rows stay aligned: 4 KiB row exchange, then win x 4 B
 // accumulators, then three bitmaps of win / 8 B, then the item's matched count.
 __host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (size_t)win * 4u + 3u * (size_t)(win / 8u) + 16u; }
+// QUORUM (§5w): the counter planes follow, win / 8 B each, as many as the launch's largest need asks for (none when it is 1)
+__host__ __device__ inline size_t bq_quorum_lds_bytes(uint32_t win, uint32_t planes) { return bq_lds_bytes(win) + (size_t)planes * (win / 8u); }
 
 // AFTER (§5s, ns_after.hip): last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
 // rest[query] through the word behind s_cnt.  With AFTER = false neither pointer is read and the code is what it was without
@@ -162,7 +287,9 @@ __host__ __device__ inline size_t bq_lds_bytes(uint32_t win) { return 4096u + (s
 // GROUPED (§5u): the MUST refs carry a clause index (BqRef::clause, dense per group: bq_plan_grouped), and the required stage
 // of a window is bq_mark_clauses: a clause NONE of whose lists has a posting in the window ends the window.  With GROUPED = false
 // the code is what it was without the parameter.
-template <bool AFTER, bool GROUPED = false>
+// QUORUM (§5w; implies GROUPED): BqRef::clause is bq_plan_quorum's word, and the required stage of a window is bq_count_clauses
+// over the counter planes behind bq_lds_bytes(win).  With QUORUM = false the code is what it was without the parameter.
+template <bool AFTER, bool GROUPED = false, bool QUORUM = false>
 __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
                                                    uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -175,6 +302,7 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     uint32_t* s_ex = s_tmp + win / 32u;
     uint32_t& s_cnt = s_ex[win / 32u];
     uint32_t& s_rest = s_ex[win / 32u + 1u];   // (inside bq_lds_bytes' last 16 bytes)
+    uint32_t* const s_pl = reinterpret_cast<uint32_t*>(s_raw + bq_lds_bytes(win));   // QUORUM: the planes, if the launch has any
     const FcItem it = items[blockIdx.x];
     const DevFcSeg sg = segs[it.seg];
     const float* __restrict__ norm = bqs[it.seg].norm;
@@ -195,10 +323,11 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
         const uint32_t role = rf[r].role;
         n_must += role == kBqMust;
         n_not += role == kBqNot;
-        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, rf[r].clause + 1u);
+        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, (QUORUM ? bq_clause_index(rf[r].clause) : rf[r].clause) + 1u);
     }
     const uint32_t my_clause = GROUPED ? bq_clause_of_lane(rf, it.ref_count, lane) : 0u;   // (once per item, not per window)
     NS_BGCNT(0, 1);
+    if (QUORUM) NS_BQCNT(0, 1);
     SdSet set{0ull, 0ull};
     uint32_t cnt = 0;
     const uint32_t tile_n = it.doc_hi - it.doc_lo;   // <= kFcTileDocs: the tile is the host's
@@ -216,7 +345,9 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
         __syncthreads();
         NS_BCNT(1, 1);
         bool alive = true;   // workgroup-uniform: the cuts depend on the item and the window alone
-        if (GROUPED && n_must) {
+        if (QUORUM && n_must) {
+            alive = bq_count_clauses<1>(sg, rf, it.ref_count, n_clauses, my_clause, w_lo, w_hi, n_words, s_bm, s_tmp, s_pl, win / 32u);
+        } else if (GROUPED && n_must) {
             alive = bq_mark_clauses<1>(sg, rf, it.ref_count, n_clauses, my_clause, w_lo, w_hi, n_words, s_bm, s_tmp);
         } else if (n_must) {
             uint32_t seen = 0;

@@ -66,9 +66,11 @@ __device__ __forceinline__ void bs_insert(SdSet& s, uint64_t key, uint32_t K, ui
 // (in every thread) when a MUST list has no posting in the tile: the item matches nothing and s_bm is not to be read.
 // GROUPED (§5u): the required stage is ns_boolean.hip's bq_mark_clauses over the tile, as k_bq_select<., true>'s is over a window;
 // false when a clause has no posting in the tile.  The scratch bitmap is clear when the NOT lists arrive, as before.
-template <bool GROUPED>
+// QUORUM (§5w; implies GROUPED): the required stage is bq_count_clauses over the tile; s_pl: the counter planes, kFcTileDocs / 32
+// words each (dynamic LDS behind the static bitmaps; NULL-like and never touched when the launch's needs are all 1).
+template <bool GROUPED, bool QUORUM = false>
 __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg, const BqRef* __restrict__ rf, uint32_t n_words,
-                                           uint32_t* s_bm, uint32_t* s_tmp) {
+                                           uint32_t* s_bm, uint32_t* s_tmp, uint32_t* s_pl = nullptr) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t w = tid; w < n_words; w += 256u) {
         s_bm[w] = 0u;
@@ -80,11 +82,13 @@ __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg,
         const uint32_t role = rf[r].role;
         n_must += role == kBqMust;
         n_not += role == kBqNot;
-        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, rf[r].clause + 1u);
+        if (GROUPED && role == kBqMust) n_clauses = max(n_clauses, (QUORUM ? bq_clause_index(rf[r].clause) : rf[r].clause) + 1u);
     }
     const uint32_t my_clause = GROUPED ? bq_clause_of_lane(rf, it.ref_count, lane) : 0u;
     __syncthreads();
-    if (GROUPED && n_must) {
+    if (QUORUM && n_must) {
+        if (!bq_count_clauses<7>(sg, rf, it.ref_count, n_clauses, my_clause, it.doc_lo, it.doc_hi, n_words, s_bm, s_tmp, s_pl, kFcTileDocs / 32u)) return false;
+    } else if (GROUPED && n_must) {
         if (!bq_mark_clauses<6>(sg, rf, it.ref_count, n_clauses, my_clause, it.doc_lo, it.doc_hi, n_words, s_bm, s_tmp)) return false;
     } else if (n_must) {
         uint32_t seen = 0;
@@ -147,12 +151,13 @@ __device__ __forceinline__ bool bs_matched(const FcItem& it, const DevFcSeg& sg,
     return true;
 }
 
-template <bool GROUPED = false>
+template <bool GROUPED = false, bool QUORUM = false>
 __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                   const DevFcSeg* __restrict__ segs, uint32_t n_buckets, uint32_t* __restrict__ counts) {
     __shared__ uint32_t s_hist[kFcMaxBuckets];
     __shared__ uint32_t s_bm[kFcTileDocs / 32u];
     __shared__ uint32_t s_tmp[kFcTileDocs / 32u];
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_bs_planes[];   // QUORUM: 16 KiB per plane of the launch, else none
     const FcItem it = items[blockIdx.x];
     const DevFcSeg sg = segs[it.seg];
     const BqRef* __restrict__ rf = refs + it.ref_begin;
@@ -160,6 +165,7 @@ __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ ite
     const uint32_t n_words = (it.doc_hi - it.doc_lo + 31u) / 32u;   // <= kFcTileDocs / 32: the tile is the host's, at most the product's
     NS_BSCNT(0, 1);
     NS_BGCNT(5, 1);
+    if (QUORUM) NS_BQCNT(6, 1);
     for (uint32_t b = tid; b < n_buckets; b += 256u) s_hist[b] = 0u;
     if (it.ref_count == 1u) {
         uint64_t lo, hi;
@@ -172,7 +178,7 @@ __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ ite
             if (d >= it.doc_lo && d < it.doc_hi) atomicAdd(&s_hist[sg.buckets[d]], 1u);
         }
     } else {
-        if (!bs_matched<GROUPED>(it, sg, rf, n_words, s_bm, s_tmp)) return;   // (workgroup-uniform; the histogram is all zero)
+        if (!bs_matched<GROUPED, QUORUM>(it, sg, rf, n_words, s_bm, s_tmp, QUORUM ? s_bs_planes : nullptr)) return;   // (workgroup-uniform; the histogram is all zero)
         for (uint32_t w = tid; w < n_words; w += 256u) {
             uint32_t bits = s_bm[w];
             while (bits) {
@@ -198,7 +204,7 @@ __global__ void __launch_bounds__(256) k_bs_count(const FcItem* __restrict__ ite
 // AFTER as in k_sd_select: last[blockIdx.x] bounds the keys that may enter, and the item's count of such keys goes into
 // rest[query].  Wave 0's own slot of s_rows is never read back, so under AFTER it is not written and its first word holds the
 // item's count instead.  With AFTER = false neither pointer is read.
-template <bool AFTER, bool GROUPED = false>
+template <bool AFTER, bool GROUPED = false, bool QUORUM = false>
 __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevSdSeg* __restrict__ sds, uint32_t K,
                                                    uint32_t asc, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -207,6 +213,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
     __shared__ uint32_t s_tmp[kFcTileDocs / 32u];
     __shared__ uint64_t s_rows[4][128];
     __shared__ uint32_t s_cnt;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_bs_planes[];   // QUORUM: 16 KiB per plane of the launch, else none
     const FcItem it = items[blockIdx.x];
     const DevFcSeg sg = segs[it.seg];
     const BqRef* __restrict__ rf = refs + it.ref_begin;
@@ -215,6 +222,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
     const uint32_t n_words = (it.doc_hi - it.doc_lo + 31u) / 32u;   // <= kFcTileDocs / 32: the tile is the host's, at most the product's
     NS_BSCNT(0, 1);
     NS_BGCNT(5, 1);
+    if (QUORUM) NS_BQCNT(6, 1);
     if (tid == 0) s_cnt = 0u;
     uint32_t* const s_rest = reinterpret_cast<uint32_t*>(&s_rows[0][0]);
     uint64_t last = kAfterAll;
@@ -241,7 +249,7 @@ __global__ void __launch_bounds__(256) k_bs_select(const FcItem* __restrict__ it
             if (AFTER) key = af_clip(key, last, kept);
             bs_insert(set, key, K, lane);
         }
-    } else if (bs_matched<GROUPED>(it, sg, rf, n_words, s_bm, s_tmp)) { // (workgroup-uniform)
+    } else if (bs_matched<GROUPED, QUORUM>(it, sg, rf, n_words, s_bm, s_tmp, QUORUM ? s_bs_planes : nullptr)) { // (workgroup-uniform)
         for (uint32_t wb = v * 64u; wb < n_words; wb += 256u) {         // (wave-uniform)
             const uint32_t w = wb + lane;
             uint32_t bits = w < n_words ? s_bm[w] : 0u;

@@ -2403,29 +2403,29 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
 // ---- boolean queries (host/boolean.hpp, csrc/ns_boolean.hip) -------------------------------------------
 bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
                                        uint64_t* found, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_batch_flat", false, filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
+    return boolean_batch_impl("search_boolean_batch_flat", kDialectBoolean, filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
 }
 
 bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                                              uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_after_batch_flat", false, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+    return boolean_batch_impl("search_boolean_after_batch_flat", kDialectBoolean, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
 }
 
 // ---- any-of groups in boolean queries (host/grouped.hpp) -------------------------------------------------
 bool Engine::search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                                              uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_grouped_after_batch_flat", true, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+    return boolean_batch_impl("search_grouped_after_batch_flat", kDialectGrouped, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
 }
 
 bool Engine::facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
                                       uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    return boolean_facet_impl("facet_grouped_batch_flat", true, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+    return boolean_facet_impl("facet_grouped_batch_flat", kDialectGrouped, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
 }
 
 bool Engine::search_grouped_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                                               const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                               uint8_t* usable, float* device_ms) {
-    return boolean_sorted_impl("search_grouped_sorted_batch_flat", true, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+    return boolean_sorted_impl("search_grouped_sorted_batch_flat", kDialectGrouped, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
 }
 
 // boolean_refs_range over parse_grouped's dialect, with the clause id of every ref next to its role; false, with a message, when
@@ -2523,8 +2523,9 @@ void Engine::boolean_refs_range(const QueryView* queries, size_t a, size_t b, ui
     }
 }
 
-bool Engine::boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+bool Engine::boolean_batch_impl(const char* fn, int dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
                                 ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
@@ -2540,7 +2541,7 @@ bool Engine::boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_ha
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
         if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
+        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
         if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
@@ -2550,13 +2551,16 @@ bool Engine::boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_ha
             continue;
         }
         float ms = 0.0f;
-        const int rc = grouped ? ns_search_grouped_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+        const int rc = quorum  ? ns_search_quorum_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
+                                                        (uint32_t)bp.refs.size(), (uint32_t)K, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
+                                                        (uint32_t)bp.ids.size(), hits + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
+                       : grouped ? ns_search_grouped_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
                                                          (uint32_t)bp.refs.size(), (uint32_t)K, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
                                                          (uint32_t)bp.ids.size(), hits + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
                                : ns_search_boolean_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
                                                          cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * K, nhits + a,
                                                          found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_search_grouped_after: " : after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
+        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_search_quorum_after: " : grouped ? "ns_search_grouped_after: " : after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
@@ -2636,16 +2640,157 @@ static bool grouped_insert(std::string& tail, const std::string& query) {
     return true;
 }
 
+// the "quorum" member of search_quorum's body (§5w): "min_should" is the `~m` piece's m (0: none); "must" lists the clauses, each
+// {"need": n, "terms": [...]}, in query order, WITHOUT the clause the `~m` piece made: its terms stay under "should", where
+// "min_should" says how many of them a document must hold.  "query" < "quorum" < "results": the member stands behind "query".
+static std::string quorum_member(const std::string& query) {
+    uint32_t min_should = 0;
+    const std::vector<nsx::QuorumTerm> terms = nsx::parse_quorum(query, &min_should);
+    std::string o = "  \"quorum\": {\n    \"min_should\": " + std::to_string(min_should) + ",\n    \"must\": [";
+    bool any_clause = false;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (terms[i].role != nsx::kRoleMust || terms[i].promoted) continue;
+        bool first_of_clause = true;
+        for (size_t j = 0; j < i; j++) first_of_clause = first_of_clause && !(terms[j].role == nsx::kRoleMust && !terms[j].promoted && terms[j].clause == terms[i].clause);
+        if (!first_of_clause) continue;
+        o += any_clause ? ",\n      {" : "\n      {";
+        o += "\n        \"need\": " + std::to_string(terms[i].need) + ",\n        \"terms\": [";
+        bool any = false;
+        for (size_t j = i; j < terms.size(); j++)
+            if (terms[j].role == nsx::kRoleMust && !terms[j].promoted && terms[j].clause == terms[i].clause) {
+                o += any ? ",\n          " : "\n          ";
+                json_escape(o, terms[j].text);
+                any = true;
+            }
+        o += "\n        ]\n      }";
+        any_clause = true;
+    }
+    o += any_clause ? "\n    ],\n" : "],\n";
+    for (int m = 0; m < 2; m++) {
+        o += std::string("    \"") + (m ? "should" : "must_not") + "\": [";
+        bool any = false;
+        for (const nsx::QuorumTerm& t : terms)
+            if (m ? (t.role == nsx::kRoleShould || t.promoted) : t.role == nsx::kRoleNot) {
+                o += any ? ",\n      " : "\n      ";
+                json_escape(o, t.text);
+                any = true;
+            }
+        o += any ? "\n    ]" : "]";
+        o += m < 1 ? ",\n" : "\n";
+    }
+    o += "  },\n";
+    return o;
+}
+
+// tail: to_json_impl's members; "query" is escaped, so the first line that starts like the "results" member is it
+static bool quorum_insert(std::string& tail, const std::string& query) {
+    const size_t at = tail.find("\n  \"results\": ");
+    if (at == std::string::npos) return false;
+    tail.insert(at + 1, quorum_member(query));
+    return true;
+}
+
+// ---- at-least-m-of-n clauses (host/quorum.hpp) -----------------------------------------------------------
+bool Engine::search_quorum_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl("search_quorum_after_batch_flat", kDialectQuorum, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_quorum_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                     uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    return boolean_facet_impl("facet_quorum_batch_flat", kDialectQuorum, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::search_quorum_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                             uint8_t* usable, float* device_ms) {
+    return boolean_sorted_impl("search_quorum_sorted_batch_flat", kDialectQuorum, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+// grouped_refs_range over parse_quorum's dialect, with the need of every ref next to its clause id: an unknown member is dropped
+// (a ref with count == 0) and the need stays.  False, with a message, when a query has more clauses than a clause value can name
+// or asks for more than kQuorumMaxNeed of a clause's terms.
+bool Engine::quorum_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
+    const uint32_t S = (uint32_t)segments.size();
+    const nsx::RowSource& rs = bp.rs;
+    bp.qd.assign(b - a, ns_query_desc{0, 0});
+    bp.refs.clear();
+    bp.roles.clear();
+    bp.clauses.clear();
+    bp.needs.clear();
+    for (size_t q = a; q < b; q++) {
+        bp.terms.clear();
+        bp.term_clauses.clear();
+        bp.term_needs.clear();
+        uint32_t largest = 0;
+        const nsx::QuorumShape shape = nsx::for_each_quorum_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
+            bp.terms.emplace_back(dict.find(p, n), role);
+            bp.term_clauses.push_back(clause);
+            bp.term_needs.push_back(need);
+            largest = std::max(largest, need);
+        });
+        uint32_t n_clauses = shape.n_clauses;
+        if (shape.min_should) {   // `~m`: every optional term joins one more required clause of need m
+            bool any = false;
+            for (size_t i = 0; i < bp.terms.size(); i++)
+                if (bp.terms[i].second == nsx::kRoleShould) {
+                    bp.terms[i].second = nsx::kRoleMust;
+                    bp.term_clauses[i] = shape.n_clauses;
+                    bp.term_needs[i] = shape.min_should;
+                    any = true;
+                }
+            if (any) n_clauses++;
+            largest = std::max(largest, shape.min_should);   // refused above the limit whether or not a term is there to promote
+        }
+        if (n_clauses > 65535u) { err_ = std::string(fn) + ": query " + std::to_string(q) + " has " + std::to_string(n_clauses) + " required clauses (at most 65535)"; return false; }
+        if (largest > nsx::kQuorumMaxNeed) {
+            err_ = std::string(fn) + ": query " + std::to_string(q) + " asks for " + std::to_string(largest) + " of a clause's terms (at most " + std::to_string(nsx::kQuorumMaxNeed) + ")";
+            return false;
+        }
+        size_t positive = 0;
+        for (const auto& t : bp.terms) positive += t.second != nsx::kRoleNot;
+        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
+        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
+        if (!usable[q]) continue;
+        for (const uint32_t sid : bp.listed)
+            for (size_t i = 0; i < bp.terms.size(); i++) {
+                const auto& t = bp.terms[i];
+                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
+                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                else if (t.second == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
+                else continue;
+                bp.roles.push_back(t.second);
+                bp.clauses.push_back((uint16_t)bp.term_clauses[i]);
+                bp.needs.push_back((uint8_t)bp.term_needs[i]);
+            }
+        bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
+    }
+    return true;
+}
+
+bool Engine::search_quorum_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return boolean_text_impl("search_quorum", kDialectQuorum, query, k, f, body);
+}
+
+bool Engine::search_quorum_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_faceted_text_impl("search_quorum_faceted", kDialectQuorum, query, k, spec, f, body);
+}
+
+bool Engine::search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return boolean_sorted_text_impl("search_quorum_sorted", kDialectQuorum, query, k, spec, f, body);
+}
+
 bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    return boolean_text_impl("search_boolean", false, query, k, f, body);
+    return boolean_text_impl("search_boolean", kDialectBoolean, query, k, f, body);
 }
 
 bool Engine::search_grouped_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    return boolean_text_impl("search_grouped", true, query, k, f, body);
+    return boolean_text_impl("search_grouped", kDialectGrouped, query, k, f, body);
 }
 
 // search_boolean's body, or (grouped) the same body over parse_grouped's dialect with "grouped" in place of "boolean"
-bool Engine::boolean_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+bool Engine::boolean_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
     const int K = std::max(1, std::min(k, 100));
@@ -2664,8 +2809,9 @@ bool Engine::boolean_text_impl(const char* name, bool grouped, const std::string
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(grouped ? search_grouped_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
-                  : search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us))) { body = err_; return false; }
+    if (!(quorum    ? search_quorum_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
+          : grouped ? search_grouped_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
+                    : search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us))) { body = err_; return false; }
     SearchResult res;
     res.query = query;
     res.k = K;
@@ -2677,7 +2823,7 @@ bool Engine::boolean_text_impl(const char* name, bool grouped, const std::string
     // "boolean" < "filter" < "found": nlohmann keeps keys sorted, so the member sits in front
     if (!grouped) { body = "{\n" + boolean_member(query) + head.substr(2) + to_json_impl(res).substr(2); return true; }
     std::string tail = to_json_impl(res).substr(2);
-    if (!grouped_insert(tail, query)) { body = err_ = std::string(name) + ": the search body has no k member"; return false; }
+    if (quorum ? !quorum_insert(tail, query) : !grouped_insert(tail, query)) { body = err_ = std::string(name) + ": the search body has no " + (quorum ? "results" : "k") + " member"; return false; }
     body = head + tail;
     return true;
 }
@@ -2687,6 +2833,21 @@ static std::string error_body(const std::string& why) {
     json_escape(o, why);
     o += "\n}";
     return o;
+}
+
+std::string Engine::search_quorum(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    return search_quorum_text(query, k, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_quorum_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_quorum_faceted_text(query, k, spec, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_quorum_sorted_text(query, k, spec, f, body) ? body : error_body(body);
 }
 
 std::string Engine::search_grouped(const std::string& query, int k, const nsx::DocFilter* f) {
@@ -2705,11 +2866,11 @@ std::string Engine::search_grouped_sorted(const std::string& query, int k, const
 }
 
 bool Engine::search_grouped_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_faceted_text_impl("search_grouped_faceted", true, query, k, spec, f, body);
+    return boolean_faceted_text_impl("search_grouped_faceted", kDialectGrouped, query, k, spec, f, body);
 }
 
 bool Engine::search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_sorted_text_impl("search_grouped_sorted", true, query, k, spec, f, body);
+    return boolean_sorted_text_impl("search_grouped_sorted", kDialectGrouped, query, k, spec, f, body);
 }
 
 std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
@@ -2726,11 +2887,12 @@ std::string Engine::search_boolean(const std::string& query, int k, const nsx::D
 // ---- facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip) --------------------------
 bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
                                       uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    return boolean_facet_impl("facet_boolean_batch_flat", false, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+    return boolean_facet_impl("facet_boolean_batch_flat", kDialectBoolean, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
 }
 
-bool Engine::boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+bool Engine::boolean_facet_impl(const char* fn, int dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
                                 std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     counts.clear();
     labels.clear();
@@ -2755,18 +2917,21 @@ bool Engine::boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSp
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
         if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
+        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
             continue;
         }
         float ms = 0.0f;
-        const int rc = grouped ? ns_facet_count_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+        const int rc = quorum  ? ns_facet_count_quorum(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
+                                                       (uint32_t)bp.refs.size(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
+                                                       counts.data() + a * B, found + a, &ms)
+                       : grouped ? ns_facet_count_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
                                                         (uint32_t)bp.refs.size(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
                                                         counts.data() + a * B, found + a, &ms)
                                : ns_facet_count_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), bp.ids.data(),
                                                         bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
-        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_facet_count_grouped: " : "ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
+        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_facet_count_quorum: " : grouped ? "ns_facet_count_grouped: " : "ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
     }
     return true;
@@ -2775,12 +2940,13 @@ bool Engine::boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSp
 bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                                               const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                               uint8_t* usable, float* device_ms) {
-    return boolean_sorted_impl("search_boolean_sorted_batch_flat", false, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+    return boolean_sorted_impl("search_boolean_sorted_batch_flat", kDialectBoolean, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
 }
 
-bool Engine::boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+bool Engine::boolean_sorted_impl(const char* fn, int dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                                  const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
                                  float* device_ms) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
@@ -2803,7 +2969,7 @@ bool Engine::boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSp
     for (size_t i = 0; i < n_sub; i++) {
         const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
         if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!grouped_refs_range(fn, queries, a, b, usable, bp)) return false;
+        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
         if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
@@ -2814,14 +2980,18 @@ bool Engine::boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSp
             continue;
         }
         float ms = 0.0f;
-        const int rc = grouped ? ns_search_sorted_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
+        const int rc = quorum  ? ns_search_sorted_quorum(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
+                                                         (uint32_t)bp.refs.size(), (uint32_t)K, spec.ascending ? NS_SORT_ASC : NS_SORT_DESC,
+                                                         cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
+                                                         hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
+                       : grouped ? ns_search_sorted_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
                                                           (uint32_t)bp.refs.size(), (uint32_t)K, spec.ascending ? NS_SORT_ASC : NS_SORT_DESC,
                                                           cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
                                                           hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
                                : ns_search_sorted_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
                                                           spec.ascending ? NS_SORT_ASC : NS_SORT_DESC, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
                                                           tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(grouped ? "ns_search_sorted_grouped: " : "ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
+        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_search_sorted_quorum: " : grouped ? "ns_search_sorted_grouped: " : "ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         for (size_t q = a; q < b; q++)
             for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
@@ -2830,21 +3000,22 @@ bool Engine::boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSp
 }
 
 bool Engine::search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_faceted_text_impl("search_boolean_faceted", false, query, k, spec, f, body);
+    return boolean_faceted_text_impl("search_boolean_faceted", kDialectBoolean, query, k, spec, f, body);
 }
 
-bool Engine::boolean_faceted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
+bool Engine::boolean_faceted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
                                        std::string& body) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
-    if (!(grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
+    if (!(quorum ? search_quorum_text(query, k, f, body) : grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const QueryView qv{query.data(), query.size()};
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(grouped ? facet_grouped_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels))) { body = err_; return false; }
+    if (!(quorum ? facet_quorum_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : grouped ? facet_grouped_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels))) { body = err_; return false; }
     // "boolean" < "facets" < "filter" < "found": the member goes behind the "boolean" member, which is the body's first and whose
     // strings are escaped, so that its closing line is the first of that form
     const size_t at = body.find("\n  },\n");
@@ -2869,14 +3040,15 @@ std::string Engine::search_boolean_faceted(const std::string& query, int k, cons
 }
 
 bool Engine::search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_sorted_text_impl("search_boolean_sorted", false, query, k, spec, f, body);
+    return boolean_sorted_text_impl("search_boolean_sorted", kDialectBoolean, query, k, spec, f, body);
 }
 
-bool Engine::boolean_sorted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
+bool Engine::boolean_sorted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
                                       std::string& body) {
+    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
-    if (!(grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
+    if (!(quorum ? search_quorum_text(query, k, f, body) : grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const size_t K = (size_t)std::max(1, std::min(k, 100));
     const QueryView qv{query.data(), query.size()};
@@ -2885,7 +3057,8 @@ bool Engine::boolean_sorted_text_impl(const char* name, bool grouped, const std:
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(grouped ? search_grouped_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
+    if (!(quorum    ? search_quorum_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
+          : grouped ? search_grouped_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
                   : search_boolean_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us))) { body = err_; return false; }
     std::vector<SearchHit> sorted;
     if (us)
@@ -3001,7 +3174,7 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
-    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::GroupedSorted) { body = err_ = "search_page: unknown mode"; return false; }
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::QuorumSorted) { body = err_ = "search_page: unknown mode"; return false; }
     const char kind = nsx::page_kind(spec.mode);
     nsx::PageCursor cur;
     if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
@@ -3043,6 +3216,12 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
         case nsx::PageSpec::GroupedSorted:
             ok = search_grouped_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
             break;
+        case nsx::PageSpec::Quorum:
+            ok = search_quorum_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
+            break;
+        case nsx::PageSpec::QuorumSorted:
+            ok = search_quorum_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
+            break;
     }
     if (!ok) { body = err_; return false; }
     SearchResult res;
@@ -3059,6 +3238,10 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
     if ((spec.mode == nsx::PageSpec::Grouped || spec.mode == nsx::PageSpec::GroupedSorted) && !grouped_insert(rest_of, query)) {   // search_grouped's "grouped" member
         body = err_ = "search_page: the search body has no k member";
+        return false;
+    }
+    if ((spec.mode == nsx::PageSpec::Quorum || spec.mode == nsx::PageSpec::QuorumSorted) && !quorum_insert(rest_of, query)) {   // search_quorum's "quorum" member
+        body = err_ = "search_page: the search body has no results member";
         return false;
     }
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)

@@ -39,6 +39,7 @@
 #include "sorted.hpp"
 #include "boolean.hpp"
 #include "grouped.hpp"
+#include "quorum.hpp"
 #include "page.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
@@ -395,6 +396,30 @@ public:
     std::string search_grouped_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
     bool search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
 
+    // At-least-m-of-n clauses (host/quorum.hpp): the three grouped batch calls over nsx::parse_quorum's dialect,
+    // `+(fever cough dyspnea fatigue)~2 -mouse` and `fever cough dyspnea ~2`, with a need per ref.  Each has its sibling's
+    // parameters (filters and cursors included) and its sibling's answers for a text with neither form.  An unknown member is
+    // dropped and the need stays, so a need above the known members matches nothing.  A need above nsx::kQuorumMaxNeed is refused
+    // with a message, like the clause limit.
+    bool search_quorum_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                        uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+    bool facet_quorum_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                 uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms = nullptr);
+    bool search_quorum_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                         const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                         uint8_t* usable, float* device_ms = nullptr);
+
+    // JSON text: the grouped siblings' bodies over this dialect, with "quorum": {"min_should": m, "must": [{"need": n, "terms":
+    // [...]}, ...], "must_not": [...], "should": [...]} in place of "grouped" (in its sorted place, behind "query").  The terms a `~m`
+    // piece promoted are reported under "should".  search_page's modes Quorum and QuorumSorted page them with the cursor kinds of
+    // Grouped and GroupedSorted.  Any failure: {"error": ...} (the _text forms: false, body = the message).
+    std::string search_quorum(const std::string& query, int k, const nsx::DocFilter* f = nullptr);
+    bool search_quorum_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    std::string search_quorum_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_quorum_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
+    std::string search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
+    bool search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
+
     // Pages past the first K (host/page.hpp).  A cursor is a position (rank, manifest position, docId) in a call's
     // total order; with one, a call answers with the first K matched documents STRICTLY AFTER it: found[q] stays the size of
     // the matched set, rest[q] (may be nullptr) is the number of matched documents after the cursor, nhits[q] = min(K, rest[q]).
@@ -496,11 +521,12 @@ private:
     bool sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
                            float* device_ms);
-    bool boolean_batch_impl(const char* fn, bool grouped, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+    enum { kDialectBoolean = 0, kDialectGrouped = 1, kDialectQuorum = 2 };   // which parser a shared implementation reads the text with
+    bool boolean_batch_impl(const char* fn, int dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
                             ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
-    bool boolean_facet_impl(const char* fn, bool grouped, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+    bool boolean_facet_impl(const char* fn, int dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
                             std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms);
-    bool boolean_sorted_impl(const char* fn, bool grouped, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+    bool boolean_sorted_impl(const char* fn, int dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
                              float* device_ms);
     // what the three boolean paths share: filter row source, the call's segment list and the refs and roles of a query range
@@ -517,15 +543,18 @@ private:
         std::vector<char> scratch;
         std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
         std::vector<uint32_t> term_clauses;               // grouped_refs_range: parallel to terms
+        std::vector<uint8_t> needs;                       // quorum_refs_range: parallel to refs
+        std::vector<uint32_t> term_needs;                 // quorum_refs_range: parallel to terms
     };
     bool boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp);
     void boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
-    bool boolean_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
-    bool boolean_faceted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
+    bool boolean_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    bool boolean_faceted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
                                    std::string& body);
-    bool boolean_sorted_text_impl(const char* name, bool grouped, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
+    bool boolean_sorted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
                                   std::string& body);
     bool grouped_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
+    bool quorum_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };

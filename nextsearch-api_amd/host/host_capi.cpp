@@ -1160,14 +1160,14 @@ static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<ns
     for (uint32_t q = 0; q < n; q++) { out[q].set = in[q].set != 0; out[q].rank = in[q].rank; out[q].seg = in[q].seg; out[q].doc = in[q].doc; }
 }
 
-// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted, 5 grouped, 6 grouped sorted
+// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted, 5 grouped, 6 grouped sorted, 7 quorum, 8 quorum sorted
 static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                            uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                            uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::SortSpec sp;
     std::string why;
-    const bool dated = mode == 3 || mode == 4 || mode == 6;
+    const bool dated = mode == 3 || mode == 4 || mode == 6 || mode == 8;
     if (dated && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
     if (n_queries && (!queries || !hits || !nhits || (dated && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
     std::vector<nextsearch::Engine::QueryView> views(n_queries);
@@ -1181,7 +1181,9 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_so
     if (!rest) { r_.resize(n_queries); rest = r_.data(); }
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     bool ok;
-    if (mode == 6) ok = e->eng.search_grouped_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    if (mode == 8) ok = e->eng.search_quorum_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 7) ok = e->eng.search_quorum_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    else if (mode == 6) ok = e->eng.search_grouped_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 5) ok = e->eng.search_grouped_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 4) ok = e->eng.search_boolean_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
@@ -1218,7 +1220,7 @@ extern "C" int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sor
 }
 
 // ---- facet counts and date order for boolean queries ----
-static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, bool grouped, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /* 0 boolean, 1 grouped, 2 quorum */, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
 
 extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
@@ -1323,7 +1325,95 @@ extern "C" int nsh_engine_search_grouped_sorted_json(nsh_engine* e, const char* 
 } NSH_CATCH(e, "nsh_engine_search_grouped_sorted_json", -1)
 }
 
-static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, bool grouped, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+// ---- at-least-m-of-n clauses (host/quorum.hpp) ----
+extern "C" uint32_t nsh_parse_quorum(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                                     uint32_t terms_cap, uint32_t* min_should_out) { try {
+    uint32_t min_should = 0;
+    const auto terms = nsx::parse_quorum(query ? query : "", &min_should);
+    std::string joined;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (i) joined.push_back(' ');
+        joined += terms[i].text;
+        if (i >= terms_cap) continue;
+        if (roles) roles[i] = terms[i].role;
+        if (clauses) clauses[i] = terms[i].clause;
+        if (needs) needs[i] = terms[i].need;
+        if (promoted) promoted[i] = terms[i].promoted ? 1 : 0;
+    }
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(joined.size(), cap - 1);
+        std::memcpy(buf, joined.data(), n);
+        buf[n] = 0;
+    }
+    if (min_should_out) *min_should_out = min_should;
+    return (uint32_t)terms.size();
+} NSH_CATCH(nullptr, "nsh_parse_quorum", 0)
+}
+
+extern "C" int nsh_engine_search_quorum_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
+                                                    const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                                    uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_quorum_after_batch", 7, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_quorum_after_batch", -1)
+}
+
+extern "C" int nsh_engine_facet_quorum_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                             uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_facet_boolean(e, "nsh_engine_facet_quorum_batch", 2, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_facet_quorum_batch", -1)
+}
+
+extern "C" int nsh_engine_search_quorum_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+                                                     uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
+                                                     uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
+    return nsh_after_batch(e, "nsh_engine_search_quorum_sorted_batch", 8, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+                           has_found, device_ms_out);
+} NSH_CATCH(e, "nsh_engine_search_quorum_sorted_batch", -1)
+}
+
+extern "C" int nsh_engine_search_quorum_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
+                                             int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+    const bool ok = e->eng.search_quorum_text(query ? query : "", k, use_filter ? &f : nullptr, s);
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_quorum_json", -1)
+}
+
+extern "C" int nsh_engine_search_quorum_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
+                                                     const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::FacetSpec sp;
+    bool ok = nsh_facet_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_quorum_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_quorum_faceted_json", -1)
+}
+
+extern "C" int nsh_engine_search_quorum_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
+                                                    const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::SortSpec sp;
+    bool ok = nsh_sort_spec_of(e, spec, sp, s);
+    if (ok) {
+        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_quorum_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_quorum_sorted_json", -1)
+}
+
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /* 0 boolean, 1 grouped, 2 quorum */, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::FacetSpec sp;
@@ -1338,7 +1428,8 @@ static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, bool grouped,
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
-    const bool ok = grouped ? e->eng.facet_grouped_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
+    const bool ok = dialect == 2 ? e->eng.facet_quorum_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
+                    : dialect ? e->eng.facet_grouped_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
                             : e->eng.facet_boolean_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out);
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
     if (counts.size() > counts_cap || (!counts.empty() && !counts_out)) {
@@ -1414,7 +1505,7 @@ extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int
     *json_out = nullptr;
     std::string s;
     nsx::PageSpec ps;
-    bool ok = mode <= 6u;
+    bool ok = mode <= 8u;
     if (!ok) s = "search_page: unknown mode " + std::to_string(mode);
     if (ok) {
         ps.mode = (nsx::PageSpec::Mode)mode;

@@ -31,7 +31,12 @@
 //   ns_tool search-grouped-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>     (needs an MI355X)
 //   ns_tool search-grouped-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean_sorted: search-boolean's JSON body with "results" in date order plus "sort", as search-sorted's.
-//   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
+//   ns_tool search-quorum <index_dir> <from> <to> <k> <query words ...>                           (needs an MI355X; `+(a b c)~2 -d`, `a b c ~2`)
+//   ns_tool search-quorum-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>      (needs an MI355X)
+//   ns_tool search-quorum-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>    (needs an MI355X)
+//        Engine::search_quorum, search_quorum_faceted, search_quorum_sorted: the grouped bodies with "quorum" in place of "grouped".
+//        The page modes quorum, quorum-newest and quorum-oldest page them.
+//   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest|grouped|grouped-newest|grouped-oldest|quorum|quorum-newest|quorum-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
 //        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
 //        "remaining"} (page.hpp).  cursor: "-" for the first page, else a page's "next".  from / to as search-filtered's.
 //   ns_tool facade-bench <index_dir> <queries.txt> <k> [reps=5] [device=0]
@@ -130,8 +135,8 @@ int main(int argc, char** argv) {
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 7 && (std::strcmp(argv[1], "search-boolean") == 0 || std::strcmp(argv[1], "search-grouped") == 0)) {
-        const bool grouped = argv[1][7] == 'g';
+    if (argc >= 7 && (std::strcmp(argv[1], "search-boolean") == 0 || std::strcmp(argv[1], "search-grouped") == 0 || std::strcmp(argv[1], "search-quorum") == 0)) {
+        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
@@ -142,12 +147,12 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[5]);
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
-        if (!(grouped ? eng.search_grouped_text(q, k, filtered ? &f : nullptr, body) : eng.search_boolean_text(q, k, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!(quorum ? eng.search_quorum_text(q, k, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_text(q, k, filtered ? &f : nullptr, body) : eng.search_boolean_text(q, k, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-faceted") == 0 || std::strcmp(argv[1], "search-grouped-faceted") == 0)) {
-        const bool grouped = argv[1][7] == 'g';
+    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-faceted") == 0 || std::strcmp(argv[1], "search-grouped-faceted") == 0 || std::strcmp(argv[1], "search-quorum-faceted") == 0)) {
+        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
         nsx::FacetSpec spec;
         if (std::strcmp(argv[3], "year") == 0) spec.kind = nsx::FacetSpec::Year;
         else if (std::strcmp(argv[3], "month") == 0) spec.kind = nsx::FacetSpec::Month;
@@ -162,12 +167,12 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!(grouped ? eng.search_grouped_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!(quorum ? eng.search_quorum_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
-    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-sorted") == 0 || std::strcmp(argv[1], "search-grouped-sorted") == 0)) {
-        const bool grouped = argv[1][7] == 'g';
+    if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-sorted") == 0 || std::strcmp(argv[1], "search-grouped-sorted") == 0 || std::strcmp(argv[1], "search-quorum-sorted") == 0)) {
+        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
         nsx::SortSpec spec;
         if (std::strcmp(argv[3], "newest") == 0) spec.ascending = false;
         else if (std::strcmp(argv[3], "oldest") == 0) spec.ascending = true;
@@ -182,7 +187,7 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!(grouped ? eng.search_grouped_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!(quorum ? eng.search_quorum_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
@@ -198,7 +203,10 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[3], "grouped") == 0) spec.mode = nsx::PageSpec::Grouped;
         else if (std::strcmp(argv[3], "grouped-newest") == 0) { spec.mode = nsx::PageSpec::GroupedSorted; spec.sort.ascending = false; }
         else if (std::strcmp(argv[3], "grouped-oldest") == 0) { spec.mode = nsx::PageSpec::GroupedSorted; spec.sort.ascending = true; }
-        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest, oldest, boolean-newest, boolean-oldest, grouped, grouped-newest or grouped-oldest, not %s\n", argv[3]); return 2; }
+        else if (std::strcmp(argv[3], "quorum") == 0) spec.mode = nsx::PageSpec::Quorum;
+        else if (std::strcmp(argv[3], "quorum-newest") == 0) { spec.mode = nsx::PageSpec::QuorumSorted; spec.sort.ascending = false; }
+        else if (std::strcmp(argv[3], "quorum-oldest") == 0) { spec.mode = nsx::PageSpec::QuorumSorted; spec.sort.ascending = true; }
+        else { std::fprintf(stderr, "page: the mode is or, and, boolean, newest, oldest, boolean-newest, boolean-oldest, grouped, grouped-newest, grouped-oldest, quorum, quorum-newest or quorum-oldest, not %s\n", argv[3]); return 2; }
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }

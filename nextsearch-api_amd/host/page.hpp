@@ -28,13 +28,13 @@ struct PageCursor {
 
 // which call a page is a page of
 struct PageSpec {
-    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u
+    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6, Quorum = 7, QuorumSorted = 8 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u; Quorum*: §5w
     Mode mode = SearchOr;
-    SortSpec sort;                       // Sorted, BooleanSorted and GroupedSorted only
+    SortSpec sort;                       // Sorted, BooleanSorted, GroupedSorted and QuorumSorted only
     bool use_filter = false;
     DocFilter filter;
 };
-inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted || m == PageSpec::GroupedSorted) ? 'd' : 's'; }
+inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted || m == PageSpec::GroupedSorted || m == PageSpec::QuorumSorted) ? 'd' : 's'; }
 
 inline std::string cursor_text(char kind, const PageCursor& c) {
     if (!c.set) return std::string();

@@ -56,7 +56,7 @@ assert HIT_DTYPE.itemsize == C.sizeof(NsHit) == 12
 assert TERM_DTYPE.itemsize == C.sizeof(NsTermRef) == 24
 assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 PAGE_CURSOR_DTYPE = np.dtype([("set", "<u4"), ("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4")])   # nsh_page_cursor: seg is a manifest position
-PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4, "grouped": 5, "grouped_sorted": 6}
+PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4, "grouped": 5, "grouped_sorted": 6, "quorum": 7, "quorum_sorted": 8}
 CURSOR_DTYPE = np.dtype([("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4"), ("set", "<u4")])   # ns_cursor
 
 # every symbol include/nextsearch_hip.h declares
@@ -66,6 +66,7 @@ HIP_SYMBOLS = [
     "ns_search_boolean", "ns_boolean_kernel_ms", "ns_search_boolean_after", "ns_search_sorted_after",
     "ns_facet_count_boolean", "ns_search_sorted_boolean", "ns_boolean_sets_kernel_ms",
     "ns_search_grouped_after", "ns_facet_count_grouped", "ns_search_sorted_grouped", "ns_grouped_kernel_ms",
+    "ns_search_quorum_after", "ns_facet_count_quorum", "ns_search_sorted_quorum", "ns_quorum_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -85,6 +86,8 @@ HOST_SYMBOLS = [
     "nsh_engine_search_page_json",
     "nsh_parse_grouped", "nsh_engine_search_grouped_after_batch", "nsh_engine_facet_grouped_batch", "nsh_engine_search_grouped_sorted_batch",
     "nsh_engine_search_grouped_json", "nsh_engine_search_grouped_faceted_json", "nsh_engine_search_grouped_sorted_json",
+    "nsh_parse_quorum", "nsh_engine_search_quorum_after_batch", "nsh_engine_facet_quorum_batch", "nsh_engine_search_quorum_sorted_batch",
+    "nsh_engine_search_quorum_json", "nsh_engine_search_quorum_faceted_json", "nsh_engine_search_quorum_sorted_json",
     "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
@@ -272,6 +275,10 @@ def hip_lib():
         L.ns_facet_count_grouped.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
         L.ns_search_sorted_grouped.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_grouped_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        L.ns_search_quorum_after.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_facet_count_quorum.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
+        L.ns_search_sorted_quorum.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_quorum_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -283,7 +290,8 @@ def hip_lib():
 DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_debug_merge_counters": 16, "ns_debug_topk_counters": 4,
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
                   "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
-                  "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11}
+                  "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11,
+                  "ns_debug_boolean_quorum_counters": 12}
 
 
 def debug_counters(reset=False):
@@ -473,6 +481,14 @@ def host_lib():
         L.nsh_engine_facet_grouped_batch.argtypes = L.nsh_engine_facet_boolean_batch.argtypes
         L.nsh_engine_search_grouped_sorted_batch.argtypes = L.nsh_engine_search_boolean_sorted_batch.argtypes
         L.nsh_engine_search_grouped_json.argtypes = L.nsh_engine_search_boolean_json.argtypes
+        L.nsh_parse_quorum.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, vp, vp, u32, vp]
+        L.nsh_parse_quorum.restype = u32
+        L.nsh_engine_search_quorum_after_batch.argtypes = L.nsh_engine_search_boolean_after_batch.argtypes
+        L.nsh_engine_facet_quorum_batch.argtypes = L.nsh_engine_facet_boolean_batch.argtypes
+        L.nsh_engine_search_quorum_sorted_batch.argtypes = L.nsh_engine_search_boolean_sorted_batch.argtypes
+        L.nsh_engine_search_quorum_json.argtypes = L.nsh_engine_search_boolean_json.argtypes
+        L.nsh_engine_search_quorum_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        L.nsh_engine_search_quorum_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_boolean_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_grouped_faceted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshFacetSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_search_grouped_sorted_json.argtypes = [vp, C.c_char_p, i32, C.POINTER(NshSortSpec), i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
@@ -1169,6 +1185,73 @@ class Engine:
         out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
         return out + (float(ms.value),) if timing else out
 
+    # ---- at-least-m-of-n clauses: the grouped batch calls over `+(a b c)~2 -d` and `a b c ~2` ----
+    def search_quorum_after_batch(self, queries, k, after=None, handle=0, timing=False):
+        """Engine::search_quorum_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_grouped_after_batch"""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_quorum_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
+                                                          hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_quorum_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def facet_quorum_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
+        """Engine::facet_quorum_batch_flat: (counts Q x n_buckets, found, has_found); as facet_grouped_batch"""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        Q = len(queries)
+        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_facet_quorum_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
+                                                   found.ctypes.data, has_found.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"facet_quorum_batch failed: {self.error()}")
+        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+
+    def search_quorum_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
+        """Engine::search_quorum_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); as
+        search_grouped_sorted_batch"""
+        sp, keep = self._sort_spec(order, custom)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_quorum_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
+                                                           cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
+                                                           nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_quorum_sorted_batch failed: {self.error()}")
+        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_quorum_json(self, query, k, date_filter=None, check=True):
+        """Engine::search_quorum: the JSON text; as search_grouped_json"""
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_quorum", self._L.nsh_engine_search_quorum_json, _as_bytes(query), k, int(date_filter is not None), _as_bytes(df),
+                               _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_quorum_faceted_json(self, query, k, kind="year", date_filter=None, custom=None, labels=None, check=True):
+        """Engine::search_quorum_faceted: the JSON text; as search_grouped_faceted_json"""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_quorum_faceted", self._L.nsh_engine_search_quorum_faceted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_quorum_sorted_json(self, query, k, order="newest", date_filter=None, custom=None, check=True):
+        """Engine::search_quorum_sorted: the JSON text; as search_grouped_sorted_json"""
+        sp, keep = self._sort_spec(order, custom)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_quorum_sorted", self._L.nsh_engine_search_quorum_sorted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
     def _json_call(self, name, fn, *args, check=True):
         out = C.c_void_p()
         rc = fn(self.h, *args, C.byref(out))
@@ -1219,7 +1302,7 @@ class Engine:
 
     def search_page_json(self, query, k, cursor="", mode="or", order="newest", date_filter=None, custom=None, check=True):
         """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" | "boolean_sorted" | "grouped" |
-        "grouped_sorted" (the sorted ones: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
+        "grouped_sorted" | "quorum" | "quorum_sorted" (the sorted ones: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         out = C.c_void_p()
@@ -2051,6 +2134,19 @@ def parse_grouped(text):
     return [(w, int(r), int(c)) for w, r, c in zip(words, roles[:n], clauses[:n])]
 
 
+def parse_quorum(text):
+    """nsx::parse_quorum (host only): ([(term, role, clause, need, promoted)], min_should); need is that of a MUST term's clause, 0 on
+    SHOULD and NOT terms; promoted: an optional term that a `~m` piece made a member of the last clause"""
+    b = _as_bytes(text)
+    cap = len(b) + 16
+    buf, roles, clauses, needs, promoted = C.create_string_buffer(cap), np.zeros(cap, np.uint8), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+    m = C.c_uint32()
+    n = int(host_lib().nsh_parse_quorum(b, buf, cap, roles.ctypes.data, clauses.ctypes.data, needs.ctypes.data, promoted.ctypes.data, cap, C.addressof(m)))
+    words = buf.value.decode().split(" ") if n else []
+    assert len(words) == n, (words, n)
+    return [(w, int(r), int(c), int(e), bool(p)) for w, r, c, e, p in zip(words, roles[:n], clauses[:n], needs[:n], promoted[:n])], int(m.value)
+
+
 def search_boolean_raw(ctx, qd, refs, roles, k, seg_ids, segs):
     """ns_search_boolean (raw): (rc, hits Q x K, nhits, found, device ms); K = clamp(k, 1, 100); roles: one uint8 per ref, or
     None (all SHOULD); segs: list of handles.  The outputs are pre-filled with 0xAB bytes."""
@@ -2305,6 +2401,93 @@ def grouped_kernel_ms(reset=True):
     calls that were given clauses, since the last reset"""
     out = (C.c_float * 6)()
     hip_lib().ns_grouped_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+# ---- at-least-m-of-n clauses (DESIGN.md §5w): the grouped siblings with one uint8 need per ref behind the clause values ----
+def _needs(needs):
+    return None if needs is None else np.ascontiguousarray(needs, dtype=np.uint8)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None and len(a) else None
+
+
+def search_quorum_after_raw(ctx, qd, refs, roles, clauses, needs, k, after, seg_ids, segs):
+    """ns_search_quorum_after (raw): (rc, hits Q x K, nhits, found, rest, device ms); needs: one uint8 per ref (read for MUST
+    refs), or None (the grouped sibling); the rest as search_grouped_after_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl, ne = _clauses(clauses), _needs(needs)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_quorum_after(ctx, qd.ctypes.data if Q else None, Q, _ptr(refs), _ptr(ro), _ptr(cl), _ptr(ne), len(refs), int(k), _ptr(cu),
+                                          _ptr(ids), sa, len(ids), hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+def facet_count_quorum(ctx, qd, refs, roles, clauses, needs, seg_ids, segs, tables, n_buckets):
+    """ns_facet_count_quorum (raw): (rc, counts Q x n_buckets, found, device ms); needs as search_quorum_after_raw's, the rest as
+    facet_count_grouped.  The outputs are pre-filled with 0xAB bytes."""
+    Q = len(qd)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl, ne = _clauses(clauses), _needs(needs)
+    counts = np.full((max(Q, 1), int(n_buckets)), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_facet_count_quorum(ctx, qd.ctypes.data if Q else None, Q, _ptr(refs), _ptr(ro), _ptr(cl), _ptr(ne), len(refs), _ptr(ids), sa, ta, len(ids),
+                                         counts.ctypes.data, found.ctypes.data, C.byref(ms))
+    return rc, counts[:Q], found[:Q], float(ms.value)
+
+
+def search_sorted_quorum_raw(ctx, qd, refs, roles, clauses, needs, k, flags, after, seg_ids, segs, tables):
+    """ns_search_sorted_quorum (raw): (rc, hits Q x K, keys Q x K, nhits, found, rest, device ms); needs as
+    search_quorum_after_raw's, the rest as search_sorted_grouped_raw.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ta = (C.c_void_p * max(len(tables), 1))(*[t.value if isinstance(t, C.c_void_p) else t for t in tables])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl, ne = _clauses(clauses), _needs(needs)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    keys = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_sorted_quorum(ctx, qd.ctypes.data if Q else None, Q, _ptr(refs), _ptr(ro), _ptr(cl), _ptr(ne), len(refs), int(k), int(flags),
+                                           _ptr(cu), _ptr(ids), sa, ta, len(ids), hits.ctypes.data, keys.ctypes.data, nhits.ctypes.data, found.ctypes.data,
+                                           rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+QUORUM_EVENTS = ["search_items", "search_clauses_counted", "search_additions", "search_saturated", "search_windows_ended", "search_duplicates_skipped",
+                 "sets_items", "sets_clauses_counted", "sets_additions", "sets_saturated", "sets_items_ended", "sets_duplicates_skipped"]
+
+
+def quorum_counters(reset=True):
+    """ns_debug_boolean_quorum_counters of the counting build as {name: value}; None for a library without them"""
+    c = debug_counters(reset=reset).get("ns_debug_boolean_quorum_counters")
+    return None if c is None else dict(zip(QUORUM_EVENTS, c))
+
+
+def quorum_kernel_ms(reset=True):
+    """(k_bq_select, k_bq_join, k_bs_count, k_bs_select, k_sd_join, k_bs_score) HIP-event ms summed over this thread's quorum
+    calls that were given needs, since the last reset"""
+    out = (C.c_float * 6)()
+    hip_lib().ns_quorum_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
