@@ -25,21 +25,94 @@ struct BoolTerm {
 
 inline bool bool_is_space(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; }
 
-// Calls fn(ptr, len, role) for every term of the query, in order.  `scratch` holds the lowercased bytes.
-template <class Fn>
-inline void for_each_boolean_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+// The three dialects of the query box.  They are nested: Grouped (grouped.hpp) is Boolean plus one level of parentheses, Quorum
+// (quorum.hpp) is Grouped plus the two `~m` forms.  A fourth dialect is one more value here and one more branch in the scanner.
+enum class Dialect : int { Boolean = 0, Grouped = 1, Quorum = 2 };
+
+static constexpr uint32_t kQuorumNeedCap = 1000000;    // what a longer run of digits reads as
+
+struct QuorumShape {
+    uint32_t n_clauses;    // of the terms as fn saw them
+    uint32_t min_should;   // the last `~m` piece's m; > 0: the caller makes every SHOULD term a MUST term of clause n_clauses, need m
+};
+
+// decimal digits at text[i ..): their value (saturating) and the index behind them; no digit: `end` == i
+inline uint32_t quorum_digits(const char* text, size_t n, size_t i, size_t& end) {
+    uint64_t v = 0;
+    end = i;
+    while (end < n && text[end] >= '0' && text[end] <= '9') {
+        v = v * 10 + (uint64_t)(text[end] - '0');
+        if (v > kQuorumNeedCap) v = kQuorumNeedCap;
+        end++;
+    }
+    return (uint32_t)v;
+}
+
+// The one scanner of the three grammars (the header comments of boolean.hpp, grouped.hpp and quorum.hpp).  Calls
+// fn(ptr, len, role, clause, need) for every term of the query, in order; `scratch` holds the lowercased bytes.  Under kRoleMust
+// `clause` counts up from 0 (one id per group, one per token outside a group) and `need` is the clause's need (>= 1); else both
+// are 0.  The optional terms come as SHOULD terms whatever min_should says: see QuorumShape.  Without groups '(' is the
+// tokenizer's business; without needs a '~' is.
+template <Dialect D, class Fn>
+inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+    constexpr bool kGroups = D != Dialect::Boolean, kNeeds = D == Dialect::Quorum;
+    QuorumShape shape{0, 0};
     size_t i = 0;
     while (i < n) {
         while (i < n && bool_is_space((unsigned char)text[i])) i++;
+        if (i >= n) break;
+        const uint8_t prefix = text[i] == '+' ? kRoleMust : text[i] == '-' ? kRoleNot : kRoleShould;
+        const size_t from = prefix == kRoleShould ? i : i + 1;
+        if (kGroups && from < n && text[from] == '(') {
+            size_t end = from + 1;
+            while (end < n && text[end] != ')') end++;
+            size_t resume = end < n ? end + 1 : n;
+            uint32_t need = 0;
+            if (kNeeds && end + 1 < n && text[end + 1] == '~') {
+                size_t behind;
+                const uint32_t m = quorum_digits(text, n, end + 2, behind);
+                if (behind > end + 2) { need = m; resume = behind; }
+            }
+            const uint8_t role = (need >= 1 && prefix == kRoleShould) ? kRoleMust : prefix;
+            if (role != kRoleMust) need = 0;
+            else if (need == 0) need = 1;
+            bool any = false;
+            for_each_base_term(text + from + 1, end - (from + 1), scratch, [&](const char* p, size_t len) {
+                fn(p, len, role, role == kRoleMust ? shape.n_clauses : 0u, need);
+                any = true;
+            });
+            if (any && role == kRoleMust) shape.n_clauses++;
+            i = resume;
+            continue;
+        }
         size_t j = i;
         while (j < n && !bool_is_space((unsigned char)text[j])) j++;
-        if (j > i) {
-            const uint8_t role = text[i] == '+' ? kRoleMust : text[i] == '-' ? kRoleNot : kRoleShould;
-            const size_t from = role == kRoleShould ? i : i + 1;
-            for_each_base_term(text + from, j - from, scratch, [&](const char* p, size_t len) { fn(p, len, role); });
+        if (kNeeds && text[i] == '~' && j > i + 1) {
+            size_t behind;
+            const uint32_t m = quorum_digits(text, n, i + 1, behind);
+            if (behind == j) { shape.min_should = m; i = j; continue; }
         }
+        for_each_base_term(text + from, j - from, scratch,
+                           [&](const char* p, size_t len) { fn(p, len, prefix, prefix == kRoleMust ? shape.n_clauses++ : 0u, prefix == kRoleMust ? 1u : 0u); });
         i = j;
     }
+    return shape;
+}
+
+// the scanner of a dialect chosen at run time
+template <class Fn>
+inline QuorumShape for_each_term(Dialect d, const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+    switch (d) {
+        case Dialect::Boolean: return for_each_dialect_term<Dialect::Boolean>(text, n, scratch, fn);
+        case Dialect::Grouped: return for_each_dialect_term<Dialect::Grouped>(text, n, scratch, fn);
+        default: return for_each_dialect_term<Dialect::Quorum>(text, n, scratch, fn);
+    }
+}
+
+// Calls fn(ptr, len, role) for every term of the query, in order.
+template <class Fn>
+inline void for_each_boolean_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+    for_each_dialect_term<Dialect::Boolean>(text, n, scratch, [&](const char* p, size_t len, uint8_t role, uint32_t, uint32_t) { fn(p, len, role); });
 }
 
 inline std::vector<BoolTerm> parse_boolean(const std::string& text) {

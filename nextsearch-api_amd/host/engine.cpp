@@ -15,6 +15,14 @@
 
 namespace nextsearch {
 
+// the body of every failure: {"error": why}, dump(2) layout
+static std::string error_body(const std::string& why) {
+    std::string o = "{\n  \"error\": ";
+    json_escape(o, why);
+    o += "\n}";
+    return o;
+}
+
 float bm25_idf(uint32_t N, uint32_t df) {
     // std::log((((N - df + 0.5f) / (df + 0.5f)) + 1.0f))   src/api_engine.cpp:45-47
     float num = (float)(uint32_t)(N - df) + 0.5f;
@@ -770,6 +778,16 @@ static size_t sub_batch_size() {   // NS_SUBBATCH overrides it (experiments)
     return v;
 }
 
+// the sub-batch ranges [a, b) of a batch of Q in order: fn(a, b), until one says false
+template <class Fn>
+static bool for_each_sub_batch(size_t Q, Fn fn) {
+    const size_t kSubBatch = sub_batch_size();
+    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
+    for (size_t i = 0; i < n_sub; i++)
+        if (!fn(Q * i / n_sub, Q * (i + 1) / n_sub)) return false;
+    return true;
+}
+
 // One contiguous range [q0, q1) of a batch on one context.  Two or more sub-batches: prepare(i + 1) on the host || kernels(i)
 // on the device || results(i - 1) on their way back.  pooled_prep: query preparation on the engine's host threads (the one
 // range of a single-device engine); otherwise on the calling thread (a multi-device engine runs one such call per device).
@@ -1040,14 +1058,7 @@ bool Engine::search_text(const std::string& query, int k, std::string& body) {
 
 std::string Engine::search(const std::string& query, int k) {
     std::string body;
-    if (!search_text(query, k, body)) {
-        // the reference lets exceptions reach the HTTP layer's 500 handler (src/api_server.cpp:76-84)
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_text(query, k, body) ? body : error_body(body);
 }
 
 // ---- autocomplete (include/api_engine.hpp:67, src/api_engine.cpp:164-187) --------------------------------------------
@@ -1192,13 +1203,7 @@ bool Engine::suggest_text(const std::string& input, int limit, std::string& body
 
 std::string Engine::suggest(const std::string& input, int limit) {
     std::string body;
-    if (!suggest_text(input, limit, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return suggest_text(input, limit, body) ? body : error_body(body);
 }
 
 // ---- spelling correction (correct.hpp, csrc/ns_fuzzy.hip) --------------------------------------------------------------
@@ -1398,13 +1403,7 @@ bool Engine::did_you_mean_text(const std::string& query, int limit, std::string&
 
 std::string Engine::did_you_mean(const std::string& query, int limit) {
     std::string body;
-    if (!did_you_mean_text(query, limit, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return did_you_mean_text(query, limit, body) ? body : error_body(body);
 }
 
 // ---- typo-tolerant completion ----------------------------------------------------------------------------
@@ -1444,13 +1443,7 @@ bool Engine::complete_text(const std::string& input, int limit, std::string& bod
 
 std::string Engine::complete(const std::string& input, int limit) {
     std::string body;
-    if (!complete_text(input, limit, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return complete_text(input, limit, body) ? body : error_body(body);
 }
 
 // ---- more like this -----------------------------------------------------------------------------------------
@@ -1698,13 +1691,7 @@ bool Engine::more_like_this_text(const std::string& uid, int k, std::string& bod
 
 std::string Engine::more_like_this(const std::string& uid, int k) {
     std::string body;
-    if (!more_like_this_text(uid, k, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return more_like_this_text(uid, k, body) ? body : error_body(body);
 }
 
 // ---- filtered search (host/filter.hpp, csrc/ns_filter.hip) ------------------------------------------------
@@ -1933,13 +1920,7 @@ bool Engine::search_filtered_text(const std::string& query, int k, const nsx::Do
 
 std::string Engine::search_filtered(const std::string& query, int k, const nsx::DocFilter& f) {
     std::string body;
-    if (!search_filtered_text(query, k, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_filtered_text(query, k, f, body) ? body : error_body(body);
 }
 
 // ---- facet counts (host/facet.hpp, csrc/ns_facet.hip) -------------------------------------------------------
@@ -2022,6 +2003,92 @@ bool Engine::ensure_facets(const nsx::FacetSpec& spec, FacetSet*& out) {
     return true;
 }
 
+// ---- what the facet, date-order, boolean and paged calls share ---------------------------------------------------------
+// The filter under a handle (0: none) and its row source; false, with a message, for a stale handle.
+bool Engine::filter_rows(const char* fn, uint32_t filter_handle, CallPrep& bp) {
+    if (!filter_handle) return true;
+    bp.f = filter_of(filter_handle);
+    if (!bp.f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
+    bp.rs.rows = bp.f->rows.data();   // search_filtered_batch_flat's row source
+    bp.rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * (uint32_t)segments.size();
+    static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
+    if (!bp.rs.rows) bp.rs.rows = &no_rows;
+    return true;
+}
+
+// The segments the refs can name, in manifest order: the index's own, or the filter's copies, without those `keep` refuses.
+template <class Keep>
+void Engine::list_segments(CallPrep& bp, Keep keep) {
+    const uint32_t S = (uint32_t)segments.size();
+    bp.is_listed.assign(S, 0);
+    for (uint32_t s = 0; s < S; s++) {
+        ns_seg* h = bp.f ? bp.f->segs[s] : dev_segs_[s];
+        if (!h || !keep(s)) continue;
+        bp.is_listed[s] = 1;
+        bp.listed.push_back(s);
+        bp.ids.push_back(bp.rs.id_base + s);
+        bp.segs.push_back(h);
+    }
+}
+
+bool Engine::boolean_prepare(const char* fn, uint32_t filter_handle, CallPrep& bp) {
+    if (!filter_rows(fn, filter_handle, bp)) return false;
+    list_segments(bp, [](uint32_t) { return true; });
+    return true;
+}
+
+// The plain search's query preparation.  With embeddings loaded: the expansion of search_batch_flat for the whole batch up
+// front, the expanded terms then go sub-batch by sub-batch (term_begin stays an index into the one refs array).  Without: one
+// sub-batch at a time into the engine's kept buffers.
+bool Engine::plain_prepare(const QueryView* queries, size_t Q, uint8_t* usable, const nsx::RowSource& rs, bool and_mode, PlainPrep& pp) {
+    pp.whole = sem.enabled;
+    if (!pp.whole) return true;
+    std::vector<std::string> qs(Q);
+    for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
+    std::vector<nsx::WeightedTerms> expanded;
+    if (!expand_queries(qs, expanded)) return false;
+    pp.qd.assign(Q, ns_query_desc{0, 0});
+    std::vector<uint8_t> us(Q, 0);
+    build_refs_range(qs, 0, Q, pp.qd, pp.refs, us, &expanded, rs, and_mode);
+    std::memcpy(usable, us.data(), Q);
+    return true;
+}
+
+void Engine::plain_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, const nsx::RowSource& rs, bool and_mode, PlainPrep& pp) {
+    if (!pp.whole) build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
+    pp.qd_at = pp.whole ? pp.qd.data() + a : flat_qd_.data();
+    pp.refs_at = pp.whole ? pp.refs.data() : flat_refs_.data();
+    pp.n_refs = pp.whole ? pp.refs.size() : flat_refs_.size();
+}
+
+// The sub-batch loop of every ranked call (score or date order, plain or boolean).  Per sub-batch [a, b): prep(a, b) prepares
+// its queries; its cursors are translated; with nothing on the device, where no ref can exist, the outputs are filled; else
+// call(a, b, cursors or nullptr, &ms) runs the device part, its time is added to the call's and the hits' segment ids become
+// manifest positions again.  prep and call say false with err_ set.
+template <class Prep, class Call>
+bool Engine::ranked_batch(const char* fn, CallPrep& bp, const nsx::PageCursor* after, size_t Q, const RankedOut& out, Prep prep, Call call) {
+    const size_t K = out.K;
+    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    return for_each_sub_batch(Q, [&](size_t a, size_t b) {
+        if (!prep(a, b)) return false;
+        if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, bp.cur)) return false;
+        if (bp.ids.empty()) {
+            std::fill(out.found + a, out.found + b, (uint64_t)0);
+            if (out.rest) std::fill(out.rest + a, out.rest + b, (uint64_t)0);
+            std::fill(out.nhits + a, out.nhits + b, 0u);
+            std::fill(out.hits + a * K, out.hits + b * K, pad);
+            if (out.keys) std::fill(out.keys + a * K, out.keys + b * K, 0u);
+            return true;
+        }
+        float ms = 0.0f;
+        if (!call(a, b, bp.cur.empty() ? nullptr : bp.cur.data(), &ms)) return false;
+        if (out.device_ms) *out.device_ms += ms;
+        for (size_t q = a; q < b; q++)
+            for (uint32_t i = 0; i < out.nhits[q]; i++) out.hits[q * K + i].seg_id -= bp.rs.id_base;
+        return true;
+    });
+}
+
 bool Engine::facet_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, uint32_t flags,
                               std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels,
                               float* device_ms, double* count_ms) {
@@ -2032,73 +2099,36 @@ bool Engine::facet_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle
     if (count_ms) *count_ms = 0.0;
     if (!ctx_) { err_ = "facet_batch_flat: no device context: facets are counted on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !found || !usable)) { err_ = "facet_batch_flat: null argument"; return false; }
-    OpenFilter* f = nullptr;
-    if (filter_handle) {
-        f = filter_of(filter_handle);
-        if (!f) { err_ = "facet_batch_flat: handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
-    }
+    CallPrep bp;
+    if (!filter_rows("facet_batch_flat", filter_handle, bp)) return false;
     FacetSet* fs = nullptr;
     if (!ensure_facets(spec, fs)) return false;
     labels = fs->labels;
     const size_t B = labels.size();
     counts.assign(Q * B, 0u);
     if (Q == 0) return true;
-    const uint32_t S = (uint32_t)segments.size();
     const bool and_mode = (flags & NS_FLAG_AND) != 0;
-    nsx::RowSource rs;
-    if (f) {   // search_filtered_batch_flat's row source
-        rs.rows = f->rows.data();
-        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
-        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
-        if (!rs.rows) rs.rows = &no_rows;
-    }
     // the segments the refs can name: the index's own, or the filter's copies, each with its position's table
-    std::vector<uint32_t> ids;
-    std::vector<ns_seg*> segs;
+    list_segments(bp, [&](uint32_t s) { return fs->dev[s] != nullptr; });
     std::vector<ns_facet*> tabs;
-    for (uint32_t s = 0; s < S; s++) {
-        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
-        if (!h || !fs->dev[s]) continue;
-        ids.push_back(rs.id_base + s);
-        segs.push_back(h);
-        tabs.push_back(fs->dev[s]);
-    }
-    auto count_range = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
-        if (ids.empty()) {   // nothing on the device: no ref can exist
+    for (const uint32_t s : bp.listed) tabs.push_back(fs->dev[s]);
+    PlainPrep pp;
+    if (!plain_prepare(queries, Q, usable, bp.rs, and_mode, pp)) return false;
+    return for_each_sub_batch(Q, [&](size_t a, size_t b) {
+        plain_range(queries, a, b, usable, bp.rs, and_mode, pp);
+        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
             return true;
         }
         float ms = 0.0f;
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = ns_facet_count(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, flags, ids.data(), segs.data(), tabs.data(),
-                                      (uint32_t)ids.size(), counts.data() + a * B, found + a, &ms);
+        const int rc = ns_facet_count(ctx_, pp.qd_at, (uint32_t)(b - a), pp.refs_at, (uint32_t)pp.n_refs, flags, bp.ids.data(), bp.segs.data(), tabs.data(),
+                                      (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
         if (rc != NS_OK) { err_ = std::string("ns_facet_count: ") + ns_last_error(ctx_); return false; }
         if (device_ms) *device_ms += ms;
         if (count_ms) *count_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return true;
-    };
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
-        std::vector<std::string> qs(Q);
-        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
-        std::vector<nsx::WeightedTerms> expanded;
-        if (!expand_queries(qs, expanded)) return false;
-        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
-        std::vector<ns_term_ref> refs;
-        std::vector<uint8_t> us(Q, 0);
-        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
-        std::memcpy(usable, us.data(), Q);
-        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
-            if (!count_range(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
-        return true;
-    }
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
-        if (!count_range(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
-    }
-    return true;
+    });
 }
 
 // the "facets" member of search_faceted's body, with the comma and newline behind it
@@ -2144,13 +2174,7 @@ bool Engine::search_faceted_text(const std::string& query, int k, const nsx::Fac
 
 std::string Engine::search_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
     std::string body;
-    if (!search_faceted_text(query, k, spec, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_faceted_text(query, k, spec, f, body) ? body : error_body(body);
 }
 
 // ---- search sorted by date (host/sorted.hpp, csrc/ns_sorted.hip) --------------------------------------------
@@ -2276,81 +2300,29 @@ bool Engine::sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32
     if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
     if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = std::string(fn) + ": flags are NS_FLAG_OR or NS_FLAG_AND; the direction is the spec's"; return false; }
-    OpenFilter* f = nullptr;
-    if (filter_handle) {
-        f = filter_of(filter_handle);
-        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
-    }
+    CallPrep bp;
+    if (!filter_rows(fn, filter_handle, bp)) return false;
     SortSet* ss = nullptr;
     if (!ensure_sorted(spec, ss)) return false;
     if (Q == 0) return true;
-    const size_t K = (size_t)std::max(1, std::min(k, 100));
-    const uint32_t S = (uint32_t)segments.size();
     const bool and_mode = (flags & NS_FLAG_AND) != 0;
     const uint32_t call_flags = flags | (spec.ascending ? NS_SORT_ASC : NS_SORT_DESC);
-    nsx::RowSource rs;
-    if (f) {   // search_filtered_batch_flat's row source
-        rs.rows = f->rows.data();
-        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
-        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
-        if (!rs.rows) rs.rows = &no_rows;
-    }
-    // the segments the refs can name, in manifest order: the index's own, or the filter's copies, each with its position's keys
-    std::vector<uint32_t> ids;
-    std::vector<ns_seg*> segs;
+    // each listed position with its keys; one without a key table is skipped (search_dialect_sorted_batch_flat refuses it)
+    list_segments(bp, [&](uint32_t s) { return ss->dev[s] != nullptr; });
     std::vector<ns_dockeys*> tabs;
-    std::vector<uint8_t> listed(S, 0);
-    for (uint32_t s = 0; s < S; s++) {
-        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
-        if (!h || !ss->dev[s]) continue;
-        listed[s] = 1;
-        ids.push_back(rs.id_base + s);
-        segs.push_back(h);
-        tabs.push_back(ss->dev[s]);
-    }
-    std::vector<ns_cursor> cur;
-    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-    auto run = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
-        if (!translate_cursors(fn, after, a, b, rs.id_base, listed, f != nullptr, cur)) return false;
-        if (ids.empty()) {   // nothing on the device: no ref can exist
-            std::fill(found + a, found + b, (uint64_t)0);
-            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
-            std::fill(nhits + a, nhits + b, 0u);
-            std::fill(hits + a * K, hits + b * K, pad);
-            std::fill(keys + a * K, keys + b * K, 0u);
+    for (const uint32_t s : bp.listed) tabs.push_back(ss->dev[s]);
+    const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, keys, nhits, found, rest, device_ms};
+    PlainPrep pp;
+    if (!plain_prepare(queries, Q, usable, bp.rs, and_mode, pp)) return false;
+    return ranked_batch(fn, bp, after, Q, out,
+        [&](size_t a, size_t b) { plain_range(queries, a, b, usable, bp.rs, and_mode, pp); return true; },
+        [&](size_t a, size_t b, const ns_cursor* cur, float* ms) {
+            const int rc = ns_search_sorted_after(ctx_, pp.qd_at, (uint32_t)(b - a), pp.refs_at, (uint32_t)pp.n_refs, (uint32_t)out.K, call_flags, cur, bp.ids.data(),
+                                                  bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), hits + a * out.K, keys + a * out.K, nhits + a, found + a,
+                                                  rest ? rest + a : nullptr, ms);
+            if (rc != NS_OK) { err_ = std::string(after ? "ns_search_sorted_after: " : "ns_search_sorted: ") + ns_last_error(ctx_); return false; }
             return true;
-        }
-        float ms = 0.0f;
-        const int rc = ns_search_sorted_after(ctx_, qd, (uint32_t)(b - a), refs, (uint32_t)n_refs, (uint32_t)K, call_flags, cur.empty() ? nullptr : cur.data(), ids.data(),
-                                              segs.data(), tabs.data(), (uint32_t)ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(after ? "ns_search_sorted_after: " : "ns_search_sorted: ") + ns_last_error(ctx_); return false; }
-        if (device_ms) *device_ms += ms;
-        for (size_t q = a; q < b; q++)
-            for (uint32_t i = 0; i < nhits[q]; i++) hits[q * K + i].seg_id -= rs.id_base;   // manifest positions
-        return true;
-    };
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
-        std::vector<std::string> qs(Q);
-        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
-        std::vector<nsx::WeightedTerms> expanded;
-        if (!expand_queries(qs, expanded)) return false;
-        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
-        std::vector<ns_term_ref> refs;
-        std::vector<uint8_t> us(Q, 0);
-        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
-        std::memcpy(usable, us.data(), Q);
-        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
-            if (!run(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
-        return true;
-    }
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
-        if (!run(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
-    }
-    return true;
+        });
 }
 
 bool Engine::search_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
@@ -2391,200 +2363,264 @@ bool Engine::search_sorted_text(const std::string& query, int k, const nsx::Sort
 
 std::string Engine::search_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
     std::string body;
-    if (!search_sorted_text(query, k, spec, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_sorted_text(query, k, spec, f, body) ? body : error_body(body);
 }
 
-// ---- boolean queries (host/boolean.hpp, csrc/ns_boolean.hip) -------------------------------------------
-bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
-                                       uint64_t* found, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_batch_flat", kDialectBoolean, filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
+// ---- boolean queries and their dialects (host/boolean.hpp, grouped.hpp, quorum.hpp) --
+// what the dialect forms call themselves in messages: the named methods of engine.hpp
+struct DialectNames { const char *first_page, *after_batch, *facet_batch, *sorted_batch, *text, *faceted_text, *sorted_text; };
+static const DialectNames& names_of(nsx::Dialect d) {
+    static const DialectNames kNames[3] = {
+        {"search_boolean_batch_flat", "search_boolean_after_batch_flat", "facet_boolean_batch_flat", "search_boolean_sorted_batch_flat", "search_boolean",
+         "search_boolean_faceted", "search_boolean_sorted"},
+        {"search_grouped_after_batch_flat", "search_grouped_after_batch_flat", "facet_grouped_batch_flat", "search_grouped_sorted_batch_flat", "search_grouped",
+         "search_grouped_faceted", "search_grouped_sorted"},
+        {"search_quorum_after_batch_flat", "search_quorum_after_batch_flat", "facet_quorum_batch_flat", "search_quorum_sorted_batch_flat", "search_quorum",
+         "search_quorum_faceted", "search_quorum_sorted"}};
+    return kNames[(int)d];
 }
 
-bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
-                                             uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_boolean_after_batch_flat", kDialectBoolean, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
-}
-
-// ---- any-of groups in boolean queries (host/grouped.hpp) -------------------------------------------------
-bool Engine::search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
-                                             uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_grouped_after_batch_flat", kDialectGrouped, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
-}
-
-bool Engine::facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
-                                      uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    return boolean_facet_impl("facet_grouped_batch_flat", kDialectGrouped, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
-}
-
-bool Engine::search_grouped_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
-                                              uint8_t* usable, float* device_ms) {
-    return boolean_sorted_impl("search_grouped_sorted_batch_flat", kDialectGrouped, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
-}
-
-// boolean_refs_range over parse_grouped's dialect, with the clause id of every ref next to its role; false, with a message, when
-// a query has more clauses than a clause value can name
-bool Engine::grouped_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
+// Descriptors, refs and roles of the queries [a, b) in the dialect's grammar.  A MUST term gets a ref in every listed segment,
+// with count == 0 where the segment has no list of it: nothing of the segment matches a lone term, and a clause loses a
+// member.  Grouped adds the clause id of every ref, Quorum its need too: an unknown member is dropped and the need stays.
+// False, with a message, when a Grouped or Quorum query has more clauses than a clause value can name, or a Quorum query asks
+// for more than kQuorumMaxNeed of a clause's terms.  Boolean never fails.
+bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* queries, size_t a, size_t b, uint8_t* usable, CallPrep& bp) {
+    const bool with_clauses = dialect != nsx::Dialect::Boolean, with_needs = dialect == nsx::Dialect::Quorum;
     const uint32_t S = (uint32_t)segments.size();
     const nsx::RowSource& rs = bp.rs;
     bp.qd.assign(b - a, ns_query_desc{0, 0});
     bp.refs.clear();
     bp.roles.clear();
     bp.clauses.clear();
-    for (size_t q = a; q < b; q++) {
-        bp.terms.clear();
-        bp.term_clauses.clear();
-        size_t positive = 0;
-        const uint32_t n_clauses = nsx::for_each_grouped_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause) {
-            bp.terms.emplace_back(dict.find(p, n), role);
-            bp.term_clauses.push_back(clause);
-            positive += role != nsx::kRoleNot;
-        });
-        if (n_clauses > 65535u) { err_ = std::string(fn) + ": query " + std::to_string(q) + " has " + std::to_string(n_clauses) + " required clauses (at most 65535)"; return false; }
-        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
-        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
-        if (!usable[q]) continue;
-        for (const uint32_t sid : bp.listed)
-            for (size_t i = 0; i < bp.terms.size(); i++) {
-                const auto& t = bp.terms[i];
-                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
-                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
-                else if (t.second == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
-                else continue;
-                bp.roles.push_back(t.second);
-                bp.clauses.push_back((uint16_t)bp.term_clauses[i]);
-            }
-        bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
-    }
-    return true;
-}
-
-// What search_boolean_batch_flat, facet_boolean_batch_flat and search_boolean_sorted_batch_flat share.  boolean_prepare: the
-// filter's row source under a handle and the segments the refs can name, in manifest order (the index's own, or the filter's
-// copies).  boolean_refs_range: descriptors, refs and roles of the queries [a, b) (qd indexed from a) and usable[a .. b).
-bool Engine::boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp) {
-    if (filter_handle) {
-        bp.f = filter_of(filter_handle);
-        if (!bp.f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
-    }
-    const uint32_t S = (uint32_t)segments.size();
-    if (bp.f) {   // search_filtered_batch_flat's row source
-        bp.rs.rows = bp.f->rows.data();
-        bp.rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
-        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
-        if (!bp.rs.rows) bp.rs.rows = &no_rows;
-    }
-    bp.is_listed.assign(S, 0);
-    for (uint32_t s = 0; s < S; s++) {
-        ns_seg* h = bp.f ? bp.f->segs[s] : dev_segs_[s];
-        if (!h) continue;
-        bp.is_listed[s] = 1;
-        bp.listed.push_back(s);
-        bp.ids.push_back(bp.rs.id_base + s);
-        bp.segs.push_back(h);
-    }
-    return true;
-}
-
-void Engine::boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
-    const uint32_t S = (uint32_t)segments.size();
-    const nsx::RowSource& rs = bp.rs;
-    bp.qd.assign(b - a, ns_query_desc{0, 0});
-    bp.refs.clear();
-    bp.roles.clear();
+    bp.needs.clear();
     for (size_t q = a; q < b; q++) {
         bp.terms.clear();
         size_t positive = 0;
-        nsx::for_each_boolean_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role) {
-            bp.terms.emplace_back(dict.find(p, n), role);
+        uint32_t largest = 0;
+        const nsx::QuorumShape shape = nsx::for_each_term(dialect, queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
+            bp.terms.push_back(CallPrep::Term{dict.find(p, n), role, clause, need});
             positive += role != nsx::kRoleNot;
+            largest = std::max(largest, need);
         });
-        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
-        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
-        if (!usable[q]) continue;
-        for (const uint32_t sid : bp.listed)
-            for (const auto& t : bp.terms) {
-                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
-                if (e && e->byte_off != nsx::kAbsent) {
-                    bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
-                    bp.roles.push_back(t.second);
-                } else if (t.second == nsx::kRoleMust) {   // the segment has no list of a required term: nothing of it matches
-                    bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});
-                    bp.roles.push_back(t.second);
+        uint32_t n_clauses = shape.n_clauses;
+        if (shape.min_should) {   // `~m`: every optional term joins one more required clause of need m
+            bool any = false;
+            for (CallPrep::Term& t : bp.terms)
+                if (t.role == nsx::kRoleShould) {
+                    t = CallPrep::Term{t.row, nsx::kRoleMust, shape.n_clauses, shape.min_should};
+                    any = true;
                 }
+            if (any) n_clauses++;
+            largest = std::max(largest, shape.min_should);   // refused above the limit whether or not a term is there to promote
+        }
+        if (with_clauses && n_clauses > 65535u) { err_ = std::string(fn) + ": query " + std::to_string(q) + " has " + std::to_string(n_clauses) + " required clauses (at most 65535)"; return false; }
+        if (with_needs && largest > nsx::kQuorumMaxNeed) {
+            err_ = std::string(fn) + ": query " + std::to_string(q) + " asks for " + std::to_string(largest) + " of a clause's terms (at most " + std::to_string(nsx::kQuorumMaxNeed) + ")";
+            return false;
+        }
+        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
+        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
+        if (!usable[q]) continue;
+        for (const uint32_t sid : bp.listed)
+            for (const CallPrep::Term& t : bp.terms) {
+                const nsx::TermSeg* e = t.row < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.row * S + sid] : &dict.row((uint32_t)t.row)[sid];
+                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                else if (t.role == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
+                else continue;
+                bp.roles.push_back(t.role);
+                if (with_clauses) bp.clauses.push_back((uint16_t)t.clause);
+                if (with_needs) bp.needs.push_back((uint8_t)t.need);
             }
         bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
     }
+    return true;
 }
 
-bool Engine::boolean_batch_impl(const char* fn, int dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+// The device calls by dialect.  The boolean call receives no clauses and the grouped call no needs: those NULLs select the
+// kernels (§5w: the QUORUM instantiations are 5-7 % slower), and each dialect keeps its C entry point and so its messages.
+bool Engine::ranked_call(nsx::Dialect dialect, bool paged, const CallPrep& bp, size_t a, size_t b, const RankedOut& out, const ns_cursor* cur, float* ms) {
+    const uint32_t nq = (uint32_t)(b - a), n_refs = (uint32_t)bp.refs.size(), n_segs = (uint32_t)bp.ids.size(), K = (uint32_t)out.K;
+    ns_hit* hits = out.hits + a * out.K;
+    uint64_t* rest = out.rest ? out.rest + a : nullptr;
+    const char* name = nullptr;
+    int rc = NS_OK;
+    switch (dialect) {
+        case nsx::Dialect::Boolean:
+            name = paged ? "ns_search_boolean_after: " : "ns_search_boolean: ";
+            rc = ns_search_boolean_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), n_refs, K, cur, bp.ids.data(), bp.segs.data(), n_segs, hits, out.nhits + a,
+                                         out.found + a, rest, ms);
+            break;
+        case nsx::Dialect::Grouped:
+            name = "ns_search_grouped_after: ";
+            rc = ns_search_grouped_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), n_refs, K, cur, bp.ids.data(), bp.segs.data(), n_segs,
+                                         hits, out.nhits + a, out.found + a, rest, ms);
+            break;
+        case nsx::Dialect::Quorum:
+            name = "ns_search_quorum_after: ";
+            rc = ns_search_quorum_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, cur, bp.ids.data(),
+                                        bp.segs.data(), n_segs, hits, out.nhits + a, out.found + a, rest, ms);
+            break;
+    }
+    if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
+    return true;
+}
+
+bool Engine::facet_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size_t b, ns_facet* const* tabs, uint32_t* counts, uint64_t* found, float* ms) {
+    const uint32_t nq = (uint32_t)(b - a), n_refs = (uint32_t)bp.refs.size(), n_segs = (uint32_t)bp.ids.size();
+    const char* name = nullptr;
+    int rc = NS_OK;
+    switch (dialect) {
+        case nsx::Dialect::Boolean:
+            name = "ns_facet_count_boolean: ";
+            rc = ns_facet_count_boolean(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), n_refs, bp.ids.data(), bp.segs.data(), tabs, n_segs, counts, found, ms);
+            break;
+        case nsx::Dialect::Grouped:
+            name = "ns_facet_count_grouped: ";
+            rc = ns_facet_count_grouped(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), n_refs, bp.ids.data(), bp.segs.data(), tabs, n_segs, counts,
+                                        found, ms);
+            break;
+        case nsx::Dialect::Quorum:
+            name = "ns_facet_count_quorum: ";
+            rc = ns_facet_count_quorum(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, bp.ids.data(), bp.segs.data(), tabs,
+                                       n_segs, counts, found, ms);
+            break;
+    }
+    if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
+    return true;
+}
+
+bool Engine::sorted_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size_t b, uint32_t direction, ns_dockeys* const* tabs, const RankedOut& out,
+                         const ns_cursor* cur, float* ms) {
+    const uint32_t nq = (uint32_t)(b - a), n_refs = (uint32_t)bp.refs.size(), n_segs = (uint32_t)bp.ids.size(), K = (uint32_t)out.K;
+    ns_hit* hits = out.hits + a * out.K;
+    uint32_t* keys = out.keys + a * out.K;
+    uint64_t* rest = out.rest ? out.rest + a : nullptr;
+    const char* name = nullptr;
+    int rc = NS_OK;
+    switch (dialect) {
+        case nsx::Dialect::Boolean:
+            name = "ns_search_sorted_boolean: ";
+            rc = ns_search_sorted_boolean(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), n_refs, K, direction, cur, bp.ids.data(), bp.segs.data(), tabs, n_segs, hits,
+                                          keys, out.nhits + a, out.found + a, rest, ms);
+            break;
+        case nsx::Dialect::Grouped:
+            name = "ns_search_sorted_grouped: ";
+            rc = ns_search_sorted_grouped(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), n_refs, K, direction, cur, bp.ids.data(), bp.segs.data(),
+                                          tabs, n_segs, hits, keys, out.nhits + a, out.found + a, rest, ms);
+            break;
+        case nsx::Dialect::Quorum:
+            name = "ns_search_sorted_quorum: ";
+            rc = ns_search_sorted_quorum(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, direction, cur, bp.ids.data(),
+                                         bp.segs.data(), tabs, n_segs, hits, keys, out.nhits + a, out.found + a, rest, ms);
+            break;
+    }
+    if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
+    return true;
+}
+
+bool Engine::boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
                                 ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
-    BooleanPrep bp;
+    CallPrep bp;
     if (!boolean_prepare(fn, filter_handle, bp)) return false;
     if (Q == 0) return true;
-    const size_t K = (size_t)std::max(1, std::min(k, 100));
-    std::vector<ns_cursor> cur;
-    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
-        if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
+    const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, nullptr, nhits, found, rest, device_ms};
+    return ranked_batch(fn, bp, after, Q, out,
+        [&](size_t a, size_t b) { return refs_range(fn, dialect, queries, a, b, usable, bp); },
+        [&](size_t a, size_t b, const ns_cursor* cur, float* ms) { return ranked_call(dialect, after != nullptr, bp, a, b, out, cur, ms); });
+}
+
+bool Engine::search_dialect_after_batch_flat(nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+                                             ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl(names_of(dialect).after_batch, dialect, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_dialect_batch_flat(nsx::Dialect dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                                      std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    const char* fn = names_of(dialect).facet_batch;
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    counts.clear();
+    labels.clear();
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: facets are counted on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    CallPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    FacetSet* fs = nullptr;
+    if (!ensure_facets(spec, fs)) return false;
+    labels = fs->labels;
+    const size_t B = labels.size();
+    counts.assign(Q * B, 0u);
+    if (Q == 0) return true;
+    std::vector<ns_facet*> tabs;
+    for (const uint32_t s : bp.listed) {
+        if (!fs->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no bucket table on the device"; return false; }
+        tabs.push_back(fs->dev[s]);
+    }
+    return for_each_sub_batch(Q, [&](size_t a, size_t b) {
+        if (!refs_range(fn, dialect, queries, a, b, usable, bp)) return false;
         if (bp.ids.empty()) {   // nothing on the device: no ref can exist
             std::fill(found + a, found + b, (uint64_t)0);
-            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
-            std::fill(nhits + a, nhits + b, 0u);
-            std::fill(hits + a * K, hits + b * K, pad);
-            continue;
+            return true;
         }
         float ms = 0.0f;
-        const int rc = quorum  ? ns_search_quorum_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
-                                                        (uint32_t)bp.refs.size(), (uint32_t)K, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
-                                                        (uint32_t)bp.ids.size(), hits + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
-                       : grouped ? ns_search_grouped_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
-                                                         (uint32_t)bp.refs.size(), (uint32_t)K, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
-                                                         (uint32_t)bp.ids.size(), hits + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
-                               : ns_search_boolean_after(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
-                                                         cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * K, nhits + a,
-                                                         found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_search_quorum_after: " : grouped ? "ns_search_grouped_after: " : after ? "ns_search_boolean_after: " : "ns_search_boolean: ") + ns_last_error(ctx_); return false; }
+        if (!facet_call(dialect, bp, a, b, tabs.data(), counts.data() + a * B, found + a, &ms)) return false;
         if (device_ms) *device_ms += ms;
-        for (size_t q = a; q < b; q++)
-            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
+        return true;
+    });
+}
+
+bool Engine::search_dialect_sorted_batch_flat(nsx::Dialect dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                              uint8_t* usable, float* device_ms) {
+    const char* fn = names_of(dialect).sorted_batch;
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    CallPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    SortSet* ss = nullptr;
+    if (!ensure_sorted(spec, ss)) return false;
+    if (Q == 0) return true;
+    std::vector<ns_dockeys*> tabs;
+    for (const uint32_t s : bp.listed) {
+        if (!ss->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no key table on the device"; return false; }
+        tabs.push_back(ss->dev[s]);
     }
-    return true;
+    const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, keys, nhits, found, rest, device_ms};
+    const uint32_t direction = spec.ascending ? NS_SORT_ASC : NS_SORT_DESC;
+    return ranked_batch(fn, bp, after, Q, out,
+        [&](size_t a, size_t b) { return refs_range(fn, dialect, queries, a, b, usable, bp); },
+        [&](size_t a, size_t b, const ns_cursor* cur, float* ms) { return sorted_call(dialect, bp, a, b, direction, tabs.data(), out, cur, ms); });
+}
+
+// one `"name": [strings]` member of a dialect's member, four spaces in: the texts of the terms that `in` keeps, in query order
+template <class T, class In>
+static void append_term_list(std::string& o, const char* name, const std::vector<T>& terms, In in, bool last) {
+    o += std::string("    \"") + name + "\": [";
+    bool any = false;
+    for (const T& t : terms)
+        if (in(t)) {
+            o += any ? ",\n      " : "\n      ";
+            json_escape(o, t.text);
+            any = true;
+        }
+    o += any ? "\n    ]" : "]";
+    o += last ? "\n" : ",\n";
 }
 
 // the "boolean" member of search_boolean's body (the parsed terms by role, in query order), with the comma and newline behind it
 static std::string boolean_member(const std::string& query) {
     const std::vector<nsx::BoolTerm> terms = nsx::parse_boolean(query);
     std::string o = "  \"boolean\": {\n";
-    static const struct { const char* name; uint8_t role; } kMembers[3] = {{"must", nsx::kRoleMust}, {"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
-    for (int m = 0; m < 3; m++) {
-        o += std::string("    \"") + kMembers[m].name + "\": [";
-        bool any = false;
-        for (const nsx::BoolTerm& t : terms)
-            if (t.role == kMembers[m].role) {
-                o += any ? ",\n      " : "\n      ";
-                json_escape(o, t.text);
-                any = true;
-            }
-        o += any ? "\n    ]" : "]";
-        o += m < 2 ? ",\n" : "\n";
-    }
+    append_term_list(o, "must", terms, [](const nsx::BoolTerm& t) { return t.role == nsx::kRoleMust; }, false);
+    append_term_list(o, "must_not", terms, [](const nsx::BoolTerm& t) { return t.role == nsx::kRoleNot; }, false);
+    append_term_list(o, "should", terms, [](const nsx::BoolTerm& t) { return t.role == nsx::kRoleShould; }, true);
     o += "  },\n";
     return o;
 }
@@ -2613,19 +2649,8 @@ static std::string grouped_member(const std::string& query) {
         any_clause = true;
     }
     o += any_clause ? "\n    ],\n" : "],\n";
-    static const struct { const char* name; uint8_t role; } kMembers[2] = {{"must_not", nsx::kRoleNot}, {"should", nsx::kRoleShould}};
-    for (int m = 0; m < 2; m++) {
-        o += std::string("    \"") + kMembers[m].name + "\": [";
-        bool any = false;
-        for (const nsx::GroupedTerm& t : terms)
-            if (t.role == kMembers[m].role) {
-                o += any ? ",\n      " : "\n      ";
-                json_escape(o, t.text);
-                any = true;
-            }
-        o += any ? "\n    ]" : "]";
-        o += m < 1 ? ",\n" : "\n";
-    }
+    append_term_list(o, "must_not", terms, [](const nsx::GroupedTerm& t) { return t.role == nsx::kRoleNot; }, false);
+    append_term_list(o, "should", terms, [](const nsx::GroupedTerm& t) { return t.role == nsx::kRoleShould; }, true);
     o += "  },\n";
     return o;
 }
@@ -2666,18 +2691,8 @@ static std::string quorum_member(const std::string& query) {
         any_clause = true;
     }
     o += any_clause ? "\n    ],\n" : "],\n";
-    for (int m = 0; m < 2; m++) {
-        o += std::string("    \"") + (m ? "should" : "must_not") + "\": [";
-        bool any = false;
-        for (const nsx::QuorumTerm& t : terms)
-            if (m ? (t.role == nsx::kRoleShould || t.promoted) : t.role == nsx::kRoleNot) {
-                o += any ? ",\n      " : "\n      ";
-                json_escape(o, t.text);
-                any = true;
-            }
-        o += any ? "\n    ]" : "]";
-        o += m < 1 ? ",\n" : "\n";
-    }
+    append_term_list(o, "must_not", terms, [](const nsx::QuorumTerm& t) { return t.role == nsx::kRoleNot; }, false);
+    append_term_list(o, "should", terms, [](const nsx::QuorumTerm& t) { return t.role == nsx::kRoleShould || t.promoted; }, true);
     o += "  },\n";
     return o;
 }
@@ -2690,107 +2705,20 @@ static bool quorum_insert(std::string& tail, const std::string& query) {
     return true;
 }
 
-// ---- at-least-m-of-n clauses (host/quorum.hpp) -----------------------------------------------------------
-bool Engine::search_quorum_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
-                                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl("search_quorum_after_batch_flat", kDialectQuorum, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
-}
-
-bool Engine::facet_quorum_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
-                                     uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    return boolean_facet_impl("facet_quorum_batch_flat", kDialectQuorum, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
-}
-
-bool Engine::search_quorum_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
-                                             uint8_t* usable, float* device_ms) {
-    return boolean_sorted_impl("search_quorum_sorted_batch_flat", kDialectQuorum, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
-}
-
-// grouped_refs_range over parse_quorum's dialect, with the need of every ref next to its clause id: an unknown member is dropped
-// (a ref with count == 0) and the need stays.  False, with a message, when a query has more clauses than a clause value can name
-// or asks for more than kQuorumMaxNeed of a clause's terms.
-bool Engine::quorum_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp) {
-    const uint32_t S = (uint32_t)segments.size();
-    const nsx::RowSource& rs = bp.rs;
-    bp.qd.assign(b - a, ns_query_desc{0, 0});
-    bp.refs.clear();
-    bp.roles.clear();
-    bp.clauses.clear();
-    bp.needs.clear();
-    for (size_t q = a; q < b; q++) {
-        bp.terms.clear();
-        bp.term_clauses.clear();
-        bp.term_needs.clear();
-        uint32_t largest = 0;
-        const nsx::QuorumShape shape = nsx::for_each_quorum_term(queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
-            bp.terms.emplace_back(dict.find(p, n), role);
-            bp.term_clauses.push_back(clause);
-            bp.term_needs.push_back(need);
-            largest = std::max(largest, need);
-        });
-        uint32_t n_clauses = shape.n_clauses;
-        if (shape.min_should) {   // `~m`: every optional term joins one more required clause of need m
-            bool any = false;
-            for (size_t i = 0; i < bp.terms.size(); i++)
-                if (bp.terms[i].second == nsx::kRoleShould) {
-                    bp.terms[i].second = nsx::kRoleMust;
-                    bp.term_clauses[i] = shape.n_clauses;
-                    bp.term_needs[i] = shape.min_should;
-                    any = true;
-                }
-            if (any) n_clauses++;
-            largest = std::max(largest, shape.min_should);   // refused above the limit whether or not a term is there to promote
-        }
-        if (n_clauses > 65535u) { err_ = std::string(fn) + ": query " + std::to_string(q) + " has " + std::to_string(n_clauses) + " required clauses (at most 65535)"; return false; }
-        if (largest > nsx::kQuorumMaxNeed) {
-            err_ = std::string(fn) + ": query " + std::to_string(q) + " asks for " + std::to_string(largest) + " of a clause's terms (at most " + std::to_string(nsx::kQuorumMaxNeed) + ")";
-            return false;
-        }
-        size_t positive = 0;
-        for (const auto& t : bp.terms) positive += t.second != nsx::kRoleNot;
-        bp.qd[q - a].term_begin = (uint32_t)bp.refs.size();
-        usable[q] = (positive != 0 && S != 0) ? 1 : 0;
-        if (!usable[q]) continue;
-        for (const uint32_t sid : bp.listed)
-            for (size_t i = 0; i < bp.terms.size(); i++) {
-                const auto& t = bp.terms[i];
-                const nsx::TermSeg* e = t.first < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.first * S + sid] : &dict.row((uint32_t)t.first)[sid];
-                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
-                else if (t.second == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
-                else continue;
-                bp.roles.push_back(t.second);
-                bp.clauses.push_back((uint16_t)bp.term_clauses[i]);
-                bp.needs.push_back((uint8_t)bp.term_needs[i]);
-            }
-        bp.qd[q - a].term_count = (uint32_t)bp.refs.size() - bp.qd[q - a].term_begin;
+// The dialect's member (the parsed query) put into a body in its sorted place (nlohmann keeps keys sorted).  front: "{\n" and
+// the "filter" member if there is one; tail: to_json_impl's members.  "boolean" is the body's first member; "grouped" stands in
+// front of tail's "k", "quorum" in front of tail's "results".  -> nullptr, or the name of the member that tail lacks
+static const char* insert_dialect_member(nsx::Dialect dialect, const std::string& query, std::string& front, std::string& tail) {
+    switch (dialect) {
+        case nsx::Dialect::Boolean: front.insert(2, boolean_member(query)); return nullptr;
+        case nsx::Dialect::Grouped: return grouped_insert(tail, query) ? nullptr : "k";
+        default: return quorum_insert(tail, query) ? nullptr : "results";
     }
-    return true;
 }
 
-bool Engine::search_quorum_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    return boolean_text_impl("search_quorum", kDialectQuorum, query, k, f, body);
-}
-
-bool Engine::search_quorum_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_faceted_text_impl("search_quorum_faceted", kDialectQuorum, query, k, spec, f, body);
-}
-
-bool Engine::search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_sorted_text_impl("search_quorum_sorted", kDialectQuorum, query, k, spec, f, body);
-}
-
-bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    return boolean_text_impl("search_boolean", kDialectBoolean, query, k, f, body);
-}
-
-bool Engine::search_grouped_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    return boolean_text_impl("search_grouped", kDialectGrouped, query, k, f, body);
-}
-
-// search_boolean's body, or (grouped) the same body over parse_grouped's dialect with "grouped" in place of "boolean"
-bool Engine::boolean_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
+// search_boolean's body, or the same body over another dialect with its member in place of "boolean"
+bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    const char* name = names_of(dialect).text;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
     const int K = std::max(1, std::min(k, 100));
@@ -2809,9 +2737,7 @@ bool Engine::boolean_text_impl(const char* name, int dialect, const std::string&
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(quorum    ? search_quorum_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
-          : grouped ? search_grouped_after_batch_flat(handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us)
-                    : search_boolean_batch_flat(handle, &qv, 1, K, hits.data(), &nh, &fd, &us))) { body = err_; return false; }
+    if (!boolean_batch_impl(names_of(dialect).first_page, dialect, handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us, nullptr)) { body = err_; return false; }
     SearchResult res;
     res.query = query;
     res.k = K;
@@ -2820,235 +2746,41 @@ bool Engine::boolean_text_impl(const char* name, int dialect, const std::string&
     res.found = fd;
     if (res.has_found)
         for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
-    // "boolean" < "filter" < "found": nlohmann keeps keys sorted, so the member sits in front
-    if (!grouped) { body = "{\n" + boolean_member(query) + head.substr(2) + to_json_impl(res).substr(2); return true; }
     std::string tail = to_json_impl(res).substr(2);
-    if (quorum ? !quorum_insert(tail, query) : !grouped_insert(tail, query)) { body = err_ = std::string(name) + ": the search body has no " + (quorum ? "results" : "k") + " member"; return false; }
+    if (const char* missing = insert_dialect_member(dialect, query, head, tail)) { body = err_ = std::string(name) + ": the search body has no " + missing + " member"; return false; }
     body = head + tail;
     return true;
 }
 
-static std::string error_body(const std::string& why) {
-    std::string o = "{\n  \"error\": ";
-    json_escape(o, why);
-    o += "\n}";
-    return o;
-}
-
-std::string Engine::search_quorum(const std::string& query, int k, const nsx::DocFilter* f) {
-    std::string body;
-    return search_quorum_text(query, k, f, body) ? body : error_body(body);
-}
-
-std::string Engine::search_quorum_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
-    std::string body;
-    return search_quorum_faceted_text(query, k, spec, f, body) ? body : error_body(body);
-}
-
-std::string Engine::search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
-    std::string body;
-    return search_quorum_sorted_text(query, k, spec, f, body) ? body : error_body(body);
-}
-
-std::string Engine::search_grouped(const std::string& query, int k, const nsx::DocFilter* f) {
-    std::string body;
-    return search_grouped_text(query, k, f, body) ? body : error_body(body);
-}
-
-std::string Engine::search_grouped_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
-    std::string body;
-    return search_grouped_faceted_text(query, k, spec, f, body) ? body : error_body(body);
-}
-
-std::string Engine::search_grouped_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
-    std::string body;
-    return search_grouped_sorted_text(query, k, spec, f, body) ? body : error_body(body);
-}
-
-bool Engine::search_grouped_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_faceted_text_impl("search_grouped_faceted", kDialectGrouped, query, k, spec, f, body);
-}
-
-bool Engine::search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_sorted_text_impl("search_grouped_sorted", kDialectGrouped, query, k, spec, f, body);
-}
-
-std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
-    std::string body;
-    if (!search_boolean_text(query, k, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
-}
-
-// ---- facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip) --------------------------
-bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
-                                      uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    return boolean_facet_impl("facet_boolean_batch_flat", kDialectBoolean, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
-}
-
-bool Engine::boolean_facet_impl(const char* fn, int dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
-                                std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
-    std::lock_guard<std::recursive_mutex> lock(mtx_);
-    counts.clear();
-    labels.clear();
-    if (device_ms) *device_ms = 0.0f;
-    if (!ctx_) { err_ = std::string(fn) + ": no device context: facets are counted on the device, there is no CPU path"; return false; }
-    if (Q && (!queries || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
-    BooleanPrep bp;
-    if (!boolean_prepare(fn, filter_handle, bp)) return false;
-    FacetSet* fs = nullptr;
-    if (!ensure_facets(spec, fs)) return false;
-    labels = fs->labels;
-    const size_t B = labels.size();
-    counts.assign(Q * B, 0u);
-    if (Q == 0) return true;
-    std::vector<ns_facet*> tabs;
-    for (const uint32_t s : bp.listed) {
-        if (!fs->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no bucket table on the device"; return false; }
-        tabs.push_back(fs->dev[s]);
-    }
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
-        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
-            std::fill(found + a, found + b, (uint64_t)0);
-            continue;
-        }
-        float ms = 0.0f;
-        const int rc = quorum  ? ns_facet_count_quorum(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
-                                                       (uint32_t)bp.refs.size(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
-                                                       counts.data() + a * B, found + a, &ms)
-                       : grouped ? ns_facet_count_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
-                                                        (uint32_t)bp.refs.size(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
-                                                        counts.data() + a * B, found + a, &ms)
-                               : ns_facet_count_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), bp.ids.data(),
-                                                        bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(), counts.data() + a * B, found + a, &ms);
-        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_facet_count_quorum: " : grouped ? "ns_facet_count_grouped: " : "ns_facet_count_boolean: ") + ns_last_error(ctx_); return false; }
-        if (device_ms) *device_ms += ms;
-    }
-    return true;
-}
-
-bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                                              const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
-                                              uint8_t* usable, float* device_ms) {
-    return boolean_sorted_impl("search_boolean_sorted_batch_flat", kDialectBoolean, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
-}
-
-bool Engine::boolean_sorted_impl(const char* fn, int dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                                 const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
-                                 float* device_ms) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
-    std::lock_guard<std::recursive_mutex> lock(mtx_);
-    if (device_ms) *device_ms = 0.0f;
-    if (!ctx_) { err_ = std::string(fn) + ": no device context: the sorted search runs on the device, there is no CPU path"; return false; }
-    if (Q && (!queries || !hits || !keys || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
-    BooleanPrep bp;
-    if (!boolean_prepare(fn, filter_handle, bp)) return false;
-    SortSet* ss = nullptr;
-    if (!ensure_sorted(spec, ss)) return false;
-    if (Q == 0) return true;
-    const size_t K = (size_t)std::max(1, std::min(k, 100));
-    std::vector<ns_dockeys*> tabs;
-    for (const uint32_t s : bp.listed) {
-        if (!ss->dev[s]) { err_ = std::string(fn) + ": segment " + std::to_string(s) + " has no key table on the device"; return false; }
-        tabs.push_back(ss->dev[s]);
-    }
-    std::vector<ns_cursor> cur;
-    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        if (!grouped) boolean_refs_range(queries, a, b, usable, bp);
-        else if (!(quorum ? quorum_refs_range(fn, queries, a, b, usable, bp) : grouped_refs_range(fn, queries, a, b, usable, bp))) return false;
-        if (!translate_cursors(fn, after, a, b, bp.rs.id_base, bp.is_listed, bp.f != nullptr, cur)) return false;
-        if (bp.ids.empty()) {   // nothing on the device: no ref can exist
-            std::fill(found + a, found + b, (uint64_t)0);
-            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
-            std::fill(nhits + a, nhits + b, 0u);
-            std::fill(hits + a * K, hits + b * K, pad);
-            std::fill(keys + a * K, keys + b * K, 0u);
-            continue;
-        }
-        float ms = 0.0f;
-        const int rc = quorum  ? ns_search_sorted_quorum(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
-                                                         (uint32_t)bp.refs.size(), (uint32_t)K, spec.ascending ? NS_SORT_ASC : NS_SORT_DESC,
-                                                         cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
-                                                         hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
-                       : grouped ? ns_search_sorted_grouped(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(),
-                                                          (uint32_t)bp.refs.size(), (uint32_t)K, spec.ascending ? NS_SORT_ASC : NS_SORT_DESC,
-                                                          cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(), tabs.data(), (uint32_t)bp.ids.size(),
-                                                          hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms)
-                               : ns_search_sorted_boolean(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), (uint32_t)bp.refs.size(), (uint32_t)K,
-                                                          spec.ascending ? NS_SORT_ASC : NS_SORT_DESC, cur.empty() ? nullptr : cur.data(), bp.ids.data(), bp.segs.data(),
-                                                          tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, keys + a * K, nhits + a, found + a, rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string(quorum ? "ns_search_sorted_quorum: " : grouped ? "ns_search_sorted_grouped: " : "ns_search_sorted_boolean: ") + ns_last_error(ctx_); return false; }
-        if (device_ms) *device_ms += ms;
-        for (size_t q = a; q < b; q++)
-            for (uint32_t j = 0; j < nhits[q]; j++) hits[q * K + j].seg_id -= bp.rs.id_base;   // manifest positions
-    }
-    return true;
-}
-
-bool Engine::search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_faceted_text_impl("search_boolean_faceted", kDialectBoolean, query, k, spec, f, body);
-}
-
-bool Engine::boolean_faceted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
-                                       std::string& body) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
+bool Engine::search_dialect_faceted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    const char* name = names_of(dialect).faceted_text;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
-    if (!(quorum ? search_quorum_text(query, k, f, body) : grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
+    if (!search_dialect_text(dialect, query, k, f, body)) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const QueryView qv{query.data(), query.size()};
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(quorum ? facet_quorum_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : grouped ? facet_grouped_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels) : facet_boolean_batch_flat(spec, handle, &qv, 1, counts, &fd, &us, labels))) { body = err_; return false; }
-    // "boolean" < "facets" < "filter" < "found": the member goes behind the "boolean" member, which is the body's first and whose
-    // strings are escaped, so that its closing line is the first of that form
-    const size_t at = body.find("\n  },\n");
-    if (grouped) {   // "facets" < "filter" < "found" < "grouped": the member is the body's first
+    if (!facet_dialect_batch_flat(dialect, spec, handle, &qv, 1, counts, &fd, &us, labels)) { body = err_; return false; }
+    if (dialect != nsx::Dialect::Boolean) {   // "facets" < "filter" < "found" < "grouped" < "quorum": the member is the body's first
         body.insert(2, facets_member(spec, labels, counts));
         return true;
     }
+    // "boolean" < "facets" < "filter" < "found": the member goes behind the "boolean" member, which is the body's first and whose
+    // strings are escaped, so that its closing line is the first of that form
+    const size_t at = body.find("\n  },\n");
     if (body.compare(0, 15, "{\n  \"boolean\": ") != 0 || at == std::string::npos) { body = err_ = std::string(name) + ": the boolean body has no boolean member"; return false; }
     body.insert(at + 6, facets_member(spec, labels, counts));
     return true;
 }
 
-std::string Engine::search_boolean_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
-    std::string body;
-    if (!search_boolean_faceted_text(query, k, spec, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
-}
-
-bool Engine::search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
-    return boolean_sorted_text_impl("search_boolean_sorted", kDialectBoolean, query, k, spec, f, body);
-}
-
-bool Engine::boolean_sorted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
-                                      std::string& body) {
-    const bool grouped = dialect != kDialectBoolean, quorum = dialect == kDialectQuorum;
+bool Engine::search_dialect_sorted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    const char* name = names_of(dialect).sorted_text;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
-    if (!(quorum ? search_quorum_text(query, k, f, body) : grouped ? search_grouped_text(query, k, f, body) : search_boolean_text(query, k, f, body))) return false;
+    if (!search_dialect_text(dialect, query, k, f, body)) return false;
     const uint32_t handle = f ? filter_lru_.front().handle : 0u;   // search_boolean's filter is the most recently used of the cache
     const size_t K = (size_t)std::max(1, std::min(k, 100));
     const QueryView qv{query.data(), query.size()};
@@ -3057,9 +2789,7 @@ bool Engine::boolean_sorted_text_impl(const char* name, int dialect, const std::
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!(quorum    ? search_quorum_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
-          : grouped ? search_grouped_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)
-                  : search_boolean_sorted_batch_flat(spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us))) { body = err_; return false; }
+    if (!search_dialect_sorted_batch_flat(dialect, spec, handle, &qv, 1, (int)K, nullptr, hits.data(), keys.data(), &nh, &fd, nullptr, &us)) { body = err_; return false; }
     std::vector<SearchHit> sorted;
     if (us)
         for (uint32_t i = 0; i < nh; i++) sorted.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
@@ -3076,15 +2806,139 @@ bool Engine::boolean_sorted_text_impl(const char* name, int dialect, const std::
     return true;
 }
 
+// ---- the named methods: forwards to the dialect forms --------------------------------------------------------------------
+bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
+                                       uint64_t* found, uint8_t* usable, float* device_ms) {
+    return boolean_batch_impl(names_of(nsx::Dialect::Boolean).first_page, nsx::Dialect::Boolean, filter_handle, queries, Q, k, nullptr, hits, nhits, found, nullptr, usable, device_ms);
+}
+
+bool Engine::search_boolean_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return search_dialect_after_batch_flat(nsx::Dialect::Boolean, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_boolean_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                     uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    return facet_dialect_batch_flat(nsx::Dialect::Boolean, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::search_boolean_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                             uint8_t* usable, float* device_ms) {
+    return search_dialect_sorted_batch_flat(nsx::Dialect::Boolean, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::search_boolean_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_text(nsx::Dialect::Boolean, query, k, f, body);
+}
+
+bool Engine::search_boolean_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_faceted_text(nsx::Dialect::Boolean, query, k, spec, f, body);
+}
+
+bool Engine::search_boolean_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_sorted_text(nsx::Dialect::Boolean, query, k, spec, f, body);
+}
+
+std::string Engine::search_boolean(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_text(nsx::Dialect::Boolean, query, k, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_boolean_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_faceted_text(nsx::Dialect::Boolean, query, k, spec, f, body) ? body : error_body(body);
+}
+
 std::string Engine::search_boolean_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
     std::string body;
-    if (!search_boolean_sorted_text(query, k, spec, f, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_dialect_sorted_text(nsx::Dialect::Boolean, query, k, spec, f, body) ? body : error_body(body);
+}
+
+bool Engine::search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                            uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return search_dialect_after_batch_flat(nsx::Dialect::Grouped, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                     uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    return facet_dialect_batch_flat(nsx::Dialect::Grouped, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::search_grouped_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                             uint8_t* usable, float* device_ms) {
+    return search_dialect_sorted_batch_flat(nsx::Dialect::Grouped, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::search_grouped_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_text(nsx::Dialect::Grouped, query, k, f, body);
+}
+
+bool Engine::search_grouped_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_faceted_text(nsx::Dialect::Grouped, query, k, spec, f, body);
+}
+
+bool Engine::search_grouped_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_sorted_text(nsx::Dialect::Grouped, query, k, spec, f, body);
+}
+
+std::string Engine::search_grouped(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_text(nsx::Dialect::Grouped, query, k, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_grouped_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_faceted_text(nsx::Dialect::Grouped, query, k, spec, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_grouped_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_sorted_text(nsx::Dialect::Grouped, query, k, spec, f, body) ? body : error_body(body);
+}
+
+bool Engine::search_quorum_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
+                                           uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return search_dialect_after_batch_flat(nsx::Dialect::Quorum, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::facet_quorum_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
+                                    uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms) {
+    return facet_dialect_batch_flat(nsx::Dialect::Quorum, spec, filter_handle, queries, Q, counts, found, usable, labels, device_ms);
+}
+
+bool Engine::search_quorum_sorted_batch_flat(const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                            uint8_t* usable, float* device_ms) {
+    return search_dialect_sorted_batch_flat(nsx::Dialect::Quorum, spec, filter_handle, queries, Q, k, after, hits, keys, nhits, found, rest, usable, device_ms);
+}
+
+bool Engine::search_quorum_text(const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_text(nsx::Dialect::Quorum, query, k, f, body);
+}
+
+bool Engine::search_quorum_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_faceted_text(nsx::Dialect::Quorum, query, k, spec, f, body);
+}
+
+bool Engine::search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_sorted_text(nsx::Dialect::Quorum, query, k, spec, f, body);
+}
+
+std::string Engine::search_quorum(const std::string& query, int k, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_text(nsx::Dialect::Quorum, query, k, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_quorum_faceted(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_faceted_text(nsx::Dialect::Quorum, query, k, spec, f, body) ? body : error_body(body);
+}
+
+std::string Engine::search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_dialect_sorted_text(nsx::Dialect::Quorum, query, k, spec, f, body) ? body : error_body(body);
 }
 
 // ---- pages past the first K (host/page.hpp, csrc/ns_after_plan.hpp) -------------------------------------
@@ -3098,77 +2952,23 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
     if (!ctx_) { err_ = std::string(fn) + ": no device context: pages are cut on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
     if (flags & ~(uint32_t)NS_FLAG_AND) { err_ = std::string(fn) + ": flags are NS_FLAG_OR or NS_FLAG_AND"; return false; }
-    OpenFilter* f = nullptr;
-    if (filter_handle) {
-        f = filter_of(filter_handle);
-        if (!f) { err_ = std::string(fn) + ": handle " + std::to_string(filter_handle) + " is stale (the filter was closed, or the index was reloaded after it was opened)"; return false; }
-    }
+    CallPrep bp;
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
     if (Q == 0) return true;
-    const size_t K = (size_t)std::max(1, std::min(k, 100));
-    const uint32_t S = (uint32_t)segments.size();
     const bool and_mode = (flags & NS_FLAG_AND) != 0;
-    nsx::RowSource rs;
-    if (f) {   // search_filtered_batch_flat's row source
-        rs.rows = f->rows.data();
-        rs.id_base = (uint32_t)(filter_handle % kMaxFilters + 1) * S;
-        static const nsx::TermSeg no_rows{nsx::kAbsent, 0u, 0.0f};
-        if (!rs.rows) rs.rows = &no_rows;
-    }
-    std::vector<uint32_t> ids;
-    std::vector<ns_seg*> segs;
-    std::vector<uint8_t> listed(S, 0);
-    for (uint32_t s = 0; s < S; s++) {
-        ns_seg* h = f ? f->segs[s] : dev_segs_[s];
-        if (!h) continue;
-        listed[s] = 1;
-        ids.push_back(rs.id_base + s);
-        segs.push_back(h);
-    }
-    std::vector<ns_cursor> cur;
+    const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, nullptr, nhits, found, rest, device_ms};
     std::vector<uint8_t> roles;
-    const ns_hit pad{-std::numeric_limits<float>::infinity(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-    auto run = [&](const ns_query_desc* qd, size_t a, size_t b, const ns_term_ref* refs, size_t n_refs) {
-        if (!translate_cursors(fn, after, a, b, rs.id_base, listed, f != nullptr, cur)) return false;
-        if (ids.empty()) {   // nothing on the device: no ref can exist
-            std::fill(found + a, found + b, (uint64_t)0);
-            if (rest) std::fill(rest + a, rest + b, (uint64_t)0);
-            std::fill(nhits + a, nhits + b, 0u);
-            std::fill(hits + a * K, hits + b * K, pad);
+    PlainPrep pp;
+    if (!plain_prepare(queries, Q, usable, bp.rs, and_mode, pp)) return false;
+    return ranked_batch(fn, bp, after, Q, out,
+        [&](size_t a, size_t b) { plain_range(queries, a, b, usable, bp.rs, and_mode, pp); return true; },
+        [&](size_t a, size_t b, const ns_cursor* cur, float* ms) {
+            if (and_mode) roles.assign(pp.n_refs, nsx::kRoleMust);
+            const int rc = ns_search_boolean_after(ctx_, pp.qd_at, (uint32_t)(b - a), pp.refs_at, and_mode ? roles.data() : nullptr, (uint32_t)pp.n_refs, (uint32_t)out.K, cur,
+                                                   bp.ids.data(), bp.segs.data(), (uint32_t)bp.ids.size(), hits + a * out.K, nhits + a, found + a, rest ? rest + a : nullptr, ms);
+            if (rc != NS_OK) { err_ = std::string("ns_search_boolean_after: ") + ns_last_error(ctx_); return false; }
             return true;
-        }
-        if (and_mode) roles.assign(n_refs, nsx::kRoleMust);
-        float ms = 0.0f;
-        const int rc = ns_search_boolean_after(ctx_, qd, (uint32_t)(b - a), refs, and_mode ? roles.data() : nullptr, (uint32_t)n_refs, (uint32_t)K,
-                                               cur.empty() ? nullptr : cur.data(), ids.data(), segs.data(), (uint32_t)ids.size(), hits + a * K, nhits + a, found + a,
-                                               rest ? rest + a : nullptr, &ms);
-        if (rc != NS_OK) { err_ = std::string("ns_search_boolean_after: ") + ns_last_error(ctx_); return false; }
-        if (device_ms) *device_ms += ms;
-        for (size_t q = a; q < b; q++)
-            for (uint32_t i = 0; i < nhits[q]; i++) hits[q * K + i].seg_id -= rs.id_base;   // manifest positions
-        return true;
-    };
-    const size_t kSubBatch = sub_batch_size();
-    const size_t n_sub = Q >= 2 * kSubBatch ? (Q + kSubBatch - 1) / kSubBatch : 1;
-    if (sem.enabled) {   // the expansion of search_batch_flat for the whole batch, then the expanded terms sub-batch by sub-batch
-        std::vector<std::string> qs(Q);
-        for (size_t q = 0; q < Q; q++) qs[q].assign(queries[q].p, queries[q].n);
-        std::vector<nsx::WeightedTerms> expanded;
-        if (!expand_queries(qs, expanded)) return false;
-        std::vector<ns_query_desc> qd(Q, ns_query_desc{0, 0});
-        std::vector<ns_term_ref> refs;
-        std::vector<uint8_t> us(Q, 0);
-        build_refs_range(qs, 0, Q, qd, refs, us, &expanded, rs, and_mode);
-        std::memcpy(usable, us.data(), Q);
-        for (size_t i = 0; i < n_sub; i++)   // term_begin stays an index into the one refs array
-            if (!run(qd.data() + Q * i / n_sub, Q * i / n_sub, Q * (i + 1) / n_sub, refs.data(), refs.size())) return false;
-        return true;
-    }
-    for (size_t i = 0; i < n_sub; i++) {
-        const size_t a = Q * i / n_sub, b = Q * (i + 1) / n_sub;
-        build_refs_parallel(queries, a, b, flat_qd_, flat_refs_, usable + a, rs, and_mode);
-        if (!run(flat_qd_.data(), a, b, flat_refs_.data(), flat_refs_.size())) return false;
-    }
-    return true;
+        });
 }
 
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
@@ -3195,34 +2995,13 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     uint32_t nh = 0;
     uint64_t fd = 0, rs = 0;
     uint8_t us = 0;
+    const nsx::PageCall call = nsx::page_call(spec.mode);
     bool ok = false;
-    switch (spec.mode) {
-        case nsx::PageSpec::SearchOr:
-        case nsx::PageSpec::SearchAnd:
-            ok = search_after_batch_flat(handle, &qv, 1, K, spec.mode == nsx::PageSpec::SearchAnd ? NS_FLAG_AND : NS_FLAG_OR, &cur, hits.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::Boolean:
-            ok = search_boolean_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::Sorted:
-            ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::BooleanSorted:
-            ok = search_boolean_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::Grouped:
-            ok = search_grouped_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::GroupedSorted:
-            ok = search_grouped_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::Quorum:
-            ok = search_quorum_after_batch_flat(handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
-            break;
-        case nsx::PageSpec::QuorumSorted:
-            ok = search_quorum_sorted_batch_flat(spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
-            break;
-    }
+    if (!call.plain)
+        ok = call.dated ? search_dialect_sorted_batch_flat(call.dialect, spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us)
+                        : search_dialect_after_batch_flat(call.dialect, handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
+    else if (call.dated) ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
+    else ok = search_after_batch_flat(handle, &qv, 1, K, spec.mode == nsx::PageSpec::SearchAnd ? NS_FLAG_AND : NS_FLAG_OR, &cur, hits.data(), &nh, &fd, &rs, &us);
     if (!ok) { body = err_; return false; }
     SearchResult res;
     res.query = query;
@@ -3232,18 +3011,10 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     res.found = fd;
     if (!res.has_found) { nh = 0; rs = 0; fd = 0; }
     for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
-    std::string o = "{\n";
-    if (spec.mode == nsx::PageSpec::Boolean || spec.mode == nsx::PageSpec::BooleanSorted) o += boolean_member(query);   // search_boolean's "boolean" member
-    o += head.substr(2);
+    std::string o = head;
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
-    if ((spec.mode == nsx::PageSpec::Grouped || spec.mode == nsx::PageSpec::GroupedSorted) && !grouped_insert(rest_of, query)) {   // search_grouped's "grouped" member
-        body = err_ = "search_page: the search body has no k member";
-        return false;
-    }
-    if ((spec.mode == nsx::PageSpec::Quorum || spec.mode == nsx::PageSpec::QuorumSorted) && !quorum_insert(rest_of, query)) {   // search_quorum's "quorum" member
-        body = err_ = "search_page: the search body has no results member";
-        return false;
-    }
+    if (!call.plain)   // the dialect's member, as in its search_* body
+        if (const char* missing = insert_dialect_member(call.dialect, query, o, rest_of)) { body = err_ = std::string("search_page: the search body has no ") + missing + " member"; return false; }
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
     const size_t at = rest_of.find("  \"query\": ");
     if (at == std::string::npos || (at != 0 && rest_of[at - 1] != '\n')) { body = err_ = "search_page: the search body has no query member"; return false; }
@@ -3276,13 +3047,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
 
 std::string Engine::search_page(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec) {
     std::string body;
-    if (!search_page_text(query, k, cursor_text, spec, body)) {
-        std::string o = "{\n  \"error\": ";
-        json_escape(o, body);
-        o += "\n}";
-        return o;
-    }
-    return body;
+    return search_page_text(query, k, cursor_text, spec, body) ? body : error_body(body);
 }
 
 }  // namespace nextsearch

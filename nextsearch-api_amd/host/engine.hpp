@@ -374,9 +374,9 @@ public:
 
     // Any-of groups in boolean queries (host/grouped.hpp): the three boolean batch calls over nsx::parse_grouped's
     // dialect, `+(covid coronavirus sars) +vaccine -mouse`.  Each has its sibling's parameters and its sibling's answers for a
-    // text without '('.  The query preparation is boolean_refs_range's with a clause id per MUST ref: every MUST token gets a
-    // ref in every listed segment, with count == 0 where the token is absent or unknown, so an unknown synonym is dropped and a
-    // clause of only unknown words kills the query.  A query with more than 65 535 clauses is refused with a message.
+    // text without '('.  The query preparation is the boolean calls' (refs_range) with a clause id per MUST ref: every MUST token
+    // gets a ref in every listed segment, with count == 0 where the token is absent or unknown, so an unknown synonym is dropped
+    // and a clause of only unknown words kills the query.  A query with more than 65 535 clauses is refused with a message.
     bool search_grouped_after_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after, ns_hit* hits,
                                          uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
     bool facet_grouped_batch_flat(const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, std::vector<uint32_t>& counts,
@@ -419,6 +419,19 @@ public:
     bool search_quorum_faceted_text(const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
     std::string search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
     bool search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
+
+    // The calls above by dialect (nsx::Dialect, host/boolean.hpp): each named method forwards to one of these, which name
+    // themselves in messages as the dialect's named method does.  DESIGN.md §5x lists what a fourth dialect adds.
+    bool search_dialect_after_batch_flat(nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+                                         ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+    bool facet_dialect_batch_flat(nsx::Dialect dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                                  std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms = nullptr);
+    bool search_dialect_sorted_batch_flat(nsx::Dialect dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                          const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* usable, float* device_ms = nullptr);
+    bool search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    bool search_dialect_faceted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
+    bool search_dialect_sorted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
 
     // Pages past the first K (host/page.hpp).  A cursor is a position (rank, manifest position, docId) in a call's
     // total order; with one, a call answers with the first K matched documents STRICTLY AFTER it: found[q] stays the size of
@@ -518,43 +531,57 @@ private:
     OpenFilter* filter_of(uint32_t handle);
     bool translate_cursors(const char* fn, const nsx::PageCursor* after, size_t a, size_t b, uint32_t id_base, const std::vector<uint8_t>& listed,
                            bool filtered, std::vector<ns_cursor>& out);
-    bool sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
-                           const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
-                           float* device_ms);
-    enum { kDialectBoolean = 0, kDialectGrouped = 1, kDialectQuorum = 2 };   // which parser a shared implementation reads the text with
-    bool boolean_batch_impl(const char* fn, int dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
-                            ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
-    bool boolean_facet_impl(const char* fn, int dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
-                            std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms);
-    bool boolean_sorted_impl(const char* fn, int dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                             const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
-                             float* device_ms);
-    // what the three boolean paths share: filter row source, the call's segment list and the refs and roles of a query range
-    struct BooleanPrep {
+    // What the ranked, facet and date-order calls share, plain and boolean alike: the filter's row source under a handle, the
+    // segments the refs can name and the call's cursors.  The boolean dialects also keep the refs of one query range here (from
+    // qd on); the plain calls keep theirs in PlainPrep.
+    struct CallPrep {
         OpenFilter* f = nullptr;
         nsx::RowSource rs;
         std::vector<uint32_t> ids, listed;      // the ids the refs use; the manifest positions behind them
         std::vector<ns_seg*> segs;
         std::vector<uint8_t> is_listed;         // per manifest position
+        std::vector<ns_cursor> cur;             // of the current sub-batch; empty: none is set
         std::vector<ns_query_desc> qd;
         std::vector<ns_term_ref> refs;
         std::vector<uint8_t> roles;
-        std::vector<uint16_t> clauses;                    // grouped_refs_range: parallel to refs
+        std::vector<uint16_t> clauses;          // Grouped, Quorum: parallel to refs
+        std::vector<uint8_t> needs;             // Quorum: parallel to refs
         std::vector<char> scratch;
-        std::vector<std::pair<int64_t, uint8_t>> terms;   // (dictionary row or -1, role) of one query
-        std::vector<uint32_t> term_clauses;               // grouped_refs_range: parallel to terms
-        std::vector<uint8_t> needs;                       // quorum_refs_range: parallel to refs
-        std::vector<uint32_t> term_needs;                 // quorum_refs_range: parallel to terms
+        struct Term { int64_t row; uint8_t role; uint32_t clause, need; };   // row: the dictionary's, or -1
+        std::vector<Term> terms;                // of one query
     };
-    bool boolean_prepare(const char* fn, uint32_t filter_handle, BooleanPrep& bp);
-    void boolean_refs_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
-    bool boolean_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
-    bool boolean_faceted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f,
-                                   std::string& body);
-    bool boolean_sorted_text_impl(const char* name, int dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f,
-                                  std::string& body);
-    bool grouped_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
-    bool quorum_refs_range(const char* fn, const QueryView* queries, size_t a, size_t b, uint8_t* usable, BooleanPrep& bp);
+    // boolean_prepare's two halves.  filter_rows: the stale-handle check and the filter's row source.  list_segments: the
+    // positions with a device copy (the index's own, or the filter's) that `keep` does not skip, in manifest order.
+    bool filter_rows(const char* fn, uint32_t filter_handle, CallPrep& bp);
+    template <class Keep> void list_segments(CallPrep& bp, Keep keep);
+    bool boolean_prepare(const char* fn, uint32_t filter_handle, CallPrep& bp);
+    // descriptors, refs, roles (and the dialect's clauses and needs) of the queries [a, b) (qd indexed from a) and usable[a .. b)
+    bool refs_range(const char* fn, nsx::Dialect dialect, const QueryView* queries, size_t a, size_t b, uint8_t* usable, CallPrep& bp);
+    // the plain search's query preparation for the sub-batches of one call
+    struct PlainPrep {
+        bool whole = false;   // semantic expansion: prepared for the whole batch up front, term_begin indexes the one refs array
+        std::vector<ns_query_desc> qd;
+        std::vector<ns_term_ref> refs;
+        const ns_query_desc* qd_at = nullptr;   // the current sub-batch's
+        const ns_term_ref* refs_at = nullptr;
+        size_t n_refs = 0;
+    };
+    bool plain_prepare(const QueryView* queries, size_t Q, uint8_t* usable, const nsx::RowSource& rs, bool and_mode, PlainPrep& pp);
+    void plain_range(const QueryView* queries, size_t a, size_t b, uint8_t* usable, const nsx::RowSource& rs, bool and_mode, PlainPrep& pp);
+    // the outputs of a ranked call: hits (and keys, or nullptr) are Q x K
+    struct RankedOut { size_t K; ns_hit* hits; uint32_t* keys; uint32_t* nhits; uint64_t* found; uint64_t* rest; float* device_ms; };
+    template <class Prep, class Call>
+    bool ranked_batch(const char* fn, CallPrep& bp, const nsx::PageCursor* after, size_t Q, const RankedOut& out, Prep prep, Call call);
+    bool sorted_batch_impl(const char* fn, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, uint32_t flags,
+                           const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                           float* device_ms);
+    // the device call of a dialect, one per shape: the only places that pick among the per-dialect C entry points
+    bool ranked_call(nsx::Dialect dialect, bool paged, const CallPrep& bp, size_t a, size_t b, const RankedOut& out, const ns_cursor* cur, float* ms);
+    bool facet_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size_t b, ns_facet* const* tabs, uint32_t* counts, uint64_t* found, float* ms);
+    bool sorted_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size_t b, uint32_t direction, ns_dockeys* const* tabs, const RankedOut& out,
+                     const ns_cursor* cur, float* ms);
+    bool boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };

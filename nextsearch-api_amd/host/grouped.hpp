@@ -1,6 +1,6 @@
 // Any-of groups in boolean queries: the query box's dialect with one level of parentheses,
 //     +(coronavirus covid sars) +(vaccine vaccination) -mouse safety
-// parse_boolean (boolean.hpp) is untouched; a text without '(' parses here as it parses there.
+// A text without '(' parses here as it parses under parse_boolean (boolean.hpp, whose scanner reads all three dialects).
 //
 // The query is split on whitespace.  A piece whose text, after an optional one-byte '+' or '-', begins with '(' opens a group:
 // its body runs to the first ')' (across whitespace), or to the end of the query if there is none, and EVERY token the
@@ -26,35 +26,10 @@ struct GroupedTerm {
     uint32_t clause;   // under kRoleMust: the clause the term belongs to; else 0
 };
 
-// Calls fn(ptr, len, role, clause) for every term of the query, in order; returns the number of clauses.  `scratch` holds the
-// lowercased bytes.
+// Calls fn(ptr, len, role, clause) for every term of the query, in order; returns the number of clauses.
 template <class Fn>
 inline uint32_t for_each_grouped_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
-    uint32_t n_clauses = 0;
-    size_t i = 0;
-    while (i < n) {
-        while (i < n && bool_is_space((unsigned char)text[i])) i++;
-        if (i >= n) break;
-        const uint8_t role = text[i] == '+' ? kRoleMust : text[i] == '-' ? kRoleNot : kRoleShould;
-        const size_t from = role == kRoleShould ? i : i + 1;
-        if (from < n && text[from] == '(') {
-            size_t end = from + 1;
-            while (end < n && text[end] != ')') end++;
-            bool any = false;
-            for_each_base_term(text + from + 1, end - (from + 1), scratch, [&](const char* p, size_t len) {
-                fn(p, len, role, role == kRoleMust ? n_clauses : 0u);
-                any = true;
-            });
-            if (any && role == kRoleMust) n_clauses++;
-            i = end < n ? end + 1 : n;
-            continue;
-        }
-        size_t j = i;
-        while (j < n && !bool_is_space((unsigned char)text[j])) j++;
-        for_each_base_term(text + from, j - from, scratch, [&](const char* p, size_t len) { fn(p, len, role, role == kRoleMust ? n_clauses++ : 0u); });
-        i = j;
-    }
-    return n_clauses;
+    return for_each_dialect_term<Dialect::Grouped>(text, n, scratch, [&](const char* p, size_t len, uint8_t role, uint32_t clause, uint32_t) { fn(p, len, role, clause); }).n_clauses;
 }
 
 inline std::vector<GroupedTerm> parse_grouped(const std::string& text) {

@@ -850,13 +850,8 @@ extern "C" int nsh_engine_search_filtered_batch(nsh_engine* e, uint32_t handle, 
 } NSH_CATCH(e, "nsh_engine_search_filtered_batch", -1)
 }
 
-// Engine::search_filtered: *json_out (free with nsh_free) is the body, or {"error": ...} with -1 returned
-extern "C" int nsh_engine_search_filtered_json(nsh_engine* e, const char* query, int k, const char* date_from, const char* date_to,
-                                               int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    const bool ok = e->eng.search_filtered_text(query ? query : "", k, nsh_doc_filter(date_from, date_to, keep_undated), s);
+// a JSON body, or on failure the engine's message as {"error": ...}, as a malloc'ed string
+static int nsh_json_out(nsh_engine* e, bool ok, std::string& s, char** json_out) {
     if (!ok) {
         nsh_set_err(e, s);
         std::string o = "{\n  \"error\": ";
@@ -867,6 +862,42 @@ extern "C" int nsh_engine_search_filtered_json(nsh_engine* e, const char* query,
     if (!*json_out) return -1;
     std::memcpy(*json_out, s.c_str(), s.size() + 1);
     return ok ? 0 : -1;
+}
+
+// A JSON entry point over a filter that may be absent: call(filter or nullptr, body) is the Engine's _text call, with whatever
+// else the entry point has to check in front of it (false: body = the message).
+template <class Call>
+static int nsh_text_json(nsh_engine* e, int use_filter, const char* date_from, const char* date_to, int keep_undated, char** json_out, Call call) {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
+    const bool ok = call(use_filter ? &f : nullptr, s);
+    return nsh_json_out(e, ok, s, json_out);
+}
+
+// the terms' texts joined with spaces into buf (cut at cap - 1 bytes): what the nsh_parse_* calls hand back
+template <class T>
+static void nsh_join_terms(const std::vector<T>& terms, char* buf, uint32_t cap) {
+    if (!buf || !cap) return;
+    std::string joined;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (i) joined.push_back(' ');
+        joined += terms[i].text;
+    }
+    const size_t n = std::min<size_t>(joined.size(), cap - 1);
+    std::memcpy(buf, joined.data(), n);
+    buf[n] = 0;
+}
+
+// Engine::search_filtered: *json_out (free with nsh_free) is the body, or {"error": ...} with -1 returned
+extern "C" int nsh_engine_search_filtered_json(nsh_engine* e, const char* query, int k, const char* date_from, const char* date_to,
+                                               int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    const bool ok = e->eng.search_filtered_text(query ? query : "", k, nsh_doc_filter(date_from, date_to, keep_undated), s);
+    return nsh_json_out(e, ok, s, json_out);
 } NSH_CATCH(e, "nsh_engine_search_filtered_json", -1)
 }
 
@@ -951,25 +982,10 @@ extern "C" int nsh_engine_facet_batch(nsh_engine* e, const nsh_facet_spec* spec,
 
 extern "C" int nsh_engine_search_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
                                               const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::FacetSpec sp;
-    bool ok = nsh_facet_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::FacetSpec sp;
+        return nsh_facet_spec_of(e, spec, sp, s) && e->eng.search_faceted_text(query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_faceted_json", -1)
 }
 
@@ -1038,25 +1054,10 @@ extern "C" int nsh_engine_search_sorted_batch(nsh_engine* e, const nsh_sort_spec
 
 extern "C" int nsh_engine_search_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                              const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::SortSpec sp;
-    bool ok = nsh_sort_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::SortSpec sp;
+        return nsh_sort_spec_of(e, spec, sp, s) && e->eng.search_sorted_text(query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_sorted_json", -1)
 }
 
@@ -1066,17 +1067,9 @@ extern "C" uint64_t nsh_engine_sort_tables_on_device(nsh_engine* e) { return e ?
 // ---- boolean queries (host/boolean.hpp) ----
 extern "C" uint32_t nsh_parse_boolean(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t roles_cap) { try {
     const auto terms = nsx::parse_boolean(query ? query : "");
-    std::string joined;
-    for (size_t i = 0; i < terms.size(); i++) {
-        if (i) joined.push_back(' ');
-        joined += terms[i].text;
-        if (roles && i < roles_cap) roles[i] = terms[i].role;
-    }
-    if (buf && cap) {
-        const size_t n = std::min<size_t>(joined.size(), cap - 1);
-        std::memcpy(buf, joined.data(), n);
-        buf[n] = 0;
-    }
+    for (size_t i = 0; i < terms.size() && i < roles_cap; i++)
+        if (roles) roles[i] = terms[i].role;
+    nsh_join_terms(terms, buf, cap);
     return (uint32_t)terms.size();
 } NSH_CATCH(nullptr, "nsh_parse_boolean", 0)
 }
@@ -1103,21 +1096,9 @@ extern "C" int nsh_engine_search_boolean_batch(nsh_engine* e, uint32_t filter_ha
 
 extern "C" int nsh_engine_search_boolean_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
                                               int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-    const bool ok = e->eng.search_boolean_text(query ? query : "", k, use_filter ? &f : nullptr, s);
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        return e->eng.search_dialect_text(nsx::Dialect::Boolean, query ? query : "", k, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_boolean_json", -1)
 }
 
@@ -1160,14 +1141,15 @@ static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<ns
     for (uint32_t q = 0; q < n; q++) { out[q].set = in[q].set != 0; out[q].rank = in[q].rank; out[q].seg = in[q].seg; out[q].doc = in[q].doc; }
 }
 
-// mode: 0 search OR, 1 search AND (nsh_engine_search_after_batch), 2 boolean, 3 sorted, 4 boolean sorted, 5 grouped, 6 grouped sorted, 7 quorum, 8 quorum sorted
-static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
+// mode: the nsx::PageSpec mode whose batch call this is (page_call: which call, and whether it is in date order)
+static int nsh_after_batch(nsh_engine* e, const char* fn, nsx::PageSpec::Mode mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                            uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                            uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::SortSpec sp;
     std::string why;
-    const bool dated = mode == 3 || mode == 4 || mode == 6 || mode == 8;
+    const nsx::PageCall call = nsx::page_call(mode);
+    const bool dated = call.dated;
     if (dated && !nsh_sort_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
     if (n_queries && (!queries || !hits || !nhits || (dated && !keys_out))) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
     std::vector<nextsearch::Engine::QueryView> views(n_queries);
@@ -1181,13 +1163,10 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_so
     if (!rest) { r_.resize(n_queries); rest = r_.data(); }
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     bool ok;
-    if (mode == 8) ok = e->eng.search_quorum_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 7) ok = e->eng.search_quorum_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 6) ok = e->eng.search_grouped_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 5) ok = e->eng.search_grouped_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 4) ok = e->eng.search_boolean_sorted_batch_flat(sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 3) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
-    else if (mode == 2) ok = e->eng.search_boolean_after_batch_flat(filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    if (!call.plain)
+        ok = dated ? e->eng.search_dialect_sorted_batch_flat(call.dialect, sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out)
+                   : e->eng.search_dialect_after_batch_flat(call.dialect, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+    else if (dated) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else ok = e->eng.search_after_batch_flat(filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
     for (uint32_t q = 0; q < n_queries; q++)
@@ -1198,7 +1177,7 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, int mode, const nsh_so
 extern "C" int nsh_engine_search_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k, uint32_t flags,
                                              const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found,
                                              float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_after_batch", (flags & NS_FLAG_AND) ? 1 : 0, nullptr, filter_handle, queries, n_queries, k, flags, after, hits, nullptr,
+    return nsh_after_batch(e, "nsh_engine_search_after_batch", (flags & NS_FLAG_AND) ? nsx::PageSpec::SearchAnd : nsx::PageSpec::SearchOr, nullptr, filter_handle, queries, n_queries, k, flags, after, hits, nullptr,
                            nhits, found, rest, has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_after_batch", -1)
 }
@@ -1206,7 +1185,7 @@ extern "C" int nsh_engine_search_after_batch(nsh_engine* e, uint32_t filter_hand
 extern "C" int nsh_engine_search_boolean_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
                                                      const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                                      uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_boolean_after_batch", 2, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_boolean_after_batch", nsx::PageSpec::Boolean, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_boolean_after_batch", -1)
 }
@@ -1214,36 +1193,29 @@ extern "C" int nsh_engine_search_boolean_after_batch(nsh_engine* e, uint32_t fil
 extern "C" int nsh_engine_search_sorted_after_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                                                     uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out,
                                                     uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_sorted_after_batch", 3, spec, filter_handle, queries, n_queries, k, flags, after, hits, keys_out, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_sorted_after_batch", nsx::PageSpec::Sorted, spec, filter_handle, queries, n_queries, k, flags, after, hits, keys_out, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_sorted_after_batch", -1)
 }
 
 // ---- facet counts and date order for boolean queries ----
-static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /* 0 boolean, 1 grouped, 2 quorum */, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, nsx::Dialect dialect, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out);
 
 extern "C" int nsh_engine_facet_boolean_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
                                               uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_facet_boolean(e, "nsh_engine_facet_boolean_batch", false, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+    return nsh_facet_boolean(e, "nsh_engine_facet_boolean_batch", nsx::Dialect::Boolean, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_facet_boolean_batch", -1)
 }
 
 // ---- any-of groups in boolean queries (host/grouped.hpp) ----
 extern "C" uint32_t nsh_parse_grouped(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t terms_cap) { try {
     const auto terms = nsx::parse_grouped(query ? query : "");
-    std::string joined;
-    for (size_t i = 0; i < terms.size(); i++) {
-        if (i) joined.push_back(' ');
-        joined += terms[i].text;
-        if (roles && i < terms_cap) roles[i] = terms[i].role;
-        if (clauses && i < terms_cap) clauses[i] = terms[i].clause;
+    for (size_t i = 0; i < terms.size() && i < terms_cap; i++) {
+        if (roles) roles[i] = terms[i].role;
+        if (clauses) clauses[i] = terms[i].clause;
     }
-    if (buf && cap) {
-        const size_t n = std::min<size_t>(joined.size(), cap - 1);
-        std::memcpy(buf, joined.data(), n);
-        buf[n] = 0;
-    }
+    nsh_join_terms(terms, buf, cap);
     return (uint32_t)terms.size();
 } NSH_CATCH(nullptr, "nsh_parse_grouped", 0)
 }
@@ -1251,77 +1223,48 @@ extern "C" uint32_t nsh_parse_grouped(const char* query, char* buf, uint32_t cap
 extern "C" int nsh_engine_search_grouped_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
                                                      const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                                      uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_grouped_after_batch", 5, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_grouped_after_batch", nsx::PageSpec::Grouped, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_grouped_after_batch", -1)
 }
 
 extern "C" int nsh_engine_facet_grouped_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
                                               uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_facet_boolean(e, "nsh_engine_facet_grouped_batch", true, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+    return nsh_facet_boolean(e, "nsh_engine_facet_grouped_batch", nsx::Dialect::Grouped, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_facet_grouped_batch", -1)
 }
 
 extern "C" int nsh_engine_search_grouped_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                                                       uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                                                       uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_grouped_sorted_batch", 6, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_grouped_sorted_batch", nsx::PageSpec::GroupedSorted, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_grouped_sorted_batch", -1)
 }
 
-// a JSON body, or on failure the engine's message as {"error": ...}, as a malloc'ed string
-static int nsh_json_out(nsh_engine* e, bool ok, std::string& s, char** json_out) {
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
-}
-
 extern "C" int nsh_engine_search_grouped_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
                                               int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-    const bool ok = e->eng.search_grouped_text(query ? query : "", k, use_filter ? &f : nullptr, s);
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        return e->eng.search_dialect_text(nsx::Dialect::Grouped, query ? query : "", k, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_grouped_json", -1)
 }
 
 extern "C" int nsh_engine_search_grouped_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
                                                       const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::FacetSpec sp;
-    bool ok = nsh_facet_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_grouped_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::FacetSpec sp;
+        return nsh_facet_spec_of(e, spec, sp, s) && e->eng.search_dialect_faceted_text(nsx::Dialect::Grouped, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_grouped_faceted_json", -1)
 }
 
 extern "C" int nsh_engine_search_grouped_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                                      const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::SortSpec sp;
-    bool ok = nsh_sort_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_grouped_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::SortSpec sp;
+        return nsh_sort_spec_of(e, spec, sp, s) && e->eng.search_dialect_sorted_text(nsx::Dialect::Grouped, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_grouped_sorted_json", -1)
 }
 
@@ -1330,21 +1273,13 @@ extern "C" uint32_t nsh_parse_quorum(const char* query, char* buf, uint32_t cap,
                                      uint32_t terms_cap, uint32_t* min_should_out) { try {
     uint32_t min_should = 0;
     const auto terms = nsx::parse_quorum(query ? query : "", &min_should);
-    std::string joined;
-    for (size_t i = 0; i < terms.size(); i++) {
-        if (i) joined.push_back(' ');
-        joined += terms[i].text;
-        if (i >= terms_cap) continue;
+    for (size_t i = 0; i < terms.size() && i < terms_cap; i++) {
         if (roles) roles[i] = terms[i].role;
         if (clauses) clauses[i] = terms[i].clause;
         if (needs) needs[i] = terms[i].need;
         if (promoted) promoted[i] = terms[i].promoted ? 1 : 0;
     }
-    if (buf && cap) {
-        const size_t n = std::min<size_t>(joined.size(), cap - 1);
-        std::memcpy(buf, joined.data(), n);
-        buf[n] = 0;
-    }
+    nsh_join_terms(terms, buf, cap);
     if (min_should_out) *min_should_out = min_should;
     return (uint32_t)terms.size();
 } NSH_CATCH(nullptr, "nsh_parse_quorum", 0)
@@ -1353,67 +1288,52 @@ extern "C" uint32_t nsh_parse_quorum(const char* query, char* buf, uint32_t cap,
 extern "C" int nsh_engine_search_quorum_after_batch(nsh_engine* e, uint32_t filter_handle, const char* const* queries, uint32_t n_queries, int k,
                                                     const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                                     uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_quorum_after_batch", 7, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_quorum_after_batch", nsx::PageSpec::Quorum, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_quorum_after_batch", -1)
 }
 
 extern "C" int nsh_engine_facet_quorum_batch(nsh_engine* e, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
                                              uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_facet_boolean(e, "nsh_engine_facet_quorum_batch", 2, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
+    return nsh_facet_boolean(e, "nsh_engine_facet_quorum_batch", nsx::Dialect::Quorum, spec, filter_handle, queries, n_queries, counts_out, counts_cap, found, has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_facet_quorum_batch", -1)
 }
 
 extern "C" int nsh_engine_search_quorum_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                                                      uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                                                      uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_quorum_sorted_batch", 8, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_quorum_sorted_batch", nsx::PageSpec::QuorumSorted, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_quorum_sorted_batch", -1)
 }
 
 extern "C" int nsh_engine_search_quorum_json(nsh_engine* e, const char* query, int k, int use_filter, const char* date_from, const char* date_to,
                                              int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-    const bool ok = e->eng.search_quorum_text(query ? query : "", k, use_filter ? &f : nullptr, s);
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        return e->eng.search_dialect_text(nsx::Dialect::Quorum, query ? query : "", k, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_quorum_json", -1)
 }
 
 extern "C" int nsh_engine_search_quorum_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
                                                      const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::FacetSpec sp;
-    bool ok = nsh_facet_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_quorum_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::FacetSpec sp;
+        return nsh_facet_spec_of(e, spec, sp, s) && e->eng.search_dialect_faceted_text(nsx::Dialect::Quorum, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_quorum_faceted_json", -1)
 }
 
 extern "C" int nsh_engine_search_quorum_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                                     const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::SortSpec sp;
-    bool ok = nsh_sort_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_quorum_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    return nsh_json_out(e, ok, s, json_out);
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::SortSpec sp;
+        return nsh_sort_spec_of(e, spec, sp, s) && e->eng.search_dialect_sorted_text(nsx::Dialect::Quorum, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_quorum_sorted_json", -1)
 }
 
-static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /* 0 boolean, 1 grouped, 2 quorum */, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
+static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, nsx::Dialect dialect, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
     nsx::FacetSpec sp;
@@ -1428,9 +1348,7 @@ static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /
     if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
     std::vector<uint32_t> counts;
     std::vector<std::string> labels;
-    const bool ok = dialect == 2 ? e->eng.facet_quorum_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
-                    : dialect ? e->eng.facet_grouped_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out)
-                            : e->eng.facet_boolean_batch_flat(sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out);
+    const bool ok = e->eng.facet_dialect_batch_flat(dialect, sp, filter_handle, views.data(), n_queries, counts, found, has_found, labels, device_ms_out);
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
     if (counts.size() > counts_cap || (!counts.empty() && !counts_out)) {
         nsh_set_err(e, fn + ": counts_out holds " + std::to_string(counts_cap) + " entries, " + std::to_string(n_queries) + " queries x " +
@@ -1446,56 +1364,26 @@ static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, int dialect /
 extern "C" int nsh_engine_search_boolean_sorted_batch(nsh_engine* e, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                                                       uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
                                                       uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) { try {
-    return nsh_after_batch(e, "nsh_engine_search_boolean_sorted_batch", 4, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
+    return nsh_after_batch(e, "nsh_engine_search_boolean_sorted_batch", nsx::PageSpec::BooleanSorted, spec, filter_handle, queries, n_queries, k, 0u, after, hits, keys_out, nhits, found, rest,
                            has_found, device_ms_out);
 } NSH_CATCH(e, "nsh_engine_search_boolean_sorted_batch", -1)
 }
 
 extern "C" int nsh_engine_search_boolean_faceted_json(nsh_engine* e, const char* query, int k, const nsh_facet_spec* spec, int use_filter, const char* date_from,
                                                       const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::FacetSpec sp;
-    bool ok = nsh_facet_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_boolean_faceted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::FacetSpec sp;
+        return nsh_facet_spec_of(e, spec, sp, s) && e->eng.search_dialect_faceted_text(nsx::Dialect::Boolean, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_boolean_faceted_json", -1)
 }
 
 extern "C" int nsh_engine_search_boolean_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                                      const char* date_to, int keep_undated, char** json_out) { try {
-    if (!e || !json_out) return -1;
-    *json_out = nullptr;
-    std::string s;
-    nsx::SortSpec sp;
-    bool ok = nsh_sort_spec_of(e, spec, sp, s);
-    if (ok) {
-        const nsx::DocFilter f = nsh_doc_filter(date_from, date_to, keep_undated);
-        ok = e->eng.search_boolean_sorted_text(query ? query : "", k, sp, use_filter ? &f : nullptr, s);
-    }
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::SortSpec sp;
+        return nsh_sort_spec_of(e, spec, sp, s) && e->eng.search_dialect_sorted_text(nsx::Dialect::Boolean, query ? query : "", k, sp, f, s);
+    });
 } NSH_CATCH(e, "nsh_engine_search_boolean_sorted_json", -1)
 }
 
@@ -1516,15 +1404,6 @@ extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int
         if (ps.use_filter) ps.filter = nsh_doc_filter(date_from, date_to, keep_undated);
         ok = e->eng.search_page_text(query ? query : "", k, cursor ? cursor : "", ps, s);
     }
-    if (!ok) {
-        nsh_set_err(e, s);
-        std::string o = "{\n  \"error\": ";
-        nextsearch::json_escape(o, s);
-        s = o + "\n}";
-    }
-    *json_out = (char*)std::malloc(s.size() + 1);
-    if (!*json_out) return -1;
-    std::memcpy(*json_out, s.c_str(), s.size() + 1);
-    return ok ? 0 : -1;
+    return nsh_json_out(e, ok, s, json_out);
 } NSH_CATCH(e, "nsh_engine_search_page_json", -1)
 }

@@ -27,10 +27,10 @@
 //   ns_tool search-boolean-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>   (needs an MI355X)
 //        Engine::search_boolean_faceted: search-boolean's JSON body plus "facets", as search-faceted's.
 //   ns_tool search-boolean-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
+//        Engine::search_boolean_sorted: search-boolean's JSON body with "results" in date order plus "sort", as search-sorted's.
 //   ns_tool search-grouped <index_dir> <from> <to> <k> <query words ...>                          (needs an MI355X; `+(a b) +c -d`)
 //   ns_tool search-grouped-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>     (needs an MI355X)
 //   ns_tool search-grouped-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>   (needs an MI355X)
-//        Engine::search_boolean_sorted: search-boolean's JSON body with "results" in date order plus "sort", as search-sorted's.
 //   ns_tool search-quorum <index_dir> <from> <to> <k> <query words ...>                           (needs an MI355X; `+(a b c)~2 -d`, `a b c ~2`)
 //   ns_tool search-quorum-faceted <index_dir> <year|month> <from> <to> <k> <query words ...>      (needs an MI355X)
 //   ns_tool search-quorum-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>    (needs an MI355X)
@@ -55,6 +55,11 @@
 #include "engine.hpp"
 #include "gen_index.hpp"
 #include "invert.hpp"
+
+// search-boolean*, search-grouped*, search-quorum*: the dialect the subcommand names
+static nsx::Dialect tool_dialect(const char* subcommand) {
+    return subcommand[7] == 'q' ? nsx::Dialect::Quorum : subcommand[7] == 'g' ? nsx::Dialect::Grouped : nsx::Dialect::Boolean;
+}
 
 int main(int argc, char** argv) {
     if (argc >= 5 && std::strcmp(argv[1], "gen-index") == 0) {
@@ -136,7 +141,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc >= 7 && (std::strcmp(argv[1], "search-boolean") == 0 || std::strcmp(argv[1], "search-grouped") == 0 || std::strcmp(argv[1], "search-quorum") == 0)) {
-        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
+        const nsx::Dialect dialect = tool_dialect(argv[1]);
         nextsearch::Engine eng(0);
         eng.index_dir = argv[2];
         if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
@@ -147,12 +152,12 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[5]);
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
-        if (!(quorum ? eng.search_quorum_text(q, k, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_text(q, k, filtered ? &f : nullptr, body) : eng.search_boolean_text(q, k, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!eng.search_dialect_text(dialect, q, k, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
     if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-faceted") == 0 || std::strcmp(argv[1], "search-grouped-faceted") == 0 || std::strcmp(argv[1], "search-quorum-faceted") == 0)) {
-        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
+        const nsx::Dialect dialect = tool_dialect(argv[1]);
         nsx::FacetSpec spec;
         if (std::strcmp(argv[3], "year") == 0) spec.kind = nsx::FacetSpec::Year;
         else if (std::strcmp(argv[3], "month") == 0) spec.kind = nsx::FacetSpec::Month;
@@ -167,12 +172,12 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!(quorum ? eng.search_quorum_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_faceted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_faceted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!eng.search_dialect_faceted_text(dialect, q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }
     if (argc >= 8 && (std::strcmp(argv[1], "search-boolean-sorted") == 0 || std::strcmp(argv[1], "search-grouped-sorted") == 0 || std::strcmp(argv[1], "search-quorum-sorted") == 0)) {
-        const bool grouped = argv[1][7] == 'g', quorum = argv[1][7] == 'q';
+        const nsx::Dialect dialect = tool_dialect(argv[1]);
         nsx::SortSpec spec;
         if (std::strcmp(argv[3], "newest") == 0) spec.ascending = false;
         else if (std::strcmp(argv[3], "oldest") == 0) spec.ascending = true;
@@ -187,7 +192,7 @@ int main(int argc, char** argv) {
         const int k = std::atoi(argv[6]);
         std::string q, body;
         for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
-        if (!(quorum ? eng.search_quorum_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : grouped ? eng.search_grouped_sorted_text(q, k, spec, filtered ? &f : nullptr, body) : eng.search_boolean_sorted_text(q, k, spec, filtered ? &f : nullptr, body))) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        if (!eng.search_dialect_sorted_text(dialect, q, k, spec, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <string>
 
+#include "boolean.hpp"
 #include "sorted.hpp"
 
 namespace nsx {
@@ -34,7 +35,21 @@ struct PageSpec {
     bool use_filter = false;
     DocFilter filter;
 };
-inline char page_kind(PageSpec::Mode m) { return (m == PageSpec::Sorted || m == PageSpec::BooleanSorted || m == PageSpec::GroupedSorted || m == PageSpec::QuorumSorted) ? 'd' : 's'; }
+// which call a mode pages: the plain search's (SearchOr, SearchAnd, Sorted) or a boolean dialect's, in score or in date order
+struct PageCall { bool plain; Dialect dialect; bool dated; };
+inline PageCall page_call(PageSpec::Mode m) {
+    switch (m) {
+        case PageSpec::Sorted: return {true, Dialect::Boolean, true};
+        case PageSpec::Boolean: return {false, Dialect::Boolean, false};
+        case PageSpec::BooleanSorted: return {false, Dialect::Boolean, true};
+        case PageSpec::Grouped: return {false, Dialect::Grouped, false};
+        case PageSpec::GroupedSorted: return {false, Dialect::Grouped, true};
+        case PageSpec::Quorum: return {false, Dialect::Quorum, false};
+        case PageSpec::QuorumSorted: return {false, Dialect::Quorum, true};
+        default: return {true, Dialect::Boolean, false};   // SearchOr, SearchAnd
+    }
+}
+inline char page_kind(PageSpec::Mode m) { return page_call(m).dated ? 'd' : 's'; }
 
 inline std::string cursor_text(char kind, const PageCursor& c) {
     if (!c.set) return std::string();

@@ -1,4 +1,4 @@
-// At-least-m-of-n clauses in boolean queries: parse_grouped's dialect (grouped.hpp, untouched) plus two forms,
+// At-least-m-of-n clauses in boolean queries: parse_grouped's dialect (grouped.hpp) plus two forms,
 //     +(fever cough dyspnea fatigue)~2 -mouse          at least two of the four
 //     fever cough dyspnea fatigue ~2                   at least two of the optional terms
 // A text with neither form parses here as it parses there.
@@ -23,7 +23,6 @@
 namespace nsx {
 
 static constexpr uint32_t kQuorumMaxNeed = 7;          // == kBqMaxNeed of csrc/ns_boolean_plan.hpp
-static constexpr uint32_t kQuorumNeedCap = 1000000;    // what a longer run of digits reads as
 
 struct QuorumTerm {
     std::string text;
@@ -33,68 +32,11 @@ struct QuorumTerm {
     bool promoted;     // an optional term that a `~m` piece made a member of the query's last clause
 };
 
-struct QuorumShape {
-    uint32_t n_clauses;    // of the terms as fn saw them
-    uint32_t min_should;   // the last `~m` piece's m; > 0: the caller makes every SHOULD term a MUST term of clause n_clauses, need m
-};
-
-// decimal digits at text[i ..): their value (saturating) and the index behind them; no digit: `end` == i
-inline uint32_t quorum_digits(const char* text, size_t n, size_t i, size_t& end) {
-    uint64_t v = 0;
-    end = i;
-    while (end < n && text[end] >= '0' && text[end] <= '9') {
-        v = v * 10 + (uint64_t)(text[end] - '0');
-        if (v > kQuorumNeedCap) v = kQuorumNeedCap;
-        end++;
-    }
-    return (uint32_t)v;
-}
-
-// Calls fn(ptr, len, role, clause, need) for every term of the query, in order: for_each_grouped_term with a need per MUST term.
-// The optional terms come as SHOULD terms (clause 0, need 0) whatever min_should says: see QuorumShape.
+// Calls fn(ptr, len, role, clause, need) for every term of the query, in order: for_each_grouped_term with a need per MUST term
+// (QuorumShape, quorum_digits and the scanner itself are boolean.hpp's).
 template <class Fn>
 inline QuorumShape for_each_quorum_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
-    QuorumShape shape{0, 0};
-    size_t i = 0;
-    while (i < n) {
-        while (i < n && bool_is_space((unsigned char)text[i])) i++;
-        if (i >= n) break;
-        const uint8_t prefix = text[i] == '+' ? kRoleMust : text[i] == '-' ? kRoleNot : kRoleShould;
-        const size_t from = prefix == kRoleShould ? i : i + 1;
-        if (from < n && text[from] == '(') {
-            size_t end = from + 1;
-            while (end < n && text[end] != ')') end++;
-            size_t resume = end < n ? end + 1 : n;
-            uint32_t need = 0;
-            if (end + 1 < n && text[end + 1] == '~') {
-                size_t behind;
-                const uint32_t m = quorum_digits(text, n, end + 2, behind);
-                if (behind > end + 2) { need = m; resume = behind; }
-            }
-            const uint8_t role = (need >= 1 && prefix == kRoleShould) ? kRoleMust : prefix;
-            if (role != kRoleMust) need = 0;
-            else if (need == 0) need = 1;
-            bool any = false;
-            for_each_base_term(text + from + 1, end - (from + 1), scratch, [&](const char* p, size_t len) {
-                fn(p, len, role, role == kRoleMust ? shape.n_clauses : 0u, need);
-                any = true;
-            });
-            if (any && role == kRoleMust) shape.n_clauses++;
-            i = resume;
-            continue;
-        }
-        size_t j = i;
-        while (j < n && !bool_is_space((unsigned char)text[j])) j++;
-        if (text[i] == '~' && j > i + 1) {
-            size_t behind;
-            const uint32_t m = quorum_digits(text, n, i + 1, behind);
-            if (behind == j) { shape.min_should = m; i = j; continue; }
-        }
-        for_each_base_term(text + from, j - from, scratch,
-                           [&](const char* p, size_t len) { fn(p, len, prefix, prefix == kRoleMust ? shape.n_clauses++ : 0u, prefix == kRoleMust ? 1u : 0u); });
-        i = j;
-    }
-    return shape;
+    return for_each_dialect_term<Dialect::Quorum>(text, n, scratch, fn);
 }
 
 // -> the terms with the `~m` promotion applied; min_should (may be NULL) gets the piece's m (0: none)

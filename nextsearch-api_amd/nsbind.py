@@ -878,15 +878,8 @@ class Engine:
 
     def search_filtered_json(self, query, k, date_from="", date_to="", keep_undated=False, check=True):
         """Engine::search_filtered: the JSON text; a failure raises (check=False: returns the {"error": ...} body)."""
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_filtered_json(self.h, _as_bytes(query), k, _as_bytes(date_from), _as_bytes(date_to),
-                                                     int(bool(keep_undated)), C.byref(out))
-        s = C.string_at(out).decode() if out else ""
-        if out:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_filtered failed: {self.error()}")
-        return s
+        return self._json_call("search_filtered", self._L.nsh_engine_search_filtered_json, _as_bytes(query), k, _as_bytes(date_from), _as_bytes(date_to),
+                               int(bool(keep_undated)), check=check)
 
     # ---- facet counts (DESIGN.md §5p) ----
     @staticmethod
@@ -939,15 +932,8 @@ class Engine:
         (check=False: returns the {"error": ...} body)."""
         sp, keep = self._facet_spec(kind, custom, labels)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_faceted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
-                                                    int(bool(ku)), C.byref(out))
-        s = C.string_at(out).decode() if out else ""
-        if out:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_faceted failed: {self.error()}")
-        return s
+        return self._json_call("search_faceted", self._L.nsh_engine_search_faceted_json, _as_bytes(query), k, C.byref(sp), int(date_filter is not None),
+                               _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     def release_facets(self):
         self._L.nsh_engine_release_facets(self.h)
@@ -1004,15 +990,8 @@ class Engine:
         (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_sorted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
-                                                   int(bool(ku)), C.byref(out))
-        body = C.string_at(out).decode() if out.value else ""
-        if out.value:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_sorted failed: {self.error()}")
-        return body
+        return self._json_call("search_sorted", self._L.nsh_engine_search_sorted_json, _as_bytes(query), k, C.byref(sp), int(date_filter is not None),
+                               _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     def search_boolean_batch(self, queries, k, handle=0, timing=False):
         """Engine::search_boolean_batch_flat: (hits Q x K, nhits, found, has_found); `+word` required, `-word` excluded, other
@@ -1032,205 +1011,73 @@ class Engine:
         """Engine::search_boolean: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure raises
         (check=False: returns the {"error": ...} body)."""
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_boolean_json(self.h, _as_bytes(query), k, int(date_filter is not None), _as_bytes(df), _as_bytes(dt),
-                                                    int(bool(ku)), C.byref(out))
-        body = C.string_at(out).decode() if out.value else ""
-        if out.value:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_boolean failed: {self.error()}")
-        return body
+        return self._json_call("search_boolean", self._L.nsh_engine_search_boolean_json, _as_bytes(query), k, int(date_filter is not None), _as_bytes(df),
+                               _as_bytes(dt), int(bool(ku)), check=check)
 
     # ---- facet counts and date order for boolean queries (DESIGN.md §5t) ----
     def facet_boolean_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
         """Engine::facet_boolean_batch_flat: (counts Q x n_buckets, found, has_found) over search_boolean_batch's matched set;
         n_buckets = len(facet_buckets(...)[1]); handle: an open filter's (0: none).  timing=True adds the kernel's device ms."""
-        sp, keep = self._facet_spec(kind, custom, labels)
-        Q = len(queries)
-        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
-        found = np.zeros(Q, dtype=np.uint64)
-        has_found = np.zeros(Q, dtype=np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_facet_boolean_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
-                                                    found.ctypes.data, has_found.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"facet_boolean_batch failed: {self.error()}")
-        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+        return self._facet_batch("facet_boolean_batch", self._L.nsh_engine_facet_boolean_batch, queries, n_buckets, kind, handle, custom, labels, timing)
 
     def search_boolean_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
         """Engine::search_boolean_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found) over
         search_boolean_batch's matched set in date order; after: None, or per query None | (rank = the sort key, manifest
         position, docId).  timing=True adds the kernels' device ms."""
-        sp, keep = self._sort_spec(order, custom)
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_boolean_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
-                                                            cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
-                                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_boolean_sorted_batch failed: {self.error()}")
-        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._sorted_batch("search_boolean_sorted_batch", self._L.nsh_engine_search_boolean_sorted_batch, queries, k, after, order, handle, custom, timing)
 
     def search_boolean_faceted_json(self, query, k, kind="year", date_filter=None, custom=None, labels=None, check=True):
         """Engine::search_boolean_faceted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure
         raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._facet_spec(kind, custom, labels)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_boolean_faceted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df),
-                                                            _as_bytes(dt), int(bool(ku)), C.byref(out))
-        body = C.string_at(out).decode() if out.value else ""
-        if out.value:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_boolean_faceted failed: {self.error()}")
-        return body
+        return self._json_call("search_boolean_faceted", self._L.nsh_engine_search_boolean_faceted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     def search_boolean_sorted_json(self, query, k, order="newest", date_filter=None, custom=None, check=True):
         """Engine::search_boolean_sorted: the JSON text.  date_filter: None, or (date_from, date_to, keep_undated).  A failure
         raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_boolean_sorted_json(self.h, _as_bytes(query), k, C.byref(sp), int(date_filter is not None), _as_bytes(df),
-                                                           _as_bytes(dt), int(bool(ku)), C.byref(out))
-        body = C.string_at(out).decode() if out.value else ""
-        if out.value:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_boolean_sorted failed: {self.error()}")
-        return body
+        return self._json_call("search_boolean_sorted", self._L.nsh_engine_search_boolean_sorted_json, _as_bytes(query), k, C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     # ---- pages past the first K (DESIGN.md §5s) ----
     def search_after_batch(self, queries, k, after=None, flags=NS_FLAG_OR, handle=0, timing=False):
         """Engine::search_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); after: None, or per query None |
         (rank = score bits, manifest position, docId).  Without a cursor it is search_batch (search_filtered_batch under a
         handle) bit for bit."""
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), int(flags), cu.ctypes.data if cu is not None and Q else None,
-                                                   hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_after_batch failed: {self.error()}")
-        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._after_batch("search_after_batch", self._L.nsh_engine_search_after_batch, queries, k, after, handle, timing, flags)
 
     def search_boolean_after_batch(self, queries, k, after=None, handle=0, timing=False):
         """Engine::search_boolean_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); after as search_after_batch's"""
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_boolean_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
-                                                           hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_boolean_after_batch failed: {self.error()}")
-        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
-
+        return self._after_batch("search_boolean_after_batch", self._L.nsh_engine_search_boolean_after_batch, queries, k, after, handle, timing)
     # ---- any-of groups in boolean queries (DESIGN.md §5u): the boolean batch calls over `+(a b) +c -d` ----
     def search_grouped_after_batch(self, queries, k, after=None, handle=0, timing=False):
         """Engine::search_grouped_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_boolean_after_batch"""
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_grouped_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
-                                                           hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_grouped_after_batch failed: {self.error()}")
-        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._after_batch("search_grouped_after_batch", self._L.nsh_engine_search_grouped_after_batch, queries, k, after, handle, timing)
 
     def facet_grouped_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
         """Engine::facet_grouped_batch_flat: (counts Q x n_buckets, found, has_found); as facet_boolean_batch"""
-        sp, keep = self._facet_spec(kind, custom, labels)
-        Q = len(queries)
-        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
-        found = np.zeros(Q, dtype=np.uint64)
-        has_found = np.zeros(Q, dtype=np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_facet_grouped_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
-                                                    found.ctypes.data, has_found.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"facet_grouped_batch failed: {self.error()}")
-        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+        return self._facet_batch("facet_grouped_batch", self._L.nsh_engine_facet_grouped_batch, queries, n_buckets, kind, handle, custom, labels, timing)
 
     def search_grouped_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
         """Engine::search_grouped_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); as
         search_boolean_sorted_batch"""
-        sp, keep = self._sort_spec(order, custom)
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_grouped_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
-                                                            cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
-                                                            nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_grouped_sorted_batch failed: {self.error()}")
-        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
-
+        return self._sorted_batch("search_grouped_sorted_batch", self._L.nsh_engine_search_grouped_sorted_batch, queries, k, after, order, handle, custom, timing)
     # ---- at-least-m-of-n clauses (DESIGN.md §5w): the grouped batch calls over `+(a b c)~2 -d` and `a b c ~2` ----
     def search_quorum_after_batch(self, queries, k, after=None, handle=0, timing=False):
         """Engine::search_quorum_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_grouped_after_batch"""
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_quorum_after_batch(self.h, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
-                                                          hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_quorum_after_batch failed: {self.error()}")
-        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._after_batch("search_quorum_after_batch", self._L.nsh_engine_search_quorum_after_batch, queries, k, after, handle, timing)
 
     def facet_quorum_batch(self, queries, n_buckets, kind="year", handle=0, custom=None, labels=None, timing=False):
         """Engine::facet_quorum_batch_flat: (counts Q x n_buckets, found, has_found); as facet_grouped_batch"""
-        sp, keep = self._facet_spec(kind, custom, labels)
-        Q = len(queries)
-        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
-        found = np.zeros(Q, dtype=np.uint64)
-        has_found = np.zeros(Q, dtype=np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_facet_quorum_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size,
-                                                   found.ctypes.data, has_found.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"facet_quorum_batch failed: {self.error()}")
-        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+        return self._facet_batch("facet_quorum_batch", self._L.nsh_engine_facet_quorum_batch, queries, n_buckets, kind, handle, custom, labels, timing)
 
     def search_quorum_sorted_batch(self, queries, k, after=None, order="newest", handle=0, custom=None, timing=False):
         """Engine::search_quorum_sorted_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); as
         search_grouped_sorted_batch"""
-        sp, keep = self._sort_spec(order, custom)
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_quorum_sorted_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k),
-                                                           cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data,
-                                                           nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_quorum_sorted_batch failed: {self.error()}")
-        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._sorted_batch("search_quorum_sorted_batch", self._L.nsh_engine_search_quorum_sorted_batch, queries, k, after, order, handle, custom, timing)
 
     def search_quorum_json(self, query, k, date_filter=None, check=True):
         """Engine::search_quorum: the JSON text; as search_grouped_json"""
@@ -1262,6 +1109,44 @@ class Engine:
             raise RuntimeError(f"{name} failed: {self.error()}")
         return body
 
+    def _ranked_batch(self, name, cfn, sp, queries, k, after, handle, timing, flags):
+        """a paged batch call, in date order with keys when sp (a sort spec) is given: the outputs, with the device ms under timing"""
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        keys = None if sp is None else np.zeros((max(Q, 1), K), dtype=np.uint32)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        args = ([] if sp is None else [C.byref(sp)]) + [int(handle), _cstr_array(queries), Q, int(k)] + ([] if flags is None else [int(flags)])
+        args += [cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data] + ([] if sp is None else [keys.ctypes.data])
+        rc = cfn(self.h, *args, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"{name} failed: {self.error()}")
+        out = (hits[:Q],) + (() if sp is None else (keys[:Q],)) + (nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def _after_batch(self, name, cfn, queries, k, after, handle, timing, flags=None):
+        """(hits Q x K, nhits, found, rest, has_found) of a score-order batch call"""
+        return self._ranked_batch(name, cfn, None, queries, k, after, handle, timing, flags)
+
+    def _sorted_batch(self, name, cfn, queries, k, after, order, handle, custom, timing, flags=None):
+        """(hits Q x K, keys Q x K, nhits, found, rest, has_found) of a date-order batch call"""
+        sp, keep = self._sort_spec(order, custom)
+        return self._ranked_batch(name, cfn, sp, queries, k, after, handle, timing, flags)
+
+    def _facet_batch(self, name, cfn, queries, n_buckets, kind, handle, custom, labels, timing):
+        """(counts Q x n_buckets, found, has_found) of a boolean dialect's facet batch call"""
+        sp, keep = self._facet_spec(kind, custom, labels)
+        Q = len(queries)
+        counts = np.zeros((Q, int(n_buckets)), dtype=np.uint32)
+        found = np.zeros(Q, dtype=np.uint64)
+        has_found = np.zeros(Q, dtype=np.uint8)
+        ms = C.c_float()
+        rc = cfn(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, counts.ctypes.data, counts.size, found.ctypes.data, has_found.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"{name} failed: {self.error()}")
+        return (counts, found, has_found, float(ms.value)) if timing else (counts, found, has_found)
+
     def search_grouped_json(self, query, k, date_filter=None, check=True):
         """Engine::search_grouped: the JSON text; as search_boolean_json"""
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
@@ -1285,35 +1170,15 @@ class Engine:
     def search_sorted_after_batch(self, queries, k, after=None, order="newest", flags=NS_FLAG_OR, handle=0, custom=None, timing=False):
         """Engine::search_sorted_after_batch_flat: (hits Q x K, keys Q x K, nhits, found, rest, has_found); after: None, or per
         query None | (rank = the sort key, manifest position, docId)"""
-        sp, keep = self._sort_spec(order, custom)
-        Q, K = len(queries), min(max(int(k), 1), 100)
-        cu = None if after is None else page_cursors(after)
-        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
-        keys = np.zeros((max(Q, 1), K), dtype=np.uint32)
-        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
-        ms = C.c_float()
-        rc = self._L.nsh_engine_search_sorted_after_batch(self.h, C.byref(sp), int(handle), _cstr_array(queries), Q, int(k), int(flags),
-                                                          cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, keys.ctypes.data, nhits.ctypes.data,
-                                                          found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
-        if rc != 0:
-            raise RuntimeError(f"search_sorted_after_batch failed: {self.error()}")
-        out = (hits[:Q], keys[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
-        return out + (float(ms.value),) if timing else out
+        return self._sorted_batch("search_sorted_after_batch", self._L.nsh_engine_search_sorted_after_batch, queries, k, after, order, handle, custom, timing, flags)
 
     def search_page_json(self, query, k, cursor="", mode="or", order="newest", date_filter=None, custom=None, check=True):
         """Engine::search_page: the JSON text of one page.  mode: "or" | "and" | "boolean" | "sorted" | "boolean_sorted" | "grouped" |
         "grouped_sorted" | "quorum" | "quorum_sorted" (the sorted ones: order / custom as search_sorted_json's); cursor: "" or a page's "next".  A failure raises (check=False: returns the {"error": ...} body)."""
         sp, keep = self._sort_spec(order, custom)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
-        out = C.c_void_p()
-        rc = self._L.nsh_engine_search_page_json(self.h, _as_bytes(query), k, _as_bytes(cursor), PAGE_MODES[mode], C.byref(sp), int(date_filter is not None),
-                                                 _as_bytes(df), _as_bytes(dt), int(bool(ku)), C.byref(out))
-        body = C.string_at(out).decode() if out.value else ""
-        if out.value:
-            self._L.nsh_free(out)
-        if rc != 0 and check:
-            raise RuntimeError(f"search_page failed: {self.error()}")
-        return body
+        return self._json_call("search_page", self._L.nsh_engine_search_page_json, _as_bytes(query), k, _as_bytes(cursor), PAGE_MODES[mode], C.byref(sp),
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     def release_sorted(self):
         self._L.nsh_engine_release_sorted(self.h)
@@ -2111,6 +1976,15 @@ def sorted_kernel_ms(reset=True):
     out = (C.c_float * 3)()
     hip_lib().ns_sorted_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
+
+
+def base_terms(text):
+    """nsx::for_each_base_term (host only): the tokens the search's tokenizer takes from text, stop words and one-byte tokens dropped"""
+    b = _as_bytes(text)
+    cap = len(b) + 2
+    buf = C.create_string_buffer(cap)
+    n = int(host_lib().nsh_base_terms(b, buf, cap))
+    return buf.value.decode().split(" ") if n else []
 
 
 def parse_boolean(text):

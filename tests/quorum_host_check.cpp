@@ -138,9 +138,55 @@ static void parser() {
     }
 }
 
+// The one scanner (host/boolean.hpp) in all three dialects over every string of 0 to 5 bytes of the grammar's own alphabet, each
+// an exact-size heap copy: it never reads past the end, and the dialects are nested (without '(' Grouped scans as Boolean,
+// without '~' Quorum scans as Grouped).
+template <nsx::Dialect D>
+static std::string scanned(const std::vector<char>& text, bool clauses, bool needs) {
+    std::vector<char> scratch;
+    std::string o;
+    const nsx::QuorumShape shape = nsx::for_each_dialect_term<D>(text.data(), text.size(), scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
+        o += std::string(p, n) + ":" + std::to_string(role);
+        if (clauses) o += "." + std::to_string(clause);
+        if (needs) o += "/" + std::to_string(need);
+        o += " ";
+    });
+    if (clauses) o += "#" + std::to_string(shape.n_clauses);
+    if (needs) o += "~" + std::to_string(shape.min_should);
+    return o;
+}
+
+static void scanner() {
+    const std::string alphabet = "+-()~ a12";
+    size_t n_texts = 0;
+    for (size_t len = 0; len <= 5; len++) {
+        size_t count = 1;
+        for (size_t i = 0; i < len; i++) count *= alphabet.size();
+        for (size_t code = 0; code < count; code++) {
+            std::vector<char> text(len);
+            bool paren = false, tilde = false;
+            for (size_t i = 0, c = code; i < len; i++, c /= alphabet.size()) {
+                text[i] = alphabet[c % alphabet.size()];
+                paren = paren || text[i] == '(';
+                tilde = tilde || text[i] == '~';
+            }
+            n_texts++;
+            // every text through every dialect; what a dialect says of a text that its smaller sibling reads alike is compared
+            const std::string b = scanned<nsx::Dialect::Boolean>(text, false, false);
+            const std::string g = scanned<nsx::Dialect::Grouped>(text, true, false), g_terms = scanned<nsx::Dialect::Grouped>(text, false, false);
+            const std::string q = scanned<nsx::Dialect::Quorum>(text, true, true), q_clauses = scanned<nsx::Dialect::Quorum>(text, true, false);
+            EXPECT(b.empty() == g_terms.empty() || paren);
+            if (!paren) EXPECT(b == g_terms);
+            if (!tilde) EXPECT(g == q_clauses && q.size() >= 2 && q.compare(q.size() - 2, 2, "~0") == 0);   // and no `~m` piece
+        }
+    }
+    EXPECT(n_texts == 66430);
+}
+
 int main() {
     planner();
     parser();
+    scanner();
     if (failures) { std::fprintf(stderr, "%d expectation(s) failed\n", failures); return 1; }
     std::puts("quorum host check OK");
     return 0;
