@@ -2134,8 +2134,7 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
         // ---- block C: what the kept tokens size ----
         if (blk.ok() && n_kept) {
             const uint32_t K = n_kept, gK = (K + 255) / 256, kt = (K + kIvTile - 1) / kIvTile;
-            uint64_t cap = 1024;
-            while (cap < 2ull * K) cap <<= 1;                      // K <= n / 2 < 2^31: cap <= 2^32, its mask fits 32 bits
+            const uint64_t cap = ig_table_slots(K);                // K <= n / 2 < 2^31: cap <= 2^32, its mask fits 32 bits
             blk.open();
             const size_t o_ks = blk.reserve((size_t)K * 4), o_kl = blk.reserve((size_t)K * 4), o_kd = blk.reserve((size_t)K * 4), o_kh = blk.reserve((size_t)K * 8);
             const size_t o_sl = blk.reserve((size_t)K * 4), o_kr = blk.reserve((size_t)K * 4), o_fi = blk.reserve((size_t)K * 4), o_tsrc = blk.reserve((size_t)K * 4);
@@ -2391,8 +2390,7 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
     CallBlock blk(ctx);
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     enum { C_TERMS = 0, C_TBYTES = 1, C_LONG = 2, C_LIVE = 3, C_DUP = 4, C_BAD = 5 };   // C_DUP / C_BAD: the smallest refused source, ~0 for none; C_LIVE: the terms that stay (filtered)
-    uint64_t cap = 1024;
-    while (cap < 2ull * T) cap <<= 1;                                  // T < 2^31: cap <= 2^32, its mask fits 32 bits
+    const uint64_t cap = ig_table_slots(T);                            // T < 2^31: cap <= 2^32, its mask fits 32 bits
     const uint32_t big_tiles = (n_big + kIvTile - 1) / kIvTile;
     const size_t scan_max = std::max<size_t>({(size_t)T + 1, (size_t)2048 * big_tiles, (size_t)1});
 
@@ -2494,8 +2492,7 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
             read_counts(blk, h_cnt);
             Td = h_cnt[C_LIVE];
         }
-        uint64_t capd = 1024;                                          // == cap unless terms were dropped
-        while (capd < 2ull * Td) capd <<= 1;
+        const uint64_t capd = ig_table_slots(Td);                      // == cap unless terms were dropped
         const uint32_t gT = (Td + 255) / 256;
         if (blk.ok() && Td) {
             blk.chk(hipMemsetAsync(d_table, 0xFF, (size_t)capd * 4, st));

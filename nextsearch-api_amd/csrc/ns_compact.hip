@@ -25,6 +25,8 @@
 
 #include <cstdint>
 
+#include "ns_ingest_text.hpp"
+
 namespace ns {
 
 constexpr uint32_t kCpWaveMax = 64;       // pairs of a document sorted by one wave
@@ -55,9 +57,7 @@ __global__ void __launch_bounds__(256) k_cp_hash(const uint8_t* __restrict__ tex
         long_list[atomicAdd(long_count, 1u)] = k;                     // (the list's order is never read: each entry writes its own khash)
         return;
     }
-    uint64_t h = 0;
-    for (uint32_t j = 0; j < len; j++) h = h * kIgP + (uint64_t)(text[s + j] + 1u);
-    khash[k] = ig_mix(h ^ len) & hash_mask;
+    khash[k] = ig_hash_bytes(text + s, len) & hash_mask;
 }
 
 // table: `mask + 1` slots of (source << 32 | new id), at least twice the source terms; *dup_src = the smallest source that

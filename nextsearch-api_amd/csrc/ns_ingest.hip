@@ -27,39 +27,9 @@
 
 #include <cstdint>
 
+#include "ns_ingest_text.hpp"
+
 namespace ns {
-
-constexpr int kIgTile = 256 * 16;            // text bytes per workgroup
-constexpr uint32_t kIgLong = 1024;           // tokens longer than this are hashed by a workgroup, not by a thread
-constexpr uint32_t kIgEmpty = 0xFFFFFFFFu;
-constexpr uint64_t kIgP = 0x9E3779B97F4A7C15ull;   // odd: the polynomial's base modulo 2^64
-
-__device__ __forceinline__ bool ig_alnum(uint32_t c) { return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u); }
-__device__ __forceinline__ uint64_t ig_mix(uint64_t h) {   // the low bits of a polynomial modulo 2^64 only see the bytes' low bits
-    h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
-    return h;
-}
-__device__ __forceinline__ uint64_t ig_pow(uint64_t b, uint32_t e) {
-    uint64_t r = 1;
-    for (; e; e >>= 1, b *= b) if (e & 1u) r *= b;
-    return r;
-}
-
-// include/textutil.hpp:31-37, the words of 2 .. 4 bytes packed little-endian ("a" falls to the length rule)
-constexpr uint32_t ig_w(const char* s) {
-    uint32_t w = 0;
-    for (int i = 0; s[i]; i++) w |= (uint32_t)(unsigned char)s[i] << (8 * i);
-    return w;
-}
-__device__ __forceinline__ bool ig_stop(uint32_t w) {
-    constexpr uint32_t sw[] = {ig_w("the"), ig_w("an"), ig_w("and"), ig_w("or"), ig_w("of"), ig_w("to"), ig_w("in"), ig_w("for"),
-                               ig_w("on"), ig_w("with"), ig_w("by"), ig_w("as"), ig_w("is"), ig_w("are"), ig_w("was"), ig_w("were"),
-                               ig_w("be"), ig_w("been"), ig_w("it"), ig_w("this"), ig_w("that"), ig_w("from"), ig_w("at")};
-    bool hit = false;
-#pragma unroll
-    for (uint32_t s : sw) hit |= (w == s);
-    return hit;
-}
 
 __global__ void __launch_bounds__(256) k_ig_docmark(const uint32_t* __restrict__ offs, uint32_t n_docs, uint32_t n, uint32_t* __restrict__ docbits) {
     const uint32_t d = blockIdx.x * 256 + threadIdx.x;
@@ -174,9 +144,7 @@ __global__ void __launch_bounds__(256) k_ig_kept(const uint8_t* __restrict__ tex
         long_list[atomicAdd(long_count, 1u)] = k;                     // (the list's order is never read: each entry writes its own khash)
         return;
     }
-    uint64_t h = 0;
-    for (uint32_t j = 0; j < len; j++) h = h * kIgP + (uint64_t)(text[s + j] + 1u);
-    khash[k] = ig_mix(h ^ len) & hash_mask;
+    khash[k] = ig_hash_bytes(text + s, len) & hash_mask;
 }
 
 __global__ void __launch_bounds__(256) k_ig_hash_long(const uint8_t* __restrict__ text, const uint32_t* __restrict__ kstart,
@@ -192,16 +160,7 @@ __global__ void __launch_bounds__(256) k_ig_hash_long(const uint8_t* __restrict_
         for (uint32_t j = b; j < e; j++) h = h * kIgP + (uint64_t)(text[s + j] + 1u);
         part[threadIdx.x] = h;
         __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t H = 0;
-            const uint64_t pc = ig_pow(kIgP, chunk);
-            for (uint32_t t = 0; t < 256; t++) {
-                const uint32_t tb = min(len, t * chunk), te = min(len, tb + chunk);
-                if (te == tb) break;
-                H = H * (te - tb == chunk ? pc : ig_pow(kIgP, te - tb)) + part[t];
-            }
-            khash[k] = ig_mix(H ^ len) & hash_mask;
-        }
+        if (threadIdx.x == 0) khash[k] = ig_hash_join(part, len) & hash_mask;
         __syncthreads();
     }
 }

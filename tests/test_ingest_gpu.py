@@ -90,7 +90,8 @@ def assert_device_equals_restatement(tmp_path, docs, name, min_tokens=0):
         got = open(os.path.join(seg, fn), "rb").read()
         assert len(got) == len(want[fn]) and got == want[fn], (name, fn)
     assert st["n_docs"] == len(fwd["kept_docs"]) and st["n_terms"] == len(fwd["terms"]) and st["pairs"] == len(fwd["pairs"])
-    assert st["kept_tokens"] == int(fwd["doc_len"].sum()) and st["tokens"] >= max(min_tokens, st["kept_tokens"])
+    raw_tokens = sum(len(ingest_ref.tokenize(ingest_ref.doc_text(d))) for d in docs)          # dropped tokens count too
+    assert st["kept_tokens"] == int(fwd["doc_len"].sum()) and st["tokens"] == raw_tokens >= max(min_tokens, st["kept_tokens"])
     print(f"{name}: {st}")
     return st, fwd
 
