@@ -36,7 +36,8 @@
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
 #include "ns_call_plan.hpp"   // host only: what a ranked call plans on top of ns_sorted_plan.hpp and ns_after_plan.hpp
-#include "ns_radix_plan.hpp"  // host only: the digits of the radix sort in ns_invert.hip
+#include "ns_radix_plan.hpp"  // host only: the digits of the radix sort in ns_invert.hip, and what the inversion plans
+#include "ns_merge_plan.hpp"  // host only: what the merge plans before it touches the device
 
 using namespace ns;
 
@@ -1726,6 +1727,66 @@ extern "C" int ns_search_batch(ns_ctx* ctx, const ns_query_desc* queries, const 
 
 
 // ------------------------------------------------------------------------------------------------
+// The scan and the radix sort that the index-building calls share (csrc/ns_invert.hip)
+// exclusive scan of a[0 .. m) in place; the sum of all goes to *d_total (device, may be NULL); d_sums: ceil(m / 1024) words
+static void ig_scan(hipStream_t st, uint32_t* d_a, uint32_t m, uint32_t* d_sums, uint32_t* d_total) {
+    const uint32_t blocks = (m + 1023) / 1024;
+    hipLaunchKernelGGL(k_iv_scan_sums, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
+    hipLaunchKernelGGL(k_iv_scan_top, dim3(1), dim3(1024), 0, st, d_sums, blocks, d_total);
+    hipLaunchKernelGGL(k_iv_scan_apply, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
+}
+
+// What the inversion's first pass reads instead of buffer *cur: the pairs, the documents' pair prefix and each tile's first and
+// last document.  d_kept receives the number of items that survive the first pass; the later passes read their n from it.
+// All NULL: a sort of buffer *cur (ig_sort).
+struct IvFirst {
+    const uint2* d_pairs = nullptr;
+    const uint64_t* d_prefix = nullptr;
+    const uint2* d_tile_docs = nullptr;
+    uint32_t* d_kept = nullptr;
+};
+using IvHistKernel = void (*)(const uint32_t*, const uint2*, uint32_t, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t);
+using IvPassKernel = void (*)(const uint2*, const uint64_t*, const uint2*, uint32_t, const uint32_t*, const uint2*, uint32_t*, uint2*, uint32_t, const uint32_t*,
+                              uint32_t, const uint32_t*, uint32_t);
+
+// The stable LSD radix sort of ns_invert.hip over the keys below key_range, digit plan from key_range alone
+// (ns_radix_plan.hpp): per pass a histogram, its scan and the scatter from buffer *cur into the other one; the result is
+// buffer *cur afterwards.  With from.d_pairs the first pass reads the pairs and writes buffer 0 (*cur need not be set).
+// last_is_final: the last pass is the LAST instantiation of k_iv_pass.  d_hist: 2048 * ceil(n / kIvTile) words at most
+static void iv_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_keys[2], uint2* d_vals[2], int* cur, uint32_t* d_hist, uint32_t* d_sums,
+                    const IvFirst& from, bool last_is_final) {
+    static const IvHistKernel kHist[4] = {k_iv_hist_w<8>, k_iv_hist_w<9>, k_iv_hist_w<10>, k_iv_hist_w<11>};   // [digit width - 8]
+    static const IvPassKernel kPass[4][2][2] = {   // [digit width - 8][first][last]
+        {{k_iv_pass<8, false, false>, k_iv_pass<8, false, true>}, {k_iv_pass<8, true, false>, k_iv_pass<8, true, true>}},
+        {{k_iv_pass<9, false, false>, k_iv_pass<9, false, true>}, {k_iv_pass<9, true, false>, k_iv_pass<9, true, true>}},
+        {{k_iv_pass<10, false, false>, k_iv_pass<10, false, true>}, {k_iv_pass<10, true, false>, k_iv_pass<10, true, true>}},
+        {{k_iv_pass<11, false, false>, k_iv_pass<11, false, true>}, {k_iv_pass<11, true, false>, k_iv_pass<11, true, true>}}};
+    const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
+    const RadixPlan rp = radix_plan(key_range);
+    uint32_t shift = 0;
+    for (int p = 0; p < rp.passes; p++) {
+        const bool first = from.d_pairs && p == 0, last = last_is_final && p == rp.passes - 1;
+        const int w = rp.pbits[p] - 8;                                 // 8 .. 11 bits: 0 .. 3
+        const int nxt = first ? 0 : (*cur ^ 1);
+        const uint32_t m = ((uint32_t)1 << rp.pbits[p]) * n_tiles;     // < 2^31: fewer than 2^20 tiles of at most 2^11 bins
+        const uint32_t* kin = first ? nullptr : d_keys[*cur];
+        const uint2* vin = first ? nullptr : d_vals[*cur];
+        const uint32_t* n_dev = first ? nullptr : from.d_kept;
+        hipLaunchKernelGGL(kHist[w], dim3(n_tiles), dim3(256), 0, st, kin, first ? from.d_pairs : (const uint2*)nullptr, n, n_dev, key_range, shift, d_hist, n_tiles);
+        ig_scan(st, d_hist, m, d_sums, first ? from.d_kept : (uint32_t*)nullptr);
+        hipLaunchKernelGGL(kPass[w][first][last], dim3(n_tiles), dim3(256), 0, st, from.d_pairs, from.d_prefix, from.d_tile_docs, key_range, kin, vin, d_keys[nxt],
+                           d_vals[nxt], n, n_dev, shift, (const uint32_t*)d_hist, n_tiles);
+        shift += (uint32_t)rp.pbits[p];
+        *cur = nxt;
+    }
+}
+
+// the sort of n (key, value) items in buffer *cur, for text ingest and compaction: every pass is k_iv_pass<B, false, false>
+static void ig_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_keys[2], uint2* d_vals[2], int* cur, uint32_t* d_hist, uint32_t* d_sums) {
+    iv_sort(st, n, key_range, d_keys, d_vals, cur, d_hist, d_sums, IvFirst{}, false);
+}
+
+// ------------------------------------------------------------------------------------------------
 // f3: forward.bin -> inverted lists (csrc/ns_invert.hip)
 // `adopt` != nullptr: the inverted lists also become the posting stream of that segment (an upload in progress whose announced
 // payload is n_pairs postings) by a device-to-device copy; postings_out may then be NULL.
@@ -1739,46 +1800,28 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
     if (n_terms == 0xFFFFFFFFu) return fail(ctx, NS_E_INVAL, "ns_invert_forward: n_terms too large");
     *kept_out = 0;
     if (device_ms_out) *device_ms_out = 0.0f;
-    std::vector<uint64_t> prefix((size_t)n_docs + 1, 0);
-    for (uint32_t d = 0; d < n_docs; d++) prefix[d + 1] = prefix[d] + doc_term_counts[d];
-    if (prefix[n_docs] != n_pairs) return fail(ctx, NS_E_INVAL, "ns_invert_forward: the per-document counts sum to %llu, not to n_pairs = %llu", (unsigned long long)prefix[n_docs], (unsigned long long)n_pairs);
+    InvertPlan plan;
+    std::string why;
+    if (!invert_plan(doc_term_counts, n_docs, n_pairs, n_terms, plan, why)) return fail(ctx, NS_E_INVAL, "ns_invert_forward: %s", why.c_str());
     if (n_terms) std::memset(df_out, 0, (size_t)n_terms * 4);
     if (!n_pairs) return NS_OK;
     if (!postings_out && !adopt) return fail(ctx, NS_E_INVAL, "ns_invert_forward: postings_out is NULL");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)n_pairs;
-    const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
+    const uint32_t n = (uint32_t)n_pairs, n_tiles = plan.n_tiles;
     // Digit plan, from n_terms alone (no device -> host sync decides it): the keys are the termIds below n_terms — a pair with
     // any other termId is dropped by the reference (src/lexicon.cpp:69-70) and leaves the sort in the first pass — so
     // the width of n_terms - 1 is sorted in ceil(bits / 11) passes of 8 .. 11 bits, as even as possible (ns_radix_plan.hpp).
-    const RadixPlan rp = radix_plan(n_terms);
-    const int passes = rp.passes;
-    const int* pbits = rp.pbits;
-    size_t m_max = 0;
-    for (int p = 0; p < passes; p++) m_max = std::max(m_max, ((size_t)1 << pbits[p]) * n_tiles);
-    const uint32_t scan_blocks_max = (uint32_t)((m_max + 1023) / 1024);
+    const int passes = plan.rp.passes;
 
     // one block from the ctx pool for all scratch arrays (a build loop inverts segment after segment of similar size;
     // ten hipMalloc + hipFree per call cost more than the device work)
-    // the documents that hold each tile's first and last pair (the host has the prefix sums; the first pass marks the
-    // documents that start in between): the last d with prefix[d] <= i
-    std::vector<uint32_t> tile_docs((size_t)n_tiles * 2);
-    {
-        uint32_t d = 0;
-        auto doc_of = [&](uint64_t i) { while (d + 1 < n_docs && prefix[d + 1] <= i) d++; return d; };   // i ascends: one sweep over the documents
-        for (uint32_t t = 0; t < n_tiles; t++) {
-            const uint64_t i0 = (uint64_t)t * kIvTile, i1 = std::min<uint64_t>(i0 + kIvTile, n) - 1;
-            tile_docs[2 * (size_t)t] = doc_of(i0);
-            tile_docs[2 * (size_t)t + 1] = doc_of(i1);
-        }
-    }
     CallBlock blk(ctx);
     const size_t nt1 = (size_t)std::max<uint32_t>(n_terms, 1);
     const size_t o_pairs = blk.reserve(dev_pairs ? 1 : (size_t)n * 8), o_v0 = blk.reserve((size_t)n * 8), o_v1 = blk.reserve(passes > 1 ? (size_t)n * 8 : 1);
     const size_t o_k0 = blk.reserve((size_t)n * 4), o_k1 = blk.reserve(passes > 1 ? (size_t)n * 4 : 1);
-    const size_t o_df = blk.reserve(nt1 * 4), o_first = blk.reserve(nt1 * 4), o_hist = blk.reserve(m_max * 4), o_sums = blk.reserve((size_t)scan_blocks_max * 4),
-                 o_kept = blk.reserve(4), o_prefix = blk.reserve(prefix.size() * 8), o_tdocs = blk.reserve((size_t)n_tiles * 8);
+    const size_t o_df = blk.reserve(nt1 * 4), o_first = blk.reserve(nt1 * 4), o_hist = blk.reserve(plan.m_max * 4), o_sums = blk.reserve((size_t)plan.scan_blocks_max * 4),
+                 o_kept = blk.reserve(4), o_prefix = blk.reserve(plan.prefix.size() * 8), o_tdocs = blk.reserve((size_t)n_tiles * 8);
     blk.alloc(2);
     if (blk.ok()) {
         uint2* d_pairs = dev_pairs ? const_cast<uint2*>(dev_pairs) : blk.at<uint2>(o_pairs);
@@ -1786,50 +1829,17 @@ static int invert_run(ns_ctx* ctx, const uint32_t* doc_term_counts, uint32_t n_d
         uint32_t* d_keys[2] = {blk.at<uint32_t>(o_k0), blk.at<uint32_t>(o_k1)};
         uint32_t *d_df = blk.at<uint32_t>(o_df), *d_first = blk.at<uint32_t>(o_first), *d_hist = blk.at<uint32_t>(o_hist), *d_sums = blk.at<uint32_t>(o_sums),
                  *d_kept = blk.at<uint32_t>(o_kept);
-        const uint64_t* d_prefix = blk.at<uint64_t>(o_prefix);
-        const uint2* d_tile_docs = blk.at<uint2>(o_tdocs);
         if (!dev_pairs) blk.upload(o_pairs, pairs, (size_t)n * 8);
-        blk.upload(o_prefix, prefix.data(), prefix.size() * 8);
-        blk.upload(o_tdocs, tile_docs.data(), tile_docs.size() * 4);
+        blk.upload(o_prefix, plan.prefix.data(), plan.prefix.size() * 8);
+        blk.upload(o_tdocs, plan.tile_docs.data(), plan.tile_docs.size() * 4);
         blk.zero(o_df, nt1 * 4);
         blk.chk(hipMemsetAsync(d_first, 0xFF, nt1 * 4, st));
         blk.record(0);
-        // pass p reads (p == 0: the pairs; else keys / vals buffer `cur`) and writes buffer `nxt`.  The number of items that
-        // survive the first pass (the kept pairs) stays on the device: the first scan leaves it in d_kept, later kernels read it.
+        // The first pass reads the pairs and writes buffer 0.  The number of items that survive it (the kept pairs) stays on
+        // the device: the first scan leaves it in d_kept, later kernels read it.
         int cur = -1;
-        uint32_t shift = 0;
-        for (int p = 0; p < passes; p++) {
-            const bool first = p == 0, last = p == passes - 1;
-            const int nxt = first ? 0 : (cur ^ 1);
-            const size_t m = ((size_t)1 << pbits[p]) * n_tiles;
-            const uint32_t scan_blocks = (uint32_t)((m + 1023) / 1024);
-            const uint32_t* kin = first ? nullptr : d_keys[cur];
-            const uint2* vin = first ? nullptr : d_vals[cur];
-            const uint32_t* n_dev = first ? nullptr : d_kept;
-#define NS_IV_HIST(B) hipLaunchKernelGGL((k_iv_hist_w<B>), dim3(n_tiles), dim3(256), 0, st, kin, first ? d_pairs : (const uint2*)nullptr, n, n_dev, n_terms, shift, d_hist, n_tiles)
-#define NS_IV_PASS3(B, F, L) hipLaunchKernelGGL((k_iv_pass<B, F, L>), dim3(n_tiles), dim3(256), 0, st, d_pairs, d_prefix, d_tile_docs, n_terms, kin, vin, d_keys[nxt], d_vals[nxt], n, n_dev, shift, d_hist, n_tiles)
-#define NS_IV_PASS(B) { if (first && last) NS_IV_PASS3(B, true, true); else if (first) NS_IV_PASS3(B, true, false); else if (last) NS_IV_PASS3(B, false, true); else NS_IV_PASS3(B, false, false); }
-            switch (pbits[p]) {
-                case 8: NS_IV_HIST(8); break;
-                case 9: NS_IV_HIST(9); break;
-                case 10: NS_IV_HIST(10); break;
-                default: NS_IV_HIST(11); break;
-            }
-            hipLaunchKernelGGL(k_iv_scan_sums, dim3(scan_blocks), dim3(256), 0, st, d_hist, (uint32_t)m, d_sums);
-            hipLaunchKernelGGL(k_iv_scan_top, dim3(1), dim3(1024), 0, st, d_sums, scan_blocks, first ? d_kept : (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_iv_scan_apply, dim3(scan_blocks), dim3(256), 0, st, d_hist, (uint32_t)m, d_sums);
-            switch (pbits[p]) {
-                case 8: NS_IV_PASS(8); break;
-                case 9: NS_IV_PASS(9); break;
-                case 10: NS_IV_PASS(10); break;
-                default: NS_IV_PASS(11); break;
-            }
-#undef NS_IV_HIST
-#undef NS_IV_PASS
-#undef NS_IV_PASS3
-            shift += (uint32_t)pbits[p];
-            cur = nxt;
-        }
+        const IvFirst from_pairs{d_pairs, blk.at<uint64_t>(o_prefix), blk.at<uint2>(o_tdocs), d_kept};
+        iv_sort(st, n, n_terms, d_keys, d_vals, &cur, d_hist, d_sums, from_pairs, true);
         const uint2* d_final = d_vals[cur];
         // df from the sorted keys: a run's first pair records where it starts, its last pair where it ends (d_df holds the ends)
         if (n_terms) hipLaunchKernelGGL(k_iv_runs, dim3((n + 1023) / 1024), dim3(256), 0, st, d_keys[cur], n, n_terms, d_first, d_df, d_kept);
@@ -1896,36 +1906,6 @@ static void forward_free_device(ns_forward* f) {
 }
 static void forward_orphan_fwd(ns_forward* f) { forward_free_device(f); f->ctx = nullptr; }
 
-// exclusive scan of a[0 .. m) in place; the sum of all goes to *d_total (device, may be NULL); d_sums: ceil(m / 1024) words
-static void ig_scan(hipStream_t st, uint32_t* d_a, uint32_t m, uint32_t* d_sums, uint32_t* d_total) {
-    const uint32_t blocks = (m + 1023) / 1024;
-    hipLaunchKernelGGL(k_iv_scan_sums, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
-    hipLaunchKernelGGL(k_iv_scan_top, dim3(1), dim3(1024), 0, st, d_sums, blocks, d_total);
-    hipLaunchKernelGGL(k_iv_scan_apply, dim3(blocks), dim3(256), 0, st, d_a, m, d_sums);
-}
-
-// stable LSD radix sort of n (key, value) items by the keys below key_range, with ns_invert.hip's passes; the input is
-// buffer *cur, the result buffer *cur afterwards.  d_hist: 2048 * ceil(n / kIvTile) words
-static void ig_sort(hipStream_t st, uint32_t n, uint32_t key_range, uint32_t* d_keys[2], uint2* d_vals[2], int* cur, uint32_t* d_hist, uint32_t* d_sums) {
-    const uint32_t n_tiles = (n + kIvTile - 1) / kIvTile;
-    const RadixPlan rp = radix_plan(key_range);
-    uint32_t shift = 0;
-    for (int p = 0; p < rp.passes; p++) {
-        const int pb = rp.pbits[p];
-        const int nxt = *cur ^ 1;
-        const uint32_t m = ((uint32_t)1 << pb) * n_tiles;
-#define NS_IG_HIST(B) hipLaunchKernelGGL((k_iv_hist_w<B>), dim3(n_tiles), dim3(256), 0, st, d_keys[*cur], (const uint2*)nullptr, n, (const uint32_t*)nullptr, key_range, shift, d_hist, n_tiles)
-#define NS_IG_PASS(B) hipLaunchKernelGGL((k_iv_pass<B, false, false>), dim3(n_tiles), dim3(256), 0, st, (const uint2*)nullptr, (const uint64_t*)nullptr, (const uint2*)nullptr, key_range, d_keys[*cur], d_vals[*cur], d_keys[nxt], d_vals[nxt], n, (const uint32_t*)nullptr, shift, d_hist, n_tiles)
-        switch (pb) { case 8: NS_IG_HIST(8); break; case 9: NS_IG_HIST(9); break; case 10: NS_IG_HIST(10); break; default: NS_IG_HIST(11); break; }
-        ig_scan(st, d_hist, m, d_sums, nullptr);
-        switch (pb) { case 8: NS_IG_PASS(8); break; case 9: NS_IG_PASS(9); break; case 10: NS_IG_PASS(10); break; default: NS_IG_PASS(11); break; }
-#undef NS_IG_HIST
-#undef NS_IG_PASS
-        shift += (uint32_t)pb;
-        *cur = nxt;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Filtered copy of a segment (csrc/ns_filter.hip)
 extern "C" int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint32_t* keep_bits, const uint64_t* byte_off,
@@ -1952,87 +1932,75 @@ extern "C" int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, 
     const uint32_t n_chunks = (n + kFlChunk - 1) / kFlChunk, m = n_chunks + 1;
     const uint32_t n_words = (n_docs + 31) / 32;
     hipStream_t st = ctx->stream;
-    uint32_t *d_bits = nullptr, *d_base = nullptr, *d_sums = nullptr, *d_total = nullptr, *d_starts = nullptr, *d_counts = nullptr, *d_ncnt = nullptr;
-    uint64_t *d_mask = nullptr, *d_noff = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the scratch of the call in one block from the ctx pool; the new segment's own arrays are hipMallocs, like a forward handle's
+    CallBlock blk(ctx);
+    const size_t o_bits = blk.reserve((size_t)std::max<uint32_t>(n_words, 1) * 4), o_mask = blk.reserve((size_t)m * 8), o_base = blk.reserve((size_t)m * 4),
+                 o_sums = blk.reserve((size_t)((m + 1023) / 1024) * 4), o_total = blk.reserve(4);
+    const size_t o_starts = blk.reserve((size_t)n_lists * 4), o_counts = blk.reserve((size_t)n_lists * 4), o_ncnt = blk.reserve((size_t)n_lists * 4),
+                 o_noff = blk.reserve((size_t)n_lists * 8);
+    blk.alloc(4);
     ns_seg* s = new ns_seg();
     s->ctx = ctx;
     s->id = new_seg_id;
     s->n_docs = n_docs;
     s->avgdl = src->avgdl;
     s->norm_safe = src->norm_safe;
-    auto cleanup = [&]() {
-        (void)hipFree(d_bits); (void)hipFree(d_base); (void)hipFree(d_sums); (void)hipFree(d_total); (void)hipFree(d_starts);
-        (void)hipFree(d_counts); (void)hipFree(d_ncnt); (void)hipFree(d_mask); (void)hipFree(d_noff);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    };
-    auto bail = [&](int code, const char* what, hipError_t e) {
-        (void)hipStreamSynchronize(st);
-        cleanup();
+    uint32_t kept = 0;
+    if (blk.ok()) {
+        uint32_t *d_bits = blk.at<uint32_t>(o_bits), *d_base = blk.at<uint32_t>(o_base), *d_sums = blk.at<uint32_t>(o_sums), *d_total = blk.at<uint32_t>(o_total);
+        uint32_t *d_starts = blk.at<uint32_t>(o_starts), *d_counts = blk.at<uint32_t>(o_counts), *d_ncnt = blk.at<uint32_t>(o_ncnt);
+        uint64_t *d_mask = blk.at<uint64_t>(o_mask), *d_noff = blk.at<uint64_t>(o_noff);
+        std::vector<uint32_t> starts(n_lists);
+        for (uint32_t i = 0; i < n_lists; i++) starts[i] = (uint32_t)(byte_off[i] / 8);
+        blk.upload(o_bits, keep_bits, (size_t)n_words * 4);
+        blk.upload(o_starts, starts.data(), (size_t)n_lists * 4);
+        blk.upload(o_counts, counts, (size_t)n_lists * 4);
+
+        // mark + scan, then the one number the host needs before it can size the copy
+        const uint32_t grid = std::min<uint32_t>((m + 3) / 4, 1u << 16);
+        blk.record(0);
+        hipLaunchKernelGGL(k_fl_mark, dim3(grid), dim3(256), 0, st, src->d_postings, n, d_bits, n_docs, d_mask, d_base);
+        ig_scan(st, d_base, m, d_sums, d_total);
+        blk.record(1);
+        blk.launched();
+        if (blk.ok()) blk.fetch(&kept, o_total, 4);
+        if (blk.ok()) blk.sync();
+        if (blk.ok() && kept > n) blk.chk(hipErrorUnknown);
+
+        if (blk.ok()) {
+            s->n_postings = kept;
+            blk.chk(hipMalloc((void**)&s->d_postings, ((size_t)kept + kPadPostings) * 8));
+            blk.chk(hipMalloc((void**)&s->d_pnorm, ((size_t)kept + kPadPostings) * 4));
+            blk.chk(hipMalloc((void**)&s->d_norm, (size_t)std::max<uint32_t>(n_docs, 1) * 4));
+        }
+        if (blk.ok()) {
+            blk.chk(hipMemsetAsync(s->d_postings + kept, 0xFF, kPadPostings * 8, st));   // docId ~0: never taken
+            blk.chk(hipMemsetAsync(s->d_pnorm + kept, 0, kPadPostings * 4, st));
+            if (n_docs) blk.chk(hipMemcpyAsync(s->d_norm, src->d_norm, (size_t)n_docs * 4, hipMemcpyDeviceToDevice, st));
+        }
+        if (blk.ok()) {
+            blk.record(2);
+            if (n_chunks) hipLaunchKernelGGL(k_fl_scatter, dim3(std::min<uint32_t>((n_chunks + 3) / 4, 1u << 16)), dim3(256), 0, st, src->d_postings, src->d_pnorm, n, d_mask, d_base, s->d_postings, s->d_pnorm);
+            if (n_lists) hipLaunchKernelGGL(k_fl_lists, dim3((n_lists + 255) / 256), dim3(256), 0, st, d_starts, d_counts, n_lists, d_mask, d_base, d_noff, d_ncnt);
+            blk.record(3);
+            blk.launched();
+        }
+        if (blk.ok() && n_lists) {
+            blk.fetch(new_byte_off_out, o_noff, (size_t)n_lists * 8);
+            blk.fetch(new_counts_out, o_ncnt, (size_t)n_lists * 4);
+        }
+        if (blk.ok() && postings_out && kept) blk.chk(hipMemcpyAsync(postings_out, s->d_postings, (size_t)kept * 8, hipMemcpyDeviceToHost, st));
+        if (blk.ok()) blk.sync();
+        float a = 0.0f, b = 0.0f;
+        if (blk.elapsed_ms(0, 1, &a) && blk.elapsed_ms(2, 3, &b) && device_ms_out) *device_ms_out = a + b;
+    }
+    const int rc = blk.finish("ns_segment_filter");
+    if (rc != NS_OK) {
         seg_free_device(s);
         delete s;
-        return fail(ctx, code, "ns_segment_filter: %s: %s", what, hipGetErrorString(e));
-    };
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_bits, (size_t)std::max<uint32_t>(n_words, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, (size_t)m * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_base, (size_t)m * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, (size_t)((m + 1023) / 1024) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_total, 4);
-    if (e == hipSuccess && n_lists) {
-        e = hipMalloc((void**)&d_starts, (size_t)n_lists * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_counts, (size_t)n_lists * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_ncnt, (size_t)n_lists * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_noff, (size_t)n_lists * 8);
-    }
-    if (e != hipSuccess) return bail(NS_E_NOMEM, "allocation", e);
-    std::vector<uint32_t> starts(n_lists);
-    for (uint32_t i = 0; i < n_lists; i++) starts[i] = (uint32_t)(byte_off[i] / 8);
-    if (n_words) e = hipMemcpyAsync(d_bits, keep_bits, (size_t)n_words * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(d_starts, starts.data(), (size_t)n_lists * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(d_counts, counts, (size_t)n_lists * 4, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return bail(NS_E_HIP, "upload", e);
-
-    // mark + scan, then the one number the host needs before it can size the copy
-    const uint32_t grid = std::min<uint32_t>((m + 3) / 4, 1u << 16);
-    (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL(k_fl_mark, dim3(grid), dim3(256), 0, st, src->d_postings, n, d_bits, n_docs, d_mask, d_base);
-    ig_scan(st, d_base, m, d_sums, d_total);
-    (void)hipEventRecord(ev[1], st);
-    uint32_t kept = 0;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&kept, d_total, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(NS_E_HIP, "mark", e);
-    if (kept > n) return bail(NS_E_HIP, "mark", hipErrorUnknown);
-
-    s->n_postings = kept;
-    if ((e = hipMalloc((void**)&s->d_postings, ((size_t)kept + kPadPostings) * 8)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc postings", e);
-    if ((e = hipMalloc((void**)&s->d_pnorm, ((size_t)kept + kPadPostings) * 4)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc per-posting norms", e);
-    if ((e = hipMalloc((void**)&s->d_norm, (size_t)std::max<uint32_t>(n_docs, 1) * 4)) != hipSuccess) return bail(NS_E_NOMEM, "hipMalloc norm", e);
-    e = hipMemsetAsync(s->d_postings + kept, 0xFF, kPadPostings * 8, st);   // docId ~0: never taken
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_pnorm + kept, 0, kPadPostings * 4, st);
-    if (e == hipSuccess && n_docs) e = hipMemcpyAsync(s->d_norm, src->d_norm, (size_t)n_docs * 4, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return bail(NS_E_HIP, "copy", e);
-    (void)hipEventRecord(ev[2], st);
-    if (n_chunks) hipLaunchKernelGGL(k_fl_scatter, dim3(std::min<uint32_t>((n_chunks + 3) / 4, 1u << 16)), dim3(256), 0, st, src->d_postings, src->d_pnorm, n, d_mask, d_base, s->d_postings, s->d_pnorm);
-    if (n_lists) hipLaunchKernelGGL(k_fl_lists, dim3((n_lists + 255) / 256), dim3(256), 0, st, d_starts, d_counts, n_lists, d_mask, d_base, d_noff, d_ncnt);
-    (void)hipEventRecord(ev[3], st);
-    e = hipGetLastError();
-    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(new_byte_off_out, d_noff, (size_t)n_lists * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_lists) e = hipMemcpyAsync(new_counts_out, d_ncnt, (size_t)n_lists * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && postings_out && kept) e = hipMemcpyAsync(postings_out, s->d_postings, (size_t)kept * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(NS_E_HIP, "scatter", e);
-    if (device_ms_out) {
-        float a = 0.0f, b = 0.0f;
-        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&b, ev[2], ev[3]);
-        *device_ms_out = a + b;
+        return rc;
     }
     if (kept_postings_out) *kept_postings_out = kept;
-    cleanup();
     if (ctx->segs.size() <= new_seg_id) ctx->segs.resize(new_seg_id + 1, nullptr);
     ctx->segs[new_seg_id] = s;
     *out = s;
@@ -2045,6 +2013,66 @@ static void read_counts(CallBlock& blk, uint32_t (&h_cnt)[8]) {
     blk.launched();
     if (blk.ok()) blk.chk(hipMemcpyAsync(h_cnt, blk.at<uint32_t>(0, 0), sizeof(h_cnt), hipMemcpyDeviceToHost, blk.st));
     if (blk.ok()) blk.sync();
+}
+
+// The dictionary stage that text ingest runs over its kept tokens and the merge over its source terms:
+// K "tokens" (start, length, hash) of d_text, the table of `cap` slots (filled with 0xFF by the caller), and what the stage
+// writes per token.  d_owner: a token's document (ingest) or source (merge).
+struct DictStage {
+    const uint8_t* d_text;
+    const uint32_t *d_kstart, *d_klen, *d_owner;
+    const uint64_t* d_khash;
+    uint32_t K;
+    uint32_t* d_table;
+    uint64_t cap;
+    uint32_t *d_kslot, *d_krep, *d_fid, *d_tsrc, *d_sums;
+};
+// the distinct byte strings: k_ig_insert, k_ig_first, their number scanned into *d_n_terms; then the counters are read
+static void dict_count_terms(CallBlock& blk, const DictStage& D, uint32_t* d_n_terms, uint32_t (&h_cnt)[8]) {
+    const uint32_t g = (D.K + 255) / 256;
+    hipLaunchKernelGGL(k_ig_insert, dim3(g), dim3(256), 0, blk.st, D.d_text, D.d_kstart, D.d_klen, D.d_khash, D.K, D.d_table, (uint32_t)(D.cap - 1), D.d_kslot);
+    hipLaunchKernelGGL(k_ig_first, dim3(g), dim3(256), 0, blk.st, D.d_table, D.d_kslot, D.K, D.d_krep, D.d_fid);
+    ig_scan(blk.st, D.d_fid, D.K, D.d_sums, d_n_terms);
+    read_counts(blk, h_cnt);
+}
+// the handle's term offsets: allocated and zeroed; with tokens, k_ig_termid (the tokens' term ids into d_ids, {owner, term} into
+// d_vals, the terms' lengths into d_toff) and the lengths scanned, their sum into *d_term_bytes
+static void dict_term_ids(CallBlock& blk, const DictStage& D, ns_forward* f, uint32_t n_terms, uint32_t* d_ids, uint2* d_vals, uint32_t* d_term_bytes) {
+    if (blk.ok()) blk.chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+    if (!blk.ok()) return;
+    blk.chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, blk.st));
+    if (!D.K) return;
+    hipLaunchKernelGGL(k_ig_termid, dim3((D.K + 255) / 256), dim3(256), 0, blk.st, D.d_krep, D.d_fid, D.d_owner, D.d_kstart, D.d_klen, D.K, d_ids, d_vals, f->d_toff, D.d_tsrc);
+    ig_scan(blk.st, f->d_toff, n_terms + 1, D.d_sums, d_term_bytes);
+}
+
+// ---- the frame around a forward handle (ns_forward_build and the merge) ----
+// test knob (variants build only): narrow the term hash so that every probe collides and the byte comparison decides
+static uint64_t ingest_hash_mask() {
+#ifdef NS_VARIANTS
+    if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) return (1ull << b) - 1ull; }
+#endif
+    return ~0ull;
+}
+static ns_forward* forward_new(ns_ctx* ctx) {
+    ns_forward* f = new ns_forward();
+    f->ctx = ctx;
+    f->info.struct_size = (uint32_t)sizeof(ns_forward_info);
+    return f;
+}
+static int forward_publish(ns_ctx* ctx, ns_forward* f, ns_forward** out) {
+    ctx->fwds.push_back(f);
+    *out = f;
+    return NS_OK;
+}
+// the end of a call that built f with `scratch_bytes` of pooled blocks: rc != NS_OK discards the half-built handle
+static int forward_finish(ns_ctx* ctx, ns_forward* f, ns_forward** out, size_t scratch_bytes, int rc) {
+    f->info.device_bytes = (uint64_t)scratch_bytes + ((uint64_t)f->info.n_terms + 1) * 4 + (uint64_t)f->info.kept_docs * 12 + f->info.n_pairs * 8 + f->info.term_bytes;
+    if (rc == NS_OK) return forward_publish(ctx, f, out);
+    forward_free_device(f);
+    delete f;
+    (void)hipGetLastError();
+    return rc;
 }
 
 extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_bytes, const uint64_t* offsets, uint32_t n_docs, ns_forward** out) {
@@ -2061,19 +2089,12 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
     if (n64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "ns_forward_build: %llu bytes of text; this build addresses text with 32 bits (below 4 GiB - 64 KiB per call: split the batch)", (unsigned long long)n64);
     if (n64 && !text) return fail(ctx, NS_E_INVAL, "ns_forward_build: text is NULL");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ns_forward* f = new ns_forward();
-    f->ctx = ctx;
-    f->info.struct_size = (uint32_t)sizeof(ns_forward_info);
+    ns_forward* f = forward_new(ctx);
     f->info.n_docs = n_docs;
-    auto publish = [&]() { ctx->fwds.push_back(f); *out = f; return NS_OK; };
-    if (n64 == 0) return publish();   // no text: no token, no document survives
+    if (n64 == 0) return forward_publish(ctx, f, out);   // no text: no token, no document survives
     const uint32_t n = (uint32_t)n64;
     hipStream_t st = ctx->stream;
-    uint64_t hash_mask = ~0ull;
-#ifdef NS_VARIANTS
-    // test knob (variants build only): narrow the hash so that every probe collides and the byte comparison decides
-    if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) hash_mask = (1ull << b) - 1ull; }
-#endif
+    const uint64_t hash_mask = ingest_hash_mask();
     CallBlock blk(ctx);
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     enum { C_TOK = 0, C_TOKE = 1, C_KEPT = 2, C_LONG = 3, C_KD = 4, C_TERMS = 5, C_TBYTES = 6, C_PAIRS = 7 };
@@ -2158,23 +2179,18 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
                 hipLaunchKernelGGL(k_iv_runs, dim3((K + 1023) / 1024), dim3(256), 0, st, d_kdoc, K, n_docs, d_dfirst, d_dlast, (const uint32_t*)nullptr);
                 hipLaunchKernelGGL(k_ig_docflag, dim3(g_docs), dim3(256), 0, st, d_dfirst, n_docs, d_didx);
                 ig_scan(st, d_didx, n_docs, d_sumsA, d_cntv + C_KD);
-                hipLaunchKernelGGL(k_ig_insert, dim3(gK), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, K, d_table, (uint32_t)(cap - 1), d_kslot);
-                hipLaunchKernelGGL(k_ig_first, dim3(gK), dim3(256), 0, st, d_table, d_kslot, K, d_krep, d_fid);
-                ig_scan(st, d_fid, K, d_sums, d_cntv + C_TERMS);
-                read_counts(blk, h_cnt);
+                const DictStage dict{d_text, d_kstart, d_klen, d_kdoc, d_khash, K, d_table, cap, d_kslot, d_krep, d_fid, d_tsrc, d_sums};
+                dict_count_terms(blk, dict, d_cntv + C_TERMS, h_cnt);
                 const uint32_t n_terms = h_cnt[C_TERMS], n_kd = h_cnt[C_KD];
                 f->info.n_terms = n_terms; f->info.kept_docs = n_kd;
                 if (blk.ok()) {
-                    blk.chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
                     blk.chk(hipMalloc((void**)&f->d_map, (size_t)n_kd * 4));
                     blk.chk(hipMalloc((void**)&f->d_len, (size_t)n_kd * 4));
                     blk.chk(hipMalloc((void**)&f->d_cnt, (size_t)n_kd * 4));
                 }
                 int cur = 0;
+                dict_term_ids(blk, dict, f, n_terms, d_keys[0], d_vals[0], d_cntv + C_TBYTES);
                 if (blk.ok()) {
-                    blk.chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
-                    hipLaunchKernelGGL(k_ig_termid, dim3(gK), dim3(256), 0, st, d_krep, d_fid, d_kdoc, d_kstart, d_klen, K, d_keys[0], d_vals[0], f->d_toff, d_tsrc);
-                    ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
                     ig_sort(st, K, n_terms, d_keys, d_vals, &cur, d_hist, d_sums);
                     hipLaunchKernelGGL(k_ig_runflag, dim3(gK), dim3(256), 0, st, d_vals[cur], K, d_kslot);
                     ig_scan(st, d_kslot, K, d_sums, d_cntv + C_PAIRS);
@@ -2208,14 +2224,7 @@ extern "C" int ns_forward_build(ns_ctx* ctx, const uint8_t* text, uint64_t text_
         if (blk.elapsed_ms(0, 1, &ms)) f->info.device_ms = ms;
     }
     const int rc = blk.finish("ns_forward_build", blk.e == hipErrorUnknown ? "token starts and ends disagree (internal error)" : nullptr);
-    f->info.device_bytes = (uint64_t)blk.held_bytes() + ((uint64_t)f->info.n_terms + 1) * 4 + (uint64_t)f->info.kept_docs * 12 + f->info.n_pairs * 8 + f->info.term_bytes;
-    if (rc != NS_OK) {
-        forward_free_device(f);
-        delete f;
-        (void)hipGetLastError();
-        return rc;
-    }
-    return publish();
+    return forward_finish(ctx, f, out, blk.held_bytes(), rc);
 }
 
 extern "C" int ns_forward_get_info(const ns_forward* fwd, ns_forward_info* info) {
@@ -2288,104 +2297,20 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
     if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
     *out = nullptr;
     if (n_src && !src) return fail(ctx, NS_E_INVAL, "%s: src is NULL", fn);
-    // ---- the totals, from the counts alone ----
-    uint64_t docs64 = 0, pairs64 = 0, terms64 = 0;
-    for (uint32_t s = 0; s < n_src; s++) {
-        docs64 += src[s].n_docs; terms64 += src[s].n_terms;
-        if (src[s].n_pairs >= (1ull << 32) || (pairs64 += src[s].n_pairs) >= (1ull << 32) - kIvTile)
-            return fail(ctx, NS_E_INVAL, "%s: more than %llu pairs up to source %u; this build indexes pairs with 32 bits (compact fewer segments)", fn, (unsigned long long)((1ull << 32) - kIvTile - 1), s);
-    }
-    if (docs64 >= 0xFFFFFFFFull) return fail(ctx, NS_E_INVAL, "%s: %llu documents; docIds are 32 bits wide (below 2^32 - 1: compact fewer segments)", fn, (unsigned long long)docs64);
-    if (terms64 >= (1ull << 31)) return fail(ctx, NS_E_INVAL, "%s: %llu source terms; the dictionary holds fewer than 2^31 (compact fewer segments)", fn, (unsigned long long)terms64);
-    uint64_t bytes64 = 0;
-    for (uint32_t s = 0; s < n_src; s++) {
-        const ns_forward_src& S = src[s];
-        if ((S.n_docs && (!S.doc_len || !S.counts)) || (S.n_pairs && !S.pairs) || (S.n_terms && !S.term_offsets)) return fail(ctx, NS_E_INVAL, "%s: source %u: null array", fn, s);
-        if (S.n_terms) {
-            if (S.term_offsets[S.n_terms] < S.term_offsets[0]) return fail(ctx, NS_E_INVAL, "%s: source %u: term offsets decrease", fn, s);
-            bytes64 += S.term_offsets[S.n_terms] - S.term_offsets[0];
-            if (bytes64 >= (1ull << 32) - 65536) return fail(ctx, NS_E_INVAL, "%s: more than 4 GiB - 64 KiB of term bytes up to source %u; this build addresses them with 32 bits (compact fewer segments)", fn, s);
-        }
-    }
-    bool filtered = false;                                             // some source has a bitmap: the stages of ns_delete.hip run
-    for (uint32_t s = 0; keep && s < n_src; s++) filtered = filtered || keep[s] != nullptr;
-    const uint32_t raw_pairs = (uint32_t)pairs64, T = (uint32_t)terms64, n = (uint32_t)bytes64;
-    uint32_t n_docs = (uint32_t)docs64, n_pairs = raw_pairs;           // filtered: the survivors', set below
-    std::vector<uint32_t> term_base((size_t)n_src + 1, 0), pair_base((size_t)n_src + 1, 0), kstart(T), klen(T), prefix((size_t)n_docs + 1, 0);
-    // filtered only: where a source's pairs lie in the upload, per surviving document its first pair there, its doc_len and
-    // count, and per source term 1 where the source has no bitmap (its terms all stay)
-    std::vector<uint32_t> raw_base, srcpos, kept_len, kept_cnt, live0;
-    if (filtered) { raw_base.assign((size_t)n_src + 1, 0); srcpos.reserve(n_docs); kept_len.reserve(n_docs); kept_cnt.reserve(n_docs); live0.assign((size_t)T + 1, 0); }
-    uint64_t total_len = 0;
-    {
-        uint32_t d = 0, k = 0, at = 0;
-        for (uint32_t s = 0; s < n_src; s++) {
-            const ns_forward_src& S = src[s];
-            uint64_t sum = 0;
-            if (!filtered) {
-                for (uint32_t j = 0; j < S.n_docs; j++, d++) { sum += S.counts[j]; total_len += S.doc_len[j]; prefix[d + 1] = (uint32_t)(pair_base[s] + sum); if (sum > S.n_pairs) break; }
-                pair_base[s + 1] = pair_base[s] + (uint32_t)S.n_pairs;
-            } else {
-                const uint32_t* bits = keep[s];
-                uint64_t stay = 0;                                     // pairs of the source's surviving documents so far
-                for (uint32_t j = 0; j < S.n_docs; j++) {
-                    const uint32_t c = S.counts[j];
-                    if (!bits || ((bits[j >> 5] >> (j & 31u)) & 1u)) {
-                        srcpos.push_back(raw_base[s] + (uint32_t)sum); kept_len.push_back(S.doc_len[j]); kept_cnt.push_back(c);
-                        total_len += S.doc_len[j];
-                        stay += c;
-                        prefix[++d] = (uint32_t)(pair_base[s] + stay);
-                    }
-                    sum += c;
-                    if (sum > S.n_pairs) break;
-                }
-                raw_base[s + 1] = raw_base[s] + (uint32_t)S.n_pairs;
-                pair_base[s + 1] = pair_base[s] + (uint32_t)stay;
-                if (!bits) std::fill(live0.begin() + term_base[s], live0.begin() + term_base[s] + S.n_terms, 1u);
-            }
-            if (sum != S.n_pairs) return fail(ctx, NS_E_INVAL, "%s: source %u: the per-document counts do not sum to n_pairs = %llu", fn, s, (unsigned long long)S.n_pairs);
-            for (uint32_t t = 0; t < S.n_terms; t++, k++) {
-                if (S.term_offsets[t + 1] < S.term_offsets[t]) return fail(ctx, NS_E_INVAL, "%s: source %u: term offsets decrease at term %u", fn, s, t);
-                kstart[k] = at + (uint32_t)(S.term_offsets[t] - S.term_offsets[0]);
-                klen[k] = (uint32_t)(S.term_offsets[t + 1] - S.term_offsets[t]);
-            }
-            if (S.n_terms && S.term_offsets[S.n_terms] != S.term_offsets[0] && !S.term_bytes) return fail(ctx, NS_E_INVAL, "%s: source %u: term_bytes is NULL", fn, s);
-            if (S.n_terms) at += (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]);
-            term_base[s + 1] = term_base[s] + S.n_terms;
-        }
-        if (filtered) { n_docs = d; n_pairs = pair_base[n_src]; prefix.resize((size_t)n_docs + 1); }
-    }
+    MergePlan plan;                                                    // everything the host derives from the sources (ns_merge_plan.hpp)
+    std::string why;
+    if (!merge_plan(src, keep, n_src, ctx->cp_inplace, plan, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const bool filtered = plan.filtered;
+    const uint32_t raw_pairs = plan.raw_pairs, T = plan.T, n = plan.text_bytes, n_docs = plan.n_docs, n_pairs = plan.n_pairs;
+    const uint32_t n_wave = plan.n_wave, n_lds = plan.n_lds, n_bigdocs = plan.n_bigdocs, n_big = plan.n_big;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ns_forward* f = new ns_forward();
-    f->ctx = ctx;
-    f->info.struct_size = (uint32_t)sizeof(ns_forward_info);
-    auto publish = [&]() { ctx->fwds.push_back(f); *out = f; return NS_OK; };
-    if (n_docs == 0) return publish();   // no document: an empty result, whatever the term lists hold
+    ns_forward* f = forward_new(ctx);
+    if (n_docs == 0) return forward_publish(ctx, f, out);   // no document: an empty result, whatever the term lists hold
     f->info.n_docs = f->info.kept_docs = n_docs;
-    f->info.n_tokens = f->info.kept_tokens = total_len;
+    f->info.n_tokens = f->info.kept_tokens = plan.total_len;
     f->info.n_pairs = n_pairs;
     hipStream_t st = ctx->stream;
-    uint64_t hash_mask = ~0ull;
-#ifdef NS_VARIANTS
-    if (const char* hb = std::getenv("NS_INGEST_HASH_BITS")) { const int b = std::atoi(hb); if (b >= 0 && b < 64) hash_mask = (1ull << b) - 1ull; }
-#endif
-    // the documents by size class: sorted by a wave, by a workgroup in LDS, or by the global radix sort (a document of one
-    // pair is in order as it is)
-    std::vector<uint32_t> l_wave, l_lds, l_big, big_prefix(1, 0);
-    for (uint32_t d = 0; d < n_docs; d++) {
-        const uint32_t c = prefix[d + 1] - prefix[d];
-        if (c < 2) continue;
-        if (ctx->cp_inplace && c <= kCpWaveMax) l_wave.push_back(d);
-        else if (ctx->cp_inplace && c <= kCpDocCut) l_lds.push_back(d);
-        else { l_big.push_back(d); big_prefix.push_back(big_prefix.back() + c); }
-    }
-    const uint32_t n_wave = (uint32_t)l_wave.size(), n_lds = (uint32_t)l_lds.size(), n_bigdocs = (uint32_t)l_big.size(), n_big = big_prefix.back();
-    std::vector<uint32_t> lists;
-    lists.reserve((size_t)n_wave + n_lds + 2 * (size_t)n_bigdocs + 1);
-    lists.insert(lists.end(), l_wave.begin(), l_wave.end());
-    lists.insert(lists.end(), l_lds.begin(), l_lds.end());
-    lists.insert(lists.end(), l_big.begin(), l_big.end());
-    lists.insert(lists.end(), big_prefix.begin(), big_prefix.end());
+    const uint64_t hash_mask = ingest_hash_mask();
 
     CallBlock blk(ctx);
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2402,15 +2327,15 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
                  o_vals = blk.reserve(T1 * 8);
     const size_t o_tab = blk.reserve((size_t)cap * 4), o_dtab = blk.reserve((size_t)cap * 8), o_long = blk.reserve(((size_t)n / kIgLong + 1) * 4),
                  o_sums = blk.reserve((scan_max / 1024 + 2) * 4);
-    const size_t o_tb = blk.reserve(term_base.size() * 4), o_pb = blk.reserve(pair_base.size() * 4), o_prefix = blk.reserve(prefix.size() * 4),
-                 o_lists = blk.reserve(lists.size() * 4);
+    const size_t o_tb = blk.reserve(plan.term_base.size() * 4), o_pb = blk.reserve(plan.pair_base.size() * 4), o_prefix = blk.reserve(plan.prefix.size() * 4),
+                 o_lists = blk.reserve(plan.lists.size() * 4);
     const size_t A = blk.alloc(2);
     // ---- block F (filtered only): the pairs as uploaded, the live flags and their scan, the source terms' (start, length),
     // the surviving terms' per-source base, the (source, old id) -> new id map, the surviving documents' places in the upload ----
     blk.open();
     const size_t o_raw = blk.reserve((size_t)raw_pairs * 8), o_live = blk.reserve(((size_t)T + 1) * 4), o_rank = blk.reserve(((size_t)T + 1) * 4), o_ks0 = blk.reserve(T1 * 4),
                  o_kl0 = blk.reserve(T1 * 4);
-    const size_t o_tbl = blk.reserve(term_base.size() * 4), o_omap = blk.reserve(T1 * 4), o_spos = blk.reserve((size_t)n_docs * 4);
+    const size_t o_tbl = blk.reserve(plan.term_base.size() * 4), o_omap = blk.reserve(T1 * 4), o_spos = blk.reserve((size_t)n_docs * 4);
     const size_t F = filtered ? blk.alloc(0) : A;
     blk.chk(hipMalloc((void**)&f->d_pairs, (size_t)n_pairs * 8));
     blk.chk(hipMalloc((void**)&f->d_map, (size_t)n_docs * 4));
@@ -2444,8 +2369,8 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
                 const uint32_t nb = S.n_terms ? (uint32_t)(S.term_offsets[S.n_terms] - S.term_offsets[0]) : 0u;
                 if (nb) blk.chk(hipMemcpyAsync(d_text + at, S.term_bytes + S.term_offsets[0], nb, hipMemcpyHostToDevice, st));
                 if (filtered) {   // (a source without a surviving pair is not uploaded: nothing reads it)
-                    if (pair_base[s + 1] != pair_base[s]) blk.chk(hipMemcpyAsync(d_raw + raw_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
-                } else if (S.n_pairs) blk.chk(hipMemcpyAsync(f->d_pairs + pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                    if (plan.pair_base[s + 1] != plan.pair_base[s]) blk.chk(hipMemcpyAsync(d_raw + plan.raw_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
+                } else if (S.n_pairs) blk.chk(hipMemcpyAsync(f->d_pairs + plan.pair_base[s], S.pairs, (size_t)S.n_pairs * 8, hipMemcpyHostToDevice, st));
                 if (S.n_docs && !filtered) {
                     blk.chk(hipMemcpyAsync(f->d_len + d, S.doc_len, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
                     blk.chk(hipMemcpyAsync(f->d_cnt + d, S.counts, (size_t)S.n_docs * 4, hipMemcpyHostToDevice, st));
@@ -2457,19 +2382,19 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
         for (uint32_t d = 0; d < n_docs; d++) iota[d] = d;
         blk.chk(hipMemcpyAsync(f->d_map, iota.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
         if (T) {
-            blk.chk(hipMemcpyAsync(d_ks0, kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
-            blk.chk(hipMemcpyAsync(d_kl0, klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_ks0, plan.kstart.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_kl0, plan.klen.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
         }
         if (filtered) {
-            blk.chk(hipMemcpyAsync(f->d_len, kept_len.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            blk.chk(hipMemcpyAsync(f->d_cnt, kept_cnt.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            blk.chk(hipMemcpyAsync(d_spos, srcpos.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-            blk.chk(hipMemcpyAsync(d_live, live0.data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(f->d_len, plan.kept_len.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(f->d_cnt, plan.kept_cnt.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_spos, plan.srcpos.data(), (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+            blk.chk(hipMemcpyAsync(d_live, plan.live0.data(), ((size_t)T + 1) * 4, hipMemcpyHostToDevice, st));
         }
-        blk.chk(hipMemcpyAsync(d_tb, term_base.data(), term_base.size() * 4, hipMemcpyHostToDevice, st));
-        blk.chk(hipMemcpyAsync(d_pb, pair_base.data(), pair_base.size() * 4, hipMemcpyHostToDevice, st));
-        blk.chk(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, st));
-        blk.chk(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_tb, plan.term_base.data(), plan.term_base.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_pb, plan.pair_base.data(), plan.pair_base.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_prefix, plan.prefix.data(), plan.prefix.size() * 4, hipMemcpyHostToDevice, st));
+        blk.chk(hipMemcpyAsync(d_lists, plan.lists.data(), plan.lists.size() * 4, hipMemcpyHostToDevice, st));
         blk.record(0);
         h_cnt[C_DUP] = h_cnt[C_BAD] = 0xFFFFFFFFu;
         blk.chk(hipMemcpyAsync(d_cntv, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
@@ -2494,26 +2419,19 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
         }
         const uint64_t capd = ig_table_slots(Td);                      // == cap unless terms were dropped
         const uint32_t gT = (Td + 255) / 256;
+        const DictStage dict{d_text, d_kstart, d_klen, d_ksrc, d_khash, Td, d_table, capd, d_kslot, d_krep, d_fid, d_tsrc, d_sums};
         if (blk.ok() && Td) {
             blk.chk(hipMemsetAsync(d_table, 0xFF, (size_t)capd * 4, st));
             blk.chk(hipMemsetAsync(d_dtab, 0xFF, (size_t)capd * 8, st));
             hipLaunchKernelGGL(k_cp_hash, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, Td, d_tbl, n_src, hash_mask, d_ksrc, d_khash, d_long, d_cntv + C_LONG);
             hipLaunchKernelGGL(k_ig_hash_long, dim3(1024), dim3(256), 0, st, d_text, d_kstart, d_klen, d_long, d_cntv + C_LONG, hash_mask, d_khash);
-            hipLaunchKernelGGL(k_ig_insert, dim3(gT), dim3(256), 0, st, d_text, d_kstart, d_klen, d_khash, Td, d_table, (uint32_t)(capd - 1), d_kslot);
-            hipLaunchKernelGGL(k_ig_first, dim3(gT), dim3(256), 0, st, d_table, d_kslot, Td, d_krep, d_fid);
-            ig_scan(st, d_fid, Td, d_sums, d_cntv + C_TERMS);
-            read_counts(blk, h_cnt);
+            dict_count_terms(blk, dict, d_cntv + C_TERMS, h_cnt);
             n_terms = h_cnt[C_TERMS];
         }
         f->info.n_terms = n_terms;
-        if (blk.ok()) blk.chk(hipMalloc((void**)&f->d_toff, ((size_t)n_terms + 1) * 4));
+        dict_term_ids(blk, dict, f, n_terms, d_newid, d_tvals, d_cntv + C_TBYTES);
         if (blk.ok()) {
-            blk.chk(hipMemsetAsync(f->d_toff, 0, ((size_t)n_terms + 1) * 4, st));
-            if (Td) {
-                hipLaunchKernelGGL(k_ig_termid, dim3(gT), dim3(256), 0, st, d_krep, d_fid, d_ksrc, d_kstart, d_klen, Td, d_newid, d_tvals, f->d_toff, d_tsrc);
-                ig_scan(st, f->d_toff, n_terms + 1, d_sums, d_cntv + C_TBYTES);
-                hipLaunchKernelGGL(k_cp_dup, dim3(gT), dim3(256), 0, st, d_newid, d_ksrc, Td, d_dtab, (uint32_t)(capd - 1), d_cntv + C_DUP);
-            }
+            if (Td) hipLaunchKernelGGL(k_cp_dup, dim3(gT), dim3(256), 0, st, d_newid, d_ksrc, Td, d_dtab, (uint32_t)(capd - 1), d_cntv + C_DUP);
             // d_omap: the map over the sources' own term ids (filtered: through the ranks; otherwise d_newid itself)
             if (filtered && T) hipLaunchKernelGGL(k_cp_keep_map, dim3((T + 255) / 256), dim3(256), 0, st, d_live, d_rank, T, d_newid, d_omap);
             if (n_pairs) hipLaunchKernelGGL(k_cp_remap, dim3((n_pairs + 255) / 256), dim3(256), 0, st, f->d_pairs, n_pairs, d_pb, d_tb, n_src, d_omap, d_cntv + C_BAD);
@@ -2556,16 +2474,9 @@ static int forward_merge_run(ns_ctx* ctx, const char* fn, const ns_forward_src* 
         float ms = 0.0f;
         if (blk.elapsed_ms(0, 1, &ms)) f->info.device_ms = ms;
     }
-    const int rc = blk.finish(fn);
-    f->info.device_bytes = (uint64_t)blk.held_bytes() + ((uint64_t)n_terms + 1) * 4 + (uint64_t)n_docs * 12 + (uint64_t)n_pairs * 8 + tbytes;
-    if (rc != NS_OK || refused_src >= 0) {
-        forward_free_device(f);
-        delete f;
-        (void)hipGetLastError();
-        if (refused_src >= 0) return fail(ctx, NS_E_INVAL, "%s: source %d: %s", fn, refused_src, refused_why);   // (the refusal is what the caller hears of)
-        return rc;
-    }
-    return publish();
+    int rc = blk.finish(fn);
+    if (refused_src >= 0) rc = fail(ctx, NS_E_INVAL, "%s: source %d: %s", fn, refused_src, refused_why);   // (the refusal is what the caller hears of)
+    return forward_finish(ctx, f, out, blk.held_bytes(), rc);
 }
 
 extern "C" int ns_forward_merge(ns_ctx* ctx, const ns_forward_src* src, uint32_t n_src, ns_forward** out) {

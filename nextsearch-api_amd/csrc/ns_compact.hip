@@ -25,14 +25,11 @@
 
 #include <cstdint>
 
+#include "ns_index_consts.hpp"   // kCpWaveMax, kCpDocCut
 #include "ns_ingest_text.hpp"
 
 namespace ns {
 
-constexpr uint32_t kCpWaveMax = 64;       // pairs of a document sorted by one wave
-// pairs of a document sorted in LDS by one workgroup: 32 KiB of 64-bit keys, so that four workgroups stay resident on a
-// CU's 160 KiB (ns_compact_doc_cut() hands it to the tests)
-constexpr uint32_t kCpDocCut = 4096;
 constexpr uint64_t kCpPad = ~0ull;        // sorts behind every pair (termId 0xFFFFFFFF is refused: it is >= n_terms)
 
 // the last s with base[s] <= i (base has n_src + 1 entries; empty sources share their base with the next one)

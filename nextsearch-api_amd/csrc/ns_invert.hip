@@ -23,10 +23,9 @@
 
 #include <cstdint>
 
-namespace ns {
+#include "ns_index_consts.hpp"   // kIvItems, kIvTile
 
-constexpr int kIvItems = 16;                 // pairs per thread per tile
-constexpr int kIvTile = 256 * kIvItems;      // pairs per workgroup
+namespace ns {
 
 // df from the SORTED keys (a histogram by atomics serialises on the frequent terms: the most frequent one
 // occurs in almost every document): a run's first pair records where it starts, its last pair where it ends;

@@ -17,7 +17,7 @@ LANES.  Shapes are built from T.
 Left out: the three-pass plans wider than [9, 8, 8] through ns_invert_forward.  They start at n_terms = 2^25 + 1, where each
 array of df's size is 128 MiB and more per copy.  The instantiations k_iv_pass<9 | 10 | 11, false, false> cannot occur in an
 inversion at all below that.  ig_sort, the sort of ns_forward_build and of compaction, launches k_iv_pass<B, false, false> for
-every pass, a single one included (csrc/ns_api.hip, NS_IG_PASS: its input is keys and values already), so the
+every pass, a single one included (csrc/ns_api.hip, ig_sort: its input is keys and values already), so the
 corpora at the end of this module reach them through one-pass sorts: 9 and 11 bits here, 10 in the suite's older corpora.  The
 three-pass corpus sorts [8, 8, 8]."""
 import collections

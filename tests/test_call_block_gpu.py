@@ -1,5 +1,6 @@
 """The pooled one-shot calls that sit on CallBlock (csrc/ns_api.hip): ns_forward_build, ns_forward_merge(_keep),
-ns_invert_forward / ns_forward_invert, ns_docterms_select, ns_sem_topk, ns_ac_suggest, ns_ac_fuzzy and ns_ac_fuzzy_prefix.
+ns_invert_forward / ns_forward_invert, ns_segment_filter, ns_docterms_select, ns_sem_topk, ns_ac_suggest, ns_ac_fuzzy and
+ns_ac_fuzzy_prefix.
 Every call here runs at a small shape through the raw C ABI; what is compared is every output byte (the times are not
 output).  The reference is each call on a ctx of its own, whose pool is empty: a block that a call gets from the pool of a
 shared ctx was another call's, often another family's, and nothing of it may show.  The refusals are host-side argument
@@ -11,14 +12,20 @@ import numpy as np
 import pytest
 
 import correct_ref
+import filter_ref
 import fuzzy_shapes
 import ingest_ref
 import nsbind
+import rawseg
 from test_ingest_gpu import gen_corpus
 
 pytestmark = pytest.mark.gpu
 NS_E_INVAL = -1
 KB64 = 64 << 10
+FL_CHUNK = 64                                # kFlChunk of csrc/ns_filter.hip: postings per chunk of ns_segment_filter
+FL_SIZES = [FL_CHUNK - 1, FL_CHUNK, FL_CHUNK + 1, 300]
+FL_DOCS = 203                                # no multiple of 32: the bitmap's last word is partly used
+FL_NEW_ID = 9
 
 
 def _new_ctx():
@@ -71,6 +78,18 @@ def inputs():
     I["ac_prefixes"] = [b"", b"a", b"a0", b"b", b"b0000", b"zz", b"A", b"a" * 64] + [prng.choice(terms)[:prng.randint(1, 4)] for _ in range(20)]
     I["fz_queries"] = [correct_ref.random_edits(prng, prng.choice(terms), prng.randint(0, 3), b"ab019-") for _ in range(40)] + [b"", b"a00001", b"zzzz"]
     I["fz_edits"] = np.array([prng.randrange(3) for _ in I["fz_queries"]], dtype=np.uint8)
+    # ---- ns_segment_filter: sources of n postings in three lists (the middle one shares its chunks with both neighbours), n on
+    # both sides of one chunk and a few hundred; every third document dropped, the bits behind the last document set ----
+    I["fl_doc_len"] = rng.integers(1, 90, FL_DOCS).astype(np.uint32)
+    I["fl_lists"] = {}
+    for n in FL_SIZES:
+        cuts = [n // 3, n // 3, n - 2 * (n // 3)]
+        I["fl_lists"][n] = [(np.sort(rng.choice(FL_DOCS, m, replace=False)).astype(np.uint32), rng.integers(1, 9, m).astype(np.uint32)) for m in cuts]
+    keep = np.ones(FL_DOCS, dtype=bool)
+    keep[2::3] = False
+    I["fl_bits"] = filter_ref.bits_of(keep, fill_tail=True)
+    I["fl_want"] = {n: filter_ref.compact(rawseg.payload_of(ls)[0].reshape(-1, 2), rawseg.payload_of(ls)[1], [len(d) for d, _ in ls], keep)
+                    for n, ls in I["fl_lists"].items()}
     return I
 
 
@@ -85,8 +104,11 @@ class Session:
     def __init__(self):
         self.L, self.ctx, self.I = nsbind.hip_lib(), _new_ctx(), inputs()
         self.dt = self.sem = self.ac = None
+        self.fl = {}
 
     def close(self):
+        for h, _, _ in self.fl.values():
+            assert self.L.ns_segment_release(self.ctx, h) == 0
         if self.dt:
             self.dt.close()
         if self.sem:
@@ -128,6 +150,28 @@ class Session:
                                       n_terms, df.ctypes.data, post.ctypes.data, C.byref(kept), C.byref(ms) if timed else None)
         assert rc != 0 or not timed or ms.value > 0.0
         return rc, [df.tobytes(), post[:kept.value].tobytes(), bytes(C.c_uint64(kept.value))]
+
+    def filter(self, n, timed, new_id=FL_NEW_ID):
+        """the filtered copy of the source of n postings under new_id, released again: the lists' new places, the payload read
+        back from the new segment, the number kept"""
+        if n not in self.fl:
+            flat, offs = rawseg.payload_of(self.I["fl_lists"][n])
+            h, dl = C.c_void_p(), self.I["fl_doc_len"]
+            assert self.L.ns_segment_upload(self.ctx, FL_SIZES.index(n), FL_DOCS, C.c_float(rawseg.avgdl_of(dl)), dl.ctypes.data, flat.ctypes.data, flat.nbytes, C.byref(h)) == 0, self.err()
+            self.fl[n] = (h, offs, np.array([len(d) for d, _ in self.I["fl_lists"][n]], dtype=np.uint32))
+        src, offs, counts = self.fl[n]
+        noff, ncnt, payload = np.full(3, 0xABABABAB, dtype=np.uint64), np.full(3, 0xABABABAB, dtype=np.uint32), np.full((n, 2), 0xABABABAB, dtype=np.uint32)
+        kept, ms, h = C.c_uint64(), C.c_float(-1.0), C.c_void_p()
+        rc = self.L.ns_segment_filter(self.ctx, src, new_id, self.I["fl_bits"].ctypes.data, offs.ctypes.data, counts.ctypes.data, 3, noff.ctypes.data, ncnt.ctypes.data,
+                                      payload.ctypes.data, C.byref(kept), C.byref(ms) if timed else None, C.byref(h))
+        if rc != 0:
+            assert not h.value
+            return rc, []
+        assert not timed or ms.value > 0.0
+        assert self.L.ns_segment_release(self.ctx, h) == 0
+        w_payload, w_off, w_cnt, w_kept = self.I["fl_want"][n]
+        assert kept.value == w_kept and 0 < w_kept < n and np.array_equal(noff, w_off) and np.array_equal(ncnt, w_cnt) and np.array_equal(payload[:w_kept], w_payload)
+        return rc, [noff.tobytes(), ncnt.tobytes(), payload[:kept.value].tobytes(), bytes(C.c_uint64(kept.value))]
 
     def select(self, timed, ids=None):
         if not self.dt:
@@ -203,6 +247,11 @@ CALLS = {
     "merge_keep": ("merge", lambda s: s.merge_keep()),
     "invert": ("invert", lambda s: _ok(s.invert(True))),
     "invert_untimed": ("invert", lambda s: _ok(s.invert(False))),
+    "filter_below_a_chunk": ("filter_chunk", lambda s: _ok(s.filter(FL_CHUNK - 1, True))),
+    "filter_a_chunk": ("filter_chunk", lambda s: _ok(s.filter(FL_CHUNK, True))),
+    "filter_above_a_chunk": ("filter_chunk", lambda s: _ok(s.filter(FL_CHUNK + 1, False))),
+    "filter": ("filter", lambda s: _ok(s.filter(300, True))),
+    "filter_untimed": ("filter", lambda s: _ok(s.filter(300, False))),
     "select": ("select", lambda s: _ok(s.select(True))),
     "select_untimed": ("select", lambda s: _ok(s.select(False))),
     "sem": ("sem", lambda s: _ok(s.sem_topk(True))),
@@ -272,6 +321,8 @@ def test_a_refused_call_between_two_runs_changes_no_byte_of_the_second():
                 rc = L.ns_forward_merge(s.ctx, arr, 2, C.byref(h)) if bits is None else L.ns_forward_merge_keep(s.ctx, arr, bits[0], 2, C.byref(h))
                 _refused(s, fn_name, rc)
                 assert "source 1" in s.err() and why in s.err() and not h.value, s.err()
+        # ns_segment_filter: a new_seg_id already in use (the source's own), after the call's host-side checks only
+        assert s.filter(300, True, new_id=FL_SIZES.index(300))[0] == NS_E_INVAL and s.err() == "segment %d already uploaded" % FL_SIZES.index(300), s.err()
         # ns_ac_suggest and ns_ac_fuzzy_prefix: offsets that decrease; ns_ac_fuzzy: more edits than the corrector allows
         down = [5, 3] + [3] * (n_q - 1)
         _refused(s, "ns_ac_suggest", s.suggest(True, offs=down)[0])
@@ -307,6 +358,7 @@ def test_pooled_blocks_carry_nothing_from_call_to_call():
     n_q, n_f = len(I["ac_prefixes"]), len(I["fz_queries"])
     assert len(I["dt_ids"]) * (2 * 4 + 2 * 25 * 4 + 4) + 5 * 256 <= KB64                       # ns_docterms_select: ids, list, term, w, count
     assert (n_q + 1) * 4 + sum(map(len, I["ac_prefixes"])) + n_q * 11 * 4 + 512 <= KB64        # ns_ac_suggest: the image and the answers
+    assert 7 * 4 + (300 // FL_CHUNK + 2) * (8 + 4) + 2 * 4 + 3 * (4 + 4 + 4 + 8) + 9 * 256 <= KB64   # ns_segment_filter: the bitmap, a mask and a base per chunk, the lists
     assert 16 * 24 * 4 + 8 * 5 * 5 * 8 + 2 * 9 * 4 + 8 * 4 + 22 * 4 + 16 * (2 * 5 + 1) * 4 + 8 * 256 <= KB64   # ns_sem_topk: its eight regions, two groups of 8
     # ... and ns_forward_build's second and third block differ: B holds three words per token (12 B x n_tokens + its scan
     # sums: at most 64 KiB up to 5000 tokens), C more than 60 B per kept token (past 64 KiB from 1100 kept tokens on)
