@@ -812,6 +812,34 @@ int ns_search_sorted_quorum(ns_ctx* ctx, const ns_query_desc* queries, uint32_t 
  * them), summed over the calling thread's calls since the last reset: out6[0..5] as ns_grouped_kernel_ms. */
 int ns_quorum_kernel_ms(float* out6, int reset);
 
+/* ---- per-document boost factors in ranked boolean search ------------------------ */
+/* A table of one fp32 factor per document, on the device, independent of any ns_seg and indexed by docId (so it serves a filter's
+ * copy of the segment unchanged), as ns_dockeys is.  A factor that is not finite or has its sign bit set (-0.0f included) is
+ * refused with NS_E_INVAL by a check on the device, and nothing stays allocated; 0.0f is legal. */
+typedef struct ns_docboost ns_docboost;
+int ns_docboost_upload(ns_ctx* ctx, uint32_t n_docs, const float* boost, ns_docboost** out);
+int ns_docboost_release(ns_ctx* ctx, ns_docboost* table);
+/* ns_search_quorum_after, parameter for parameter, with one table per listed segment behind `segs`.
+ *   MATCHED SET, found, rest, ORDER, HITS, cursors, refusals: the sibling's.
+ *   SCORE        fp32(score * boosts[i][docId]): ONE rounded multiply of the sibling's finished sum.  The product's bits are the
+ *                rank (a negative score times 0.0f is -0.0f, which ranks just below +0.0f); a hit's score and a cursor's rank
+ *                are those bits.
+ *   boosts == NULL: the call IS the sibling (the same plan, the same kernels, the same bytes out).  Tables that are all 1.0f give
+ *                the sibling's answers byte for byte, through the boosted kernels.
+ *   A NULL entry, a table of another ctx or a table shorter than its segment's n_docs: NS_E_INVAL.
+ * roles / clauses / needs == NULL mean what they mean in the sibling, so plain OR and AND search (every ref SHOULD, every ref
+ * MUST) get factors through this call too. */
+int ns_search_boosted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                            const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the boolean call */,
+                            const uint8_t* needs /* n_terms; NULL = the grouped call */, uint32_t n_terms, uint32_t k,
+                            const ns_cursor* after /* n_queries; NULL = none (page 1) */, const uint32_t* seg_ids, ns_seg* const* segs,
+                            ns_docboost* const* boosts /* n_segs; NULL = the sibling */, uint32_t n_segs, ns_hit* hits_out /* Q x K */,
+                            uint32_t* nhits_out, uint64_t* found_out /* may be NULL */, uint64_t* rest_out /* may be NULL */,
+                            float* device_ms_out /* may be NULL */);
+/* HIP-event time of the launches of ns_search_boosted_after calls that were given tables (with boosts == NULL the sibling's sums
+ * count them), summed over the calling thread's calls since the last reset: out2[0..1] = k_bq_select, k_bq_join, milliseconds. */
+int ns_boosted_kernel_ms(float* out2, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

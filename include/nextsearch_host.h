@@ -540,6 +540,51 @@ int nsh_engine_search_quorum_faceted_json(nsh_engine* e, const char* query, int 
 int nsh_engine_search_quorum_sorted_json(nsh_engine* e, const char* query, int k, const nsh_sort_spec* spec, int use_filter, const char* date_from,
                                          const char* date_to, int keep_undated, char** json_out);
 
+/* ---- boosts: per-document factors, recency decay and term^w (host/boost.hpp) ----
+ * A boost is one fp32 factor per document; the device multiplies a matched document's finished score by it, once, and ranks by
+ * the product.  kind 0 custom: `custom` holds the segments' factor arrays back to back in manifest order, n_custom = the documents
+ * of the index; a factor that is negative (-0.0f included) or not finite is refused.  kind 1 exponential: f = 2^(-age /
+ * scale_days); kind 2 linear: f = max(0, 1 - age / scale_days); age = max(0, |days(origin) - days(date)| - offset_days) in civil
+ * days of the document's publish_time (a missing month or day reads as 1); origin: a date as the filter bounds are, NULL or "" =
+ * the newest dated document; an undated document takes f = undated.  The factor of kinds 1 and 2 is (1 - weight) + weight * f,
+ * computed in double and rounded once to fp32; weight = 0 gives 1.0f everywhere and so the unboosted answers, bit for bit.
+ * Refused with a message: weight outside [0, 1], scale_days <= 0, offset_days or undated below 0, an origin that is not a date. */
+typedef struct nsh_boost_spec {
+    uint32_t kind;
+    double weight;
+    const char* origin;
+    double scale_days, offset_days, undated;
+    const float* custom;
+    uint64_t n_custom;
+} nsh_boost_spec;
+/* Engine::boost_table (host only: works with device < 0): the factors of every document, the segments back to back in manifest
+ * order, into out[0 .. cap); returns their number (call with cap = 0 to size the array), or -1 with a message. */
+int64_t nsh_engine_boost_table(nsh_engine* e, const nsh_boost_spec* spec, float* out, uint64_t cap);
+/* The device copies of a spec's tables are built by the first call that needs them and kept until another spec, a reload() or
+ * this call drops them. */
+void nsh_engine_release_boosts(nsh_engine* e);
+uint64_t nsh_engine_boost_tables_on_device(nsh_engine* e);
+/* nsx::parse_boosted: nsh_parse_quorum's dialect plus the suffix `^w` on a word or `+word` (`vaccine^2.5`) and on a group behind
+ * its ')' and optional `~m` (`+(covid sars)^0.5`, `(a b c)~2^3`).  w is digits with at most one '.', in (0, 1e6]; anything else
+ * leaves the '^' to the tokenizer; on a `-` piece the suffix is consumed and ignored.  weights[i] (may be NULL) = the weight of
+ * term i, 1.0f without a suffix; everything else as nsh_parse_quorum, whose answer this is for a text without a valid `^w`. */
+uint32_t nsh_parse_boosted(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                           float* weights, uint32_t terms_cap, uint32_t* min_should_out);
+/* Engine::search_boosted_after_batch_flat: nsh_engine_search_quorum_after_batch over that dialect, parameter for parameter, behind
+ * spec (NULL: term weights only).  A hit's score, and so a cursor's rank, is the bits of fp32(score * factor). */
+int nsh_engine_search_boosted_after_batch(nsh_engine* e, const nsh_boost_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                          int k, const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                          uint8_t* has_found, float* device_ms_out);
+/* Engine::search_boosted: *json_out (free with nsh_free) = the body of nsh_engine_search_quorum_json over this dialect with
+ * "boosted" in place of "quorum" (the same members; a "must" clause also carries "weight", a "should" entry is {"term", "weight"})
+ * and, with a spec, "boost": {"kind", "offset_days", "origin", "scale_days", "undated", "weight"}; keys stay sorted: both stand in
+ * front of "filter".  On failure -1 and {"error": ...}.  nsh_engine_search_boosted_page_json pages it (cursors of kind 's');
+ * nsh_engine_search_page_json's mode 9 is that call without a spec. */
+int nsh_engine_search_boosted_json(nsh_engine* e, const char* query, int k, const nsh_boost_spec* spec, int use_filter, const char* date_from,
+                                   const char* date_to, int keep_undated, char** json_out);
+int nsh_engine_search_boosted_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, int use_filter,
+                                        const char* date_from, const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

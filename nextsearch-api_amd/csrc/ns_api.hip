@@ -3137,9 +3137,10 @@ extern "C" int ns_boolean_kernel_ms(float* out2, int reset) {
     return NS_OK;
 }
 
+struct ns_docboost;
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                      const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
-                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out);
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out, ns_docboost* const* boosts = nullptr);
 
 extern "C" int ns_search_boolean(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                                  uint32_t n_terms, uint32_t k, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
@@ -3194,9 +3195,64 @@ extern "C" int ns_search_quorum_after(ns_ctx* ctx, const ns_query_desc* queries,
                      found_out, rest_out, device_ms_out);
 }
 
+// Per-document boost factors (csrc/ns_boolean.hip k_bq_select<true, ., ., true>)
+struct ns_docboost {
+    ns_ctx* ctx = nullptr;
+    uint32_t n_docs = 0;
+    float* d_boost = nullptr;
+};
+static thread_local float g_bb_ms[2] = {0.0f, 0.0f};   // k_bq_select, k_bq_join: summed over the thread's ns_search_boosted_after calls with tables (ns_boosted_kernel_ms)
+
+extern "C" int ns_docboost_upload(ns_ctx* ctx, uint32_t n_docs, const float* boost, ns_docboost** out) {
+    const char* fn = "ns_docboost_upload";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (!out) return fail(ctx, NS_E_INVAL, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (n_docs && !boost) return fail(ctx, NS_E_INVAL, "%s: boost is NULL", fn);
+    ns_docboost* t = new ns_docboost();
+    t->ctx = ctx; t->n_docs = n_docs;
+    bool refused = false;
+    const hipError_t e = upload_checked(ctx, boost, n_docs, &t->d_boost, &refused, [&](const float* d_table, uint32_t* d_bad, dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(k_bq_boost_check, grid, dim3(256), 0, st, d_table, n_docs, d_bad);
+    });
+    if (e != hipSuccess || refused) {
+        delete t;
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? NS_E_NOMEM : NS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return fail(ctx, NS_E_INVAL, "%s: a document has a factor that is not finite or has its sign bit set", fn);
+    }
+    *out = t;
+    return NS_OK;
+}
+
+extern "C" int ns_docboost_release(ns_ctx* ctx, ns_docboost* table) {
+    if (!ctx || !table || table->ctx != ctx) return fail(ctx, NS_E_INVAL, "ns_docboost_release: table does not belong to this ctx");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(table->d_boost);
+    delete table;
+    return NS_OK;
+}
+
+extern "C" int ns_boosted_kernel_ms(float* out2, int reset) {
+    if (!out2) return NS_E_INVAL;
+    for (int i = 0; i < 2; i++) out2[i] = g_bb_ms[i];
+    if (reset) g_bb_ms[0] = g_bb_ms[1] = 0.0f;
+    return NS_OK;
+}
+
+// boosts == NULL is the quorum sibling, plan and kernels; otherwise the sibling's plan, every item given a bound (kAfterAll
+// without a cursor), and the BOOST instantiations of k_bq_select.  The join is the sibling's: it carries key bits.
+extern "C" int ns_search_boosted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                       const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after,
+                                       const uint32_t* seg_ids, ns_seg* const* segs, ns_docboost* const* boosts, uint32_t n_segs, ns_hit* hits_out,
+                                       uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+    return bq_search(ctx, "ns_search_boosted_after", queries, n_queries, terms, roles, clauses, needs, n_terms, k, after, seg_ids, segs, n_segs, hits_out, nhits_out,
+                     found_out, rest_out, device_ms_out, boosts);
+}
+
 static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
                      const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const ns_cursor* after, const uint32_t* seg_ids, ns_seg* const* segs, uint32_t n_segs, ns_hit* hits_out,
-                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out) {
+                     uint32_t* nhits_out, uint64_t* found_out, uint64_t* rest_out, float* device_ms_out, ns_docboost* const* boosts) {
     if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
     if (device_ms_out) *device_ms_out = 0.0f;
     if (n_queries == 0) return NS_OK;
@@ -3204,9 +3260,17 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
     if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
     std::vector<FcSegView> views;
     std::vector<DevFcSeg> dsegs;
-    std::vector<DevBqSeg> bqs(n_segs);
+    std::vector<DevBqSeg> bqs(boosts ? 2 * (size_t)n_segs : (size_t)n_segs);   // with tables: n_segs DevBqBoost behind
     const int rc = bind_segments<void>(ctx, fn, seg_ids, segs, nullptr, nullptr, n_segs, views, dsegs, [&](uint32_t i, const ns_seg* s, const void*) {
-        bqs[i] = DevBqSeg{s->d_norm, seg_ids[i], 0u};
+        bqs[i] = DevBqSeg{s->d_norm, seg_ids[i], boosts ? n_segs : 0u};
+        if (boosts) {
+            const ns_docboost* t = boosts[i];
+            if (!t) return fail(ctx, NS_E_INVAL, "%s: segment or boost table %u is NULL", fn, i);
+            if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: boost table %u does not belong to this ctx", fn, i);
+            if (t->n_docs < s->n_docs) return fail(ctx, NS_E_INVAL, "%s: boost table %u has %u factors, its segment has %u documents", fn, i, t->n_docs, s->n_docs);
+            const DevBqBoost b{t->d_boost, 0ull};
+            std::memcpy(&bqs[(size_t)n_segs + i], &b, sizeof(b));
+        }
         return (int)NS_OK;
     });
     if (rc != NS_OK) return rc;
@@ -3224,13 +3288,16 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
     if (!ranked_call_plan(items, n_queries, k, after, views, [](uint32_t bits) { return after_ord(bits); }, false, kSdCandBytes, plan, why))
         return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (boosts) ranked_plan_bound_all(items.size(), plan);   // (the BOOST kernels exist with AFTER alone)
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    static const SelectKernel<BqRef, DevBqSeg> kBoosted[3] = {k_bq_select<true, false, false, true>, k_bq_select<true, true, false, true>,
+                                                              k_bq_select<true, true, true, true>};   // [boolean, grouped, quorum]
     static const SelectKernel<BqRef, DevBqSeg> kSelect[3][2] = {{k_bq_select<false, false>, k_bq_select<true, false>},
                                                                 {k_bq_select<false, true>, k_bq_select<true, true>},
                                                                 {k_bq_select<false, true, true>, k_bq_select<true, true, true>}};   // [boolean, grouped, quorum][paged]
     const uint32_t K = plan.K;
     RankedCall<BqRef, DevBqSeg> c{items, refs, dsegs, bqs, plan, n_queries};
-    c.select = kSelect[quorum ? 2 : grouped][plan.paged];
+    c.select = boosts ? kBoosted[quorum ? 2 : grouped] : kSelect[quorum ? 2 : grouped][plan.paged];
     c.select_arg = win;
     c.select_lds = quorum ? bq_quorum_lds_bytes(win, bq_launch_planes(max_need)) : bq_lds_bytes(win);   // (the product's: at most 42 KiB)
 #if defined(NS_VARIANTS) || defined(NS_COUNT)
@@ -3238,7 +3305,7 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
         c.before = hipFuncSetAttribute(reinterpret_cast<const void*>(c.select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.select_lds);
 #endif
     c.stages = 2;
-    c.ms_acc = quorum ? g_qq_ms : grouped ? g_gq_ms : g_bq_ms;
+    c.ms_acc = boosts ? g_bb_ms : quorum ? g_qq_ms : grouped ? g_gq_ms : g_bq_ms;
     c.hits_out = hits_out; c.nhits_out = nhits_out; c.found_out = found_out; c.rest_out = rest_out; c.device_ms_out = device_ms_out;
     return run_ranked(ctx, fn, c, [=](const RankedDev<BqRef, DevBqSeg>& d, const SdBatch& b, hipStream_t st) {
         hipLaunchKernelGGL(k_bq_join, dim3((b.q_end - b.q_begin + 3) / 4), dim3(256), 0, st, d.items, d.q_off, b.q_begin, b.q_end, b.item_begin, d.aux, d.cand, K, d.hits, d.nhits);
@@ -3977,6 +4044,8 @@ extern "C" int ns_debug_boolean_counters(unsigned long long* out, int reset) { r
 extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBgcnt>(HIP_SYMBOL(ns::g_ns_bgcnt), out, reset); }
 // the quorum required stage (ns_boolean.hip k_bq_select<., ., true>; ns_boolean_sets.hip bs_matched<., true>): 12 values
 extern "C" int ns_debug_boolean_quorum_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBqcnt>(HIP_SYMBOL(ns::g_ns_bqcnt), out, reset); }
+// per-document factors (ns_boolean.hip k_bq_select<true, ., ., true>): 8 values
+extern "C" int ns_debug_boolean_boost_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBbcnt>(HIP_SYMBOL(ns::g_ns_bbcnt), out, reset); }
 // facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values
 extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBscnt>(HIP_SYMBOL(ns::g_ns_bscnt), out, reset); }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values

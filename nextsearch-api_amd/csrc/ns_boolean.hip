@@ -40,8 +40,15 @@ namespace ns {
 struct DevBqSeg {
     const float* norm;   // per document (ns_seg::d_norm)
     uint32_t seg_id;     // the id the refs use for this segment
-    uint32_t pad;
+    uint32_t boost_at;   // BOOST launches (§5z): entry boost_at of this array, read as a DevBqBoost, is segment 0's; else 0
 };
+// Per-document factors (§5z, ns_docboost): a sibling of DevBqSeg of the same size, so that the array of a BOOST launch carries
+// n_segs DevBqSeg and then n_segs DevBqBoost, and DevBqSeg keeps its 16 bytes for every other launch.
+struct DevBqBoost {
+    const float* boost;  // per document: at least the segment's n_docs finite factors without a sign bit
+    uint64_t pad;
+};
+static_assert(sizeof(DevBqBoost) == sizeof(DevBqSeg), "the two share one array");
 
 #ifdef NS_COUNT
 // Counting build only: events of the two kernels since the last reset (ns_debug_boolean_counters).  0 items, 1 windows,
@@ -65,11 +72,19 @@ __device__ unsigned long long g_ns_bgcnt[kNsBgcnt];
 constexpr int kNsBqcnt = 12;
 __device__ unsigned long long g_ns_bqcnt[kNsBqcnt];
 #define NS_BQCNT(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_ns_bqcnt[(i)], (unsigned long long)(v)); } while (0)
+// Per-document factors (§5z; ns_debug_boolean_boost_counters), the BOOST instantiations of k_bq_select only: 0 work items, 1 items
+// swept (at least one window reached the sweep), 2 documents whose score was multiplied, 3 boosted keys a cursor clipped, 4 swept
+// windows in which every matched document's factor is 0.0f, 5..7 the work items of <true, false, false, true>, <true, true, false,
+// true> and <true, true, true, true>.
+constexpr int kNsBbcnt = 8;
+__device__ unsigned long long g_ns_bbcnt[kNsBbcnt];
+#define NS_BBCNT(i, v) do { if (BOOST && threadIdx.x == 0) atomicAdd(&g_ns_bbcnt[(i)], (unsigned long long)(v)); } while (0)
 #else
 #define NS_BCNT(i, v)
 #define NS_BCNT_WAVE(i, v)
 #define NS_BGCNT(i, v)
 #define NS_BQCNT(i, v)
+#define NS_BBCNT(i, v)
 #endif
 
 __device__ __forceinline__ uint32_t bq_ord(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
@@ -289,7 +304,13 @@ __host__ __device__ inline size_t bq_quorum_lds_bytes(uint32_t win, uint32_t pla
 // the code is what it was without the parameter.
 // QUORUM (§5w; implies GROUPED): BqRef::clause is bq_plan_quorum's word, and the required stage of a window is bq_count_clauses
 // over the counter planes behind bq_lds_bytes(win).  With QUORUM = false the code is what it was without the parameter.
-template <bool AFTER, bool GROUPED = false, bool QUORUM = false>
+// BOOST (§5z; instantiated with AFTER alone, a call without a cursor passes kAfterAll for every item): in the sweep the lane that
+// owns a set bit gathers its document's factor from the segment's DevBqBoost (one dependent 4-byte global load per matched
+// document, as k_sd_select gathers its key) and the key carries ord(fp32(score * factor)).  The score is the FINISHED sum: the
+// score stage stored it to LDS and a barrier lies in between, so the multiply is one rounding of its own and cannot be contracted
+// into the last accumulation (it is written __fmul_rn all the same).  A negative score times 0.0f is -0.0f, which ord puts just
+// below +0.0f.  With BOOST = false the code is what it was without the parameter.
+template <bool AFTER, bool GROUPED = false, bool QUORUM = false, bool BOOST = false>
 __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
                                                    uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -306,9 +327,12 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     const FcItem it = items[blockIdx.x];
     const DevFcSeg sg = segs[it.seg];
     const float* __restrict__ norm = bqs[it.seg].norm;
+    const float* __restrict__ boost = BOOST ? reinterpret_cast<const DevBqBoost*>(bqs)[bqs[it.seg].boost_at + it.seg].boost : nullptr;
     const BqRef* __restrict__ rf = refs + it.ref_begin;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, v = tid >> 6;
     NS_BCNT(0, 1);
+    NS_BBCNT(0, 1);
+    NS_BBCNT(QUORUM ? 7 : GROUPED ? 6 : 5, 1);
     if (tid == 0) s_cnt = 0u;
     uint64_t last = kAfterAll;
     uint32_t kept = 0;
@@ -330,6 +354,9 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     if (QUORUM) NS_BQCNT(0, 1);
     SdSet set{0ull, 0ull};
     uint32_t cnt = 0;
+#ifdef NS_COUNT
+    bool swept = false;   // BOOST: a window of the item reached the sweep (workgroup-uniform)
+#endif
     const uint32_t tile_n = it.doc_hi - it.doc_lo;   // <= kFcTileDocs: the tile is the host's
     for (uint32_t tile_rel = 0; tile_rel < tile_n; tile_rel += win) {   // (tile_rel + win <= 2^17 + 2^15: no wrap)
         const uint32_t w_lo = it.doc_lo + tile_rel;
@@ -423,6 +450,10 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
             }
             __syncthreads();
         }
+#ifdef NS_COUNT
+        uint32_t multiplied = 0, clipped = 0;
+        bool nonzero = false;   // BOOST: a factor of this thread's documents is not 0.0f
+#endif
         for (uint32_t wb = v * 64u; wb < n_words; wb += 256u) {   // (wave-uniform)
             const uint32_t w = wb + lane;
             uint32_t bits = w < n_words ? s_bm[w] : 0u;
@@ -432,13 +463,36 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
                 if (bits) {
                     const uint32_t rel = w * 32u + (uint32_t)__builtin_ctz(bits);   // < n: only such bits are set
                     bits &= bits - 1u;
-                    key = ((uint64_t)bq_ord(__float_as_uint(s_acc[rel])) << 32) | (uint32_t)~(tile_rel + rel);
+                    float score = s_acc[rel];
+                    if (BOOST) {
+                        const float f = boost[w_lo + rel];   // w_lo + rel < w_hi <= n_docs <= the table's length (the call checked)
+                        score = __fmul_rn(score, f);
+#ifdef NS_COUNT
+                        multiplied++;
+                        nonzero = nonzero || f != 0.0f;
+#endif
+                    }
+                    key = ((uint64_t)bq_ord(__float_as_uint(score)) << 32) | (uint32_t)~(tile_rel + rel);
                 }
+#ifdef NS_COUNT
+                if (BOOST && key != 0ull && key > last) clipped++;
+#endif
                 if (AFTER) key = af_clip(key, last, kept);
                 bq_insert(set, key, K, lane);
             }
         }
+#ifdef NS_COUNT
+        if (BOOST) {   // (every thread of the workgroup is here: what leaves a window early leaves it above, uniformly)
+            if (multiplied) atomicAdd(&g_ns_bbcnt[2], (unsigned long long)multiplied);
+            if (clipped) atomicAdd(&g_ns_bbcnt[3], (unsigned long long)clipped);
+            if (!__syncthreads_or(nonzero ? 1 : 0)) NS_BBCNT(4, 1);
+            swept = true;
+        }
+#endif
     }
+#ifdef NS_COUNT
+    if (BOOST && swept) NS_BBCNT(1, 1);
+#endif
     __syncthreads();   // (s_cnt is zero; nobody reads the accumulators any more)
     if (cnt) atomicAdd(&s_cnt, cnt);
     if (AFTER && kept) atomicAdd(&s_rest, kept);
@@ -456,6 +510,16 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     uint64_t* __restrict__ row = cand + (size_t)blockIdx.x * K;
     if (lane < K) row[lane] = set.hi;
     if (64u + lane < K) row[64u + lane] = set.lo;
+}
+
+// At the upload of a factor table (ns_docboost_upload; as k_sd_check): is a factor not finite, or is its sign bit set (-0.0f too)?
+__global__ void __launch_bounds__(256) k_bq_boost_check(const float* __restrict__ boost, uint32_t n_docs, uint32_t* __restrict__ bad) {
+    bool any = false;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_docs; i += gridDim.x * 256u) {
+        const uint32_t b = __float_as_uint(boost[i]);
+        any = any || (b & 0x80000000u) != 0u || (b & 0x7F800000u) == 0x7F800000u;
+    }
+    if (any) atomicOr(bad, 1u);
 }
 
 // items / q_off index the whole call's items; cand holds the rows of the items from item_begin on.

@@ -78,4 +78,12 @@ inline bool ranked_call_plan(const std::vector<FcItem>& items, uint32_t n_querie
     return true;
 }
 
+// A call whose select kernel exists with AFTER = true alone (ns_search_boosted_after with tables): a plan without
+// a cursor gets the bound that lets every key pass for each of its items, so that rest counts what found counts.
+inline void ranked_plan_bound_all(size_t n_items, RankedPlan& plan) {
+    if (plan.paged) return;
+    plan.last.assign(n_items, kAfterAll);
+    plan.paged = true;
+}
+
 }  // namespace ns

@@ -8,6 +8,7 @@
 // No parentheses, no phrases, no nesting.
 #pragma once
 
+#include <charconv>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -26,8 +27,9 @@ struct BoolTerm {
 inline bool bool_is_space(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; }
 
 // The three dialects of the query box.  They are nested: Grouped (grouped.hpp) is Boolean plus one level of parentheses, Quorum
-// (quorum.hpp) is Grouped plus the two `~m` forms.  A fourth dialect is one more value here and one more branch in the scanner.
-enum class Dialect : int { Boolean = 0, Grouped = 1, Quorum = 2 };
+// (quorum.hpp) is Grouped plus the two `~m` forms, Boosted (boost.hpp) is Quorum plus the `^w` suffix.  A further dialect is one
+// more value here and one more branch in the scanner.
+enum class Dialect : int { Boolean = 0, Grouped = 1, Quorum = 2, Boosted = 3 };
 
 static constexpr uint32_t kQuorumNeedCap = 1000000;    // what a longer run of digits reads as
 
@@ -48,14 +50,37 @@ inline uint32_t quorum_digits(const char* text, size_t n, size_t i, size_t& end)
     return (uint32_t)v;
 }
 
-// The one scanner of the three grammars (the header comments of boolean.hpp, grouped.hpp and quorum.hpp).  Calls
+static constexpr double kBoostMaxWeight = 1e6;         // a `^w` is a weight for 0 < w <= this
+
+// Boosted: `^w` at text[i ..), where the piece ends at `stop`: '^', then digits with at most one '.' and at least one digit, up
+// to `stop` exactly, their value in (0, kBoostMaxWeight] and above 0 as an fp32 too.  -> the weight, or 0: no weight stands there
+// (an exponent, a sign, a second '.', nothing, zero, too much), and the '^' is the tokenizer's business.
+inline float boost_weight_at(const char* text, size_t stop, size_t i) {
+    if (i >= stop || text[i] != '^' || i + 1 >= stop) return 0.0f;
+    size_t dots = 0, digits = 0;
+    for (size_t j = i + 1; j < stop; j++) {
+        if (text[j] == '.') dots++;
+        else if (text[j] >= '0' && text[j] <= '9') digits++;
+        else return 0.0f;
+    }
+    if (dots > 1 || digits == 0) return 0.0f;
+    double v = 0.0;
+    const auto r = std::from_chars(text + i + 1, text + stop, v, std::chars_format::fixed);
+    if (r.ec != std::errc() || r.ptr != text + stop || !(v > 0.0) || v > kBoostMaxWeight) return 0.0f;
+    return (float)v;
+}
+
+// The one scanner of the four grammars (the header comments of boolean.hpp, grouped.hpp, quorum.hpp and boost.hpp).  Calls
 // fn(ptr, len, role, clause, need) for every term of the query, in order; `scratch` holds the lowercased bytes.  Under kRoleMust
 // `clause` counts up from 0 (one id per group, one per token outside a group) and `need` is the clause's need (>= 1); else both
 // are 0.  The optional terms come as SHOULD terms whatever min_should says: see QuorumShape.  Without groups '(' is the
-// tokenizer's business; without needs a '~' is.
+// tokenizer's business; without needs a '~' is; without weights a '^' is.  Boosted: *weight holds the weight of the piece (1.0f
+// without a valid suffix, and on a `-` piece, where the suffix is consumed and ignored) whenever fn is called.
 template <Dialect D, class Fn>
-inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
-    constexpr bool kGroups = D != Dialect::Boolean, kNeeds = D == Dialect::Quorum;
+inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr) {
+    constexpr bool kGroups = D != Dialect::Boolean, kNeeds = D == Dialect::Quorum || D == Dialect::Boosted, kWeights = D == Dialect::Boosted;
+    float unused = 1.0f;
+    float& w_now = weight ? *weight : unused;
     QuorumShape shape{0, 0};
     size_t i = 0;
     while (i < n) {
@@ -72,6 +97,13 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
                 size_t behind;
                 const uint32_t m = quorum_digits(text, n, end + 2, behind);
                 if (behind > end + 2) { need = m; resume = behind; }
+            }
+            w_now = 1.0f;
+            if (kWeights && resume < n && text[resume] == '^') {   // behind the ')' and the `~m`, up to the next blank
+                size_t stop = resume;
+                while (stop < n && !bool_is_space((unsigned char)text[stop])) stop++;
+                const float w = boost_weight_at(text, stop, resume);
+                if (w > 0.0f) { resume = stop; if (prefix != kRoleNot) w_now = w; }
             }
             const uint8_t role = (need >= 1 && prefix == kRoleShould) ? kRoleMust : prefix;
             if (role != kRoleMust) need = 0;
@@ -92,7 +124,15 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
             const uint32_t m = quorum_digits(text, n, i + 1, behind);
             if (behind == j) { shape.min_should = m; i = j; continue; }
         }
-        for_each_base_term(text + from, j - from, scratch,
+        size_t to = j;
+        w_now = 1.0f;
+        if (kWeights) {   // the piece's last '^', if a weight and nothing else stands behind it
+            size_t hat = j;
+            while (hat > from && text[hat - 1] != '^') hat--;
+            const float w = hat > from ? boost_weight_at(text, j, hat - 1) : 0.0f;
+            if (w > 0.0f) { to = hat - 1; if (prefix != kRoleNot) w_now = w; }
+        }
+        for_each_base_term(text + from, to - from, scratch,
                            [&](const char* p, size_t len) { fn(p, len, prefix, prefix == kRoleMust ? shape.n_clauses++ : 0u, prefix == kRoleMust ? 1u : 0u); });
         i = j;
     }
@@ -101,11 +141,13 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
 
 // the scanner of a dialect chosen at run time
 template <class Fn>
-inline QuorumShape for_each_term(Dialect d, const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+inline QuorumShape for_each_term(Dialect d, const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr) {
+    if (weight) *weight = 1.0f;
     switch (d) {
         case Dialect::Boolean: return for_each_dialect_term<Dialect::Boolean>(text, n, scratch, fn);
         case Dialect::Grouped: return for_each_dialect_term<Dialect::Grouped>(text, n, scratch, fn);
-        default: return for_each_dialect_term<Dialect::Quorum>(text, n, scratch, fn);
+        case Dialect::Quorum: return for_each_dialect_term<Dialect::Quorum>(text, n, scratch, fn);
+        default: return for_each_dialect_term<Dialect::Boosted>(text, n, scratch, fn, weight);
     }
 }
 

@@ -59,6 +59,7 @@ void Engine::release_device_segments() {
     release_similar();
     release_facets();
     release_sorted();
+    release_boosts();
     close_all_filters();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
@@ -2370,13 +2371,15 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
 // what the dialect forms call themselves in messages: the named methods of engine.hpp
 struct DialectNames { const char *first_page, *after_batch, *facet_batch, *sorted_batch, *text, *faceted_text, *sorted_text; };
 static const DialectNames& names_of(nsx::Dialect d) {
-    static const DialectNames kNames[3] = {
+    static const DialectNames kNames[4] = {
         {"search_boolean_batch_flat", "search_boolean_after_batch_flat", "facet_boolean_batch_flat", "search_boolean_sorted_batch_flat", "search_boolean",
          "search_boolean_faceted", "search_boolean_sorted"},
         {"search_grouped_after_batch_flat", "search_grouped_after_batch_flat", "facet_grouped_batch_flat", "search_grouped_sorted_batch_flat", "search_grouped",
          "search_grouped_faceted", "search_grouped_sorted"},
         {"search_quorum_after_batch_flat", "search_quorum_after_batch_flat", "facet_quorum_batch_flat", "search_quorum_sorted_batch_flat", "search_quorum",
-         "search_quorum_faceted", "search_quorum_sorted"}};
+         "search_quorum_faceted", "search_quorum_sorted"},
+        {"search_boosted_after_batch_flat", "search_boosted_after_batch_flat", "facet_boosted_batch_flat", "search_boosted_sorted_batch_flat", "search_boosted",
+         "search_boosted_faceted", "search_boosted_sorted"}};   // (Boosted has the ranked call alone: DESIGN.md §5z, left out)
     return kNames[(int)d];
 }
 
@@ -2386,8 +2389,9 @@ static const DialectNames& names_of(nsx::Dialect d) {
 // False, with a message, when a Grouped or Quorum query has more clauses than a clause value can name, or a Quorum query asks
 // for more than kQuorumMaxNeed of a clause's terms.  Boolean never fails.
 bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* queries, size_t a, size_t b, uint8_t* usable, CallPrep& bp) {
-    const bool with_clauses = dialect != nsx::Dialect::Boolean, with_needs = dialect == nsx::Dialect::Quorum;
+    const bool with_clauses = dialect != nsx::Dialect::Boolean, with_needs = dialect == nsx::Dialect::Quorum || dialect == nsx::Dialect::Boosted;
     const uint32_t S = (uint32_t)segments.size();
+    float weight = 1.0f;   // Boosted: the `^w` of the piece the scanner is in; else 1.0f
     const nsx::RowSource& rs = bp.rs;
     bp.qd.assign(b - a, ns_query_desc{0, 0});
     bp.refs.clear();
@@ -2399,16 +2403,16 @@ bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* q
         size_t positive = 0;
         uint32_t largest = 0;
         const nsx::QuorumShape shape = nsx::for_each_term(dialect, queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
-            bp.terms.push_back(CallPrep::Term{dict.find(p, n), role, clause, need});
+            bp.terms.push_back(CallPrep::Term{dict.find(p, n), role, clause, need, weight});
             positive += role != nsx::kRoleNot;
             largest = std::max(largest, need);
-        });
+        }, &weight);
         uint32_t n_clauses = shape.n_clauses;
         if (shape.min_should) {   // `~m`: every optional term joins one more required clause of need m
             bool any = false;
             for (CallPrep::Term& t : bp.terms)
                 if (t.role == nsx::kRoleShould) {
-                    t = CallPrep::Term{t.row, nsx::kRoleMust, shape.n_clauses, shape.min_should};
+                    t = CallPrep::Term{t.row, nsx::kRoleMust, shape.n_clauses, shape.min_should, t.weight};
                     any = true;
                 }
             if (any) n_clauses++;
@@ -2425,7 +2429,7 @@ bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* q
         for (const uint32_t sid : bp.listed)
             for (const CallPrep::Term& t : bp.terms) {
                 const nsx::TermSeg* e = t.row < 0 ? nullptr : rs.rows ? &rs.rows[(size_t)t.row * S + sid] : &dict.row((uint32_t)t.row)[sid];
-                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, 1.0f});
+                if (e && e->byte_off != nsx::kAbsent) bp.refs.push_back(ns_term_ref{rs.id_base + sid, e->count, e->byte_off, e->idf, t.weight});
                 else if (t.role == nsx::kRoleMust) bp.refs.push_back(ns_term_ref{rs.id_base + sid, 0u, 0u, 0.0f, 1.0f});   // an absent member of its clause
                 else continue;
                 bp.roles.push_back(t.role);
@@ -2461,6 +2465,11 @@ bool Engine::ranked_call(nsx::Dialect dialect, bool paged, const CallPrep& bp, s
             rc = ns_search_quorum_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, cur, bp.ids.data(),
                                         bp.segs.data(), n_segs, hits, out.nhits + a, out.found + a, rest, ms);
             break;
+        case nsx::Dialect::Boosted:   // without tables (term weights only) the call is the quorum call, kernels and all
+            name = "ns_search_boosted_after: ";
+            rc = ns_search_boosted_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, cur, bp.ids.data(),
+                                         bp.segs.data(), bp.boosts.empty() ? nullptr : bp.boosts.data(), n_segs, hits, out.nhits + a, out.found + a, rest, ms);
+            break;
     }
     if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
     return true;
@@ -2485,6 +2494,7 @@ bool Engine::facet_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size
             rc = ns_facet_count_quorum(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, bp.ids.data(), bp.segs.data(), tabs,
                                        n_segs, counts, found, ms);
             break;
+        case nsx::Dialect::Boosted: err_ = "facet counts do not depend on a score: use the quorum call"; return false;
     }
     if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
     return true;
@@ -2514,19 +2524,25 @@ bool Engine::sorted_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, siz
             rc = ns_search_sorted_quorum(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, direction, cur, bp.ids.data(),
                                          bp.segs.data(), tabs, n_segs, hits, keys, out.nhits + a, out.found + a, rest, ms);
             break;
+        case nsx::Dialect::Boosted: err_ = "date order does not depend on a score: use the quorum call"; return false;
     }
     if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
     return true;
 }
 
 bool Engine::boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
-                                ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+                                ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms, const nsx::BoostSpec* boost) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (device_ms) *device_ms = 0.0f;
     if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
     if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
     CallPrep bp;
     if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    if (boost && dialect == nsx::Dialect::Boosted) {   // the factor tables of the listed segments (a filter's copies keep the docIds)
+        BoostSet* bs = nullptr;
+        if (!ensure_boosts(*boost, bs)) { err_ = std::string(fn) + ": " + err_; return false; }
+        for (const uint32_t s : bp.listed) bp.boosts.push_back(bs->dev[s]);
+    }
     if (Q == 0) return true;
     const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, nullptr, nhits, found, rest, device_ms};
     return ranked_batch(fn, bp, after, Q, out,
@@ -2535,8 +2551,8 @@ bool Engine::boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t f
 }
 
 bool Engine::search_dialect_after_batch_flat(nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
-                                             ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
-    return boolean_batch_impl(names_of(dialect).after_batch, dialect, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+                                             ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms, const nsx::BoostSpec* boost) {
+    return boolean_batch_impl(names_of(dialect).after_batch, dialect, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms, boost);
 }
 
 bool Engine::facet_dialect_batch_flat(nsx::Dialect dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
@@ -2705,19 +2721,92 @@ static bool quorum_insert(std::string& tail, const std::string& query) {
     return true;
 }
 
+// a double as json_number_from_float prints the widened float
+static void json_number_from_double(std::string& out, double d) {
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), d);
+    std::string s(buf, r.ptr);
+    if (s.find_first_of(".eEn") == std::string::npos) s += ".0";
+    out += s;
+}
+
+// the "boost" member of search_boosted's body (§5z): the spec as given, the origin without its blanks ("" = the newest dated document)
+static std::string boost_member(const nsx::BoostSpec& b) {
+    std::string o = "  \"boost\": {\n    \"kind\": ";
+    json_escape(o, nsx::boost_name(b));
+    o += ",\n    \"offset_days\": ";
+    json_number_from_double(o, b.offset_days);
+    o += ",\n    \"origin\": ";
+    json_escape(o, std::string(nsx::detail::strip_blanks(b.origin)));
+    o += ",\n    \"scale_days\": ";
+    json_number_from_double(o, b.scale_days);
+    o += ",\n    \"undated\": ";
+    json_number_from_double(o, b.undated);
+    o += ",\n    \"weight\": ";
+    json_number_from_double(o, b.weight);
+    o += "\n  },\n";
+    return o;
+}
+
+// the "boosted" member of search_boosted's body (§5z): quorum_member's, where a "must" clause also carries the "weight" of its
+// piece and a "should" entry is {"term", "weight"}; "must_not" stays a list of strings (a weight there says nothing)
+static std::string boosted_member(const std::string& query) {
+    uint32_t min_should = 0;
+    const std::vector<nsx::BoostedTerm> terms = nsx::parse_boosted(query, &min_should);
+    std::string o = "  \"boosted\": {\n    \"min_should\": " + std::to_string(min_should) + ",\n    \"must\": [";
+    bool any_clause = false;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (terms[i].role != nsx::kRoleMust || terms[i].promoted) continue;
+        bool first_of_clause = true;
+        for (size_t j = 0; j < i; j++) first_of_clause = first_of_clause && !(terms[j].role == nsx::kRoleMust && !terms[j].promoted && terms[j].clause == terms[i].clause);
+        if (!first_of_clause) continue;
+        o += any_clause ? ",\n      {" : "\n      {";
+        o += "\n        \"need\": " + std::to_string(terms[i].need) + ",\n        \"terms\": [";
+        bool any = false;
+        for (size_t j = i; j < terms.size(); j++)
+            if (terms[j].role == nsx::kRoleMust && !terms[j].promoted && terms[j].clause == terms[i].clause) {
+                o += any ? ",\n          " : "\n          ";
+                json_escape(o, terms[j].text);
+                any = true;
+            }
+        o += "\n        ],\n        \"weight\": ";
+        json_number_from_float(o, terms[i].weight);
+        o += "\n      }";
+        any_clause = true;
+    }
+    o += any_clause ? "\n    ],\n" : "],\n";
+    append_term_list(o, "must_not", terms, [](const nsx::BoostedTerm& t) { return t.role == nsx::kRoleNot; }, false);
+    o += "    \"should\": [";
+    bool any = false;
+    for (const nsx::BoostedTerm& t : terms)
+        if (t.role == nsx::kRoleShould || t.promoted) {
+            o += any ? ",\n      {\n        \"term\": " : "\n      {\n        \"term\": ";
+            json_escape(o, t.text);
+            o += ",\n        \"weight\": ";
+            json_number_from_float(o, t.weight);
+            o += "\n      }";
+            any = true;
+        }
+    o += any ? "\n    ]\n" : "]\n";
+    o += "  },\n";
+    return o;
+}
+
 // The dialect's member (the parsed query) put into a body in its sorted place (nlohmann keeps keys sorted).  front: "{\n" and
 // the "filter" member if there is one; tail: to_json_impl's members.  "boolean" is the body's first member; "grouped" stands in
 // front of tail's "k", "quorum" in front of tail's "results".  -> nullptr, or the name of the member that tail lacks
-static const char* insert_dialect_member(nsx::Dialect dialect, const std::string& query, std::string& front, std::string& tail) {
+// "boost" and "boosted" are the body's first two.
+static const char* insert_dialect_member(nsx::Dialect dialect, const std::string& query, std::string& front, std::string& tail, const nsx::BoostSpec* boost = nullptr) {
     switch (dialect) {
         case nsx::Dialect::Boolean: front.insert(2, boolean_member(query)); return nullptr;
         case nsx::Dialect::Grouped: return grouped_insert(tail, query) ? nullptr : "k";
-        default: return quorum_insert(tail, query) ? nullptr : "results";
+        case nsx::Dialect::Quorum: return quorum_insert(tail, query) ? nullptr : "results";
+        default: front.insert(2, (boost ? boost_member(*boost) : std::string()) + boosted_member(query)); return nullptr;
     }
 }
 
 // search_boolean's body, or the same body over another dialect with its member in place of "boolean"
-bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body) {
+bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body, const nsx::BoostSpec* boost) {
     const char* name = names_of(dialect).text;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
@@ -2737,7 +2826,7 @@ bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query,
     uint32_t nh = 0;
     uint64_t fd = 0;
     uint8_t us = 0;
-    if (!boolean_batch_impl(names_of(dialect).first_page, dialect, handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us, nullptr)) { body = err_; return false; }
+    if (!boolean_batch_impl(names_of(dialect).first_page, dialect, handle, &qv, 1, K, nullptr, hits.data(), &nh, &fd, nullptr, &us, nullptr, boost)) { body = err_; return false; }
     SearchResult res;
     res.query = query;
     res.k = K;
@@ -2747,7 +2836,7 @@ bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query,
     if (res.has_found)
         for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     std::string tail = to_json_impl(res).substr(2);
-    if (const char* missing = insert_dialect_member(dialect, query, head, tail)) { body = err_ = std::string(name) + ": the search body has no " + missing + " member"; return false; }
+    if (const char* missing = insert_dialect_member(dialect, query, head, tail, boost)) { body = err_ = std::string(name) + ": the search body has no " + missing + " member"; return false; }
     body = head + tail;
     return true;
 }
@@ -2804,6 +2893,103 @@ bool Engine::search_dialect_sorted_text(nsx::Dialect dialect, const std::string&
     o += "\n}";
     body = std::move(o);
     return true;
+}
+
+// ---- boosts (host/boost.hpp) --------------------------------------------------------------------------------
+void Engine::release_boosts() {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (ctx_)
+        for (ns_docboost* t : boosts_.dev)
+            if (t) (void)ns_docboost_release(ctx_, t);
+    boosts_ = BoostSet{};
+}
+
+size_t Engine::boost_tables_on_device() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const ns_docboost* t : boosts_.dev) n += t != nullptr;
+    return n;
+}
+
+bool Engine::boost_table(const nsx::BoostSpec& spec, std::vector<std::vector<float>>& tables) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    tables.clear();
+    const size_t S = segments.size();
+    uint32_t origin_key = 0;
+    if (!nsx::boost_check(spec, origin_key, err_)) return false;
+    if (spec.kind == nsx::BoostSpec::Custom) {
+        if (spec.custom.size() != S) { err_ = "boost custom: " + std::to_string(spec.custom.size()) + " factor arrays for " + std::to_string(S) + " segments"; return false; }
+        for (size_t s = 0; s < S; s++) {
+            if (spec.custom[s].size() != segments[s].N) {
+                err_ = "boost custom: the factor array of segment " + std::to_string(s) + " has " + std::to_string(spec.custom[s].size()) + " entries, the segment " + std::to_string(segments[s].N) + " documents";
+                return false;
+            }
+            for (const float f : spec.custom[s])
+                if (!nsx::boost_factor_ok(f)) { err_ = "boost custom: segment " + std::to_string(s) + " holds a factor that is negative or not finite"; return false; }
+        }
+        tables = spec.custom;
+        return true;
+    }
+    std::vector<std::vector<uint32_t>> keys;
+    if (!sort_keys(nsx::SortSpec{}, keys)) return false;   // date_key() of publish_time per document, 0 = undated
+    int64_t origin_days = 0;
+    if (origin_key) origin_days = nsx::days_of_key(origin_key);
+    else {
+        bool any = false;
+        for (const auto& ks : keys)
+            for (const uint32_t k : ks)
+                if (k) { const int64_t d = nsx::days_of_key(k); origin_days = any ? std::max(origin_days, d) : d; any = true; }
+    }
+    tables.resize(S);
+    for (size_t s = 0; s < S; s++) {
+        tables[s].resize(keys[s].size());
+        for (size_t d = 0; d < keys[s].size(); d++) tables[s][d] = nsx::boost_decay(spec, origin_days, keys[s][d]);
+    }
+    return true;
+}
+
+// the spec's factors on the host and, for every segment with a device copy, on the device; another spec takes the set's place
+bool Engine::ensure_boosts(const nsx::BoostSpec& spec, BoostSet*& out) {
+    std::string key = "custom";
+    if (spec.kind != nsx::BoostSpec::Custom) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "%d|%a|%a|%a|%a|", (int)spec.kind, spec.weight, spec.scale_days, spec.offset_days, spec.undated);
+        key = buf + std::string(nsx::detail::strip_blanks(spec.origin));
+    }
+    if (boosts_.built && (boosts_.key != key || (spec.kind == nsx::BoostSpec::Custom && boosts_.tables != spec.custom))) release_boosts();
+    if (!boosts_.built) {
+        BoostSet fresh;
+        fresh.key = key;
+        if (!boost_table(spec, fresh.tables)) return false;
+        fresh.dev.assign(segments.size(), nullptr);
+        for (uint32_t s = 0; s < segments.size(); s++) {
+            if (!dev_segs_[s]) continue;
+            const int rc = ns_docboost_upload(ctx_, segments[s].N, fresh.tables[s].data(), &fresh.dev[s]);
+            if (rc != NS_OK) {
+                err_ = std::string("ns_docboost_upload: ") + ns_last_error(ctx_);
+                for (ns_docboost* t : fresh.dev) if (t) (void)ns_docboost_release(ctx_, t);
+                return false;
+            }
+        }
+        fresh.built = true;
+        boosts_ = std::move(fresh);
+    }
+    out = &boosts_;
+    return true;
+}
+
+bool Engine::search_boosted_after_batch_flat(const nsx::BoostSpec* spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
+                                             ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms) {
+    return search_dialect_after_batch_flat(nsx::Dialect::Boosted, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms, spec);
+}
+
+bool Engine::search_boosted_text(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::DocFilter* f, std::string& body) {
+    return search_dialect_text(nsx::Dialect::Boosted, query, k, f, body, spec);
+}
+
+std::string Engine::search_boosted(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_boosted_text(query, k, spec, f, body) ? body : error_body(body);
 }
 
 // ---- the named methods: forwards to the dialect forms --------------------------------------------------------------------
@@ -2974,7 +3160,8 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
-    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::QuorumSorted) { body = err_ = "search_page: unknown mode"; return false; }
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::Boosted) { body = err_ = "search_page: unknown mode"; return false; }
+    const nsx::BoostSpec* boost = (spec.mode == nsx::PageSpec::Boosted && spec.use_boost) ? &spec.boost : nullptr;
     const char kind = nsx::page_kind(spec.mode);
     nsx::PageCursor cur;
     if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
@@ -2999,7 +3186,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     bool ok = false;
     if (!call.plain)
         ok = call.dated ? search_dialect_sorted_batch_flat(call.dialect, spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us)
-                        : search_dialect_after_batch_flat(call.dialect, handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us);
+                        : search_dialect_after_batch_flat(call.dialect, handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us, nullptr, boost);
     else if (call.dated) ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
     else ok = search_after_batch_flat(handle, &qv, 1, K, spec.mode == nsx::PageSpec::SearchAnd ? NS_FLAG_AND : NS_FLAG_OR, &cur, hits.data(), &nh, &fd, &rs, &us);
     if (!ok) { body = err_; return false; }
@@ -3014,7 +3201,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     std::string o = head;
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
     if (!call.plain)   // the dialect's member, as in its search_* body
-        if (const char* missing = insert_dialect_member(call.dialect, query, o, rest_of)) { body = err_ = std::string("search_page: the search body has no ") + missing + " member"; return false; }
+        if (const char* missing = insert_dialect_member(call.dialect, query, o, rest_of, boost)) { body = err_ = std::string("search_page: the search body has no ") + missing + " member"; return false; }
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
     const size_t at = rest_of.find("  \"query\": ");
     if (at == std::string::npos || (at != 0 && rest_of[at - 1] != '\n')) { body = err_ = "search_page: the search body has no query member"; return false; }

@@ -40,6 +40,7 @@
 #include "boolean.hpp"
 #include "grouped.hpp"
 #include "quorum.hpp"
+#include "boost.hpp"
 #include "page.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
@@ -420,16 +421,41 @@ public:
     std::string search_quorum_sorted(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f = nullptr);
     bool search_quorum_sorted_text(const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
 
+    // Boosts (host/boost.hpp, csrc/ns_boolean.hip k_bq_select<true, ., ., true>): the quorum ranked call over
+    // nsx::parse_boosted's dialect, `+(covid sars)^0.5 vaccine^2.5`, whose `^w` becomes the qweight of the piece's terms, with one
+    // fp32 factor per document multiplied into the finished score: relevance that prefers recent documents, or documents of a
+    // high static rank.  boost_table: the spec's factors per segment in manifest order; host only (works on a host-only engine);
+    // false, with a message, for a spec boost_check refuses or custom factors that do not fit the index, are negative (-0.0f
+    // included) or not finite.  search_boosted_after_batch_flat is search_quorum_after_batch_flat parameter for parameter
+    // (filter handle and cursors included; a cursor's rank is the product's bits) behind `spec`; spec == nullptr: term weights
+    // only, through the sibling's kernels.  A weight of 0 gives the quorum call's answers bit for bit for a text without `^w`.
+    // The device copies of the tables are built by the first call that needs them (never by reload()), one set at a time (another
+    // spec takes its place), serve the filtered copies unchanged, and are freed by reload(), release_boosts() and the destructor.
+    bool boost_table(const nsx::BoostSpec& spec, std::vector<std::vector<float>>& tables);
+    bool search_boosted_after_batch_flat(const nsx::BoostSpec* spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
+                                         const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                                         float* device_ms = nullptr);
+    // JSON text: search_quorum's body with "boosted" in place of "quorum" (the same members; a "must" clause carries "weight", a
+    // "should" entry is {"term", "weight"}) and, with a spec, "boost": {"kind", "offset_days", "origin", "scale_days", "undated",
+    // "weight"}; both stand in front of "filter".  search_page's mode Boosted pages it with cursors of kind 's'.  Any failure:
+    // {"error": ...} (search_boosted_text: false, body = the message).
+    std::string search_boosted(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::DocFilter* f = nullptr);
+    bool search_boosted_text(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::DocFilter* f, std::string& body);
+    void release_boosts();
+    size_t boost_tables_on_device() const;   // factor tables with a device copy right now
+
     // The calls above by dialect (nsx::Dialect, host/boolean.hpp): each named method forwards to one of these, which name
     // themselves in messages as the dialect's named method does.  DESIGN.md §5x lists what a fourth dialect adds.
+    // boost (Dialect::Boosted only; may be nullptr): the factors of search_boosted_after_batch_flat and search_boosted_text.
     bool search_dialect_after_batch_flat(nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
-                                         ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr);
+                                         ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms = nullptr,
+                                         const nsx::BoostSpec* boost = nullptr);
     bool facet_dialect_batch_flat(nsx::Dialect dialect, const nsx::FacetSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
                                   std::vector<uint32_t>& counts, uint64_t* found, uint8_t* usable, std::vector<std::string>& labels, float* device_ms = nullptr);
     bool search_dialect_sorted_batch_flat(nsx::Dialect dialect, const nsx::SortSpec& spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
                                           const nsx::PageCursor* after, ns_hit* hits, uint32_t* keys, uint32_t* nhits, uint64_t* found, uint64_t* rest,
                                           uint8_t* usable, float* device_ms = nullptr);
-    bool search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body);
+    bool search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body, const nsx::BoostSpec* boost = nullptr);
     bool search_dialect_faceted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::FacetSpec& spec, const nsx::DocFilter* f, std::string& body);
     bool search_dialect_sorted_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::SortSpec& spec, const nsx::DocFilter* f, std::string& body);
 
@@ -545,9 +571,10 @@ private:
         std::vector<ns_term_ref> refs;
         std::vector<uint8_t> roles;
         std::vector<uint16_t> clauses;          // Grouped, Quorum: parallel to refs
-        std::vector<uint8_t> needs;             // Quorum: parallel to refs
+        std::vector<uint8_t> needs;             // Quorum, Boosted: parallel to refs
+        std::vector<ns_docboost*> boosts;       // Boosted under a spec: parallel to segs; empty: none
         std::vector<char> scratch;
-        struct Term { int64_t row; uint8_t role; uint32_t clause, need; };   // row: the dictionary's, or -1
+        struct Term { int64_t row; uint8_t role; uint32_t clause, need; float weight; };   // row: the dictionary's, or -1
         std::vector<Term> terms;                // of one query
     };
     // boolean_prepare's two halves.  filter_rows: the stale-handle check and the filter's row source.  list_segments: the
@@ -581,7 +608,8 @@ private:
     bool sorted_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size_t b, uint32_t direction, ns_dockeys* const* tabs, const RankedOut& out,
                      const ns_cursor* cur, float* ms);
     bool boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k,
-                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms);
+                            const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms,
+                            const nsx::BoostSpec* boost = nullptr);
     void close_filter_slot(OpenFilter& f);
     void close_all_filters();
     struct FilterLruEnt { std::string key; uint32_t handle; };
@@ -603,6 +631,15 @@ private:
     };
     SortSet sorts_[2];
     bool ensure_sorted(const nsx::SortSpec& spec, SortSet*& out);
+    // boost factors: the last spec's host tables and their device copies (nullptr: the segment has none); key: the decay's parameters
+    struct BoostSet {
+        bool built = false;
+        std::string key;
+        std::vector<std::vector<float>> tables;
+        std::vector<ns_docboost*> dev;
+    };
+    BoostSet boosts_;
+    bool ensure_boosts(const nsx::BoostSpec& spec, BoostSet*& out);
     mutable std::string err_;
 };
 

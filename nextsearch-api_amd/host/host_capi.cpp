@@ -1144,7 +1144,7 @@ static void nsh_cursors_of(const nsh_page_cursor* in, uint32_t n, std::vector<ns
 // mode: the nsx::PageSpec mode whose batch call this is (page_call: which call, and whether it is in date order)
 static int nsh_after_batch(nsh_engine* e, const char* fn, nsx::PageSpec::Mode mode, const nsh_sort_spec* spec, uint32_t filter_handle, const char* const* queries,
                            uint32_t n_queries, int k, uint32_t flags, const nsh_page_cursor* after, void* hits, uint32_t* keys_out, uint32_t* nhits,
-                           uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out) {
+                           uint64_t* found, uint64_t* rest, uint8_t* has_found, float* device_ms_out, const nsx::BoostSpec* boost = nullptr) {
     if (!e) return -1;
     nsx::SortSpec sp;
     std::string why;
@@ -1165,7 +1165,7 @@ static int nsh_after_batch(nsh_engine* e, const char* fn, nsx::PageSpec::Mode mo
     bool ok;
     if (!call.plain)
         ok = dated ? e->eng.search_dialect_sorted_batch_flat(call.dialect, sp, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out)
-                   : e->eng.search_dialect_after_batch_flat(call.dialect, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
+                   : e->eng.search_dialect_after_batch_flat(call.dialect, filter_handle, views.data(), n_queries, k, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out, boost);
     else if (dated) ok = e->eng.search_sorted_after_batch_flat(sp, filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, keys_out, nhits, found, rest, has_found, device_ms_out);
     else ok = e->eng.search_after_batch_flat(filter_handle, views.data(), n_queries, k, flags, cp, (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out);
     if (!ok) { nsh_set_err(e, e->eng.last_error()); return -1; }
@@ -1333,6 +1333,110 @@ extern "C" int nsh_engine_search_quorum_sorted_json(nsh_engine* e, const char* q
 } NSH_CATCH(e, "nsh_engine_search_quorum_sorted_json", -1)
 }
 
+// ---- boosts (host/boost.hpp) ----
+// in == NULL: no spec (`have` false)
+static bool nsh_boost_spec_of(nsh_engine* e, const nsh_boost_spec* in, nsx::BoostSpec& out, bool& have, std::string& why) {
+    have = in != nullptr;
+    if (!in) return true;
+    if (in->kind > 2u) { why = "boost: unknown kind " + std::to_string(in->kind); return false; }
+    out.kind = (nsx::BoostSpec::Kind)in->kind;
+    out.weight = in->weight;
+    out.origin = in->origin ? in->origin : "";
+    out.scale_days = in->scale_days;
+    out.offset_days = in->offset_days;
+    out.undated = in->undated;
+    if (out.kind != nsx::BoostSpec::Custom) return true;
+    if (in->n_custom && !in->custom) { why = "boost custom: null array"; return false; }
+    // whole arrays as far as the factors reach; factors left over become one more: the engine refuses either with a message
+    uint64_t at = 0;
+    for (const auto& sd : e->eng.segments) {
+        if (at + sd.N > in->n_custom) break;
+        out.custom.emplace_back(in->custom + at, in->custom + at + sd.N);
+        at += sd.N;
+    }
+    if (out.custom.size() == e->eng.segments.size() && at != in->n_custom) out.custom.emplace_back(in->custom + at, in->custom + in->n_custom);
+    return true;
+}
+
+extern "C" int64_t nsh_engine_boost_table(nsh_engine* e, const nsh_boost_spec* spec, float* out, uint64_t cap) { try {
+    if (!e) return -1;
+    nsx::BoostSpec sp;
+    std::string why;
+    bool have = false;
+    if (!nsh_boost_spec_of(e, spec, sp, have, why)) { nsh_set_err(e, why); return -1; }
+    if (!have) { nsh_set_err(e, "boost: spec is NULL"); return -1; }
+    std::vector<std::vector<float>> tables;
+    if (!e->eng.boost_table(sp, tables)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    uint64_t at = 0;
+    for (const auto& t : tables) {
+        for (size_t i = 0; i < t.size(); i++)
+            if (out && at + i < cap) out[at + i] = t[i];
+        at += t.size();
+    }
+    return (int64_t)at;
+} NSH_CATCH(e, "nsh_engine_boost_table", -1)
+}
+
+extern "C" void nsh_engine_release_boosts(nsh_engine* e) { try { if (e) e->eng.release_boosts(); } NSH_CATCH_VOID(e, "nsh_engine_release_boosts") }
+extern "C" uint64_t nsh_engine_boost_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.boost_tables_on_device() : 0; }
+
+extern "C" uint32_t nsh_parse_boosted(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                                      float* weights, uint32_t terms_cap, uint32_t* min_should_out) { try {
+    uint32_t min_should = 0;
+    const auto terms = nsx::parse_boosted(query ? query : "", &min_should);
+    for (size_t i = 0; i < terms.size() && i < terms_cap; i++) {
+        if (roles) roles[i] = terms[i].role;
+        if (clauses) clauses[i] = terms[i].clause;
+        if (needs) needs[i] = terms[i].need;
+        if (promoted) promoted[i] = terms[i].promoted ? 1 : 0;
+        if (weights) weights[i] = terms[i].weight;
+    }
+    nsh_join_terms(terms, buf, cap);
+    if (min_should_out) *min_should_out = min_should;
+    return (uint32_t)terms.size();
+} NSH_CATCH(nullptr, "nsh_parse_boosted", 0)
+}
+
+extern "C" int nsh_engine_search_boosted_after_batch(nsh_engine* e, const nsh_boost_spec* spec, uint32_t filter_handle, const char* const* queries, uint32_t n_queries,
+                                                     int k, const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                                     uint8_t* has_found, float* device_ms_out) { try {
+    if (!e) return -1;
+    nsx::BoostSpec sp;
+    std::string why;
+    bool have = false;
+    if (!nsh_boost_spec_of(e, spec, sp, have, why)) { nsh_set_err(e, why); return -1; }
+    return nsh_after_batch(e, "nsh_engine_search_boosted_after_batch", nsx::PageSpec::Boosted, nullptr, filter_handle, queries, n_queries, k, 0u, after, hits, nullptr, nhits, found, rest,
+                           has_found, device_ms_out, have ? &sp : nullptr);
+} NSH_CATCH(e, "nsh_engine_search_boosted_after_batch", -1)
+}
+
+extern "C" int nsh_engine_search_boosted_json(nsh_engine* e, const char* query, int k, const nsh_boost_spec* spec, int use_filter, const char* date_from,
+                                              const char* date_to, int keep_undated, char** json_out) { try {
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::BoostSpec sp;
+        bool have = false;
+        return nsh_boost_spec_of(e, spec, sp, have, s) && e->eng.search_boosted_text(query ? query : "", k, have ? &sp : nullptr, f, s);
+    });
+} NSH_CATCH(e, "nsh_engine_search_boosted_json", -1)
+}
+
+extern "C" int nsh_engine_search_boosted_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, int use_filter,
+                                                   const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::PageSpec ps;
+    ps.mode = nsx::PageSpec::Boosted;
+    bool ok = nsh_boost_spec_of(e, spec, ps.boost, ps.use_boost, s);
+    if (ok) {
+        ps.use_filter = use_filter != 0;
+        if (ps.use_filter) ps.filter = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_page_text(query ? query : "", k, cursor ? cursor : "", ps, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_boosted_page_json", -1)
+}
+
 static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, nsx::Dialect dialect, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;
@@ -1393,7 +1497,7 @@ extern "C" int nsh_engine_search_page_json(nsh_engine* e, const char* query, int
     *json_out = nullptr;
     std::string s;
     nsx::PageSpec ps;
-    bool ok = mode <= 8u;
+    bool ok = mode <= 9u;   // (9: boosted without a spec; nsh_engine_search_boosted_page_json takes one)
     if (!ok) s = "search_page: unknown mode " + std::to_string(mode);
     if (ok) {
         ps.mode = (nsx::PageSpec::Mode)mode;

@@ -36,6 +36,9 @@
 //   ns_tool search-quorum-sorted <index_dir> <newest|oldest> <from> <to> <k> <query words ...>    (needs an MI355X)
 //        Engine::search_quorum, search_quorum_faceted, search_quorum_sorted: the grouped bodies with "quorum" in place of "grouped".
 //        The page modes quorum, quorum-newest and quorum-oldest page them.
+//   ns_tool search-boosted <index_dir> <none|exponential|linear> <weight> <scale_days> <offset_days> <origin|-> <from> <to> <k> <query words ...>   (needs an MI355X; `+(a b)^0.5 c^2.5`)
+//        Engine::search_boosted: search-quorum's body with "boosted" in place of "quorum" and, unless the decay is none, "boost";
+//        relevance times a recency factor per document (host/boost.hpp); undated documents keep their score.
 //   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest|grouped|grouped-newest|grouped-oldest|quorum|quorum-newest|quorum-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
 //        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
 //        "remaining"} (page.hpp).  cursor: "-" for the first page, else a page's "next".  from / to as search-filtered's.
@@ -153,6 +156,30 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 6; i < argc; i++) { if (i > 6) q.push_back(' '); q += argv[i]; }
         if (!eng.search_dialect_text(dialect, q, k, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "%s failed: %s\n", argv[1], body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 12 && std::strcmp(argv[1], "search-boosted") == 0) {
+        nsx::BoostSpec spec;
+        const bool boosted = std::strcmp(argv[3], "none") != 0;
+        if (std::strcmp(argv[3], "exponential") == 0) spec.kind = nsx::BoostSpec::Exponential;
+        else if (std::strcmp(argv[3], "linear") == 0) spec.kind = nsx::BoostSpec::Linear;
+        else if (boosted) { std::fprintf(stderr, "search-boosted: the decay is none, exponential or linear, not %s\n", argv[3]); return 2; }
+        spec.weight = std::atof(argv[4]);
+        spec.scale_days = std::atof(argv[5]);
+        spec.offset_days = std::atof(argv[6]);
+        if (std::strcmp(argv[7], "-") != 0) spec.origin = argv[7];
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[8], "-") != 0 || std::strcmp(argv[9], "-") != 0;
+        if (std::strcmp(argv[8], "-") != 0) f.date_from = argv[8];
+        if (std::strcmp(argv[9], "-") != 0) f.date_to = argv[9];
+        const int k = std::atoi(argv[10]);
+        std::string q, body;
+        for (int i = 11; i < argc; i++) { if (i > 11) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_boosted_text(q, k, boosted ? &spec : nullptr, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boosted failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

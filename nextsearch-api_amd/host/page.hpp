@@ -16,6 +16,7 @@
 #include <string>
 
 #include "boolean.hpp"
+#include "boost.hpp"
 #include "sorted.hpp"
 
 namespace nsx {
@@ -29,8 +30,10 @@ struct PageCursor {
 
 // which call a page is a page of
 struct PageSpec {
-    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6, Quorum = 7, QuorumSorted = 8 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u; Quorum*: §5w
+    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6, Quorum = 7, QuorumSorted = 8, Boosted = 9 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u; Quorum*: §5w; Boosted: §5z
     Mode mode = SearchOr;
+    bool use_boost = false;              // Boosted only: false = term weights alone
+    BoostSpec boost;
     SortSpec sort;                       // Sorted, BooleanSorted, GroupedSorted and QuorumSorted only
     bool use_filter = false;
     DocFilter filter;
@@ -46,6 +49,7 @@ inline PageCall page_call(PageSpec::Mode m) {
         case PageSpec::GroupedSorted: return {false, Dialect::Grouped, true};
         case PageSpec::Quorum: return {false, Dialect::Quorum, false};
         case PageSpec::QuorumSorted: return {false, Dialect::Quorum, true};
+        case PageSpec::Boosted: return {false, Dialect::Boosted, false};
         default: return {true, Dialect::Boolean, false};   // SearchOr, SearchAnd
     }
 }

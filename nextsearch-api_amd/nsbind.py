@@ -56,7 +56,7 @@ assert HIT_DTYPE.itemsize == C.sizeof(NsHit) == 12
 assert TERM_DTYPE.itemsize == C.sizeof(NsTermRef) == 24
 assert QDESC_DTYPE.itemsize == C.sizeof(NsQueryDesc) == 8
 PAGE_CURSOR_DTYPE = np.dtype([("set", "<u4"), ("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4")])   # nsh_page_cursor: seg is a manifest position
-PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4, "grouped": 5, "grouped_sorted": 6, "quorum": 7, "quorum_sorted": 8}
+PAGE_MODES = {"or": 0, "and": 1, "boolean": 2, "sorted": 3, "boolean_sorted": 4, "grouped": 5, "grouped_sorted": 6, "quorum": 7, "quorum_sorted": 8, "boosted": 9}
 CURSOR_DTYPE = np.dtype([("rank", "<u4"), ("seg", "<u4"), ("doc", "<u4"), ("set", "<u4")])   # ns_cursor
 
 # every symbol include/nextsearch_hip.h declares
@@ -67,6 +67,7 @@ HIP_SYMBOLS = [
     "ns_facet_count_boolean", "ns_search_sorted_boolean", "ns_boolean_sets_kernel_ms",
     "ns_search_grouped_after", "ns_facet_count_grouped", "ns_search_sorted_grouped", "ns_grouped_kernel_ms",
     "ns_search_quorum_after", "ns_facet_count_quorum", "ns_search_sorted_quorum", "ns_quorum_kernel_ms",
+    "ns_docboost_upload", "ns_docboost_release", "ns_search_boosted_after", "ns_boosted_kernel_ms",
     "ns_segment_filter",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -88,6 +89,8 @@ HOST_SYMBOLS = [
     "nsh_engine_search_grouped_json", "nsh_engine_search_grouped_faceted_json", "nsh_engine_search_grouped_sorted_json",
     "nsh_parse_quorum", "nsh_engine_search_quorum_after_batch", "nsh_engine_facet_quorum_batch", "nsh_engine_search_quorum_sorted_batch",
     "nsh_engine_search_quorum_json", "nsh_engine_search_quorum_faceted_json", "nsh_engine_search_quorum_sorted_json",
+    "nsh_engine_boost_table", "nsh_engine_release_boosts", "nsh_engine_boost_tables_on_device", "nsh_parse_boosted", "nsh_engine_search_boosted_after_batch",
+    "nsh_engine_search_boosted_json", "nsh_engine_search_boosted_page_json",
     "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
@@ -163,6 +166,14 @@ class NshSortSpec(C.Structure):   # include/nextsearch_host.h nsh_sort_spec
 
 
 SORT_ORDERS = {"newest": (0, 0), "oldest": (0, 1)}   # name -> (kind, ascending); custom keys: kind 1
+
+
+class NshBoostSpec(C.Structure):   # include/nextsearch_host.h nsh_boost_spec
+    _fields_ = [("kind", C.c_uint32), ("weight", C.c_double), ("origin", C.c_char_p), ("scale_days", C.c_double), ("offset_days", C.c_double),
+                ("undated", C.c_double), ("custom", C.c_void_p), ("n_custom", C.c_uint64)]
+
+
+BOOST_KINDS = {"custom": 0, "exponential": 1, "linear": 2}
 
 _hip = None
 _host = None
@@ -279,6 +290,11 @@ def hip_lib():
         L.ns_facet_count_quorum.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
         L.ns_search_sorted_quorum.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         L.ns_quorum_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        if hasattr(L, "ns_search_boosted_after"):   # (an A/B run may load a library from before the boost factors: NS_HIP_LIB)
+            L.ns_docboost_upload.argtypes = [vp, u32, vp, C.POINTER(vp)]
+            L.ns_docboost_release.argtypes = [vp, vp]
+            L.ns_search_boosted_after.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
+            L.ns_boosted_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -291,7 +307,7 @@ DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_deb
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
                   "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
                   "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11,
-                  "ns_debug_boolean_quorum_counters": 12}
+                  "ns_debug_boolean_quorum_counters": 12, "ns_debug_boolean_boost_counters": 8}
 
 
 def debug_counters(reset=False):
@@ -484,6 +500,19 @@ def host_lib():
         L.nsh_parse_quorum.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, vp, vp, u32, vp]
         L.nsh_parse_quorum.restype = u32
         L.nsh_engine_search_quorum_after_batch.argtypes = L.nsh_engine_search_boolean_after_batch.argtypes
+        if hasattr(L, "nsh_engine_boost_table"):   # (an A/B run may load a host library from before the boosts)
+            bsp = C.POINTER(NshBoostSpec)
+            L.nsh_engine_boost_table.argtypes = [vp, bsp, vp, C.c_uint64]
+            L.nsh_engine_boost_table.restype = C.c_int64
+            L.nsh_engine_release_boosts.argtypes = [vp]
+            L.nsh_engine_release_boosts.restype = None
+            L.nsh_engine_boost_tables_on_device.argtypes = [vp]
+            L.nsh_engine_boost_tables_on_device.restype = C.c_uint64
+            L.nsh_parse_boosted.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, vp, vp, vp, u32, vp]
+            L.nsh_parse_boosted.restype = u32
+            L.nsh_engine_search_boosted_after_batch.argtypes = [vp, bsp] + L.nsh_engine_search_boolean_after_batch.argtypes[1:]
+            L.nsh_engine_search_boosted_json.argtypes = [vp, C.c_char_p, i32, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+            L.nsh_engine_search_boosted_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_facet_quorum_batch.argtypes = L.nsh_engine_facet_boolean_batch.argtypes
         L.nsh_engine_search_quorum_sorted_batch.argtypes = L.nsh_engine_search_boolean_sorted_batch.argtypes
         L.nsh_engine_search_quorum_json.argtypes = L.nsh_engine_search_boolean_json.argtypes
@@ -1098,6 +1127,77 @@ class Engine:
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         return self._json_call("search_quorum_sorted", self._L.nsh_engine_search_quorum_sorted_json, _as_bytes(query), k, C.byref(sp),
                                int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    # ---- boosts: per-document factors, recency decay and term^w ----
+    @staticmethod
+    def _boost_spec(boost):
+        """boost: None (term weights only), or a dict: kind "exponential" | "linear" with weight, origin, scale_days, offset_days,
+        undated (defaults 1.0, "", 365.0, 0.0, 1.0), or kind "custom" with custom = one float32 factor array per segment
+        -> (pointer or None, what must stay alive)"""
+        if boost is None:
+            return None, None
+        sp = NshBoostSpec()
+        sp.kind = BOOST_KINDS[boost.get("kind", "exponential")]
+        sp.weight, sp.scale_days = float(boost.get("weight", 1.0)), float(boost.get("scale_days", 365.0))
+        sp.offset_days, sp.undated = float(boost.get("offset_days", 0.0)), float(boost.get("undated", 1.0))
+        origin = _as_bytes(boost.get("origin", ""))
+        sp.origin = origin
+        keep = None
+        if sp.kind == 0:
+            custom = boost["custom"]
+            keep = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float32) for c in custom]) if len(custom) else np.zeros(0, np.float32))
+            sp.custom, sp.n_custom = (keep.ctypes.data if len(keep) else None), len(keep)
+        return C.byref(sp), (sp, origin, keep)
+
+    def boost_table(self, boost):
+        """Engine::boost_table (host only): [one float32 factor array per segment]"""
+        sp, keep = self._boost_spec(boost)
+        sizes = [self.segment_info(s)["n_docs"] for s in range(self.num_segments)]
+        flat = np.zeros(max(sum(sizes), 1), dtype=np.float32)
+        n = self._L.nsh_engine_boost_table(self.h, sp, flat.ctypes.data, len(flat))
+        if n < 0:
+            raise RuntimeError(f"boost_table failed: {self.error()}")
+        out, at = [], 0
+        for m in sizes:
+            out.append(flat[at:at + m].copy())
+            at += m
+        return out
+
+    def search_boosted_after_batch(self, queries, k, boost=None, after=None, handle=0, timing=False):
+        """Engine::search_boosted_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_quorum_after_batch over
+        `term^w` texts, the scores multiplied by the boost's factor per document; a cursor's rank is a product's bits"""
+        sp, keep = self._boost_spec(boost)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_boosted_after_batch(self.h, sp, int(handle), _cstr_array(queries), Q, int(k), cu.ctypes.data if cu is not None and Q else None,
+                                                           hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_boosted_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_boosted_json(self, query, k, boost=None, date_filter=None, check=True):
+        """Engine::search_boosted: the JSON text; as search_quorum_json, with "boosted" and (with a boost) "boost" """
+        sp, keep = self._boost_spec(boost)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_boosted", self._L.nsh_engine_search_boosted_json, _as_bytes(query), k, sp, int(date_filter is not None), _as_bytes(df),
+                               _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_boosted_page_json(self, query, k, cursor="", boost=None, date_filter=None, check=True):
+        """Engine::search_page in mode Boosted: one page of search_boosted_json's ranking; cursor: "" or a page's "next" """
+        sp, keep = self._boost_spec(boost)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_page", self._L.nsh_engine_search_boosted_page_json, _as_bytes(query), k, _as_bytes(cursor), sp,
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    def release_boosts(self):
+        self._L.nsh_engine_release_boosts(self.h)
+
+    def boost_tables_on_device(self):
+        return int(self._L.nsh_engine_boost_tables_on_device(self.h))
 
     def _json_call(self, name, fn, *args, check=True):
         out = C.c_void_p()
@@ -2008,6 +2108,22 @@ def parse_grouped(text):
     return [(w, int(r), int(c)) for w, r, c in zip(words, roles[:n], clauses[:n])]
 
 
+def parse_boosted(text):
+    """nsx::parse_boosted (host only): ([(term, role, clause, need, promoted, weight)], min_should); as parse_quorum's, with the
+    `^w` of the term's piece (1.0 without one)"""
+    b = _as_bytes(text)
+    cap = len(b) + 1
+    buf = C.create_string_buffer(cap)
+    roles, clauses, needs, promoted = np.zeros(cap, np.uint8), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+    weights = np.zeros(cap, np.float32)
+    m = C.c_uint32()
+    n = int(host_lib().nsh_parse_boosted(b, buf, cap, roles.ctypes.data, clauses.ctypes.data, needs.ctypes.data, promoted.ctypes.data, weights.ctypes.data, cap,
+                                         C.addressof(m)))
+    terms = buf.value.decode().split(" ") if n else []
+    assert len(terms) == n
+    return [(terms[i], int(roles[i]), int(clauses[i]), int(needs[i]), bool(promoted[i]), float(weights[i])) for i in range(n)], int(m.value)
+
+
 def parse_quorum(text):
     """nsx::parse_quorum (host only): ([(term, role, clause, need, promoted)], min_should); need is that of a MUST term's clause, 0 on
     SHOULD and NOT terms; promoted: an optional term that a `~m` piece made a member of the last clause"""
@@ -2362,6 +2478,57 @@ def quorum_kernel_ms(reset=True):
     calls that were given needs, since the last reset"""
     out = (C.c_float * 6)()
     hip_lib().ns_quorum_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+def docboost_upload(ctx, boost):
+    """ns_docboost_upload (raw): (rc, handle); boost: one fp32 factor per document (finite, no sign bit; the bytes go up as
+    they are, so a float32 array keeps its NaN payloads and its -0.0)"""
+    a = np.ascontiguousarray(boost, dtype=np.float32)
+    h = C.c_void_p()
+    rc = hip_lib().ns_docboost_upload(ctx, len(a), a.ctypes.data if len(a) else None, C.byref(h))
+    return rc, h
+
+
+def docboost_release(ctx, table):
+    return hip_lib().ns_docboost_release(ctx, table)
+
+
+def search_boosted_after_raw(ctx, qd, refs, roles, clauses, needs, k, after, seg_ids, segs, boosts):
+    """ns_search_boosted_after (raw): (rc, hits Q x K, nhits, found, rest, device ms); boosts: a list of ns_docboost handles, one
+    per listed segment (an entry may be None), or None (the quorum sibling); the rest as search_quorum_after_raw.  The outputs
+    are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ba = None if boosts is None else (C.c_void_p * max(len(boosts), 1))(*[b.value if isinstance(b, C.c_void_p) else b for b in boosts])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl, ne = _clauses(clauses), _needs(needs)
+    cu = None if after is None else np.ascontiguousarray(after, dtype=CURSOR_DTYPE)
+    assert cu is None or len(cu) == Q
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    rest = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_boosted_after(ctx, qd.ctypes.data if Q else None, Q, _ptr(refs), _ptr(ro), _ptr(cl), _ptr(ne), len(refs), int(k), _ptr(cu),
+                                           _ptr(ids), sa, ba, len(ids), hits.ctypes.data, nhits.ctypes.data, found.ctypes.data, rest.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], nhits[:Q], found[:Q], rest[:Q], float(ms.value)
+
+
+BOOST_EVENTS = ["items", "items_swept", "documents_multiplied", "keys_clipped", "windows_all_zero", "items_boolean", "items_grouped", "items_quorum"]
+
+
+def boost_counters(reset=True):
+    """ns_debug_boolean_boost_counters of the counting build as {name: value}; None for a library without them"""
+    c = debug_counters(reset=reset).get("ns_debug_boolean_boost_counters")
+    return None if c is None else dict(zip(BOOST_EVENTS, c))
+
+
+def boosted_kernel_ms(reset=True):
+    """(k_bq_select, k_bq_join) HIP-event ms summed over this thread's ns_search_boosted_after calls that were given tables"""
+    out = (C.c_float * 2)()
+    hip_lib().ns_boosted_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
