@@ -552,6 +552,26 @@ void ns_docterms_destroy(ns_docterms* h);
 /* Documents of at most this many pairs are streamed by one wave, longer ones by a workgroup (the tests' size classes; a
  * document of at most 64 pairs is one chunk of the wave's stream). */
 uint32_t ns_docterms_doc_cut(void);
+/* Related terms (csrc/ns_terms.hip, csrc/ns_terms_plan.hpp): what a SET of documents is about.  Row i is
+ * the documents doc_ids[row_off[i] .. row_off[i + 1]) of the handle's segment; the call sorts them and drops repeats, so a
+ * document named twice counts once.  RULE (host/related.hpp is the authority): fg[t] = the row's documents that hold a
+ * pair (t, tf) with tf >= max(min_tf, 1); t qualifies when fg[t] >= max(min_docs, 1), min_df <= df[t] <= max_df,
+ * df[t] >= 1 and 0 < idf[t] < inf; w = (float)fg[t] * idf[t], one fp32 multiply; the selection is the first
+ * T = clamp(max_terms, 1, 64) qualifying terms by (bit pattern of w descending, termId ascending).
+ * Outputs: term_out / docs_out (= fg) / w_out [i * T + r] for r < count_out[i], ~0u, 0 and 0.0f past the count;
+ * ndocs_out[i] = the distinct documents of row i.  An empty row is valid (count 0).  Synchronous; device_ms_out (may be
+ * NULL): the counting kernel's time.  n_rows == 0 returns NS_OK.  NS_E_INVAL with a message, and nothing launched, for a
+ * NULL argument, a row_off that does not start at 0 or descends, a doc id >= n_docs and a row of more than
+ * ns_docterms_max_row_docs() distinct documents (the device counts in bytes).  The counting needs every document's term
+ * ids strictly ascending, the order ns_forward_fetch gives: the first call checks the handle once with a kernel and
+ * remembers the answer; a handle that fails is refused here with NS_E_INVAL (ns_docterms_select still answers it).  An
+ * orphaned handle returns NS_E_STATE. */
+int ns_docterms_aggregate(ns_docterms* h, const uint32_t* doc_ids, const uint64_t* row_off /* n_rows + 1 */, uint32_t n_rows,
+                          uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df,
+                          uint32_t* term_out, uint32_t* docs_out, float* w_out /* n_rows * T each */,
+                          uint32_t* count_out, uint32_t* ndocs_out /* n_rows each */, float* device_ms_out);
+uint32_t ns_docterms_window(void);          /* term ids per window of the counting kernel's LDS table */
+uint32_t ns_docterms_max_row_docs(void);    /* 255 */
 
 /* ---- facet counts (csrc/ns_facet.hip, csrc/ns_facet_plan.hpp) ------------------ */
 /* A per-document bucket table on the device, independent of any ns_seg: bucket_of_doc[n_docs], each < n_buckets,

@@ -305,6 +305,32 @@ int nsh_engine_more_like_this_json(nsh_engine* e, const char* uid, uint64_t uid_
 void nsh_engine_release_similar(nsh_engine* e);
 uint64_t nsh_engine_similar_segments_on_device(nsh_engine* e);
 
+/* Related terms (host/related.hpp is the rule, csrc/ns_terms.hip runs it on the device).
+ * nsh_related_aggregate_host: the rule on one host thread, over the arrays ns_docterms_upload / ns_docterms_aggregate take:
+ * counts[n_docs] and pairs (u32 {termId, tf} x n_pairs), df[n_terms] / idf[n_terms] by term id, row i = doc_ids[row_off[i] ..
+ * row_off[i + 1]); term_out / docs_out / w_out n_rows x T with T = clamp(max_terms, 1, 64), count_out / ndocs_out[n_rows];
+ * rows padded with ~0u / 0 / 0.0f.  -1 for counts that do not sum to n_pairs, a bad row_off, a doc id >= n_docs, a termId
+ * >= n_terms, a row of more than 255 distinct documents and a visited document whose term ids do not ascend. */
+int nsh_related_aggregate_host(const uint32_t* counts, uint32_t n_docs, const uint32_t* pairs, uint64_t n_pairs, const uint32_t* df,
+                               const float* idf, uint32_t n_terms, const uint32_t* doc_ids, const uint64_t* row_off, uint32_t n_rows,
+                               uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df,
+                               uint32_t* term_out, uint32_t* docs_out, float* w_out, uint32_t* count_out, uint32_t* ndocs_out);
+/* Engine::terms_batch: row q = the (manifest position, docId) pairs seg_doc[2j], seg_doc[2j + 1] for j in row_off[q] ..
+ * row_off[q + 1].  With To = clamp(max_terms, 1, 32): docs_out / df_out / w_out n_rows x To (0 past count_out[q]),
+ * ndocs_out[n_rows]; optional, malloc'ed (nsh_free): *term_bytes_out / *term_offsets_out, the terms of all rows back to back,
+ * row-major in rank order, sum(count_out) + 1 offsets.  device_ms_out may be NULL.  -1 for a pair out of range or a bad
+ * row_off (nothing runs), a row over the cap, a segment without forward files, no device, or on failure. */
+int nsh_engine_terms_batch(nsh_engine* e, const uint32_t* seg_doc, const uint64_t* row_off, uint64_t n_rows, uint32_t max_terms,
+                           uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df, uint32_t* docs_out, uint64_t* df_out,
+                           float* w_out, uint32_t* count_out, uint32_t* ndocs_out, char** term_bytes_out, uint64_t** term_offsets_out,
+                           float* device_ms_out);
+/* Engine::related_terms: *json_out receives {"found", "query", "sample", "segments", "terms": [{"df", "docs", "term",
+ * "weight"}]} in dump(2) layout (free with nsh_free).  filtered != 0: the search runs under the date filter (date_from,
+ * date_to, keep_undated) as nsh_engine_search_filtered_json's.  -1 on failure (nsh_engine_error has the message). */
+int nsh_engine_related_terms_json(nsh_engine* e, const char* query, uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df,
+                                  uint32_t max_df, uint32_t sample, int filtered, const char* date_from, const char* date_to,
+                                  int keep_undated, char** json_out);
+
 /* ---- filtered search (host/filter.hpp) ----
  * nsh_date_key: "YYYY", "YYYY-MM" (01..12) or "YYYY-MM-DD" (01..31), blanks stripped -> Y * 10000 + M * 100 + D with the
  * missing parts 0; anything else 0 = undated.

@@ -29,6 +29,8 @@
 #include "ns_filter.hip"
 #include "ns_facet.hip"
 #include "ns_similar.hip"
+#include "ns_terms.hip"     // after ns_similar.hip (ml_shfl, ml_sort_up, ml_join)
+#include "ns_terms_plan.hpp"
 #include "ns_sorted.hip"   // after ns_facet.hip (fc_cut, fc_mark, fc_lower_bound) and ns_similar.hip (ml_sort_up, ml_merge_down, ml_join)
 #include "ns_boolean.hip"  // after ns_sorted.hip (SdSet, sd_insert) and ns_facet.hip (fc_cut, fc_mark)
 #include "ns_boolean_sets.hip"  // after ns_boolean.hip (BqRef), ns_sorted.hip (SdSet, sd_key, sd_insert, DevSdSeg, af_clip) and ns_facet.hip
@@ -2512,6 +2514,7 @@ struct ns_docterms {
     uint32_t* d_off = nullptr;      // n_docs + 1
     uint32_t* d_df = nullptr;       // n_terms
     float* d_idf = nullptr;         // n_terms
+    int ordered = -1;               // ns_docterms_aggregate: -1 not looked at yet, 1 every document's term ids ascend, 0 one does not (k_ta_order)
 };
 
 static void docterms_free_device(ns_docterms* h) {
@@ -2636,6 +2639,98 @@ extern "C" int ns_docterms_select(ns_docterms* h, const uint32_t* doc_ids, uint3
         blk.sync();
         float ms = 0.0f;
         if (device_ms_out && blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
+    }
+    return blk.finish(fn);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Related terms: what a set of documents is about (csrc/ns_terms.hip, csrc/ns_terms_plan.hpp)
+extern "C" uint32_t ns_docterms_window(void) {
+#ifdef NS_VARIANTS
+    if (std::getenv("NS_TERMS_WINDOW_15")) return 1u << 15;             // the A/B knob below (variants build only)
+#endif
+    return 1u << kTaWindowLog2;
+}
+extern "C" uint32_t ns_docterms_max_row_docs(void) { return kTaMaxRowDocs; }
+#ifdef NS_COUNT
+static unsigned long long g_ta_rows_refused = 0;   // rows over the cap (they never reach the device)
+#endif
+
+extern "C" int ns_docterms_aggregate(ns_docterms* h, const uint32_t* doc_ids, const uint64_t* row_off, uint32_t n_rows, uint32_t max_terms,
+                                     uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df, uint32_t* term_out,
+                                     uint32_t* docs_out, float* w_out, uint32_t* count_out, uint32_t* ndocs_out, float* device_ms_out) {
+    const char* fn = "ns_docterms_aggregate";
+    if (!h) return fail(nullptr, NS_E_INVAL, "%s: handle is NULL", fn);
+    ns_ctx* ctx = h->ctx;
+    if (!ctx) return fail(nullptr, NS_E_STATE, "%s: the handle's ctx has been destroyed", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_rows == 0) return NS_OK;
+    if (!row_off || !term_out || !docs_out || !w_out || !count_out || !ndocs_out) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    // nothing is launched before row_off and every doc id have been checked and every row fits the byte counters
+    TermsPlan plan;
+    std::string why;
+    bool planned = false;
+    if (row_off[0] == 0 && row_off[n_rows] != 0 && !doc_ids) why = "null argument";
+    else planned = terms_plan(doc_ids, row_off, n_rows, h->doc_off.data(), h->n_docs, plan, why);
+#ifdef NS_COUNT
+    g_ta_rows_refused += plan.over_cap;
+#endif
+    if (!planned) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const uint32_t T = std::max(1u, std::min(max_terms, kTaMaxTerms));
+    const TaRule rule{std::max(1u, min_tf), std::max(1u, min_docs), min_df, max_df};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (h->ordered < 0) {   // once per handle: do the term ids of every document ascend?
+        CallBlock chk(ctx);
+        const size_t o_bad = chk.reserve(4);
+        chk.alloc(0);
+        uint32_t bad = 0;
+        if (chk.ok()) {
+            chk.zero(o_bad, 4);
+            if (chk.ok() && h->n_pairs > 1) hipLaunchKernelGGL(k_ta_order, dim3((h->n_pairs + 255) / 256), dim3(256), 0, st, h->d_pairs, h->n_pairs, h->d_off, h->n_docs, chk.at<uint32_t>(o_bad));
+            chk.launched();
+            chk.fetch(&bad, o_bad, 4);
+            chk.sync();
+        }
+        const bool ok = chk.ok();
+        const int rc = chk.finish(fn);
+        if (rc != NS_OK) return rc;
+        if (ok) h->ordered = bad ? 0 : 1;
+    }
+    if (h->ordered != 1)
+        return fail(ctx, NS_E_INVAL, "%s: a document of this handle does not hold its term ids in strictly ascending order (the order ns_forward_fetch gives); the counting needs it", fn);
+    const size_t n_docs_all = plan.docs.size();
+    CallBlock blk(ctx);
+    const size_t o_docs = blk.reserve(std::max<size_t>(n_docs_all, 1) * 4), o_first = blk.reserve(((size_t)n_rows + 1) * 4), o_order = blk.reserve((size_t)n_rows * 4),
+                 o_term = blk.reserve((size_t)n_rows * T * 4), o_fg = blk.reserve((size_t)n_rows * T * 4), o_w = blk.reserve((size_t)n_rows * T * 4),
+                 o_cnt = blk.reserve((size_t)n_rows * 4);
+    blk.alloc(2);
+    if (blk.ok()) {
+        blk.upload(o_docs, plan.docs.data(), n_docs_all * 4);
+        blk.upload(o_first, plan.first.data(), ((size_t)n_rows + 1) * 4);
+        blk.upload(o_order, plan.order.data(), (size_t)n_rows * 4);
+        blk.record(0);
+        if (blk.ok()) {
+            const uint32_t *d_docs = blk.at<uint32_t>(o_docs), *d_first = blk.at<uint32_t>(o_first), *d_order = blk.at<uint32_t>(o_order);
+            uint32_t *d_term = blk.at<uint32_t>(o_term), *d_fg = blk.at<uint32_t>(o_fg), *d_w = blk.at<uint32_t>(o_w), *d_cnt = blk.at<uint32_t>(o_cnt);
+#ifdef NS_VARIANTS
+            // A/B knob (variants build only): the other window size; same rows
+            if (std::getenv("NS_TERMS_WINDOW_15"))
+                hipLaunchKernelGGL((k_ta_count<15>), dim3(n_rows), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, h->n_terms, d_docs, d_first, d_order, rule, T, d_term, d_fg, d_w, d_cnt);
+            else
+#endif
+            hipLaunchKernelGGL((k_ta_count<kTaWindowLog2>), dim3(n_rows), dim3(256), 0, st, h->d_pairs, h->d_off, h->d_df, h->d_idf, h->n_terms, d_docs, d_first, d_order, rule, T, d_term, d_fg, d_w, d_cnt);
+        }
+        blk.launched();
+        blk.record(1);
+        blk.fetch(term_out, o_term, (size_t)n_rows * T * 4);
+        blk.fetch(docs_out, o_fg, (size_t)n_rows * T * 4);
+        blk.fetch(w_out, o_w, (size_t)n_rows * T * 4);
+        blk.fetch(count_out, o_cnt, (size_t)n_rows * 4);
+        blk.sync();
+        float ms = 0.0f;
+        if (device_ms_out && blk.elapsed_ms(0, 1, &ms)) *device_ms_out = ms;
+        if (blk.ok()) for (uint32_t i = 0; i < n_rows; i++) ndocs_out[i] = plan.first[i + 1] - plan.first[i];
     }
     return blk.finish(fn);
 }
@@ -4050,4 +4145,11 @@ extern "C" int ns_debug_boolean_boost_counters(unsigned long long* out, int rese
 extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBscnt>(HIP_SYMBOL(ns::g_ns_bscnt), out, reset); }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values
 extern "C" int ns_debug_fuzzy_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsZcnt>(HIP_SYMBOL(ns::g_ns_zcnt), out, reset); }
+// related terms (ns_terms.hip k_ta_count): 8 values; value 5, the rows refused over the cap, is counted on the host
+extern "C" int ns_debug_terms_counters(unsigned long long* out, int reset) {
+    const int rc = debug_counters<ns::kNsTacnt>(HIP_SYMBOL(ns::g_ns_tacnt), out, reset);
+    if (rc == 0 && out) out[5] = g_ta_rows_refused;
+    if (rc == 0 && reset) g_ta_rows_refused = 0;
+    return rc;
+}
 #endif

@@ -1695,6 +1695,171 @@ std::string Engine::more_like_this(const std::string& uid, int k) {
     return more_like_this_text(uid, k, body) ? body : error_body(body);
 }
 
+// ---- related terms (host/related.hpp, csrc/ns_terms.hip) ---------------------------------------------------
+bool Engine::related_rows(const std::pair<uint32_t, uint32_t>* seg_doc, const uint64_t* row_off, size_t Q, const nsx::RelatedOptions& opt,
+                          std::vector<std::vector<nsx::RelatedCand>>& rows, std::vector<uint32_t>& ndocs, float* device_ms) {
+    rows.clear();
+    ndocs.clear();
+    if (device_ms) *device_ms = 0.0f;
+    if (Q && (!row_off || (row_off[Q] && !seg_doc))) { err_ = "terms_batch: null argument"; return false; }
+    if (Q >= 0xFFFFFFFFull) { err_ = "terms_batch: too many rows"; return false; }
+    if (Q && row_off[0] != 0) { err_ = "terms_batch: row_off[0] is not 0"; return false; }
+    for (size_t q = 0; q < Q; q++)
+        if (row_off[q + 1] < row_off[q]) { err_ = "terms_batch: row_off[" + std::to_string(q + 1) + "] is below row_off[" + std::to_string(q) + "]"; return false; }
+    for (uint64_t j = 0; Q && j < row_off[Q]; j++)
+        if (seg_doc[j].first >= segments.size() || seg_doc[j].second >= segments[seg_doc[j].first].cord_uid.size()) {
+            err_ = "terms_batch: (segment " + std::to_string(seg_doc[j].first) + ", document " + std::to_string(seg_doc[j].second) + ") is not in the index";
+            return false;
+        }
+    if (!ctx_) { err_ = "terms_batch: no device context (the counting runs on the device; there is no CPU path)"; return false; }
+    rows.resize(Q);
+    ndocs.assign(Q, 0u);
+    if (Q == 0) return true;
+    const uint32_t S = (uint32_t)segments.size(), T = nsx::kRelatedMaxTerms;
+    const bool one = S == 1;                                           // the options reach the device as they are
+    const uint32_t dev_min_docs = one ? opt.min_docs : 1u, dev_min_df = one ? opt.min_df : 1u, dev_max_df = one ? opt.max_df : 0xFFFFFFFFu;
+    uint64_t N = 0;
+    for (const auto& seg : segments) N += seg.N;
+    struct Part { uint32_t docs = 0, first_pos = 0, term_id = 0; };
+    std::vector<std::unordered_map<std::string, Part>> acc(Q);
+    std::vector<uint32_t> which, ids, t_, g_, c_, n_;
+    std::vector<uint64_t> off;
+    std::vector<float> w_;
+    std::string key;
+    for (uint32_t s = 0; s < S; s++) {
+        which.clear(); ids.clear(); off.assign(1, 0ull);
+        for (size_t q = 0; q < Q; q++) {
+            const size_t before = ids.size();
+            for (uint64_t j = row_off[q]; j < row_off[q + 1]; j++)
+                if (seg_doc[j].first == s) ids.push_back(seg_doc[j].second);
+            if (ids.size() == before) continue;
+            which.push_back((uint32_t)q);
+            off.push_back(ids.size());
+        }
+        if (which.empty()) continue;
+        if (!ensure_similar(s)) return false;
+        const size_t R = which.size();
+        t_.resize(R * T); g_.resize(R * T); w_.resize(R * T); c_.resize(R); n_.resize(R);
+        float ms = 0.0f;
+        const int rc = ns_docterms_aggregate(similar_[s].dev, ids.data(), off.data(), (uint32_t)R, T, opt.min_tf, dev_min_docs, dev_min_df, dev_max_df,
+                                             t_.data(), g_.data(), w_.data(), c_.data(), n_.data(), &ms);
+        if (rc != NS_OK) { err_ = "ns_docterms_aggregate (segment " + seg_names[s] + "): " + ns_last_error(ctx_); return false; }
+        if (device_ms) *device_ms += ms;
+        const SimilarSeg& ss = similar_[s];
+        for (size_t i = 0; i < R; i++) {
+            ndocs[which[i]] += n_[i];
+            for (uint32_t r = 0; r < c_[i]; r++) {
+                const uint32_t t = t_[i * T + r];
+                key.assign((const char*)ss.term_bytes.data() + ss.term_offsets[t], (size_t)(ss.term_offsets[t + 1] - ss.term_offsets[t]));
+                auto ins = acc[which[i]].emplace(key, Part{0u, s, t});   // segments in manifest order: the first holder stays
+                ins.first->second.docs += g_[i * T + r];
+            }
+        }
+    }
+    const uint32_t need_docs = std::max(1u, opt.min_docs);
+    for (size_t q = 0; q < Q; q++) {
+        std::vector<nsx::RelatedCand>& out = rows[q];
+        for (const auto& kv : acc[q]) {
+            uint64_t df = 0;
+            for (const auto& seg : segments) {
+                const auto it = seg.lex.find(kv.first);
+                if (it != seg.lex.end()) df += it->second.df;
+            }
+            if (kv.second.docs < need_docs || df < 1 || df < opt.min_df || df > opt.max_df || df > 0xFFFFFFFFull) continue;
+            const float idf = bm25_idf((uint32_t)std::min<uint64_t>(N, 0xFFFFFFFFull), (uint32_t)df);
+            if (!(idf > 0.0f) || !(idf <= std::numeric_limits<float>::max())) continue;
+            nsx::RelatedCand c;
+            c.term = kv.first; c.docs = kv.second.docs; c.df = df; c.w = (float)kv.second.docs * idf;
+            c.first_pos = kv.second.first_pos; c.term_id = kv.second.term_id;
+            out.push_back(std::move(c));
+        }
+        nsx::related_merge_order(out);
+    }
+    return true;
+}
+
+bool Engine::terms_batch(const std::pair<uint32_t, uint32_t>* seg_doc, const uint64_t* row_off, size_t Q, const nsx::RelatedOptions& opt,
+                         uint32_t* docs_out, uint64_t* df_out, float* w_out, uint32_t* count_out, uint32_t* ndocs_out,
+                         std::vector<std::vector<std::string>>* terms_out, float* device_ms) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (terms_out) terms_out->clear();
+    if (Q && (!docs_out || !df_out || !w_out || !count_out || !ndocs_out)) { err_ = "terms_batch: null argument"; return false; }
+    std::vector<std::vector<nsx::RelatedCand>> rows;
+    std::vector<uint32_t> ndocs;
+    if (!related_rows(seg_doc, row_off, Q, opt, rows, ndocs, device_ms)) return false;
+    const uint32_t To = nsx::related_clamp_out(opt.max_terms);
+    if (terms_out) terms_out->assign(Q, {});
+    for (size_t q = 0; q < Q; q++) {
+        const uint32_t n = (uint32_t)std::min<size_t>(rows[q].size(), To);
+        for (uint32_t r = 0; r < To; r++) {
+            docs_out[q * To + r] = r < n ? rows[q][r].docs : 0u;
+            df_out[q * To + r] = r < n ? rows[q][r].df : 0ull;
+            w_out[q * To + r] = r < n ? rows[q][r].w : 0.0f;
+            if (terms_out && r < n) (*terms_out)[q].push_back(rows[q][r].term);
+        }
+        count_out[q] = n;
+        ndocs_out[q] = ndocs[q];
+    }
+    return true;
+}
+
+bool Engine::related_terms_text(const std::string& query, const nsx::RelatedOptions& opt, const nsx::DocFilter* f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    err_.clear();
+    if (!ctx_) { body = err_ = "related_terms: no device context (the search and the counting run on the device; there is no CPU path)"; return false; }
+    const int K = (int)nsx::related_clamp_sample(opt.sample);
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits((size_t)K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (f) {
+        nsx::DateRange r;
+        OpenFilter* of = lru_filter(*f, r);
+        if (!of) { body = err_; return false; }
+        if (!search_filtered_batch_flat(of->handle, &qv, 1, K, NS_FLAG_OR, hits.data(), &nh, &fd, &us)) { body = err_; return false; }
+    } else if (!search_batch_flat(&qv, 1, K, NS_FLAG_OR, hits.data(), &nh, &fd, &us)) { body = err_; return false; }
+    if (!us) { nh = 0; fd = 0; }
+    std::vector<std::pair<uint32_t, uint32_t>> row(nh);
+    for (uint32_t i = 0; i < nh; i++) row[i] = {hits[i].seg_id, hits[i].doc_id};
+    const uint64_t off[2] = {0, nh};
+    std::vector<std::vector<nsx::RelatedCand>> rows;
+    std::vector<uint32_t> ndocs;
+    if (!related_rows(row.data(), off, 1, opt, rows, ndocs, nullptr)) { body = err_; return false; }
+    const std::vector<std::string> own = base_terms(query);
+    const uint32_t To = nsx::related_clamp_out(opt.max_terms);
+    std::vector<const nsx::RelatedCand*> keep;
+    for (const nsx::RelatedCand& c : rows[0]) {
+        if (keep.size() == To) break;
+        if (std::find(own.begin(), own.end(), c.term) == own.end()) keep.push_back(&c);
+    }
+    std::string& o = body;
+    o.clear();
+    o += "{\n  \"found\": " + std::to_string(fd) + ",\n  \"query\": ";
+    json_escape(o, query);
+    o += ",\n  \"sample\": " + std::to_string(nh) + ",\n  \"segments\": " + std::to_string(segments.size()) + ",\n";
+    if (keep.empty()) {
+        o += "  \"terms\": []\n}";
+        return true;
+    }
+    o += "  \"terms\": [\n";
+    for (size_t i = 0; i < keep.size(); i++) {
+        o += "    {\n      \"df\": " + std::to_string(keep[i]->df) + ",\n      \"docs\": " + std::to_string(keep[i]->docs) + ",\n      \"term\": ";
+        json_escape(o, keep[i]->term);
+        o += ",\n      \"weight\": ";
+        json_number_from_float(o, keep[i]->w);
+        o += i + 1 < keep.size() ? "\n    },\n" : "\n    }\n";
+    }
+    o += "  ]\n}";
+    return true;
+}
+
+std::string Engine::related_terms(const std::string& query, const nsx::RelatedOptions& opt, const nsx::DocFilter* f) {
+    std::string body;
+    return related_terms_text(query, opt, f, body) ? body : error_body(body);
+}
+
 // ---- filtered search (host/filter.hpp, csrc/ns_filter.hip) ------------------------------------------------
 bool Engine::filter_bits(const nsx::DocFilter& f, std::vector<std::vector<uint32_t>>& bits) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
@@ -1868,11 +2033,9 @@ bool Engine::search_filtered_batch_flat(uint32_t handle, const QueryView* querie
     return run_range(ctx_, queries, 0, Q, K, flags, hits, nhits, found, usable, /*pooled_prep*/ true, err_, rs);
 }
 
-bool Engine::search_filtered_text(const std::string& query, int k, const nsx::DocFilter& f, std::string& body) {
-    std::lock_guard<std::recursive_mutex> lock(mtx_);
-    if (!ctx_) { body = err_ = "search_filtered: no device context: this engine has no CPU scoring path"; return false; }
-    nsx::DateRange r;
-    if (!nsx::parse_filter(f, r, err_)) { body = err_; return false; }
+// search_filtered's and related_terms' cache of open filters: the last kFilterLru distinct filters stay open
+Engine::OpenFilter* Engine::lru_filter(const nsx::DocFilter& f, nsx::DateRange& r) {
+    if (!nsx::parse_filter(f, r, err_)) return nullptr;
     const std::string key = r.cache_key();
     OpenFilter* of = nullptr;
     for (auto it = filter_lru_.begin(); it != filter_lru_.end(); ++it)
@@ -1889,10 +2052,19 @@ bool Engine::search_filtered_text(const std::string& query, int k, const nsx::Do
         }
         nsx::DocFilter norm{r.from_text, r.to_text, r.keep_undated};
         uint32_t h = 0;
-        if (!open_filter(norm, h, nullptr)) { body = err_; return false; }
+        if (!open_filter(norm, h, nullptr)) return nullptr;
         filter_lru_.push_front(FilterLruEnt{key, h});
         of = filter_of(h);
     }
+    return of;
+}
+
+bool Engine::search_filtered_text(const std::string& query, int k, const nsx::DocFilter& f, std::string& body) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = "search_filtered: no device context: this engine has no CPU scoring path"; return false; }
+    nsx::DateRange r;
+    OpenFilter* of = lru_filter(f, r);
+    if (!of) { body = err_; return false; }
     const int K = std::max(1, std::min(k, 100));
     const QueryView qv{query.data(), query.size()};
     std::vector<ns_hit> hits((size_t)K);

@@ -32,6 +32,7 @@
 #include "index_format.hpp"
 #include "metadata.hpp"
 #include "semantic.hpp"
+#include "related.hpp"
 #include "similar.hpp"
 #include "correct.hpp"
 #include "filter.hpp"
@@ -260,6 +261,28 @@ public:
     size_t similar_segments_on_device() const;   // segments whose forward index has a device copy right now
     // df / idf by term id of segment seg as similar_batch uploads them (host only: works without a device)
     bool similar_term_stats(uint32_t seg, std::vector<uint32_t>& df, std::vector<float>& idf);
+
+    // Related terms (host/related.hpp, csrc/ns_terms.hip): what a set of documents is about.  Row q is the
+    // documents seg_doc[row_off[q] .. row_off[q + 1]) = (manifest position, docId), of any segments; a pair out of range or a
+    // row_off that does not start at 0 or descends is refused and nothing runs.  The rows are split by segment; every touched
+    // segment answers its parts with ONE ns_docterms_aggregate (max_terms = 64) over ensure_similar's handle, and the lists
+    // meet on the host by related.hpp's merge rule: docs summed, df summed over all loaded segments, idf = bm25_idf(N, df),
+    // w = (float)docs * idf.  With one loaded segment the options reach the device as they are and the answer is the device
+    // row; with several the device counts with min_docs 1 and no df bounds, and min_docs / min_df / max_df judge the summed
+    // numbers — a term that misses one segment's 64 is undercounted there (compact() makes it exact).  At most
+    // kRelatedMaxDocs distinct documents of a row per segment.  Outputs Q x To, To = clamp(opt.max_terms, 1, 32):
+    // docs_out / df_out / w_out [q * To + r] for r < count_out[q] (0 past it), ndocs_out[q] = the row's distinct documents,
+    // terms_out (may be null) the byte strings.  device_ms (may be null): the aggregate calls' kernel time summed.
+    bool terms_batch(const std::pair<uint32_t, uint32_t>* seg_doc, const uint64_t* row_off, size_t Q, const nsx::RelatedOptions& opt,
+                     uint32_t* docs_out, uint64_t* df_out, float* w_out, uint32_t* count_out, uint32_t* ndocs_out,
+                     std::vector<std::vector<std::string>>* terms_out = nullptr, float* device_ms = nullptr);
+    // JSON text {"found", "query", "sample", "segments", "terms": [{"df", "docs", "term", "weight"}]} in dump(2) layout: the
+    // plain search (under the filter when one is given) with K = clamp(opt.sample, 1, 100); its hits are one row ("sample" =
+    // how many); the terms the query's own tokens name are dropped before the cut, which keeps the answer exact for queries of
+    // at most 32 distinct terms (a segment's list holds 64).  No hits: "terms": [].  Any failure: {"error": ...}
+    // (related_terms_text: false, body = the message).
+    std::string related_terms(const std::string& query, const nsx::RelatedOptions& opt = {}, const nsx::DocFilter* f = nullptr);
+    bool related_terms_text(const std::string& query, const nsx::RelatedOptions& opt, const nsx::DocFilter* f, std::string& body);
 
     // Filtered search (host/filter.hpp, csrc/ns_filter.hip).  A filter is one keep-bitmap per segment, in
     // manifest order, ceil(N / 32) words each.  filter_bits: the bitmaps of a date filter from metadata.csv's publish_time
@@ -536,6 +559,11 @@ private:
     struct SimilarSeg { ns_docterms* dev = nullptr; std::vector<uint8_t> term_bytes; std::vector<uint64_t> term_offsets; };
     std::vector<SimilarSeg> similar_;
     bool ensure_similar(uint32_t seg);
+    // terms_batch's rows before the cut: per row every merged candidate, in the merge rule's order
+    bool related_rows(const std::pair<uint32_t, uint32_t>* seg_doc, const uint64_t* row_off, size_t Q, const nsx::RelatedOptions& opt,
+                      std::vector<std::vector<nsx::RelatedCand>>& rows, std::vector<uint32_t>& ndocs, float* device_ms);
+    struct OpenFilter;
+    OpenFilter* lru_filter(const nsx::DocFilter& f, nsx::DateRange& r);   // search_filtered's cache of open filters; nullptr: err_ is set
     void append_results_json(std::string& o, const std::vector<SearchHit>& hits) const;
     std::vector<ns_seg*> dev_segs_;
     // further devices holding a replica of the index (multi-device engine): context + segments each

@@ -758,6 +758,76 @@ static nsx::DocFilter nsh_doc_filter(const char* from, const char* to, int keep_
     f.keep_undated = keep_undated != 0;
     return f;
 }
+
+// ---- related terms ----
+extern "C" int nsh_related_aggregate_host(const uint32_t* counts, uint32_t n_docs, const uint32_t* pairs, uint64_t n_pairs, const uint32_t* df,
+                                          const float* idf, uint32_t n_terms, const uint32_t* doc_ids, const uint64_t* row_off, uint32_t n_rows,
+                                          uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df,
+                                          uint32_t* term_out, uint32_t* docs_out, float* w_out, uint32_t* count_out, uint32_t* ndocs_out) { try {
+    if ((n_docs && !counts) || (n_pairs && !pairs) || (n_terms && (!df || !idf))) return -1;
+    if (n_rows && (!row_off || !term_out || !docs_out || !w_out || !count_out || !ndocs_out || (row_off[n_rows] && !doc_ids))) return -1;
+    std::vector<uint64_t> off((size_t)n_docs + 1, 0);
+    for (uint32_t d = 0; d < n_docs; d++) off[d + 1] = off[d] + counts[d];
+    if (off[n_docs] != n_pairs) return -1;
+    return nsx::related_aggregate_host(off.data(), n_docs, pairs, df, idf, n_terms, doc_ids, row_off, n_rows, max_terms, min_tf, min_docs, min_df, max_df,
+                                       term_out, docs_out, w_out, count_out, ndocs_out);
+} catch (...) { return -1; }
+}
+
+static nsx::RelatedOptions nsh_related_options(uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df, uint32_t sample) {
+    nsx::RelatedOptions o;
+    o.max_terms = max_terms; o.min_tf = min_tf; o.min_docs = min_docs; o.min_df = min_df; o.max_df = max_df; o.sample = sample;
+    return o;
+}
+
+extern "C" int nsh_engine_terms_batch(nsh_engine* e, const uint32_t* seg_doc, const uint64_t* row_off, uint64_t n_rows, uint32_t max_terms,
+                                      uint32_t min_tf, uint32_t min_docs, uint32_t min_df, uint32_t max_df, uint32_t* docs_out, uint64_t* df_out,
+                                      float* w_out, uint32_t* count_out, uint32_t* ndocs_out, char** term_bytes_out, uint64_t** term_offsets_out,
+                                      float* device_ms_out) { try {
+    if (!e) return -1;
+    if (term_bytes_out) *term_bytes_out = nullptr;
+    if (term_offsets_out) *term_offsets_out = nullptr;
+    if (n_rows && (!row_off || (row_off[n_rows] && !seg_doc))) { nsh_set_err(e, "nsh_engine_terms_batch: null argument"); return -1; }
+    for (uint64_t q = 0; q < n_rows; q++)
+        if (row_off[q + 1] < row_off[q]) { nsh_set_err(e, "nsh_engine_terms_batch: row_off descends"); return -1; }
+    std::vector<std::pair<uint32_t, uint32_t>> ids(n_rows ? (size_t)row_off[n_rows] : 0);
+    for (size_t i = 0; i < ids.size(); i++) ids[i] = {seg_doc[2 * i], seg_doc[2 * i + 1]};
+    const bool want_terms = term_bytes_out && term_offsets_out;
+    std::vector<std::vector<std::string>> terms;
+    if (!e->eng.terms_batch(ids.data(), row_off, (size_t)n_rows, nsh_related_options(max_terms, min_tf, min_docs, min_df, max_df, 100), docs_out, df_out,
+                            w_out, count_out, ndocs_out, want_terms ? &terms : nullptr, device_ms_out)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    if (!want_terms) return 0;
+    size_t total = 0, bytes = 0;
+    for (const auto& row : terms) { total += row.size(); for (const auto& t : row) bytes += t.size(); }
+    char* tb = (char*)std::malloc(bytes + 1);
+    uint64_t* to = (uint64_t*)std::malloc((total + 1) * sizeof(uint64_t));
+    if (!tb || !to) { std::free(tb); std::free(to); nsh_set_err(e, "nsh_engine_terms_batch: out of memory"); return -1; }
+    size_t j = 0, at = 0;
+    for (const auto& row : terms)
+        for (const auto& t : row) { to[j++] = at; std::memcpy(tb + at, t.data(), t.size()); at += t.size(); }
+    to[j] = at;
+    tb[at] = 0;
+    *term_bytes_out = tb;
+    *term_offsets_out = to;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_terms_batch", -1)
+}
+
+extern "C" int nsh_engine_related_terms_json(nsh_engine* e, const char* query, uint32_t max_terms, uint32_t min_tf, uint32_t min_docs, uint32_t min_df,
+                                             uint32_t max_df, uint32_t sample, int filtered, const char* date_from, const char* date_to,
+                                             int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    std::string s;
+    const nsx::DocFilter f = filtered ? nsh_doc_filter(date_from, date_to, keep_undated) : nsx::DocFilter{};
+    const bool ok = e->eng.related_terms_text(query ? query : "", nsh_related_options(max_terms, min_tf, min_docs, min_df, max_df, sample), filtered ? &f : nullptr, s);
+    if (!ok) { nsh_set_err(e, e->eng.last_error()); *json_out = nullptr; return -1; }
+    *json_out = (char*)std::malloc(s.size() + 1);
+    if (!*json_out) return -1;
+    std::memcpy(*json_out, s.c_str(), s.size() + 1);
+    return 0;
+} NSH_CATCH(e, "nsh_engine_related_terms_json", -1)
+}
+
 static void nsh_filter_stats_out(const nsx::FilterStats& st, uint64_t* stats_u64, double* stats_ms) {
     if (stats_u64) {
         stats_u64[0] = st.docs_kept; stats_u64[1] = st.docs_total; stats_u64[2] = st.postings_kept; stats_u64[3] = st.postings_total;

@@ -80,6 +80,7 @@ HIP_SYMBOLS = [
     "ns_forward_merge", "ns_forward_invert", "ns_compact_doc_cut", "ns_ctx_use_docsort", "ns_radix_plan", "ns_radix_tile",
     "ns_forward_merge_keep",
     "ns_docterms_upload", "ns_docterms_select", "ns_docterms_destroy", "ns_docterms_doc_cut",
+    "ns_docterms_aggregate", "ns_docterms_window", "ns_docterms_max_row_docs",
 ]
 HOST_SYMBOLS = [
     "nsh_parse_boolean", "nsh_engine_search_boolean_batch", "nsh_engine_search_boolean_json",
@@ -112,6 +113,7 @@ HOST_SYMBOLS = [
     "nsh_similar_select_host", "nsh_similar_clamp_terms", "nsh_similar_clamp_k", "nsh_similar_qweight", "nsh_similar_defaults",
     "nsh_engine_similar_term_stats", "nsh_engine_similar_batch", "nsh_engine_more_like_this_json", "nsh_engine_release_similar",
     "nsh_engine_similar_segments_on_device",
+    "nsh_related_aggregate_host", "nsh_engine_terms_batch", "nsh_engine_related_terms_json",
 ]
 
 class NsForwardInfo(C.Structure):   # include/nextsearch_hip.h ns_forward_info
@@ -266,6 +268,11 @@ def hip_lib():
         L.ns_docterms_destroy.restype = None
         L.ns_docterms_doc_cut.argtypes = []
         L.ns_docterms_doc_cut.restype = u32
+        L.ns_docterms_aggregate.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ns_docterms_window.argtypes = []
+        L.ns_docterms_window.restype = u32
+        L.ns_docterms_max_row_docs.argtypes = []
+        L.ns_docterms_max_row_docs.restype = u32
         L.ns_facet_upload.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
         L.ns_facet_release.argtypes = [vp, vp]
         L.ns_facet_count.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp, vp, u32, vp, vp, C.POINTER(C.c_float)]
@@ -307,7 +314,8 @@ DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_deb
                   "ns_debug_join_counters": 16, "ns_debug_facet_counters": 8, "ns_debug_sorted_counters": 9,
                   "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
                   "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11,
-                  "ns_debug_boolean_quorum_counters": 12, "ns_debug_boolean_boost_counters": 8}
+                  "ns_debug_boolean_quorum_counters": 12, "ns_debug_boolean_boost_counters": 8,
+                  "ns_debug_terms_counters": 8}
 
 
 def debug_counters(reset=False):
@@ -445,6 +453,9 @@ def host_lib():
         L.nsh_similar_defaults.restype = None
         L.nsh_engine_similar_term_stats.argtypes = [vp, u32, vp, vp, u64]
         L.nsh_engine_similar_term_stats.restype = C.c_int64
+        L.nsh_related_aggregate_host.argtypes = [vp, u32, vp, u64, vp, vp, u32, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
+        L.nsh_engine_terms_batch.argtypes = [vp, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_float)]
+        L.nsh_engine_related_terms_json.argtypes = [vp, C.c_char_p, u32, u32, u32, u32, u32, u32, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_similar_batch.argtypes = [vp, vp, u64, i32, u32, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
         L.nsh_engine_more_like_this_json.argtypes = [vp, C.c_char_p, u64, i32, C.POINTER(vp)]
         L.nsh_engine_release_similar.argtypes = [vp]
@@ -1469,6 +1480,48 @@ class Engine:
         self._L.nsh_free(out)
         return s
 
+    def terms_batch(self, rows, **opt):
+        """Engine::terms_batch over rows of (manifest position, docId) pairs; options as RELATED_DEFAULTS.  Returns per row
+        [(term bytes, docs, df, w)] in rank order, ndocs u32[Q] and the device time."""
+        o = dict(RELATED_DEFAULTS, **opt)
+        off = np.zeros(len(rows) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64) if len(rows) else []
+        flat = [np.asarray(list(r), dtype=np.uint32).reshape(-1, 2) for r in rows if len(r)]
+        ids = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((1, 2), np.uint32))
+        Q, To = len(rows), max(1, min(int(o["max_terms"]), 32))
+        docs, df, w = np.zeros((Q, To), np.uint32), np.zeros((Q, To), np.uint64), np.zeros((Q, To), np.float32)
+        cnt, ndocs = np.zeros(Q, np.uint32), np.zeros(Q, np.uint32)
+        tb, to, ms = C.c_void_p(), C.c_void_p(), C.c_float()
+        rc = self._L.nsh_engine_terms_batch(self.h, ids.ctypes.data, off.ctypes.data, Q, o["max_terms"], o["min_tf"], o["min_docs"], o["min_df"], o["max_df"],
+                                            docs.ctypes.data, df.ctypes.data, w.ctypes.data, cnt.ctypes.data, ndocs.ctypes.data, C.byref(tb), C.byref(to), C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"terms_batch failed: {self.error()}")
+        total = int(cnt.sum())
+        offs = np.ctypeslib.as_array(C.cast(to, C.POINTER(C.c_uint64)), shape=(total + 1,)).copy()
+        raw = C.string_at(tb, int(offs[total]))
+        self._L.nsh_free(tb)
+        self._L.nsh_free(to)
+        out, j = [], 0
+        for q in range(Q):
+            out.append([(raw[int(offs[j + r]):int(offs[j + r + 1])], int(docs[q, r]), int(df[q, r]), w[q, r]) for r in range(int(cnt[q]))])
+            j += int(cnt[q])
+        return out, ndocs, ms.value
+
+    def related_terms_json(self, query, date_filter=None, **opt):
+        """Engine::related_terms as bytes; date_filter: None or (date_from, date_to, keep_undated)"""
+        o = dict(RELATED_DEFAULTS, **opt)
+        f = date_filter or ("", "", False)
+        out = C.c_void_p()
+        rc = self._L.nsh_engine_related_terms_json(self.h, _as_bytes(query), o["max_terms"], o["min_tf"], o["min_docs"], o["min_df"], o["max_df"], o["sample"],
+                                                   1 if date_filter else 0, _as_bytes(f[0]), _as_bytes(f[1]), int(bool(f[2])), C.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"related_terms failed: {self.error()}")
+        s = C.string_at(out)
+        self._L.nsh_free(out)
+        return s
+
+    related_terms = related_terms_json
+
     def release_similar(self):
         self._L.nsh_engine_release_similar(self.h)
 
@@ -1714,6 +1767,39 @@ def similar_select_host(part, df, idf, doc_ids, max_terms=25, min_tf=1, min_df=1
     return term, w, count
 
 
+RELATED_DEFAULTS = {"max_terms": 10, "min_tf": 1, "min_docs": 2, "min_df": 1, "max_df": 0xFFFFFFFF, "sample": 100}   # nsx::RelatedOptions
+
+
+def related_clamp_terms(max_terms):
+    """T of one segment's aggregate: clamp(max_terms, 1, 64)"""
+    return max(1, min(int(max_terms), 64))
+
+
+def related_rows_flat(rows):
+    """a list of doc id lists -> (ids u32[total], row_off u64[n + 1])"""
+    off = np.zeros(len(rows) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64) if len(rows) else []
+    flat = [np.asarray(r, dtype=np.uint32).ravel() for r in rows if len(r)]
+    ids = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1, np.uint32), dtype=np.uint32)
+    return ids, off
+
+
+def related_aggregate_host(part, df, idf, rows, max_terms=10, min_tf=1, min_docs=2, min_df=1, max_df=0xFFFFFFFF):
+    """nsh_related_aggregate_host (the rule on one host thread) over a part in forward_build's form and df / idf by term id ->
+    (term u32[n, T], docs u32[n, T], w f32[n, T], count u32[n], ndocs u32[n]); ValueError when the input is refused"""
+    cnt, pairs, df, idf = _select_arrays(part, df, idf)
+    ids, off = related_rows_flat(rows)
+    n, T = len(rows), related_clamp_terms(max_terms)
+    term, docs, count, ndocs = (np.full(shape, 0x5A5A5A5A, dtype=np.uint32) for shape in ((n, T), (n, T), n, n))
+    w = np.full((n, T), 0x5A5A5A5A, dtype=np.uint32).view(np.float32)
+    rc = host_lib().nsh_related_aggregate_host(cnt.ctypes.data, len(cnt), pairs.ctypes.data, len(pairs), df.ctypes.data, idf.ctypes.data, len(df),
+                                               ids.ctypes.data, off.ctypes.data, n, max_terms, min_tf, min_docs, min_df, max_df, term.ctypes.data,
+                                               docs.ctypes.data, w.ctypes.data, count.ctypes.data, ndocs.ctypes.data)
+    if rc != 0:
+        raise ValueError("nsh_related_aggregate_host refused its input")
+    return term, docs, w, count, ndocs
+
+
 class DocTerms:
     """Raw ns_docterms_upload / ns_docterms_select over a part in forward_build's form (counts, pairs[n, 2]; doc_len and terms are
     not needed) and df / idf by term id; n_pairs / n_terms override what is announced (refusal tests).  Raises RuntimeError
@@ -1743,6 +1829,20 @@ class DocTerms:
         if rc != NS_OK:
             raise RuntimeError(f"ns_docterms_select: {rc}: {self._L.ns_last_error(self.ctx if rc != -5 else None).decode()}", rc)
         return term, w, count, ms.value
+
+    def aggregate(self, rows, max_terms=10, min_tf=1, min_docs=2, min_df=1, max_df=0xFFFFFFFF):
+        """ns_docterms_aggregate over rows (a list of doc id lists) -> (term u32[n, T], docs u32[n, T], w f32[n, T], count u32[n],
+        ndocs u32[n], device_ms); the outputs start as garbage so that the padding is the call's"""
+        ids, off = related_rows_flat(rows)
+        n, T = len(rows), related_clamp_terms(max_terms)
+        term, docs, count, ndocs = (np.full(shape, 0x5A5A5A5A, dtype=np.uint32) for shape in ((n, T), (n, T), n, n))
+        w = np.full((n, T), 0x5A5A5A5A, dtype=np.uint32).view(np.float32)
+        ms = C.c_float()
+        rc = self._L.ns_docterms_aggregate(self.h, ids.ctypes.data, off.ctypes.data, n, max_terms, min_tf, min_docs, min_df, max_df, term.ctypes.data,
+                                           docs.ctypes.data, w.ctypes.data, count.ctypes.data, ndocs.ctypes.data, C.byref(ms))
+        if rc != NS_OK:
+            raise RuntimeError(f"ns_docterms_aggregate: {rc}: {self._L.ns_last_error(self.ctx if rc != -5 else None).decode()}", rc)
+        return term, docs, w, count, ndocs, ms.value
 
     def close(self):
         if self.h:
