@@ -189,6 +189,29 @@ int ns_segment_build_skips(ns_ctx* ctx, ns_seg* seg, const uint64_t* byte_off, c
 int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint32_t* keep_bits, const uint64_t* byte_off,
                       const uint32_t* counts, uint32_t n_lists, uint64_t* new_byte_off_out, uint32_t* new_counts_out,
                       void* postings_out, uint64_t* kept_postings_out, float* device_ms_out, ns_seg** out);
+/* A derived segment of copied lists and union lists (csrc/ns_union.hip).  Group g, g < n_groups, names the
+ * member lists [group_begin[g], group_begin[g + 1]) of `src`; member i is [member_off[i] / 8, + member_cnt[i]) as in
+ * ns_term_ref (members may overlap, repeat and come in any order); n_members = group_begin[n_groups].  The NEW segment,
+ * published under new_seg_id, holds one list per group:
+ *   one member         the list copied verbatim, a docId >= n_docs included
+ *   two or more        the docId-ascending list {d, sum of tf over the member postings that name d} for every d < n_docs that a
+ *                      member names with a non-zero sum.  Members are summed as given (a list named twice counts twice), a
+ *                      member posting with docId >= n_docs is dropped, the sum is a uint32_t and wraps.
+ *   none, or all empty count 0
+ * new_byte_off_out[g], new_counts_out[g]: the group's place in the new payload; lists do not overlap and start at multiples
+ * of 8.  The segment has the source's n_docs, avgdl and norms, is padded like an uploaded one, has no packed / impact streams,
+ * skip tables or block maxima (ns_segment_build_skips works on it as on any segment) and keeps no pointer into `src`: the two
+ * are released in either order with ns_segment_release.  postings_out (host, may be NULL; needs n_postings_out): the new
+ * payload, for tests and tools; its capacity is the caller's: the single groups' counts plus, per group of two or more,
+ * min(sum of member counts, n_docs) postings.  n_postings_out, rounds_out, device_ms_out (may be NULL): postings written;
+ * rounds of table scratch the multi groups took (ns_ctx_union_scratch); device time of the call.  Synchronous.  NS_E_INVAL:
+ * what ns_segment_filter refuses, a group_begin that is not non-decreasing from 0, postings_out without n_postings_out. */
+int ns_segment_union(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint64_t* member_off, const uint32_t* member_cnt,
+                     const uint32_t* group_begin, uint32_t n_groups, uint64_t* new_byte_off_out, uint32_t* new_counts_out,
+                     void* postings_out, uint64_t* n_postings_out, uint32_t* rounds_out, float* device_ms_out, ns_seg** out);
+/* Table scratch of ns_segment_union per round, in bytes: one uint32_t[n_docs] table per group of two or more members, as many
+ * groups a round as fit, and always at least one.  0: the default, 64 MiB.  NS_E_INVAL above 16 GiB. */
+int ns_ctx_union_scratch(ns_ctx* ctx, uint64_t bytes);
 /* on = 0: batches prepared from now on ignore skip tables (default: on = 1). */
 int ns_ctx_use_skips(ns_ctx* ctx, int on);
 /* Block-max scores with `found`-exact pruning.  The reference reads every posting of every scored list

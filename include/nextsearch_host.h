@@ -611,6 +611,37 @@ int nsh_engine_search_boosted_json(nsh_engine* e, const char* query, int k, cons
 int nsh_engine_search_boosted_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, int use_filter,
                                         const char* date_from, const char* date_to, int keep_undated, char** json_out);
 
+/* ---- prefix terms: `vaccin*` (host/prefix.hpp) ----
+ * nsx::parse_prefixed: nsh_parse_boosted's dialect plus the prefix term.  A '*' directly behind a token's last byte marks the token
+ * as a prefix, provided the next byte is not alphanumeric or the text ends there, inside or outside a group and before a `^w`;
+ * every other '*' stays a separator.  A prefix is lower-cased, dropped below 2 bytes and NOT tested against the stop-word list.
+ * prefix[i] (may be NULL) = 1 where term i is a prefix (its text comes without the '*'); everything else as nsh_parse_boosted,
+ * whose answer this is for a text without such a '*'. */
+uint32_t nsh_parse_prefixed(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                            float* weights, uint8_t* prefix, uint32_t terms_cap, uint32_t* min_should_out);
+/* Engine::expand_prefix (host only: works with device < 0): the terms of the autocomplete table that begin with `prefix` (a term
+ * equal to it included), in byte order, joined with blanks into buf (cut at cap - 1 bytes; *bytes_out, may be NULL: the bytes the
+ * whole answer needs); returns their number, or -1 with a message.  max_expansions: 1 .. 65535, 0 = the default, 1024; with more
+ * matches those of the largest summed df, then the smallest bytes, stay (nsh_engine_suggest_json's order) and *truncated_out (may
+ * be NULL) is 1.  A term the dictionary does not hold is skipped. */
+int64_t nsh_engine_expand_prefix(nsh_engine* e, const char* prefix, uint32_t max_expansions, char* buf, uint64_t cap, uint64_t* bytes_out, int* truncated_out);
+/* Engine::search_prefixed_after_batch_flat: nsh_engine_search_boosted_after_batch over that dialect, parameter for parameter, with
+ * max_expansions behind spec.  In a segment a prefix is ONE blended term: the union of its expansions' lists there with the tf
+ * summed per document, the df the size of the union and the idf computed from that df (ns_segment_union builds the lists on the
+ * device, once per call and segment); with one expansion there it is that term's own list and idf.  A non-zero filter_handle is
+ * refused with a message.  A batch without a prefix is nsh_engine_search_boosted_after_batch's call. */
+int nsh_engine_search_prefixed_after_batch(nsh_engine* e, const nsh_boost_spec* spec, uint32_t max_expansions, uint32_t filter_handle, const char* const* queries,
+                                           uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                           uint8_t* has_found, float* device_ms_out);
+/* Engine::search_prefixed: *json_out (free with nsh_free) = nsh_engine_search_boosted_json's body with "prefixed" in place of
+ * "boosted" (a prefix term prints with its '*') and "prefixes": [{"expansions", "prefix", "truncated"}], the query's distinct
+ * prefixes in query order; keys stay sorted: both stand in front of "query".  use_filter != 0 is refused.  On failure -1 and
+ * {"error": ...}.  nsh_engine_search_prefixed_page_json pages it (cursors of kind 's'). */
+int nsh_engine_search_prefixed_json(nsh_engine* e, const char* query, int k, const nsh_boost_spec* spec, uint32_t max_expansions, int use_filter,
+                                    const char* date_from, const char* date_to, int keep_undated, char** json_out);
+int nsh_engine_search_prefixed_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, uint32_t max_expansions,
+                                         int use_filter, const char* date_from, const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@
 #include "ns_compact.hip"
 #include "ns_delete.hip"
 #include "ns_filter.hip"
+#include "ns_union.hip"    // includes ns_union_plan.hpp (host only: what ns_segment_union plans before it touches the device)
 #include "ns_facet.hip"
 #include "ns_similar.hip"
 #include "ns_terms.hip"     // after ns_similar.hip (ml_shfl, ml_sort_up, ml_join)
@@ -132,6 +133,7 @@ struct ns_ctx {
     std::vector<ns_forward*> fwds;   // live forward-index handles (ns_forward_build, ns_forward_merge): orphaned, not freed, by ns_ctx_destroy
     bool cp_inplace = true;          // ns_forward_merge sorts documents up to kCpDocCut pairs where they lie (ns_ctx_use_docsort)
     std::vector<ns_docterms*> dts;   // live ns_docterms handles (ns_docterms_upload): orphaned, not freed, by ns_ctx_destroy
+    uint64_t union_scratch = kUnDefaultScratch;   // table bytes per round of ns_segment_union (ns_ctx_union_scratch)
 };
 
 static thread_local std::string g_create_err;
@@ -2003,6 +2005,142 @@ extern "C" int ns_segment_filter(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, 
         return rc;
     }
     if (kept_postings_out) *kept_postings_out = kept;
+    if (ctx->segs.size() <= new_seg_id) ctx->segs.resize(new_seg_id + 1, nullptr);
+    ctx->segs[new_seg_id] = s;
+    *out = s;
+    return NS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// A derived segment of copied lists and union lists (csrc/ns_union.hip, csrc/ns_union_plan.hpp)
+extern "C" int ns_ctx_union_scratch(ns_ctx* ctx, uint64_t bytes) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_ctx_union_scratch: ctx is NULL");
+    if (bytes > kUnMaxScratch) return fail(ctx, NS_E_INVAL, "ns_ctx_union_scratch: %llu bytes (at most %llu)", (unsigned long long)bytes, (unsigned long long)kUnMaxScratch);
+    ctx->union_scratch = bytes ? bytes : kUnDefaultScratch;
+    return NS_OK;
+}
+
+extern "C" int ns_segment_union(ns_ctx* ctx, ns_seg* src, uint32_t new_seg_id, const uint64_t* member_off, const uint32_t* member_cnt,
+                                const uint32_t* group_begin, uint32_t n_groups, uint64_t* new_byte_off_out, uint32_t* new_counts_out,
+                                void* postings_out, uint64_t* n_postings_out, uint32_t* rounds_out, float* device_ms_out, ns_seg** out) {
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "ns_segment_union: ctx is NULL");
+    if (!out) return fail(ctx, NS_E_INVAL, "ns_segment_union: out is NULL");
+    *out = nullptr;
+    if (!src) return fail(ctx, NS_E_INVAL, "ns_segment_union: src is NULL");
+    if (src->ctx != ctx) return fail(ctx, NS_E_INVAL, "ns_segment_union: the source does not belong to this ctx");
+    if (src->pending) return fail(ctx, NS_E_INVAL, "ns_segment_union: the source's upload has not ended");
+    if (src->id >= ctx->segs.size() || ctx->segs[src->id] != src) return fail(ctx, NS_E_INVAL, "ns_segment_union: the source does not belong to this ctx");
+    if (!group_begin) return fail(ctx, NS_E_INVAL, "ns_segment_union: group_begin is NULL");
+    if (n_groups && (!new_byte_off_out || !new_counts_out)) return fail(ctx, NS_E_INVAL, "ns_segment_union: null list arrays");
+    if (postings_out && !n_postings_out) return fail(ctx, NS_E_INVAL, "ns_segment_union: postings_out without n_postings_out");
+    if (group_begin[0] != 0) return fail(ctx, NS_E_INVAL, "ns_segment_union: group_begin[0] is %u, not 0", group_begin[0]);
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (group_begin[g + 1] < group_begin[g]) return fail(ctx, NS_E_INVAL, "ns_segment_union: group_begin decreases at group %u", g);
+    const uint32_t n_members = group_begin[n_groups];
+    if (n_members && (!member_off || !member_cnt)) return fail(ctx, NS_E_INVAL, "ns_segment_union: null list arrays");
+    if (new_seg_id >= (1u << 20)) return fail(ctx, NS_E_INVAL, "seg_id %u too large", new_seg_id);
+    if (new_seg_id < ctx->segs.size() && ctx->segs[new_seg_id]) return fail(ctx, NS_E_INVAL, "segment %u already uploaded", new_seg_id);
+    for (const ns_seg* p : ctx->pending_uploads)
+        if (p->id == new_seg_id) return fail(ctx, NS_E_INVAL, "segment %u is being uploaded", new_seg_id);
+    if (src->n_postings >= (1ull << 32) - 2 * kUnChunk) return fail(ctx, NS_E_INVAL, "ns_segment_union: the source has too many postings");
+    if (int rc = check_lists(ctx, src, member_off, member_cnt, n_members)) return rc;
+    uint64_t named = 0;
+    for (uint32_t i = 0; i < n_members; i++) named += member_cnt[i];
+    if (named >= (1ull << 32) - 2 * kUnChunk) return fail(ctx, NS_E_INVAL, "ns_segment_union: the members have too many postings");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    const uint32_t n_docs = src->n_docs, cpt = (n_docs + kUnChunk - 1) / kUnChunk;
+    std::vector<uint32_t> firsts(n_members);
+    for (uint32_t i = 0; i < n_members; i++) firsts[i] = (uint32_t)(member_off[i] / 8);
+    const UnionPlan plan = union_plan(firsts.data(), member_cnt, group_begin, n_groups, n_docs, ctx->union_scratch);
+    const uint32_t n_rounds = (uint32_t)plan.rounds.size(), n_tabled = (uint32_t)plan.tabled.size();
+    const uint32_t R = std::min<uint32_t>(plan.tables_per_round, std::max<uint32_t>(n_tabled, 1));   // tables the call holds
+    const uint32_t m = R * cpt + 1;
+    const size_t n_copy = plan.copy_items.size(), n_add = plan.add_items.size();
+    // what the host knows of the answers: the single groups' places; k_un_lists stores the tabled groups' over the zeros
+    std::vector<uint64_t> noff(n_groups, 0);
+    std::vector<uint32_t> ncnt(n_groups, 0);
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (group_begin[g + 1] - group_begin[g] == 1) { noff[g] = (uint64_t)plan.single_off[g] * 8; ncnt[g] = member_cnt[group_begin[g]]; }
+    std::vector<uint32_t> run(n_rounds + 1, 0);
+    run[0] = (uint32_t)plan.single_postings;
+
+    hipStream_t st = ctx->stream;
+    // the scratch of the call in one block from the ctx pool; the new segment's own arrays are hipMallocs, like a filtered copy's
+    CallBlock blk(ctx);
+    const size_t o_tables = blk.reserve(n_tabled ? (size_t)R * std::max<uint32_t>(n_docs, 1) * 4 : 4), o_mask = blk.reserve((size_t)m * 8),
+                 o_base = blk.reserve((size_t)m * 4), o_sums = blk.reserve((size_t)((m + 1023) / 1024) * 4), o_run = blk.reserve((size_t)(n_rounds + 1) * 4);
+    const size_t o_copy = blk.reserve(n_copy * sizeof(UnCopyItem)), o_add = blk.reserve(n_add * sizeof(UnAddItem)), o_tabled = blk.reserve((size_t)n_tabled * 4),
+                 o_ncnt = blk.reserve((size_t)n_groups * 4), o_noff = blk.reserve((size_t)n_groups * 8);
+    blk.alloc(2);
+    ns_seg* s = new ns_seg();
+    s->ctx = ctx;
+    s->id = new_seg_id;
+    s->n_docs = n_docs;
+    s->avgdl = src->avgdl;
+    s->norm_safe = src->norm_safe;
+    uint32_t written = 0;
+    if (blk.ok()) {
+        uint32_t *d_tables = blk.at<uint32_t>(o_tables), *d_base = blk.at<uint32_t>(o_base), *d_sums = blk.at<uint32_t>(o_sums), *d_run = blk.at<uint32_t>(o_run);
+        uint32_t *d_tabled = blk.at<uint32_t>(o_tabled), *d_ncnt = blk.at<uint32_t>(o_ncnt);
+        uint64_t *d_mask = blk.at<uint64_t>(o_mask), *d_noff = blk.at<uint64_t>(o_noff);
+        const UnCopyItem* d_copy = blk.at<UnCopyItem>(o_copy);
+        const UnAddItem* d_add = blk.at<UnAddItem>(o_add);
+        blk.chk(hipMalloc((void**)&s->d_postings, ((size_t)plan.bound + kPadPostings) * 8));
+        blk.chk(hipMalloc((void**)&s->d_pnorm, ((size_t)plan.bound + kPadPostings) * 4));
+        blk.chk(hipMalloc((void**)&s->d_norm, (size_t)std::max<uint32_t>(n_docs, 1) * 4));
+        if (blk.ok()) {
+            blk.upload(o_run, run.data(), (size_t)(n_rounds + 1) * 4);
+            blk.upload(o_copy, plan.copy_items.data(), n_copy * sizeof(UnCopyItem));
+            blk.upload(o_add, plan.add_items.data(), n_add * sizeof(UnAddItem));
+            blk.upload(o_tabled, plan.tabled.data(), (size_t)n_tabled * 4);
+            blk.upload(o_ncnt, ncnt.data(), (size_t)n_groups * 4);
+            blk.upload(o_noff, noff.data(), (size_t)n_groups * 8);
+            if (n_docs) blk.chk(hipMemcpyAsync(s->d_norm, src->d_norm, (size_t)n_docs * 4, hipMemcpyDeviceToDevice, st));
+        }
+        if (blk.ok()) {
+            blk.record(0);
+            if (n_copy) hipLaunchKernelGGL(k_un_copy, dim3(std::min<uint32_t>(((uint32_t)n_copy + 3) / 4, 1u << 16)), dim3(256), 0, st, src->d_postings, src->d_pnorm, d_copy, (uint32_t)n_copy, s->d_postings, s->d_pnorm);
+            for (uint32_t r = 0; r < n_rounds && blk.ok(); r++) {
+                const UnRound& rd = plan.rounds[r];
+                const uint32_t chunks = rd.n_tables * cpt, mr = chunks + 1;
+                blk.chk(hipMemsetAsync(d_tables, 0, (size_t)rd.n_tables * n_docs * 4, st));
+                if (rd.n_items) hipLaunchKernelGGL(k_un_add, dim3(std::min<uint32_t>((rd.n_items + 3) / 4, 1u << 16)), dim3(256), 0, st, src->d_postings, d_add + rd.first_item, rd.n_items, n_docs, d_tables);
+                hipLaunchKernelGGL(k_un_mark, dim3(std::min<uint32_t>((mr + 3) / 4, 1u << 16)), dim3(256), 0, st, d_tables, rd.n_tables, n_docs, cpt, d_mask, d_base);
+                ig_scan(st, d_base, mr, d_sums, (uint32_t*)nullptr);
+                if (chunks) hipLaunchKernelGGL(k_un_scatter, dim3(std::min<uint32_t>((chunks + 3) / 4, 1u << 16)), dim3(256), 0, st, d_tables, rd.n_tables, n_docs, cpt, d_mask, d_base, d_run + r, src->d_norm, s->d_postings, s->d_pnorm);
+                hipLaunchKernelGGL(k_un_lists, dim3((rd.n_tables + 255) / 256), dim3(256), 0, st, d_tabled + rd.first_table, rd.n_tables, cpt, d_base, d_run + r, d_noff, d_ncnt);
+                blk.launched();
+            }
+            hipLaunchKernelGGL(k_un_pad, dim3((kPadPostings + 255) / 256), dim3(256), 0, st, d_run + n_rounds, (uint32_t)kPadPostings, s->d_postings, s->d_pnorm);
+            blk.record(1);
+            blk.launched();
+        }
+        // the one synchronisation: how many postings were written, and the groups' places
+        if (blk.ok()) blk.chk(hipMemcpyAsync(&written, d_run + n_rounds, 4, hipMemcpyDeviceToHost, st));
+        if (blk.ok() && n_groups) {
+            blk.fetch(new_byte_off_out, o_noff, (size_t)n_groups * 8);
+            blk.fetch(new_counts_out, o_ncnt, (size_t)n_groups * 4);
+        }
+        if (blk.ok()) blk.sync();
+        if (blk.ok() && written > plan.bound) blk.chk(hipErrorUnknown);
+        float ms = 0.0f;
+        if (blk.elapsed_ms(0, 1, &ms) && device_ms_out) *device_ms_out = ms;
+        // the payload for tests and tools: its size is known only now
+        if (blk.ok() && postings_out && written) {
+            blk.chk(hipMemcpyAsync(postings_out, s->d_postings, (size_t)written * 8, hipMemcpyDeviceToHost, st));
+            blk.sync();
+        }
+    }
+    const int rc = blk.finish("ns_segment_union");
+    if (rc != NS_OK) {
+        seg_free_device(s);
+        delete s;
+        return rc;
+    }
+    s->n_postings = written;
+    if (n_postings_out) *n_postings_out = written;
+    if (rounds_out) *rounds_out = n_rounds;
     if (ctx->segs.size() <= new_seg_id) ctx->segs.resize(new_seg_id + 1, nullptr);
     ctx->segs[new_seg_id] = s;
     *out = s;

@@ -27,9 +27,9 @@ struct BoolTerm {
 inline bool bool_is_space(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; }
 
 // The three dialects of the query box.  They are nested: Grouped (grouped.hpp) is Boolean plus one level of parentheses, Quorum
-// (quorum.hpp) is Grouped plus the two `~m` forms, Boosted (boost.hpp) is Quorum plus the `^w` suffix.  A further dialect is one
-// more value here and one more branch in the scanner.
-enum class Dialect : int { Boolean = 0, Grouped = 1, Quorum = 2, Boosted = 3 };
+// (quorum.hpp) is Grouped plus the two `~m` forms, Boosted (boost.hpp) is Quorum plus the `^w` suffix, Prefixed (prefix.hpp) is
+// Boosted plus the prefix term `word*`.  A further dialect is one more value here and one more branch in the scanner.
+enum class Dialect : int { Boolean = 0, Grouped = 1, Quorum = 2, Boosted = 3, Prefixed = 4 };
 
 static constexpr uint32_t kQuorumNeedCap = 1000000;    // what a longer run of digits reads as
 
@@ -70,17 +70,26 @@ inline float boost_weight_at(const char* text, size_t stop, size_t i) {
     return (float)v;
 }
 
-// The one scanner of the four grammars (the header comments of boolean.hpp, grouped.hpp, quorum.hpp and boost.hpp).  Calls
+// The one scanner of the five grammars (the header comments of boolean.hpp, grouped.hpp, quorum.hpp, boost.hpp and prefix.hpp).  Calls
 // fn(ptr, len, role, clause, need) for every term of the query, in order; `scratch` holds the lowercased bytes.  Under kRoleMust
 // `clause` counts up from 0 (one id per group, one per token outside a group) and `need` is the clause's need (>= 1); else both
 // are 0.  The optional terms come as SHOULD terms whatever min_should says: see QuorumShape.  Without groups '(' is the
 // tokenizer's business; without needs a '~' is; without weights a '^' is.  Boosted: *weight holds the weight of the piece (1.0f
-// without a valid suffix, and on a `-` piece, where the suffix is consumed and ignored) whenever fn is called.
+// without a valid suffix, and on a `-` piece, where the suffix is consumed and ignored) whenever fn is called.  Prefixed:
+// *is_prefix says whether the term fn is called with is a prefix term (for_each_star_term), inside a group and before a `^w` too.
 template <Dialect D, class Fn>
-inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr) {
-    constexpr bool kGroups = D != Dialect::Boolean, kNeeds = D == Dialect::Quorum || D == Dialect::Boosted, kWeights = D == Dialect::Boosted;
+inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr, bool* is_prefix = nullptr) {
+    constexpr bool kPrefixes = D == Dialect::Prefixed;
+    constexpr bool kGroups = D != Dialect::Boolean, kNeeds = D == Dialect::Quorum || D == Dialect::Boosted || kPrefixes, kWeights = D == Dialect::Boosted || kPrefixes;
     float unused = 1.0f;
     float& w_now = weight ? *weight : unused;
+    bool unused_star = false;
+    bool& star_now = is_prefix ? *is_prefix : unused_star;
+    // the tokens of a piece's body: for_each_base_term's, or with prefix terms its sibling's
+    auto tokens = [&](const char* p, size_t len, auto emit) {
+        if constexpr (kPrefixes) for_each_star_term(p, len, scratch, [&](const char* t, size_t tl, bool star) { star_now = star; emit(t, tl); });
+        else for_each_base_term(p, len, scratch, emit);
+    };
     QuorumShape shape{0, 0};
     size_t i = 0;
     while (i < n) {
@@ -109,7 +118,7 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
             if (role != kRoleMust) need = 0;
             else if (need == 0) need = 1;
             bool any = false;
-            for_each_base_term(text + from + 1, end - (from + 1), scratch, [&](const char* p, size_t len) {
+            tokens(text + from + 1, end - (from + 1), [&](const char* p, size_t len) {
                 fn(p, len, role, role == kRoleMust ? shape.n_clauses : 0u, need);
                 any = true;
             });
@@ -132,8 +141,7 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
             const float w = hat > from ? boost_weight_at(text, j, hat - 1) : 0.0f;
             if (w > 0.0f) { to = hat - 1; if (prefix != kRoleNot) w_now = w; }
         }
-        for_each_base_term(text + from, to - from, scratch,
-                           [&](const char* p, size_t len) { fn(p, len, prefix, prefix == kRoleMust ? shape.n_clauses++ : 0u, prefix == kRoleMust ? 1u : 0u); });
+        tokens(text + from, to - from, [&](const char* p, size_t len) { fn(p, len, prefix, prefix == kRoleMust ? shape.n_clauses++ : 0u, prefix == kRoleMust ? 1u : 0u); });
         i = j;
     }
     return shape;
@@ -141,9 +149,11 @@ inline QuorumShape for_each_dialect_term(const char* text, size_t n, std::vector
 
 // the scanner of a dialect chosen at run time
 template <class Fn>
-inline QuorumShape for_each_term(Dialect d, const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr) {
+inline QuorumShape for_each_term(Dialect d, const char* text, size_t n, std::vector<char>& scratch, Fn fn, float* weight = nullptr, bool* is_prefix = nullptr) {
     if (weight) *weight = 1.0f;
+    if (is_prefix) *is_prefix = false;
     switch (d) {
+        case Dialect::Prefixed: return for_each_dialect_term<Dialect::Prefixed>(text, n, scratch, fn, weight, is_prefix);
         case Dialect::Boolean: return for_each_dialect_term<Dialect::Boolean>(text, n, scratch, fn);
         case Dialect::Grouped: return for_each_dialect_term<Dialect::Grouped>(text, n, scratch, fn);
         case Dialect::Quorum: return for_each_dialect_term<Dialect::Quorum>(text, n, scratch, fn);

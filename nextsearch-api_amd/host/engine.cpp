@@ -2543,7 +2543,7 @@ std::string Engine::search_sorted(const std::string& query, int k, const nsx::So
 // what the dialect forms call themselves in messages: the named methods of engine.hpp
 struct DialectNames { const char *first_page, *after_batch, *facet_batch, *sorted_batch, *text, *faceted_text, *sorted_text; };
 static const DialectNames& names_of(nsx::Dialect d) {
-    static const DialectNames kNames[4] = {
+    static const DialectNames kNames[5] = {
         {"search_boolean_batch_flat", "search_boolean_after_batch_flat", "facet_boolean_batch_flat", "search_boolean_sorted_batch_flat", "search_boolean",
          "search_boolean_faceted", "search_boolean_sorted"},
         {"search_grouped_after_batch_flat", "search_grouped_after_batch_flat", "facet_grouped_batch_flat", "search_grouped_sorted_batch_flat", "search_grouped",
@@ -2551,7 +2551,9 @@ static const DialectNames& names_of(nsx::Dialect d) {
         {"search_quorum_after_batch_flat", "search_quorum_after_batch_flat", "facet_quorum_batch_flat", "search_quorum_sorted_batch_flat", "search_quorum",
          "search_quorum_faceted", "search_quorum_sorted"},
         {"search_boosted_after_batch_flat", "search_boosted_after_batch_flat", "facet_boosted_batch_flat", "search_boosted_sorted_batch_flat", "search_boosted",
-         "search_boosted_faceted", "search_boosted_sorted"}};   // (Boosted has the ranked call alone: DESIGN.md §5z, left out)
+         "search_boosted_faceted", "search_boosted_sorted"},   // (Boosted has the ranked call alone: DESIGN.md §5z, left out)
+        {"search_prefixed_after_batch_flat", "search_prefixed_after_batch_flat", "facet_prefixed_batch_flat", "search_prefixed_sorted_batch_flat", "search_prefixed",
+         "search_prefixed_faceted", "search_prefixed_sorted"}};   // (Prefixed too: §5ab, left out)
     return kNames[(int)d];
 }
 
@@ -2561,9 +2563,19 @@ static const DialectNames& names_of(nsx::Dialect d) {
 // False, with a message, when a Grouped or Quorum query has more clauses than a clause value can name, or a Quorum query asks
 // for more than kQuorumMaxNeed of a clause's terms.  Boolean never fails.
 bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* queries, size_t a, size_t b, uint8_t* usable, CallPrep& bp) {
-    const bool with_clauses = dialect != nsx::Dialect::Boolean, with_needs = dialect == nsx::Dialect::Quorum || dialect == nsx::Dialect::Boosted;
+    const bool with_clauses = dialect != nsx::Dialect::Boolean,
+               with_needs = dialect == nsx::Dialect::Quorum || dialect == nsx::Dialect::Boosted || dialect == nsx::Dialect::Prefixed;
     const uint32_t S = (uint32_t)segments.size();
     float weight = 1.0f;   // Boosted: the `^w` of the piece the scanner is in; else 1.0f
+    bool star = false;     // Prefixed: the term the scanner hands over is a prefix
+    // Prefixed: a term's row is one of the call's own (bp.px), which bp.rs.rows holds: a prefix's, or the dictionary term's there
+    auto local_row = [&](const char* p, size_t n) -> int64_t {
+        if (star) { const auto it = bp.px->of_prefix.find(std::string(p, n)); return it == bp.px->of_prefix.end() ? -1 : (int64_t)it->second; }
+        const int64_t gid = dict.find(p, n);
+        if (gid < 0) return -1;
+        const auto it = bp.px->of_term.find((uint32_t)gid);
+        return it == bp.px->of_term.end() ? -1 : (int64_t)it->second;
+    };
     const nsx::RowSource& rs = bp.rs;
     bp.qd.assign(b - a, ns_query_desc{0, 0});
     bp.refs.clear();
@@ -2575,10 +2587,10 @@ bool Engine::refs_range(const char* fn, nsx::Dialect dialect, const QueryView* q
         size_t positive = 0;
         uint32_t largest = 0;
         const nsx::QuorumShape shape = nsx::for_each_term(dialect, queries[q].p, queries[q].n, bp.scratch, [&](const char* p, size_t n, uint8_t role, uint32_t clause, uint32_t need) {
-            bp.terms.push_back(CallPrep::Term{dict.find(p, n), role, clause, need, weight});
+            bp.terms.push_back(CallPrep::Term{bp.px ? local_row(p, n) : dict.find(p, n), role, clause, need, weight});
             positive += role != nsx::kRoleNot;
             largest = std::max(largest, need);
-        }, &weight);
+        }, &weight, &star);
         uint32_t n_clauses = shape.n_clauses;
         if (shape.min_should) {   // `~m`: every optional term joins one more required clause of need m
             bool any = false;
@@ -2638,6 +2650,7 @@ bool Engine::ranked_call(nsx::Dialect dialect, bool paged, const CallPrep& bp, s
                                         bp.segs.data(), n_segs, hits, out.nhits + a, out.found + a, rest, ms);
             break;
         case nsx::Dialect::Boosted:   // without tables (term weights only) the call is the quorum call, kernels and all
+        case nsx::Dialect::Prefixed:  // the Boosted call over the derived segments
             name = "ns_search_boosted_after: ";
             rc = ns_search_boosted_after(ctx_, bp.qd.data(), nq, bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(), n_refs, K, cur, bp.ids.data(),
                                          bp.segs.data(), bp.boosts.empty() ? nullptr : bp.boosts.data(), n_segs, hits, out.nhits + a, out.found + a, rest, ms);
@@ -2667,6 +2680,7 @@ bool Engine::facet_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, size
                                        n_segs, counts, found, ms);
             break;
         case nsx::Dialect::Boosted: err_ = "facet counts do not depend on a score: use the quorum call"; return false;
+        case nsx::Dialect::Prefixed: err_ = "facet counts for prefixed queries are not built (DESIGN.md §5ab, left out)"; return false;
     }
     if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
     return true;
@@ -2697,6 +2711,7 @@ bool Engine::sorted_call(nsx::Dialect dialect, const CallPrep& bp, size_t a, siz
                                          bp.segs.data(), tabs, n_segs, hits, keys, out.nhits + a, out.found + a, rest, ms);
             break;
         case nsx::Dialect::Boosted: err_ = "date order does not depend on a score: use the quorum call"; return false;
+        case nsx::Dialect::Prefixed: err_ = "date order for prefixed queries is not built (DESIGN.md §5ab, left out)"; return false;
     }
     if (rc != NS_OK) { err_ = std::string(name) + ns_last_error(ctx_); return false; }
     return true;
@@ -2724,6 +2739,8 @@ bool Engine::boolean_batch_impl(const char* fn, nsx::Dialect dialect, uint32_t f
 
 bool Engine::search_dialect_after_batch_flat(nsx::Dialect dialect, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,
                                              ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable, float* device_ms, const nsx::BoostSpec* boost) {
+    if (dialect == nsx::Dialect::Prefixed)   // its own call: the derived segments (the default PrefixSpec)
+        return search_prefixed_after_batch_flat(boost, nsx::PrefixSpec{}, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
     return boolean_batch_impl(names_of(dialect).after_batch, dialect, filter_handle, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms, boost);
 }
 
@@ -2922,10 +2939,8 @@ static std::string boost_member(const nsx::BoostSpec& b) {
 
 // the "boosted" member of search_boosted's body (§5z): quorum_member's, where a "must" clause also carries the "weight" of its
 // piece and a "should" entry is {"term", "weight"}; "must_not" stays a list of strings (a weight there says nothing)
-static std::string boosted_member(const std::string& query) {
-    uint32_t min_should = 0;
-    const std::vector<nsx::BoostedTerm> terms = nsx::parse_boosted(query, &min_should);
-    std::string o = "  \"boosted\": {\n    \"min_should\": " + std::to_string(min_should) + ",\n    \"must\": [";
+static std::string boosted_member_of(const char* name, const std::vector<nsx::BoostedTerm>& terms, uint32_t min_should) {
+    std::string o = std::string("  \"") + name + "\": {\n    \"min_should\": " + std::to_string(min_should) + ",\n    \"must\": [";
     bool any_clause = false;
     for (size_t i = 0; i < terms.size(); i++) {
         if (terms[i].role != nsx::kRoleMust || terms[i].promoted) continue;
@@ -2964,6 +2979,34 @@ static std::string boosted_member(const std::string& query) {
     return o;
 }
 
+static std::string boosted_member(const std::string& query) {
+    uint32_t min_should = 0;
+    const std::vector<nsx::BoostedTerm> terms = nsx::parse_boosted(query, &min_should);
+    return boosted_member_of("boosted", terms, min_should);
+}
+
+// the "prefixed" member of search_prefixed's body (§5ab): boosted_member's, where a prefix term prints with its '*'
+static std::string prefixed_member(const std::string& query) {
+    uint32_t min_should = 0;
+    std::vector<nsx::BoostedTerm> terms;
+    for (const nsx::PrefixedTerm& t : nsx::parse_prefixed(query, &min_should))
+        terms.push_back(nsx::BoostedTerm{t.prefix ? t.text + "*" : t.text, t.role, t.clause, t.need, t.promoted, t.weight});
+    return boosted_member_of("prefixed", terms, min_should);
+}
+
+// the "prefixes" member behind it: what the call did with the query's distinct prefixes, in query order
+static std::string prefixes_member(const std::vector<nsx::PrefixInfo>& info) {
+    std::string o = "  \"prefixes\": [";
+    for (size_t i = 0; i < info.size(); i++) {
+        o += i ? ",\n    {\n      \"expansions\": " : "\n    {\n      \"expansions\": ";
+        o += std::to_string(info[i].expansions) + ",\n      \"prefix\": ";
+        json_escape(o, info[i].prefix);
+        o += std::string(",\n      \"truncated\": ") + (info[i].truncated ? "true" : "false") + "\n    }";
+    }
+    o += info.empty() ? "],\n" : "\n  ],\n";
+    return o;
+}
+
 // The dialect's member (the parsed query) put into a body in its sorted place (nlohmann keeps keys sorted).  front: "{\n" and
 // the "filter" member if there is one; tail: to_json_impl's members.  "boolean" is the body's first member; "grouped" stands in
 // front of tail's "k", "quorum" in front of tail's "results".  -> nullptr, or the name of the member that tail lacks
@@ -2979,6 +3022,7 @@ static const char* insert_dialect_member(nsx::Dialect dialect, const std::string
 
 // search_boolean's body, or the same body over another dialect with its member in place of "boolean"
 bool Engine::search_dialect_text(nsx::Dialect dialect, const std::string& query, int k, const nsx::DocFilter* f, std::string& body, const nsx::BoostSpec* boost) {
+    if (dialect == nsx::Dialect::Prefixed) return search_prefixed_text(query, k, boost, nsx::PrefixSpec{}, f, body);
     const char* name = names_of(dialect).text;
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
@@ -3164,6 +3208,222 @@ std::string Engine::search_boosted(const std::string& query, int k, const nsx::B
     return search_boosted_text(query, k, spec, f, body) ? body : error_body(body);
 }
 
+// ---- prefix terms (host/prefix.hpp, csrc/ns_union.hip) ----------------------------------------------------
+// The dictionary rows of the terms of suggest_table that begin with the prefix [p, p + n), in byte order; table_idx (may be
+// nullptr): their rows in the table.  The table is sorted by bytes, so they are ONE range; more than max_expansions of them:
+// the best by (score descending, table row ascending) stay.
+bool Engine::expand_prefix_rows(const char* p, size_t n, uint32_t max_expansions, std::vector<uint32_t>& rows, std::vector<uint32_t>* table_idx, bool& truncated) const {
+    rows.clear();
+    if (table_idx) table_idx->clear();
+    truncated = false;
+    const nsx::SuggestTable& t = suggest_table;
+    // -1, 0, +1: term i against the prefix as a byte string; begins: the term has the prefix in front
+    auto begins = [&](size_t i) { return t.term_len(i) >= n && std::memcmp(t.term(i), p, n) == 0; };
+    auto below = [&](size_t i) {
+        const size_t m = std::min(t.term_len(i), n);
+        const int c = std::memcmp(t.term(i), p, m);
+        return c != 0 ? c < 0 : t.term_len(i) < n;
+    };
+    size_t lo = 0, hi = t.size();
+    while (lo < hi) { const size_t mid = (lo + hi) / 2; if (below(mid)) lo = mid + 1; else hi = mid; }
+    size_t end = lo, top = t.size();
+    while (end < top) { const size_t mid = (end + top) / 2; if (begins(mid)) end = mid + 1; else top = mid; }
+    std::vector<uint32_t> kept(end - lo);
+    for (size_t i = lo; i < end; i++) kept[i - lo] = (uint32_t)i;
+    if (kept.size() > max_expansions) {
+        truncated = true;
+        std::partial_sort(kept.begin(), kept.begin() + max_expansions, kept.end(),
+                          [&](uint32_t a, uint32_t b) { return t.score[a] != t.score[b] ? t.score[a] > t.score[b] : a < b; });
+        kept.resize(max_expansions);
+        std::sort(kept.begin(), kept.end());
+    }
+    for (const uint32_t i : kept) {
+        const int64_t gid = dict.find(t.term(i), t.term_len(i));
+        if (gid < 0 || (!rows.empty() && rows.back() == (uint32_t)gid)) continue;   // not a term of the lexicons as it stands; the table's second row of a term
+        rows.push_back((uint32_t)gid);
+        if (table_idx) table_idx->push_back(i);
+    }
+    return true;
+}
+
+bool Engine::expand_prefix(const std::string& prefix, uint32_t max_expansions, std::vector<std::string>& terms, bool& truncated) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    terms.clear();
+    truncated = false;
+    nsx::PrefixSpec ps;
+    ps.max_expansions = max_expansions;
+    if (!nsx::prefix_check(ps, err_)) { err_ = "expand_prefix: " + err_; return false; }
+    std::string norm;
+    nsx::normalize_token(prefix.data(), prefix.size(), norm);
+    std::vector<uint32_t> rows, idx;
+    expand_prefix_rows(norm.data(), norm.size(), max_expansions, rows, &idx, truncated);
+    for (const uint32_t i : idx) terms.emplace_back(suggest_table.term(i), suggest_table.term_len(i));
+    return true;
+}
+
+void Engine::release_prefix_segments(PrefixRows& px) {
+    for (ns_seg*& s : px.segs)
+        if (s) { (void)ns_segment_release(ctx_, s); s = nullptr; }
+}
+
+bool Engine::search_prefixed_after_batch_flat(const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                                              int k, const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                                              float* device_ms, std::vector<std::vector<nsx::PrefixInfo>>* prefixes) {
+    const char* fn = names_of(nsx::Dialect::Prefixed).after_batch;
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (prefixes) prefixes->assign(Q, std::vector<nsx::PrefixInfo>());
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: boolean queries run on the device, there is no CPU path"; return false; }
+    if (Q && (!queries || !hits || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    if (filter_handle) { err_ = std::string(fn) + ": a filter is refused: prefix terms do not run under a filter (a filtered union needs the unfiltered union's df for its idf)"; return false; }
+    if (!nsx::prefix_check(prefix_spec, err_)) { err_ = std::string(fn) + ": " + err_; return false; }
+    // the batch's distinct ordinary terms and distinct prefixes, in order of first appearance
+    PrefixRows px;
+    std::vector<std::vector<uint32_t>> per_query(prefixes ? Q : 0);
+    {
+        std::vector<char> scratch;
+        for (size_t q = 0; q < Q; q++)
+            nsx::for_each_prefixed_term(queries[q].p, queries[q].n, scratch, [&](const char* p, size_t n, uint8_t, uint32_t, uint32_t, float, bool star) {
+                if (!star) {
+                    const int64_t gid = dict.find(p, n);
+                    if (gid >= 0 && px.of_term.emplace((uint32_t)gid, (uint32_t)px.terms.size()).second) px.terms.push_back((uint32_t)gid);
+                    return;
+                }
+                const auto at = px.of_prefix.emplace(std::string(p, n), (uint32_t)px.info.size());
+                if (at.second) px.info.push_back(nsx::PrefixInfo{std::string(p, n), 0u, false});
+                if (prefixes && std::find(per_query[q].begin(), per_query[q].end(), at.first->second) == per_query[q].end()) per_query[q].push_back(at.first->second);
+            });
+    }
+    if (px.info.empty())   // no prefix anywhere: the Boosted call, untouched
+        return search_boosted_after_batch_flat(spec, 0, queries, Q, k, after, hits, nhits, found, rest, usable, device_ms);
+    const uint32_t n_ord = (uint32_t)px.terms.size(), P = (uint32_t)px.info.size(), S = (uint32_t)segments.size();
+    for (auto& kv : px.of_prefix) kv.second += n_ord;
+    px.expansions.resize(P);
+    for (uint32_t i = 0; i < P; i++) {
+        expand_prefix_rows(px.info[i].prefix.data(), px.info[i].prefix.size(), prefix_spec.max_expansions, px.expansions[i], nullptr, px.info[i].truncated);
+        px.info[i].expansions = (uint32_t)px.expansions[i].size();
+    }
+    if (prefixes)
+        for (size_t q = 0; q < Q; q++)
+            for (const uint32_t i : per_query[q]) (*prefixes)[q].push_back(px.info[i]);
+
+    CallPrep bp;
+    if (!boolean_prepare(fn, 0, bp)) return false;
+    if (spec) {
+        BoostSet* bs = nullptr;
+        if (!ensure_boosts(*spec, bs)) { err_ = std::string(fn) + ": " + err_; return false; }
+        for (const uint32_t s : bp.listed) bp.boosts.push_back(bs->dev[s]);
+    }
+    // one derived segment per listed position, under ids above the filters' range
+    if (((uint64_t)kMaxFilters + 2) * S > (1u << 20)) { err_ = std::string(fn) + ": the derived segments' ids would reach 2^20"; return false; }
+    const uint32_t id_base = (uint32_t)(kMaxFilters + 1) * S;
+    const nsx::TermSeg absent{nsx::kAbsent, 0u, 0.0f};
+    px.rows.assign((size_t)(n_ord + P) * S, absent);
+    px.segs.assign(S, nullptr);
+    struct Release { Engine* e; PrefixRows* px; ~Release() { e->release_prefix_segments(*px); } } release{this, &px};
+    float union_ms = 0.0f;
+    std::vector<uint64_t> off, noff, soff;
+    std::vector<uint32_t> cnt, gb, ncnt, scnt, row_of;
+    std::vector<float> idf_of;   // of a copied list: its dictionary row's; of a union: computed from its count
+    std::vector<uint8_t> is_union;
+    for (size_t li = 0; li < bp.listed.size(); li++) {
+        const uint32_t sid = bp.listed[li];
+        const nsx::SegmentData& sd = segments[sid];
+        // a list that lies inside the payload (a damaged record stays absent, as under a filter)
+        auto inside = [&](const nsx::TermSeg& e) { return e.byte_off != nsx::kAbsent && e.byte_off % 8 == 0 && e.byte_off / 8 + e.count <= sd.postings_bytes / 8; };
+        off.clear(); cnt.clear(); row_of.clear(); idf_of.clear(); is_union.clear();
+        gb.assign(1, 0u);
+        for (uint32_t r = 0; r < n_ord; r++) {
+            const nsx::TermSeg& e = dict.row(px.terms[r])[sid];
+            if (!inside(e)) continue;
+            off.push_back(e.byte_off); cnt.push_back(e.count);
+            gb.push_back((uint32_t)off.size()); row_of.push_back(r); idf_of.push_back(e.idf); is_union.push_back(0);
+        }
+        for (uint32_t i = 0; i < P; i++) {
+            const size_t first = off.size();
+            float own = 0.0f;
+            for (const uint32_t gid : px.expansions[i]) {
+                const nsx::TermSeg& e = dict.row(gid)[sid];
+                if (!inside(e)) continue;
+                off.push_back(e.byte_off); cnt.push_back(e.count);
+                own = e.idf;
+            }
+            if (off.size() == first) continue;   // an absent term of this segment
+            gb.push_back((uint32_t)off.size()); row_of.push_back(n_ord + i); idf_of.push_back(own); is_union.push_back(off.size() - first >= 2);
+        }
+        const uint32_t G = (uint32_t)row_of.size();
+        noff.assign(std::max<uint32_t>(G, 1), 0); ncnt.assign(std::max<uint32_t>(G, 1), 0);
+        float ms = 0.0f;
+        const int rc = ns_segment_union(ctx_, dev_segs_[sid], id_base + sid, off.data(), cnt.data(), gb.data(), G, noff.data(), ncnt.data(), nullptr, nullptr, nullptr, &ms,
+                                        &px.segs[sid]);
+        if (rc != NS_OK) { err_ = std::string("ns_segment_union: ") + ns_last_error(ctx_); return false; }
+        union_ms += ms;
+        const uint32_t min_count = std::max<uint32_t>(64u, sd.N / 512u);   // reload()'s rule for skip tables
+        soff.clear(); scnt.clear();
+        for (uint32_t g = 0; g < G; g++) {
+            if (is_union[g] && !ncnt[g]) continue;
+            px.rows[(size_t)row_of[g] * S + sid] = nsx::TermSeg{noff[g], ncnt[g], is_union[g] ? bm25_idf(sd.N, ncnt[g]) : idf_of[g]};
+            if (ncnt[g] >= min_count) { soff.push_back(noff[g]); scnt.push_back(ncnt[g]); }
+        }
+        if (!soff.empty()) (void)ns_segment_build_skips(ctx_, px.segs[sid], soff.data(), scnt.data(), (uint32_t)soff.size());
+        bp.ids[li] = id_base + sid;
+        bp.segs[li] = px.segs[sid];
+    }
+    bp.rs.rows = px.rows.data();
+    bp.rs.id_base = id_base;
+    bp.px = &px;
+    if (device_ms) *device_ms += union_ms;
+    if (Q == 0) return true;
+    const RankedOut out{(size_t)std::max(1, std::min(k, 100)), hits, nullptr, nhits, found, rest, device_ms};
+    return ranked_batch(fn, bp, after, Q, out,
+        [&](size_t a, size_t b) { return refs_range(fn, nsx::Dialect::Prefixed, queries, a, b, usable, bp); },
+        [&](size_t a, size_t b, const ns_cursor* cur, float* ms) { return ranked_call(nsx::Dialect::Prefixed, after != nullptr, bp, a, b, out, cur, ms); });
+}
+
+// one query's page of the prefixed call and the two members of its bodies, "prefixed" and "prefixes"
+bool Engine::prefix_page(const std::string& query, int k, const nsx::PageCursor* cur, const nsx::BoostSpec* boost, const nsx::PrefixSpec& ps, ns_hit* hits, uint32_t* nh,
+                         uint64_t* fd, uint64_t* rs, uint8_t* us, std::string& member) {
+    const QueryView qv{query.data(), query.size()};
+    std::vector<std::vector<nsx::PrefixInfo>> info;
+    if (!search_prefixed_after_batch_flat(boost, ps, 0, &qv, 1, k, cur, hits, nh, fd, rs, us, nullptr, &info)) return false;
+    member = prefixed_member(query) + prefixes_member(info[0]);
+    return true;
+}
+
+bool Engine::search_prefixed_text(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec, const nsx::DocFilter* f, std::string& body) {
+    const char* name = names_of(nsx::Dialect::Prefixed).text;
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
+    if (f) { body = err_ = std::string(name) + ": a filter is refused: prefix terms do not run under a filter (a filtered union needs the unfiltered union's df for its idf)"; return false; }
+    const int K = std::max(1, std::min(k, 100));
+    std::vector<ns_hit> hits((size_t)K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    std::string member;
+    if (!prefix_page(query, K, nullptr, spec, prefix_spec, hits.data(), &nh, &fd, nullptr, &us, member)) { body = err_; return false; }
+    SearchResult res;
+    res.query = query;
+    res.k = K;
+    res.segments = (int)segments.size();
+    res.has_found = us != 0;
+    res.found = fd;
+    if (res.has_found)
+        for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    std::string tail = to_json_impl(res).substr(2);
+    // "k" < "prefixed" < "prefixes" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
+    const size_t at = tail.find("  \"query\": ");
+    if (at == std::string::npos || (at != 0 && tail[at - 1] != '\n')) { body = err_ = std::string(name) + ": the search body has no query member"; return false; }
+    tail.insert(at, member);
+    body = "{\n" + (spec ? boost_member(*spec) : std::string()) + tail;
+    return true;
+}
+
+std::string Engine::search_prefixed(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_prefixed_text(query, k, spec, prefix_spec, f, body) ? body : error_body(body);
+}
+
 // ---- the named methods: forwards to the dialect forms --------------------------------------------------------------------
 bool Engine::search_boolean_batch_flat(uint32_t filter_handle, const QueryView* queries, size_t Q, int k, ns_hit* hits, uint32_t* nhits,
                                        uint64_t* found, uint8_t* usable, float* device_ms) {
@@ -3332,8 +3592,11 @@ bool Engine::search_after_batch_flat(uint32_t filter_handle, const QueryView* qu
 bool Engine::search_page_text(const std::string& query, int k, const std::string& cursor_text, const nsx::PageSpec& spec, std::string& body) {
     std::lock_guard<std::recursive_mutex> lock(mtx_);
     if (!ctx_) { body = err_ = "search_page: no device context: this engine has no CPU scoring path"; return false; }
-    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::Boosted) { body = err_ = "search_page: unknown mode"; return false; }
-    const nsx::BoostSpec* boost = (spec.mode == nsx::PageSpec::Boosted && spec.use_boost) ? &spec.boost : nullptr;
+    if ((unsigned)spec.mode > (unsigned)nsx::PageSpec::Prefixed) { body = err_ = "search_page: unknown mode"; return false; }
+    const bool prefixed = spec.mode == nsx::PageSpec::Prefixed;
+    if (prefixed && spec.use_filter) { body = err_ = "search_page: a filter is refused: prefix terms do not run under a filter (a filtered union needs the unfiltered union's df for its idf)"; return false; }
+    const nsx::BoostSpec* boost = ((spec.mode == nsx::PageSpec::Boosted || prefixed) && spec.use_boost) ? &spec.boost : nullptr;
+    std::string prefix_members;   // Prefixed: "prefixed" and "prefixes"
     const char kind = nsx::page_kind(spec.mode);
     nsx::PageCursor cur;
     if (!nsx::parse_cursor(cursor_text, kind, cur, err_)) { body = err_ = "search_page: " + err_; return false; }
@@ -3356,7 +3619,8 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     uint8_t us = 0;
     const nsx::PageCall call = nsx::page_call(spec.mode);
     bool ok = false;
-    if (!call.plain)
+    if (prefixed) ok = prefix_page(query, K, &cur, boost, spec.prefix, hits.data(), &nh, &fd, &rs, &us, prefix_members);
+    else if (!call.plain)
         ok = call.dated ? search_dialect_sorted_batch_flat(call.dialect, spec.sort, handle, &qv, 1, K, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us)
                         : search_dialect_after_batch_flat(call.dialect, handle, &qv, 1, K, &cur, hits.data(), &nh, &fd, &rs, &us, nullptr, boost);
     else if (call.dated) ok = search_sorted_after_batch_flat(spec.sort, handle, &qv, 1, K, NS_FLAG_OR, &cur, hits.data(), keys.data(), &nh, &fd, &rs, &us);
@@ -3372,7 +3636,8 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
     std::string o = head;
     std::string rest_of = to_json_impl(res).substr(2);   // "found" (when usable), "k", "query", "results", "segments"
-    if (!call.plain)   // the dialect's member, as in its search_* body
+    if (prefixed) o += boost ? boost_member(*boost) : std::string();   // its own members stand behind "page"
+    else if (!call.plain)   // the dialect's member, as in its search_* body
         if (const char* missing = insert_dialect_member(call.dialect, query, o, rest_of, boost)) { body = err_ = std::string("search_page: the search body has no ") + missing + " member"; return false; }
     // "k" < "page" < "query": nlohmann keeps keys sorted ("query" is escaped: no line of it starts like a member)
     const size_t at = rest_of.find("  \"query\": ");
@@ -3392,7 +3657,7 @@ bool Engine::search_page_text(const std::string& query, int k, const std::string
     }
     page += ",\n    \"offset\": " + std::to_string(fd - rs);
     page += ",\n    \"remaining\": " + std::to_string(rs - nh) + "\n  },\n";
-    rest_of.insert(at, page);
+    rest_of.insert(at, page + prefix_members);   // "page" < "prefixed" < "prefixes" < "query"
     o += rest_of;
     if (kind == 'd') {   // search_sorted's "sort" member behind "segments"
         o.resize(o.size() - 2);                 // the closing "\n}"

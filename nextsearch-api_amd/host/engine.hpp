@@ -22,6 +22,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -42,6 +43,7 @@
 #include "grouped.hpp"
 #include "quorum.hpp"
 #include "boost.hpp"
+#include "prefix.hpp"
 #include "page.hpp"
 #include "suggest.hpp"
 #include "term_dict.hpp"
@@ -467,6 +469,31 @@ public:
     void release_boosts();
     size_t boost_tables_on_device() const;   // factor tables with a device copy right now
 
+    // Prefix terms (host/prefix.hpp, csrc/ns_union.hip behind ns_segment_union): `vaccin*` in the Boosted dialect.
+    // expand_prefix: the terms of suggest_table that begin with `prefix` (lower-case alnum bytes; a term equal to it included),
+    // in byte order; more than max_expansions (1 .. 65535): those with the largest score, then the smallest bytes, are kept
+    // (suggest's order) and `truncated` is set; a kept term the dictionary does not hold is skipped, and a term the table holds
+    // twice comes once.  Host only: works on a host-only engine.  False, with a message, for a max_expansions out of range.
+    bool expand_prefix(const std::string& prefix, uint32_t max_expansions, std::vector<std::string>& terms, bool& truncated);
+    // search_boosted_after_batch_flat over nsx::parse_prefixed's dialect.  Per listed segment ONE ns_segment_union for the whole
+    // batch on the primary context: each distinct ordinary list the batch names is a single group, each distinct prefix one group
+    // of its expansions' lists there (none: an absent term; one: that term's own row, idf included; more: the union, its idf
+    // bm25_idf(N, its count)).  The derived segments take ids above the filters' range, serve the call through a call-local row
+    // table and are released before the call returns, on failure too; hits and cursors name manifest positions as everywhere.
+    // A batch without any prefix is forwarded to search_boosted_after_batch_flat untouched.  A non-zero filter handle is refused:
+    // a filtered union needs the unfiltered union's df for its idf.  prefixes (may be nullptr): per query its distinct prefixes
+    // in query order.  The search cache is not used.
+    bool search_prefixed_after_batch_flat(const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec, uint32_t filter_handle, const QueryView* queries, size_t Q,
+                                          int k, const nsx::PageCursor* after, ns_hit* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest, uint8_t* usable,
+                                          float* device_ms = nullptr, std::vector<std::vector<nsx::PrefixInfo>>* prefixes = nullptr);
+    // JSON text: search_boosted's body with "prefixed" in place of "boosted" (a prefix term prints with its '*'), and
+    // "prefixes": [{"expansions", "prefix", "truncated"}], the query's distinct prefixes in query order; keys stay sorted: both
+    // stand in front of "query".  A DocFilter is refused with a message.  search_page's mode Prefixed pages it with cursors of
+    // kind 's'.  Any failure: {"error": ...} (search_prefixed_text: false, body = the message).
+    std::string search_prefixed(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec = nsx::PrefixSpec{},
+                                const nsx::DocFilter* f = nullptr);
+    bool search_prefixed_text(const std::string& query, int k, const nsx::BoostSpec* spec, const nsx::PrefixSpec& prefix_spec, const nsx::DocFilter* f, std::string& body);
+
     // The calls above by dialect (nsx::Dialect, host/boolean.hpp): each named method forwards to one of these, which name
     // themselves in messages as the dialect's named method does.  DESIGN.md §5x lists what a fourth dialect adds.
     // boost (Dialect::Boosted only; may be nullptr): the factors of search_boosted_after_batch_flat and search_boosted_text.
@@ -585,6 +612,16 @@ private:
     OpenFilter* filter_of(uint32_t handle);
     bool translate_cursors(const char* fn, const nsx::PageCursor* after, size_t a, size_t b, uint32_t id_base, const std::vector<uint8_t>& listed,
                            bool filtered, std::vector<ns_cursor>& out);
+    // the rows of one search_prefixed_after_batch_flat call: the batch's distinct ordinary terms first, then its distinct prefixes
+    struct PrefixRows {
+        std::unordered_map<uint32_t, uint32_t> of_term;       // dictionary row -> call-local row
+        std::unordered_map<std::string, uint32_t> of_prefix;  // prefix -> call-local row
+        std::vector<uint32_t> terms;                          // call-local row -> dictionary row, the ordinary terms
+        std::vector<std::vector<uint32_t>> expansions;        // per prefix: the dictionary rows of its expansions, distinct
+        std::vector<nsx::PrefixInfo> info;                    // per prefix
+        std::vector<nsx::TermSeg> rows;                       // [call-local row][manifest position]
+        std::vector<ns_seg*> segs;                            // the derived segments per manifest position
+    };
     // What the ranked, facet and date-order calls share, plain and boolean alike: the filter's row source under a handle, the
     // segments the refs can name and the call's cursors.  The boolean dialects also keep the refs of one query range here (from
     // qd on); the plain calls keep theirs in PlainPrep.
@@ -604,7 +641,12 @@ private:
         std::vector<char> scratch;
         struct Term { int64_t row; uint8_t role; uint32_t clause, need; float weight; };   // row: the dictionary's, or -1
         std::vector<Term> terms;                // of one query
+        const PrefixRows* px = nullptr;          // Prefixed: the call-local rows that rs.rows holds (a term's row is one of THEM)
     };
+    bool expand_prefix_rows(const char* p, size_t n, uint32_t max_expansions, std::vector<uint32_t>& rows, std::vector<uint32_t>* table_idx, bool& truncated) const;
+    void release_prefix_segments(PrefixRows& px);
+    bool prefix_page(const std::string& query, int k, const nsx::PageCursor* cur, const nsx::BoostSpec* boost, const nsx::PrefixSpec& ps, ns_hit* hits, uint32_t* nh,
+                     uint64_t* fd, uint64_t* rs, uint8_t* us, std::string& member);
     // boolean_prepare's two halves.  filter_rows: the stale-handle check and the filter's row source.  list_segments: the
     // positions with a device copy (the index's own, or the filter's) that `keep` does not skip, in manifest order.
     bool filter_rows(const char* fn, uint32_t filter_handle, CallPrep& bp);

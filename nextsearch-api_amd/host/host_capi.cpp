@@ -1507,6 +1507,110 @@ extern "C" int nsh_engine_search_boosted_page_json(nsh_engine* e, const char* qu
 } NSH_CATCH(e, "nsh_engine_search_boosted_page_json", -1)
 }
 
+// ---- prefix terms (host/prefix.hpp) ----
+static nsx::PrefixSpec nsh_prefix_spec_of(uint32_t max_expansions) {
+    nsx::PrefixSpec ps;
+    if (max_expansions) ps.max_expansions = max_expansions;
+    return ps;
+}
+
+extern "C" uint32_t nsh_parse_prefixed(const char* query, char* buf, uint32_t cap, uint8_t* roles, uint32_t* clauses, uint32_t* needs, uint8_t* promoted,
+                                       float* weights, uint8_t* prefix, uint32_t terms_cap, uint32_t* min_should_out) { try {
+    uint32_t min_should = 0;
+    const auto terms = nsx::parse_prefixed(query ? query : "", &min_should);
+    for (size_t i = 0; i < terms.size() && i < terms_cap; i++) {
+        if (roles) roles[i] = terms[i].role;
+        if (clauses) clauses[i] = terms[i].clause;
+        if (needs) needs[i] = terms[i].need;
+        if (promoted) promoted[i] = terms[i].promoted ? 1 : 0;
+        if (weights) weights[i] = terms[i].weight;
+        if (prefix) prefix[i] = terms[i].prefix ? 1 : 0;
+    }
+    nsh_join_terms(terms, buf, cap);
+    if (min_should_out) *min_should_out = min_should;
+    return (uint32_t)terms.size();
+} NSH_CATCH(nullptr, "nsh_parse_prefixed", 0)
+}
+
+extern "C" int64_t nsh_engine_expand_prefix(nsh_engine* e, const char* prefix, uint32_t max_expansions, char* buf, uint64_t cap, uint64_t* bytes_out, int* truncated_out) { try {
+    if (!e) return -1;
+    std::vector<std::string> terms;
+    bool truncated = false;
+    if (!e->eng.expand_prefix(prefix ? prefix : "", nsh_prefix_spec_of(max_expansions).max_expansions, terms, truncated)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    std::string joined;
+    for (size_t i = 0; i < terms.size(); i++) {
+        if (i) joined.push_back(' ');
+        joined += terms[i];
+    }
+    if (bytes_out) *bytes_out = joined.size() + 1;
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(joined.size(), cap - 1);
+        std::memcpy(buf, joined.data(), n);
+        buf[n] = 0;
+    }
+    if (truncated_out) *truncated_out = truncated ? 1 : 0;
+    return (int64_t)terms.size();
+} NSH_CATCH(e, "nsh_engine_expand_prefix", -1)
+}
+
+extern "C" int nsh_engine_search_prefixed_after_batch(nsh_engine* e, const nsh_boost_spec* spec, uint32_t max_expansions, uint32_t filter_handle, const char* const* queries,
+                                                      uint32_t n_queries, int k, const nsh_page_cursor* after, void* hits, uint32_t* nhits, uint64_t* found, uint64_t* rest,
+                                                      uint8_t* has_found, float* device_ms_out) { try {
+    const char* fn = "nsh_engine_search_prefixed_after_batch";
+    if (!e) return -1;
+    nsx::BoostSpec sp;
+    std::string why;
+    bool have = false;
+    if (!nsh_boost_spec_of(e, spec, sp, have, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !nhits)) { nsh_set_err(e, std::string(fn) + ": null argument"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<nsx::PageCursor> cur;
+    nsh_cursors_of(after, n_queries, cur);
+    std::vector<uint64_t> f_, r_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!rest) { r_.resize(n_queries); rest = r_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    if (!e->eng.search_prefixed_after_batch_flat(have ? &sp : nullptr, nsh_prefix_spec_of(max_expansions), filter_handle, views.data(), n_queries, k, after ? cur.data() : nullptr,
+                                                 (ns_hit*)hits, nhits, found, rest, has_found, device_ms_out)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = rest[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_search_prefixed_after_batch", -1)
+}
+
+extern "C" int nsh_engine_search_prefixed_json(nsh_engine* e, const char* query, int k, const nsh_boost_spec* spec, uint32_t max_expansions, int use_filter,
+                                               const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::BoostSpec sp;
+        bool have = false;
+        return nsh_boost_spec_of(e, spec, sp, have, s) && e->eng.search_prefixed_text(query ? query : "", k, have ? &sp : nullptr, nsh_prefix_spec_of(max_expansions), f, s);
+    });
+} NSH_CATCH(e, "nsh_engine_search_prefixed_json", -1)
+}
+
+extern "C" int nsh_engine_search_prefixed_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, uint32_t max_expansions,
+                                                    int use_filter, const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
+    if (!e || !json_out) return -1;
+    *json_out = nullptr;
+    std::string s;
+    nsx::PageSpec ps;
+    ps.mode = nsx::PageSpec::Prefixed;
+    ps.prefix = nsh_prefix_spec_of(max_expansions);
+    bool ok = nsh_boost_spec_of(e, spec, ps.boost, ps.use_boost, s);
+    if (ok) {
+        ps.use_filter = use_filter != 0;
+        if (ps.use_filter) ps.filter = nsh_doc_filter(date_from, date_to, keep_undated);
+        ok = e->eng.search_page_text(query ? query : "", k, cursor ? cursor : "", ps, s);
+    }
+    return nsh_json_out(e, ok, s, json_out);
+} NSH_CATCH(e, "nsh_engine_search_prefixed_page_json", -1)
+}
+
 static int nsh_facet_boolean(nsh_engine* e, const std::string& fn, nsx::Dialect dialect, const nsh_facet_spec* spec, uint32_t filter_handle, const char* const* queries,
                              uint32_t n_queries, uint32_t* counts_out, uint64_t counts_cap, uint64_t* found, uint8_t* has_found, float* device_ms_out) {
     if (!e) return -1;

@@ -17,6 +17,7 @@
 
 #include "boolean.hpp"
 #include "boost.hpp"
+#include "prefix.hpp"
 #include "sorted.hpp"
 
 namespace nsx {
@@ -30,10 +31,11 @@ struct PageCursor {
 
 // which call a page is a page of
 struct PageSpec {
-    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6, Quorum = 7, QuorumSorted = 8, Boosted = 9 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u; Quorum*: §5w; Boosted: §5z
+    enum Mode { SearchOr = 0, SearchAnd = 1, Boolean = 2, Sorted = 3, BooleanSorted = 4, Grouped = 5, GroupedSorted = 6, Quorum = 7, QuorumSorted = 8, Boosted = 9, Prefixed = 10 };   // BooleanSorted: DESIGN.md §5t; Grouped*: §5u; Quorum*: §5w; Boosted: §5z; Prefixed: §5ab
     Mode mode = SearchOr;
-    bool use_boost = false;              // Boosted only: false = term weights alone
+    bool use_boost = false;              // Boosted and Prefixed only: false = term weights alone
     BoostSpec boost;
+    PrefixSpec prefix;                   // Prefixed only
     SortSpec sort;                       // Sorted, BooleanSorted, GroupedSorted and QuorumSorted only
     bool use_filter = false;
     DocFilter filter;
@@ -50,6 +52,7 @@ inline PageCall page_call(PageSpec::Mode m) {
         case PageSpec::Quorum: return {false, Dialect::Quorum, false};
         case PageSpec::QuorumSorted: return {false, Dialect::Quorum, true};
         case PageSpec::Boosted: return {false, Dialect::Boosted, false};
+        case PageSpec::Prefixed: return {false, Dialect::Prefixed, false};
         default: return {true, Dialect::Boolean, false};   // SearchOr, SearchAnd
     }
 }

@@ -144,4 +144,23 @@ inline void for_each_base_term(const char* text, size_t n, std::vector<char>& sc
     }
 }
 
+// for_each_base_term's sibling for a grammar with prefix terms (prefix.hpp): fn(ptr, len, is_prefix).  A '*' directly behind a
+// token's last byte, with no alphanumeric byte behind it (or the text ends there), makes the token a prefix: it is kept from 2 bytes
+// on and is NOT tested against the stop-word list.  Every other '*' is a separator, and every other token is for_each_base_term's.
+template <class Fn>
+inline void for_each_star_term(const char* text, size_t n, std::vector<char>& scratch, Fn fn) {
+    if (scratch.size() < n + 1) scratch.resize(n + 1);
+    char* buf = scratch.data();
+    size_t len = 0;
+    auto is_alnum = [](unsigned char c) { return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); };
+    for (size_t i = 0; i <= n; i++) {
+        const unsigned char c = i < n ? (unsigned char)text[i] : 0;
+        if (is_alnum(c)) { buf[len++] = (c >= 'A' && c <= 'Z') ? (char)(c - 'A' + 'a') : (char)c; continue; }
+        const bool star = i < n && c == '*' && len > 0 && !(i + 1 < n && is_alnum((unsigned char)text[i + 1]));
+        if (star) { if (len >= 2) fn((const char*)buf, len, true); }
+        else if (len >= 2 && !is_stopword_span(buf, len)) fn((const char*)buf, len, false);
+        len = 0;
+    }
+}
+
 }  // namespace nsx

@@ -68,7 +68,7 @@ HIP_SYMBOLS = [
     "ns_search_grouped_after", "ns_facet_count_grouped", "ns_search_sorted_grouped", "ns_grouped_kernel_ms",
     "ns_search_quorum_after", "ns_facet_count_quorum", "ns_search_sorted_quorum", "ns_quorum_kernel_ms",
     "ns_docboost_upload", "ns_docboost_release", "ns_search_boosted_after", "ns_boosted_kernel_ms",
-    "ns_segment_filter",
+    "ns_segment_filter", "ns_segment_union", "ns_ctx_union_scratch",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
     "ns_batch_bind_outputs", "ns_batch_run", "ns_batch_stream", "ns_batch_gap_ms", "ns_batch_sync", "ns_batch_fetch", "ns_batch_get_info",
@@ -92,6 +92,7 @@ HOST_SYMBOLS = [
     "nsh_engine_search_quorum_json", "nsh_engine_search_quorum_faceted_json", "nsh_engine_search_quorum_sorted_json",
     "nsh_engine_boost_table", "nsh_engine_release_boosts", "nsh_engine_boost_tables_on_device", "nsh_parse_boosted", "nsh_engine_search_boosted_after_batch",
     "nsh_engine_search_boosted_json", "nsh_engine_search_boosted_page_json",
+    "nsh_parse_prefixed", "nsh_engine_expand_prefix", "nsh_engine_search_prefixed_after_batch", "nsh_engine_search_prefixed_json", "nsh_engine_search_prefixed_page_json",
     "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
     "nsh_engine_facet_buckets", "nsh_engine_facet_batch", "nsh_engine_search_faceted_json", "nsh_engine_release_facets", "nsh_engine_facet_tables_on_device",
@@ -213,6 +214,8 @@ def hip_lib():
         L.ns_segment_build_skips.argtypes = [vp, vp, vp, vp, u32]
         L.ns_ctx_use_skips.argtypes = [vp, i32]
         L.ns_segment_filter.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, C.POINTER(u64), C.POINTER(C.c_float), C.POINTER(vp)]
+        L.ns_segment_union.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(vp)]
+        L.ns_ctx_union_scratch.argtypes = [vp, u64]
         L.ns_ctx_set_host_threads.argtypes = [vp, u32]
         L.ns_ctx_set_overlap.argtypes = [vp, i32]
         L.ns_segment_build_packed.argtypes = [vp, vp]
@@ -524,6 +527,14 @@ def host_lib():
             L.nsh_engine_search_boosted_after_batch.argtypes = [vp, bsp] + L.nsh_engine_search_boolean_after_batch.argtypes[1:]
             L.nsh_engine_search_boosted_json.argtypes = [vp, C.c_char_p, i32, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
             L.nsh_engine_search_boosted_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        if hasattr(L, "nsh_parse_prefixed"):   # (likewise: a host library from before the prefix terms)
+            L.nsh_parse_prefixed.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, vp, vp, vp, vp, u32, vp]
+            L.nsh_parse_prefixed.restype = u32
+            L.nsh_engine_expand_prefix.argtypes = [vp, C.c_char_p, u32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(i32)]
+            L.nsh_engine_expand_prefix.restype = C.c_int64
+            L.nsh_engine_search_prefixed_after_batch.argtypes = [vp, bsp, u32] + L.nsh_engine_search_boolean_after_batch.argtypes[1:]
+            L.nsh_engine_search_prefixed_json.argtypes = [vp, C.c_char_p, i32, bsp, u32, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+            L.nsh_engine_search_prefixed_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, bsp, u32, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         L.nsh_engine_facet_quorum_batch.argtypes = L.nsh_engine_facet_boolean_batch.argtypes
         L.nsh_engine_search_quorum_sorted_batch.argtypes = L.nsh_engine_search_boolean_sorted_batch.argtypes
         L.nsh_engine_search_quorum_json.argtypes = L.nsh_engine_search_boolean_json.argtypes
@@ -1202,6 +1213,52 @@ class Engine:
         sp, keep = self._boost_spec(boost)
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         return self._json_call("search_page", self._L.nsh_engine_search_boosted_page_json, _as_bytes(query), k, _as_bytes(cursor), sp,
+                               int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    # ---- prefix terms: `vaccin*` ----
+    def expand_prefix(self, prefix, max_expansions=0):
+        """Engine::expand_prefix (host only): (the terms of the autocomplete table that begin with `prefix`, in byte order;
+        truncated); max_expansions: 1 .. 65535, 0 = the default, 1024"""
+        b = _as_bytes(prefix)
+        need, trunc = C.c_uint64(), C.c_int()
+        n = self._L.nsh_engine_expand_prefix(self.h, b, int(max_expansions), None, 0, C.byref(need), C.byref(trunc))
+        if n < 0:
+            raise RuntimeError(f"expand_prefix failed: {self.error()}")
+        buf = C.create_string_buffer(max(int(need.value), 1))
+        n = self._L.nsh_engine_expand_prefix(self.h, b, int(max_expansions), buf, len(buf), None, C.byref(trunc))
+        terms = buf.value.decode().split(" ") if n else []
+        assert len(terms) == n
+        return terms, bool(trunc.value)
+
+    def search_prefixed_after_batch(self, queries, k, boost=None, max_expansions=0, after=None, handle=0, timing=False):
+        """Engine::search_prefixed_after_batch_flat: (hits Q x K, nhits, found, rest, has_found); as search_boosted_after_batch over
+        texts with prefix terms (`vaccin*`), each a blended term per segment; a non-zero handle is refused"""
+        sp, keep = self._boost_spec(boost)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        cu = None if after is None else page_cursors(after)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        nhits, found, rest, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_prefixed_after_batch(self.h, sp, int(max_expansions), int(handle), _cstr_array(queries), Q, int(k),
+                                                            cu.ctypes.data if cu is not None and Q else None, hits.ctypes.data, nhits.ctypes.data, found.ctypes.data,
+                                                            rest.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_prefixed_after_batch failed: {self.error()}")
+        out = (hits[:Q], nhits[:Q], found[:Q], rest[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_prefixed_json(self, query, k, boost=None, max_expansions=0, date_filter=None, check=True):
+        """Engine::search_prefixed: the JSON text; as search_boosted_json, with "prefixed" and "prefixes"; a date_filter is refused"""
+        sp, keep = self._boost_spec(boost)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_prefixed", self._L.nsh_engine_search_prefixed_json, _as_bytes(query), k, sp, int(max_expansions), int(date_filter is not None),
+                               _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    def search_prefixed_page_json(self, query, k, cursor="", boost=None, max_expansions=0, date_filter=None, check=True):
+        """Engine::search_page in mode Prefixed: one page of search_prefixed_json's ranking; cursor: "" or a page's "next" """
+        sp, keep = self._boost_spec(boost)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_page", self._L.nsh_engine_search_prefixed_page_json, _as_bytes(query), k, _as_bytes(cursor), sp, int(max_expansions),
                                int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
 
     def release_boosts(self):
@@ -2108,6 +2165,38 @@ def segment_filter(ctx, src, new_seg_id, keep_bits, byte_off, counts, payload_ca
     if rc != 0:
         raise RuntimeError(f"ns_segment_filter failed ({rc}): {L.ns_last_error(ctx).decode()}")
     return h, noff[:n], ncnt[:n], int(kept.value), float(ms.value), (payload[: kept.value] if payload is not None else None)
+
+
+def segment_union(ctx, src, new_seg_id, member_off, member_cnt, group_begin, n_docs=None):
+    """ns_segment_union (raw): the derived segment of handle `src` under id new_seg_id, one list per group.  n_docs: the
+    source's number of documents when the new payload is wanted back (None: it stays on the device).  Returns (handle, new
+    byte offsets, new counts, postings written, rounds, device ms, new payload as (n, 2) uint32 or None)."""
+    L = hip_lib()
+    off = np.ascontiguousarray(member_off, dtype=np.uint64)
+    cnt = np.ascontiguousarray(member_cnt, dtype=np.uint32)
+    gb = np.ascontiguousarray(group_begin, dtype=np.uint32)
+    n, G = len(off), max(len(gb) - 1, 0)
+    noff, ncnt = np.zeros(max(G, 1), dtype=np.uint64), np.zeros(max(G, 1), dtype=np.uint32)
+    payload = None
+    if n_docs is not None:   # the capacity is the caller's: single groups whole, groups of two or more min(sum of member counts, n_docs)
+        sums = [int(cnt[gb[g]:gb[g + 1]].sum(dtype=np.uint64)) for g in range(G)]
+        bound = sum(s if gb[g + 1] - gb[g] == 1 else min(s, int(n_docs)) for g, s in enumerate(sums))
+        payload = np.zeros((max(bound, 1), 2), dtype=np.uint32)
+    written, rounds, ms, h = C.c_uint64(), C.c_uint32(), C.c_float(), C.c_void_p()
+    rc = L.ns_segment_union(ctx, src, int(new_seg_id), off.ctypes.data if n else None, cnt.ctypes.data if n else None,
+                            gb.ctypes.data if len(gb) else None, G, noff.ctypes.data if G else None, ncnt.ctypes.data if G else None,
+                            payload.ctypes.data if payload is not None else None, C.byref(written), C.byref(rounds), C.byref(ms), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"ns_segment_union failed ({rc}): {L.ns_last_error(ctx).decode()}")
+    return h, noff[:G], ncnt[:G], int(written.value), int(rounds.value), float(ms.value), (payload[: written.value] if payload is not None else None)
+
+
+def ctx_union_scratch(ctx, nbytes):
+    """ns_ctx_union_scratch: table bytes per round of ns_segment_union (0: the default); raises on failure"""
+    L = hip_lib()
+    rc = L.ns_ctx_union_scratch(ctx, int(nbytes))
+    if rc != 0:
+        raise RuntimeError(f"ns_ctx_union_scratch failed ({rc}): {L.ns_last_error(ctx).decode()}")
 
 
 def facet_tile_docs():
