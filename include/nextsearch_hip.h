@@ -883,6 +883,41 @@ int ns_search_boosted_after(ns_ctx* ctx, const ns_query_desc* queries, uint32_t 
  * count them), summed over the calling thread's calls since the last reset: out2[0..1] = k_bq_select, k_bq_join, milliseconds. */
 int ns_boosted_kernel_ms(float* out2, int reset);
 
+/* ---- one hit per group: ranked hits collapsed by a per-document key ------------ */
+/* ns_search_boosted_after without a cursor, plus one group table per listed segment: an ns_dockeys table as ns_dockeys_upload
+ * makes it, indexed by docId (so it serves a filter's copy of the segment unchanged).
+ *   KEYS         0 keeps its meaning, "no key": the document stands alone and is never collapsed with anything, not even with
+ *                other key-0 documents.  Any other key names a group; the keys of one call are ONE key space, so equal keys in
+ *                different segments are the same group.  0xFFFFFFFF stays refused by the upload.
+ *   HITS         Take the sibling's matched set in its one total order: ord(bits of fp32(score * factor)) descending, then the
+ *                position of the segment in the call's list, then docId.  Delete every document that has an earlier document of
+ *                the same non-zero key.  The first K = clamp(k, 1, NS_MAX_K) of what remains are the hits: each is its group's
+ *                first member in the uncollapsed order and carries that document's score bits, segment and docId exactly as the
+ *                sibling reports them.
+ *   nhits[q]     min(K, distinct non-zero keys in the matched set + matched key-0 documents); the tail is padded as the sibling's.
+ *   found[q]     the size of the matched set in documents: the sibling's value.
+ *   groups_out   [q * K + r] the hit's key as uploaded (0 for a stand-alone hit, 0 in the padded tail).
+ *   others_out   [q * K + r] the matched documents of the whole call that carry the hit's key, minus one; 0 for key 0 and in the
+ *                tail.  Documents a NOT ref or a filter removed are not matched and not counted.  NULL skips that pass entirely.
+ *   Tables that are all 0, and tables in which every document has a key of its own, give ns_search_boosted_after(after = NULL)'s
+ *   hits, nhits and found byte for byte, through the collapsing kernels.  One key on every document gives one hit per query, the
+ *   sibling's first, with others = found - 1.
+ *   boosts / roles / clauses / needs == NULL mean what they mean in the sibling.
+ *   Refusals (NS_E_INVAL, nothing launched): the sibling's, and a NULL group table, a table of another ctx, a table whose n_docs
+ *   differs from its segment's.
+ * There is no cursor: a document behind a cursor represents its group only if no member lies in front of the cursor, which a
+ * cursor over tile-local rows cannot know.  The first K <= NS_MAX_K groups are what the call answers. */
+int ns_search_collapsed(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms,
+                        const uint8_t* roles /* n_terms; NULL = all SHOULD */, const uint16_t* clauses /* n_terms; NULL = the boolean call */,
+                        const uint8_t* needs /* n_terms; NULL = the grouped call */, uint32_t n_terms, uint32_t k,
+                        const uint32_t* seg_ids, ns_seg* const* segs, ns_docboost* const* boosts /* n_segs; NULL = none */,
+                        ns_dockeys* const* groups /* n_segs */, uint32_t n_segs, ns_hit* hits_out /* Q x K */,
+                        uint32_t* groups_out /* Q x K */, uint32_t* others_out /* Q x K; may be NULL */, uint32_t* nhits_out,
+                        uint64_t* found_out /* may be NULL */, float* device_ms_out /* may be NULL */);
+/* HIP-event time of the launches of ns_search_collapsed, summed over the calling thread's calls since the last reset:
+ * out3[0..2] = k_bq_select, k_bq_join_collapsed, k_cl_count (0 while no call asked for others), milliseconds. */
+int ns_collapsed_kernel_ms(float* out3, int reset);
+
 /* ---- tuning knobs (per ctx; 0 = library default) --------------------------------------------- */
 /* variant: 0 = the product's one scoring launch, k_uscore — every work item picks the driver-stream body, the doc-tile body
  * or (ns_ctx_use_pruning) the block-max body; term groups of more than 64 terms fall back to the workgroup-tile kernel

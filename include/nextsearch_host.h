@@ -642,6 +642,35 @@ int nsh_engine_search_prefixed_json(nsh_engine* e, const char* query, int k, con
 int nsh_engine_search_prefixed_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, uint32_t max_expansions,
                                          int use_filter, const char* date_from, const char* date_to, int keep_undated, char** json_out);
 
+/* ---- collapsed hits: one hit per title, author or custom key (host/collapse.hpp) ----
+ * kind: 0 title (a dense id per normalised title, by first appearance in manifest order; an empty title is key 0 = stands alone),
+ * 1 author (the same over the author field), 2 custom: `custom` holds one uint32 per document, the segments back to back in
+ * manifest order (n_custom of them; 0 = no key, 0xFFFFFFFF refused). */
+typedef struct nsh_collapse_spec {
+    uint32_t kind;
+    const uint32_t* custom;
+    uint64_t n_custom;
+} nsh_collapse_spec;
+/* Engine::collapse_table (host only: works with device < 0): the keys of every document, the segments back to back in manifest
+ * order, into out[0 .. cap); returns their number (call with cap = 0 to size the array), or -1 with a message. */
+int64_t nsh_engine_collapse_table(nsh_engine* e, const nsh_collapse_spec* spec, uint32_t* out, uint64_t cap);
+/* The device copies of a spec's keys are built by the first call that needs them and kept until another spec, a reload() or this
+ * call drops them. */
+void nsh_engine_release_collapse(nsh_engine* e);
+uint64_t nsh_engine_collapse_tables_on_device(nsh_engine* e);
+/* Engine::search_collapsed_batch_flat: nsh_engine_search_boosted_after_batch without cursors, one hit per group.  hits, groups and
+ * others are n_queries x clamp(k, 1, 100); groups[q * K + r] = the hit's key, others[q * K + r] = the other matched documents
+ * with that key (others may be NULL: not counted).  boost may be NULL.  A `*` prefix term is refused.  -1 with a message on
+ * failure. */
+int nsh_engine_search_collapsed_batch(nsh_engine* e, const nsh_collapse_spec* collapse, const nsh_boost_spec* boost, uint32_t filter_handle,
+                                      const char* const* queries, uint32_t n_queries, int k, void* hits, uint32_t* groups, uint32_t* others, uint32_t* nhits,
+                                      uint64_t* found, uint8_t* has_found, float* device_ms_out);
+/* Engine::search_collapsed: *json_out (free with nsh_free) = nsh_engine_search_boosted_json's body with "collapsed" in place of
+ * "boosted", "collapse": {"field": "title" | "author" | "custom"} in front of it and "others": n in every result.  On failure -1
+ * and {"error": ...}. */
+int nsh_engine_search_collapsed_json(nsh_engine* e, const char* query, int k, const nsh_collapse_spec* collapse, const nsh_boost_spec* boost, int use_filter,
+                                     const char* date_from, const char* date_to, int keep_undated, char** json_out);
+
 #ifdef __cplusplus
 }
 #endif

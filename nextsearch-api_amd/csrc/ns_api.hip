@@ -35,6 +35,7 @@
 #include "ns_sorted.hip"   // after ns_facet.hip (fc_cut, fc_mark, fc_lower_bound) and ns_similar.hip (ml_sort_up, ml_merge_down, ml_join)
 #include "ns_boolean.hip"  // after ns_sorted.hip (SdSet, sd_insert) and ns_facet.hip (fc_cut, fc_mark)
 #include "ns_boolean_sets.hip"  // after ns_boolean.hip (BqRef), ns_sorted.hip (SdSet, sd_key, sd_insert, DevSdSeg, af_clip) and ns_facet.hip
+#include "ns_collapse.hip"   // after ns_boolean.hip (CgSet, DevBqGroup) and ns_boolean_sets.hip (bs_matched); includes ns_collapse_plan.hpp (host only)
 #include "ns_sem.hip"
 #include "ns_suggest.hip"
 #include "ns_fuzzy.hip"
@@ -3546,6 +3547,149 @@ static int bq_search(ns_ctx* ctx, const char* fn, const ns_query_desc* queries, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// One hit per group (csrc/ns_boolean.hip k_bq_select<false, ., ., ., true> and k_bq_join_collapsed, csrc/ns_collapse.hip k_cl_count,
+// csrc/ns_collapse_plan.hpp)
+static thread_local float g_cl_ms[3] = {0.0f, 0.0f, 0.0f};   // k_bq_select, k_bq_join_collapsed, k_cl_count: summed over the thread's ns_search_collapsed calls (ns_collapsed_kernel_ms)
+
+extern "C" int ns_collapsed_kernel_ms(float* out3, int reset) {
+    if (!out3) return NS_E_INVAL;
+    for (int i = 0; i < 3; i++) out3[i] = g_cl_ms[i];
+    if (reset) g_cl_ms[0] = g_cl_ms[1] = g_cl_ms[2] = 0.0f;
+    return NS_OK;
+}
+
+// ns_search_boosted_after's validation and plan without a cursor; the block is run_ranked's plus the groups and others rows, and
+// per cut the count kernel runs behind the join when others are asked for.
+extern "C" int ns_search_collapsed(ns_ctx* ctx, const ns_query_desc* queries, uint32_t n_queries, const ns_term_ref* terms, const uint8_t* roles,
+                                   const uint16_t* clauses, const uint8_t* needs, uint32_t n_terms, uint32_t k, const uint32_t* seg_ids,
+                                   ns_seg* const* segs, ns_docboost* const* boosts, ns_dockeys* const* groups, uint32_t n_segs, ns_hit* hits_out,
+                                   uint32_t* groups_out, uint32_t* others_out, uint32_t* nhits_out, uint64_t* found_out, float* device_ms_out) {
+    const char* fn = "ns_search_collapsed";
+    if (!ctx) return fail(nullptr, NS_E_INVAL, "%s: ctx is NULL", fn);
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (n_queries == 0) return NS_OK;
+    if (!queries || !hits_out || !groups_out || !nhits_out || (n_terms && !terms)) return fail(ctx, NS_E_INVAL, "%s: null argument", fn);
+    if (!n_segs) return fail(ctx, NS_E_INVAL, "%s: no segment listed", fn);
+    if (!groups) return fail(ctx, NS_E_INVAL, "%s: null group tables", fn);
+    std::vector<FcSegView> views;
+    std::vector<DevFcSeg> dsegs;
+    std::vector<DevBqSeg> bqs(3 * (size_t)n_segs);   // n_segs DevBqSeg, n_segs DevBqBoost (zero without boosts), n_segs DevBqGroup
+    std::memset(bqs.data(), 0, bqs.size() * sizeof(DevBqSeg));
+    const int rc = bind_segments<void>(ctx, fn, seg_ids, segs, nullptr, nullptr, n_segs, views, dsegs, [&](uint32_t i, const ns_seg* s, const void*) {
+        bqs[i] = DevBqSeg{s->d_norm, seg_ids[i], n_segs};
+        if (boosts) {
+            const ns_docboost* t = boosts[i];
+            if (!t) return fail(ctx, NS_E_INVAL, "%s: segment or boost table %u is NULL", fn, i);
+            if (t->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: boost table %u does not belong to this ctx", fn, i);
+            if (t->n_docs < s->n_docs) return fail(ctx, NS_E_INVAL, "%s: boost table %u has %u factors, its segment has %u documents", fn, i, t->n_docs, s->n_docs);
+            const DevBqBoost b{t->d_boost, 0ull};
+            std::memcpy(&bqs[(size_t)n_segs + i], &b, sizeof(b));
+        }
+        const ns_dockeys* g = groups[i];
+        if (!g) return fail(ctx, NS_E_INVAL, "%s: segment or group table %u is NULL", fn, i);
+        if (g->ctx != ctx) return fail(ctx, NS_E_INVAL, "%s: group table %u does not belong to this ctx", fn, i);
+        if (g->n_docs != s->n_docs) return fail(ctx, NS_E_INVAL, "%s: group table %u keys %u documents, its segment has %u", fn, i, g->n_docs, s->n_docs);
+        const DevBqGroup dg{g->d_keys, 0ull};
+        std::memcpy(&bqs[2 * (size_t)n_segs + i], &dg, sizeof(dg));
+        return (int)NS_OK;
+    });
+    if (rc != NS_OK) return rc;
+    std::vector<BqRef> refs;
+    std::vector<FcItem> items;
+    RankedPlan plan;
+    CollapsePlan cp;
+    std::string why;
+    const uint32_t tile = ns_facet_tile_docs(), win = bq_win_docs(tile);
+    const uint16_t* const given = clauses;
+    clauses = bq_live_clauses(clauses, n_terms, roles);
+    if (!bq_live_needs(given, clauses, needs, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const bool grouped = clauses != nullptr;   // (with clauses the QUORUM kernels run: a call without needs plans need 1 everywhere)
+    uint32_t max_need = 0;
+    if (bq_plan_quorum(queries, n_queries, terms, roles, clauses, needs, n_terms, views.data(), n_segs, tile, refs, items, max_need, why) != NS_OK)
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    if (!ranked_call_plan(items, n_queries, k, nullptr, views, [](uint32_t bits) { return after_ord(bits); }, false, kSdCandBytes, plan, why))
+        return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    const uint32_t planes = grouped ? bq_launch_planes(max_need) : 0u;
+    if (!collapse_plan(plan, n_queries, others_out != nullptr, planes, cp, why)) return fail(ctx, NS_E_INVAL, "%s: %s", fn, why.c_str());
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    static const SelectKernel<BqRef, DevBqSeg> kSelect[2][2] = {{k_bq_select<false, false, false, false, true>, k_bq_select<false, false, false, true, true>},
+                                                                {k_bq_select<false, true, true, false, true>, k_bq_select<false, true, true, true, true>}};   // [clauses][boosts]
+    using CountKernel = void (*)(const FcItem*, const BqRef*, const DevFcSeg*, const DevBqSeg*, uint32_t, const uint32_t*, const uint32_t*, uint32_t*);
+    static const CountKernel kCount[2] = {k_cl_count<false, false>, k_cl_count<true, true>};
+    const SelectKernel<BqRef, DevBqSeg> select = kSelect[grouped][boosts != nullptr];
+    const CountKernel count = kCount[grouped];
+    const size_t select_lds = grouped ? bq_quorum_lds_bytes(win, planes) : bq_lds_bytes(win);
+    const uint32_t K = plan.K;
+    const size_t n_out = cp.out_slots;
+    CallBlock blk(ctx);
+#if defined(NS_VARIANTS) || defined(NS_COUNT)
+    if (select_lds > (48u << 10))   // (the test windows only: the product's fits the default)
+        blk.chk(hipFuncSetAttribute(reinterpret_cast<const void*>(select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds));
+#endif
+    if (cp.count_lds) blk.chk(hipFuncSetAttribute(reinterpret_cast<const void*>(count), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cp.count_lds));
+    const size_t per_cut = (size_t)cp.stages + 1;
+    const size_t o_items = blk.reserve(items.size() * sizeof(FcItem)), o_refs = blk.reserve(refs.size() * sizeof(BqRef)),
+                 o_segs = blk.reserve(dsegs.size() * sizeof(DevFcSeg)), o_aux = blk.reserve(bqs.size() * sizeof(DevBqSeg)),
+                 o_qoff = blk.reserve(plan.q_off.size() * 4), o_hits = blk.reserve(n_out * sizeof(ns_hit)), o_groups = blk.reserve(n_out * 4),
+                 o_others = blk.reserve(cp.count ? n_out * 4 : 0), o_nhits = blk.reserve((size_t)n_queries * 4),
+                 o_found = blk.reserve((size_t)n_queries * 8), o_cand = blk.reserve((size_t)plan.cand_rows * K * 8);   // <= kSdCandBytes
+    blk.alloc(plan.cuts.size() * per_cut);
+    if (blk.ok()) {
+        blk.upload(o_items, items.data(), items.size() * sizeof(FcItem));
+        blk.upload(o_refs, refs.data(), refs.size() * sizeof(BqRef));
+        blk.upload(o_segs, dsegs.data(), dsegs.size() * sizeof(DevFcSeg));
+        blk.upload(o_aux, bqs.data(), bqs.size() * sizeof(DevBqSeg));
+        blk.upload(o_qoff, plan.q_off.data(), plan.q_off.size() * 4);
+        blk.zero(o_found, (size_t)n_queries * 8);
+        const FcItem* d_items = blk.at<const FcItem>(o_items);
+        const BqRef* d_refs = blk.at<const BqRef>(o_refs);
+        const DevFcSeg* d_segs = blk.at<const DevFcSeg>(o_segs);
+        const DevBqSeg* d_aux = blk.at<const DevBqSeg>(o_aux);
+        uint32_t* d_others = cp.count ? blk.at<uint32_t>(o_others) : nullptr;
+        for (size_t i = 0; i < plan.cuts.size() && blk.ok(); i++) {
+            const SdBatch& b = plan.cuts[i];
+            const uint32_t n_it = b.item_end - b.item_begin;
+            blk.record(i * per_cut + 0);
+            if (n_it) {
+                hipLaunchKernelGGL(select, dim3(n_it), dim3(256), select_lds, blk.st, d_items + b.item_begin, d_refs, d_segs, d_aux, K, win, blk.at<uint64_t>(o_cand),
+                                   blk.at<unsigned long long>(o_found), (const uint64_t*)nullptr, (unsigned long long*)nullptr);
+                blk.launched();
+            }
+            blk.record(i * per_cut + 1);
+            hipLaunchKernelGGL(k_bq_join_collapsed, dim3((b.q_end - b.q_begin + 3) / 4), dim3(256), 0, blk.st, d_items, blk.at<const uint32_t>(o_qoff), b.q_begin,
+                               b.q_end, b.item_begin, d_aux, blk.at<const uint64_t>(o_cand), K, blk.at<uint32_t>(o_hits), blk.at<uint32_t>(o_nhits),
+                               blk.at<uint32_t>(o_groups), d_others);
+            blk.launched();
+            blk.record(i * per_cut + 2);
+            if (cp.count) {
+                if (n_it) {
+                    hipLaunchKernelGGL(count, dim3(n_it), dim3(256), cp.count_lds, blk.st, d_items + b.item_begin, d_refs, d_segs, d_aux, K,
+                                       blk.at<const uint32_t>(o_nhits), blk.at<const uint32_t>(o_groups), d_others);
+                    blk.launched();
+                }
+                blk.record(i * per_cut + 3);
+            }
+        }
+        blk.fetch(hits_out, o_hits, n_out * sizeof(ns_hit));
+        blk.fetch(groups_out, o_groups, n_out * 4);
+        if (cp.count) blk.fetch(others_out, o_others, n_out * 4);
+        blk.fetch(nhits_out, o_nhits, (size_t)n_queries * 4);
+        if (found_out) blk.fetch(found_out, o_found, (size_t)n_queries * 8);
+        blk.sync();
+        if (blk.ok()) {
+            float sum = 0.0f;
+            for (size_t i = 0; i < plan.cuts.size(); i++)
+                for (uint32_t j = 0; j < cp.stages; j++) {
+                    float ms = 0.0f;
+                    if (blk.elapsed_ms(i * per_cut + j, i * per_cut + j + 1, &ms)) { g_cl_ms[j] += ms; sum += ms; }
+                }
+            if (device_ms_out) *device_ms_out = sum;
+        }
+    }
+    return blk.finish(fn);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Facet counts and date order for boolean queries (csrc/ns_boolean_sets.hip)
 static thread_local float g_bs_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // k_bs_count, k_bs_select, k_sd_join, k_bs_score: summed over the thread's calls (ns_boolean_sets_kernel_ms)
 
@@ -4279,6 +4423,8 @@ extern "C" int ns_debug_boolean_groups_counters(unsigned long long* out, int res
 extern "C" int ns_debug_boolean_quorum_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBqcnt>(HIP_SYMBOL(ns::g_ns_bqcnt), out, reset); }
 // per-document factors (ns_boolean.hip k_bq_select<true, ., ., true>): 8 values
 extern "C" int ns_debug_boolean_boost_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBbcnt>(HIP_SYMBOL(ns::g_ns_bbcnt), out, reset); }
+// one hit per group (ns_boolean.hip k_bq_select<false, ., ., ., true>, k_bq_join_collapsed; ns_collapse.hip k_cl_count): 14 values
+extern "C" int ns_debug_collapse_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsClcnt>(HIP_SYMBOL(ns::g_ns_clcnt), out, reset); }
 // facets and date order of boolean queries (ns_boolean_sets.hip k_bs_count, k_bs_select, k_bs_score): 12 values
 extern "C" int ns_debug_boolean_sets_counters(unsigned long long* out, int reset) { return debug_counters<ns::kNsBscnt>(HIP_SYMBOL(ns::g_ns_bscnt), out, reset); }
 // the corrector's and completion's build, scan and select kernels (ns_fuzzy.hip): 17 values

@@ -34,6 +34,7 @@
 #include <cstdint>
 
 #include "ns_boolean_plan.hpp"
+#include "ns_collapse_plan.hpp"   // cl_others_seed (host and device)
 
 namespace ns {
 
@@ -49,6 +50,17 @@ struct DevBqBoost {
     uint64_t pad;
 };
 static_assert(sizeof(DevBqBoost) == sizeof(DevBqSeg), "the two share one array");
+// Per-document groups (§5ac, ns_search_collapsed): a third sibling.  The array of a COLLAPSE launch carries n_segs DevBqSeg, n_segs
+// DevBqBoost (read by its BOOST instantiations alone) and n_segs DevBqGroup; boost_at = n_segs in every entry, so segment s's
+// group table is entry 2 * boost_at + s.
+struct DevBqGroup {
+    const uint32_t* group;  // per document: the segment's n_docs keys of an ns_dockeys table (0 = stands alone)
+    uint64_t pad;
+};
+static_assert(sizeof(DevBqGroup) == sizeof(DevBqSeg), "the three share one array");
+__device__ __forceinline__ const uint32_t* bq_group_table(const DevBqSeg* __restrict__ bqs, uint32_t seg) {
+    return reinterpret_cast<const DevBqGroup*>(bqs)[2u * bqs[seg].boost_at + seg].group;
+}
 
 #ifdef NS_COUNT
 // Counting build only: events of the two kernels since the last reset (ns_debug_boolean_counters).  0 items, 1 windows,
@@ -79,12 +91,25 @@ __device__ unsigned long long g_ns_bqcnt[kNsBqcnt];
 constexpr int kNsBbcnt = 8;
 __device__ unsigned long long g_ns_bbcnt[kNsBbcnt];
 #define NS_BBCNT(i, v) do { if (BOOST && threadIdx.x == 0) atomicAdd(&g_ns_bbcnt[(i)], (unsigned long long)(v)); } while (0)
+// One hit per group (§5ac; ns_debug_collapse_counters), the COLLAPSE instantiations of k_bq_select, k_bq_join_collapsed and
+// ns_collapse.hip's k_cl_count.  Counted per wave: 0 rounds of 64 skipped on the threshold ballot, 1 candidates dropped because their
+// group's kept entry is better, 2 replacements, 3 replacements or evictions that moved an entry across the hi / lo register
+// boundary, 4 fresh insertions, 5 key-0 candidates that beat the threshold, 6 rounds in which two survivors carry one group,
+// 7 duplicates met while the four waves' sets are merged, 8 join duplicates from two tiles of one segment, 9 join duplicates
+// from two segments.  10 documents the count pass counted, 11 work items it skipped (no grouped hit), 12 work items of the
+// collapsing select, 13 work items of the count pass.
+constexpr int kNsClcnt = 14;
+__device__ unsigned long long g_ns_clcnt[kNsClcnt];
+#define NS_CLCNT(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_ns_clcnt[(i)], (unsigned long long)(v)); } while (0)
+#define NS_CLCNT_WAVE(i, v) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&g_ns_clcnt[(i)], (unsigned long long)(v)); } while (0)
 #else
 #define NS_BCNT(i, v)
 #define NS_BCNT_WAVE(i, v)
 #define NS_BGCNT(i, v)
 #define NS_BQCNT(i, v)
 #define NS_BBCNT(i, v)
+#define NS_CLCNT(i, v)
+#define NS_CLCNT_WAVE(i, v)
 #endif
 
 __device__ __forceinline__ uint32_t bq_ord(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
@@ -105,6 +130,91 @@ __device__ __forceinline__ void bq_insert(SdSet& s, uint64_t key, uint32_t K, ui
     }
 #else
     sd_insert(s, key, K, lane);
+#endif
+}
+
+// The collapsing kept set (§5ac): SdSet with a 32-bit group next to each key.  INVARIANT: slots 0 .. K - 1 (hi lane 0 .. 63, then lo
+// lane 0 .. 63) hold distinct keys, descending, 0 = none and then nothing behind it; no two of them carry the same non-zero
+// group; slots K .. 127 are empty.  Group 0 stands alone: it never equals a kept group.
+struct CgSet {
+    uint64_t hi, lo;
+    uint32_t ghi, glo;
+};
+__device__ __forceinline__ uint64_t cg_shfl_up1(uint64_t key) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)key, 1u, 64);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(key >> 32), 1u, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+// One candidate, the same in all 64 lanes (key != 0).  p: the slot of the group's kept entry, or K - 1, the slot a fresh entry
+// pushes out.  ins: how many kept keys are larger, the slot the candidate would take.  ins > p: the group's entry is better, or K
+// kept keys are; nothing changes.  Else the candidate takes slot ins, the entries of [ins, p) move down by one, and what was in
+// slot p (the group's worse entry, or the K-th key) is gone: one group less or the same groups, still sorted.
+// STAGE (the counting build's): 0 the sweep, 1 the merge of the four waves' sets, 2 the join; dup_low: the low word of the kept
+// entry a duplicate met, else untouched.  Returns whether the candidate's group was kept already.
+template <int STAGE>
+__device__ __forceinline__ bool cg_insert_one(CgSet& s, uint64_t key, uint32_t g, uint32_t K, uint32_t lane, uint32_t& dup_low) {
+    const unsigned long long mh = __ballot(g != 0u && s.hi != 0ull && s.ghi == g);
+    const unsigned long long ml = K > 64u ? __ballot(g != 0u && s.lo != 0ull && s.glo == g) : 0ull;
+    const bool dup = (mh | ml) != 0ull;
+    const uint32_t p = mh ? (uint32_t)__builtin_ctzll(mh) : ml ? 64u + (uint32_t)__builtin_ctzll(ml) : K - 1u;
+    uint32_t ins = (uint32_t)__popcll(__ballot(s.hi > key));
+    if (K > 64u) ins += (uint32_t)__popcll(__ballot(s.lo > key));
+#ifdef NS_COUNT
+    if (dup) dup_low = p < 64u ? (uint32_t)ml_shfl(s.hi, p) : (uint32_t)ml_shfl(s.lo, p - 64u);
+    if (g == 0u) NS_CLCNT_WAVE(5, 1);
+    if (dup && STAGE == 1) NS_CLCNT_WAVE(7, 1);
+    if (dup && ins > p) NS_CLCNT_WAVE(1, 1);
+    if (dup && ins <= p) NS_CLCNT_WAVE(2, 1);
+    if (!dup && ins <= p) NS_CLCNT_WAVE(4, 1);
+    if (ins < 64u && p >= 64u) NS_CLCNT_WAVE(3, 1);   // (ins <= p: what was in hi lane 63 is in lo lane 0 afterwards)
+#else
+    (void)dup_low;
+#endif
+    if (ins > p) return dup;                            // (wave-uniform)
+    if (K > 64u && p >= 64u) {                          // lo first: it takes hi's last entry as it still is
+        const uint32_t i = 64u + lane;
+        const uint64_t from_hi = ml_shfl(s.hi, 63u), up = cg_shfl_up1(s.lo);
+        const uint32_t g_from_hi = (uint32_t)__shfl((int)s.ghi, 63, 64), g_up = (uint32_t)__shfl_up((int)s.glo, 1u, 64);
+        if (i == ins) { s.lo = key; s.glo = g; }
+        else if (i > ins && i <= p) { s.lo = lane ? up : from_hi; s.glo = lane ? g_up : g_from_hi; }
+    }
+    if (ins < 64u) {
+        const uint64_t up = cg_shfl_up1(s.hi);
+        const uint32_t g_up = (uint32_t)__shfl_up((int)s.ghi, 1u, 64);
+        if (lane == ins) { s.hi = key; s.ghi = g; }
+        else if (lane > ins && lane <= p) { s.hi = up; s.ghi = g_up; }
+    }
+    return dup;
+}
+// Offers one (key, group) per lane (any order, key 0 = none).  All 64 lanes call it together.  The threshold skip is sd_insert's:
+// a key at or below the K-th kept key cannot enter on its own and cannot be its group's best among the kept, whose keys are all
+// above it.  The survivors of the ballot are taken one at a time in lane order, so a second member of a group finds the first in
+// the set; a survivor the growing threshold has overtaken meanwhile drops out at ins > p.
+// on_dup(low): called (wave-uniformly) for every survivor whose group was kept already, with the low word of the kept entry it met;
+// the counting build's join tells the two kinds of duplicate apart with it, every other caller passes nothing (CgNoDup).
+struct CgNoDup { __device__ __forceinline__ void operator()(uint32_t) const {} };
+template <int STAGE, class OnDup = CgNoDup>
+__device__ __forceinline__ void cg_insert(CgSet& s, uint64_t key, uint32_t g, uint32_t K, uint32_t lane, OnDup on_dup = OnDup()) {
+    const uint64_t thr = K <= 64u ? ml_shfl(s.hi, K - 1u) : ml_shfl(s.lo, K - 65u);   // the current K-th key (0 while fewer are kept)
+    unsigned long long live = __ballot(key > thr);
+    if (live == 0ull) { NS_CLCNT_WAVE(0, 1); return; }                                // (wave-uniform)
+#ifdef NS_COUNT
+    bool pair = false;
+    const unsigned long long all = live;
+#endif
+    while (live) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(live);
+        live &= live - 1ull;
+        const uint64_t k1 = ml_shfl(key, l);
+        const uint32_t g1 = (uint32_t)__shfl((int)g, (int)l, 64);
+#ifdef NS_COUNT
+        pair = pair || (g1 != 0u && (__ballot(g == g1 && lane > l) & all) != 0ull);
+#endif
+        uint32_t low = 0;
+        if (cg_insert_one<STAGE>(s, k1, g1, K, lane, low)) on_dup(low);
+    }
+#ifdef NS_COUNT
+    if (pair) NS_CLCNT_WAVE(6, 1);
 #endif
 }
 
@@ -310,7 +420,12 @@ __host__ __device__ inline size_t bq_quorum_lds_bytes(uint32_t win, uint32_t pla
 // score stage stored it to LDS and a barrier lies in between, so the multiply is one rounding of its own and cannot be contracted
 // into the last accumulation (it is written __fmul_rn all the same).  A negative score times 0.0f is -0.0f, which ord puts just
 // below +0.0f.  With BOOST = false the code is what it was without the parameter.
-template <bool AFTER, bool GROUPED = false, bool QUORUM = false, bool BOOST = false>
+// COLLAPSE (§5ac, ns_search_collapsed; instantiated without AFTER: the call has no cursor): in the sweep the lane that owns a set bit
+// gathers its document's group from the segment's DevBqGroup, 4 bytes next to the factor, and the keys go through the collapsing
+// set (CgSet / cg_insert) in place of SdSet.  The four waves' sets meet in s_rows as keys alone: wave 0 gathers a key's group again
+// by the docId in its low word, so the LDS is what it was.  The item's row holds the tile's best K groups by their tile-best
+// document, keys alone.  With COLLAPSE = false the code is what it was without the parameter.
+template <bool AFTER, bool GROUPED = false, bool QUORUM = false, bool BOOST = false, bool COLLAPSE = false>
 __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ items, const BqRef* __restrict__ refs,
                                                    const DevFcSeg* __restrict__ segs, const DevBqSeg* __restrict__ bqs, uint32_t K,
                                                    uint32_t win, uint64_t* __restrict__ cand, unsigned long long* __restrict__ found,
@@ -328,9 +443,12 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     const DevFcSeg sg = segs[it.seg];
     const float* __restrict__ norm = bqs[it.seg].norm;
     const float* __restrict__ boost = BOOST ? reinterpret_cast<const DevBqBoost*>(bqs)[bqs[it.seg].boost_at + it.seg].boost : nullptr;
+    static_assert(!(COLLAPSE && AFTER), "the collapsed call has no cursor");
+    const uint32_t* __restrict__ grp = COLLAPSE ? bq_group_table(bqs, it.seg) : nullptr;
     const BqRef* __restrict__ rf = refs + it.ref_begin;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, v = tid >> 6;
     NS_BCNT(0, 1);
+    if (COLLAPSE) NS_CLCNT(12, 1);
     NS_BBCNT(0, 1);
     NS_BBCNT(QUORUM ? 7 : GROUPED ? 6 : 5, 1);
     if (tid == 0) s_cnt = 0u;
@@ -353,6 +471,7 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     NS_BGCNT(0, 1);
     if (QUORUM) NS_BQCNT(0, 1);
     SdSet set{0ull, 0ull};
+    CgSet cset{0ull, 0ull, 0u, 0u};   // COLLAPSE: in place of `set`
     uint32_t cnt = 0;
 #ifdef NS_COUNT
     bool swept = false;   // BOOST: a window of the item reached the sweep (workgroup-uniform)
@@ -460,9 +579,11 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
             cnt += (uint32_t)__popc(bits);
             while (__ballot(bits != 0u) != 0ull) {
                 uint64_t key = 0;
+                uint32_t g = 0;
                 if (bits) {
                     const uint32_t rel = w * 32u + (uint32_t)__builtin_ctz(bits);   // < n: only such bits are set
                     bits &= bits - 1u;
+                    if (COLLAPSE) g = grp[w_lo + rel];   // w_lo + rel < w_hi <= n_docs = the table's length (the call checked)
                     float score = s_acc[rel];
                     if (BOOST) {
                         const float f = boost[w_lo + rel];   // w_lo + rel < w_hi <= n_docs <= the table's length (the call checked)
@@ -478,7 +599,8 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
                 if (BOOST && key != 0ull && key > last) clipped++;
 #endif
                 if (AFTER) key = af_clip(key, last, kept);
-                bq_insert(set, key, K, lane);
+                if (COLLAPSE) cg_insert<0>(cset, key, g, K, lane);
+                else bq_insert(set, key, K, lane);
             }
         }
 #ifdef NS_COUNT
@@ -496,18 +618,32 @@ __global__ void __launch_bounds__(256) k_bq_select(const FcItem* __restrict__ it
     __syncthreads();   // (s_cnt is zero; nobody reads the accumulators any more)
     if (cnt) atomicAdd(&s_cnt, cnt);
     if (AFTER && kept) atomicAdd(&s_rest, kept);
-    s_rows[v][lane] = set.hi;
-    s_rows[v][64u + lane] = set.lo;
+    s_rows[v][lane] = COLLAPSE ? cset.hi : set.hi;
+    s_rows[v][64u + lane] = COLLAPSE ? cset.lo : set.lo;
     __syncthreads();
     if (v != 0u) return;
     if (tid == 0 && s_cnt) atomicAdd(&found[it.query], (unsigned long long)s_cnt);
     if (AFTER && tid == 0 && s_rest) atomicAdd(&rest[it.query], (unsigned long long)s_rest);
+    uint64_t* __restrict__ row = cand + (size_t)blockIdx.x * K;
+    if (COLLAPSE) {
+#pragma unroll 1
+        for (uint32_t o = 1; o < 4u; o++)
+#pragma unroll 1
+            for (uint32_t half = 0; half < (K > 64u ? 2u : 1u); half++) {
+                const uint64_t key = s_rows[o][half * 64u + lane];
+                // the key's document is it.doc_lo + ~low < it.doc_hi <= n_docs: the sweep made it from such a document
+                const uint32_t g = key ? grp[it.doc_lo + ~(uint32_t)key] : 0u;
+                cg_insert<1>(cset, key, g, K, lane);
+            }
+        if (lane < K) row[lane] = cset.hi;
+        if (64u + lane < K) row[64u + lane] = cset.lo;
+        return;
+    }
 #pragma unroll 1
     for (uint32_t o = 1; o < 4u; o++) {
         bq_insert(set, s_rows[o][lane], K, lane);
         if (K > 64u) bq_insert(set, s_rows[o][64u + lane], K, lane);
     }
-    uint64_t* __restrict__ row = cand + (size_t)blockIdx.x * K;
     if (lane < K) row[lane] = set.hi;
     if (64u + lane < K) row[64u + lane] = set.lo;
 }
@@ -563,6 +699,68 @@ __global__ void __launch_bounds__(256) k_bq_join(const FcItem* __restrict__ item
             hits[at * 3u + 1u] = 0xFFFFFFFFu;
             hits[at * 3u + 2u] = 0xFFFFFFFFu;
         }
+    }
+    if (lane == 0) nhits[q] = n;
+}
+
+// k_bq_join for ns_search_collapsed (§5ac), a kernel of its own so that k_bq_join keeps its name and its figures.  The rows of a
+// query's items are joined through the collapsing set; a candidate's group is gathered from its item's segment table by its
+// docId.  EXACT: a row holds its tile's best K groups by their tile-best document.  A group of the global first K has its
+// global best in some tile; the groups that beat it there beat it globally too, so there are fewer than K of them and it is in
+// that tile's row; of two rows' entries of one group the insertion keeps the better.  Writes the hits and the pad as k_bq_join
+// does, groups[q * K + r] = the hit's group (0 in the pad) and, with others != NULL, others[q * K + r] = 0xFFFFFFFF for a hit
+// with a group and 0 otherwise: k_cl_count adds the group's matched documents, the hit among them, and the sum is "others".
+__global__ void __launch_bounds__(256) k_bq_join_collapsed(const FcItem* __restrict__ items, const uint32_t* __restrict__ q_off, uint32_t q_begin,
+                                                           uint32_t q_end, uint32_t item_begin, const DevBqSeg* __restrict__ bqs,
+                                                           const uint64_t* __restrict__ cand, uint32_t K, uint32_t* __restrict__ hits,
+                                                           uint32_t* __restrict__ nhits, uint32_t* __restrict__ groups,
+                                                           uint32_t* __restrict__ others) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = q_begin + blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= q_end) return;                                            // (wave-uniform; no barrier in this kernel)
+    const uint32_t ib = q_off[q], ie = q_off[q + 1u];
+    CgSet set{0ull, 0ull, 0u, 0u};
+    for (uint32_t i = ib; i < ie; i++) {
+        const uint64_t* __restrict__ row = cand + (size_t)(i - item_begin) * K;
+        if (row[0] == 0ull) continue;                                  // an item that matched nothing (wave-uniform)
+        const FcItem it = items[i];
+        const uint32_t* __restrict__ grp = bq_group_table(bqs, it.seg);
+        const uint32_t base = (i - ib) * kSdRowSlots;
+#pragma unroll 1
+        for (uint32_t slot = lane; slot < kSdRowSlots && slot - lane < K; slot += 64u) {   // (wave-uniform: slot - lane is 0 or 64)
+            const uint64_t c = slot < K ? row[slot] : 0ull;
+            const uint64_t key = c ? ((c >> 32) << 32) | (uint32_t)~(base + slot) : 0ull;
+            const uint32_t g = c ? grp[it.doc_lo + ~(uint32_t)c] : 0u;   // a document of the tile: < doc_hi <= n_docs
+#ifdef NS_COUNT
+            cg_insert<2>(set, key, g, K, lane, [&](uint32_t low) { NS_CLCNT_WAVE(items[ib + ~low / kSdRowSlots].seg == it.seg ? 8 : 9, 1); });
+#else
+            cg_insert<2>(set, key, g, K, lane);
+#endif
+        }
+    }
+    uint32_t n = 0;
+#pragma unroll 1
+    for (uint32_t r = lane; r - lane < K; r += 64u) {                  // (r - lane is 0 or 64; K <= 128)
+        const uint64_t jk = r < 64u ? set.hi : set.lo;
+        const uint32_t g = r < 64u ? set.ghi : set.glo;
+        const bool have = r < K && jk != 0ull;
+        n += (uint32_t)__popcll(__ballot(have));
+        if (r >= K) continue;
+        const size_t at = (size_t)q * K + r;
+        if (have) {
+            const uint32_t low = ~(uint32_t)jk, rel = low / kSdRowSlots, slot = low % kSdRowSlots;
+            const FcItem it = items[ib + rel];
+            const uint64_t c = cand[(size_t)(ib + rel - item_begin) * K + slot];
+            hits[at * 3u + 0u] = bq_unord((uint32_t)(c >> 32));
+            hits[at * 3u + 1u] = bqs[it.seg].seg_id;
+            hits[at * 3u + 2u] = it.doc_lo + ~(uint32_t)c;
+        } else {
+            hits[at * 3u + 0u] = 0xFF800000u;                         // -inf
+            hits[at * 3u + 1u] = 0xFFFFFFFFu;
+            hits[at * 3u + 2u] = 0xFFFFFFFFu;
+        }
+        groups[at] = have ? g : 0u;
+        if (others) others[at] = cl_others_seed(g, have);
     }
     if (lane == 0) nhits[q] = n;
 }

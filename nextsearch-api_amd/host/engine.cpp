@@ -60,6 +60,7 @@ void Engine::release_device_segments() {
     release_facets();
     release_sorted();
     release_boosts();
+    release_collapse();
     close_all_filters();
     if (ctx_)
         for (ns_seg* s : dev_segs_)
@@ -3192,6 +3193,174 @@ bool Engine::ensure_boosts(const nsx::BoostSpec& spec, BoostSet*& out) {
     }
     out = &boosts_;
     return true;
+}
+
+// ---- collapsed hits (host/collapse.hpp) -------------------------------------------------------------------
+void Engine::release_collapse() {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (ctx_)
+        for (ns_dockeys* t : collapse_.dev)
+            if (t) (void)ns_dockeys_release(ctx_, t);
+    collapse_ = CollapseSet{};
+}
+
+size_t Engine::collapse_tables_on_device() const {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    size_t n = 0;
+    for (const ns_dockeys* t : collapse_.dev) n += t != nullptr;
+    return n;
+}
+
+bool Engine::collapse_table(const nsx::CollapseSpec& spec, std::vector<std::vector<uint32_t>>& tables) {
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    tables.clear();
+    if (!nsx::collapse_check(spec, err_)) return false;
+    const size_t S = segments.size();
+    if (spec.kind == nsx::CollapseSpec::Custom) {
+        std::vector<uint32_t> n_docs(S);
+        for (size_t s = 0; s < S; s++) n_docs[s] = segments[s].N;
+        if (!nsx::collapse_custom_check(spec, n_docs, err_)) return false;
+        tables = spec.custom;
+        return true;
+    }
+    nsx::CollapseIds ids;
+    tables.resize(S);
+    for (uint32_t s = 0; s < S; s++) {
+        tables[s].resize(segments[s].N);
+        for (uint32_t d = 0; d < segments[s].N; d++) {
+            const nsx::MetaFields* md = meta.get(s, d);   // nullptr: no metadata row = no key
+            tables[s][d] = md ? ids.key_of(spec.kind == nsx::CollapseSpec::Title ? md->title : md->author) : 0u;
+        }
+    }
+    return true;
+}
+
+// the spec's keys on the host and, for every segment with a device copy, on the device; another spec takes the set's place
+bool Engine::ensure_collapse(const nsx::CollapseSpec& spec, CollapseSet*& out) {
+    if (collapse_.built && (collapse_.kind != (int)spec.kind || (spec.kind == nsx::CollapseSpec::Custom && collapse_.keys != spec.custom))) release_collapse();
+    if (!collapse_.built) {
+        CollapseSet fresh;
+        fresh.kind = (int)spec.kind;
+        if (!collapse_table(spec, fresh.keys)) return false;
+        fresh.dev.assign(segments.size(), nullptr);
+        for (uint32_t s = 0; s < segments.size(); s++) {
+            if (!dev_segs_[s]) continue;
+            const int rc = ns_dockeys_upload(ctx_, segments[s].N, fresh.keys[s].data(), &fresh.dev[s]);
+            if (rc != NS_OK) {
+                err_ = std::string("ns_dockeys_upload: ") + ns_last_error(ctx_);
+                for (ns_dockeys* t : fresh.dev) if (t) (void)ns_dockeys_release(ctx_, t);
+                return false;
+            }
+        }
+        fresh.built = true;
+        collapse_ = std::move(fresh);
+    }
+    out = &collapse_;
+    return true;
+}
+
+bool Engine::search_collapsed_batch_flat(const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec, uint32_t filter_handle, const QueryView* queries,
+                                         size_t Q, int k, ns_hit* hits, uint32_t* groups, uint32_t* others, uint32_t* nhits, uint64_t* found, uint8_t* usable,
+                                         float* device_ms) {
+    const char* fn = "search_collapsed_batch_flat";
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    if (device_ms) *device_ms = 0.0f;
+    if (Q && (!queries || !hits || !groups || !nhits || !found || !usable)) { err_ = std::string(fn) + ": null argument"; return false; }
+    CallPrep bp;
+    for (size_t q = 0; q < Q; q++) {   // (before the device is asked for: the text alone decides)
+        const std::string prefix = nsx::collapse_first_prefix(queries[q].p, queries[q].n, bp.scratch);
+        if (!prefix.empty()) { err_ = std::string(fn) + ": query " + std::to_string(q) + " holds the prefix term " + prefix + "*: prefix terms are not collapsed (DESIGN.md 5ac, left out)"; return false; }
+    }
+    if (!ctx_) { err_ = std::string(fn) + ": no device context: collapsed queries run on the device, there is no CPU path"; return false; }
+    if (!boolean_prepare(fn, filter_handle, bp)) return false;
+    CollapseSet* cs = nullptr;
+    if (!ensure_collapse(collapse_spec, cs)) { err_ = std::string(fn) + ": " + err_; return false; }
+    std::vector<ns_dockeys*> tabs;
+    for (const uint32_t s : bp.listed) tabs.push_back(cs->dev[s]);   // (a filter's copies keep the docIds)
+    if (boost_spec) {
+        BoostSet* bs = nullptr;
+        if (!ensure_boosts(*boost_spec, bs)) { err_ = std::string(fn) + ": " + err_; return false; }
+        for (const uint32_t s : bp.listed) bp.boosts.push_back(bs->dev[s]);
+    }
+    if (Q == 0) return true;
+    const size_t K = (size_t)std::max(1, std::min(k, 100));
+    const RankedOut out{K, hits, groups, nhits, found, nullptr, device_ms};   // (keys = groups: an empty index fills them with 0)
+    if (!ranked_batch(fn, bp, nullptr, Q, out,
+        [&](size_t a, size_t b) { return refs_range(fn, nsx::Dialect::Boosted, queries, a, b, usable, bp); },
+        [&](size_t a, size_t b, const ns_cursor*, float* ms) {
+            const int rc = ns_search_collapsed(ctx_, bp.qd.data(), (uint32_t)(b - a), bp.refs.data(), bp.roles.data(), bp.clauses.data(), bp.needs.data(),
+                                               (uint32_t)bp.refs.size(), (uint32_t)K, bp.ids.data(), bp.segs.data(), bp.boosts.empty() ? nullptr : bp.boosts.data(),
+                                               tabs.data(), (uint32_t)bp.ids.size(), hits + a * K, groups + a * K, others ? others + a * K : nullptr, nhits + a,
+                                               found + a, ms);
+            if (rc != NS_OK) { err_ = std::string("ns_search_collapsed: ") + ns_last_error(ctx_); return false; }
+            return true;
+        })) return false;
+    if (bp.ids.empty() && others) std::fill(others, others + Q * K, 0u);   // nothing on the device: ranked_batch filled the rest
+    return true;
+}
+
+bool Engine::search_collapsed_text(const std::string& query, int k, const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec, const nsx::DocFilter* f,
+                                   std::string& body) {
+    const char* name = "search_collapsed";
+    std::lock_guard<std::recursive_mutex> lock(mtx_);
+    {
+        std::vector<char> scratch;
+        const std::string prefix = nsx::collapse_first_prefix(query.data(), query.size(), scratch);
+        if (!prefix.empty()) { body = err_ = std::string(name) + ": the query holds the prefix term " + prefix + "*: prefix terms are not collapsed (DESIGN.md 5ac, left out)"; return false; }
+    }
+    if (!ctx_) { body = err_ = std::string(name) + ": no device context: this engine has no CPU scoring path"; return false; }
+    const int K = std::max(1, std::min(k, 100));
+    uint32_t handle = 0;
+    std::string head = "{\n";
+    if (f) {   // search_filtered's filter (cached, most recently used in front) and its "filter" member
+        std::string ignored;
+        if (!search_filtered_text(std::string(), K, *f, ignored)) { body = err_; return false; }
+        handle = filter_lru_.front().handle;
+        const size_t at = ignored.find("\n  },\n");
+        if (ignored.compare(0, 14, "{\n  \"filter\": ") != 0 || at == std::string::npos) { body = err_ = std::string(name) + ": the filtered body has no filter member"; return false; }
+        head = ignored.substr(0, at + 6);
+    }
+    const QueryView qv{query.data(), query.size()};
+    std::vector<ns_hit> hits((size_t)K);
+    std::vector<uint32_t> groups((size_t)K), others((size_t)K);
+    uint32_t nh = 0;
+    uint64_t fd = 0;
+    uint8_t us = 0;
+    if (!search_collapsed_batch_flat(collapse_spec, boost_spec, handle, &qv, 1, K, hits.data(), groups.data(), others.data(), &nh, &fd, &us, nullptr)) { body = err_; return false; }
+    SearchResult res;
+    res.query = query;
+    res.k = K;
+    res.segments = (int)segments.size();
+    res.has_found = us != 0;
+    res.found = fd;
+    if (res.has_found)
+        for (uint32_t i = 0; i < nh; i++) res.hits.push_back(SearchHit{hits[i].score, hits[i].seg_id, hits[i].doc_id});
+    std::string tail = to_json_impl(res).substr(2);
+    // "others" behind every result's "docId" line ("cord_uid" < "docId" < "others" < "publish_time"; strings are escaped, so no
+    // other line of the body starts like that one)
+    size_t at = 0;
+    for (size_t i = 0; i < res.hits.size(); i++) {
+        const std::string line = "      \"docId\": " + std::to_string(res.hits[i].doc) + ",\n";
+        at = tail.find(line, at);
+        if (at == std::string::npos) { body = err_ = std::string(name) + ": the search body has no docId member"; return false; }
+        at += line.size();
+        const std::string more = "      \"others\": " + std::to_string(others[i]) + ",\n";
+        tail.insert(at, more);
+        at += more.size();
+    }
+    uint32_t min_should = 0;
+    const std::vector<nsx::BoostedTerm> terms = nsx::parse_boosted(query, &min_should);
+    std::string members = boost_spec ? boost_member(*boost_spec) : std::string();
+    members += std::string("  \"collapse\": {\n    \"field\": \"") + nsx::collapse_name(collapse_spec) + "\"\n  },\n";
+    members += boosted_member_of("collapsed", terms, min_should);
+    head.insert(2, members);   // "boost" < "collapse" < "collapsed" < "filter"
+    body = head + tail;
+    return true;
+}
+
+std::string Engine::search_collapsed(const std::string& query, int k, const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec, const nsx::DocFilter* f) {
+    std::string body;
+    return search_collapsed_text(query, k, collapse_spec, boost_spec, f, body) ? body : error_body(body);
 }
 
 bool Engine::search_boosted_after_batch_flat(const nsx::BoostSpec* spec, uint32_t filter_handle, const QueryView* queries, size_t Q, int k, const nsx::PageCursor* after,

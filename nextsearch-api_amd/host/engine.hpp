@@ -43,6 +43,7 @@
 #include "grouped.hpp"
 #include "quorum.hpp"
 #include "boost.hpp"
+#include "collapse.hpp"
 #include "prefix.hpp"
 #include "page.hpp"
 #include "suggest.hpp"
@@ -469,6 +470,30 @@ public:
     void release_boosts();
     size_t boost_tables_on_device() const;   // factor tables with a device copy right now
 
+    // Collapsed hits (host/collapse.hpp, csrc/ns_boolean.hip k_bq_select<false, ., ., ., true>, csrc/ns_collapse.hip):
+    // the boosted ranked call with one hit per group of documents.  A group is the documents that share a collapse key: the
+    // normalised title, the author field, or the caller's keys; a document without one stands alone.  Groups rank by their best
+    // member, the hit IS that member (score, segment, docId as search_boosted reports it), and others[] says how many more
+    // matched documents carry its key.  collapse_table: the spec's keys per segment in manifest order; host only (works on a
+    // host-only engine); false, with a message, for custom keys that do not fit the index or hold 0xFFFFFFFF.
+    // search_collapsed_batch_flat reads nsx::parse_boosted's dialect; boost_spec may be nullptr; hits name manifest positions;
+    // groups and others are Q x K like hits (others may be nullptr: the count pass is skipped).  There is no cursor and no page
+    // mode (§5ac, left out), and a `*` prefix term is refused with a message.  The device copies of the keys are built by the
+    // first call that needs them (never by reload()), one set at a time (another spec takes its place), serve the filtered copies
+    // unchanged, and are freed by reload(), release_collapse() and the destructor.
+    bool collapse_table(const nsx::CollapseSpec& spec, std::vector<std::vector<uint32_t>>& tables);
+    bool search_collapsed_batch_flat(const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec, uint32_t filter_handle, const QueryView* queries,
+                                     size_t Q, int k, ns_hit* hits, uint32_t* groups, uint32_t* others, uint32_t* nhits, uint64_t* found, uint8_t* usable,
+                                     float* device_ms = nullptr);
+    // JSON text: search_boosted's body with "collapsed" in place of "boosted", "collapse": {"field": "title" | "author" | "custom"}
+    // in front of it, and "others": n in every result.  Any failure: {"error": ...} (search_collapsed_text: false, body = the message).
+    std::string search_collapsed(const std::string& query, int k, const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec = nullptr,
+                                 const nsx::DocFilter* f = nullptr);
+    bool search_collapsed_text(const std::string& query, int k, const nsx::CollapseSpec& collapse_spec, const nsx::BoostSpec* boost_spec, const nsx::DocFilter* f,
+                               std::string& body);
+    void release_collapse();
+    size_t collapse_tables_on_device() const;   // key tables with a device copy right now
+
     // Prefix terms (host/prefix.hpp, csrc/ns_union.hip behind ns_segment_union): `vaccin*` in the Boosted dialect.
     // expand_prefix: the terms of suggest_table that begin with `prefix` (lower-case alnum bytes; a term equal to it included),
     // in byte order; more than max_expansions (1 .. 65535): those with the largest score, then the smallest bytes, are kept
@@ -710,6 +735,15 @@ private:
     };
     BoostSet boosts_;
     bool ensure_boosts(const nsx::BoostSpec& spec, BoostSet*& out);
+    // collapse keys: the last spec's host keys and their device copies (nullptr: the segment has none)
+    struct CollapseSet {
+        bool built = false;
+        int kind = 0;
+        std::vector<std::vector<uint32_t>> keys;
+        std::vector<ns_dockeys*> dev;
+    };
+    CollapseSet collapse_;
+    bool ensure_collapse(const nsx::CollapseSpec& spec, CollapseSet*& out);
     mutable std::string err_;
 };
 

@@ -1490,6 +1490,83 @@ extern "C" int nsh_engine_search_boosted_json(nsh_engine* e, const char* query, 
 } NSH_CATCH(e, "nsh_engine_search_boosted_json", -1)
 }
 
+// ---- collapsed hits (host/collapse.hpp) ----
+static bool nsh_collapse_spec_of(nsh_engine* e, const nsh_collapse_spec* in, nsx::CollapseSpec& out, std::string& why) {
+    if (!in) { why = "collapse: spec is NULL"; return false; }
+    if (in->kind > 2u) { why = "collapse: unknown kind " + std::to_string(in->kind); return false; }
+    out.kind = (nsx::CollapseSpec::Kind)in->kind;
+    if (out.kind != nsx::CollapseSpec::Custom) return true;
+    if (in->n_custom && !in->custom) { why = "collapse custom: null array"; return false; }
+    // whole arrays as far as the keys reach; keys left over become one more: the engine refuses either with a message
+    uint64_t at = 0;
+    for (const auto& sd : e->eng.segments) {
+        if (at + sd.N > in->n_custom) break;
+        out.custom.emplace_back(in->custom + at, in->custom + at + sd.N);
+        at += sd.N;
+    }
+    if (out.custom.size() == e->eng.segments.size() && at != in->n_custom) out.custom.emplace_back(in->custom + at, in->custom + in->n_custom);
+    return true;
+}
+
+extern "C" int64_t nsh_engine_collapse_table(nsh_engine* e, const nsh_collapse_spec* spec, uint32_t* out, uint64_t cap) { try {
+    if (!e) return -1;
+    nsx::CollapseSpec sp;
+    std::string why;
+    if (!nsh_collapse_spec_of(e, spec, sp, why)) { nsh_set_err(e, why); return -1; }
+    std::vector<std::vector<uint32_t>> tables;
+    if (!e->eng.collapse_table(sp, tables)) { nsh_set_err(e, e->eng.last_error()); return -1; }
+    uint64_t at = 0;
+    for (const auto& t : tables) {
+        for (size_t i = 0; i < t.size(); i++)
+            if (out && at + i < cap) out[at + i] = t[i];
+        at += t.size();
+    }
+    return (int64_t)at;
+} NSH_CATCH(e, "nsh_engine_collapse_table", -1)
+}
+
+extern "C" void nsh_engine_release_collapse(nsh_engine* e) { try { if (e) e->eng.release_collapse(); } NSH_CATCH_VOID(e, "nsh_engine_release_collapse") }
+extern "C" uint64_t nsh_engine_collapse_tables_on_device(nsh_engine* e) { return e ? (uint64_t)e->eng.collapse_tables_on_device() : 0; }
+
+extern "C" int nsh_engine_search_collapsed_batch(nsh_engine* e, const nsh_collapse_spec* collapse, const nsh_boost_spec* boost, uint32_t filter_handle,
+                                                 const char* const* queries, uint32_t n_queries, int k, void* hits, uint32_t* groups, uint32_t* others,
+                                                 uint32_t* nhits, uint64_t* found, uint8_t* has_found, float* device_ms_out) { try {
+    if (!e) return -1;
+    nsx::CollapseSpec cs;
+    nsx::BoostSpec bs;
+    std::string why;
+    bool have = false;
+    if (!nsh_collapse_spec_of(e, collapse, cs, why) || !nsh_boost_spec_of(e, boost, bs, have, why)) { nsh_set_err(e, why); return -1; }
+    if (n_queries && (!queries || !hits || !groups || !nhits)) { nsh_set_err(e, "nsh_engine_search_collapsed_batch: null argument"); return -1; }
+    std::vector<nextsearch::Engine::QueryView> views(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) views[q] = {queries[q] ? queries[q] : "", queries[q] ? std::strlen(queries[q]) : 0};
+    std::vector<uint64_t> f_;
+    std::vector<uint8_t> u_;
+    if (!found) { f_.resize(n_queries); found = f_.data(); }
+    if (!has_found) { u_.resize(n_queries); has_found = u_.data(); }
+    if (!e->eng.search_collapsed_batch_flat(cs, have ? &bs : nullptr, filter_handle, views.data(), n_queries, k, (ns_hit*)hits, groups, others, nhits, found, has_found,
+                                            device_ms_out)) {
+        nsh_set_err(e, e->eng.last_error());
+        return -1;
+    }
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (!has_found[q]) found[q] = 0;
+    return 0;
+} NSH_CATCH(e, "nsh_engine_search_collapsed_batch", -1)
+}
+
+extern "C" int nsh_engine_search_collapsed_json(nsh_engine* e, const char* query, int k, const nsh_collapse_spec* collapse, const nsh_boost_spec* boost,
+                                                int use_filter, const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
+    return nsh_text_json(e, use_filter, date_from, date_to, keep_undated, json_out, [&](const nsx::DocFilter* f, std::string& s) {
+        nsx::CollapseSpec cs;
+        nsx::BoostSpec bs;
+        bool have = false;
+        return nsh_collapse_spec_of(e, collapse, cs, s) && nsh_boost_spec_of(e, boost, bs, have, s) &&
+               e->eng.search_collapsed_text(query ? query : "", k, cs, have ? &bs : nullptr, f, s);
+    });
+} NSH_CATCH(e, "nsh_engine_search_collapsed_json", -1)
+}
+
 extern "C" int nsh_engine_search_boosted_page_json(nsh_engine* e, const char* query, int k, const char* cursor, const nsh_boost_spec* spec, int use_filter,
                                                    const char* date_from, const char* date_to, int keep_undated, char** json_out) { try {
     if (!e || !json_out) return -1;

@@ -39,6 +39,9 @@
 //   ns_tool search-boosted <index_dir> <none|exponential|linear> <weight> <scale_days> <offset_days> <origin|-> <from> <to> <k> <query words ...>   (needs an MI355X; `+(a b)^0.5 c^2.5`)
 //        Engine::search_boosted: search-quorum's body with "boosted" in place of "quorum" and, unless the decay is none, "boost";
 //        relevance times a recency factor per document (host/boost.hpp); undated documents keep their score.
+//   ns_tool search-collapsed <index_dir> <title|author> <from> <to> <k> <query words ...>   (needs an MI355X)
+//        Engine::search_collapsed: search-boosted's body (decay none) with one hit per title or author, "collapsed" in place of
+//        "boosted", "collapse": {"field"} and "others": n in every result.  from / to as search-filtered's.
 //   ns_tool page <index_dir> <or|and|boolean|newest|oldest|boolean-newest|boolean-oldest|grouped|grouped-newest|grouped-oldest|quorum|quorum-newest|quorum-oldest> <from> <to> <k> <cursor|-> <query words ...>   (needs an MI355X)
 //        Engine::search_page: one page of that mode's result, its JSON body plus "page": {"cursor", "next", "offset",
 //        "remaining"} (page.hpp).  cursor: "-" for the first page, else a page's "next".  from / to as search-filtered's.
@@ -180,6 +183,25 @@ int main(int argc, char** argv) {
         std::string q, body;
         for (int i = 11; i < argc; i++) { if (i > 11) q.push_back(' '); q += argv[i]; }
         if (!eng.search_boosted_text(q, k, boosted ? &spec : nullptr, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-boosted failed: %s\n", body.c_str()); return 1; }
+        std::printf("%s\n", body.c_str());
+        return 0;
+    }
+    if (argc >= 8 && std::strcmp(argv[1], "search-collapsed") == 0) {
+        nsx::CollapseSpec spec;
+        if (std::strcmp(argv[3], "title") == 0) spec.kind = nsx::CollapseSpec::Title;
+        else if (std::strcmp(argv[3], "author") == 0) spec.kind = nsx::CollapseSpec::Author;
+        else { std::fprintf(stderr, "search-collapsed: the field is title or author, not %s\n", argv[3]); return 2; }
+        nextsearch::Engine eng(0);
+        eng.index_dir = argv[2];
+        if (!eng.reload()) { std::fprintf(stderr, "reload failed: %s\n", eng.last_error().c_str()); return 1; }
+        nsx::DocFilter f;
+        const bool filtered = std::strcmp(argv[4], "-") != 0 || std::strcmp(argv[5], "-") != 0;
+        if (std::strcmp(argv[4], "-") != 0) f.date_from = argv[4];
+        if (std::strcmp(argv[5], "-") != 0) f.date_to = argv[5];
+        const int k = std::atoi(argv[6]);
+        std::string q, body;
+        for (int i = 7; i < argc; i++) { if (i > 7) q.push_back(' '); q += argv[i]; }
+        if (!eng.search_collapsed_text(q, k, spec, nullptr, filtered ? &f : nullptr, body)) { std::fprintf(stderr, "search-collapsed failed: %s\n", body.c_str()); return 1; }
         std::printf("%s\n", body.c_str());
         return 0;
     }

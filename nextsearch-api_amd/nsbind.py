@@ -68,6 +68,7 @@ HIP_SYMBOLS = [
     "ns_search_grouped_after", "ns_facet_count_grouped", "ns_search_sorted_grouped", "ns_grouped_kernel_ms",
     "ns_search_quorum_after", "ns_facet_count_quorum", "ns_search_sorted_quorum", "ns_quorum_kernel_ms",
     "ns_docboost_upload", "ns_docboost_release", "ns_search_boosted_after", "ns_boosted_kernel_ms",
+    "ns_search_collapsed", "ns_collapsed_kernel_ms",
     "ns_segment_filter", "ns_segment_union", "ns_ctx_union_scratch",
     "ns_ctx_create", "ns_ctx_destroy", "ns_ctx_set_stream", "ns_last_error", "ns_device_name",
     "ns_segment_upload", "ns_segment_release", "ns_segment_upload_begin", "ns_segment_upload_append", "ns_segment_upload_end", "ns_search_batch", "ns_batch_prepare",
@@ -92,6 +93,8 @@ HOST_SYMBOLS = [
     "nsh_engine_search_quorum_json", "nsh_engine_search_quorum_faceted_json", "nsh_engine_search_quorum_sorted_json",
     "nsh_engine_boost_table", "nsh_engine_release_boosts", "nsh_engine_boost_tables_on_device", "nsh_parse_boosted", "nsh_engine_search_boosted_after_batch",
     "nsh_engine_search_boosted_json", "nsh_engine_search_boosted_page_json",
+    "nsh_engine_collapse_table", "nsh_engine_release_collapse", "nsh_engine_collapse_tables_on_device", "nsh_engine_search_collapsed_batch",
+    "nsh_engine_search_collapsed_json",
     "nsh_parse_prefixed", "nsh_engine_expand_prefix", "nsh_engine_search_prefixed_after_batch", "nsh_engine_search_prefixed_json", "nsh_engine_search_prefixed_page_json",
     "nsh_engine_facet_boolean_batch", "nsh_engine_search_boolean_sorted_batch", "nsh_engine_search_boolean_faceted_json", "nsh_engine_search_boolean_sorted_json",
     "nsh_engine_sort_keys", "nsh_engine_search_sorted_batch", "nsh_engine_search_sorted_json", "nsh_engine_release_sorted", "nsh_engine_sort_tables_on_device",
@@ -177,6 +180,13 @@ class NshBoostSpec(C.Structure):   # include/nextsearch_host.h nsh_boost_spec
 
 
 BOOST_KINDS = {"custom": 0, "exponential": 1, "linear": 2}
+
+
+class NshCollapseSpec(C.Structure):   # include/nextsearch_host.h nsh_collapse_spec
+    _fields_ = [("kind", C.c_uint32), ("custom", C.c_void_p), ("n_custom", C.c_uint64)]
+
+
+COLLAPSE_KINDS = {"title": 0, "author": 1, "custom": 2}
 
 _hip = None
 _host = None
@@ -305,6 +315,9 @@ def hip_lib():
             L.ns_docboost_release.argtypes = [vp, vp]
             L.ns_search_boosted_after.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(C.c_float)]
             L.ns_boosted_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
+        if hasattr(L, "ns_search_collapsed"):       # (likewise: a library from before the collapsed call)
+            L.ns_search_collapsed.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+            L.ns_collapsed_kernel_ms.argtypes = [C.POINTER(C.c_float), i32]
         for name in DEBUG_COUNTERS:   # the counting build (make count) exports them; the product library does not
             if hasattr(L, name):
                 getattr(L, name).argtypes = [C.POINTER(u64), i32]
@@ -318,7 +331,7 @@ DEBUG_COUNTERS = {"ns_debug_counters": 32, "ns_debug_tile_counters": 12, "ns_deb
                   "ns_debug_boolean_counters": 8, "ns_debug_after_counters": 5, "ns_debug_fuzzy_counters": 17,
                   "ns_debug_boolean_sets_counters": 12, "ns_debug_boolean_groups_counters": 11,
                   "ns_debug_boolean_quorum_counters": 12, "ns_debug_boolean_boost_counters": 8,
-                  "ns_debug_terms_counters": 8}
+                  "ns_debug_terms_counters": 8, "ns_debug_collapse_counters": 14}
 
 
 def debug_counters(reset=False):
@@ -526,6 +539,16 @@ def host_lib():
             L.nsh_parse_boosted.restype = u32
             L.nsh_engine_search_boosted_after_batch.argtypes = [vp, bsp] + L.nsh_engine_search_boolean_after_batch.argtypes[1:]
             L.nsh_engine_search_boosted_json.argtypes = [vp, C.c_char_p, i32, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+            if hasattr(L, "nsh_engine_collapse_table"):   # (likewise: a host library from before the collapsed call)
+                csp = C.POINTER(NshCollapseSpec)
+                L.nsh_engine_collapse_table.argtypes = [vp, csp, vp, C.c_uint64]
+                L.nsh_engine_collapse_table.restype = C.c_int64
+                L.nsh_engine_release_collapse.argtypes = [vp]
+                L.nsh_engine_release_collapse.restype = None
+                L.nsh_engine_collapse_tables_on_device.argtypes = [vp]
+                L.nsh_engine_collapse_tables_on_device.restype = C.c_uint64
+                L.nsh_engine_search_collapsed_batch.argtypes = [vp, csp, bsp, u32, vp, u32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+                L.nsh_engine_search_collapsed_json.argtypes = [vp, C.c_char_p, i32, csp, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
             L.nsh_engine_search_boosted_page_json.argtypes = [vp, C.c_char_p, i32, C.c_char_p, bsp, i32, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
         if hasattr(L, "nsh_parse_prefixed"):   # (likewise: a host library from before the prefix terms)
             L.nsh_parse_prefixed.argtypes = [C.c_char_p, C.c_char_p, u32, vp, vp, vp, vp, vp, vp, u32, vp]
@@ -1260,6 +1283,66 @@ class Engine:
         df, dt, ku = date_filter if date_filter is not None else ("", "", False)
         return self._json_call("search_page", self._L.nsh_engine_search_prefixed_page_json, _as_bytes(query), k, _as_bytes(cursor), sp, int(max_expansions),
                                int(date_filter is not None), _as_bytes(df), _as_bytes(dt), int(bool(ku)), check=check)
+
+    # ---- collapsed hits: one hit per title, author or custom key ----
+    @staticmethod
+    def _collapse_spec(collapse):
+        """collapse: "title", "author", or a list of one uint32 key array per segment (custom) -> (pointer, what must stay alive)"""
+        sp = NshCollapseSpec()
+        keep = None
+        if isinstance(collapse, str):
+            sp.kind = COLLAPSE_KINDS[collapse]
+        else:
+            sp.kind = COLLAPSE_KINDS["custom"]
+            keep = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32) for c in collapse]) if len(collapse) else np.zeros(0, np.uint32))
+            sp.custom, sp.n_custom = (keep.ctypes.data if len(keep) else None), len(keep)
+        return C.byref(sp), (sp, keep)
+
+    def collapse_table(self, collapse):
+        """Engine::collapse_table (host only): [one uint32 key array per segment]"""
+        sp, keep = self._collapse_spec(collapse)
+        sizes = [self.segment_info(s)["n_docs"] for s in range(self.num_segments)]
+        flat = np.zeros(max(sum(sizes), 1), dtype=np.uint32)
+        n = self._L.nsh_engine_collapse_table(self.h, sp, flat.ctypes.data, len(flat))
+        if n < 0:
+            raise RuntimeError(f"collapse_table failed: {self.error()}")
+        out, at = [], 0
+        for m in sizes:
+            out.append(flat[at:at + m].copy())
+            at += m
+        return out
+
+    def search_collapsed_batch(self, queries, k, collapse="title", boost=None, handle=0, others=True, timing=False):
+        """Engine::search_collapsed_batch_flat: (hits Q x K, groups Q x K, others Q x K or None, nhits, found, has_found); one hit per
+        group of documents that share a collapse key, the group's best member; others: how many more matched documents carry it"""
+        cp, keep_c = self._collapse_spec(collapse)
+        bp, keep_b = self._boost_spec(boost)
+        Q, K = len(queries), min(max(int(k), 1), 100)
+        hits = np.zeros((max(Q, 1), K), dtype=HIT_DTYPE)
+        groups = np.zeros((max(Q, 1), K), dtype=np.uint32)
+        oth = np.zeros((max(Q, 1), K), dtype=np.uint32) if others else None
+        nhits, found, has = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint8)
+        ms = C.c_float()
+        rc = self._L.nsh_engine_search_collapsed_batch(self.h, cp, bp, int(handle), _cstr_array(queries), Q, int(k), hits.ctypes.data, groups.ctypes.data,
+                                                       None if oth is None else oth.ctypes.data, nhits.ctypes.data, found.ctypes.data, has.ctypes.data, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"search_collapsed_batch failed: {self.error()}")
+        out = (hits[:Q], groups[:Q], None if oth is None else oth[:Q], nhits[:Q], found[:Q], has[:Q])
+        return out + (float(ms.value),) if timing else out
+
+    def search_collapsed_json(self, query, k, collapse="title", boost=None, date_filter=None, check=True):
+        """Engine::search_collapsed: the JSON text; as search_boosted_json, with "collapsed", "collapse" and "others" in every result"""
+        cp, keep_c = self._collapse_spec(collapse)
+        bp, keep_b = self._boost_spec(boost)
+        df, dt, ku = date_filter if date_filter is not None else ("", "", False)
+        return self._json_call("search_collapsed", self._L.nsh_engine_search_collapsed_json, _as_bytes(query), k, cp, bp, int(date_filter is not None), _as_bytes(df),
+                               _as_bytes(dt), int(bool(ku)), check=check)
+
+    def release_collapse(self):
+        self._L.nsh_engine_release_collapse(self.h)
+
+    def collapse_tables_on_device(self):
+        return int(self._L.nsh_engine_collapse_tables_on_device(self.h))
 
     def release_boosts(self):
         self._L.nsh_engine_release_boosts(self.h)
@@ -2718,6 +2801,47 @@ def boosted_kernel_ms(reset=True):
     """(k_bq_select, k_bq_join) HIP-event ms summed over this thread's ns_search_boosted_after calls that were given tables"""
     out = (C.c_float * 2)()
     hip_lib().ns_boosted_kernel_ms(out, int(bool(reset)))
+    return [float(v) for v in out]
+
+
+def search_collapsed_raw(ctx, qd, refs, roles, clauses, needs, k, seg_ids, segs, boosts, groups, others=True):
+    """ns_search_collapsed (raw): (rc, hits Q x K, groups Q x K, others Q x K or None, nhits, found, device ms); groups: a list of
+    ns_dockeys handles, one per listed segment (an entry may be None), or None; boosts as in search_boosted_after_raw; others:
+    False passes others_out = NULL.  The outputs are pre-filled with 0xAB bytes."""
+    Q, K = len(qd), min(max(int(k), 1), 100)
+    ids = np.ascontiguousarray(seg_ids, dtype=np.uint32)
+    sa = (C.c_void_p * max(len(segs), 1))(*[s.value if isinstance(s, C.c_void_p) else s for s in segs])
+    ba = None if boosts is None else (C.c_void_p * max(len(boosts), 1))(*[b.value if isinstance(b, C.c_void_p) else b for b in boosts])
+    ga = None if groups is None else (C.c_void_p * max(len(groups), 1))(*[g.value if isinstance(g, C.c_void_p) else g for g in groups])
+    ro = None if roles is None else np.ascontiguousarray(roles, dtype=np.uint8)
+    cl, ne = _clauses(clauses), _needs(needs)
+    hits = np.full((max(Q, 1), K), 0xAB, dtype=np.uint8).repeat(12, axis=1).view(HIT_DTYPE)
+    gout = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32)
+    oout = np.full((max(Q, 1), K), 0xABABABAB, dtype=np.uint32) if others else None
+    nhits = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint32)
+    found = np.full(max(Q, 1), 0xABABABAB, dtype=np.uint64)
+    ms = C.c_float()
+    rc = hip_lib().ns_search_collapsed(ctx, qd.ctypes.data if Q else None, Q, _ptr(refs), _ptr(ro), _ptr(cl), _ptr(ne), len(refs), int(k), _ptr(ids), sa, ba, ga,
+                                       len(ids), hits.ctypes.data, gout.ctypes.data, None if oout is None else oout.ctypes.data, nhits.ctypes.data,
+                                       found.ctypes.data, C.byref(ms))
+    return rc, hits[:Q], gout[:Q], None if oout is None else oout[:Q], nhits[:Q], found[:Q], float(ms.value)
+
+
+COLLAPSE_EVENTS = ["rounds_skipped", "dropped_for_better", "replacements", "across_boundary", "fresh_insertions", "key0_candidates", "pairs_in_a_round",
+                   "wave_merge_duplicates", "join_duplicates_tiles", "join_duplicates_segments", "documents_counted", "count_items_skipped",
+                   "select_items", "count_items"]
+
+
+def collapse_counters(reset=True):
+    """ns_debug_collapse_counters of the counting build as {name: value}; None for a library without them"""
+    c = debug_counters(reset=reset).get("ns_debug_collapse_counters")
+    return None if c is None else dict(zip(COLLAPSE_EVENTS, c))
+
+
+def collapsed_kernel_ms(reset=True):
+    """(k_bq_select, k_bq_join_collapsed, k_cl_count) HIP-event ms summed over this thread's ns_search_collapsed calls"""
+    out = (C.c_float * 3)()
+    hip_lib().ns_collapsed_kernel_ms(out, int(bool(reset)))
     return [float(v) for v in out]
 
 
